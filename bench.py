@@ -1,7 +1,11 @@
 #!/usr/bin/env python
 """bench.py -- throughput of the CenterPose inference hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+
+K timed steps after W untimed ones; `ms_per_step` on the result line is the time of one timed step.  --dump-outputs DIR
+writes what the last timed step returned (the decoded records; for the default workload also the post-processed records
+and the poses) as DIR/<name>.npy; inputs and weights are seeded, so two builds can be compared output for output.
 
 N > 1: the driver launches this file under `python -m torch.distributed.run --nproc-per-node N ...` (one rank per GPU,
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment); when it is started directly with --gpus N > 1 and no
@@ -99,7 +103,15 @@ def parse():
     ap.add_argument("--dry-run", action="store_true",
                     help="plumbing rehearsal without a device: stub pipeline, real process group / barriers / all-gather "
                          "(tests/test_bench_cpu.py runs it with CP_BENCH_BACKEND=gloo, world size 2)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all), for output-by-output comparison of two builds")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload == "track_e2e":
+        ap.error("--dump-outputs: the track_e2e workload has no single step output (it times a host-in-the-loop video run)")
+    return args
 
 
 def respawn_under_torchrun(args):
@@ -222,7 +234,7 @@ class Pipeline(object):
             if stage is None:
                 stage = self._stages[n] = hip.PoseStage(n, det.shape[1], self.device, depth=2)
             post, cnt, poses, done = stage.submit(det, self.meta[:n], self.cam[:n], 0.3, nms=True, rep_mode=1)
-        self.last = (cnt, poses)
+        self.last = (post, cnt, poses)
         if self.gather:  # BASELINE configs[3]: every rank sees every image's detections
             return self.gather_timer(det), poses
         return det, poses
@@ -234,7 +246,7 @@ class Pipeline(object):
         n = None
         if self.last is not None:
             torch.cuda.synchronize()
-            n = int(self.last[0].sum().item())
+            n = int(self.last[1].sum().item())
         return ms, n
 
 
@@ -261,7 +273,8 @@ class DryPipeline(object):
 
 
 def timed_region(pipe, steps, warmup, barrier, profile=True):
-    """W untimed steps, then exactly `steps` timed ones between barriers; per-launch HIP events on every 4th step."""
+    """W untimed steps, then exactly `steps` timed ones between barriers; per-launch HIP events on every 4th step.  What the
+    last timed step returned is left in ``pipe.last_out`` (--dump-outputs)."""
     for _ in range(warmup):
         pipe.step()
     every = 4 if steps >= 8 else 1
@@ -275,9 +288,10 @@ def timed_region(pipe, steps, warmup, barrier, profile=True):
             on = i % every == 0
             pipe.model.profile(on)
             sampled += int(on)
-        pipe.step()
+        out = pipe.step()
     barrier()
     dt = time.perf_counter() - t0
+    pipe.last_out = out
     if not profile:
         return dt, {}, {}, 0
     pipe.model.profile(False)
@@ -876,14 +890,54 @@ def write_detail(d):
     """The full record of the run (per-kernel tables, notes, every leg's roofline object) beside the compact line."""
     path = os.environ.get("CP_BENCH_DETAIL")
     if not path:
+        # never a committed file: profiles/ holds the recorded runs, build/ is git-ignored
         scratch = os.path.join(REPO, "gpurun_out")
-        path = os.path.join(scratch if os.path.isdir(scratch) else os.path.join(REPO, "profiles"), "bench_detail_last.json")
+        path = os.path.join(scratch if os.path.isdir(scratch) else os.path.join(REPO, "build"), "bench_detail_last.json")
     try:
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
         with open(path, "w") as f:
             json.dump(d, f, indent=1)
         return os.path.relpath(path, REPO)
     except OSError:
         return None
+
+
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(pipe, path):
+    """--dump-outputs DIR: what the last timed step handed its caller, as DIR/<name>.npy.  Every workload: `detections`, the
+    decoded records [B, 100, 118] (all ranks' after the per-step all-gather when N > 1).  full: also the pose stage's results,
+    `counts` [B] and the first counts[b] rows of `post` [B, 100, 120] and `poses` [B, 100, 40]; the rows past the count are
+    not part of the result (reused buffers) and are written as zeros.  Integers are written as float64.  Should the whole
+    exceed DUMP_BYTES_MAX, every array keeps the same fixed, seeded sample of its leading-axis rows (`sample_rows.npy`)."""
+    import numpy as np
+
+    out = pipe.last_out
+    det = out[0] if isinstance(out, tuple) else out
+    arrays = {"detections": det}
+    last = getattr(pipe, "last", None)
+    if pipe.workload == "full" and last is not None:
+        post, cnt, poses = last
+        valid = torch.arange(post.shape[1], device=cnt.device).view(1, -1) < cnt.view(-1, 1).long()
+        arrays["counts"] = cnt
+        arrays["post"] = torch.where(valid.unsqueeze(-1), post, torch.zeros((), dtype=post.dtype, device=post.device))
+        arrays["poses"] = torch.where(valid.unsqueeze(-1), poses, torch.zeros((), dtype=poses.dtype, device=poses.device))
+    if torch.cuda.is_available() and det.is_cuda:
+        torch.cuda.synchronize()
+    arrays = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    arrays = {k: v if v.dtype in (np.float32, np.float64) else v.astype(np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_BYTES_MAX:
+        n = det.shape[0]
+        keep = max(1, int(n * DUMP_BYTES_MAX // total))
+        rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrays = {k: v[rows] for k, v in arrays.items()}
+        arrays["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(v))
+    return sorted(arrays)
 
 
 def main():
@@ -932,7 +986,7 @@ def main():
     if args.workload == "track_e2e":  # host-in-the-loop measurement, single GPU
         if world != 1:
             raise SystemExit("track_e2e is a single-process measurement")
-        leg = track_e2e_leg(device, args.precision, batch, max(args.steps, 4), max(args.warmup, 2))
+        leg = track_e2e_leg(device, args.precision, batch, args.steps, max(args.warmup, 2))
         leg.update({"metric": "frames/sec over %d concurrent videos (CenterPoseTrack loop incl. host tracker)" % batch,
                     "n_gpus": 1, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "data": "synthetic",
                     "dtype": "f32", "config": {"workload": leg["workload"]}})
@@ -951,6 +1005,9 @@ def main():
         side = torch.cuda.Stream(device=device)  # a non-default stream (hipGraph capture needs one)
         torch.cuda.set_stream(side)
     dt, prof, roles, sampled = timed_region(pipe, args.steps, args.warmup, barrier, profile=not dry)
+    dumped = None
+    if args.dump_outputs and rank == 0:  # before anything else runs on the pipeline's buffers
+        dumped = dump_outputs(pipe, args.dump_outputs)
     rccl_ranks = 1
     allgather = None
     if dist is not None:
@@ -1069,6 +1126,8 @@ def main():
         }
         line = compact_line(out)
         line["detail"] = write_detail(out)
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         print(json.dumps(line), flush=True)
     if dist is not None:
         barrier()  # rank 0 may still be measuring the batch-1 latency; leave together

@@ -1,6 +1,7 @@
 """ORACLE tooling (build container only): generate tests/golden/* from the REFERENCE itself.
 
-Run:  python -m oracle.tools.make_goldens
+Run:  python -m oracle.tools.make_goldens          (all fixtures)
+      python -m oracle.tools.make_goldens pins     (only those of pin_goldens)
 Every fixture below is an output of the reference's own code (imported from /root/reference via
 oracle/tools/ref_harness.py), on seeded inputs that the tests regenerate; the oracle restatements
 and the HIP path are both checked against them.
@@ -438,8 +439,54 @@ def main():
     render_goldens()
     tracker_goldens()
     opts_goldens()
+    pin_goldens()
     print("done ->", GOLD)
 
 
+PIN_DECODE_SEED = 4242
+
+
+def im2col_pin_case():
+    """The out-of-image-heavy im2col case of tests/test_oracle_pins.py (offsets x3: many samples fall outside)."""
+    x, w, b, off, mask = dcn_case(seed=9, B=1, C=8, Co=4, H=9, W=7)
+    return x, off * 3, mask
+
+
+def backbone_pin_case():
+    """dlav1_34 on its own seeded weights and a non-square 96x64 frame (tests/test_oracle_pins.py)."""
+    return synth.make_state_dict("dlav1_34", seed=5), synth.frames(1, seed=6, h=96, w=64)
+
+
+def pin_goldens():
+    """The reference's outputs on the inputs tests/test_oracle_pins.py pins the oracle with, bit for bit:
+      im2col_ref.npz            the reference's compiled CPU im2col (oracle/_ref) on im2col_pin_case ("pin") and on every
+                                DCN_GENERIC_SHAPES case ("g<i>")
+      decode_pose_pin.npz       reference ``object_pose_decode`` on synth_heads(1, PIN_DECODE_SEED), "<semantics>/<key>"
+      backbone_dlav1_pin.npz    reference ``model(x)[-1]`` on backbone_pin_case"""
+    cols = {}
+    x, off, mask = im2col_pin_case()
+    cols["pin"] = odcn.im2col(x, off, mask, 3, 3, 1, 1, 1, 1, 1, 1, 1, kind="reference")[0].numpy()
+    for i in range(len(DCN_GENERIC_SHAPES)):
+        gx, _, _, goff, gmask, (kh, kw, sh, sw, ph, pw, dh, dw, dg) = dcn_generic_case(i)
+        cols["g%d" % i] = odcn.im2col(gx, goff, gmask, kh, kw, ph, pw, sh, sw, dh, dw, dg, kind="reference")[0].numpy()
+    np.savez_compressed(os.path.join(GOLD, "im2col_ref.npz"), **cols)
+    d = odec.synth_heads(1, seed=PIN_DECODE_SEED)
+    dec = {}
+    for sem in ("bool", "uint8"):
+        dec.update({"%s/%s" % (sem, k): v for k, v in reference_decode_run(d, False, sem).items()})
+    np.savez_compressed(os.path.join(GOLD, "decode_pose_pin.npz"), **dec)
+    sd, x = backbone_pin_case()
+    model = rh.create_reference_model("dlav1_34", synth.HEADS_POSE, False)
+    model.load_state_dict(sd, strict=True)
+    with torch.no_grad():
+        z = model(x, None, None, None)[-1]
+    np.savez_compressed(os.path.join(GOLD, "backbone_dlav1_pin.npz"), **{k: v.numpy() for k, v in z.items()})
+    print("pins: im2col", len(cols), "decode", len(dec), "backbone", len(z))
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["pins"]:
+        odcn.build()
+        pin_goldens()
+    else:
+        main()

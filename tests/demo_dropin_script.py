@@ -1,10 +1,10 @@
-"""Run in a fresh interpreter by tests/test_demo_dropin.py: the REFERENCE's src/demo.py, unmodified, with this repo's
-package in place of the reference's ``lib`` (INTEGRATION.md level 0: put centerpose_amd/ ahead of src/ on sys.path).
+"""Run in a fresh interpreter by tests/test_demo_dropin.py: a demo-style caller of this repo's package as a drop-in ``lib``
+(INTEGRATION.md level 0: put centerpose_amd/ ahead of the application's own directory on sys.path) -- `lib.opts`,
+`lib.detectors.detector_factory`, `Detector(opt).run(image_path, meta_inp=meta)` and the nine timing keys of its result.
 
-usage: python demo_dropin_script.py <reference src dir> <image> <checkpoint>
-Only what cannot exist on this GPU-less build box is substituted: cv2 (absent: imread through PIL, no windows) and the
-two device stages of ``process`` / PnP (the oracle's CPU forward, decode and PnP stand in for libcenterpose_hip.so)."""
-import importlib.util
+usage: python demo_dropin_script.py <image> <checkpoint>
+Only what cannot exist on a GPU-less machine is substituted: cv2 (if absent: imread through PIL, no windows) and the two
+device stages of ``process`` / PnP (the oracle's CPU forward, decode and PnP stand in for libcenterpose_hip.so)."""
 import os
 import sys
 import types
@@ -12,7 +12,7 @@ import types
 import numpy as np
 import torch
 
-ref_src, image, ckpt = sys.argv[1], sys.argv[2], sys.argv[3]
+image, ckpt = sys.argv[1], sys.argv[2]
 REPO = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "centerpose_amd"))   # `lib` now resolves to centerpose_amd/lib
@@ -29,15 +29,12 @@ except ImportError:
     cv2.VideoCapture = None
     sys.modules["cv2"] = cv2
 
-spec = importlib.util.spec_from_file_location("reference_demo", os.path.join(ref_src, "demo.py"))
-demo = importlib.util.module_from_spec(spec)
-spec.loader.exec_module(demo)                    # `from lib.opts import opts`, `from lib.detectors...` -> this repo
-import lib  # noqa: E402
+import lib  # noqa: E402  (this repo's package)
 
 assert os.path.realpath(os.path.dirname(lib.__file__)).startswith(os.path.realpath(REPO)), lib.__file__
 from lib.opts import opts  # noqa: E402
 
-# ---- what demo.py's __main__ block does (demo.py:88-155) ----
+# ---- the options a demo run sets (a chair, PnP on, the demo's camera) ----
 opt = opts().parser.parse_args(["--demo", image, "--arch", "dla_34", "--load_model", ckpt, "--gpus", "-1", "--c", "chair"])
 opt.nms = True
 opt.obj_scale = True
@@ -74,5 +71,13 @@ def process(self, images, pre_images=None, pre_hms=None, pre_hm_hp=None, pre_ind
 ObjectPoseDetector.process = process
 cps.solve_pnp_batch = _oracle_pnp_rows
 bd.solve_pnp_batch = _oracle_pnp_rows
-demo.demo(opt, meta)
+
+# ---- what a demo does per image: one run() on the file's path, then the timing line ----
+from lib.detectors.detector_factory import detector_factory  # noqa: E402
+
+TIME_STATS = ["tot", "load", "pre", "net", "dec", "post", "merge", "pnp", "track"]
+detector = detector_factory[opt.task](opt)
+ret = detector.run(image, meta_inp=meta)
+assert {"results", "boxes", "output"} <= set(ret), sorted(ret)
+print("Frame 0|" + "".join("%s %.3fs |" % (k, ret[k]) for k in TIME_STATS))
 print("DEMO_DROPIN_OK")

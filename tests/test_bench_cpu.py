@@ -41,6 +41,20 @@ def test_bench_single_rank_dry_run_has_no_group():
     assert d["n_gpus"] == 1 and d["rccl_ranks"] == 1 and d["config"]["global_batch"] == 64
 
 
+def test_bench_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: the records the last timed step returned, as .npy in float32 / float64; --steps is the number of
+    timed steps and `ms_per_step` one step's time."""
+    import numpy as np
+
+    out = tmp_path / "dump"
+    d = _run(["--dry-run", "--steps", "5", "--warmup", "1", "--dump-outputs", str(out)])
+    assert d["steps"] == 5 and d["ms_per_step"] > 0 and abs(d["value"] - 64 * 5 / (d["ms_per_step"] * 5e-3)) / d["value"] < 1e-3
+    assert d["dumped_outputs"] == ["detections"]
+    det = np.load(str(out / "detections.npy"))
+    assert det.dtype == np.float32 and det.shape == (64, 100, 118)
+    assert (det[:, :, 2] == np.arange(64, dtype=np.float32).reshape(64, 1)).all()   # the dry pipeline's image tags
+
+
 def test_bench_eight_ranks_dress_rehearsal():
     """BASELINE configs[3] plumbing without hardware: 8 ranks over gloo, 64 images each, one checked all-gather; the line
     carries a cpu_baseline stub for N > 1 so that a SCALE parser never finds the key missing."""
