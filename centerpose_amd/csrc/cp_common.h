@@ -347,6 +347,12 @@ int cp_launch_decode(hipStream_t s, int B, int J, int H, int W, float* hm, const
                      const float* hps_unc, const float* scale, const float* scale_unc, const float* reg, float* hm_hp,
                      const float* hp_offset, const float* tracking, const float* tracking_hp, int K, int rep_mode,
                      int fit_gaussian, float balance, int legacy_bool_mask, int apply_sigmoid, float* det, void* ws);
+// tiled peaks (any W % 4 == 0, W <= 4096, K <= H*W <= 2^20; decode.hip): 0 bytes = unsupported shape
+size_t cp_decode_tiled_ws_bytes(int B, int J, int H, int W, int K);
+int cp_launch_decode_tiled(hipStream_t s, int B, int J, int H, int W, float* hm, const float* hps, const float* wh,
+                           const float* hps_unc, const float* scale, const float* scale_unc, const float* reg, float* hm_hp,
+                           const float* hp_offset, const float* tracking, const float* tracking_hp, int K, int rep_mode,
+                           int fit_gaussian, float balance, int legacy_bool_mask, int apply_sigmoid, float* det, void* ws);
 
 // ---- generic DCNv2 forward on the reference's NCHW layouts (dcn_generic.hip): any C / kernel / stride / dilation / dg ----
 int cp_launch_dcn_generic(hipStream_t s, const float* x, const float* w, const float* bias, const float* offset,

@@ -12,6 +12,13 @@
 //                  scans the K candidates (float ops in the reference's order, no FMA contraction so
 //                  argmin / threshold decisions match the CPU bit for bit).
 //
+// Sizes.  cp_decode (peaks_kernel + assoc_kernel): K <= 128, W % 4 == 0, K <= H*W <= 32768 (the whole map in one
+// workgroup's LDS).  cp_decode_tiled (peaks_tile_kernel + peaks_merge_kernel + assoc_kernel, and sigmoid_maps_kernel
+// with apply_sigmoid): the same records bit for bit for K <= H*W <= 1048576 (a 4096 x 4096 network input), W % 4 == 0,
+// W <= 4096; the map is cut into bands of whole rows (<= 8192 pixels + two halo rows each), and each band's top K is merged
+// per map.  cp_model_detect takes the tiled path above 32768 output pixels (e.g. --keep_res 1280 x 720 -> 184 x 328,
+// Objectron's 1440 x 1920 portrait frames -> 488 x 368, --input_res 1024 -> 256 x 256).
+//
 // Output: det[B][K][118] float32 records (field offsets in cp_common.h / centerpose_hip.h).
 #include "cp_common.h"
 
@@ -480,6 +487,279 @@ __global__ __launch_bounds__(128) void assoc_kernel(const AssocParams p) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Tiled peaks: maps of any size up to TL_HWMAX pixels.  Stage A (peaks_tile_kernel, grid T x (J+1) x B) gives each
+// workgroup a band of R = TL_PIX / W whole rows plus one halo row above and below, computes peaks_kernel's NMS keys on
+// the band and writes the band's top min(K, band pixels) as 64-bit composites (key << 32 | ~pixel index), largest first,
+// padded with 0.  Stage B (peaks_merge_kernel, grid (J+1) x B) selects the exact top K of a map's T x K candidates and
+// writes pk_score / pk_ind as peaks_kernel does.  Exact: the global top K under the total order (key desc, index asc)
+// is a subset of the union of the bands' local top K.  Stage B keeps the candidates in band-major order, and the bands
+// are consecutive pixel ranges, so among equal keys candidate order IS pixel order: the tie rule needs no index sort.
+constexpr int TL_G = 2;                                   // groups of four pixels per lane in a band
+constexpr int TL_PIX = PK_THREADS * TL_G * 4;             // 8192 pixels per band at most (128 x 128 -> 2 bands)
+constexpr int TL_WMAX = 4096;                             // a band holds at least two whole rows
+constexpr int TL_HWMAX = 1 << 20;                         // 1024 x 1024 output grid = 4096 x 4096 input
+constexpr int TL_NL = (TL_PIX + 2 * TL_WMAX) / (4 * PK_THREADS);  // 16-byte loads per lane: band + halos
+constexpr int TL_MERGE_CAP = 16 * PK_THREADS * 2;         // candidates per map stage B holds (>= 256 bands x 128)
+
+typedef uint32_t tl_u32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t tl_rsrc(const void* p, unsigned bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
+}
+
+struct SelectSmem {
+    unsigned long long list[128], sorted[128];
+    int hist[256];
+    int scan_sh[34];
+    int sel[2];  // digit, need
+    int cnt;
+};
+
+// peaks_kernel's selection restated over G x E keys per lane (E = 4 pixels of a band, or 2 candidates of a merge): exact
+// top K (key desc, then lower linear position (g, lane, e) first) into sm.sorted[0 .. K), composites (key << 32 | lo(g, e)),
+// largest first, zeros behind.  Key 0 marks an empty slot; at least K keys must be non-zero.
+template <int G, int E, typename LoFn>
+__device__ __forceinline__ void select_top(SelectSmem& sm, const uint32_t (&key)[G * E], LoFn lo, int K) {
+    const int tid = threadIdx.x;
+    int n_pos = 0, n_zero = 0;
+#pragma unroll
+    for (int i = 0; i < G * E; ++i) {
+        n_pos += key[i] > ZKEY ? 1 : 0;
+        n_zero += key[i] == ZKEY ? 1 : 0;
+    }
+    int tot_pos, tot_zero;
+    block_sum2(n_pos, n_zero, sm.scan_sh, &tot_pos, &tot_zero);
+
+    uint32_t prefix = 0u;
+    int need = K;
+    if (tot_pos < K && tot_pos + tot_zero >= K) {
+        prefix = ZKEY;
+        need = K - tot_pos;
+    } else {
+        const uint32_t floor_excl = tot_pos >= K ? ZKEY : 0u;
+        uint32_t maskb = 0u;
+        for (int pass = 3; pass >= 0; --pass) {
+            const int shift = pass * 8;
+            if (tid < 256) sm.hist[tid] = 0;
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < G * E; ++i)
+                if (key[i] > floor_excl && (key[i] & maskb) == prefix) atomicAdd(&sm.hist[(key[i] >> shift) & 255u], 1);
+            __syncthreads();
+            if (tid < 64) {
+                const int h0 = sm.hist[4 * tid], h1 = sm.hist[4 * tid + 1], h2 = sm.hist[4 * tid + 2], h3 = sm.hist[4 * tid + 3];
+                const int s = h0 + h1 + h2 + h3;
+                int suf = s;
+#pragma unroll
+                for (int o = 1; o < 64; o <<= 1) {
+                    const int y = __shfl_down(suf, o, 64);
+                    if (tid + o < 64) suf += y;
+                }
+                const int above = suf - s;
+                if (above < need && need <= suf) {
+                    int c = above, d = 4 * tid + 3;
+                    const int hh[4] = {h0, h1, h2, h3};
+                    for (int q = 3; q >= 0; --q) {
+                        if (c + hh[q] >= need) { d = 4 * tid + q; break; }
+                        c += hh[q];
+                    }
+                    sm.sel[0] = d;
+                    sm.sel[1] = need - c;
+                }
+            }
+            __syncthreads();
+            prefix |= ((uint32_t)sm.sel[0]) << shift;
+            maskb |= 0xffu << shift;
+            need = sm.sel[1];
+            __syncthreads();
+        }
+    }
+    int my_eq = 0, dummy = 0;
+#pragma unroll
+    for (int i = 0; i < G * E; ++i) my_eq += (key[i] == prefix) ? 1 : 0;
+    int total_eq;
+    block_sum2(my_eq, 0, sm.scan_sh, &total_eq, &dummy);
+    if (tid == 0) sm.cnt = 0;
+    if (tid < 128) sm.list[tid] = sm.sorted[tid] = 0ull;
+    __syncthreads();
+    const bool all_eq = total_eq <= need;
+    int taken_before = 0;
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        int rank = 0;
+        if (!all_eq) {
+            int c = 0;
+#pragma unroll
+            for (int e = 0; e < E; ++e) c += key[g * E + e] == prefix ? 1 : 0;
+            int tot_g;
+            rank = taken_before + block_excl_scan(c, sm.scan_sh, &tot_g);
+            taken_before += tot_g;
+        }
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            const uint32_t k = key[g * E + e];
+            bool take = k > prefix;
+            if (k == prefix) {
+                take = all_eq || rank < need;
+                ++rank;
+            }
+            if (take && k != 0u) {
+                const int slot = atomicAdd(&sm.cnt, 1);
+                if (slot < 128) sm.list[slot] = ((unsigned long long)k << 32) | (unsigned long long)lo(g, e);
+            }
+        }
+    }
+    __syncthreads();
+    if (tid < 128) {
+        const unsigned long long mine = sm.list[tid];
+        int rank = 0;
+#pragma unroll 16
+        for (int j = 0; j < 128; ++j) rank += sm.list[j] > mine ? 1 : 0;
+        sm.sorted[mine ? rank : 127] = mine;
+    }
+    __syncthreads();
+}
+
+// Stage A.  Band t of map (mi, b): rows [t R, t R + R) and the halo rows above and below, one contiguous range of the map
+// read with branch-free 16-byte buffer loads (every lane issues TL_NL of them, the ones past the range return 0 and are
+// not stored) into LDS.  With apply_sigmoid the band and halo values are sigmoided in registers with peaks_kernel's
+// expression and NOT written back here: a neighbouring band still reads these rows as its halo (sigmoid_maps_kernel
+// writes them after every band has read).  cand[b][mi][NS]: band t's K composites at t K; a pad slot at T K when T K is odd.
+__global__ __launch_bounds__(PK_THREADS) void peaks_tile_kernel(const float* __restrict__ hm, const float* __restrict__ hm_hp,
+                                                                int J, int H, int W, int K, int R, int NS, int apply_sigmoid,
+                                                                unsigned long long* __restrict__ cand) {
+    const int t = blockIdx.x, mi = blockIdx.y, b = blockIdx.z, T = gridDim.x, NM = J + 1;
+    const int HW = H * W;
+    const float* map = (mi == 0) ? hm + (size_t)b * HW : hm_hp + ((size_t)b * J + (mi - 1)) * HW;
+    const int row0 = t * R, rows = min(R, H - row0), ra = max(row0 - 1, 0), rb = min(row0 + R + 1, H);
+    const int n_reg = (rb - ra) * W;  // floats in the staged range, a multiple of 4
+    __shared__ __attribute__((aligned(16))) float smap[TL_PIX + 2 * TL_WMAX];
+    __shared__ SelectSmem sm;
+    const int tid = threadIdx.x;
+
+    const __amdgpu_buffer_rsrc_t rs = tl_rsrc(map + (size_t)ra * W, (unsigned)n_reg * 4u);
+    tl_u32x4 q[TL_NL];
+#pragma unroll
+    for (int i = 0; i < TL_NL; ++i) q[i] = __builtin_amdgcn_raw_buffer_load_b128(rs, (i * PK_THREADS + tid) * 16, 0, 0);
+#pragma unroll
+    for (int i = 0; i < TL_NL; ++i) {
+        float4 v = make_float4(__uint_as_float(q[i].x), __uint_as_float(q[i].y), __uint_as_float(q[i].z),
+                               __uint_as_float(q[i].w));
+        if (apply_sigmoid) {
+            v.x = 1.f / (1.f + expf(-v.x));
+            v.y = 1.f / (1.f + expf(-v.y));
+            v.z = 1.f / (1.f + expf(-v.z));
+            v.w = 1.f / (1.f + expf(-v.w));
+        }
+        const int i4 = i * PK_THREADS + tid;
+        if (4 * i4 < n_reg) reinterpret_cast<float4*>(smap)[i4] = v;
+    }
+    __syncthreads();
+
+    // ---- NMS keys of the band's pixels, exactly as peaks_kernel ----
+    const int nt4 = (rows * W) >> 2, off = (row0 - ra) * W;
+    uint32_t key[TL_G * 4];
+    const float NINF = -__builtin_huge_valf();
+#pragma unroll
+    for (int g = 0; g < TL_G; ++g) {
+        const int i4 = g * PK_THREADS + tid;
+        if (i4 < nt4) {
+            const int p = i4 << 2;
+            const int y = row0 + p / W, x0 = p - (p / W) * W;
+            const float4 vc = *reinterpret_cast<const float4*>(smap + off + p);
+            float m0 = NINF, m1 = NINF, m2 = NINF, m3 = NINF;
+#pragma unroll
+            for (int dy = -1; dy <= 1; ++dy) {
+                const int yy = y + dy;
+                if (yy < 0 || yy >= H) continue;
+                const int rbs = (yy - ra) * W + x0;
+                const float4 c = *reinterpret_cast<const float4*>(smap + rbs);
+                const float l = x0 > 0 ? smap[rbs - 1] : NINF, r = x0 + 4 < W ? smap[rbs + 4] : NINF;
+                m0 = fmaxf(m0, fmaxf(l, fmaxf(c.x, c.y)));
+                m1 = fmaxf(m1, fmaxf(c.x, fmaxf(c.y, c.z)));
+                m2 = fmaxf(m2, fmaxf(c.y, fmaxf(c.z, c.w)));
+                m3 = fmaxf(m3, fmaxf(c.z, fmaxf(c.w, r)));
+            }
+            const float vv[4] = {vc.x, vc.y, vc.z, vc.w}, mm[4] = {m0, m1, m2, m3};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float kept = (mm[e] == vv[e]) ? vv[e] : vv[e] * 0.0f;
+                uint32_t k = f2ord(kept + 0.0f);
+                if (k == 0u) k = 1u;
+                key[g * 4 + e] = k;
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) key[g * 4 + e] = 0u;
+        }
+    }
+    const uint32_t p0 = (uint32_t)(row0 * W);
+    select_top<TL_G, 4>(sm, key, [&](int g, int e) { return 0xffffffffu - (p0 + (uint32_t)(((g * PK_THREADS + tid) << 2) + e)); },
+                        min(K, rows * W));
+    unsigned long long* out = cand + ((size_t)b * NM + mi) * NS + (size_t)t * K;
+    if (tid < K) out[tid] = sm.sorted[tid];
+    if (t == T - 1 && tid == K && T * K < NS) out[K] = 0ull;
+}
+
+// Stage B.  Lane tid, group g holds candidates 2 (g * 1024 + tid) and + 1 (one 16-byte load per group, whole lines per
+// wave); slots past NS read 0 = empty.
+template <int G>
+__global__ __launch_bounds__(PK_THREADS) void peaks_merge_kernel(const unsigned long long* __restrict__ cand, int NS, int K,
+                                                                 float* __restrict__ pk_score, int* __restrict__ pk_ind) {
+    const int mi = blockIdx.x, b = blockIdx.y, nm = gridDim.x, tid = threadIdx.x;
+    __shared__ SelectSmem sm;
+    const __amdgpu_buffer_rsrc_t rs = tl_rsrc(cand + ((size_t)b * nm + mi) * NS, (unsigned)NS * 8u);
+    tl_u32x4 q[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) q[g] = __builtin_amdgcn_raw_buffer_load_b128(rs, (g * PK_THREADS + tid) * 16, 0, 0);
+    uint32_t key[G * 2], lo[G * 2];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        lo[2 * g] = q[g].x;
+        key[2 * g] = q[g].y;
+        lo[2 * g + 1] = q[g].z;
+        key[2 * g + 1] = q[g].w;
+    }
+    select_top<G, 2>(sm, key, [&](int g, int e) { return lo[g * 2 + e]; }, K);
+    if (tid < K) {
+        const unsigned long long e = sm.sorted[tid];
+        const size_t o = ((size_t)b * nm + mi) * K + tid;
+        pk_score[o] = ord2f((uint32_t)(e >> 32));
+        pk_ind[o] = (int)(0xffffffffu - (uint32_t)(e & 0xffffffffull));
+    }
+}
+
+// In-place sigmoid of hm / hm_hp for the tiled path, launched after peaks_tile_kernel (whose halo reads it must follow);
+// the expression is peaks_kernel's, so the maps and the keys see identical values.  grid (ceil(HW/4 / 256), J+1, B).
+__global__ __launch_bounds__(256) void sigmoid_maps_kernel(float* __restrict__ hm, float* __restrict__ hm_hp, int J, int HW) {
+    const int i4 = blockIdx.x * 256 + threadIdx.x, mi = blockIdx.y, b = blockIdx.z;
+    if (4 * i4 >= HW) return;
+    float* map = (mi == 0) ? hm + (size_t)b * HW : hm_hp + ((size_t)b * J + (mi - 1)) * HW;
+    float4 v = reinterpret_cast<float4*>(map)[i4];
+    v.x = 1.f / (1.f + expf(-v.x));
+    v.y = 1.f / (1.f + expf(-v.y));
+    v.z = 1.f / (1.f + expf(-v.z));
+    v.w = 1.f / (1.f + expf(-v.w));
+    reinterpret_cast<float4*>(map)[i4] = v;
+}
+
+struct TiledGeom {
+    int R, T, NS;  // rows per band, bands, candidate slots per map (T K rounded up to even)
+};
+
+bool tiled_geom(int J, int H, int W, int K, TiledGeom* g) {
+    if (J < 1 || K < 1 || K > 128 || H < 1 || W < 4 || W % 4 != 0 || W > TL_WMAX) return false;
+    const long long hw = (long long)H * W;
+    if (hw > TL_HWMAX || hw < K) return false;
+    g->R = TL_PIX / W;
+    g->T = (H + g->R - 1) / g->R;
+    g->NS = (g->T * K + 1) & ~1;
+    return g->NS <= TL_MERGE_CAP;
+}
+
+size_t tiled_pk_bytes(int B, int J, int K) { return ((size_t)B * (J + 1) * K * 8 + 255) & ~(size_t)255; }
+
 }  // namespace
 
 size_t cp_decode_ws_bytes(int B, int J, int K) { return (size_t)B * (J + 1) * K * 8 + 256; }
@@ -497,6 +777,46 @@ int cp_launch_decode(hipStream_t s, int B, int J, int H, int W, float* hm, const
     else
         hipLaunchKernelGGL(peaks_kernel<8>, dim3(J + 1, B), dim3(PK_THREADS), 0, s, hm, hm_hp, J, H, W, K, apply_sigmoid,
                            pk_score, pk_ind);
+    AssocParams p;
+    p.hps = hps; p.wh = wh; p.hps_unc = hps_unc; p.scale = scale; p.scale_unc = scale_unc; p.reg = reg;
+    p.hm_hp = hm_hp; p.hp_offset = hp_offset; p.tracking = tracking; p.tracking_hp = tracking_hp;
+    p.pk_score = pk_score; p.pk_ind = pk_ind; p.det = det;
+    p.B = B; p.J = J; p.H = H; p.W = W; p.K = K; p.rep_mode = rep_mode; p.fit_gaussian = fit_gaussian;
+    p.legacy_bool_mask = legacy_bool_mask; p.balance = balance;
+    hipLaunchKernelGGL(assoc_kernel, dim3(J, B), dim3(128), 3 * K * sizeof(float), s, p);
+    return hipGetLastError() == hipSuccess ? CP_OK : CP_ERR_LAUNCH;
+}
+
+size_t cp_decode_tiled_ws_bytes(int B, int J, int H, int W, int K) {
+    TiledGeom g;
+    if (B < 1 || !tiled_geom(J, H, W, K, &g)) return 0;
+    return tiled_pk_bytes(B, J, K) + (size_t)B * (J + 1) * g.NS * 8 + 256;
+}
+
+// Workspace: [pk_score B (J+1) K f32][pk_ind B (J+1) K i32] (peaks_kernel's layout), 256-aligned, then the candidates
+// [B][J+1][NS] u64.  Four launches (three without apply_sigmoid), fixed per shape.
+int cp_launch_decode_tiled(hipStream_t s, int B, int J, int H, int W, float* hm, const float* hps, const float* wh,
+                           const float* hps_unc, const float* scale, const float* scale_unc, const float* reg, float* hm_hp,
+                           const float* hp_offset, const float* tracking, const float* tracking_hp, int K, int rep_mode,
+                           int fit_gaussian, float balance, int legacy_bool_mask, int apply_sigmoid, float* det, void* ws) {
+    TiledGeom g;
+    if (B < 1 || !tiled_geom(J, H, W, K, &g) || ((uintptr_t)ws & 15u) != 0) return CP_ERR_INVALID;
+    float* pk_score = (float*)ws;
+    int* pk_ind = (int*)((char*)ws + (size_t)B * (J + 1) * K * 4);
+    unsigned long long* cand = (unsigned long long*)((char*)ws + tiled_pk_bytes(B, J, K));
+    hipLaunchKernelGGL(peaks_tile_kernel, dim3(g.T, J + 1, B), dim3(PK_THREADS), 0, s, hm, hm_hp, J, H, W, K, g.R, g.NS,
+                       apply_sigmoid, cand);
+    if (apply_sigmoid)
+        hipLaunchKernelGGL(sigmoid_maps_kernel, dim3((H * W / 4 + 255) / 256, J + 1, B), dim3(256), 0, s, hm, hm_hp, J, H * W);
+    const int cap = g.NS <= 2 * PK_THREADS ? 1 : g.NS <= 4 * PK_THREADS ? 2 : g.NS <= 8 * PK_THREADS ? 4
+                  : g.NS <= 16 * PK_THREADS ? 8 : 16;
+    switch (cap) {
+        case 1: hipLaunchKernelGGL(peaks_merge_kernel<1>, dim3(J + 1, B), dim3(PK_THREADS), 0, s, cand, g.NS, K, pk_score, pk_ind); break;
+        case 2: hipLaunchKernelGGL(peaks_merge_kernel<2>, dim3(J + 1, B), dim3(PK_THREADS), 0, s, cand, g.NS, K, pk_score, pk_ind); break;
+        case 4: hipLaunchKernelGGL(peaks_merge_kernel<4>, dim3(J + 1, B), dim3(PK_THREADS), 0, s, cand, g.NS, K, pk_score, pk_ind); break;
+        case 8: hipLaunchKernelGGL(peaks_merge_kernel<8>, dim3(J + 1, B), dim3(PK_THREADS), 0, s, cand, g.NS, K, pk_score, pk_ind); break;
+        default: hipLaunchKernelGGL(peaks_merge_kernel<16>, dim3(J + 1, B), dim3(PK_THREADS), 0, s, cand, g.NS, K, pk_score, pk_ind); break;
+    }
     AssocParams p;
     p.hps = hps; p.wh = wh; p.hps_unc = hps_unc; p.scale = scale; p.scale_unc = scale_unc; p.reg = reg;
     p.hm_hp = hm_hp; p.hp_offset = hp_offset; p.tracking = tracking; p.tracking_hp = tracking_hp;

@@ -1752,9 +1752,16 @@ int cp_model_forward(cp_model* m, cp_stream_t stream, int B, int H, int W, const
                         workspace, workspace_bytes, false);
 }
 
+// the decode's share of a detect workspace: peaks_kernel up to 32768 output pixels, the tiled peaks above (0: unsupported)
+static size_t detect_decode_ws_bytes(int B, int H, int W, int K) {
+    const int ho = H / 4, wo = W / 4;
+    return ho * wo <= 32768 ? cp_decode_ws_bytes(B, 8, K) : cp_decode_tiled_ws_bytes(B, 8, ho, wo, K);
+}
+
 size_t cp_model_detect_workspace_bytes(cp_model* m, int B, int H, int W, int K) {
     const size_t a = cp_model_workspace_bytes(m, B, H, W);
-    return a ? align_up(a, 256) + cp_decode_ws_bytes(B, 8, K) : 0;
+    const size_t d = detect_decode_ws_bytes(B, H, W, K);
+    return a && d ? align_up(a, 256) + d : 0;
 }
 
 // backbone + heads + sigmoid + decode in one call (what ObjectPoseDetector.process does, object_pose.py:131-165),
@@ -1767,7 +1774,10 @@ int cp_model_detect(cp_model* m, cp_stream_t stream, int B, int H, int W, const 
     if (!m->finalized) return fail(CP_ERR_STATE, "model not finalized");
     const size_t model_ws = align_up(cp_model_workspace_bytes(m, B, H, W), 256);
     if (model_ws == 0) return CP_ERR_INVALID;
-    if (workspace_bytes < model_ws + cp_decode_ws_bytes(B, 8, K)) return fail(CP_ERR_INVALID, "workspace too small");
+    const bool tiled = (H / 4) * (W / 4) > 32768;
+    const size_t dec_ws = detect_decode_ws_bytes(B, H, W, K);
+    if (dec_ws == 0) return fail(CP_ERR_INVALID, "detect: unsupported decode shape (need K <= 128, K <= H*W/16 <= 2^20, W/4 <= 4096)");
+    if (workspace_bytes < model_ws + dec_ws) return fail(CP_ERR_INVALID, "workspace too small");
     // decode inputs by head name (opts.py:394-426)
     float* hp[11] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     const char* names[11] = {"hm", "hps", "wh", "hps_uncertainty", "scale", "scale_uncertainty", "reg", "hm_hp",
@@ -1795,14 +1805,14 @@ int cp_model_detect(cp_model* m, cp_stream_t stream, int B, int H, int W, const 
             r.e1 = m->get_event();
             (void)hipEventRecord(r.e0, s);
         }
-        rc = cp_launch_decode(s, B, 8, H / 4, W / 4, hp[0], hp[1], hp[2], hp[3], hp[4], hp[5], hp[6], hp[7], hp[8], hp[9],
-                              hp[10], K, rep_mode, fit_gaussian, balance, legacy_bool_mask, 0, det,
-                              (char*)workspace + model_ws);
+        rc = (tiled ? cp_launch_decode_tiled : cp_launch_decode)(
+            s, B, 8, H / 4, W / 4, hp[0], hp[1], hp[2], hp[3], hp[4], hp[5], hp[6], hp[7], hp[8], hp[9], hp[10], K, rep_mode,
+            fit_gaussian, balance, legacy_bool_mask, 0, det, (char*)workspace + model_ws);
         if (m->profile) {
             (void)hipEventRecord(r.e1, s);
             m->prof.push_back(r);
         }
-        if (rc != CP_OK) return fail(rc, "detect: decode failed (need K <= 128 <= H*W/16 <= 32768)");
+        if (rc != CP_OK) return fail(rc, "detect: decode failed (need K <= 128, K <= H*W/16 <= 2^20, W/4 <= 4096)");
         return rc;
     };
     if (!use_graph || m->profile) return enqueue();
@@ -2110,6 +2120,29 @@ int cp_decode(cp_stream_t stream, int B, int H, int W, float* hm, const float* h
                               reg, hm_hp, hp_offset, tracking, tracking_hp, K, rep_mode, fit_gaussian, balance,
                               legacy_bool_mask, apply_sigmoid, det, workspace);
     if (rc != CP_OK) return fail(rc, "decode: unsupported shape (need K <= 128 <= H*W <= 32768, W % 4 == 0) or launch failure");
+    return CP_OK;
+}
+
+size_t cp_decode_tiled_workspace_bytes(int B, int H, int W, int K) { return cp_decode_tiled_ws_bytes(B, 8, H, W, K); }
+
+int cp_decode_tiled(cp_stream_t stream, int B, int H, int W, float* hm, const float* hps, const float* wh,
+                    const float* hps_uncertainty, const float* scale, const float* scale_uncertainty, const float* reg,
+                    float* hm_hp, const float* hp_offset, const float* tracking, const float* tracking_hp, int K,
+                    int rep_mode, int fit_gaussian, float balance, int legacy_bool_mask, int apply_sigmoid, float* det,
+                    void* workspace, size_t workspace_bytes) {
+    if (!hm || !hps || !wh || !hm_hp || !det || !workspace)
+        return fail(CP_ERR_INVALID, "hm, hps, wh, hm_hp, det and workspace are required");
+    if (B < 1 || rep_mode < 0 || rep_mode > 4) return fail(CP_ERR_INVALID, "bad B / rep_mode");
+    const size_t need = cp_decode_tiled_workspace_bytes(B, H, W, K);
+    if (need == 0)
+        return fail(CP_ERR_INVALID, "decode_tiled: unsupported shape (need 1 <= K <= 128, K <= H*W <= 1048576, "
+                                    "W % 4 == 0, W <= 4096)");
+    if (workspace_bytes < need) return fail(CP_ERR_INVALID, "workspace too small");
+    if (((uintptr_t)workspace & 15u) != 0) return fail(CP_ERR_INVALID, "decode_tiled: workspace must be 16-byte aligned");
+    int rc = cp_launch_decode_tiled((hipStream_t)stream, B, 8, H, W, hm, hps, wh, hps_uncertainty, scale, scale_uncertainty,
+                                    reg, hm_hp, hp_offset, tracking, tracking_hp, K, rep_mode, fit_gaussian, balance,
+                                    legacy_bool_mask, apply_sigmoid, det, workspace);
+    if (rc != CP_OK) return fail(rc, "decode_tiled: launch failure");
     return CP_OK;
 }
 

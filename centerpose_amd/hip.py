@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CENTERPOSE_HIP_LIB") or os.path.join(_HERE, "libcenterpose_hip.so")
 
 _lib = None
-ABI_VERSION = 6  # CP_ABI_VERSION of include/centerpose_hip.h this binding was written against
+ABI_VERSION = 7  # CP_ABI_VERSION of include/centerpose_hip.h this binding was written against
 
 c_void_p = ctypes.c_void_p
 c_int = ctypes.c_int
@@ -77,6 +77,9 @@ def lib():
     _sig(L.cp_decode_workspace_bytes, c_size_t, c_int, c_int)
     _sig(L.cp_decode, c_int, c_void_p, c_int, c_int, c_int, *([c_void_p] * 11), c_int, c_int, c_int, ctypes.c_float,
          c_int, c_int, c_void_p, c_void_p, c_size_t)
+    _sig(L.cp_decode_tiled_workspace_bytes, c_size_t, c_int, c_int, c_int, c_int)
+    _sig(L.cp_decode_tiled, c_int, c_void_p, c_int, c_int, c_int, *([c_void_p] * 11), c_int, c_int, c_int, ctypes.c_float,
+         c_int, c_int, c_void_p, c_void_p, c_size_t)
     _sig(L.cp_model_detect_workspace_bytes, c_size_t, c_void_p, c_int, c_int, c_int, c_int)
     _sig(L.cp_model_detect, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
          ctypes.POINTER(c_void_p), c_int, c_int, c_int, ctypes.c_float, c_int, c_void_p, c_void_p, c_size_t, c_int)
@@ -136,7 +139,8 @@ def exported_symbols():
             "cp_kernel_variant_name", "cp_set_default_precision", "cp_model_set_precision", "cp_model_detect_workspace_bytes", "cp_model_detect", "cp_set_debug", "cp_preprocess", "cp_preprocess_batch", "cp_postprocess_workspace_bytes", "cp_postprocess", "cp_render_gaussians",
             "cp_model_profile_roles", "cp_role_name", "cp_pnp_from_post_workspace_bytes", "cp_pnp_from_post", "cp_resize_u8",
             "cp_abi_version", "cp_num_kernel_variants", "cp_num_roles", "cp_track_state_bytes", "cp_track_workspace_bytes",
-            "cp_track_reset", "cp_track_step", "cp_track_status", "cp_linear_assignment"]
+            "cp_track_reset", "cp_track_step", "cp_track_status", "cp_linear_assignment", "cp_decode_tiled_workspace_bytes",
+            "cp_decode_tiled"]
 
 
 def _check(rc, what):
@@ -239,6 +243,32 @@ def decode_raw(hm, hps, wh, hm_hp, hps_uncertainty=None, scale=None, scale_uncer
                      int(bool(fit_gaussian)), float(balance), int(bool(legacy_bool_mask)), int(bool(apply_sigmoid)),
                      _ptr(det), _ptr(ws), n)
     _check(rc, "cp_decode")
+    return det
+
+
+def decode_raw_tiled(hm, hps, wh, hm_hp, hps_uncertainty=None, scale=None, scale_uncertainty=None, reg=None,
+                     hp_offset=None, tracking=None, tracking_hp=None, K=100, rep_mode=1, fit_gaussian=False,
+                     balance=2.0, legacy_bool_mask=False, apply_sigmoid=False):
+    """``decode_raw`` through cp_decode_tiled: the same records, bit for bit, for output grids of any size up to 1048576
+    pixels (W % 4 == 0, W <= 4096, K <= 128).  The workspace grows with H*W and is sized here."""
+    L = lib()
+    for t in (hm, hps, wh, hm_hp):
+        if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32):
+            raise RuntimeError("decode_tiled: required heads must be contiguous float32 device tensors")
+    opt = [None if t is None else _dev(t) for t in (hps_uncertainty, scale, scale_uncertainty, reg, hp_offset,
+                                                    tracking, tracking_hp)]
+    B, _, H, W = hm.shape
+    n = L.cp_decode_tiled_workspace_bytes(B, H, W, int(K))
+    if n == 0:
+        raise RuntimeError("decode_tiled: unsupported shape B=%d H=%d W=%d K=%d (need 1 <= K <= 128, K <= H*W <= 1048576, "
+                           "W %% 4 == 0, W <= 4096)" % (B, H, W, K))
+    det = torch.empty(B, K, DET_STRIDE, device=hm.device, dtype=torch.float32)
+    ws = torch.empty(n, dtype=torch.uint8, device=hm.device)
+    rc = L.cp_decode_tiled(_stream(), B, H, W, _ptr(hm), _ptr(hps), _ptr(wh), _ptr(opt[0]), _ptr(opt[1]), _ptr(opt[2]),
+                           _ptr(opt[3]), _ptr(hm_hp), _ptr(opt[4]), _ptr(opt[5]), _ptr(opt[6]), int(K), int(rep_mode),
+                           int(bool(fit_gaussian)), float(balance), int(bool(legacy_bool_mask)), int(bool(apply_sigmoid)),
+                           _ptr(det), _ptr(ws), n)
+    _check(rc, "cp_decode_tiled")
     return det
 
 

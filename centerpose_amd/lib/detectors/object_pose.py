@@ -5,7 +5,7 @@ import numpy as np
 import torch
 
 from ..models.decode import object_pose_decode_raw
-from ..utils.post_process import object_pose_post_process
+from ..utils.post_process import length_ratio, object_pose_post_process
 from .base_detector import BaseDetector
 
 
@@ -131,7 +131,7 @@ class ObjectPoseDetector(BaseDetector):
         for b, meta in enumerate(metas):
             w, h = meta['out_width'], meta['out_height']
             arr[b, :6] = get_affine_transform(meta['c'], meta['s'], 0, (w, h), inv=1).reshape(-1)
-            arr[b, 6] = meta['s'] / max(w, h)
+            arr[b, 6] = length_ratio(meta['s'], w, h)
         use_nms = bool(self.opt.nms or len(self.opt.test_scales) > 1)
         rec, cnt = _hip.postprocess(self.raw_dets, arr, self.opt.vis_thresh, use_nms)
         self.post_dev = (rec, cnt)  # stays on the device for cp_pnp_from_post (run_batch)

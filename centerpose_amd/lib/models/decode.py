@@ -1,5 +1,6 @@
 """``object_pose_decode`` with the reference's signature and return schema (models/decode.py:72-375),
-executed by the device decode kernels (centerpose_hip.h: cp_decode).
+executed by the device decode kernels (centerpose_hip.h: cp_decode; cp_decode_tiled for output grids above 32768
+pixels, e.g. --keep_res on 1280 x 720 video or --input_res 1024).
 
 Differences that are deliberate and documented:
   * ``mask_2 == 7`` uses the torch<=1.1 semantics (AND of its 7 conditions) by default; set
@@ -11,6 +12,8 @@ category, 8 joints); anything else raises.
 import torch
 
 from centerpose_amd import hip as _hip
+
+_PEAKS_ONE_WORKGROUP = 32768  # largest output grid cp_decode takes (one workgroup per map)
 
 
 def _nms(heat, kernel=3):
@@ -37,7 +40,9 @@ def object_pose_decode_raw(heat, kps, wh=None, kps_displacement_std=None, obj_sc
     if heat.size(1) != 1 or kps.size(1) != 16:
         raise NotImplementedError("one category / 8 joints (opts.py:435-440)")
     fit = bool(getattr(opt, 'tracking_task', False) or getattr(opt, 'refined_Kalman', False) or opt.rep_mode == 2)
-    return _hip.decode_raw(heat.contiguous(), kps.contiguous(), wh.contiguous(), hm_hp.contiguous(),
+    H, W = heat.shape[-2:]
+    run = _hip.decode_raw if H * W <= _PEAKS_ONE_WORKGROUP else _hip.decode_raw_tiled
+    return run(heat.contiguous(), kps.contiguous(), wh.contiguous(), hm_hp.contiguous(),
                            hps_uncertainty=kps_displacement_std, scale=obj_scale,
                            scale_uncertainty=obj_scale_uncertainty, reg=reg, hp_offset=hp_offset, tracking=tracking,
                            tracking_hp=tracking_hp, K=opt.K, rep_mode=opt.rep_mode, fit_gaussian=fit,

@@ -39,8 +39,9 @@ typedef struct cp_model cp_model;
  * meaning.  History: 1 = round-1 header; 2 = cp_preprocess takes the FORWARD 2x3 affine as double[6] and inverts it
  * itself (round 1: the inverse as float[6]); 3 = cp_dcnv2_forward accepts every shape of the reference op (generic
  * kernel), cp_num_kernel_variants() / cp_num_roles() size the profile buffers; 4 = cp_track_* added; 5 = cp_track_status, list truncation instead of reset on overflow;
- * 6 = cp_preprocess_batch, cp_linear_assignment, CP_NUM_KERNEL_VARIANTS 43, cp_set_debug moved out of this header (centerpose_hip_testing.h). */
-#define CP_ABI_VERSION 6
+ * 6 = cp_preprocess_batch, cp_linear_assignment, CP_NUM_KERNEL_VARIANTS 43, cp_set_debug moved out of this header (centerpose_hip_testing.h);
+ * 7 = cp_decode_tiled / cp_decode_tiled_workspace_bytes, cp_model_detect decodes output grids above 32768 pixels. */
+#define CP_ABI_VERSION 7
 const char* cp_version(void);
 int cp_abi_version(void);
 const char* cp_last_error(void);
@@ -103,7 +104,9 @@ int cp_model_forward(cp_model* m, cp_stream_t stream, int B, int H, int W, const
  * cp_model_forward and cp_decode; head_out[] receives the head tensors (hm / hm_hp post-sigmoid), det the
  * [B,K,118] records.  With use_graph != 0 the launch sequence is captured into a hipGraph on first use (keyed
  * by every pointer / size argument, so buffers must be reused) and replayed afterwards: a frame costs one graph
- * launch instead of ~120 kernel launches.  Needs a non-default stream; ignored while profiling is armed. */
+ * launch instead of ~120 kernel launches.  Needs a non-default stream; ignored while profiling is armed.
+ * Output grids (H/4) x (W/4) above 32768 pixels are decoded by cp_decode_tiled's kernels (its size limits apply, and
+ * the workspace grows with the grid); up to 32768 pixels the launches and workspace are cp_decode's. */
 size_t cp_model_detect_workspace_bytes(cp_model* m, int B, int H, int W, int K);
 int cp_model_detect(cp_model* m, cp_stream_t stream, int B, int H, int W, const float* images, const float* pre_img,
                     const float* pre_hm, const float* pre_hm_hp, float* const* head_out, int K, int rep_mode,
@@ -192,6 +195,12 @@ int cp_conv2d_nhwc(cp_stream_t stream, const float* x, const float* w, const flo
  *   kps_heatmap_height[110:118]  — the 13 keys of decode.py:347-361, output-grid units.
  * Ordering: (score desc, pixel index asc); torch.topk's order among exactly equal scores is
  * implementation-defined, so parity is defined on distinct scores.
+ *
+ * cp_decode_tiled: the same arguments, outputs and ordering as cp_decode (bit-identical wherever both accept a shape)
+ * for output grids of any size: 1 <= K <= 128, K <= H*W <= 1048576 (a 4096 x 4096 network input), W % 4 == 0 and
+ * W <= 4096; anything else returns CP_ERR_INVALID.  The peaks are found per band of whole rows and merged per map, so
+ * the workspace grows with H*W: cp_decode_tiled_workspace_bytes(B, H, W, K) (0 for an unsupported shape); it must be
+ * 16-byte aligned.  cp_model_detect takes this path for output grids above 32768 pixels.
  * ------------------------------------------------------------------------------------------ */
 #define CP_DET_STRIDE 118
 size_t cp_decode_workspace_bytes(int B, int K);
@@ -200,6 +209,12 @@ int cp_decode(cp_stream_t stream, int B, int H, int W, float* hm, const float* h
               float* hm_hp, const float* hp_offset, const float* tracking, const float* tracking_hp, int K,
               int rep_mode, int fit_gaussian, float balance, int legacy_bool_mask, int apply_sigmoid, float* det,
               void* workspace, size_t workspace_bytes);
+size_t cp_decode_tiled_workspace_bytes(int B, int H, int W, int K);
+int cp_decode_tiled(cp_stream_t stream, int B, int H, int W, float* hm, const float* hps, const float* wh,
+                    const float* hps_uncertainty, const float* scale, const float* scale_uncertainty, const float* reg,
+                    float* hm_hp, const float* hp_offset, const float* tracking, const float* tracking_hp, int K,
+                    int rep_mode, int fit_gaussian, float balance, int legacy_bool_mask, int apply_sigmoid, float* det,
+                    void* workspace, size_t workspace_bytes);
 
 /* ------------------------------------------------------------------------------------------
  * Pre-process — replaces `BaseDetector.pre_process`'s image work
