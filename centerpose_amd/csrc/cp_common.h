@@ -359,6 +359,11 @@ int cp_launch_dcn_generic(hipStream_t s, const float* x, const float* w, const f
                           const float* mask, float* out, int B, int C, int H, int W, int Co, int Ho, int Wo, int kh, int kw,
                           int sh, int sw, int ph, int pw, int dh, int dw, int dg);
 
+// ---- Objectron box metrics (box3d.hip; numerics in box3d_common.h) ----
+int cp_launch_box_iou(hipStream_t s, const double* a, const double* b, int n, double* iou);
+int cp_launch_box_eval(hipStream_t s, const double* pred3d, const double* gt3d, const double* pred2d, const double* mo2c,
+                       const double* proj, const int* single, int n, int num_symmetry, double* out);
+
 // ---- batched PnP (pnp.hip) ----
 #define CP_PNP_STRIDE 40
 size_t cp_pnp_ws_bytes(int N);

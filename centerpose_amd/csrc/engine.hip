@@ -2068,6 +2068,22 @@ int cp_track_step(cp_stream_t stream, const cp_track_params* params, const doubl
     return rc == CP_OK ? CP_OK : fail(rc, "cp_track_step: launch failed");
 }
 
+int cp_box_iou(cp_stream_t stream, const double* a, const double* b, int n, double* iou) {
+    if (n < 1) return fail(CP_ERR_INVALID, "cp_box_iou: n must be >= 1");
+    if (!a || !b || !iou) return fail(CP_ERR_INVALID, "cp_box_iou: null argument");
+    return cp_launch_box_iou((hipStream_t)stream, a, b, n, iou);
+}
+
+int cp_box_eval(cp_stream_t stream, const double* pred3d, const double* gt3d, const double* pred2d, const double* mo2c,
+                const double* proj, const int* single_rotation, int n, int num_symmetry, double* out) {
+    if (n < 1) return fail(CP_ERR_INVALID, "cp_box_eval: n must be >= 1");
+    if (num_symmetry < 1) return fail(CP_ERR_INVALID, "cp_box_eval: num_symmetry must be >= 1");
+    if (!pred3d || !gt3d || !pred2d || !mo2c || !proj || !single_rotation || !out)
+        return fail(CP_ERR_INVALID, "cp_box_eval: null argument");
+    return cp_launch_box_eval((hipStream_t)stream, pred3d, gt3d, pred2d, mo2c, proj, single_rotation, n, num_symmetry,
+                              out);
+}
+
 int cp_linear_assignment(const double* cost, int n_rows, int n_cols, int solver, int* match_out) {
     if (n_rows < 0 || n_cols < 0 || (n_rows > 0 && !match_out) || (n_rows > 0 && n_cols > 0 && !cost) || (solver != 1 && solver != 2))
         return fail(CP_ERR_INVALID, "cp_linear_assignment: bad argument (solver: 1 Munkres, 2 scipy LSAP)");

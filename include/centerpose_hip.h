@@ -40,7 +40,8 @@ typedef struct cp_model cp_model;
  * itself (round 1: the inverse as float[6]); 3 = cp_dcnv2_forward accepts every shape of the reference op (generic
  * kernel), cp_num_kernel_variants() / cp_num_roles() size the profile buffers; 4 = cp_track_* added; 5 = cp_track_status, list truncation instead of reset on overflow;
  * 6 = cp_preprocess_batch, cp_linear_assignment, CP_NUM_KERNEL_VARIANTS 43, cp_set_debug moved out of this header (centerpose_hip_testing.h);
- * 7 = cp_decode_tiled / cp_decode_tiled_workspace_bytes, cp_model_detect decodes output grids above 32768 pixels. */
+ * 7 = cp_decode_tiled / cp_decode_tiled_workspace_bytes, cp_model_detect decodes output grids above 32768 pixels;
+ *     later additions without a version change: cp_box_iou, cp_box_eval. */
 #define CP_ABI_VERSION 7
 const char* cp_version(void);
 int cp_abi_version(void);
@@ -379,6 +380,37 @@ int cp_track_status(cp_stream_t stream, const void* state, int B, int* dropped_o
  *   solver     1 = scikit-learn 0.22.2's Munkres, 2 = scipy's rectangular LSAP (cp_track_params.hungarian)
  *   match_out  HOST int32 [n_rows]: column of each row, -1 for rows left out (min(n_rows, n_cols) rows get one) */
 int cp_linear_assignment(const double* cost, int n_rows, int n_cols, int solver, int* match_out);
+
+/* Objectron box metrics, float64 (added without an ABI change: new entry points only).  Boxes are the evaluator's 9 x 3
+ * vertex sets (centre + 8 corners in objectron/dataset/box.py order).  All pointers are DEVICE memory owned by the caller;
+ * both calls only enqueue on `stream`.
+ *
+ * cp_box_iou: IoU3D.IoU(Box(a[i]), Box(b[i])).iou() (objectron/dataset/iou.py:22-37) for i < n -> iou [n].  Same fit,
+ *   transforms and Sutherland-Hodgman clipping as the reference; the intersection volume is the divergence theorem over
+ *   the clipped faces instead of qhull (agrees to ~1e-13, to ~1e-6 where vertices lie within the 1e-6 plane epsilon).
+ *
+ * cp_box_eval: for each of n matched pairs, Evaluator.evaluate_3d and evaluate_2d (eval_image_official.py:673-793) with
+ *   eval_num_symmetry = num_symmetry >= 1:
+ *   pred3d [n,9,3] the (scaled) predicted box, gt3d [n,9,3] the annotation, pred2d [n,9,2] the predicted projection,
+ *   mo2c [n,4,4] and proj [n,4,4] the annotation's object-to-camera and projection matrices, single_rotation [n] int32:
+ *   nonzero evaluates rotation index 0 only in both sweeps (eval_mug_symmetric False on a mug).
+ *   out [n, CP_BOX_EVAL_STRIDE]:
+ *     [0] IoU of the best rotation (first index of the maximum; 0 when no rotation has IoU > 0)
+ *     [1] ADD  [2] ADD-S  [3] azimuth error  [4] polar error (degrees) of that rotation; with no IoU > 0,
+ *         ADD = ADD-S = 1.0 (_MAX_DISTANCE) and the viewpoint errors of the unrotated prediction
+ *     [5] 2D error: the minimum mean reprojection distance over the 2D sweep (first index on ties)
+ *     [6] best 3D rotation index (-1: none)  [7] best 2D index  [8] CP_BOX_FLAG_* bits:
+ *         SINGULAR_RAY  a 4 x 4 ray solve of compute_ray met an exactly zero pivot (numpy's inv raises and the
+ *                       reference falls back to pinv): the viewpoint errors are NaN
+ *         SINGULAR_MO2C mo2c is singular (the reference raises): the 2D error is NaN
+ *         CLIP_OVERFLOW a clipped polygon exceeded its 10-vertex capacity (not expected for boxes) */
+#define CP_BOX_EVAL_STRIDE 9
+#define CP_BOX_FLAG_SINGULAR_RAY 1
+#define CP_BOX_FLAG_SINGULAR_MO2C 2
+#define CP_BOX_FLAG_CLIP_OVERFLOW 4
+int cp_box_iou(cp_stream_t stream, const double* a, const double* b, int n, double* iou);
+int cp_box_eval(cp_stream_t stream, const double* pred3d, const double* gt3d, const double* pred2d, const double* mo2c,
+                const double* proj, const int* single_rotation, int n, int num_symmetry, double* out);
 
 #ifdef __cplusplus
 }
