@@ -1,11 +1,15 @@
 #!/usr/bin/env python
 """bench.py -- throughput of the CenterPose inference hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 K timed steps after W untimed ones; `ms_per_step` on the result line is the time of one timed step.  --dump-outputs DIR
 writes what the last timed step returned (the decoded records; for the default workload also the post-processed records
 and the poses) as DIR/<name>.npy; inputs and weights are seeded, so two builds can be compared output for output.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the dump, and the result line with the
+`roofline` read from the timed steps' own launch events.  --full adds every measurement that takes runs of its own: the
+batch-1 latencies, the nested `legs` and the `cpu_baseline` (see `extras`); without it those keys are null or a stub.
 
 N > 1: the driver launches this file under `python -m torch.distributed.run --nproc-per-node N ...` (one rank per GPU,
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment); when it is started directly with --gpus N > 1 and no
@@ -20,7 +24,7 @@ random-init weights -> backbone (DLA-34 + DCNv2 up-sampling + fused heads) -> si
 post-process + soft-NMS -> PnP-input assembly -> batched PnP, everything on the device, no host synchronisation inside
 a step.  One "step" = one batch through that chain, inputs resident in HBM before the timed region.
 
-Extra objects on the ONE JSON line rank 0 prints:
+Extra objects on the ONE JSON line rank 0 prints (all but `roofline` with --full only):
   roofline      dominant kernel of the timed region: algorithmic FLOPs of its launches / their HIP-event durations
                 (events recorded on the launch stream) vs the dense matrix peak of gfx950, plus the figures
                 BASELINE.json's north_star names: roofline.dcn (DCNv2 + offset convolutions vs SURVEY 8(d)'s
@@ -84,19 +88,22 @@ WORKLOAD_TEXT = {
 }
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="full", choices=sorted(WORKLOAD_TEXT),
-                    help="full (default): BASELINE configs[2]; decode: configs[1]; the others: see the `legs` of the default run")
+                    help="full (default): BASELINE configs[2]; decode: configs[1]; the others: see the `legs` of a --full run")
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (default: the configuration's)")
     ap.add_argument("--precision", default="f16x3", choices=["f32", "f16x3"],
                     help="f32: exact float32 MFMA; f16x3: split-binary16 MFMA (float32-class accuracy)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-legs", action="store_true", help="skip the nested legs of the default run")
-    ap.add_argument("--no-latency", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the batch-1 latencies, the nested legs (other configurations and "
+                         "precisions) and the reference's CPU baseline; a plain run skips them")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-legs", action="store_true", help="--full without the nested legs of the default workload")
+    ap.add_argument("--no-latency", action="store_true", help="--full without the batch-1 latencies")
     ap.add_argument("--serial-pnp", action="store_true",
                     help="full: run the PnP solve on the network's stream (A/B against the side-stream default)")
     ap.add_argument("--dbg", type=int, default=0, help="cp_set_debug flags (kernel A/B switches, tuning only)")
@@ -106,12 +113,20 @@ def parse():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / float64, "
                          "at most 64 MB in all), for output-by-output comparison of two builds")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
     if args.dump_outputs and args.workload == "track_e2e":
         ap.error("--dump-outputs: the track_e2e workload has no single step output (it times a host-in-the-loop video run)")
     return args
+
+
+def extras(args, world, dry):
+    """Which measurements rank 0 makes after the timed steps: none without --full (a plain run times the headline only)."""
+    on = args.full and not dry
+    return {"latency": on and not args.no_latency and args.workload in ("full", "decode", "hourglass"),
+            "legs": on and world == 1 and args.workload == "full" and not args.no_legs,
+            "cpu_baseline": on and world == 1 and not args.no_cpu_baseline}
 
 
 def respawn_under_torchrun(args):
@@ -1044,6 +1059,7 @@ def main():
     value = world * batch * args.steps / dt
 
     if rank == 0:
+        more = extras(args, world, dry)
         roof = None if dry else roofline_object(prof, roles, sampled, batch, args.precision, args.workload)
         if roof is not None and args.workload == "full":
             ms, n = pipe.pnp_stats()
@@ -1054,13 +1070,13 @@ def main():
                                "note": "PnP-input assembly + batched solve of one batch, HIP events on hip.PoseStage's side "
                                        "stream; runs under the next batch's network (DESIGN 3.6)"}
         lat = lat_det = None
-        if not dry and not args.no_latency and args.workload in ("full", "decode", "hourglass"):
+        if more["latency"]:
             pipe.gather = False  # rank 0 alone: no collective inside the batch-1 latency loop
             lat = frame_latency(pipe)
             if args.workload == "full":
                 lat_det = detect_latency(pipe)
         legs = None
-        if not dry and world == 1 and args.workload == "full" and not args.no_legs:
+        if more["legs"]:
             # the other configurations, driver-timed in the same run (short legs; each has its own roofline object)
             del pipe.model
             pipe._stages.clear()
@@ -1090,10 +1106,12 @@ def main():
             except Exception as e:  # the host-in-the-loop leg must not take the headline line down with it
                 legs["track_e2e"] = {"error": "%s: %s" % (type(e).__name__, e)}
         cpu = None
-        if not dry and world == 1 and not args.no_cpu_baseline:
+        if more["cpu_baseline"]:
             cpu = cpu_baseline(args.workload, pipe.arch)
         elif world > 1:
             cpu = {"skipped": "N > 1: the reference's CPU path is timed on rank 0 of the N = 1 run only"}
+        elif not dry and not args.full:
+            cpu = {"skipped": "the reference's CPU path is timed by --full runs only"}
         key = pipe.arch + ("_track" if pipe.track else "")
         gf = GFLOP_PER_IMG[key]
         tail = {"full": " + post-process + PnP", "decode": "", "hourglass": ""}.get(args.workload, " + detection all-gather")

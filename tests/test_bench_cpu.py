@@ -36,6 +36,25 @@ def test_bench_gpus_flag_spawns_that_many_ranks():
     assert d["data"].startswith("dry-run") and d["dry_run_devices"] == [0, 1]
 
 
+def test_plain_run_measures_the_headline_only():
+    """A plain `bench.py --gpus 1 --steps N --warmup W` makes no measurement after its timed steps (no batch-1 latency, no
+    nested legs, no CPU baseline); --full makes every one of them, each --no-* flag takes its own away, and dry runs make none."""
+    sys.path.insert(0, REPO)
+    import bench
+
+    base = ["--gpus", "1", "--steps", "20", "--warmup", "5"]
+    assert bench.extras(bench.parse(base), 1, False) == {"latency": False, "legs": False, "cpu_baseline": False}
+    assert bench.extras(bench.parse(base + ["--dump-outputs", "d"]), 1, False) == {"latency": False, "legs": False, "cpu_baseline": False}
+    assert bench.extras(bench.parse(base + ["--full"]), 1, False) == {"latency": True, "legs": True, "cpu_baseline": True}
+    assert bench.extras(bench.parse(base + ["--full"]), 1, True) == {"latency": False, "legs": False, "cpu_baseline": False}
+    assert bench.extras(bench.parse(base + ["--full"]), 2, False) == {"latency": True, "legs": False, "cpu_baseline": False}
+    assert bench.extras(bench.parse(base + ["--full", "--workload", "decode"]), 1, False) == \
+        {"latency": True, "legs": False, "cpu_baseline": True}
+    for flag, key in (("--no-latency", "latency"), ("--no-legs", "legs"), ("--no-cpu-baseline", "cpu_baseline")):
+        got = bench.extras(bench.parse(base + ["--full", flag]), 1, False)
+        assert got == {k: k != key for k in got}, flag
+
+
 def test_bench_single_rank_dry_run_has_no_group():
     d = _run(["--dry-run", "--steps", "2", "--warmup", "0"])
     assert d["n_gpus"] == 1 and d["rccl_ranks"] == 1 and d["config"]["global_batch"] == 64

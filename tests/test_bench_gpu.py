@@ -19,7 +19,7 @@ def test_bench_two_ranks_on_one_gpu_over_gloo(device):
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--no-legs", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=600)
+                        "--full", "--no-legs", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -58,8 +58,8 @@ def test_bench_two_gpus_over_rccl_preflight(device):
 def test_bench_single_rank_under_the_launcher_equals_the_plain_launch(device):
     """N = 1 as the driver starts a scaling series (`python -m torch.distributed.run --nproc-per-node 1 ... bench.py --gpus 1`)
     must be the same measurement as `python bench.py`: same workload, batch, no collective, a roofline, and a throughput within
-    run-to-run noise of the plain launch."""
-    argv = ["--gpus", "1", "--steps", "6", "--warmup", "2", "--no-legs", "--no-cpu-baseline", "--no-latency"]
+    run-to-run noise of the plain launch.  Without --full neither run measures anything after its timed steps."""
+    argv = ["--gpus", "1", "--steps", "6", "--warmup", "2"]
     plain = _bench(argv, {})
     port = str(34000 + os.getpid() % 2000)
     under = _bench(argv, {}, launcher=[sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
@@ -67,5 +67,6 @@ def test_bench_single_rank_under_the_launcher_equals_the_plain_launch(device):
     for d in (plain, under):
         assert d["n_gpus"] == 1 and d["rccl_ranks"] == 1 and d["config"]["global_batch"] == 64
         assert "single rank" in d["config"]["parallelism"] and d["roofline"]["kernel"]
+        assert d["legs"] is None and d["p50_frame_ms_batch1"] is None and "skipped" in d["cpu_baseline"]
     assert plain["config"] == under["config"] and plain["metric"] == under["metric"]
     assert abs(plain["value"] - under["value"]) / plain["value"] < 0.08

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Regenerate the judged artefacts under gpurun_out/refresh/ on the GPU box (copy into profiles/ afterwards):
-#   the default bench line (BASELINE configs[2] on top, every other configuration as a nested leg), the per-launch layer
+#   the --full bench line (BASELINE configs[2] on top, every other configuration as a nested leg), the per-launch layer
 #   CSV, rocprofv3 kernel-trace stats and the two PMC passes (FETCH_SIZE / WRITE_SIZE in separate runs, no other
 #   tracing) of the default bench command's timed region.
 #   usage: tools/refresh_profiles.sh [quick]     quick = bench line + kernel stats only
@@ -9,7 +9,7 @@ R=$PWD
 O=$R/gpurun_out/refresh
 rm -rf $O; mkdir -p $O
 export TMPDIR=/tmp
-timeout 900 python bench.py 2>$O/bench_default.err | tail -1 > $O/bench_default.json
+timeout 900 python bench.py --full 2>$O/bench_default.err | tail -1 > $O/bench_default.json
 B="--no-cpu-baseline --no-latency --no-legs"
 CP_PROFILE_DUMP=$O/layers_default.csv timeout 300 python bench.py --steps 8 --warmup 2 $B 2>/dev/null | tail -1 > $O/bench_layers.json
 cd /tmp

@@ -1,13 +1,13 @@
 #!/bin/bash
 # A round's artefacts on the GPU box -> gpurun_out/<tag>/ (copied into profiles/<tag>_* afterwards):
-#   full GPU test suite, the default bench line (+ detail file), rocprofv3 kernel-trace stats of the bench command, the SQ
+#   full GPU test suite, the --full bench line (+ detail file), rocprofv3 kernel-trace stats of the bench command, the SQ
 #   counter passes (tools/pmc_sq.txt, one --pmc line per run) and the FETCH_SIZE / WRITE_SIZE passes, the DCN A/B per layer
 #   shape, the batch-1 frame trace, the PnP micro-benchmark.    usage: tools/refresh_round.sh <tag, e.g. r05> [quick]
 set -u
 TAG=${1:?usage: tools/refresh_round.sh <tag> [quick]}; shift
 R=$PWD; O=$R/gpurun_out/$TAG; rm -rf $O; mkdir -p $O; export TMPDIR=/tmp
 timeout 1500 python -m pytest tests -m gpu -q 2>&1 | tail -6 | tee $O/pytest_gpu.txt
-CP_BENCH_DETAIL=$O/bench_detail.json timeout 1200 python bench.py 2>$O/bench_default.err | tail -1 > $O/bench_default.json
+CP_BENCH_DETAIL=$O/bench_detail.json timeout 1200 python bench.py --full 2>$O/bench_default.err | tail -1 > $O/bench_default.json
 B="--no-cpu-baseline --no-latency --no-legs"
 cd /tmp
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python $R/bench.py --steps 10 --warmup 3 $B > $O/kt.log 2>&1
