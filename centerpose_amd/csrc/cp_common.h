@@ -200,7 +200,9 @@ int cp_launch_splitk_epilogue(const ConvParams& p, hipStream_t stream);
 // K steps (of 16 for the f32 kernels, 32 for f16x3) and output tiles of the launch cp_launch_conv[16] would make
 void cp_conv_geometry(const ConvParams& p, bool f16x3, int* tiles, int* nk);
 const char* cp_conv_variant_name(int v);
-#define CP_NUM_CONV_VARIANTS 43
+#define CP_NUM_CONV_VARIANTS 45
+#define CP_VARIANT_DECONV_F32 43  // deconv16.hip, exact f32
+#define CP_VARIANT_DECONV16 44    // deconv16.hip, f16x3
 #define CP_VARIANT_STRM16 41
 #define CP_VARIANT_LOWC1S 42
 #define CP_VARIANT_GRU 26
@@ -291,6 +293,24 @@ int cp_launch_lowc(int kind, const float* in, float* out, const void* w_hi, cons
 int cp_launch_lowc_fused(const float* in, float* out, const void* w0_hi, const void* w0_lo, const float* scale0, const float* shift0,
                          const void* w1_hi, const void* w1_lo, const float* scale1, const float* shift1, float bound_l, float bound_s,
                          const unsigned* in_amax, unsigned* out_amax, int B, int H, int W, int planes, hipStream_t s);
+// dense ConvTranspose2d(k=4, stride=2, pad=1) + per-channel affine (+ ReLU), four sub-pixel classes in one launch (deconv16.hip).
+// Weights packed by cp_launch_pack_deconv from PyTorch [Cin][Cout][4][4]: wf float32 and / or hi / lo binary16, each
+// [4][cp_deconv_cout_pad(Cout)][4*Cin]; inv[co] = 2^-e of the binary16 rows (f16x3 `scale` must carry it).  Cin % 32 == 0.
+struct DeconvLaunch {
+    const float* x;  // [B,H,W,Cin]
+    const float* wf;
+    const void* w_hi;
+    const void* w_lo;
+    const float* scale;  // [CoutPad] or nullptr
+    const float* shift;  // [CoutPad] or nullptr
+    float* out;          // [B,2H,2W,Cout]
+    const unsigned* in_amax;  // f16x3: the input's |max| slot (nullptr: operand used as is)
+    unsigned* out_amax;       // the output's |max| slot or nullptr
+    int B, H, W, Cin, Cout, relu, f16x3;
+};
+int cp_deconv_cout_pad(int Cout);
+int cp_launch_pack_deconv(const float* w, float* wf, void* hi, void* lo, float* inv, int Cin, int Cout, hipStream_t s);
+int cp_launch_deconv(const DeconvLaunch& l, hipStream_t s);
 #define CP_PREC_F32 0
 #define CP_PREC_F16X3 1
 
@@ -298,6 +318,8 @@ int cp_launch_lowc_fused(const float* in, float* out, const void* w0_hi, const v
 int cp_launch_nchw_to_nhwc(const float* in, float* out, int B, int C, int H, int W, int Cpad, hipStream_t s);
 int cp_launch_nhwc_to_nchw(const float* in, float* out, int B, int C, int H, int W, int ldi, hipStream_t s);
 int cp_launch_maxpool2(const float* in, float* out, int B, int H, int W, int C, hipStream_t s);
+// MaxPool2d(3, stride 2, pad 1) (resnet_dcn.py PoseResNet.maxpool): padding is -inf; optional |max| slot of the output
+int cp_launch_maxpool3s2(const float* in, float* out, int B, int H, int W, int C, unsigned* out_amax, hipStream_t s);
 // the element-wise producers below take an optional |max| slot for their output (ConvParams::out_amax)
 // depth-wise ConvTranspose2d(k=2f, stride=f, pad=f/2) of `in` [B,H,W,C] plus `add` [B,fH,fW,C] -> out
 int cp_launch_upsample_add(const float* in, const float* w, const float* add, float* out, int B, int H, int W,

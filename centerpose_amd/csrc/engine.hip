@@ -141,6 +141,17 @@ struct DeformW {
     ConvW main;    // DCN weight, scale/shift = folded bias + BN
 };
 
+// dense ConvTranspose2d(k=4, s=2, p=1) + folded BatchNorm of a resdcn deconv stage (deconv16.hip)
+struct DeconvW {
+    float* wf = nullptr;       // float32 sub-kernels [4][CoutPad][4*Cin]
+    void* hi = nullptr;        // split-f16 copies, rows times 2^e per output channel
+    void* lo = nullptr;
+    float* scale = nullptr;    // [CoutPad] folded BatchNorm scale
+    float* scale16 = nullptr;  // scale * 2^-e
+    float* shift = nullptr;
+    int Cin = 0, Cout = 0;
+};
+
 struct HeadW {
     std::string name;
     int classes = 0;
@@ -157,6 +168,7 @@ struct HeadW {
 struct cp_model {
     std::string arch;
     bool gru = false, tracking = false, finalized = false, hourglass = false;
+    int resnet = 0;  // resdcn_N: N (resnet_dcn.py), else 0
     int precision = g_default_precision;
     int head_conv = 256;
     std::vector<std::pair<std::string, int>> heads;
@@ -164,6 +176,7 @@ struct cp_model {
     std::map<std::string, ConvW> convs;
     std::map<std::string, DeformW> deforms;
     std::map<std::string, float*> ups;
+    std::map<std::string, DeconvW> deconvs;
     std::vector<HeadW> headw;
     // every fused head of the model in ONE launch (they all read the same feature map): the heads' 3x3 fragments,
     // scale / shift, 1x1 fragments and w2_inv tables concatenated along N (ConvParams::fuse_ngroups)
@@ -396,16 +409,20 @@ struct Packer {
             // the outer project of a 2-level tree never influences the output (Tree.forward :214-217)
         }
     }
-    void deform(const std::string& p, int chi, int cho) {
+    // DCN (dcn_v2.py: weight, bias, conv_offset_mask) + BatchNorm `bn`, stored under `key`; the DCN bias folds into the
+    // BatchNorm's shift
+    void deform(const std::string& key, const std::string& dcn, const std::string& bn, int chi, int cho) {
         DeformW d;
-        d.offset = pack({p + ".conv.conv_offset_mask.weight"}, 27, chi, 3, 3);
-        if (const auto* b = get(p + ".conv.conv_offset_mask.bias", 27)) set_affine(d.offset, nullptr, *b);
-        d.main = pack({p + ".conv.weight"}, cho, chi, 3, 3);
-        const auto* bias = get(p + ".conv.bias", cho);
+        d.offset = pack({dcn + ".conv_offset_mask.weight"}, 27, chi, 3, 3);
+        if (const auto* b = get(dcn + ".conv_offset_mask.bias", 27)) set_affine(d.offset, nullptr, *b);
+        d.main = pack({dcn + ".weight"}, cho, chi, 3, 3);
+        const auto* bias = get(dcn + ".bias", cho);
         std::vector<float> sc, sh;
-        if (bias && bn_fold(p + ".actf.0", cho, bias, sc, sh)) set_affine(d.main, &sc, sh);
-        m->deforms[p] = d;
+        if (bias && bn_fold(bn, cho, bias, sc, sh)) set_affine(d.main, &sc, sh);
+        m->deforms[key] = d;
     }
+    // DLA's DeformConv (pose_dla_dcn.py:377-389): DCN at `.conv`, BatchNorm at `.actf.0`
+    void deform(const std::string& p, int chi, int cho) { deform(p, p + ".conv", p + ".actf.0", chi, cho); }
     void ida(const std::string& p, int o, const std::vector<int>& channels, const std::vector<int>& up_f) {
         for (size_t i = 1; i < channels.size(); ++i) {
             const std::string k = std::to_string(i);
@@ -469,6 +486,101 @@ struct Packer {
             m->headw.push_back(hw);
         }
         group_heads();
+    }
+
+    // ---- PoseResNet with DCN up-sampling (resnet_dcn.py) ----
+    // depth -> (Bottleneck?, blocks per layer): resnet_spec
+    static bool resnet_spec(int depth, bool* bottleneck, int* blocks) {
+        static const int spec[5][5] = {{18, 2, 2, 2, 2}, {34, 3, 4, 6, 3}, {50, 3, 4, 6, 3}, {101, 3, 4, 23, 3}, {152, 3, 8, 36, 3}};
+        for (const auto& r : spec)
+            if (r[0] == depth) {
+                *bottleneck = depth >= 50;
+                for (int i = 0; i < 4; ++i) blocks[i] = r[i + 1];
+                return true;
+            }
+        return false;
+    }
+    void run_resnet() {
+        bool bott = false;
+        int blocks[4] = {0, 0, 0, 0};
+        if (!resnet_spec(m->resnet, &bott, blocks)) {
+            status = CP_ERR_STATE;
+            missing = "resnet depth";
+            return;
+        }
+        conv_bn("conv1", "conv1", "bn1", 64, 3, 7, 4);
+        int inp = 64;
+        const int exp = bott ? 4 : 1;
+        for (int l = 0; l < 4; ++l) {
+            const int planes = 64 << l, stride = l ? 2 : 1;
+            for (int b = 0; b < blocks[l]; ++b) {
+                const std::string p = "layer" + std::to_string(l + 1) + "." + std::to_string(b);
+                if (bott) {
+                    conv_bn(p + ".conv1", p + ".conv1", p + ".bn1", planes, inp, 1);
+                    conv_bn(p + ".conv2", p + ".conv2", p + ".bn2", planes, planes, 3);
+                    conv_bn(p + ".conv3", p + ".conv3", p + ".bn3", planes * exp, planes, 1);
+                } else {
+                    conv_bn(p + ".conv1", p + ".conv1", p + ".bn1", planes, inp, 3);
+                    conv_bn(p + ".conv2", p + ".conv2", p + ".bn2", planes, planes, 3);
+                }
+                if (b == 0 && (stride != 1 || inp != planes * exp))
+                    conv_bn(p + ".downsample", p + ".downsample.0", p + ".downsample.1", planes * exp, inp, 1);
+                inp = planes * exp;
+            }
+        }
+        static const int filters[3] = {256, 128, 64};
+        for (int i = 0; i < 3; ++i) {
+            const int c = filters[i];
+            const std::string fc = "deconv_layers." + std::to_string(6 * i);
+            deform(fc, fc, "deconv_layers." + std::to_string(6 * i + 1), inp, c);
+            deconv_bn("deconv_layers." + std::to_string(6 * i + 3), "deconv_layers." + std::to_string(6 * i + 4), c, c);
+            inp = c;
+        }
+        const int hc = m->head_conv;
+        for (auto& h : m->heads) {
+            HeadW hw;
+            hw.name = h.first;
+            hw.classes = h.second;
+            hw.c0 = pack({h.first + ".0.weight"}, hc, 64, 3, 3);
+            if (const auto* b = get(h.first + ".0.bias", hc)) set_affine(hw.c0, nullptr, *b);
+            hw.c1 = pack({h.first + ".2.weight"}, h.second, hc, 1, 1);
+            if (const auto* b = get(h.first + ".2.bias", h.second)) set_affine(hw.c1, nullptr, *b);
+            m->headw.push_back(hw);
+        }
+    }
+    // ConvTranspose2d(cin, cout, 4, 2, 1, bias=False) + BatchNorm2d: the four sub-pixel kernels in both precisions
+    void deconv_bn(const std::string& up, const std::string& bn, int cin, int cout) {
+        DeconvW d;
+        d.Cin = cin;
+        d.Cout = cout;
+        const auto* w = get(up + ".weight", (size_t)cin * cout * 16);
+        std::vector<float> sc, sh;
+        if (!w || !bn_fold(bn, cout, nullptr, sc, sh)) return;
+        const int cpad = cp_deconv_cout_pad(cout);
+        const size_t n = (size_t)4 * cpad * 4 * cin;
+        d.wf = dev_alloc(n, false);
+        d.hi = dev_alloc((n + 1) / 2, false);
+        d.lo = dev_alloc((n + 1) / 2, false);
+        d.scale16 = dev_alloc(cpad);
+        sc.resize(cpad, 1.f);
+        sh.resize(cpad, 0.f);
+        d.scale = upload(sc);
+        d.shift = upload(sh);
+        if (!d.wf || !d.hi || !d.lo || !d.scale16 || !d.scale || !d.shift) return;
+        // the raw PyTorch-layout weight and the 2^-e rows are only needed while packing: freed right after
+        float *tmp = nullptr, *inv = nullptr;
+        if (!hip_ok(hipMalloc((void**)&tmp, w->size() * sizeof(float))) || !hip_ok(hipMalloc((void**)&inv, cpad * sizeof(float)))) {
+            (void)hipFree(tmp);
+            return;
+        }
+        int rc = hipMemcpy(tmp, w->data(), w->size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess ? CP_OK : CP_ERR_LAUNCH;
+        if (rc == CP_OK) rc = cp_launch_pack_deconv(tmp, d.wf, d.hi, d.lo, inv, cin, cout, nullptr);
+        if (rc == CP_OK) rc = cp_launch_scale16(d.scale, inv, d.scale16, cpad, nullptr);
+        hip_ok(hipDeviceSynchronize());
+        (void)hipFree(tmp);
+        (void)hipFree(inv);
+        if (rc != CP_OK && status == CP_OK) status = rc;
+        m->deconvs[up] = d;
     }
 
     // concatenate the fused heads' operands for the grouped launch (all heads must be fusable and of one shape)
@@ -1237,6 +1349,109 @@ struct Fwd {
         }
     }
 
+    // ---- PoseResNet forward (resnet_dcn.py: PoseResNet.forward, BasicBlock / Bottleneck.forward) ----
+    Tensor deconv(const std::string& p, const Tensor& x) {
+        const DeconvW& d = m->deconvs.at(p);
+        Tensor o = make(d.Cout, 2 * x.H, 2 * x.W);
+        if (m->dry) return o;
+        DeconvLaunch l;
+        std::memset(&l, 0, sizeof(l));
+        l.f16x3 = m->precision == CP_PREC_F16X3;
+        l.x = x.ptr();
+        l.wf = d.wf;
+        l.w_hi = d.hi;
+        l.w_lo = d.lo;
+        l.scale = l.f16x3 ? d.scale16 : d.scale;
+        l.shift = d.shift;
+        l.out = o.ptr();
+        l.in_amax = x.amax;
+        l.out_amax = o.amax;
+        l.B = B;
+        l.H = x.H;
+        l.W = x.W;
+        l.Cin = x.C;
+        l.Cout = d.Cout;
+        l.relu = 1;
+        if (x.C != d.Cin) {
+            chk(fail(CP_ERR_INVALID, "deconv: channel mismatch"));
+            return o;
+        }
+        if (m->profile) {
+            cp_model::ProfRec r;
+            r.variant = l.f16x3 ? CP_VARIANT_DECONV16 : CP_VARIANT_DECONV_F32;
+            r.role = CP_ROLE_DECONV;
+            const double M = (double)B * x.H * x.W;  // rows of one sub-pixel class
+            r.flops = 2.0 * 4 * M * d.Cout * 4.0 * d.Cin;
+            r.bytes = 4.0 * (M * d.Cin + 4 * M * d.Cout + 16.0 * d.Cin * d.Cout);
+            r.M = (int)(4 * M); r.N = d.Cout; r.K = 4 * d.Cin; r.kh = 4; r.stride = 2;
+            r.e0 = m->get_event();
+            r.e1 = m->get_event();
+            (void)hipEventRecord(r.e0, s);
+            chk(cp_launch_deconv(l, s));
+            (void)hipEventRecord(r.e1, s);
+            m->prof.push_back(r);
+        } else {
+            chk(cp_launch_deconv(l, s));
+        }
+        return o;
+    }
+    Tensor maxpool3(const Tensor& x) {
+        Tensor o = make(x.C, (x.H - 1) / 2 + 1, (x.W - 1) / 2 + 1);
+        if (!m->dry) chk(cp_launch_maxpool3s2(x.ptr(), o.ptr(), B, x.H, x.W, x.C, o.amax, s));
+        return o;
+    }
+    Tensor res_block(const std::string& p, const Tensor& x, int stride, bool bott) {
+        Tensor sk;
+        const Tensor* res = &x;
+        if (m->convs.count(p + ".downsample")) {
+            sk = conv(cw(p + ".downsample"), {&x}, stride, 0, CP_ACT_NONE);
+            res = &sk;
+        }
+        if (bott) {
+            Tensor a = conv(cw(p + ".conv1"), {&x}, 1, 0, CP_ACT_RELU);
+            Tensor b = conv(cw(p + ".conv2"), {&a}, stride, 1, CP_ACT_RELU);
+            a = Tensor();
+            return conv(cw(p + ".conv3"), {&b}, 1, 0, CP_ACT_RELU, res);  // relu(bn3(conv3) + residual)
+        }
+        Tensor a = conv(cw(p + ".conv1"), {&x}, stride, 1, CP_ACT_RELU);
+        return conv(cw(p + ".conv2"), {&a}, 1, 1, CP_ACT_RELU, res);  // relu(bn2(conv2) + residual)
+    }
+    void run_resnet(int H, int W, const float* images, float* const* head_out, int sigmoid_hm) {
+        bool bott = false;
+        int blocks[4] = {0, 0, 0, 0};
+        Packer::resnet_spec(m->resnet, &bott, blocks);
+        init_slots();
+        Tensor x;
+        {
+            Tensor in = to_nhwc(images, 3, 4, H, W);
+            Tensor c1 = conv(cw("conv1"), {&in}, 2, 3, CP_ACT_RELU);
+            in = Tensor();
+            x = maxpool3(c1);
+        }
+        tap("maxpool", x);
+        for (int l = 0; l < 4; ++l) {
+            const std::string ln = "layer" + std::to_string(l + 1);
+            for (int b = 0; b < blocks[l]; ++b) x = res_block(ln + "." + std::to_string(b), x, b == 0 && l ? 2 : 1, bott);
+            tap(ln, x);
+        }
+        for (int i = 0; i < 3; ++i) {
+            const std::string fc = "deconv_layers." + std::to_string(6 * i);
+            x = deform(fc, x);
+            tap("deconv_layers." + std::to_string(6 * i + 2), x);
+            x = deconv("deconv_layers." + std::to_string(6 * i + 3), x);
+            tap("deconv_layers." + std::to_string(6 * i + 5), x);
+        }
+        for (size_t i = 0; i < m->headw.size(); ++i) {
+            const HeadW& hw = m->headw[i];
+            const bool sg = sigmoid_hm && (hw.name == "hm" || hw.name == "hm_hp");
+            role = CP_ROLE_HEAD;
+            Tensor hid = conv(hw.c0, {&x}, 1, 1, CP_ACT_RELU);
+            role = CP_ROLE_HEAD_FINAL;
+            conv(hw.c1, {&hid}, 1, 0, sg ? CP_ACT_SIGMOID : CP_ACT_NONE, nullptr, nullptr, 0,
+                 m->dry ? (float*)0x1000 : head_out[i], hw.classes);
+        }
+    }
+
     void run(int H, int W, const float* images, const float* pre_img, const float* pre_hm, const float* pre_hm_hp,
              float* const* head_out, int sigmoid_hm) {
         init_slots();
@@ -1556,6 +1771,7 @@ int forward_impl(cp_model* m, hipStream_t stream, int B, int H, int W, const flo
     m->status = CP_OK;
     Fwd f{m, B, stream};
     if (m->hourglass) f.run_hourglass(H, W, images, head_out, sigmoid_hm);
+    else if (m->resnet) f.run_resnet(H, W, images, head_out, sigmoid_hm);
     else f.run(H, W, images, pre_img, pre_hm, pre_hm_hp, head_out, sigmoid_hm);
     if (!dry && m->arena.overflow)
         return fail(CP_ERR_INVALID, "workspace too small: " + std::to_string(ws_bytes) + " bytes given, this launch sequence peaks at " +
@@ -1579,15 +1795,21 @@ int cp_model_create(const char* arch, int tracking_task, int num_heads, const ch
                     const int* head_classes, int head_conv, cp_model** out) {
     if (!arch || !out || num_heads < 1 || !head_names || !head_classes) return fail(CP_ERR_INVALID, "null argument");
     std::string a(arch);
-    if (a != "dla_34" && a != "dlav1_34" && a != "hourglass")
-        return fail(CP_ERR_INVALID, "arch must be dla_34, dlav1_34 or hourglass");
+    int resnet = 0;
+    for (int d : {18, 34, 50, 101, 152})
+        if (a == "resdcn_" + std::to_string(d)) resnet = d;
+    if (a != "dla_34" && a != "dlav1_34" && a != "hourglass" && !resnet)
+        return fail(CP_ERR_INVALID, "arch must be dla_34, dlav1_34, hourglass or resdcn_18|34|50|101|152");
     if (a == "hourglass" && tracking_task)
         return fail(CP_ERR_INVALID, "the hourglass takes a single frame (large_hourglass.py:266)");
+    if (resnet && tracking_task)
+        return fail(CP_ERR_INVALID, a + " takes a single frame (resnet_dcn.py: PoseResNet.forward)");
     if (head_conv <= 0 || head_conv % 32 != 0) return fail(CP_ERR_INVALID, "head_conv must be a positive multiple of 32");
     cp_model* m = new cp_model();
     m->arch = a;
     m->gru = (a == "dlav1_34");
     m->hourglass = (a == "hourglass");
+    m->resnet = resnet;
     m->tracking = tracking_task != 0;
     m->head_conv = head_conv;
     for (int i = 0; i < num_heads; ++i) m->heads.push_back({head_names[i], head_classes[i]});
@@ -1626,6 +1848,7 @@ int cp_model_finalize(cp_model* m) {
     if (m->finalized) return CP_OK;
     Packer pk{m};
     if (m->hourglass) pk.run_hourglass();
+    else if (m->resnet) pk.run_resnet();
     else pk.run();
     pk.hip_ok(hipDeviceSynchronize());
     if (pk.status != CP_OK)
@@ -1698,7 +1921,7 @@ const char* cp_kernel_variant_name(int v) { return cp_conv_variant_name(v); }
 
 const char* cp_role_name(int role) {
     static const char* names[CP_NUM_ROLES] = {"conv", "conv1x1", "dcn", "dcn_offset", "head", "head_final", "gru", "lowc",
-                                              "decode"};
+                                              "decode", "deconv"};
     return (role >= 0 && role < CP_NUM_ROLES) ? names[role] : "?";
 }
 
@@ -1871,6 +2094,63 @@ size_t cp_conv2d_workspace_bytes(int Cin, int Cout, int KH, int KW) {
     // (+ the fragment-ordered copies of the binary16 weights)
     return align_up(kpad * cpad * sizeof(float), 256) + 4 * align_up(kpad * cpad * 2, 256) +
            3 * align_up(cpad * sizeof(float), 256) + (size_t)CP_AMAX_SUB * CP_AMAX_STRIDE * sizeof(unsigned);
+}
+
+size_t cp_conv_transpose2d_workspace_bytes(int Cin, int Cout) {
+    const size_t cpad = (size_t)cp_deconv_cout_pad(Cout > 0 ? Cout : 1), n = 4 * cpad * 4 * (size_t)(Cin > 0 ? Cin : 0);
+    // float32 sub-kernels + two binary16 copies + 2^-e per row + scale * 2^-e + the input's |max| slot
+    return align_up(n * 4, 256) + 2 * align_up(n * 2, 256) + 2 * align_up(cpad * 4, 256) +
+           (size_t)CP_AMAX_SUB * CP_AMAX_STRIDE * sizeof(unsigned);
+}
+
+int cp_conv_transpose2d_nhwc(cp_stream_t stream, const float* x, const float* w, const float* scale, const float* shift, float* out,
+                             int B, int H, int W, int Cin, int Cout, int act, void* workspace, size_t workspace_bytes) {
+    if (!x || !w || !out || !workspace) return fail(CP_ERR_INVALID, "null argument");
+    if (B < 1 || H < 1 || W < 1 || Cout < 1) return fail(CP_ERR_INVALID, "empty shape");
+    if (Cin % 32) return fail(CP_ERR_INVALID, "Cin must be a multiple of 32");
+    if (act != CP_ACT_NONE && act != CP_ACT_RELU) return fail(CP_ERR_INVALID, "act must be 0 (none) or 1 (relu)");
+    if (workspace_bytes < cp_conv_transpose2d_workspace_bytes(Cin, Cout)) return fail(CP_ERR_INVALID, "workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t cpad = (size_t)cp_deconv_cout_pad(Cout), n = 4 * cpad * 4 * (size_t)Cin;
+    char* q = (char*)workspace;
+    float* wf = (float*)q;
+    q += align_up(n * 4, 256);
+    void* hi = q;
+    q += align_up(n * 2, 256);
+    void* lo = q;
+    q += align_up(n * 2, 256);
+    float* inv = (float*)q;
+    q += align_up(cpad * 4, 256);
+    float* sc16 = (float*)q;
+    q += align_up(cpad * 4, 256);
+    unsigned* slot = (unsigned*)q;
+    DeconvLaunch l;
+    std::memset(&l, 0, sizeof(l));
+    l.f16x3 = g_default_precision == CP_PREC_F16X3;
+    int rc = cp_launch_pack_deconv(w, l.f16x3 ? nullptr : wf, l.f16x3 ? hi : nullptr, l.f16x3 ? lo : nullptr, inv, Cin, Cout, s);
+    if (rc == CP_OK && l.f16x3) {
+        // range-safe operands as in cp_conv2d_nhwc: per-channel weight scale (folded into scale16), per-tensor activation scale
+        if (hipMemsetAsync(slot, 0, (size_t)CP_AMAX_SUB * CP_AMAX_STRIDE * sizeof(unsigned), s) != hipSuccess) return CP_ERR_LAUNCH;
+        rc = cp_launch_scale16(scale, inv, sc16, Cout, s);
+        if (rc == CP_OK) rc = cp_launch_absmax(x, (size_t)B * H * W * Cin, slot, s);
+    }
+    if (rc != CP_OK) return fail(rc, "deconv weight packing failed");
+    l.x = x;
+    l.wf = wf;
+    l.w_hi = hi;
+    l.w_lo = lo;
+    l.scale = l.f16x3 ? sc16 : scale;
+    l.shift = shift;
+    l.out = out;
+    l.in_amax = l.f16x3 ? slot : nullptr;
+    l.B = B;
+    l.H = H;
+    l.W = W;
+    l.Cin = Cin;
+    l.Cout = Cout;
+    l.relu = act == CP_ACT_RELU;
+    rc = cp_launch_deconv(l, s);
+    return rc == CP_OK ? CP_OK : fail(rc, "deconv launch failed (shape too large for 32-bit offsets?)");
 }
 
 int cp_conv2d_nhwc(cp_stream_t stream, const float* x, const float* w, const float* scale, const float* shift,

@@ -83,6 +83,42 @@ __global__ void maxpool2_kernel(const float* __restrict__ in, float* __restrict_
     }
 }
 
+// MaxPool2d(kernel 3, stride 2, padding 1) (resnet_dcn.py: PoseResNet.maxpool); padded taps count as -inf, so every window
+// holds at least its centre tap.  The output's |max| goes to its slot (the stem's input to layer1 is an f16x3 operand).
+__global__ void maxpool3s2_kernel(const float* __restrict__ in, float* __restrict__ out, int B, int H, int W, int C4,
+                                  unsigned* __restrict__ out_amax) {
+    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+    const size_t total = (size_t)B * Ho * Wo * C4;
+    const float4* in4 = reinterpret_cast<const float4*>(in);
+    float4* out4 = reinterpret_cast<float4*>(out);
+    float amax = 0.f;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int c = (int)(i % C4);
+        size_t t = i / C4;
+        const int wo = (int)(t % Wo);
+        t /= Wo;
+        const int ho = (int)(t % Ho);
+        const int b = (int)(t / Ho);
+        float4 r = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+        for (int dy = -1; dy <= 1; ++dy) {
+            const int y = 2 * ho + dy;
+            if ((unsigned)y >= (unsigned)H) continue;
+            for (int dx = -1; dx <= 1; ++dx) {
+                const int x = 2 * wo + dx;
+                if ((unsigned)x >= (unsigned)W) continue;
+                const float4 v = in4[(((size_t)b * H + y) * W + x) * C4 + c];
+                r.x = fmaxf(r.x, v.x);
+                r.y = fmaxf(r.y, v.y);
+                r.z = fmaxf(r.z, v.z);
+                r.w = fmaxf(r.w, v.w);
+            }
+        }
+        out4[i] = r;
+        amax = fmaxf(amax, fmaxf(fmaxf(fabsf(r.x), fabsf(r.y)), fmaxf(fabsf(r.z), fabsf(r.w))));
+    }
+    if (out_amax) cp_amax_commit(out_amax, amax);
+}
+
 // Depth-wise ConvTranspose2d(C, C, k=2f, stride=f, padding=f/2, groups=C) + add (IDAUp.forward,
 // pose_dla_dcn.py:411-417).  out[y,x,c] = add[y,x,c] + sum_{ky,kx} in[(y+p-ky)/f, (x+p-kx)/f, c] * w[c,ky,kx]
 // over taps with (y+p-ky) % f == 0 and the source inside the image: exactly 2x2 taps per output pixel.
@@ -549,6 +585,13 @@ int cp_launch_maxpool2(const float* in, float* out, int B, int H, int W, int C, 
     if (C % 4 || H % 2 || W % 2) return CP_ERR_INVALID;
     hipLaunchKernelGGL(maxpool2_kernel, dim3(grid_for((size_t)B * (H / 2) * (W / 2) * (C / 4))), dim3(TPB), 0, s, in,
                        out, B, H, W, C / 4);
+    return check();
+}
+
+int cp_launch_maxpool3s2(const float* in, float* out, int B, int H, int W, int C, unsigned* out_amax, hipStream_t s) {
+    if (C % 4 || H < 1 || W < 1) return CP_ERR_INVALID;
+    const size_t n = (size_t)B * ((H - 1) / 2 + 1) * ((W - 1) / 2 + 1) * (C / 4);
+    hipLaunchKernelGGL(maxpool3s2_kernel, dim3(grid_for(n)), dim3(TPB), 0, s, in, out, B, H, W, C / 4, out_amax);
     return check();
 }
 

@@ -72,6 +72,9 @@ def lib():
     _sig(L.cp_model_forward_tap, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
          c_void_p, ctypes.POINTER(c_void_p), c_int, c_void_p, c_size_t, c_char_p, c_void_p, ctypes.POINTER(c_int))
     _sig(L.cp_conv2d_workspace_bytes, c_size_t, c_int, c_int, c_int, c_int)
+    _sig(L.cp_conv_transpose2d_workspace_bytes, c_size_t, c_int, c_int)
+    _sig(L.cp_conv_transpose2d_nhwc, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t)
     _sig(L.cp_conv2d_nhwc, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
          *([c_int] * 10), c_void_p, c_size_t)
     _sig(L.cp_decode_workspace_bytes, c_size_t, c_int, c_int)
@@ -142,7 +145,8 @@ def exported_symbols():
             "cp_model_profile_roles", "cp_role_name", "cp_pnp_from_post_workspace_bytes", "cp_pnp_from_post", "cp_resize_u8",
             "cp_abi_version", "cp_num_kernel_variants", "cp_num_roles", "cp_track_state_bytes", "cp_track_workspace_bytes",
             "cp_track_reset", "cp_track_step", "cp_track_status", "cp_linear_assignment", "cp_decode_tiled_workspace_bytes",
-            "cp_decode_tiled", "cp_box_iou", "cp_box_eval"]
+            "cp_decode_tiled", "cp_box_iou", "cp_box_eval", "cp_conv_transpose2d_workspace_bytes",
+            "cp_conv_transpose2d_nhwc"]
 
 
 def _check(rc, what):
@@ -206,6 +210,26 @@ def conv2d_nhwc(x, w, scale=None, shift=None, residual=None, stride=1, pad=0, ac
     rc = L.cp_conv2d_nhwc(_stream(), _ptr(x), _ptr(w), _ptr(scale), _ptr(shift), _ptr(residual), _ptr(out),
                           B, H, W, Cin, Cout, KH, KW, stride, pad, act, _ptr(ws), nbytes)
     _check(rc, "cp_conv2d_nhwc")
+    return out
+
+
+def conv_transpose2d(x, w, scale=None, shift=None, act=0):
+    """x [B,H,W,Cin] NHWC, w [Cin,Cout,4,4] (ConvTranspose2d(k=4, stride=2, padding=1) layout) -> [B,2H,2W,Cout] NHWC,
+    y = act(deconv(x) * scale + shift); act 0 none, 1 relu.  Precision: set_default_precision."""
+    L = lib()
+    x, w = _dev(x), _dev(w)
+    B, H, W, Cin = x.shape
+    if tuple(w.shape[2:]) != (4, 4) or w.shape[0] != Cin:
+        raise RuntimeError("conv_transpose2d: weight must be [Cin, Cout, 4, 4], got %s" % (tuple(w.shape),))
+    Cout = w.shape[1]
+    out = torch.empty(B, 2 * H, 2 * W, Cout, device=x.device, dtype=torch.float32)
+    nbytes = L.cp_conv_transpose2d_workspace_bytes(Cin, Cout)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    scale = _dev(scale) if scale is not None else None
+    shift = _dev(shift) if shift is not None else None
+    rc = L.cp_conv_transpose2d_nhwc(_stream(), _ptr(x), _ptr(w), _ptr(scale), _ptr(shift), _ptr(out),
+                                    B, H, W, Cin, Cout, act, _ptr(ws), nbytes)
+    _check(rc, "cp_conv_transpose2d_nhwc")
     return out
 
 
@@ -787,7 +811,7 @@ def track_record_to_dict(r, opt=None):
 
 
 class HipModel(object):
-    """Device-resident DLA-34 / DLA-34+ConvGRU network built from a reference-format state dict."""
+    """Device-resident DLA-34 / DLA-34+ConvGRU / hourglass / resdcn_N network built from a reference-format state dict."""
 
     def __init__(self, arch, heads, state_dict, tracking_task=False, head_conv=256, precision=None):
         L = lib()

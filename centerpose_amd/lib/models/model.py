@@ -12,7 +12,7 @@ import torch
 from centerpose_amd import hip as _hip
 from centerpose_amd import synth as _synth
 
-_SUPPORTED = ('dla', 'dlav1', 'hourglass')  # model.py:16-23: the other factories are not named by any benchmark config
+_SUPPORTED = ('dla', 'dlav1', 'hourglass', 'resdcn')  # model.py:16-23: the other factories are not named by any benchmark config
 
 
 class HipPoseNet(object):
@@ -22,6 +22,14 @@ class HipPoseNet(object):
     def __init__(self, arch, num_layers, heads, head_conv, opt=None):
         if arch == 'hourglass':  # get_large_hourglass_net ignores num_layers / head_conv (large_hourglass.py:311-313)
             self.arch = 'hourglass'
+        elif arch == 'resdcn':
+            if num_layers not in _synth.RESNET_SPEC:  # resnet_dcn.py: resnet_spec
+                raise NotImplementedError("resdcn depth must be one of %s; got %d" % (sorted(_synth.RESNET_SPEC), num_layers))
+            if opt is not None and getattr(opt, 'tracking_task', False):
+                raise NotImplementedError("resdcn_%d takes a single frame (resnet_dcn.py: PoseResNet.forward)" % num_layers)
+            if head_conv <= 0:
+                raise NotImplementedError("resdcn_%d: head_conv must be a positive multiple of 32, got %d" % (num_layers, head_conv))
+            self.arch = "resdcn_%d" % num_layers
         elif num_layers != 34:
             raise NotImplementedError("only DLA-34 is built (BASELINE configs); got %s_%d" % (arch, num_layers))
         else:
@@ -121,7 +129,11 @@ def _hourglass(num_layers, heads, head_conv=256, down_ratio=4, opt=None):
     return HipPoseNet('hourglass', num_layers, heads, head_conv, opt)
 
 
-_model_factory = {'dla': _dla, 'dlav1': _dlav1, 'hourglass': _hourglass}
+def _resdcn(num_layers, heads, head_conv=64, down_ratio=4, opt=None):
+    return HipPoseNet('resdcn', num_layers, heads, head_conv, opt)
+
+
+_model_factory = {'dla': _dla, 'dlav1': _dlav1, 'hourglass': _hourglass, 'resdcn': _resdcn}
 
 
 def create_model(arch, heads, head_conv, opt=None):

@@ -146,10 +146,64 @@ def hourglass_param_spec(heads=None, nstack=2):
     return s
 
 
+RESNET_SPEC = {18: (False, [2, 2, 2, 2]), 34: (False, [3, 4, 6, 3]), 50: (True, [3, 4, 6, 3]),
+               101: (True, [3, 4, 23, 3]), 152: (True, [3, 8, 36, 3])}  # resnet_dcn.py: resnet_spec (True: Bottleneck)
+
+
+def resdcn_param_spec(depth, heads=None, head_conv=64):
+    """OrderedDict name -> shape of the reference ``PoseResNet`` state dict (resnet_dcn.py, DCN up-sampling)."""
+    heads = heads or HEADS_POSE
+    bottleneck, blocks = RESNET_SPEC[depth]
+    exp = 4 if bottleneck else 1
+    s = OrderedDict()
+    s["conv1.weight"] = (64, 3, 7, 7)
+    _bn(s, "bn1", 64)
+    inp = 64
+    for li, n in enumerate(blocks):
+        planes, stride = 64 << li, (2 if li else 1)
+        for b in range(n):
+            p = "layer%d.%d" % (li + 1, b)
+            if bottleneck:
+                s[p + ".conv1.weight"] = (planes, inp, 1, 1)
+                _bn(s, p + ".bn1", planes)
+                s[p + ".conv2.weight"] = (planes, planes, 3, 3)
+                _bn(s, p + ".bn2", planes)
+                s[p + ".conv3.weight"] = (planes * exp, planes, 1, 1)
+                _bn(s, p + ".bn3", planes * exp)
+            else:
+                s[p + ".conv1.weight"] = (planes, inp, 3, 3)
+                _bn(s, p + ".bn1", planes)
+                s[p + ".conv2.weight"] = (planes, planes, 3, 3)
+                _bn(s, p + ".bn2", planes)
+            if b == 0 and (stride != 1 or inp != planes * exp):
+                s[p + ".downsample.0.weight"] = (planes * exp, inp, 1, 1)
+                _bn(s, p + ".downsample.1", planes * exp)
+            inp = planes * exp
+    for i, c in enumerate((256, 128, 64)):
+        fc = "deconv_layers.%d" % (6 * i)
+        s[fc + ".weight"] = (c, inp, 3, 3)
+        s[fc + ".bias"] = (c,)
+        s[fc + ".conv_offset_mask.weight"] = (27, inp, 3, 3)
+        s[fc + ".conv_offset_mask.bias"] = (27,)
+        _bn(s, "deconv_layers.%d" % (6 * i + 1), c)
+        s["deconv_layers.%d.weight" % (6 * i + 3)] = (c, c, 4, 4)
+        _bn(s, "deconv_layers.%d" % (6 * i + 4), c)
+        inp = c
+    for h, classes in heads.items():
+        s[h + ".0.weight"] = (head_conv, 64, 3, 3)
+        s[h + ".0.bias"] = (head_conv,)
+        s[h + ".2.weight"] = (classes, head_conv, 1, 1)
+        s[h + ".2.bias"] = (classes,)
+    return s
+
+
 def param_spec(arch="dla_34", heads=None, tracking=False, head_conv=256):
-    """OrderedDict name -> shape of the reference state dict for 'dla_34' / 'dlav1_34' (DLASeg) / 'hourglass'."""
+    """OrderedDict name -> shape of the reference state dict for 'dla_34' / 'dlav1_34' (DLASeg) / 'hourglass' /
+    'resdcn_N' (PoseResNet)."""
     if arch == "hourglass":
         return hourglass_param_spec(heads)
+    if arch.startswith("resdcn_"):
+        return resdcn_param_spec(int(arch.split("_")[1]), heads, head_conv)
     base_arch = arch.split("_")[0]
     assert base_arch in ("dla", "dlav1"), arch
     heads = heads or (HEADS_TRACK if tracking else HEADS_POSE)
@@ -194,6 +248,14 @@ def param_spec(arch="dla_34", heads=None, tracking=False, head_conv=256):
     return s
 
 
+def abs_checksum(sd):
+    """Exactly rounded sum of |w| over the floating-point tensors of a state dict (math.fsum: independent of the
+    summation order, so of the machine and of torch's thread count)."""
+    import math
+
+    return math.fsum(math.fsum(v.detach().double().abs().reshape(-1).tolist()) for v in sd.values() if v.is_floating_point())
+
+
 def _gen(seed, name):
     g = torch.Generator(device="cpu")
     g.manual_seed((int(seed) * 1000003 + zlib.crc32(name.encode())) % (2 ** 63 - 1))
@@ -222,8 +284,10 @@ def load_scales(arch, tracking):
 
 
 def make_state_dict(arch="dla_34", heads=None, tracking=False, seed=DEFAULT_SEED, scales=None,
-                    head_conv=256):
+                    head_conv=None):
     """Random weights in the reference's ``state_dict`` format (float32 CPU tensors)."""
+    if head_conv is None:
+        head_conv = 64 if arch.startswith("resdcn_") else 256  # opts.py: the arch's default head_conv
     spec = param_spec(arch, heads, tracking, head_conv)
     if scales is None:
         scales = load_scales(arch, tracking)
@@ -232,6 +296,7 @@ def make_state_dict(arch="dla_34", heads=None, tracking=False, seed=DEFAULT_SEED
     final_hm_bias = {"%s.%d.bias" % (h, last) for h in heads_ if "hm" in h}
     if arch == "hourglass":  # heat[-1].bias.fill_(-2.19) on every stack (large_hourglass.py:246-247)
         final_hm_bias = {"%s.%d.1.bias" % (h, k) for h in heads_ if "hm" in h for k in range(2)}
+    resdcn = arch.startswith("resdcn_")
     sd = OrderedDict()
     for name, shape in spec.items():
         g = _gen(seed, name)
@@ -254,6 +319,19 @@ def make_state_dict(arch="dla_34", heads=None, tracking=False, seed=DEFAULT_SEED
                 t = torch.randn(shape, generator=g) * 0.1
         elif ".up_" in name:
             t = _bilinear_up(shape) * (torch.rand(shape, generator=g) * 0.2 + 0.9)
+        elif resdcn and shape[2] == 4:  # dense ConvTranspose2d(k=4, s=2): random (not fill_up_weights), every tap used
+            t = torch.randn(shape, generator=g) * math.sqrt(2.0 / (4 * shape[0]))  # 4 taps per input channel reach a pixel
+        elif resdcn:
+            fan_in = shape[1] * shape[2] * shape[3]
+            t = torch.randn(shape, generator=g) * math.sqrt(2.0 / fan_in)
+            last_conv = ".conv3.weight" if "layer" in name and RESNET_SPEC[int(arch.split("_")[1])][0] else ".conv2.weight"
+            if name.startswith("layer") and name.endswith(last_conv):
+                t = t * 0.25  # the residual branch that is ADDED: activations stay O(1) through 152 layers
+            elif name.endswith(".conv_offset_mask.weight"):
+                # offsets of O(1-3) pixels: the DCN gather is exercised off the grid (Bottleneck stacks end 4x wider)
+                t = t * (0.3 if RESNET_SPEC[int(arch.split("_")[1])][0] else 1.5)
+            elif shape[2] == 1 and name.split(".")[0] in heads_:
+                t = t * 0.7  # final 1x1 of a head: logits of std ~2 around the -2.19 bias
         else:  # conv weight, He-normal on fan_in
             fan_in = shape[1] * shape[2] * shape[3]
             t = torch.randn(shape, generator=g) * math.sqrt(2.0 / fan_in)

@@ -76,6 +76,7 @@ int cp_dcnv2_forward(cp_stream_t stream, const float* input, const float* weight
  *   detectors/object_pose.py:135-138).
  *
  * arch: "dla_34" (DLA-34 + DCNv2 up-sampling) or "dlav1_34" (+ ConvGRU + GroupNorm heads).
+ *       "resdcn_18|34|50|101|152": ResNet + three DCNv2 / ConvTranspose2d up-sampling stages (resnet_dcn.py), single frame.
  * heads: names/classes in the order of `opt.heads` (opts.py:394-426).
  * Parameters are fed one tensor at a time under the reference's state_dict names (HOST float32
  * pointers; `module.` prefixes are the caller's business as in model.py:43-48); finalize folds
@@ -141,7 +142,7 @@ int cp_model_set_precision(cp_model* m, int precision);
  * pair.  cp_model_profile_read drains them: out[v*4 + 0..3] = {launches, total milliseconds, total
  * algorithmic FLOPs (2*M*Cout*KH*KW*Cin), total algorithmic bytes (input + output + weights
  * [+ offsets/mask] [+ residual], float32)} per kernel variant v in [0, CP_NUM_KERNEL_VARIANTS). */
-#define CP_NUM_KERNEL_VARIANTS 43
+#define CP_NUM_KERNEL_VARIANTS 45
 int cp_num_kernel_variants(void); /* the value the LIBRARY was built with: size cp_model_profile_read's buffer from it */
 int cp_model_profile(cp_model* m, int enable);
 int cp_model_profile_read(cp_model* m, double* out, int num_variants);
@@ -158,7 +159,8 @@ const char* cp_kernel_variant_name(int v);
 #define CP_ROLE_GRU 6         /* ConvGRU convolutions (convGRU.py:32-39) */
 #define CP_ROLE_LOWC 7        /* stem / level0 / level1 direct kernels (f16x3 mode) */
 #define CP_ROLE_DECODE 8      /* cp_model_detect's decode launch (both kernels) */
-#define CP_NUM_ROLES 9
+#define CP_ROLE_DECONV 9      /* dense ConvTranspose2d(k=4, s=2) + BatchNorm + ReLU of the resdcn up-sampling */
+#define CP_NUM_ROLES 10
 int cp_num_roles(void);
 int cp_model_profile_roles(cp_model* m, double* out, int num_roles);
 const char* cp_role_name(int role);
@@ -172,6 +174,15 @@ size_t cp_conv2d_workspace_bytes(int Cin, int Cout, int KH, int KW);
 int cp_conv2d_nhwc(cp_stream_t stream, const float* x, const float* w, const float* scale, const float* shift,
                    const float* residual, float* out, int B, int H, int W, int Cin, int Cout, int KH, int KW,
                    int stride, int pad, int act, void* workspace, size_t workspace_bytes);
+
+/* Dense ConvTranspose2d(Cin, Cout, kernel 4, stride 2, padding 1, bias=False) followed by an optional per-channel affine
+ * and ReLU (resnet_dcn.py's deconv `up` layers with their BatchNorm): x [B,H,W,Cin] NHWC, w [Cin,Cout,4,4] (PyTorch
+ * layout, DEVICE), scale/shift [Cout] or NULL, out [B,2H,2W,Cout] NHWC.  act: 0 none, 1 relu.  Cin % 32 == 0.
+ * Precision follows cp_set_default_precision (exact f32 or f16x3 with range-safe scaling). */
+size_t cp_conv_transpose2d_workspace_bytes(int Cin, int Cout);
+int cp_conv_transpose2d_nhwc(cp_stream_t stream, const float* x, const float* w, const float* scale, const float* shift,
+                             float* out, int B, int H, int W, int Cin, int Cout, int act, void* workspace,
+                             size_t workspace_bytes);
 
 /* ------------------------------------------------------------------------------------------
  * Heat-map decode — replaces `object_pose_decode(..., Inference=True)` (models/decode.py:72-375,
