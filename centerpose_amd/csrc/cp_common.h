@@ -381,6 +381,17 @@ int cp_launch_dcn_generic(hipStream_t s, const float* x, const float* w, const f
                           const float* mask, float* out, int B, int C, int H, int W, int Co, int Ho, int Wo, int kh, int kw,
                           int sh, int sw, int ph, int pw, int dh, int dw, int dg);
 
+// ---- DCNv2 backward (dcn_bwd.hip): every shape the forward accepts; NCHW in and out, float32 ----
+struct DcnBwdArgs {
+    const float *input, *weight, *offset, *mask, *grad_output;
+    float *grad_input, *grad_offset, *grad_mask, *grad_weight, *grad_bias;
+    int B, C, H, W, Co, Ho, Wo, kh, kw, sh, sw, ph, pw, dh, dw, dg;
+};
+bool cp_dcn_backward_fast(int C, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int dg);
+size_t cp_dcn_backward_ws_bytes(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw, int dh,
+                                int dw, int dg);
+int cp_launch_dcn_backward(hipStream_t s, const DcnBwdArgs& a, void* ws);
+
 // ---- Objectron box metrics (box3d.hip; numerics in box3d_common.h) ----
 int cp_launch_box_iou(hipStream_t s, const double* a, const double* b, int n, double* iou);
 int cp_launch_box_eval(hipStream_t s, const double* pred3d, const double* gt3d, const double* pred2d, const double* mo2c,

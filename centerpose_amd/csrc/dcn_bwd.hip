@@ -1,0 +1,504 @@
+// DCNv2 backward (cp_dcnv2_backward): the input, offset, mask, weight and bias gradients of the modulated deformable
+// convolution, with the semantics of the reference's CUDA op (DCNv2/src/cuda/
+// dcn_v2_cuda.cu:206-340 and the col2im / col2im_coord kernels of dcn_v2_im2col_cuda.cu:197-327), quirks included.
+//
+// Index: k = tap * C + c throughout (tap = i * kw + j), against the reference's c * kh * kw + tap; the weight is
+// re-ordered once.  Launch sequence per call (all on the caller's stream, float32 arithmetic only):
+//   1. wt[co][k] = weight[co][c][tap]; go_t = grad_output as [B*Ho*Wo][Co]; fast path: x staged NHWC, the NHWC input
+//      gradient zeroed (generic path: the caller's grad_input zeroed).
+//   2. per chunk of `nb` images:
+//      gcol_kernel  grad_col[b][k][pix] = sum_co wt[co][k] * go[b][co][pix]  (v_mfma_f32_32x32x2_f32, co ascending);
+//      data kernel  per sample (b, group, tap, pixel), channels ascending in one lane:
+//                     grad_offset (h, w) = sum_c coord_weight(x) * grad_col * mask    (col2im_coord, :256-327)
+//                     grad_mask          = sum_c grad_col * bilinear(x)
+//                     grad_input        += bilinear weight * grad_col * mask at the in-image corners (col2im, :197-254)
+//                   fast path (dcn_bwd_halo_kernel): a 16 x 4 pixel patch x 9 taps per workgroup, the corner adds of a
+//                   channel chunk go to an LDS halo tile around the patch (float LDS atomics); only corners outside it
+//                   are global atomics; the tile is flushed with one global atomic per non-zero (cell, channel).
+//                   generic path (dcn_bwd_generic_kernel): one lane per sample, corner adds straight to NCHW global.
+//   3. wgrad_kernel  slab[s][co][k] = sum over the pixels of slab s of go_t[q][co] * col[q][k], col = the forward's
+//      modulated im2col computed in the B operand's lane (v_mfma_f32_32x32x2_f32, pixels ascending);
+//      wgrad_reduce_kernel sums the slabs in slab order; bias_kernel sums grad_output per channel in a fixed tree.
+//   4. fast path: the NHWC input gradient back to NCHW.
+// grad_offset, grad_mask, grad_weight and grad_bias are bitwise reproducible (every sum has a fixed order); grad_input
+// is summed with float atomics, so its last bits depend on arrival order.
+#include "igemm_common.h"
+
+#include <algorithm>
+
+namespace {
+
+constexpr int HALO_R = 4;                  // halo margin around the 16 x 4 patch (taps reach 1, offsets the rest)
+constexpr int PT_X = 16, PT_Y = 4;         // patch of output pixels per workgroup of the halo kernel
+constexpr int HX = PT_X + 2 * HALO_R + 1;  // + 1: the high corner of a sample at the margin's edge
+constexpr int HY = PT_Y + 2 * HALO_R + 1;
+constexpr int WG_COUT = 4;                 // 32-row Co tiles per wave of the weight-gradient kernel (at most)
+
+struct BwdP {
+    const float* x;     // [B,C,H,W]
+    const float* xh;    // [B,H,W,C] (fast path) or nullptr
+    const float* wt;    // [Co][T*C]
+    const float* off;   // [B, dg*2T, Ho, Wo]
+    const float* mask;  // [B, dg*T, Ho, Wo]
+    const float* go;    // [B, Co, Ho, Wo]
+    const float* go_t;  // [B*Ho*Wo, Co]
+    float* gcol;        // [nb][T*C][Ho*Wo]
+    float* gin;         // fast: [B,H,W,C]; generic: [B,C,H,W]
+    float* goff;
+    float* gmask;
+    float* slab;        // [nslab][Co][T*C]
+    int B, C, H, W, Co, Ho, Wo, kh, kw, sh, sw, ph, pw, dh, dw, dg;
+    int b0, nb, slab_px, nslab;
+};
+
+__global__ void wt_kernel(const float* __restrict__ w, float* __restrict__ wt, int Co, int C, int T) {
+    const size_t n = (size_t)Co * C * T;
+    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
+        const size_t co = e / ((size_t)C * T);
+        const int r = (int)(e - co * C * T), c = r / T, t = r - c * T;
+        wt[co * C * T + (size_t)t * C + c] = w[e];
+    }
+}
+
+// grad_col of images b0 .. b0+nb-1: D[k][pix] over K = Co.  A[k][co] = wt[co][k], B[co][pix] = go[b][co][pix].
+// A workgroup of 4 waves owns 128 k x 128 pixels; each wave 64 x 64 (2 x 2 accumulators).
+__global__ __launch_bounds__(256) void gcol_kernel(const BwdP p) {
+    const int TC = p.C * p.kh * p.kw, HWo = p.Ho * p.Wo;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int k0 = blockIdx.y * 128 + (wv >> 1) * 64, px0 = blockIdx.x * 128 + (wv & 1) * 64;
+    const int bi = blockIdx.z, b = p.b0 + bi;
+    const int r = lane & 31, h = lane >> 5;
+    const float* go = p.go + (size_t)b * p.Co * HWo;
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int n = 0; n < 2; ++n)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[m][n][e] = 0.f;
+    const bool ka0 = k0 + r < TC, ka1 = k0 + 32 + r < TC;
+    const bool pb0 = px0 + r < HWo, pb1 = px0 + 32 + r < HWo;
+    for (int c2 = 0; c2 < p.Co; c2 += 2) {  // uniform over the wave; lane half h takes co = c2 + h
+        const int co = c2 + h;
+        const bool cv = co < p.Co;
+        const float* wr = p.wt + (size_t)(cv ? co : 0) * TC;
+        const float* gr = go + (size_t)(cv ? co : 0) * HWo;
+        const float a0 = (cv && ka0) ? wr[k0 + r] : 0.f;
+        const float a1 = (cv && ka1) ? wr[k0 + 32 + r] : 0.f;
+        const float b0v = (cv && pb0) ? gr[px0 + r] : 0.f;
+        const float b1v = (cv && pb1) ? gr[px0 + 32 + r] : 0.f;
+        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0v, acc[0][0], 0, 0, 0);
+        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1v, acc[0][1], 0, 0, 0);
+        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0v, acc[1][0], 0, 0, 0);
+        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1v, acc[1][1], 0, 0, 0);
+    }
+    float* out = p.gcol + (size_t)bi * TC * HWo;
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int n = 0; n < 2; ++n) {
+            const int px = px0 + 32 * n + r;
+            if (px >= HWo) continue;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int k = k0 + 32 * m + (e & 3) + 8 * (e >> 2) + 4 * h;
+                if (k < TC) out[(size_t)k * HWo + px] = acc[m][n][e];
+            }
+        }
+}
+
+// One sample: position, 1-D weights and corner validity (dcn_v2_im2col_cuda.cu dmcn_im2col_bilinear / the get_*_weight
+// helpers use the same floor / +1 corners and the same in-image tests).
+struct Sample {
+    bool in;          // inside (-1, H) x (-1, W): otherwise it contributes to nothing
+    int y0, x0;       // low corner
+    float lh, lw, hh, hw;
+    bool c1, c2, c3, c4;  // (y0,x0) (y0,x0+1) (y0+1,x0) (y0+1,x0+1) inside the image
+};
+
+__device__ __forceinline__ Sample make_sample(float sy, float sx, int H, int W) {
+    Sample s;
+    s.in = !(sy <= -1.f || sx <= -1.f || sy >= (float)H || sx >= (float)W);
+    const float fy = floorf(sy), fx = floorf(sx);
+    s.y0 = s.in ? (int)fy : -2;
+    s.x0 = s.in ? (int)fx : -2;
+    s.lh = sy - fy;
+    s.lw = sx - fx;
+    s.hh = 1.f - s.lh;
+    s.hw = 1.f - s.lw;
+    s.c1 = s.in && s.y0 >= 0 && s.x0 >= 0;
+    s.c2 = s.in && s.y0 >= 0 && s.x0 + 1 <= W - 1;
+    s.c3 = s.in && s.y0 + 1 <= H - 1 && s.x0 >= 0;
+    s.c4 = s.in && s.y0 + 1 <= H - 1 && s.x0 + 1 <= W - 1;
+    return s;
+}
+
+// fast path: 3x3, stride 1, pad 1, dilation 1, one deformable group, C % CH == 0; x and the input gradient NHWC.
+// 9 waves: wave = tap, lane = pixel of the 16 x 4 patch.
+template <int CH>
+__global__ __launch_bounds__(576) void dcn_bwd_halo_kernel(const BwdP p) {
+    __shared__ float halo[HY * HX * (CH + 1)];  // + 1: cells of one channel fall in different banks
+    const int C = p.C, H = p.H, W = p.W, HWo = p.Ho * p.Wo, TC = 9 * C;
+    const int tap = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int ty0 = blockIdx.y * PT_Y, tx0 = blockIdx.x * PT_X;
+    const int ho = ty0 + (lane >> 4), wo = tx0 + (lane & 15);
+    const int bi = blockIdx.z, b = p.b0 + bi;
+    const bool act = ho < p.Ho && wo < p.Wo;
+    const int pix = act ? ho * p.Wo + wo : 0;
+    const int hy0 = ty0 - HALO_R, hx0 = tx0 - HALO_R;
+    const int i = tap / 3, j = tap - 3 * i;
+    const float oh = act ? p.off[((size_t)b * 18 + 2 * tap) * HWo + pix] : 0.f;
+    const float ow = act ? p.off[((size_t)b * 18 + 2 * tap + 1) * HWo + pix] : 0.f;
+    const float m = act ? p.mask[((size_t)b * 9 + tap) * HWo + pix] : 0.f;
+    const Sample s = make_sample((float)(ho - 1 + i) + oh, (float)(wo - 1 + j) + ow, H, W);
+    const bool live = act && s.in;
+    const float w1 = s.hh * s.hw, w2 = s.hh * s.lw, w3 = s.lh * s.hw, w4 = s.lh * s.lw;
+    // corner cells in the halo tile (-1: outside it, the add goes to global memory)
+    int cell[4];
+    size_t gaddr[4];
+    bool cv[4] = {s.c1 && live, s.c2 && live, s.c3 && live, s.c4 && live};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int y = s.y0 + (q >> 1), x = s.x0 + (q & 1);
+        const int ly = y - hy0, lx = x - hx0;
+        cell[q] = (ly >= 0 && ly < HY && lx >= 0 && lx < HX) ? ly * HX + lx : -1;
+        gaddr[q] = cv[q] ? (((size_t)b * H + y) * W + x) * C : 0;
+    }
+    const float* xb = p.xh;
+    const float* gc = p.gcol + ((size_t)bi * TC + (size_t)tap * C) * HWo + pix;
+    float vh = 0.f, vw = 0.f, mv = 0.f;
+    for (int c0 = 0; c0 < C; c0 += CH) {
+        for (int e = threadIdx.x; e < HY * HX * (CH + 1); e += 576) halo[e] = 0.f;
+        __syncthreads();
+        if (live) {
+            for (int cc = 0; cc < CH; cc += 4) {
+                const int c = c0 + cc;
+                const float4 v1 = cv[0] ? ld4(xb + gaddr[0] + c) : zero4();
+                const float4 v2 = cv[1] ? ld4(xb + gaddr[1] + c) : zero4();
+                const float4 v3 = cv[2] ? ld4(xb + gaddr[2] + c) : zero4();
+                const float4 v4 = cv[3] ? ld4(xb + gaddr[3] + c) : zero4();
+                const float a1[4] = {v1.x, v1.y, v1.z, v1.w}, a2[4] = {v2.x, v2.y, v2.z, v2.w};
+                const float a3[4] = {v3.x, v3.y, v3.z, v3.w}, a4[4] = {v4.x, v4.y, v4.z, v4.w};
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const float g = gc[(size_t)(c + u) * HWo];
+                    const float cwh = -s.hw * a1[u] - s.lw * a2[u] + s.hw * a3[u] + s.lw * a4[u];
+                    const float cww = -s.hh * a1[u] + s.hh * a2[u] - s.lh * a3[u] + s.lh * a4[u];
+                    vh += cwh * g * m;
+                    vw += cww * g * m;
+                    mv += g * (w1 * a1[u] + w2 * a2[u] + w3 * a3[u] + w4 * a4[u]);
+                    const float gm = g * m;
+                    const float add[4] = {w1 * gm, w2 * gm, w3 * gm, w4 * gm};
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        if (!cv[q]) continue;
+                        if (cell[q] >= 0)
+                            atomicAdd(&halo[cell[q] * (CH + 1) + cc + u], add[q]);
+                        else
+                            atomicAdd(p.gin + gaddr[q] + c + u, add[q]);
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        // flush: one global add per non-zero (cell, channel) inside the image; lanes run along the channels
+        for (int e = threadIdx.x; e < HY * HX * CH; e += 576) {
+            const int cl = e / CH, cc = e - cl * CH;
+            const int ly = cl / HX, lx = cl - ly * HX;
+            const int y = hy0 + ly, x = hx0 + lx;
+            const float v = halo[cl * (CH + 1) + cc];
+            if (y >= 0 && y < H && x >= 0 && x < W && v != 0.f)
+                atomicAdd(p.gin + (((size_t)b * H + y) * W + x) * C + c0 + cc, v);
+        }
+        __syncthreads();
+    }
+    if (act) {
+        p.goff[((size_t)b * 18 + 2 * tap) * HWo + pix] = vh;
+        p.goff[((size_t)b * 18 + 2 * tap + 1) * HWo + pix] = vw;
+        p.gmask[((size_t)b * 9 + tap) * HWo + pix] = mv;
+    }
+}
+
+// generic path: any kernel / stride / padding / dilation / deformable_group / C; NCHW throughout.  One lane per
+// sample (image of the chunk, group, tap, pixel).  The input gradient's sample uses pad_h on both axes, as the reference's
+// launchers do (dcn_v2_im2col_cuda.cu:368, dcn_v2_im2col_cpu.cpp:364); offsets and masks use (pad_h, pad_w).
+__global__ __launch_bounds__(256) void dcn_bwd_generic_kernel(const BwdP p) {
+    const int T = p.kh * p.kw, HWo = p.Ho * p.Wo, TC = p.C * T, cpg = p.C / p.dg;
+    const size_t n = (size_t)p.nb * p.dg * T * HWo;
+    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
+        const int pix = (int)(e % HWo);
+        size_t r = e / HWo;
+        const int tap = (int)(r % T);
+        r /= T;
+        const int g = (int)(r % p.dg);
+        const int bi = (int)(r / p.dg), b = p.b0 + bi;
+        const int ho = pix / p.Wo, wo = pix - ho * p.Wo;
+        const int i = tap / p.kw, j = tap - i * p.kw;
+        const size_t ob = ((size_t)b * p.dg + g) * 2 * T;
+        const float oh = p.off[(ob + 2 * tap) * HWo + pix], ow = p.off[(ob + 2 * tap + 1) * HWo + pix];
+        const size_t mi = (((size_t)b * p.dg + g) * T + tap) * HWo + pix;
+        const float m = p.mask[mi];
+        const float sy = (float)(ho * p.sh - p.ph + i * p.dh) + oh;
+        const Sample s = make_sample(sy, (float)(wo * p.sw - p.pw + j * p.dw) + ow, p.H, p.W);
+        const Sample t = make_sample(sy, (float)(wo * p.sw - p.ph + j * p.dw) + ow, p.H, p.W);  // the col2im quirk
+        const float w1 = s.hh * s.hw, w2 = s.hh * s.lw, w3 = s.lh * s.hw, w4 = s.lh * s.lw;
+        const float t1 = t.hh * t.hw, t2 = t.hh * t.lw, t3 = t.lh * t.hw, t4 = t.lh * t.lw;
+        float vh = 0.f, vw = 0.f, mv = 0.f;
+        for (int cl = 0; cl < cpg; ++cl) {
+            const int c = g * cpg + cl;
+            const float gv = p.gcol[((size_t)bi * TC + (size_t)tap * p.C + c) * HWo + pix];
+            const size_t plane = ((size_t)b * p.C + c) * p.H * p.W;
+            if (s.in) {
+                const float* xp = p.x + plane;
+                const float a1 = s.c1 ? xp[(size_t)s.y0 * p.W + s.x0] : 0.f;
+                const float a2 = s.c2 ? xp[(size_t)s.y0 * p.W + s.x0 + 1] : 0.f;
+                const float a3 = s.c3 ? xp[(size_t)(s.y0 + 1) * p.W + s.x0] : 0.f;
+                const float a4 = s.c4 ? xp[(size_t)(s.y0 + 1) * p.W + s.x0 + 1] : 0.f;
+                vh += (-s.hw * a1 - s.lw * a2 + s.hw * a3 + s.lw * a4) * gv * m;
+                vw += (-s.hh * a1 + s.hh * a2 - s.lh * a3 + s.lh * a4) * gv * m;
+                mv += gv * (w1 * a1 + w2 * a2 + w3 * a3 + w4 * a4);
+            }
+            if (t.in) {
+                const float gm = gv * m;
+                float* gp = p.gin + plane;
+                if (t.c1) atomicAdd(gp + (size_t)t.y0 * p.W + t.x0, t1 * gm);
+                if (t.c2) atomicAdd(gp + (size_t)t.y0 * p.W + t.x0 + 1, t2 * gm);
+                if (t.c3) atomicAdd(gp + (size_t)(t.y0 + 1) * p.W + t.x0, t3 * gm);
+                if (t.c4) atomicAdd(gp + (size_t)(t.y0 + 1) * p.W + t.x0 + 1, t4 * gm);
+            }
+        }
+        p.goff[(ob + 2 * tap) * HWo + pix] = vh;
+        p.goff[(ob + 2 * tap + 1) * HWo + pix] = vw;
+        p.gmask[mi] = mv;
+    }
+}
+
+// slab[s][co][k] = sum_{q in slab s} go_t[q][co] * col(q, k): D[co][k] over K = pixels, 2 per MFMA step.  A wave owns
+// 32 k columns and NCO 32-row Co tiles; lane l builds col(q0 + (l >> 5), k0 + (l & 31)) itself.
+template <int NCO>
+__global__ __launch_bounds__(256) void wgrad_kernel(const BwdP p) {
+    const int T = p.kh * p.kw, TC = p.C * T, HWo = p.Ho * p.Wo, cpg = p.C / p.dg;
+    const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+    const int k0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 32;
+    if (k0 >= TC) return;
+    const int co0 = blockIdx.y * 32 * NCO;
+    const int sl = blockIdx.z;
+    const int Q = p.B * HWo;
+    const int q_beg = sl * p.slab_px, q_end = min(Q, q_beg + p.slab_px);
+    const int k = k0 + r;
+    const bool kv = k < TC;
+    const int tap = kv ? k / p.C : 0, c = kv ? k - tap * p.C : 0;
+    const int i = tap / p.kw, j = tap - i * p.kw;
+    const int g = c / cpg;
+    f32x16 acc[NCO];
+#pragma unroll
+    for (int t = 0; t < NCO; ++t)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
+    for (int q0 = q_beg; q0 < q_end; q0 += 2) {
+        const int q = q0 + h;
+        const bool qv = q < q_end;
+        float bv = 0.f;
+        if (qv && kv) {
+            const int b = q / HWo, pix = q - b * HWo;
+            const int ho = pix / p.Wo, wo = pix - ho * p.Wo;
+            const size_t ob = ((size_t)b * p.dg + g) * 2 * T;
+            const float oh = p.off[(ob + 2 * tap) * HWo + pix], ow = p.off[(ob + 2 * tap + 1) * HWo + pix];
+            const float m = p.mask[(((size_t)b * p.dg + g) * T + tap) * HWo + pix];
+            const Sample s = make_sample((float)(ho * p.sh - p.ph + i * p.dh) + oh,
+                                         (float)(wo * p.sw - p.pw + j * p.dw) + ow, p.H, p.W);
+            float a1 = 0.f, a2 = 0.f, a3 = 0.f, a4 = 0.f;
+            if (p.xh) {
+                const float* xb = p.xh + (size_t)b * p.H * p.W * p.C + c;
+                if (s.c1) a1 = xb[((size_t)s.y0 * p.W + s.x0) * p.C];
+                if (s.c2) a2 = xb[((size_t)s.y0 * p.W + s.x0 + 1) * p.C];
+                if (s.c3) a3 = xb[((size_t)(s.y0 + 1) * p.W + s.x0) * p.C];
+                if (s.c4) a4 = xb[((size_t)(s.y0 + 1) * p.W + s.x0 + 1) * p.C];
+            } else {
+                const float* xp = p.x + ((size_t)b * p.C + c) * p.H * p.W;
+                if (s.c1) a1 = xp[(size_t)s.y0 * p.W + s.x0];
+                if (s.c2) a2 = xp[(size_t)s.y0 * p.W + s.x0 + 1];
+                if (s.c3) a3 = xp[(size_t)(s.y0 + 1) * p.W + s.x0];
+                if (s.c4) a4 = xp[(size_t)(s.y0 + 1) * p.W + s.x0 + 1];
+            }
+            // the forward's column value: (w1 v1 + w2 v2 + w3 v3 + w4 v4) * mask, zero outside (-1, H) x (-1, W)
+            const float val = (s.hh * s.hw) * a1 + (s.hh * s.lw) * a2 + (s.lh * s.hw) * a3 + (s.lh * s.lw) * a4;
+            bv = s.in ? val * m : 0.f;
+        }
+        const float* gr = p.go_t + (size_t)(qv ? q : 0) * p.Co;
+#pragma unroll
+        for (int t = 0; t < NCO; ++t) {
+            const int co = co0 + 32 * t + r;
+            const float av = (qv && co < p.Co) ? gr[co] : 0.f;
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[t], 0, 0, 0);
+        }
+    }
+    float* out = p.slab + (size_t)sl * p.Co * TC;
+    if (!kv) return;
+#pragma unroll
+    for (int t = 0; t < NCO; ++t)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const int co = co0 + 32 * t + (e & 3) + 8 * (e >> 2) + 4 * h;
+            if (co < p.Co) out[(size_t)co * TC + k] = acc[t][e];
+        }
+}
+
+// grad_weight[co][c][tap] = sum over slabs in slab order
+__global__ void wgrad_reduce_kernel(const float* __restrict__ slab, float* __restrict__ gw, int nslab, int Co, int C, int T) {
+    const size_t n = (size_t)Co * C * T, TC = (size_t)C * T;
+    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
+        const size_t co = e / TC;
+        const int r = (int)(e - co * TC), c = r / T, t = r - c * T;
+        const size_t src = co * TC + (size_t)t * C + c;
+        float v = 0.f;
+        for (int s = 0; s < nslab; ++s) v += slab[(size_t)s * n + src];
+        gw[e] = v;
+    }
+}
+
+// grad_bias[co] = sum over images and pixels of grad_output, a fixed per-thread stride and a fixed tree
+__global__ __launch_bounds__(256) void bias_kernel(const float* __restrict__ go, float* __restrict__ gb, int B, int Co, int HWo) {
+    __shared__ float red[256];
+    const int co = blockIdx.x;
+    float v = 0.f;
+    for (int b = 0; b < B; ++b) {
+        const float* pl = go + ((size_t)b * Co + co) * HWo;
+        for (int e = threadIdx.x; e < HWo; e += 256) v += pl[e];
+    }
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) gb[co] = red[0];
+}
+
+inline size_t al(size_t x) { return (x + 255) / 256 * 256; }
+
+struct Plan {
+    bool fast;
+    int nb, nslab, slab_px;
+    size_t wt, go_t, xh, gin, gcol, slab, total;  // byte offsets / total
+};
+
+Plan plan(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int dg) {
+    Plan P;
+    const int Ho = (H + 2 * ph - (dh * (kh - 1) + 1)) / sh + 1, Wo = (W + 2 * pw - (dw * (kw - 1) + 1)) / sw + 1;
+    const size_t HWo = (size_t)Ho * Wo, TC = (size_t)C * kh * kw, Q = (size_t)B * HWo;
+    P.fast = cp_dcn_backward_fast(C, kh, kw, sh, sw, ph, pw, dh, dw, dg);
+    const size_t per_img = TC * HWo * 4;
+    const size_t cap = (size_t)256 << 20;  // grad_col chunk: at most 256 MiB (or one image)
+    P.nb = (int)std::max<size_t>(1, std::min<size_t>((size_t)B, cap / per_img));
+    const size_t tiles = ((TC + 31) / 32) * ((Co + 32 * WG_COUT - 1) / (32 * WG_COUT));
+    size_t ns = (8192 + tiles - 1) / tiles;                                   // about 8 waves per SIMD
+    ns = std::min(ns, std::max<size_t>(1, ((size_t)64 << 20) / (Co * TC * 4)));  // slabs: at most 64 MiB
+    ns = std::max<size_t>(1, std::min(ns, (Q + 63) / 64));                    // at least 64 pixels a slab
+    size_t spx = (Q + ns - 1) / ns;
+    spx = (spx + 1) & ~(size_t)1;
+    P.slab_px = (int)spx;
+    P.nslab = (int)((Q + spx - 1) / spx);
+    size_t o = 0;
+    P.wt = o;
+    o += al((size_t)Co * TC * 4);
+    P.go_t = o;
+    o += al(Q * Co * 4);
+    P.xh = o;
+    P.gin = o;
+    if (P.fast) {
+        o += al((size_t)B * H * W * C * 4);
+        P.gin = o;
+        o += al((size_t)B * H * W * C * 4);
+    }
+    P.gcol = o;
+    o += al((size_t)P.nb * per_img);
+    P.slab = o;
+    o += al((size_t)P.nslab * Co * TC * 4);
+    P.total = o;
+    return P;
+}
+
+inline bool ok() { return hipGetLastError() == hipSuccess; }
+
+}  // namespace
+
+bool cp_dcn_backward_fast(int C, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int dg) {
+    return kh == 3 && kw == 3 && sh == 1 && sw == 1 && ph == 1 && pw == 1 && dh == 1 && dw == 1 && dg == 1 && C % 16 == 0;
+}
+
+size_t cp_dcn_backward_ws_bytes(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw, int dh,
+                                int dw, int dg) {
+    return plan(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, dg).total;
+}
+
+int cp_launch_dcn_backward(hipStream_t s, const DcnBwdArgs& a, void* ws) {
+    const Plan P = plan(a.B, a.C, a.H, a.W, a.Co, a.kh, a.kw, a.sh, a.sw, a.ph, a.pw, a.dh, a.dw, a.dg);
+    char* w8 = (char*)ws;
+    const int T = a.kh * a.kw, TC = a.C * T;
+    BwdP p;
+    p.x = a.input;
+    p.xh = P.fast ? (const float*)(w8 + P.xh) : nullptr;
+    p.wt = (const float*)(w8 + P.wt);
+    p.off = a.offset;
+    p.mask = a.mask;
+    p.go = a.grad_output;
+    p.go_t = (const float*)(w8 + P.go_t);
+    p.gcol = (float*)(w8 + P.gcol);
+    p.gin = P.fast ? (float*)(w8 + P.gin) : a.grad_input;
+    p.goff = a.grad_offset;
+    p.gmask = a.grad_mask;
+    p.slab = (float*)(w8 + P.slab);
+    p.B = a.B, p.C = a.C, p.H = a.H, p.W = a.W, p.Co = a.Co, p.Ho = a.Ho, p.Wo = a.Wo;
+    p.kh = a.kh, p.kw = a.kw, p.sh = a.sh, p.sw = a.sw, p.ph = a.ph, p.pw = a.pw, p.dh = a.dh, p.dw = a.dw, p.dg = a.dg;
+    p.nb = P.nb, p.slab_px = P.slab_px, p.nslab = P.nslab;
+    const int HWo = a.Ho * a.Wo;
+    const size_t in_bytes = (size_t)a.B * a.C * a.H * a.W * 4;
+
+    hipLaunchKernelGGL(wt_kernel, dim3(256), dim3(256), 0, s, a.weight, (float*)p.wt, a.Co, a.C, T);
+    if (!ok()) return CP_ERR_LAUNCH;
+    int rc = cp_launch_nchw_to_nhwc(a.grad_output, (float*)p.go_t, a.B, a.Co, a.Ho, a.Wo, a.Co, s);
+    if (rc != CP_OK) return rc;
+    if (P.fast) {
+        rc = cp_launch_nchw_to_nhwc(a.input, (float*)p.xh, a.B, a.C, a.H, a.W, a.C, s);
+        if (rc != CP_OK) return rc;
+    }
+    if (hipMemsetAsync(p.gin, 0, in_bytes, s) != hipSuccess) return CP_ERR_LAUNCH;
+
+    for (int b0 = 0; b0 < a.B; b0 += P.nb) {
+        p.b0 = b0;
+        p.nb = std::min(P.nb, a.B - b0);
+        hipLaunchKernelGGL(gcol_kernel, dim3((HWo + 127) / 128, (TC + 127) / 128, p.nb), dim3(256), 0, s, p);
+        if (!ok()) return CP_ERR_LAUNCH;
+        if (P.fast) {
+            const dim3 grid((a.Wo + PT_X - 1) / PT_X, (a.Ho + PT_Y - 1) / PT_Y, p.nb);
+            if (a.C % 32 == 0)
+                hipLaunchKernelGGL(dcn_bwd_halo_kernel<32>, grid, dim3(576), 0, s, p);
+            else
+                hipLaunchKernelGGL(dcn_bwd_halo_kernel<16>, grid, dim3(576), 0, s, p);
+        } else {
+            const size_t n = (size_t)p.nb * a.dg * T * HWo;
+            const size_t blocks = std::min<size_t>((n + 255) / 256, 65536);
+            hipLaunchKernelGGL(dcn_bwd_generic_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p);
+        }
+        if (!ok()) return CP_ERR_LAUNCH;
+    }
+    p.b0 = 0;
+    p.nb = P.nb;
+    const dim3 wg_grid((TC + 127) / 128, 1, P.nslab);
+    if (a.Co <= 32)
+        hipLaunchKernelGGL(wgrad_kernel<1>, wg_grid, dim3(256), 0, s, p);
+    else if (a.Co <= 64)
+        hipLaunchKernelGGL(wgrad_kernel<2>, wg_grid, dim3(256), 0, s, p);
+    else
+        hipLaunchKernelGGL(wgrad_kernel<WG_COUT>, dim3(wg_grid.x, (a.Co + 32 * WG_COUT - 1) / (32 * WG_COUT), P.nslab),
+                           dim3(256), 0, s, p);
+    if (!ok()) return CP_ERR_LAUNCH;
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(1024), dim3(256), 0, s, (const float*)p.slab, a.grad_weight, P.nslab, a.Co,
+                       a.C, T);
+    if (!ok()) return CP_ERR_LAUNCH;
+    hipLaunchKernelGGL(bias_kernel, dim3(a.Co), dim3(256), 0, s, a.grad_output, a.grad_bias, a.B, a.Co, HWo);
+    if (!ok()) return CP_ERR_LAUNCH;
+    if (P.fast) return cp_launch_nhwc_to_nchw(p.gin, a.grad_input, a.B, a.C, a.H, a.W, a.C, s);
+    return CP_OK;
+}

@@ -2444,6 +2444,50 @@ int cp_decode_tiled(cp_stream_t stream, int B, int H, int W, float* hm, const fl
 
 // DCNv2 forward with the reference's NCHW layouts (see header).  Workspace layout:
 //   [x NHWC B*H*W*C][offmask NHWC B*H*W*32][y NHWC B*H*W*Co][packed weights][shift CoutPad]
+// DCNv2 backward: shape checks here (as the forward's), kernels in dcn_bwd.hip
+static const char* dcn_bwd_shape_error(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw,
+                                       int dh, int dw, int dg, int* Ho, int* Wo) {
+    if (B < 1 || C < 1 || H < 1 || W < 1 || Co < 1 || kh < 1 || kw < 1 || sh < 1 || sw < 1 || ph < 0 || pw < 0 || dh < 1 ||
+        dw < 1 || dg < 1 || C % dg != 0)
+        return "dcn_v2_backward: bad shape argument (C must be divisible by deformable_group)";
+    const long long ho = ((long long)H + 2LL * ph - ((long long)dh * (kh - 1) + 1)) / sh + 1;
+    const long long wo = ((long long)W + 2LL * pw - ((long long)dw * (kw - 1) + 1)) / sw + 1;
+    if (ho < 1 || wo < 1 || H + 2LL * ph < (long long)dh * (kh - 1) + 1 || W + 2LL * pw < (long long)dw * (kw - 1) + 1)
+        return "dcn_v2_backward: empty output (kernel extent larger than the padded input)";
+    const long long lim = 0x7fffffffLL, T = (long long)kh * kw;
+    if ((long long)B * C * H * W >= lim || (long long)B * Co * ho * wo >= lim || (long long)B * dg * 2 * T * ho * wo >= lim ||
+        (long long)Co * C * T >= lim || (long long)C * T * ho * wo >= lim)
+        return "dcn_v2_backward: a tensor has 2^31 elements or more";
+    *Ho = (int)ho;
+    *Wo = (int)wo;
+    return nullptr;
+}
+
+size_t cp_dcnv2_backward_workspace_bytes(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw,
+                                         int dh, int dw, int deformable_group) {
+    int Ho = 0, Wo = 0;
+    if (dcn_bwd_shape_error(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group, &Ho, &Wo)) return 0;
+    return cp_dcn_backward_ws_bytes(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group);
+}
+
+int cp_dcnv2_backward(cp_stream_t stream, const float* input, const float* weight, const float* offset, const float* mask,
+                      const float* grad_output, float* grad_input, float* grad_offset, float* grad_mask, float* grad_weight,
+                      float* grad_bias, int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw,
+                      int dh, int dw, int deformable_group, void* workspace, size_t workspace_bytes) {
+    int Ho = 0, Wo = 0;
+    if (const char* e = dcn_bwd_shape_error(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group, &Ho, &Wo))
+        return fail(CP_ERR_INVALID, e);
+    if (!input || !weight || !offset || !mask || !grad_output || !grad_input || !grad_offset || !grad_mask || !grad_weight ||
+        !grad_bias || !workspace)
+        return fail(CP_ERR_INVALID, "dcn_v2_backward: null argument");
+    if (workspace_bytes < cp_dcn_backward_ws_bytes(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group))
+        return fail(CP_ERR_INVALID, "dcn_v2_backward: workspace too small");
+    DcnBwdArgs a{input, weight, offset, mask, grad_output, grad_input, grad_offset, grad_mask, grad_weight, grad_bias,
+                 B, C, H, W, Co, Ho, Wo, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group};
+    const int rc = cp_launch_dcn_backward((hipStream_t)stream, a, workspace);
+    return rc == CP_OK ? CP_OK : fail(rc, "dcn_v2_backward: kernel launch failed");
+}
+
 size_t cp_dcnv2_workspace_bytes(int B, int C, int H, int W, int Co) {
     const size_t px = (size_t)B * H * W;
     const size_t cpad = align_up((size_t)Co, cp_conv_tile_n(Co));

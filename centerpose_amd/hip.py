@@ -61,6 +61,8 @@ def lib():
     _sig(L.cp_dcnv2_workspace_bytes, c_size_t, c_int, c_int, c_int, c_int, c_int)
     _sig(L.cp_dcnv2_forward, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
          *([c_int] * 14), c_void_p, c_size_t)
+    _sig(L.cp_dcnv2_backward_workspace_bytes, c_size_t, *([c_int] * 14))
+    _sig(L.cp_dcnv2_backward, c_int, *([c_void_p] * 11), *([c_int] * 14), c_void_p, c_size_t)
     _sig(L.cp_model_create, c_int, c_char_p, c_int, c_int, ctypes.POINTER(c_char_p), ctypes.POINTER(c_int), c_int,
          ctypes.POINTER(c_void_p))
     _sig(L.cp_model_set_param, c_int, c_void_p, c_char_p, c_void_p, ctypes.c_int64)
@@ -146,7 +148,7 @@ def exported_symbols():
             "cp_abi_version", "cp_num_kernel_variants", "cp_num_roles", "cp_track_state_bytes", "cp_track_workspace_bytes",
             "cp_track_reset", "cp_track_step", "cp_track_status", "cp_linear_assignment", "cp_decode_tiled_workspace_bytes",
             "cp_decode_tiled", "cp_box_iou", "cp_box_eval", "cp_conv_transpose2d_workspace_bytes",
-            "cp_conv_transpose2d_nhwc"]
+            "cp_conv_transpose2d_nhwc", "cp_dcnv2_backward_workspace_bytes", "cp_dcnv2_backward"]
 
 
 def _check(rc, what):
@@ -191,6 +193,38 @@ def dcn_v2_forward(input, weight, bias, offset, mask, kh, kw, sh, sw, ph, pw, dh
                             B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group, _ptr(ws), nbytes)
     _check(rc, "cp_dcnv2_forward")
     return out
+
+
+def dcn_v2_backward(input, weight, bias, offset, mask, grad_output, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group,
+                    workspace=None):
+    """Same 15-argument signature as the reference's ``_ext.dcn_v2_backward`` (DCNv2/src/vision.cpp:6, dcn_v2.h:48-80):
+    returns [grad_input, grad_offset, grad_mask, grad_weight, grad_bias], float32 on the input's device.  ``workspace`` (a
+    uint8 device tensor of at least the queried size) may be passed to skip the allocation; a smaller one is an error."""
+    L = lib()
+    input, weight, bias, offset, mask, grad_output = map(_dev, (input, weight, bias, offset, mask, grad_output))
+    B, C, H, W = input.shape
+    Co = weight.shape[0]
+    Ho = (H + 2 * ph - (dh * (kh - 1) + 1)) // sh + 1  # dcn_v2_cuda.cu:242-243
+    Wo = (W + 2 * pw - (dw * (kw - 1) + 1)) // sw + 1
+    if Ho < 1 or Wo < 1:
+        raise RuntimeError("dcn_v2_backward: empty output")
+    for name, t, shape in (("weight", weight, (Co, C, kh, kw)), ("bias", bias, (Co,)),
+                           ("offset", offset, (B, deformable_group * 2 * kh * kw, Ho, Wo)),
+                           ("mask", mask, (B, deformable_group * kh * kw, Ho, Wo)),
+                           ("grad_output", grad_output, (B, Co, Ho, Wo))):
+        if tuple(t.shape) != shape:
+            raise RuntimeError("dcn_v2_backward: %s has shape %s, expected %s" % (name, tuple(t.shape), shape))
+    grads = [torch.empty_like(t) for t in (input, offset, mask, weight, bias)]
+    nbytes = L.cp_dcnv2_backward_workspace_bytes(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group)
+    if nbytes == 0:
+        raise RuntimeError("dcn_v2_backward: shape refused by the library")
+    if workspace is None:
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=input.device)
+    rc = L.cp_dcnv2_backward(_stream(), _ptr(input), _ptr(weight), _ptr(offset), _ptr(mask), _ptr(grad_output),
+                             *[_ptr(g) for g in grads], B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group,
+                             _ptr(workspace), workspace.numel() * workspace.element_size())
+    _check(rc, "cp_dcnv2_backward")
+    return grads
 
 
 def conv2d_nhwc(x, w, scale=None, shift=None, residual=None, stride=1, pad=0, act=0):

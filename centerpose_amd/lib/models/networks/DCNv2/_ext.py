@@ -1,6 +1,6 @@
-"""Stand-in for the reference's pybind module ``_ext`` (DCNv2/src/vision.cpp:4-9): the forward entry
-point with the identical 14-argument signature, routed to libcenterpose_hip.so.  Backward and the
-PS-ROI pooling ops are training-only / unused by CenterPose and are not provided."""
+"""Stand-in for the reference's pybind module ``_ext`` (DCNv2/src/vision.cpp:4-9): the forward and backward entry
+points with the identical 14- and 15-argument signatures, routed to libcenterpose_hip.so.  The PS-ROI pooling ops are
+unused by CenterPose and are not provided."""
 from centerpose_amd import hip as _hip
 
 
@@ -13,10 +13,19 @@ def dcn_v2_forward(input, weight, bias, offset, mask, kernel_h, kernel_w, stride
                                pad_h, pad_w, dilation_h, dilation_w, deformable_group)
 
 
-def _training_only(*args, **kwargs):
-    raise RuntimeError("centerpose_hip is an inference library: dcn_v2_backward / PS-ROI pooling are not built")
+def dcn_v2_backward(input, weight, bias, offset, mask, grad_output, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w,
+                    dilation_h, dilation_w, deformable_group):
+    """[grad_input, grad_offset, grad_mask, grad_weight, grad_bias] (dcn_v2.h:48-80); the reference's semantics, including
+    its input gradient's use of pad_h on both axes (include/centerpose_hip.h, cp_dcnv2_backward)."""
+    if not input.is_cuda:
+        raise RuntimeError("Not compiled with CPU support: centerpose_hip runs on the HIP device only")
+    return _hip.dcn_v2_backward(input, weight, bias, offset, mask, grad_output, kernel_h, kernel_w, stride_h, stride_w,
+                                pad_h, pad_w, dilation_h, dilation_w, deformable_group)
 
 
-dcn_v2_backward = _training_only
-dcn_v2_psroi_pooling_forward = _training_only
-dcn_v2_psroi_pooling_backward = _training_only
+def _not_built(*args, **kwargs):
+    raise RuntimeError("centerpose_hip: PS-ROI pooling is not built (CenterPose does not use it)")
+
+
+dcn_v2_psroi_pooling_forward = _not_built
+dcn_v2_psroi_pooling_backward = _not_built

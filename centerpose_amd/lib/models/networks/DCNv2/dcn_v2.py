@@ -1,4 +1,4 @@
-"""Forward-only ``DCNv2`` / ``DCN`` shells over ``_ext.dcn_v2_forward`` (the HIP kernels behind include/centerpose_hip.h).
+"""``DCNv2`` / ``DCN`` over ``_ext.dcn_v2_forward`` / ``_ext.dcn_v2_backward`` (the HIP kernels behind include/centerpose_hip.h).
 
 What is contractual here is the reference's surface (DCNv2/dcn_v2.py:57-128): the constructor argument order, the state-dict
 names (``weight``, ``bias``, ``conv_offset_mask.weight`` / ``.bias``), the initial values, and what ``forward`` means.  The
@@ -8,6 +8,8 @@ import collections
 
 import torch
 from torch import nn
+from torch.autograd import Function
+from torch.autograd.function import once_differentiable
 
 from . import _ext
 
@@ -18,12 +20,32 @@ def _two(v):
     return (int(v[0]), int(v[1])) if isinstance(v, (tuple, list)) else (int(v), int(v))
 
 
-def dcn_v2_conv(input, offset, mask, weight, bias, stride, padding, dilation, deformable_groups):
-    """What ``_DCNv2.apply`` computes in the forward direction (dcn_v2.py:16-35); no autograd graph is recorded."""
-    (sh, sw), (ph, pw), (dh, dw) = _two(stride), _two(padding), _two(dilation)
-    with torch.no_grad():
-        return _ext.dcn_v2_forward(input, weight, bias, offset, mask, int(weight.shape[2]), int(weight.shape[3]),
-                                   sh, sw, ph, pw, dh, dw, int(deformable_groups))
+class _DCNv2(Function):
+    """The reference's autograd function (dcn_v2.py:16-51): forward through ``_ext.dcn_v2_forward`` (the same kernels, and so
+    the same values, as a call outside grad mode), backward through ``_ext.dcn_v2_backward``."""
+
+    @staticmethod
+    def forward(ctx, input, offset, mask, weight, bias, stride, padding, dilation, deformable_groups):
+        ctx.stride, ctx.padding, ctx.dilation = _two(stride), _two(padding), _two(dilation)
+        ctx.kernel_size = _two(weight.shape[2:4])
+        ctx.deformable_groups = int(deformable_groups)
+        output = _ext.dcn_v2_forward(input, weight, bias, offset, mask, ctx.kernel_size[0], ctx.kernel_size[1],
+                                     ctx.stride[0], ctx.stride[1], ctx.padding[0], ctx.padding[1], ctx.dilation[0],
+                                     ctx.dilation[1], ctx.deformable_groups)
+        ctx.save_for_backward(input, offset, mask, weight, bias)
+        return output
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        input, offset, mask, weight, bias = ctx.saved_tensors
+        grad_input, grad_offset, grad_mask, grad_weight, grad_bias = _ext.dcn_v2_backward(
+            input, weight, bias, offset, mask, grad_output, ctx.kernel_size[0], ctx.kernel_size[1], ctx.stride[0],
+            ctx.stride[1], ctx.padding[0], ctx.padding[1], ctx.dilation[0], ctx.dilation[1], ctx.deformable_groups)
+        return grad_input, grad_offset, grad_mask, grad_weight, grad_bias, None, None, None, None
+
+
+dcn_v2_conv = _DCNv2.apply
 
 
 class DCNv2(nn.Module):

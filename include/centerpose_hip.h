@@ -71,6 +71,37 @@ int cp_dcnv2_forward(cp_stream_t stream, const float* input, const float* weight
                      void* workspace, size_t workspace_bytes);
 
 /* ------------------------------------------------------------------------------------------
+ * DCNv2 backward — replaces `_ext.dcn_v2_backward`
+ *   models/networks/DCNv2/src/vision.cpp:6, dcn_v2.h:38-80, cuda/dcn_v2_cuda.cu:206-340 (cpu/dcn_v2_cpu.cpp:109-238)
+ *   and its launchers modulated_deformable_col2im{,_coord}_cuda (cuda/dcn_v2_im2col_cuda.cu:197-327).
+ * Layouts and shape arguments are those of cp_dcnv2_forward (NCHW float32, offset channels (dh, dw) interleaved per
+ * tap); grad_output [B,Co,Ho,Wo].  Outputs, all written (not accumulated), all required (no NULL):
+ *   grad_input [B,C,H,W], grad_offset / grad_mask as offset / mask, grad_weight [Co,C,kh,kw], grad_bias [Co].
+ * Semantics of the reference's op, quirks included:
+ *   - a sample outside (-1, H) x (-1, W) contributes to no gradient; only in-image corners are read or written;
+ *   - grad_input uses pad_h for BOTH axes, as the reference's col2im launchers do (dcn_v2_im2col_cuda.cu:368,
+ *     dcn_v2_im2col_cpu.cpp:364); grad_offset / grad_mask / grad_weight use (pad_h, pad_w).  Only matters when
+ *     pad_h != pad_w (never in CenterPose);
+ *   - grad_offset is multiplied by the mask; grad_mask = sum_c grad_col * bilinear(input).
+ * Arithmetic is exact float32 (v_mfma_f32_32x32x2_f32 contractions, float32 VALU elsewhere) whatever
+ * cp_set_default_precision says: the precision mode governs the forward only.
+ * Reproducibility: grad_offset, grad_mask, grad_weight and grad_bias are bitwise reproducible run to run; grad_input
+ * is summed with float atomics and may differ in the last bits.
+ * Two paths, same semantics: 3x3 / stride 1 / pad 1 / dilation 1 / deformable_group 1 / C % 16 == 0 (every CenterPose
+ * and resdcn DCN layer) stages the input NHWC and scatters through an LDS halo tile; everything else runs a generic
+ * kernel.  Shapes are checked as the forward checks them, and every tensor must have fewer than 2^31 elements;
+ * CP_ERR_INVALID before any launch otherwise, or when workspace_bytes is below the query.  Launches on `stream` and
+ * never synchronises.
+ * ------------------------------------------------------------------------------------------ */
+size_t cp_dcnv2_backward_workspace_bytes(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph,
+                                         int pw, int dh, int dw, int deformable_group);
+int cp_dcnv2_backward(cp_stream_t stream, const float* input, const float* weight, const float* offset,
+                      const float* mask, const float* grad_output, float* grad_input, float* grad_offset,
+                      float* grad_mask, float* grad_weight, float* grad_bias, int B, int C, int H, int W, int Co,
+                      int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int deformable_group,
+                      void* workspace, size_t workspace_bytes);
+
+/* ------------------------------------------------------------------------------------------
  * Backbone + heads — replaces `create_model` / `load_model` / `model(images, pre_images,
  *   pre_hms, pre_hm_hp)[-1]`  (models/model.py:26-87, models/networks/pose_dla_dcn.py:457-570,
  *   detectors/object_pose.py:135-138).
