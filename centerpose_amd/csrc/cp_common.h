@@ -392,6 +392,17 @@ size_t cp_dcn_backward_ws_bytes(int B, int C, int H, int W, int Co, int kh, int 
                                 int dw, int dg);
 int cp_launch_dcn_backward(hipStream_t s, const DcnBwdArgs& a, void* ws);
 
+// ---- ObjectPoseLoss (pose_loss.hip; numerics in pose_loss_common.h) ----
+struct cp_pose_loss_desc;
+const char* cp_pose_loss_check(const cp_pose_loss_desc* d);                           // nullptr: accepted
+const char* cp_pose_loss_check_grads(const cp_pose_loss_desc* d, const float* const* dmaps,
+                                     float* const* grad);  // nullptr: accepted
+size_t cp_pose_loss_ws_bytes(const cp_pose_loss_desc* d);                              // 0: refused
+int cp_launch_pose_loss_forward(hipStream_t s, const cp_pose_loss_desc* d, float* loss, float* stats, long long* choice,
+                                float* terms_out, void* ws);
+int cp_launch_pose_loss_backward(hipStream_t s, const cp_pose_loss_desc* d, const float* dloss, const float* const* dmaps,
+                                 float* const* grad, void* ws);
+
 // ---- Objectron box metrics (box3d.hip; numerics in box3d_common.h) ----
 int cp_launch_box_iou(hipStream_t s, const double* a, const double* b, int n, double* iou);
 int cp_launch_box_eval(hipStream_t s, const double* pred3d, const double* gt3d, const double* pred2d, const double* mo2c,

@@ -2364,6 +2364,27 @@ int cp_box_eval(cp_stream_t stream, const double* pred3d, const double* gt3d, co
                               out);
 }
 
+size_t cp_pose_loss_workspace_bytes(const cp_pose_loss_desc* d) { return cp_pose_loss_ws_bytes(d); }
+
+int cp_pose_loss_forward(cp_stream_t stream, const cp_pose_loss_desc* d, float* loss, float* stats, long long* choice,
+                         float* terms_out, void* workspace, size_t workspace_bytes) {
+    if (const char* e = cp_pose_loss_check(d)) return fail(CP_ERR_INVALID, e);
+    if (!loss || !stats || !choice || !workspace) return fail(CP_ERR_INVALID, "pose_loss_forward: null argument");
+    if (workspace_bytes < cp_pose_loss_ws_bytes(d)) return fail(CP_ERR_INVALID, "pose_loss_forward: workspace too small");
+    const int rc = cp_launch_pose_loss_forward((hipStream_t)stream, d, loss, stats, choice, terms_out, workspace);
+    return rc == CP_OK ? CP_OK : fail(rc, "pose_loss_forward: kernel launch failed");
+}
+
+int cp_pose_loss_backward(cp_stream_t stream, const cp_pose_loss_desc* d, const float* dloss, const float* const* dmaps,
+                          float* const* grad, void* workspace, size_t workspace_bytes) {
+    if (const char* e = cp_pose_loss_check(d)) return fail(CP_ERR_INVALID, e);
+    if (const char* e = cp_pose_loss_check_grads(d, dmaps, grad)) return fail(CP_ERR_INVALID, e);
+    if (!dloss || !workspace) return fail(CP_ERR_INVALID, "pose_loss_backward: null argument");
+    if (workspace_bytes < cp_pose_loss_ws_bytes(d)) return fail(CP_ERR_INVALID, "pose_loss_backward: workspace too small");
+    const int rc = cp_launch_pose_loss_backward((hipStream_t)stream, d, dloss, dmaps, grad, workspace);
+    return rc == CP_OK ? CP_OK : fail(rc, "pose_loss_backward: kernel launch failed");
+}
+
 int cp_linear_assignment(const double* cost, int n_rows, int n_cols, int solver, int* match_out) {
     if (n_rows < 0 || n_cols < 0 || (n_rows > 0 && !match_out) || (n_rows > 0 && n_cols > 0 && !cost) || (solver != 1 && solver != 2))
         return fail(CP_ERR_INVALID, "cp_linear_assignment: bad argument (solver: 1 Munkres, 2 scipy LSAP)");

@@ -31,6 +31,27 @@ class TrackParams(ctypes.Structure):
                                             "cap", "hungarian", "baseline")]
 
 
+# ---- ObjectPoseLoss (cp_pose_loss_*): names in the order of the CP_PL_H_* / CP_PL_T_* constants ----
+POSE_LOSS_MAX_STACKS = 4
+POSE_LOSS_HEADS = ("hm", "hm_hp", "hps", "hps_uncertainty", "wh", "reg", "scale", "scale_uncertainty", "hp_offset",
+                   "tracking", "tracking_hp")
+POSE_LOSS_TERMS = ("hm", "wh", "off", "hp", "hm_hp", "hp_offset", "obj_scale", "tracking", "tracking_hp")
+POSE_LOSS_STATS = ("loss", "hm_loss", "hp_loss", "hm_hp_loss", "hp_offset_loss", "wh_loss", "off_loss", "obj_scale_loss",
+                   "tracking_loss", "tracking_hp_loss")
+PL_VAL, PL_RESIDUAL, PL_HPS_UNCERTAINTY, PL_SCALE_UNCERTAINTY, PL_HM_HP_MAPS = 1, 2, 4, 8, 16
+_PL_GT = ("gt_hm", "gt_hm_hp", "ind", "reg_mask", "gt_hps", "hps_mask", "gt_wh", "gt_reg", "gt_scale", "hp_ind", "hp_mask",
+          "gt_hp_offset", "gt_tracking", "tracking_mask", "gt_tracking_hp", "tracking_hp_mask")
+
+
+class PoseLossDesc(ctypes.Structure):
+    """cp_pose_loss_desc of include/centerpose_hip.h (field for field)."""
+    _fields_ = [(n, c_int) for n in ("B", "S", "K", "H", "W", "num_classes", "num_joints", "num_stacks", "terms", "flags")] + \
+               [("weight", ctypes.c_float * 9), ("kl_kps", ctypes.c_float), ("kl_scale", ctypes.c_float),
+                ("dimension_ref", ctypes.c_float * 3)] + [(n, c_void_p) for n in _PL_GT] + \
+               [("head", (c_void_p * len(POSE_LOSS_HEADS)) * POSE_LOSS_MAX_STACKS),
+                ("clamped", (c_void_p * 2) * POSE_LOSS_MAX_STACKS)]
+
+
 def _sig(fn, restype, *argtypes):
     fn.restype = restype
     fn.argtypes = list(argtypes)
@@ -118,6 +139,11 @@ def lib():
     _sig(L.cp_linear_assignment, c_int, c_void_p, c_int, c_int, c_int, ctypes.POINTER(c_int))
     _sig(L.cp_box_iou, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p)
     _sig(L.cp_box_eval, c_int, c_void_p, *([c_void_p] * 6), c_int, c_int, c_void_p)
+    _sig(L.cp_pose_loss_workspace_bytes, c_size_t, ctypes.POINTER(PoseLossDesc))
+    _sig(L.cp_pose_loss_forward, c_int, c_void_p, ctypes.POINTER(PoseLossDesc), c_void_p, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_size_t)
+    _sig(L.cp_pose_loss_backward, c_int, c_void_p, ctypes.POINTER(PoseLossDesc), c_void_p, ctypes.POINTER(c_void_p),
+         ctypes.POINTER(c_void_p), c_void_p, c_size_t)
     _lib = L
     return L
 
@@ -148,7 +174,8 @@ def exported_symbols():
             "cp_abi_version", "cp_num_kernel_variants", "cp_num_roles", "cp_track_state_bytes", "cp_track_workspace_bytes",
             "cp_track_reset", "cp_track_step", "cp_track_status", "cp_linear_assignment", "cp_decode_tiled_workspace_bytes",
             "cp_decode_tiled", "cp_box_iou", "cp_box_eval", "cp_conv_transpose2d_workspace_bytes",
-            "cp_conv_transpose2d_nhwc", "cp_dcnv2_backward_workspace_bytes", "cp_dcnv2_backward"]
+            "cp_conv_transpose2d_nhwc", "cp_dcnv2_backward_workspace_bytes", "cp_dcnv2_backward",
+            "cp_pose_loss_workspace_bytes", "cp_pose_loss_forward", "cp_pose_loss_backward"]
 
 
 def _check(rc, what):
@@ -989,3 +1016,170 @@ class HipModel(object):
         return outs, det
 
     __call__ = forward
+
+
+# batch key -> (descriptor field, kind): kind "f" float32 values, "m" a mask (any dtype -> float32), "i" indices
+_PL_BATCH = (("hm", "gt_hm", "f"), ("hm_hp", "gt_hm_hp", "f"), ("ind", "ind", "i"), ("reg_mask", "reg_mask", "m"),
+             ("hps", "gt_hps", "f"), ("hps_mask", "hps_mask", "m"), ("wh", "gt_wh", "f"), ("reg", "gt_reg", "f"),
+             ("scale", "gt_scale", "f"), ("hp_ind", "hp_ind", "i"), ("hp_mask", "hp_mask", "m"),
+             ("hp_offset", "gt_hp_offset", "f"), ("tracking", "gt_tracking", "f"), ("tracking_mask", "tracking_mask", "m"),
+             ("tracking_hp", "gt_tracking_hp", "f"), ("tracking_hp_mask", "tracking_hp_mask", "m"))
+
+
+def _pl_used(terms, flags):
+    """Head names and batch keys the counted terms (bit i: POSE_LOSS_TERMS[i]) read."""
+    on = {t for i, t in enumerate(POSE_LOSS_TERMS) if terms >> i & 1}
+    train = not flags & PL_VAL
+    heads, keys = ["hm", "hps"], ["hm", "ind", "hps", "hps_mask"]
+    if flags & PL_HM_HP_MAPS or "hm_hp" in on:
+        heads.append("hm_hp"), keys.append("hm_hp")
+    if train and flags & PL_HPS_UNCERTAINTY:
+        heads.append("hps_uncertainty")
+    for t, h, k in (("wh", "wh", ("wh", "reg_mask")), ("off", "reg", ("reg", "reg_mask")),
+                    ("obj_scale", "scale", ("scale", "reg_mask")), ("hp_offset", "hp_offset", ("hp_offset", "hp_ind", "hp_mask")),
+                    ("tracking", "tracking", ("tracking", "tracking_mask")),
+                    ("tracking_hp", "tracking_hp", ("tracking_hp", "tracking_hp_mask"))):
+        if t in on:
+            heads.append(h)
+            keys.extend(x for x in k if x not in keys)
+    if "obj_scale" in on and train and flags & PL_SCALE_UNCERTAINTY:
+        heads.append("scale_uncertainty")
+    return heads, keys
+
+
+def pose_loss_forward(outputs, batch, terms, flags, weights, kl_kps=0.1, kl_scale=0.1, dimension_ref=(1.0, 1.0, 1.0),
+                      with_terms=False):
+    """cp_pose_loss_forward: ObjectPoseLoss's loss on the device.  ``outputs`` is a list (one per stack) of dicts of NCHW
+    float32 head tensors; the hm (and hm_hp) tensors are overwritten in place with sigmoid(logit).  ``batch`` holds the
+    dataset's collated ground truth on the same device ([B,S,...]; uint8 / int64 masks, int64 indices).  ``terms`` has
+    bit i set when POSE_LOSS_TERMS[i] counts, ``flags`` is PL_* bits, ``weights`` the nine term weights.
+    Returns (loss [], stats [10], choice int64 [B], terms [9,B,S] or None, clamped [(hm, hm_hp or None)] per stack, state);
+    ``state`` is what pose_loss_backward needs.  An index outside [0, H*W) raises ValueError before any launch."""
+    L = lib()
+    heads_used, keys = _pl_used(terms, flags)
+    ns = len(outputs)
+    if not 1 <= ns <= POSE_LOSS_MAX_STACKS:
+        raise ValueError("pose_loss: 1 to %d stacks" % POSE_LOSS_MAX_STACKS)
+    hm = outputs[0]["hm"]
+    B, C, H, W = hm.shape
+    dev = hm.device
+    for k in keys:
+        if k not in batch:
+            raise ValueError("pose_loss: batch['%s'] is missing" % k)
+        if not batch[k].is_cuda or batch[k].device != dev:
+            raise ValueError("pose_loss: batch['%s'] must live on %s" % (k, dev))
+    S, K = batch["ind"].shape[1], batch["ind"].shape[2]
+    J = batch["hps"].shape[-1] // 2
+    HW = H * W
+    shapes = {"hm": (B, S, C, H, W), "hm_hp": (B, S, J, H, W), "ind": (B, S, K), "reg_mask": (B, S, K),
+              "hps": (B, S, K, 2 * J), "hps_mask": (B, S, K, 2 * J), "wh": (B, S, K, 2), "reg": (B, S, K, 2),
+              "scale": (B, S, K, 3), "hp_ind": (B, S, K * J), "hp_mask": (B, S, K * J), "hp_offset": (B, S, K * J, 2),
+              "tracking": (B, S, K, 2), "tracking_mask": (B, S, K), "tracking_hp": (B, S, K, 2 * J),
+              "tracking_hp_mask": (B, S, K, 2 * J)}
+    for k in keys:
+        if tuple(batch[k].shape) != shapes[k]:
+            raise ValueError("pose_loss: batch['%s'] has shape %s, expected %s" % (k, tuple(batch[k].shape), shapes[k]))
+    hchan = {"hm": C, "hm_hp": J, "hps": 2 * J, "hps_uncertainty": 2 * J, "wh": 2, "reg": 2, "scale": 3,
+             "scale_uncertainty": 3, "hp_offset": 2, "tracking": 2, "tracking_hp": 2 * J}
+    for st, out in enumerate(outputs):
+        for h in heads_used:
+            t = out.get(h)
+            if t is None:
+                raise ValueError("pose_loss: outputs[%d]['%s'] is missing" % (st, h))
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or t.data_ptr() % 16:
+                raise ValueError("pose_loss: outputs[%d]['%s'] must be a contiguous, 16-byte aligned float32 tensor on %s"
+                                 % (st, h, dev))
+            if tuple(t.shape) != (B, hchan[h], H, W):
+                raise ValueError("pose_loss: outputs[%d]['%s'] has shape %s, expected %s"
+                                 % (st, h, tuple(t.shape), (B, hchan[h], H, W)))
+    # every index in [0, H*W): one reduction, one read-back (torch.gather refuses the same batches)
+    idx_keys = [k for k in ("ind", "hp_ind") if k in keys]
+    bad = torch.stack([((batch[k] < 0) | (batch[k] >= HW)).any() for k in idx_keys]).to(torch.int32)
+    nbad = (bad * torch.tensor([1 << i for i in range(len(idx_keys))], dtype=torch.int32, device=dev)).sum().item()
+    for i, k in enumerate(idx_keys):
+        if nbad >> i & 1:
+            raise ValueError("pose_loss: batch['%s'] holds an index outside [0, %d)" % (k, HW))
+    keep = []
+    d = PoseLossDesc()
+    d.B, d.S, d.K, d.H, d.W, d.num_classes, d.num_joints, d.num_stacks = B, S, K, H, W, C, J, ns
+    d.terms, d.flags = int(terms), int(flags)
+    for i in range(9):
+        d.weight[i] = float(weights[i])
+    d.kl_kps, d.kl_scale = float(kl_kps), float(kl_scale)
+    for i in range(3):
+        d.dimension_ref[i] = float(dimension_ref[i])
+    for key, field, kind in _PL_BATCH:
+        if key not in keys:
+            continue
+        t = batch[key]
+        t = t.to(torch.int32) if kind == "i" else t.float()
+        t = t.contiguous()
+        if t.data_ptr() % 16:  # the heat-map kernels read float4 lines: an offset view gets aligned storage
+            t = t.clone()
+        keep.append(t)
+        setattr(d, field, t.data_ptr())
+    clamped = []
+    for st, out in enumerate(outputs):
+        for i, h in enumerate(POSE_LOSS_HEADS):
+            if h in heads_used:
+                d.head[st][i] = out[h].data_ptr()
+        pair = []
+        for j, h in enumerate(("hm", "hm_hp")):
+            if h in heads_used:
+                c = torch.empty_like(out[h])
+                d.clamped[st][j] = c.data_ptr()
+                pair.append(c)
+            else:
+                pair.append(None)
+        clamped.append(tuple(pair))
+    nbytes = L.cp_pose_loss_workspace_bytes(ctypes.byref(d))
+    if nbytes == 0:
+        _check(L.cp_pose_loss_forward(_stream(), ctypes.byref(d), None, None, None, None, None, 0), "cp_pose_loss_forward")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    stats = torch.empty(10, dtype=torch.float32, device=dev)
+    choice = torch.empty(B, dtype=torch.int64, device=dev)
+    tm = torch.empty(9, B, S, dtype=torch.float32, device=dev) if with_terms else None
+    _check(L.cp_pose_loss_forward(_stream(), ctypes.byref(d), _ptr(loss), _ptr(stats), _ptr(choice), _ptr(tm), _ptr(ws),
+                                  nbytes), "cp_pose_loss_forward")
+    state = {"desc": d, "ws": ws, "keep": keep, "heads": heads_used, "outputs": [dict(o) for o in outputs]}
+    return loss, stats, choice, tm, clamped, state
+
+
+def _aligned(t):
+    t = t.float().contiguous()
+    return t.clone() if t.data_ptr() % 16 else t
+
+
+def pose_loss_backward(state, dloss, dmaps=None):
+    """cp_pose_loss_backward: dL/d(head) of every head the counted terms use, for the forward that made ``state``;
+    ``dloss`` a one-element float32 device tensor.  ``dmaps`` (optional, one (hm, hm_hp) pair per stack, entries may be
+    None) are gradients arriving on the in-place sigmoid tensors; they are chained through the sigmoid and added.
+    Returns a list (one per stack) of {head name: gradient}."""
+    d = state["desc"]
+    dloss = dloss.reshape(1).float().contiguous()
+    ws = state["ws"]
+    grads = []
+    ptrs = (c_void_p * (POSE_LOSS_MAX_STACKS * len(POSE_LOSS_HEADS)))()
+    dm = (c_void_p * (2 * POSE_LOSS_MAX_STACKS))()
+    hold = []
+    counted = {"hm": True, "hm_hp": bool(d.terms >> POSE_LOSS_TERMS.index("hm_hp") & 1)}
+    for st, out in enumerate(state["outputs"]):
+        g = {}
+        for j, h in enumerate(("hm", "hm_hp")):
+            t = dmaps[st][j] if dmaps is not None else None
+            if t is not None and h in state["heads"]:
+                t = _aligned(t)
+                hold.append(t)
+                dm[2 * st + j] = t.data_ptr()
+        for i, h in enumerate(POSE_LOSS_HEADS):
+            if h not in state["heads"]:
+                continue
+            if h in counted and not counted[h] and not dm[2 * st + (h == "hm_hp")]:
+                continue
+            g[h] = torch.empty_like(out[h])
+            ptrs[st * len(POSE_LOSS_HEADS) + i] = g[h].data_ptr()
+        grads.append(g)
+    _check(lib().cp_pose_loss_backward(_stream(), ctypes.byref(d), _ptr(dloss), dm, ptrs, _ptr(ws),
+                                       ws.numel()), "cp_pose_loss_backward")
+    return grads

@@ -41,7 +41,8 @@ typedef struct cp_model cp_model;
  * kernel), cp_num_kernel_variants() / cp_num_roles() size the profile buffers; 4 = cp_track_* added; 5 = cp_track_status, list truncation instead of reset on overflow;
  * 6 = cp_preprocess_batch, cp_linear_assignment, CP_NUM_KERNEL_VARIANTS 43, cp_set_debug moved out of this header (centerpose_hip_testing.h);
  * 7 = cp_decode_tiled / cp_decode_tiled_workspace_bytes, cp_model_detect decodes output grids above 32768 pixels;
- *     later additions without a version change: cp_box_iou, cp_box_eval. */
+ *     later additions without a version change: cp_box_iou, cp_box_eval, cp_pose_loss_workspace_bytes,
+ *     cp_pose_loss_forward, cp_pose_loss_backward. */
 #define CP_ABI_VERSION 7
 const char* cp_version(void);
 int cp_abi_version(void);
@@ -453,6 +454,106 @@ int cp_linear_assignment(const double* cost, int n_rows, int n_cols, int solver,
 int cp_box_iou(cp_stream_t stream, const double* a, const double* b, int n, double* iou);
 int cp_box_eval(cp_stream_t stream, const double* pred3d, const double* gt3d, const double* pred2d, const double* mo2c,
                 const double* proj, const int* single_rotation, int n, int num_symmetry, double* out);
+
+/* ------------------------------------------------------------------------------------------
+ * Training loss — replaces `ObjectPoseLoss.forward` and the autograd backward of its graph
+ *   trains/object_pose.py:22-205 with models/losses.py:47-75 (_neg_loss / FocalLoss), :143-226 (RegL1Loss,
+ *   RegKLDScaleLoss, RegKLDKeyLoss), :243-254 (RegWeightedL1Loss), models/utils.py:9-50 (_sigmoid,
+ *   _transpose_and_gather_feat).
+ * Every term is computed per (image b, symmetry variant s), giving [B,S] matrices; summed over the stacks (each / num_stacks)
+ * and weighted, the per-variant total picks choice[b] = argmin over s of total*valid + inf*(!valid), valid = sum_k ind > 0,
+ * with torch.argmin's rules (first minimum; first NaN if any).  loss and the stats are the means over b of the chosen
+ * entries.  The backward differentiates the chosen entries only, as the reference's graph does.
+ *
+ * Layouts (all contiguous; the binding converts the dataset's uint8 / int64 masks to float32 and the indices to int32):
+ *   heads  [B, ch, H, W] float32, one set per stack:  hm ch = num_classes, hm_hp J, hps / hps_uncertainty / tracking_hp 2J,
+ *          wh / reg / hp_offset / tracking 2, scale / scale_uncertainty 3 (J = num_joints)
+ *   gt     hm [B,S,num_classes,H,W], hm_hp [B,S,J,H,W], ind [B,S,K] int32, reg_mask [B,S,K], hps / hps_mask [B,S,K,2J],
+ *          wh / reg / tracking [B,S,K,2], scale [B,S,K,3], hp_ind [B,S,K*J] int32, hp_mask [B,S,K*J],
+ *          hp_offset [B,S,K*J,2], tracking_mask [B,S,K], tracking_hp / tracking_hp_mask [B,S,K,2J]
+ * Terms (CP_PL_T_*, the order of the weighted sum at object_pose.py:163-168):
+ *   hm, hm_hp  focal loss; the forward overwrites the head's logits with sigmoid(logit) in place (_sigmoid's sigmoid_)
+ *              and writes clamp(sigmoid, 1e-4, 1-1e-4) to `clamped`; the backward reads that in-place sigmoid back
+ *   hp         RegWeightedL1Loss on hps, or RegKLDKeyLoss with hps_uncertainty (CP_PL_HPS_UNCERTAINTY, train phase)
+ *   wh, off    RegL1Loss with reg_mask;  hp_offset RegL1Loss with hp_ind / hp_mask;  tracking RegL1Loss, tracking_mask
+ *   obj_scale  train: RegL1Loss (exp(pred) * dimension_ref with CP_PL_RESIDUAL) or RegKLDScaleLoss with
+ *              scale_uncertainty (CP_PL_SCALE_UNCERTAINTY); val (CP_PL_VAL): RegL1Loss's relative form, numerator
+ *              1*mask - pred*mask, target zeros replaced by 1e-6
+ *   tracking_hp RegWeightedL1Loss with tracking_hp_mask
+ *   The L1 denominators add 1e-4, the KLD ones 1e-6, as the reference.  A term whose bit of `terms` is clear counts 0.
+ * Outputs of the forward (device): loss [1]; stats [10] in the reference's key order: loss, hm, hp, hm_hp, hp_offset, wh,
+ *   off, obj_scale, tracking, tracking_hp (a term that is off gives 0); choice [B] int64; optional terms_out
+ *   [CP_PL_NUM_TERMS, B, S] (each term's [B,S] matrix, summed over the stacks); clamped heat maps per stack.
+ * Backward: dloss is a device pointer to dL/dloss (one float, read on the device).  dmaps (host array [num_stacks * 2],
+ *   may be NULL, as may each entry) gives dL/d(in-place sigmoid) of hm [st*2] / hm_hp [st*2+1] from graphs built on the
+ *   overwritten logits tensor; it is chained through the sigmoid (dmaps * y (1 - y), sigmoid_'s backward) and added to the
+ *   loss' gradient.  grad[st * CP_PL_NUM_HEADS + h] receives dL/d(head h of stack st) (written, not accumulated) and must
+ *   be non-NULL for every head a counted term uses, and for a heat map with a dmaps entry; the others are ignored.
+ *   `workspace` must be the one the forward wrote, unchanged.
+ * Reproducibility: no float atomics; per-workgroup partials are summed in a fixed order that does not depend on s, and
+ *   repeated indices are accumulated serially per image, so every output is bitwise reproducible run to run and identical
+ *   variants give identical terms.
+ * Limits: 1 <= num_stacks <= CP_PL_MAX_STACKS, 1 <= S <= CP_PL_MAX_S, 1 <= K <= CP_PL_MAX_K, K*J <= CP_PL_MAX_K * 32,
+ *   1 <= J <= 32, num_classes >= 1, (H*W) % 4 == 0, every head and ground-truth tensor below 2^31 elements; the hm / hm_hp
+ *   heads, their clamped maps, gt_hm, gt_hm_hp, their gradients and dmaps 16-byte aligned (float4 lines); NULL pointers
+ *   that a counted term needs, a misaligned heat-map pointer or a workspace below the query return CP_ERR_INVALID before
+ *   any launch.  An index outside
+ *   [0, H*W) is read at 0 and counts as masked (the binding refuses such batches before calling).  Launches on `stream`,
+ *   never allocates, never synchronises.
+ * ------------------------------------------------------------------------------------------ */
+#define CP_PL_MAX_STACKS 4
+#define CP_PL_MAX_S 64
+#define CP_PL_MAX_K 256
+#define CP_PL_NUM_TERMS 9
+#define CP_PL_T_HM 0
+#define CP_PL_T_WH 1
+#define CP_PL_T_OFF 2
+#define CP_PL_T_HP 3
+#define CP_PL_T_HM_HP 4
+#define CP_PL_T_HP_OFFSET 5
+#define CP_PL_T_SCALE 6
+#define CP_PL_T_TRACKING 7
+#define CP_PL_T_TRACKING_HP 8
+#define CP_PL_NUM_HEADS 11
+#define CP_PL_H_HM 0
+#define CP_PL_H_HM_HP 1
+#define CP_PL_H_HPS 2
+#define CP_PL_H_HPS_UNC 3
+#define CP_PL_H_WH 4
+#define CP_PL_H_REG 5
+#define CP_PL_H_SCALE 6
+#define CP_PL_H_SCALE_UNC 7
+#define CP_PL_H_HP_OFFSET 8
+#define CP_PL_H_TRACKING 9
+#define CP_PL_H_TRACKING_HP 10
+#define CP_PL_VAL 1                /* phase == 'val' */
+#define CP_PL_RESIDUAL 2           /* opt.use_residual */
+#define CP_PL_HPS_UNCERTAINTY 4    /* opt.hps_uncertainty */
+#define CP_PL_SCALE_UNCERTAINTY 8  /* opt.obj_scale_uncertainty */
+#define CP_PL_HM_HP_MAPS 16        /* opt.hm_hp: the hm_hp heads get the sigmoid side effect even when the term is off */
+#define CP_PL_NUM_STATS 10
+typedef struct cp_pose_loss_desc {
+    int B, S, K, H, W, num_classes, num_joints, num_stacks;
+    int terms; /* bit CP_PL_T_*: the term counts */
+    int flags; /* CP_PL_VAL | CP_PL_RESIDUAL | ... */
+    float weight[CP_PL_NUM_TERMS]; /* opt.*_weight per term (off and hp_offset both take off_weight) */
+    float kl_kps, kl_scale;        /* opt.KL_kps_uncertainty, opt.KL_scale_uncertainty */
+    float dimension_ref[3];        /* opt.dimension_ref (CP_PL_RESIDUAL) */
+    /* ground truth (batch[...]) */
+    const float *gt_hm, *gt_hm_hp;
+    const int* ind;
+    const float *reg_mask, *gt_hps, *hps_mask, *gt_wh, *gt_reg, *gt_scale;
+    const int* hp_ind;
+    const float *hp_mask, *gt_hp_offset, *gt_tracking, *tracking_mask, *gt_tracking_hp, *tracking_hp_mask;
+    /* heads: head[st][CP_PL_H_*]; hm / hm_hp are overwritten in place by the forward */
+    float* head[CP_PL_MAX_STACKS][CP_PL_NUM_HEADS];
+    float* clamped[CP_PL_MAX_STACKS][2]; /* clamp(sigmoid) of hm [0] and hm_hp [1] */
+} cp_pose_loss_desc;
+size_t cp_pose_loss_workspace_bytes(const cp_pose_loss_desc* d);
+int cp_pose_loss_forward(cp_stream_t stream, const cp_pose_loss_desc* d, float* loss, float* stats, long long* choice,
+                         float* terms_out, void* workspace, size_t workspace_bytes);
+int cp_pose_loss_backward(cp_stream_t stream, const cp_pose_loss_desc* d, const float* dloss, const float* const* dmaps,
+                          float* const* grad, void* workspace, size_t workspace_bytes);
 
 #ifdef __cplusplus
 }
