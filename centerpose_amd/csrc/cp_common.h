@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/centerpose_hip_testing.h"  // CP_SEL_* (ConvParams::dbg)
+
 // The kernels of this library rely on the raw-buffer range check of the gfx9 / CDNA family as gfx950 implements it: a lane whose
 // (voffset + soffset [+ immediate]) lies beyond the descriptor's num_records reads 0 -- per dword for a 16-byte access that
 // straddles the end -- and its stores / LDS-DMA writes are dropped (zeros land in LDS).  Out-of-picture halo pixels, padded
@@ -188,7 +190,7 @@ struct ConvParams {
     const unsigned* in_amax[CP_MAX_SRC];  // nullptr: operand used as is (scale 1)
     unsigned* out_amax;                   // nullptr: the output's |max| is not tracked
     const float* fuse_w2_inv;             // fused head: 2^-e of the 1x1 weights per final channel [32]
-    int dbg;  // tuning ablations (tools/conv_bench.py --dbg): 1 skip A loads, 2 skip B loads, 4 skip LDS stores, 8 skip MFMA
+    int dbg;  // kernel-selection switches of cp_set_debug (CP_SEL_*, include/centerpose_hip_testing.h)
     const float* offmask;  // DCN mode: NHWC [B,H,W,32] = 18 offsets (dh,dw interleaved per tap) + 9 masks (already sigmoided) + 5 pad
 };
 
@@ -221,8 +223,8 @@ int cp_launch_halo16(const ConvParams& p, int bn, hipStream_t stream);
 bool cp_strm16_supported(const ConvParams& p);
 int cp_strm16_jobs(const ConvParams& p);
 int cp_launch_strm16(const ConvParams& p, hipStream_t stream);
-// fused DCNv2 gather + contraction (dcn16.hip); bn = N tile (64 / 128), variant = alternative wave count (tuning)
-int cp_launch_dcn16(const ConvParams& p, int bn, int variant, hipStream_t stream);
+// fused DCNv2 gather + contraction (dcn16.hip); bn = N tile (64 / 128)
+int cp_launch_dcn16(const ConvParams& p, int bn, hipStream_t stream);
 // dcn16p.hip: patch-resident DCNv2 (gather from an LDS-staged halo); N tile 64, or 128 where cp_dcn16p_wide says so
 // pw16.hip: 1x1 / stride-1 layers (incl. virtual concats) as a register-only stream, weight fragments from w16f_*
 bool cp_pw16_supported(const ConvParams& p);

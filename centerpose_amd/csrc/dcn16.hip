@@ -21,7 +21,7 @@
 // costs 18 x 16-byte-per-lane load instructions per wave, 4 waves share the CU's one texture addresser at 16 clk per
 // instruction = 1152 clk, i.e. <= 245 (N 64) / 490 (N 128) TFLOP/s however well the loads overlap.
 // Same tiles, LDS layout (unpadded 64-byte rows, XOR-swizzled 16-byte chunks), tile map, epilogue and operand
-// pre-scaling (ConvParams::in_amax) as igemm16.hip; results are bit-identical to the loop this replaces.
+// pre-scaling (ConvParams::in_amax) as igemm16.hip; results are bit-identical to the un-pipelined loop this replaced.
 #include "igemm16_common.h"
 
 namespace {
@@ -298,9 +298,8 @@ int launch_dcn16(const ConvParams& p, hipStream_t stream) {
 
 }  // namespace
 
-// bn: N tile (64 or 128).  variant (cp_set_debug bits 1024 / 2048, tuning A/B): 0 = default shapes, 1 = the other wave
-// count for that N tile.
-int cp_launch_dcn16(const ConvParams& p, int bn, int variant, hipStream_t stream) {
+// bn: N tile (64 or 128)
+int cp_launch_dcn16(const ConvParams& p, int bn, hipStream_t stream) {
     if (!p.offmask || !p.w16_hi || !p.w16_lo || p.KH != 3 || p.KW != 3 || p.stride != 1 || p.pad != 1 || p.nsrc != 1 ||
         p.H != p.Ho || p.W != p.Wo || p.Cin % BK16 != 0)
         return CP_ERR_INVALID;
@@ -308,7 +307,7 @@ int cp_launch_dcn16(const ConvParams& p, int bn, int variant, hipStream_t stream
     // measured on the dlav1_34 B=32 step (profiles/r02_dcn_ab.txt): N 64: 4 waves of 64x32, two blocks per CU (110 TFLOP/s)
     // vs 8 waves at 128 VGPRs (108); N 128: 8 waves of 64x32, one block per CU (152) vs 4 waves of 64x64 at 256 VGPRs (136)
     if (bn == 64 && p.tile_m == 64) return launch_dcn16<1, 1, 2, 2, 2>(p, stream);  // small launches: 64 x 64 tiles (ConvParams::tile_m)
-    if (bn == 64) return variant ? launch_dcn16<1, 1, 4, 2, 4>(p, stream) : launch_dcn16<2, 1, 2, 2, 2>(p, stream);
-    if (bn == 128) return variant ? launch_dcn16<2, 2, 2, 2, 1>(p, stream) : launch_dcn16<2, 1, 2, 4, 2>(p, stream);
+    if (bn == 64) return launch_dcn16<2, 1, 2, 2, 2>(p, stream);
+    if (bn == 128) return launch_dcn16<2, 1, 2, 4, 2>(p, stream);
     return CP_ERR_INVALID;
 }

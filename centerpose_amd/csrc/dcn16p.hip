@@ -460,10 +460,10 @@ int cp_dcn16p_blocks(const ConvParams& p) { return p.B * (p.H / TH) * (p.W / TW)
 // The 128-wide N tile (NT = 4: gather, blend and split once per 128 outputs instead of once per 64) for layers with whole
 // 128-channel tiles whose launch still gives every CU a workgroup (measured at B = 64, profiles/r05_dcn_wide_ab.txt: 128 -> 128
 // @64^2 379 -> 262 us, 256 -> 128 @32^2 171 -> 131, 256 -> 256 @32^2 364 -> 258, and 512 -> 256 @16^2 -- 256 workgroups -- 160 ->
-// 151).  cp_set_debug 524288: never (A/B runs, tests).
+// 151).  CP_SEL_DCN16P_NOT_WIDE: never (A/B runs, tests).
 bool cp_dcn16p_wide(const ConvParams& p) {
-    return cp_dcn16p_supported(p) && p.CoutPad % 128 == 0 && !(p.dbg & 524288) &&
-           ((p.dbg & 65536) || p.B * (p.H / TH) * (p.W / TW) * (p.CoutPad / 128) >= 256);  // (65536: launches of any size, tests)
+    return cp_dcn16p_supported(p) && p.CoutPad % 128 == 0 && !(p.dbg & CP_SEL_DCN16P_NOT_WIDE) &&
+           ((p.dbg & CP_SEL_DCN16P_ALWAYS) || p.B * (p.H / TH) * (p.W / TW) * (p.CoutPad / 128) >= 256);  // (ALWAYS: any size, tests)
 }
 
 int cp_launch_dcn16p(const ConvParams& p, hipStream_t stream) {

@@ -624,6 +624,6 @@ int cp_launch_dcn16s(const ConvParams& p, hipStream_t stream) {
     }
     const int items = cp_dcn16s_items(p);
     int blocks = items < max_blocks ? (items + 7) / 8 * 8 : max_blocks;
-    if (p.dbg & 8388608) blocks = 8;  // tests: one workgroup per XCD, so that small problems walk several items per workgroup
+    if (p.dbg & CP_SEL_DCN16S_GRID8) blocks = 8;  // tests: one workgroup per XCD, so that small problems walk several items per workgroup
     return launch_dcn16s<2>(p, blocks, stream);
 }

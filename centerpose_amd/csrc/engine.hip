@@ -134,7 +134,7 @@ int g_default_precision = CP_PREC_F32;
 // split-K policy: launches with fewer output tiles than kSplitTiles (and >= 8 K steps) are cut into K slices until
 // about kSplitTarget workgroups exist
 constexpr int kSplitTiles = 128, kSplitTarget = 384;  // (384 / 512 measured: B=32 equal, hourglass B=1 latency +7 %)
-int g_dbg = 0;  // cp_set_debug (include/centerpose_hip_testing.h: kernel SELECTION switches for the parity tests and A/B runs; every choice computes the layer correctly): 4 1x1 layers with fragment-shaped A loads (pw16_kernel) instead of whole lines through staging rows (pw16s_kernel), 8 split-K epilogue element-wise (not the quad form), 1 grouped heads write slabs + reduction launch, 2 grouped heads one workgroup per head (not per patch), 16 small launches on 128-row tiles, 32 no head fusion, 64 no lowc kernels, 128 GN heads' 1x1 on the f32 kernel, 256 unfused ConvGRU step, 512 no activation |max| tracking / pre-scale, 1024 previous DCN loop, 2048 alternative DCN wave counts, 4096 / 8192 halo kernel never / everywhere, 16384 LDS-staged weights in the N=32 halo kernel, 32768 / 65536 patch-resident DCN never / everywhere, 524288 patch-resident DCN never on the 128-wide N tile, 1048576 / 2097152 streamed DCN (dcn16s) never / everywhere, 33554432 / 67108864 three-workgroup DCN (dcn16t) everywhere / never, 134217728 stem and level0 as two kernels (not the fused one), 262144 / 1073741824 level1 never / always on the row-streaming kernel, 268435456 / 536870912 row-streamed 64 -> <= 32 channel 3x3 layers (strm16) never / at any size, 131072 GroupNorm'd heads' 1x1 on the matrix cores, 4194304 1x1 layers on the LDS-staged loop instead of pw16.hip, 8388608 cp_dcnv2_forward always on the generic kernel, 16777216 fused heads one launch per head instead of one grouped launch
+int g_dbg = 0;  // cp_set_debug: CP_SEL_* kernel-selection switches (include/centerpose_hip_testing.h)
 
 struct DeformW {
     ConvW offset;  // conv_offset_mask (27 -> 32 padded), shift = bias
@@ -795,7 +795,7 @@ struct Fwd {
     int nslots = 0;
     void init_slots() {
         slots_t.blk = std::make_shared<Block>(&m->arena, kSlotBytes);
-        if (m->dry || m->precision != CP_PREC_F16X3 || (g_dbg & 512)) return;  // 512: A/B switch, operands used unscaled
+        if (m->dry || m->precision != CP_PREC_F16X3 || (g_dbg & CP_SEL_NO_PRESCALE)) return;  // operands used unscaled (range-safety tests)
         slots = (unsigned*)slots_t.ptr();
         if (hipMemsetAsync(slots, 0, kSlotBytes, s) != hipSuccess) chk(CP_ERR_LAUNCH);
     }
@@ -920,7 +920,7 @@ struct Fwd {
     bool fused_heads_grouped(const Tensor& x, float* const* head_out, int sigmoid_hm) {
         const auto& g = m->head_group;
         const int n = (int)m->headw.size();
-        if (!g.ok || m->precision != CP_PREC_F16X3 || m->tap_name || (g_dbg & 32) || (g_dbg & 16777216) || x.C != g.Cin)
+        if (!g.ok || m->precision != CP_PREC_F16X3 || m->tap_name || (g_dbg & (CP_SEL_NO_HEAD_FUSION | CP_SEL_HEADS_PER_HEAD_LAUNCH)) || x.C != g.Cin)
             return false;
         ConvParams p;
         std::memset(&p, 0, sizeof(p));
@@ -950,10 +950,11 @@ struct Fwd {
         p.fuse_ngroups = n;
         p.fuse_gtiles = g.hid / 128;
         p.fuse_out = (float*)0x1000;  // placeholder for the eligibility check
-        // the kernel walks a head's hidden tiles and writes the finished maps itself (cp_set_debug 1: slabs + reduction launch)
-        // 2: every head of a patch in one workgroup (one staging for all of them) -- when the patches alone fill the device
-        // several times over; below that (small batches) one workgroup per patch and head
-        p.fuse_final = (g.Cin == 64 && g.hid == 256 && !(g_dbg & 1)) ? (((g_dbg & 2) || B * (x.H / 8) * (x.W / 16) < 2048) ? 1 : 2) : 0;
+        // the kernel walks a head's hidden tiles and writes the finished maps itself (CP_SEL_HEADS_SLABS: slabs + reduction
+        // launch); 2: every head of a patch in one workgroup (one staging for all of them) -- when the patches alone fill the
+        // device several times over; below that (small batches, CP_SEL_HEADS_WG_PER_HEAD) one workgroup per patch and head
+        p.fuse_final = (g.Cin == 64 && g.hid == 256 && !(g_dbg & CP_SEL_HEADS_SLABS))
+                           ? (((g_dbg & CP_SEL_HEADS_WG_PER_HEAD) || B * (x.H / 8) * (x.W / 16) < 2048) ? 1 : 2) : 0;
         if (!cp_halo16_fused_head_supported(p)) return false;
         if (B * (x.H / 8) * (x.W / 16) * (p.CoutPad / 128) < kSplitTiles) return false;  // small maps: per-head split-K path
         HeadReduceGroup rg;
@@ -1100,16 +1101,16 @@ struct Fwd {
             cp_conv_geometry(p, use16, &tiles, &nk);
             // small launches of the f16x3 path run on 64 x 64 tiles (four times the workgroups per slice): a quarter of the
             // slices and of the slab bytes (slices x M x Cout x 4) for the same workgroup count, and no split at all where that
-            // already gives kSplitTiles workgroups.  cp_set_debug 16: the 128-row tiles everywhere (A/B runs).
+            // already gives kSplitTiles workgroups.  CP_SEL_TILE128_SMALL: the 128-row tiles everywhere (A/B runs).
             // Measured at B = 1 / 2 / 4 / 8 (profiles/NOTES.md): pays up to 32 tiles of 128 rows, up to 64 when K is short.
             if (use16 && tiles > 0 && (tiles <= 32 || (tiles <= 64 && nk <= 36)) && nk >= 8 && !p.gn_stats && !p.gn_in_a &&
-                p.CoutPad % 64 == 0 && w.Cout >= 64 && !(g_dbg & 16)) {
+                p.CoutPad % 64 == 0 && w.Cout >= 64 && !(g_dbg & CP_SEL_TILE128_SMALL)) {
                 p.tile_m = p.tile_n = 64;
                 cp_conv_geometry(p, use16, &tiles, &nk);
             }
             // (64 x 64 tiles are a quarter of the work each: they are still cut along K below one workgroup per CU)
-            // (cp_set_debug 536870912 -- tests: the row-streaming kernel at any size -- keeps such a layer whole)
-            const bool force_strm = use16 && (g_dbg & 536870912) && cp_strm16_supported(p);
+            // (CP_SEL_STRM16_ALWAYS -- tests: the row-streaming kernel at any size -- keeps such a layer whole)
+            const bool force_strm = use16 && (g_dbg & CP_SEL_STRM16_ALWAYS) && cp_strm16_supported(p);
             if (tiles > 0 && tiles < (p.tile_m == 64 ? 256 : kSplitTiles) && nk >= 8 && !p.gn_stats && !force_strm) {
                 int want = (kSplitTarget + tiles - 1) / tiles;
                 if (want > nk / 2) want = nk / 2;
@@ -1241,12 +1242,12 @@ struct Fwd {
 
     // the network's first layers through lowc.hip (f16x3 mode only); returns an invalid Tensor when not applicable
     Tensor lowc(const std::string& name, int kind, const float* in, int H, int W, int planes, const unsigned* in_amax) {
-        if (m->precision != CP_PREC_F16X3 || (g_dbg & 64)) return Tensor();
+        if (m->precision != CP_PREC_F16X3 || (g_dbg & CP_SEL_NO_LOWC)) return Tensor();
         const int Ho = kind == 2 ? (H - 1) / 2 + 1 : H, Wo = kind == 2 ? (W - 1) / 2 + 1 : W;
         // level1: the row-streaming kernel (lowc1s_kernel, kind 5) from the batch at which bands of >= 8 output rows give every wave
-        // slot of the chip a strip (cp_set_debug 262144: never, 1073741824: at any size -- tests)
-        if (kind == 2 && m->lowc.count(name + ".rows") && !(g_dbg & 262144) &&
-            ((g_dbg & 1073741824) || (long)B * ((Wo + 31) / 32) * ((Ho + 7) / 8) >= 2048))
+        // slot of the chip a strip (CP_SEL_LEVEL1_ROWS_NEVER / _ALWAYS: never / at any size -- tests)
+        if (kind == 2 && m->lowc.count(name + ".rows") && !(g_dbg & CP_SEL_LEVEL1_ROWS_NEVER) &&
+            ((g_dbg & CP_SEL_LEVEL1_ROWS_ALWAYS) || (long)B * ((Wo + 31) / 32) * ((Ho + 7) / 8) >= 2048))
             kind = 5;
         auto it = m->lowc.find(kind == 5 ? name + ".rows" : name);
         if (it == m->lowc.end()) return Tensor();
@@ -1338,7 +1339,7 @@ struct Fwd {
         for (size_t i = 0; i < m->headw.size(); ++i) {
             const HeadW& hw = m->headw[i];
             const bool sg = sigmoid_hm && (hw.name == "hm" || hw.name == "hm_hp");
-            if (hw.w2_hi && m->precision == CP_PREC_F16X3 && !m->tap_name && !(g_dbg & 32) &&
+            if (hw.w2_hi && m->precision == CP_PREC_F16X3 && !m->tap_name && !(g_dbg & CP_SEL_NO_HEAD_FUSION) &&
                 fused_head(hw, cnv, sg, m->dry ? (float*)0x1000 : head_out[i]))
                 continue;
             role = CP_ROLE_HEAD;
@@ -1455,12 +1456,12 @@ struct Fwd {
     void run(int H, int W, const float* images, const float* pre_img, const float* pre_hm, const float* pre_hm_hp,
              float* const* head_out, int sigmoid_hm) {
         init_slots();
-        const bool use_lowc = m->precision == CP_PREC_F16X3 && !(g_dbg & 64) && m->lowc.count("base.base_layer");
+        const bool use_lowc = m->precision == CP_PREC_F16X3 && !(g_dbg & CP_SEL_NO_LOWC) && m->lowc.count("base.base_layer");
         // stem + level0 in one launch when nothing is added to the stem's output (no previous-frame stems) and nobody asks for it
-        // (cp_set_debug 134217728: the two kernels, A/B runs and tests)
+        // (CP_SEL_STEM_LEVEL0_UNFUSED: the two kernels, A/B runs and tests)
         const bool no_pre = m->dry ? m->dry_variant == 1 : (!pre_img && !pre_hm && !pre_hm_hp);
         const bool fuse01 = use_lowc && no_pre && m->lowc.count("base.level0.rows") && m->stem_bound_l > 0.f &&
-                            !(g_dbg & 134217728) && !(m->tap_name && std::strcmp(m->tap_name, "base.base_layer") == 0) &&
+                            !(g_dbg & CP_SEL_STEM_LEVEL0_UNFUSED) && !(m->tap_name && std::strcmp(m->tap_name, "base.base_layer") == 0) &&
                             !m->convs.count("base.pre_img_layer") && !m->convs.count("base.pre_hm_layer") && !m->convs.count("base.pre_hm_hp_layer");
         Tensor l0f;
         if (fuse01) {
@@ -1595,7 +1596,7 @@ struct Fwd {
                 if (st == 0) {
                     // h0 = 0: the three hidden-side convolutions are identically zero (convGRU.py:51,80-84)
                     if (!m->dry) chk(cp_launch_gru_gate(x3.ptr(), nullptr, nullptr, hn.ptr(), M, hn.amax, s));
-                } else if (m->precision == CP_PREC_F16X3 && m->gru_h16_hi && !(g_dbg & 256) &&
+                } else if (m->precision == CP_PREC_F16X3 && m->gru_h16_hi && !(g_dbg & CP_SEL_GRU_UNFUSED) &&
                            (size_t)M * 192 * 4 < (size_t)0xf0000000u) {
                     // hidden-side convolution with the gate arithmetic in its epilogue: h3 is never written
                     if (!m->dry) {
@@ -1687,7 +1688,7 @@ struct Fwd {
                 if (fuse_gn && !m->dry) gn_stats_out = stats;
             }
             const bool sg = sigmoid_hm && (hw.name == "hm" || hw.name == "hm_hp");
-            if (!m->gru && hw.w2_hi && m->precision == CP_PREC_F16X3 && !m->tap_name && !(g_dbg & 32) &&
+            if (!m->gru && hw.w2_hi && m->precision == CP_PREC_F16X3 && !m->tap_name && !(g_dbg & CP_SEL_NO_HEAD_FUSION) &&
                 fused_head(hw, *src, sg, m->dry ? (float*)0x1000 : head_out[i]))
                 continue;
             role = CP_ROLE_HEAD;
@@ -1696,7 +1697,7 @@ struct Fwd {
                 if (fuse_gn) {
                     // statistics came out of the conv epilogue; normalise + affine + ReLU happens in the 1x1 loader
                     const bool affine16 = m->precision == CP_PREC_F16X3 && hw.c1.w16_hi && (hid.H * hid.W) % 128 == 0 &&
-                                          !(g_dbg & 128);
+                                          !(g_dbg & CP_SEL_GN_HEAD_F32);
                     if (affine16) {
                         // f16x3 1x1 kernel: the normalisation pre-folded to y = relu(a*x + d) per (image, channel)
                         ad = make(2 * hid.C, 1, 1);
@@ -1724,7 +1725,7 @@ struct Fwd {
                 }
             }
             role = CP_ROLE_HEAD_FINAL;
-            if (gn_in_a && !(g_dbg & 131072) && hid.C % 64 == 0 && hid.C <= 256 && (hid.H * hid.W) % 64 == 0 &&
+            if (gn_in_a && !(g_dbg & CP_SEL_GN_HEAD_MFMA) && hid.C % 64 == 0 && hid.C <= 256 && (hid.H * hid.W) % 64 == 0 &&
                 ((size_t)B * hid.H * hid.W) % 256 == 0 && hw.classes <= 16 && !m->tap_name) {
                 // float32 vector-ALU kernel (ewise.hip: gn_final_kernel): the layer is an HBM stream of the hidden tensor
                 auto launch = [&]() -> int {
@@ -1859,6 +1860,9 @@ int cp_model_finalize(cp_model* m) {
 }
 
 int cp_set_debug(int flags) {
+    // a bit outside CP_SEL_ALL (unknown, or a retired switch) is refused rather than reinterpreted
+    if (flags & ~CP_SEL_ALL)
+        return fail(CP_ERR_INVALID, "cp_set_debug: unknown switch bits " + std::to_string(flags & ~CP_SEL_ALL));
     g_dbg = flags;
     return CP_OK;
 }
@@ -2547,7 +2551,7 @@ extern "C" int cp_dcnv2_forward(cp_stream_t stream, const float* input, const fl
         return fail(CP_ERR_INVALID, "dcn_v2_forward: bad shape argument (C must be divisible by deformable_group)");
     hipStream_t s = (hipStream_t)stream;
     const bool fast = kh == 3 && kw == 3 && sh == 1 && sw == 1 && ph == 1 && pw == 1 && dh == 1 && dw == 1 &&
-                      deformable_group == 1 && C % 16 == 0 && cp_conv_tile_n(Co) >= 64 && !(g_dbg & 8388608);
+                      deformable_group == 1 && C % 16 == 0 && cp_conv_tile_n(Co) >= 64 && !(g_dbg & CP_SEL_DCN_GENERIC);
     if (!fast) {
         // everything CenterPose does not use (other kernels / strides / dilations, deformable groups, tiny channel
         // counts): the generic float32 kernel on the reference's own layouts, no workspace

@@ -85,8 +85,7 @@ __global__ __launch_bounds__(256, (BDIRECT && EPI == 0 && MT * NT <= 2) ? 3 : 2)
         // head's weights (0.6 MB) in its 4 MB L2, so the shared input is read from HBM once -- head-slowest over the whole
         // map streamed it once per head (2.17 GB per launch at B = 64 against 0.42 GB algorithmic, profiles/pmc_traffic.json
         // of the first grouped form), n-fastest over all heads cycled through 4.1 MB of weights per patch (3 % slower)
-        const int bsel = (p.dbg >> 18) & 3;  // cp_set_debug bits 18-19 (A/B): band of 8 / 128 patches / the whole map
-        const int HEAD_BAND = bsel == 0 ? 32 : bsel == 1 ? 8 : bsel == 2 ? 128 : tiles_m;
+        constexpr int HEAD_BAND = 32;  // (HBM traffic per launch, profiles/NOTES.md round 3: bands of 8 / 128 / the whole map fetch more)
         // fuse_final: one workgroup per (patch, head) -- tiles_n counts heads, tn becomes the head's first hidden tile below
         const int gt = FT ? 1 : p.fuse_gtiles, per_band = HEAD_BAND * tiles_n;
         const int band = tile / per_band, m0 = band * HEAD_BAND;
@@ -666,9 +665,9 @@ bool cp_halo16_supported(const ConvParams& p) {
 // bn: N tile the weights were padded for (32 / 64 / 128)
 int cp_launch_halo16(const ConvParams& p, int bn, hipStream_t stream) {
     if (!cp_halo16_supported(p) || p.CoutPad % bn != 0) return CP_ERR_INVALID;
-    // weight fragments straight from the fragment-ordered copy when the layer has one (cp_set_debug 16384: the LDS-staged
+    // weight fragments straight from the fragment-ordered copy when the layer has one (CP_SEL_HALO_LDS_WEIGHTS: the LDS-staged
     // weight tile instead, A/B runs)
-    const bool direct = p.w16f_hi && p.w16f_lo && !(p.dbg & 16384);
+    const bool direct = p.w16f_hi && p.w16f_lo && !(p.dbg & CP_SEL_HALO_LDS_WEIGHTS);
     if (bn == 128) return direct ? launch_halo<2, 2, 2, 2, true>(p, stream) : launch_halo<2, 2, 2, 2>(p, stream);
     if (bn == 64) return direct ? launch_halo<2, 1, 2, 2, true>(p, stream) : launch_halo<2, 1, 2, 2>(p, stream);
     if (bn == 32) return direct ? launch_halo<1, 1, 4, 1, true>(p, stream) : launch_halo<1, 1, 4, 1>(p, stream);
@@ -677,8 +676,8 @@ int cp_launch_halo16(const ConvParams& p, int bn, hipStream_t stream) {
 
 // the geometry / operand conditions of the two fused forms (their own launchers check the epilogue operands)
 static bool halo16_fused_geometry(const ConvParams& p) {
-    return p.w16f_hi && p.w16f_lo && !(p.dbg & 4096) && !(p.dbg & 16384) && p.KH == 3 && p.KW == 3 && p.stride == 1 &&
-           p.pad == 1 && p.nsrc == 1 && !p.offmask && !p.gn_in_a && !p.gn_in_mr && !p.gn_stats && p.splitk <= 1 &&
+    return p.w16f_hi && p.w16f_lo && !(p.dbg & (CP_SEL_HALO_NEVER | CP_SEL_HALO_LDS_WEIGHTS)) && p.KH == 3 && p.KW == 3 &&
+           p.stride == 1 && p.pad == 1 && p.nsrc == 1 && !p.offmask && !p.gn_in_a && !p.gn_in_mr && !p.gn_stats && p.splitk <= 1 &&
            p.Cin % CK == 0 && p.H % TH == 0 && p.W % TW == 0 && p.H == p.Ho && p.W == p.Wo && p.Kpad16 == 9 * p.Cin &&
            (size_t)p.B * p.H * p.W * p.Cin * 4 < (size_t)0xf0000000u;
 }

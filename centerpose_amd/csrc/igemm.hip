@@ -499,7 +499,7 @@ int cp_launch_splitk_epilogue(const ConvParams& p, hipStream_t stream) {
     const size_t slab_bytes = (size_t)p.B * p.Ho * p.Wo * p.CoutPad * 4;
     const bool quad = p.store == CP_STORE_NHWC && p.Cout % 4 == 0 && p.CoutPad % 4 == 0 && p.ldo % 4 == 0 && p.coff % 4 == 0 &&
                       (!p.res || p.res_ld % 4 == 0) && p.splitk <= 32 && slab_bytes * 32 < (size_t)0xf0000000u &&
-                      total / 4 < (size_t)0x7fffffff && !(p.dbg & 8);  // (cp_set_debug 8: the element-wise form, A/B)
+                      total / 4 < (size_t)0x7fffffff && !(p.dbg & CP_SEL_SPLITK_ELEMENTWISE);  // (the element-wise form, A/B)
     if (quad) {
         int g = (int)((total / 4 + 255) / 256);
         if (g > 4096) g = 4096;

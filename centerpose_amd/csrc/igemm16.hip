@@ -14,341 +14,18 @@
 //     the row (see swz()) so that ds_read_b128 / ds_write_b64 lane groups are bank-conflict free;
 //   * weights are split and packed once at model load as [co][tap][ci] binary16 pairs (hi / lo arrays);
 //   * BK = 32 (two 32x32x16 MFMA k-steps per LDS tile).
-// Kernels: igemm16p_kernel (hand-pipelined K loop; all non-DCN layers, optional fused prediction head) and
-// igemm16_kernel (previous loop structure; DCN gather layers).  Requirements: every source's channel count % 32 == 0;
+// Kernel: igemm16p_kernel (hand-pipelined K loop, optional fused prediction head); the DCNv2 layers run in dcn16*.hip.
+// Requirements: every source's channel count % 32 == 0;
 // the 16-channel layers at the top of the network run in lowc.hip, the <= 16-wide GroupNorm'd final 1x1 heads on the
 // exact-f32 kernel.
 #include "igemm16_common.h"
 
 namespace {
 
-// PF2: two register sets for the global->LDS staging, i.e. tile t+2 is in flight while tile t is multiplied (a
-// 32-deep K-step is only ~770 MFMA cycles per wave, shorter than an L2 round trip under load).
-template <int MT, int NT, int WM, int WN, bool DCN, bool MULTISRC, bool PF2>
-__global__ __launch_bounds__(NT16, (DCN && NT == 1) ? 3 : 2) void igemm16_kernel(const ConvParams p, const int tiles_m, const int tiles_n) {
-    typedef Frag<32> F;
-    typedef F::acc_t acc_t;
-    constexpr int BM = 32 * MT * WM, BN = 32 * NT * WN;
-    static_assert(WM * WN * 64 == NT16, "4 waves");
-    constexpr int A_SLOTS = BM * BK16 / 4 / NT16;          // float4 per thread per K-step
-    constexpr int B_CHUNKS = BN * BK16 * 2 / 16;            // 16-byte chunks per array (hi or lo)
-    constexpr int B_SLOTS = (B_CHUNKS + NT16 - 1) / NT16;   // per array
-    constexpr int A_SZ = BM * LDH, B_SZ = BN * LDH;         // halfs per array per buffer
-    constexpr int BUF = 2 * A_SZ + 2 * B_SZ;
-    // two distinct LDS objects (not one array): in the fused steady state the stores go to one buffer and the
-    // fragment reads to the other, and the compiler may only interleave them if it can prove they do not alias
-    __shared__ __attribute__((aligned(16))) _Float16 lds0[BUF];
-    __shared__ __attribute__((aligned(16))) _Float16 lds1[BUF];
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wid = tid >> 6;
-    const int wm = wid / WN, wn = wid % WN;
-    const int tile = tile_of_block(tiles_m, tiles_n);
-    const int tn = tile % tiles_n, tm = tile / tiles_n;
-    const int M = p.B * p.Ho * p.Wo;
-    PixelDecomp pdec;
-    pdec.init(p.Ho, p.Wo, M);
-
-    // ---- per-thread A-slot geometry: slot j covers pixel row (tid / 8) + 32 * j, float4 column tid % 8 ----
-    const int k4 = tid & 7;
-    int a_b[A_SLOTS], a_h0[A_SLOTS], a_w0[A_SLOTS], a_pix0[A_SLOTS];
-    unsigned a_vmask[A_SLOTS], a_byte0[A_SLOTS];
-    bool a_ok[A_SLOTS];
-#pragma unroll
-    for (int j = 0; j < A_SLOTS; ++j) {
-        const int m = tm * BM + (tid >> 3) + j * 32;
-        a_ok[j] = m < M;
-        const int mm = a_ok[j] ? m : 0;
-        int b, ho, wo;
-        pdec.split(mm, &b, &ho, &wo);
-        a_b[j] = b;
-        a_h0[j] = ho * p.stride - p.pad;
-        a_w0[j] = wo * p.stride - p.pad;
-        a_pix0[j] = (b * p.H + a_h0[j]) * p.W + a_w0[j];
-        a_byte0[j] = (unsigned)(a_pix0[j] * p.src_c[0] + k4 * 4) * 4u;  // single-source fast path (wraps for halo; masked)
-        a_vmask[j] = (!DCN && a_ok[j]) ? tap_valid_mask(a_h0[j], a_w0[j], p.H, p.W, p.KH, p.KW) : 0u;
-    }
-
-    float4 a_reg0[A_SLOTS], a_reg1[PF2 ? A_SLOTS : 1];
-    u32x4 bh_reg0[B_SLOTS], bl_reg0[B_SLOTS], bh_reg1[PF2 ? B_SLOTS : 1], bl_reg1[PF2 ? B_SLOTS : 1];
-    const int nk = p.Kpad16 / BK16;
-    int kt0, kt1;
-    splitk_range(p, nk, &kt0, &kt1);
-    int u_tap = 0, u_kh = 0, u_kw = 0, u_c0 = 0, u_src = 0, u_cs = 0;
-    bool u_first = true;
-    if (kt0 > 0) {
-        const int k0 = kt0 * BK16;
-        u_tap = k0 / p.Cin;
-        u_c0 = k0 - u_tap * p.Cin;
-        u_kh = u_tap / p.KW;
-        u_kw = u_tap - u_kh * p.KW;
-        u_cs = u_c0;
-        if (MULTISRC) {
-            for (int q = 0; q < 3; ++q) {
-                const int cur = q == 0 ? p.src_c[0] : q == 1 ? p.src_c[1] : p.src_c[2];
-                if (u_src == q && u_cs >= cur) { u_cs -= cur; ++u_src; }
-            }
-        }
-    }
-    int d_idx[DCN ? A_SLOTS : 1][4];
-    float d_w[DCN ? A_SLOTS : 1][4];
-    // power-of-two pre-scale of the activations (ConvParams::in_amax); DCN folds it into the bilinear weights
-    float afwd, ainv;
-    conv_in_scale(p, &afwd, &ainv);
-
-    // weights: [CoutPad][Kpad16] binary16, k contiguous; chunk f -> row n = f / 4, 16-byte column f % 4
-    const _Float16* wh = reinterpret_cast<const _Float16*>(p.w16_hi);
-    const _Float16* wl = reinterpret_cast<const _Float16*>(p.w16_lo);
-    const unsigned w_bytes = (unsigned)((size_t)p.CoutPad * p.Kpad16 * 2);
-    const __amdgpu_buffer_rsrc_t r_wh = make_rsrc(wh, w_bytes), r_wl = make_rsrc(wl, w_bytes);
-    const unsigned img_px = (unsigned)p.B * p.H * p.W;
-    const __amdgpu_buffer_rsrc_t r_s0 = make_rsrc(p.src[0], img_px * p.src_c[0] * 4u);
-    const __amdgpu_buffer_rsrc_t r_s1 = make_rsrc(MULTISRC ? p.src[1] : p.src[0], MULTISRC ? img_px * p.src_c[1] * 4u : 0u);
-    const __amdgpu_buffer_rsrc_t r_s2 = make_rsrc(MULTISRC && p.nsrc > 2 ? p.src[2] : p.src[0], MULTISRC && p.nsrc > 2 ? img_px * p.src_c[2] * 4u : 0u);
-    const __amdgpu_buffer_rsrc_t r_s3 = make_rsrc(MULTISRC && p.nsrc > 3 ? p.src[3] : p.src[0], MULTISRC && p.nsrc > 3 ? img_px * p.src_c[3] * 4u : 0u);
-    unsigned b_off[B_SLOTS];  // byte offsets into the packed binary16 weights
-#pragma unroll
-    for (int j = 0; j < B_SLOTS; ++j) {
-        const int f = tid + j * NT16;
-        b_off[j] = (unsigned)(((size_t)(tn * BN + f / 4) * p.Kpad16 + (f % 4) * 8 + (size_t)kt0 * BK16) * 2);
-    }
-
-    auto load_tile = [&](float4* a_reg, u32x4* bh_reg, u32x4* bl_reg) {
-#pragma unroll
-        for (int j = 0; j < B_SLOTS; ++j) {
-            const int f = tid + j * NT16;
-            if (B_CHUNKS % NT16 == 0 || f < B_CHUNKS) {
-                bh_reg[j] = __builtin_amdgcn_raw_buffer_load_b128(r_wh, (int)b_off[j], 0, 0);
-                bl_reg[j] = __builtin_amdgcn_raw_buffer_load_b128(r_wl, (int)b_off[j], 0, 0);
-                b_off[j] += BK16 * 2;
-            }
-        }
-        if (!DCN) {
-            __amdgpu_buffer_rsrc_t rs = r_s0;
-            int sc = p.src_c[0];
-            if (MULTISRC) {
-                if (u_src == 1) { rs = r_s1; sc = p.src_c[1]; }
-                else if (u_src == 2) { rs = r_s2; sc = p.src_c[2]; }
-                else if (u_src == 3) { rs = r_s3; sc = p.src_c[3]; }
-            }
-            const int tap_pix = u_kh * p.W + u_kw;
-            const int coff = u_cs + k4 * 4;
-            const unsigned bit = 1u << u_tap;
-            if (MULTISRC) {
-#pragma unroll
-                for (int j = 0; j < A_SLOTS; ++j) {
-                    const unsigned off = (unsigned)((a_pix0[j] + tap_pix) * sc + coff) * 4u;
-                    a_reg[j] = buf_ld4(rs, (a_vmask[j] & bit) ? off : OOB);
-                }
-            } else {
-                // per-slot byte base is fixed; the (tap, channel) part is wave-uniform scalar arithmetic
-                const unsigned uoff = (unsigned)(tap_pix * sc + u_cs) * 4u;
-#pragma unroll
-                for (int j = 0; j < A_SLOTS; ++j) a_reg[j] = buf_ld4(rs, (a_vmask[j] & bit) ? a_byte0[j] + uoff : OOB);
-            }
-        } else {
-            const int C = p.Cin;
-            if (u_c0 == 0 || u_first) {
-                u_first = false;
-#pragma unroll
-                for (int j = 0; j < A_SLOTS; ++j) {
-                    int i0 = (int)OOB_BASE, i1 = (int)OOB_BASE, i2 = (int)OOB_BASE, i3 = (int)OOB_BASE;
-                    float w1 = 0.f, w2 = 0.f, w3 = 0.f, w4 = 0.f;
-                    if (a_ok[j]) {
-                        const size_t pix = (size_t)(a_b[j] * p.H + (a_h0[j] + p.pad)) * p.W + (a_w0[j] + p.pad);
-                        const float* om = p.offmask + pix * 32;
-                        const float dh = om[2 * u_tap], dw = om[2 * u_tap + 1], mk = om[18 + u_tap] * afwd;
-                        const float h_im = (float)(a_h0[j] + u_kh) + dh;
-                        const float w_im = (float)(a_w0[j] + u_kw) + dw;
-                        if (h_im > -1.f && w_im > -1.f && h_im < (float)p.H && w_im < (float)p.W) {
-                            const int h_lo = (int)floorf(h_im), w_lo = (int)floorf(w_im);
-                            const int h_hi = h_lo + 1, w_hi = w_lo + 1;
-                            const float lh = h_im - (float)h_lo, lw = w_im - (float)w_lo;
-                            const float hh = 1.f - lh, hw = 1.f - lw;
-                            // byte offsets of the 4 corners' channel vectors (invalid corners keep OOB_BASE, which
-                            // stays out of range after the small per-K-step channel offset is added)
-                            const int bb = a_b[j] * p.H;
-                            const int cb = C * 4;
-                            if (h_lo >= 0 && w_lo >= 0) i0 = ((bb + h_lo) * p.W + w_lo) * cb;
-                            if (h_lo >= 0 && w_hi <= p.W - 1) i1 = ((bb + h_lo) * p.W + w_hi) * cb;
-                            if (h_hi <= p.H - 1 && w_lo >= 0) i2 = ((bb + h_hi) * p.W + w_lo) * cb;
-                            if (h_hi <= p.H - 1 && w_hi <= p.W - 1) i3 = ((bb + h_hi) * p.W + w_hi) * cb;
-                            w1 = hh * hw * mk; w2 = hh * lw * mk; w3 = lh * hw * mk; w4 = lh * lw * mk;
-                        }
-                    }
-                    d_idx[j][0] = i0; d_idx[j][1] = i1; d_idx[j][2] = i2; d_idx[j][3] = i3;
-                    d_w[j][0] = w1; d_w[j][1] = w2; d_w[j][2] = w3; d_w[j][3] = w4;
-                }
-            }
-            const unsigned coff = (unsigned)(u_c0 + k4 * 4) * 4u;
-#pragma unroll
-            for (int j = 0; j < A_SLOTS; ++j) {
-                const float4 v1 = buf_ld4(r_s0, (unsigned)d_idx[j][0] + coff);
-                const float4 v2 = buf_ld4(r_s0, (unsigned)d_idx[j][1] + coff);
-                const float4 v3 = buf_ld4(r_s0, (unsigned)d_idx[j][2] + coff);
-                const float4 v4 = buf_ld4(r_s0, (unsigned)d_idx[j][3] + coff);
-                const float w1 = d_w[j][0], w2 = d_w[j][1], w3 = d_w[j][2], w4 = d_w[j][3];
-                float4 v;
-                v.x = fmaf(w4, v4.x, fmaf(w3, v3.x, fmaf(w2, v2.x, w1 * v1.x)));
-                v.y = fmaf(w4, v4.y, fmaf(w3, v3.y, fmaf(w2, v2.y, w1 * v1.y)));
-                v.z = fmaf(w4, v4.z, fmaf(w3, v3.z, fmaf(w2, v2.z, w1 * v1.z)));
-                v.w = fmaf(w4, v4.w, fmaf(w3, v3.w, fmaf(w2, v2.w, w1 * v1.w)));
-                a_reg[j] = v;
-            }
-        }
-        // advance the wave-uniform K walk by one 32-wide step
-        u_c0 += BK16;
-        u_cs += BK16;
-        if (u_c0 >= p.Cin) {
-            u_c0 = 0; u_cs = 0; u_src = 0;
-            ++u_tap;
-            if (++u_kw == p.KW) { u_kw = 0; ++u_kh; }
-        } else if (MULTISRC) {
-            const int cur = u_src == 0 ? p.src_c[0] : u_src == 1 ? p.src_c[1] : u_src == 2 ? p.src_c[2] : p.src_c[3];
-            if (u_cs >= cur) { u_cs = 0; ++u_src; }
-        }
-    };
-
-    auto store_tile = [&](int buf, const float4* a_reg, const u32x4* bh_reg, const u32x4* bl_reg) {
-        _Float16* Ah = buf ? lds1 : lds0;
-        _Float16* Al = Ah + A_SZ;
-        _Float16* Bh = Al + A_SZ;
-        _Float16* Bl = Bh + B_SZ;
-#pragma unroll
-        for (int j = 0; j < A_SLOTS; ++j) {
-            const int row = (tid >> 3) + j * 32;
-            const float as = DCN ? 1.f : afwd;
-            const Split2 s0 = split2(a_reg[j].x * as, a_reg[j].y * as), s1 = split2(a_reg[j].z * as, a_reg[j].w * as);
-            const int col = ((((k4 >> 1) ^ swz(row)) << 1) | (k4 & 1)) * 4;  // halfs
-            *reinterpret_cast<u32x2*>(Ah + row * LDH + col) = u32x2{s0.hi, s1.hi};
-            *reinterpret_cast<u32x2*>(Al + row * LDH + col) = u32x2{s0.lo, s1.lo};
-        }
-#pragma unroll
-        for (int j = 0; j < B_SLOTS; ++j) {
-            const int f = tid + j * NT16;
-            if (B_CHUNKS % NT16 == 0 || f < B_CHUNKS) {
-                const int n = f / 4, c = f % 4;
-                *reinterpret_cast<u32x4*>(Bh + n * LDH + (c ^ swz(n)) * 8) = bh_reg[j];
-                *reinterpret_cast<u32x4*>(Bl + n * LDH + (c ^ swz(n)) * 8) = bl_reg[j];
-            }
-        }
-    };
-
-    acc_t acc[MT][NT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int r = 0; r < F::NACC; ++r) acc[i][j][r] = 0.f;
-
-    const int lrow = lane >> 5;  // which 8-wide k group of the 16-deep MFMA step
-    const int lcol = lane & 31;
-
-    auto mma_tile = [&](int buf) {
-        // fragment rows are (tile base, a multiple of 32) + lcol, so the swizzle only depends on lcol
-        const _Float16* base = buf ? lds1 : lds0;
-        const _Float16* Ah = base + (wm * (MT * 32) + lcol) * LDH;
-        const _Float16* Al = Ah + A_SZ;
-        const _Float16* Bh = base + 2 * A_SZ + (wn * (NT * 32) + lcol) * LDH;
-        const _Float16* Bl = Bh + B_SZ;
-#pragma unroll
-        for (int ks = 0; ks < BK16 / 16; ++ks) {
-            const int co = (((ks * 2 + lrow) ^ swz(lcol)) * 8);
-            h8 ah[MT], al[MT], bh[NT], bl[NT];
-#pragma unroll
-            for (int i = 0; i < MT; ++i) {
-                ah[i] = *reinterpret_cast<const h8*>(Ah + i * 32 * LDH + co);
-                al[i] = *reinterpret_cast<const h8*>(Al + i * 32 * LDH + co);
-            }
-#pragma unroll
-            for (int j = 0; j < NT; ++j) {
-                bh[j] = *reinterpret_cast<const h8*>(Bh + j * 32 * LDH + co);
-                bl[j] = *reinterpret_cast<const h8*>(Bl + j * 32 * LDH + co);
-            }
-            // term-major order: an accumulator is reused only after the MT*NT-1 other fragments' MFMAs, so no
-            // MFMA waits on the result of the one issued just before it
-#pragma unroll
-            for (int i = 0; i < MT; ++i)
-#pragma unroll
-                for (int j = 0; j < NT; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < MT; ++i)
-#pragma unroll
-                for (int j = 0; j < NT; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < MT; ++i)
-#pragma unroll
-                for (int j = 0; j < NT; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-        }
-    };
-
-    if (!PF2) {
-        load_tile(a_reg0, bh_reg0, bl_reg0);
-        store_tile(0, a_reg0, bh_reg0, bl_reg0);
-        __syncthreads();
-        for (int kt = kt0; kt < kt1; ++kt) {
-            const int buf = (kt - kt0) & 1;
-            if (kt + 1 < kt1) load_tile(a_reg0, bh_reg0, bl_reg0);
-            mma_tile(buf);
-            if (kt + 1 < kt1) store_tile(buf ^ 1, a_reg0, bh_reg0, bl_reg0);
-            __syncthreads();
-        }
-    } else {
-        // tiles t+1 and t+2 are in registers / in flight while tile t is multiplied out of LDS.  In the steady state
-        // the conversion + LDS store of tile t+1 is issued in the same basic block as the MFMAs of tile t and the
-        // scheduler is told to interleave them (one MFMA, a few VALU, an LDS op, ...): the in-order wave then
-        // converts and stores under the 32-cycle shadow of each MFMA instead of after all of them.
-        const int n = kt1 - kt0;
-        load_tile(a_reg0, bh_reg0, bl_reg0);
-        if (n > 1) load_tile(a_reg1, bh_reg1, bl_reg1);
-        store_tile(0, a_reg0, bh_reg0, bl_reg0);
-        __syncthreads();
-        auto fused = [&](int bufc, const float4* a_reg, const u32x4* bh_reg, const u32x4* bl_reg) {
-            store_tile(bufc ^ 1, a_reg, bh_reg, bl_reg);
-            mma_tile(bufc);
-#pragma unroll
-            for (int g = 0; g < MT * NT * 6; ++g) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // one MFMA
-                __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);  // three VALU (conversion)
-                if (g & 1) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);  // an LDS write
-                else __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);        // an LDS read (next fragments)
-            }
-        };
-        int kt = 0;
-        while (kt + 3 < n) {
-            load_tile(a_reg0, bh_reg0, bl_reg0);      // tile kt+2 -> set 0
-            fused(0, a_reg1, bh_reg1, bl_reg1);       // store tile kt+1 (set 1) into buffer 1, multiply buffer 0
-            __syncthreads();
-            load_tile(a_reg1, bh_reg1, bl_reg1);      // tile kt+3 -> set 1
-            fused(1, a_reg0, bh_reg0, bl_reg0);       // store tile kt+2 (set 0) into buffer 0, multiply buffer 1
-            __syncthreads();
-            kt += 2;
-        }
-        for (; kt < n; kt += 2) {  // tail: same order with the loads / stores guarded
-            if (kt + 2 < n) load_tile(a_reg0, bh_reg0, bl_reg0);
-            if (kt + 1 < n) store_tile(1, a_reg1, bh_reg1, bl_reg1);
-            mma_tile(0);
-            __syncthreads();
-            if (kt + 1 >= n) break;
-            if (kt + 3 < n) load_tile(a_reg1, bh_reg1, bl_reg1);
-            if (kt + 2 < n) store_tile(0, a_reg0, bh_reg0, bl_reg0);
-            mma_tile(1);
-            __syncthreads();
-        }
-    }
-    if (p.splitk > 1) igemm_store_partial<32, MT, NT, WM, WN>(p, acc, tm, tn, wm, wn, lane, blockIdx.y);
-    else igemm_epilogue<32, MT, NT, WM, WN>(p, acc, tm, tn, wm, wn, lane, ainv);
-}
-
 // ---------------------------------------------------------------------------------------------------------------
-// Software-pipelined K loop (non-DCN layers).  Same tiles, LDS layout, loaders and epilogue as igemm16_kernel, but the
-// order in which a wave issues its work is written out by hand and pinned with sched_barrier, because the wave is
-// in-order and the MFMA pipe is only busy while something else is NOT making the wave wait:
+// Software-pipelined K loop.  The order in which a wave issues its work is written out by hand and pinned with
+// sched_barrier, because the wave is in-order and the MFMA pipe is only busy while something else is NOT making the wave
+// wait:
 //
 //   iteration t (tile t in LDS buffer t&1; fragment sets F0 = k-step 0, F1 = k-step 1; one register set G holds the
 //   global data of tile t+1):
@@ -814,21 +491,14 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void igemm16p_kernel(const ConvPar
     else igemm_epilogue<32, MT, NT, WM, WN>(p, acc, tm, tn, wm, wn, lane, ainv);
 }
 
-template <int MT, int NT, int WM, int WN, bool DCN, bool MULTISRC>
+template <int MT, int NT, int WM, int WN, bool MULTISRC>
 int launch16(const ConvParams& p, hipStream_t stream) {
-    constexpr bool PF2 = false;  // the DCN loader blends on arrival: one register set
     constexpr int BM = 32 * MT * WM, BN = 32 * NT * WN;
     const int M = p.B * p.Ho * p.Wo;
     const int tiles_m = (M + BM - 1) / BM, tiles_n = p.CoutPad / BN;
     if (p.CoutPad % BN != 0 || p.Kpad16 % BK16 != 0) return CP_ERR_INVALID;
     const dim3 grid(tiles_m * tiles_n, p.splitk > 1 ? p.splitk : 1);
-    if constexpr (!DCN) {
-        // every non-DCN layer runs the pipelined kernel; igemm16_kernel is only instantiated for the DCN gather layers
-        hipLaunchKernelGGL((igemm16p_kernel<MT, NT, WM, WN, MULTISRC>), grid, dim3(NT16), 0, stream, p, tiles_m, tiles_n);
-        return hipGetLastError() == hipSuccess ? CP_OK : CP_ERR_LAUNCH;
-    }
-    hipLaunchKernelGGL((igemm16_kernel<MT, NT, WM, WN, DCN, MULTISRC, PF2>), grid, dim3(NT16), 0, stream, p, tiles_m,
-                       tiles_n);
+    hipLaunchKernelGGL((igemm16p_kernel<MT, NT, WM, WN, MULTISRC>), grid, dim3(NT16), 0, stream, p, tiles_m, tiles_n);
     return hipGetLastError() == hipSuccess ? CP_OK : CP_ERR_LAUNCH;
 }
 
@@ -962,53 +632,53 @@ static int conv16_tile_n(const ConvParams& p) {
 }
 
 // DCNv2 layers whose launch fills the chip gather from an LDS-staged halo (dcn16p.hip); small launches keep dcn16.hip
-// (split-K).  cp_set_debug: 32768 = never, 65536 = every eligible layer (tests, A/B runs).
+// (split-K).  CP_SEL_DCN16P_NEVER / _ALWAYS: never / every eligible layer (tests, A/B runs).
 static bool dcn16p_wanted(const ConvParams& p) {
-    if ((p.dbg & 32768) || (p.dbg & 1024) || !cp_dcn16p_supported(p)) return false;
+    if ((p.dbg & CP_SEL_DCN16P_NEVER) || !cp_dcn16p_supported(p)) return false;
     // from 64 blocks up (round 3; 256 before): at batch 1 the 128 x 128 and 64 x 64 maps are 128 / 64-block launches, and one
     // patch-resident launch beats the split-K gather kernel + its epilogue launch (frame 1.666 -> 1.627 ms, 2.089 -> 2.044;
     // thresholds 128 / 32 / none: 1.639 / 1.643 / 1.637)
-    return (p.dbg & 65536) || cp_dcn16p_blocks(p) >= 64;
+    return (p.dbg & CP_SEL_DCN16P_ALWAYS) || cp_dcn16p_blocks(p) >= 64;
 }
 
 // ... and, when every resident workgroup gets many (patch, N tile) items, from the persistent streamed form of the same
 // gather (dcn16s.hip): measured per layer shape at B = 64 (tools/dcn_ab.py, profiles/r04_dcn_ab.txt) it is ahead from 8 items
 // per workgroup (64 -> 64 @ 128 x 128: -3 %, 128 -> 128 @ 64 x 64: -3 %) and behind below that (2 - 4 items: +3 ... +6 %).
-// cp_set_debug: 1048576 = never, 2097152 = every eligible launch (tests, A/B runs).
+// CP_SEL_DCN16S_NEVER / _ALWAYS: never / every eligible launch (tests, A/B runs).
 static bool dcn16s_wanted(const ConvParams& p) {
-    if ((p.dbg & 1048576) || !dcn16p_wanted(p) || !cp_dcn16s_supported(p)) return false;
-    if (cp_dcn16p_wide(p) && !(p.dbg & 2097152)) return false;  // 128 output channels per tile: the 128-wide patch kernel (round 5)
-    return (p.dbg & 2097152) || cp_dcn16s_items(p) >= 4096;
+    if ((p.dbg & CP_SEL_DCN16S_NEVER) || !dcn16p_wanted(p) || !cp_dcn16s_supported(p)) return false;
+    if (cp_dcn16p_wide(p) && !(p.dbg & CP_SEL_DCN16S_ALWAYS)) return false;  // 128 output channels per tile: the 128-wide patch kernel (round 5)
+    return (p.dbg & CP_SEL_DCN16S_ALWAYS) || cp_dcn16s_items(p) >= 4096;
 }
 
 // ... and the layers without whole 128-channel tiles (Cout = 64: no wider tile to share a blend) from the three-workgroups-per-CU
 // form (dcn16t.hip) once the launch has more workgroups than the chip holds at three per CU: B = 64, same box, alternating
 // launches (profiles/r06_dcn16t_ab.txt): 64 -> 64 @128^2 (8192 workgroups) 393 (dcn16s) / 414 (dcn16p) -> 360 us, 128 -> 64 @64^2
 // (2048) 183 -> 169, 256 -> 64 @32^2 (512) 87 -> 91 (stays on dcn16p).
-// cp_set_debug: 33554432 = every eligible launch, 67108864 = never (tests, A/B runs).
+// CP_SEL_DCN16T_ALWAYS / _NEVER: every eligible launch / never (tests, A/B runs).
 static bool dcn16t_wanted(const ConvParams& p) {
-    if ((p.dbg & 67108864) || !dcn16p_wanted(p) || !cp_dcn16t_supported(p)) return false;
-    if (p.dbg & 33554432) return true;
-    if (p.dbg & 2097152) return false;  // (dcn16s asked for by name)
+    if ((p.dbg & CP_SEL_DCN16T_NEVER) || !dcn16p_wanted(p) || !cp_dcn16t_supported(p)) return false;
+    if (p.dbg & CP_SEL_DCN16T_ALWAYS) return true;
+    if (p.dbg & CP_SEL_DCN16S_ALWAYS) return false;  // (dcn16s asked for by name)
     return !cp_dcn16p_wide(p) && cp_dcn16p_blocks(p) >= 1024;
 }
 
 // 64 -> <= 32 channel 3x3 layers (DCN offset / mask convolutions) with at least one (strip, band) job per wave slot of the chip: the
-// row-streaming kernel of strm16.hip.  cp_set_debug: 268435456 = never, 536870912 = every eligible layer (tests).
+// row-streaming kernel of strm16.hip.  CP_SEL_STRM16_NEVER / _ALWAYS: never / every eligible layer (tests).
 static bool strm16_wanted(const ConvParams& p) {
-    if ((p.dbg & 268435456) || (p.dbg & 4096) || !cp_strm16_supported(p)) return false;
-    return (p.dbg & 536870912) || cp_strm16_jobs(p) >= 1024;
+    if ((p.dbg & CP_SEL_STRM16_NEVER) || (p.dbg & CP_SEL_HALO_NEVER) || !cp_strm16_supported(p)) return false;
+    return (p.dbg & CP_SEL_STRM16_ALWAYS) || cp_strm16_jobs(p) >= 1024;
 }
 
 static bool halo16_wanted(const ConvParams& p, int bn) {
-    if ((p.dbg & 4096) || p.gn_in_a || !cp_halo16_supported(p)) return false;
+    if ((p.dbg & CP_SEL_HALO_NEVER) || p.gn_in_a || !cp_halo16_supported(p)) return false;
     // with the weight fragments coming straight from L2 (no barrier inside a chunk) the halo kernel beats the per-tap
-    // implicit GEMM on every N tile; with an LDS weight tile only on the 32-wide one (8192: everywhere anyway, A/B runs)
-    return bn == 32 || (p.w16f_hi && p.w16f_lo && !(p.dbg & 16384)) || (p.dbg & 8192);
+    // implicit GEMM on every N tile; with an LDS weight tile only on the 32-wide one (CP_SEL_HALO_ALWAYS: everywhere anyway, A/B runs)
+    return bn == 32 || (p.w16f_hi && p.w16f_lo && !(p.dbg & CP_SEL_HALO_LDS_WEIGHTS)) || (p.dbg & CP_SEL_HALO_ALWAYS);
 }
 
-// 1x1 layers: the register-only stream of pw16.hip (cp_set_debug 4194304: the LDS-staged loop instead, A/B runs)
-static bool pw16_wanted(const ConvParams& p) { return !(p.dbg & 4194304) && cp_pw16_supported(p); }
+// 1x1 layers: the register-only stream of pw16.hip (CP_SEL_PW16_NEVER: the LDS-staged loop instead, A/B runs)
+static bool pw16_wanted(const ConvParams& p) { return !(p.dbg & CP_SEL_PW16_NEVER) && cp_pw16_supported(p); }
 
 bool cp_conv16_supported(const ConvParams& p) {
     if (!p.w16_hi || !p.w16_lo || p.Cin % BK16 != 0 || p.KH * p.KW > 32) return false;
@@ -1044,27 +714,25 @@ int cp_launch_conv16(const ConvParams& p, hipStream_t stream) {
     if (p.offmask) {
         if (p.KH != 3 || p.KW != 3 || p.stride != 1 || p.pad != 1 || p.nsrc != 1 || p.H != p.Ho || p.W != p.Wo)
             return CP_ERR_INVALID;
-        // dcn16.hip: the software-pipelined gather kernel; cp_set_debug(1024) keeps the previous un-pipelined loop
-        // (igemm16_kernel<DCN>) for A/B runs, 2048 selects the other wave count of the new kernel
+        // the patch-resident gathers where the launch fills the chip, dcn16.hip's software-pipelined gather otherwise
         if (dcn16t_wanted(p)) return cp_launch_dcn16t(p, stream);
         if (dcn16s_wanted(p)) return cp_launch_dcn16s(p, stream);
         if (dcn16p_wanted(p)) return cp_launch_dcn16p(p, stream);
-        if (!(p.dbg & 1024)) return cp_launch_dcn16(p, bn, (p.dbg & 2048) ? 1 : 0, stream);
-        return bn == 128 ? launch16<2, 2, 2, 2, true, false>(p, stream) : launch16<2, 1, 2, 2, true, false>(p, stream);
+        return cp_launch_dcn16(p, bn, stream);
     }
     // 3x3 / stride 1 layers with full 8x16 patches can run on the halo-resident kernel (halo16.hip).  Measured on the
     // dlav1_34 B=32 step (profiles/r02_halo_ab.txt): N tile 32 (conv_offset_mask) 62 -> 103 TFLOP/s, N 64 223 -> 212,
     // N 128 288 -> 290: with 64+ output channels the loop is bound by MFMA issue + fragment reads at the sustained
     // clock, not by the A-side loads / conversion the halo removes, so only the 32-wide tile uses it by default.
-    // cp_set_debug: 4096 = never, 8192 = every eligible layer (A/B runs).
+    // CP_SEL_HALO_NEVER / _ALWAYS: never / every eligible layer (A/B runs).
     // small launches on 64 x 64 tiles (ConvParams::tile_m): the LDS-staged loop, whatever the layer shape
-    if (bn == 64 && p.tile_m == 64) return cat ? launch16<1, 1, 2, 2, false, true>(p, stream) : launch16<1, 1, 2, 2, false, false>(p, stream);
+    if (bn == 64 && p.tile_m == 64) return cat ? launch16<1, 1, 2, 2, true>(p, stream) : launch16<1, 1, 2, 2, false>(p, stream);
     if (bn == 32 && strm16_wanted(p)) return cp_launch_strm16(p, stream);
     if (halo16_wanted(p, bn)) return cp_launch_halo16(p, bn, stream);
     if (pw16_wanted(p)) return cp_launch_pw16(p, stream);
-    if (bn == 128) return cat ? launch16<2, 2, 2, 2, false, true>(p, stream) : launch16<2, 2, 2, 2, false, false>(p, stream);
-    if (bn == 64) return cat ? launch16<2, 1, 2, 2, false, true>(p, stream) : launch16<2, 1, 2, 2, false, false>(p, stream);
-    return cat ? launch16<1, 1, 4, 1, false, true>(p, stream) : launch16<1, 1, 4, 1, false, false>(p, stream);
+    if (bn == 128) return cat ? launch16<2, 2, 2, 2, true>(p, stream) : launch16<2, 2, 2, 2, false>(p, stream);
+    if (bn == 64) return cat ? launch16<2, 1, 2, 2, true>(p, stream) : launch16<2, 1, 2, 2, false>(p, stream);
+    return cat ? launch16<1, 1, 4, 1, true>(p, stream) : launch16<1, 1, 4, 1, false>(p, stream);
 }
 
 // kernel-variant ids continue after the exact-f32 ones (cp_conv_variant): 14.. = split-f16 instantiations

@@ -311,7 +311,7 @@ bool cp_pw16_supported(const ConvParams& p) {
 
 int cp_launch_pw16(const ConvParams& p, hipStream_t stream) {
     if (!cp_pw16_supported(p)) return CP_ERR_INVALID;
-    // whole-line A loads through wave-private staging rows (cp_set_debug 4: the fragment-shaped loads of pw16_kernel, A/B runs)
-    if (!(p.dbg & 4)) return p.CoutPad % 128 == 0 ? launch_pw16s<4>(p, stream) : launch_pw16s<2>(p, stream);
+    // whole-line A loads through wave-private staging rows (CP_SEL_PW16_FRAG_A: the fragment-shaped loads of pw16_kernel, A/B runs)
+    if (!(p.dbg & CP_SEL_PW16_FRAG_A)) return p.CoutPad % 128 == 0 ? launch_pw16s<4>(p, stream) : launch_pw16s<2>(p, stream);
     return p.CoutPad % 128 == 0 ? launch_pw16<4>(p, stream) : launch_pw16<2>(p, stream);
 }

@@ -4,7 +4,9 @@ PyTorch-ROCm is only the tensor container / allocator / stream provider here: ev
 ``data_ptr()`` device pointers and the current HIP stream to the library.  There is NO fallback:
 if the shared library is missing or a call fails, a ``RuntimeError`` is raised.
 """
+import contextlib
 import ctypes
+import enum
 import os
 from collections import OrderedDict
 
@@ -182,6 +184,51 @@ def _check(rc, what):
     if rc != 0:
         msg = lib().cp_last_error().decode() if _lib is not None else ""
         raise RuntimeError("centerpose_hip: %s failed with code %d (%s)" % (what, rc, msg))
+
+
+class KernelSel(enum.IntFlag):
+    """The CP_SEL_* kernel-selection switches of include/centerpose_hip_testing.h (name = the header's without CP_SEL_)."""
+    HEADS_SLABS = 0x00000001
+    HEADS_WG_PER_HEAD = 0x00000002
+    PW16_FRAG_A = 0x00000004
+    SPLITK_ELEMENTWISE = 0x00000008
+    TILE128_SMALL = 0x00000010
+    NO_HEAD_FUSION = 0x00000020
+    NO_LOWC = 0x00000040
+    GN_HEAD_F32 = 0x00000080
+    GRU_UNFUSED = 0x00000100
+    NO_PRESCALE = 0x00000200
+    DCN16S_GRID8 = 0x00000400
+    HALO_NEVER = 0x00001000
+    HALO_ALWAYS = 0x00002000
+    HALO_LDS_WEIGHTS = 0x00004000
+    DCN16P_NEVER = 0x00008000
+    DCN16P_ALWAYS = 0x00010000
+    GN_HEAD_MFMA = 0x00020000
+    LEVEL1_ROWS_NEVER = 0x00040000
+    DCN16P_NOT_WIDE = 0x00080000
+    DCN16S_NEVER = 0x00100000
+    DCN16S_ALWAYS = 0x00200000
+    PW16_NEVER = 0x00400000
+    DCN_GENERIC = 0x00800000
+    HEADS_PER_HEAD_LAUNCH = 0x01000000
+    DCN16T_ALWAYS = 0x02000000
+    DCN16T_NEVER = 0x04000000
+    STEM_LEVEL0_UNFUSED = 0x08000000
+    STRM16_NEVER = 0x10000000
+    STRM16_ALWAYS = 0x20000000
+    LEVEL1_ROWS_ALWAYS = 0x40000000
+
+
+@contextlib.contextmanager
+def select_kernels(flags):
+    """Run the block under the kernel-selection switches ``flags`` (KernelSel; cp_set_debug, a test hook) and return to the
+    engine's own choice (0) on the way out, whatever happens inside."""
+    _check(lib().cp_set_debug(int(flags)), "cp_set_debug")
+    try:
+        yield
+    finally:
+        lib().cp_set_debug(0)
 
 
 def _stream():

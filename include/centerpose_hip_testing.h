@@ -10,13 +10,43 @@ extern "C" {
 #endif
 
 /* Kernel SELECTION switches (process-global; 0 = the engine's own choice).  Every bit picks another implementation of the
- * same layer among the ones the library ships -- per-head launches instead of the grouped head launch, the element-wise
- * split-K epilogue instead of the quad form, dcn16p instead of dcn16s, the generic DCN kernel instead of the fused ones,
- * 128-row tiles for small launches, ... (the list is next to g_dbg in csrc/engine.hip) -- so that the parity tests can compare
- * two implementations on one input.  Every combination computes the layer correctly (to the summation-order round-off the
- * tests state); the timing ablations of earlier rounds, under which results were wrong, no longer exist in the library.
- * Bit 512 (operands of the f16x3 products used without the |max| pre-scale) is correct only for inputs inside binary16's
- * range and exists for the range-safety tests. */
+ * same layer among the ones the library ships, so that the parity tests can compare two implementations on one input.
+ * Every combination computes the layer correctly (to the summation-order round-off the tests state), except that
+ * CP_SEL_NO_PRESCALE is correct only for inputs inside binary16's range (it exists for the range-safety tests).
+ * cp_set_debug returns CP_ERR_INVALID, and keeps the current selection, when a bit outside CP_SEL_ALL is set.  Bit 11
+ * (2048, once "alternative DCN wave counts") is unused and refused. */
+#define CP_SEL_HEADS_SLABS 0x00000001          /* grouped fused heads write slabs + a reduction launch (no fuse_final) */
+#define CP_SEL_HEADS_WG_PER_HEAD 0x00000002    /* grouped fused heads: one workgroup per (patch, head), not per patch */
+#define CP_SEL_PW16_FRAG_A 0x00000004          /* 1x1 layers: fragment-shaped A loads (pw16_kernel), not staging rows */
+#define CP_SEL_SPLITK_ELEMENTWISE 0x00000008   /* split-K epilogue element-wise, not the quad form */
+#define CP_SEL_TILE128_SMALL 0x00000010        /* small launches on 128-row tiles, not 64 x 64 */
+#define CP_SEL_NO_HEAD_FUSION 0x00000020       /* prediction heads as separate 3x3 and 1x1 layers */
+#define CP_SEL_NO_LOWC 0x00000040              /* no lowc.hip kernels for the first layers */
+#define CP_SEL_GN_HEAD_F32 0x00000080          /* GroupNorm'd heads' 1x1 on the exact-f32 kernel */
+#define CP_SEL_GRU_UNFUSED 0x00000100          /* ConvGRU step without the fused gate epilogue */
+#define CP_SEL_NO_PRESCALE 0x00000200          /* no activation |max| tracking / pre-scale of f16x3 operands */
+#define CP_SEL_DCN16S_GRID8 0x00000400         /* dcn16s on 8 workgroups, so small launches walk several items each */
+#define CP_SEL_HALO_NEVER 0x00001000           /* halo16 never (per-tap implicit GEMM instead) */
+#define CP_SEL_HALO_ALWAYS 0x00002000          /* halo16 for every eligible N tile, not the 32-wide one only */
+#define CP_SEL_HALO_LDS_WEIGHTS 0x00004000     /* LDS-staged weights in the halo16 kernels, not fragments from L2 */
+#define CP_SEL_DCN16P_NEVER 0x00008000         /* patch-resident DCN kernels (dcn16p / s / t) never */
+#define CP_SEL_DCN16P_ALWAYS 0x00010000        /* patch-resident DCN kernels for launches of any size */
+#define CP_SEL_GN_HEAD_MFMA 0x00020000         /* GroupNorm'd heads' final 1x1 on the matrix cores, not gn_final_kernel */
+#define CP_SEL_LEVEL1_ROWS_NEVER 0x00040000    /* level1 never on the row-streaming lowc kernel */
+#define CP_SEL_DCN16P_NOT_WIDE 0x00080000      /* dcn16p never on the 128-wide N tile */
+#define CP_SEL_DCN16S_NEVER 0x00100000         /* streamed DCN (dcn16s) never */
+#define CP_SEL_DCN16S_ALWAYS 0x00200000        /* dcn16s for every eligible launch */
+#define CP_SEL_PW16_NEVER 0x00400000           /* 1x1 layers on the LDS-staged loop, not pw16.hip */
+#define CP_SEL_DCN_GENERIC 0x00800000          /* cp_dcnv2_forward always on the generic f32 kernel */
+#define CP_SEL_HEADS_PER_HEAD_LAUNCH 0x01000000 /* fused heads one launch per head, not one grouped launch */
+#define CP_SEL_DCN16T_ALWAYS 0x02000000        /* three-workgroup DCN (dcn16t) for every eligible launch */
+#define CP_SEL_DCN16T_NEVER 0x04000000         /* dcn16t never */
+#define CP_SEL_STEM_LEVEL0_UNFUSED 0x08000000  /* stem and level0 as two kernels, not the fused one */
+#define CP_SEL_STRM16_NEVER 0x10000000         /* row-streamed 64 -> <= 32 channel 3x3 layers (strm16) never */
+#define CP_SEL_STRM16_ALWAYS 0x20000000        /* strm16 for layers of any size */
+#define CP_SEL_LEVEL1_ROWS_ALWAYS 0x40000000   /* level1 on the row-streaming lowc kernel at any size */
+#define CP_SEL_ALL 0x7ffff7ff                  /* every defined switch */
+
 int cp_set_debug(int flags);
 
 #ifdef __cplusplus

@@ -16,6 +16,7 @@ from oracle import pnp as opnp
 from oracle.tools import make_goldens as mg
 
 pytestmark = pytest.mark.gpu
+S = hip.KernelSel
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 CONFIGS = [("dla_34", False), ("dlav1_34", False), ("dla_34", True), ("dlav1_34", True)]
 
@@ -140,7 +141,7 @@ def test_dcn_generic_shapes_vs_reference_golden(device, i):
 
 
 def test_dcn_generic_and_fast_path_agree(device):
-    """The same CenterPose-shaped layer through both kernels (cp_set_debug 8388608 forces the generic one)."""
+    """The same CenterPose-shaped layer through both kernels (S.DCN_GENERIC forces the generic one)."""
     g = torch.Generator().manual_seed(9)
     x = torch.randn(2, 64, 32, 32, generator=g)
     w = torch.randn(64, 64, 3, 3, generator=g) / 24.0
@@ -149,11 +150,8 @@ def test_dcn_generic_and_fast_path_agree(device):
     mask = torch.rand(2, 9, 32, 32, generator=g)
     t = [v.to(device) for v in (x, w, b, off, mask)]
     fast = hip.dcn_v2_forward(*t, 3, 3, 1, 1, 1, 1, 1, 1, 1).cpu()
-    hip.lib().cp_set_debug(8388608)
-    try:
+    with hip.select_kernels(S.DCN_GENERIC):
         slow = hip.dcn_v2_forward(*t, 3, 3, 1, 1, 1, 1, 1, 1, 1).cpu()
-    finally:
-        hip.lib().cp_set_debug(0)
     torch.testing.assert_close(fast, slow, rtol=0, atol=2e-5 * float(slow.abs().max()))
 
 
@@ -202,8 +200,8 @@ def test_conv_both_precisions_vs_float64(device, precision, Cin, Cout, k, s, res
 ])
 def test_pointwise_stream_kernel_vs_float64_and_lds_loop(device, f16x3, B, H, W, Cin, Cout, res, act):
     """pw16.hip (1x1 layers as a register-only stream: A fragments straight from global memory, weight fragments from the
-    fragment-ordered copy) against a float64 convolution and against the LDS-staged loop it replaces (cp_set_debug
-    4194304): the same products summed in the same order."""
+    fragment-ordered copy) against a float64 convolution and against the LDS-staged loop it replaces (S.PW16_NEVER):
+    the same products summed in the same order."""
     g = torch.Generator().manual_seed(Cin + Cout + H)
     x = torch.randn(B, Cin, H, W, generator=g)
     w = torch.randn(Cout, Cin, 1, 1, generator=g) / Cin ** 0.5
@@ -215,16 +213,10 @@ def test_pointwise_stream_kernel_vs_float64_and_lds_loop(device, f16x3, B, H, W,
     args = (x.permute(0, 2, 3, 1).contiguous().to(device), w.to(device), None, None,
             r.permute(0, 2, 3, 1).contiguous().to(device) if res else None, 1, 0, act)
     out = hip.conv2d_nhwc(*args).permute(0, 3, 1, 2).cpu()
-    hip.lib().cp_set_debug(4194304)
-    try:
+    with hip.select_kernels(S.PW16_NEVER):
         old = hip.conv2d_nhwc(*args).permute(0, 3, 1, 2).cpu()
-    finally:
-        hip.lib().cp_set_debug(0)
-    hip.lib().cp_set_debug(4)   # round 5's form of the stream: fragment-shaped A loads instead of whole lines through staging rows
-    try:
+    with hip.select_kernels(S.PW16_FRAG_A):   # round 5's form of the stream: fragment-shaped A loads, not whole lines via staging rows
         frag = hip.conv2d_nhwc(*args).permute(0, 3, 1, 2).cpu()
-    finally:
-        hip.lib().cp_set_debug(0)
     scale = float(ref.abs().max())
     assert float((out.double() - ref).abs().max()) < 2e-5 * scale
     assert float((out - old).abs().max()) < 2e-6 * scale
@@ -240,7 +232,7 @@ def test_pointwise_stream_kernel_vs_float64_and_lds_loop(device, f16x3, B, H, W,
 ])
 def test_halo_resident_conv3x3_vs_float64_and_previous_kernel(device, f16x3, B, H, W, Cin, Cout, res, act):
     """halo16.hip (3x3 / stride 1 layers whose maps tile into 8x16 patches) against a float64 convolution, and against
-    the per-tap implicit-GEMM kernel it replaces (cp_set_debug 4096): same products, different summation order."""
+    the per-tap implicit-GEMM kernel it replaces (S.HALO_NEVER): same products, different summation order."""
     g = torch.Generator().manual_seed(Cin + Cout + H)
     x = torch.randn(B, Cin, H, W, generator=g)
     w = torch.randn(Cout, Cin, 3, 3, generator=g) / (Cin * 9) ** 0.5
@@ -250,16 +242,10 @@ def test_halo_resident_conv3x3_vs_float64_and_previous_kernel(device, f16x3, B, 
     ref = F.relu(ref) if act == 1 else ref
     args = (x.permute(0, 2, 3, 1).contiguous().to(device), w.to(device), None, None,
             r.permute(0, 2, 3, 1).contiguous().to(device) if res else None, 1, 1, act)
-    hip.lib().cp_set_debug(8192)   # the halo kernel for every eligible N tile (default: the 32-wide one only)
-    try:
+    with hip.select_kernels(S.HALO_ALWAYS):   # the halo kernel for every eligible N tile (default: the 32-wide one only)
         out = hip.conv2d_nhwc(*args).permute(0, 3, 1, 2).cpu().double()
-    finally:
-        hip.lib().cp_set_debug(0)
-    hip.lib().cp_set_debug(4096)
-    try:
+    with hip.select_kernels(S.HALO_NEVER):
         old = hip.conv2d_nhwc(*args).permute(0, 3, 1, 2).cpu().double()
-    finally:
-        hip.lib().cp_set_debug(0)
     assert float((out - ref).abs().max() / ref.abs().max()) < 2e-5
     assert float((out - old).abs().max() / ref.abs().max()) < 2e-6
     assert not torch.equal(out, old) or Cin == 64   # two different kernels really ran (summation order differs)
@@ -273,8 +259,8 @@ def test_halo_resident_conv3x3_vs_float64_and_previous_kernel(device, f16x3, B, 
     (5, 128, 128, 2),   # the offset convolutions' own map size: more jobs than one workgroup's waves, several jobs per wave
 ])
 def test_streamed_conv3x3_c64_n32_vs_float64_and_other_kernels(device, f16x3, B, H, W, act):
-    """strm16.hip (64 -> <= 32 channel 3x3 layers as wave-private row streams, weights in LDS; cp_set_debug 536870912: at any size)
-    against a float64 convolution and against the kernel it replaces (268435456: halo16's 32-wide tile where the map tiles into
+    """strm16.hip (64 -> <= 32 channel 3x3 layers as wave-private row streams, weights in LDS; S.STRM16_ALWAYS: at any size)
+    against a float64 convolution and against the kernel it replaces (S.STRM16_NEVER: halo16's 32-wide tile where the map tiles into
     8 x 16 patches, the per-tap implicit GEMM otherwise -- both sum in the same order); the sigmoid by hardware exp2 / rcp
     (|error| < 3e-7) instead of expf.  How the profile shows that strm16 ran: test_backbone_at_bench_batch_every_image_every_launch."""
     g = torch.Generator().manual_seed(B * 100 + H + W)
@@ -286,13 +272,10 @@ def test_streamed_conv3x3_c64_n32_vs_float64_and_other_kernels(device, f16x3, B,
     ref = F.relu(ref) if act == 1 else torch.sigmoid(ref) if act == 2 else ref
     args = (x.permute(0, 2, 3, 1).contiguous().to(device), w.to(device), scale.to(device), shift.to(device), None, 1, 1, act)
     outs = {}
-    for name, dbg in (("strm16", 536870912), ("other", 268435456)):
-        hip.lib().cp_set_debug(dbg)
-        try:
+    for name, sel in (("strm16", S.STRM16_ALWAYS), ("other", S.STRM16_NEVER)):
+        with hip.select_kernels(sel):
             outs[name] = hip.conv2d_nhwc(*args).permute(0, 3, 1, 2).cpu().double()
             again = hip.conv2d_nhwc(*args).permute(0, 3, 1, 2).cpu().double()
-        finally:
-            hip.lib().cp_set_debug(0)
         assert torch.equal(outs[name], again), name
         assert float((outs[name] - ref).abs().max() / ref.abs().max()) < 2e-5, name
     assert float((outs["strm16"] - outs["other"]).abs().max() / ref.abs().max()) < 2e-6
@@ -326,8 +309,8 @@ def test_dcn_both_precisions_vs_oracle(device, precision):
 ])
 def test_dcn_patch_resident_vs_oracle_and_gather_kernel(device, B, C, Co, H, W, std):
     """dcn16p.hip (samples gathered from an LDS-staged halo, exception samples from spare patch rows, overflowing blocks
-    through buffer loads) against the float64 oracle and against dcn16.hip (cp_set_debug 32768): same products, different
-    summation order.  cp_set_debug 65536 selects it for launches of any size."""
+    through buffer loads) against the float64 oracle and against dcn16.hip (S.DCN16P_NEVER): same products, different
+    summation order.  S.DCN16P_ALWAYS selects it for launches of any size."""
     hip.set_default_precision("f16x3")
     try:
         g = torch.Generator().manual_seed(C + H + int(std * 10))
@@ -338,21 +321,12 @@ def test_dcn_patch_resident_vs_oracle_and_gather_kernel(device, B, C, Co, H, W, 
         mask = torch.rand(B, 9, H, W, generator=g)
         ref = odcn.dcn_v2_forward_f64(x, w, b, off, mask)
         args = [t.to(device) for t in (x, w, b, off, mask)] + [3, 3, 1, 1, 1, 1, 1, 1, 1]
-        hip.lib().cp_set_debug(65536)
-        try:
+        with hip.select_kernels(S.DCN16P_ALWAYS):
             out = hip.dcn_v2_forward(*args).cpu()
-        finally:
-            hip.lib().cp_set_debug(0)
-        hip.lib().cp_set_debug(32768)
-        try:
+        with hip.select_kernels(S.DCN16P_NEVER):
             old = hip.dcn_v2_forward(*args).cpu()
-        finally:
-            hip.lib().cp_set_debug(0)
-        hip.lib().cp_set_debug(65536 | 524288)   # never the 128-wide N tile
-        try:
+        with hip.select_kernels(S.DCN16P_ALWAYS | S.DCN16P_NOT_WIDE):
             narrow = hip.dcn_v2_forward(*args).cpu()
-        finally:
-            hip.lib().cp_set_debug(0)
     finally:
         hip.set_default_precision("f32")
     assert float((out.double() - ref).abs().max() / ref.abs().max()) < 2e-5
@@ -376,8 +350,10 @@ def test_dcn_patch_resident_vs_oracle_and_gather_kernel(device, B, C, Co, H, W, 
 ])
 def test_dcn_streamed_persistent_vs_oracle_and_gather_kernel(device, B, C, Co, H, W, std, grid8):
     """dcn16s.hip (persistent workgroups, halo chunks and exception corners streamed by LDS-DMA into two buffers) against the
-    float64 oracle and against dcn16.hip (cp_set_debug 32768).  cp_set_debug 65536 | 2097152 selects it for launches of any size,
-    8388608 limits the grid to 8 workgroups so that small problems exercise the item-to-item hand-over."""
+    float64 oracle and against dcn16.hip (S.DCN16P_NEVER).  S.DCN16P_ALWAYS | S.DCN16S_ALWAYS selects it for launches of any
+    size; S.DCN16S_GRID8 limits the grid to 8 workgroups so that small problems exercise the item-to-item hand-over.  Items are
+    independent and there are no atomics, so the 8-workgroup grid must give the default grid's result bit for bit -- and not
+    the generic kernel's (S.DCN_GENERIC), which would agree with the oracle too."""
     hip.set_default_precision("f16x3")
     try:
         g = torch.Generator().manual_seed(C + H + int(std * 10))
@@ -388,23 +364,26 @@ def test_dcn_streamed_persistent_vs_oracle_and_gather_kernel(device, B, C, Co, H
         mask = torch.rand(B, 9, H, W, generator=g)
         ref = odcn.dcn_v2_forward_f64(x, w, b, off, mask)
         args = [t.to(device) for t in (x, w, b, off, mask)] + [3, 3, 1, 1, 1, 1, 1, 1, 1]
-        hip.lib().cp_set_debug(65536 | 2097152 | (8388608 if grid8 else 0))
-        try:
+        s16 = S.DCN16P_ALWAYS | S.DCN16S_ALWAYS
+        with hip.select_kernels(s16 | (S.DCN16S_GRID8 if grid8 else 0)):
             out = hip.dcn_v2_forward(*args).cpu()
             out2 = hip.dcn_v2_forward(*args).cpu()
-        finally:
-            hip.lib().cp_set_debug(0)
-        hip.lib().cp_set_debug(32768)
-        try:
+        with hip.select_kernels(S.DCN16P_NEVER):
             old = hip.dcn_v2_forward(*args).cpu()
-        finally:
-            hip.lib().cp_set_debug(0)
+        if grid8:
+            with hip.select_kernels(s16):
+                full = hip.dcn_v2_forward(*args).cpu()
+            with hip.select_kernels(S.DCN_GENERIC):
+                generic = hip.dcn_v2_forward(*args).cpu()
     finally:
         hip.set_default_precision("f32")
     assert torch.equal(out, out2)   # deterministic (no atomics on the data path, no race between DMA and gather)
     assert float((out.double() - ref).abs().max() / ref.abs().max()) < 2e-5
     assert float((out - old).abs().max() / ref.abs().max()) < 2e-6
     assert not torch.equal(out, old)   # two different kernels really ran (summation order differs)
+    if grid8:
+        assert torch.equal(out, full)           # the hand-over between items changes no bit
+        assert not torch.equal(out, generic)    # dcn16s really ran on 8 workgroups, not the generic kernel
 
 
 @pytest.mark.parametrize("B,C,Co,H,W,std", [
@@ -420,9 +399,9 @@ def test_dcn_streamed_persistent_vs_oracle_and_gather_kernel(device, B, C, Co, H
 ])
 def test_dcn_three_workgroups_per_cu_vs_oracle_and_other_kernels(device, B, C, Co, H, W, std):
     """dcn16t.hip (dcn16p's gather on a 168-register / 46 KB budget: three workgroups per CU, 16-channel chunks, transposed product,
-    first chunk requested in the prologue) against the float64 oracle, against dcn16.hip (cp_set_debug 32768: another summation
-    order) and against dcn16s.hip (the same K order (16-channel chunk, tap): bit-identical).  cp_set_debug 65536 | 33554432 selects
-    it for launches of any size."""
+    first chunk requested in the prologue) against the float64 oracle, against dcn16.hip (S.DCN16P_NEVER: another summation
+    order) and against dcn16s.hip (the same K order (16-channel chunk, tap): bit-identical).  S.DCN16P_ALWAYS | S.DCN16T_ALWAYS
+    selects it for launches of any size."""
     hip.set_default_precision("f16x3")
     try:
         g = torch.Generator().manual_seed(C + H + int(std * 10))
@@ -434,12 +413,11 @@ def test_dcn_three_workgroups_per_cu_vs_oracle_and_other_kernels(device, B, C, C
         ref = odcn.dcn_v2_forward_f64(x, w, b, off, mask)
         args = [t.to(device) for t in (x, w, b, off, mask)] + [3, 3, 1, 1, 1, 1, 1, 1, 1]
         outs = {}
-        for name, dbg in (("t", 65536 | 33554432), ("t2", 65536 | 33554432), ("gather", 32768), ("s", 65536 | 2097152 | 67108864)):
-            hip.lib().cp_set_debug(dbg)
-            try:
+        t = S.DCN16P_ALWAYS | S.DCN16T_ALWAYS
+        for name, sel in (("t", t), ("t2", t), ("gather", S.DCN16P_NEVER),
+                          ("s", S.DCN16P_ALWAYS | S.DCN16S_ALWAYS | S.DCN16T_NEVER)):
+            with hip.select_kernels(sel):
                 outs[name] = hip.dcn_v2_forward(*args).cpu()
-            finally:
-                hip.lib().cp_set_debug(0)
     finally:
         hip.set_default_precision("f32")
     assert torch.equal(outs["t"], outs["t2"])   # deterministic
@@ -454,9 +432,10 @@ def test_dcn_at_bench_batch_size_independent_properties(device, C, Co, HW):
     """The two heaviest DCNv2 shapes of the benchmark, at the benchmark's batch (B = 64: 8192 / 4096 patches, where no CPU oracle
     finishes in seconds) through properties that do not depend on the size:
       * the launch really goes to the kernel the dispatcher means -- dcn16t (three workgroups per CU, round 6) for 64 -> 64, dcn16p on
-        the 128-wide N tile for 128 -> 128 -- and it agrees with another patch kernel (dcn16p: 67108864 | 1048576, resp. dcn16s:
-        65536 | 2097152) and with the gather kernel dcn16 (32768) to summation-order round-off; the 128-wide tile equals the 64-wide
-        one (524288 | 1048576 | 67108864) and dcn16t equals dcn16s (same K order) bit for bit;
+        the 128-wide N tile for 128 -> 128 -- and it agrees with another patch kernel (dcn16p: DCN16T_NEVER | DCN16S_NEVER, resp.
+        dcn16s: DCN16P_ALWAYS | DCN16S_ALWAYS) and with the gather kernel dcn16 (DCN16P_NEVER) to summation-order round-off; the
+        128-wide tile equals the 64-wide one (DCN16P_NOT_WIDE | DCN16S_NEVER | DCN16T_NEVER) and dcn16t equals dcn16s (same K
+        order) bit for bit;
       * homogeneity: without a bias f(4 x) == 4 f(x) bit for bit -- every operand is pre-scaled by exact powers of two
         (profiles/NOTES.md 3.1), so a power-of-two input scale must come out as exactly that scale;
       * additivity in the input for fixed offsets / masks: f(x1 + x2) - f(x1) - f(x2) + f(0) == 0 to round-off;
@@ -475,19 +454,14 @@ def test_dcn_at_bench_batch_size_independent_properties(device, C, Co, HW):
         f = lambda x, m=mask: hip.dcn_v2_forward(x, w, b, off, m, *tail)
         y1 = f(x1)
         scale = float(y1.abs().max())
-        for dbg in ((67108864 | 1048576 if Co % 128 else 65536 | 2097152), 32768):
-            hip.lib().cp_set_debug(dbg)
-            try:
+        for sel in ((S.DCN16T_NEVER | S.DCN16S_NEVER if Co % 128 else S.DCN16P_ALWAYS | S.DCN16S_ALWAYS), S.DCN16P_NEVER):
+            with hip.select_kernels(sel):
                 other = f(x1)
-            finally:
-                hip.lib().cp_set_debug(0)
-            assert not torch.equal(other, y1), dbg            # a different kernel ran
-            assert float((other - y1).abs().max()) / scale < 2e-6, dbg
-        hip.lib().cp_set_debug(524288 | 1048576 | 67108864 if Co % 128 == 0 else 67108864 | 65536 | 2097152)
-        try:
+            assert not torch.equal(other, y1), sel            # a different kernel ran
+            assert float((other - y1).abs().max()) / scale < 2e-6, sel
+        with hip.select_kernels(S.DCN16P_NOT_WIDE | S.DCN16S_NEVER | S.DCN16T_NEVER if Co % 128 == 0
+                                else S.DCN16T_NEVER | S.DCN16P_ALWAYS | S.DCN16S_ALWAYS):
             assert torch.equal(f(x1), y1)
-        finally:
-            hip.lib().cp_set_debug(0)
         bias = b.view(1, Co, 1, 1)
         # (without a bias the property is exact: the products, their sums and the epilogue's power-of-two scales carry the factor 4
         # through unchanged; with one, fl(4 X + b) - b and 4 (fl(X + b) - b) differ by the roundings of the additions: a few ulp)
@@ -505,8 +479,12 @@ def test_dcn_at_bench_batch_size_independent_properties(device, C, Co, HW):
 
 
 @pytest.mark.parametrize("B,C,Co,HW,n", [(16, 64, 64, 128, 300), (64, 256, 256, 32, 500)])
-@pytest.mark.parametrize("kernel,dbg", [("dcn16p", 65536 | 1048576 | 67108864), ("dcn16t", 65536 | 33554432), ("dcn16p on the 64-wide N tile only", 65536 | 1048576 | 524288 | 67108864),
-                                        ("dcn16s", 65536 | 2097152)])
+# (the selections are passed as plain ints: the test ids keep their numbers)
+@pytest.mark.parametrize("kernel,dbg", [("dcn16p", int(S.DCN16P_ALWAYS | S.DCN16S_NEVER | S.DCN16T_NEVER)),
+                                        ("dcn16t", int(S.DCN16P_ALWAYS | S.DCN16T_ALWAYS)),
+                                        ("dcn16p on the 64-wide N tile only",
+                                         int(S.DCN16P_ALWAYS | S.DCN16S_NEVER | S.DCN16P_NOT_WIDE | S.DCN16T_NEVER)),
+                                        ("dcn16s", int(S.DCN16P_ALWAYS | S.DCN16S_ALWAYS))])
 def test_dcn_kernels_are_stable_over_many_launches(device, kernel, dbg, B, C, Co, HW, n):
     """Regression for the wrong set-up values found in round 4 and explained in round 5 (profiles/NOTES.md: a packed-f32 op with a
     set op_sel bit, which the SLP vectorizer made of the set-up's two sums in the early-prologue build, is computed wrongly in
@@ -524,21 +502,20 @@ def test_dcn_kernels_are_stable_over_many_launches(device, kernel, dbg, B, C, Co
         off = (torch.randn(B, 18, HW, HW, generator=g) * 1.5).to(device)
         mask = torch.rand(B, 9, HW, HW, generator=g).to(device)
         args = [x, w, b, off, mask, 3, 3, 1, 1, 1, 1, 1, 1, 1]
-        hip.lib().cp_set_debug(32768)
-        ref = hip.dcn_v2_forward(*args)
-        hip.lib().cp_set_debug(dbg)
+        with hip.select_kernels(S.DCN16P_NEVER):
+            ref = hip.dcn_v2_forward(*args)
         scale = float(ref.abs().max())
         first, worst, nbad = None, 0.0, 0
-        for _ in range(n):
-            y = hip.dcn_v2_forward(*args)
-            if first is None:
-                first = y.clone()
-                assert not torch.equal(first, ref)   # another kernel than the reference's really ran
-            err = float((y - ref).abs().max()) / scale
-            worst = max(worst, err)
-            nbad += int(not torch.equal(y, first))
+        with hip.select_kernels(dbg):
+            for _ in range(n):
+                y = hip.dcn_v2_forward(*args)
+                if first is None:
+                    first = y.clone()
+                    assert not torch.equal(first, ref)   # another kernel than the reference's really ran
+                err = float((y - ref).abs().max()) / scale
+                worst = max(worst, err)
+                nbad += int(not torch.equal(y, first))
     finally:
-        hip.lib().cp_set_debug(0)
         hip.set_default_precision("f32")
     assert worst < 2e-6, (kernel, worst)
     assert nbad == 0, (kernel, nbad)   # bit-identical from launch to launch
@@ -839,7 +816,7 @@ def test_conv_kernels_are_stable_over_many_launches(device, f16x3, name, B, H, C
 def test_fused_stem_level0_vs_two_kernels_and_oracle(device, arch, B, h, w):
     """lowc2_kernel (stem 7x7 + level0 3x3 in one launch: a wave streams down a 14-column strip, the 16-channel tensor between the
     two layers never exists; its pre-scale comes from a bound, not from a measured |max|) against the two-kernel form
-    (cp_set_debug 134217728) on level0's output (tap) -- other pre-scale and another summation order: float32 round-off -- and,
+    (S.STEM_LEVEL0_UNFUSED) on level0's output (tap) -- other pre-scale and another summation order: float32 round-off -- and,
     through the whole network, against the CPU oracle at the north-star gates.  Sizes: strips that end inside the picture (96 x 160:
     12 strips, the last 6 columns wide; 224: exactly 16), one band and several, a picture smaller than a band, B not a power of
     two.  The tap of the stem itself still works (the engine falls back to two kernels for it)."""
@@ -856,14 +833,11 @@ def test_fused_stem_level0_vs_two_kernels_and_oracle(device, arch, B, h, w):
     t1 = t1.clone()
     _, t1b = model.forward(x, tap="base.level0")
     assert torch.equal(t1, t1b)   # deterministic
-    hip.lib().cp_set_debug(134217728)
-    try:
+    with hip.select_kernels(S.STEM_LEVEL0_UNFUSED):
         model.profile(True)
         _, t0 = model.forward(x, tap="base.level0")
         assert any(n.startswith("lowc_stem7x7") for n in model.profile_read())
         model.profile(False)
-    finally:
-        hip.lib().cp_set_debug(0)
     assert t1.shape == t0.shape == (B, 16, h, w)
     assert float((t1 - t0).abs().max()) < 2e-6 * max(1.0, float(t0.abs().max()))
     _, ts = model.forward(x, tap="base.base_layer")   # asking for the stem's output selects the two-kernel form
@@ -878,7 +852,7 @@ def test_fused_stem_level0_vs_two_kernels_and_oracle(device, arch, B, h, w):
                                         ("dla_34", 1, 32, 32), ("dla_34", 5, 64, 224), ("dla_34", 2, 160, 352)])
 def test_row_streamed_level1_vs_tile_kernel_and_float64(device, arch, B, h, w):
     """lowc1s_kernel (level1, 3x3 / stride 2, 16 -> 32 as a row stream: even / odd input columns in separate LDS planes, two rolling
-    accumulators; cp_set_debug 1073741824: at any size, 262144: never) on level1's output (tap) against the tile kernel -- other
+    accumulators; S.LEVEL1_ROWS_ALWAYS: at any size, S.LEVEL1_ROWS_NEVER: never) on level1's output (tap) against the tile kernel -- other
     MFMA shape, other summation order: float32 round-off -- and against a float64 convolution of level0's output with the folded
     BatchNorm + ReLU (pose_dla_dcn.py:310-322).  Sizes: strips that end inside the picture (80 / 112 / 176 output columns), one band
     and several, pictures smaller than a strip, several jobs per wave."""
@@ -887,9 +861,8 @@ def test_row_streamed_level1_vs_tile_kernel_and_float64(device, arch, B, h, w):
     x = synth.frames(B, seed=29, h=h, w=w).to(device)
     model = hip.HipModel(arch, heads, sd, precision="f16x3")
     outs = {}
-    for name, dbg, want in (("rows", 1073741824, "lowc_3x3s2_c16_rows"), ("tile", 262144, "lowc_3x3s2_c16_f16x3")):
-        hip.lib().cp_set_debug(dbg)
-        try:
+    for name, sel, want in (("rows", S.LEVEL1_ROWS_ALWAYS, "lowc_3x3s2_c16_rows"), ("tile", S.LEVEL1_ROWS_NEVER, "lowc_3x3s2_c16_f16x3")):
+        with hip.select_kernels(sel):
             model.profile(True)
             _, t = model.forward(x, tap="base.level1")
             ran = model.profile_read()
@@ -897,8 +870,6 @@ def test_row_streamed_level1_vs_tile_kernel_and_float64(device, arch, B, h, w):
             outs[name] = t.clone()
             _, t2 = model.forward(x, tap="base.level1")
             assert torch.equal(outs[name], t2), name   # deterministic
-        finally:
-            hip.lib().cp_set_debug(0)
         assert any(n.startswith(want) for n in ran), (name, sorted(ran))
     _, l0 = model.forward(x, tap="base.level0")
     wgt = sd["base.level1.0.weight"].double()
@@ -932,18 +903,15 @@ def test_first_layers_are_stable_over_many_launches(device):
 def test_splitk_epilogue_quad_form_equals_elementwise(device, arch, B):
     """Small launches are cut along K by the engine (batch 1 - 2: 48 of a dla_34 frame's 138 launches are split-K epilogues);
     the slices' slabs are summed by splitk_epilogue.  Its quad form (four channels per lane, every slab read in flight at once)
-    against the element-wise form (cp_set_debug 8) on whole networks: the same additions in slice order -> every head
+    against the element-wise form (S.SPLITK_ELEMENTWISE) on whole networks: the same additions in slice order -> every head
     bit-identical, 10 forwards each way.  (cp_conv2d_nhwc never splits K, so this cannot be a single-layer test.)"""
     heads = synth.HEADS_POSE
     model = hip.HipModel(arch, heads, synth.make_state_dict(arch, heads), precision="f16x3")
     x = synth.frames(B, seed=11).to(device)
     first = {k: v.clone() for k, v in model(x, sigmoid_hm=True).items()}
     for it in range(20):
-        hip.lib().cp_set_debug(8 if it % 2 == 0 else 0)
-        try:
+        with hip.select_kernels(S.SPLITK_ELEMENTWISE if it % 2 == 0 else 0):
             z = model(x, sigmoid_hm=True)
-        finally:
-            hip.lib().cp_set_debug(0)
         for name in first:
             assert torch.equal(z[name], first[name]), (it, name)
 
@@ -962,15 +930,12 @@ def test_grouped_fused_heads_equal_per_head_launches(device, arch, B, hw, tracki
     model = hip.HipModel(arch, heads, sd, tracking_task=tracking, precision="f16x3")
     run = lambda: {k: v.clone() for k, v in model(x, sigmoid_hm=True, **kw).items()}
     z = run()
-    # 16777216: one launch per head; 1: one grouped launch that writes per-tile slabs + the reduction launch; 2: a workgroup
-    # walks the hidden tiles of ONE head and finishes its maps (the default below 2048 patches; from there -- the B = 16 case
-    # here -- a workgroup walks every head of its patch)
-    for dbg in (16777216, 1, 2):
-        hip.lib().cp_set_debug(dbg)
-        try:
+    # HEADS_PER_HEAD_LAUNCH: one launch per head; HEADS_SLABS: one grouped launch that writes per-tile slabs + the reduction
+    # launch; HEADS_WG_PER_HEAD: a workgroup walks the hidden tiles of ONE head and finishes its maps (the default below 2048
+    # patches; from there -- the B = 16 case here -- a workgroup walks every head of its patch)
+    for sel in (S.HEADS_PER_HEAD_LAUNCH, S.HEADS_SLABS, S.HEADS_WG_PER_HEAD):
+        with hip.select_kernels(sel):
             z1 = run()
-        finally:
-            hip.lib().cp_set_debug(0)
         for k in heads:
             assert torch.isfinite(z[k]).all(), k
             assert torch.equal(z[k], z1[k]), (dbg, k, float((z[k] - z1[k]).abs().max()))
@@ -996,7 +961,7 @@ def test_backbone_vs_reference_golden(device, arch, tracking, prec):
 @pytest.mark.parametrize("arch,tracking", CONFIGS)
 def test_backbone_with_row_streamed_offset_convolutions_vs_reference_golden(device, arch, tracking):
     """The reference goldens again with the 64-channel conv_offset_mask layers forced onto strm16.hip at the goldens' small size
-    (cp_set_debug 536870912; by default the kernel only takes them from B = 32 at 128 x 128): 27 of 32 channels, the mask sigmoid
+    (S.STRM16_ALWAYS; by default the kernel only takes them from B = 32 at 128 x 128): 27 of 32 channels, the mask sigmoid
     from channel 18 (dcn_v2.py:105-125), few jobs per workgroup.  Same gates as test_backbone_vs_reference_golden, and against the
     default dispatch the heads may differ only by what the sigmoid form (exp2 / rcp, < 3e-7 per mask) propagates."""
     heads = synth.HEADS_TRACK if tracking else synth.HEADS_POSE
@@ -1006,15 +971,12 @@ def test_backbone_with_row_streamed_offset_convolutions_vs_reference_golden(devi
     model = hip.HipModel(arch, heads, sd, tracking_task=tracking, precision="f16x3")
     args = (x.to(device),), {k: v.to(device) for k, v in kw.items()}
     z0 = {k: v.clone() for k, v in model(*args[0], **args[1]).items()}
-    hip.lib().cp_set_debug(536870912)
-    try:
+    with hip.select_kernels(S.STRM16_ALWAYS):
         model.profile(True)
         z = {k: v.clone() for k, v in model(*args[0], **args[1]).items()}
         torch.cuda.synchronize()
         ran = model.profile_read()
         model.profile(False)
-    finally:
-        hip.lib().cp_set_debug(0)
     assert any(name.startswith("strm16_f16x3") for name in ran), sorted(ran)
     for k in heads:
         ref = gold[k]
@@ -1100,7 +1062,7 @@ def test_hourglass_256_vs_oracle_and_rejects_bad_sizes(device):
 
 def test_fused_head_matches_unfused_path(device):
     """dla_34 heads (conv3x3 -> ReLU -> conv1x1, no GroupNorm) run as one fused kernel in f16x3 mode; the two-kernel
-    path (debug flag 32) must give the same maps to float32 round-off, and the fused path must be deterministic."""
+    path (S.NO_HEAD_FUSION) must give the same maps to float32 round-off, and the fused path must be deterministic."""
     heads = synth.HEADS_POSE
     sd = synth.make_state_dict("dla_34", heads)
     x = synth.frames(2, seed=29, h=256, w=256).to(device)
@@ -1113,19 +1075,13 @@ def test_fused_head_matches_unfused_path(device):
     model.profile(False)
     z = {k: v.clone() for k, v in model(x, sigmoid_hm=True).items()}
     z2 = model(x, sigmoid_hm=True)
-    hip.lib().cp_set_debug(32)
-    try:
+    with hip.select_kernels(S.NO_HEAD_FUSION):
         zu = {k: v.clone() for k, v in model(x, sigmoid_hm=True).items()}
-    finally:
-        hip.lib().cp_set_debug(0)
-    hip.lib().cp_set_debug(4096)   # the same fusion on the per-tap implicit-GEMM kernel (what ragged maps fall back to)
-    try:
+    with hip.select_kernels(S.HALO_NEVER):   # the same fusion on the per-tap implicit-GEMM kernel (what ragged maps fall back to)
         model.profile(True)
         zi = {k: v.clone() for k, v in model(x, sigmoid_hm=True).items()}
         assert "igemm16_head_f16x3_m128n128" in model.profile_read()
         model.profile(False)
-    finally:
-        hip.lib().cp_set_debug(0)
     for k in heads:
         assert torch.equal(z[k], z2[k]), k
         assert z[k].shape == zu[k].shape
@@ -1135,8 +1091,8 @@ def test_fused_head_matches_unfused_path(device):
 
 def test_convgru_step_kernels_agree(device):
     """dlav1_34's ConvGRU hidden-side step (convGRU.py:32-39) has three implementations: the gate arithmetic fused into
-    the halo-resident kernel (maps that tile into 8x16 patches), into the per-tap implicit-GEMM kernel (cp_set_debug 4096,
-    what ragged maps fall back to) and the unfused convolution + gate kernel (256).  Same products, different summation
+    the halo-resident kernel (maps that tile into 8x16 patches), into the per-tap implicit-GEMM kernel (S.HALO_NEVER,
+    what ragged maps fall back to) and the unfused convolution + gate kernel (S.GRU_UNFUSED).  Same products, different summation
     orders: the heads must agree to float32 round-off."""
     heads = synth.HEADS_POSE
     sd = synth.make_state_dict("dlav1_34", heads)
@@ -1146,14 +1102,11 @@ def test_convgru_step_kernels_agree(device):
     z = {k: v.clone() for k, v in model(x, sigmoid_hm=True).items()}
     assert "halo16_gru_f16x3_m128n96" in model.profile_read()
     outs = {}
-    for flag, name in ((4096, "igemm16_gru_f16x3_m128n96"), (256, None)):
-        hip.lib().cp_set_debug(flag)
-        try:
+    for flag, name in ((S.HALO_NEVER, "igemm16_gru_f16x3_m128n96"), (S.GRU_UNFUSED, None)):
+        with hip.select_kernels(flag):
             outs[flag] = {k: v.clone() for k, v in model(x, sigmoid_hm=True).items()}
             if name:
                 assert name in model.profile_read()
-        finally:
-            hip.lib().cp_set_debug(0)
     model.profile(False)
     for k in heads:
         for flag in outs:

@@ -43,6 +43,40 @@ def test_library_exports_every_declared_symbol_and_nothing_else(built):
     assert own == declared, sorted(own ^ declared)
 
 
+def test_kernel_selection_switches_are_named_single_bits(built):
+    """cp_set_debug's switches (include/centerpose_hip_testing.h) are one named CP_SEL_* bit each with one meaning, mirrored
+    exactly by hip.KernelSel; the sources under csrc/ test them only by name; the library accepts every defined switch and
+    their union (CP_SEL_ALL) and refuses any other bit."""
+    text = open(os.path.join(REPO, "include", "centerpose_hip_testing.h")).read()
+    defs = {n: int(v, 0) for n, v in re.findall(r"#define\s+CP_SEL_(\w+)\s+(0x[0-9a-fA-F]+|\d+)\b", text)}
+    mask = defs.pop("ALL")
+    assert defs and all(v > 0 and v & (v - 1) == 0 for v in defs.values()), defs
+    assert len(set(defs.values())) == len(defs), defs
+    union = 0
+    for v in defs.values():
+        union |= v
+    assert mask == union and union < 2 ** 31
+    assert defs == {f.name: f.value for f in hip.KernelSel}
+    csrc = os.path.join(REPO, "centerpose_amd", "csrc")
+    literal = re.compile(r"dbg\s*(&|>>)\s*\(?\d")
+    bad = ["%s:%d" % (f, i) for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h", ".cpp", ".c"))
+           for i, line in enumerate(open(os.path.join(csrc, f)), 1) if literal.search(line)]
+    assert not bad, bad
+    try:
+        for v in sorted(defs.values()) + [union, 0]:
+            assert built.cp_set_debug(v) == 0, hex(v)
+        for bit in range(32):
+            if not union >> bit & 1:
+                assert built.cp_set_debug(-2 ** 31 if bit == 31 else 1 << bit) == -1, bit
+                assert b"cp_set_debug" in built.cp_last_error()
+        assert built.cp_set_debug(union | 2048) == -1   # a retired switch next to valid ones
+        with pytest.raises(RuntimeError):
+            with hip.select_kernels(2048):
+                pass
+    finally:
+        built.cp_set_debug(0)
+
+
 def test_last_error_is_per_thread(built):
     """cp_last_error() returns the calling thread's last message (centerpose_hip.h, Threading): a failure on another thread does
     not replace it."""

@@ -20,7 +20,7 @@ ap.add_argument("--k", type=int, default=3)
 ap.add_argument("--stride", type=int, default=1)
 ap.add_argument("--prec", default="f16x3")
 ap.add_argument("--iters", type=int, default=20)
-ap.add_argument("--dbg", type=int, default=0, help="cp_set_debug flags (see engine.hip: g_dbg)")
+ap.add_argument("--dbg", type=int, default=0, help="cp_set_debug flags (CP_SEL_* of include/centerpose_hip_testing.h)")
 ap.add_argument("--check", action="store_true")
 a = ap.parse_args()
 dev = torch.device("cuda:0")

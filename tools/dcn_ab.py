@@ -10,7 +10,7 @@ import sys
 
 SHAPES = [  # (Cin, Cout, HW, count in the network)
     (64, 64, 128, 5), (128, 64, 64, 4), (128, 128, 64, 2), (256, 128, 32, 2), (256, 256, 32, 1), (256, 64, 32, 1), (512, 256, 16, 1)]
-MODES = [("dcn16p", 1048576 | 524288 | 67108864), ("dcn16pw", 1048576 | 67108864), ("dcn16s", 2097152), ("dcn16t", 33554432)]  # (dcn16pw: the 128-wide N tile where Cout % 128 == 0)
+MODES = ["dcn16p", "dcn16pw", "dcn16s", "dcn16t"]  # (dcn16pw: the 128-wide N tile where Cout % 128 == 0)
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--b", type=int, default=64)
@@ -22,17 +22,17 @@ ap.add_argument("--only", default=None, help="dcn16p | dcn16pw | dcn16s | dcn16t
 a = ap.parse_args()
 SHAPES = SHAPES[:a.nshapes]
 if a.only:
-    MODES = [m for m in MODES if m[0] == a.only]
+    MODES = [m for m in MODES if m == a.only]
 
 if a.parse:
     f = sorted(glob.glob(os.path.join(a.parse, "**", "*kernel_trace.csv"), recursive=True))[0]
     rows = [r for r in csv.DictReader(open(f)) if any(k in r["Kernel_Name"] for k in ("dcn16p_kernel", "dcn16s_kernel", "dcn16t_kernel"))]
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
     i = 0
-    tot = {m: 0.0 for m, _ in MODES}
+    tot = {m: 0.0 for m in MODES}
     for (ci, co, hw, cnt) in SHAPES:
         line = "%3d->%3d @%3d x%d:" % (ci, co, hw, cnt)
-        for m, _ in MODES:
+        for m in MODES:
             grp = rows[i:i + 2 + a.n]
             i += 2 + a.n
             names = {("dcn16t" if "dcn16t" in r["Kernel_Name"] else "dcn16s" if "dcn16s" in r["Kernel_Name"] else "dcn16pw" if "dcn16p_kernel<4" in r["Kernel_Name"] else "dcn16p") for r in grp}
@@ -41,7 +41,7 @@ if a.parse:
             tot[m] += avg * cnt
             line += "  %s %8.1f us (%s)" % (m, avg, "/".join(sorted(names)))
         print(line)
-    print("network DCN main total per step: " + "  ".join("%s %.3f ms" % (m, tot[m] / 1e3) for m, _ in MODES))
+    print("network DCN main total per step: " + "  ".join("%s %.3f ms" % (m, tot[m] / 1e3) for m in MODES))
     sys.exit(0)
 
 import torch  # noqa: E402
@@ -49,6 +49,9 @@ import torch  # noqa: E402
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from centerpose_amd import hip  # noqa: E402
 
+S = hip.KernelSel
+SEL = {"dcn16p": S.DCN16S_NEVER | S.DCN16P_NOT_WIDE | S.DCN16T_NEVER, "dcn16pw": S.DCN16S_NEVER | S.DCN16T_NEVER,
+       "dcn16s": S.DCN16S_ALWAYS, "dcn16t": S.DCN16T_ALWAYS}
 hip.set_default_precision("f16x3")
 g = torch.Generator().manual_seed(1)
 for (ci, co, hw, cnt) in SHAPES:
@@ -58,13 +61,12 @@ for (ci, co, hw, cnt) in SHAPES:
     off = (torch.randn(a.b, 18, hw, hw, generator=g) * a.std).cuda()
     mask = torch.rand(a.b, 9, hw, hw, generator=g).cuda()
     outs = []
-    for m, dbg in MODES:
-        hip.lib().cp_set_debug(65536 | dbg)
-        for _ in range(2 + a.n):
-            y = hip.dcn_v2_forward(x, w, bias, off, mask, 3, 3, 1, 1, 1, 1, 1, 1, 1)
-        torch.cuda.synchronize()
+    for m in MODES:
+        with hip.select_kernels(S.DCN16P_ALWAYS | SEL[m]):
+            for _ in range(2 + a.n):
+                y = hip.dcn_v2_forward(x, w, bias, off, mask, 3, 3, 1, 1, 1, 1, 1, 1, 1)
+            torch.cuda.synchronize()
         outs.append(y)
-    hip.lib().cp_set_debug(0)
     err = float((outs[0] - outs[2]).abs().max() / outs[0].abs().max()) if len(outs) > 2 else -1.0
     errt = float((outs[0] - outs[-1]).abs().max() / outs[0].abs().max())
     print("%d->%d @%d: max |dcn16p - dcn16s| / max = %.2e; |dcn16p - dcn16t| / max = %.2e; dcn16t == dcn16s bit for bit: %s; 128-wide == 64-wide: %s" % (

@@ -3,6 +3,7 @@ import os, sys
 import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 from centerpose_amd import hip
+S = hip.KernelSel
 hip.set_default_precision("f16x3")
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 64
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 4
@@ -15,11 +16,11 @@ for ci, co, hw in SHAPES:
     off = (torch.randn(B, 18, hw, hw, generator=g) * 1.5).cuda()
     mask = torch.rand(B, 9, hw, hw, generator=g).cuda()
     outs = {}
-    for name, dbg in [("dcn16", 32768)] + [("dcn16p_%d" % i, 65536 | 1048576) for i in range(reps)] + [("dcn16s_%d" % i, 65536 | 2097152) for i in range(reps)]:
-        hip.lib().cp_set_debug(dbg)
-        outs[name] = hip.dcn_v2_forward(x, w, bias, off, mask, 3, 3, 1, 1, 1, 1, 1, 1, 1)
-        torch.cuda.synchronize()
-    hip.lib().cp_set_debug(0)
+    for name, sel in ([("dcn16", S.DCN16P_NEVER)] + [("dcn16p_%d" % i, S.DCN16P_ALWAYS | S.DCN16S_NEVER) for i in range(reps)] +
+                      [("dcn16s_%d" % i, S.DCN16P_ALWAYS | S.DCN16S_ALWAYS) for i in range(reps)]):
+        with hip.select_kernels(sel):
+            outs[name] = hip.dcn_v2_forward(x, w, bias, off, mask, 3, 3, 1, 1, 1, 1, 1, 1, 1)
+            torch.cuda.synchronize()
     ref = outs["dcn16"]
     print("%d->%d @%d" % (ci, co, hw))
     for k, v in outs.items():
