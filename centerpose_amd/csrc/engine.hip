@@ -2538,6 +2538,27 @@ __global__ void dcn_offmask_pack_kernel(const float* __restrict__ offset, const 
         om[i] = v;
     }
 }
+
+// max |mask| of the packed records (channels 18 .. 26) -> `slot`
+__global__ void dcn_mask_amax_kernel(const float* __restrict__ om, size_t px, unsigned* __restrict__ slot) {
+    float m = 0.f;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < px * 9; i += (size_t)gridDim.x * blockDim.x)
+        m = fmaxf(m, fabsf(om[(i / 9) * 32 + 18 + i % 9]));
+    cp_amax_commit(slot, m);
+}
+
+// The f16x3 DCN kernels fold the mask into the corner weights of the pre-scaled activation, so the blended value is bounded
+// by max |x| * max |mask|, not max |x|: a caller-supplied mask above 1 would push it past binary16's range (hi half saturated,
+// lo half infinite).  Raise x's bound to max |x| * max(1, max |mask|), rounded up; masks within [-1, 1] leave it untouched.
+__global__ void dcn_act_bound_kernel(unsigned* __restrict__ x_slot, const unsigned* __restrict__ mask_slot) {
+    if (threadIdx.x != 0) return;
+    const float am = __uint_as_float(cp_amax_read(mask_slot));
+    if (!(am > 1.f)) return;
+    const double d = (double)__uint_as_float(cp_amax_read(x_slot)) * (double)am;  // exact (24 + 24 bits)
+    float bound = (float)d;
+    if ((double)bound < d) bound = __uint_as_float(__float_as_uint(bound) + 1u);  // rounded up
+    x_slot[0] = max(x_slot[0], __float_as_uint(bound));
+}
 }  // namespace
 
 extern "C" int cp_dcnv2_forward(cp_stream_t stream, const float* input, const float* weight, const float* bias,
@@ -2623,6 +2644,12 @@ extern "C" int cp_dcnv2_forward(cp_stream_t stream, const float* input, const fl
         if (rc == CP_OK) rc = cp_launch_pack_weight16(weight, (void*)p.w16_hi, (void*)p.w16_lo, Co, C, 9, p.Kpad16, 0, wfwd, s);
         if (rc == CP_OK) rc = cp_launch_scale16(nullptr, winv, sc16, Co, s);
         if (rc == CP_OK) rc = cp_launch_absmax(x_nhwc, px * C, slot, s);
+        if (rc == CP_OK) {  // the mask's |max| in slot 1 of the (zeroed) slot block, then folded into x's bound
+            const size_t g = std::min<size_t>((px * 9 + 255) / 256, 2048);
+            hipLaunchKernelGGL(dcn_mask_amax_kernel, dim3((unsigned)g), dim3(256), 0, s, (const float*)om, px, slot + 1);
+            hipLaunchKernelGGL(dcn_act_bound_kernel, dim3(1), dim3(64), 0, s, slot, (const unsigned*)(slot + 1));
+            if (hipGetLastError() != hipSuccess) rc = CP_ERR_LAUNCH;
+        }
         char* w16f = (char*)slot + (size_t)CP_AMAX_SUB * CP_AMAX_STRIDE * sizeof(unsigned);
         if (rc == CP_OK) rc = cp_launch_frag16_repack(p.w16_hi, w16f, cpad, p.Kpad16, s);
         if (rc == CP_OK) rc = cp_launch_frag16_repack(p.w16_lo, w16f + sz, cpad, p.Kpad16, s);
