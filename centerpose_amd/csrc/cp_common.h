@@ -405,6 +405,12 @@ int cp_launch_pose_loss_forward(hipStream_t s, const cp_pose_loss_desc* d, float
 int cp_launch_pose_loss_backward(hipStream_t s, const cp_pose_loss_desc* d, const float* dloss, const float* const* dmaps,
                                  float* const* grad, void* ws);
 
+// ---- ObjectPose training targets (pose_targets.hip; per-object logic in pose_targets_common.h) ----
+struct cp_pose_targets_desc;
+const char* cp_pose_targets_check(const cp_pose_targets_desc* d);  // nullptr: accepted (reads the host records)
+size_t cp_pose_targets_ws_bytes(const cp_pose_targets_desc* d);    // 0: refused
+int cp_launch_pose_targets(hipStream_t s, const cp_pose_targets_desc* d, void* ws);
+
 // ---- Objectron box metrics (box3d.hip; numerics in box3d_common.h) ----
 int cp_launch_box_iou(hipStream_t s, const double* a, const double* b, int n, double* iou);
 int cp_launch_box_eval(hipStream_t s, const double* pred3d, const double* gt3d, const double* pred2d, const double* mo2c,

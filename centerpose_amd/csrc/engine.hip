@@ -2667,3 +2667,13 @@ extern "C" int cp_dcnv2_forward(cp_stream_t stream, const float* input, const fl
     if (rc != CP_OK) return rc;
     return cp_launch_nhwc_to_nchw(y_nhwc, output, B, Co, H, W, Co, s);
 }
+
+size_t cp_pose_targets_workspace_bytes(const cp_pose_targets_desc* d) { return cp_pose_targets_ws_bytes(d); }
+
+int cp_pose_targets(cp_stream_t stream, const cp_pose_targets_desc* d, void* workspace, size_t workspace_bytes) {
+    if (const char* e = cp_pose_targets_check(d)) return fail(CP_ERR_INVALID, e);
+    if (!workspace) return fail(CP_ERR_INVALID, "pose_targets: null workspace");
+    if (workspace_bytes < cp_pose_targets_ws_bytes(d)) return fail(CP_ERR_INVALID, "pose_targets: workspace too small");
+    const int rc = cp_launch_pose_targets((hipStream_t)stream, d, workspace);
+    return rc == CP_OK ? CP_OK : fail(rc, "pose_targets: copy or kernel launch failed");
+}

@@ -54,6 +54,23 @@ class PoseLossDesc(ctypes.Structure):
                 ("clamped", (c_void_p * 2) * POSE_LOSS_MAX_STACKS)]
 
 
+# ---- ObjectPose training targets (cp_pose_targets*): record layouts of include/centerpose_hip.h ----
+CP_ERR_INVALID = -1
+PT_MAX_OBJS = 64
+PT_IMG_STRIDE, PT_OBJ_STRIDE = 32, 64
+PT_IMG = dict(trans=0, width=6, height=7, flipped=8, rot=9, num_objs=10, proj=11)
+PT_OBJ = dict(nsym=0, cuboid=1, quat=19, loc=23, kps3d=26, scale=53)
+PT_FLAGS = ("center_3D", "use_absolute_scale", "obj_scale", "hps_uncertainty", "reg_hp_offset", "hm_hp")
+PT_OUTPUTS = ("hm", "hm_hp", "reg_mask", "ind", "hps", "hps_mask", "hps_uncertainty", "wh", "reg", "scale",
+              "scale_uncertainty", "hp_offset", "hp_ind", "hp_mask")
+
+
+class PoseTargetsDesc(ctypes.Structure):
+    """cp_pose_targets_desc of include/centerpose_hip.h (field for field)."""
+    _fields_ = [(n, c_int) for n in ("B", "S", "R", "max_objs", "num_joints") + PT_FLAGS] + \
+               [("images", c_void_p), ("objects", c_void_p)] + [("out_" + n, c_void_p) for n in PT_OUTPUTS]
+
+
 def _sig(fn, restype, *argtypes):
     fn.restype = restype
     fn.argtypes = list(argtypes)
@@ -146,6 +163,8 @@ def lib():
          c_void_p, c_size_t)
     _sig(L.cp_pose_loss_backward, c_int, c_void_p, ctypes.POINTER(PoseLossDesc), c_void_p, ctypes.POINTER(c_void_p),
          ctypes.POINTER(c_void_p), c_void_p, c_size_t)
+    _sig(L.cp_pose_targets_workspace_bytes, c_size_t, ctypes.POINTER(PoseTargetsDesc))
+    _sig(L.cp_pose_targets, c_int, c_void_p, ctypes.POINTER(PoseTargetsDesc), c_void_p, c_size_t)
     _lib = L
     return L
 
@@ -177,7 +196,8 @@ def exported_symbols():
             "cp_track_reset", "cp_track_step", "cp_track_status", "cp_linear_assignment", "cp_decode_tiled_workspace_bytes",
             "cp_decode_tiled", "cp_box_iou", "cp_box_eval", "cp_conv_transpose2d_workspace_bytes",
             "cp_conv_transpose2d_nhwc", "cp_dcnv2_backward_workspace_bytes", "cp_dcnv2_backward",
-            "cp_pose_loss_workspace_bytes", "cp_pose_loss_forward", "cp_pose_loss_backward"]
+            "cp_pose_loss_workspace_bytes", "cp_pose_loss_forward", "cp_pose_loss_backward",
+            "cp_pose_targets_workspace_bytes", "cp_pose_targets"]
 
 
 def _check(rc, what):
@@ -1230,3 +1250,40 @@ def pose_loss_backward(state, dloss, dmaps=None):
     _check(lib().cp_pose_loss_backward(_stream(), ctypes.byref(d), _ptr(dloss), dm, ptrs, _ptr(ws),
                                        ws.numel()), "cp_pose_loss_backward")
     return grads
+
+
+def pose_targets_desc(images, objects, S, R, flags, out):
+    """cp_pose_targets_desc for host float64 records ``images`` [B, PT_IMG_STRIDE] and ``objects`` [B, K, PT_OBJ_STRIDE]
+    (numpy arrays, kept alive by the caller), ``flags`` {PT_FLAGS name: bool} and ``out`` {PT_OUTPUTS name: tensor or
+    None}."""
+    d = PoseTargetsDesc()
+    d.B, d.S, d.R = images.shape[0], int(S), int(R)
+    d.max_objs, d.num_joints = objects.shape[1], 8
+    for n in PT_FLAGS:
+        setattr(d, n, int(bool(flags.get(n, False))))
+    d.images, d.objects = images.ctypes.data, objects.ctypes.data
+    for n in PT_OUTPUTS:
+        t = out.get(n)
+        setattr(d, "out_" + n, t.data_ptr() if t is not None else None)
+    return d
+
+
+def pose_targets(images, objects, S, R, flags, out):
+    """cp_pose_targets: the training targets of a batch, written into the device tensors of ``out`` on the current
+    stream.  ``images`` / ``objects`` are the host records (converted to pageable float64 copies here, which the call
+    stages before it returns); refused arguments raise ValueError before any launch."""
+    import numpy as np
+
+    images = np.array(images, dtype=np.float64, order="C", copy=True)
+    objects = np.array(objects, dtype=np.float64, order="C", copy=True)
+    if images.ndim != 2 or images.shape[1] != PT_IMG_STRIDE or objects.ndim != 3 or \
+            objects.shape[0] != images.shape[0] or objects.shape[2] != PT_OBJ_STRIDE:
+        raise ValueError("pose_targets: records must be [B, %d] and [B, K, %d]" % (PT_IMG_STRIDE, PT_OBJ_STRIDE))
+    L = lib()
+    d = pose_targets_desc(images, objects, S, R, flags, out)
+    nbytes = L.cp_pose_targets_workspace_bytes(ctypes.byref(d))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=out["hm"].device) if nbytes else None
+    rc = L.cp_pose_targets(_stream(), ctypes.byref(d), _ptr(ws), nbytes)
+    if rc == CP_ERR_INVALID:
+        raise ValueError("centerpose_hip: cp_pose_targets: %s" % L.cp_last_error().decode())
+    _check(rc, "cp_pose_targets")

@@ -42,7 +42,7 @@ typedef struct cp_model cp_model;
  * 6 = cp_preprocess_batch, cp_linear_assignment, CP_NUM_KERNEL_VARIANTS 43, cp_set_debug moved out of this header (centerpose_hip_testing.h);
  * 7 = cp_decode_tiled / cp_decode_tiled_workspace_bytes, cp_model_detect decodes output grids above 32768 pixels;
  *     later additions without a version change: cp_box_iou, cp_box_eval, cp_pose_loss_workspace_bytes,
- *     cp_pose_loss_forward, cp_pose_loss_backward. */
+ *     cp_pose_loss_forward, cp_pose_loss_backward, cp_pose_targets_workspace_bytes, cp_pose_targets. */
 #define CP_ABI_VERSION 7
 const char* cp_version(void);
 int cp_abi_version(void);
@@ -554,6 +554,75 @@ int cp_pose_loss_forward(cp_stream_t stream, const cp_pose_loss_desc* d, float* 
                          float* terms_out, void* workspace, size_t workspace_bytes);
 int cp_pose_loss_backward(cp_stream_t stream, const cp_pose_loss_desc* d, const float* dloss, const float* const* dmaps,
                           float* const* grad, void* workspace, size_t workspace_bytes);
+
+/* ------------------------------------------------------------------------------------------
+ * ObjectPose training targets — replaces the current-frame part of ObjectPoseDataset.__getitem__
+ *   datasets/dataset_combined.py:957-1130 (+ the arrays of :368-393), for a batch, already collated to [B,S,...].
+ * The host keeps image decoding, the augmentation draws and the output affine trans_output_rot (:354); the records below
+ * carry them (centerpose_amd/pose_targets.py pack_annotations writes them).  S = the category's variant count
+ * (:357-366), R = opt.output_res, K = max_objs (10 in the reference, :128), num_joints = 8.
+ * Records (HOST pointers, float64; staged into the workspace with hipMemcpyAsync on `stream`, so pageable memory may be
+ * reused when the call returns):
+ *   images [B][CP_PT_IMG_STRIDE]
+ *     0..5   trans_output_rot, the 2x3 output affine, row-major (:354)
+ *     6, 7   width, height of the decoded image (:317)
+ *     8      flipped, 0 or 1 (:324-326)
+ *     9      rot, the augmentation angle in degrees; only rot != 0 is read (:1043)
+ *     10     num_objs = min(len(anns['objects']), max_objs) (:300)
+ *     11..26 anns['camera_data']['camera_projection_matrix'], 4x4 row-major (:957)
+ *   objects [B][K][CP_PT_OBJ_STRIDE] (slots k >= num_objs are not read)
+ *     0      the object's variant count, 1 <= n <= S: 4 or 1 from ann['symmetric'], or the value carried over from the
+ *            previous object when the key is missing (:962-966)
+ *     1..18  ann['projected_cuboid'], 9 x (x, y), centre first (:974)
+ *     19..22 ann['quaternion_xyzw'] (:986)
+ *     23..25 ann['location'] (:987)
+ *     26..52 ann['keypoints_3d'], 9 x (x, y, z) (:988)
+ *     53..55 ann['scale'] (:1058-1062)
+ * Outputs (DEVICE pointers), the collated `ret` entries, every element written (no pre-clear needed):
+ *   out_hm [B,S,1,R,R] f32, out_hm_hp [B,S,8,R,R] f32 (hm_hp), out_reg_mask [B,S,K] u8, out_ind [B,S,K] i64,
+ *   out_hps [B,S,K,16] f32, out_hps_mask [B,S,K,16] u8, out_hps_uncertainty [B,S,K,16] f32 (hps_uncertainty),
+ *   out_scale [B,S,K,3] f32 (obj_scale), out_hp_offset [B,S,K*8,2] f32, out_hp_ind / out_hp_mask [B,S,K*8] i64
+ *   (reg_hp_offset); out_wh / out_reg [B,S,K,2] f32 and out_scale_uncertainty [B,S,K,3] f32 (all zeros) are written
+ *   when non-NULL.  An output its option turns off is ignored and may be NULL; one it turns on must not be.
+ * Semantics are the reference's, integer behaviour included: variant projection in float64 truncated with int(),
+ *   corners truncated toward zero into int64 after the visibility test, the joints' affine assigned into int64 (so
+ *   hp_offset is always 0), max(0, int(gaussian_radius)), hm / hm_hp = the max over the covering Gaussians of
+ *   float32(exp(-(dx^2+dy^2) / (2 sigma^2))), sigma = (2r+1)/6.  Bitwise deterministic (no atomics).
+ * Refused with CP_ERR_INVALID before any device work: NULL pointers as above, B, S, R < 1, R > 46340, K outside
+ *   [1, CP_PT_MAX_OBJS], num_joints != 8, hm / hm_hp not 16-byte aligned, num_objs outside [0, K], a variant count outside
+ *   [1, S], a workspace below the query.  Launches on `stream`, never allocates, never synchronises.
+ * ------------------------------------------------------------------------------------------ */
+#define CP_PT_MAX_OBJS 64
+#define CP_PT_IMG_STRIDE 32
+#define CP_PT_IMG_TRANS 0
+#define CP_PT_IMG_WIDTH 6
+#define CP_PT_IMG_HEIGHT 7
+#define CP_PT_IMG_FLIPPED 8
+#define CP_PT_IMG_ROT 9
+#define CP_PT_IMG_NUM_OBJS 10
+#define CP_PT_IMG_PROJ 11
+#define CP_PT_OBJ_STRIDE 64
+#define CP_PT_OBJ_NSYM 0
+#define CP_PT_OBJ_CUBOID 1
+#define CP_PT_OBJ_QUAT 19
+#define CP_PT_OBJ_LOC 23
+#define CP_PT_OBJ_KPS3D 26
+#define CP_PT_OBJ_SCALE 53
+typedef struct cp_pose_targets_desc {
+    int B, S, R, max_objs, num_joints;
+    /* opt.center_3D, opt.use_absolute_scale, opt.obj_scale, opt.hps_uncertainty, opt.reg_hp_offset, opt.hm_hp (0 / 1) */
+    int center_3D, use_absolute_scale, obj_scale, hps_uncertainty, reg_hp_offset, hm_hp;
+    const double *images, *objects; /* host records, layouts above */
+    float *out_hm, *out_hm_hp;
+    unsigned char* out_reg_mask;
+    long long* out_ind;
+    float* out_hps;
+    unsigned char* out_hps_mask;
+    float *out_hps_uncertainty, *out_wh, *out_reg, *out_scale, *out_scale_uncertainty, *out_hp_offset;
+    long long *out_hp_ind, *out_hp_mask;
+} cp_pose_targets_desc;
+size_t cp_pose_targets_workspace_bytes(const cp_pose_targets_desc* d); /* 0: shape refused */
+int cp_pose_targets(cp_stream_t stream, const cp_pose_targets_desc* d, void* workspace, size_t workspace_bytes);
 
 #ifdef __cplusplus
 }
