@@ -1,0 +1,858 @@
+// The forward pass: a fixed sequence of HIP kernel launches on the caller's stream out of a caller-provided workspace
+// (deterministic arena, no allocation, no sync).  Fwd decides per layer which kernel runs; a dry run of the same code is the
+// work-space query.
+//
+// Topology follows the reference modules (paths relative to the reference's src/lib/models/networks):
+//   DLA.forward pose_dla_dcn.py:310-322, Tree.forward :211-224, Root :160-168, BasicBlock :48-62,
+//   DLAUp :437-443, IDAUp :411-417, DeformConv :386-389 (DCN: DCNv2/dcn_v2.py:118-128),
+//   DLASeg.forward :523-570, ConvGRU convGRU.py:72-94, GroupNorm GN.py:4-9.
+#include "engine_model.h"
+
+using namespace cp_engine;
+
+namespace {
+
+// split-K policy: launches with fewer output tiles than kSplitTiles (and >= 8 K steps) are cut into K slices until
+// about kSplitTarget workgroups exist
+constexpr int kSplitTiles = 128, kSplitTarget = 384;  // (384 / 512 measured: B=32 equal, hourglass B=1 latency +7 %)
+
+// ------------------------------------ forward -------------------------------------------------
+struct Fwd {
+    cp_model* m;
+    int B;
+    hipStream_t s;
+    // GroupNorm fusion hooks for the next conv() call (reset after use)
+    double* gn_stats_out = nullptr;
+    const float* gn_in_mr = nullptr;
+    const float* gn_in_a = nullptr;  // f16x3 form of the same fusion: per (image, channel) a, d planes
+    const float* gn_in_d = nullptr;
+    const float* gn_in_gamma = nullptr;
+    const float* gn_in_beta = nullptr;
+    int role = -1;  // CP_ROLE_* of the next conv() call when the shape does not say it (heads, GRU); reset after use
+    const unsigned* gn_in_amax = nullptr;  // bound on max|relu(a*x + d)| for the GNIN loader's pre-scale
+    // |max| slots of this forward's tensors (f16x3 range-safe scaling, ConvParams::in_amax): one zeroed block at the
+    // start of the arena, a slot per Tensor in creation order
+    static constexpr int kMaxSlots = CP_AMAX_STRIDE;
+    static constexpr size_t kSlotBytes = (size_t)CP_AMAX_SUB * CP_AMAX_STRIDE * sizeof(unsigned);
+    Tensor slots_t;
+    unsigned* slots = nullptr;
+    int nslots = 0;
+    void init_slots() {
+        slots_t.blk = std::make_shared<Block>(&m->arena, kSlotBytes);
+        if (m->dry || m->precision != CP_PREC_F16X3 || (g_dbg & CP_SEL_NO_PRESCALE)) return;  // operands used unscaled (range-safety tests)
+        slots = (unsigned*)slots_t.ptr();
+        if (hipMemsetAsync(slots, 0, kSlotBytes, s) != hipSuccess) chk(CP_ERR_LAUNCH);
+    }
+    unsigned* new_slot() {
+        if (!slots) return nullptr;
+        if (nslots >= kMaxSlots) {
+            chk(fail(CP_ERR_STATE, "out of |max| slots"));
+            return nullptr;
+        }
+        return slots + nslots++;
+    }
+    // |max| of a caller-owned input (network images): one extra read of the tensor
+    unsigned* input_slot(const float* x, size_t n) {
+        unsigned* sl = new_slot();
+        if (sl) chk(cp_launch_absmax(x, n, sl, s));
+        return sl;
+    }
+
+    void chk(int rc) {
+        if (rc != CP_OK && m->status == CP_OK) m->status = rc;
+    }
+    // every profiled launch goes through here: `describe` (what the launch is charged for) only runs while profiling
+    template <class D, class F>
+    void timed(D&& describe, F&& launch) {
+        chk(cp_engine::timed(m, s, describe, launch));
+    }
+    Tensor make(int C, int H, int W) {
+        Tensor t;
+        t.C = C;
+        t.H = H;
+        t.W = W;
+        t.blk = std::make_shared<Block>(&m->arena, (size_t)B * H * W * C * sizeof(float));
+        t.amax = new_slot();
+        return t;
+    }
+    void tap(const char* name, const Tensor& t, int c_valid = 0) {
+        if (m->dry || !m->tap_name || std::strcmp(name, m->tap_name) != 0) return;
+        const int C = c_valid ? c_valid : t.C;
+        chk(cp_launch_nhwc_to_nchw(t.ptr(), m->tap_out, B, C, t.H, t.W, t.C, s));
+        if (m->tap_dims) {
+            m->tap_dims[0] = C;
+            m->tap_dims[1] = t.H;
+            m->tap_dims[2] = t.W;
+        }
+    }
+    void tap(const std::string& name, const Tensor& t, int c_valid = 0) { tap(name.c_str(), t, c_valid); }
+
+    // conv3x3 (+bias, ReLU) -> conv1x1 (+bias, optional sigmoid) of a prediction head in one kernel + a slice reduction;
+    // returns false (nothing launched) when the launch would want split-K or the shapes are not eligible
+    bool fused_head(const HeadW& hw, const Tensor& x, bool sigmoid, float* out_nchw) {
+        const ConvW& w = hw.c0;
+        if (x.C != w.CinP) return false;
+        const float* src = x.ptr();
+        ConvParams p = conv_params(B, x.H, x.W, &src, &x.C, 1, w, 1, 1, CP_ACT_RELU);
+        p.splitk = 1;
+        p.fuse_w2_hi = hw.w2_hi;
+        p.fuse_w2_lo = hw.w2_lo;
+        p.fuse_w2_inv = hw.w2_inv;
+        p.fuse_c2 = hw.classes;
+        conv_params_f16(p, w, &x.amax, true, true);
+        if (w.KH != 3 || w.KW != 3 || !cp_head_fuse_supported(p, hw.classes)) return false;
+        int tiles = 0, nk = 0;
+        cp_conv_geometry(p, true, &tiles, &nk);
+        if (tiles < kSplitTiles && nk >= 8) return false;  // small launches keep the split-K path (conv())
+        const int slices = p.CoutPad / 128;
+        Tensor slabs = make(slices * hw.classes, p.Ho, p.Wo);
+        p.fuse_out = slabs.ptr();
+        auto launch = [&]() -> int {
+            int rc = cp_launch_conv16_fused_head(p, s);
+            if (rc == CP_OK)
+                rc = cp_launch_head_reduce(slabs.ptr(), hw.c1.shift, out_nchw, slices, hw.classes, B, p.Ho * p.Wo,
+                                           sigmoid ? 1 : 0, s);
+            return rc;
+        };
+        if (m->dry) return true;
+        timed([&](cp_model::ProfRec& r) {
+            r.variant = cp_halo16_fused_head_supported(p) ? CP_VARIANT_HALO_HEAD : CP_VARIANT_FUSED_HEAD;
+            r.role = CP_ROLE_HEAD;
+            const double M = (double)B * p.Ho * p.Wo;
+            r.flops = 2.0 * M * w.Cout * (double)(w.KH * w.KW * w.Cin) + 2.0 * M * hw.classes * (double)w.Cout;
+            // algorithmic bytes: input once + final maps once + both weight sets (the hidden tensor is not counted:
+            // it is not part of the head's definition, only of the unfused implementation)
+            r.bytes = 4.0 * ((double)B * x.H * x.W * w.Cin + M * hw.classes + (double)w.KH * w.KW * w.Cin * w.Cout +
+                             (double)w.Cout * hw.classes);
+            r.M = (int)M; r.N = w.Cout; r.K = w.KH * w.KW * w.Cin; r.kh = w.KH; r.stride = 1;
+        }, launch);
+        return true;
+    }
+
+    // every fused head of the model in one launch + one slice reduction (cp_model::head_group); false = nothing launched
+    bool fused_heads_grouped(const Tensor& x, float* const* head_out, int sigmoid_hm) {
+        const auto& g = m->head_group;
+        const int n = (int)m->headw.size();
+        if (!g.ok || m->precision != CP_PREC_F16X3 || m->tap_name || (g_dbg & (CP_SEL_NO_HEAD_FUSION | CP_SEL_HEADS_PER_HEAD_LAUNCH)) || x.C != g.Cin)
+            return false;
+        ConvW w;  // the heads' 3x3 layers side by side along N: fragment-ordered f16x3 operands only
+        w.KH = w.KW = 3;
+        w.K = w.Kpad = w.Kpad16 = g.Kpad16;
+        w.Cout = w.CoutPad = n * g.hid;
+        w.scale16 = g.scale16;
+        w.shift = g.shift;
+        w.w16f_hi = g.w16f_hi;
+        w.w16f_lo = g.w16f_lo;
+        const float* src = x.ptr();
+        ConvParams p = conv_params(B, x.H, x.W, &src, &x.C, 1, w, 1, 1, CP_ACT_RELU);
+        conv_params_f16(p, w, &x.amax, true, true);
+        p.splitk = 1;
+        p.fuse_w2_hi = g.w2_hi;
+        p.fuse_w2_lo = g.w2_lo;
+        p.fuse_w2_inv = g.w2_inv;
+        p.fuse_ngroups = n;
+        p.fuse_gtiles = g.hid / 128;
+        p.fuse_out = (float*)0x1000;  // placeholder for the eligibility check
+        // the kernel walks a head's hidden tiles and writes the finished maps itself (CP_SEL_HEADS_SLABS: slabs + reduction
+        // launch); 2: every head of a patch in one workgroup (one staging for all of them) -- when the patches alone fill the
+        // device several times over; below that (small batches, CP_SEL_HEADS_WG_PER_HEAD) one workgroup per patch and head
+        p.fuse_final = (g.Cin == 64 && g.hid == 256 && !(g_dbg & CP_SEL_HEADS_SLABS))
+                           ? (((g_dbg & CP_SEL_HEADS_WG_PER_HEAD) || B * (x.H / 8) * (x.W / 16) < 2048) ? 1 : 2) : 0;
+        if (!cp_halo16_fused_head_supported(p)) return false;
+        if (B * (x.H / 8) * (x.W / 16) * (p.CoutPad / 128) < kSplitTiles) return false;  // small maps: per-head split-K path
+        HeadReduceGroup rg;
+        std::memset(&rg, 0, sizeof(rg));
+        rg.n = n;
+        rg.slices = p.fuse_gtiles;
+        int planes = 0;
+        double flops = 0.0, bytes = 0.0;
+        const double M = (double)B * x.H * x.W;
+        for (int i = 0; i < n; ++i) {
+            const HeadW& hw = m->headw[i];
+            p.fuse_gc2[i] = rg.c2[i] = hw.classes;
+            p.fuse_gbase[i] = rg.base[i] = planes;
+            planes += p.fuse_gtiles * hw.classes;
+            rg.sigmoid[i] = sigmoid_hm && (hw.name == "hm" || hw.name == "hm_hp");
+            rg.bias[i] = hw.c1.shift;
+            rg.out[i] = m->dry ? nullptr : head_out[i];
+            p.fuse_gsig[i] = rg.sigmoid[i];
+            p.fuse_gbias[i] = rg.bias[i];
+            p.fuse_gout[i] = rg.out[i];
+            flops += 2.0 * M * g.hid * (9.0 * g.Cin) + 2.0 * M * hw.classes * (double)g.hid;
+            bytes += 4.0 * (M * hw.classes + 9.0 * g.Cin * g.hid + (double)g.hid * hw.classes);
+        }
+        bytes += 4.0 * M * g.Cin;  // the shared input is read once
+        Tensor slabs;
+        if (!p.fuse_final) slabs = make(planes, x.H, x.W);
+        if (m->dry) return true;
+        p.fuse_out = p.fuse_final ? nullptr : slabs.ptr();
+        auto launch = [&]() -> int {
+            int rc = cp_launch_halo16_fused_head(p, s);
+            if (rc == CP_OK && !p.fuse_final) rc = cp_launch_head_reduce_grouped(slabs.ptr(), rg, B, x.H * x.W, s);
+            return rc;
+        };
+        timed([&](cp_model::ProfRec& r) {
+            r.variant = CP_VARIANT_HALO_HEAD;
+            r.role = CP_ROLE_HEAD;
+            r.flops = flops;
+            r.bytes = bytes;
+            r.M = (int)M; r.N = p.CoutPad; r.K = 9 * g.Cin; r.kh = 3; r.stride = 1;
+        }, launch);
+        return true;
+    }
+
+    // generic conv into a fresh NHWC tensor (or into user NCHW memory when out_nchw != nullptr)
+    Tensor conv(const ConvW& w, const std::vector<const Tensor*>& srcs, int stride, int pad, int act,
+                const Tensor* res = nullptr, const Tensor* offmask = nullptr, int act_from = 0,
+                float* out_nchw = nullptr, int out_ld = 0) {
+        const Tensor& x0 = *srcs[0];
+        const int nsrc = (int)srcs.size();
+        const float* src[CP_MAX_SRC];
+        int src_c[CP_MAX_SRC];
+        const unsigned* src_amax[CP_MAX_SRC];
+        for (int i = 0; i < nsrc; ++i) {
+            src[i] = srcs[i]->ptr();
+            src_c[i] = srcs[i]->C;
+            src_amax[i] = srcs[i]->amax;
+        }
+        ConvParams p = conv_params(B, x0.H, x0.W, src, src_c, nsrc, w, stride, pad, act);
+        if (p.Cin != w.CinP) {
+            chk(fail(CP_ERR_INVALID, "conv: channel mismatch"));
+            return Tensor();
+        }
+        p.res = res ? res->ptr() : nullptr;
+        p.res_ld = res ? res->C : 0;
+        p.act_from = act_from;
+        p.offmask = offmask ? offmask->ptr() : nullptr;
+        p.gn_stats = gn_stats_out;
+        p.gn_groups = 32;
+        p.gn_cpg = w.Cout / 32 > 0 ? w.Cout / 32 : 1;
+        if (gn_in_a) {
+            p.gn_in_a = gn_in_a;
+            p.gn_in_d = gn_in_d;
+        }
+        if (gn_in_mr) {
+            p.gn_in_mr = gn_in_mr;
+            p.gn_in_gamma = gn_in_gamma;
+            p.gn_in_beta = gn_in_beta;
+            p.gn_cpg = w.Cin / 32;
+        }
+        const bool use16 = conv_params_f16(p, w, src_amax, m->precision == CP_PREC_F16X3);
+        if (use16 && p.gn_in_a) p.in_amax[0] = gn_in_amax;
+        if (p.gn_in_a && !use16) {  // the per-channel affine form only exists in the f16x3 1x1 kernel
+            chk(fail(CP_ERR_INVALID, "conv: GroupNorm affine input without an f16x3 kernel"));
+            return Tensor();
+        }
+        Tensor out;
+        if (out_nchw) {
+            p.out = out_nchw;
+            p.store = CP_STORE_NCHW;
+            p.ldo = out_ld;
+            p.coff = 0;
+        } else {
+            // offset/mask maps keep their padded width so the DCN loader can index [pixel*32 + c]
+            const int cstore = (act == CP_ACT_SIGMOID_FROM) ? w.CoutPad : w.Cout;
+            out = make(cstore, p.Ho, p.Wo);
+            p.out = out.ptr();
+            p.out_amax = act == CP_ACT_SIGMOID_FROM ? nullptr : out.amax;  // offset/mask maps are never a GEMM operand
+            p.store = CP_STORE_NHWC;
+            p.ldo = cstore;
+            p.coff = 0;
+        }
+        // deterministic split-K for launches with too few output tiles to fill 256 CUs (low-resolution layers at
+        // small batch): slices write slabs, a small epilogue kernel sums them in order
+        Tensor partial;
+        p.splitk = 1;
+        {
+            int tiles = 0, nk = 0;
+            cp_conv_geometry(p, use16, &tiles, &nk);
+            // small launches of the f16x3 path run on 64 x 64 tiles (four times the workgroups per slice): a quarter of the
+            // slices and of the slab bytes (slices x M x Cout x 4) for the same workgroup count, and no split at all where that
+            // already gives kSplitTiles workgroups.  CP_SEL_TILE128_SMALL: the 128-row tiles everywhere (A/B runs).
+            // Measured at B = 1 / 2 / 4 / 8 (profiles/NOTES.md): pays up to 32 tiles of 128 rows, up to 64 when K is short.
+            if (use16 && tiles > 0 && (tiles <= 32 || (tiles <= 64 && nk <= 36)) && nk >= 8 && !p.gn_stats && !p.gn_in_a &&
+                p.CoutPad % 64 == 0 && w.Cout >= 64 && !(g_dbg & CP_SEL_TILE128_SMALL)) {
+                p.tile_m = p.tile_n = 64;
+                cp_conv_geometry(p, use16, &tiles, &nk);
+            }
+            // (64 x 64 tiles are a quarter of the work each: they are still cut along K below one workgroup per CU)
+            // (CP_SEL_STRM16_ALWAYS -- tests: the row-streaming kernel at any size -- keeps such a layer whole)
+            const bool force_strm = use16 && (g_dbg & CP_SEL_STRM16_ALWAYS) && cp_strm16_supported(p);
+            if (tiles > 0 && tiles < (p.tile_m == 64 ? 256 : kSplitTiles) && nk >= 8 && !p.gn_stats && !force_strm) {
+                int want = (kSplitTarget + tiles - 1) / tiles;
+                if (want > nk / 2) want = nk / 2;
+                if (want > 32) want = 32;
+                if (want > 1) {
+                    const int per = (nk + want - 1) / want;
+                    const int sk = (nk + per - 1) / per;
+                    if (sk > 1) {
+                        p.splitk = sk;
+                        partial = make(sk * p.CoutPad, p.Ho, p.Wo);
+                        p.partial = partial.ptr();
+                    }
+                }
+            }
+        }
+        auto launch = [&]() -> int {
+            int rc = use16 ? cp_launch_conv16(p, s) : cp_launch_conv(p, s);
+            if (rc == CP_OK && p.splitk > 1) rc = cp_launch_splitk_epilogue(p, s);
+            return rc;
+        };
+        if (!m->dry)
+            timed([&](cp_model::ProfRec& r) {
+                r.variant = use16 ? cp_conv16_variant(p) : cp_conv_variant(p);
+                r.role = role >= 0 ? role : offmask ? CP_ROLE_DCN : act == CP_ACT_SIGMOID_FROM ? CP_ROLE_DCN_OFFSET
+                         : (w.KH == 1 && w.KW == 1) ? CP_ROLE_CONV1X1 : CP_ROLE_CONV;
+                const double M = (double)B * p.Ho * p.Wo;
+                const int cin_real = w.Cin;  // un-padded input channels
+                r.flops = 2.0 * M * w.Cout * (double)(w.KH * w.KW * cin_real);
+                // algorithmic bytes: input once + output once + weights (+ offsets/mask for DCN, + residual)
+                r.bytes = 4.0 * ((double)B * x0.H * x0.W * cin_real + M * w.Cout +
+                                 (double)w.KH * w.KW * cin_real * w.Cout + (offmask ? M * 27 : 0.0) +
+                                 (res ? M * w.Cout : 0.0));
+                r.M = (int)M; r.N = w.Cout; r.K = w.KH * w.KW * cin_real; r.kh = w.KH; r.stride = stride;
+            }, launch);
+        gn_stats_out = nullptr;
+        gn_in_mr = nullptr;
+        gn_in_a = nullptr;
+        gn_in_d = nullptr;
+        gn_in_amax = nullptr;
+        role = -1;
+        return out;
+    }
+    const ConvW& cw(const std::string& k) { return m->convs.at(k); }
+
+    Tensor maxpool(const Tensor& x) {
+        Tensor o = make(x.C, x.H / 2, x.W / 2);
+        o.amax = x.amax;  // max|maxpool(x)| <= max|x|: the input's slot is a valid bound
+        if (!m->dry) chk(cp_launch_maxpool2(x.ptr(), o.ptr(), B, x.H, x.W, x.C, s));
+        return o;
+    }
+
+    Tensor basic_block(const std::string& p, const Tensor& x, int stride, const Tensor& residual) {
+        Tensor t = conv(cw(p + ".conv1"), {&x}, stride, 1, CP_ACT_RELU);
+        Tensor o = conv(cw(p + ".conv2"), {&t}, 1, 1, CP_ACT_RELU, &residual);
+        tap(p, o);
+        return o;
+    }
+
+    // one-level Tree (Tree.forward with levels == 1); `bottom` may be supplied by the caller when it
+    // already computed maxpool(x) (the outer two-level tree needs the same tensor as a root child)
+    Tensor tree1(const std::string& p, const Tensor& x, int cin, int cout, int stride, bool level_root,
+                 std::vector<const Tensor*> children, const Tensor* bottom_in = nullptr) {
+        Tensor bottom_own;
+        const Tensor* bottom = &x;
+        if (stride > 1) {
+            if (bottom_in) bottom = bottom_in;
+            else {
+                bottom_own = maxpool(x);
+                bottom = &bottom_own;
+            }
+        }
+        Tensor proj;
+        const Tensor* residual = bottom;
+        if (cin != cout) {
+            proj = conv(cw(p + ".project"), {bottom}, 1, 0, CP_ACT_NONE);
+            residual = &proj;
+        }
+        if (level_root) children.insert(children.begin(), bottom);
+        Tensor x1 = basic_block(p + ".tree1", x, stride, *residual);
+        proj = Tensor();
+        Tensor x2 = basic_block(p + ".tree2", x1, 1, x1);
+        std::vector<const Tensor*> srcs = {&x2, &x1};
+        for (auto* c : children) srcs.push_back(c);
+        Tensor o = conv(cw(p + ".root"), srcs, 1, 0, CP_ACT_RELU);
+        tap(p + ".root", o);
+        return o;
+    }
+    // two-level Tree with level_root = true (base.level3 / base.level4)
+    Tensor tree2(const std::string& p, const Tensor& x, int cin, int cout) {
+        Tensor bottom = maxpool(x);
+        Tensor x1 = tree1(p + ".tree1", x, cin, cout, 2, false, {}, &bottom);
+        return tree1(p + ".tree2", x1, cout, cout, 1, false, {&bottom, &x1});
+    }
+
+    Tensor deform(const std::string& p, const Tensor& x) {
+        const DeformW& d = m->deforms.at(p);
+        Tensor om = conv(d.offset, {&x}, 1, 1, CP_ACT_SIGMOID_FROM, nullptr, nullptr, 18);
+        tap(p + ".offmask", om, 27);
+        Tensor o = conv(d.main, {&x}, 1, 1, CP_ACT_RELU, nullptr, &om);
+        tap(p, o);
+        return o;
+    }
+    Tensor upsample_add(const std::string& p, const Tensor& x, int f, const Tensor& add) {
+        Tensor o = make(x.C, x.H * f, x.W * f);
+        if (!m->dry)
+            chk(cp_launch_upsample_add(x.ptr(), m->ups.at(p), add.ptr(), o.ptr(), B, x.H, x.W, x.C, f, o.amax, s));
+        return o;
+    }
+    // IDAUp.forward: layers[i] = node(up(proj(layers[i])) + layers[i-1])
+    void ida(const std::string& p, std::vector<Tensor>& layers, int startp, int endp, const std::vector<int>& up_f) {
+        for (int i = startp + 1; i < endp; ++i) {
+            const std::string k = std::to_string(i - startp);
+            Tensor t = deform(p + ".proj_" + k, layers[i]);
+            Tensor u = upsample_add(p + ".up_" + k, t, up_f[i - startp], layers[i - 1]);
+            t = Tensor();
+            layers[i] = deform(p + ".node_" + k, u);
+        }
+    }
+
+    // the network's first layers through lowc.hip (f16x3 mode only); returns an invalid Tensor when not applicable
+    Tensor lowc(const std::string& name, int kind, const float* in, int H, int W, int planes, const unsigned* in_amax) {
+        if (m->precision != CP_PREC_F16X3 || (g_dbg & CP_SEL_NO_LOWC)) return Tensor();
+        const int Ho = kind == 2 ? (H - 1) / 2 + 1 : H, Wo = kind == 2 ? (W - 1) / 2 + 1 : W;
+        // level1: the row-streaming kernel (lowc1s_kernel, kind 5) from the batch at which bands of >= 8 output rows give every wave
+        // slot of the chip a strip (CP_SEL_LEVEL1_ROWS_NEVER / _ALWAYS: never / at any size -- tests)
+        if (kind == 2 && m->lowc.count(name + ".rows") && !(g_dbg & CP_SEL_LEVEL1_ROWS_NEVER) &&
+            ((g_dbg & CP_SEL_LEVEL1_ROWS_ALWAYS) || (long)B * ((Wo + 31) / 32) * ((Ho + 7) / 8) >= 2048))
+            kind = 5;
+        auto it = m->lowc.find(kind == 5 ? name + ".rows" : name);
+        if (it == m->lowc.end()) return Tensor();
+        const ConvW& w = cw(name);
+        const bool stem = kind == 0 || kind == 3;  // 3: the 8-plane stem (two groups of 4 planes)
+        const bool l1 = kind == 2 || kind == 5;
+        const int cout = l1 ? 32 : 16, cin = stem ? planes : 16, k = stem ? 7 : 3;
+        Tensor out = make(cout, Ho, Wo);
+        if (m->dry) return out;
+        auto launch = [&]() {
+            return cp_launch_lowc(kind, in, out.ptr(), it->second.hi, it->second.lo, it->second.scale16, w.shift, in_amax,
+                                  out.amax, B, H, W, planes, s);
+        };
+        timed([&](cp_model::ProfRec& r) {
+            r.variant = kind == 5 ? CP_VARIANT_LOWC1S : CP_VARIANT_LOWC0 + (kind == 3 ? 0 : kind);
+            r.role = CP_ROLE_LOWC;
+            const double M = (double)B * Ho * Wo;
+            r.flops = 2.0 * M * cout * (double)(k * k * cin);
+            r.bytes = 4.0 * ((double)B * H * W * cin + M * cout + (double)k * k * cin * cout);
+            r.M = (int)M; r.N = cout; r.K = k * k * cin; r.kh = k; r.stride = l1 ? 2 : 1;
+        }, launch);
+        return out;
+    }
+
+    Tensor to_nhwc(const float* nchw, int C, int Cpad, int H, int W) {
+        Tensor t = make(Cpad, H, W);
+        t.amax = nullptr;  // re-laid network inputs only feed the exact-f32 stems
+        if (!m->dry) chk(cp_launch_nchw_to_nhwc(nchw, t.ptr(), B, C, H, W, Cpad, s));
+        return t;
+    }
+    // a 7x7 stem of the DLA base on a caller-owned NCHW input of C planes: the direct low-channel kernel (lowc.hip) where it
+    // applies, else the input re-laid to Cpad channels + the generic conv
+    Tensor stem(const char* name, int kind, const float* nchw, int H, int W, int C, int Cpad, bool use_lowc) {
+        Tensor t = lowc(name, kind, nchw, H, W, C, use_lowc && !m->dry ? input_slot(nchw, (size_t)B * C * H * W) : nullptr);
+        if (!t.valid()) {
+            Tensor in = to_nhwc(nchw, C, Cpad, H, W);
+            t = conv(cw(name), {&in}, 1, 3, CP_ACT_RELU);
+        }
+        return t;
+    }
+
+    // ---- stacked hourglass forward (large_hourglass.py:50-78, 129-189, 266-286) ----
+    Tensor hg_residual(const std::string& p, const Tensor& x, int stride) {
+        Tensor t = conv(cw(p + ".conv1"), {&x}, stride, 1, CP_ACT_RELU);
+        if (m->convs.count(p + ".skip")) {
+            Tensor sk = conv(cw(p + ".skip"), {&x}, stride, 0, CP_ACT_NONE);
+            return conv(cw(p + ".conv2"), {&t}, 1, 1, CP_ACT_RELU, &sk);  // relu(bn2(conv2) + skip)
+        }
+        return conv(cw(p + ".conv2"), {&t}, 1, 1, CP_ACT_RELU, &x);
+    }
+    Tensor hg_seq(const std::string& p, Tensor x, int n, int first_stride) {
+        for (int i = 0; i < n; ++i) x = hg_residual(p + "." + std::to_string(i), x, i == 0 ? first_stride : 1);
+        return x;
+    }
+    Tensor hg_kp(const std::string& p, const Tensor& x, int n, const int* mods) {
+        const int cm = mods[0], nm = mods[1];
+        Tensor up1 = hg_seq(p + ".up1", x, cm, 1);
+        Tensor low = hg_seq(p + ".low1", x, cm, 2);
+        low = n > 1 ? hg_kp(p + ".low2", low, n - 1, mods + 1) : hg_seq(p + ".low2", low, nm, 1);
+        low = hg_seq(p + ".low3", low, cm, 1);
+        Tensor out = make(up1.C, up1.H, up1.W);
+        if (!m->dry)
+            chk(cp_launch_upsample2_nearest_add(up1.ptr(), low.ptr(), out.ptr(), B, low.H, low.W, low.C, out.amax, s));
+        tap(p, out);
+        return out;
+    }
+    void run_hourglass(int H, int W, const float* images, float* const* head_out, int sigmoid_hm) {
+        static const int mods[6] = {2, 2, 2, 2, 2, 4};
+        init_slots();
+        Tensor inter;
+        {
+            Tensor in = to_nhwc(images, 3, 4, H, W);
+            Tensor p0 = conv(cw("pre.0"), {&in}, 2, 3, CP_ACT_RELU);
+            inter = hg_residual("pre.1", p0, 2);
+        }
+        tap("pre", inter);
+        Tensor cnv;
+        for (int k = 0; k < 2; ++k) {
+            const std::string ks = std::to_string(k);
+            Tensor kp = hg_kp("kps." + ks, inter, 5, mods);
+            cnv = conv(cw("cnvs." + ks), {&kp}, 1, 1, CP_ACT_RELU);
+            tap("cnvs." + ks, cnv);
+            if (k == 0) {
+                Tensor a = conv(cw("inters_.0"), {&inter}, 1, 0, CP_ACT_NONE);
+                Tensor b = conv(cw("cnvs_.0"), {&cnv}, 1, 0, CP_ACT_RELU, &a);  // relu(inters_(inter) + cnvs_(cnv))
+                inter = hg_residual("inters.0", b, 1);
+            }
+        }
+        if (fused_heads_grouped(cnv, head_out, sigmoid_hm)) return;
+        for (size_t i = 0; i < m->headw.size(); ++i) {
+            const HeadW& hw = m->headw[i];
+            const bool sg = sigmoid_hm && (hw.name == "hm" || hw.name == "hm_hp");
+            if (hw.w2_hi && m->precision == CP_PREC_F16X3 && !m->tap_name && !(g_dbg & CP_SEL_NO_HEAD_FUSION) &&
+                fused_head(hw, cnv, sg, m->dry ? (float*)0x1000 : head_out[i]))
+                continue;
+            role = CP_ROLE_HEAD;
+            Tensor hid = conv(hw.c0, {&cnv}, 1, 1, CP_ACT_RELU);
+            role = CP_ROLE_HEAD_FINAL;
+            conv(hw.c1, {&hid}, 1, 0, sg ? CP_ACT_SIGMOID : CP_ACT_NONE, nullptr, nullptr, 0,
+                 m->dry ? (float*)0x1000 : head_out[i], hw.classes);
+        }
+    }
+
+    // ---- PoseResNet forward (resnet_dcn.py: PoseResNet.forward, BasicBlock / Bottleneck.forward) ----
+    Tensor deconv(const std::string& p, const Tensor& x) {
+        const DeconvW& d = m->deconvs.at(p);
+        Tensor o = make(d.Cout, 2 * x.H, 2 * x.W);
+        if (m->dry) return o;
+        if (x.C != d.Cin) {
+            chk(fail(CP_ERR_INVALID, "deconv: channel mismatch"));
+            return o;
+        }
+        const DeconvLaunch l = deconv_launch(d, m->precision == CP_PREC_F16X3, x.ptr(), x.amax, B, x.H, x.W, o.ptr(), o.amax, true);
+        timed([&](cp_model::ProfRec& r) {
+            r.variant = l.f16x3 ? CP_VARIANT_DECONV16 : CP_VARIANT_DECONV_F32;
+            r.role = CP_ROLE_DECONV;
+            const double M = (double)B * x.H * x.W;  // rows of one sub-pixel class
+            r.flops = 2.0 * 4 * M * d.Cout * 4.0 * d.Cin;
+            r.bytes = 4.0 * (M * d.Cin + 4 * M * d.Cout + 16.0 * d.Cin * d.Cout);
+            r.M = (int)(4 * M); r.N = d.Cout; r.K = 4 * d.Cin; r.kh = 4; r.stride = 2;
+        }, [&]() { return cp_launch_deconv(l, s); });
+        return o;
+    }
+    Tensor maxpool3(const Tensor& x) {
+        Tensor o = make(x.C, (x.H - 1) / 2 + 1, (x.W - 1) / 2 + 1);
+        if (!m->dry) chk(cp_launch_maxpool3s2(x.ptr(), o.ptr(), B, x.H, x.W, x.C, o.amax, s));
+        return o;
+    }
+    Tensor res_block(const std::string& p, const Tensor& x, int stride, bool bott) {
+        Tensor sk;
+        const Tensor* res = &x;
+        if (m->convs.count(p + ".downsample")) {
+            sk = conv(cw(p + ".downsample"), {&x}, stride, 0, CP_ACT_NONE);
+            res = &sk;
+        }
+        if (bott) {
+            Tensor a = conv(cw(p + ".conv1"), {&x}, 1, 0, CP_ACT_RELU);
+            Tensor b = conv(cw(p + ".conv2"), {&a}, stride, 1, CP_ACT_RELU);
+            a = Tensor();
+            return conv(cw(p + ".conv3"), {&b}, 1, 0, CP_ACT_RELU, res);  // relu(bn3(conv3) + residual)
+        }
+        Tensor a = conv(cw(p + ".conv1"), {&x}, stride, 1, CP_ACT_RELU);
+        return conv(cw(p + ".conv2"), {&a}, 1, 1, CP_ACT_RELU, res);  // relu(bn2(conv2) + residual)
+    }
+    void run_resnet(int H, int W, const float* images, float* const* head_out, int sigmoid_hm) {
+        bool bott = false;
+        int blocks[4] = {0, 0, 0, 0};
+        resnet_spec(m->resnet, &bott, blocks);
+        init_slots();
+        Tensor x;
+        {
+            Tensor in = to_nhwc(images, 3, 4, H, W);
+            Tensor c1 = conv(cw("conv1"), {&in}, 2, 3, CP_ACT_RELU);
+            in = Tensor();
+            x = maxpool3(c1);
+        }
+        tap("maxpool", x);
+        for (int l = 0; l < 4; ++l) {
+            const std::string ln = "layer" + std::to_string(l + 1);
+            for (int b = 0; b < blocks[l]; ++b) x = res_block(ln + "." + std::to_string(b), x, b == 0 && l ? 2 : 1, bott);
+            tap(ln, x);
+        }
+        for (int i = 0; i < 3; ++i) {
+            const std::string fc = "deconv_layers." + std::to_string(6 * i);
+            x = deform(fc, x);
+            tap("deconv_layers." + std::to_string(6 * i + 2), x);
+            x = deconv("deconv_layers." + std::to_string(6 * i + 3), x);
+            tap("deconv_layers." + std::to_string(6 * i + 5), x);
+        }
+        for (size_t i = 0; i < m->headw.size(); ++i) {
+            const HeadW& hw = m->headw[i];
+            const bool sg = sigmoid_hm && (hw.name == "hm" || hw.name == "hm_hp");
+            role = CP_ROLE_HEAD;
+            Tensor hid = conv(hw.c0, {&x}, 1, 1, CP_ACT_RELU);
+            role = CP_ROLE_HEAD_FINAL;
+            conv(hw.c1, {&hid}, 1, 0, sg ? CP_ACT_SIGMOID : CP_ACT_NONE, nullptr, nullptr, 0,
+                 m->dry ? (float*)0x1000 : head_out[i], hw.classes);
+        }
+    }
+
+    void run(int H, int W, const float* images, const float* pre_img, const float* pre_hm, const float* pre_hm_hp,
+             float* const* head_out, int sigmoid_hm) {
+        init_slots();
+        const bool use_lowc = m->precision == CP_PREC_F16X3 && !(g_dbg & CP_SEL_NO_LOWC) && m->lowc.count("base.base_layer");
+        // stem + level0 in one launch when nothing is added to the stem's output (no previous-frame stems) and nobody asks for it
+        // (CP_SEL_STEM_LEVEL0_UNFUSED: the two kernels, A/B runs and tests)
+        const bool no_pre = m->dry ? m->dry_variant == 1 : (!pre_img && !pre_hm && !pre_hm_hp);
+        const bool fuse01 = use_lowc && no_pre && m->lowc.count("base.level0.rows") && m->stem_bound_l > 0.f &&
+                            !(g_dbg & CP_SEL_STEM_LEVEL0_UNFUSED) && !(m->tap_name && std::strcmp(m->tap_name, "base.base_layer") == 0) &&
+                            !m->convs.count("base.pre_img_layer") && !m->convs.count("base.pre_hm_layer") && !m->convs.count("base.pre_hm_hp_layer");
+        Tensor l0f;
+        if (fuse01) {
+            const unsigned* in_slot = !m->dry ? input_slot(images, (size_t)B * 3 * H * W) : nullptr;
+            l0f = make(16, H, W);
+            if (!m->dry) {
+                const LowcW& a = m->lowc["base.base_layer"];
+                const LowcW& c = m->lowc["base.level0.rows"];
+                auto launch = [&]() {
+                    return cp_launch_lowc_fused(images, l0f.ptr(), a.hi, a.lo, a.scale16, cw("base.base_layer").shift, c.hi, c.lo, c.scale16,
+                                                cw("base.level0").shift, m->stem_bound_l, m->stem_bound_s, in_slot, l0f.amax, B, H, W, 3, s);
+                };
+                timed([&](cp_model::ProfRec& r) {
+                    r.variant = CP_VARIANT_LOWC01;
+                    r.role = CP_ROLE_LOWC;
+                    const double M = (double)B * H * W;
+                    r.flops = 2.0 * M * 16 * (147.0 + 144.0);
+                    r.bytes = 4.0 * (M * 3 + M * 16);
+                    r.M = (int)M; r.N = 16; r.K = 147 + 144; r.kh = 7; r.stride = 1;
+                }, launch);
+            }
+        }
+        Tensor x0 = fuse01 ? Tensor() : stem("base.base_layer", 0, images, H, W, 3, 4, use_lowc);
+        // a dry run (workspace query) is sized for every stem the model has
+        if (m->dry) {
+            if (!m->convs.count("base.pre_img_layer")) pre_img = nullptr;
+            if (!m->convs.count("base.pre_hm_layer")) pre_hm = nullptr;
+            if (!m->convs.count("base.pre_hm_hp_layer")) pre_hm_hp = nullptr;
+        }
+        if ((pre_img && !m->convs.count("base.pre_img_layer")) || (pre_hm && !m->convs.count("base.pre_hm_layer")) ||
+            (pre_hm_hp && !m->convs.count("base.pre_hm_hp_layer"))) {
+            chk(fail(CP_ERR_INVALID, "a previous-frame input was given to a model built without that pre_* layer"));
+            return;
+        }
+        if (pre_img || pre_hm || pre_hm_hp) {
+            Tensor a, b, c;
+            if (pre_img) a = stem("base.pre_img_layer", 0, pre_img, H, W, 3, 4, use_lowc);
+            if (pre_hm) b = stem("base.pre_hm_layer", 0, pre_hm, H, W, 1, 4, use_lowc);
+            if (pre_hm_hp) c = stem("base.pre_hm_hp_layer", 3, pre_hm_hp, H, W, 8, 8, use_lowc);
+            // x = x + pre_img_layer(..) + pre_hm_layer(..) + pre_hm_hp_layer(..)  (left-to-right, :312-318)
+            std::vector<const Tensor*> adds;
+            for (Tensor* t : {&a, &b, &c})
+                if (t->valid()) adds.push_back(t);
+            Tensor sum = make(16, H, W);
+            if (!m->dry)
+                chk(cp_launch_add_relu_sum(x0.ptr(), adds[0]->ptr(), adds.size() > 1 ? adds[1]->ptr() : nullptr,
+                                           adds.size() > 2 ? adds[2]->ptr() : nullptr, sum.ptr(),
+                                           (size_t)B * H * W * 16, sum.amax, s));
+            x0 = sum;
+        }
+        if (!fuse01) tap("base.base_layer", x0);
+        Tensor l0 = fuse01 ? l0f : lowc("base.level0", 1, x0.ptr(), H, W, 16, x0.amax);
+        l0f = Tensor();  // (one owner: the block returns to the arena when l0 is dropped below)
+        if (!l0.valid()) l0 = conv(cw("base.level0"), {&x0}, 1, 1, CP_ACT_RELU);
+        tap("base.level0", l0);
+        x0 = Tensor();
+        Tensor l1 = lowc("base.level1", 2, l0.ptr(), H, W, 16, l0.amax);
+        if (!l1.valid()) l1 = conv(cw("base.level1"), {&l0}, 2, 1, CP_ACT_RELU);
+        tap("base.level1", l1);
+        l0 = Tensor();
+        std::vector<Tensor> L(6);
+        L[2] = tree1("base.level2", l1, 32, 64, 2, false, {});
+        l1 = Tensor();
+        L[3] = tree2("base.level3", L[2], 64, 128);
+        L[4] = tree2("base.level4", L[3], 128, 256);
+        L[5] = tree1("base.level5", L[4], 256, 512, 2, true, {});
+        tap("base.level2", L[2]);
+        tap("base.level3", L[3]);
+        tap("base.level4", L[4]);
+        tap("base.level5", L[5]);
+
+        // DLAUp.forward (:437-443): out = [after ida_2, after ida_1, after ida_0, L5]
+        ida("dla_up.ida_0", L, 4, 6, {1, 2});
+        Tensor o2 = L[5];  // 256 @ 1/8... (after ida_0: 256 ch at L4 resolution)
+        ida("dla_up.ida_1", L, 3, 6, {1, 2, 2});
+        Tensor o1 = L[5];
+        ida("dla_up.ida_2", L, 2, 6, {1, 2, 2, 2});
+        Tensor o0 = L[5];
+        for (auto& t : L) t = Tensor();
+        // DLASeg.forward (:531-536): ida_up over [o0, o1, o2]
+        std::vector<Tensor> y = {o0, o1, o2};
+        o0 = o1 = o2 = Tensor();
+        ida("ida_up", y, 0, 3, {1, 2, 4});
+        Tensor feat = y[2];
+        y.clear();
+        tap("feat", feat);
+
+        std::vector<Tensor> gru_out;
+        if (m->gru) {
+            const int steps = m->tracking ? 4 : 3;
+            role = CP_ROLE_GRU;
+            Tensor x3 = conv(m->gru_x, {&feat}, 1, 1, CP_ACT_NONE);
+            Tensor h;
+            for (int st = 0; st < steps; ++st) {
+                Tensor hn = make(64, feat.H, feat.W);
+                const size_t M = (size_t)B * feat.H * feat.W;
+                if (st == 0) {
+                    // h0 = 0: the three hidden-side convolutions are identically zero (convGRU.py:51,80-84)
+                    if (!m->dry) chk(cp_launch_gru_gate(x3.ptr(), nullptr, nullptr, hn.ptr(), M, hn.amax, s));
+                } else if (m->precision == CP_PREC_F16X3 && m->gru_h16_hi && !(g_dbg & CP_SEL_GRU_UNFUSED) &&
+                           (size_t)M * 192 * 4 < (size_t)0xf0000000u) {
+                    // hidden-side convolution with the gate arithmetic in its epilogue: h3 is never written
+                    if (!m->dry) {
+                        ConvW w;  // the three hidden-side 3x3 layers in fused-gate order: f16x3 operands only, no affine
+                        w.KH = w.KW = 3;
+                        w.K = w.Kpad = w.Kpad16 = 576;
+                        w.Cout = w.CoutPad = 192;
+                        w.w16_hi = m->gru_h16_hi;
+                        w.w16_lo = m->gru_h16_lo;
+                        w.w16f_hi = m->gru_h16f_hi;
+                        w.w16f_lo = m->gru_h16f_lo;
+                        w.scale16 = m->gru_h16_inv;  // 2^-e of the fused-order weight rows
+                        const float* src = h.ptr();
+                        ConvParams p = conv_params(B, feat.H, feat.W, &src, &h.C, 1, w, 1, 1, CP_ACT_NONE);
+                        conv_params_f16(p, w, &h.amax, true, true);
+                        p.out_amax = hn.amax;
+                        p.out = hn.ptr();
+                        p.gru_x3 = x3.ptr();
+                        p.gru_hprev = h.ptr();
+                        p.splitk = 1;
+                        timed([&](cp_model::ProfRec& r) {
+                            r.variant = cp_halo16_gru_supported(p) ? CP_VARIANT_HALO_GRU : CP_VARIANT_GRU;
+                            r.role = CP_ROLE_GRU;
+                            r.flops = 2.0 * (double)M * 192 * 576;
+                            r.bytes = 4.0 * ((double)M * (64 + 192 + 64 + 64) + 576.0 * 192);
+                            r.M = (int)M; r.N = 192; r.K = 576; r.kh = 3; r.stride = 1;
+                        }, [&]() { return cp_launch_conv16_gru(p, s); });
+                    }
+                } else {
+                    role = CP_ROLE_GRU;
+                    Tensor h3 = conv(m->gru_h, {&h}, 1, 1, CP_ACT_NONE);
+                    if (!m->dry) chk(cp_launch_gru_gate(x3.ptr(), h3.ptr(), h.ptr(), hn.ptr(), M, hn.amax, s));
+                }
+                h = hn;
+                gru_out.push_back(h);
+                tap(("convGRU.step" + std::to_string(st)).c_str(), h);
+            }
+        }
+
+        // GroupNorm statistics of every head (32 groups x (sum, sumsq) doubles per image = 128 floats per image and head):
+        // one block, zeroed by one memset per forward pass instead of one per head
+        if (!m->gru && fused_heads_grouped(feat, head_out, sigmoid_hm)) return;
+        Tensor stats_all;
+        if (m->gru) {
+            stats_all = make(128 * (int)m->headw.size(), 1, 1);
+            if (!m->dry && hipMemsetAsync(stats_all.ptr(), 0, sizeof(double) * 64 * B * m->headw.size(), s) != hipSuccess)
+                chk(CP_ERR_LAUNCH);
+        }
+        for (size_t i = 0; i < m->headw.size(); ++i) {
+            const HeadW& hw = m->headw[i];
+            const Tensor* src = &feat;
+            if (m->gru) {
+                int r = -1;
+                const std::string& n = hw.name;
+                if (m->tracking) {
+                    if (n == "tracking" || n == "tracking_hp") r = 0;
+                    else if (n == "hm" || n == "wh" || n == "reg") r = 1;
+                    else if (n == "hm_hp" || n == "hp_offset" || n == "hps" || n == "hps_uncertainty") r = 2;
+                    else if (n == "scale" || n == "scale_uncertainty") r = 3;
+                } else {
+                    if (n == "hm" || n == "wh" || n == "reg") r = 0;
+                    else if (n == "hm_hp" || n == "hp_offset" || n == "hps") r = 1;
+                    else if (n == "scale") r = 2;
+                }
+                if (r < 0) {  // unreachable: cp_model_create refuses heads outside the routing table
+                    chk(fail(CP_ERR_STATE, "head without a ConvGRU step"));
+                    continue;
+                }
+                src = &gru_out[r];
+            }
+            Tensor mr, ad;
+            double* stats = m->gru && !m->dry ? (double*)stats_all.ptr() + (size_t)i * 64 * B : nullptr;
+            const bool fuse_gn = m->gru && ((src->H * src->W) % 32 == 0) && hw.c0.Cout % 32 == 0 && (hw.c0.Cout / 32) % 4 == 0;
+            if (m->gru) {
+                mr = make(64, 1, 1);
+                if (fuse_gn && !m->dry) gn_stats_out = stats;
+            }
+            const bool sg = sigmoid_hm && (hw.name == "hm" || hw.name == "hm_hp");
+            if (!m->gru && hw.w2_hi && m->precision == CP_PREC_F16X3 && !m->tap_name && !(g_dbg & CP_SEL_NO_HEAD_FUSION) &&
+                fused_head(hw, *src, sg, m->dry ? (float*)0x1000 : head_out[i]))
+                continue;
+            role = CP_ROLE_HEAD;
+            Tensor hid = conv(hw.c0, {src}, 1, 1, m->gru ? CP_ACT_NONE : CP_ACT_RELU);
+            if (m->gru) {
+                if (fuse_gn) {
+                    // statistics came out of the conv epilogue; normalise + affine + ReLU happens in the 1x1 loader
+                    const bool affine16 = m->precision == CP_PREC_F16X3 && hw.c1.w16_hi && (hid.H * hid.W) % 128 == 0 &&
+                                          !(g_dbg & CP_SEL_GN_HEAD_F32);
+                    if (affine16) {
+                        // f16x3 1x1 kernel: the normalisation pre-folded to y = relu(a*x + d) per (image, channel)
+                        ad = make(2 * hid.C, 1, 1);
+                        if (!m->dry) {
+                            float* ap = ad.ptr();
+                            float* dp = ap + (size_t)B * hid.C;
+                            unsigned* bound = new_slot();
+                            chk(cp_launch_gn_affine((const double*)stats, hw.gn_gamma, hw.gn_beta, ap, dp, B, hid.C, 32,
+                                                    (double)hid.H * hid.W * (hid.C / 32), 1e-5f, hid.amax, bound, s));
+                            gn_in_a = ap;
+                            gn_in_d = dp;
+                            gn_in_amax = bound;
+                        }
+                    } else if (!m->dry) {
+                        chk(cp_launch_gn_finalize((const double*)stats, mr.ptr(), B * 32,
+                                                  (double)hid.H * hid.W * (hid.C / 32), 1e-5f, s));
+                        gn_in_mr = mr.ptr();
+                        gn_in_gamma = hw.gn_gamma;
+                        gn_in_beta = hw.gn_beta;
+                    }
+                } else if (!m->dry) {
+                    // in place: the slot keeps the larger of the raw and the normalised |max| -- a valid bound
+                    chk(cp_launch_groupnorm_relu(hid.ptr(), hw.gn_gamma, hw.gn_beta, stats, B,
+                                                 hid.H * hid.W, hid.C, 32, 1e-5f, hid.amax, s));
+                }
+            }
+            role = CP_ROLE_HEAD_FINAL;
+            if (gn_in_a && !(g_dbg & CP_SEL_GN_HEAD_MFMA) && hid.C % 64 == 0 && hid.C <= 256 && (hid.H * hid.W) % 64 == 0 &&
+                ((size_t)B * hid.H * hid.W) % 256 == 0 && hw.classes <= 16 && !m->tap_name) {
+                // float32 vector-ALU kernel (ewise.hip: gn_final_kernel): the layer is an HBM stream of the hidden tensor
+                auto launch = [&]() -> int {
+                    return cp_launch_gn_final(hid.ptr(), gn_in_a, gn_in_d, hw.c1.wp, hw.c1.shift, head_out[i], B, hid.H * hid.W,
+                                              hid.C, hw.classes, hw.c1.CoutPad, sg ? 1 : 0, s);
+                };
+                timed([&](cp_model::ProfRec& r) {
+                    r.variant = CP_VARIANT_GN_FINAL;
+                    r.role = CP_ROLE_HEAD_FINAL;
+                    const double M = (double)B * hid.H * hid.W;
+                    r.flops = 2.0 * M * hw.classes * (double)hid.C;
+                    r.bytes = 4.0 * (M * hid.C + M * hw.classes + (double)hid.C * hw.classes);
+                    r.M = (int)M; r.N = hw.classes; r.K = hid.C; r.kh = 1; r.stride = 1;
+                }, launch);
+                gn_in_a = gn_in_d = nullptr;
+                gn_in_amax = nullptr;
+                role = -1;
+                continue;
+            }
+            conv(hw.c1, {&hid}, 1, 0, sg ? CP_ACT_SIGMOID : CP_ACT_NONE, nullptr, nullptr, 0,
+                 m->dry ? (float*)0x1000 : head_out[i], hw.classes);
+        }
+    }
+};
+
+}  // namespace
+
+int cp_engine::forward_impl(cp_model* m, hipStream_t stream, int B, int H, int W, const float* images, const float* pre_img,
+                 const float* pre_hm, const float* pre_hm_hp, float* const* head_out, int sigmoid_hm, void* ws,
+                 size_t ws_bytes, bool dry) {
+    if (!m || !m->finalized) return fail(CP_ERR_STATE, "model not finalized");
+    if (B < 1 || H % 32 || W % 32 || H < 32 || W < 32) return fail(CP_ERR_INVALID, "H and W must be multiples of 32");
+    if (m->hourglass && (H % 128 || W % 128))
+        return fail(CP_ERR_INVALID, "hourglass: H and W must be multiples of 128 (stride 4, then five stride-2 levels)");
+    m->arena.reset(dry ? nullptr : ws, ws_bytes);
+    m->dry = dry;
+    m->status = CP_OK;
+    Fwd f{m, B, stream};
+    if (m->hourglass) f.run_hourglass(H, W, images, head_out, sigmoid_hm);
+    else if (m->resnet) f.run_resnet(H, W, images, head_out, sigmoid_hm);
+    else f.run(H, W, images, pre_img, pre_hm, pre_hm_hp, head_out, sigmoid_hm);
+    if (!dry && m->arena.overflow)
+        return fail(CP_ERR_INVALID, "workspace too small: " + std::to_string(ws_bytes) + " bytes given, this launch sequence peaks at " +
+                                        std::to_string(m->arena.peak));
+    return m->status;
+}

@@ -1,0 +1,342 @@
+// What the engine's translation units share: the model's data types and work-space arena, the one place a ConvParams /
+// DeconvLaunch is built, and the profiling bracket around a launch.
+//   engine_pack.hip     parameter folding and packing (cp_model_create .. cp_model_finalize, cp_model_destroy)
+//   engine_forward.hip  the forward pass and its kernel dispatch (forward_impl)
+//   ops.hip             the stand-alone operators (cp_conv2d_nhwc, cp_conv_transpose2d_nhwc, cp_dcnv2_forward / _backward)
+//   engine.hip          the model's run-time C ABI and the one-line wrappers of the other modules
+// Everything here has C++ linkage (only the C ABI of include/centerpose_hip.h is exported unmangled).
+#pragma once
+#include "../../include/centerpose_hip.h"
+#include "../../include/centerpose_hip_testing.h"
+#undef CP_OK
+#undef CP_ERR_INVALID
+#undef CP_ERR_LAUNCH
+#undef CP_ERR_ALLOC
+#undef CP_ERR_STATE
+#undef CP_DET_STRIDE
+#undef CP_PNP_STRIDE
+#undef CP_TRACK_STRIDE
+#include "cp_common.h"
+
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <memory>
+#include <string>
+#include <vector>
+
+namespace cp_engine {
+
+// sets the calling thread's cp_last_error() text and returns `code` (one definition, engine.hip)
+int fail(int code, const std::string& msg);
+
+extern int g_default_precision;
+extern int g_dbg;  // cp_set_debug: CP_SEL_* kernel-selection switches (include/centerpose_hip_testing.h)
+
+inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// ---------------------------------------------------------------------------------------------
+// Deterministic first-fit arena over a caller-provided workspace.  A dry run (base == nullptr)
+// replays the same allocation sequence to measure the peak, so cp_model_workspace_bytes() and
+// cp_model_forward() always agree.
+// ---------------------------------------------------------------------------------------------
+struct Arena {
+    char* base = nullptr;
+    size_t cap = 0, peak = 0;
+    bool overflow = false;
+    std::vector<std::pair<size_t, size_t>> free_;  // (offset, size), sorted by offset
+
+    void reset(void* b, size_t c) {
+        base = (char*)b;
+        cap = c;
+        peak = 0;
+        overflow = false;
+        free_.clear();
+        free_.push_back({0, (size_t)1 << 62});
+    }
+    size_t alloc(size_t bytes) {
+        bytes = align_up(bytes, 256);
+        for (size_t i = 0; i < free_.size(); ++i) {
+            if (free_[i].second >= bytes) {
+                const size_t off = free_[i].first;
+                free_[i].first += bytes;
+                free_[i].second -= bytes;
+                if (free_[i].second == 0) free_.erase(free_.begin() + i);
+                if (off + bytes > peak) peak = off + bytes;
+                if (base && off + bytes > cap) overflow = true;
+                return off;
+            }
+        }
+        overflow = true;
+        return 0;
+    }
+    void release(size_t off, size_t bytes) {
+        bytes = align_up(bytes, 256);
+        size_t i = 0;
+        while (i < free_.size() && free_[i].first < off) ++i;
+        free_.insert(free_.begin() + i, {off, bytes});
+        if (i + 1 < free_.size() && free_[i].first + free_[i].second == free_[i + 1].first) {
+            free_[i].second += free_[i + 1].second;
+            free_.erase(free_.begin() + i + 1);
+        }
+        if (i > 0 && free_[i - 1].first + free_[i - 1].second == free_[i].first) {
+            free_[i - 1].second += free_[i].second;
+            free_.erase(free_.begin() + i);
+        }
+    }
+};
+
+struct Block {
+    Arena* a;
+    size_t off, bytes;
+    Block(Arena* a_, size_t b) : a(a_), off(a_->alloc(b)), bytes(b) {}
+    ~Block() { a->release(off, bytes); }
+};
+
+// NHWC activation handle; memory returns to the arena when the last handle dies (the single stream
+// orders reuse after the last enqueued consumer).
+struct Tensor {
+    std::shared_ptr<Block> blk;
+    int C = 0, H = 0, W = 0;
+    unsigned* amax = nullptr;  // 4-byte slot holding the float bits of max|x| (f16x3 mode; ConvParams::in_amax)
+    float* ptr() const { return blk->a->base ? (float*)(blk->a->base + blk->off) : nullptr; }
+    bool valid() const { return (bool)blk; }
+};
+
+struct ConvW {
+    float* wp = nullptr;           // [Kpad][CoutPad]
+    const float* scale = nullptr;  // [CoutPad] or nullptr
+    const float* shift = nullptr;  // [CoutPad] or nullptr
+    int Cin = 0, CinP = 0, Cout = 0, CoutPad = 0, KH = 0, KW = 0, K = 0, Kpad = 0;
+    void* w16_hi = nullptr;  // split-f16 copies [CoutPad][K] (only when every K-step of 32 stays inside one tap)
+    void* w16_lo = nullptr;
+    int Kpad16 = 0;
+    void* w16f_hi = nullptr;  // DCN main convolutions: the same in MFMA fragment order (dcn16p.hip)
+    void* w16f_lo = nullptr;
+    // per-output-channel power-of-two pre-scale of the split-f16 copies: rows are stored times wfwd[co] = 2^e,
+    // winv = 2^-e, scale16 = (scale or 1) * winv is what the f16x3 kernels' epilogue multiplies with
+    float* wfwd = nullptr;
+    float* winv = nullptr;
+    float* scale16 = nullptr;
+};
+
+struct LowcW {
+    void* hi = nullptr;
+    void* lo = nullptr;
+    float* scale16 = nullptr;  // folded BatchNorm scale x 2^-e of the fragment rows
+};
+
+struct DeformW {
+    ConvW offset;  // conv_offset_mask (27 -> 32 padded), shift = bias
+    ConvW main;    // DCN weight, scale/shift = folded bias + BN
+};
+
+// dense ConvTranspose2d(k=4, s=2, p=1) + folded BatchNorm of a resdcn deconv stage (deconv16.hip)
+struct DeconvW {
+    float* wf = nullptr;           // float32 sub-kernels [4][CoutPad][4*Cin]
+    void* hi = nullptr;            // split-f16 copies, rows times 2^e per output channel
+    void* lo = nullptr;
+    const float* scale = nullptr;  // [CoutPad] folded BatchNorm scale
+    float* scale16 = nullptr;      // scale * 2^-e
+    const float* shift = nullptr;
+    int Cin = 0, Cout = 0;
+};
+
+struct HeadW {
+    std::string name;
+    int classes = 0;
+    ConvW c0, c1;
+    void* w2_hi = nullptr;  // fused-head form of c1 (cp_launch_pack_head_w2); null when the pair is not eligible
+    void* w2_lo = nullptr;
+    float* w2_inv = nullptr;  // [32] 2^-e per final channel (+ [32] 2^e used while packing)
+    float* gn_gamma = nullptr;
+    float* gn_beta = nullptr;
+};
+
+// resdcn depth -> (Bottleneck?, blocks per layer): resnet_spec of resnet_dcn.py
+inline bool resnet_spec(int depth, bool* bottleneck, int* blocks) {
+    static const int spec[5][5] = {{18, 2, 2, 2, 2}, {34, 3, 4, 6, 3}, {50, 3, 4, 6, 3}, {101, 3, 4, 23, 3}, {152, 3, 8, 36, 3}};
+    for (const auto& r : spec)
+        if (r[0] == depth) {
+            *bottleneck = depth >= 50;
+            for (int i = 0; i < 4; ++i) blocks[i] = r[i + 1];
+            return true;
+        }
+    return false;
+}
+
+}  // namespace cp_engine
+
+struct cp_model {
+    std::string arch;
+    bool gru = false, tracking = false, finalized = false, hourglass = false;
+    int resnet = 0;  // resdcn_N: N (resnet_dcn.py), else 0
+    int precision = cp_engine::g_default_precision;
+    int head_conv = 256;
+    std::vector<std::pair<std::string, int>> heads;
+    std::map<std::string, std::vector<float>> params;  // host copies until finalize
+    std::map<std::string, cp_engine::ConvW> convs;
+    std::map<std::string, cp_engine::DeformW> deforms;
+    std::map<std::string, float*> ups;
+    std::map<std::string, cp_engine::DeconvW> deconvs;
+    std::vector<cp_engine::HeadW> headw;
+    // every fused head of the model in ONE launch (they all read the same feature map): the heads' 3x3 fragments,
+    // scale / shift, 1x1 fragments and w2_inv tables concatenated along N (ConvParams::fuse_ngroups)
+    struct HeadGroup {
+        bool ok = false;
+        void* w16f_hi = nullptr;
+        void* w16f_lo = nullptr;
+        void* w2_hi = nullptr;
+        void* w2_lo = nullptr;
+        float* scale16 = nullptr;
+        float* shift = nullptr;
+        float* w2_inv = nullptr;
+        int Cin = 0, hid = 0, Kpad16 = 0;
+    } head_group;
+    std::map<std::string, cp_engine::LowcW> lowc;  // hi / lo weight fragments of the lowc.hip layers
+    int ws_key[4] = {0, 0, 0, -1};  // (B, H, W, g_dbg) of the cached work-space query below
+    size_t ws_cached = 0;
+    int dry_variant = 0;  // work-space query: 1 = the dry run takes the fused stem + level0 path where the model allows it (the query
+                          // runs both forms and returns the larger peak: switches and taps may select either form later)
+    float stem_bound_l = 0.f, stem_bound_s = 0.f;  // |base_layer out| <= stem_bound_l * max|image| + stem_bound_s (fused stem + level0)
+    cp_engine::ConvW gru_x, gru_h;
+    void* gru_h16_hi = nullptr;  // hidden-side GRU weights re-ordered [tile][r|z|n][32] for the fused-gate kernel
+    void* gru_h16_lo = nullptr;
+    void* gru_h16f_hi = nullptr;  // ... and in MFMA fragment order (halo16.hip)
+    void* gru_h16f_lo = nullptr;
+    float* gru_h16_fwd = nullptr;  // [192] per-row 2^e of the fused-order copies, and the matching 2^-e
+    float* gru_h16_inv = nullptr;
+    std::vector<void*> device_allocs;
+    cp_engine::Arena arena;
+    // forward-call state
+    hipStream_t stream = nullptr;
+    int B = 0;
+    bool dry = false;
+    int status = CP_OK;
+    const char* tap_name = nullptr;
+    float* tap_out = nullptr;
+    int* tap_dims = nullptr;
+    // optional per-launch profiling of the implicit-GEMM kernels (HIP events on the launch stream)
+    struct ProfRec {
+        int variant;
+        int role = 0;  // CP_ROLE_*
+        double flops, bytes;
+        int M, N, K, kh, stride;
+        hipEvent_t e0, e1;
+    };
+    std::map<std::vector<uint64_t>, hipGraphExec_t> graphs;  // captured detect() launches, keyed by every argument
+    bool profile = false;
+    std::vector<ProfRec> prof;
+    double roles[CP_NUM_ROLES * 4] = {0};  // per-role totals of the last cp_model_profile_read
+    std::vector<hipEvent_t> event_pool;
+    hipEvent_t get_event() {
+        if (!event_pool.empty()) {
+            hipEvent_t e = event_pool.back();
+            event_pool.pop_back();
+            return e;
+        }
+        hipEvent_t e = nullptr;
+        (void)hipEventCreate(&e);
+        return e;
+    }
+};
+
+namespace cp_engine {
+
+int forward_impl(cp_model* m, hipStream_t stream, int B, int H, int W, const float* images, const float* pre_img,
+                 const float* pre_hm, const float* pre_hm_hp, float* const* head_out, int sigmoid_hm, void* ws,
+                 size_t ws_bytes, bool dry);
+
+// The one profiling bracket: runs `launch` (-> CP_* code).  While the model is profiling, `describe` fills in what the launch
+// is charged for (variant, role, flops, bytes, shape) and two events on `s` around it time it for cp_model_profile_read.
+// Both are inlined lambdas: nothing is evaluated, allocated or copied for the record when profiling is off.
+template <class D, class F>
+inline int timed(cp_model* m, hipStream_t s, D&& describe, F&& launch) {
+    if (!m->profile) return launch();
+    cp_model::ProfRec r;
+    describe(r);
+    r.e0 = m->get_event();
+    r.e1 = m->get_event();
+    (void)hipEventRecord(r.e0, s);
+    const int rc = launch();
+    (void)hipEventRecord(r.e1, s);
+    m->prof.push_back(r);
+    return rc;
+}
+
+// The one place a ConvParams is built.  Zeroed, then what every convolution launch has in common: the sources (a virtual
+// concat along C, all B x H x W), the geometry, and the float32 form of the weights with their epilogue.  The caller adds
+// only what is its own (residual, offsets, fusion pointers, GroupNorm hooks, split-K, where the output goes).
+inline ConvParams conv_params(int B, int H, int W, const float* const* src, const int* src_c, int nsrc, const ConvW& w,
+                              int stride, int pad, int act) {
+    ConvParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.nsrc = nsrc;
+    for (int i = 0; i < nsrc; ++i) {
+        p.src[i] = src[i];
+        p.src_c[i] = src_c[i];
+        p.Cin += src_c[i];
+    }
+    p.B = B;
+    p.H = H;
+    p.W = W;
+    p.Ho = (H + 2 * pad - w.KH) / stride + 1;
+    p.Wo = (W + 2 * pad - w.KW) / stride + 1;
+    p.KH = w.KH;
+    p.KW = w.KW;
+    p.stride = stride;
+    p.pad = pad;
+    p.K = w.K;
+    p.Kpad = w.Kpad;
+    p.wp = w.wp;
+    p.Cout = w.Cout;
+    p.CoutPad = w.CoutPad;
+    p.scale = w.scale;
+    p.shift = w.shift;
+    p.act = act;
+    p.dbg = g_dbg;
+    return p;
+}
+// Second step, after the caller's own fields: attaches w's split-f16 operands, and where the f16x3 kernels take the launch --
+// `f16x3` (the caller's precision) and cp_conv16_supported(p) as p stands now, or an `f16_only` kernel that has no float32
+// form (fused heads, fused GRU step) -- switches the epilogue to scale16 and hands over the sources' |max| slots.
+// Returns whether they take it.
+inline bool conv_params_f16(ConvParams& p, const ConvW& w, const unsigned* const* in_amax, bool f16x3, bool f16_only = false) {
+    p.w16_hi = w.w16_hi;
+    p.w16_lo = w.w16_lo;
+    p.w16f_hi = w.w16f_hi;
+    p.w16f_lo = w.w16f_lo;
+    p.Kpad16 = w.Kpad16;
+    if (!f16_only && !(f16x3 && cp_conv16_supported(p))) return false;
+    p.scale = w.scale16;
+    for (int i = 0; i < p.nsrc; ++i) p.in_amax[i] = in_amax[i];
+    return true;
+}
+
+// ... and a DeconvLaunch: x [B,H,W,d.Cin] -> out [B,2H,2W,d.Cout], operands and scale of the chosen arithmetic
+inline DeconvLaunch deconv_launch(const DeconvW& d, bool f16x3, const float* x, const unsigned* in_amax, int B, int H, int W,
+                                  float* out, unsigned* out_amax, bool relu) {
+    DeconvLaunch l;
+    std::memset(&l, 0, sizeof(l));
+    l.f16x3 = f16x3;
+    l.x = x;
+    l.wf = d.wf;
+    l.w_hi = d.hi;
+    l.w_lo = d.lo;
+    l.scale = f16x3 ? d.scale16 : d.scale;
+    l.shift = d.shift;
+    l.out = out;
+    l.in_amax = in_amax;
+    l.out_amax = out_amax;
+    l.B = B;
+    l.H = H;
+    l.W = W;
+    l.Cin = d.Cin;
+    l.Cout = d.Cout;
+    l.relu = relu;
+    return l;
+}
+
+}  // namespace cp_engine

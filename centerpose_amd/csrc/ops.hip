@@ -1,0 +1,366 @@
+// The stand-alone operators of the C ABI (include/centerpose_hip.h): single layers on caller tensors, outside any cp_model
+// -- cp_conv2d_nhwc, cp_conv_transpose2d_nhwc, cp_dcnv2_forward / cp_dcnv2_backward.  Each packs its PyTorch-layout weights
+// into a caller-provided workspace on every call and then launches the same kernels as the engine.
+#include "engine_model.h"
+
+using namespace cp_engine;
+
+namespace {
+
+// Bump carver over an operator's workspace.  Each operator describes its regions once, in a *_carve function: run on the
+// caller's pointer it hands out the regions, run on nullptr it only counts, and *_workspace_bytes is `off` of that run -- the
+// size and the carve-up cannot drift apart.
+struct Carve {
+    char* base;
+    size_t off = 0;
+    template <class T>
+    T* take(size_t bytes) {
+        T* p = base ? (T*)(base + off) : nullptr;
+        off += align_up(bytes, 256);
+        return p;
+    }
+};
+
+constexpr size_t kSlotBytes = (size_t)CP_AMAX_SUB * CP_AMAX_STRIDE * sizeof(unsigned);  // one |max| slot block
+
+// Regions of a [Cout,Cin,kh,kw] weight packed for the f16x3 kernels: two binary16 copies [cpad][kpad], the per-channel weight
+// scales (2^e, 2^-e, scale * 2^-e), the input's |max| slot block, the fragment-ordered copies of the binary16 weights
+struct Pack16 {
+    void *hi, *lo;
+    float *wfwd, *winv, *sc16;
+    unsigned* slot;
+    void *fhi, *flo;
+};
+Pack16 carve_pack16(Carve& c, size_t kpad, size_t cpad) {
+    Pack16 r;
+    r.hi = c.take<void>(kpad * cpad * 2);
+    r.lo = c.take<void>(kpad * cpad * 2);
+    r.wfwd = c.take<float>(cpad * sizeof(float));
+    r.winv = c.take<float>(cpad * sizeof(float));
+    r.sc16 = c.take<float>(cpad * sizeof(float));
+    r.slot = c.take<unsigned>(kSlotBytes);
+    r.fhi = c.take<void>(kpad * cpad * 2);
+    r.flo = c.take<void>(kpad * cpad * 2);
+    return r;
+}
+
+__global__ void dcn_offmask_pack_kernel(const float* __restrict__ offset, const float* __restrict__ mask,
+                                        float* __restrict__ om, int B, int HW) {
+    // offset [B,18,HW], mask [B,9,HW] -> om [B,HW,32]
+    const size_t total = (size_t)B * HW * 32;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int c = (int)(i & 31);
+        const size_t px = i >> 5;
+        const size_t b = px / HW, p = px - b * HW;
+        float v = 0.f;
+        if (c < 18) v = offset[(b * 18 + c) * HW + p];
+        else if (c < 27) v = mask[(b * 9 + (c - 18)) * HW + p];
+        om[i] = v;
+    }
+}
+
+// max |mask| of the packed records (channels 18 .. 26) -> `slot`
+__global__ void dcn_mask_amax_kernel(const float* __restrict__ om, size_t px, unsigned* __restrict__ slot) {
+    float m = 0.f;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < px * 9; i += (size_t)gridDim.x * blockDim.x)
+        m = fmaxf(m, fabsf(om[(i / 9) * 32 + 18 + i % 9]));
+    cp_amax_commit(slot, m);
+}
+
+// The f16x3 DCN kernels fold the mask into the corner weights of the pre-scaled activation, so the blended value is bounded
+// by max |x| * max |mask|, not max |x|: a caller-supplied mask above 1 would push it past binary16's range (hi half saturated,
+// lo half infinite).  Raise x's bound to max |x| * max(1, max |mask|), rounded up; masks within [-1, 1] leave it untouched.
+__global__ void dcn_act_bound_kernel(unsigned* __restrict__ x_slot, const unsigned* __restrict__ mask_slot) {
+    if (threadIdx.x != 0) return;
+    const float am = __uint_as_float(cp_amax_read(mask_slot));
+    if (!(am > 1.f)) return;
+    const double d = (double)__uint_as_float(cp_amax_read(x_slot)) * (double)am;  // exact (24 + 24 bits)
+    float bound = (float)d;
+    if ((double)bound < d) bound = __uint_as_float(__float_as_uint(bound) + 1u);  // rounded up
+    x_slot[0] = max(x_slot[0], __float_as_uint(bound));
+}
+
+// Packs the PyTorch-layout weight `wt` ([w.Cout][w.Cin][taps]) for the f16x3 path into the carved regions `r` and measures the
+// input: range-safe operands -- per-channel power-of-two weight scale (folded into scale16 with `scale`), per-tensor activation
+// scale from one |max| pass over x[0..nx).  `om` (DCN: the packed offset / mask records of `px` pixels): the mask's |max| goes to
+// slot 1 of the (zeroed) slot block and is folded into x's bound.  The fragment-ordered copies exist when the shape allows
+// them.  On CP_OK the f16x3 fields of `w` describe the packed operands.
+int pack_f16x3(const Pack16& r, const float* wt, const float* scale, int taps, ConvW& w, const float* x, size_t nx,
+               const float* om, size_t px, hipStream_t s) {
+    if (hipMemsetAsync(r.hi, 0, (char*)r.wfwd - (char*)r.hi, s) != hipSuccess) return CP_ERR_LAUNCH;
+    if (hipMemsetAsync(r.wfwd, 0, (char*)r.fhi - (char*)r.wfwd, s) != hipSuccess) return CP_ERR_LAUNCH;
+    w.w16_hi = r.hi;
+    w.w16_lo = r.lo;
+    w.Kpad16 = w.K;
+    w.scale16 = r.sc16;
+    int rc = cp_launch_weight_scale(wt, w.Cout, w.Cin * taps, r.wfwd, r.winv, s);
+    if (rc == CP_OK) rc = cp_launch_pack_weight16(wt, r.hi, r.lo, w.Cout, w.Cin, taps, w.Kpad16, 0, r.wfwd, s);
+    if (rc == CP_OK) rc = cp_launch_scale16(scale, r.winv, r.sc16, w.Cout, s);
+    if (rc == CP_OK) rc = cp_launch_absmax(x, nx, r.slot, s);
+    if (rc == CP_OK && om) {
+        const size_t g = std::min<size_t>((px * 9 + 255) / 256, 2048);
+        hipLaunchKernelGGL(dcn_mask_amax_kernel, dim3((unsigned)g), dim3(256), 0, s, om, px, r.slot + 1);
+        hipLaunchKernelGGL(dcn_act_bound_kernel, dim3(1), dim3(64), 0, s, r.slot, (const unsigned*)(r.slot + 1));
+        if (hipGetLastError() != hipSuccess) rc = CP_ERR_LAUNCH;
+    }
+    if (rc == CP_OK && w.CoutPad % 32 == 0 && w.Kpad16 % 16 == 0) {
+        rc = cp_launch_frag16_repack(r.hi, r.fhi, w.CoutPad, w.Kpad16, s);
+        if (rc == CP_OK) rc = cp_launch_frag16_repack(r.lo, r.flo, w.CoutPad, w.Kpad16, s);
+        w.w16f_hi = r.fhi;
+        w.w16f_lo = r.flo;
+    }
+    return rc;
+}
+
+// cp_conv2d_nhwc: f32 packed weights [kpad][cpad] + the f16x3 regions
+struct Conv2dWs {
+    float* wp;
+    Pack16 f16;
+};
+Conv2dWs conv2d_carve(Carve& c, int Cin, int Cout, int KH, int KW) {
+    const size_t kpad = align_up((size_t)KH * KW * Cin, 16);
+    const size_t cpad = align_up((size_t)Cout, cp_conv_tile_n(Cout));
+    Conv2dWs r;
+    r.wp = c.take<float>(kpad * cpad * sizeof(float));
+    r.f16 = carve_pack16(c, kpad, cpad);
+    return r;
+}
+
+// cp_conv_transpose2d_nhwc: float32 sub-kernels + two binary16 copies + 2^-e per row + scale * 2^-e + the input's |max| slot
+struct DeconvWs {
+    float* wf;
+    void *hi, *lo;
+    float *inv, *sc16;
+    unsigned* slot;
+};
+DeconvWs deconv_carve(Carve& c, int Cin, int Cout) {
+    const size_t cpad = (size_t)cp_deconv_cout_pad(Cout > 0 ? Cout : 1), n = 4 * cpad * 4 * (size_t)(Cin > 0 ? Cin : 0);
+    DeconvWs r;
+    r.wf = c.take<float>(n * 4);
+    r.hi = c.take<void>(n * 2);
+    r.lo = c.take<void>(n * 2);
+    r.inv = c.take<float>(cpad * 4);
+    r.sc16 = c.take<float>(cpad * 4);
+    r.slot = c.take<unsigned>(kSlotBytes);
+    return r;
+}
+
+// cp_dcnv2_forward (fast path): [x NHWC B*H*W*C][offmask NHWC B*H*W*32][y NHWC B*H*W*Co][packed weights][shift cpad] + the
+// f16x3 regions
+struct DcnWs {
+    float *x, *om, *y, *wp, *shift;
+    Pack16 f16;
+};
+DcnWs dcn_carve(Carve& c, int B, int C, int H, int W, int Co) {
+    const size_t px = (size_t)B * H * W;
+    const size_t cpad = align_up((size_t)Co, cp_conv_tile_n(Co));
+    DcnWs r;
+    r.x = c.take<float>(px * C * 4);
+    r.om = c.take<float>(px * 32 * 4);
+    r.y = c.take<float>(px * Co * 4);
+    r.wp = c.take<float>((size_t)9 * C * cpad * 4);
+    r.shift = c.take<float>(cpad * 4);
+    r.f16 = carve_pack16(c, (size_t)9 * C, cpad);
+    return r;
+}
+
+// DCNv2 backward: shape checks here (as the forward's), kernels in dcn_bwd.hip
+const char* dcn_bwd_shape_error(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw, int dh,
+                                int dw, int dg, int* Ho, int* Wo) {
+    if (B < 1 || C < 1 || H < 1 || W < 1 || Co < 1 || kh < 1 || kw < 1 || sh < 1 || sw < 1 || ph < 0 || pw < 0 || dh < 1 ||
+        dw < 1 || dg < 1 || C % dg != 0)
+        return "dcn_v2_backward: bad shape argument (C must be divisible by deformable_group)";
+    const long long ho = ((long long)H + 2LL * ph - ((long long)dh * (kh - 1) + 1)) / sh + 1;
+    const long long wo = ((long long)W + 2LL * pw - ((long long)dw * (kw - 1) + 1)) / sw + 1;
+    if (ho < 1 || wo < 1 || H + 2LL * ph < (long long)dh * (kh - 1) + 1 || W + 2LL * pw < (long long)dw * (kw - 1) + 1)
+        return "dcn_v2_backward: empty output (kernel extent larger than the padded input)";
+    const long long lim = 0x7fffffffLL, T = (long long)kh * kw;
+    if ((long long)B * C * H * W >= lim || (long long)B * Co * ho * wo >= lim || (long long)B * dg * 2 * T * ho * wo >= lim ||
+        (long long)Co * C * T >= lim || (long long)C * T * ho * wo >= lim)
+        return "dcn_v2_backward: a tensor has 2^31 elements or more";
+    *Ho = (int)ho;
+    *Wo = (int)wo;
+    return nullptr;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t cp_conv2d_workspace_bytes(int Cin, int Cout, int KH, int KW) {
+    Carve c{nullptr};
+    conv2d_carve(c, Cin, Cout, KH, KW);
+    return c.off;
+}
+
+size_t cp_conv_transpose2d_workspace_bytes(int Cin, int Cout) {
+    Carve c{nullptr};
+    deconv_carve(c, Cin, Cout);
+    return c.off;
+}
+
+size_t cp_dcnv2_workspace_bytes(int B, int C, int H, int W, int Co) {
+    Carve c{nullptr};
+    dcn_carve(c, B, C, H, W, Co);
+    return c.off;
+}
+
+int cp_conv_transpose2d_nhwc(cp_stream_t stream, const float* x, const float* w, const float* scale, const float* shift, float* out,
+                             int B, int H, int W, int Cin, int Cout, int act, void* workspace, size_t workspace_bytes) {
+    if (!x || !w || !out || !workspace) return fail(CP_ERR_INVALID, "null argument");
+    if (B < 1 || H < 1 || W < 1 || Cout < 1) return fail(CP_ERR_INVALID, "empty shape");
+    if (Cin % 32) return fail(CP_ERR_INVALID, "Cin must be a multiple of 32");
+    if (act != CP_ACT_NONE && act != CP_ACT_RELU) return fail(CP_ERR_INVALID, "act must be 0 (none) or 1 (relu)");
+    Carve c{(char*)workspace};
+    const DeconvWs r = deconv_carve(c, Cin, Cout);
+    if (workspace_bytes < c.off) return fail(CP_ERR_INVALID, "workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    const bool f16x3 = g_default_precision == CP_PREC_F16X3;
+    int rc = cp_launch_pack_deconv(w, f16x3 ? nullptr : r.wf, f16x3 ? r.hi : nullptr, f16x3 ? r.lo : nullptr, r.inv, Cin, Cout, s);
+    if (rc == CP_OK && f16x3) {
+        // range-safe operands as in cp_conv2d_nhwc: per-channel weight scale (folded into scale16), per-tensor activation scale
+        if (hipMemsetAsync(r.slot, 0, kSlotBytes, s) != hipSuccess) return CP_ERR_LAUNCH;
+        rc = cp_launch_scale16(scale, r.inv, r.sc16, Cout, s);
+        if (rc == CP_OK) rc = cp_launch_absmax(x, (size_t)B * H * W * Cin, r.slot, s);
+    }
+    if (rc != CP_OK) return fail(rc, "deconv weight packing failed");
+    DeconvW d;
+    d.wf = r.wf;
+    d.hi = r.hi;
+    d.lo = r.lo;
+    d.scale = scale;
+    d.scale16 = r.sc16;
+    d.shift = shift;
+    d.Cin = Cin;
+    d.Cout = Cout;
+    rc = cp_launch_deconv(deconv_launch(d, f16x3, x, f16x3 ? r.slot : nullptr, B, H, W, out, nullptr, act == CP_ACT_RELU), s);
+    return rc == CP_OK ? CP_OK : fail(rc, "deconv launch failed (shape too large for 32-bit offsets?)");
+}
+
+int cp_conv2d_nhwc(cp_stream_t stream, const float* x, const float* w, const float* scale, const float* shift,
+                   const float* residual, float* out, int B, int H, int W, int Cin, int Cout, int KH, int KW,
+                   int stride, int pad, int act, void* workspace, size_t workspace_bytes) {
+    if (!x || !w || !out || !workspace) return fail(CP_ERR_INVALID, "null argument");
+    if (Cin % 4) return fail(CP_ERR_INVALID, "Cin must be a multiple of 4");
+    Carve c{(char*)workspace};
+    const Conv2dWs r = conv2d_carve(c, Cin, Cout, KH, KW);
+    if (workspace_bytes < c.off) return fail(CP_ERR_INVALID, "workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    const int bn = cp_conv_tile_n(Cout);
+    ConvW cw;
+    cw.Cin = cw.CinP = Cin;
+    cw.Cout = Cout;
+    cw.CoutPad = (int)align_up(Cout, bn);
+    cw.KH = KH;
+    cw.KW = KW;
+    cw.K = KH * KW * Cin;
+    cw.Kpad = (int)align_up(cw.K, 16);
+    cw.wp = r.wp;
+    cw.scale = scale;
+    cw.shift = shift;
+    // scale/shift are read up to CoutPad: only allow un-padded Cout when they are given
+    if ((scale || shift) && cw.CoutPad != Cout) return fail(CP_ERR_INVALID, "scale/shift need Cout % tile_n == 0");
+    if (hipMemsetAsync(r.wp, 0, (size_t)cw.Kpad * cw.CoutPad * sizeof(float), s) != hipSuccess) return CP_ERR_LAUNCH;
+    int rc = cp_launch_pack_weight(w, r.wp, Cout, Cin, KH * KW, Cin, cw.CoutPad, 0, s);
+    if (rc != CP_OK) return rc;
+    ConvParams p = conv_params(B, H, W, &x, &Cin, 1, cw, stride, pad, act);
+    p.res = residual;
+    p.res_ld = Cout;
+    p.out = out;
+    p.store = CP_STORE_NHWC;
+    p.ldo = Cout;
+    if (g_default_precision == CP_PREC_F16X3 && Cin % 32 == 0 && KH * KW <= 32 && bn >= 32) {
+        rc = pack_f16x3(r.f16, w, scale, KH * KW, cw, x, (size_t)B * H * W * Cin, nullptr, 0, s);
+        if (rc != CP_OK) return rc;
+        const unsigned* slot = r.f16.slot;
+        if (conv_params_f16(p, cw, &slot, true)) return cp_launch_conv16(p, s);
+    }
+    return cp_launch_conv(p, s);
+}
+
+size_t cp_dcnv2_backward_workspace_bytes(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw,
+                                         int dh, int dw, int deformable_group) {
+    int Ho = 0, Wo = 0;
+    if (dcn_bwd_shape_error(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group, &Ho, &Wo)) return 0;
+    return cp_dcn_backward_ws_bytes(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group);
+}
+
+int cp_dcnv2_backward(cp_stream_t stream, const float* input, const float* weight, const float* offset, const float* mask,
+                      const float* grad_output, float* grad_input, float* grad_offset, float* grad_mask, float* grad_weight,
+                      float* grad_bias, int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw,
+                      int dh, int dw, int deformable_group, void* workspace, size_t workspace_bytes) {
+    int Ho = 0, Wo = 0;
+    if (const char* e = dcn_bwd_shape_error(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group, &Ho, &Wo))
+        return fail(CP_ERR_INVALID, e);
+    if (!input || !weight || !offset || !mask || !grad_output || !grad_input || !grad_offset || !grad_mask || !grad_weight ||
+        !grad_bias || !workspace)
+        return fail(CP_ERR_INVALID, "dcn_v2_backward: null argument");
+    if (workspace_bytes < cp_dcn_backward_ws_bytes(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group))
+        return fail(CP_ERR_INVALID, "dcn_v2_backward: workspace too small");
+    DcnBwdArgs a{input, weight, offset, mask, grad_output, grad_input, grad_offset, grad_mask, grad_weight, grad_bias,
+                 B, C, H, W, Co, Ho, Wo, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group};
+    const int rc = cp_launch_dcn_backward((hipStream_t)stream, a, workspace);
+    return rc == CP_OK ? CP_OK : fail(rc, "dcn_v2_backward: kernel launch failed");
+}
+
+// DCNv2 forward with the reference's NCHW layouts (see header)
+int cp_dcnv2_forward(cp_stream_t stream, const float* input, const float* weight, const float* bias, const float* offset,
+                     const float* mask, float* output, int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw,
+                     int ph, int pw, int dh, int dw, int deformable_group, void* workspace, size_t workspace_bytes) {
+    if (!input || !weight || !bias || !offset || !mask || !output || !workspace)
+        return fail(CP_ERR_INVALID, "null argument");
+    if (B < 1 || C < 1 || H < 1 || W < 1 || Co < 1 || kh < 1 || kw < 1 || sh < 1 || sw < 1 || ph < 0 || pw < 0 || dh < 1 ||
+        dw < 1 || deformable_group < 1 || C % deformable_group != 0)
+        return fail(CP_ERR_INVALID, "dcn_v2_forward: bad shape argument (C must be divisible by deformable_group)");
+    hipStream_t s = (hipStream_t)stream;
+    const bool fast = kh == 3 && kw == 3 && sh == 1 && sw == 1 && ph == 1 && pw == 1 && dh == 1 && dw == 1 &&
+                      deformable_group == 1 && C % 16 == 0 && cp_conv_tile_n(Co) >= 64 && !(g_dbg & CP_SEL_DCN_GENERIC);
+    if (!fast) {
+        // everything CenterPose does not use (other kernels / strides / dilations, deformable groups, tiny channel
+        // counts): the generic float32 kernel on the reference's own layouts, no workspace
+        const int Ho = (H + 2 * ph - (dh * (kh - 1) + 1)) / sh + 1, Wo = (W + 2 * pw - (dw * (kw - 1) + 1)) / sw + 1;
+        if (Ho < 1 || Wo < 1) return fail(CP_ERR_INVALID, "dcn_v2_forward: empty output");
+        const int rc = cp_launch_dcn_generic(s, input, weight, bias, offset, mask, output, B, C, H, W, Co, Ho, Wo, kh, kw, sh,
+                                             sw, ph, pw, dh, dw, deformable_group);
+        return rc == CP_OK ? CP_OK : fail(rc, "dcn_v2_forward: generic kernel launch failed");
+    }
+    Carve c{(char*)workspace};
+    const DcnWs r = dcn_carve(c, B, C, H, W, Co);
+    if (workspace_bytes < c.off) return fail(CP_ERR_INVALID, "workspace too small");
+    const size_t px = (size_t)B * H * W;
+    ConvW cw;
+    cw.Cin = cw.CinP = C;
+    cw.Cout = Co;
+    cw.CoutPad = (int)align_up((size_t)Co, cp_conv_tile_n(Co));
+    cw.KH = cw.KW = 3;
+    cw.K = cw.Kpad = 9 * C;
+    cw.wp = r.wp;
+    cw.shift = r.shift;
+    int rc = cp_launch_nchw_to_nhwc(input, r.x, B, C, H, W, C, s);
+    if (rc != CP_OK) return rc;
+    hipLaunchKernelGGL(dcn_offmask_pack_kernel, dim3(2048), dim3(256), 0, s, offset, mask, r.om, B, H * W);
+    if (hipMemsetAsync(r.wp, 0, (size_t)9 * C * cw.CoutPad * 4, s) != hipSuccess) return CP_ERR_LAUNCH;
+    if (hipMemsetAsync(r.shift, 0, (size_t)cw.CoutPad * 4, s) != hipSuccess) return CP_ERR_LAUNCH;
+    if (hipMemcpyAsync(r.shift, bias, (size_t)Co * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return CP_ERR_LAUNCH;
+    rc = cp_launch_pack_weight(weight, r.wp, Co, C, 9, C, cw.CoutPad, 0, s);
+    if (rc != CP_OK) return rc;
+    const float* src = r.x;
+    ConvParams p = conv_params(B, H, W, &src, &C, 1, cw, 1, 1, CP_ACT_NONE);
+    p.out = r.y;
+    p.store = CP_STORE_NHWC;
+    p.ldo = Co;
+    p.offmask = r.om;
+    bool use16 = false;
+    if (g_default_precision == CP_PREC_F16X3 && C % 32 == 0) {
+        rc = pack_f16x3(r.f16, weight, nullptr, 9, cw, r.x, px * C, r.om, px, s);
+        if (rc != CP_OK) return rc;
+        const unsigned* slot = r.f16.slot;
+        use16 = conv_params_f16(p, cw, &slot, true);
+        if (!use16) p.w16_hi = p.w16_lo = nullptr;
+    }
+    rc = use16 ? cp_launch_conv16(p, s) : cp_launch_conv(p, s);
+    if (rc != CP_OK) return rc;
+    return cp_launch_nhwc_to_nchw(r.y, output, B, Co, H, W, Co, s);
+}
+
+}  // extern "C"

@@ -2,7 +2,7 @@
 
 What is contractual here is the reference's surface (DCNv2/dcn_v2.py:57-128): the constructor argument order, the state-dict
 names (``weight``, ``bias``, ``conv_offset_mask.weight`` / ``.bias``), the initial values, and what ``forward`` means.  The
-engine (csrc/engine.hip) never goes through these modules; they exist for code that builds the reference's layers one by one
+engine (csrc/engine_forward.hip) never goes through these modules; they exist for code that builds the reference's layers one by one
 (the reference's own ``testcpu.py`` self-checks run against them, tests/test_gpu_parity.py)."""
 import collections
 

@@ -919,7 +919,7 @@ def test_splitk_epilogue_quad_form_equals_elementwise(device, arch, B):
 @pytest.mark.parametrize("arch,B,hw,tracking", [("dla_34", 2, 256, False), ("hourglass", 1, 512, False), ("dla_34", 1, 512, False),
                                                 ("dla_34", 16, 512, False), ("dla_34", 16, 512, True)])
 def test_grouped_fused_heads_equal_per_head_launches(device, arch, B, hw, tracking):
-    """All fused prediction heads in ONE launch (engine.hip: fused_heads_grouped; concatenated operands, per-tile head
+    """All fused prediction heads in ONE launch (engine_forward.hip: fused_heads_grouped; concatenated operands, per-tile head
     table; a workgroup walks the hidden tiles of its head and finishes the maps) against one launch per head and against the
     slab + reduction-launch form: the same arithmetic in the same order -> bit-identical head tensors, sigmoid included."""
     # (tracking: the twelve heads of the CenterPoseTrack network -- the most a grouped launch walks -- on the two-frame inputs)
