@@ -192,6 +192,13 @@ struct ConvParams {
     const float* fuse_w2_inv;             // fused head: 2^-e of the 1x1 weights per final channel [32]
     int dbg;  // kernel-selection switches of cp_set_debug (CP_SEL_*, include/centerpose_hip_testing.h)
     const float* offmask;  // DCN mode: NHWC [B,H,W,32] = 18 offsets (dh,dw interleaved per tap) + 9 masks (already sigmoided) + 5 pad
+    // Fused head over a LIST of output pixels instead of the whole map (igemm16.hip, cp_launch_conv16_fused_head_rows): GEMM row m
+    // is image b = m / rows_per_image, pixel row_index[b * row_index_stride + m % rows_per_image] (= ho * Wo + wo, clamped into
+    // the map), M = B * rows_per_image.  Taps outside the image are zero as everywhere; a pixel listed twice is computed twice.
+    // Slabs as above with this M; with fuse_ngroups > 0 the grouped plane layout (fuse_gtiles / fuse_gc2 / fuse_gbase) and
+    // fuse_w2_inv[g * 64 + c].
+    const int* row_index;
+    int rows_per_image, row_index_stride;
 };
 
 int cp_launch_conv(const ConvParams& p, hipStream_t stream);
@@ -202,7 +209,8 @@ int cp_launch_splitk_epilogue(const ConvParams& p, hipStream_t stream);
 // K steps (of 16 for the f32 kernels, 32 for f16x3) and output tiles of the launch cp_launch_conv[16] would make
 void cp_conv_geometry(const ConvParams& p, bool f16x3, int* tiles, int* nk);
 const char* cp_conv_variant_name(int v);
-#define CP_NUM_CONV_VARIANTS 45
+#define CP_NUM_CONV_VARIANTS 46
+#define CP_VARIANT_HEAD_ROWS 45  // igemm16p fused head over a pixel list (regression heads at the decoded peaks)
 #define CP_VARIANT_DECONV_F32 43  // deconv16.hip, exact f32
 #define CP_VARIANT_DECONV16 44    // deconv16.hip, f16x3
 #define CP_VARIANT_STRM16 41
@@ -266,6 +274,8 @@ int cp_launch_absmax(const float* x, size_t n, unsigned* slot, hipStream_t s);
 // (w1: [C2][Chid] float32 -> two arrays of Chid*32 binary16); slice reduction + bias (+ sigmoid) -> NCHW
 bool cp_head_fuse_supported(const ConvParams& p, int c2);
 int cp_launch_conv16_fused_head(const ConvParams& p, hipStream_t stream);
+// the same head at the pixels of ConvParams::row_index only (always the per-tap implicit GEMM: scattered pixels share no patch)
+int cp_launch_conv16_fused_head_rows(const ConvParams& p, hipStream_t stream);
 // w2_inv: [32] floats, receives 2^-e per final channel (the packed rows are scaled by 2^e)
 int cp_launch_pack_head_w2(const float* w1, void* hi, void* lo, float* w2_inv, int C2, int Chid, hipStream_t s);
 int cp_launch_head_reduce(const float* slabs, const float* bias, float* out_nchw, int slices, int C2, int B, int HW,
@@ -371,6 +381,19 @@ int cp_launch_decode(hipStream_t s, int B, int J, int H, int W, float* hm, const
                      const float* hps_unc, const float* scale, const float* scale_unc, const float* reg, float* hm_hp,
                      const float* hp_offset, const float* tracking, const float* tracking_hp, int K, int rep_mode,
                      int fit_gaussian, float balance, int legacy_bool_mask, int apply_sigmoid, float* det, void* ws);
+// The two halves of either decode.  Peaks: NMS + top-K of hm and the J hm_hp maps -> pk_score / pk_ind [B][J+1][K] (`cand`: the
+// tiled form's candidate buffer = its workspace behind the peak tables; unused up to 32768 pixels).  Assoc: the records from
+// the peak tables.  compact == 0: the regression heads are dense NCHW maps read at pk_ind; compact != 0: they are tables holding
+// the values AT the peaks -- [B][C][K] (entry k = the head at pk_ind[b][0][k]) for the centre-indexed heads and
+// hp_offset [B][J][2][K] (entry k of joint j = the head at pk_ind[b][j + 1][k]); hm_hp stays the dense map.
+int cp_launch_decode_peaks(hipStream_t s, int B, int J, int H, int W, float* hm, float* hm_hp, int K, int apply_sigmoid,
+                           float* pk_score, int* pk_ind, void* cand);
+int cp_launch_decode_assoc(hipStream_t s, int B, int J, int H, int W, const float* hps, const float* wh, const float* hps_unc,
+                           const float* scale, const float* scale_unc, const float* reg, const float* hm_hp,
+                           const float* hp_offset, const float* tracking, const float* tracking_hp, const float* pk_score,
+                           const int* pk_ind, int K, int rep_mode, int fit_gaussian, float balance, int legacy_bool_mask,
+                           int compact, float* det);
+size_t cp_decode_cand_bytes(int B, int J, int H, int W, int K);  // 0 up to 32768 pixels; (size_t)-1: unsupported shape
 // tiled peaks (any W % 4 == 0, W <= 4096, K <= H*W <= 2^20; decode.hip): 0 bytes = unsupported shape
 size_t cp_decode_tiled_ws_bytes(int B, int J, int H, int W, int K);
 int cp_launch_decode_tiled(hipStream_t s, int B, int J, int H, int W, float* hm, const float* hps, const float* wh,

@@ -283,6 +283,9 @@ struct AssocParams {
     float* det;
     int B, J, H, W, K, rep_mode, fit_gaussian, legacy_bool_mask;
     float balance;
+    // 0: the regression heads are dense maps [B][C][H*W], read at the peak's pixel; 1: compact tables [B][C][K] holding the
+    // values at the centre peaks (entry k), hp_offset [B][J][2][K] at the joint peaks.  hm_hp is the dense map either way.
+    int compact;
 };
 
 __device__ __forceinline__ float sel_mix(float m, float a, float b) {
@@ -353,6 +356,8 @@ __device__ void window_moments(const float* data, int H, int W, float xf, float 
 __global__ __launch_bounds__(128) void assoc_kernel(const AssocParams p) {
     const int j = blockIdx.x, b = blockIdx.y, k = threadIdx.x;
     const int K = p.K, J = p.J, H = p.H, W = p.W, HW = H * W, NM = J + 1;
+    // plane stride of a regression head and the plane-relative position of (joint peak k, centre peak k) in it
+    const int PS = p.compact ? K : HW;
     extern __shared__ float sh[];
     float* cx = sh;
     float* cy = sh + K;
@@ -366,8 +371,9 @@ __global__ __launch_bounds__(128) void assoc_kernel(const AssocParams p) {
         const int ind = p.pk_ind[o];
         float x = (float)(ind % W), y = (float)(ind / W);
         if (p.hp_offset) {
-            x = __fadd_rn(x, p.hp_offset[((size_t)b * 2 + 0) * HW + ind]);
-            y = __fadd_rn(y, p.hp_offset[((size_t)b * 2 + 1) * HW + ind]);
+            const size_t o0 = p.compact ? ((size_t)b * J + j) * 2 * K + k : (size_t)b * 2 * HW + ind;
+            x = __fadd_rn(x, p.hp_offset[o0]);
+            y = __fadd_rn(y, p.hp_offset[o0 + PS]);
         } else {
             x = __fadd_rn(x, 0.5f);
             y = __fadd_rn(y, 0.5f);
@@ -384,19 +390,20 @@ __global__ __launch_bounds__(128) void assoc_kernel(const AssocParams p) {
     const size_t oc = ((size_t)b * NM) * K + k;
     const float score = p.pk_score[oc];
     const int ind = p.pk_ind[oc];
+    const int at = p.compact ? k : ind;  // where this centre sits inside a head's plane
     const float xs_i = (float)(ind % W), ys_i = (float)(ind / W);
     float xs = xs_i, ys = ys_i;
     if (p.reg) {
-        xs = __fadd_rn(xs_i, p.reg[((size_t)b * 2 + 0) * HW + ind]);
-        ys = __fadd_rn(ys_i, p.reg[((size_t)b * 2 + 1) * HW + ind]);
+        xs = __fadd_rn(xs_i, p.reg[((size_t)b * 2 + 0) * PS + at]);
+        ys = __fadd_rn(ys_i, p.reg[((size_t)b * 2 + 1) * PS + at]);
     } else {
         xs = __fadd_rn(xs_i, 0.5f);
         ys = __fadd_rn(ys_i, 0.5f);
     }
-    const float w2 = p.wh[((size_t)b * 2 + 0) * HW + ind] / 2.f, h2 = p.wh[((size_t)b * 2 + 1) * HW + ind] / 2.f;
+    const float w2 = p.wh[((size_t)b * 2 + 0) * PS + at] / 2.f, h2 = p.wh[((size_t)b * 2 + 1) * PS + at] / 2.f;
     const float l = __fsub_rn(xs, w2), t = __fsub_rn(ys, h2), r = __fadd_rn(xs, w2), bt = __fadd_rn(ys, h2);
-    const float kx = __fadd_rn(p.hps[((size_t)b * 2 * J + 2 * j) * HW + ind], xs_i);
-    const float ky = __fadd_rn(p.hps[((size_t)b * 2 * J + 2 * j + 1) * HW + ind], ys_i);
+    const float kx = __fadd_rn(p.hps[((size_t)b * 2 * J + 2 * j) * PS + at], xs_i);
+    const float ky = __fadd_rn(p.hps[((size_t)b * 2 * J + 2 * j + 1) * PS + at], ys_i);
 
     // ---- nearest heat-map peak (decode.py:147-156) ----
     float best = 0.f;
@@ -468,9 +475,9 @@ __global__ __launch_bounds__(128) void assoc_kernel(const AssocParams p) {
     for (int q = 0; q < 2; ++q) {
         const int c = 2 * j + q;
         float v = 0.f;
-        if (p.hps_unc) v = __fmul_rn(sqrtf(expf(p.hps_unc[((size_t)b * 2 * J + c) * HW + ind])), p.balance);
+        if (p.hps_unc) v = __fmul_rn(sqrtf(expf(p.hps_unc[((size_t)b * 2 * J + c) * PS + at])), p.balance);
         d[CP_DET_KPS_DISP_STD + c] = v;
-        d[CP_DET_TRACKING_HP + c] = p.tracking_hp ? p.tracking_hp[((size_t)b * 2 * J + c) * HW + ind] : 0.f;
+        d[CP_DET_TRACKING_HP + c] = p.tracking_hp ? p.tracking_hp[((size_t)b * 2 * J + c) * PS + at] : 0.f;
     }
     if (j == 0) {
         d[CP_DET_BBOX + 0] = l;
@@ -480,10 +487,10 @@ __global__ __launch_bounds__(128) void assoc_kernel(const AssocParams p) {
         d[CP_DET_SCORE] = score;
         d[CP_DET_CLS] = 0.f;  // single category (opts.py:435): clses = topk_ind / K = 0
         for (int c = 0; c < 3; ++c) {
-            d[CP_DET_SCALE + c] = p.scale ? p.scale[((size_t)b * 3 + c) * HW + ind] : 0.f;
-            d[CP_DET_SCALE_UNC + c] = p.scale_unc ? sqrtf(expf(p.scale_unc[((size_t)b * 3 + c) * HW + ind])) : 0.f;
+            d[CP_DET_SCALE + c] = p.scale ? p.scale[((size_t)b * 3 + c) * PS + at] : 0.f;
+            d[CP_DET_SCALE_UNC + c] = p.scale_unc ? sqrtf(expf(p.scale_unc[((size_t)b * 3 + c) * PS + at])) : 0.f;
         }
-        for (int c = 0; c < 2; ++c) d[CP_DET_TRACKING + c] = p.tracking ? p.tracking[((size_t)b * 2 + c) * HW + ind] : 0.f;
+        for (int c = 0; c < 2; ++c) d[CP_DET_TRACKING + c] = p.tracking ? p.tracking[((size_t)b * 2 + c) * PS + at] : 0.f;
     }
 }
 
@@ -760,9 +767,73 @@ bool tiled_geom(int J, int H, int W, int K, TiledGeom* g) {
 
 size_t tiled_pk_bytes(int B, int J, int K) { return ((size_t)B * (J + 1) * K * 8 + 255) & ~(size_t)255; }
 
+// the tiled form of the peaks half: bands -> (sigmoid in place) -> merge
+int launch_peaks_tiled(hipStream_t s, int B, int J, int H, int W, float* hm, float* hm_hp, int K, int apply_sigmoid,
+                       float* pk_score, int* pk_ind, void* cand_ws) {
+    TiledGeom g;
+    if (B < 1 || !tiled_geom(J, H, W, K, &g) || !cand_ws || ((uintptr_t)cand_ws & 15u) != 0) return CP_ERR_INVALID;
+    unsigned long long* cand = (unsigned long long*)cand_ws;
+    hipLaunchKernelGGL(peaks_tile_kernel, dim3(g.T, J + 1, B), dim3(PK_THREADS), 0, s, hm, hm_hp, J, H, W, K, g.R, g.NS,
+                       apply_sigmoid, cand);
+    if (apply_sigmoid)
+        hipLaunchKernelGGL(sigmoid_maps_kernel, dim3((H * W / 4 + 255) / 256, J + 1, B), dim3(256), 0, s, hm, hm_hp, J, H * W);
+    const int cap = g.NS <= 2 * PK_THREADS ? 1 : g.NS <= 4 * PK_THREADS ? 2 : g.NS <= 8 * PK_THREADS ? 4
+                  : g.NS <= 16 * PK_THREADS ? 8 : 16;
+    switch (cap) {
+        case 1: hipLaunchKernelGGL(peaks_merge_kernel<1>, dim3(J + 1, B), dim3(PK_THREADS), 0, s, cand, g.NS, K, pk_score, pk_ind); break;
+        case 2: hipLaunchKernelGGL(peaks_merge_kernel<2>, dim3(J + 1, B), dim3(PK_THREADS), 0, s, cand, g.NS, K, pk_score, pk_ind); break;
+        case 4: hipLaunchKernelGGL(peaks_merge_kernel<4>, dim3(J + 1, B), dim3(PK_THREADS), 0, s, cand, g.NS, K, pk_score, pk_ind); break;
+        case 8: hipLaunchKernelGGL(peaks_merge_kernel<8>, dim3(J + 1, B), dim3(PK_THREADS), 0, s, cand, g.NS, K, pk_score, pk_ind); break;
+        default: hipLaunchKernelGGL(peaks_merge_kernel<16>, dim3(J + 1, B), dim3(PK_THREADS), 0, s, cand, g.NS, K, pk_score, pk_ind); break;
+    }
+    return hipGetLastError() == hipSuccess ? CP_OK : CP_ERR_LAUNCH;
+}
+
 }  // namespace
 
 size_t cp_decode_ws_bytes(int B, int J, int K) { return (size_t)B * (J + 1) * K * 8 + 256; }
+
+size_t cp_decode_cand_bytes(int B, int J, int H, int W, int K) {
+    if (B < 1 || J < 1 || K < 1 || K > 128 || H < 1 || W < 4 || W % 4 != 0 || (long long)H * W < K) return (size_t)-1;
+    if ((long long)H * W <= PK_THREADS * 32) return 0;
+    TiledGeom g;
+    if (B < 1 || !tiled_geom(J, H, W, K, &g)) return (size_t)-1;
+    return (size_t)B * (J + 1) * g.NS * 8;
+}
+
+// Peaks half.  Up to 32768 pixels one kernel; above, the tiled form (three launches, two when the maps are already
+// sigmoided) with its candidates [B][J+1][NS] u64 in `cand`.
+int cp_launch_decode_peaks(hipStream_t s, int B, int J, int H, int W, float* hm, float* hm_hp, int K, int apply_sigmoid,
+                           float* pk_score, int* pk_ind, void* cand_ws) {
+    if (B < 1 || K < 1 || K > 128 || J < 1 || W % 4 != 0 || (long long)H * W < K) return CP_ERR_INVALID;
+    if (H * W <= PK_THREADS * 32) {
+        if (H * W <= PK_THREADS * 16)
+            hipLaunchKernelGGL(peaks_kernel<4>, dim3(J + 1, B), dim3(PK_THREADS), 0, s, hm, hm_hp, J, H, W, K, apply_sigmoid,
+                               pk_score, pk_ind);
+        else
+            hipLaunchKernelGGL(peaks_kernel<8>, dim3(J + 1, B), dim3(PK_THREADS), 0, s, hm, hm_hp, J, H, W, K, apply_sigmoid,
+                               pk_score, pk_ind);
+        return hipGetLastError() == hipSuccess ? CP_OK : CP_ERR_LAUNCH;
+    }
+    return launch_peaks_tiled(s, B, J, H, W, hm, hm_hp, K, apply_sigmoid, pk_score, pk_ind, cand_ws);
+}
+
+int cp_launch_decode_assoc(hipStream_t s, int B, int J, int H, int W, const float* hps, const float* wh, const float* hps_unc,
+                           const float* scale, const float* scale_unc, const float* reg, const float* hm_hp,
+                           const float* hp_offset, const float* tracking, const float* tracking_hp, const float* pk_score,
+                           const int* pk_ind, int K, int rep_mode, int fit_gaussian, float balance, int legacy_bool_mask,
+                           int compact, float* det) {
+    if (B < 1 || K < 1 || K > 128 || J < 1) return CP_ERR_INVALID;
+    AssocParams p;
+    p.hps = hps; p.wh = wh; p.hps_unc = hps_unc; p.scale = scale; p.scale_unc = scale_unc; p.reg = reg;
+    p.hm_hp = hm_hp; p.hp_offset = hp_offset; p.tracking = tracking; p.tracking_hp = tracking_hp;
+    p.pk_score = pk_score; p.pk_ind = pk_ind; p.det = det;
+    p.B = B; p.J = J; p.H = H; p.W = W; p.K = K; p.rep_mode = rep_mode; p.fit_gaussian = fit_gaussian;
+    p.legacy_bool_mask = legacy_bool_mask; p.balance = balance;
+    p.compact = compact ? 1 : 0;
+    hipLaunchKernelGGL(assoc_kernel, dim3(J, B), dim3(128), 3 * K * sizeof(float), s, p);
+    return hipGetLastError() == hipSuccess ? CP_OK : CP_ERR_LAUNCH;
+}
 
 int cp_launch_decode(hipStream_t s, int B, int J, int H, int W, float* hm, const float* hps, const float* wh,
                      const float* hps_unc, const float* scale, const float* scale_unc, const float* reg, float* hm_hp,
@@ -771,20 +842,10 @@ int cp_launch_decode(hipStream_t s, int B, int J, int H, int W, float* hm, const
     if (H * W > PK_THREADS * 32 || H * W < K || K < 1 || K > 128 || J < 1 || W % 4 != 0) return CP_ERR_INVALID;
     float* pk_score = (float*)ws;
     int* pk_ind = (int*)((char*)ws + (size_t)B * (J + 1) * K * 4);
-    if (H * W <= PK_THREADS * 16)
-        hipLaunchKernelGGL(peaks_kernel<4>, dim3(J + 1, B), dim3(PK_THREADS), 0, s, hm, hm_hp, J, H, W, K, apply_sigmoid,
-                           pk_score, pk_ind);
-    else
-        hipLaunchKernelGGL(peaks_kernel<8>, dim3(J + 1, B), dim3(PK_THREADS), 0, s, hm, hm_hp, J, H, W, K, apply_sigmoid,
-                           pk_score, pk_ind);
-    AssocParams p;
-    p.hps = hps; p.wh = wh; p.hps_unc = hps_unc; p.scale = scale; p.scale_unc = scale_unc; p.reg = reg;
-    p.hm_hp = hm_hp; p.hp_offset = hp_offset; p.tracking = tracking; p.tracking_hp = tracking_hp;
-    p.pk_score = pk_score; p.pk_ind = pk_ind; p.det = det;
-    p.B = B; p.J = J; p.H = H; p.W = W; p.K = K; p.rep_mode = rep_mode; p.fit_gaussian = fit_gaussian;
-    p.legacy_bool_mask = legacy_bool_mask; p.balance = balance;
-    hipLaunchKernelGGL(assoc_kernel, dim3(J, B), dim3(128), 3 * K * sizeof(float), s, p);
-    return hipGetLastError() == hipSuccess ? CP_OK : CP_ERR_LAUNCH;
+    const int rc = cp_launch_decode_peaks(s, B, J, H, W, hm, hm_hp, K, apply_sigmoid, pk_score, pk_ind, nullptr);
+    if (rc != CP_OK) return rc;
+    return cp_launch_decode_assoc(s, B, J, H, W, hps, wh, hps_unc, scale, scale_unc, reg, hm_hp, hp_offset, tracking, tracking_hp,
+                                  pk_score, pk_ind, K, rep_mode, fit_gaussian, balance, legacy_bool_mask, 0, det);
 }
 
 size_t cp_decode_tiled_ws_bytes(int B, int J, int H, int W, int K) {
@@ -803,26 +864,8 @@ int cp_launch_decode_tiled(hipStream_t s, int B, int J, int H, int W, float* hm,
     if (B < 1 || !tiled_geom(J, H, W, K, &g) || ((uintptr_t)ws & 15u) != 0) return CP_ERR_INVALID;
     float* pk_score = (float*)ws;
     int* pk_ind = (int*)((char*)ws + (size_t)B * (J + 1) * K * 4);
-    unsigned long long* cand = (unsigned long long*)((char*)ws + tiled_pk_bytes(B, J, K));
-    hipLaunchKernelGGL(peaks_tile_kernel, dim3(g.T, J + 1, B), dim3(PK_THREADS), 0, s, hm, hm_hp, J, H, W, K, g.R, g.NS,
-                       apply_sigmoid, cand);
-    if (apply_sigmoid)
-        hipLaunchKernelGGL(sigmoid_maps_kernel, dim3((H * W / 4 + 255) / 256, J + 1, B), dim3(256), 0, s, hm, hm_hp, J, H * W);
-    const int cap = g.NS <= 2 * PK_THREADS ? 1 : g.NS <= 4 * PK_THREADS ? 2 : g.NS <= 8 * PK_THREADS ? 4
-                  : g.NS <= 16 * PK_THREADS ? 8 : 16;
-    switch (cap) {
-        case 1: hipLaunchKernelGGL(peaks_merge_kernel<1>, dim3(J + 1, B), dim3(PK_THREADS), 0, s, cand, g.NS, K, pk_score, pk_ind); break;
-        case 2: hipLaunchKernelGGL(peaks_merge_kernel<2>, dim3(J + 1, B), dim3(PK_THREADS), 0, s, cand, g.NS, K, pk_score, pk_ind); break;
-        case 4: hipLaunchKernelGGL(peaks_merge_kernel<4>, dim3(J + 1, B), dim3(PK_THREADS), 0, s, cand, g.NS, K, pk_score, pk_ind); break;
-        case 8: hipLaunchKernelGGL(peaks_merge_kernel<8>, dim3(J + 1, B), dim3(PK_THREADS), 0, s, cand, g.NS, K, pk_score, pk_ind); break;
-        default: hipLaunchKernelGGL(peaks_merge_kernel<16>, dim3(J + 1, B), dim3(PK_THREADS), 0, s, cand, g.NS, K, pk_score, pk_ind); break;
-    }
-    AssocParams p;
-    p.hps = hps; p.wh = wh; p.hps_unc = hps_unc; p.scale = scale; p.scale_unc = scale_unc; p.reg = reg;
-    p.hm_hp = hm_hp; p.hp_offset = hp_offset; p.tracking = tracking; p.tracking_hp = tracking_hp;
-    p.pk_score = pk_score; p.pk_ind = pk_ind; p.det = det;
-    p.B = B; p.J = J; p.H = H; p.W = W; p.K = K; p.rep_mode = rep_mode; p.fit_gaussian = fit_gaussian;
-    p.legacy_bool_mask = legacy_bool_mask; p.balance = balance;
-    hipLaunchKernelGGL(assoc_kernel, dim3(J, B), dim3(128), 3 * K * sizeof(float), s, p);
-    return hipGetLastError() == hipSuccess ? CP_OK : CP_ERR_LAUNCH;
+    const int rc = launch_peaks_tiled(s, B, J, H, W, hm, hm_hp, K, apply_sigmoid, pk_score, pk_ind, (char*)ws + tiled_pk_bytes(B, J, K));
+    if (rc != CP_OK) return rc;
+    return cp_launch_decode_assoc(s, B, J, H, W, hps, wh, hps_unc, scale, scale_unc, reg, hm_hp, hp_offset, tracking, tracking_hp,
+                                  pk_score, pk_ind, K, rep_mode, fit_gaussian, balance, legacy_bool_mask, 0, det);
 }

@@ -20,6 +20,44 @@ int g_dbg = 0;
 
 using namespace cp_engine;
 
+// a call that is about to write `ws`: the feature map a lean detect left in it (cp_model::kept) is gone
+static void drop_kept_in(cp_model* m, const void* ws, size_t bytes) {
+    const char* k = (const char*)m->kept.ptr;
+    if (k && k >= (const char*)ws && k < (const char*)ws + bytes) m->kept = cp_model::KeptFeat();
+}
+
+// captured launch sequences of a model, keyed by every argument: replay the graph of `key`, capturing `enqueue` on first use
+template <class F>
+static int replay_or_capture(cp_model* m, hipStream_t s, const std::vector<uint64_t>& key, F&& enqueue) {
+    auto it = m->graphs.find(key);
+    if (it == m->graphs.end()) {
+        if (s == nullptr) return fail(CP_ERR_INVALID, "graph capture needs a non-default stream");
+        if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) != hipSuccess)
+            return fail(CP_ERR_LAUNCH, "hipStreamBeginCapture failed");
+        const int rc = enqueue();
+        hipGraph_t g = nullptr;
+        const hipError_t e = hipStreamEndCapture(s, &g);
+        if (rc != CP_OK || e != hipSuccess || !g) {
+            if (g) (void)hipGraphDestroy(g);
+            return rc != CP_OK ? rc : fail(CP_ERR_LAUNCH, "hipStreamEndCapture failed");
+        }
+        hipGraphExec_t ex = nullptr;
+        if (hipGraphInstantiate(&ex, g, nullptr, nullptr, 0) != hipSuccess) {
+            (void)hipGraphDestroy(g);
+            return fail(CP_ERR_LAUNCH, "hipGraphInstantiate failed");
+        }
+        (void)hipGraphDestroy(g);
+        if (m->graphs.size() >= 16) {  // bound the cache
+            for (auto& kv : m->graphs) (void)hipGraphExecDestroy(kv.second);
+            m->graphs.clear();
+            m->graph_kept.clear();
+        }
+        it = m->graphs.emplace(key, ex).first;
+    }
+    return hipGraphLaunch(it->second, s) == hipSuccess ? CP_OK : fail(CP_ERR_LAUNCH, "hipGraphLaunch failed");
+}
+
+
 // ============================================ C ABI ==============================================
 extern "C" {
 
@@ -138,6 +176,7 @@ int cp_model_forward(cp_model* m, cp_stream_t stream, int B, int H, int W, const
                      void* workspace, size_t workspace_bytes) {
     if (!images || !head_out || !workspace) return fail(CP_ERR_INVALID, "null argument");
     m->tap_name = nullptr;
+    drop_kept_in(m, workspace, workspace_bytes);
     return forward_impl(m, (hipStream_t)stream, B, H, W, images, pre_img, pre_hm, pre_hm_hp, head_out, sigmoid_hm,
                         workspace, workspace_bytes, false);
 }
@@ -156,6 +195,8 @@ size_t cp_model_detect_workspace_bytes(cp_model* m, int B, int H, int W, int K) 
 
 // backbone + heads + sigmoid + decode in one call (what ObjectPoseDetector.process does, object_pose.py:131-165),
 // optionally replayed from a captured hipGraph (the ~120 launches of a frame become one graph launch).
+// Every head is computed on every output pixel here, although the decode reads the regression heads at the peaks only: those dense maps
+// are a by-product.  cp_model_detect_lean below leaves them out (and cp_model_dense_heads computes them on request, at their old cost).
 int cp_model_detect(cp_model* m, cp_stream_t stream, int B, int H, int W, const float* images, const float* pre_img,
                     const float* pre_hm, const float* pre_hm_hp, float* const* head_out, int K, int rep_mode,
                     int fit_gaussian, float balance, int legacy_bool_mask, float* det, void* workspace,
@@ -198,37 +239,132 @@ int cp_model_detect(cp_model* m, cp_stream_t stream, int B, int H, int W, const 
         if (rc != CP_OK) return fail(rc, "detect: decode failed (need K <= 128, K <= H*W/16 <= 2^20, W/4 <= 4096)");
         return rc;
     };
+    drop_kept_in(m, workspace, workspace_bytes);
     if (!use_graph || m->profile) return enqueue();
     std::vector<uint64_t> key = {(uint64_t)B, (uint64_t)H, (uint64_t)W, (uint64_t)images, (uint64_t)pre_img,
                                  (uint64_t)pre_hm, (uint64_t)pre_hm_hp, (uint64_t)K, (uint64_t)rep_mode,
                                  (uint64_t)fit_gaussian, (uint64_t)legacy_bool_mask, (uint64_t)det, (uint64_t)workspace,
                                  (uint64_t)m->precision, (uint64_t)(balance * 1e6f), (uint64_t)s, (uint64_t)(unsigned)g_dbg};
     for (size_t i = 0; i < m->headw.size(); ++i) key.push_back((uint64_t)head_out[i]);
-    auto it = m->graphs.find(key);
-    if (it == m->graphs.end()) {
-        if (s == nullptr) return fail(CP_ERR_INVALID, "graph capture needs a non-default stream");
-        if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) != hipSuccess)
-            return fail(CP_ERR_LAUNCH, "hipStreamBeginCapture failed");
-        const int rc = enqueue();
-        hipGraph_t g = nullptr;
-        const hipError_t e = hipStreamEndCapture(s, &g);
-        if (rc != CP_OK || e != hipSuccess || !g) {
-            if (g) (void)hipGraphDestroy(g);
-            return rc != CP_OK ? rc : fail(CP_ERR_LAUNCH, "hipStreamEndCapture failed");
-        }
-        hipGraphExec_t ex = nullptr;
-        if (hipGraphInstantiate(&ex, g, nullptr, nullptr, 0) != hipSuccess) {
-            (void)hipGraphDestroy(g);
-            return fail(CP_ERR_LAUNCH, "hipGraphInstantiate failed");
-        }
-        (void)hipGraphDestroy(g);
-        if (m->graphs.size() >= 16) {  // bound the cache
-            for (auto& kv : m->graphs) (void)hipGraphExecDestroy(kv.second);
-            m->graphs.clear();
-        }
-        it = m->graphs.emplace(key, ex).first;
+    return replay_or_capture(m, s, key, enqueue);
+}
+
+int cp_model_lean_supported(cp_model* m, int B, int H, int W) {
+    if (!m || !m->finalized) return 0;
+    if (m->gru || m->resnet || m->precision != CP_PREC_F16X3 || !m->hm_group.ok || !m->reg_group.ok) return 0;
+    if (m->lean_key[0] == B && m->lean_key[1] == H && m->lean_key[2] == W && m->lean_key[3] == g_dbg && m->lean_key[4] == m->precision)
+        return m->lean_ok ? 1 : 0;
+    // the forward pass itself decides (a dry run of it, as for the work-space query)
+    cp_model::LeanCall lc;
+    std::memset(&lc, 0, sizeof(lc));
+    lc.K = 1;
+    const char* const tap_before = m->tap_name;
+    m->tap_name = nullptr;
+    m->lean = &lc;
+    m->lean_taken = false;
+    const int rc = forward_impl(m, nullptr, B, H, W, nullptr, nullptr, nullptr, nullptr, nullptr, 1, nullptr, 0, true);
+    m->lean = nullptr;
+    m->tap_name = tap_before;
+    m->lean_key[0] = B; m->lean_key[1] = H; m->lean_key[2] = W; m->lean_key[3] = g_dbg; m->lean_key[4] = m->precision;
+    m->lean_ok = rc == CP_OK && m->lean_taken;
+    return m->lean_ok ? 1 : 0;
+}
+
+// behind the model's arena: the tiled peaks' candidates, then the slabs of the pixel-list launches
+static size_t lean_scratch_bytes(cp_model* m, int B, int H, int W, int K) {
+    const size_t cand = cp_decode_cand_bytes(B, 8, H / 4, W / 4, K);
+    if (cand == (size_t)-1 || K < 1 || K > 128 || (long long)(H / 4) * (W / 4) < K) return 0;
+    // (models whose grouped head launch goes through slabs, the hourglass: room for cp_model_dense_heads' too)
+    const size_t dense = lean_finished_maps(m) ? 0 : lean_slab_bytes(m, (size_t)B * (H / 4) * (W / 4));
+    return align_up(cand, 256) + lean_slab_bytes(m, (size_t)B * 8 * K) + dense + 256;
+}
+
+size_t cp_model_detect_lean_workspace_bytes(cp_model* m, int B, int H, int W, int K) {
+    if (!cp_model_lean_supported(m, B, H, W)) return 0;
+    const size_t a = cp_model_workspace_bytes(m, B, H, W);
+    const size_t d = lean_scratch_bytes(m, B, H, W, K);
+    return a && d ? align_up(a, 256) + d : 0;
+}
+
+int cp_model_detect_lean(cp_model* m, cp_stream_t stream, int B, int H, int W, const float* images, const float* pre_img,
+                         const float* pre_hm, const float* pre_hm_hp, float* const* head_out, float* const* table_out,
+                         float* pk_score, int* pk_ind, int K, int rep_mode, int fit_gaussian, float balance,
+                         int legacy_bool_mask, float* det, void* workspace, size_t workspace_bytes, int use_graph) {
+    if (!m || !images || !head_out || !table_out || !pk_score || !pk_ind || !det || !workspace)
+        return fail(CP_ERR_INVALID, "null argument");
+    if (!m->finalized) return fail(CP_ERR_STATE, "model not finalized");
+    if (!cp_model_lean_supported(m, B, H, W))
+        return fail(CP_ERR_STATE, "lean detect: this model / shape / switch setting runs the dense heads (cp_model_lean_supported)");
+    const size_t model_ws = align_up(cp_model_workspace_bytes(m, B, H, W), 256);
+    const size_t scratch = lean_scratch_bytes(m, B, H, W, K);
+    if (model_ws == 0) return CP_ERR_INVALID;
+    if (scratch == 0) return fail(CP_ERR_INVALID, "detect: unsupported decode shape (need K <= 128, K <= H*W/16 <= 2^20, W/4 <= 4096)");
+    if (workspace_bytes < model_ws + scratch) return fail(CP_ERR_INVALID, "workspace too small");
+    for (size_t i = 0; i < m->headw.size(); ++i) {
+        const bool map = m->headw[i].name == "hm" || m->headw[i].name == "hm_hp";
+        if (map ? !head_out[i] : !table_out[i]) return fail(CP_ERR_INVALID, "lean detect: hm / hm_hp need a map, every other head a table");
     }
-    return hipGraphLaunch(it->second, s) == hipSuccess ? CP_OK : fail(CP_ERR_LAUNCH, "hipGraphLaunch failed");
+    hipStream_t s = (hipStream_t)stream;
+    cp_model::LeanCall lc;
+    lc.table_out = table_out;
+    lc.pk_score = pk_score;
+    lc.pk_ind = pk_ind;
+    lc.scratch = (char*)workspace + model_ws;
+    lc.dense_slabs = lean_finished_maps(m) ? nullptr
+                                           : (float*)((char*)lc.scratch + align_up(cp_decode_cand_bytes(B, 8, H / 4, W / 4, K), 256) +
+                                                      lean_slab_bytes(m, (size_t)B * 8 * K));
+    lc.K = K; lc.rep_mode = rep_mode; lc.fit_gaussian = fit_gaussian; lc.legacy_bool_mask = legacy_bool_mask;
+    lc.balance = balance;
+    lc.det = det;
+    m->kept = cp_model::KeptFeat();
+    auto enqueue = [&]() -> int {
+        m->tap_name = nullptr;
+        m->lean = &lc;
+        const int rc = forward_impl(m, s, B, H, W, images, pre_img, pre_hm, pre_hm_hp, head_out, 1, workspace, model_ws, false);
+        m->lean = nullptr;
+        return rc;
+    };
+    if (!use_graph || m->profile) return enqueue();
+    std::vector<uint64_t> key = {(uint64_t)B, (uint64_t)H, (uint64_t)W, (uint64_t)images, (uint64_t)pre_img,
+                                 (uint64_t)pre_hm, (uint64_t)pre_hm_hp, (uint64_t)K, (uint64_t)rep_mode,
+                                 (uint64_t)fit_gaussian, (uint64_t)legacy_bool_mask, (uint64_t)det, (uint64_t)workspace,
+                                 (uint64_t)m->precision, (uint64_t)(balance * 1e6f), (uint64_t)s, (uint64_t)(unsigned)g_dbg,
+                                 (uint64_t)pk_score, (uint64_t)pk_ind, ~(uint64_t)0 /* lean */};
+    for (size_t i = 0; i < m->headw.size(); ++i) {
+        key.push_back((uint64_t)head_out[i]);
+        key.push_back((uint64_t)table_out[i]);
+    }
+    const int rc = replay_or_capture(m, s, key, enqueue);
+    if (rc != CP_OK) return rc;
+    // a replay runs no host code: where the feature map lives was noted when the graph was captured
+    if (m->kept.ptr) m->graph_kept[key] = m->kept;
+    else {
+        auto it = m->graph_kept.find(key);
+        if (it != m->graph_kept.end()) m->kept = it->second;
+    }
+    return CP_OK;
+}
+
+int cp_model_dense_heads(cp_model* m, cp_stream_t stream, float* const* head_out) {
+    if (!m || !head_out) return fail(CP_ERR_INVALID, "null argument");
+    if (!m->kept.ptr) return fail(CP_ERR_STATE, "dense heads: no feature map kept (the last call on this model was not a lean detect)");
+    for (int i : m->reg_group.idx)
+        if (!head_out[i]) return fail(CP_ERR_INVALID, "dense heads: no output for head " + m->headw[i].name);
+    return kept_dense_heads(m, (hipStream_t)stream, head_out);
+}
+
+size_t cp_model_heads_at_workspace_bytes(cp_model* m, int B, int n) {
+    if (!m || !m->reg_group.ok || B < 1 || n < 1) return 0;
+    return lean_slab_bytes(m, (size_t)B * n) + 256;
+}
+
+int cp_model_heads_at(cp_model* m, cp_stream_t stream, const int* index, int n, float* const* table_out, void* workspace,
+                      size_t workspace_bytes) {
+    if (!m || !index || !table_out || !workspace || n < 1) return fail(CP_ERR_INVALID, "bad argument");
+    if (!m->kept.ptr) return fail(CP_ERR_STATE, "heads at pixels: no feature map kept (the last call on this model was not a lean detect)");
+    if (workspace_bytes < cp_model_heads_at_workspace_bytes(m, m->kept.B, n) || ((uintptr_t)workspace & 15u))
+        return fail(CP_ERR_INVALID, "workspace too small or not 16-byte aligned");
+    return kept_heads_at(m, (hipStream_t)stream, index, n, table_out, (float*)workspace);
 }
 
 int cp_model_forward_tap(cp_model* m, cp_stream_t stream, int B, int H, int W, const float* images,
@@ -236,6 +372,7 @@ int cp_model_forward_tap(cp_model* m, cp_stream_t stream, int B, int H, int W, c
                          int sigmoid_hm, void* workspace, size_t workspace_bytes, const char* tap_name, float* tap_out,
                          int* tap_dims) {
     if (!images || !head_out || !workspace) return fail(CP_ERR_INVALID, "null argument");
+    drop_kept_in(m, workspace, workspace_bytes);
     m->tap_name = tap_name;
     m->tap_out = tap_out;
     m->tap_dims = tap_dims;
@@ -450,6 +587,33 @@ int cp_decode(cp_stream_t stream, int B, int H, int W, float* hm, const float* h
                               legacy_bool_mask, apply_sigmoid, det, workspace);
     if (rc != CP_OK) return fail(rc, "decode: unsupported shape (need K <= 128 <= H*W <= 32768, W % 4 == 0) or launch failure");
     return CP_OK;
+}
+
+size_t cp_decode_peaks_workspace_bytes(int B, int H, int W, int K) {
+    const size_t cand = cp_decode_cand_bytes(B, 8, H, W, K);
+    return cand == (size_t)-1 ? 0 : cand + 256;
+}
+
+int cp_decode_peaks(cp_stream_t stream, int B, int H, int W, float* hm, float* hm_hp, int K, int apply_sigmoid, float* pk_score,
+                    int* pk_ind, void* workspace, size_t workspace_bytes) {
+    if (!hm || !hm_hp || !pk_score || !pk_ind || !workspace) return fail(CP_ERR_INVALID, "null argument");
+    const size_t need = cp_decode_peaks_workspace_bytes(B, H, W, K);
+    if (need == 0) return fail(CP_ERR_INVALID, "unsupported shape (need K <= 128, K <= H*W <= 2^20, W % 4 == 0, W <= 4096)");
+    if (workspace_bytes < need || ((uintptr_t)workspace & 15u)) return fail(CP_ERR_INVALID, "workspace too small or not 16-byte aligned");
+    const int rc = cp_launch_decode_peaks((hipStream_t)stream, B, 8, H, W, hm, hm_hp, K, apply_sigmoid, pk_score, pk_ind, workspace);
+    return rc == CP_OK ? rc : fail(rc, "cp_decode_peaks: launch failed or unsupported shape");
+}
+
+int cp_decode_gathered(cp_stream_t stream, int B, int H, int W, const float* hm_hp, const float* hps, const float* wh,
+                       const float* hps_uncertainty, const float* scale, const float* scale_uncertainty, const float* reg,
+                       const float* hp_offset, const float* tracking, const float* tracking_hp, const float* pk_score,
+                       const int* pk_ind, int K, int rep_mode, int fit_gaussian, float balance, int legacy_bool_mask, float* det) {
+    if (!hm_hp || !hps || !wh || !pk_score || !pk_ind || !det) return fail(CP_ERR_INVALID, "null argument");
+    if (B < 1 || K < 1 || K > 128 || H < 1 || W < 1) return fail(CP_ERR_INVALID, "bad shape");
+    const int rc = cp_launch_decode_assoc((hipStream_t)stream, B, 8, H, W, hps, wh, hps_uncertainty, scale, scale_uncertainty, reg,
+                                          hm_hp, hp_offset, tracking, tracking_hp, pk_score, pk_ind, K, rep_mode, fit_gaussian,
+                                          balance, legacy_bool_mask, 1, det);
+    return rc == CP_OK ? rc : fail(rc, "cp_decode_gathered: launch failed");
 }
 
 size_t cp_decode_tiled_workspace_bytes(int B, int H, int W, int K) { return cp_decode_tiled_ws_bytes(B, 8, H, W, K); }

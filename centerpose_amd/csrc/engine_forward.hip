@@ -15,6 +15,11 @@ namespace {
 // split-K policy: launches with fewer output tiles than kSplitTiles (and >= 8 K steps) are cut into K slices until
 // about kSplitTarget workgroups exist
 constexpr int kSplitTiles = 128, kSplitTarget = 384;  // (384 / 512 measured: B=32 equal, hourglass B=1 latency +7 %)
+// lean detect (heads at the peaks only) from this many output pixels per call: it trades five sevenths of the dense head launch,
+// which shrinks with the batch, for dependent small launches between peaks and association, which do not.  Measured on dla_34 at
+// 512 x 512 (graph replay, p50, lean - dense): B = 1 (16384 pixels) +0.011 ms, B = 2 -0.049, B = 4 -0.146, B = 8 -0.333, B = 16 -0.716
+// (profiles/lean_detect_ab.txt).
+constexpr long kLeanMinPixels = 32768;
 
 // ------------------------------------ forward -------------------------------------------------
 struct Fwd {
@@ -129,11 +134,21 @@ struct Fwd {
         return true;
     }
 
-    // every fused head of the model in one launch + one slice reduction (cp_model::head_group); false = nothing launched
+    // every fused head of the model in one launch + one slice reduction (cp_model::head_group); false = nothing launched.
+    // A lean detect call (cp_model::lean) runs its own head stage here instead.
     bool fused_heads_grouped(const Tensor& x, float* const* head_out, int sigmoid_hm) {
-        const auto& g = m->head_group;
-        const int n = (int)m->headw.size();
-        if (!g.ok || m->precision != CP_PREC_F16X3 || m->tap_name || (g_dbg & (CP_SEL_NO_HEAD_FUSION | CP_SEL_HEADS_PER_HEAD_LAUNCH)) || x.C != g.Cin)
+        if (m->lean) return lean_heads(x, head_out);
+        return grouped_launch(m->head_group, x.ptr(), x.amax, x.C, x.H, x.W, head_out, sigmoid_hm, nullptr);
+    }
+
+    // the heads of group g (a subset of the model's heads, cp_model::HeadGroup::idx) on the feature map `src` in one halo16
+    // launch; head_out is indexed like the model's heads.  The choice of the kernel form looks at the model's whole head set, not
+    // at g: a head's map must not depend on which other heads share its launch.  slab_mem: where the slabs + reduction form keeps
+    // its slabs (nullptr: in the arena).
+    bool grouped_launch(const cp_model::HeadGroup& g, const float* src, unsigned* src_amax, int C, int H, int W,
+                        float* const* head_out, int sigmoid_hm, float* slab_mem) {
+        const int n = (int)g.idx.size(), n_all = (int)m->headw.size();
+        if (!g.ok || m->precision != CP_PREC_F16X3 || m->tap_name || (g_dbg & (CP_SEL_NO_HEAD_FUSION | CP_SEL_HEADS_PER_HEAD_LAUNCH)) || C != g.Cin)
             return false;
         ConvW w;  // the heads' 3x3 layers side by side along N: fragment-ordered f16x3 operands only
         w.KH = w.KW = 3;
@@ -143,9 +158,9 @@ struct Fwd {
         w.shift = g.shift;
         w.w16f_hi = g.w16f_hi;
         w.w16f_lo = g.w16f_lo;
-        const float* src = x.ptr();
-        ConvParams p = conv_params(B, x.H, x.W, &src, &x.C, 1, w, 1, 1, CP_ACT_RELU);
-        conv_params_f16(p, w, &x.amax, true, true);
+        ConvParams p = conv_params(B, H, W, &src, &C, 1, w, 1, 1, CP_ACT_RELU);
+        const unsigned* amax_c = src_amax;
+        conv_params_f16(p, w, &amax_c, true, true);
         p.splitk = 1;
         p.fuse_w2_hi = g.w2_hi;
         p.fuse_w2_lo = g.w2_lo;
@@ -157,24 +172,24 @@ struct Fwd {
         // launch); 2: every head of a patch in one workgroup (one staging for all of them) -- when the patches alone fill the
         // device several times over; below that (small batches, CP_SEL_HEADS_WG_PER_HEAD) one workgroup per patch and head
         p.fuse_final = (g.Cin == 64 && g.hid == 256 && !(g_dbg & CP_SEL_HEADS_SLABS))
-                           ? (((g_dbg & CP_SEL_HEADS_WG_PER_HEAD) || B * (x.H / 8) * (x.W / 16) < 2048) ? 1 : 2) : 0;
+                           ? (((g_dbg & CP_SEL_HEADS_WG_PER_HEAD) || B * (H / 8) * (W / 16) < 2048) ? 1 : 2) : 0;
         if (!cp_halo16_fused_head_supported(p)) return false;
-        if (B * (x.H / 8) * (x.W / 16) * (p.CoutPad / 128) < kSplitTiles) return false;  // small maps: per-head split-K path
+        if (B * (H / 8) * (W / 16) * (n_all * g.hid / 128) < kSplitTiles) return false;  // small maps: per-head split-K path
         HeadReduceGroup rg;
         std::memset(&rg, 0, sizeof(rg));
         rg.n = n;
         rg.slices = p.fuse_gtiles;
         int planes = 0;
         double flops = 0.0, bytes = 0.0;
-        const double M = (double)B * x.H * x.W;
+        const double M = (double)B * H * W;
         for (int i = 0; i < n; ++i) {
-            const HeadW& hw = m->headw[i];
+            const HeadW& hw = m->headw[g.idx[i]];
             p.fuse_gc2[i] = rg.c2[i] = hw.classes;
             p.fuse_gbase[i] = rg.base[i] = planes;
             planes += p.fuse_gtiles * hw.classes;
             rg.sigmoid[i] = sigmoid_hm && (hw.name == "hm" || hw.name == "hm_hp");
             rg.bias[i] = hw.c1.shift;
-            rg.out[i] = m->dry ? nullptr : head_out[i];
+            rg.out[i] = m->dry ? nullptr : head_out[g.idx[i]];
             p.fuse_gsig[i] = rg.sigmoid[i];
             p.fuse_gbias[i] = rg.bias[i];
             p.fuse_gout[i] = rg.out[i];
@@ -183,12 +198,12 @@ struct Fwd {
         }
         bytes += 4.0 * M * g.Cin;  // the shared input is read once
         Tensor slabs;
-        if (!p.fuse_final) slabs = make(planes, x.H, x.W);
+        if (!p.fuse_final && !slab_mem) slabs = make(planes, H, W);
         if (m->dry) return true;
-        p.fuse_out = p.fuse_final ? nullptr : slabs.ptr();
+        p.fuse_out = p.fuse_final ? nullptr : slab_mem ? slab_mem : slabs.ptr();
         auto launch = [&]() -> int {
             int rc = cp_launch_halo16_fused_head(p, s);
-            if (rc == CP_OK && !p.fuse_final) rc = cp_launch_head_reduce_grouped(slabs.ptr(), rg, B, x.H * x.W, s);
+            if (rc == CP_OK && !p.fuse_final) rc = cp_launch_head_reduce_grouped(p.fuse_out, rg, B, H * W, s);
             return rc;
         };
         timed([&](cp_model::ProfRec& r) {
@@ -198,6 +213,124 @@ struct Fwd {
             r.bytes = bytes;
             r.M = (int)M; r.N = p.CoutPad; r.K = 9 * g.Cin; r.kh = 3; r.stride = 1;
         }, launch);
+        return true;
+    }
+
+    // Heads [first, first + count) of cp_model::reg_group evaluated at a list of pixels of the feature map `src` only (per image:
+    // `rpi` entries at index + b * stride) in one launch of the pixel-list kernel + one slice reduction:
+    // table_out[model head] receives [Bout][classes][Kt] with Bout * Kt = B * rpi rows in list order.  slabs: lean_slab_bytes().
+    void heads_at_rows(int first, int count, const float* src, unsigned* src_amax, int C, int H, int W, const int* index,
+                       int stride, int rpi, int Bout, int Kt, float* const* table_out, float* slabs) {
+        const auto& g = m->reg_group;
+        const size_t wbytes = (size_t)g.hid * g.Kpad16 * 2, w2bytes = (size_t)g.hid * 32 * 2;
+        ConvW w;  // the heads' 3x3 layers side by side along N, [co][k] rows
+        w.KH = w.KW = 3;
+        w.K = w.Kpad = w.Kpad16 = g.Kpad16;
+        w.Cin = w.CinP = g.Cin;
+        w.Cout = w.CoutPad = count * g.hid;
+        w.scale16 = g.scale16 + (size_t)first * g.hid;
+        w.shift = g.shift + (size_t)first * g.hid;
+        w.w16_hi = (char*)g.w16_hi + first * wbytes;
+        w.w16_lo = (char*)g.w16_lo + first * wbytes;
+        ConvParams p = conv_params(B, H, W, &src, &C, 1, w, 1, 1, CP_ACT_RELU);
+        const unsigned* amax_c = src_amax;
+        conv_params_f16(p, w, &amax_c, true, true);  // the dense launch's pre-scale: the same operands in the first product
+        p.splitk = 1;
+        p.fuse_w2_hi = (char*)g.w2_hi + first * w2bytes;
+        p.fuse_w2_lo = (char*)g.w2_lo + first * w2bytes;
+        p.fuse_w2_inv = g.w2_inv + (size_t)first * 64;
+        p.fuse_ngroups = count;
+        p.fuse_gtiles = g.hid / 128;
+        p.fuse_out = slabs;
+        p.row_index = index;
+        p.rows_per_image = rpi;
+        p.row_index_stride = stride;
+        HeadReduceGroup rg;
+        std::memset(&rg, 0, sizeof(rg));
+        rg.n = count;
+        rg.slices = p.fuse_gtiles;
+        int planes = 0;
+        const double M = (double)B * rpi;
+        double flops = 0.0, bytes = 4.0 * M * 9.0 * g.Cin;
+        for (int i = 0; i < count; ++i) {
+            const HeadW& hw = m->headw[g.idx[first + i]];
+            p.fuse_gc2[i] = rg.c2[i] = hw.classes;
+            p.fuse_gbase[i] = rg.base[i] = planes;
+            planes += p.fuse_gtiles * hw.classes;
+            rg.bias[i] = hw.c1.shift;
+            rg.out[i] = table_out[g.idx[first + i]];
+            if (!rg.out[i]) {
+                chk(fail(CP_ERR_INVALID, "heads at pixels: no table for head " + hw.name));
+                return;
+            }
+            flops += 2.0 * M * g.hid * (9.0 * g.Cin) + 2.0 * M * hw.classes * (double)g.hid;
+            bytes += 4.0 * (M * hw.classes + 9.0 * g.Cin * g.hid + (double)g.hid * hw.classes);
+        }
+        timed([&](cp_model::ProfRec& r) {
+            r.variant = CP_VARIANT_HEAD_ROWS;
+            r.role = CP_ROLE_HEAD;
+            r.flops = flops;  // what the launch executes: its rows only
+            r.bytes = bytes;
+            r.M = (int)M; r.N = p.CoutPad; r.K = 9 * g.Cin; r.kh = 3; r.stride = 1;
+        }, [&]() -> int {
+            int rc = cp_launch_conv16_fused_head_rows(p, s);
+            if (rc == CP_OK) rc = cp_launch_head_reduce_grouped(slabs, rg, Bout, Kt, s);
+            return rc;
+        });
+    }
+
+    // The head stage of cp_model_detect_lean: hm + hm_hp densely -> peaks -> the other heads at the peaks' pixels only (what the
+    // decode reads of them, decode.hip: assoc_kernel) -> records.  The feature map stays where it is for cp_model_dense_heads.
+    bool lean_heads(const Tensor& x, float* const* head_out) {
+        const cp_model::LeanCall& lc = *m->lean;
+        const auto& gr = m->reg_group;
+        const int J = 8, K = lc.K, nc = m->lean_ncentre, nr = (int)gr.idx.size();
+        if (!gr.ok || !m->hm_group.ok || (long)B * x.H * x.W < kLeanMinPixels || !grouped_launch(m->hm_group, x.ptr(), x.amax, x.C, x.H, x.W, head_out, 1, nullptr)) {
+            chk(fail(CP_ERR_STATE, "lean detect: this model / shape / switch setting runs the dense heads (cp_model_lean_supported)"));
+            return true;
+        }
+        m->lean_taken = true;
+        if (m->dry) return true;
+        m->kept.ptr = x.ptr();
+        m->kept.amax = x.amax;
+        m->kept.B = B; m->kept.H = x.H; m->kept.W = x.W; m->kept.C = x.C;
+        m->kept.slabs = lc.dense_slabs;
+        float *hm = nullptr, *hm_hp = nullptr;
+        const float* tb[11] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        static const char* names[11] = {"hm", "hps", "wh", "hps_uncertainty", "scale", "scale_uncertainty", "reg", "hm_hp",
+                                        "hp_offset", "tracking", "tracking_hp"};
+        for (size_t i = 0; i < m->headw.size(); ++i) {
+            if (m->headw[i].name == "hm") hm = head_out[i];
+            if (m->headw[i].name == "hm_hp") hm_hp = head_out[i];
+            for (int j = 0; j < 11; ++j)
+                if (m->headw[i].name == names[j]) tb[j] = lc.table_out[i];
+        }
+        const size_t cand = cp_decode_cand_bytes(B, J, x.H, x.W, K);
+        if (cand == (size_t)-1 || !tb[1] || !tb[2]) {
+            chk(fail(CP_ERR_INVALID, "lean detect: unsupported decode shape, or no table for hps / wh"));
+            return true;
+        }
+        float* slabs = (float*)((char*)lc.scratch + align_up(cand, 256));
+        const double hw = (double)x.H * x.W;
+        auto decode_rec = [&](cp_model::ProfRec& r, double bytes) {
+            r.variant = -1;
+            r.role = CP_ROLE_DECODE;
+            r.flops = 0.0;
+            r.bytes = bytes;
+            r.M = B; r.N = K; r.K = (int)hw; r.kh = 0; r.stride = 0;
+        };
+        timed([&](cp_model::ProfRec& r) { decode_rec(r, (double)B * 9.0 * hw * 4); },
+              [&]() { return cp_launch_decode_peaks(s, B, J, x.H, x.W, hm, hm_hp, K, 0, lc.pk_score, lc.pk_ind, lc.scratch); });
+        // centre-indexed heads at the K peaks of map 0, hp_offset at the K peaks of each of the J joint maps
+        heads_at_rows(0, nc, x.ptr(), x.amax, x.C, x.H, x.W, lc.pk_ind, (J + 1) * K, K, B, K, lc.table_out, slabs);
+        if (nr > nc)
+            heads_at_rows(nc, 1, x.ptr(), x.amax, x.C, x.H, x.W, lc.pk_ind + K, (J + 1) * K, J * K, B * J, K, lc.table_out, slabs);
+        timed([&](cp_model::ProfRec& r) { decode_rec(r, (double)B * (K * 60.0 * 4 + 8.0 * K * 2 * 4 + (double)K * CP_DET_STRIDE * 4)); },
+              [&]() {
+                  return cp_launch_decode_assoc(s, B, J, x.H, x.W, tb[1], tb[2], tb[3], tb[4], tb[5], tb[6], hm_hp, tb[8], tb[9], tb[10],
+                                                lc.pk_score, lc.pk_ind, K, lc.rep_mode, lc.fit_gaussian, lc.balance,
+                                                lc.legacy_bool_mask, 1, lc.det);
+              });
         return true;
     }
 
@@ -854,5 +987,28 @@ int cp_engine::forward_impl(cp_model* m, hipStream_t stream, int B, int H, int W
     if (!dry && m->arena.overflow)
         return fail(CP_ERR_INVALID, "workspace too small: " + std::to_string(ws_bytes) + " bytes given, this launch sequence peaks at " +
                                         std::to_string(m->arena.peak));
+    return m->status;
+}
+
+// the heads of group g on the feature map the last lean detect kept (cp_model_dense_heads)
+int cp_engine::kept_dense_heads(cp_model* m, hipStream_t stream, float* const* head_out) {
+    const auto& k = m->kept;
+    m->dry = false;
+    m->status = CP_OK;
+    Fwd f{m, k.B, stream};
+    if (!lean_finished_maps(m) && !k.slabs)
+        return fail(CP_ERR_STATE, "dense heads: the lean detect's workspace was sized without room for the slabs this switch setting needs");
+    if (!f.grouped_launch(m->reg_group, k.ptr, k.amax, k.C, k.H, k.W, head_out, 0, k.slabs))
+        return fail(CP_ERR_STATE, "dense heads: the grouped head launch does not apply under the current switches");
+    return m->status;
+}
+
+// every regression head at caller-given pixels of the kept feature map (cp_model_heads_at)
+int cp_engine::kept_heads_at(cp_model* m, hipStream_t stream, const int* index, int n, float* const* table_out, float* slabs) {
+    const auto& k = m->kept;
+    m->dry = false;
+    m->status = CP_OK;
+    Fwd f{m, k.B, stream};
+    f.heads_at_rows(0, (int)m->reg_group.idx.size(), k.ptr, k.amax, k.C, k.H, k.W, index, n, n, k.B, n, table_out, slabs);
     return m->status;
 }

@@ -194,7 +194,36 @@ struct cp_model {
         float* shift = nullptr;
         float* w2_inv = nullptr;
         int Cin = 0, hid = 0, Kpad16 = 0;
+        void* w16_hi = nullptr;  // the 3x3 weights as [co][k] rows as well (pixel-list kernel), reg_group only
+        void* w16_lo = nullptr;
+        std::vector<int> idx;    // the group's heads (indices into headw) in concatenation order
     } head_group;
+    // cp_model_detect_lean: hm + hm_hp (dense), and every other head (first lean_ncentre: read at the centre peaks; then hp_offset)
+    HeadGroup hm_group, reg_group;
+    int lean_ncentre = 0;
+    // one lean detect call: what forward_impl's head stage does instead of the dense launch of every head (engine_forward.hip)
+    struct LeanCall {
+        float* const* table_out;  // per head of the model: its compact table, or nullptr (hm, hm_hp, heads not wanted)
+        float* pk_score;          // [B][J+1][K]
+        int* pk_ind;
+        void* scratch;            // tiled peaks' candidates, then the pixel-list launches' slabs
+        float* dense_slabs;       // where cp_model_dense_heads may keep its slabs (models whose grouped launch needs them), or nullptr
+        int K, rep_mode, fit_gaussian, legacy_bool_mask;
+        float balance;
+        float* det;
+    };
+    const LeanCall* lean = nullptr;
+    bool lean_taken = false;  // set by the head stage when it ran (or, dry, would run) the lean sequence
+    int lean_key[5] = {0, 0, 0, -1, -1};  // (B, H, W, g_dbg, precision) of the cached cp_model_lean_supported answer
+    bool lean_ok = false;
+    // the feature map the heads of the last lean detect read: it stays in the caller's workspace until the next call that uses it
+    struct KeptFeat {
+        const float* ptr = nullptr;
+        unsigned* amax = nullptr;
+        int B = 0, H = 0, W = 0, C = 0;  // (H, W: of the feature map)
+        float* slabs = nullptr;          // LeanCall::dense_slabs of that call
+    } kept;
+    std::map<std::vector<uint64_t>, KeptFeat> graph_kept;  // ... per captured lean graph (a replay does not run the host code)
     std::map<std::string, cp_engine::LowcW> lowc;  // hi / lo weight fragments of the lowc.hip layers
     int ws_key[4] = {0, 0, 0, -1};  // (B, H, W, g_dbg) of the cached work-space query below
     size_t ws_cached = 0;
@@ -248,6 +277,21 @@ namespace cp_engine {
 int forward_impl(cp_model* m, hipStream_t stream, int B, int H, int W, const float* images, const float* pre_img,
                  const float* pre_hm, const float* pre_hm_hp, float* const* head_out, int sigmoid_hm, void* ws,
                  size_t ws_bytes, bool dry);
+
+int kept_dense_heads(cp_model* m, hipStream_t stream, float* const* head_out);
+int kept_heads_at(cp_model* m, hipStream_t stream, const int* index, int n, float* const* table_out, float* slabs);
+
+// slab bytes of a pixel-list launch of every head of cp_model::reg_group over `rows` rows (two hidden slices per head)
+inline size_t lean_slab_bytes(const cp_model* m, size_t rows) {
+    size_t planes = 0;
+    for (int i : m->reg_group.idx) planes += (size_t)(m->reg_group.hid / 128) * m->headw[i].classes;
+    return align_up(planes * rows * sizeof(float), 256);
+}
+
+// does the grouped head launch write finished maps (halo16: fuse_final), or slabs + a reduction launch?
+inline bool lean_finished_maps(const cp_model* m) {
+    return m->head_group.Cin == 64 && m->head_group.hid == 256 && !(g_dbg & CP_SEL_HEADS_SLABS);
+}
 
 // The one profiling bracket: runs `launch` (-> CP_* code).  While the model is profiling, `describe` fills in what the launch
 // is charged for (variant, role, flops, bytes, shape) and two events on `s` around it time it for cp_model_profile_read.

@@ -340,41 +340,73 @@ struct Packer {
         m->deconvs[up] = d;
     }
 
-    // concatenate the fused heads' operands for the grouped launch (all heads must be fusable and of one shape)
-    void group_heads() {
-        auto& g = m->head_group;
-        const size_t n = m->headw.size();
+    // concatenate the fused heads' operands for a grouped launch (all heads must be fusable and of one shape): the heads `idx` of
+    // m->headw in that order.  `rows`: also the [co][k] copies of the 3x3 weights, which the pixel-list kernel reads.
+    void group_heads(cp_model::HeadGroup& g, const std::vector<int>& idx, bool rows) {
+        const size_t n = idx.size();
         if (n < 2 || n > CP_MAX_HEAD_GROUP || status != CP_OK) return;
-        const ConvW& c = m->headw[0].c0;
-        for (const HeadW& h : m->headw)
+        const ConvW& c = m->headw[idx[0]].c0;
+        for (int i : idx) {
+            const HeadW& h = m->headw[i];
             if (!h.w2_hi || !h.w2_lo || !h.w2_inv || !h.c0.w16f_hi || !h.c0.w16f_lo || !h.c0.scale16 || !h.c0.shift ||
                 h.c0.Cin != c.Cin || h.c0.CoutPad != c.CoutPad || h.c0.Cout != c.CoutPad || h.c0.Kpad16 != c.Kpad16 ||
-                h.c0.KH != 3 || h.c0.KW != 3 || c.CoutPad % 128 != 0)
+                h.c0.KH != 3 || h.c0.KW != 3 || c.CoutPad % 128 != 0 || (rows && (!h.c0.w16_hi || !h.c0.w16_lo)))
                 return;
+        }
         const size_t wbytes = (size_t)c.CoutPad * c.Kpad16 * 2, w2bytes = (size_t)c.CoutPad * 32 * 2;
         g.w16f_hi = dev_alloc(n * wbytes / 4, false);
         g.w16f_lo = dev_alloc(n * wbytes / 4, false);
+        if (rows) {
+            g.w16_hi = dev_alloc(n * wbytes / 4, false);
+            g.w16_lo = dev_alloc(n * wbytes / 4, false);
+        }
         g.w2_hi = dev_alloc(n * w2bytes / 4, false);
         g.w2_lo = dev_alloc(n * w2bytes / 4, false);
         g.scale16 = dev_alloc(n * c.CoutPad, false);
         g.shift = dev_alloc(n * c.CoutPad, false);
         g.w2_inv = dev_alloc(n * 64, false);
-        if (!g.w16f_hi || !g.w16f_lo || !g.w2_hi || !g.w2_lo || !g.scale16 || !g.shift || !g.w2_inv) return;
+        if (!g.w16f_hi || !g.w16f_lo || !g.w2_hi || !g.w2_lo || !g.scale16 || !g.shift || !g.w2_inv || (rows && (!g.w16_hi || !g.w16_lo)))
+            return;
         for (size_t i = 0; i < n; ++i) {
-            const HeadW& h = m->headw[i];
+            const HeadW& h = m->headw[idx[i]];
             const auto d2d = hipMemcpyDeviceToDevice;
             hip_ok(hipMemcpy((char*)g.w16f_hi + i * wbytes, h.c0.w16f_hi, wbytes, d2d));
             hip_ok(hipMemcpy((char*)g.w16f_lo + i * wbytes, h.c0.w16f_lo, wbytes, d2d));
+            if (rows) {
+                hip_ok(hipMemcpy((char*)g.w16_hi + i * wbytes, h.c0.w16_hi, wbytes, d2d));
+                hip_ok(hipMemcpy((char*)g.w16_lo + i * wbytes, h.c0.w16_lo, wbytes, d2d));
+            }
             hip_ok(hipMemcpy((char*)g.w2_hi + i * w2bytes, h.w2_hi, w2bytes, d2d));
             hip_ok(hipMemcpy((char*)g.w2_lo + i * w2bytes, h.w2_lo, w2bytes, d2d));
             hip_ok(hipMemcpy(g.scale16 + i * c.CoutPad, h.c0.scale16, (size_t)c.CoutPad * 4, d2d));
             hip_ok(hipMemcpy(g.shift + i * c.CoutPad, h.c0.shift, (size_t)c.CoutPad * 4, d2d));
             hip_ok(hipMemcpy(g.w2_inv + i * 64, h.w2_inv, 64 * 4, d2d));
         }
+        g.idx = idx;
         g.Cin = c.Cin;
         g.hid = c.CoutPad;
         g.Kpad16 = c.Kpad16;
         g.ok = status == CP_OK;
+    }
+    // head_group: every head (cp_model_forward, cp_model_detect).  For cp_model_detect_lean the heads in two groups: the heat-maps
+    // the decode reads everywhere (hm, hm_hp), and the regression heads it reads at the peaks only -- the centre-indexed ones first,
+    // hp_offset (read at the joint peaks) last.
+    void group_heads() {
+        std::vector<int> all, maps, reg;
+        int hp_off = -1;
+        for (int i = 0; i < (int)m->headw.size(); ++i) {
+            const std::string& n = m->headw[i].name;
+            all.push_back(i);
+            if (n == "hm" || n == "hm_hp") maps.push_back(i);
+            else if (n == "hp_offset") hp_off = i;
+            else reg.push_back(i);
+        }
+        group_heads(m->head_group, all, false);
+        if (!m->head_group.ok || maps.size() != 2 || reg.size() < 2) return;
+        m->lean_ncentre = (int)reg.size();
+        if (hp_off >= 0) reg.push_back(hp_off);
+        group_heads(m->hm_group, maps, false);
+        group_heads(m->reg_group, reg, true);
     }
 
     // weight fragments for the direct low-channel kernels (f16x3 mode); the folded BatchNorm comes from the ConvW

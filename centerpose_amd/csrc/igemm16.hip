@@ -51,10 +51,13 @@ namespace {
 // GRU (128x96 tiles: MT 1, NT 3, 4x1 waves): fused ConvGRU gate epilogue, see ConvParams::gru_x3.  Fragment j of a
 // wave's accumulators is gate j (r, z, n) of the same 32 channels, so a lane holds all three pre-activations of its
 // (pixel, channel) pairs and the gate arithmetic needs no exchange.
-template <int MT, int NT, int WM, int WN, bool MULTISRC, bool FUSE = false, bool GNIN = false, bool GRU = false>
+// ROWS (FUSE only): the tile's rows are the pixels of a list (ConvParams::row_index) instead of consecutive pixels of the map --
+// the regression heads evaluated at the decoded peaks only.  Only the prologue's row -> pixel step and the slab address differ.
+template <int MT, int NT, int WM, int WN, bool MULTISRC, bool FUSE = false, bool GNIN = false, bool GRU = false, bool ROWS = false>
 __global__ __launch_bounds__(WM * WN * 64, 2) void igemm16p_kernel(const ConvParams p, const int tiles_m, const int tiles_n) {
     static_assert(!FUSE || (MT == 2 && NT == 2 && WM == 2 && WN == 2 && !MULTISRC), "fused head: 128x128 tiles");
     static_assert(!GRU || (MT == 1 && NT == 3 && WM == 4 && WN == 1 && !MULTISRC && !FUSE), "GRU: 128x96 tiles");
+    static_assert(!ROWS || FUSE, "pixel lists: fused heads only");
     typedef Frag<32> F;
     typedef F::acc_t acc_t;
     constexpr int BM = 32 * MT * WM, BN = 32 * NT * WN;
@@ -79,7 +82,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void igemm16p_kernel(const ConvPar
     const int wm = wid / WN, wn = wid % WN;
     const int tile = tile_of_block(tiles_m, tiles_n);
     const int tn = tile % tiles_n, tm = tile / tiles_n;
-    const int M = p.B * p.Ho * p.Wo;
+    const int M = ROWS ? p.B * p.rows_per_image : p.B * p.Ho * p.Wo;
     PixelDecomp pdec;
     pdec.init(p.Ho, p.Wo, M);
 
@@ -92,7 +95,12 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void igemm16p_kernel(const ConvPar
         const bool ok = m < M;
         const int mm = ok ? m : 0;
         int b, ho, wo;
-        pdec.split(mm, &b, &ho, &wo);
+        if constexpr (ROWS) {
+            b = mm / p.rows_per_image;
+            const int ind = min(max(p.row_index[(size_t)b * p.row_index_stride + (mm - b * p.rows_per_image)], 0), p.Ho * p.Wo - 1);
+            ho = ind / p.Wo;
+            wo = ind - ho * p.Wo;
+        } else pdec.split(mm, &b, &ho, &wo);
         const int h0 = ho * p.stride - p.pad, w0 = wo * p.stride - p.pad;
         a_pix0[j] = (b * p.H + h0) * p.W + w0;
         a_byte0[j] = (unsigned)(a_pix0[j] * p.src_c[0] + k4 * 4) * 4u;
@@ -409,9 +417,13 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void igemm16p_kernel(const ConvPar
         __syncthreads();  // every wave is done with the tile buffers
         float* red = reinterpret_cast<float*>(lds);  // [wm][i][r][lane]
         // back to true units: 2^-e of this wave's hidden pre-scale and of the 1x1 weights' per-channel scale
+        // (ROWS, several heads side by side along N: this tile's head, its final channels and its first slab plane)
+        const int gh = ROWS && p.fuse_ngroups > 0 ? tn / p.fuse_gtiles : 0;
+        const int c2 = ROWS && p.fuse_ngroups > 0 ? p.fuse_gc2[gh] : p.fuse_c2;
+        const int plane0 = ROWS && p.fuse_ngroups > 0 ? p.fuse_gbase[gh] + (tn - gh * p.fuse_gtiles) * c2 : tn * c2;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const float wi = (p.fuse_w2_inv ? p.fuse_w2_inv[F::row(r, lane)] : 1.f) * hinv;
+            const float wi = (p.fuse_w2_inv ? p.fuse_w2_inv[gh * 64 + F::row(r, lane)] : 1.f) * hinv;
             acc2[0][r] *= wi;
             acc2[1][r] *= wi;
         }
@@ -430,7 +442,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void igemm16p_kernel(const ConvPar
                 for (int r = 0; r < 16; ++r) {
                     const int c = F::row(r, lane);
                     const float v = acc2[i][r] + red[((wm * 2 + i) * 16 + r) * 64 + lane];
-                    if (c < p.fuse_c2 && m < M) p.fuse_out[((size_t)tn * p.fuse_c2 + c) * M + m] = v;
+                    if (c < c2 && m < M) p.fuse_out[((size_t)plane0 + c) * M + m] = v;
                 }
             }
         }
@@ -771,6 +783,25 @@ int cp_launch_conv16_fused_head(const ConvParams& p, hipStream_t stream) {
     const int tiles_m = (M + 127) / 128, tiles_n = p.CoutPad / 128;
     hipLaunchKernelGGL((igemm16p_kernel<2, 2, 2, 2, false, true>), dim3(tiles_m * tiles_n), dim3(NT16), 0, stream, p,
                        tiles_m, tiles_n);
+    return hipGetLastError() == hipSuccess ? CP_OK : CP_ERR_LAUNCH;
+}
+
+int cp_launch_conv16_fused_head_rows(const ConvParams& p, hipStream_t stream) {
+    const int c2 = p.fuse_ngroups > 0 ? 1 : p.fuse_c2;  // (grouped: the per-head widths are checked below)
+    if (!cp_head_fuse_supported(p, c2) || !p.fuse_w2_hi || !p.fuse_w2_lo || !p.fuse_out || p.splitk > 1 || !p.row_index ||
+        p.rows_per_image < 1 || p.row_index_stride < p.rows_per_image || p.KH != 3 || p.KW != 3 || p.stride != 1 || p.pad != 1 ||
+        p.fuse_ngroups < 0 || p.fuse_ngroups > CP_MAX_HEAD_GROUP)
+        return CP_ERR_INVALID;
+    if (p.fuse_ngroups > 0) {
+        if (p.fuse_gtiles < 1 || p.fuse_ngroups * p.fuse_gtiles * 128 != p.CoutPad) return CP_ERR_INVALID;
+        for (int g = 0; g < p.fuse_ngroups; ++g)
+            if (p.fuse_gc2[g] < 1 || p.fuse_gc2[g] > 32 || p.fuse_gbase[g] < 0) return CP_ERR_INVALID;
+    }
+    const long long M = (long long)p.B * p.rows_per_image;
+    if (M >= (1ll << 24)) return CP_ERR_INVALID;
+    const int tiles_m = (int)((M + 127) / 128), tiles_n = p.CoutPad / 128;
+    hipLaunchKernelGGL((igemm16p_kernel<2, 2, 2, 2, false, true, false, false, true>), dim3(tiles_m * tiles_n), dim3(NT16), 0,
+                       stream, p, tiles_m, tiles_n);
     return hipGetLastError() == hipSuccess ? CP_OK : CP_ERR_LAUNCH;
 }
 

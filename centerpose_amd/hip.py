@@ -9,6 +9,7 @@ import ctypes
 import enum
 import os
 from collections import OrderedDict
+from collections.abc import Mapping
 
 import torch
 
@@ -128,6 +129,19 @@ def lib():
     _sig(L.cp_model_detect_workspace_bytes, c_size_t, c_void_p, c_int, c_int, c_int, c_int)
     _sig(L.cp_model_detect, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
          ctypes.POINTER(c_void_p), c_int, c_int, c_int, ctypes.c_float, c_int, c_void_p, c_void_p, c_size_t, c_int)
+    _sig(L.cp_model_lean_supported, c_int, c_void_p, c_int, c_int, c_int)
+    _sig(L.cp_model_detect_lean_workspace_bytes, c_size_t, c_void_p, c_int, c_int, c_int, c_int)
+    _sig(L.cp_model_detect_lean, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+         ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_float, c_int,
+         c_void_p, c_void_p, c_size_t, c_int)
+    _sig(L.cp_model_dense_heads, c_int, c_void_p, c_void_p, ctypes.POINTER(c_void_p))
+    _sig(L.cp_model_heads_at_workspace_bytes, c_size_t, c_void_p, c_int, c_int)
+    _sig(L.cp_model_heads_at, c_int, c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(c_void_p), c_void_p, c_size_t)
+    _sig(L.cp_decode_peaks_workspace_bytes, c_size_t, c_int, c_int, c_int, c_int)
+    _sig(L.cp_decode_peaks, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+         c_void_p, c_size_t)
+    _sig(L.cp_decode_gathered, c_int, c_void_p, c_int, c_int, c_int, *([c_void_p] * 12), c_int, c_int, c_int, ctypes.c_float,
+         c_int, c_void_p)
     _sig(L.cp_set_default_precision, c_int, c_int)
     _sig(L.cp_set_debug, c_int, c_int)
     _sig(L.cp_render_gaussians, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int)
@@ -197,7 +211,10 @@ def exported_symbols():
             "cp_decode_tiled", "cp_box_iou", "cp_box_eval", "cp_conv_transpose2d_workspace_bytes",
             "cp_conv_transpose2d_nhwc", "cp_dcnv2_backward_workspace_bytes", "cp_dcnv2_backward",
             "cp_pose_loss_workspace_bytes", "cp_pose_loss_forward", "cp_pose_loss_backward",
-            "cp_pose_targets_workspace_bytes", "cp_pose_targets"]
+            "cp_pose_targets_workspace_bytes", "cp_pose_targets", "cp_model_lean_supported",
+            "cp_model_detect_lean_workspace_bytes", "cp_model_detect_lean", "cp_model_dense_heads",
+            "cp_model_heads_at_workspace_bytes", "cp_model_heads_at", "cp_decode_peaks_workspace_bytes", "cp_decode_peaks",
+            "cp_decode_gathered"]
 
 
 def _check(rc, what):
@@ -938,6 +955,101 @@ def track_record_to_dict(r, opt=None):
     return d
 
 
+# heads the decode reads at the peaks only (every head but the two heat-maps); hp_offset at the joint peaks, the rest at the centres
+_MAP_HEADS = ("hm", "hm_hp")
+
+
+def decode_peaks(hm, hm_hp, K=100, apply_sigmoid=False):
+    """The first half of the decode (cp_decode_peaks): NMS + top-K of hm [B,1,H,W] and hm_hp [B,8,H,W] ->
+    (pk_score float32 [B,9,K], pk_ind int32 [B,9,K]); index = y * W + x, map 0 = hm, 1..8 = hm_hp.  Any grid decode_raw or
+    decode_raw_tiled accepts."""
+    L = lib()
+    hm, hm_hp = _dev(hm), _dev(hm_hp)
+    B, _, H, W = hm.shape
+    n = L.cp_decode_peaks_workspace_bytes(B, H, W, int(K))
+    if n == 0:
+        raise RuntimeError("cp_decode_peaks: unsupported shape")
+    ws = torch.empty(n, dtype=torch.uint8, device=hm.device)
+    pk_score = torch.empty(B, 9, K, device=hm.device, dtype=torch.float32)
+    pk_ind = torch.empty(B, 9, K, device=hm.device, dtype=torch.int32)
+    _check(L.cp_decode_peaks(_stream(), B, H, W, _ptr(hm), _ptr(hm_hp), int(K), int(bool(apply_sigmoid)), _ptr(pk_score),
+                             _ptr(pk_ind), _ptr(ws), ws.numel()), "cp_decode_peaks")
+    return pk_score, pk_ind
+
+
+def decode_gathered(hm_hp, pk_score, pk_ind, hps, wh, hps_uncertainty=None, scale=None, scale_uncertainty=None, reg=None,
+                    hp_offset=None, tracking=None, tracking_hp=None, rep_mode=1, fit_gaussian=False, balance=2.0,
+                    legacy_bool_mask=False):
+    """The second half of the decode on COMPACT tables (cp_decode_gathered): each regression head holds its values at the
+    peaks only -- [B,C,K] at the centre peaks pk_ind[:, 0], hp_offset [B,8,2,K] at the joint peaks pk_ind[:, 1:] -- and
+    hm_hp is the dense (sigmoided) map.  -> det [B,K,118], bit-identical to decode_raw on maps holding the same values."""
+    L = lib()
+    hm_hp = _dev(hm_hp)
+    B, _, H, W = hm_hp.shape
+    K = pk_ind.shape[2]
+    opt = [None if t is None else _dev(t) for t in (hps, wh, hps_uncertainty, scale, scale_uncertainty, reg, hp_offset,
+                                                     tracking, tracking_hp)]
+    want = (16, 2, 16, 3, 3, 2, None, 2, 16)
+    for t, c in zip(opt, want):
+        if t is not None and tuple(t.shape) != ((B, 8, 2, K) if c is None else (B, c, K)):
+            raise ValueError("decode_gathered: a table has shape %s" % (tuple(t.shape),))
+    det = torch.empty(B, K, DET_STRIDE, device=hm_hp.device, dtype=torch.float32)
+    pk_score, pk_ind = pk_score.contiguous(), pk_ind.contiguous()
+    if pk_score.dtype != torch.float32 or pk_ind.dtype != torch.int32:
+        raise ValueError("decode_gathered: pk_score float32 and pk_ind int32 expected")
+    _check(L.cp_decode_gathered(_stream(), B, H, W, _ptr(hm_hp), *[_ptr(t) for t in opt], _ptr(pk_score), _ptr(pk_ind),
+                                int(K), int(rep_mode), int(bool(fit_gaussian)), float(balance), int(bool(legacy_bool_mask)),
+                                _ptr(det)), "cp_decode_gathered")
+    return det
+
+
+class LazyHeads(Mapping):
+    """What ``HipModel.detect(heads="lazy")`` returns for the heads on a model that takes the lean path: a read-only mapping
+    with the model's head names in order.  ``hm`` / ``hm_hp`` are there at once.  Any other key -- also through ``items()`` /
+    ``values()`` -- is the dense map the decode never needed: it is computed on first access from the feature map the detect
+    call left behind (cp_model_dense_heads, on the current stream, all remaining heads in one launch) and cached.  After the
+    next ``detect`` on the model that feature map is gone and such an access raises.
+    ``gathered``: head -> compact table of the lean path ([B,C,K] at the centre peaks, hp_offset [B,8,2,K] at the joint
+    peaks); ``pk_score`` / ``pk_ind``: the peaks [B,9,K]."""
+
+    def __init__(self, model, gen, shapes, ready, gathered, pk_score, pk_ind):
+        self._model, self._gen, self._shapes = model, gen, shapes
+        self._ready = dict(ready)
+        self.gathered, self.pk_score, self.pk_ind = gathered, pk_score, pk_ind
+
+    def __iter__(self):
+        return iter(self._shapes)
+
+    def __len__(self):
+        return len(self._shapes)
+
+    def __contains__(self, k):   # (Mapping's own asks __getitem__, which would compute the maps)
+        return k in self._shapes
+
+    def __getitem__(self, k):
+        if k not in self._shapes:
+            raise KeyError(k)
+        if k not in self._ready:
+            self._materialise()
+        return self._ready[k]
+
+    def materialised(self):
+        return len(self._ready) == len(self._shapes)
+
+    def _materialise(self):
+        m = self._model
+        if m._det_gen != self._gen:
+            raise RuntimeError("detect: the dense '%s' maps of this call were not read before the next detect() on the model, and "
+                               "the feature map they are computed from is gone; read them earlier or call detect(heads=\"dense\")"
+                               % "', '".join(k for k in self._shapes if k not in self._ready))
+        dev = self.pk_ind.device
+        new = OrderedDict((k, torch.empty(*shp, device=dev, dtype=torch.float32)) for k, shp in self._shapes.items()
+                          if k not in self._ready)
+        ptrs = (c_void_p * len(self._shapes))(*[new[k].data_ptr() if k in new else 0 for k in self._shapes])
+        _check(lib().cp_model_dense_heads(m._h, _stream(), ptrs), "cp_model_dense_heads")
+        self._ready.update(new)
+
+
 class HipModel(object):
     """Device-resident DLA-34 / DLA-34+ConvGRU / hourglass / resdcn_N network built from a reference-format state dict."""
 
@@ -1051,14 +1163,80 @@ class HipModel(object):
             raise RuntimeError("unknown tap %r" % tap)
         return outs, tap_buf[: B * C * h * w].view(B, C, h, w)
 
-    def detect(self, images, pre_img=None, pre_hm=None, pre_hm_hp=None, K=100, rep_mode=1, fit_gaussian=False,
-               balance=2.0, legacy_bool_mask=False, graph=True):
-        """backbone + heads + sigmoid + decode in one library call -> (heads dict, det [B,K,118]).
-        Output tensors are owned by the model and REUSED by the next call with the same batch shape (that is what lets
-        the launch sequence be replayed from a hipGraph).  With ``graph`` the caller must run on a non-default stream
-        and pass the same input tensors (copy new frames into them)."""
+    def lean_supported(self, B, H, W):
+        """Does detect(heads="lazy") take the lean path for this shape (cp_model_lean_supported)?"""
+        return bool(lib().cp_model_lean_supported(self._h, int(B), int(H), int(W)))
+
+    def heads_at(self, index):
+        """The regression heads (every head but hm / hm_hp) at the pixels ``index`` [B,n] (int32, y * (W/4) + x) of the feature
+        map the last lean detect() left behind -> OrderedDict head -> [B,classes,n] (cp_model_heads_at)."""
+        L = lib()
+        index = index.to(torch.int32).contiguous()
+        B, n = index.shape
+        out = OrderedDict((k, torch.empty(B, c, n, device=index.device, dtype=torch.float32)) for k, c in self.heads.items()
+                          if k not in _MAP_HEADS)
+        ptrs = (c_void_p * len(self.heads))(*[out[k].data_ptr() if k in out else 0 for k in self.heads])
+        nb = L.cp_model_heads_at_workspace_bytes(self._h, B, n)
+        ws = torch.empty(max(nb, 256), dtype=torch.uint8, device=index.device)
+        _check(L.cp_model_heads_at(self._h, _stream(), _ptr(index), n, ptrs, _ptr(ws), ws.numel()), "cp_model_heads_at")
+        return out
+
+    def _detect_lean(self, images, pre_img, pre_hm, pre_hm_hp, K, rep_mode, fit_gaussian, balance, legacy_bool_mask, graph):
         L = lib()
         B, _, H, W = images.shape
+        dev = images.device
+        key = ("lean", B, H, W, str(dev), K)
+        st = getattr(self, "_lean_state", None)
+        if st is None or st[0] != key:
+            f32 = dict(device=dev, dtype=torch.float32)
+            maps = OrderedDict((k, torch.empty(B, self.heads[k], H // 4, W // 4, **f32)) for k in _MAP_HEADS)
+            tables = OrderedDict((k, torch.empty(*((B, 8, 2, K) if k == "hp_offset" else (B, c, K)), **f32))
+                                 for k, c in self.heads.items() if k not in _MAP_HEADS)
+            pk_score = torch.empty(B, 9, K, **f32)
+            pk_ind = torch.empty(B, 9, K, device=dev, dtype=torch.int32)
+            det = torch.empty(B, K, DET_STRIDE, **f32)
+            n = L.cp_model_detect_lean_workspace_bytes(self._h, B, H, W, K)
+            if n == 0:
+                raise RuntimeError("cp_model_detect_lean_workspace_bytes failed: " + L.cp_last_error().decode())
+            ws = torch.empty(n, dtype=torch.uint8, device=dev)
+            hp = (c_void_p * len(self.heads))(*[maps[k].data_ptr() if k in maps else 0 for k in self.heads])
+            tp = (c_void_p * len(self.heads))(*[tables[k].data_ptr() if k in tables else 0 for k in self.heads])
+            shapes = OrderedDict((k, (B, c, H // 4, W // 4)) for k, c in self.heads.items())
+            st = (key, maps, tables, pk_score, pk_ind, det, ws, hp, tp, shapes)
+            self._lean_state = st
+        _, maps, tables, pk_score, pk_ind, det, ws, hp, tp, shapes = st
+        rc = L.cp_model_detect_lean(self._h, _stream(), B, H, W, _ptr(images), _ptr(pre_img), _ptr(pre_hm), _ptr(pre_hm_hp),
+                                    hp, tp, _ptr(pk_score), _ptr(pk_ind), int(K), int(rep_mode), int(bool(fit_gaussian)),
+                                    float(balance), int(bool(legacy_bool_mask)), _ptr(det), _ptr(ws), ws.numel(),
+                                    int(bool(graph)))
+        _check(rc, "cp_model_detect_lean")
+        return LazyHeads(self, self._det_gen, shapes, maps, tables, pk_score, pk_ind), det
+
+    def detect(self, images, pre_img=None, pre_hm=None, pre_hm_hp=None, K=100, rep_mode=1, fit_gaussian=False,
+               balance=2.0, legacy_bool_mask=False, graph=True, heads="lazy"):
+        """backbone + heads + sigmoid + decode in one library call -> (heads mapping, det [B,K,118]).
+        Output tensors are owned by the model and REUSED by the next call with the same batch shape (that is what lets
+        the launch sequence be replayed from a hipGraph).  With ``graph`` the caller must run on a non-default stream
+        and pass the same input tensors (copy new frames into them).
+
+        The decode reads hm and hm_hp on every pixel, but the regression heads only at the decoded peaks: their dense maps
+        are a by-product it never needed.  ``heads="lazy"`` (default), on a model that supports it (f16x3, grouped fused
+        heads: dla_34, hourglass -- ``lean_supported``), runs cp_model_detect_lean, which evaluates those heads at the peaks
+        only; the first return value is then a ``LazyHeads`` mapping (same keys, same order) whose regression maps are
+        computed on first access, at their old cost, and only until the next ``detect`` on the model (afterwards such an
+        access raises).  On any other model ``"lazy"`` is today's call and returns the plain OrderedDict.
+        ``heads="dense"``: cp_model_detect, every map computed up front."""
+        if heads not in ("lazy", "dense"):
+            raise ValueError("detect: heads must be 'lazy' or 'dense'")
+        L = lib()
+        B, _, H, W = images.shape
+        for t in (images, pre_img, pre_hm, pre_hm_hp):
+            if t is not None and not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32):
+                raise RuntimeError("detect: inputs must be contiguous float32 device tensors")
+        self._det_gen = getattr(self, "_det_gen", 0) + 1   # (what a LazyHeads of an earlier call checks)
+        if heads == "lazy" and L.cp_model_lean_supported(self._h, B, H, W):
+            return self._detect_lean(images, pre_img, pre_hm, pre_hm_hp, K, rep_mode, fit_gaussian, balance, legacy_bool_mask,
+                                     graph)
         key = ("det", B, H, W, str(images.device), K)
         st = getattr(self, "_det_state", None)
         if st is None or st[0] != key:

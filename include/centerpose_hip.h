@@ -42,7 +42,9 @@ typedef struct cp_model cp_model;
  * 6 = cp_preprocess_batch, cp_linear_assignment, CP_NUM_KERNEL_VARIANTS 43, cp_set_debug moved out of this header (centerpose_hip_testing.h);
  * 7 = cp_decode_tiled / cp_decode_tiled_workspace_bytes, cp_model_detect decodes output grids above 32768 pixels;
  *     later additions without a version change: cp_box_iou, cp_box_eval, cp_pose_loss_workspace_bytes,
- *     cp_pose_loss_forward, cp_pose_loss_backward, cp_pose_targets_workspace_bytes, cp_pose_targets. */
+ *     cp_pose_loss_forward, cp_pose_loss_backward, cp_pose_targets_workspace_bytes, cp_pose_targets,
+ *     cp_model_lean_supported, cp_model_detect_lean(_workspace_bytes), cp_model_dense_heads, cp_model_heads_at(_workspace_bytes),
+ *     cp_decode_peaks(_workspace_bytes), cp_decode_gathered; CP_NUM_KERNEL_VARIANTS 46. */
 #define CP_ABI_VERSION 7
 const char* cp_version(void);
 int cp_abi_version(void);
@@ -140,12 +142,46 @@ int cp_model_forward(cp_model* m, cp_stream_t stream, int B, int H, int W, const
  * by every pointer / size argument, so buffers must be reused) and replayed afterwards: a frame costs one graph
  * launch instead of ~120 kernel launches.  Needs a non-default stream; ignored while profiling is armed.
  * Output grids (H/4) x (W/4) above 32768 pixels are decoded by cp_decode_tiled's kernels (its size limits apply, and
- * the workspace grows with the grid); up to 32768 pixels the launches and workspace are cp_decode's. */
+ * the workspace grows with the grid); up to 32768 pixels the launches and workspace are cp_decode's.
+ * Every head is computed on every output pixel, although the decode reads only hm and hm_hp everywhere and the regression
+ * heads at the decoded peaks: the dense regression maps are a by-product.  A caller that wants the records asks
+ * cp_model_detect_lean below and gets the maps on request (cp_model_dense_heads) at their old cost. */
 size_t cp_model_detect_workspace_bytes(cp_model* m, int B, int H, int W, int K);
 int cp_model_detect(cp_model* m, cp_stream_t stream, int B, int H, int W, const float* images, const float* pre_img,
                     const float* pre_hm, const float* pre_hm_hp, float* const* head_out, int K, int rep_mode,
                     int fit_gaussian, float balance, int legacy_bool_mask, float* det, void* workspace,
                     size_t workspace_bytes, int use_graph);
+
+/* cp_model_detect without the dense regression maps.  Sequence, on one stream: backbone -> hm and hm_hp densely (sigmoided) ->
+ * peaks (NMS + top-K of the 1 + 8 maps) -> every other head evaluated ONLY at the pixels the decode reads it at (hp_offset at
+ * the K peaks of each joint map, the rest at the K centre peaks: the fused 3x3 + ReLU + 1x1 head as an implicit GEMM over a
+ * pixel list, same operands and pre-scale as the dense launch) -> records.  Per image 4 heads at K pixels and one at 8 K instead
+ * of 5 heads at (H/4)(W/4).
+ *   cp_model_lean_supported  1 when the model, shape, precision and switch setting take this path: f16x3, no ConvGRU, the
+ *                            grouped fused-head form (dla_34, hourglass).  Otherwise 0, and the entries below return
+ *                            CP_ERR_STATE / 0 bytes: call cp_model_detect.
+ *   head_out[i]   hm, hm_hp: [B,classes,H/4,W/4] as cp_model_detect; other entries are not read.
+ *   table_out[i]  every other head: its compact table.  Centre-indexed heads [B,classes,K]: entry k = the head at
+ *                 pk_ind[b][0][k]; hp_offset [B,8,2,K]: entry k of joint j = the head at pk_ind[b][j + 1][k].
+ *   pk_score, pk_ind  [B,9,K] float32 / int32: the peaks (score desc; index = y * (W/4) + x), map 0 = hm, 1..8 = hm_hp.
+ *   det           as cp_model_detect.  Against it: score and cls are bit-equal; a gathered entry differs from the dense map's
+ *                 by float32 summation order and last bits of the second product's pre-scale (<= 2e-5 * max(1, max|head|)).
+ * The feature map the heads read stays in `workspace` until the next call that uses the model or the workspace:
+ *   cp_model_dense_heads  writes the dense [B,classes,H/4,W/4] maps of every head other than hm / hm_hp from it (head_out
+ *                         indexed like the model's heads; hm / hm_hp entries ignored), bit-identical to cp_model_forward's;
+ *   cp_model_heads_at     evaluates those heads at a caller's pixel list index[B][n] (y * (W/4) + x, values outside the map
+ *                         are clamped into it; duplicates allowed) into table_out[i] = [B,classes,n].
+ * Both return CP_ERR_STATE when no feature map is kept. */
+int cp_model_lean_supported(cp_model* m, int B, int H, int W);
+size_t cp_model_detect_lean_workspace_bytes(cp_model* m, int B, int H, int W, int K);
+int cp_model_detect_lean(cp_model* m, cp_stream_t stream, int B, int H, int W, const float* images, const float* pre_img,
+                         const float* pre_hm, const float* pre_hm_hp, float* const* head_out, float* const* table_out,
+                         float* pk_score, int* pk_ind, int K, int rep_mode, int fit_gaussian, float balance,
+                         int legacy_bool_mask, float* det, void* workspace, size_t workspace_bytes, int use_graph);
+int cp_model_dense_heads(cp_model* m, cp_stream_t stream, float* const* head_out);
+size_t cp_model_heads_at_workspace_bytes(cp_model* m, int B, int n);
+int cp_model_heads_at(cp_model* m, cp_stream_t stream, const int* index, int n, float* const* table_out, void* workspace,
+                      size_t workspace_bytes);
 
 /* Debug/parity aid: same as cp_model_forward but additionally copies the named intermediate
  * activation (names follow the reference module paths, e.g. "base.level3", "dla_up.ida_2.node_3",
@@ -174,7 +210,7 @@ int cp_model_set_precision(cp_model* m, int precision);
  * pair.  cp_model_profile_read drains them: out[v*4 + 0..3] = {launches, total milliseconds, total
  * algorithmic FLOPs (2*M*Cout*KH*KW*Cin), total algorithmic bytes (input + output + weights
  * [+ offsets/mask] [+ residual], float32)} per kernel variant v in [0, CP_NUM_KERNEL_VARIANTS). */
-#define CP_NUM_KERNEL_VARIANTS 45
+#define CP_NUM_KERNEL_VARIANTS 46
 int cp_num_kernel_variants(void); /* the value the LIBRARY was built with: size cp_model_profile_read's buffer from it */
 int cp_model_profile(cp_model* m, int enable);
 int cp_model_profile_read(cp_model* m, double* out, int num_variants);
@@ -259,6 +295,25 @@ int cp_decode_tiled(cp_stream_t stream, int B, int H, int W, float* hm, const fl
                     float* hm_hp, const float* hp_offset, const float* tracking, const float* tracking_hp, int K,
                     int rep_mode, int fit_gaussian, float balance, int legacy_bool_mask, int apply_sigmoid, float* det,
                     void* workspace, size_t workspace_bytes);
+
+/* The decode in its two halves (cp_decode and cp_decode_tiled are the two called in sequence), for callers that evaluate the
+ * regression heads at the peaks only (cp_model_detect_lean does exactly this):
+ *   cp_decode_peaks     hm [B,1,H,W], hm_hp [B,8,H,W] (apply_sigmoid as cp_decode) -> pk_score / pk_ind [B,9,K]: the K peaks
+ *                       of each map after the 3x3 NMS, score descending, index = y * W + x; map 0 = hm, 1..8 = hm_hp.
+ *                       Any shape cp_decode or cp_decode_tiled accepts; workspace: cp_decode_peaks_workspace_bytes (0 =
+ *                       unsupported shape), 16-byte aligned.
+ *   cp_decode_gathered  the records from the peaks and COMPACT tables holding each regression head at the peaks: hps
+ *                       [B,16,K], wh [B,2,K] and the optional hps_uncertainty [B,16,K], scale [B,3,K], scale_uncertainty
+ *                       [B,3,K], reg [B,2,K], tracking [B,2,K], tracking_hp [B,16,K] (entry k = the head at pk_ind[b][0][k]),
+ *                       hp_offset [B,8,2,K] (entry k of joint j = the head at pk_ind[b][j+1][k]); hm_hp is the dense map.
+ *                       Same float expressions as cp_decode: tables copied out of dense maps give bit-identical records. */
+size_t cp_decode_peaks_workspace_bytes(int B, int H, int W, int K);
+int cp_decode_peaks(cp_stream_t stream, int B, int H, int W, float* hm, float* hm_hp, int K, int apply_sigmoid, float* pk_score,
+                    int* pk_ind, void* workspace, size_t workspace_bytes);
+int cp_decode_gathered(cp_stream_t stream, int B, int H, int W, const float* hm_hp, const float* hps, const float* wh,
+                       const float* hps_uncertainty, const float* scale, const float* scale_uncertainty, const float* reg,
+                       const float* hp_offset, const float* tracking, const float* tracking_hp, const float* pk_score,
+                       const int* pk_ind, int K, int rep_mode, int fit_gaussian, float balance, int legacy_bool_mask, float* det);
 
 /* ------------------------------------------------------------------------------------------
  * Pre-process — replaces `BaseDetector.pre_process`'s image work
