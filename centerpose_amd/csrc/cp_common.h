@@ -417,6 +417,24 @@ size_t cp_dcn_backward_ws_bytes(int B, int C, int H, int W, int Co, int kh, int 
                                 int dw, int dg);
 int cp_launch_dcn_backward(hipStream_t s, const DcnBwdArgs& a, void* ws);
 
+// ---- prediction-head block backward (heads_bwd.hip): n heads conv3x3 -> ReLU -> conv1x1 on one NHWC feature map ----
+struct PoseHeadsArgs {
+    const float* feat;          // [B,H,W,Cin]
+    int n;                      // heads
+    const float* const* w0;     // [hid,Cin,3,3] per head (PyTorch layout)
+    const float* const* b0;     // [hid]
+    const float* const* w1;     // [classes_i,hid]
+    const float* const* b1;     // [classes_i]
+    const int* classes;
+    int B, H, W, Cin, hid;
+};
+int cp_pose_heads_chunk(int B, int H, int W, int hid);  // images whose hidden layer is materialised at a time
+size_t cp_pose_heads_backward_ws_bytes(int B, int H, int W, int Cin, int hid, int max_classes);
+// grad_out[i] NCHW or nullptr (zero parameter gradients, no contribution); grad_feat NHWC or nullptr (not computed)
+int cp_launch_pose_heads_backward(hipStream_t s, const PoseHeadsArgs& a, const float* const* grad_out, float* const* grad_w0,
+                                  float* const* grad_b0, float* const* grad_w1, float* const* grad_b1, float* grad_feat,
+                                  void* ws);
+
 // ---- ObjectPoseLoss (pose_loss.hip; numerics in pose_loss_common.h) ----
 struct cp_pose_loss_desc;
 const char* cp_pose_loss_check(const cp_pose_loss_desc* d);                           // nullptr: accepted

@@ -181,6 +181,20 @@ int cp_model_forward(cp_model* m, cp_stream_t stream, int B, int H, int W, const
                         workspace, workspace_bytes, false);
 }
 
+int cp_model_features(cp_model* m, cp_stream_t stream, int B, int H, int W, const float* images, const float* pre_img,
+                      const float* pre_hm, const float* pre_hm_hp, float* feat_out, void* workspace, size_t workspace_bytes) {
+    if (!m || !images || !feat_out || !workspace) return fail(CP_ERR_INVALID, "null argument");
+    if (m->gru) return fail(CP_ERR_STATE, "cp_model_features: dlav1 heads read the ConvGRU steps through GroupNorm, not one feature map");
+    if (m->hourglass) return fail(CP_ERR_STATE, "cp_model_features: hourglass has two stacks of heads, not one feature map");
+    m->tap_name = nullptr;
+    drop_kept_in(m, workspace, workspace_bytes);
+    m->feat_out = feat_out;
+    const int rc = forward_impl(m, (hipStream_t)stream, B, H, W, images, pre_img, pre_hm, pre_hm_hp, nullptr, 0, workspace,
+                                workspace_bytes, false);
+    m->feat_out = nullptr;
+    return rc;
+}
+
 // the decode's share of a detect workspace: peaks_kernel up to 32768 output pixels, the tiled peaks above (0: unsupported)
 static size_t detect_decode_ws_bytes(int B, int H, int W, int K) {
     const int ho = H / 4, wo = W / 4;

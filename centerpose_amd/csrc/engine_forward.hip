@@ -91,6 +91,13 @@ struct Fwd {
         }
     }
     void tap(const std::string& name, const Tensor& t, int c_valid = 0) { tap(name.c_str(), t, c_valid); }
+    // cp_model_features: hands the heads' input to the caller; true = the pass ends here, no head is launched
+    bool features_only(const Tensor& t) {
+        if (!m->feat_out || m->dry) return false;
+        if (hipMemcpyAsync(m->feat_out, t.ptr(), (size_t)B * t.H * t.W * t.C * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess)
+            chk(CP_ERR_LAUNCH);
+        return true;
+    }
 
     // conv3x3 (+bias, ReLU) -> conv1x1 (+bias, optional sigmoid) of a prediction head in one kernel + a slice reduction;
     // returns false (nothing launched) when the launch would want split-K or the shapes are not eligible
@@ -707,6 +714,7 @@ struct Fwd {
             x = deconv("deconv_layers." + std::to_string(6 * i + 3), x);
             tap("deconv_layers." + std::to_string(6 * i + 5), x);
         }
+        if (features_only(x)) return;
         for (size_t i = 0; i < m->headw.size(); ++i) {
             const HeadW& hw = m->headw[i];
             const bool sg = sigmoid_hm && (hw.name == "hm" || hw.name == "hm_hp");
@@ -813,6 +821,7 @@ struct Fwd {
         Tensor feat = y[2];
         y.clear();
         tap("feat", feat);
+        if (features_only(feat)) return;
 
         std::vector<Tensor> gru_out;
         if (m->gru) {

@@ -2,7 +2,7 @@
 // DeconvLaunch is built, and the profiling bracket around a launch.
 //   engine_pack.hip     parameter folding and packing (cp_model_create .. cp_model_finalize, cp_model_destroy)
 //   engine_forward.hip  the forward pass and its kernel dispatch (forward_impl)
-//   ops.hip             the stand-alone operators (cp_conv2d_nhwc, cp_conv_transpose2d_nhwc, cp_dcnv2_forward / _backward)
+//   ops.hip             the stand-alone operators (cp_conv2d_nhwc, cp_conv_transpose2d_nhwc, cp_dcnv2_forward / _backward, cp_pose_heads_*)
 //   engine.hip          the model's run-time C ABI and the one-line wrappers of the other modules
 // Everything here has C++ linkage (only the C ABI of include/centerpose_hip.h is exported unmangled).
 #pragma once
@@ -247,6 +247,7 @@ struct cp_model {
     const char* tap_name = nullptr;
     float* tap_out = nullptr;
     int* tap_dims = nullptr;
+    float* feat_out = nullptr;  // cp_model_features: the heads' input goes here (NHWC) and the pass ends before the heads
     // optional per-launch profiling of the implicit-GEMM kernels (HIP events on the launch stream)
     struct ProfRec {
         int variant;

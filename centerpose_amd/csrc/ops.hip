@@ -1,6 +1,7 @@
 // The stand-alone operators of the C ABI (include/centerpose_hip.h): single layers on caller tensors, outside any cp_model
-// -- cp_conv2d_nhwc, cp_conv_transpose2d_nhwc, cp_dcnv2_forward / cp_dcnv2_backward.  Each packs its PyTorch-layout weights
-// into a caller-provided workspace on every call and then launches the same kernels as the engine.
+// -- cp_conv2d_nhwc, cp_conv_transpose2d_nhwc, cp_dcnv2_forward / cp_dcnv2_backward, cp_pose_heads_forward / _backward.
+// Each packs its PyTorch-layout weights into a caller-provided workspace on every call and then launches the same kernels as
+// the engine.
 #include "engine_model.h"
 
 using namespace cp_engine;
@@ -183,9 +184,156 @@ const char* dcn_bwd_shape_error(int B, int C, int H, int W, int Co, int kh, int 
     return nullptr;
 }
 
+// Prediction-head block (cp_pose_heads_forward / _backward): shape checks shared by the calls and their workspace queries
+const char* heads_shape_error(int B, int H, int W, int Cin, int hid, int n, const int* classes, int* cmax) {
+    if (n < 1 || !classes) return "pose_heads: at least one head (and its class count) is needed";
+    if (B < 1 || H < 1 || W < 1) return "pose_heads: B, H and W must be at least 1";
+    if (Cin < 32 || Cin % 32) return "pose_heads: Cin must be a positive multiple of 32";
+    if (hid < 32 || hid % 32) return "pose_heads: the hidden width must be a positive multiple of 32";
+    int mx = 0;
+    for (int i = 0; i < n; ++i) {
+        if (classes[i] < 1 || classes[i] > 64) return "pose_heads: classes must be in 1..64 for every head";
+        mx = std::max(mx, classes[i]);
+    }
+    const long long lim = 0x7fffffffLL, px = (long long)B * H * W;
+    if (px * Cin >= lim || px * mx >= lim || (long long)H * W * hid >= lim || (long long)hid * Cin * 9 >= lim)
+        return "pose_heads: a tensor has 2^31 elements or more";
+    *cmax = mx;
+    return nullptr;
+}
+
+// cp_pose_heads_forward: per head the 3x3 layer's float32 and f16x3 operands + bias, the 1x1 layer's, one hidden chunk
+struct HeadsFwdWs {
+    float *wp0, *shift0, *wp1, *shift1, *hid;
+    Pack16 f16;
+};
+HeadsFwdWs heads_fwd_carve(Carve& c, int B, int H, int W, int Cin, int hid) {
+    const size_t k0 = (size_t)9 * Cin, hpad = align_up((size_t)hid, cp_conv_tile_n(hid));
+    HeadsFwdWs r;
+    r.wp0 = c.take<float>(k0 * hpad * 4);
+    r.shift0 = c.take<float>(hpad * 4);
+    r.wp1 = c.take<float>((size_t)hid * 64 * 4);
+    r.shift1 = c.take<float>(64 * 4);
+    r.f16 = carve_pack16(c, k0, hpad);
+    r.hid = c.take<float>((size_t)cp_pose_heads_chunk(B, H, W, hid) * H * W * hid * 4);
+    return r;
+}
+
 }  // namespace
 
 extern "C" {
+
+int cp_pose_heads_chunk_images(int B, int H, int W, int hid) {
+    if (B < 1 || H < 1 || W < 1 || hid < 1) return 0;
+    return cp_pose_heads_chunk(B, H, W, hid);
+}
+
+size_t cp_pose_heads_forward_workspace_bytes(int B, int H, int W, int Cin, int hid, int n, const int* classes) {
+    int cmax = 0;
+    if (const char* e = heads_shape_error(B, H, W, Cin, hid, n, classes, &cmax)) {
+        fail(CP_ERR_INVALID, e);
+        return 0;
+    }
+    Carve c{nullptr};
+    heads_fwd_carve(c, B, H, W, Cin, hid);
+    return c.off;
+}
+
+size_t cp_pose_heads_backward_workspace_bytes(int B, int H, int W, int Cin, int hid, int n, const int* classes) {
+    int cmax = 0;
+    if (const char* e = heads_shape_error(B, H, W, Cin, hid, n, classes, &cmax)) {
+        fail(CP_ERR_INVALID, e);
+        return 0;
+    }
+    return cp_pose_heads_backward_ws_bytes(B, H, W, Cin, hid, cmax);
+}
+
+int cp_pose_heads_forward(cp_stream_t stream, const float* feat, int n, const float* const* w0, const float* const* b0,
+                          const float* const* w1, const float* const* b1, const int* classes, float* const* out, int B, int H,
+                          int W, int Cin, int hid, void* workspace, size_t workspace_bytes) {
+    int cmax = 0;
+    if (const char* e = heads_shape_error(B, H, W, Cin, hid, n, classes, &cmax)) return fail(CP_ERR_INVALID, e);
+    if (!feat || !w0 || !b0 || !w1 || !b1 || !out || !workspace) return fail(CP_ERR_INVALID, "pose_heads_forward: null argument");
+    for (int i = 0; i < n; ++i)
+        if (!w0[i] || !b0[i] || !w1[i] || !b1[i] || !out[i]) return fail(CP_ERR_INVALID, "pose_heads_forward: null argument");
+    Carve c{(char*)workspace};
+    const HeadsFwdWs r = heads_fwd_carve(c, B, H, W, Cin, hid);
+    if (workspace_bytes < c.off) return fail(CP_ERR_INVALID, "pose_heads_forward: workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    const int HW = H * W, chunk = cp_pose_heads_chunk(B, H, W, hid);
+    const bool f16x3 = g_default_precision == CP_PREC_F16X3;
+    for (int i = 0; i < n; ++i) {
+        const int cls = classes[i];
+        ConvW c0, c1;
+        c0.Cin = c0.CinP = Cin;
+        c0.Cout = hid;
+        c0.CoutPad = (int)align_up((size_t)hid, cp_conv_tile_n(hid));
+        c0.KH = c0.KW = 3;
+        c0.K = c0.Kpad = 9 * Cin;
+        c0.wp = r.wp0;
+        c0.shift = r.shift0;
+        c1.Cin = c1.CinP = hid;
+        c1.Cout = cls;
+        c1.CoutPad = (int)align_up((size_t)cls, cp_conv_tile_n(cls));
+        c1.KH = c1.KW = 1;
+        c1.K = c1.Kpad = hid;
+        c1.wp = r.wp1;
+        c1.shift = r.shift1;
+        if (hipMemsetAsync(r.wp0, 0, (char*)r.f16.hi - (char*)r.wp0, s) != hipSuccess) return CP_ERR_LAUNCH;
+        int rc = cp_launch_pack_weight(w0[i], r.wp0, hid, Cin, 9, Cin, c0.CoutPad, 0, s);
+        if (rc == CP_OK) rc = cp_launch_pack_weight(w1[i], r.wp1, cls, hid, 1, hid, c1.CoutPad, 0, s);
+        if (rc != CP_OK) return fail(rc, "pose_heads_forward: weight packing failed");
+        if (hipMemcpyAsync(r.shift0, b0[i], (size_t)hid * 4, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+            hipMemcpyAsync(r.shift1, b1[i], (size_t)cls * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)
+            return CP_ERR_LAUNCH;
+        if (f16x3) {  // range-safe f16x3 operands of the 3x3 layer, as cp_conv2d_nhwc builds them; the 1x1 layer stays exact
+            rc = pack_f16x3(r.f16, w0[i], nullptr, 9, c0, feat, (size_t)B * HW * Cin, nullptr, 0, s);
+            if (rc != CP_OK) return fail(rc, "pose_heads_forward: f16x3 packing failed");
+        }
+        for (int b = 0; b < B; b += chunk) {
+            const int nb = std::min(chunk, B - b);
+            const float* src = feat + (size_t)b * HW * Cin;
+            ConvParams p = conv_params(nb, H, W, &src, &Cin, 1, c0, 1, 1, CP_ACT_RELU);
+            p.out = r.hid;
+            p.store = CP_STORE_NHWC;
+            p.ldo = hid;
+            const unsigned* slot = r.f16.slot;
+            if (f16x3 && conv_params_f16(p, c0, &slot, true)) rc = cp_launch_conv16(p, s);
+            else {
+                p.w16_hi = p.w16_lo = p.w16f_hi = p.w16f_lo = nullptr;
+                rc = cp_launch_conv(p, s);
+            }
+            if (rc != CP_OK) return fail(rc, "pose_heads_forward: 3x3 launch failed");
+            const float* hsrc = r.hid;
+            ConvParams q = conv_params(nb, H, W, &hsrc, &hid, 1, c1, 1, 0, CP_ACT_NONE);
+            q.out = out[i] + (size_t)b * cls * HW;
+            q.store = CP_STORE_NCHW;
+            q.ldo = cls;
+            rc = cp_launch_conv(q, s);
+            if (rc != CP_OK) return fail(rc, "pose_heads_forward: 1x1 launch failed");
+        }
+    }
+    return CP_OK;
+}
+
+int cp_pose_heads_backward(cp_stream_t stream, const float* feat, int n, const float* const* w0, const float* const* b0,
+                           const float* const* w1, const float* const* b1, const int* classes, const float* const* grad_out,
+                           float* const* grad_w0, float* const* grad_b0, float* const* grad_w1, float* const* grad_b1,
+                           float* grad_feat, int B, int H, int W, int Cin, int hid, void* workspace, size_t workspace_bytes) {
+    int cmax = 0;
+    if (const char* e = heads_shape_error(B, H, W, Cin, hid, n, classes, &cmax)) return fail(CP_ERR_INVALID, e);
+    if (!feat || !w0 || !b0 || !w1 || !b1 || !grad_out || !grad_w0 || !grad_b0 || !grad_w1 || !grad_b1 || !workspace)
+        return fail(CP_ERR_INVALID, "pose_heads_backward: null argument");
+    for (int i = 0; i < n; ++i)
+        if (!w0[i] || !b0[i] || !w1[i] || !b1[i] || !grad_w0[i] || !grad_b0[i] || !grad_w1[i] || !grad_b1[i])
+            return fail(CP_ERR_INVALID, "pose_heads_backward: null argument");
+    if (workspace_bytes < cp_pose_heads_backward_ws_bytes(B, H, W, Cin, hid, cmax))
+        return fail(CP_ERR_INVALID, "pose_heads_backward: workspace too small");
+    const PoseHeadsArgs a{feat, n, w0, b0, w1, b1, classes, B, H, W, Cin, hid};
+    const int rc = cp_launch_pose_heads_backward((hipStream_t)stream, a, grad_out, grad_w0, grad_b0, grad_w1, grad_b1, grad_feat,
+                                                 workspace);
+    return rc == CP_OK ? CP_OK : fail(rc, "pose_heads_backward: kernel launch failed");
+}
 
 size_t cp_conv2d_workspace_bytes(int Cin, int Cout, int KH, int KW) {
     Carve c{nullptr};

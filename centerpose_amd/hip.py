@@ -104,6 +104,15 @@ def lib():
          *([c_int] * 14), c_void_p, c_size_t)
     _sig(L.cp_dcnv2_backward_workspace_bytes, c_size_t, *([c_int] * 14))
     _sig(L.cp_dcnv2_backward, c_int, *([c_void_p] * 11), *([c_int] * 14), c_void_p, c_size_t)
+    _sig(L.cp_pose_heads_chunk_images, c_int, c_int, c_int, c_int, c_int)
+    _sig(L.cp_pose_heads_forward_workspace_bytes, c_size_t, *([c_int] * 6), ctypes.POINTER(c_int))
+    _sig(L.cp_pose_heads_backward_workspace_bytes, c_size_t, *([c_int] * 6), ctypes.POINTER(c_int))
+    _sig(L.cp_pose_heads_forward, c_int, c_void_p, c_void_p, c_int, *([ctypes.POINTER(c_void_p)] * 4), ctypes.POINTER(c_int),
+         ctypes.POINTER(c_void_p), *([c_int] * 5), c_void_p, c_size_t)
+    _sig(L.cp_pose_heads_backward, c_int, c_void_p, c_void_p, c_int, *([ctypes.POINTER(c_void_p)] * 4), ctypes.POINTER(c_int),
+         *([ctypes.POINTER(c_void_p)] * 5), c_void_p, *([c_int] * 5), c_void_p, c_size_t)
+    _sig(L.cp_model_features, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_void_p, c_size_t)
     _sig(L.cp_model_create, c_int, c_char_p, c_int, c_int, ctypes.POINTER(c_char_p), ctypes.POINTER(c_int), c_int,
          ctypes.POINTER(c_void_p))
     _sig(L.cp_model_set_param, c_int, c_void_p, c_char_p, c_void_p, ctypes.c_int64)
@@ -214,7 +223,9 @@ def exported_symbols():
             "cp_pose_targets_workspace_bytes", "cp_pose_targets", "cp_model_lean_supported",
             "cp_model_detect_lean_workspace_bytes", "cp_model_detect_lean", "cp_model_dense_heads",
             "cp_model_heads_at_workspace_bytes", "cp_model_heads_at", "cp_decode_peaks_workspace_bytes", "cp_decode_peaks",
-            "cp_decode_gathered"]
+            "cp_decode_gathered", "cp_pose_heads_chunk_images", "cp_pose_heads_forward_workspace_bytes",
+            "cp_pose_heads_forward", "cp_pose_heads_backward_workspace_bytes", "cp_pose_heads_backward",
+            "cp_model_features"]
 
 
 def _check(rc, what):
@@ -336,6 +347,97 @@ def dcn_v2_backward(input, weight, bias, offset, mask, grad_output, kh, kw, sh, 
                              _ptr(workspace), workspace.numel() * workspace.element_size())
     _check(rc, "cp_dcnv2_backward")
     return grads
+
+
+def _nhwc_view(feat):
+    """[B,C,H,W] tensor -> the same values as NHWC memory ([B,C,H,W] tensor in channels_last format; no copy when it already is)."""
+    if not feat.is_cuda:
+        raise RuntimeError("centerpose_hip: tensors must live on the HIP device (no CPU path)")
+    if feat.dim() != 4:
+        raise RuntimeError("pose_heads: feat must be [B, Cin, H, W]")
+    return feat.float().contiguous(memory_format=torch.channels_last)
+
+
+def _heads_args(feat, params):
+    """Shape checks and the pointer tables of a pose_heads call.  ``params``: per head (w0 [hid,Cin,3,3], b0 [hid],
+    w1 [classes,hid,1,1], b1 [classes])."""
+    B, Cin, H, W = feat.shape
+    if len(params) < 1:
+        raise RuntimeError("pose_heads: at least one head is needed")
+    hid = params[0][0].shape[0]
+    flat, classes = [], []
+    for i, (w0, b0, w1, b1) in enumerate(params):
+        w0, b0, w1, b1 = map(_dev, (w0, b0, w1, b1))
+        c = w1.shape[0]
+        for name, t, shape in (("w0", w0, (hid, Cin, 3, 3)), ("b0", b0, (hid,)), ("w1", w1, (c, hid, 1, 1)), ("b1", b1, (c,))):
+            if tuple(t.shape) != shape:
+                raise RuntimeError("pose_heads: head %d %s has shape %s, expected %s" % (i, name, tuple(t.shape), shape))
+        flat.append((w0, b0, w1, b1))
+        classes.append(int(c))
+    n = len(flat)
+    tables = [(c_void_p * n)(*[p[k].data_ptr() for p in flat]) for k in range(4)]
+    return flat, tables, (c_int * n)(*classes), classes, (B, H, W, Cin, hid)
+
+
+def pose_heads_chunk_images(B, H, W, hid):
+    """Images whose hidden layer pose_heads_backward materialises at a time (cp_pose_heads_chunk_images)."""
+    return int(lib().cp_pose_heads_chunk_images(int(B), int(H), int(W), int(hid)))
+
+
+def pose_heads_forward(feat, params):
+    """The prediction-head block conv3x3 -> ReLU -> conv1x1 of every head on one feature map (cp_pose_heads_forward).
+    ``feat`` [B,Cin,H,W] (NCHW-contiguous or channels_last; the kernels read NHWC), ``params`` a list of (w0, b0, w1, b1)
+    per head -> list of [B,classes_i,H,W] raw logits."""
+    L = lib()
+    feat = _nhwc_view(feat)
+    flat, tables, cls_arr, classes, (B, H, W, Cin, hid) = _heads_args(feat, params)
+    outs = [torch.empty(B, c, H, W, device=feat.device, dtype=torch.float32) for c in classes]
+    optr = (c_void_p * len(outs))(*[t.data_ptr() for t in outs])
+    nbytes = L.cp_pose_heads_forward_workspace_bytes(B, H, W, Cin, hid, len(outs), cls_arr)
+    if nbytes == 0:
+        raise RuntimeError("pose_heads_forward: shape refused by the library (%s)" % L.cp_last_error().decode())
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=feat.device)
+    rc = L.cp_pose_heads_forward(_stream(), _ptr(feat), len(outs), *tables, cls_arr, optr, B, H, W, Cin, hid, _ptr(ws), nbytes)
+    _check(rc, "cp_pose_heads_forward")
+    return outs
+
+
+def pose_heads_backward(feat, params, grad_outs, need_feat_grad=True, grad_feat=None):
+    """Gradients of pose_heads_forward (cp_pose_heads_backward).  ``grad_outs``: per head a [B,classes_i,H,W] tensor or None (a
+    head the loss does not use: zero parameter gradients, nothing added to grad_feat).  Returns (grad_feat, grads) with
+    grads[i] = (grad_w0, grad_b0, grad_w1, grad_b1); grad_feat is a [B,Cin,H,W] channels_last tensor, or None when
+    ``need_feat_grad`` is false (the data-gradient contraction is then not launched).  ``grad_feat``: an optional
+    channels_last buffer to write into."""
+    L = lib()
+    feat = _nhwc_view(feat)
+    flat, tables, cls_arr, classes, (B, H, W, Cin, hid) = _heads_args(feat, params)
+    n = len(flat)
+    if len(grad_outs) != n:
+        raise RuntimeError("pose_heads_backward: %d gradients for %d heads" % (len(grad_outs), n))
+    gos = []
+    for i, g in enumerate(grad_outs):
+        if g is not None:
+            g = _dev(g)
+            if tuple(g.shape) != (B, classes[i], H, W):
+                raise RuntimeError("pose_heads_backward: grad_out %d has shape %s, expected %s"
+                                   % (i, tuple(g.shape), (B, classes[i], H, W)))
+        gos.append(g)
+    grads = [tuple(torch.empty_like(t) for t in p) for p in flat]
+    gtab = [(c_void_p * n)(*[g[k].data_ptr() for g in grads]) for k in range(4)]
+    goptr = (c_void_p * n)(*[g.data_ptr() if g is not None else None for g in gos])
+    if need_feat_grad and grad_feat is None:
+        grad_feat = torch.empty_like(feat, memory_format=torch.channels_last)
+    if need_feat_grad and not (grad_feat.is_cuda and grad_feat.dtype == torch.float32 and grad_feat.shape == feat.shape and
+                               grad_feat.is_contiguous(memory_format=torch.channels_last)):
+        raise RuntimeError("pose_heads_backward: grad_feat must be a float32 channels_last tensor of feat's shape")
+    nbytes = L.cp_pose_heads_backward_workspace_bytes(B, H, W, Cin, hid, n, cls_arr)
+    if nbytes == 0:
+        raise RuntimeError("pose_heads_backward: shape refused by the library (%s)" % L.cp_last_error().decode())
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=feat.device)
+    rc = L.cp_pose_heads_backward(_stream(), _ptr(feat), n, *tables, cls_arr, goptr, *gtab,
+                                  _ptr(grad_feat) if need_feat_grad else c_void_p(0), B, H, W, Cin, hid, _ptr(ws), nbytes)
+    _check(rc, "cp_pose_heads_backward")
+    return (grad_feat if need_feat_grad else None), grads
 
 
 def conv2d_nhwc(x, w, scale=None, shift=None, residual=None, stride=1, pad=0, act=0):
@@ -1162,6 +1264,25 @@ class HipModel(object):
         if C == 0:
             raise RuntimeError("unknown tap %r" % tap)
         return outs, tap_buf[: B * C * h * w].view(B, C, h, w)
+
+    def features(self, images, pre_img=None, pre_hm=None, pre_hm_hp=None):
+        """The tensor the heads read (cp_model_features): images [B,3,H,W] -> [B,Cin,H/4,W/4] in channels_last memory format (the
+        engine's NHWC buffer, no copy); no head is launched.  dla_34 and resdcn_* only."""
+        L = lib()
+        if self.arch.startswith("dlav1") or self.arch == "hourglass":
+            raise NotImplementedError("features(): %s has no single feature map that plain conv3x3 -> ReLU -> conv1x1 heads read"
+                                      % self.arch)
+        images = _dev(images)
+        B, _, H, W = images.shape
+        pre_img = _dev(pre_img) if pre_img is not None else None
+        pre_hm = _dev(pre_hm) if pre_hm is not None else None
+        pre_hm_hp = _dev(pre_hm_hp) if pre_hm_hp is not None else None
+        feat = torch.empty(B, H // 4, W // 4, 64, device=images.device, dtype=torch.float32)
+        ws = self._workspace(B, H, W, images.device)
+        rc = L.cp_model_features(self._h, _stream(), B, H, W, _ptr(images), _ptr(pre_img), _ptr(pre_hm), _ptr(pre_hm_hp),
+                                 _ptr(feat), _ptr(ws), ws.numel())
+        _check(rc, "cp_model_features")
+        return feat.permute(0, 3, 1, 2)
 
     def lean_supported(self, B, H, W):
         """Does detect(heads="lazy") take the lean path for this shape (cp_model_lean_supported)?"""

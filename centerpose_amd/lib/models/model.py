@@ -93,7 +93,44 @@ class HipPoseNet(object):
 
     def train(self, mode=True):
         if mode:
-            raise NotImplementedError("centerpose_hip is an inference library")
+            raise NotImplementedError("centerpose_hip runs the backbone for inference only; to train the prediction heads on "
+                                      "its frozen features use model.head_module() (centerpose_amd.pose_heads.PoseHeads)")
+        return self
+
+    # ---- training the heads on the frozen backbone (centerpose_amd/pose_heads.py) ----
+    def _plain_heads(self, what):
+        if self.arch.startswith('dlav1') or self.arch == 'hourglass':
+            raise NotImplementedError("%s: %s has no conv3x3 -> ReLU -> conv1x1 heads on one feature map (dlav1: ConvGRU + "
+                                      "GroupNorm heads; hourglass: two stacks)" % (what, self.arch))
+        if self.head_conv <= 0:
+            raise NotImplementedError("%s: head_conv must be positive, got %d" % (what, self.head_conv))
+
+    def features(self, x, pre_img=None, pre_hm=None, pre_hm_hp=None):
+        """The feature map the heads read, [B, 64, H/4, W/4] in channels_last memory format; no head runs and no graph is kept
+        (the backbone is frozen)."""
+        self._plain_heads("features()")
+        if not x.is_cuda:
+            raise RuntimeError("HipPoseNet runs on the HIP device only: move the model and inputs with .to('cuda')")
+        return self._engine().features(x, pre_img, pre_hm, pre_hm_hp)
+
+    def head_module(self):
+        """A ``PoseHeads`` holding copies of this model's current head parameters (train it, then ``load_heads``)."""
+        self._plain_heads("head_module()")
+        from centerpose_amd.pose_heads import PoseHeads
+        module = PoseHeads(self.heads, 64, self.head_conv)
+        module.load_state_dict({k: self._sd[k] for k in module.state_dict()})
+        return module
+
+    def load_heads(self, module):
+        """Copies a ``PoseHeads``' parameters back into this model; the next call / detector run uses them."""
+        self._plain_heads("load_heads()")
+        sd = module.state_dict()
+        for k, v in sd.items():
+            if k not in self._sd or tuple(self._sd[k].shape) != tuple(v.shape):
+                raise RuntimeError("load_heads: %s does not match this model's heads" % k)
+        for k, v in sd.items():
+            self._sd[k] = v.detach().cpu().float().clone()
+        self._hip = None
         return self
 
     def parameters(self):

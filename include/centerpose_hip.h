@@ -44,7 +44,8 @@ typedef struct cp_model cp_model;
  *     later additions without a version change: cp_box_iou, cp_box_eval, cp_pose_loss_workspace_bytes,
  *     cp_pose_loss_forward, cp_pose_loss_backward, cp_pose_targets_workspace_bytes, cp_pose_targets,
  *     cp_model_lean_supported, cp_model_detect_lean(_workspace_bytes), cp_model_dense_heads, cp_model_heads_at(_workspace_bytes),
- *     cp_decode_peaks(_workspace_bytes), cp_decode_gathered; CP_NUM_KERNEL_VARIANTS 46. */
+ *     cp_decode_peaks(_workspace_bytes), cp_decode_gathered; CP_NUM_KERNEL_VARIANTS 46;
+ *     cp_pose_heads_forward / _backward (+ _workspace_bytes, cp_pose_heads_chunk_images), cp_model_features. */
 #define CP_ABI_VERSION 7
 const char* cp_version(void);
 int cp_abi_version(void);
@@ -105,6 +106,44 @@ int cp_dcnv2_backward(cp_stream_t stream, const float* input, const float* weigh
                       void* workspace, size_t workspace_bytes);
 
 /* ------------------------------------------------------------------------------------------
+ * Prediction-head block, forward and backward — replaces the per-head loop
+ *   `for head in self.heads: z[head] = self.__getattr__(head)(y[-1])` and its autograd graph
+ *   (models/networks/pose_dla_dcn.py:491-521 builds the Sequentials, :537-539 runs them; resnet_dcn.py likewise):
+ *   head i = Conv2d(Cin, hid, 3, padding=1) -> ReLU -> Conv2d(hid, classes_i, 1), all n heads on one feature map.
+ * feat [B,H,W,Cin] NHWC (the engine's layout; a channels_last torch tensor [B,Cin,H,W] is this memory).  The pointer
+ * arrays are HOST arrays of n device pointers: w0[i] [hid,Cin,3,3], b0[i] [hid], w1[i] [classes_i,hid,1,1],
+ * b1[i] [classes_i] in PyTorch layout; classes[i] in 1..64 (host ints); hid shared by the heads.
+ *   forward   out[i] [B,classes_i,H,W] NCHW raw logits (what cp_model_forward returns).  Built from the library's
+ *             convolution kernels; the 3x3 layer follows cp_set_default_precision like cp_conv2d_nhwc, the 1x1 is float32.
+ *   backward  grad_out[i] [B,classes_i,H,W] NCHW, or NULL for a head the loss does not use: it contributes nothing
+ *             and its four parameter gradients are written as zeros.  Outputs, written (not accumulated):
+ *             grad_w0[i], grad_b0[i], grad_w1[i], grad_b1[i] in the parameters' layouts, and grad_feat [B,H,W,Cin] NHWC
+ *             = the sum over the heads, or NULL (frozen backbone): the data-gradient contraction is then not launched.
+ * Semantics are autograd's for the block; the ReLU gate is `hidden > 0` on the hidden value the backward recomputes.
+ * Backward arithmetic is exact float32 (v_mfma_f32_32x32x2_f32 contractions, float32 VALU elsewhere) whatever
+ * cp_set_default_precision says.  Nothing is kept between forward and backward: the backward recomputes a head's hidden
+ * layer for cp_pose_heads_chunk_images(B, H, W, hid) images at a time (at most 256 MiB, or one image) inside `workspace`
+ * and drops it; the hidden maps of all heads never exist together.
+ * Reproducibility: every gradient, grad_feat included, is bitwise reproducible run to run (weight and bias gradients are
+ * summed over pixel slabs in slab order, grad_feat over the heads in index order; no atomics).
+ * Accepted: Cin % 32 == 0, hid % 32 == 0, any B, H, W >= 1, every tensor (and one image's hidden map) below 2^31
+ * elements; anything else, a NULL pointer other than those named above or a workspace below the query returns
+ * CP_ERR_INVALID with a cp_last_error() text before any launch (the queries return 0).  Launches on `stream`, never
+ * synchronises.
+ * ------------------------------------------------------------------------------------------ */
+int cp_pose_heads_chunk_images(int B, int H, int W, int hid);
+size_t cp_pose_heads_forward_workspace_bytes(int B, int H, int W, int Cin, int hid, int n, const int* classes);
+int cp_pose_heads_forward(cp_stream_t stream, const float* feat, int n, const float* const* w0, const float* const* b0,
+                          const float* const* w1, const float* const* b1, const int* classes, float* const* out, int B,
+                          int H, int W, int Cin, int hid, void* workspace, size_t workspace_bytes);
+size_t cp_pose_heads_backward_workspace_bytes(int B, int H, int W, int Cin, int hid, int n, const int* classes);
+int cp_pose_heads_backward(cp_stream_t stream, const float* feat, int n, const float* const* w0, const float* const* b0,
+                           const float* const* w1, const float* const* b1, const int* classes,
+                           const float* const* grad_out, float* const* grad_w0, float* const* grad_b0,
+                           float* const* grad_w1, float* const* grad_b1, float* grad_feat, int B, int H, int W, int Cin,
+                           int hid, void* workspace, size_t workspace_bytes);
+
+/* ------------------------------------------------------------------------------------------
  * Backbone + heads — replaces `create_model` / `load_model` / `model(images, pre_images,
  *   pre_hms, pre_hm_hp)[-1]`  (models/model.py:26-87, models/networks/pose_dla_dcn.py:457-570,
  *   detectors/object_pose.py:135-138).
@@ -134,6 +173,15 @@ size_t cp_model_workspace_bytes(cp_model* m, int B, int H, int W);
 int cp_model_forward(cp_model* m, cp_stream_t stream, int B, int H, int W, const float* images,
                      const float* pre_img, const float* pre_hm, const float* pre_hm_hp, float* const* head_out,
                      int sigmoid_hm, void* workspace, size_t workspace_bytes);
+
+/* The forward pass up to the tensor the heads read (pose_dla_dcn.py:531-536 `y[-1]`; resnet_dcn.py: the output of
+ * deconv_layers), written to feat_out as [B,H/4,W/4,Cin] NHWC; no head is launched.  Arguments and workspace
+ * (cp_model_workspace_bytes) as cp_model_forward.  Bit-identical to the "feat" tap (resdcn: "deconv_layers.17") up to the
+ * layout.  For models whose head block has the plain conv3x3 -> ReLU -> conv1x1 form: dla_34 and resdcn_*; dlav1_34
+ * (ConvGRU + GroupNorm heads) and hourglass (two stacks) return CP_ERR_STATE.  Feeds cp_pose_heads_forward / _backward. */
+int cp_model_features(cp_model* m, cp_stream_t stream, int B, int H, int W, const float* images, const float* pre_img,
+                      const float* pre_hm, const float* pre_hm_hp, float* feat_out, void* workspace,
+                      size_t workspace_bytes);
 
 /* One frame batch end to end on the device: backbone + heads + sigmoid(hm, hm_hp) + decode — what
  * `ObjectPoseDetector.process` does (detectors/object_pose.py:131-165) — in ONE call.  Arguments as in
