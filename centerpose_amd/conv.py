@@ -1,0 +1,141 @@
+"""Ordinary convolutions on the library's kernels, forward and backward: ``conv2d``, ``Conv2d`` and ``use_hip_convs``.
+
+The reference's backbones are mostly ``nn.Conv2d``: DLA's ``BasicBlock`` 3x3 pairs (pose_dla_dcn.py:48-62), the 1x1 ``Root`` and
+``project`` layers, ResNet's 1x1 stride-2 down-samples and the 3x3 ``conv_offset_mask`` of every ``DCN`` (DCNv2/dcn_v2.py:118-128).
+``conv2d`` is one autograd function over ``cp_conv2d_nhwc`` (forward; precision follows ``hip.set_default_precision``) and
+``cp_conv2d_backward_nhwc`` (backward; float32, bitwise reproducible).  ``Conv2d`` is ``nn.Conv2d`` with that forward and nothing
+else changed, and ``use_hip_convs(model)`` re-classes a tree's eligible convolutions in place, so a network that trains through
+torch moves its convolutions onto the library in one line and keeps its parameters, optimizer state and checkpoints.
+
+BatchNorm, residual adds and everything else stay torch's; dilation, groups and ``in_channels % 4 != 0`` are not built.
+"""
+import torch
+from torch import nn
+from torch.autograd import Function
+from torch.autograd.function import once_differentiable
+
+from . import hip as _hip
+
+
+def _nhwc(t):
+    """Logical [B,C,H,W] tensor -> its values as a contiguous [B,H,W,C] tensor (no copy when it is channels_last already)."""
+    return _hip._nhwc_view(t).permute(0, 2, 3, 1)
+
+
+class _Conv2dFn(Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride, pad, relu):
+        xh = _nhwc(x)
+        w = _hip._dev(weight)
+        cout = w.shape[0]
+        wf, shift = w, None
+        if bias is not None:
+            # the forward operator reads `shift` up to its N tile: pad the weight and the bias with zero channels, slice the output
+            tile = 16 if cout <= 16 else 32 if cout <= 32 else 128 if cout % 128 == 0 else 64
+            cpad = (cout + tile - 1) // tile * tile
+            shift = _hip._dev(bias)
+            if cpad != cout:
+                wf = torch.cat([w, w.new_zeros((cpad - cout,) + tuple(w.shape[1:]))])
+                shift = torch.cat([shift, shift.new_zeros(cpad - cout)])
+        y = _hip.conv2d_nhwc(xh, wf, shift=shift, stride=stride, pad=pad, act=1 if relu else 0)
+        if y.shape[3] != cout:
+            y = y[..., :cout].contiguous()
+        ctx.stride, ctx.pad, ctx.relu, ctx.has_bias = stride, pad, relu, bias is not None
+        if relu:
+            ctx.save_for_backward(x, weight, y)
+        else:
+            ctx.save_for_backward(x, weight)
+        return y.permute(0, 3, 1, 2)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        x, weight = ctx.saved_tensors[:2]
+        y = ctx.saved_tensors[2] if ctx.relu else None
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_b = ctx.has_bias and ctx.needs_input_grad[2]
+        if not (need_x or need_w or need_b):
+            return None, None, None, None, None, None
+        gx, gw, gb = _hip.conv2d_backward(_nhwc(x), weight, _nhwc(grad_out), stride=ctx.stride, pad=ctx.pad, y=y,
+                                          need_x_grad=need_x, need_bias_grad=need_b)
+        return (gx.permute(0, 3, 1, 2) if need_x else None, gw if need_w else None, gb if need_b else None, None, None, None)
+
+
+def _pair(v, what):
+    if isinstance(v, str):
+        raise NotImplementedError("conv2d: string %s is not built" % what)
+    if isinstance(v, (tuple, list)):
+        if len(v) != 2 or v[0] != v[1]:
+            raise NotImplementedError("conv2d: %s must be the same on both axes, got %r" % (what, tuple(v)))
+        v = v[0]
+    return int(v)
+
+
+def conv2d(x, weight, bias=None, stride=1, padding=0, relu=False):
+    """``relu?(F.conv2d(x, weight, bias, stride, padding))`` on the HIP kernels with autograd.  ``x`` is a logical [B,Cin,H,W] tensor on
+    the device, NCHW-contiguous or channels_last (the kernels read NHWC; channels_last costs no copy); the result is
+    channels_last.  Dilation 1, groups 1, ``Cin % 4 == 0``."""
+    if not x.is_cuda:
+        raise RuntimeError("centerpose_hip: tensors must live on the HIP device (no CPU path)")
+    if x.dim() != 4 or weight.dim() != 4 or weight.shape[1] != x.shape[1]:
+        raise RuntimeError("conv2d: x must be [B,Cin,H,W] and weight [Cout,Cin,KH,KW], got %s and %s"
+                           % (tuple(x.shape), tuple(weight.shape)))
+    return _Conv2dFn.apply(x, weight, bias, _pair(stride, "stride"), _pair(padding, "padding"), bool(relu))
+
+
+def _refusal(m):
+    """Why the library cannot run this nn.Conv2d's configuration, or None."""
+    if tuple(m.dilation) != (1, 1):
+        return "dilation %r (only 1 is built)" % (tuple(m.dilation),)
+    if m.groups != 1:
+        return "groups = %d (only 1 is built)" % m.groups
+    if m.padding_mode != 'zeros':
+        return "padding_mode %r (only 'zeros' is built)" % m.padding_mode
+    if isinstance(m.padding, str):
+        return "string padding %r" % m.padding
+    if m.stride[0] != m.stride[1] or m.padding[0] != m.padding[1]:
+        return "stride / padding differ between the axes"
+    if m.in_channels % 4:
+        return "in_channels = %d is not a multiple of 4" % m.in_channels
+    kh, kw = m.kernel_size
+    if not (1 <= kh <= 7 and 1 <= kw <= 7 and 1 <= m.stride[0] <= 4 and m.padding[0] < min(kh, kw)):
+        return "geometry outside kernel 1..7, stride 1..4, padding < kernel"
+    return None
+
+
+class Conv2d(nn.Conv2d):
+    """``nn.Conv2d`` whose forward and backward run on the library (``conv2d``).  Constructor, parameters, initial values,
+    ``state_dict`` and ``repr`` are ``nn.Conv2d``'s; ``relu = True`` fuses a following ReLU into the layer."""
+    relu = False
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        why = _refusal(self)
+        if why:
+            raise NotImplementedError("centerpose_amd.conv.Conv2d: " + why)
+
+    def forward(self, input):
+        return conv2d(input, self.weight, self.bias, self.stride[0], self.padding[0], self.relu)
+
+
+def use_hip_convs(module):
+    """Re-class every eligible ``nn.Conv2d`` under ``module`` (itself included) to ``Conv2d`` in place: the Parameter objects, the
+    module names and the state-dict keys stay as they are.  Returns ``(converted, skipped)``: the converted modules' names and
+    ``{name: reason}`` for the convolutions left alone (groups, dilation, ``in_channels % 4``, transposed or subclassed
+    convolutions).  Modules that already are ``Conv2d`` appear in neither."""
+    converted, skipped = [], {}
+    for name, m in module.named_modules():
+        if isinstance(m, Conv2d):
+            continue
+        if isinstance(m, nn.ConvTranspose2d):
+            skipped[name] = "ConvTranspose2d is not built"
+        elif type(m) is nn.Conv2d:
+            why = _refusal(m)
+            if why:
+                skipped[name] = why
+            else:
+                m.__class__ = Conv2d
+                converted.append(name)
+        elif isinstance(m, nn.Conv2d):
+            skipped[name] = "subclass %s of nn.Conv2d keeps its own forward" % type(m).__name__
+    return converted, skipped

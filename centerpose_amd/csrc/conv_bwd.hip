@@ -1,0 +1,537 @@
+// Backward of the ordinary convolution (cp_conv2d_backward_nhwc): autograd's gradients of out = conv2d(x, w) + bias, dilation 1,
+// groups 1, on the forward's layouts (x [B,H,W,Cin] NHWC, w [Cout,Cin,KH,KW], grad_out [B,Ho,Wo,Cout] NHWC).  It replaces
+// torch.nn.Conv2d's backward in pose_dla_dcn.py:48-62 (BasicBlock), the Root / project 1x1s and DCNv2/dcn_v2.py:118-128
+// (conv_offset_mask).  Float32 arithmetic only; every sum has a fixed order; no atomics.
+//
+// On the caller's stream:
+//   0. stage    (stage_kernel) gs[q][CoP] = grad_out[q][co] * (y[q][co] > 0), zero in the pad lanes co >= Cout, CoP = Cout
+//               rounded up to 32 on the MFMA path; the same pass leaves per-slab column sums, which bias_reduce_kernel adds in
+//               a fixed order into grad_bias.  Skipped when there is nothing to gate, pad or sum (grad_out is then read in place).
+//   1. wgrad    MFMA path: slab[s][co][k] = sum over the output rows of slab s of gs[q][co] * x[q * stride + tap - pad][c],
+//               k = tap * Cin + c (wgrad_kernel: v_mfma_f32_32x32x2_f32 with K = output pixels, heads_bwd.hip's wgrad0_kernel
+//               generalised over kernel size and stride); wgrad_reduce_kernel sums the slabs in a fixed order into the PyTorch
+//               layout.  Generic path: one thread per weight element and slab (wgrad_generic_kernel), the same reduction.
+//   2. dgrad    stride 1, MFMA path: the exact-f32 implicit GEMM of igemm.hip on gs with the taps mirrored and the channel
+//               roles swapped (pack_dgrad_kernel).  Stride 2, MFMA path: dgrad_s2_kernel, one dense contraction per input
+//               pixel parity class (deconv16.hip's sub-pixel form), written straight into the interleaved grad_x.  Generic
+//               path: a gather per grad_x element (dgrad_generic_kernel).  Not launched when the caller passes no grad_x.
+#include "igemm_common.h"
+
+#include <algorithm>
+#include <cstring>
+
+namespace {
+
+// gs[q][c] (c < CoP) = gated grad_out, zero for c >= Cout, when `gs` is given; part[slab][c] = the slab's column sums when
+// `part` is given.  A workgroup owns `slab_px` pixels (blockIdx.x) and CT channels (blockIdx.y; CT a power of two <= 64);
+// thread = (pixel lane, channel), so a wave reads whole rows.  Sums: pixels ascending per pixel lane, then the pixel lanes in
+// index order.
+__global__ __launch_bounds__(256) void stage_kernel(const float* __restrict__ go, const float* __restrict__ y,
+                                                    float* __restrict__ gs, float* __restrict__ part, int Q, int Cout, int CoP,
+                                                    int CT, int slab_px) {
+    __shared__ float red[256];
+    const int PL = 256 / CT, cl = threadIdx.x % CT, pl = threadIdx.x / CT;
+    const int q_beg = blockIdx.x * slab_px, q_end = min(Q, q_beg + slab_px);
+    const int c = blockIdx.y * CT + cl;
+    const bool cv = c < Cout, cw = gs && c < CoP;
+    float sum = 0.f;
+#pragma unroll 4
+    for (int q = q_beg + pl; q < q_end; q += PL) {
+        const size_t src = cv ? (size_t)q * Cout + c : 0;
+        float v = go[src];
+        if (y) v = y[src] > 0.f ? v : 0.f;
+        v = cv ? v : 0.f;
+        if (cw) gs[(size_t)q * CoP + c] = v;
+        sum += v;
+    }
+    if (!part) return;
+    red[threadIdx.x] = sum;
+    __syncthreads();
+    if (pl == 0 && c < CoP) {
+        float t = red[cl];
+        for (int j = 1; j < PL; ++j) t += red[j * CT + cl];
+        part[(size_t)blockIdx.x * CoP + c] = t;
+    }
+}
+
+// Slab sums in a fixed two-level order: a workgroup is 32 elements x 8 slab lanes; lane l adds the slabs l, l + 8, ... in
+// ascending order, then the eight lanes are added in lane order (a serial walk over up to 512 slabs is one long chain of
+// dependent adds behind strided loads).
+// gb[c] = the slabs' partials
+__global__ __launch_bounds__(256) void bias_reduce_kernel(const float* __restrict__ part, float* __restrict__ gb, int nslab, int Cout,
+                                                          int CoP) {
+    __shared__ float red[256];
+    const int el = threadIdx.x & 31, sl = threadIdx.x >> 5, c = blockIdx.x * 32 + el;
+    float v = 0.f;
+    if (c < Cout)
+        for (int s = sl; s < nslab; s += 8) v += part[(size_t)s * CoP + c];
+    red[threadIdx.x] = v;
+    __syncthreads();
+    if (sl == 0 && c < Cout) {
+        float t = red[el];
+        for (int j = 1; j < 8; ++j) t += red[j * 32 + el];
+        gb[c] = t;
+    }
+}
+
+// slab[s][co][k] over the output rows [s * rows_per_slab, ...): D[co][k] with K = output pixels, two per MFMA step (lane half
+// = pixel parity along x), eight steps' operands requested at a time.  A[co][q] = gs[q][h0 + lane & 31] (a 128-byte line per
+// half), B[q][k] = x[q * stride + tap - pad][c0 + lane & 31] (likewise: a k tile of 32 stays inside one tap because
+// Cin % 32 == 0); out-of-image taps and the ragged end of a row are zeros by select, never by a branch around the load.  A
+// wave owns NH co tiles x 2 k tiles; the four waves of a workgroup take neighbouring k tile pairs of the same co tiles.
+template <int NH>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void wgrad_kernel(
+    const float* __restrict__ gs, const float* __restrict__ x, float* __restrict__ slab, int rows, int Ho, int Wo, int H, int W,
+    int Cin, int CoP, int KW, int taps, int stride, int pad, int rows_per_slab) {
+    constexpr int WU = 8;
+    const int TC = taps * Cin, KT = TC / 32, KJ = (KT + 1) / 2;
+    const int lane = threadIdx.x & 63, r = lane & 31, hh = lane >> 5;
+    const int job = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+    const int hg = job / KJ, kj = job - hg * KJ;
+    if (hg * 32 * NH >= CoP) return;
+    const int h0 = hg * 32 * NH;
+    int dy[2], dx[2], c0[2];
+    bool kv[2];
+#pragma unroll
+    for (int n = 0; n < 2; ++n) {
+        const int kt = kj * 2 + n;
+        kv[n] = kt < KT;
+        const int k0 = kv[n] ? kt * 32 : 0, tap = k0 / Cin;
+        c0[n] = k0 - tap * Cin;
+        dy[n] = tap / KW - pad;
+        dx[n] = tap - (tap / KW) * KW - pad;
+    }
+    f32x16 acc[NH][2];
+#pragma unroll
+    for (int t = 0; t < NH; ++t)
+#pragma unroll
+        for (int n = 0; n < 2; ++n)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[t][n][e] = 0.f;
+    const int row_beg = blockIdx.z * rows_per_slab, row_end = min(rows, row_beg + rows_per_slab);
+    for (int row = row_beg; row < row_end; ++row) {
+        const int b = row / Ho, oy = row - b * Ho;
+        const float* arow = gs + (size_t)row * Wo * CoP + h0 + r;
+        const float* brow[2];
+        bool yv[2];
+#pragma unroll
+        for (int n = 0; n < 2; ++n) {
+            const int iy = oy * stride + dy[n];
+            yv[n] = kv[n] && (unsigned)iy < (unsigned)H;
+            brow[n] = x + ((size_t)b * H + (yv[n] ? iy : 0)) * W * Cin + c0[n] + r;
+        }
+        // two pixels per step, WU steps per chunk: the chunk's operands are all requested before its first MFMA is issued, so
+        // one memory round trip covers WU steps (steps past the row's end: clamped addresses, zeros)
+        auto load = [&](int x0, float (&a)[NH], float (&bq)[2]) {
+            const int ox = x0 + hh;
+            const bool xv = ox < Wo;
+            const int xc = xv ? ox : Wo - 1;
+#pragma unroll
+            for (int t = 0; t < NH; ++t) {
+                const float v = arow[(size_t)xc * CoP + 32 * t];
+                a[t] = xv ? v : 0.f;
+            }
+#pragma unroll
+            for (int n = 0; n < 2; ++n) {
+                const int ix = ox * stride + dx[n];
+                const bool ok = xv && yv[n] && (unsigned)ix < (unsigned)W;
+                const float v = brow[n][(size_t)(ok ? ix : 0) * Cin];
+                bq[n] = ok ? v : 0.f;
+            }
+        };
+        for (int x0 = 0; x0 < Wo; x0 += 2 * WU) {
+            float a[WU][NH], bq[WU][2];
+#pragma unroll
+            for (int u = 0; u < WU; ++u) load(x0 + 2 * u, a[u], bq[u]);
+#pragma unroll
+            for (int u = 0; u < WU; ++u)
+#pragma unroll
+                for (int t = 0; t < NH; ++t)
+#pragma unroll
+                    for (int n = 0; n < 2; ++n)
+                        acc[t][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u][t], bq[u][n], acc[t][n], 0, 0, 0);
+        }
+    }
+    float* out = slab + (size_t)blockIdx.z * CoP * TC;
+#pragma unroll
+    for (int t = 0; t < NH; ++t)
+#pragma unroll
+        for (int n = 0; n < 2; ++n) {
+            if (!kv[n]) continue;
+            const int k = (kj * 2 + n) * 32 + r;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int h = h0 + 32 * t + (e & 3) + 8 * (e >> 2) + 4 * hh;
+                out[(size_t)h * TC + k] = acc[t][n][e];
+            }
+        }
+}
+
+// grad_w[co][c][tap] = the slabs [co][tap * Cin + c] (co < Cout of CoP rows), summed in bias_reduce_kernel's two-level order;
+// threads walk the slabs' own element order (whole 128-byte lines per slab) and scatter the one write
+__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ slab, float* __restrict__ gw, int nslab, int Cout,
+                                                           int CoP, int Cin, int taps) {
+    __shared__ float red[256];
+    const size_t TC = (size_t)taps * Cin, n = (size_t)Cout * TC, ss = (size_t)CoP * TC;
+    const int el = threadIdx.x & 31, sl = threadIdx.x >> 5;
+    for (size_t base = (size_t)blockIdx.x * 32; base < n; base += (size_t)gridDim.x * 32) {  // (uniform per workgroup)
+        const size_t i = base + el;
+        float v = 0.f;
+        if (i < n)
+            for (int s = sl; s < nslab; s += 8) v += slab[(size_t)s * ss + i];
+        red[threadIdx.x] = v;
+        __syncthreads();
+        if (sl == 0 && i < n) {
+            float t = red[el];
+            for (int j = 1; j < 8; ++j) t += red[j * 32 + el];
+            const size_t h = i / TC;
+            const int k = (int)(i - h * TC), tap = k / Cin, c = k - tap * Cin;
+            gw[(h * Cin + c) * taps + tap] = t;
+        }
+        __syncthreads();
+    }
+}
+
+// Generic weight gradient: slab[s][e], e = (co, c, tap) in the PyTorch order, over the output rows of slab s, pixels ascending
+__global__ void wgrad_generic_kernel(const float* __restrict__ gs, const float* __restrict__ x, float* __restrict__ slab, int rows,
+                                     int Ho, int Wo, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
+                                     int rows_per_slab) {
+    const int taps = KH * KW, n = Cout * Cin * taps;
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    const int co = e / (Cin * taps), rr = e - co * Cin * taps, c = rr / taps, t = rr - c * taps;
+    const int ky = t / KW, kx = t - ky * KW;
+    const int row_beg = blockIdx.y * rows_per_slab, row_end = min(rows, row_beg + rows_per_slab);
+    float v = 0.f;
+    for (int row = row_beg; row < row_end; ++row) {
+        const int b = row / Ho, oy = row - b * Ho, iy = oy * stride + ky - pad;
+        if ((unsigned)iy >= (unsigned)H) continue;
+        const float* xr = x + ((size_t)b * H + iy) * W * Cin + c;
+        const float* gr = gs + (size_t)row * Wo * Cout + co;
+        for (int ox = 0; ox < Wo; ++ox) {
+            const int ix = ox * stride + kx - pad;
+            if ((unsigned)ix < (unsigned)W) v = fmaf(gr[(size_t)ox * Cout], xr[(size_t)ix * Cin], v);
+        }
+    }
+    slab[(size_t)blockIdx.y * n + e] = v;
+}
+
+__global__ void slab_reduce_kernel(const float* __restrict__ slab, float* __restrict__ out, int nslab, int n) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    float v = 0.f;
+    for (int s = 0; s < nslab; ++s) v += slab[(size_t)s * n + e];
+    out[e] = v;
+}
+
+// Generic data gradient, gather form: one thread per grad_x element; taps in (ky, kx) order, output channels ascending
+__global__ void dgrad_generic_kernel(const float* __restrict__ gs, const float* __restrict__ w, float* __restrict__ gx, int B, int H,
+                                     int W, int Cin, int Cout, int Ho, int Wo, int KH, int KW, int stride, int pad) {
+    const size_t n = (size_t)B * H * W * Cin;
+    const int taps = KH * KW;
+    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
+        const int c = (int)(e % Cin);
+        const size_t px = e / Cin;
+        const int ix = (int)(px % W), iy = (int)((px / W) % H), b = (int)(px / ((size_t)W * H));
+        float v = 0.f;
+        for (int ky = 0; ky < KH; ++ky) {
+            const int ty = iy + pad - ky;
+            if (ty < 0 || ty % stride) continue;
+            const int oy = ty / stride;
+            if (oy >= Ho) continue;
+            for (int kx = 0; kx < KW; ++kx) {
+                const int tx = ix + pad - kx;
+                if (tx < 0 || tx % stride) continue;
+                const int ox = tx / stride;
+                if (ox >= Wo) continue;
+                const float* gr = gs + (((size_t)b * Ho + oy) * Wo + ox) * Cout;
+                const float* wr = w + (size_t)c * taps + ky * KW + kx;
+                for (int co = 0; co < Cout; ++co) v = fmaf(gr[co], wr[(size_t)co * Cin * taps], v);
+            }
+        }
+        gx[e] = v;
+    }
+}
+
+// Stride-1 data gradient operand: wB[(taps - 1 - tap) * CoP + co][c] = w[co][c][tap] (buffer pre-zeroed: pad rows co >= Cout and
+// pad columns c >= Cin stay zero): the data gradient is the K x K / pad K/2 convolution of grad_out with the taps mirrored and
+// the channel roles swapped (1x1: one tap, its own mirror)
+__global__ void pack_dgrad_kernel(const float* __restrict__ w, float* __restrict__ wB, int Cout, int CoP, int Cin, int taps, int cpad) {
+    const size_t n = (size_t)Cout * Cin * taps;
+    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
+        const int co = (int)(e / ((size_t)Cin * taps));
+        const int rr = (int)(e - (size_t)co * Cin * taps), c = rr / taps, t = rr - c * taps;
+        wB[((size_t)(taps - 1 - t) * CoP + co) * cpad + c] = w[e];
+    }
+}
+
+// Stride-2 data gradient operand: wT[tap][co][c] = w[co][c][tap] (pre-zeroed: pad rows stay zero)
+__global__ void pack_dgrad_s2_kernel(const float* __restrict__ w, float* __restrict__ wT, int Cout, int CoP, int Cin, int taps) {
+    const size_t n = (size_t)Cout * Cin * taps;
+    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
+        const int co = (int)(e / ((size_t)Cin * taps));
+        const int rr = (int)(e - (size_t)co * Cin * taps), c = rr / taps, t = rr - c * taps;
+        wT[((size_t)t * CoP + co) * Cin + c] = w[e];
+    }
+}
+
+// Stride-2 data gradient in sub-pixel form.  blockIdx.y = input pixel parity class (py, px): its pixels (2 jy + py, 2 jx + px)
+// receive only the taps with ky = py + pad, kx = px + pad (mod 2), each from the grad_out pixel (jy + (py + pad - ky) / 2,
+// jx + (px + pad - kx) / 2) -- for 3x3 / pad 1 that is 1, 2, 2 and 4 taps, nine in all, so no zero-inserted work; for 1x1 the
+// even / even class gets the contraction and the other three write zero lines.  Per class a dense GEMM D[pixel][c] with
+// K = (taps of the class) x CoP: a wave owns 2 x 32 class pixels and NT x 32 input channels.  A[pixel][k]: a lane reads 16
+// bytes of its pixel's gs row (lane half = which four of eight k), B[k][c] = wT[tap][k][n0 + lane & 31]: a 128-byte line per
+// half; four MFMAs pair k = j with k = 4 + j.  Halo pixels and the ragged last tile are zeros by select; the tap list is
+// wave-uniform.  The results go straight into the interleaved NHWC grad_x.
+template <int NT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void dgrad_s2_kernel(
+    const float* __restrict__ gs, const float* __restrict__ wT, float* __restrict__ gx, int B, int H, int W, int Cin, int CoP,
+    int Ho, int Wo, int KK, int pad) {
+    constexpr int DU = NT == 4 ? 2 : 4;
+    __shared__ int opix[4][64];
+    const int lane = threadIdx.x & 63, r = lane & 31, hh = lane >> 5;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int py = blockIdx.y >> 1, px = blockIdx.y & 1;
+    const int Hc = (H - py + 1) >> 1, Wc = (W - px + 1) >> 1, M = B * Hc * Wc;  // (H - py + 1) / 2 pixels of this parity
+    const int NG = Cin / (32 * NT);
+    const int job = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wv);
+    const int mt = job / NG, ng = job - mt * NG;
+    const bool active = mt * 64 < M;  // wave-uniform
+    const int n0 = ng * 32 * NT;
+    // this lane's two class pixels (A rows r of the two M tiles)
+    int pb[2], pjy[2], pjx[2];
+    bool pv[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int m = mt * 64 + i * 32 + r;
+        pv[i] = active && m < M;
+        const int mc = pv[i] ? m : 0, hw = max(Hc * Wc, 1), wc = max(Wc, 1);
+        pb[i] = mc / hw;
+        const int rem = mc - pb[i] * hw;
+        pjy[i] = rem / wc;
+        pjx[i] = rem - pjy[i] * wc;
+        // the pixel's offset in grad_x (elements / Cin), shared with the lanes that store its row
+        if (hh == 0) opix[wv][i * 32 + r] = pv[i] ? (pb[i] * H + 2 * pjy[i] + py) * W + 2 * pjx[i] + px : -1;
+    }
+    __syncthreads();
+    if (!active) return;
+    f32x16 acc[2][NT];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < NT; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    for (int ky = 0; ky < KK; ++ky) {
+        if ((py + pad - ky) & 1) continue;  // wave-uniform
+        const int oyo = (py + pad - ky) >> 1;
+        for (int kx = 0; kx < KK; ++kx) {
+            if ((px + pad - kx) & 1) continue;
+            const int oxo = (px + pad - kx) >> 1;
+            const float* ap[2];
+            bool ok[2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const int oy = pjy[i] + oyo, ox = pjx[i] + oxo;
+                ok[i] = pv[i] && (unsigned)oy < (unsigned)Ho && (unsigned)ox < (unsigned)Wo;
+                ap[i] = gs + (ok[i] ? (((size_t)pb[i] * Ho + oy) * Wo + ox) * CoP : 0) + 4 * hh;
+            }
+            const float* bp = wT + (size_t)(ky * KK + kx) * CoP * Cin + (size_t)(4 * hh) * Cin + n0 + r;
+            auto load = [&](int k0, float4 (&a)[2], float (&bq)[4][NT]) {
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    const float4 v = ld4(ap[i] + k0);
+                    a[i] = ok[i] ? v : zero4();
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) bq[j][t] = bp[(size_t)(k0 + j) * Cin + 32 * t];
+            };
+            // DU steps of eight k per chunk, all requested before the chunk's first MFMA (CoP % 32 == 0: whole chunks)
+            for (int k0 = 0; k0 < CoP; k0 += 8 * DU) {
+                float4 a[DU][2];
+                float bq[DU][4][NT];
+#pragma unroll
+                for (int u = 0; u < DU; ++u) load(k0 + 8 * u, a[u], bq[u]);
+#pragma unroll
+                for (int u = 0; u < DU; ++u) {
+                    const float av[2][4] = {{a[u][0].x, a[u][0].y, a[u][0].z, a[u][0].w}, {a[u][1].x, a[u][1].y, a[u][1].z, a[u][1].w}};
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+#pragma unroll
+                        for (int i = 0; i < 2; ++i)
+#pragma unroll
+                            for (int t = 0; t < NT; ++t)
+                                acc[i][t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i][j], bq[u][j][t], acc[i][t], 0, 0, 0);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const int o = opix[wv][i * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh];
+            if (o < 0) continue;
+            float* dst = gx + (size_t)o * Cin + n0 + r;
+#pragma unroll
+            for (int t = 0; t < NT; ++t) dst[32 * t] = acc[i][t][e];
+        }
+}
+
+inline size_t al(size_t x) { return (x + 255) / 256 * 256; }
+inline bool ok() { return hipGetLastError() == hipSuccess; }
+inline int nh_of(int c) { return c % 128 == 0 ? 4 : c % 64 == 0 ? 2 : 1; }
+
+struct Plan {
+    bool mfma;
+    int Ho, Wo, CoP, cpad, taps;
+    int st_ct, st_px, st_slabs;      // stage_kernel: channel lanes, pixels per slab, slabs
+    int wg_rows, wg_slabs, wg_jobs;  // weight gradient: output rows per slab, slabs, wave jobs (MFMA path)
+    size_t gs, part, slab, wB, wB_bytes, total;
+};
+
+Plan plan(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, bool need_gx) {
+    Plan P;
+    P.mfma = cp_conv_backward_mfma(Cin, KH, KW, stride, pad);
+    P.Ho = (H + 2 * pad - KH) / stride + 1;
+    P.Wo = (W + 2 * pad - KW) / stride + 1;
+    P.taps = KH * KW;
+    P.CoP = P.mfma ? (Cout + 31) / 32 * 32 : Cout;
+    P.cpad = (Cin + cp_conv_tile_n(Cin) - 1) / cp_conv_tile_n(Cin) * cp_conv_tile_n(Cin);
+    const size_t Q = (size_t)B * P.Ho * P.Wo, rows = (size_t)B * P.Ho;
+    int ct = 1;
+    while (ct < P.CoP && ct < 64) ct <<= 1;
+    P.st_ct = ct;
+    const size_t ss = std::max<size_t>(1, std::min<size_t>(512, (Q + 63) / 64));
+    P.st_px = (int)((Q + ss - 1) / ss);
+    P.st_slabs = (int)((Q + P.st_px - 1) / P.st_px);
+    const size_t wbytes = (size_t)P.CoP * P.taps * Cin * 4;
+    size_t ns;
+    if (P.mfma) {  // about two waves per SIMD; slabs of whole output rows, at most 64 MiB of them
+        const int KT = P.taps * Cin / 32;
+        P.wg_jobs = (P.CoP / (32 * nh_of(P.CoP))) * ((KT + 1) / 2);
+        ns = std::min<size_t>(512, (2048 + P.wg_jobs - 1) / P.wg_jobs);
+    } else {
+        P.wg_jobs = 0;
+        ns = 64;
+    }
+    ns = std::min(ns, std::max<size_t>(1, ((size_t)64 << 20) / wbytes));
+    ns = std::max<size_t>(1, std::min(ns, rows));
+    P.wg_rows = (int)((rows + ns - 1) / ns);
+    P.wg_slabs = (int)((rows + P.wg_rows - 1) / P.wg_rows);
+    P.wB_bytes = !need_gx || !P.mfma ? 0 : stride == 1 ? (size_t)P.taps * P.CoP * P.cpad * 4 : wbytes;
+    size_t o = 0;
+    P.gs = o;
+    o += al(Q * P.CoP * 4);
+    P.part = o;
+    o += al(ss * P.CoP * 4);  // (the slab counts' upper bounds: monotone in B)
+    P.slab = o;
+    o += al(ns * wbytes);
+    P.wB = o;
+    o += al(P.wB_bytes);
+    P.total = o;
+    return P;
+}
+
+}  // namespace
+
+bool cp_conv_backward_mfma(int Cin, int KH, int KW, int stride, int pad) {
+    return KH == KW && (KH == 1 || KH == 3) && (stride == 1 || stride == 2) && pad == KH / 2 && Cin % 32 == 0;
+}
+
+size_t cp_conv_backward_ws_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int need_grad_x) {
+    return plan(B, H, W, Cin, Cout, KH, KW, stride, pad, need_grad_x != 0).total;
+}
+
+int cp_launch_conv_backward(hipStream_t s, const ConvBwdArgs& a, void* ws) {
+    const Plan P = plan(a.B, a.H, a.W, a.Cin, a.Cout, a.KH, a.KW, a.stride, a.pad, a.gx != nullptr);
+    char* w8 = (char*)ws;
+    float* gsb = (float*)(w8 + P.gs);
+    float* part = (float*)(w8 + P.part);
+    float* slab = (float*)(w8 + P.slab);
+    float* wB = (float*)(w8 + P.wB);
+    const int B = a.B, H = a.H, W = a.W, Cin = a.Cin, Cout = a.Cout, Ho = P.Ho, Wo = P.Wo, CoP = P.CoP, taps = P.taps;
+    const int Q = B * Ho * Wo, rows = B * Ho;
+    // 0. stage: gate, pad, bias partials
+    const bool staged = a.y || CoP != Cout;
+    const float* gs = staged ? gsb : a.go;
+    if (staged || a.gb) {
+        hipLaunchKernelGGL(stage_kernel, dim3(P.st_slabs, (CoP + P.st_ct - 1) / P.st_ct), dim3(256), 0, s, a.go, a.y, staged ? gsb : (float*)nullptr,
+                           a.gb ? part : (float*)nullptr, Q, Cout, CoP, P.st_ct, P.st_px);
+        if (!ok()) return CP_ERR_LAUNCH;
+        if (a.gb) {
+            hipLaunchKernelGGL(bias_reduce_kernel, dim3((Cout + 31) / 32), dim3(256), 0, s, (const float*)part, a.gb,
+                               P.st_slabs, Cout, CoP);
+            if (!ok()) return CP_ERR_LAUNCH;
+        }
+    }
+    // 1. grad_w
+    if (P.mfma) {
+        const dim3 wg((P.wg_jobs + 3) / 4, 1, P.wg_slabs);
+#define CP_WGRAD(NH)                                                                                                        \
+    hipLaunchKernelGGL(wgrad_kernel<NH>, wg, dim3(256), 0, s, gs, a.x, slab, rows, Ho, Wo, H, W, Cin, CoP, a.KW, taps, a.stride, \
+                       a.pad, P.wg_rows)
+        switch (nh_of(CoP)) {
+            case 4: CP_WGRAD(4); break;
+            case 2: CP_WGRAD(2); break;
+            default: CP_WGRAD(1);
+        }
+#undef CP_WGRAD
+        if (!ok()) return CP_ERR_LAUNCH;
+        const size_t rg = std::min<size_t>(((size_t)Cout * taps * Cin + 31) / 32, 8192);
+        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)rg), dim3(256), 0, s, (const float*)slab, a.gw, P.wg_slabs, Cout, CoP,
+                           Cin, taps);
+        if (!ok()) return CP_ERR_LAUNCH;
+    } else {
+        const int n = Cout * Cin * taps;
+        hipLaunchKernelGGL(wgrad_generic_kernel, dim3((n + 255) / 256, P.wg_slabs), dim3(256), 0, s, gs, a.x, slab, rows, Ho, Wo, H,
+                           W, Cin, Cout, a.KH, a.KW, a.stride, a.pad, P.wg_rows);
+        if (!ok()) return CP_ERR_LAUNCH;
+        hipLaunchKernelGGL(slab_reduce_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (const float*)slab, a.gw, P.wg_slabs, n);
+        if (!ok()) return CP_ERR_LAUNCH;
+    }
+    // 2. grad_x
+    if (!a.gx) return CP_OK;
+    if (!P.mfma) {
+        const size_t n = (size_t)B * H * W * Cin;
+        hipLaunchKernelGGL(dgrad_generic_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 65536)), dim3(256), 0, s, gs, a.w,
+                           a.gx, B, H, W, Cin, Cout, Ho, Wo, a.KH, a.KW, a.stride, a.pad);
+        return ok() ? CP_OK : CP_ERR_LAUNCH;
+    }
+    if (hipMemsetAsync(wB, 0, P.wB_bytes, s) != hipSuccess) return CP_ERR_LAUNCH;
+    if (a.stride == 1) {
+        hipLaunchKernelGGL(pack_dgrad_kernel, dim3(256), dim3(256), 0, s, a.w, wB, Cout, CoP, Cin, taps, P.cpad);
+        if (!ok()) return CP_ERR_LAUNCH;
+        ConvParams d;
+        memset(&d, 0, sizeof(d));
+        d.nsrc = 1;
+        d.src[0] = gs;
+        d.src_c[0] = d.Cin = CoP;
+        d.B = B, d.H = d.Ho = H, d.W = d.Wo = W;  // (stride 1, pad K / 2: the output grid is the input grid)
+        d.KH = a.KH, d.KW = a.KW, d.stride = 1, d.pad = a.pad;
+        d.K = d.Kpad = taps * CoP;
+        d.wp = wB;
+        d.Cout = Cin, d.CoutPad = P.cpad;
+        d.act = CP_ACT_NONE;
+        d.out = a.gx;
+        d.store = CP_STORE_NHWC;
+        d.ldo = Cin;
+        return cp_launch_conv(d, s);
+    }
+    hipLaunchKernelGGL(pack_dgrad_s2_kernel, dim3(256), dim3(256), 0, s, a.w, wB, Cout, CoP, Cin, taps);
+    if (!ok()) return CP_ERR_LAUNCH;
+    const int M0 = B * ((H + 1) / 2) * ((W + 1) / 2);  // the even / even class has the most pixels
+    const int nt = nh_of(Cin), jobs = ((M0 + 63) / 64) * (Cin / (32 * nt));
+    const dim3 dg((jobs + 3) / 4, 4);
+#define CP_DGRAD(NT) \
+    hipLaunchKernelGGL(dgrad_s2_kernel<NT>, dg, dim3(256), 0, s, gs, (const float*)wB, a.gx, B, H, W, Cin, CoP, Ho, Wo, a.KH, a.pad)
+    switch (nt) {
+        case 4: CP_DGRAD(4); break;
+        case 2: CP_DGRAD(2); break;
+        default: CP_DGRAD(1);
+    }
+#undef CP_DGRAD
+    return ok() ? CP_OK : CP_ERR_LAUNCH;
+}

@@ -435,6 +435,16 @@ int cp_launch_pose_heads_backward(hipStream_t s, const PoseHeadsArgs& a, const f
                                   float* const* grad_b0, float* const* grad_w1, float* const* grad_b1, float* grad_feat,
                                   void* ws);
 
+// ---- Conv2d backward (conv_bwd.hip): gradients of out = conv2d(x, w) + bias on the forward's NHWC layouts, float32 ----
+struct ConvBwdArgs {
+    const float *x, *w, *y, *go;  // y (the activated forward output) or nullptr: grad_out is gated by y > 0
+    float *gx, *gw, *gb;          // gx / gb nullptr: not computed
+    int B, H, W, Cin, Cout, KH, KW, stride, pad;
+};
+bool cp_conv_backward_mfma(int Cin, int KH, int KW, int stride, int pad);  // the geometry takes the MFMA kernels
+size_t cp_conv_backward_ws_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int need_grad_x);
+int cp_launch_conv_backward(hipStream_t s, const ConvBwdArgs& a, void* ws);
+
 // ---- ObjectPoseLoss (pose_loss.hip; numerics in pose_loss_common.h) ----
 struct cp_pose_loss_desc;
 const char* cp_pose_loss_check(const cp_pose_loss_desc* d);                           // nullptr: accepted

@@ -1,5 +1,6 @@
 // The stand-alone operators of the C ABI (include/centerpose_hip.h): single layers on caller tensors, outside any cp_model
-// -- cp_conv2d_nhwc, cp_conv_transpose2d_nhwc, cp_dcnv2_forward / cp_dcnv2_backward, cp_pose_heads_forward / _backward.
+// -- cp_conv2d_nhwc / cp_conv2d_backward_nhwc, cp_conv_transpose2d_nhwc, cp_dcnv2_forward / cp_dcnv2_backward,
+// cp_pose_heads_forward / _backward.
 // Each packs its PyTorch-layout weights into a caller-provided workspace on every call and then launches the same kernels as
 // the engine.
 #include "engine_model.h"
@@ -199,6 +200,20 @@ const char* heads_shape_error(int B, int H, int W, int Cin, int hid, int n, cons
     if (px * Cin >= lim || px * mx >= lim || (long long)H * W * hid >= lim || (long long)hid * Cin * 9 >= lim)
         return "pose_heads: a tensor has 2^31 elements or more";
     *cmax = mx;
+    return nullptr;
+}
+
+// Conv2d backward: shape checks shared by the call and its workspace query, kernels in conv_bwd.hip
+const char* conv_bwd_shape_error(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
+    if (B < 1 || H < 1 || W < 1 || Cout < 1) return "conv2d_backward: B, H, W and Cout must be at least 1";
+    if (Cin < 4 || Cin % 4) return "conv2d_backward: Cin must be a positive multiple of 4";
+    if (KH < 1 || KH > 7 || KW < 1 || KW > 7 || stride < 1 || stride > 4 || pad < 0 || pad >= KH || pad >= KW)
+        return "conv2d_backward: unsupported geometry (KH, KW in 1..7, stride in 1..4, 0 <= pad < K)";
+    if (H + 2 * pad < KH || W + 2 * pad < KW) return "conv2d_backward: empty output (kernel extent larger than the padded input)";
+    const long long ho = (H + 2 * pad - KH) / stride + 1, wo = (W + 2 * pad - KW) / stride + 1;
+    const long long lim = 0x7fffffffLL, cop = ((long long)Cout + 31) / 32 * 32;
+    if ((long long)B * H * W * Cin >= lim || (long long)B * ho * wo * cop >= lim || cop * Cin * KH * KW >= lim)
+        return "conv2d_backward: a tensor has 2^31 elements or more";
     return nullptr;
 }
 
@@ -424,6 +439,27 @@ int cp_conv2d_nhwc(cp_stream_t stream, const float* x, const float* w, const flo
         if (conv_params_f16(p, cw, &slot, true)) return cp_launch_conv16(p, s);
     }
     return cp_launch_conv(p, s);
+}
+
+size_t cp_conv2d_backward_workspace_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
+                                          int need_grad_x) {
+    if (const char* e = conv_bwd_shape_error(B, H, W, Cin, Cout, KH, KW, stride, pad)) {
+        fail(CP_ERR_INVALID, e);
+        return 0;
+    }
+    return cp_conv_backward_ws_bytes(B, H, W, Cin, Cout, KH, KW, stride, pad, need_grad_x);
+}
+
+int cp_conv2d_backward_nhwc(cp_stream_t stream, const float* x, const float* w, const float* y_or_null, const float* grad_out,
+                            float* grad_x_or_null, float* grad_w, float* grad_bias_or_null, int B, int H, int W, int Cin,
+                            int Cout, int KH, int KW, int stride, int pad, void* workspace, size_t workspace_bytes) {
+    if (const char* e = conv_bwd_shape_error(B, H, W, Cin, Cout, KH, KW, stride, pad)) return fail(CP_ERR_INVALID, e);
+    if (!x || !w || !grad_out || !grad_w || !workspace) return fail(CP_ERR_INVALID, "conv2d_backward: null argument");
+    if (workspace_bytes < cp_conv_backward_ws_bytes(B, H, W, Cin, Cout, KH, KW, stride, pad, grad_x_or_null != nullptr))
+        return fail(CP_ERR_INVALID, "conv2d_backward: workspace too small");
+    const ConvBwdArgs a{x, w, y_or_null, grad_out, grad_x_or_null, grad_w, grad_bias_or_null, B, H, W, Cin, Cout, KH, KW, stride, pad};
+    const int rc = cp_launch_conv_backward((hipStream_t)stream, a, workspace);
+    return rc == CP_OK ? CP_OK : fail(rc, "conv2d_backward: kernel launch failed");
 }
 
 size_t cp_dcnv2_backward_workspace_bytes(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw,

@@ -129,6 +129,8 @@ def lib():
          c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t)
     _sig(L.cp_conv2d_nhwc, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
          *([c_int] * 10), c_void_p, c_size_t)
+    _sig(L.cp_conv2d_backward_workspace_bytes, c_size_t, *([c_int] * 10))
+    _sig(L.cp_conv2d_backward_nhwc, c_int, *([c_void_p] * 8), *([c_int] * 9), c_void_p, c_size_t)
     _sig(L.cp_decode_workspace_bytes, c_size_t, c_int, c_int)
     _sig(L.cp_decode, c_int, c_void_p, c_int, c_int, c_int, *([c_void_p] * 11), c_int, c_int, c_int, ctypes.c_float,
          c_int, c_int, c_void_p, c_void_p, c_size_t)
@@ -225,7 +227,7 @@ def exported_symbols():
             "cp_model_heads_at_workspace_bytes", "cp_model_heads_at", "cp_decode_peaks_workspace_bytes", "cp_decode_peaks",
             "cp_decode_gathered", "cp_pose_heads_chunk_images", "cp_pose_heads_forward_workspace_bytes",
             "cp_pose_heads_forward", "cp_pose_heads_backward_workspace_bytes", "cp_pose_heads_backward",
-            "cp_model_features"]
+            "cp_model_features", "cp_conv2d_backward_workspace_bytes", "cp_conv2d_backward_nhwc"]
 
 
 def _check(rc, what):
@@ -458,6 +460,37 @@ def conv2d_nhwc(x, w, scale=None, shift=None, residual=None, stride=1, pad=0, ac
                           B, H, W, Cin, Cout, KH, KW, stride, pad, act, _ptr(ws), nbytes)
     _check(rc, "cp_conv2d_nhwc")
     return out
+
+
+def conv2d_backward(x, w, grad_out, stride=1, pad=0, y=None, need_x_grad=True, need_bias_grad=True):
+    """Gradients of ``conv2d_nhwc(x, w, shift=bias)`` (cp_conv2d_backward_nhwc): x [B,H,W,Cin] NHWC, w [Cout,Cin,KH,KW],
+    grad_out [B,Ho,Wo,Cout] NHWC -> (grad_x [B,H,W,Cin] | None, grad_w [Cout,Cin,KH,KW], grad_bias [Cout] | None).  ``y``: the
+    activated forward output when the layer ended in a ReLU (grad_out is gated by y > 0).  Float32 and bitwise reproducible."""
+    L = lib()
+    x, w, grad_out = _dev(x), _dev(w), _dev(grad_out)
+    y = _dev(y) if y is not None else None
+    if x.dim() != 4 or w.dim() != 4 or w.shape[1] != x.shape[3]:
+        raise RuntimeError("conv2d_backward: x must be [B,H,W,Cin] and w [Cout,Cin,KH,KW], got %s and %s"
+                           % (tuple(x.shape), tuple(w.shape)))
+    B, H, W, Cin = x.shape
+    Cout, _, KH, KW = w.shape
+    stride, pad = int(stride), int(pad)
+    nbytes = L.cp_conv2d_backward_workspace_bytes(B, H, W, Cin, Cout, KH, KW, stride, pad, int(bool(need_x_grad)))
+    if nbytes == 0:
+        raise RuntimeError("conv2d_backward: shape refused by the library (%s)" % L.cp_last_error().decode())
+    Ho = (H + 2 * pad - KH) // stride + 1
+    Wo = (W + 2 * pad - KW) // stride + 1
+    for name, t in (("grad_out", grad_out), ("y", y)):
+        if t is not None and tuple(t.shape) != (B, Ho, Wo, Cout):
+            raise RuntimeError("conv2d_backward: %s has shape %s, expected %s" % (name, tuple(t.shape), (B, Ho, Wo, Cout)))
+    grad_x = torch.empty_like(x) if need_x_grad else None
+    grad_w = torch.empty_like(w)
+    grad_b = torch.empty(Cout, device=x.device, dtype=torch.float32) if need_bias_grad else None
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    rc = L.cp_conv2d_backward_nhwc(_stream(), _ptr(x), _ptr(w), _ptr(y), _ptr(grad_out), _ptr(grad_x), _ptr(grad_w),
+                                   _ptr(grad_b), B, H, W, Cin, Cout, KH, KW, stride, pad, _ptr(ws), nbytes)
+    _check(rc, "cp_conv2d_backward_nhwc")
+    return grad_x, grad_w, grad_b
 
 
 def conv_transpose2d(x, w, scale=None, shift=None, act=0):

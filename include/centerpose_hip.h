@@ -291,6 +291,34 @@ int cp_conv2d_nhwc(cp_stream_t stream, const float* x, const float* w, const flo
                    const float* residual, float* out, int B, int H, int W, int Cin, int Cout, int KH, int KW,
                    int stride, int pad, int act, void* workspace, size_t workspace_bytes);
 
+/* ------------------------------------------------------------------------------------------
+ * Conv2d backward — replaces torch.nn.Conv2d's backward in models/networks/pose_dla_dcn.py:48-62 (BasicBlock's 3x3
+ *   pairs), the Root / project 1x1 layers, ResNet's 1x1 stride-2 down-samples and DCNv2/dcn_v2.py:118-128
+ *   (conv_offset_mask): autograd's gradients of out = conv2d(x, w) + bias with dilation 1 and groups 1.
+ * Layouts are cp_conv2d_nhwc's: x [B,H,W,Cin] NHWC, w [Cout,Cin,KH,KW] (PyTorch layout), grad_out [B,Ho,Wo,Cout] NHWC with
+ * Ho = (H + 2 pad - KH) / stride + 1 (Wo likewise).  Outputs, written (not accumulated): grad_w [Cout,Cin,KH,KW],
+ * grad_bias [Cout] (sums of grad_out over images and pixels) and grad_x [B,H,W,Cin] NHWC.  A NULL grad_x or grad_bias is
+ * not computed and not touched.  y (the ACTIVATED forward output, [B,Ho,Wo,Cout]) or NULL: when given, the layer was
+ * relu(conv + bias) and grad_out is gated by y > 0 wherever it is read.  BatchNorm scale / shift and residual inputs of the
+ * forward are not part of this operator: callers compose them.
+ * Arithmetic is float32 whatever cp_set_default_precision says; every sum has a fixed order and there are no atomics, so
+ * all outputs are bitwise reproducible call to call.
+ * MFMA path (v_mfma_f32_32x32x2_f32): KH == KW in {1, 3}, stride in {1, 2}, pad == KH / 2, Cin % 32 == 0, any H, W >= 1 and
+ * any Cout (grad_out is staged once into the workspace, zero-padded to a multiple of 32 channels: 27 is the case that
+ * matters).  Everything else with KH, KW in 1..7, stride in 1..4, 0 <= pad < min(KH, KW), Cin % 4 == 0 takes plain
+ * deterministic kernels that are correct, not fast.
+ * Refused with CP_ERR_INVALID and a cp_last_error() text before any launch (the query returns 0): a NULL pointer other
+ * than those named above, a workspace below the query, B / H / W / Cout < 1, Cin % 4 != 0, another geometry, an empty output
+ * grid, a tensor of 2^31 elements or more.  The query is host arithmetic; need_grad_x == 0 leaves out the data gradient's
+ * operands.  Launches on `stream`, never synchronises.
+ * ------------------------------------------------------------------------------------------ */
+size_t cp_conv2d_backward_workspace_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
+                                          int need_grad_x);
+int cp_conv2d_backward_nhwc(cp_stream_t stream, const float* x, const float* w, const float* y_or_null,
+                            const float* grad_out, float* grad_x_or_null, float* grad_w, float* grad_bias_or_null, int B,
+                            int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, void* workspace,
+                            size_t workspace_bytes);
+
 /* Dense ConvTranspose2d(Cin, Cout, kernel 4, stride 2, padding 1, bias=False) followed by an optional per-channel affine
  * and ReLU (resnet_dcn.py's deconv `up` layers with their BatchNorm): x [B,H,W,Cin] NHWC, w [Cin,Cout,4,4] (PyTorch
  * layout, DEVICE), scale/shift [Cout] or NULL, out [B,2H,2W,Cout] NHWC.  act: 0 none, 1 relu.  Cin % 32 == 0.
