@@ -199,6 +199,13 @@ struct ConvParams {
     // fuse_w2_inv[g * 64 + c].
     const int* row_index;
     int rows_per_image, row_index_stride;
+    // IDAUp's up-sample + add in the epilogue of the DCN that produces `add` (dcn16t.hip, cp_dcn16t_upadd_supported): the kernel
+    // writes u = act(...) + up(up_t) (upadd_common.h) to `out` and |max| of u to out_amax; its own output is never stored.
+    // up_t: NHWC [B, H / up_f, W / up_f, up_ld] with Cout valid channels, complete in memory before the launch; up_wt: the
+    // depth-wise kernels as [tap = ky * 2 up_f + kx][Cout].  up_t == nullptr: a plain launch.
+    const float* up_t;
+    const float* up_wt;
+    int up_ld, up_f;
 };
 
 int cp_launch_conv(const ConvParams& p, hipStream_t stream);
@@ -253,6 +260,7 @@ int cp_launch_frag16_repack(const void* w16, void* w16f, int CoutPad, int Kpad16
 // dcn16t.hip: dcn16p's gather written for three workgroups per CU (16-channel chunks, one gather set, two weight sets)
 #define CP_VARIANT_DCN16T 39
 bool cp_dcn16t_supported(const ConvParams& p);
+bool cp_dcn16t_upadd_supported(const ConvParams& p);  // ... with ConvParams::up_t (one 64-channel N tile, up_f 2 or 4)
 int cp_launch_dcn16t(const ConvParams& p, hipStream_t stream);
 #define CP_VARIANT_DCN16P 30
 #define CP_VARIANT_GN_FINAL 31

@@ -33,6 +33,7 @@
 #include <type_traits>
 
 #include "patch16_common.h"
+#include "upadd_common.h"
 
 namespace {
 
@@ -74,7 +75,8 @@ __device__ __forceinline__ int t_opaque(int v) {
 
 typedef float t_f32x2 __attribute__((ext_vector_type(2)));
 
-template <int NT>
+// UPADD: the epilogue adds IDAUp's up-sampled t (ConvParams::up_t) to the activated output and stores that sum instead (below)
+template <int NT, bool UPADD = false>
 __global__ __launch_bounds__(256, 3) void dcn16t_kernel(const ConvParams p, const int tiles_m, const int tiles_n) {
     typedef Frag<32> F;
     typedef F::acc_t acc_t;
@@ -424,6 +426,41 @@ __global__ __launch_bounds__(256, 3) void dcn16t_kernel(const ConvParams p, cons
         const int nb0 = tn * (32 * NT);  // first channel of this N tile (scalar)
         const bool relu = p.act == CP_ACT_RELU;
         float amax = 0.f;
+        // UPADD: u = act(...) + up(t) per 16-byte piece (upadd_common.h).  A lane's pixel, and with it its 2 x 2 taps of t and of the
+        // kernel, is the same for its eight channel quads: four byte offsets into t (a tap outside t: beyond the descriptor, zeros)
+        // and four into the weight table, + the quad's channel offset (scalar).  The table ([tap][64 channels], 4 KB for f = 2, 16 KB
+        // for f = 4) goes into the patch's LDS, which is dead once every wave has left the K loop; a tap's row is U_WSTR bytes so
+        // that the (tap, lane half) pairs of one ds_read_b128 spread over the banks.
+        constexpr int U_WSTR = 64 * 4 + 32;
+        __amdgpu_buffer_rsrc_t r_t = r_sc;
+        unsigned u_toff[2][2];
+        int u_woff[2][2];
+        if constexpr (UPADD) {
+            const int f = p.up_f, k = 2 * f, Ht = p.H / f, Wt = p.W / f, ntap = k * k;
+            static_assert(T_NPIX_ALL * T_PSTR >= 64 * U_WSTR, "the f = 4 table fits the patch");
+            const int t = wid * 64 + ln;  // (the thread id, rebuilt like the lane id: not held across the K loops)
+            __syncthreads();  // every wave is done with the patch
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {  // piece i of the table = (tap i / 16, channel quad i % 16)
+                const int i = t + 256 * r;
+                if (i < ntap * 16)
+                    *reinterpret_cast<float4*>(patch + (i >> 4) * U_WSTR + (i & 15) * 16) = reinterpret_cast<const float4*>(p.up_wt)[i];
+            }
+            r_t = make_rsrc(p.up_t, (unsigned)p.B * Ht * Wt * (unsigned)p.up_ld * 4u);
+            int ky0, kx0, iy0, ix0;
+            cp_upadd_axis(ty0 + 2 * wid + patch_perm_row(lc), f, &ky0, &iy0);
+            cp_upadd_axis(tx0 + patch_perm_col(lc), f, &kx0, &ix0);
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+#pragma unroll
+                for (int bb = 0; bb < 2; ++bb) {
+                    const int iy = iy0 - a, ix = ix0 - bb;
+                    const bool ok = (unsigned)iy < (unsigned)Ht && (unsigned)ix < (unsigned)Wt;
+                    u_toff[a][bb] = ok ? (unsigned)(((b * Ht + iy) * Wt + ix) * p.up_ld) * 4u + 16u * h4 : OOB_BASE;
+                    u_woff[a][bb] = ((ky0 + a * f) * k + kx0 + bb * f) * U_WSTR + 16 * h4;
+                }
+            __syncthreads();  // the table is in LDS
+        }
 #pragma unroll
         for (int j = 0; j < NT; ++j)
 #pragma unroll
@@ -436,6 +473,18 @@ __global__ __launch_bounds__(256, 3) void dcn16t_kernel(const ConvParams p, cons
                 if (relu) {
 #pragma unroll
                     for (int i = 0; i < 4; ++i) v[i] = fmaxf(v[i], 0.f);
+                }
+                if constexpr (UPADD) {
+                    float4 tv[2][2], wv[2][2];
+#pragma unroll
+                    for (int a = 0; a < 2; ++a)
+#pragma unroll
+                        for (int bb = 0; bb < 2; ++bb) {
+                            tv[a][bb] = t_ld4s(r_t, u_toff[a][bb], nsc);
+                            wv[a][bb] = *reinterpret_cast<const float4*>(patch + u_woff[a][bb] + (32 * j + 8 * g4) * 4);
+                        }
+                    const float4 u = cp_upadd_piece(tv, wv, make_float4(v[0], v[1], v[2], v[3]));
+                    v[0] = u.x; v[1] = u.y; v[2] = u.z; v[3] = u.w;
                 }
                 const int n0 = nb0 + 32 * j + 8 * g4 + 4 * h4;  // (Cout % 4 == 0: a quad is inside or outside)
                 const bool n_ok = n0 < p.Cout;
@@ -455,9 +504,18 @@ __global__ __launch_bounds__(256, 3) void dcn16t_kernel(const ConvParams p, cons
 // chunk count even
 bool cp_dcn16t_supported(const ConvParams& p) { return cp_dcn16s_supported(p); }
 
+// ... with the up-sample + add epilogue: one N tile that is the whole 64-channel pixel (the weight table in LDS is [tap][64], the
+// stored tensor is u itself: no channel offset), t with 64 valid channels per pixel at 1 / f of the resolution, 32-bit offsets
+bool cp_dcn16t_upadd_supported(const ConvParams& p) {
+    return cp_dcn16t_supported(p) && p.up_t && p.up_wt && (p.up_f == 2 || p.up_f == 4) && p.Cout == 64 && p.CoutPad == 64 &&
+           p.ldo == 64 && p.coff == 0 && p.up_ld >= 64 && p.up_ld % 4 == 0 && p.H % p.up_f == 0 && p.W % p.up_f == 0 &&
+           (size_t)p.B * (p.H / p.up_f) * (p.W / p.up_f) * p.up_ld * 4 < (size_t)0xf0000000u;
+}
+
 int cp_launch_dcn16t(const ConvParams& p, hipStream_t stream) {
-    if (!cp_dcn16t_supported(p)) return CP_ERR_INVALID;
+    if (!cp_dcn16t_supported(p) || (p.up_t && !cp_dcn16t_upadd_supported(p))) return CP_ERR_INVALID;
     const int tiles_m = p.B * (p.H / T_TH) * (p.W / T_TW), tiles_n = p.CoutPad / 64;
-    hipLaunchKernelGGL((dcn16t_kernel<2>), dim3(tiles_m * tiles_n), dim3(256), 0, stream, p, tiles_m, tiles_n);
+    if (p.up_t) hipLaunchKernelGGL((dcn16t_kernel<2, true>), dim3(tiles_m * tiles_n), dim3(256), 0, stream, p, tiles_m, tiles_n);
+    else hipLaunchKernelGGL((dcn16t_kernel<2>), dim3(tiles_m * tiles_n), dim3(256), 0, stream, p, tiles_m, tiles_n);
     return hipGetLastError() == hipSuccess ? CP_OK : CP_ERR_LAUNCH;
 }

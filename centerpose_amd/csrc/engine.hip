@@ -151,17 +151,20 @@ size_t cp_model_workspace_bytes(cp_model* m, int B, int H, int W) {
     }
     // The launch sequence -- and with it the arena's allocation order -- has variants the caller may select later: the first
     // layers fused or not (engine: fuse01), and a tap request, which turns the fused heads off.  The query runs the dry pass for
-    // every combination and returns the largest peak.
+    // every combination and returns the largest peak.  So does the IDAUp sequence (up-sample + add inside the preceding node or not).
     if (m->ws_cached && m->ws_key[0] == B && m->ws_key[1] == H && m->ws_key[2] == W && m->ws_key[3] == g_dbg && m->finalized)
-        return m->ws_cached;   // (cp_model_detect asks on every call: four dry passes per frame would show in the batch-1 latency)
+        return m->ws_cached;   // (cp_model_detect asks on every call: eight dry passes per frame would show in the batch-1 latency)
     size_t peak = 0;
     const char* const tap_before = m->tap_name;
-    for (int v = 0; v < 4; ++v) {
+    const int nv = m->ups_t.empty() ? 4 : 8;  // (models without an IDAUp have one form of it)
+    for (int v = 0; v < nv; ++v) {
         m->dry_variant = v & 1;
         m->tap_name = (v & 2) ? "" : nullptr;   // "" matches no tensor name: only the routing changes
+        m->dry_no_upadd = (v & 4) != 0;         // (a tap on an IDAUp node: its output has to exist)
         const int rc = forward_impl(m, nullptr, B, H, W, nullptr, (const float*)1, (const float*)1, (const float*)1, nullptr, 0,
                                     nullptr, 0, true);
         m->dry_variant = 0;
+        m->dry_no_upadd = false;
         m->tap_name = tap_before;
         if (rc != CP_OK) return 0;
         if (m->arena.peak > peak) peak = m->arena.peak;

@@ -342,9 +342,66 @@ struct Fwd {
     }
 
     // generic conv into a fresh NHWC tensor (or into user NCHW memory when out_nchw != nullptr)
+    // IDAUp's next up-sample + add, done by the epilogue of the node that produces `add` (ida()): the conv's output tensor is
+    // u = act(conv) + up(t), the node's own output does not exist
+    struct UpFuse {
+        const Tensor* t;
+        const float* wt;  // cp_model::ups_t
+        int f;
+    };
+    // deterministic split-K for launches with too few output tiles to fill 256 CUs (low-resolution layers at
+    // small batch): slices write slabs, a small epilogue kernel sums them in order.  Returns the slices (1: no split) and sets
+    // the launch's tile.
+    int plan_split(ConvParams& p, bool use16, const ConvW& w) {
+        int tiles = 0, nk = 0;
+        cp_conv_geometry(p, use16, &tiles, &nk);
+        // small launches of the f16x3 path run on 64 x 64 tiles (four times the workgroups per slice): a quarter of the
+        // slices and of the slab bytes (slices x M x Cout x 4) for the same workgroup count, and no split at all where that
+        // already gives kSplitTiles workgroups.  CP_SEL_TILE128_SMALL: the 128-row tiles everywhere (A/B runs).
+        // Measured at B = 1 / 2 / 4 / 8 (profiles/NOTES.md): pays up to 32 tiles of 128 rows, up to 64 when K is short.
+        if (use16 && tiles > 0 && (tiles <= 32 || (tiles <= 64 && nk <= 36)) && nk >= 8 && !p.gn_stats && !p.gn_in_a &&
+            p.CoutPad % 64 == 0 && w.Cout >= 64 && !(g_dbg & CP_SEL_TILE128_SMALL)) {
+            p.tile_m = p.tile_n = 64;
+            cp_conv_geometry(p, use16, &tiles, &nk);
+        }
+        // (64 x 64 tiles are a quarter of the work each: they are still cut along K below one workgroup per CU)
+        // (CP_SEL_STRM16_ALWAYS -- tests: the row-streaming kernel at any size -- keeps such a layer whole)
+        const bool force_strm = use16 && (g_dbg & CP_SEL_STRM16_ALWAYS) && cp_strm16_supported(p);
+        if (tiles > 0 && tiles < (p.tile_m == 64 ? 256 : kSplitTiles) && nk >= 8 && !p.gn_stats && !force_strm) {
+            int want = (kSplitTarget + tiles - 1) / tiles;
+            if (want > nk / 2) want = nk / 2;
+            if (want > 32) want = 32;
+            if (want > 1) {
+                const int per = (nk + want - 1) / want;
+                const int sk = (nk + per - 1) / per;
+                if (sk > 1) return sk;
+            }
+        }
+        return 1;
+    }
+    // Would the DCN `d` on a C x H x W input, asked to add the up-sampling by f of a tensor of t_c channels, run on the kernel that
+    // can (dcn16t's UPADD instance)?  The answer of conv() below for the same launch, from the shapes alone: a dry run and the
+    // real pass decide alike.
+    bool upadd_fusable(const DeformW& d, int C, int H, int W, int t_c, int f) {
+        if (m->precision != CP_PREC_F16X3 || m->dry_no_upadd) return false;
+        const float* const some = (const float*)0x1000;  // (placeholders: only null / non-null is looked at)
+        ConvParams p = conv_params(B, H, W, &some, &C, 1, d.main, 1, 1, CP_ACT_RELU);
+        if (p.Cin != d.main.CinP) return false;
+        p.offmask = some;
+        const unsigned* no_amax = nullptr;
+        if (!conv_params_f16(p, d.main, &no_amax, true)) return false;
+        p.store = CP_STORE_NHWC;
+        p.ldo = d.main.Cout;
+        p.up_t = p.up_wt = some;
+        p.up_ld = t_c;
+        p.up_f = f;
+        p.splitk = plan_split(p, true, d.main);
+        return p.splitk == 1 && cp_conv16_variant(p) == CP_VARIANT_DCN16T && cp_dcn16t_upadd_supported(p);
+    }
+
     Tensor conv(const ConvW& w, const std::vector<const Tensor*>& srcs, int stride, int pad, int act,
                 const Tensor* res = nullptr, const Tensor* offmask = nullptr, int act_from = 0,
-                float* out_nchw = nullptr, int out_ld = 0) {
+                float* out_nchw = nullptr, int out_ld = 0, const UpFuse* up = nullptr) {
         const Tensor& x0 = *srcs[0];
         const int nsrc = (int)srcs.size();
         const float* src[CP_MAX_SRC];
@@ -399,39 +456,18 @@ struct Fwd {
             p.ldo = cstore;
             p.coff = 0;
         }
-        // deterministic split-K for launches with too few output tiles to fill 256 CUs (low-resolution layers at
-        // small batch): slices write slabs, a small epilogue kernel sums them in order
         Tensor partial;
-        p.splitk = 1;
-        {
-            int tiles = 0, nk = 0;
-            cp_conv_geometry(p, use16, &tiles, &nk);
-            // small launches of the f16x3 path run on 64 x 64 tiles (four times the workgroups per slice): a quarter of the
-            // slices and of the slab bytes (slices x M x Cout x 4) for the same workgroup count, and no split at all where that
-            // already gives kSplitTiles workgroups.  CP_SEL_TILE128_SMALL: the 128-row tiles everywhere (A/B runs).
-            // Measured at B = 1 / 2 / 4 / 8 (profiles/NOTES.md): pays up to 32 tiles of 128 rows, up to 64 when K is short.
-            if (use16 && tiles > 0 && (tiles <= 32 || (tiles <= 64 && nk <= 36)) && nk >= 8 && !p.gn_stats && !p.gn_in_a &&
-                p.CoutPad % 64 == 0 && w.Cout >= 64 && !(g_dbg & CP_SEL_TILE128_SMALL)) {
-                p.tile_m = p.tile_n = 64;
-                cp_conv_geometry(p, use16, &tiles, &nk);
-            }
-            // (64 x 64 tiles are a quarter of the work each: they are still cut along K below one workgroup per CU)
-            // (CP_SEL_STRM16_ALWAYS -- tests: the row-streaming kernel at any size -- keeps such a layer whole)
-            const bool force_strm = use16 && (g_dbg & CP_SEL_STRM16_ALWAYS) && cp_strm16_supported(p);
-            if (tiles > 0 && tiles < (p.tile_m == 64 ? 256 : kSplitTiles) && nk >= 8 && !p.gn_stats && !force_strm) {
-                int want = (kSplitTarget + tiles - 1) / tiles;
-                if (want > nk / 2) want = nk / 2;
-                if (want > 32) want = 32;
-                if (want > 1) {
-                    const int per = (nk + want - 1) / want;
-                    const int sk = (nk + per - 1) / per;
-                    if (sk > 1) {
-                        p.splitk = sk;
-                        partial = make(sk * p.CoutPad, p.Ho, p.Wo);
-                        p.partial = partial.ptr();
-                    }
-                }
-            }
+        p.splitk = plan_split(p, use16, w);
+        if (p.splitk > 1) {
+            partial = make(p.splitk * p.CoutPad, p.Ho, p.Wo);
+            p.partial = partial.ptr();
+        }
+        if (up) {
+            p.up_t = up->t->ptr();
+            p.up_wt = up->wt;
+            p.up_ld = up->t->C;
+            p.up_f = up->f;
+            // (the caller asked upadd_fusable() first; cp_launch_conv16 refuses a launch that lands on a kernel without the epilogue)
         }
         auto launch = [&]() -> int {
             int rc = use16 ? cp_launch_conv16(p, s) : cp_launch_conv(p, s);
@@ -449,7 +485,7 @@ struct Fwd {
                 // algorithmic bytes: input once + output once + weights (+ offsets/mask for DCN, + residual)
                 r.bytes = 4.0 * ((double)B * x0.H * x0.W * cin_real + M * w.Cout +
                                  (double)w.KH * w.KW * cin_real * w.Cout + (offmask ? M * 27 : 0.0) +
-                                 (res ? M * w.Cout : 0.0));
+                                 (res ? M * w.Cout : 0.0) + (up ? (double)B * up->t->H * up->t->W * w.Cout : 0.0));
                 r.M = (int)M; r.N = w.Cout; r.K = w.KH * w.KW * cin_real; r.kh = w.KH; r.stride = stride;
             }, launch);
         gn_stats_out = nullptr;
@@ -512,12 +548,13 @@ struct Fwd {
         return tree1(p + ".tree2", x1, cout, cout, 1, false, {&bottom, &x1});
     }
 
-    Tensor deform(const std::string& p, const Tensor& x) {
+    // up: the node's epilogue adds IDAUp's next up-sampled tensor; what comes back is that sum (conv(): UpFuse)
+    Tensor deform(const std::string& p, const Tensor& x, const UpFuse* up = nullptr) {
         const DeformW& d = m->deforms.at(p);
         Tensor om = conv(d.offset, {&x}, 1, 1, CP_ACT_SIGMOID_FROM, nullptr, nullptr, 18);
         tap(p + ".offmask", om, 27);
-        Tensor o = conv(d.main, {&x}, 1, 1, CP_ACT_RELU, nullptr, &om);
-        tap(p, o);
+        Tensor o = conv(d.main, {&x}, 1, 1, CP_ACT_RELU, nullptr, &om, 0, nullptr, 0, up);
+        if (!up) tap(p, o);
         return o;
     }
     Tensor upsample_add(const std::string& p, const Tensor& x, int f, const Tensor& add) {
@@ -526,14 +563,38 @@ struct Fwd {
             chk(cp_launch_upsample_add(x.ptr(), m->ups.at(p), add.ptr(), o.ptr(), B, x.H, x.W, x.C, f, o.amax, s));
         return o;
     }
-    // IDAUp.forward: layers[i] = node(up(proj(layers[i])) + layers[i-1])
-    void ida(const std::string& p, std::vector<Tensor>& layers, int startp, int endp, const std::vector<int>& up_f) {
+    // IDAUp.forward: layers[i] = node(up(proj(layers[i])) + layers[i-1]).
+    // node_dead: the caller reads none of the node outputs but the last.  From the second iteration on `add` is the previous node's
+    // output, and the projections do not depend on the node chain (proj_k reads layers[i] as it came in): proj_{k+1} is then launched
+    // BEFORE node_k, whose epilogue adds up(t_{k+1}) to its activated output and stores u_{k+1} directly (dcn16t.hip, UPADD) -- node_k's
+    // own output is never written and the upsample_add launch of iteration k + 1 (a read of `add`, a write of u) does not exist.
+    // Where the node's launch is not dcn16t's (other shapes, small launches, float32, CP_SEL_DCN16T_NEVER) or a tap names a node,
+    // the sequence is the plain one.  Both forms round identically (upadd_common.h).
+    void ida(const std::string& p, std::vector<Tensor>& layers, int startp, int endp, const std::vector<int>& up_f,
+             bool node_dead = false) {
+        const bool tap_on_node = m->tap_name && std::strstr(m->tap_name, ".node_") != nullptr;
+        Tensor u_next;  // u of the next iteration, written by this iteration's node
         for (int i = startp + 1; i < endp; ++i) {
             const std::string k = std::to_string(i - startp);
-            Tensor t = deform(p + ".proj_" + k, layers[i]);
-            Tensor u = upsample_add(p + ".up_" + k, t, up_f[i - startp], layers[i - 1]);
-            t = Tensor();
-            layers[i] = deform(p + ".node_" + k, u);
+            Tensor u = u_next;
+            u_next = Tensor();
+            if (!u.valid()) {
+                Tensor t = deform(p + ".proj_" + k, layers[i]);
+                u = upsample_add(p + ".up_" + k, t, up_f[i - startp], layers[i - 1]);
+            }
+            tap(p + ".up_" + k, u);
+            const std::string kn = std::to_string(i + 1 - startp);
+            const int fn = i + 1 < endp ? up_f[i + 1 - startp] : 0;
+            const DeformW& node = m->deforms.at(p + ".node_" + k);
+            if (node_dead && !tap_on_node && i + 1 < endp && m->ups_t.count(p + ".up_" + kn) &&
+                upadd_fusable(node, u.C, u.H, u.W, m->deforms.at(p + ".proj_" + kn).main.Cout, fn)) {
+                Tensor t = deform(p + ".proj_" + kn, layers[i + 1]);
+                const UpFuse up = {&t, m->ups_t.at(p + ".up_" + kn), fn};
+                u_next = deform(p + ".node_" + k, u, &up);
+                layers[i] = Tensor();  // (dead by the caller's word)
+            } else {
+                layers[i] = deform(p + ".node_" + k, u);
+            }
         }
     }
 
@@ -811,13 +872,13 @@ struct Fwd {
         Tensor o2 = L[5];  // 256 @ 1/8... (after ida_0: 256 ch at L4 resolution)
         ida("dla_up.ida_1", L, 3, 6, {1, 2, 2});
         Tensor o1 = L[5];
-        ida("dla_up.ida_2", L, 2, 6, {1, 2, 2, 2});
+        ida("dla_up.ida_2", L, 2, 6, {1, 2, 2, 2}, true);  // (only L[5] is read below)
         Tensor o0 = L[5];
         for (auto& t : L) t = Tensor();
         // DLASeg.forward (:531-536): ida_up over [o0, o1, o2]
         std::vector<Tensor> y = {o0, o1, o2};
         o0 = o1 = o2 = Tensor();
-        ida("ida_up", y, 0, 3, {1, 2, 4});
+        ida("ida_up", y, 0, 3, {1, 2, 4}, true);  // (only y[2] is read below)
         Tensor feat = y[2];
         y.clear();
         tap("feat", feat);

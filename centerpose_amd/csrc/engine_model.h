@@ -179,7 +179,8 @@ struct cp_model {
     std::map<std::string, std::vector<float>> params;  // host copies until finalize
     std::map<std::string, cp_engine::ConvW> convs;
     std::map<std::string, cp_engine::DeformW> deforms;
-    std::map<std::string, float*> ups;
+    std::map<std::string, float*> ups;    // IDAUp's depth-wise up-sampling kernels [C][k][k] as in the checkpoint
+    std::map<std::string, float*> ups_t;  // ... and as [tap][C]
     std::map<std::string, cp_engine::DeconvW> deconvs;
     std::vector<cp_engine::HeadW> headw;
     // every fused head of the model in ONE launch (they all read the same feature map): the heads' 3x3 fragments,
@@ -227,6 +228,7 @@ struct cp_model {
     std::map<std::string, cp_engine::LowcW> lowc;  // hi / lo weight fragments of the lowc.hip layers
     int ws_key[4] = {0, 0, 0, -1};  // (B, H, W, g_dbg) of the cached work-space query below
     size_t ws_cached = 0;
+    bool dry_no_upadd = false;  // work-space query: the IDAUp sequence without the up-sample + add epilogues (a tap on a node selects it)
     int dry_variant = 0;  // work-space query: 1 = the dry run takes the fused stem + level0 path where the model allows it (the query
                           // runs both forms and returns the larger peak: switches and taps may select either form later)
     float stem_bound_l = 0.f, stem_bound_s = 0.f;  // |base_layer out| <= stem_bound_l * max|image| + stem_bound_s (fused stem + level0)

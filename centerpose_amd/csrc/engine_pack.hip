@@ -197,7 +197,15 @@ struct Packer {
             deform(p + ".proj_" + k, channels[i], o);
             deform(p + ".node_" + k, o, o);
             const int f = up_f[i];
-            if (const auto* w = get(p + ".up_" + k + ".weight", (size_t)o * 4 * f * f)) m->ups[p + ".up_" + k] = upload(*w);
+            if (const auto* w = get(p + ".up_" + k + ".weight", (size_t)o * 4 * f * f)) {
+                m->ups[p + ".up_" + k] = upload(*w);
+                // ... and as [tap][channel] for the DCN epilogue that adds the up-sampled tensor (dcn16t.hip, ConvParams::up_wt)
+                const int kk = 4 * f * f;
+                std::vector<float> wt((size_t)o * kk);
+                for (int c = 0; c < o; ++c)
+                    for (int t = 0; t < kk; ++t) wt[(size_t)t * o + c] = (*w)[(size_t)c * kk + t];
+                m->ups_t[p + ".up_" + k] = upload(wt);
+            }
         }
     }
     // ---- stacked hourglass (large_hourglass.py) ----

@@ -1,5 +1,6 @@
 // HBM-bound data-movement / element-wise kernels of the backbone (float32 NHWC, 16 B per lane).
 #include "cp_common.h"
+#include "upadd_common.h"
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
@@ -138,7 +139,7 @@ __global__ void upsample_add_kernel(const float* __restrict__ in, const float* _
     }
     __syncthreads();
     // 32-bit index math throughout (B*Ho*Wo*C/4 < 2^31 for every supported shape)
-    const int p = f / 2, Ho = H * f, Wo = W * f, C4 = C >> 2;
+    const int Ho = H * f, Wo = W * f, C4 = C >> 2;
     const unsigned total = (unsigned)B * Ho * Wo * C4;
     const __amdgpu_buffer_rsrc_t r_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(in), 0, (int)((unsigned)B * H * W * C * 4u), 0x00020000);
     const __amdgpu_buffer_rsrc_t r_add = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(add ? add : in), 0, add ? (int)(total * 16u) : 0, 0x00020000);
@@ -160,9 +161,10 @@ __global__ void upsample_add_kernel(const float* __restrict__ in, const float* _
         const int y = (int)(t % (unsigned)Ho);
         const int b = (int)(t / (unsigned)Ho);
         const bool live = i < total;
-        // ky ranges over { (y+p) % f, (y+p) % f + f }
-        const int ky0 = (y + p) % f, kx0 = (x + p) % f;
-        const int iy0 = (y + p - ky0) / f, ix0 = (x + p - kx0) / f;  // source of tap (ky0, kx0); the other tap is one less
+        // ky ranges over { (y+p) % f, (y+p) % f + f }; (iy0, ix0): source of tap (ky0, kx0); the other tap is one less
+        int ky0, kx0, iy0, ix0;
+        cp_upadd_axis(y, f, &ky0, &iy0);
+        cp_upadd_axis(x, f, &kx0, &ix0);
         q.wi = (ky0 * k + kx0) * C4 + (int)c4;
 #pragma unroll
         for (int a = 0; a < 2; ++a)
@@ -177,19 +179,13 @@ __global__ void upsample_add_kernel(const float* __restrict__ in, const float* _
         q.acc = make_float4(__uint_as_float(ra.x), __uint_as_float(ra.y), __uint_as_float(ra.z), __uint_as_float(ra.w));
     };
     auto finish = [&](unsigned i, const Piece& q) {
-        float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+        float4 wv[2][2];
 #pragma unroll
         for (int a = 0; a < 2; ++a)
 #pragma unroll
-            for (int bb = 0; bb < 2; ++bb) {
-                const float4 wv = reinterpret_cast<const float4*>(wt)[q.wi + (a * k + bb) * f * C4];   // (float4 index: the alignment is provable)
-                s.x += q.v[a][bb].x * wv.x;
-                s.y += q.v[a][bb].y * wv.y;
-                s.z += q.v[a][bb].z * wv.z;
-                s.w += q.v[a][bb].w * wv.w;
-            }
-        float4 acc = q.acc;
-        acc.x += s.x; acc.y += s.y; acc.z += s.z; acc.w += s.w;
+            for (int bb = 0; bb < 2; ++bb)
+                wv[a][bb] = reinterpret_cast<const float4*>(wt)[q.wi + (a * k + bb) * f * C4];   // (float4 index: the alignment is provable)
+        const float4 acc = cp_upadd_piece(q.v, wv, q.acc);
         amax = fmaxf(amax, fmaxf(fmaxf(fabsf(acc.x), fabsf(acc.y)), fmaxf(fabsf(acc.z), fabsf(acc.w))));   // (a piece beyond the tensor is all zeros)
         const u32x4 pk = {__float_as_uint(acc.x), __float_as_uint(acc.y), __float_as_uint(acc.z), __float_as_uint(acc.w)};
         __builtin_amdgcn_raw_buffer_store_b128(pk, r_out, (int)(i < total ? i * 16u : 0xffffffffu), 0, 0);

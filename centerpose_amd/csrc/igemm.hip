@@ -513,7 +513,7 @@ int cp_launch_splitk_epilogue(const ConvParams& p, hipStream_t stream) {
 }
 
 int cp_launch_conv(const ConvParams& p, hipStream_t stream) {
-    if (p.nsrc < 1 || p.nsrc > CP_MAX_SRC || p.Cin % 4 != 0) return CP_ERR_INVALID;
+    if (p.nsrc < 1 || p.nsrc > CP_MAX_SRC || p.Cin % 4 != 0 || p.up_t) return CP_ERR_INVALID;  // (up_t: an f16x3 epilogue, dcn16t.hip)
     for (int s = 0; s < p.nsrc; ++s)
         if (p.src_c[s] % 4 != 0 || (p.nsrc > 1 && p.src_c[s] % BK != 0)) return CP_ERR_INVALID;
     const int bn = cp_conv_tile_n(p.Cout);

@@ -714,6 +714,8 @@ bool cp_conv16_supported(const ConvParams& p) {
 
 int cp_launch_conv16(const ConvParams& p, hipStream_t stream) {
     if (!cp_conv16_supported(p)) return CP_ERR_INVALID;
+    // the up-sample + add epilogue (ConvParams::up_t) exists in dcn16t only: a launch that would go elsewhere is an error
+    if (p.up_t && !(p.offmask && dcn16t_wanted(p) && cp_dcn16t_upadd_supported(p))) return CP_ERR_INVALID;
     const int bn = conv16_tile_n(p);
     const bool cat = p.nsrc > 1;
     if (p.gn_in_a) {

@@ -1269,7 +1269,9 @@ class HipModel(object):
 
     def forward(self, images, pre_img=None, pre_hm=None, pre_hm_hp=None, sigmoid_hm=False, tap=None):
         """images [B,3,H,W] on the HIP device -> OrderedDict head -> [B,classes,H/4,W/4].
-        With ``tap`` also returns the named intermediate activation as NCHW."""
+        With ``tap`` also returns the named intermediate activation as NCHW.  A tap changes the launch sequence: the fused heads
+        are off, and a tap whose name contains ``.node_`` (an IDAUp node or its offset / mask map) runs every IDAUp with its
+        stand-alone up-sample + add launches, so a profile taken with such a tap is that of the unfused sequence."""
         L = lib()
         images = _dev(images)
         B, _, H, W = images.shape
