@@ -7,7 +7,8 @@ The reference's backbones are mostly ``nn.Conv2d``: DLA's ``BasicBlock`` 3x3 pai
 else changed, and ``use_hip_convs(model)`` re-classes a tree's eligible convolutions in place, so a network that trains through
 torch moves its convolutions onto the library in one line and keeps its parameters, optimizer state and checkpoints.
 
-BatchNorm, residual adds and everything else stay torch's; dilation, groups and ``in_channels % 4 != 0`` are not built.
+BatchNorm and the residual adds are ``norm.py``'s (``use_hip_norms``); pooling and everything else stay torch's; dilation, groups
+and ``in_channels % 4 != 0`` are not built.
 """
 import torch
 from torch import nn

@@ -1,0 +1,427 @@
+// BatchNorm2d for training, fused with the residual add and the ReLU (cp_batchnorm_forward_nhwc / cp_batchnorm_backward_nhwc):
+// y = act((x - mean) * invstd * gamma + beta [+ residual]) on float32 NHWC tensors with the batch's own statistics (training)
+// or the running ones (evaluation), and autograd's gradients of it.  It replaces the nn.BatchNorm2d -> `out += residual` ->
+// ReLU chains of pose_dla_dcn.py:40-62 (BasicBlock), pose_dla_dcn.py:150-168 (Root), pose_dla_dcn.py:381 (the DCN's actf) and
+// resnet_dcn.py.  Float32 arithmetic, no atomics, every sum in a fixed order that depends on the shape alone.
+//
+// All five streaming kernels share one thread map (lane_of): the tensor is P = B*H*W pixel rows of C floats; a wave reads 16
+// bytes per lane, so with L = C / 4 lanes per row, CL = min(L, 64) lanes take a row and a wave takes PW = 64 / CL rows at a
+// time (C = 16: 16 rows, one 1 KiB run of whole 128-byte lines; C = 20: 12 rows, 60 of 64 lanes busy); rows wider than a
+// wave (C > 256) are covered by ceil(L / 64) channel passes (blockIdx.y).  A workgroup is four waves on neighbouring rows and
+// owns a slab of rows (blockIdx.x); a lane keeps its four channels for the whole slab, so the per-channel coefficients sit in
+// registers and the sums need no shuffles.
+//
+// On the caller's stream:
+//   forward, training    stats_kernel     per slab and channel: mean and M2 = sum (x - mean)^2.  A lane sums d = x - pivot and d^2
+//                                         about its own first row (E[x^2] - mean^2 from raw sums loses every digit at
+//                                         |mean| >> std); lanes are merged by Chan's rule in its many-way form: mean = ref +
+//                                         sum n_i (m_i - ref) / n, M2 = sum M2_i + n_i (m_i - mean)^2, in lane order.
+//                        finalize_kernel  the slabs merged by the same rule, 8 slab lanes x 32 channels, slabs ascending per lane
+//                                         then the lanes in order; writes save_mean, save_invstd, updates the running pair.
+//   forward, evaluation  eval_stats_kernel  save_mean / save_invstd from the running pair.
+//   forward              apply_kernel     y, whole lines in and out.
+//   backward             bwd_reduce_kernel / bwd_finalize_kernel   grad_beta = sum g, grad_gamma = sum g * xhat (g gated by y > 0)
+//                        bwd_apply_kernel grad_x (and grad_residual = g when asked) in one pass.
+#include "igemm_common.h"
+
+#include <algorithm>
+
+namespace {
+
+struct Lane {
+    bool active;  // this lane holds channels of this pass
+    int c;        // its first channel
+    int k, S;     // it owns the slab's rows k, k + S, ...
+    int CL;       // lanes per row
+};
+
+__device__ __forceinline__ Lane lane_of(int C) {
+    const int L = C >> 2, CL = min(L, 64), PW = 64 / CL;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int pl = lane / CL, cl = lane - pl * CL, cg = blockIdx.y * 64 + cl;
+    Lane ln;
+    ln.active = pl < PW && cg < L;
+    ln.c = 4 * cg;
+    ln.k = w * PW + pl;
+    ln.S = 4 * PW;
+    ln.CL = CL;
+    return ln;
+}
+// index into a 256-entry LDS table of the lane that owns row phase k of the same channels (k < S)
+__device__ __forceinline__ int peer(const Lane& ln, int k) {
+    const int PW = ln.S >> 2, w = k / PW, pl = k - w * PW;
+    return w * 64 + pl * ln.CL + (threadIdx.x & 63) % ln.CL;
+}
+// rows of phase k in a slab of len rows
+__device__ __forceinline__ int rows_of(int len, int k, int S) { return k < len ? (len - k + S - 1) / S : 0; }
+
+__device__ __forceinline__ void st4(float* p, const float (&v)[4]) { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
+__device__ __forceinline__ void un4(const float4 v, float (&o)[4]) { o[0] = v.x, o[1] = v.y, o[2] = v.z, o[3] = v.w; }
+
+// part[slab][0][c] = the slab's mean, part[slab][1][c] = its M2
+__global__ __launch_bounds__(256) void stats_kernel(const float* __restrict__ x, float* __restrict__ part, int P, int C, int slab_px) {
+    __shared__ float4 sm[256], sq[256];
+    const Lane ln = lane_of(C);
+    const int q_beg = blockIdx.x * slab_px, len = min(P - q_beg, slab_px);
+    const int n = ln.active ? rows_of(len, ln.k, ln.S) : 0;
+    float piv[4] = {0.f, 0.f, 0.f, 0.f}, s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
+    if (n > 0) {
+        const float* px = x + (size_t)(q_beg + ln.k) * C + ln.c;
+        const size_t step = (size_t)ln.S * C;
+        un4(ld4(px), piv);
+        auto add = [&](const float4 v4) {
+            float v[4];
+            un4(v4, v);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float d = v[i] - piv[i];
+                s1[i] += d;
+                s2[i] = fmaf(d, d, s2[i]);
+            }
+        };
+        int j = 0;
+        for (; j + 4 <= n; j += 4) {  // four rows requested before the first is used
+            const float4 v0 = ld4(px), v1 = ld4(px + step), v2 = ld4(px + 2 * step), v3 = ld4(px + 3 * step);
+            px += 4 * step;
+            add(v0), add(v1), add(v2), add(v3);
+        }
+        for (; j < n; ++j, px += step) add(ld4(px));
+    }
+    const float rn = n > 0 ? 1.f / (float)n : 0.f;
+    float m[4], q[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        m[i] = fmaf(s1[i], rn, piv[i]);
+        q[i] = fmaxf(s2[i] - s1[i] * s1[i] * rn, 0.f);
+    }
+    sm[threadIdx.x] = make_float4(m[0], m[1], m[2], m[3]);
+    sq[threadIdx.x] = make_float4(q[0], q[1], q[2], q[3]);
+    __syncthreads();
+    if (!ln.active || ln.k != 0) return;
+    // the row phases in order; phase 0 (this lane) is never empty
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int k = 1; k < ln.S; ++k) {
+        const float nk = (float)rows_of(len, k, ln.S);
+        float t[4];
+        un4(sm[peer(ln, k)], t);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[i] = fmaf(nk, t[i] - m[i], acc[i]);
+    }
+    float mean[4], M2[4] = {0.f, 0.f, 0.f, 0.f};
+    const float rl = 1.f / (float)len;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) mean[i] = fmaf(acc[i], rl, m[i]);
+    for (int k = 0; k < ln.S; ++k) {
+        const float nk = (float)rows_of(len, k, ln.S);
+        const int p = peer(ln, k);
+        float t[4], u[4];
+        un4(sm[p], t);
+        un4(sq[p], u);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float d = t[i] - mean[i];
+            M2[i] += fmaf(nk * d, d, u[i]);
+        }
+    }
+    float* out = part + (size_t)blockIdx.x * 2 * C + ln.c;
+    st4(out, mean);
+    st4(out + C, M2);
+}
+
+// The slabs merged per channel: a workgroup is 32 channels x 8 slab lanes; a lane walks the slabs sl, sl + 8, ... in ascending
+// order, then the eight lanes are added in lane order.  Two rounds: the mean about slab 0's, then M2 about that mean.
+__global__ __launch_bounds__(256) void finalize_kernel(const float* __restrict__ part, float* __restrict__ save_mean,
+                                                       float* __restrict__ save_invstd, float* __restrict__ rmean,
+                                                       float* __restrict__ rvar, int P, int C, int slab_px, int nslab, float momentum,
+                                                       float eps) {
+    __shared__ float red[256];
+    const int el = threadIdx.x & 31, sl = threadIdx.x >> 5, c = blockIdx.x * 32 + el;
+    const bool cv = c < C;
+    const float ref = cv ? part[c] : 0.f, n = (float)P;
+    auto rows = [&](int s) { return (float)min(slab_px, P - s * slab_px); };
+    float a = 0.f;
+    if (cv)
+        for (int s = sl; s < nslab; s += 8) a = fmaf(rows(s), part[(size_t)s * 2 * C + c] - ref, a);
+    red[threadIdx.x] = a;
+    __syncthreads();
+    float t = red[el];
+    for (int j = 1; j < 8; ++j) t += red[j * 32 + el];
+    const float mean = ref + t / n;
+    __syncthreads();
+    float b = 0.f;
+    if (cv)
+        for (int s = sl; s < nslab; s += 8) {
+            const float* ps = part + (size_t)s * 2 * C + c;
+            const float d = ps[0] - mean;
+            b += fmaf(rows(s) * d, d, ps[C]);
+        }
+    red[threadIdx.x] = b;
+    __syncthreads();
+    if (sl != 0 || !cv) return;
+    float M2 = red[el];
+    for (int j = 1; j < 8; ++j) M2 += red[j * 32 + el];
+    save_mean[c] = mean;
+    save_invstd[c] = 1.f / sqrtf(M2 / n + eps);
+    if (rmean) rmean[c] = (1.f - momentum) * rmean[c] + momentum * mean;
+    if (rvar) rvar[c] = (1.f - momentum) * rvar[c] + momentum * (M2 / (n - 1.f));
+}
+
+__global__ void eval_stats_kernel(const float* __restrict__ rmean, const float* __restrict__ rvar, float* __restrict__ save_mean,
+                                  float* __restrict__ save_invstd, int C, float eps) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    save_mean[c] = rmean[c];
+    save_invstd[c] = 1.f / sqrtf(rvar[c] + eps);
+}
+
+// y = act((x - mean) * (invstd * gamma) + beta [+ res])
+__global__ __launch_bounds__(256) void apply_kernel(const float* __restrict__ x, const float* __restrict__ res, float* __restrict__ y,
+                                                    const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                    const float* __restrict__ gamma, const float* __restrict__ beta, int P, int C,
+                                                    int slab_px, int act) {
+    const Lane ln = lane_of(C);
+    const int q_beg = blockIdx.x * slab_px, len = min(P - q_beg, slab_px);
+    const int n = ln.active ? rows_of(len, ln.k, ln.S) : 0;
+    if (n == 0) return;
+    float mu[4], a[4], sh[4] = {0.f, 0.f, 0.f, 0.f};
+    un4(ld4(mean + ln.c), mu);
+    un4(ld4(invstd + ln.c), a);
+    if (gamma) {
+        float g[4];
+        un4(ld4(gamma + ln.c), g);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) a[i] *= g[i];
+    }
+    if (beta) un4(ld4(beta + ln.c), sh);
+    size_t off = (size_t)(q_beg + ln.k) * C + ln.c;
+    const size_t step = (size_t)ln.S * C;
+    auto put = [&](size_t o, const float4 v4, const float4 r4) {
+        float v[4], r[4], out[4];
+        un4(v4, v);
+        un4(r4, r);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float t = fmaf(v[i] - mu[i], a[i], sh[i]) + r[i];
+            out[i] = act ? fmaxf(t, 0.f) : t;
+        }
+        st4(y + o, out);
+    };
+    auto ldr = [&](size_t o) { return res ? ld4(res + o) : zero4(); };
+    int j = 0;
+    for (; j + 4 <= n; j += 4, off += 4 * step) {
+        const float4 v0 = ld4(x + off), v1 = ld4(x + off + step), v2 = ld4(x + off + 2 * step), v3 = ld4(x + off + 3 * step);
+        const float4 r0 = ldr(off), r1 = ldr(off + step), r2 = ldr(off + 2 * step), r3 = ldr(off + 3 * step);
+        put(off, v0, r0), put(off + step, v1, r1), put(off + 2 * step, v2, r2), put(off + 3 * step, v3, r3);
+    }
+    for (; j < n; ++j, off += step) put(off, ld4(x + off), ldr(off));
+}
+
+__device__ __forceinline__ float4 gate4(const float4 g, const float4 y) {
+    return make_float4(y.x > 0.f ? g.x : 0.f, y.y > 0.f ? g.y : 0.f, y.z > 0.f ? g.z : 0.f, y.w > 0.f ? g.w : 0.f);
+}
+
+// part[slab][0][c] = sum g, part[slab][1][c] = sum g * (x - mean) over the slab's rows: rows ascending per lane, then the row
+// phases in order
+__global__ __launch_bounds__(256) void bwd_reduce_kernel(const float* __restrict__ x, const float* __restrict__ y,
+                                                         const float* __restrict__ go, const float* __restrict__ mean,
+                                                         float* __restrict__ part, int P, int C, int slab_px) {
+    __shared__ float4 sg[256], sx[256];
+    const Lane ln = lane_of(C);
+    const int q_beg = blockIdx.x * slab_px, len = min(P - q_beg, slab_px);
+    const int n = ln.active ? rows_of(len, ln.k, ln.S) : 0;
+    float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
+    if (n > 0) {
+        float mu[4];
+        un4(ld4(mean + ln.c), mu);
+        size_t off = (size_t)(q_beg + ln.k) * C + ln.c;
+        const size_t step = (size_t)ln.S * C;
+        auto ldg = [&](size_t o) {
+            const float4 g = ld4(go + o);
+            return y ? gate4(g, ld4(y + o)) : g;
+        };
+        auto add = [&](const float4 g4, const float4 v4) {
+            float g[4], v[4];
+            un4(g4, g);
+            un4(v4, v);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                s1[i] += g[i];
+                s2[i] = fmaf(g[i], v[i] - mu[i], s2[i]);
+            }
+        };
+        int j = 0;
+        for (; j + 2 <= n; j += 2, off += 2 * step) {
+            const float4 v0 = ld4(x + off), v1 = ld4(x + off + step);
+            const float4 g0 = ldg(off), g1 = ldg(off + step);
+            add(g0, v0), add(g1, v1);
+        }
+        for (; j < n; ++j, off += step) add(ldg(off), ld4(x + off));
+    }
+    sg[threadIdx.x] = make_float4(s1[0], s1[1], s1[2], s1[3]);
+    sx[threadIdx.x] = make_float4(s2[0], s2[1], s2[2], s2[3]);
+    __syncthreads();
+    if (!ln.active || ln.k != 0) return;
+    for (int k = 1; k < ln.S; ++k) {
+        const int p = peer(ln, k);
+        float t[4], u[4];
+        un4(sg[p], t);
+        un4(sx[p], u);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) s1[i] += t[i], s2[i] += u[i];
+    }
+    float* out = part + (size_t)blockIdx.x * 2 * C + ln.c;
+    st4(out, s1);
+    st4(out + C, s2);
+}
+
+// sums[0][c] = grad_beta, sums[1][c] = grad_gamma = invstd * sum g (x - mean), in finalize_kernel's order; the caller's
+// grad_beta / grad_gamma get a copy when given
+__global__ __launch_bounds__(256) void bwd_finalize_kernel(const float* __restrict__ part, const float* __restrict__ invstd,
+                                                           float* __restrict__ sums, float* __restrict__ gg, float* __restrict__ gb,
+                                                           int C, int nslab) {
+    __shared__ float r1[256], r2[256];
+    const int el = threadIdx.x & 31, sl = threadIdx.x >> 5, c = blockIdx.x * 32 + el;
+    const bool cv = c < C;
+    float a = 0.f, b = 0.f;
+    if (cv)
+        for (int s = sl; s < nslab; s += 8) {
+            const float* ps = part + (size_t)s * 2 * C + c;
+            a += ps[0];
+            b += ps[C];
+        }
+    r1[threadIdx.x] = a;
+    r2[threadIdx.x] = b;
+    __syncthreads();
+    if (sl != 0 || !cv) return;
+    for (int j = 1; j < 8; ++j) a += r1[j * 32 + el], b += r2[j * 32 + el];
+    b *= invstd[c];
+    sums[c] = a;
+    sums[C + c] = b;
+    if (gb) gb[c] = a;
+    if (gg) gg[c] = b;
+}
+
+// training: grad_x = gamma * invstd * (g - grad_beta / n - xhat * grad_gamma / n); evaluation: gamma * invstd * g;
+// grad_residual = g.  gx or gres may be null (not both).
+__global__ __launch_bounds__(256) void bwd_apply_kernel(const float* __restrict__ x, const float* __restrict__ y,
+                                                        const float* __restrict__ go, const float* __restrict__ gamma,
+                                                        const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                        const float* __restrict__ sums, float* __restrict__ gx,
+                                                        float* __restrict__ gres, int P, int C, int slab_px, int training) {
+    const Lane ln = lane_of(C);
+    const int q_beg = blockIdx.x * slab_px, len = min(P - q_beg, slab_px);
+    const int n = ln.active ? rows_of(len, ln.k, ln.S) : 0;
+    if (n == 0) return;
+    const bool need_x = training && gx;  // (x enters grad_x only through the batch statistics)
+    float mu[4] = {0.f, 0.f, 0.f, 0.f}, a[4], k1[4] = {0.f, 0.f, 0.f, 0.f}, k2[4] = {0.f, 0.f, 0.f, 0.f};
+    un4(ld4(invstd + ln.c), a);
+    if (need_x) {
+        float s1[4], s2[4];
+        const float rn = 1.f / (float)P;
+        un4(ld4(mean + ln.c), mu);
+        un4(ld4(sums + ln.c), s1);
+        un4(ld4(sums + C + ln.c), s2);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) k1[i] = s1[i] * rn, k2[i] = s2[i] * rn * a[i];
+    }
+    if (gamma) {
+        float g[4];
+        un4(ld4(gamma + ln.c), g);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) a[i] *= g[i];
+    }
+    size_t off = (size_t)(q_beg + ln.k) * C + ln.c;
+    const size_t step = (size_t)ln.S * C;
+    auto ldg = [&](size_t o) {
+        const float4 g = ld4(go + o);
+        return y ? gate4(g, ld4(y + o)) : g;
+    };
+    auto ldx = [&](size_t o) { return need_x ? ld4(x + o) : zero4(); };
+    auto put = [&](size_t o, const float4 g4, const float4 v4) {
+        float g[4], v[4], out[4];
+        un4(g4, g);
+        un4(v4, v);
+        if (gres) st4(gres + o, g);
+        if (!gx) return;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) out[i] = a[i] * (g[i] - k1[i] - (v[i] - mu[i]) * k2[i]);
+        st4(gx + o, out);
+    };
+    int j = 0;
+    for (; j + 2 <= n; j += 2, off += 2 * step) {
+        const float4 g0 = ldg(off), g1 = ldg(off + step);
+        const float4 v0 = ldx(off), v1 = ldx(off + step);
+        put(off, g0, v0), put(off + step, g1, v1);
+    }
+    for (; j < n; ++j, off += step) put(off, ldg(off), ldx(off));
+}
+
+inline bool ok() { return hipGetLastError() == hipSuccess; }
+
+// Slabs of whole workgroup steps (S rows).  Reductions: at least eight steps per slab and at most about 2048 workgroups, so the
+// partials stay small and the finalize short; element-wise passes: eight steps per workgroup.
+struct Plan {
+    int P, npass, S;
+    int red_px, red_slabs, red_bound;  // rows per slab, slabs, and a bound on them that is monotone in P (sizes the workspace)
+    int app_px, app_slabs;
+    size_t part, sums, total;
+};
+
+Plan plan(int B, int H, int W, int C) {
+    Plan p;
+    const int L = C / 4, CL = std::min(L, 64);
+    p.P = B * H * W;
+    p.npass = (L + 63) / 64;
+    p.S = 4 * (64 / CL);
+    const int steps = (p.P + p.S - 1) / p.S;
+    p.red_bound = std::max(1, std::min((steps + 7) / 8, std::max(1, 2048 / p.npass)));
+    p.red_px = (steps + p.red_bound - 1) / p.red_bound * p.S;
+    p.red_slabs = (p.P + p.red_px - 1) / p.red_px;
+    p.app_px = 8 * p.S;
+    p.app_slabs = (p.P + p.app_px - 1) / p.app_px;
+    const auto al = [](size_t x) { return (x + 255) / 256 * 256; };
+    p.part = 0;
+    p.sums = al((size_t)p.red_bound * 2 * C * 4);
+    p.total = p.sums + al((size_t)2 * C * 4);
+    return p;
+}
+
+}  // namespace
+
+size_t cp_batchnorm_ws_bytes(int B, int H, int W, int C) { return plan(B, H, W, C).total; }
+
+int cp_launch_batchnorm_forward(hipStream_t s, const BnFwdArgs& a, void* ws) {
+    const Plan p = plan(a.B, a.H, a.W, a.C);
+    float* part = (float*)((char*)ws + p.part);
+    if (a.training) {
+        hipLaunchKernelGGL(stats_kernel, dim3(p.red_slabs, p.npass), dim3(256), 0, s, a.x, part, p.P, a.C, p.red_px);
+        if (!ok()) return CP_ERR_LAUNCH;
+        hipLaunchKernelGGL(finalize_kernel, dim3((a.C + 31) / 32), dim3(256), 0, s, (const float*)part, a.mean, a.invstd, a.rmean,
+                           a.rvar, p.P, a.C, p.red_px, p.red_slabs, a.momentum, a.eps);
+    } else {
+        hipLaunchKernelGGL(eval_stats_kernel, dim3((a.C + 255) / 256), dim3(256), 0, s, (const float*)a.rmean, (const float*)a.rvar,
+                           a.mean, a.invstd, a.C, a.eps);
+    }
+    if (!ok()) return CP_ERR_LAUNCH;
+    hipLaunchKernelGGL(apply_kernel, dim3(p.app_slabs, p.npass), dim3(256), 0, s, a.x, a.res, a.y, (const float*)a.mean,
+                       (const float*)a.invstd, a.gamma, a.beta, p.P, a.C, p.app_px, a.act);
+    return ok() ? CP_OK : CP_ERR_LAUNCH;
+}
+
+int cp_launch_batchnorm_backward(hipStream_t s, const BnBwdArgs& a, void* ws) {
+    const Plan p = plan(a.B, a.H, a.W, a.C);
+    float* part = (float*)((char*)ws + p.part);
+    float* sums = (float*)((char*)ws + p.sums);
+    if (a.gg || a.gb || (a.training && a.gx)) {
+        hipLaunchKernelGGL(bwd_reduce_kernel, dim3(p.red_slabs, p.npass), dim3(256), 0, s, a.x, a.y, a.go, a.mean, part, p.P, a.C,
+                           p.red_px);
+        if (!ok()) return CP_ERR_LAUNCH;
+        hipLaunchKernelGGL(bwd_finalize_kernel, dim3((a.C + 31) / 32), dim3(256), 0, s, (const float*)part, a.invstd, sums, a.gg,
+                           a.gb, a.C, p.red_slabs);
+        if (!ok()) return CP_ERR_LAUNCH;
+    }
+    if (!a.gx && !a.gres) return CP_OK;
+    hipLaunchKernelGGL(bwd_apply_kernel, dim3(p.app_slabs, p.npass), dim3(256), 0, s, a.x, a.y, a.go, a.gamma, a.mean, a.invstd,
+                       (const float*)sums, a.gx, a.gres, p.P, a.C, p.app_px, a.training);
+    return ok() ? CP_OK : CP_ERR_LAUNCH;
+}

@@ -453,6 +453,24 @@ bool cp_conv_backward_mfma(int Cin, int KH, int KW, int stride, int pad);  // th
 size_t cp_conv_backward_ws_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int need_grad_x);
 int cp_launch_conv_backward(hipStream_t s, const ConvBwdArgs& a, void* ws);
 
+// ---- BatchNorm2d, training and evaluation, fused with the residual add and ReLU (batchnorm.hip): float32 NHWC ----
+struct BnFwdArgs {
+    const float *x, *gamma, *beta, *res;  // gamma / beta nullptr: 1 / 0; res nullptr: no residual
+    float *rmean, *rvar;                  // running statistics: updated (training, may be nullptr) or read (evaluation)
+    float *y, *mean, *invstd;
+    int B, H, W, C, training;
+    float momentum, eps;
+    int act;
+};
+struct BnBwdArgs {
+    const float *x, *y, *go, *gamma, *mean, *invstd;  // y (the activated output) or nullptr: grad_out is gated by y > 0
+    float *gx, *gres, *gg, *gb;                       // each nullptr: not computed
+    int B, H, W, C, training;
+};
+size_t cp_batchnorm_ws_bytes(int B, int H, int W, int C);
+int cp_launch_batchnorm_forward(hipStream_t s, const BnFwdArgs& a, void* ws);
+int cp_launch_batchnorm_backward(hipStream_t s, const BnBwdArgs& a, void* ws);
+
 // ---- ObjectPoseLoss (pose_loss.hip; numerics in pose_loss_common.h) ----
 struct cp_pose_loss_desc;
 const char* cp_pose_loss_check(const cp_pose_loss_desc* d);                           // nullptr: accepted

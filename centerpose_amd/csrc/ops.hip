@@ -1,6 +1,6 @@
 // The stand-alone operators of the C ABI (include/centerpose_hip.h): single layers on caller tensors, outside any cp_model
-// -- cp_conv2d_nhwc / cp_conv2d_backward_nhwc, cp_conv_transpose2d_nhwc, cp_dcnv2_forward / cp_dcnv2_backward,
-// cp_pose_heads_forward / _backward.
+// -- cp_conv2d_nhwc / cp_conv2d_backward_nhwc, cp_batchnorm_forward_nhwc / _backward_nhwc, cp_conv_transpose2d_nhwc,
+// cp_dcnv2_forward / cp_dcnv2_backward, cp_pose_heads_forward / _backward.
 // Each packs its PyTorch-layout weights into a caller-provided workspace on every call and then launches the same kernels as
 // the engine.
 #include "engine_model.h"
@@ -215,6 +215,20 @@ const char* conv_bwd_shape_error(int B, int H, int W, int Cin, int Cout, int KH,
     if ((long long)B * H * W * Cin >= lim || (long long)B * ho * wo * cop >= lim || cop * Cin * KH * KW >= lim)
         return "conv2d_backward: a tensor has 2^31 elements or more";
     return nullptr;
+}
+
+// BatchNorm: shape checks shared by the two calls and their workspace query, kernels in batchnorm.hip
+const char* bn_shape_error(int B, int H, int W, int C) {
+    if (B < 1 || H < 1 || W < 1) return "batchnorm: B, H and W must be at least 1";
+    if (C < 4 || C > 4096 || C % 4) return "batchnorm: C must be a multiple of 4 in 4..4096";
+    if ((long long)B * H * W * C >= 0x7fffffffLL) return "batchnorm: a tensor has 2^31 elements or more";
+    return nullptr;
+}
+// the kernels read and write 16 bytes per lane
+bool bn_aligned(std::initializer_list<const void*> ptrs) {
+    for (const void* p : ptrs)
+        if ((uintptr_t)p & 15) return false;
+    return true;
 }
 
 // cp_pose_heads_forward: per head the 3x3 layer's float32 and f16x3 operands + bias, the 1x1 layer's, one hidden chunk
@@ -460,6 +474,53 @@ int cp_conv2d_backward_nhwc(cp_stream_t stream, const float* x, const float* w, 
     const ConvBwdArgs a{x, w, y_or_null, grad_out, grad_x_or_null, grad_w, grad_bias_or_null, B, H, W, Cin, Cout, KH, KW, stride, pad};
     const int rc = cp_launch_conv_backward((hipStream_t)stream, a, workspace);
     return rc == CP_OK ? CP_OK : fail(rc, "conv2d_backward: kernel launch failed");
+}
+
+size_t cp_batchnorm_workspace_bytes(int B, int H, int W, int C) {
+    if (const char* e = bn_shape_error(B, H, W, C)) {
+        fail(CP_ERR_INVALID, e);
+        return 0;
+    }
+    return cp_batchnorm_ws_bytes(B, H, W, C);
+}
+
+int cp_batchnorm_forward_nhwc(cp_stream_t stream, const float* x, const float* gamma_or_null, const float* beta_or_null,
+                              const float* residual_or_null, float* running_mean_or_null, float* running_var_or_null, float* y,
+                              float* save_mean, float* save_invstd, int B, int H, int W, int C, int training, float momentum,
+                              float eps, int act, void* workspace, size_t workspace_bytes) {
+    if (const char* e = bn_shape_error(B, H, W, C)) return fail(CP_ERR_INVALID, e);
+    if (!x || !y || !save_mean || !save_invstd || !workspace) return fail(CP_ERR_INVALID, "batchnorm_forward: null argument");
+    if (training && (long long)B * H * W < 2)
+        return fail(CP_ERR_INVALID, "batchnorm_forward: training needs more than one value per channel (B*H*W >= 2)");
+    if (!training && (!running_mean_or_null || !running_var_or_null))
+        return fail(CP_ERR_INVALID, "batchnorm_forward: evaluation needs running_mean and running_var");
+    if (act != 0 && act != 1) return fail(CP_ERR_INVALID, "batchnorm_forward: act must be 0 (none) or 1 (relu)");
+    if (!(eps >= 0.f)) return fail(CP_ERR_INVALID, "batchnorm_forward: eps must not be negative");
+    if (y == x) return fail(CP_ERR_INVALID, "batchnorm_forward: y must not alias x");
+    if (!bn_aligned({x, gamma_or_null, beta_or_null, residual_or_null, y, save_mean, save_invstd, workspace}))
+        return fail(CP_ERR_INVALID, "batchnorm_forward: tensors must be 16-byte aligned");
+    if (workspace_bytes < cp_batchnorm_ws_bytes(B, H, W, C)) return fail(CP_ERR_INVALID, "batchnorm_forward: workspace too small");
+    const BnFwdArgs a{x, gamma_or_null, beta_or_null, residual_or_null, running_mean_or_null, running_var_or_null, y, save_mean,
+                      save_invstd, B, H, W, C, training != 0, momentum, eps, act};
+    const int rc = cp_launch_batchnorm_forward((hipStream_t)stream, a, workspace);
+    return rc == CP_OK ? CP_OK : fail(rc, "batchnorm_forward: kernel launch failed");
+}
+
+int cp_batchnorm_backward_nhwc(cp_stream_t stream, const float* x, const float* y_or_null, const float* grad_out,
+                               const float* gamma_or_null, const float* save_mean, const float* save_invstd, float* grad_x_or_null,
+                               float* grad_residual_or_null, float* grad_gamma_or_null, float* grad_beta_or_null, int B, int H,
+                               int W, int C, int training, void* workspace, size_t workspace_bytes) {
+    if (const char* e = bn_shape_error(B, H, W, C)) return fail(CP_ERR_INVALID, e);
+    if (!x || !grad_out || !save_mean || !save_invstd || !workspace) return fail(CP_ERR_INVALID, "batchnorm_backward: null argument");
+    if (training && (long long)B * H * W < 2)
+        return fail(CP_ERR_INVALID, "batchnorm_backward: training needs more than one value per channel (B*H*W >= 2)");
+    if (!bn_aligned({x, y_or_null, grad_out, gamma_or_null, save_mean, save_invstd, grad_x_or_null, grad_residual_or_null, workspace}))
+        return fail(CP_ERR_INVALID, "batchnorm_backward: tensors must be 16-byte aligned");
+    if (workspace_bytes < cp_batchnorm_ws_bytes(B, H, W, C)) return fail(CP_ERR_INVALID, "batchnorm_backward: workspace too small");
+    const BnBwdArgs a{x, y_or_null, grad_out, gamma_or_null, save_mean, save_invstd, grad_x_or_null, grad_residual_or_null,
+                      grad_gamma_or_null, grad_beta_or_null, B, H, W, C, training != 0};
+    const int rc = cp_launch_batchnorm_backward((hipStream_t)stream, a, workspace);
+    return rc == CP_OK ? CP_OK : fail(rc, "batchnorm_backward: kernel launch failed");
 }
 
 size_t cp_dcnv2_backward_workspace_bytes(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw,

@@ -131,6 +131,10 @@ def lib():
          *([c_int] * 10), c_void_p, c_size_t)
     _sig(L.cp_conv2d_backward_workspace_bytes, c_size_t, *([c_int] * 10))
     _sig(L.cp_conv2d_backward_nhwc, c_int, *([c_void_p] * 8), *([c_int] * 9), c_void_p, c_size_t)
+    _sig(L.cp_batchnorm_workspace_bytes, c_size_t, *([c_int] * 4))
+    _sig(L.cp_batchnorm_forward_nhwc, c_int, *([c_void_p] * 10), *([c_int] * 5), ctypes.c_float, ctypes.c_float, c_int, c_void_p,
+         c_size_t)
+    _sig(L.cp_batchnorm_backward_nhwc, c_int, *([c_void_p] * 11), *([c_int] * 5), c_void_p, c_size_t)
     _sig(L.cp_decode_workspace_bytes, c_size_t, c_int, c_int)
     _sig(L.cp_decode, c_int, c_void_p, c_int, c_int, c_int, *([c_void_p] * 11), c_int, c_int, c_int, ctypes.c_float,
          c_int, c_int, c_void_p, c_void_p, c_size_t)
@@ -227,7 +231,8 @@ def exported_symbols():
             "cp_model_heads_at_workspace_bytes", "cp_model_heads_at", "cp_decode_peaks_workspace_bytes", "cp_decode_peaks",
             "cp_decode_gathered", "cp_pose_heads_chunk_images", "cp_pose_heads_forward_workspace_bytes",
             "cp_pose_heads_forward", "cp_pose_heads_backward_workspace_bytes", "cp_pose_heads_backward",
-            "cp_model_features", "cp_conv2d_backward_workspace_bytes", "cp_conv2d_backward_nhwc"]
+            "cp_model_features", "cp_conv2d_backward_workspace_bytes", "cp_conv2d_backward_nhwc",
+            "cp_batchnorm_workspace_bytes", "cp_batchnorm_forward_nhwc", "cp_batchnorm_backward_nhwc"]
 
 
 def _check(rc, what):
@@ -491,6 +496,83 @@ def conv2d_backward(x, w, grad_out, stride=1, pad=0, y=None, need_x_grad=True, n
                                    _ptr(grad_b), B, H, W, Cin, Cout, KH, KW, stride, pad, _ptr(ws), nbytes)
     _check(rc, "cp_conv2d_backward_nhwc")
     return grad_x, grad_w, grad_b
+
+
+def _bn_vec(t, C, name):
+    if t is None:
+        return None
+    t = _dev(t)
+    if tuple(t.shape) != (C,):
+        raise RuntimeError("batch_norm: %s has shape %s, expected %s" % (name, tuple(t.shape), (C,)))
+    return t
+
+
+def _bn_ws(L, x):
+    if not x.is_cuda:
+        raise RuntimeError("centerpose_hip: tensors must live on the HIP device (no CPU path)")
+    if x.dim() != 4:
+        raise RuntimeError("batch_norm: x must be [B,H,W,C], got %s" % (tuple(x.shape),))
+    B, H, W, C = x.shape
+    nbytes = L.cp_batchnorm_workspace_bytes(B, H, W, C)
+    if nbytes == 0:
+        raise RuntimeError("batch_norm: shape refused by the library (%s)" % L.cp_last_error().decode())
+    return (B, H, W, C), nbytes, torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+
+
+def batch_norm_forward(x, gamma=None, beta=None, residual=None, running_mean=None, running_var=None, training=True,
+                       momentum=0.1, eps=1e-5, act=0):
+    """``act(batch_norm(x) [+ residual])`` (cp_batchnorm_forward_nhwc): x, residual [B,H,W,C] NHWC, gamma / beta [C] or None
+    (1 / 0) -> (y [B,H,W,C], save_mean [C], save_invstd [C]).  ``training``: the batch's statistics, and running_mean /
+    running_var (float32 device tensors, when given) are updated IN PLACE with ``momentum``; otherwise they are the
+    statistics.  act 0 none, 1 relu.  Float32 and bitwise reproducible."""
+    L = lib()
+    geo, nbytes, ws = _bn_ws(L, x)
+    x = _dev(x)
+    C = geo[3]
+    gamma, beta = _bn_vec(gamma, C, "gamma"), _bn_vec(beta, C, "beta")
+    if residual is not None:
+        residual = _dev(residual)
+        if residual.shape != x.shape:
+            raise RuntimeError("batch_norm: residual has shape %s, expected %s" % (tuple(residual.shape), tuple(x.shape)))
+    for name, t in (("running_mean", running_mean), ("running_var", running_var)):
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (C,)):
+            raise RuntimeError("batch_norm: %s must be a contiguous float32 [%d] tensor on the HIP device" % (name, C))
+    y = torch.empty_like(x)
+    mean = torch.empty(C, device=x.device, dtype=torch.float32)
+    invstd = torch.empty_like(mean)
+    rc = L.cp_batchnorm_forward_nhwc(_stream(), _ptr(x), _ptr(gamma), _ptr(beta), _ptr(residual), _ptr(running_mean),
+                                     _ptr(running_var), _ptr(y), _ptr(mean), _ptr(invstd), *geo, int(bool(training)),
+                                     float(momentum), float(eps), int(act), _ptr(ws), nbytes)
+    _check(rc, "cp_batchnorm_forward_nhwc")
+    return y, mean, invstd
+
+
+def batch_norm_backward(x, grad_out, save_mean, save_invstd, gamma=None, y=None, training=True, need_x_grad=True,
+                        need_residual_grad=False, need_gamma_grad=True, need_beta_grad=True):
+    """Gradients of batch_norm_forward (cp_batchnorm_backward_nhwc) -> (grad_x, grad_residual, grad_gamma, grad_beta), None
+    where not asked for.  ``y``: the activated forward output when act was 1 (grad_out is gated by y > 0); without it
+    grad_residual is ``grad_out`` itself, not a copy.  Float32 and bitwise reproducible."""
+    L = lib()
+    geo, nbytes, ws = _bn_ws(L, x)
+    x, grad_out = _dev(x), _dev(grad_out)
+    y = _dev(y) if y is not None else None
+    C = geo[3]
+    for name, t in (("grad_out", grad_out), ("y", y)):
+        if t is not None and t.shape != x.shape:
+            raise RuntimeError("batch_norm_backward: %s has shape %s, expected %s" % (name, tuple(t.shape), tuple(x.shape)))
+    gamma, save_mean, save_invstd = _bn_vec(gamma, C, "gamma"), _bn_vec(save_mean, C, "save_mean"), _bn_vec(save_invstd, C, "save_invstd")
+    grad_x = torch.empty_like(x) if need_x_grad else None
+    grad_res = torch.empty_like(x) if need_residual_grad and y is not None else None
+    grad_g = torch.empty(C, device=x.device, dtype=torch.float32) if need_gamma_grad else None
+    grad_b = torch.empty(C, device=x.device, dtype=torch.float32) if need_beta_grad else None
+    if need_x_grad or grad_res is not None or need_gamma_grad or need_beta_grad:
+        rc = L.cp_batchnorm_backward_nhwc(_stream(), _ptr(x), _ptr(y), _ptr(grad_out), _ptr(gamma), _ptr(save_mean),
+                                          _ptr(save_invstd), _ptr(grad_x), _ptr(grad_res), _ptr(grad_g), _ptr(grad_b), *geo,
+                                          int(bool(training)), _ptr(ws), nbytes)
+        _check(rc, "cp_batchnorm_backward_nhwc")
+    if need_residual_grad and y is None:
+        grad_res = grad_out
+    return grad_x, grad_res, grad_g, grad_b
 
 
 def conv_transpose2d(x, w, scale=None, shift=None, act=0):

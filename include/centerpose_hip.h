@@ -319,6 +319,39 @@ int cp_conv2d_backward_nhwc(cp_stream_t stream, const float* x, const float* w, 
                             int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, void* workspace,
                             size_t workspace_bytes);
 
+/* ------------------------------------------------------------------------------------------
+ * BatchNorm2d for training, fused with the residual add and the ReLU — replaces the nn.BatchNorm2d(momentum=0.1) ->
+ *   `out += residual` -> ReLU chains of models/networks/pose_dla_dcn.py:40-62 (BasicBlock), pose_dla_dcn.py:150-168 (Root),
+ *   pose_dla_dcn.py:381 (the DCN's actf) and resnet_dcn.py, forward and backward:
+ *     y = act((x - mean) * invstd * gamma + beta [+ residual]),  act: 0 none, 1 relu.
+ * All tensors float32; x, residual, y, grad_out, grad_x, grad_residual [B,H,W,C] NHWC; gamma, beta, the statistics and their
+ * gradients [C].  C % 4 == 0, 4 <= C <= 4096; every pointer 16-byte aligned.  NULL gamma / beta mean 1 / 0 (affine=False).
+ * Forward, training != 0: mean and the biased variance of the batch (over B*H*W values per channel, at least 2) are
+ * computed without forming E[x^2] - mean^2 (pivoted sums merged by Chan's rule); save_mean = mean, save_invstd =
+ * 1 / sqrt(var + eps); running_mean / running_var, when given, become (1 - momentum) * r + momentum * stat, the variance
+ * unbiased by n / (n - 1).  Forward, training == 0: the running pair (required) gives save_mean and save_invstd and is left
+ * alone.  y must not alias x.
+ * Backward: g = grad_out, gated by y > 0 when y (the forward's ACTIVATED output) is given; xhat = (x - save_mean) * save_invstd;
+ * grad_beta = sum g, grad_gamma = sum g * xhat; grad_x = gamma * invstd * (g - grad_beta / n - xhat * grad_gamma / n) in
+ * training, gamma * invstd * g in evaluation; grad_residual = g.  Outputs are written, not accumulated; a NULL output is not
+ * computed and not touched.  (With y == NULL grad_residual is grad_out itself: callers pass NULL and reuse grad_out.)
+ * No atomics; every sum has a fixed order that depends on the shape alone: all outputs are bitwise reproducible call to call.
+ * Refused with CP_ERR_INVALID and a cp_last_error() text before any launch (the query returns 0 for the shape ones): a NULL
+ * pointer other than those named *_or_null, a workspace below the query, B / H / W < 1, C % 4 != 0 or outside 4..4096,
+ * training with B*H*W < 2, evaluation without the running pair, act outside {0, 1}, eps < 0, a tensor of 2^31 elements or
+ * more.  The query is host arithmetic, serves both calls and is monotone in B.  Launches on `stream`, never synchronises.
+ * ------------------------------------------------------------------------------------------ */
+size_t cp_batchnorm_workspace_bytes(int B, int H, int W, int C);
+int cp_batchnorm_forward_nhwc(cp_stream_t stream, const float* x, const float* gamma_or_null, const float* beta_or_null,
+                              const float* residual_or_null, float* running_mean_or_null, float* running_var_or_null,
+                              float* y, float* save_mean, float* save_invstd, int B, int H, int W, int C, int training,
+                              float momentum, float eps, int act, void* workspace, size_t workspace_bytes);
+int cp_batchnorm_backward_nhwc(cp_stream_t stream, const float* x, const float* y_or_null, const float* grad_out,
+                               const float* gamma_or_null, const float* save_mean, const float* save_invstd,
+                               float* grad_x_or_null, float* grad_residual_or_null, float* grad_gamma_or_null,
+                               float* grad_beta_or_null, int B, int H, int W, int C, int training, void* workspace,
+                               size_t workspace_bytes);
+
 /* Dense ConvTranspose2d(Cin, Cout, kernel 4, stride 2, padding 1, bias=False) followed by an optional per-channel affine
  * and ReLU (resnet_dcn.py's deconv `up` layers with their BatchNorm): x [B,H,W,Cin] NHWC, w [Cin,Cout,4,4] (PyTorch
  * layout, DEVICE), scale/shift [Cout] or NULL, out [B,2H,2W,Cout] NHWC.  act: 0 none, 1 relu.  Cin % 32 == 0.
