@@ -8,17 +8,19 @@
 //               rounded up to 32 on the MFMA path; the same pass leaves per-slab column sums, which bias_reduce_kernel adds in
 //               a fixed order into grad_bias.  Skipped when there is nothing to gate, pad or sum (grad_out is then read in place).
 //   1. wgrad    MFMA path: slab[s][co][k] = sum over the output rows of slab s of gs[q][co] * x[q * stride + tap - pad][c],
-//               k = tap * Cin + c (wgrad_kernel: v_mfma_f32_32x32x2_f32 with K = output pixels, heads_bwd.hip's wgrad0_kernel
-//               generalised over kernel size and stride); wgrad_reduce_kernel sums the slabs in a fixed order into the PyTorch
-//               layout.  Generic path: one thread per weight element and slab (wgrad_generic_kernel), the same reduction.
+//               k = tap * Cin + c (wgrad_kernel: v_mfma_f32_32x32x2_f32 with K = output pixels, kernels 1x1 and 3x3, strides 1
+//               and 2); wgrad_reduce_kernel sums the slabs in a fixed order into the PyTorch layout.  Generic path: one thread
+//               per weight element and slab (wgrad_generic_kernel), the same reduction.
 //   2. dgrad    stride 1, MFMA path: the exact-f32 implicit GEMM of igemm.hip on gs with the taps mirrored and the channel
 //               roles swapped (pack_dgrad_kernel).  Stride 2, MFMA path: dgrad_s2_kernel, one dense contraction per input
 //               pixel parity class (deconv16.hip's sub-pixel form), written straight into the interleaved grad_x.  Generic
 //               path: a gather per grad_x element (dgrad_generic_kernel).  Not launched when the caller passes no grad_x.
+// The MFMA weight gradient and the stride-1 data gradient are also the library's only ones: cp_launch_conv_wgrad and
+// cp_launch_conv_dgrad_pack / _s1 (cp_common.h) are what step 1 and 2 call, and what heads_bwd.hip calls for its 3x3 layer.
+#include "engine_model.h"
 #include "igemm_common.h"
 
 #include <algorithm>
-#include <cstring>
 
 namespace {
 
@@ -168,9 +170,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void w
 }
 
 // grad_w[co][c][tap] = the slabs [co][tap * Cin + c] (co < Cout of CoP rows), summed in bias_reduce_kernel's two-level order;
-// threads walk the slabs' own element order (whole 128-byte lines per slab) and scatter the one write
+// threads walk the slabs' own element order (whole 128-byte lines per slab) and scatter the one write.  `accum`: the value
+// already in grad_w is added last, to the finished sum of the slabs (a caller that works through its batch in chunks: chunks
+// in chunk order); without it the slabs' sum is stored as it is.
 __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ slab, float* __restrict__ gw, int nslab, int Cout,
-                                                           int CoP, int Cin, int taps) {
+                                                           int CoP, int Cin, int taps, int accum) {
     __shared__ float red[256];
     const size_t TC = (size_t)taps * Cin, n = (size_t)Cout * TC, ss = (size_t)CoP * TC;
     const int el = threadIdx.x & 31, sl = threadIdx.x >> 5;
@@ -186,7 +190,8 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
             for (int j = 1; j < 8; ++j) t += red[j * 32 + el];
             const size_t h = i / TC;
             const int k = (int)(i - h * TC), tap = k / Cin, c = k - tap * Cin;
-            gw[(h * Cin + c) * taps + tap] = t;
+            float* dst = gw + (h * Cin + c) * taps + tap;
+            *dst = accum ? *dst + t : t;
         }
         __syncthreads();
     }
@@ -384,12 +389,24 @@ inline size_t al(size_t x) { return (x + 255) / 256 * 256; }
 inline bool ok() { return hipGetLastError() == hipSuccess; }
 inline int nh_of(int c) { return c % 128 == 0 ? 4 : c % 64 == 0 ? 2 : 1; }
 
+// Weight-gradient slabs of whole output rows: `ns` of them wanted, at most 64 MiB and at most one per row
+ConvWgradPlan slab_plan(size_t rows, size_t ns, size_t wbytes, int jobs) {
+    ns = std::min(ns, std::max<size_t>(1, ((size_t)64 << 20) / wbytes));
+    ns = std::max<size_t>(1, std::min(ns, rows));
+    ConvWgradPlan P;
+    P.jobs = jobs;
+    P.rows_per_slab = (int)((rows + ns - 1) / ns);
+    P.slabs = (int)((rows + P.rows_per_slab - 1) / P.rows_per_slab);
+    P.slab_bytes = ns * wbytes;  // (the slab count's upper bound: monotone in rows)
+    return P;
+}
+
 struct Plan {
     bool mfma;
-    int Ho, Wo, CoP, cpad, taps;
-    int st_ct, st_px, st_slabs;      // stage_kernel: channel lanes, pixels per slab, slabs
-    int wg_rows, wg_slabs, wg_jobs;  // weight gradient: output rows per slab, slabs, wave jobs (MFMA path)
-    size_t gs, part, slab, wB, wB_bytes, total;
+    int Ho, Wo, CoP, taps;
+    int st_ct, st_px, st_slabs;  // stage_kernel: channel lanes, pixels per slab, slabs
+    ConvWgradPlan wg;            // weight gradient, either path
+    size_t gs, part, slab, wB, total;
 };
 
 Plan plan(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, bool need_gx) {
@@ -399,7 +416,6 @@ Plan plan(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, in
     P.Wo = (W + 2 * pad - KW) / stride + 1;
     P.taps = KH * KW;
     P.CoP = P.mfma ? (Cout + 31) / 32 * 32 : Cout;
-    P.cpad = (Cin + cp_conv_tile_n(Cin) - 1) / cp_conv_tile_n(Cin) * cp_conv_tile_n(Cin);
     const size_t Q = (size_t)B * P.Ho * P.Wo, rows = (size_t)B * P.Ho;
     int ct = 1;
     while (ct < P.CoP && ct < 64) ct <<= 1;
@@ -408,29 +424,16 @@ Plan plan(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, in
     P.st_px = (int)((Q + ss - 1) / ss);
     P.st_slabs = (int)((Q + P.st_px - 1) / P.st_px);
     const size_t wbytes = (size_t)P.CoP * P.taps * Cin * 4;
-    size_t ns;
-    if (P.mfma) {  // about two waves per SIMD; slabs of whole output rows, at most 64 MiB of them
-        const int KT = P.taps * Cin / 32;
-        P.wg_jobs = (P.CoP / (32 * nh_of(P.CoP))) * ((KT + 1) / 2);
-        ns = std::min<size_t>(512, (2048 + P.wg_jobs - 1) / P.wg_jobs);
-    } else {
-        P.wg_jobs = 0;
-        ns = 64;
-    }
-    ns = std::min(ns, std::max<size_t>(1, ((size_t)64 << 20) / wbytes));
-    ns = std::max<size_t>(1, std::min(ns, rows));
-    P.wg_rows = (int)((rows + ns - 1) / ns);
-    P.wg_slabs = (int)((rows + P.wg_rows - 1) / P.wg_rows);
-    P.wB_bytes = !need_gx || !P.mfma ? 0 : stride == 1 ? (size_t)P.taps * P.CoP * P.cpad * 4 : wbytes;
+    P.wg = P.mfma ? cp_conv_wgrad_plan(rows, Cin, P.CoP, P.taps) : slab_plan(rows, 64, wbytes, 0);
     size_t o = 0;
     P.gs = o;
     o += al(Q * P.CoP * 4);
     P.part = o;
-    o += al(ss * P.CoP * 4);  // (the slab counts' upper bounds: monotone in B)
+    o += al(ss * P.CoP * 4);  // (the slab count's upper bound: monotone in B)
     P.slab = o;
-    o += al(ns * wbytes);
+    o += al(P.wg.slab_bytes);
     P.wB = o;
-    o += al(P.wB_bytes);
+    o += al(!need_gx || !P.mfma ? 0 : stride == 1 ? cp_conv_dgrad_pack_bytes(Cin, P.CoP, P.taps) : wbytes);
     P.total = o;
     return P;
 }
@@ -439,6 +442,58 @@ Plan plan(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, in
 
 bool cp_conv_backward_mfma(int Cin, int KH, int KW, int stride, int pad) {
     return KH == KW && (KH == 1 || KH == 3) && (stride == 1 || stride == 2) && pad == KH / 2 && Cin % 32 == 0;
+}
+
+// about two waves per SIMD, at most 512 slabs
+ConvWgradPlan cp_conv_wgrad_plan(size_t rows, int Cin, int CoP, int taps) {
+    const int KT = taps * Cin / 32, jobs = (CoP / (32 * nh_of(CoP))) * ((KT + 1) / 2);
+    return slab_plan(rows, std::min<size_t>(512, (2048 + jobs - 1) / jobs), (size_t)CoP * taps * Cin * 4, jobs);
+}
+
+int cp_launch_conv_wgrad(hipStream_t s, const ConvBwdArgs& a, const float* gs, int CoP, const ConvWgradPlan& P, float* slab,
+                         int accum) {
+    const int Ho = (a.H + 2 * a.pad - a.KH) / a.stride + 1, Wo = (a.W + 2 * a.pad - a.KW) / a.stride + 1;
+    const int taps = a.KH * a.KW, rows = a.B * Ho, slabs = (rows + P.rows_per_slab - 1) / P.rows_per_slab;
+    const dim3 wg((P.jobs + 3) / 4, 1, slabs);
+#define CP_WGRAD(NH)                                                                                                            \
+    hipLaunchKernelGGL(wgrad_kernel<NH>, wg, dim3(256), 0, s, gs, a.x, slab, rows, Ho, Wo, a.H, a.W, a.Cin, CoP, a.KW, taps, a.stride, \
+                       a.pad, P.rows_per_slab)
+    switch (nh_of(CoP)) {
+        case 4: CP_WGRAD(4); break;
+        case 2: CP_WGRAD(2); break;
+        default: CP_WGRAD(1);
+    }
+#undef CP_WGRAD
+    if (!ok()) return CP_ERR_LAUNCH;
+    const size_t rg = std::min<size_t>(((size_t)a.Cout * taps * a.Cin + 31) / 32, 8192);
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)rg), dim3(256), 0, s, (const float*)slab, a.gw, slabs, a.Cout, CoP, a.Cin,
+                       taps, accum);
+    return ok() ? CP_OK : CP_ERR_LAUNCH;
+}
+
+// wB [taps CoP][cpad], cpad = Cin rounded up to the N tile of the convolution that reads it
+static int dgrad_cpad(int Cin) { return (int)cp_engine::align_up((size_t)Cin, cp_conv_tile_n(Cin)); }
+
+size_t cp_conv_dgrad_pack_bytes(int Cin, int CoP, int taps) { return (size_t)taps * CoP * dgrad_cpad(Cin) * 4; }
+
+int cp_launch_conv_dgrad_pack(hipStream_t s, const float* w, float* wB, int Cin, int Cout, int CoP, int taps) {
+    if (hipMemsetAsync(wB, 0, cp_conv_dgrad_pack_bytes(Cin, CoP, taps), s) != hipSuccess) return CP_ERR_LAUNCH;
+    hipLaunchKernelGGL(pack_dgrad_kernel, dim3(256), dim3(256), 0, s, w, wB, Cout, CoP, Cin, taps, dgrad_cpad(Cin));
+    return ok() ? CP_OK : CP_ERR_LAUNCH;
+}
+
+int cp_launch_conv_dgrad_s1(hipStream_t s, const ConvBwdArgs& a, const float* gs, int CoP, const float* wB, const float* res) {
+    // (stride 1, pad K / 2: the output grid is the input grid, and the operand is a [a.Cin][CoP][KH][KW] weight)
+    ConvParams d = cp_engine::conv_params(a.B, a.H, a.W, &gs, &CoP, 1,
+                                          cp_engine::conv_w_f32((float*)wB, nullptr, nullptr, CoP, a.Cin, a.KH, a.KW), 1, a.pad,
+                                          CP_ACT_NONE);
+    d.dbg = 0;  // cp_set_debug's switches choose among inference kernels for A/B runs: a gradient does not depend on them
+    d.res = res;
+    d.res_ld = a.Cin;
+    d.out = a.gx;
+    d.store = CP_STORE_NHWC;
+    d.ldo = a.Cin;
+    return cp_launch_conv(d, s);
 }
 
 size_t cp_conv_backward_ws_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int need_grad_x) {
@@ -469,27 +524,14 @@ int cp_launch_conv_backward(hipStream_t s, const ConvBwdArgs& a, void* ws) {
     }
     // 1. grad_w
     if (P.mfma) {
-        const dim3 wg((P.wg_jobs + 3) / 4, 1, P.wg_slabs);
-#define CP_WGRAD(NH)                                                                                                        \
-    hipLaunchKernelGGL(wgrad_kernel<NH>, wg, dim3(256), 0, s, gs, a.x, slab, rows, Ho, Wo, H, W, Cin, CoP, a.KW, taps, a.stride, \
-                       a.pad, P.wg_rows)
-        switch (nh_of(CoP)) {
-            case 4: CP_WGRAD(4); break;
-            case 2: CP_WGRAD(2); break;
-            default: CP_WGRAD(1);
-        }
-#undef CP_WGRAD
-        if (!ok()) return CP_ERR_LAUNCH;
-        const size_t rg = std::min<size_t>(((size_t)Cout * taps * Cin + 31) / 32, 8192);
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)rg), dim3(256), 0, s, (const float*)slab, a.gw, P.wg_slabs, Cout, CoP,
-                           Cin, taps);
-        if (!ok()) return CP_ERR_LAUNCH;
+        const int rc = cp_launch_conv_wgrad(s, a, gs, CoP, P.wg, slab, 0);
+        if (rc != CP_OK) return rc;
     } else {
         const int n = Cout * Cin * taps;
-        hipLaunchKernelGGL(wgrad_generic_kernel, dim3((n + 255) / 256, P.wg_slabs), dim3(256), 0, s, gs, a.x, slab, rows, Ho, Wo, H,
-                           W, Cin, Cout, a.KH, a.KW, a.stride, a.pad, P.wg_rows);
+        hipLaunchKernelGGL(wgrad_generic_kernel, dim3((n + 255) / 256, P.wg.slabs), dim3(256), 0, s, gs, a.x, slab, rows, Ho, Wo, H,
+                           W, Cin, Cout, a.KH, a.KW, a.stride, a.pad, P.wg.rows_per_slab);
         if (!ok()) return CP_ERR_LAUNCH;
-        hipLaunchKernelGGL(slab_reduce_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (const float*)slab, a.gw, P.wg_slabs, n);
+        hipLaunchKernelGGL(slab_reduce_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (const float*)slab, a.gw, P.wg.slabs, n);
         if (!ok()) return CP_ERR_LAUNCH;
     }
     // 2. grad_x
@@ -500,26 +542,11 @@ int cp_launch_conv_backward(hipStream_t s, const ConvBwdArgs& a, void* ws) {
                            a.gx, B, H, W, Cin, Cout, Ho, Wo, a.KH, a.KW, a.stride, a.pad);
         return ok() ? CP_OK : CP_ERR_LAUNCH;
     }
-    if (hipMemsetAsync(wB, 0, P.wB_bytes, s) != hipSuccess) return CP_ERR_LAUNCH;
     if (a.stride == 1) {
-        hipLaunchKernelGGL(pack_dgrad_kernel, dim3(256), dim3(256), 0, s, a.w, wB, Cout, CoP, Cin, taps, P.cpad);
-        if (!ok()) return CP_ERR_LAUNCH;
-        ConvParams d;
-        memset(&d, 0, sizeof(d));
-        d.nsrc = 1;
-        d.src[0] = gs;
-        d.src_c[0] = d.Cin = CoP;
-        d.B = B, d.H = d.Ho = H, d.W = d.Wo = W;  // (stride 1, pad K / 2: the output grid is the input grid)
-        d.KH = a.KH, d.KW = a.KW, d.stride = 1, d.pad = a.pad;
-        d.K = d.Kpad = taps * CoP;
-        d.wp = wB;
-        d.Cout = Cin, d.CoutPad = P.cpad;
-        d.act = CP_ACT_NONE;
-        d.out = a.gx;
-        d.store = CP_STORE_NHWC;
-        d.ldo = Cin;
-        return cp_launch_conv(d, s);
+        const int rc = cp_launch_conv_dgrad_pack(s, a.w, wB, Cin, Cout, CoP, taps);
+        return rc != CP_OK ? rc : cp_launch_conv_dgrad_s1(s, a, gs, CoP, wB, nullptr);
     }
+    if (hipMemsetAsync(wB, 0, (size_t)CoP * taps * Cin * 4, s) != hipSuccess) return CP_ERR_LAUNCH;
     hipLaunchKernelGGL(pack_dgrad_s2_kernel, dim3(256), dim3(256), 0, s, a.w, wB, Cout, CoP, Cin, taps);
     if (!ok()) return CP_ERR_LAUNCH;
     const int M0 = B * ((H + 1) / 2) * ((W + 1) / 2);  // the even / even class has the most pixels

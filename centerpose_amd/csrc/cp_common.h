@@ -452,6 +452,22 @@ struct ConvBwdArgs {
 bool cp_conv_backward_mfma(int Cin, int KH, int KW, int stride, int pad);  // the geometry takes the MFMA kernels
 size_t cp_conv_backward_ws_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int need_grad_x);
 int cp_launch_conv_backward(hipStream_t s, const ConvBwdArgs& a, void* ws);
+// Its two MFMA contractions (cp_conv_backward_mfma geometries) as building blocks: cp_launch_conv_backward is made of them, and
+// heads_bwd.hip runs them per head and chunk of images.  They read the geometry, x, gw and gx of `a` and, in place of a.go,
+// gs [B,Ho,Wo,CoP]: grad_out already gated, CoP = Cout rounded up to 32 with zeros in the pad lanes.
+struct ConvWgradPlan {
+    int rows_per_slab, slabs, jobs;  // output rows per slab, slabs, wave jobs of wgrad_kernel
+    size_t slab_bytes;               // the slab buffer (an upper bound of slabs x CoP x taps Cin x 4, monotone in rows)
+};
+ConvWgradPlan cp_conv_wgrad_plan(size_t rows, int Cin, int CoP, int taps);  // rows = B x Ho
+// a.gw = (accum ? a.gw : 0) + the slabs' sum.  P may have been planned for more rows than a.B x Ho (a partial last chunk).
+int cp_launch_conv_wgrad(hipStream_t s, const ConvBwdArgs& a, const float* gs, int CoP, const ConvWgradPlan& P, float* slab,
+                         int accum);
+// Stride 1: w in the data gradient's operand form wB (any contents before), once per weight; then a.gx = gs (*) w^T (+ res
+// [B,H,W,Cin], which may be a.gx itself) per launch
+size_t cp_conv_dgrad_pack_bytes(int Cin, int CoP, int taps);
+int cp_launch_conv_dgrad_pack(hipStream_t s, const float* w, float* wB, int Cin, int Cout, int CoP, int taps);
+int cp_launch_conv_dgrad_s1(hipStream_t s, const ConvBwdArgs& a, const float* gs, int CoP, const float* wB, const float* res);
 
 // ---- BatchNorm2d, training and evaluation, fused with the residual add and ReLU (batchnorm.hip): float32 NHWC ----
 struct BnFwdArgs {

@@ -4,6 +4,7 @@
 //   engine_forward.hip  the forward pass and its kernel dispatch (forward_impl)
 //   ops.hip             the stand-alone operators (cp_conv2d_nhwc, cp_conv_transpose2d_nhwc, cp_dcnv2_forward / _backward, cp_pose_heads_*)
 //   engine.hip          the model's run-time C ABI and the one-line wrappers of the other modules
+//   heads_bwd.hip, conv_bwd.hip  take conv_w_f32 / conv_params for the igemm.hip launches of their backward passes
 // Everything here has C++ linkage (only the C ABI of include/centerpose_hip.h is exported unmangled).
 #pragma once
 #include "../../include/centerpose_hip.h"
@@ -311,6 +312,23 @@ inline int timed(cp_model* m, hipStream_t s, D&& describe, F&& launch) {
     (void)hipEventRecord(r.e1, s);
     m->prof.push_back(r);
     return rc;
+}
+
+// ConvW of a float32 weight as cp_launch_pack_weight lays it out in a caller's buffer: wp [Kpad][CoutPad], K = KH KW Cin rounded
+// up to the kernels' K step and Cout to the launch's N tile; no f16x3 operands (pack_f16x3 of ops.hip adds them)
+inline ConvW conv_w_f32(float* wp, const float* scale, const float* shift, int Cin, int Cout, int KH, int KW) {
+    ConvW w;
+    w.wp = wp;
+    w.scale = scale;
+    w.shift = shift;
+    w.Cin = w.CinP = Cin;
+    w.Cout = Cout;
+    w.CoutPad = (int)align_up((size_t)Cout, cp_conv_tile_n(Cout));
+    w.KH = KH;
+    w.KW = KW;
+    w.K = KH * KW * Cin;
+    w.Kpad = (int)align_up((size_t)w.K, 16);
+    return w;
 }
 
 // The one place a ConvParams is built.  Zeroed, then what every convolution launch has in common: the sources (a virtual

@@ -293,21 +293,8 @@ int cp_pose_heads_forward(cp_stream_t stream, const float* feat, int n, const fl
     const bool f16x3 = g_default_precision == CP_PREC_F16X3;
     for (int i = 0; i < n; ++i) {
         const int cls = classes[i];
-        ConvW c0, c1;
-        c0.Cin = c0.CinP = Cin;
-        c0.Cout = hid;
-        c0.CoutPad = (int)align_up((size_t)hid, cp_conv_tile_n(hid));
-        c0.KH = c0.KW = 3;
-        c0.K = c0.Kpad = 9 * Cin;
-        c0.wp = r.wp0;
-        c0.shift = r.shift0;
-        c1.Cin = c1.CinP = hid;
-        c1.Cout = cls;
-        c1.CoutPad = (int)align_up((size_t)cls, cp_conv_tile_n(cls));
-        c1.KH = c1.KW = 1;
-        c1.K = c1.Kpad = hid;
-        c1.wp = r.wp1;
-        c1.shift = r.shift1;
+        ConvW c0 = conv_w_f32(r.wp0, nullptr, r.shift0, Cin, hid, 3, 3);
+        const ConvW c1 = conv_w_f32(r.wp1, nullptr, r.shift1, hid, cls, 1, 1);
         if (hipMemsetAsync(r.wp0, 0, (char*)r.f16.hi - (char*)r.wp0, s) != hipSuccess) return CP_ERR_LAUNCH;
         int rc = cp_launch_pack_weight(w0[i], r.wp0, hid, Cin, 9, Cin, c0.CoutPad, 0, s);
         if (rc == CP_OK) rc = cp_launch_pack_weight(w1[i], r.wp1, cls, hid, 1, hid, c1.CoutPad, 0, s);
@@ -424,17 +411,7 @@ int cp_conv2d_nhwc(cp_stream_t stream, const float* x, const float* w, const flo
     if (workspace_bytes < c.off) return fail(CP_ERR_INVALID, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
     const int bn = cp_conv_tile_n(Cout);
-    ConvW cw;
-    cw.Cin = cw.CinP = Cin;
-    cw.Cout = Cout;
-    cw.CoutPad = (int)align_up(Cout, bn);
-    cw.KH = KH;
-    cw.KW = KW;
-    cw.K = KH * KW * Cin;
-    cw.Kpad = (int)align_up(cw.K, 16);
-    cw.wp = r.wp;
-    cw.scale = scale;
-    cw.shift = shift;
+    ConvW cw = conv_w_f32(r.wp, scale, shift, Cin, Cout, KH, KW);
     // scale/shift are read up to CoutPad: only allow un-padded Cout when they are given
     if ((scale || shift) && cw.CoutPad != Cout) return fail(CP_ERR_INVALID, "scale/shift need Cout % tile_n == 0");
     if (hipMemsetAsync(r.wp, 0, (size_t)cw.Kpad * cw.CoutPad * sizeof(float), s) != hipSuccess) return CP_ERR_LAUNCH;
@@ -573,14 +550,7 @@ int cp_dcnv2_forward(cp_stream_t stream, const float* input, const float* weight
     const DcnWs r = dcn_carve(c, B, C, H, W, Co);
     if (workspace_bytes < c.off) return fail(CP_ERR_INVALID, "workspace too small");
     const size_t px = (size_t)B * H * W;
-    ConvW cw;
-    cw.Cin = cw.CinP = C;
-    cw.Cout = Co;
-    cw.CoutPad = (int)align_up((size_t)Co, cp_conv_tile_n(Co));
-    cw.KH = cw.KW = 3;
-    cw.K = cw.Kpad = 9 * C;
-    cw.wp = r.wp;
-    cw.shift = r.shift;
+    ConvW cw = conv_w_f32(r.wp, nullptr, r.shift, C, Co, 3, 3);
     int rc = cp_launch_nchw_to_nhwc(input, r.x, B, C, H, W, C, s);
     if (rc != CP_OK) return rc;
     hipLaunchKernelGGL(dcn_offmask_pack_kernel, dim3(2048), dim3(256), 0, s, offset, mask, r.om, B, H * W);

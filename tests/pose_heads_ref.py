@@ -155,3 +155,13 @@ DYADIC_SHAPES = {
     "classes_1": (1, 64, 64, 16, 16, (1,)),
     "classes_64": (1, 64, 64, 16, 16, (64,)),
 }
+
+# ---- single-head cases on which cp_pose_heads_backward and cp_conv2d_backward_nhwc must agree bit for bit: the heads' 3x3 layer
+# runs conv_bwd.hip's weight and data gradient, so the same grad_hidden gives the same bits.  The smallest shapes that reach each
+# accumulator count of the weight-gradient kernel (hid 96 / 64 / 256: NH = 1 / 2 / 4), with ragged rows and a slab that spans images
+SHARED_CONV_CASES = {
+    # name: (seed, B, Cin, hid, H, W, classes)
+    "nh2_two_images_13x19": (101, 2, 64, 64, 13, 19, (1,)),
+    "nh1_9x7": (102, 1, 128, 96, 9, 7, (1,)),
+    "nh4_8x10": (103, 1, 64, 256, 8, 10, (1,)),
+}

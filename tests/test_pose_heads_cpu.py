@@ -228,3 +228,10 @@ def test_dyadic_generator_holds_for_every_gpu_shape(name):
     assert len(case.params) == len(classes) and case.feat.shape == (B, Cin, H, W)
     smallest = min(float(torch.nn.functional.conv2d(case.feat, w0, b0, padding=1).abs().min()) for w0, b0, _, _ in case.params)
     assert smallest >= 1 / 32
+
+
+@pytest.mark.parametrize("name", sorted(R.SHARED_CONV_CASES))
+def test_dyadic_generator_holds_for_the_shared_conv_cases(name):
+    seed, B, Cin, hid, H, W, classes = R.SHARED_CONV_CASES[name]
+    case = R.dyadic_case(seed, B, Cin, hid, H, W, classes)   # asserts inside
+    assert classes == (1,) and len(case.params) == 1 and case.feat.shape == (B, Cin, H, W)

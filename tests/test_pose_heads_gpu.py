@@ -148,6 +148,29 @@ def test_chunk_boundary_inside_the_batch(device):
         assert torch.equal(one[0], gfeat[b]), b
 
 
+@pytest.mark.parametrize("name", sorted(R.SHARED_CONV_CASES))
+def test_heads_and_conv2d_backward_share_one_implementation(device, name):
+    """The heads' 3x3 layer goes through conv_bwd.hip: with one class, grad_hidden is one rounded float32 product gated by an
+    exactly known hidden value, so torch reproduces it bit for bit, and cp_conv2d_backward_nhwc on it must return the bits of
+    grad_w0 and grad_feat (same kernels, same plan, same order)."""
+    seed, *shape = R.SHARED_CONV_CASES[name]
+    case = R.dyadic_case(seed, *shape)
+    feat, params, gos = _to(device, case)
+    w0, b0, w1, _ = case.params[0]
+    h = torch.nn.functional.conv2d(case.feat, w0, b0, padding=1)   # exact (check_dyadic)
+    gh = torch.where(h > 0, case.grad_outs[0] * w1.view(1, -1, 1, 1), torch.zeros(()))
+    gfeat, grads = hip.pose_heads_backward(feat, params, gos)
+    gx, gw, _ = hip.conv2d_backward(feat.permute(0, 2, 3, 1), params[0][0], gh.to(device).permute(0, 2, 3, 1).contiguous(),
+                                    stride=1, pad=1, need_bias_grad=False)
+    ref = R.reference(case.feat, case.params, case.grad_outs)["grads"][0][0]
+    err, tol = float((grads[0][0].cpu().double() - ref).abs().max()), GRAD_TOL * float(ref.abs().max())
+    print("%s: grad_w0 err %.3e (tol %.3e); differing elements: grad_w0 %d, grad_feat %d"
+          % (name, err, tol, int((grads[0][0] != gw).sum()), int((gfeat.permute(0, 2, 3, 1) != gx).sum())))
+    assert err <= tol   # the equality below cannot be met by two equally wrong results
+    assert torch.equal(grads[0][0], gw)
+    assert torch.equal(gfeat.permute(0, 2, 3, 1), gx)
+
+
 def _model(arch, device, tracking=False):
     heads = synth.HEADS_POSE
     opt = None
