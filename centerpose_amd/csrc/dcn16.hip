@@ -22,7 +22,7 @@
 // instruction = 1152 clk, i.e. <= 245 (N 64) / 490 (N 128) TFLOP/s however well the loads overlap.
 // Same tiles, LDS layout (unpadded 64-byte rows, XOR-swizzled 16-byte chunks), tile map, epilogue and operand
 // pre-scaling (ConvParams::in_amax) as igemm16.hip; results are bit-identical to the un-pipelined loop this replaced.
-#include "igemm16_common.h"
+#include "dcn_patch_common.h"
 
 namespace {
 
@@ -83,20 +83,9 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void dcn16_kernel(const ConvPara
                 const int kh = tap / 3, kw = tap - kh * 3;
                 const float h_im = (float)(y - 1 + kh) + dh;
                 const float w_im = (float)(x - 1 + kw) + dw;
-                if (h_im > -1.f && w_im > -1.f && h_im < (float)p.H && w_im < (float)p.W) {
-                    const int h_lo = (int)floorf(h_im), w_lo = (int)floorf(w_im);
-                    const int h_hi = h_lo + 1, w_hi = w_lo + 1;
-                    const float lh = h_im - (float)h_lo, lw = w_im - (float)w_lo;
-                    const float hh = 1.f - lh, hw = 1.f - lw;
-                    int vm = 0;
-                    if (h_lo >= 0 && w_lo >= 0) vm |= 1;
-                    if (h_lo >= 0 && w_hi <= p.W - 1) vm |= 2;
-                    if (h_hi <= p.H - 1 && w_lo >= 0) vm |= 4;
-                    if (h_hi <= p.H - 1 && w_hi <= p.W - 1) vm |= 8;
-                    base = (((b * p.H + h_lo) * p.W + w_lo) * cb) | vm;  // may be "before" the tensor when h_lo / w_lo = -1:
-                                                                          // only valid corners are ever dereferenced
-                    w1 = hh * hw * mk; w2 = hh * lw * mk; w3 = lh * hw * mk; w4 = lh * lw * mk;
-                }
+                const DcnCorner s = dcn_corner_sample(h_im, w_im, mk, b, p.H, p.W, cb);
+                base = s.base;
+                w1 = s.w1; w2 = s.w2; w3 = s.w3; w4 = s.w4;
             }
             tab_base[e] = base;
             *reinterpret_cast<float4*>(tab_w[e]) = make_float4(w1, w2, w3, w4);
@@ -193,7 +182,6 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void dcn16_kernel(const ConvPara
 #pragma unroll
         for (int j = 0; j < A_SLOTS; ++j) {
             // fma(w4, v4, fma(w3, v3, fma(w2, v2, w1 * v1))) per component, two components per v_pk_fma_f32
-            typedef float f32x2 __attribute__((ext_vector_type(2)));
             const f32x2 w1 = {d_w[j][0], d_w[j][0]}, w2 = {d_w[j][1], d_w[j][1]}, w3 = {d_w[j][2], d_w[j][2]},
                         w4 = {d_w[j][3], d_w[j][3]};
             const float4 v1 = raw[j][0], v2 = raw[j][1], v3 = raw[j][2], v4 = raw[j][3];

@@ -24,22 +24,17 @@
 //     wave's gather / blend overlaps another's MFMAs.  (The first version kept the weights in a double-buffered LDS
 //     tile with a barrier per tap: 19 % MFMA busy, waves 45 % parked at s_waitcnt / s_barrier.)
 //   * The gather of K step u + 1 is issued before the blend / MFMAs of step u (two register sets).
-//   * The bilinear set-up (corner address, 4 weights with mask and activation pre-scale folded in) of a lane's 9 taps
-//     lives in 45 registers for the whole kernel.  The two lanes that share a pixel (the two 8-channel halves of a
-//     K step) compute 5 and 4 taps each and swap the results with v_permlane32_swap.
-//   * Samples whose 2x2 corner block leaves the staged halo (|offset| > 2..3 px at the patch border: 2 % of samples
-//     at sigma = 1.5 px, 7 % at 1.9 -- the synthetic network's layers measure 1.4 .. 1.93) are "exceptions": the
-//     set-up appends them (corner, 4 weights) to a block list (LDS atomic) and takes weights (1, 0, 0, 0) itself; the
-//     staging blends each one's four corners per chunk into a spare patch pixel, which the K loop then reads like any
-//     other corner -- no branch.  A block with more than ECAP = 184 exceptions (offsets of sigma > 3 px everywhere)
-//     switches, as a whole, to gathering through buffer loads like dcn16.hip (slower, same results).
+//   * The bilinear set-up (5 + 4 taps by the two lanes that share a pixel, swapped), the exception samples (2 x 2 corner blocks
+//     that leave the staged halo: |offset| > 2..3 px at the patch border, 2 % of samples at sigma = 1.5 px, 7 % at 1.9 -- the
+//     synthetic network's layers measure 1.4 .. 1.93 -- blended into one of ECAP = 184 spare pixels by the staging), the block-wide
+//     switch to buffer loads beyond that capacity, the blend + split and the MFMA term order are dcn_patch_common.h's, shared with
+//     dcn16s.hip and dcn16t.hip.
 // K order is (32-channel chunk, tap, 16-channel half): same products as dcn16.hip, different summation order.
 // LDS: (308 + 207) x 144 B + 4.4 KB of lists = 78.6 KB => two blocks per CU, whose staging / compute phases overlap.
 #include <type_traits>
 
+#include "dcn_patch_common.h"
 #include "patch16_common.h"
-
-
 
 namespace {
 
@@ -51,28 +46,13 @@ constexpr int ECAP = 184;                                              // except
 constexpr int NPIX_ALL = NPIX + ECAP + PW + 1;                         // + the 3 other "corners" of the last one: 515
 constexpr int NSTEP = 18;                                              // K steps (16 channels of one tap) per chunk
 
-__device__ __forceinline__ float4 buf_ld4s(__amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, soff, 0);
-    return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-}
+// LDS geometry for dcn_setup_taps: counted in patch pixels (x PSTR after the swap)
+struct PGeo {
+    static constexpr int PH = ::PH, PW = ::PW, HALO = ::HALO, ECAP = ::ECAP;
+    static __device__ __forceinline__ int corner(int qy, int qx) { return qy * ::PW + qx; }
+    static __device__ __forceinline__ int spare(int e) { return NPIX + e; }
+};
 
-// both 32-lane halves of `v` for every lane: {lower half's value, upper half's value}
-__device__ __forceinline__ void both_halves5(const uint32_t (&v)[5], uint32_t (&lo)[5], uint32_t (&hi)[5]) {
-    // v_permlane32_swap_b32 vdst, vsrc exchanges vdst[32..63] with vsrc[0..31]; with both operands holding v every lane ends up
-    // with {the lower half's value, the upper half's value}.  Written out by hand, each swap on its own pair of registers with
-    // the wait states the hazard table asks for inside the statement (VALU write -> v_permlane*_swap read: 2).  (Round 4 padded
-    // these swaps while hunting wrong set-up values; the swaps were innocent -- the cause was a packed-f32 op with a set op_sel
-    // bit, profiles/NOTES.md round 5 -- but the hand-written form costs nothing and stays.)
-    uint32_t a0 = v[0], a1 = v[1], a2 = v[2], a3 = v[3], a4 = v[4], b0 = v[0], b1 = v[1], b2 = v[2], b3 = v[3], b4 = v[4];
-    asm volatile("s_nop 4\n\tv_permlane32_swap_b32 %0, %5\n\ts_nop 1\n\tv_permlane32_swap_b32 %1, %6\n\ts_nop 1\n\t"
-                 "v_permlane32_swap_b32 %2, %7\n\ts_nop 1\n\tv_permlane32_swap_b32 %3, %8\n\ts_nop 1\n\t"
-                 "v_permlane32_swap_b32 %4, %9\n\ts_nop 4"
-                 : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(b0), "+v"(b1), "+v"(b2), "+v"(b3), "+v"(b4));
-    lo[0] = a0; lo[1] = a1; lo[2] = a2; lo[3] = a3; lo[4] = a4;
-    hi[0] = b0; hi[1] = b1; hi[2] = b2; hi[3] = b3; hi[4] = b4;
-}
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 template <int NT>
 __global__ __launch_bounds__(256, 2) void dcn16p_kernel(const ConvParams p, const int tiles_m, const int tiles_n) {
     typedef Frag<32> F;
@@ -123,74 +103,17 @@ __global__ __launch_bounds__(256, 2) void dcn16p_kernel(const ConvParams p, cons
     const unsigned rec = (unsigned)((b * p.H + y) * p.W + x) * 128u;  // the pixel's offset / mask record (32 floats)
     // this lane's share of the record: taps 5 lrow .. 5 lrow + 4 (slot 4 of the upper half is a dummy, tap "9")
     float od[12], omk[5];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const float4 v = buf_ld4(r_om, rec + (unsigned)lrow * 40u + 16u * i);
-        od[4 * i] = v.x; od[4 * i + 1] = v.y; od[4 * i + 2] = v.z; od[4 * i + 3] = v.w;
-    }
-    {
-        const float4 v = buf_ld4(r_om, rec + 72u + (unsigned)lrow * 20u);
-        omk[0] = v.x; omk[1] = v.y; omk[2] = v.z; omk[3] = v.w;
-        omk[4] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r_om, (int)(rec + 88u + (unsigned)lrow * 20u), 0, 0));
-    }
+    dcn_load_record(r_om, rec, lrow, od, omk);
     __syncthreads();  // exc_count = 0 is visible
 
     // ---- bilinear set-up (dcn_v2_im2col_cuda.cu:25-54, 150-187): 5 tap slots per lane, then both halves swap ----
     uint32_t sq[5], sw[5][4];  // patch pixel of corner (h_lo, w_lo); corner weights x mask x activation pre-scale
-    const float fy0 = (float)(y - 1), fx0 = (float)(x - 1);
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-        // tap 5 lrow + j = (kh, kw): lower half (0,0) (0,1) (0,2) (1,0) (1,1); upper half (1,2) (2,0) (2,1) (2,2) (-)
-        const float khf = lrow ? (float)((5 + j) / 3) : (float)(j / 3);
-        const float kwf = lrow ? (float)((5 + j) % 3) : (float)(j % 3);
-        float h_im = (fy0 + khf) + od[2 * j];
-        float w_im = (fx0 + kwf) + od[2 * j + 1];
-        const bool valid = h_im > -1.f && w_im > -1.f && h_im < (float)p.H && w_im < (float)p.W && !(lrow && j == 4);
-        h_im = valid ? h_im : 0.f;  // keeps the arithmetic below finite; its weights are zeroed through the mask
-        w_im = valid ? w_im : 0.f;
-        const float mk = valid ? omk[j] * afwd : 0.f;
-        const float fh = floorf(h_im), fw = floorf(w_im);
-        const int h_lo = (int)fh, w_lo = (int)fw;
-        const float lh = h_im - fh, lw = w_im - fw;
-        const float hh = 1.f - lh, hw = 1.f - lw;
-        sw[j][0] = __float_as_uint(hh * hw * mk);
-        sw[j][1] = __float_as_uint(hh * lw * mk);
-        sw[j][2] = __float_as_uint(lh * hw * mk);
-        sw[j][3] = __float_as_uint(lh * lw * mk);
-        const int qy = h_lo - (ty0 - HALO), qx = w_lo - (tx0 - HALO);
-        const bool inp = (unsigned)qy <= (unsigned)(PH - 2) && (unsigned)qx <= (unsigned)(PW - 2);
-        int q = inp ? qy * PW + qx : 0;
-        if (valid && !inp) {  // exception sample: file its corner and weights; the staging blends it into spare pixel e,
-                              // which this lane then reads with weights (1, 0, 0, 0)
-            const int e = atomicAdd(&exc_count, 1);
-            if (e < ECAP) {
-                exc_key[e] = ((h_lo + 1) << 16) | (w_lo + 1);
-                exc_goff[e] = ((b * p.H + h_lo) * p.W + w_lo) * cb;
-                *reinterpret_cast<float4*>(exc_w[e]) = make_float4(__uint_as_float(sw[j][0]), __uint_as_float(sw[j][1]),
-                                                                   __uint_as_float(sw[j][2]), __uint_as_float(sw[j][3]));
-                sw[j][0] = __float_as_uint(1.f);
-                sw[j][1] = sw[j][2] = sw[j][3] = 0u;
-                q = NPIX + e;
-            }
-        }
-        sq[j] = (uint32_t)q;
-    }
+    const DcnExcList exc = {exc_key, exc_goff, &exc_w[0][0], &exc_count};
+    dcn_setup_taps<PGeo>(od, omk, lrow, y, x, ty0, tx0, b, p.H, p.W, cb, afwd, exc, sq, sw);
     int addr[9];     // byte address in `patch` of corner (h_lo, w_lo) + this lane's 32-byte channel half; in the
                      // buffer-load mode: that corner's byte offset into the input tensor | 4 corner-validity bits
     f32x2 bw[9][2];  // {w1, w2}, {w3, w4}: corner weights x mask x activation pre-scale
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-        const uint32_t pack[5] = {sq[j], sw[j][0], sw[j][1], sw[j][2], sw[j][3]};
-        uint32_t lo[5], hi[5];
-        both_halves5(pack, lo, hi);
-        addr[j] = (int)lo[0] * PSTR + lrow * 32;
-        if (j < 4) addr[5 + j] = (int)hi[0] * PSTR + lrow * 32;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            bw[j][c >> 1][c & 1] = __uint_as_float(lo[1 + c]);
-            if (j < 4) bw[5 + j][c >> 1][c & 1] = __uint_as_float(hi[1 + c]);
-        }
-    }
+    dcn_expand_taps<PSTR>(sq, sw, lrow, addr, bw);
     __syncthreads();
     const int nexc_all = __builtin_amdgcn_readfirstlane(exc_count);  // scalar: the mode branches below stay uniform
     const bool slow = nexc_all > ECAP;                               // block-uniform
@@ -239,24 +162,8 @@ __global__ __launch_bounds__(256, 2) void dcn16p_kernel(const ConvParams p, cons
     // mfma_war_probe.hip finds no write-after-read hazard on MFMA operands -- and it measured the same in both places) and, in
     // the 128-wide kernel, the gather of the next step into the registers the blend has just freed.
     auto mma_step = [&](const float4 (&r)[4][2], const f32x2 (&w)[2], int s0, auto&& mid) {
-        // fma(w4, v4, fma(w3, v3, fma(w2, v2, w1 * v1))) per channel (dcn16.hip's order), two per v_pk_fma_f32
-        uint32_t hi[4], lo[4];
-#pragma unroll
-        for (int hq = 0; hq < 2; ++hq) {
-            const float4 v1 = r[0][hq], v2 = r[1][hq], v3 = r[2][hq], v4 = r[3][hq];
-            // plain v_fma_f32: same products in the same order as the v_pk_fma_f32 form this replaced, which measured 4 % slower
-            // -- packed float32 VALU beside MFMAs is an anti-lever on this part (MI355X_MICROARCH.md, instruction table)
-            const float w1 = w[0].x, w2 = w[0].y, w3 = w[1].x, w4 = w[1].y;
-            const float o0 = fmaf(w4, v4.x, fmaf(w3, v3.x, fmaf(w2, v2.x, w1 * v1.x)));
-            const float o1 = fmaf(w4, v4.y, fmaf(w3, v3.y, fmaf(w2, v2.y, w1 * v1.y)));
-            const float o2 = fmaf(w4, v4.z, fmaf(w3, v3.z, fmaf(w2, v2.z, w1 * v1.z)));
-            const float o3 = fmaf(w4, v4.w, fmaf(w3, v3.w, fmaf(w2, v2.w, w1 * v1.w)));
-            const Split2 t0 = split2(o0, o1), t1 = split2(o2, o3);
-            hi[2 * hq] = t0.hi; hi[2 * hq + 1] = t1.hi;
-            lo[2 * hq] = t0.lo; lo[2 * hq + 1] = t1.lo;
-        }
-        const u32x4 ahv = {hi[0], hi[1], hi[2], hi[3]}, alv = {lo[0], lo[1], lo[2], lo[3]};
-        const h8 ah = *reinterpret_cast<const h8*>(&ahv), al = *reinterpret_cast<const h8*>(&alv);
+        h8 ah, al;
+        dcn_blend_split(r, w, &ah, &al);
 #pragma unroll
         for (int h = 0; h < NH; ++h) {
             const u32x4 (&bh)[NW] = wbh[(s0 + h) % 3];
@@ -264,16 +171,7 @@ __global__ __launch_bounds__(256, 2) void dcn16p_kernel(const ConvParams p, cons
             __builtin_amdgcn_sched_barrier(0);
             mid(h);
             __builtin_amdgcn_sched_barrier(0);
-            // same term order as igemm16.hip (lo*hi, hi*lo, hi*hi)
-#pragma unroll
-            for (int j = 0; j < NW; ++j)
-                acc[0][h * NW + j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, *reinterpret_cast<const h8*>(&bh[j]), acc[0][h * NW + j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < NW; ++j)
-                acc[0][h * NW + j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, *reinterpret_cast<const h8*>(&bl[j]), acc[0][h * NW + j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < NW; ++j)
-                acc[0][h * NW + j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, *reinterpret_cast<const h8*>(&bh[j]), acc[0][h * NW + j], 0, 0, 0);
+            dcn_mma3<false, NW>(&acc[0][h * NW], ah, al, bh, bl);
         }
     };
 
@@ -286,28 +184,6 @@ __global__ __launch_bounds__(256, 2) void dcn16p_kernel(const ConvParams p, cons
                 const int co = ((c >> 1) * PW + (c & 1)) * PSTR;
                 r[c][0] = *reinterpret_cast<const float4*>(ap + co);
                 r[c][1] = *reinterpret_cast<const float4*>(ap + co + 16);
-            }
-        };
-        // exception samples: 8 threads each (one channel quad per thread), 32 samples per pass: the four corners are
-        // blended here (same FMA order as the K loop) into the sample's spare pixel; addresses are rebuilt per chunk from
-        // the block's list (LDS) -- no registers held across the K loop
-        auto stage_exceptions = [&](int csoff) {
-            for (int e = tid >> 3; e < nexc; e += 32) {
-                const int key = exc_key[e], go = exc_goff[e] + (tid & 7) * 16;
-                const float4 w = *reinterpret_cast<const float4*>(exc_w[e]);
-                const int iy = (key >> 16) - 1, ix = (key & 0xffff) - 1;
-                const bool y0 = (unsigned)iy < (unsigned)p.H, y1 = (unsigned)(iy + 1) < (unsigned)p.H;
-                const bool x0 = (unsigned)ix < (unsigned)p.W, x1 = (unsigned)(ix + 1) < (unsigned)p.W;
-                const float4 v1 = buf_ld4s(r_x, (y0 && x0) ? (unsigned)go : OOB, csoff);
-                const float4 v2 = buf_ld4s(r_x, (y0 && x1) ? (unsigned)(go + cb) : OOB, csoff);
-                const float4 v3 = buf_ld4s(r_x, (y1 && x0) ? (unsigned)(go + rowb) : OOB, csoff);
-                const float4 v4 = buf_ld4s(r_x, (y1 && x1) ? (unsigned)(go + rowb + cb) : OOB, csoff);
-                float4 o;
-                o.x = fmaf(w.w, v4.x, fmaf(w.z, v3.x, fmaf(w.y, v2.x, w.x * v1.x)));
-                o.y = fmaf(w.w, v4.y, fmaf(w.z, v3.y, fmaf(w.y, v2.y, w.x * v1.y)));
-                o.z = fmaf(w.w, v4.z, fmaf(w.z, v3.z, fmaf(w.y, v2.z, w.x * v1.z)));
-                o.w = fmaf(w.w, v4.w, fmaf(w.z, v3.w, fmaf(w.y, v2.w, w.x * v1.w)));
-                *reinterpret_cast<float4*>(patch + (NPIX + e) * PSTR + (tid & 7) * 16) = o;
             }
         };
         // weights of half-steps 0 and 1 in flight before the first chunk is staged (half-step s refills set (s + 2) % 3 with s + 2)
@@ -337,7 +213,7 @@ __global__ __launch_bounds__(256, 2) void dcn16p_kernel(const ConvParams p, cons
                     float4 sv[PH - H1 > 0 ? PH - H1 : 1];
 #pragma unroll
                     for (int s = H1; s < PH; ++s) sv[s - H1] = buf_ld4s(r_x, row_off(s), csoff);
-                    stage_exceptions(csoff);
+                    dcn_stage_exceptions<CKC / 4, PSTR>(tid, nexc, exc, r_x, p.H, p.W, cb, rowb, csoff, patch + NPIX * PSTR);
 #pragma unroll
                     for (int s = H1; s < PH; ++s)
                         if (spx < PW) *reinterpret_cast<float4*>(patch + st_lds + s * (PW * PSTR)) = sv[s - H1];
@@ -368,36 +244,7 @@ __global__ __launch_bounds__(256, 2) void dcn16p_kernel(const ConvParams p, cons
         // ================= buffer-load mode: every block sample through the texture path =================
         // corner offsets | validity bits and the weights of the lane's 9 taps, from the record again: the fast set-up
         // does not keep the offsets, and it replaced the weights of the samples it filed as exceptions
-        {
-            float o9[28];
-#pragma unroll
-            for (int i = 0; i < 7; ++i) {
-                const float4 v = buf_ld4(r_om, rec + 16u * i);
-                o9[4 * i] = v.x; o9[4 * i + 1] = v.y; o9[4 * i + 2] = v.z; o9[4 * i + 3] = v.w;
-            }
-#pragma unroll
-            for (int t = 0; t < 9; ++t) {
-                const float h_im = (float)(y - 1 + t / 3) + o9[2 * t];
-                const float w_im = (float)(x - 1 + t % 3) + o9[2 * t + 1];
-                int gb = 0;
-                float w1 = 0.f, w2 = 0.f, w3 = 0.f, w4 = 0.f;
-                if (h_im > -1.f && w_im > -1.f && h_im < (float)p.H && w_im < (float)p.W) {
-                    const int h_lo = (int)floorf(h_im), w_lo = (int)floorf(w_im);
-                    const float lh = h_im - (float)h_lo, lw = w_im - (float)w_lo;
-                    const float hh = 1.f - lh, hw = 1.f - lw, mk = o9[18 + t] * afwd;
-                    int vm = 0;
-                    if (h_lo >= 0 && w_lo >= 0) vm |= 1;
-                    if (h_lo >= 0 && w_lo + 1 <= p.W - 1) vm |= 2;
-                    if (h_lo + 1 <= p.H - 1 && w_lo >= 0) vm |= 4;
-                    if (h_lo + 1 <= p.H - 1 && w_lo + 1 <= p.W - 1) vm |= 8;
-                    gb = (((b * p.H + h_lo) * p.W + w_lo) * cb) | vm;
-                    w1 = hh * hw * mk; w2 = hh * lw * mk; w3 = lh * hw * mk; w4 = lh * lw * mk;
-                }
-                addr[t] = gb;
-                bw[t][0] = f32x2{w1, w2};
-                bw[t][1] = f32x2{w3, w4};
-            }
-        }
+        dcn_setup_global(r_om, rec, y, x, b, p.H, p.W, cb, afwd, addr, bw);
         issue_hs(0, 0);
         issue_hs(1, 0);
         for (int ch = 0; ch < nch; ++ch) {
@@ -406,13 +253,7 @@ __global__ __launch_bounds__(256, 2) void dcn16p_kernel(const ConvParams p, cons
                 const int t = u >> 1, ks = u & 1;
                 float4 r[4][2];
                 const int so = (ch * CKC + ks * 16) * 4;
-                const int base = (addr[t] & ~15) + lrow * 32;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {  // invalid corners out of range (-> 0)
-                    const int gi = (addr[t] & (1 << c)) ? base + (c >> 1) * rowb + (c & 1) * cb : (int)OOB_BASE;
-                    r[c][0] = buf_ld4s(r_x, (unsigned)gi, so);
-                    r[c][1] = buf_ld4s(r_x, (unsigned)gi + 16u, so);
-                }
+                dcn_gather_global(r_x, addr[t], lrow, rowb, cb, so, r);
                 mma_step(r, bw[t], u * NH, [&](int h) { issue_hs(u * NH + h + 2, ch); });
                 __builtin_amdgcn_sched_barrier(0);  // keep the loads of later steps below: the register file is full
             }

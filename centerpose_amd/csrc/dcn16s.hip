@@ -23,9 +23,12 @@
 // corners sit at (row + 4 col + quad) mod 16 sixteen-byte bank groups (1552 B = 97 groups = 1 mod 16): all distinct.
 // Corner / K-step / quad offsets are immediates, one address register per (lane, tap), as in dcn16p.
 // K order is (16-channel chunk, tap): same products as dcn16.hip / dcn16p.hip, different summation order.
+// The bilinear set-up, the exception list, the buffer-load fallback, the blend + split and the MFMA term order are
+// dcn_patch_common.h's, shared with dcn16p.hip and dcn16t.hip.
 // LDS: 2 x 30.6 KB buffers + 16 KB corner buffer + 1.5 KB lists = 79.2 KB => two workgroups per CU.
 #include <type_traits>
 
+#include "dcn_patch_common.h"
 #include "patch16_common.h"
 
 namespace {
@@ -49,26 +52,6 @@ constexpr int S_NSTEP = 9;                                         // K steps (o
 static_assert(S_BUFB % 16 == 0 && S_LDS <= 80 * 1024 - 128, "two workgroups per CU");
 static_assert((S_ROWB / 16) % 16 == 1, "row pitch = 1 bank group mod 16");
 
-__device__ __forceinline__ float4 s_ld4s(__amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, soff, 0);
-    return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-}
-
-__device__ __forceinline__ void s_both_halves5(const uint32_t (&v)[5], uint32_t (&lo)[5], uint32_t (&hi)[5]) {
-    // v_permlane32_swap_b32 vdst, vsrc exchanges vdst[32..63] with vsrc[0..31]; with both operands holding v every lane ends up
-    // with {the lower half's value, the upper half's value}.  Written out by hand, each swap on its own pair of registers with
-    // the wait states the hazard table asks for inside the statement (VALU write -> v_permlane*_swap read: 2).  (Round 4 padded
-    // these swaps while hunting wrong set-up values; the swaps were innocent -- the cause was a packed-f32 op with a set op_sel
-    // bit, profiles/NOTES.md round 5 -- but the hand-written form costs nothing and stays.)
-    uint32_t a0 = v[0], a1 = v[1], a2 = v[2], a3 = v[3], a4 = v[4], b0 = v[0], b1 = v[1], b2 = v[2], b3 = v[3], b4 = v[4];
-    asm volatile("s_nop 4\n\tv_permlane32_swap_b32 %0, %5\n\ts_nop 1\n\tv_permlane32_swap_b32 %1, %6\n\ts_nop 1\n\t"
-                 "v_permlane32_swap_b32 %2, %7\n\ts_nop 1\n\tv_permlane32_swap_b32 %3, %8\n\ts_nop 1\n\t"
-                 "v_permlane32_swap_b32 %4, %9\n\ts_nop 4"
-                 : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(b0), "+v"(b1), "+v"(b2), "+v"(b3), "+v"(b4));
-    lo[0] = a0; lo[1] = a1; lo[2] = a2; lo[3] = a3; lo[4] = a4;
-    hi[0] = b0; hi[1] = b1; hi[2] = b2; hi[3] = b3; hi[4] = b4;
-}
-
 // One LDS-DMA piece: lane l's 16 bytes at (voff + soff) of the buffer land at LDS byte lds_addr + 16 l (lanes masked off by
 // EXEC write nothing; out-of-range offsets write zeros).  The compiler does not count it: completion = an explicit
 // s_waitcnt vmcnt, visibility to other waves = a barrier after that.  s_nop 4: the operands may come straight from
@@ -80,14 +63,12 @@ __device__ __forceinline__ void s_dma16(__amdgpu_buffer_rsrc_t r, unsigned voff,
                  : "memory", "m0");
 }
 
-typedef float s_f32x2 __attribute__((ext_vector_type(2)));
-
-// The lane id behind an optimisation barrier: everything derived from it is recomputed where it is used (a handful of VALU
-// per chunk) instead of being hoisted out of the item loop and held -- or spilled -- across the K loops.
-__device__ __forceinline__ int s_opaque(int v) {
-    asm volatile("" : "+v"(v));
-    return v;
-}
+// LDS geometry for dcn_setup_taps: counted in bytes of a chunk buffer
+struct SGeo {
+    static constexpr int PH = S_PH, PW = S_PW, HALO = S_HALO, ECAP = S_ECAP;
+    static __device__ __forceinline__ int corner(int qy, int qx) { return qy * S_ROWB + qx * S_PXB; }
+    static __device__ __forceinline__ int spare(int e) { return S_SP0 + e * S_PXB; }
+};
 
 // (image, top-left output pixel, N tile) of item `it` (n fastest)
 struct SItem {
@@ -138,7 +119,7 @@ __global__ __launch_bounds__(256, 2) void dcn16s_kernel(const ConvParams p, cons
     // ---- halo DMA of chunk `ch` of the patch at (b, ty0, tx0) into buffer `buf`: wave w carries patch rows 4 w .. 4 w + 3,
     //      two pieces of 12 pixels x 4 quads each (lanes 0 .. 47) ----
     auto issue_halo = [&](const SItem& t, int ch, int buf) {
-        const int ln = s_opaque(lane);
+        const int ln = lane_opaque(lane);
         // column validity of this lane's pixel in either half row (-> all-ones offset = out of range = zeros)
         const int gx0 = t.tx0 - S_HALO + (ln >> 2);
         const unsigned vh0 = (unsigned)gx0 < (unsigned)p.W ? (unsigned)(gx0 * cb + (ln & 3) * 16) : OOB;
@@ -159,17 +140,10 @@ __global__ __launch_bounds__(256, 2) void dcn16s_kernel(const ConvParams p, cons
     // ---- offset / mask record of this lane's pixel: taps 5 lrow .. 5 lrow + 4 (slot 4 of the upper half is a dummy) ----
     float od[12], omk[5];
     auto load_record = [&](const SItem& t) {
-        const int ln = s_opaque(lane), lrow = ln >> 5, q8 = (ln >> 2) & 7;
+        const int ln = lane_opaque(lane), lrow = ln >> 5, q8 = (ln >> 2) & 7;
         const int y = t.ty0 + 4 * (wid >> 1) + (q8 >> 1), x = t.tx0 + 8 * (wid & 1) + 4 * ((0x96 >> q8) & 1) + (ln & 3);
         const unsigned rec = (unsigned)((t.b * p.H + y) * p.W + x) * 128u;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const float4 v = buf_ld4(r_om, rec + (unsigned)lrow * 40u + 16u * i);
-            od[4 * i] = v.x; od[4 * i + 1] = v.y; od[4 * i + 2] = v.z; od[4 * i + 3] = v.w;
-        }
-        const float4 v = buf_ld4(r_om, rec + 72u + (unsigned)lrow * 20u);
-        omk[0] = v.x; omk[1] = v.y; omk[2] = v.z; omk[3] = v.w;
-        omk[4] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r_om, (int)(rec + 88u + (unsigned)lrow * 20u), 0, 0));
+        dcn_load_record(r_om, rec, lrow, od, omk);
     };
 
     // ---- weight fragments: (n tile j of 32, K step g of 16) = 1 KB in lane order at ((j Gk + g) 64 + lane) 16 B; three
@@ -226,64 +200,16 @@ __global__ __launch_bounds__(256, 2) void dcn16s_kernel(const ConvParams p, cons
         int* const ecnt = reinterpret_cast<int*>(smem + S_ECNT);
 
         // ---- bilinear set-up (dcn_v2_im2col_cuda.cu:25-54, 150-187): 5 tap slots per lane, then both halves swap ----
-        const int ln0 = s_opaque(lane), lrow = ln0 >> 5, q8 = (ln0 >> 2) & 7;
+        const int ln0 = lane_opaque(lane), lrow = ln0 >> 5, q8 = (ln0 >> 2) & 7;
         const int y = cur.ty0 + 4 * (wid >> 1) + (q8 >> 1), x = cur.tx0 + 8 * (wid & 1) + 4 * ((0x96 >> q8) & 1) + (ln0 & 3);
         uint32_t sq[5], sw[5][4];  // byte offset of corner (h_lo, w_lo) in a chunk buffer; corner weights x mask x pre-scale
-        const float fy0 = (float)(y - 1), fx0 = (float)(x - 1);
-#pragma unroll
-        for (int j = 0; j < 5; ++j) {
-            // tap 5 lrow + j = (kh, kw): lower half (0,0) (0,1) (0,2) (1,0) (1,1); upper half (1,2) (2,0) (2,1) (2,2) (-)
-            const float khf = lrow ? (float)((5 + j) / 3) : (float)(j / 3);
-            const float kwf = lrow ? (float)((5 + j) % 3) : (float)(j % 3);
-            float h_im = (fy0 + khf) + od[2 * j];
-            float w_im = (fx0 + kwf) + od[2 * j + 1];
-            const bool valid = h_im > -1.f && w_im > -1.f && h_im < (float)p.H && w_im < (float)p.W && !(lrow && j == 4);
-            h_im = valid ? h_im : 0.f;
-            w_im = valid ? w_im : 0.f;
-            const float mk = valid ? omk[j] * afwd : 0.f;
-            const float fh = floorf(h_im), fw = floorf(w_im);
-            const int h_lo = (int)fh, w_lo = (int)fw;
-            const float lh = h_im - fh, lw = w_im - fw;
-            const float hh = 1.f - lh, hw = 1.f - lw;
-            sw[j][0] = __float_as_uint(hh * hw * mk);
-            sw[j][1] = __float_as_uint(hh * lw * mk);
-            sw[j][2] = __float_as_uint(lh * hw * mk);
-            sw[j][3] = __float_as_uint(lh * lw * mk);
-            const int qy = h_lo - (cur.ty0 - S_HALO), qx = w_lo - (cur.tx0 - S_HALO);
-            const bool inp = (unsigned)qy <= (unsigned)(S_PH - 2) && (unsigned)qx <= (unsigned)(S_PW - 2);
-            int q = inp ? qy * S_ROWB + qx * S_PXB : 0;
-            if (valid && !inp) {  // exception sample: file its corner and weights; this lane then reads spare pixel e with
-                                  // weights (1, 0, 0, 0)
-                const int e = atomicAdd(&ecnt[parity], 1);
-                if (e < S_ECAP) {
-                    reinterpret_cast<int*>(smem + S_EKEY)[e] = ((h_lo + 1) << 16) | (w_lo + 1);
-                    reinterpret_cast<int*>(smem + S_EGOFF)[e] = ((cur.b * p.H + h_lo) * p.W + w_lo) * cb;
-                    *reinterpret_cast<float4*>(smem + S_EW + e * 16) =
-                        make_float4(__uint_as_float(sw[j][0]), __uint_as_float(sw[j][1]), __uint_as_float(sw[j][2]),
-                                    __uint_as_float(sw[j][3]));
-                    sw[j][0] = __float_as_uint(1.f);
-                    sw[j][1] = sw[j][2] = sw[j][3] = 0u;
-                    q = S_SP0 + e * S_PXB;
-                }
-            }
-            sq[j] = (uint32_t)q;
-        }
+        const DcnExcList exc = {reinterpret_cast<int*>(smem + S_EKEY), reinterpret_cast<int*>(smem + S_EGOFF),
+                                reinterpret_cast<float*>(smem + S_EW), &ecnt[parity]};
+        dcn_setup_taps<SGeo>(od, omk, lrow, y, x, cur.ty0, cur.tx0, cur.b, p.H, p.W, cb, afwd, exc, sq, sw);
         int addr[9];       // fast mode: byte offset in a chunk buffer of corner (h_lo, w_lo) + this lane's 32-byte channel
                            // half; buffer-load mode: that corner's byte offset into the input tensor | 4 validity bits
-        s_f32x2 bw[9][2];  // {w1, w2}, {w3, w4}
-#pragma unroll
-        for (int j = 0; j < 5; ++j) {
-            const uint32_t pack[5] = {sq[j], sw[j][0], sw[j][1], sw[j][2], sw[j][3]};
-            uint32_t lo[5], hi[5];
-            s_both_halves5(pack, lo, hi);
-            addr[j] = (int)lo[0] + lrow * 32;
-            if (j < 4) addr[5 + j] = (int)hi[0] + lrow * 32;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                bw[j][c >> 1][c & 1] = __uint_as_float(lo[1 + c]);
-                if (j < 4) bw[5 + j][c >> 1][c & 1] = __uint_as_float(hi[1 + c]);
-            }
-        }
+        f32x2 bw[9][2];  // {w1, w2}, {w3, w4}
+        dcn_expand_taps<1>(sq, sw, lrow, addr, bw);
         __syncthreads();  // the exception list is complete
         const int nexc_all = __builtin_amdgcn_readfirstlane(ecnt[parity]);
         const bool slow = nexc_all > S_ECAP;  // block-uniform
@@ -300,35 +226,14 @@ __global__ __launch_bounds__(256, 2) void dcn16s_kernel(const ConvParams p, cons
         // blend + split of one gathered K step, then its 3 NT MFMAs (term order of igemm16.hip: lo*hi, hi*lo, hi*hi).  `mid` runs
         // between the two: the refill of the weight set the PREVIOUS step consumed -- never right behind that step's MFMAs, whose
         // B operand a fast-returning load would overwrite while the matrix pipe still reads it (dcn16p.hip, mma_step).
-        auto mma_step = [&](const float4 (&r)[4][2], const s_f32x2 (&w)[2], const u32x4 (&bh)[NT], const u32x4 (&bl)[NT],
+        auto mma_step = [&](const float4 (&r)[4][2], const f32x2 (&w)[2], const u32x4 (&bh)[NT], const u32x4 (&bl)[NT],
                             auto&& mid) {
-            uint32_t hi[4], lo[4];
-#pragma unroll
-            for (int hq = 0; hq < 2; ++hq) {
-                const float4 v1 = r[0][hq], v2 = r[1][hq], v3 = r[2][hq], v4 = r[3][hq];
-                const float w1 = w[0].x, w2 = w[0].y, w3 = w[1].x, w4 = w[1].y;
-                const float o0 = fmaf(w4, v4.x, fmaf(w3, v3.x, fmaf(w2, v2.x, w1 * v1.x)));
-                const float o1 = fmaf(w4, v4.y, fmaf(w3, v3.y, fmaf(w2, v2.y, w1 * v1.y)));
-                const float o2 = fmaf(w4, v4.z, fmaf(w3, v3.z, fmaf(w2, v2.z, w1 * v1.z)));
-                const float o3 = fmaf(w4, v4.w, fmaf(w3, v3.w, fmaf(w2, v2.w, w1 * v1.w)));
-                const Split2 t0 = split2(o0, o1), t1 = split2(o2, o3);
-                hi[2 * hq] = t0.hi; hi[2 * hq + 1] = t1.hi;
-                lo[2 * hq] = t0.lo; lo[2 * hq + 1] = t1.lo;
-            }
-            const u32x4 ahv = {hi[0], hi[1], hi[2], hi[3]}, alv = {lo[0], lo[1], lo[2], lo[3]};
-            const h8 ah = *reinterpret_cast<const h8*>(&ahv), al = *reinterpret_cast<const h8*>(&alv);
+            h8 ah, al;
+            dcn_blend_split(r, w, &ah, &al);
             __builtin_amdgcn_sched_barrier(0);
             mid();
             __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int j = 0; j < NT; ++j)
-                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const h8*>(&bh[j]), al, acc[j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < NT; ++j)
-                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const h8*>(&bl[j]), ah, acc[j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < NT; ++j)
-                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const h8*>(&bh[j]), ah, acc[j], 0, 0, 0);
+            dcn_mma3<true, NT>(acc, ah, al, bh, bl);  // the transposed tile (mma1 below)
         };
         // inside step (ch, t): the weight set step t - 1 consumed takes the step two ahead -- of this chunk, of the next one, or of
         // the next item's first chunk
@@ -353,7 +258,7 @@ __global__ __launch_bounds__(256, 2) void dcn16s_kernel(const ConvParams p, cons
                 for (int j = 0; j < 4; ++j) {
                     const int pc = wid + 4 * j;
                     if (4 * pc < nexc) {  // scalar
-                        const int ln = s_opaque(lane);
+                        const int ln = lane_opaque(lane);
                         const int e = 4 * pc + (ln >> 4), c = (ln >> 2) & 3;
                         const int key = reinterpret_cast<const int*>(smem + S_EKEY)[e];
                         const int go = reinterpret_cast<const int*>(smem + S_EGOFF)[e];
@@ -367,7 +272,7 @@ __global__ __launch_bounds__(256, 2) void dcn16s_kernel(const ConvParams p, cons
             // the wave's exceptions blended corner buffer -> spare pixels of buffer `buf` (same FMA order as the K loop);
             // lane = (j, i, quad): exception 4 (w + 4 j) + i
             auto blend_corners = [&](int buf) {
-                const int ln = s_opaque(lane);
+                const int ln = lane_opaque(lane);
                 const int e = 4 * (wid + 4 * (ln >> 4)) + ((ln >> 2) & 3);
                 if (e < nexc) {
                     const unsigned char* cp0 = smem + S_CORN + e * 256 + (ln & 3) * 16;
@@ -376,11 +281,7 @@ __global__ __launch_bounds__(256, 2) void dcn16s_kernel(const ConvParams p, cons
                     const float4 v3 = *reinterpret_cast<const float4*>(cp0 + 128);
                     const float4 v4 = *reinterpret_cast<const float4*>(cp0 + 192);
                     const float4 w = *reinterpret_cast<const float4*>(smem + S_EW + e * 16);
-                    float4 o;
-                    o.x = fmaf(w.w, v4.x, fmaf(w.z, v3.x, fmaf(w.y, v2.x, w.x * v1.x)));
-                    o.y = fmaf(w.w, v4.y, fmaf(w.z, v3.y, fmaf(w.y, v2.y, w.x * v1.y)));
-                    o.z = fmaf(w.w, v4.z, fmaf(w.z, v3.z, fmaf(w.y, v2.z, w.x * v1.z)));
-                    o.w = fmaf(w.w, v4.w, fmaf(w.z, v3.w, fmaf(w.y, v2.w, w.x * v1.w)));
+                    const float4 o = dcn_blend4(w.x, w.y, w.z, w.w, v1, v2, v3, v4);
                     *reinterpret_cast<float4*>(smem + buf * S_BUFB + S_SP0 + e * S_PXB + (ln & 3) * 16) = o;
                 }
             };
@@ -419,7 +320,7 @@ __global__ __launch_bounds__(256, 2) void dcn16s_kernel(const ConvParams p, cons
                 uint32_t ahi[2][4], alo[2][4];  // split A operands of steps t (consumed by the MFMAs) and t + 1 (being produced)
                 float o[4];
                 // blend of quad hq in three pieces of 8 VALU: fma(w4, v4, fma(w3, v3, fma(w2, v2, w1 * v1))), then the hi / lo split
-                auto blend_piece = [&](const float4 (&r)[4][2], const s_f32x2 (&w)[2], uint32_t (&hi)[4], uint32_t (&lo)[4], int hq,
+                auto blend_piece = [&](const float4 (&r)[4][2], const f32x2 (&w)[2], uint32_t (&hi)[4], uint32_t (&lo)[4], int hq,
                                        int piece) {
                     if (piece == 0) {
                         const float4 v1 = r[0][hq], v2 = r[1][hq];
@@ -489,49 +390,13 @@ __global__ __launch_bounds__(256, 2) void dcn16s_kernel(const ConvParams p, cons
         } else {
             // ================= buffer-load mode: every sample of the patch through the texture path =================
             if (has_next) issue_halo(nxt, 0, 0);  // the next item's first chunk (this item's copy in buffer 0 is not used)
-            {
-                const unsigned rec = (unsigned)((cur.b * p.H + y) * p.W + x) * 128u;
-                float o9[28];
-#pragma unroll
-                for (int i = 0; i < 7; ++i) {
-                    const float4 v = buf_ld4(r_om, rec + 16u * i);
-                    o9[4 * i] = v.x; o9[4 * i + 1] = v.y; o9[4 * i + 2] = v.z; o9[4 * i + 3] = v.w;
-                }
-#pragma unroll
-                for (int t = 0; t < 9; ++t) {
-                    const float h_im = (float)(y - 1 + t / 3) + o9[2 * t];
-                    const float w_im = (float)(x - 1 + t % 3) + o9[2 * t + 1];
-                    int gb = 0;
-                    float w1 = 0.f, w2 = 0.f, w3 = 0.f, w4 = 0.f;
-                    if (h_im > -1.f && w_im > -1.f && h_im < (float)p.H && w_im < (float)p.W) {
-                        const int h_lo = (int)floorf(h_im), w_lo = (int)floorf(w_im);
-                        const float lh = h_im - (float)h_lo, lw = w_im - (float)w_lo;
-                        const float hh = 1.f - lh, hw = 1.f - lw, mk = o9[18 + t] * afwd;
-                        int vm = 0;
-                        if (h_lo >= 0 && w_lo >= 0) vm |= 1;
-                        if (h_lo >= 0 && w_lo + 1 <= p.W - 1) vm |= 2;
-                        if (h_lo + 1 <= p.H - 1 && w_lo >= 0) vm |= 4;
-                        if (h_lo + 1 <= p.H - 1 && w_lo + 1 <= p.W - 1) vm |= 8;
-                        gb = (((cur.b * p.H + h_lo) * p.W + w_lo) * cb) | vm;
-                        w1 = hh * hw * mk; w2 = hh * lw * mk; w3 = lh * hw * mk; w4 = lh * lw * mk;
-                    }
-                    addr[t] = gb;
-                    bw[t][0] = s_f32x2{w1, w2};
-                    bw[t][1] = s_f32x2{w3, w4};
-                }
-            }
+            dcn_setup_global(r_om, (unsigned)((cur.b * p.H + y) * p.W + x) * 128u, y, x, cur.b, p.H, p.W, cb, afwd, addr, bw);
             for (int ch = 0; ch < nch; ++ch) {
 #pragma unroll
                 for (int t = 0; t < S_NSTEP; ++t) {
                     float4 r[4][2];
                     const int so = ch * S_PXB;
-                    const int base = (addr[t] & ~15) + lrow * 32;
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {  // invalid corners out of range (-> 0)
-                        const int gi = (addr[t] & (1 << c)) ? base + (c >> 1) * rowb + (c & 1) * cb : (int)OOB_BASE;
-                        r[c][0] = s_ld4s(r_x, (unsigned)gi, so);
-                        r[c][1] = s_ld4s(r_x, (unsigned)gi + 16u, so);
-                    }
+                    dcn_gather_global(r_x, addr[t], lrow, rowb, cb, so, r);
                     mma_step(r, bw[t], wbh[t % 3], wbl[t % 3], [&]() { refill(ch, t); });
                     __builtin_amdgcn_sched_barrier(0);
                 }
@@ -546,7 +411,7 @@ __global__ __launch_bounds__(256, 2) void dcn16s_kernel(const ConvParams p, cons
             // transposed tile: accumulator 4 g + i of N tile j in lane (pixel = lane % 32, half h4) = output channel
             // 32 j + 8 g + 4 h4 + i of that lane's own pixel -> one 16-byte store per (j, g), 2 NT x 4 per lane instead of 16 NT
             // 4-byte ones (the epilogue was store-issue-bound: 4.2 k of an item's 41 k clocks, tools/dcn16s_timeline.py)
-            const int ln = s_opaque(lane), h4 = ln >> 5, q8 = (ln >> 2) & 7;
+            const int ln = lane_opaque(lane), h4 = ln >> 5, q8 = (ln >> 2) & 7;
             const int pix0 = (cur.b * p.H + cur.ty0 + 4 * (wid >> 1)) * p.W + cur.tx0 + 8 * (wid & 1);  // scalar
             float* frag_out = p.out + (size_t)pix0 * p.ldo + p.coff;
             const __amdgpu_buffer_rsrc_t ro = make_rsrc(frag_out, (unsigned)((3 * p.W + 8) * p.ldo) * 4u);

@@ -1,5 +1,6 @@
 """A/B of the DCNv2 main kernels per layer shape of dla_34 at batch B: dcn16p (patch-resident, 64-wide N tile), dcn16pw (the same on
-the 128-wide N tile where the layer has whole 128-channel tiles) and dcn16s (persistent, streamed).
+the 128-wide N tile where the layer has whole 128-channel tiles), dcn16s (persistent, streamed) and dcn16t (patch-resident on the
+three-workgroups-per-CU budget).
 Run under rocprofv3 --kernel-trace; `--parse DIR` then prints the average kernel duration per (shape, kernel) from the trace.
 usage: rocprofv3 --kernel-trace --output-format csv -d OUT -- python tools/dcn_ab.py [--b 64] [--n 5] ; python tools/dcn_ab.py --parse OUT"""
 import argparse
