@@ -469,6 +469,20 @@ size_t cp_conv_dgrad_pack_bytes(int Cin, int CoP, int taps);
 int cp_launch_conv_dgrad_pack(hipStream_t s, const float* w, float* wB, int Cin, int Cout, int CoP, int taps);
 int cp_launch_conv_dgrad_s1(hipStream_t s, const ConvBwdArgs& a, const float* gs, int CoP, const float* wB, const float* res);
 
+// ---- ConvTranspose2d backward (deconv_bwd.hip): IDAUp's depth-wise `up` (k = 2 stride, pad = stride / 2, groups = C) and the
+// dense k 4 / stride 2 / pad 1 layer, on the forward's NHWC layouts, float32 ----
+#define CP_DECONV_DW_TABLE_BYTES 61440  // the depth-wise kernels stage w as [k k][C] floats in LDS beside a 4 KiB exchange area
+struct DeconvBwdArgs {
+    const float *x, *w, *go;  // x [B,H,W,Cin], w [Cin,Cout/groups,K,K], go [B,stride H,stride W,Cout]
+    float *gx, *gw;           // gx nullptr: not computed
+    int B, H, W, Cin, Cout, stride, groups;
+};
+bool cp_deconv_dw_geometry(int Cin, int Cout, int K, int stride, int pad, int groups);
+bool cp_deconv_dense_geometry(int Cin, int Cout, int K, int stride, int pad, int groups);
+// (for a geometry one of the two predicates accepts)
+size_t cp_deconv_backward_ws_bytes(int B, int H, int W, int Cin, int Cout, int stride, int groups, int need_grad_x);
+int cp_launch_deconv_backward(hipStream_t s, const DeconvBwdArgs& a, void* ws);
+
 // ---- BatchNorm2d, training and evaluation, fused with the residual add and ReLU (batchnorm.hip): float32 NHWC ----
 struct BnFwdArgs {
     const float *x, *gamma, *beta, *res;  // gamma / beta nullptr: 1 / 0; res nullptr: no residual

@@ -1,0 +1,250 @@
+// Backward of the two transposed convolutions of the up-sampling paths (cp_conv_transpose2d_backward_nhwc), float32 NHWC, no
+// atomics, every sum in a fixed order:
+//   depth-wise  IDAUp's `up` (pose_dla_dcn.py:402-417): ConvTranspose2d(C, C, k = 2f, stride f, padding f/2, groups C), the
+//               forward of upsample_add_kernel (ewise.hip) in upadd_common.h's notation.  New kernels, below.
+//   dense       resnet_dcn.py:232-240's deconv layers: ConvTranspose2d(Cin, Cout, 4, stride 2, padding 1).  No kernel of its own:
+//               the transposed convolution is the adjoint of conv2d(., w, stride 2, pad 1) with w [Cin,Cout,4,4] read as
+//               [out,in,4,4], so its data gradient IS that convolution of grad_out (the exact-f32 implicit GEMM of igemm.hip) and
+//               its weight gradient is that convolution's weight gradient with the roles of input and output gradient swapped
+//               (cp_launch_conv_wgrad: `x` = grad_out, `gs` = x; wgrad_reduce_kernel then writes [Cin][Cout][4][4]).
+#include "engine_model.h"
+
+#include <algorithm>
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+namespace {
+
+// Depth-wise backward, both gradients from one pass over grad_out:
+//   grad_x[b,iy,ix,c] = sum_{ky,kx} go[b, iy f - p + ky, ix f - p + kx, c] * w[c,ky,kx]
+//   grad_w[c,ky,kx]   = sum_{b,iy,ix} x[b,iy,ix,c] * go[b, iy f - p + ky, ix f - p + kx, c]
+// A thread owns one source pixel, one channel quad (16 bytes) and one group of 4 x 4 taps: k = 4 has one group (G = 1), k = 8
+// four (G = 4, one per wave-sized quarter of the workgroup).  It requests its sixteen grad_out pieces -- and x -- before using
+// any, without a branch: a tap outside the grid (and a pixel beyond the slab) is requested beyond the buffer descriptor and
+// comes back as zeros.  Each piece feeds both sums while it is in registers, so grad_out is not read once per gradient; the
+// windows of neighbouring source pixels overlap (a piece is wanted by 2 x 2 of them), which the caches absorb: those threads
+// sit in the same or the neighbouring workgroup.  Lanes of one pixel are consecutive channel quads, so a request covers whole
+// 128-byte lines wherever C % 32 == 0.
+//   grad_x: the group's sixteen products in (ky, kx) order from 0; with G = 4 the groups' sums then meet in LDS and are added
+//           in group order.  Not computed and not stored when gx is NULL.
+//   grad_w: sixteen float4 accumulators per thread over the pixels of its pixel lane, ascending; at the end the pixel lanes
+//           are added in lane order through LDS and the workgroup writes part[slab][tap][C].  dw_wgrad_reduce_kernel adds the
+//           slabs in bias_reduce_kernel's two-level order.
+// LDS: [256 float4 exchange][k k C weights as [tap][channel], one ds_read_b128 per lane and tap].
+template <int G>
+__global__ __launch_bounds__(256) void dw_bwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                     const float* __restrict__ go, float* __restrict__ gx,
+                                                     float* __restrict__ part, int B, int H, int W, int C, int f, int px_per_slab) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float4* xch = reinterpret_cast<float4*>(smem);
+    float* wt = smem + 1024;
+    const int k = 2 * f, kk = k * k, p = f / 2, C4 = C >> 2;
+    for (int i = threadIdx.x; i < C * kk; i += 256) {
+        const int c = i / kk, t = i - c * kk;
+        wt[t * C + c] = w[i];
+    }
+    __syncthreads();
+    constexpr int IT = 256 / G;  // (pixel lane, channel quad) items per tap group
+    const int tg = threadIdx.x / IT, local = threadIdx.x - tg * IT;
+    const int PL = IT / C4;  // >= 1: C4 <= IT is part of the accepted geometry
+    const int pl = local / C4, cq = local - pl * C4;
+    const bool lane_on = pl < PL;
+    const int ty0 = (tg / (k / 4)) * 4, tx0 = (tg % (k / 4)) * 4;  // the group's first tap
+    const int Ho = H * f, Wo = W * f, Q = B * H * W;
+    const int q_beg = blockIdx.x * px_per_slab, q_end = min(Q, q_beg + px_per_slab);
+    // (Q f f C < 2^30 elements: every byte offset below fits 32 bits)
+    const __amdgpu_buffer_rsrc_t r_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x), 0, (int)((unsigned)Q * C * 4u), 0x00020000);
+    const __amdgpu_buffer_rsrc_t r_go = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(go), 0, (int)((unsigned)Q * f * f * C * 4u), 0x00020000);
+    const __amdgpu_buffer_rsrc_t r_gx = __builtin_amdgcn_make_buffer_rsrc(gx ? gx : const_cast<float*>(x), 0, gx ? (int)((unsigned)Q * C * 4u) : 0, 0x00020000);
+    float4 acc[16];
+#pragma unroll
+    for (int t = 0; t < 16; ++t) acc[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int q0 = q_beg; q0 < q_end; q0 += PL) {  // (uniform per workgroup: the barriers below are reached by every thread)
+        const int q = q0 + pl;
+        const bool live = lane_on && q < q_end;
+        const int qc = live ? q : 0;
+        const int ix = qc % W, rest = qc / W, iy = rest % H, b = rest / H;
+        const u32x4 rx = __builtin_amdgcn_raw_buffer_load_b128(r_x, (int)(live ? ((unsigned)qc * C4 + cq) * 16u : 0xffffffffu), 0, 0);
+        float4 g[16];
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const int y = iy * f - p + ty0 + r, xx = ix * f - p + tx0 + c;
+                const bool ok = live && (unsigned)y < (unsigned)Ho && (unsigned)xx < (unsigned)Wo;
+                const u32x4 raw = __builtin_amdgcn_raw_buffer_load_b128(
+                    r_go, (int)(ok ? (((unsigned)(b * Ho + y) * Wo + xx) * C4 + cq) * 16u : 0xffffffffu), 0, 0);
+                g[r * 4 + c] = make_float4(__uint_as_float(raw.x), __uint_as_float(raw.y), __uint_as_float(raw.z), __uint_as_float(raw.w));
+            }
+        const float4 xv = make_float4(__uint_as_float(rx.x), __uint_as_float(rx.y), __uint_as_float(rx.z), __uint_as_float(rx.w));
+        float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int t = 0; t < 16; ++t) {
+            acc[t].x += xv.x * g[t].x;
+            acc[t].y += xv.y * g[t].y;
+            acc[t].z += xv.z * g[t].z;
+            acc[t].w += xv.w * g[t].w;
+        }
+        if (gx) {  // (uniform)
+#pragma unroll
+            for (int t = 0; t < 16; ++t) {  // (float4 index: the alignment is provable; a lane without a pixel holds zeros)
+                const float4 wv = reinterpret_cast<const float4*>(wt)[((ty0 + (t >> 2)) * k + tx0 + (t & 3)) * C4 + cq];
+                s.x += g[t].x * wv.x;
+                s.y += g[t].y * wv.y;
+                s.z += g[t].z * wv.z;
+                s.w += g[t].w * wv.w;
+            }
+            if (G > 1) {
+                xch[threadIdx.x] = s;
+                __syncthreads();
+                if (tg == 0) {
+#pragma unroll
+                    for (int j = 1; j < G; ++j) {
+                        const float4 o = xch[j * IT + local];
+                        s.x += o.x;
+                        s.y += o.y;
+                        s.z += o.z;
+                        s.w += o.w;
+                    }
+                }
+                __syncthreads();
+            }
+            const u32x4 pk = {__float_as_uint(s.x), __float_as_uint(s.y), __float_as_uint(s.z), __float_as_uint(s.w)};
+            __builtin_amdgcn_raw_buffer_store_b128(pk, r_gx, (int)(live && tg == 0 ? ((unsigned)qc * C4 + cq) * 16u : 0xffffffffu), 0, 0);
+        }
+    }
+    // the pixel lanes' accumulators, tap by tap, in lane order (lanes that own no pixel hold zeros and are not read)
+    float* out = part + (size_t)blockIdx.x * kk * C;
+#pragma unroll
+    for (int t = 0; t < 16; ++t) {
+        __syncthreads();
+        xch[threadIdx.x] = acc[t];
+        __syncthreads();
+        if (lane_on && pl == 0) {
+            float4 v = xch[tg * IT + cq];
+            for (int j = 1; j < PL; ++j) {
+                const float4 o = xch[tg * IT + j * C4 + cq];
+                v.x += o.x;
+                v.y += o.y;
+                v.z += o.z;
+                v.w += o.w;
+            }
+            const int tap = (ty0 + (t >> 2)) * k + tx0 + (t & 3);
+            *reinterpret_cast<float4*>(out + (size_t)tap * C + 4 * cq) = v;
+        }
+    }
+}
+
+// gw[c][tap] = the slabs' part[s][tap][c], summed in bias_reduce_kernel's two-level order: a workgroup is 32 elements x 8 slab
+// lanes; lane l adds the slabs l, l + 8, ... ascending, then the eight lanes are added in lane order
+__global__ __launch_bounds__(256) void dw_wgrad_reduce_kernel(const float* __restrict__ part, float* __restrict__ gw, int nslab, int C,
+                                                              int kk) {
+    __shared__ float red[256];
+    const int n = kk * C;
+    const int el = threadIdx.x & 31, sl = threadIdx.x >> 5, e = blockIdx.x * 32 + el;
+    float v = 0.f;
+    if (e < n)
+        for (int s = sl; s < nslab; s += 8) v += part[(size_t)s * n + e];
+    red[threadIdx.x] = v;
+    __syncthreads();
+    if (sl == 0 && e < n) {
+        float t = red[el];
+        for (int j = 1; j < 8; ++j) t += red[j * 32 + el];
+        const int tap = e / C, c = e - tap * C;
+        gw[(size_t)c * kk + tap] = t;
+    }
+}
+
+inline size_t al(size_t x) { return (x + 255) / 256 * 256; }
+inline bool ok() { return hipGetLastError() == hipSuccess; }
+
+// Depth-wise slabs: whole pixel-lane rounds, about eight rounds per workgroup, at most 1024 slabs (monotone in B)
+struct DwPlan {
+    int G, PL, px_per_slab, slabs;
+    size_t lds, part_bytes;
+};
+DwPlan dw_plan(int B, int H, int W, int C, int f) {
+    DwPlan P;
+    const int k = 2 * f;
+    P.G = k * k / 16;
+    P.PL = (256 / P.G) / (C / 4);
+    const size_t Q = (size_t)B * H * W;
+    const size_t rounds = (Q + P.PL - 1) / P.PL;
+    const size_t want = std::max<size_t>(1, std::min<size_t>(1024, (rounds + 7) / 8));
+    const size_t rps = (rounds + want - 1) / want;
+    P.px_per_slab = (int)(rps * P.PL);
+    P.slabs = (int)((Q + P.px_per_slab - 1) / P.px_per_slab);
+    P.lds = (1024 + (size_t)k * k * C) * sizeof(float);
+    P.part_bytes = want * k * k * C * sizeof(float);  // (the slab count's upper bound: monotone in B)
+    return P;
+}
+
+struct DensePlan {
+    ConvWgradPlan wg;
+    int cpad;  // the data gradient's N tile padding of Cin
+    size_t slab, wp, total;
+};
+DensePlan dense_plan(int B, int H, int W, int Cin, int Cout, bool need_gx) {
+    DensePlan P;
+    P.wg = cp_conv_wgrad_plan((size_t)B * H, Cout, Cin, 16);
+    P.cpad = (int)cp_engine::align_up((size_t)Cin, cp_conv_tile_n(Cin));
+    size_t o = 0;
+    P.slab = o;
+    o += al(P.wg.slab_bytes);
+    P.wp = o;
+    o += al(need_gx ? (size_t)16 * Cout * P.cpad * 4 : 0);
+    P.total = o;
+    return P;
+}
+
+}  // namespace
+
+bool cp_deconv_dw_geometry(int Cin, int Cout, int K, int stride, int pad, int groups) {
+    return groups == Cin && Cin == Cout && (stride == 2 || stride == 4) && K == 2 * stride && pad == stride / 2 && Cin >= 4 &&
+           Cin % 4 == 0 && (size_t)K * K * Cin * sizeof(float) <= CP_DECONV_DW_TABLE_BYTES;
+}
+
+bool cp_deconv_dense_geometry(int Cin, int Cout, int K, int stride, int pad, int groups) {
+    return groups == 1 && K == 4 && stride == 2 && pad == 1 && Cin >= 32 && Cin % 32 == 0 && Cout >= 32 && Cout % 32 == 0;
+}
+
+size_t cp_deconv_backward_ws_bytes(int B, int H, int W, int Cin, int Cout, int stride, int groups, int need_grad_x) {
+    if (groups != 1) return al(dw_plan(B, H, W, Cin, stride).part_bytes);
+    return dense_plan(B, H, W, Cin, Cout, need_grad_x != 0).total;
+}
+
+int cp_launch_deconv_backward(hipStream_t s, const DeconvBwdArgs& a, void* ws) {
+    if (a.groups != 1) {
+        const DwPlan P = dw_plan(a.B, a.H, a.W, a.Cin, a.stride);
+        float* part = (float*)ws;
+        if (P.G == 1)
+            hipLaunchKernelGGL(dw_bwd_kernel<1>, dim3(P.slabs), dim3(256), P.lds, s, a.x, a.w, a.go, a.gx, part, a.B, a.H, a.W, a.Cin,
+                               a.stride, P.px_per_slab);
+        else
+            hipLaunchKernelGGL(dw_bwd_kernel<4>, dim3(P.slabs), dim3(256), P.lds, s, a.x, a.w, a.go, a.gx, part, a.B, a.H, a.W, a.Cin,
+                               a.stride, P.px_per_slab);
+        if (!ok()) return CP_ERR_LAUNCH;
+        const int kk = 4 * a.stride * a.stride;
+        hipLaunchKernelGGL(dw_wgrad_reduce_kernel, dim3((kk * a.Cin + 31) / 32), dim3(256), 0, s, (const float*)part, a.gw, P.slabs,
+                           a.Cin, kk);
+        return ok() ? CP_OK : CP_ERR_LAUNCH;
+    }
+    const DensePlan P = dense_plan(a.B, a.H, a.W, a.Cin, a.Cout, a.gx != nullptr);
+    char* w8 = (char*)ws;
+    // grad_w: the stride-2 convolution's weight gradient with grad_out as its input and x as its output gradient
+    const ConvBwdArgs c{a.go, nullptr, nullptr, nullptr, nullptr, a.gw, nullptr, a.B, 2 * a.H, 2 * a.W, a.Cout, a.Cin, 4, 4, 2, 1};
+    int rc = cp_launch_conv_wgrad(s, c, a.x, a.Cin, P.wg, (float*)(w8 + P.slab), 0);
+    if (rc != CP_OK || !a.gx) return rc;
+    // grad_x = conv2d(grad_out, w as [out = Cin][in = Cout][4][4], stride 2, pad 1), exact float32
+    float* wp = (float*)(w8 + P.wp);
+    if (hipMemsetAsync(wp, 0, (size_t)16 * a.Cout * P.cpad * 4, s) != hipSuccess) return CP_ERR_LAUNCH;
+    rc = cp_launch_pack_weight(a.w, wp, a.Cin, a.Cout, 16, a.Cout, P.cpad, 0, s);
+    if (rc != CP_OK) return rc;
+    ConvParams d = cp_engine::conv_params(a.B, 2 * a.H, 2 * a.W, &a.go, &a.Cout, 1,
+                                          cp_engine::conv_w_f32(wp, nullptr, nullptr, a.Cout, a.Cin, 4, 4), 2, 1, CP_ACT_NONE);
+    d.dbg = 0;  // cp_set_debug's switches choose among inference kernels for A/B runs: a gradient does not depend on them
+    d.out = a.gx;
+    d.store = CP_STORE_NHWC;
+    d.ldo = a.Cin;
+    return cp_launch_conv(d, s);
+}

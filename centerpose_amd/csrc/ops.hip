@@ -1,6 +1,6 @@
 // The stand-alone operators of the C ABI (include/centerpose_hip.h): single layers on caller tensors, outside any cp_model
 // -- cp_conv2d_nhwc / cp_conv2d_backward_nhwc, cp_batchnorm_forward_nhwc / _backward_nhwc, cp_conv_transpose2d_nhwc,
-// cp_dcnv2_forward / cp_dcnv2_backward, cp_pose_heads_forward / _backward.
+// cp_conv_transpose2d_dw_nhwc / cp_conv_transpose2d_backward_nhwc, cp_dcnv2_forward / cp_dcnv2_backward, cp_pose_heads_forward / _backward.
 // Each packs its PyTorch-layout weights into a caller-provided workspace on every call and then launches the same kernels as
 // the engine.
 #include "engine_model.h"
@@ -214,6 +214,23 @@ const char* conv_bwd_shape_error(int B, int H, int W, int Cin, int Cout, int KH,
     const long long lim = 0x7fffffffLL, cop = ((long long)Cout + 31) / 32 * 32;
     if ((long long)B * H * W * Cin >= lim || (long long)B * ho * wo * cop >= lim || cop * Cin * KH * KW >= lim)
         return "conv2d_backward: a tensor has 2^31 elements or more";
+    return nullptr;
+}
+
+// ConvTranspose2d backward and the depth-wise forward: shape checks shared by the calls and the workspace query, kernels in
+// deconv_bwd.hip and ewise.hip
+const char* deconv_shape_error(int B, int H, int W, int Cin, int Cout, int K, int stride, int pad, int groups) {
+    if (B < 1 || H < 1 || W < 1) return "conv_transpose2d: B, H and W must be at least 1";
+    const bool dw = cp_deconv_dw_geometry(Cin, Cout, K, stride, pad, groups);
+    if (!dw && !cp_deconv_dense_geometry(Cin, Cout, K, stride, pad, groups))
+        return "conv_transpose2d: unsupported geometry (depth-wise: groups == Cin == Cout, stride 2 or 4, K == 2 stride, pad == "
+               "stride / 2, C % 4 == 0, K K C floats within the LDS table; dense: groups 1, K 4, stride 2, pad 1, Cin and Cout "
+               "multiples of 32)";
+    // (the depth-wise kernels address their tensors through 32-bit byte offsets: 2^30 elements)
+    const long long lim = dw ? 0x40000000LL : 0x7fffffffLL, px = (long long)B * H * W;
+    if (px * Cin >= lim || px * stride * stride * Cout >= lim || (long long)Cin * (Cout / groups) * K * K >= lim)
+        return dw ? "conv_transpose2d: a tensor has 2^30 elements or more (the depth-wise kernels' limit)"
+                  : "conv_transpose2d: a tensor has 2^31 elements or more";
     return nullptr;
 }
 
@@ -451,6 +468,38 @@ int cp_conv2d_backward_nhwc(cp_stream_t stream, const float* x, const float* w, 
     const ConvBwdArgs a{x, w, y_or_null, grad_out, grad_x_or_null, grad_w, grad_bias_or_null, B, H, W, Cin, Cout, KH, KW, stride, pad};
     const int rc = cp_launch_conv_backward((hipStream_t)stream, a, workspace);
     return rc == CP_OK ? CP_OK : fail(rc, "conv2d_backward: kernel launch failed");
+}
+
+int cp_conv_transpose2d_dw_nhwc(cp_stream_t stream, const float* x, const float* w, const float* add_or_null, float* out, int B,
+                                int H, int W, int C, int f) {
+    if (const char* e = deconv_shape_error(B, H, W, C, C, 2 * f, f, f / 2, C)) return fail(CP_ERR_INVALID, e);
+    if (!x || !w || !out) return fail(CP_ERR_INVALID, "conv_transpose2d_dw: null argument");
+    if (!bn_aligned({x, w, add_or_null, out})) return fail(CP_ERR_INVALID, "conv_transpose2d_dw: tensors must be 16-byte aligned");
+    const int rc = cp_launch_upsample_add(x, w, add_or_null, out, B, H, W, C, f, nullptr, (hipStream_t)stream);
+    return rc == CP_OK ? CP_OK : fail(rc, "conv_transpose2d_dw: kernel launch failed");
+}
+
+size_t cp_conv_transpose2d_backward_workspace_bytes(int B, int H, int W, int Cin, int Cout, int K, int stride, int pad, int groups,
+                                                    int need_grad_x) {
+    if (const char* e = deconv_shape_error(B, H, W, Cin, Cout, K, stride, pad, groups)) {
+        fail(CP_ERR_INVALID, e);
+        return 0;
+    }
+    return cp_deconv_backward_ws_bytes(B, H, W, Cin, Cout, stride, groups, need_grad_x);
+}
+
+int cp_conv_transpose2d_backward_nhwc(cp_stream_t stream, const float* x, const float* w, const float* grad_out,
+                                      float* grad_x_or_null, float* grad_w, int B, int H, int W, int Cin, int Cout, int K,
+                                      int stride, int pad, int groups, void* workspace, size_t workspace_bytes) {
+    if (const char* e = deconv_shape_error(B, H, W, Cin, Cout, K, stride, pad, groups)) return fail(CP_ERR_INVALID, e);
+    if (!x || !w || !grad_out || !grad_w || !workspace) return fail(CP_ERR_INVALID, "conv_transpose2d_backward: null argument");
+    if (!bn_aligned({x, w, grad_out, grad_x_or_null, grad_w, workspace}))
+        return fail(CP_ERR_INVALID, "conv_transpose2d_backward: tensors must be 16-byte aligned");
+    if (workspace_bytes < cp_deconv_backward_ws_bytes(B, H, W, Cin, Cout, stride, groups, grad_x_or_null != nullptr))
+        return fail(CP_ERR_INVALID, "conv_transpose2d_backward: workspace too small");
+    const DeconvBwdArgs a{x, w, grad_out, grad_x_or_null, grad_w, B, H, W, Cin, Cout, stride, groups};
+    const int rc = cp_launch_deconv_backward((hipStream_t)stream, a, workspace);
+    return rc == CP_OK ? CP_OK : fail(rc, "conv_transpose2d_backward: kernel launch failed");
 }
 
 size_t cp_batchnorm_workspace_bytes(int B, int H, int W, int C) {

@@ -131,6 +131,9 @@ def lib():
          *([c_int] * 10), c_void_p, c_size_t)
     _sig(L.cp_conv2d_backward_workspace_bytes, c_size_t, *([c_int] * 10))
     _sig(L.cp_conv2d_backward_nhwc, c_int, *([c_void_p] * 8), *([c_int] * 9), c_void_p, c_size_t)
+    _sig(L.cp_conv_transpose2d_dw_nhwc, c_int, *([c_void_p] * 5), *([c_int] * 5))
+    _sig(L.cp_conv_transpose2d_backward_workspace_bytes, c_size_t, *([c_int] * 10))
+    _sig(L.cp_conv_transpose2d_backward_nhwc, c_int, *([c_void_p] * 6), *([c_int] * 9), c_void_p, c_size_t)
     _sig(L.cp_batchnorm_workspace_bytes, c_size_t, *([c_int] * 4))
     _sig(L.cp_batchnorm_forward_nhwc, c_int, *([c_void_p] * 10), *([c_int] * 5), ctypes.c_float, ctypes.c_float, c_int, c_void_p,
          c_size_t)
@@ -232,7 +235,9 @@ def exported_symbols():
             "cp_decode_gathered", "cp_pose_heads_chunk_images", "cp_pose_heads_forward_workspace_bytes",
             "cp_pose_heads_forward", "cp_pose_heads_backward_workspace_bytes", "cp_pose_heads_backward",
             "cp_model_features", "cp_conv2d_backward_workspace_bytes", "cp_conv2d_backward_nhwc",
-            "cp_batchnorm_workspace_bytes", "cp_batchnorm_forward_nhwc", "cp_batchnorm_backward_nhwc"]
+            "cp_batchnorm_workspace_bytes", "cp_batchnorm_forward_nhwc", "cp_batchnorm_backward_nhwc",
+            "cp_conv_transpose2d_dw_nhwc", "cp_conv_transpose2d_backward_workspace_bytes",
+            "cp_conv_transpose2d_backward_nhwc"]
 
 
 def _check(rc, what):
@@ -593,6 +598,53 @@ def conv_transpose2d(x, w, scale=None, shift=None, act=0):
                                     B, H, W, Cin, Cout, act, _ptr(ws), nbytes)
     _check(rc, "cp_conv_transpose2d_nhwc")
     return out
+
+
+def conv_transpose2d_dw(x, w, f, add=None):
+    """IDAUp's depth-wise up-sampling (cp_conv_transpose2d_dw_nhwc): x [B,H,W,C] NHWC, w [C,1,2f,2f] (ConvTranspose2d(C, C, 2f,
+    stride=f, padding=f//2, groups=C) layout), add [B,fH,fW,C] or None -> add + up(x), [B,fH,fW,C] NHWC.  Float32."""
+    L = lib()
+    x, w = _dev(x), _dev(w)
+    f = int(f)
+    if x.dim() != 4 or w.dim() != 4 or tuple(w.shape) != (x.shape[3], 1, 2 * f, 2 * f):
+        raise RuntimeError("conv_transpose2d_dw: x must be [B,H,W,C] and w [C,1,2f,2f], got %s and %s (f = %d)"
+                           % (tuple(x.shape), tuple(w.shape), f))
+    B, H, W, C = x.shape
+    if add is not None:
+        add = _dev(add)
+        if tuple(add.shape) != (B, f * H, f * W, C):
+            raise RuntimeError("conv_transpose2d_dw: add has shape %s, expected %s" % (tuple(add.shape), (B, f * H, f * W, C)))
+    out = torch.empty(B, f * H, f * W, C, device=x.device, dtype=torch.float32)
+    rc = L.cp_conv_transpose2d_dw_nhwc(_stream(), _ptr(x), _ptr(w), _ptr(add), _ptr(out), B, H, W, C, f)
+    _check(rc, "cp_conv_transpose2d_dw_nhwc")
+    return out
+
+
+def conv_transpose2d_backward(x, w, grad_out, stride, pad, groups=1, need_x_grad=True):
+    """Gradients of a bias-free ``ConvTranspose2d`` (cp_conv_transpose2d_backward_nhwc): x [B,H,W,Cin] NHWC, w [Cin,Cout/groups,K,K],
+    grad_out [B,stride H,stride W,Cout] NHWC -> (grad_x [B,H,W,Cin] | None, grad_w like w).  Depth-wise (groups == Cin == Cout,
+    stride 2 or 4, K = 2 stride, pad = stride / 2) or dense (groups 1, K 4, stride 2, pad 1).  Float32 and bitwise reproducible."""
+    L = lib()
+    x, w, grad_out = _dev(x), _dev(w), _dev(grad_out)
+    stride, pad, groups = int(stride), int(pad), int(groups)
+    if x.dim() != 4 or w.dim() != 4 or w.shape[0] != x.shape[3] or w.shape[2] != w.shape[3] or groups < 1:
+        raise RuntimeError("conv_transpose2d_backward: x must be [B,H,W,Cin] and w [Cin,Cout/groups,K,K], got %s and %s"
+                           % (tuple(x.shape), tuple(w.shape)))
+    B, H, W, Cin = x.shape
+    Cout, K = w.shape[1] * groups, w.shape[2]
+    nbytes = L.cp_conv_transpose2d_backward_workspace_bytes(B, H, W, Cin, Cout, K, stride, pad, groups, int(bool(need_x_grad)))
+    if nbytes == 0:
+        raise RuntimeError("conv_transpose2d_backward: shape refused by the library (%s)" % L.cp_last_error().decode())
+    if tuple(grad_out.shape) != (B, stride * H, stride * W, Cout):
+        raise RuntimeError("conv_transpose2d_backward: grad_out has shape %s, expected %s"
+                           % (tuple(grad_out.shape), (B, stride * H, stride * W, Cout)))
+    grad_x = torch.empty_like(x) if need_x_grad else None
+    grad_w = torch.empty_like(w)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    rc = L.cp_conv_transpose2d_backward_nhwc(_stream(), _ptr(x), _ptr(w), _ptr(grad_out), _ptr(grad_x), _ptr(grad_w), B, H, W, Cin,
+                                             Cout, K, stride, pad, groups, _ptr(ws), nbytes)
+    _check(rc, "cp_conv_transpose2d_backward_nhwc")
+    return grad_x, grad_w
 
 
 PRECISIONS = {"f32": 0, "f16x3": 1}

@@ -362,6 +362,36 @@ int cp_conv_transpose2d_nhwc(cp_stream_t stream, const float* x, const float* w,
                              size_t workspace_bytes);
 
 /* ------------------------------------------------------------------------------------------
+ * ConvTranspose2d for training — the up-sampling layers of both backbone families, float32 NHWC:
+ *   depth-wise  IDAUp's `up` of models/networks/pose_dla_dcn.py:402-417: ConvTranspose2d(C, C, K = 2 f, stride f, padding f / 2,
+ *               groups C, bias=False), w [C,1,K,K] (PyTorch layout), x [B,H,W,C] -> [B,fH,fW,C].
+ *   dense       the deconv layers of models/networks/resnet_dcn.py:232-240: ConvTranspose2d(Cin, Cout, 4, stride 2, padding 1,
+ *               bias=False), w [Cin,Cout,4,4], x [B,H,W,Cin] -> [B,2H,2W,Cout] (forward: cp_conv_transpose2d_nhwc above).
+ * cp_conv_transpose2d_dw_nhwc is the depth-wise forward, out = add_or_null + up(x): the kernel the engine's IDAUp runs, with
+ * the `layers[i] + layers[i - 1]` of the following node fused (add and out [B,fH,fW,C]; NULL: no addend).  No workspace.
+ * cp_conv_transpose2d_backward_nhwc: autograd's gradients of either layer from grad_out [B, stride H, stride W, Cout]:
+ * grad_w in w's layout and grad_x [B,H,W,Cin], written, not accumulated; a NULL grad_x is not computed and not touched.
+ * Arithmetic is float32 whatever cp_set_default_precision says; every sum has a fixed order and there are no atomics, so all
+ * outputs are bitwise reproducible call to call.
+ * Accepted geometries:
+ *   depth-wise  groups == Cin == Cout, stride in {2, 4}, K == 2 stride, pad == stride / 2, C % 4 == 0, and the [K K][C] float
+ *               weight table within the 60 KiB of LDS the kernels stage it in: C <= 960 at stride 2, C <= 240 at stride 4
+ *               (the forward call takes the same set); tensors below 2^30 elements (32-bit byte offsets)
+ *   dense       groups == 1, K == 4, stride == 2, pad == 1, Cin % 32 == 0, Cout % 32 == 0
+ * Refused with CP_ERR_INVALID and a cp_last_error() text before any launch (the query returns 0): a NULL pointer other than
+ * those named *_or_null, a workspace below the query, B / H / W < 1, another geometry, a tensor of 2^31 elements or more, a
+ * pointer that is not 16-byte aligned.  The query is host arithmetic and monotone in B; need_grad_x == 0 leaves out the data
+ * gradient's operands.  Launches on `stream`, never synchronises.
+ * ------------------------------------------------------------------------------------------ */
+int cp_conv_transpose2d_dw_nhwc(cp_stream_t stream, const float* x, const float* w, const float* add_or_null, float* out,
+                                int B, int H, int W, int C, int f);
+size_t cp_conv_transpose2d_backward_workspace_bytes(int B, int H, int W, int Cin, int Cout, int K, int stride, int pad,
+                                                    int groups, int need_grad_x);
+int cp_conv_transpose2d_backward_nhwc(cp_stream_t stream, const float* x, const float* w, const float* grad_out,
+                                      float* grad_x_or_null, float* grad_w, int B, int H, int W, int Cin, int Cout, int K,
+                                      int stride, int pad, int groups, void* workspace, size_t workspace_bytes);
+
+/* ------------------------------------------------------------------------------------------
  * Heat-map decode — replaces `object_pose_decode(..., Inference=True)` (models/decode.py:72-375,
  *   models/utils.py:43-47; called from detectors/object_pose.py:154-161) including the 13
  *   device->host copies and the per-point Python loop (decode.py:191-252).
