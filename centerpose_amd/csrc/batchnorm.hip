@@ -16,12 +16,13 @@
 //                                         about its own first row (E[x^2] - mean^2 from raw sums loses every digit at
 //                                         |mean| >> std); lanes are merged by Chan's rule in its many-way form: mean = ref +
 //                                         sum n_i (m_i - ref) / n, M2 = sum M2_i + n_i (m_i - mean)^2, in lane order.
-//                        finalize_kernel  the slabs merged by the same rule, 8 slab lanes x 32 channels, slabs ascending per lane
-//                                         then the lanes in order; writes save_mean, save_invstd, updates the running pair.
+//                        finalize_kernel  the slabs merged by the same rule, each round a two_level_sum (op_common.h); writes
+//                                         save_mean, save_invstd, updates the running pair.
 //   forward, evaluation  eval_stats_kernel  save_mean / save_invstd from the running pair.
 //   forward              apply_kernel     y, whole lines in and out.
 //   backward             bwd_reduce_kernel / bwd_finalize_kernel   grad_beta = sum g, grad_gamma = sum g * xhat (g gated by y > 0)
 //                        bwd_apply_kernel grad_x (and grad_residual = g when asked) in one pass.
+#include "op_common.h"
 #include "igemm_common.h"
 
 #include <algorithm>
@@ -128,38 +129,27 @@ __global__ __launch_bounds__(256) void stats_kernel(const float* __restrict__ x,
     st4(out + C, M2);
 }
 
-// The slabs merged per channel: a workgroup is 32 channels x 8 slab lanes; a lane walks the slabs sl, sl + 8, ... in ascending
-// order, then the eight lanes are added in lane order.  Two rounds: the mean about slab 0's, then M2 about that mean.
+// The slabs merged per channel, 32 channels per workgroup, in two rounds of two_level_sum: the mean about slab 0's, then M2
+// about that mean.
 __global__ __launch_bounds__(256) void finalize_kernel(const float* __restrict__ part, float* __restrict__ save_mean,
                                                        float* __restrict__ save_invstd, float* __restrict__ rmean,
                                                        float* __restrict__ rvar, int P, int C, int slab_px, int nslab, float momentum,
                                                        float eps) {
     __shared__ float red[256];
-    const int el = threadIdx.x & 31, sl = threadIdx.x >> 5, c = blockIdx.x * 32 + el;
+    const int c = blockIdx.x * 32 + (threadIdx.x & 31);
     const bool cv = c < C;
     const float ref = cv ? part[c] : 0.f, n = (float)P;
     auto rows = [&](int s) { return (float)min(slab_px, P - s * slab_px); };
-    float a = 0.f;
-    if (cv)
-        for (int s = sl; s < nslab; s += 8) a = fmaf(rows(s), part[(size_t)s * 2 * C + c] - ref, a);
-    red[threadIdx.x] = a;
-    __syncthreads();
-    float t = red[el];
-    for (int j = 1; j < 8; ++j) t += red[j * 32 + el];
+    const float t = two_level_sum(red, cv, nslab, 0.f,
+                                  [&](float a, int s) { return fmaf(rows(s), part[(size_t)s * 2 * C + c] - ref, a); });
     const float mean = ref + t / n;
     __syncthreads();
-    float b = 0.f;
-    if (cv)
-        for (int s = sl; s < nslab; s += 8) {
-            const float* ps = part + (size_t)s * 2 * C + c;
-            const float d = ps[0] - mean;
-            b += fmaf(rows(s) * d, d, ps[C]);
-        }
-    red[threadIdx.x] = b;
-    __syncthreads();
-    if (sl != 0 || !cv) return;
-    float M2 = red[el];
-    for (int j = 1; j < 8; ++j) M2 += red[j * 32 + el];
+    const float M2 = two_level_sum(red, cv, nslab, 0.f, [&](float b, int s) {
+        const float* ps = part + (size_t)s * 2 * C + c;
+        const float d = ps[0] - mean;
+        return b + fmaf(rows(s) * d, d, ps[C]);
+    });
+    if (threadIdx.x >= 32 || !cv) return;
     save_mean[c] = mean;
     save_invstd[c] = 1.f / sqrtf(M2 / n + eps);
     if (rmean) rmean[c] = (1.f - momentum) * rmean[c] + momentum * mean;
@@ -274,31 +264,29 @@ __global__ __launch_bounds__(256) void bwd_reduce_kernel(const float* __restrict
     st4(out + C, s2);
 }
 
-// sums[0][c] = grad_beta, sums[1][c] = grad_gamma = invstd * sum g (x - mean), in finalize_kernel's order; the caller's
-// grad_beta / grad_gamma get a copy when given
+struct Sum2 {
+    float a, b;
+};
+__device__ __forceinline__ Sum2 operator+(const Sum2 x, const Sum2 y) { return {x.a + y.a, x.b + y.b}; }
+
+// sums[0][c] = grad_beta, sums[1][c] = grad_gamma = invstd * sum g (x - mean), both by one two_level_sum over the slabs; the
+// caller's grad_beta / grad_gamma get a copy when given
 __global__ __launch_bounds__(256) void bwd_finalize_kernel(const float* __restrict__ part, const float* __restrict__ invstd,
                                                            float* __restrict__ sums, float* __restrict__ gg, float* __restrict__ gb,
                                                            int C, int nslab) {
-    __shared__ float r1[256], r2[256];
-    const int el = threadIdx.x & 31, sl = threadIdx.x >> 5, c = blockIdx.x * 32 + el;
+    __shared__ Sum2 red[256];
+    const int c = blockIdx.x * 32 + (threadIdx.x & 31);
     const bool cv = c < C;
-    float a = 0.f, b = 0.f;
-    if (cv)
-        for (int s = sl; s < nslab; s += 8) {
-            const float* ps = part + (size_t)s * 2 * C + c;
-            a += ps[0];
-            b += ps[C];
-        }
-    r1[threadIdx.x] = a;
-    r2[threadIdx.x] = b;
-    __syncthreads();
-    if (sl != 0 || !cv) return;
-    for (int j = 1; j < 8; ++j) a += r1[j * 32 + el], b += r2[j * 32 + el];
-    b *= invstd[c];
-    sums[c] = a;
-    sums[C + c] = b;
-    if (gb) gb[c] = a;
-    if (gg) gg[c] = b;
+    Sum2 t = two_level_sum(red, cv, nslab, Sum2{0.f, 0.f}, [&](Sum2 v, int s) {
+        const float* ps = part + (size_t)s * 2 * C + c;
+        return v + Sum2{ps[0], ps[C]};
+    });
+    if (threadIdx.x >= 32 || !cv) return;
+    t.b *= invstd[c];
+    sums[c] = t.a;
+    sums[C + c] = t.b;
+    if (gb) gb[c] = t.a;
+    if (gg) gg[c] = t.b;
 }
 
 // training: grad_x = gamma * invstd * (g - grad_beta / n - xhat * grad_gamma / n); evaluation: gamma * invstd * g;
@@ -356,15 +344,12 @@ __global__ __launch_bounds__(256) void bwd_apply_kernel(const float* __restrict_
     for (; j < n; ++j, off += step) put(off, ldg(off), ldx(off));
 }
 
-inline bool ok() { return hipGetLastError() == hipSuccess; }
-
 // Slabs of whole workgroup steps (S rows).  Reductions: at least eight steps per slab and at most about 2048 workgroups, so the
 // partials stay small and the finalize short; element-wise passes: eight steps per workgroup.
 struct Plan {
     int P, npass, S;
     int red_px, red_slabs, red_bound;  // rows per slab, slabs, and a bound on them that is monotone in P (sizes the workspace)
     int app_px, app_slabs;
-    size_t part, sums, total;
 };
 
 Plan plan(int B, int H, int W, int C) {
@@ -379,49 +364,61 @@ Plan plan(int B, int H, int W, int C) {
     p.red_slabs = (p.P + p.red_px - 1) / p.red_px;
     p.app_px = 8 * p.S;
     p.app_slabs = (p.P + p.app_px - 1) / p.app_px;
-    const auto al = [](size_t x) { return (x + 255) / 256 * 256; };
-    p.part = 0;
-    p.sums = al((size_t)p.red_bound * 2 * C * 4);
-    p.total = p.sums + al((size_t)2 * C * 4);
     return p;
+}
+
+struct Ws {
+    float *part, *sums;  // the slabs' partials [slab][2][C]; the backward's two sums [2][C]
+};
+Ws bn_carve(Carve& c, const Plan& p, int C) {
+    Ws r;
+    r.part = c.take<float>((size_t)p.red_bound * 2 * C * 4);
+    r.sums = c.take<float>((size_t)2 * C * 4);
+    return r;
 }
 
 }  // namespace
 
-size_t cp_batchnorm_ws_bytes(int B, int H, int W, int C) { return plan(B, H, W, C).total; }
+size_t cp_batchnorm_ws_bytes(int B, int H, int W, int C) {
+    Carve c{nullptr};
+    bn_carve(c, plan(B, H, W, C), C);
+    return c.off;
+}
 
 int cp_launch_batchnorm_forward(hipStream_t s, const BnFwdArgs& a, void* ws) {
     const Plan p = plan(a.B, a.H, a.W, a.C);
-    float* part = (float*)((char*)ws + p.part);
+    Carve cv{(char*)ws};
+    float* part = bn_carve(cv, p, a.C).part;
     if (a.training) {
         hipLaunchKernelGGL(stats_kernel, dim3(p.red_slabs, p.npass), dim3(256), 0, s, a.x, part, p.P, a.C, p.red_px);
-        if (!ok()) return CP_ERR_LAUNCH;
+        if (!launch_ok()) return CP_ERR_LAUNCH;
         hipLaunchKernelGGL(finalize_kernel, dim3((a.C + 31) / 32), dim3(256), 0, s, (const float*)part, a.mean, a.invstd, a.rmean,
                            a.rvar, p.P, a.C, p.red_px, p.red_slabs, a.momentum, a.eps);
     } else {
         hipLaunchKernelGGL(eval_stats_kernel, dim3((a.C + 255) / 256), dim3(256), 0, s, (const float*)a.rmean, (const float*)a.rvar,
                            a.mean, a.invstd, a.C, a.eps);
     }
-    if (!ok()) return CP_ERR_LAUNCH;
+    if (!launch_ok()) return CP_ERR_LAUNCH;
     hipLaunchKernelGGL(apply_kernel, dim3(p.app_slabs, p.npass), dim3(256), 0, s, a.x, a.res, a.y, (const float*)a.mean,
                        (const float*)a.invstd, a.gamma, a.beta, p.P, a.C, p.app_px, a.act);
-    return ok() ? CP_OK : CP_ERR_LAUNCH;
+    return launch_ok() ? CP_OK : CP_ERR_LAUNCH;
 }
 
 int cp_launch_batchnorm_backward(hipStream_t s, const BnBwdArgs& a, void* ws) {
     const Plan p = plan(a.B, a.H, a.W, a.C);
-    float* part = (float*)((char*)ws + p.part);
-    float* sums = (float*)((char*)ws + p.sums);
+    Carve cv{(char*)ws};
+    const Ws r = bn_carve(cv, p, a.C);
+    float *part = r.part, *sums = r.sums;
     if (a.gg || a.gb || (a.training && a.gx)) {
         hipLaunchKernelGGL(bwd_reduce_kernel, dim3(p.red_slabs, p.npass), dim3(256), 0, s, a.x, a.y, a.go, a.mean, part, p.P, a.C,
                            p.red_px);
-        if (!ok()) return CP_ERR_LAUNCH;
+        if (!launch_ok()) return CP_ERR_LAUNCH;
         hipLaunchKernelGGL(bwd_finalize_kernel, dim3((a.C + 31) / 32), dim3(256), 0, s, (const float*)part, a.invstd, sums, a.gg,
                            a.gb, a.C, p.red_slabs);
-        if (!ok()) return CP_ERR_LAUNCH;
+        if (!launch_ok()) return CP_ERR_LAUNCH;
     }
     if (!a.gx && !a.gres) return CP_OK;
     hipLaunchKernelGGL(bwd_apply_kernel, dim3(p.app_slabs, p.npass), dim3(256), 0, s, a.x, a.y, a.go, a.gamma, a.mean, a.invstd,
                        (const float*)sums, a.gx, a.gres, p.P, a.C, p.app_px, a.training);
-    return ok() ? CP_OK : CP_ERR_LAUNCH;
+    return launch_ok() ? CP_OK : CP_ERR_LAUNCH;
 }

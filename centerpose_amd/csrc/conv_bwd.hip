@@ -17,7 +17,8 @@
 //               path: a gather per grad_x element (dgrad_generic_kernel).  Not launched when the caller passes no grad_x.
 // The MFMA weight gradient and the stride-1 data gradient are also the library's only ones: cp_launch_conv_wgrad and
 // cp_launch_conv_dgrad_pack / _s1 (cp_common.h) are what step 1 and 2 call, and what heads_bwd.hip calls for its 3x3 layer.
-#include "engine_model.h"
+// cp_launch_rowsum_nchw, the NCHW bias gradient of dcn_bwd.hip and heads_bwd.hip, is here for the same reason.
+#include "op_common.h"
 #include "igemm_common.h"
 
 #include <algorithm>
@@ -56,24 +57,13 @@ __global__ __launch_bounds__(256) void stage_kernel(const float* __restrict__ go
     }
 }
 
-// Slab sums in a fixed two-level order: a workgroup is 32 elements x 8 slab lanes; lane l adds the slabs l, l + 8, ... in
-// ascending order, then the eight lanes are added in lane order (a serial walk over up to 512 slabs is one long chain of
-// dependent adds behind strided loads).
-// gb[c] = the slabs' partials
+// gb[c] = the slabs' partials (two_level_sum)
 __global__ __launch_bounds__(256) void bias_reduce_kernel(const float* __restrict__ part, float* __restrict__ gb, int nslab, int Cout,
                                                           int CoP) {
     __shared__ float red[256];
-    const int el = threadIdx.x & 31, sl = threadIdx.x >> 5, c = blockIdx.x * 32 + el;
-    float v = 0.f;
-    if (c < Cout)
-        for (int s = sl; s < nslab; s += 8) v += part[(size_t)s * CoP + c];
-    red[threadIdx.x] = v;
-    __syncthreads();
-    if (sl == 0 && c < Cout) {
-        float t = red[el];
-        for (int j = 1; j < 8; ++j) t += red[j * 32 + el];
-        gb[c] = t;
-    }
+    const int c = blockIdx.x * 32 + (threadIdx.x & 31);
+    const float t = two_level_sum(red, c < Cout, nslab, 0.f, [&](float v, int s) { return v + part[(size_t)s * CoP + c]; });
+    if (threadIdx.x < 32 && c < Cout) gb[c] = t;
 }
 
 // slab[s][co][k] over the output rows [s * rows_per_slab, ...): D[co][k] with K = output pixels, two per MFMA step (lane half
@@ -169,25 +159,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void w
         }
 }
 
-// grad_w[co][c][tap] = the slabs [co][tap * Cin + c] (co < Cout of CoP rows), summed in bias_reduce_kernel's two-level order;
-// threads walk the slabs' own element order (whole 128-byte lines per slab) and scatter the one write.  `accum`: the value
-// already in grad_w is added last, to the finished sum of the slabs (a caller that works through its batch in chunks: chunks
-// in chunk order); without it the slabs' sum is stored as it is.
+// grad_w[co][c][tap] = the slabs [co][tap * Cin + c] (co < Cout of CoP rows), summed by two_level_sum; threads walk the slabs'
+// own element order (whole 128-byte lines per slab) and scatter the one write.  `accum`: the value already in grad_w is added
+// LAST, to the finished sum of the slabs (a caller that works through its batch in chunks: chunks in chunk order); without it
+// the slabs' sum is stored as it is.
 __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ slab, float* __restrict__ gw, int nslab, int Cout,
                                                            int CoP, int Cin, int taps, int accum) {
     __shared__ float red[256];
     const size_t TC = (size_t)taps * Cin, n = (size_t)Cout * TC, ss = (size_t)CoP * TC;
-    const int el = threadIdx.x & 31, sl = threadIdx.x >> 5;
     for (size_t base = (size_t)blockIdx.x * 32; base < n; base += (size_t)gridDim.x * 32) {  // (uniform per workgroup)
-        const size_t i = base + el;
-        float v = 0.f;
-        if (i < n)
-            for (int s = sl; s < nslab; s += 8) v += slab[(size_t)s * ss + i];
-        red[threadIdx.x] = v;
-        __syncthreads();
-        if (sl == 0 && i < n) {
-            float t = red[el];
-            for (int j = 1; j < 8; ++j) t += red[j * 32 + el];
+        const size_t i = base + (threadIdx.x & 31);
+        const float t = two_level_sum(red, i < n, nslab, 0.f, [&](float v, int s) { return v + slab[(size_t)s * ss + i]; });
+        if (threadIdx.x < 32 && i < n) {
             const size_t h = i / TC;
             const int k = (int)(i - h * TC), tap = k / Cin, c = k - tap * Cin;
             float* dst = gw + (h * Cin + c) * taps + tap;
@@ -224,9 +207,7 @@ __global__ void wgrad_generic_kernel(const float* __restrict__ gs, const float* 
 __global__ void slab_reduce_kernel(const float* __restrict__ slab, float* __restrict__ out, int nslab, int n) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n) return;
-    float v = 0.f;
-    for (int s = 0; s < nslab; ++s) v += slab[(size_t)s * n + e];
-    out[e] = v;
+    out[e] = serial_sum(slab, nslab, n, e, 0.f);
 }
 
 // Generic data gradient, gather form: one thread per grad_x element; taps in (ky, kx) order, output channels ascending
@@ -256,6 +237,24 @@ __global__ void dgrad_generic_kernel(const float* __restrict__ gs, const float* 
         }
         gx[e] = v;
     }
+}
+
+// out[c] = sum over images and pixels of g [B][C][HW]: a fixed per-thread stride and a fixed tree
+__global__ __launch_bounds__(256) void rowsum_kernel(const float* __restrict__ g, float* __restrict__ out, int B, int C, int HW) {
+    __shared__ float red[256];
+    const int c = blockIdx.x;
+    float v = 0.f;
+    for (int b = 0; b < B; ++b) {
+        const float* pl = g + ((size_t)b * C + c) * HW;
+        for (int e = threadIdx.x; e < HW; e += 256) v += pl[e];
+    }
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[c] = red[0];
 }
 
 // Stride-1 data gradient operand: wB[(taps - 1 - tap) * CoP + co][c] = w[co][c][tap] (buffer pre-zeroed: pad rows co >= Cout and
@@ -385,8 +384,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void d
         }
 }
 
-inline size_t al(size_t x) { return (x + 255) / 256 * 256; }
-inline bool ok() { return hipGetLastError() == hipSuccess; }
 inline int nh_of(int c) { return c % 128 == 0 ? 4 : c % 64 == 0 ? 2 : 1; }
 
 // Weight-gradient slabs of whole output rows: `ns` of them wanted, at most 64 MiB and at most one per row
@@ -404,12 +401,11 @@ ConvWgradPlan slab_plan(size_t rows, size_t ns, size_t wbytes, int jobs) {
 struct Plan {
     bool mfma;
     int Ho, Wo, CoP, taps;
-    int st_ct, st_px, st_slabs;  // stage_kernel: channel lanes, pixels per slab, slabs
-    ConvWgradPlan wg;            // weight gradient, either path
-    size_t gs, part, slab, wB, total;
+    int st_ct, st_px, st_slabs, st_bound;  // stage_kernel: channel lanes, pixels per slab, slabs and their upper bound
+    ConvWgradPlan wg;                      // weight gradient, either path
 };
 
-Plan plan(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, bool need_gx) {
+Plan plan(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
     Plan P;
     P.mfma = cp_conv_backward_mfma(Cin, KH, KW, stride, pad);
     P.Ho = (H + 2 * pad - KH) / stride + 1;
@@ -420,22 +416,25 @@ Plan plan(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, in
     int ct = 1;
     while (ct < P.CoP && ct < 64) ct <<= 1;
     P.st_ct = ct;
-    const size_t ss = std::max<size_t>(1, std::min<size_t>(512, (Q + 63) / 64));
-    P.st_px = (int)((Q + ss - 1) / ss);
+    P.st_bound = (int)std::max<size_t>(1, std::min<size_t>(512, (Q + 63) / 64));
+    P.st_px = (int)((Q + P.st_bound - 1) / P.st_bound);
     P.st_slabs = (int)((Q + P.st_px - 1) / P.st_px);
-    const size_t wbytes = (size_t)P.CoP * P.taps * Cin * 4;
-    P.wg = P.mfma ? cp_conv_wgrad_plan(rows, Cin, P.CoP, P.taps) : slab_plan(rows, 64, wbytes, 0);
-    size_t o = 0;
-    P.gs = o;
-    o += al(Q * P.CoP * 4);
-    P.part = o;
-    o += al(ss * P.CoP * 4);  // (the slab count's upper bound: monotone in B)
-    P.slab = o;
-    o += al(P.wg.slab_bytes);
-    P.wB = o;
-    o += al(!need_gx || !P.mfma ? 0 : stride == 1 ? cp_conv_dgrad_pack_bytes(Cin, P.CoP, P.taps) : wbytes);
-    P.total = o;
+    P.wg = P.mfma ? cp_conv_wgrad_plan(rows, Cin, P.CoP, P.taps) : slab_plan(rows, 64, (size_t)P.CoP * P.taps * Cin * 4, 0);
     return P;
+}
+
+struct Ws {
+    float *gs, *part, *slab, *wB;
+};
+Ws conv_bwd_carve(Carve& c, const Plan& P, int B, int Cin, int stride, bool need_gx) {
+    Ws r;
+    r.gs = c.take<float>((size_t)B * P.Ho * P.Wo * P.CoP * 4);
+    r.part = c.take<float>((size_t)P.st_bound * P.CoP * 4);  // (the slab count's upper bound: monotone in B)
+    r.slab = c.take<float>(P.wg.slab_bytes);
+    r.wB = c.take<float>(!need_gx || !P.mfma ? 0
+                         : stride == 1       ? cp_conv_dgrad_pack_bytes(Cin, P.CoP, P.taps)
+                                             : (size_t)P.CoP * P.taps * Cin * 4);
+    return r;
 }
 
 }  // namespace
@@ -464,11 +463,11 @@ int cp_launch_conv_wgrad(hipStream_t s, const ConvBwdArgs& a, const float* gs, i
         default: CP_WGRAD(1);
     }
 #undef CP_WGRAD
-    if (!ok()) return CP_ERR_LAUNCH;
+    if (!launch_ok()) return CP_ERR_LAUNCH;
     const size_t rg = std::min<size_t>(((size_t)a.Cout * taps * a.Cin + 31) / 32, 8192);
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)rg), dim3(256), 0, s, (const float*)slab, a.gw, slabs, a.Cout, CoP, a.Cin,
                        taps, accum);
-    return ok() ? CP_OK : CP_ERR_LAUNCH;
+    return launch_ok() ? CP_OK : CP_ERR_LAUNCH;
 }
 
 // wB [taps CoP][cpad], cpad = Cin rounded up to the N tile of the convolution that reads it
@@ -479,34 +478,33 @@ size_t cp_conv_dgrad_pack_bytes(int Cin, int CoP, int taps) { return (size_t)tap
 int cp_launch_conv_dgrad_pack(hipStream_t s, const float* w, float* wB, int Cin, int Cout, int CoP, int taps) {
     if (hipMemsetAsync(wB, 0, cp_conv_dgrad_pack_bytes(Cin, CoP, taps), s) != hipSuccess) return CP_ERR_LAUNCH;
     hipLaunchKernelGGL(pack_dgrad_kernel, dim3(256), dim3(256), 0, s, w, wB, Cout, CoP, Cin, taps, dgrad_cpad(Cin));
-    return ok() ? CP_OK : CP_ERR_LAUNCH;
+    return launch_ok() ? CP_OK : CP_ERR_LAUNCH;
 }
 
 int cp_launch_conv_dgrad_s1(hipStream_t s, const ConvBwdArgs& a, const float* gs, int CoP, const float* wB, const float* res) {
     // (stride 1, pad K / 2: the output grid is the input grid, and the operand is a [a.Cin][CoP][KH][KW] weight)
-    ConvParams d = cp_engine::conv_params(a.B, a.H, a.W, &gs, &CoP, 1,
-                                          cp_engine::conv_w_f32((float*)wB, nullptr, nullptr, CoP, a.Cin, a.KH, a.KW), 1, a.pad,
-                                          CP_ACT_NONE);
-    d.dbg = 0;  // cp_set_debug's switches choose among inference kernels for A/B runs: a gradient does not depend on them
+    ConvParams d = grad_conv_params(a.B, a.H, a.W, gs, CoP, (float*)wB, nullptr, a.Cin, a.KH, a.KW, 1, a.pad, a.gx);
     d.res = res;
     d.res_ld = a.Cin;
-    d.out = a.gx;
-    d.store = CP_STORE_NHWC;
-    d.ldo = a.Cin;
     return cp_launch_conv(d, s);
 }
 
+int cp_launch_rowsum_nchw(const float* g, float* out, int B, int C, int HW, hipStream_t s) {
+    hipLaunchKernelGGL(rowsum_kernel, dim3(C), dim3(256), 0, s, g, out, B, C, HW);
+    return launch_ok() ? CP_OK : CP_ERR_LAUNCH;
+}
+
 size_t cp_conv_backward_ws_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int need_grad_x) {
-    return plan(B, H, W, Cin, Cout, KH, KW, stride, pad, need_grad_x != 0).total;
+    Carve c{nullptr};
+    conv_bwd_carve(c, plan(B, H, W, Cin, Cout, KH, KW, stride, pad), B, Cin, stride, need_grad_x != 0);
+    return c.off;
 }
 
 int cp_launch_conv_backward(hipStream_t s, const ConvBwdArgs& a, void* ws) {
-    const Plan P = plan(a.B, a.H, a.W, a.Cin, a.Cout, a.KH, a.KW, a.stride, a.pad, a.gx != nullptr);
-    char* w8 = (char*)ws;
-    float* gsb = (float*)(w8 + P.gs);
-    float* part = (float*)(w8 + P.part);
-    float* slab = (float*)(w8 + P.slab);
-    float* wB = (float*)(w8 + P.wB);
+    const Plan P = plan(a.B, a.H, a.W, a.Cin, a.Cout, a.KH, a.KW, a.stride, a.pad);
+    Carve cv{(char*)ws};
+    const Ws r = conv_bwd_carve(cv, P, a.B, a.Cin, a.stride, a.gx != nullptr);
+    float *gsb = r.gs, *part = r.part, *slab = r.slab, *wB = r.wB;
     const int B = a.B, H = a.H, W = a.W, Cin = a.Cin, Cout = a.Cout, Ho = P.Ho, Wo = P.Wo, CoP = P.CoP, taps = P.taps;
     const int Q = B * Ho * Wo, rows = B * Ho;
     // 0. stage: gate, pad, bias partials
@@ -515,11 +513,11 @@ int cp_launch_conv_backward(hipStream_t s, const ConvBwdArgs& a, void* ws) {
     if (staged || a.gb) {
         hipLaunchKernelGGL(stage_kernel, dim3(P.st_slabs, (CoP + P.st_ct - 1) / P.st_ct), dim3(256), 0, s, a.go, a.y, staged ? gsb : (float*)nullptr,
                            a.gb ? part : (float*)nullptr, Q, Cout, CoP, P.st_ct, P.st_px);
-        if (!ok()) return CP_ERR_LAUNCH;
+        if (!launch_ok()) return CP_ERR_LAUNCH;
         if (a.gb) {
             hipLaunchKernelGGL(bias_reduce_kernel, dim3((Cout + 31) / 32), dim3(256), 0, s, (const float*)part, a.gb,
                                P.st_slabs, Cout, CoP);
-            if (!ok()) return CP_ERR_LAUNCH;
+            if (!launch_ok()) return CP_ERR_LAUNCH;
         }
     }
     // 1. grad_w
@@ -530,9 +528,9 @@ int cp_launch_conv_backward(hipStream_t s, const ConvBwdArgs& a, void* ws) {
         const int n = Cout * Cin * taps;
         hipLaunchKernelGGL(wgrad_generic_kernel, dim3((n + 255) / 256, P.wg.slabs), dim3(256), 0, s, gs, a.x, slab, rows, Ho, Wo, H,
                            W, Cin, Cout, a.KH, a.KW, a.stride, a.pad, P.wg.rows_per_slab);
-        if (!ok()) return CP_ERR_LAUNCH;
+        if (!launch_ok()) return CP_ERR_LAUNCH;
         hipLaunchKernelGGL(slab_reduce_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (const float*)slab, a.gw, P.wg.slabs, n);
-        if (!ok()) return CP_ERR_LAUNCH;
+        if (!launch_ok()) return CP_ERR_LAUNCH;
     }
     // 2. grad_x
     if (!a.gx) return CP_OK;
@@ -540,7 +538,7 @@ int cp_launch_conv_backward(hipStream_t s, const ConvBwdArgs& a, void* ws) {
         const size_t n = (size_t)B * H * W * Cin;
         hipLaunchKernelGGL(dgrad_generic_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 65536)), dim3(256), 0, s, gs, a.w,
                            a.gx, B, H, W, Cin, Cout, Ho, Wo, a.KH, a.KW, a.stride, a.pad);
-        return ok() ? CP_OK : CP_ERR_LAUNCH;
+        return launch_ok() ? CP_OK : CP_ERR_LAUNCH;
     }
     if (a.stride == 1) {
         const int rc = cp_launch_conv_dgrad_pack(s, a.w, wB, Cin, Cout, CoP, taps);
@@ -548,7 +546,7 @@ int cp_launch_conv_backward(hipStream_t s, const ConvBwdArgs& a, void* ws) {
     }
     if (hipMemsetAsync(wB, 0, (size_t)CoP * taps * Cin * 4, s) != hipSuccess) return CP_ERR_LAUNCH;
     hipLaunchKernelGGL(pack_dgrad_s2_kernel, dim3(256), dim3(256), 0, s, a.w, wB, Cout, CoP, Cin, taps);
-    if (!ok()) return CP_ERR_LAUNCH;
+    if (!launch_ok()) return CP_ERR_LAUNCH;
     const int M0 = B * ((H + 1) / 2) * ((W + 1) / 2);  // the even / even class has the most pixels
     const int nt = nh_of(Cin), jobs = ((M0 + 63) / 64) * (Cin / (32 * nt));
     const dim3 dg((jobs + 3) / 4, 4);
@@ -560,5 +558,5 @@ int cp_launch_conv_backward(hipStream_t s, const ConvBwdArgs& a, void* ws) {
         default: CP_DGRAD(1);
     }
 #undef CP_DGRAD
-    return ok() ? CP_OK : CP_ERR_LAUNCH;
+    return launch_ok() ? CP_OK : CP_ERR_LAUNCH;
 }

@@ -468,6 +468,8 @@ int cp_launch_conv_wgrad(hipStream_t s, const ConvBwdArgs& a, const float* gs, i
 size_t cp_conv_dgrad_pack_bytes(int Cin, int CoP, int taps);
 int cp_launch_conv_dgrad_pack(hipStream_t s, const float* w, float* wB, int Cin, int Cout, int CoP, int taps);
 int cp_launch_conv_dgrad_s1(hipStream_t s, const ConvBwdArgs& a, const float* gs, int CoP, const float* wB, const float* res);
+// out[c] = sum over images and pixels of g [B,C,HW] (NCHW): a bias gradient, in a fixed order (dcn_bwd.hip, heads_bwd.hip)
+int cp_launch_rowsum_nchw(const float* g, float* out, int B, int C, int HW, hipStream_t s);
 
 // ---- ConvTranspose2d backward (deconv_bwd.hip): IDAUp's depth-wise `up` (k = 2 stride, pad = stride / 2, groups = C) and the
 // dense k 4 / stride 2 / pad 1 layer, on the forward's NHWC layouts, float32 ----

@@ -18,10 +18,11 @@
 //                   generic path (dcn_bwd_generic_kernel): one lane per sample, corner adds straight to NCHW global.
 //   3. wgrad_kernel  slab[s][co][k] = sum over the pixels of slab s of go_t[q][co] * col[q][k], col = the forward's
 //      modulated im2col computed in the B operand's lane (v_mfma_f32_32x32x2_f32, pixels ascending);
-//      wgrad_reduce_kernel sums the slabs in slab order; bias_kernel sums grad_output per channel in a fixed tree.
+//      wgrad_reduce_kernel sums the slabs in slab order; cp_launch_rowsum_nchw sums grad_output per channel in a fixed tree.
 //   4. fast path: the NHWC input gradient back to NCHW.
 // grad_offset, grad_mask, grad_weight and grad_bias are bitwise reproducible (every sum has a fixed order); grad_input
 // is summed with float atomics, so its last bits depend on arrival order.
+#include "op_common.h"
 #include "igemm_common.h"
 
 #include <algorithm>
@@ -344,43 +345,20 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const BwdP p) {
         }
 }
 
-// grad_weight[co][c][tap] = sum over slabs in slab order
+// grad_weight[co][c][tap] = the slabs' [co][tap][c] by serial_sum
 __global__ void wgrad_reduce_kernel(const float* __restrict__ slab, float* __restrict__ gw, int nslab, int Co, int C, int T) {
     const size_t n = (size_t)Co * C * T, TC = (size_t)C * T;
     for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
         const size_t co = e / TC;
         const int r = (int)(e - co * TC), c = r / T, t = r - c * T;
         const size_t src = co * TC + (size_t)t * C + c;
-        float v = 0.f;
-        for (int s = 0; s < nslab; ++s) v += slab[(size_t)s * n + src];
-        gw[e] = v;
+        gw[e] = serial_sum(slab, nslab, n, src, 0.f);
     }
 }
-
-// grad_bias[co] = sum over images and pixels of grad_output, a fixed per-thread stride and a fixed tree
-__global__ __launch_bounds__(256) void bias_kernel(const float* __restrict__ go, float* __restrict__ gb, int B, int Co, int HWo) {
-    __shared__ float red[256];
-    const int co = blockIdx.x;
-    float v = 0.f;
-    for (int b = 0; b < B; ++b) {
-        const float* pl = go + ((size_t)b * Co + co) * HWo;
-        for (int e = threadIdx.x; e < HWo; e += 256) v += pl[e];
-    }
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) gb[co] = red[0];
-}
-
-inline size_t al(size_t x) { return (x + 255) / 256 * 256; }
 
 struct Plan {
     bool fast;
     int nb, nslab, slab_px;
-    size_t wt, go_t, xh, gin, gcol, slab, total;  // byte offsets / total
 };
 
 Plan plan(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int dg) {
@@ -399,27 +377,24 @@ Plan plan(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, in
     spx = (spx + 1) & ~(size_t)1;
     P.slab_px = (int)spx;
     P.nslab = (int)((Q + spx - 1) / spx);
-    size_t o = 0;
-    P.wt = o;
-    o += al((size_t)Co * TC * 4);
-    P.go_t = o;
-    o += al(Q * Co * 4);
-    P.xh = o;
-    P.gin = o;
-    if (P.fast) {
-        o += al((size_t)B * H * W * C * 4);
-        P.gin = o;
-        o += al((size_t)B * H * W * C * 4);
-    }
-    P.gcol = o;
-    o += al((size_t)P.nb * per_img);
-    P.slab = o;
-    o += al((size_t)P.nslab * Co * TC * 4);
-    P.total = o;
     return P;
 }
 
-inline bool ok() { return hipGetLastError() == hipSuccess; }
+// xh / gin (the NHWC copies of input and grad_input) exist on the fast path only
+struct Ws {
+    float *wt, *go_t, *xh, *gin, *gcol, *slab;
+};
+Ws dcn_bwd_carve(Carve& c, const Plan& P, int B, int C, int H, int W, int Co, int Ho, int Wo, int T) {
+    const size_t TC = (size_t)C * T, HWo = (size_t)Ho * Wo;
+    Ws r;
+    r.wt = c.take<float>((size_t)Co * TC * 4);
+    r.go_t = c.take<float>((size_t)B * HWo * Co * 4);
+    r.xh = P.fast ? c.take<float>((size_t)B * H * W * C * 4) : nullptr;
+    r.gin = P.fast ? c.take<float>((size_t)B * H * W * C * 4) : nullptr;
+    r.gcol = c.take<float>((size_t)P.nb * TC * HWo * 4);
+    r.slab = c.take<float>((size_t)P.nslab * Co * TC * 4);
+    return r;
+}
 
 }  // namespace
 
@@ -429,26 +404,30 @@ bool cp_dcn_backward_fast(int C, int kh, int kw, int sh, int sw, int ph, int pw,
 
 size_t cp_dcn_backward_ws_bytes(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw, int dh,
                                 int dw, int dg) {
-    return plan(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, dg).total;
+    const int Ho = (H + 2 * ph - (dh * (kh - 1) + 1)) / sh + 1, Wo = (W + 2 * pw - (dw * (kw - 1) + 1)) / sw + 1;
+    Carve c{nullptr};
+    dcn_bwd_carve(c, plan(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, dg), B, C, H, W, Co, Ho, Wo, kh * kw);
+    return c.off;
 }
 
 int cp_launch_dcn_backward(hipStream_t s, const DcnBwdArgs& a, void* ws) {
     const Plan P = plan(a.B, a.C, a.H, a.W, a.Co, a.kh, a.kw, a.sh, a.sw, a.ph, a.pw, a.dh, a.dw, a.dg);
-    char* w8 = (char*)ws;
     const int T = a.kh * a.kw, TC = a.C * T;
+    Carve cv{(char*)ws};
+    const Ws r = dcn_bwd_carve(cv, P, a.B, a.C, a.H, a.W, a.Co, a.Ho, a.Wo, T);
     BwdP p;
     p.x = a.input;
-    p.xh = P.fast ? (const float*)(w8 + P.xh) : nullptr;
-    p.wt = (const float*)(w8 + P.wt);
+    p.xh = r.xh;
+    p.wt = r.wt;
     p.off = a.offset;
     p.mask = a.mask;
     p.go = a.grad_output;
-    p.go_t = (const float*)(w8 + P.go_t);
-    p.gcol = (float*)(w8 + P.gcol);
-    p.gin = P.fast ? (float*)(w8 + P.gin) : a.grad_input;
+    p.go_t = r.go_t;
+    p.gcol = r.gcol;
+    p.gin = P.fast ? r.gin : a.grad_input;
     p.goff = a.grad_offset;
     p.gmask = a.grad_mask;
-    p.slab = (float*)(w8 + P.slab);
+    p.slab = r.slab;
     p.B = a.B, p.C = a.C, p.H = a.H, p.W = a.W, p.Co = a.Co, p.Ho = a.Ho, p.Wo = a.Wo;
     p.kh = a.kh, p.kw = a.kw, p.sh = a.sh, p.sw = a.sw, p.ph = a.ph, p.pw = a.pw, p.dh = a.dh, p.dw = a.dw, p.dg = a.dg;
     p.nb = P.nb, p.slab_px = P.slab_px, p.nslab = P.nslab;
@@ -456,7 +435,7 @@ int cp_launch_dcn_backward(hipStream_t s, const DcnBwdArgs& a, void* ws) {
     const size_t in_bytes = (size_t)a.B * a.C * a.H * a.W * 4;
 
     hipLaunchKernelGGL(wt_kernel, dim3(256), dim3(256), 0, s, a.weight, (float*)p.wt, a.Co, a.C, T);
-    if (!ok()) return CP_ERR_LAUNCH;
+    if (!launch_ok()) return CP_ERR_LAUNCH;
     int rc = cp_launch_nchw_to_nhwc(a.grad_output, (float*)p.go_t, a.B, a.Co, a.Ho, a.Wo, a.Co, s);
     if (rc != CP_OK) return rc;
     if (P.fast) {
@@ -469,7 +448,7 @@ int cp_launch_dcn_backward(hipStream_t s, const DcnBwdArgs& a, void* ws) {
         p.b0 = b0;
         p.nb = std::min(P.nb, a.B - b0);
         hipLaunchKernelGGL(gcol_kernel, dim3((HWo + 127) / 128, (TC + 127) / 128, p.nb), dim3(256), 0, s, p);
-        if (!ok()) return CP_ERR_LAUNCH;
+        if (!launch_ok()) return CP_ERR_LAUNCH;
         if (P.fast) {
             const dim3 grid((a.Wo + PT_X - 1) / PT_X, (a.Ho + PT_Y - 1) / PT_Y, p.nb);
             if (a.C % 32 == 0)
@@ -481,7 +460,7 @@ int cp_launch_dcn_backward(hipStream_t s, const DcnBwdArgs& a, void* ws) {
             const size_t blocks = std::min<size_t>((n + 255) / 256, 65536);
             hipLaunchKernelGGL(dcn_bwd_generic_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p);
         }
-        if (!ok()) return CP_ERR_LAUNCH;
+        if (!launch_ok()) return CP_ERR_LAUNCH;
     }
     p.b0 = 0;
     p.nb = P.nb;
@@ -493,12 +472,12 @@ int cp_launch_dcn_backward(hipStream_t s, const DcnBwdArgs& a, void* ws) {
     else
         hipLaunchKernelGGL(wgrad_kernel<WG_COUT>, dim3(wg_grid.x, (a.Co + 32 * WG_COUT - 1) / (32 * WG_COUT), P.nslab),
                            dim3(256), 0, s, p);
-    if (!ok()) return CP_ERR_LAUNCH;
+    if (!launch_ok()) return CP_ERR_LAUNCH;
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(1024), dim3(256), 0, s, (const float*)p.slab, a.grad_weight, P.nslab, a.Co,
                        a.C, T);
-    if (!ok()) return CP_ERR_LAUNCH;
-    hipLaunchKernelGGL(bias_kernel, dim3(a.Co), dim3(256), 0, s, a.grad_output, a.grad_bias, a.B, a.Co, HWo);
-    if (!ok()) return CP_ERR_LAUNCH;
+    if (!launch_ok()) return CP_ERR_LAUNCH;
+    rc = cp_launch_rowsum_nchw(a.grad_output, a.grad_bias, a.B, a.Co, HWo, s);
+    if (rc != CP_OK) return rc;
     if (P.fast) return cp_launch_nhwc_to_nchw(p.gin, a.grad_input, a.B, a.C, a.H, a.W, a.C, s);
     return CP_OK;
 }

@@ -7,7 +7,7 @@
 //               [out,in,4,4], so its data gradient IS that convolution of grad_out (the exact-f32 implicit GEMM of igemm.hip) and
 //               its weight gradient is that convolution's weight gradient with the roles of input and output gradient swapped
 //               (cp_launch_conv_wgrad: `x` = grad_out, `gs` = x; wgrad_reduce_kernel then writes [Cin][Cout][4][4]).
-#include "engine_model.h"
+#include "op_common.h"
 
 #include <algorithm>
 
@@ -29,7 +29,7 @@ namespace {
 //           in group order.  Not computed and not stored when gx is NULL.
 //   grad_w: sixteen float4 accumulators per thread over the pixels of its pixel lane, ascending; at the end the pixel lanes
 //           are added in lane order through LDS and the workgroup writes part[slab][tap][C].  dw_wgrad_reduce_kernel adds the
-//           slabs in bias_reduce_kernel's two-level order.
+//           slabs by two_level_sum.
 // LDS: [256 float4 exchange][k k C weights as [tap][channel], one ds_read_b128 per lane and tap].
 template <int G>
 __global__ __launch_bounds__(256) void dw_bwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
@@ -135,28 +135,17 @@ __global__ __launch_bounds__(256) void dw_bwd_kernel(const float* __restrict__ x
     }
 }
 
-// gw[c][tap] = the slabs' part[s][tap][c], summed in bias_reduce_kernel's two-level order: a workgroup is 32 elements x 8 slab
-// lanes; lane l adds the slabs l, l + 8, ... ascending, then the eight lanes are added in lane order
+// gw[c][tap] = the slabs' part[s][tap][c] (two_level_sum)
 __global__ __launch_bounds__(256) void dw_wgrad_reduce_kernel(const float* __restrict__ part, float* __restrict__ gw, int nslab, int C,
                                                               int kk) {
     __shared__ float red[256];
-    const int n = kk * C;
-    const int el = threadIdx.x & 31, sl = threadIdx.x >> 5, e = blockIdx.x * 32 + el;
-    float v = 0.f;
-    if (e < n)
-        for (int s = sl; s < nslab; s += 8) v += part[(size_t)s * n + e];
-    red[threadIdx.x] = v;
-    __syncthreads();
-    if (sl == 0 && e < n) {
-        float t = red[el];
-        for (int j = 1; j < 8; ++j) t += red[j * 32 + el];
+    const int n = kk * C, e = blockIdx.x * 32 + (threadIdx.x & 31);
+    const float t = two_level_sum(red, e < n, nslab, 0.f, [&](float v, int s) { return v + part[(size_t)s * n + e]; });
+    if (threadIdx.x < 32 && e < n) {
         const int tap = e / C, c = e - tap * C;
         gw[(size_t)c * kk + tap] = t;
     }
 }
-
-inline size_t al(size_t x) { return (x + 255) / 256 * 256; }
-inline bool ok() { return hipGetLastError() == hipSuccess; }
 
 // Depth-wise slabs: whole pixel-lane rounds, about eight rounds per workgroup, at most 1024 slabs (monotone in B)
 struct DwPlan {
@@ -179,22 +168,26 @@ DwPlan dw_plan(int B, int H, int W, int C, int f) {
     return P;
 }
 
+float* dw_carve(Carve& c, const DwPlan& P) { return c.take<float>(P.part_bytes); }
+
 struct DensePlan {
     ConvWgradPlan wg;
     int cpad;  // the data gradient's N tile padding of Cin
-    size_t slab, wp, total;
 };
-DensePlan dense_plan(int B, int H, int W, int Cin, int Cout, bool need_gx) {
+DensePlan dense_plan(int B, int H, int Cin, int Cout) {
     DensePlan P;
     P.wg = cp_conv_wgrad_plan((size_t)B * H, Cout, Cin, 16);
     P.cpad = (int)cp_engine::align_up((size_t)Cin, cp_conv_tile_n(Cin));
-    size_t o = 0;
-    P.slab = o;
-    o += al(P.wg.slab_bytes);
-    P.wp = o;
-    o += al(need_gx ? (size_t)16 * Cout * P.cpad * 4 : 0);
-    P.total = o;
     return P;
+}
+struct DenseWs {
+    float *slab, *wp;
+};
+DenseWs dense_carve(Carve& c, const DensePlan& P, int Cout, bool need_gx) {
+    DenseWs r;
+    r.slab = c.take<float>(P.wg.slab_bytes);
+    r.wp = c.take<float>(need_gx ? (size_t)16 * Cout * P.cpad * 4 : 0);
+    return r;
 }
 
 }  // namespace
@@ -209,42 +202,41 @@ bool cp_deconv_dense_geometry(int Cin, int Cout, int K, int stride, int pad, int
 }
 
 size_t cp_deconv_backward_ws_bytes(int B, int H, int W, int Cin, int Cout, int stride, int groups, int need_grad_x) {
-    if (groups != 1) return al(dw_plan(B, H, W, Cin, stride).part_bytes);
-    return dense_plan(B, H, W, Cin, Cout, need_grad_x != 0).total;
+    Carve c{nullptr};
+    if (groups != 1)
+        dw_carve(c, dw_plan(B, H, W, Cin, stride));
+    else
+        dense_carve(c, dense_plan(B, H, Cin, Cout), Cout, need_grad_x != 0);
+    return c.off;
 }
 
 int cp_launch_deconv_backward(hipStream_t s, const DeconvBwdArgs& a, void* ws) {
+    Carve cv{(char*)ws};
     if (a.groups != 1) {
         const DwPlan P = dw_plan(a.B, a.H, a.W, a.Cin, a.stride);
-        float* part = (float*)ws;
+        float* part = dw_carve(cv, P);
         if (P.G == 1)
             hipLaunchKernelGGL(dw_bwd_kernel<1>, dim3(P.slabs), dim3(256), P.lds, s, a.x, a.w, a.go, a.gx, part, a.B, a.H, a.W, a.Cin,
                                a.stride, P.px_per_slab);
         else
             hipLaunchKernelGGL(dw_bwd_kernel<4>, dim3(P.slabs), dim3(256), P.lds, s, a.x, a.w, a.go, a.gx, part, a.B, a.H, a.W, a.Cin,
                                a.stride, P.px_per_slab);
-        if (!ok()) return CP_ERR_LAUNCH;
+        if (!launch_ok()) return CP_ERR_LAUNCH;
         const int kk = 4 * a.stride * a.stride;
         hipLaunchKernelGGL(dw_wgrad_reduce_kernel, dim3((kk * a.Cin + 31) / 32), dim3(256), 0, s, (const float*)part, a.gw, P.slabs,
                            a.Cin, kk);
-        return ok() ? CP_OK : CP_ERR_LAUNCH;
+        return launch_ok() ? CP_OK : CP_ERR_LAUNCH;
     }
-    const DensePlan P = dense_plan(a.B, a.H, a.W, a.Cin, a.Cout, a.gx != nullptr);
-    char* w8 = (char*)ws;
+    const DensePlan P = dense_plan(a.B, a.H, a.Cin, a.Cout);
+    const DenseWs r = dense_carve(cv, P, a.Cout, a.gx != nullptr);
     // grad_w: the stride-2 convolution's weight gradient with grad_out as its input and x as its output gradient
     const ConvBwdArgs c{a.go, nullptr, nullptr, nullptr, nullptr, a.gw, nullptr, a.B, 2 * a.H, 2 * a.W, a.Cout, a.Cin, 4, 4, 2, 1};
-    int rc = cp_launch_conv_wgrad(s, c, a.x, a.Cin, P.wg, (float*)(w8 + P.slab), 0);
+    int rc = cp_launch_conv_wgrad(s, c, a.x, a.Cin, P.wg, r.slab, 0);
     if (rc != CP_OK || !a.gx) return rc;
     // grad_x = conv2d(grad_out, w as [out = Cin][in = Cout][4][4], stride 2, pad 1), exact float32
-    float* wp = (float*)(w8 + P.wp);
-    if (hipMemsetAsync(wp, 0, (size_t)16 * a.Cout * P.cpad * 4, s) != hipSuccess) return CP_ERR_LAUNCH;
-    rc = cp_launch_pack_weight(a.w, wp, a.Cin, a.Cout, 16, a.Cout, P.cpad, 0, s);
+    if (hipMemsetAsync(r.wp, 0, (size_t)16 * a.Cout * P.cpad * 4, s) != hipSuccess) return CP_ERR_LAUNCH;
+    rc = cp_launch_pack_weight(a.w, r.wp, a.Cin, a.Cout, 16, a.Cout, P.cpad, 0, s);
     if (rc != CP_OK) return rc;
-    ConvParams d = cp_engine::conv_params(a.B, 2 * a.H, 2 * a.W, &a.go, &a.Cout, 1,
-                                          cp_engine::conv_w_f32(wp, nullptr, nullptr, a.Cout, a.Cin, 4, 4), 2, 1, CP_ACT_NONE);
-    d.dbg = 0;  // cp_set_debug's switches choose among inference kernels for A/B runs: a gradient does not depend on them
-    d.out = a.gx;
-    d.store = CP_STORE_NHWC;
-    d.ldo = a.Cin;
+    const ConvParams d = grad_conv_params(a.B, 2 * a.H, 2 * a.W, a.go, a.Cout, r.wp, nullptr, a.Cin, 4, 4, 2, 1, a.gx);
     return cp_launch_conv(d, s);
 }

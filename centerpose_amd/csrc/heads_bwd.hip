@@ -16,12 +16,12 @@
 //               once per head, cp_launch_conv_dgrad_s1 per chunk: the implicit GEMM of step 1 with K = 9 hid); the first head
 //               writes the chunk, later heads add to it through the kernel's residual input (same stream: no atomics, no halo
 //               exchange).  Skipped entirely when the caller passes no grad_feat.
-//   grad_b1 = per-channel sums of grad_out in a fixed tree (rowsum_kernel), once per head.
+//   grad_b1 = per-channel sums of grad_out in a fixed tree (cp_launch_rowsum_nchw), once per head.
 // Every sum has a fixed order, so all outputs are bitwise reproducible run to run.  The hidden chunk makes one round trip
 // through memory per step (write in 1, read + write in 2, read in 3 and 4): 16 MiB per image and head at 128 x 128 x 256
 // against 14.5 GFLOP of contractions, i.e. a few percent of the matrix time; it is the price of building steps 1 and 4
 // from the library's tuned convolution instead of a hand-fused tile pipeline.
-#include "engine_model.h"
+#include "op_common.h"
 
 #include <algorithm>
 
@@ -102,48 +102,25 @@ __global__ __launch_bounds__(256) void thin_kernel(float* __restrict__ hb, const
     for (int c = wv; c <= cls; c += 4) out[(size_t)c * hid + h] = red[(c < cls ? c : CMAX) * 64 + lane];
 }
 
-// gw1[c][h] and gb0[h] = (accum ? previous : 0) + the slabs' partials in slab order
+// gw1[c][h] and gb0[h] = the slabs' partials by serial_sum.  `accum`: the sum STARTS from the value already there (a later chunk
+// of the batch continues the earlier chunks' chain), otherwise from zero.
 __global__ void thin_reduce_kernel(const float* __restrict__ part, float* __restrict__ gw1, float* __restrict__ gb0, int nslab,
                                    int cls, int hid, int accum) {
     const int n = (cls + 1) * hid;
     for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < n; e += gridDim.x * blockDim.x) {
         float* dst = e < cls * hid ? gw1 + e : gb0 + (e - cls * hid);
-        float v = accum ? *dst : 0.f;
-        for (int s = 0; s < nslab; ++s) v += part[(size_t)s * n + e];
-        *dst = v;
+        *dst = serial_sum(part, nslab, (size_t)n, (size_t)e, accum ? *dst : 0.f);
     }
 }
-
-// gb[c] = sum over images and pixels of g [B][C][HW]: a fixed per-thread stride and a fixed tree
-__global__ __launch_bounds__(256) void rowsum_kernel(const float* __restrict__ g, float* __restrict__ gb, int B, int C, int HW) {
-    __shared__ float red[256];
-    const int c = blockIdx.x;
-    float v = 0.f;
-    for (int b = 0; b < B; ++b) {
-        const float* pl = g + ((size_t)b * C + c) * HW;
-        for (int e = threadIdx.x; e < HW; e += 256) v += pl[e];
-    }
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) gb[c] = red[0];
-}
-
-inline size_t al(size_t x) { return (x + 255) / 256 * 256; }
-inline bool ok() { return hipGetLastError() == hipSuccess; }
 
 struct Plan {
     int nb;                   // images per chunk
     int hpad;                 // hid padded to the hidden convolution's N tile
     int thin_px, thin_slabs;  // thin_kernel: pixels per slab, slabs of a full chunk
     ConvWgradPlan wg;         // the weight gradient of a full chunk
-    size_t wA, shift, wB, hb, go_t, part, slab, total;  // byte offsets / total
 };
 
-Plan plan(int B, int H, int W, int Cin, int hid, int cmax) {
+Plan plan(int B, int H, int W, int Cin, int hid) {
     Plan P;
     const size_t HW = (size_t)H * W;
     P.nb = cp_pose_heads_chunk(B, H, W, hid);
@@ -154,23 +131,24 @@ Plan plan(int B, int H, int W, int Cin, int hid, int cmax) {
     P.thin_px = (int)((Q + ts - 1) / ts);
     P.thin_slabs = (int)((Q + P.thin_px - 1) / P.thin_px);
     P.wg = cp_conv_wgrad_plan((size_t)P.nb * H, Cin, hid, 9);
-    size_t o = 0;
-    P.wA = o;
-    o += al((size_t)9 * Cin * P.hpad * 4);
-    P.shift = o;
-    o += al((size_t)P.hpad * 4);
-    P.wB = o;
-    o += al(cp_conv_dgrad_pack_bytes(Cin, hid, 9));
-    P.hb = o;
-    o += al(Q * hid * 4);
-    P.go_t = o;
-    o += al(Q * cmax * 4);
-    P.part = o;
-    o += al((size_t)P.thin_slabs * (cmax + 1) * hid * 4);
-    P.slab = o;
-    o += al(P.wg.slab_bytes);
-    P.total = o;
     return P;
+}
+
+// wA [9 Cin][hpad] and shift [hpad] are adjacent: one memset clears both
+struct Ws {
+    float *wA, *shift, *wB, *hb, *go_t, *part, *slab;
+};
+Ws heads_bwd_carve(Carve& c, const Plan& P, int H, int W, int Cin, int hid, int cmax) {
+    const size_t Q = (size_t)P.nb * H * W;
+    Ws r;
+    r.wA = c.take<float>((size_t)9 * Cin * P.hpad * 4);
+    r.shift = c.take<float>((size_t)P.hpad * 4);
+    r.wB = c.take<float>(cp_conv_dgrad_pack_bytes(Cin, hid, 9));
+    r.hb = c.take<float>(Q * hid * 4);
+    r.go_t = c.take<float>(Q * cmax * 4);
+    r.part = c.take<float>((size_t)P.thin_slabs * (cmax + 1) * hid * 4);
+    r.slab = c.take<float>(P.wg.slab_bytes);
+    return r;
 }
 
 }  // namespace
@@ -182,7 +160,9 @@ int cp_pose_heads_chunk(int B, int H, int W, int hid) {
 }
 
 size_t cp_pose_heads_backward_ws_bytes(int B, int H, int W, int Cin, int hid, int max_classes) {
-    return plan(B, H, W, Cin, hid, max_classes).total;
+    Carve c{nullptr};
+    heads_bwd_carve(c, plan(B, H, W, Cin, hid), H, W, Cin, hid, max_classes);
+    return c.off;
 }
 
 int cp_launch_pose_heads_backward(hipStream_t s, const PoseHeadsArgs& a, const float* const* grad_out, float* const* grad_w0,
@@ -190,15 +170,10 @@ int cp_launch_pose_heads_backward(hipStream_t s, const PoseHeadsArgs& a, const f
                                   void* ws) {
     int cmax = 1;
     for (int i = 0; i < a.n; ++i) cmax = std::max(cmax, a.classes[i]);
-    const Plan P = plan(a.B, a.H, a.W, a.Cin, a.hid, cmax);
-    char* w8 = (char*)ws;
-    float* wA = (float*)(w8 + P.wA);
-    float* shift = (float*)(w8 + P.shift);
-    float* wB = (float*)(w8 + P.wB);
-    float* hb = (float*)(w8 + P.hb);
-    float* go_t = (float*)(w8 + P.go_t);
-    float* part = (float*)(w8 + P.part);
-    float* slab = (float*)(w8 + P.slab);
+    const Plan P = plan(a.B, a.H, a.W, a.Cin, a.hid);
+    Carve cv{(char*)ws};
+    const Ws r = heads_bwd_carve(cv, P, a.H, a.W, a.Cin, a.hid, cmax);
+    float *wA = r.wA, *shift = r.shift, *wB = r.wB, *hb = r.hb, *go_t = r.go_t, *part = r.part, *slab = r.slab;
     const int B = a.B, H = a.H, W = a.W, Cin = a.Cin, hid = a.hid, HW = H * W;
     bool feat_written = false;
     for (int i = 0; i < a.n; ++i) {
@@ -212,7 +187,7 @@ int cp_launch_pose_heads_backward(hipStream_t s, const PoseHeadsArgs& a, const f
             continue;
         }
         // the head's packed operands: wA [9 Cin][hpad] and b0 padded for the hidden layer, wB for the data gradient
-        if (hipMemsetAsync(wA, 0, P.wB - P.wA, s) != hipSuccess) return CP_ERR_LAUNCH;
+        if (hipMemsetAsync(wA, 0, (char*)wB - (char*)wA, s) != hipSuccess) return CP_ERR_LAUNCH;
         int rc = cp_launch_pack_weight(a.w0[i], wA, hid, Cin, 9, Cin, P.hpad, 0, s);
         if (rc != CP_OK) return rc;
         if (hipMemcpyAsync(shift, a.b0[i], (size_t)hid * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return CP_ERR_LAUNCH;
@@ -220,19 +195,14 @@ int cp_launch_pose_heads_backward(hipStream_t s, const PoseHeadsArgs& a, const f
             rc = cp_launch_conv_dgrad_pack(s, a.w0[i], wB, Cin, hid, hid, 9);
             if (rc != CP_OK) return rc;
         }
-        hipLaunchKernelGGL(rowsum_kernel, dim3(cls), dim3(256), 0, s, grad_out[i], grad_b1[i], B, cls, HW);
-        if (!ok()) return CP_ERR_LAUNCH;
+        rc = cp_launch_rowsum_nchw(grad_out[i], grad_b1[i], B, cls, HW, s);
+        if (rc != CP_OK) return rc;
         for (int b0 = 0; b0 < B; b0 += P.nb) {
             const int nb = std::min(P.nb, B - b0), Q = nb * HW, accum = b0 > 0;
             const float* fc = a.feat + (size_t)b0 * HW * Cin;
             float* gf = grad_feat ? grad_feat + (size_t)b0 * HW * Cin : nullptr;
             // 1. hidden (pre-activation)
-            ConvParams p = cp_engine::conv_params(nb, H, W, &fc, &Cin, 1, cp_engine::conv_w_f32(wA, nullptr, shift, Cin, hid, 3, 3),
-                                                  1, 1, CP_ACT_NONE);
-            p.dbg = 0;  // cp_set_debug's switches choose among inference kernels for A/B runs: a gradient does not depend on them
-            p.out = hb;
-            p.store = CP_STORE_NHWC;
-            p.ldo = hid;
+            const ConvParams p = grad_conv_params(nb, H, W, fc, Cin, wA, shift, hid, 3, 3, 1, 1, hb);
             rc = cp_launch_conv(p, s);
             if (rc != CP_OK) return rc;
             // 2. thin
@@ -246,10 +216,10 @@ int cp_launch_pose_heads_backward(hipStream_t s, const PoseHeadsArgs& a, const f
                 hipLaunchKernelGGL(thin_kernel<16>, tg, dim3(256), 0, s, hb, (const float*)go_t, a.w1[i], part, Q, hid, cls, P.thin_px);
             else
                 hipLaunchKernelGGL(thin_kernel<64>, tg, dim3(256), 0, s, hb, (const float*)go_t, a.w1[i], part, Q, hid, cls, P.thin_px);
-            if (!ok()) return CP_ERR_LAUNCH;
+            if (!launch_ok()) return CP_ERR_LAUNCH;
             hipLaunchKernelGGL(thin_reduce_kernel, dim3(((cls + 1) * hid + 255) / 256), dim3(256), 0, s, (const float*)part,
                                grad_w1[i], grad_b0[i], tslabs, cls, hid, accum);
-            if (!ok()) return CP_ERR_LAUNCH;
+            if (!launch_ok()) return CP_ERR_LAUNCH;
             // 3. grad_w0 and 4. grad_feat of the chunk: the 3x3 layer's Conv2d backward on gs = grad_hidden (hid % 32 == 0: nothing
             // to stage).  grad_feat is written by the first head with a gradient and added to by the others.
             const ConvBwdArgs c{fc, a.w0[i], nullptr, nullptr, gf, grad_w0[i], nullptr, nb, H, W, Cin, hid, 3, 3, 1, 1};

@@ -1,0 +1,64 @@
+// What the stand-alone operators share (ops.hip and the training operators dcn_bwd.hip, heads_bwd.hip, conv_bwd.hip,
+// deconv_bwd.hip, batchnorm.hip): the workspace carver, the launch check, the two fixed-order slab sums and the ConvParams of a
+// convolution that runs as part of a gradient.  The summation orders are contract (the tests compare bitwise), so they are
+// written here once.
+#pragma once
+#include "engine_model.h"
+
+// Bump carver over an operator's workspace.  Each operator describes its regions once, in a *_carve function: run on the
+// caller's pointer it hands out the regions, run on nullptr it only counts, and *_workspace_bytes is `off` of that run -- the
+// size and the carve-up cannot drift apart.
+struct Carve {
+    char* base;
+    size_t off = 0;
+    template <class T>
+    T* take(size_t bytes) {
+        T* p = base ? (T*)(base + off) : nullptr;
+        off += cp_engine::align_up(bytes, 256);
+        return p;
+    }
+};
+
+inline bool launch_ok() { return hipGetLastError() == hipSuccess; }
+
+// The two-level slab sum: a workgroup of 256 threads is 32 elements x 8 slab lanes (element threadIdx.x & 31, lane sl =
+// threadIdx.x >> 5).  A lane folds acc = step(acc, s) over its slabs s = sl, sl + 8, ... in ascending order, starting from
+// `init` (a serial walk over hundreds of slabs is one long chain of dependent adds behind strided loads); after one barrier the
+// result is lane 0's value plus the lanes 1..7 in lane order.  Every thread of the workgroup must call it; every thread gets
+// the result (the callers store it from the sl == 0 thread).  `valid`: the element exists; where not, no slab is read.  The
+// caller puts a barrier before the next use of `red`.  T is float, or a small struct with operator+ that carries several
+// sums through one walk over the slabs (batchnorm.hip's Sum2: one workgroup may own all of up to 2048 slabs, so a second
+// walk would double that kernel's time).
+template <class T, class F>
+__device__ __forceinline__ T two_level_sum(T (&red)[256], bool valid, int nslab, T init, F step) {
+    const int el = threadIdx.x & 31, sl = threadIdx.x >> 5;
+    T acc = init;
+    if (valid)
+        for (int s = sl; s < nslab; s += 8) acc = step(acc, s);
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    T t = red[el];
+    for (int j = 1; j < 8; ++j) t = t + red[j * 32 + el];
+    return t;
+}
+
+// The serial slab sum: init + part[0][e] + part[1][e] + ..., slabs ascending, `stride` elements apart
+__device__ __forceinline__ float serial_sum(const float* __restrict__ part, int nslab, size_t stride, size_t e, float init) {
+    float v = init;
+    for (int s = 0; s < nslab; ++s) v += part[(size_t)s * stride + e];
+    return v;
+}
+
+// ConvParams of an exact-f32 convolution that runs as part of a gradient: src [B,H,W,Cin] NHWC with the float32 weight wp as
+// cp_launch_pack_weight lays it out (conv_w_f32), out [B,Ho,Wo,Cout] NHWC.  dbg = 0: cp_set_debug's switches choose among
+// inference kernels for A/B runs, and a gradient does not depend on them.
+inline ConvParams grad_conv_params(int B, int H, int W, const float* src, int Cin, float* wp, const float* shift, int Cout, int KH,
+                                   int KW, int stride, int pad, float* out) {
+    ConvParams p = cp_engine::conv_params(B, H, W, &src, &Cin, 1, cp_engine::conv_w_f32(wp, nullptr, shift, Cin, Cout, KH, KW), stride,
+                                          pad, CP_ACT_NONE);
+    p.dbg = 0;
+    p.out = out;
+    p.store = CP_STORE_NHWC;
+    p.ldo = Cout;
+    return p;
+}

@@ -3,25 +3,11 @@
 // cp_conv_transpose2d_dw_nhwc / cp_conv_transpose2d_backward_nhwc, cp_dcnv2_forward / cp_dcnv2_backward, cp_pose_heads_forward / _backward.
 // Each packs its PyTorch-layout weights into a caller-provided workspace on every call and then launches the same kernels as
 // the engine.
-#include "engine_model.h"
+#include "op_common.h"
 
 using namespace cp_engine;
 
 namespace {
-
-// Bump carver over an operator's workspace.  Each operator describes its regions once, in a *_carve function: run on the
-// caller's pointer it hands out the regions, run on nullptr it only counts, and *_workspace_bytes is `off` of that run -- the
-// size and the carve-up cannot drift apart.
-struct Carve {
-    char* base;
-    size_t off = 0;
-    template <class T>
-    T* take(size_t bytes) {
-        T* p = base ? (T*)(base + off) : nullptr;
-        off += align_up(bytes, 256);
-        return p;
-    }
-};
 
 constexpr size_t kSlotBytes = (size_t)CP_AMAX_SUB * CP_AMAX_STRIDE * sizeof(unsigned);  // one |max| slot block
 

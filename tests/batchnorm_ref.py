@@ -17,9 +17,10 @@ import torch.nn.functional as F
 Case = collections.namedtuple("Case", "B H W C")
 # (1,1,2,4): n = 2, minimum C; (2,5,7,16), (3,9,11,64): small ragged grids; (2,3,5,20): five lanes per row, does not divide a
 # wave; (2,13,13,136): 34 lanes per row; (1,7,9,512): two channel passes; (3,37,45,32): ragged, several slabs; (2,128,128,16):
-# many slabs, DLA level 0's width
+# many slabs, DLA level 0's width; (1,14,14,256), (1,16,16,256), (1,16,18,256): 7, 8, 9 reduction slabs, around the eight
+# lanes of the two-level slab sum (a lane without a slab, one each, one lane with two)
 CASES = [Case(1, 1, 2, 4), Case(2, 5, 7, 16), Case(3, 9, 11, 64), Case(2, 3, 5, 20), Case(2, 13, 13, 136), Case(1, 7, 9, 512),
-         Case(3, 37, 45, 32), Case(2, 128, 128, 16)]
+         Case(3, 37, 45, 32), Case(2, 128, 128, 16), Case(1, 14, 14, 256), Case(1, 16, 16, 256), Case(1, 16, 18, 256)]
 LARGE_MEAN_CASES = [Case(2, 8, 8, 32), Case(4, 33, 31, 128)]
 EPS, MOMENTUM = 1e-5, 0.1
 TOL = 1e-4   # x max |reference| per output: the project's gradient tolerance

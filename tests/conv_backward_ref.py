@@ -23,7 +23,13 @@ def _c(B, Cin, Cout, H, W, k, stride, pad=None):
 
 MFMA_CASES = [_c(2, 64, 64, 128, 128, 3, 1), _c(2, 32, 64, 37, 45, 3, 2), _c(2, 64, 128, 64, 64, 3, 2), _c(1, 256, 512, 32, 32, 3, 2),
               _c(2, 512, 512, 16, 16, 3, 1), _c(2, 128, 64, 33, 20, 1, 1), _c(1, 448, 128, 64, 64, 1, 1), _c(1, 64, 128, 31, 31, 1, 2),
-              _c(3, 32, 32, 1, 1, 3, 1), _c(1, 32, 32, 2, 3, 3, 2)]
+              _c(3, 32, 32, 1, 1, 3, 1), _c(1, 32, 32, 2, 3, 3, 2),
+              # slab counts around the eight lanes of the two-level slab sum (a lane without a slab, one each, one lane with
+              # two); Cout 40 also has pad lanes and an element tail in the 32-wide groups.
+              # 1x1: weight-gradient slabs = output rows = 7, 8, 9
+              _c(1, 32, 40, 7, 7, 1, 1), _c(1, 32, 40, 8, 8, 1, 1), _c(1, 32, 40, 9, 9, 1, 1),
+              # 3x3: stage / bias slabs 7, 8, 9 (Q = 441, 506, 552 output pixels)
+              _c(1, 32, 40, 21, 21, 3, 1), _c(1, 32, 40, 22, 23, 3, 1), _c(1, 32, 40, 23, 24, 3, 1)]
 PADDED_CASES = [_c(2, 64, 27, 40, 40, 3, 1), _c(1, 128, 27, 64, 64, 3, 1)]
 GENERIC_CASES = [_c(2, 16, 32, 50, 50, 3, 2), _c(1, 4, 16, 64, 64, 7, 1), _c(1, 36, 20, 17, 23, 3, 1), _c(1, 8, 8, 29, 31, 5, 3, 2),
                  _c(1, 64, 64, 20, 20, 3, 1, 0)]

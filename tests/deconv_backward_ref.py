@@ -28,7 +28,11 @@ DW_CASES = [dw(1, 1, 1, 4, 2),      # one source pixel, every tap at an edge
             dw(2, 5, 7, 64, 4),     # the f = 4 layer's width
             dw(1, 7, 9, 256, 2),    # the widest weight table
             dw(2, 33, 31, 64, 2),   # several slabs, ragged
-            dw(1, 64, 64, 64, 2)]   # the workload's row length
+            dw(1, 64, 64, 64, 2),   # the workload's row length
+            # slab counts around the eight lanes of the two-level slab sum: 7, 8, 9 slabs
+            dw(1, 28, 28, 64, 2), dw(1, 32, 32, 64, 2), dw(1, 33, 33, 64, 2),
+            # the same 7, 8, 9 slabs on the four-tap-group instance
+            dw(1, 28, 28, 16, 4), dw(1, 32, 32, 16, 4), dw(1, 33, 33, 16, 4)]
 DENSE_CASES = [dense(1, 1, 1, 32, 32),       # minimum shape
                dense(2, 3, 5, 32, 64),       # unequal channel counts
                dense(2, 7, 9, 64, 32),       # the other way round
