@@ -503,6 +503,22 @@ size_t cp_batchnorm_ws_bytes(int B, int H, int W, int C);
 int cp_launch_batchnorm_forward(hipStream_t s, const BnFwdArgs& a, void* ws);
 int cp_launch_batchnorm_backward(hipStream_t s, const BnBwdArgs& a, void* ws);
 
+// ---- MaxPool2d for training (pool.hip): (kernel, stride, pad) = (2, 2, 0), flooring, or (3, 2, 1), padding as -inf; float32
+// NHWC, C % 4 == 0, a non-empty output.  The winner of a window is torch's (first maximum in row-major order) in both calls ----
+bool cp_maxpool_geometry(int kernel, int stride, int pad);
+int cp_launch_maxpool_forward(hipStream_t s, const float* x, float* out, int B, int H, int W, int C, int kernel);
+int cp_launch_maxpool_backward(hipStream_t s, const float* x, const float* go, float* gx, int B, int H, int W, int C, int kernel);
+
+// ---- Weight / bias gradient of the 7x7, padding-3 image stems (stem_bwd.hip): x NCHW with Cin in 1..3 planes, grad_out NHWC ----
+struct StemBwdArgs {
+    const float *x, *go, *y;  // y (the activated forward output) or nullptr: grad_out is gated by y > 0
+    float *gw, *gb;           // gb nullptr: not stored
+    int B, H, W, Cin, Cout, stride;
+};
+const char* cp_stem_backward_shape_error(int B, int H, int W, int Cin, int Cout, int stride);  // nullptr: accepted
+size_t cp_stem_backward_ws_bytes(int B, int H, int W, int Cin, int Cout, int stride);
+int cp_launch_stem_backward(hipStream_t s, const StemBwdArgs& a, void* ws);
+
 // ---- ObjectPoseLoss (pose_loss.hip; numerics in pose_loss_common.h) ----
 struct cp_pose_loss_desc;
 const char* cp_pose_loss_check(const cp_pose_loss_desc* d);                           // nullptr: accepted

@@ -1,6 +1,7 @@
 // The stand-alone operators of the C ABI (include/centerpose_hip.h): single layers on caller tensors, outside any cp_model
 // -- cp_conv2d_nhwc / cp_conv2d_backward_nhwc, cp_batchnorm_forward_nhwc / _backward_nhwc, cp_conv_transpose2d_nhwc,
-// cp_conv_transpose2d_dw_nhwc / cp_conv_transpose2d_backward_nhwc, cp_dcnv2_forward / cp_dcnv2_backward, cp_pose_heads_forward / _backward.
+// cp_conv_transpose2d_dw_nhwc / cp_conv_transpose2d_backward_nhwc, cp_dcnv2_forward / cp_dcnv2_backward, cp_pose_heads_forward / _backward,
+// cp_maxpool2d_forward_nhwc / _backward_nhwc, cp_conv2d_stem_backward.
 // Each packs its PyTorch-layout weights into a caller-provided workspace on every call and then launches the same kernels as
 // the engine.
 #include "op_common.h"
@@ -533,6 +534,56 @@ int cp_batchnorm_backward_nhwc(cp_stream_t stream, const float* x, const float* 
                       grad_gamma_or_null, grad_beta_or_null, B, H, W, C, training != 0};
     const int rc = cp_launch_batchnorm_backward((hipStream_t)stream, a, workspace);
     return rc == CP_OK ? CP_OK : fail(rc, "batchnorm_backward: kernel launch failed");
+}
+
+// MaxPool2d, forward and backward (pool.hip)
+static const char* maxpool_shape_error(int B, int H, int W, int C, int kernel, int stride, int pad) {
+    if (!cp_maxpool_geometry(kernel, stride, pad))
+        return "maxpool2d: unsupported geometry ((kernel, stride, padding) must be (2, 2, 0) or (3, 2, 1))";
+    if (B < 1 || H < 1 || W < 1) return "maxpool2d: B, H and W must be at least 1";
+    if (C < 4 || C % 4) return "maxpool2d: C must be a positive multiple of 4";
+    if (H + 2 * pad < kernel || W + 2 * pad < kernel) return "maxpool2d: empty output (the window is larger than the padded input)";
+    if ((long long)B * H * W * C >= 0x7fffffffLL) return "maxpool2d: a tensor has 2^31 elements or more";
+    return nullptr;
+}
+
+int cp_maxpool2d_forward_nhwc(cp_stream_t stream, const float* x, float* out, int B, int H, int W, int C, int kernel, int stride,
+                              int pad) {
+    if (const char* e = maxpool_shape_error(B, H, W, C, kernel, stride, pad)) return fail(CP_ERR_INVALID, e);
+    if (!x || !out) return fail(CP_ERR_INVALID, "maxpool2d_forward: null argument");
+    if (!bn_aligned({x, out})) return fail(CP_ERR_INVALID, "maxpool2d_forward: tensors must be 16-byte aligned");
+    const int rc = cp_launch_maxpool_forward((hipStream_t)stream, x, out, B, H, W, C, kernel);
+    return rc == CP_OK ? CP_OK : fail(rc, "maxpool2d_forward: kernel launch failed");
+}
+
+int cp_maxpool2d_backward_nhwc(cp_stream_t stream, const float* x, const float* grad_out, float* grad_x, int B, int H, int W, int C,
+                               int kernel, int stride, int pad) {
+    if (const char* e = maxpool_shape_error(B, H, W, C, kernel, stride, pad)) return fail(CP_ERR_INVALID, e);
+    if (!x || !grad_out || !grad_x) return fail(CP_ERR_INVALID, "maxpool2d_backward: null argument");
+    if (!bn_aligned({x, grad_out, grad_x})) return fail(CP_ERR_INVALID, "maxpool2d_backward: tensors must be 16-byte aligned");
+    const int rc = cp_launch_maxpool_backward((hipStream_t)stream, x, grad_out, grad_x, B, H, W, C, kernel);
+    return rc == CP_OK ? CP_OK : fail(rc, "maxpool2d_backward: kernel launch failed");
+}
+
+// The image stems' weight / bias gradient (stem_bwd.hip)
+size_t cp_conv2d_stem_backward_workspace_bytes(int B, int H, int W, int Cin, int Cout, int stride) {
+    if (const char* e = cp_stem_backward_shape_error(B, H, W, Cin, Cout, stride)) {
+        fail(CP_ERR_INVALID, e);
+        return 0;
+    }
+    return cp_stem_backward_ws_bytes(B, H, W, Cin, Cout, stride);
+}
+
+int cp_conv2d_stem_backward(cp_stream_t stream, const float* x_nchw, const float* grad_out_nhwc, const float* y_or_null,
+                            float* grad_w, float* grad_bias_or_null, void* workspace, size_t workspace_bytes, int B, int H, int W,
+                            int Cin, int Cout, int stride) {
+    if (const char* e = cp_stem_backward_shape_error(B, H, W, Cin, Cout, stride)) return fail(CP_ERR_INVALID, e);
+    if (!x_nchw || !grad_out_nhwc || !grad_w || !workspace) return fail(CP_ERR_INVALID, "conv2d_stem_backward: null argument");
+    if (workspace_bytes < cp_stem_backward_ws_bytes(B, H, W, Cin, Cout, stride))
+        return fail(CP_ERR_INVALID, "conv2d_stem_backward: workspace too small");
+    const StemBwdArgs a{x_nchw, grad_out_nhwc, y_or_null, grad_w, grad_bias_or_null, B, H, W, Cin, Cout, stride};
+    const int rc = cp_launch_stem_backward((hipStream_t)stream, a, workspace);
+    return rc == CP_OK ? CP_OK : fail(rc, "conv2d_stem_backward: kernel launch failed");
 }
 
 size_t cp_dcnv2_backward_workspace_bytes(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw,

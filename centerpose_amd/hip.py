@@ -138,6 +138,10 @@ def lib():
     _sig(L.cp_batchnorm_forward_nhwc, c_int, *([c_void_p] * 10), *([c_int] * 5), ctypes.c_float, ctypes.c_float, c_int, c_void_p,
          c_size_t)
     _sig(L.cp_batchnorm_backward_nhwc, c_int, *([c_void_p] * 11), *([c_int] * 5), c_void_p, c_size_t)
+    _sig(L.cp_maxpool2d_forward_nhwc, c_int, c_void_p, c_void_p, c_void_p, *([c_int] * 7))
+    _sig(L.cp_maxpool2d_backward_nhwc, c_int, c_void_p, c_void_p, c_void_p, c_void_p, *([c_int] * 7))
+    _sig(L.cp_conv2d_stem_backward_workspace_bytes, c_size_t, *([c_int] * 6))
+    _sig(L.cp_conv2d_stem_backward, c_int, *([c_void_p] * 7), c_size_t, *([c_int] * 6))
     _sig(L.cp_decode_workspace_bytes, c_size_t, c_int, c_int)
     _sig(L.cp_decode, c_int, c_void_p, c_int, c_int, c_int, *([c_void_p] * 11), c_int, c_int, c_int, ctypes.c_float,
          c_int, c_int, c_void_p, c_void_p, c_size_t)
@@ -237,7 +241,8 @@ def exported_symbols():
             "cp_model_features", "cp_conv2d_backward_workspace_bytes", "cp_conv2d_backward_nhwc",
             "cp_batchnorm_workspace_bytes", "cp_batchnorm_forward_nhwc", "cp_batchnorm_backward_nhwc",
             "cp_conv_transpose2d_dw_nhwc", "cp_conv_transpose2d_backward_workspace_bytes",
-            "cp_conv_transpose2d_backward_nhwc"]
+            "cp_conv_transpose2d_backward_nhwc", "cp_maxpool2d_forward_nhwc", "cp_maxpool2d_backward_nhwc",
+            "cp_conv2d_stem_backward_workspace_bytes", "cp_conv2d_stem_backward"]
 
 
 def _check(rc, what):
@@ -645,6 +650,70 @@ def conv_transpose2d_backward(x, w, grad_out, stride, pad, groups=1, need_x_grad
                                              Cout, K, stride, pad, groups, _ptr(ws), nbytes)
     _check(rc, "cp_conv_transpose2d_backward_nhwc")
     return grad_x, grad_w
+
+
+def _pool_out(H, W, kernel, stride, pad):
+    return (H + 2 * pad - kernel) // stride + 1, (W + 2 * pad - kernel) // stride + 1
+
+
+def max_pool2d_forward(x, kernel, stride, pad):
+    """``F.max_pool2d`` on an NHWC tensor (cp_maxpool2d_forward_nhwc): x [B,H,W,C] -> [B,Ho,Wo,C].  (kernel, stride, pad) is
+    (2, 2, 0), which floors, or (3, 2, 1), padding as -inf; C % 4 == 0.  Bitwise torch's values."""
+    x = _dev(x)
+    if x.dim() != 4:
+        raise RuntimeError("max_pool2d: x must be [B,H,W,C], got %s" % (tuple(x.shape),))
+    B, H, W, C = x.shape
+    kernel, stride, pad = int(kernel), int(stride), int(pad)
+    Ho, Wo = _pool_out(H, W, kernel, stride, pad)
+    out = torch.empty(B, max(Ho, 0), max(Wo, 0), C, device=x.device, dtype=torch.float32)
+    _check(lib().cp_maxpool2d_forward_nhwc(_stream(), _ptr(x), _ptr(out), B, H, W, C, kernel, stride, pad),
+           "cp_maxpool2d_forward_nhwc")
+    return out
+
+
+def max_pool2d_backward(x, grad_out, kernel, stride, pad):
+    """Gradient of max_pool2d_forward (cp_maxpool2d_backward_nhwc): x [B,H,W,C], grad_out [B,Ho,Wo,C] -> grad_x [B,H,W,C].  The
+    winner of every window is recomputed from x (torch's: the first maximum in row-major order); bitwise reproducible."""
+    x, grad_out = _dev(x), _dev(grad_out)
+    if x.dim() != 4:
+        raise RuntimeError("max_pool2d_backward: x must be [B,H,W,C], got %s" % (tuple(x.shape),))
+    B, H, W, C = x.shape
+    kernel, stride, pad = int(kernel), int(stride), int(pad)
+    Ho, Wo = _pool_out(H, W, kernel, stride, pad)
+    if tuple(grad_out.shape) != (B, Ho, Wo, C):
+        raise RuntimeError("max_pool2d_backward: grad_out has shape %s, expected %s" % (tuple(grad_out.shape), (B, Ho, Wo, C)))
+    grad_x = torch.empty_like(x)
+    _check(lib().cp_maxpool2d_backward_nhwc(_stream(), _ptr(x), _ptr(grad_out), _ptr(grad_x), B, H, W, C, kernel, stride, pad),
+           "cp_maxpool2d_backward_nhwc")
+    return grad_x
+
+
+def conv2d_stem_backward(x, grad_out, stride=1, y=None, need_bias_grad=True):
+    """Weight and bias gradient of a 7x7, padding-3 stem (cp_conv2d_stem_backward): x [B,Cin,H,W] NCHW planes with Cin in 1..3,
+    grad_out [B,Ho,Wo,Cout] NHWC -> (grad_w [Cout,Cin,7,7], grad_bias [Cout] | None).  ``y``: the activated forward output when
+    the layer ended in a ReLU (grad_out is gated by y > 0).  Float32 and bitwise reproducible; there is no input gradient."""
+    L = lib()
+    x, grad_out = _dev(x), _dev(grad_out)
+    y = _dev(y) if y is not None else None
+    if x.dim() != 4 or grad_out.dim() != 4:
+        raise RuntimeError("conv2d_stem_backward: x must be [B,Cin,H,W] and grad_out [B,Ho,Wo,Cout], got %s and %s"
+                           % (tuple(x.shape), tuple(grad_out.shape)))
+    B, Cin, H, W = x.shape
+    Cout, stride = grad_out.shape[3], int(stride)
+    nbytes = L.cp_conv2d_stem_backward_workspace_bytes(B, H, W, Cin, Cout, stride)
+    if nbytes == 0:
+        raise RuntimeError("conv2d_stem_backward: shape refused by the library (%s)" % L.cp_last_error().decode())
+    want = (B, (H - 1) // stride + 1, (W - 1) // stride + 1, Cout)
+    for name, t in (("grad_out", grad_out), ("y", y)):
+        if t is not None and tuple(t.shape) != want:
+            raise RuntimeError("conv2d_stem_backward: %s has shape %s, expected %s" % (name, tuple(t.shape), want))
+    grad_w = torch.empty(Cout, Cin, 7, 7, device=x.device, dtype=torch.float32)
+    grad_b = torch.empty(Cout, device=x.device, dtype=torch.float32) if need_bias_grad else None
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    rc = L.cp_conv2d_stem_backward(_stream(), _ptr(x), _ptr(grad_out), _ptr(y), _ptr(grad_w), _ptr(grad_b), _ptr(ws), nbytes,
+                                   B, H, W, Cin, Cout, stride)
+    _check(rc, "cp_conv2d_stem_backward")
+    return grad_w, grad_b
 
 
 PRECISIONS = {"f32": 0, "f16x3": 1}

@@ -133,6 +133,28 @@ class HipPoseNet(object):
         self._hip = None
         return self
 
+    # ---- training the whole network (centerpose_amd/pose_net.py) ----
+    def train_module(self):
+        """A ``PoseNet`` holding copies of this model's current parameters and buffers (train it, then ``load_module``)."""
+        from centerpose_amd.pose_net import PoseNet
+        net = PoseNet(self.heads, self.head_conv, self.opt, arch=self.arch)
+        net.load_state_dict(self._sd, strict=True)
+        return net
+
+    def load_module(self, net):
+        """Copies a ``PoseNet``'s parameters and buffers (the running statistics and ``num_batches_tracked`` included) back into
+        this model; the next call / detector run uses them."""
+        sd = net.state_dict()
+        bad = [k for k in self._sd if k not in sd or tuple(sd[k].shape) != tuple(self._sd[k].shape)] + \
+              [k for k in sd if k not in self._sd]
+        if bad:
+            raise RuntimeError("load_module: the module does not match this model (first differences: %s)" % bad[:5])
+        for k, v in sd.items():
+            v = v.detach().cpu()
+            self._sd[k] = (v.float() if v.is_floating_point() else v).clone()
+        self._hip = None
+        return self
+
     def parameters(self):
         return (v for k, v in self._sd.items() if v.is_floating_point() and 'running_' not in k)
 

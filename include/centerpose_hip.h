@@ -392,6 +392,45 @@ int cp_conv_transpose2d_backward_nhwc(cp_stream_t stream, const float* x, const 
                                       int stride, int pad, int groups, void* workspace, size_t workspace_bytes);
 
 /* ------------------------------------------------------------------------------------------
+ * MaxPool2d for training — Tree.downsample of models/networks/pose_dla_dcn.py:211-224 (kernel 2, stride 2, padding 0; it floors,
+ *   so an odd last row / column belongs to no window) and the maxpool of models/networks/resnet_dcn.py (kernel 3, stride 2,
+ *   padding 1; padding counts as -inf), forward and backward, float32 NHWC:
+ *   x, grad_x [B,H,W,C]; out, grad_out [B,Ho,Wo,C], Ho = (H + 2 pad - kernel) / 2 + 1 (Wo likewise).
+ * The winner of a window is torch's in both calls: the taps inside the image are scanned in row-major order and a tap replaces
+ * the current one only if it is strictly greater (or a NaN), so a window of equal values (the zeros a ReLU leaves) selects its
+ * first tap.  The forward copies the winners, so it is bitwise torch's.  The backward keeps no index tensor: every grad_x
+ * element recomputes, from x, the winner of each window that covers it (one at kernel 2, up to four at kernel 3) and adds that
+ * window's grad_out where it is the winner itself, windows in (row, column) order; elements that no window covers or that never
+ * win are exact zeros.  grad_x is written, not accumulated.  No atomics; bitwise reproducible call to call.
+ * Refused with CP_ERR_INVALID and a cp_last_error() text before any launch: a NULL pointer, another (kernel, stride, pad),
+ * B / H / W < 1, C % 4 != 0, an empty output (H or W below the window), a pointer that is not 16-byte aligned, a tensor of
+ * 2^31 elements or more.  No workspace.  Launches on `stream`, never synchronises.
+ * ------------------------------------------------------------------------------------------ */
+int cp_maxpool2d_forward_nhwc(cp_stream_t stream, const float* x, float* out, int B, int H, int W, int C, int kernel, int stride,
+                              int pad);
+int cp_maxpool2d_backward_nhwc(cp_stream_t stream, const float* x, const float* grad_out, float* grad_x, int B, int H, int W,
+                               int C, int kernel, int stride, int pad);
+
+/* ------------------------------------------------------------------------------------------
+ * Weight and bias gradient of the image stems — Conv2d(Cin, Cout, kernel 7, stride 1 | 2, padding 3) with Cin in 1..3, the
+ *   layers cp_conv2d_backward_nhwc refuses: base_layer, pre_img_layer and pre_hm_layer of models/networks/pose_dla_dcn.py:247-271
+ *   and conv1 of models/networks/resnet_dcn.py.
+ * x_nchw [B,Cin,H,W] is the caller's image as a data loader hands it over (planes, NOT NHWC); grad_out_nhwc and y [B,Ho,Wo,Cout]
+ * NHWC with Ho = (H - 1) / stride + 1 (Wo likewise).  Outputs, written (not accumulated): grad_w [Cout,Cin,7,7] (PyTorch layout)
+ * and grad_bias [Cout] (NULL: not stored).  y (the ACTIVATED forward output) or NULL: when given, grad_out is gated by y > 0.
+ * There is no data gradient: the input is an image.  Cout in {16, 32, 48, 64}.
+ * Float32 on v_mfma_f32_16x16x4_f32 whatever cp_set_default_precision says; partial sums per workgroup go to the workspace and
+ * are added in a fixed order; no atomics: bitwise reproducible call to call.
+ * Refused with CP_ERR_INVALID and a cp_last_error() text before any launch (the query returns 0): a NULL pointer other than
+ * those named *_or_null, a workspace below the query, B / H / W < 1, another Cin / Cout / stride, a tensor of 2^31 elements or
+ * more.  The query is host arithmetic.  Launches on `stream`, never synchronises.
+ * ------------------------------------------------------------------------------------------ */
+size_t cp_conv2d_stem_backward_workspace_bytes(int B, int H, int W, int Cin, int Cout, int stride);
+int cp_conv2d_stem_backward(cp_stream_t stream, const float* x_nchw, const float* grad_out_nhwc, const float* y_or_null,
+                            float* grad_w, float* grad_bias_or_null, void* workspace, size_t workspace_bytes, int B, int H,
+                            int W, int Cin, int Cout, int stride);
+
+/* ------------------------------------------------------------------------------------------
  * Heat-map decode — replaces `object_pose_decode(..., Inference=True)` (models/decode.py:72-375,
  *   models/utils.py:43-47; called from detectors/object_pose.py:154-161) including the 13
  *   device->host copies and the per-point Python loop (decode.py:191-252).

@@ -1,0 +1,209 @@
+"""Training the whole dla_34 network on the library: one step of centerpose_amd.pose_net.PoseNet, and the two layer families it
+added (the image stems, the max-pools) next to their baselines, in one process (GPU).
+
+    python tools/pose_net_bench.py [--batch 16] [--size 512] [--iters 3] [--rounds 3] [--skip-step] [--out profiles/pose_net_bench.txt]
+
+1. ``step``: forward + backward of PoseNet (random linear loss on the head maps) at ``size`` x ``size``, with the time split per
+   layer family: every ``centerpose_amd.hip`` operator call of the step is bracketed by HIP events (stem / conv / bn / pool /
+   dcn / up / heads, forward and backward apart); what is left of the step's wall time is torch glue (cat, sigmoid, the offset
+   split, layout copies, the loss).
+2. ``stem``: forward + backward of the 3 -> 16 (base_layer, pre_img_layer) and 1 -> 16 (pre_hm_layer) stems, three routes:
+   ``library`` (stem.stem_conv2d: 4-channel forward + cp_conv2d_stem_backward), ``torch`` (F.conv2d on the planes, weight gradient
+   through torch autograd) and ``padded`` (the only route before this operator: conv.conv2d on the image padded to 4 planes,
+   whose weight gradient is wgrad_generic_kernel).  None computes an input gradient.
+3. ``pool``: forward + backward of the four max-pooled tensors of dla_34 (the inputs of levels 2 .. 5) on the library and with
+   F.max_pool2d, channels_last on both sides.
+
+HIP events around ``iters`` steps, ``rounds`` rounds alternating the routes after a warm-up of each; the median round and all
+rounds are reported, one JSON line per measurement.  There is no speed gate: the baselines are measured in the same run.
+Models: the stem's weight gradient is 2 B Ho Wo 49 Cin Cout FLOP and reads grad_out (B Ho Wo Cout floats) once; a pool step
+reads x twice and grad_out once and writes out and grad_x once.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+from collections import OrderedDict
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+FAMILIES = {"conv2d_nhwc": "conv fwd", "conv2d_backward": "conv bwd", "conv2d_stem_backward": "stem bwd",
+            "batch_norm_forward": "bn fwd", "batch_norm_backward": "bn bwd", "max_pool2d_forward": "pool fwd",
+            "max_pool2d_backward": "pool bwd", "conv_transpose2d_dw": "up fwd", "conv_transpose2d_backward": "up bwd",
+            "dcn_v2_forward": "dcn fwd", "dcn_v2_backward": "dcn bwd", "pose_heads_forward": "heads fwd",
+            "pose_heads_backward": "heads bwd"}
+
+
+def main():
+    import torch
+    import torch.nn.functional as F
+
+    from centerpose_amd import conv, hip, pool, stem, synth
+    from centerpose_amd.pose_net import PoseNet
+
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--size", type=int, default=512)
+    ap.add_argument("--iters", type=int, default=3)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--head-conv", type=int, default=256)
+    ap.add_argument("--skip-step", action="store_true", help="only the stem and pool measurements")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("pose_net_bench: no HIP device (there is nothing to measure on the CPU)")
+    dev = torch.device("cuda:0")
+    hip.set_default_precision("f32")
+    B, S = a.batch, a.size
+    lines = []
+
+    def emit(d):
+        print(json.dumps(d), flush=True)
+        lines.append(json.dumps(d))
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(a.iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / a.iters
+
+    def compare(sides):
+        """Warm-up of every route, then `rounds` alternating rounds -> {route: (median ms, [rounds])}"""
+        for fn in sides.values():
+            fn()
+            fn()
+        res = {s: [] for s in sides}
+        for _ in range(a.rounds):
+            for s, fn in sides.items():
+                res[s].append(timed(fn))
+        return {s: (statistics.median(v), v) for s, v in res.items()}
+
+    # ---- 2. the stems ----
+    for name, cin in (("base_layer / pre_img_layer", 3), ("pre_hm_layer", 1)):
+        g = torch.Generator(device=dev).manual_seed(1)
+        x = torch.randn(B, cin, S, S, device=dev, generator=g)
+        w = (torch.randn(16, cin, 7, 7, device=dev, generator=g) / (49 * cin) ** 0.5).requires_grad_(True)
+        go = torch.randn(B, 16, S, S, device=dev, generator=g).contiguous(memory_format=torch.channels_last)
+        x4 = F.pad(x, (0, 0, 0, 0, 0, 4 - cin)).contiguous(memory_format=torch.channels_last)
+        w4 = F.pad(w.detach(), (0, 0, 0, 0, 0, 4 - cin)).requires_grad_(True)
+
+        def run(fn, wt):
+            wt.grad = None
+            fn().backward(go)
+
+        sides = OrderedDict([("library", lambda: run(lambda: stem.stem_conv2d(x, w, None, 1), w)),
+                             ("torch", lambda: run(lambda: F.conv2d(x, w, None, 1, 3), w)),
+                             ("padded", lambda: run(lambda: conv.conv2d(x4, w4, None, 1, 3), w4))])
+        r = compare(sides)
+        sides["library"]()
+        gl = w.grad.clone()
+        sides["torch"]()
+        diff = float((gl - w.grad).abs().max() / w.grad.abs().max())
+        # the backward alone (the new kernel): cp_conv2d_stem_backward on the same tensors
+        gon = go.permute(0, 2, 3, 1)
+        bwd = statistics.median([timed(lambda: hip.conv2d_stem_backward(x, gon, 1)) for _ in range(a.rounds)])
+        fl, byt = 2.0 * B * S * S * 49 * cin * 16, 4.0 * B * S * S * (16 + cin)
+        emit({"what": "stem", "layer": name, "B": B, "Cin": cin, "Cout": 16, "HxW": S,
+              "library_ms": round(r["library"][0], 3), "torch_ms": round(r["torch"][0], 3), "padded_generic_ms": round(r["padded"][0], 3),
+              "library_ms_rounds": [round(v, 3) for v in r["library"][1]], "torch_ms_rounds": [round(v, 3) for v in r["torch"][1]],
+              "padded_generic_ms_rounds": [round(v, 3) for v in r["padded"][1]],
+              "padded_over_library": round(r["padded"][0] / r["library"][0], 2), "torch_over_library": round(r["torch"][0] / r["library"][0], 2),
+              "stem_backward_kernel_ms": round(bwd, 3), "stem_backward_tflops": round(fl / bwd / 1e9, 2),
+              "stem_backward_gb_per_s": round(byt / bwd / 1e6, 1), "max_rel_grad_diff_vs_torch": diff})
+        del x, w, go, x4, w4, sides
+        torch.cuda.empty_cache()
+
+    # ---- 3. the max-pools ----
+    for name, C, R in (("level2", 32, S // 2), ("level3", 64, S // 4), ("level4", 128, S // 8), ("level5", 256, S // 16)):
+        g = torch.Generator(device=dev).manual_seed(2)
+        x = torch.relu(torch.randn(B, C, R, R, device=dev, generator=g)).contiguous(memory_format=torch.channels_last).requires_grad_(True)
+        go = torch.randn(B, C, R // 2, R // 2, device=dev, generator=g).contiguous(memory_format=torch.channels_last)
+
+        def run(fn):
+            x.grad = None
+            fn().backward(go)
+
+        sides = OrderedDict([("library", lambda: run(lambda: pool.max_pool2d(x, 2, 2))), ("torch", lambda: run(lambda: F.max_pool2d(x, 2, 2)))])
+        r = compare(sides)
+        sides["library"]()
+        gl = x.grad.clone()
+        sides["torch"]()
+        byt = 4.0 * B * C * R * R * (2 + 1) + 4.0 * B * C * (R // 2) ** 2 * 2
+        emit({"what": "pool", "layer": name + ".downsample", "B": B, "C": C, "HxW": R, "library_ms": round(r["library"][0], 3),
+              "torch_ms": round(r["torch"][0], 3), "library_ms_rounds": [round(v, 3) for v in r["library"][1]],
+              "torch_ms_rounds": [round(v, 3) for v in r["torch"][1]], "library_over_torch": round(r["library"][0] / r["torch"][0], 2),
+              "library_gb_per_s": round(byt / r["library"][0] / 1e6, 1), "grad_bitwise_equal_torch": bool(torch.equal(gl, x.grad))})
+        del x, go, sides
+        torch.cuda.empty_cache()
+
+    # ---- 1. the whole step ----
+    if not a.skip_step:
+        heads = synth.HEADS_POSE
+        net = PoseNet(heads, head_conv=a.head_conv)
+        net.load_state_dict(synth.make_state_dict("dla_34", heads, head_conv=a.head_conv))
+        net = net.to(dev).train()
+        x = synth.frames(B, h=S, w=S).to(dev)
+        g = torch.Generator(device=dev).manual_seed(3)
+        lin = {h: torch.randn(B, c, S // 4, S // 4, device=dev, generator=g) for h, c in heads.items()}
+
+        def step():
+            net.zero_grad(set_to_none=True)
+            z = net(x)[0]
+            sum((z[h] * lin[h]).sum() for h in z).backward()
+
+        step()
+        step()
+        total = [timed(step) for _ in range(a.rounds)]
+        # one more step with every operator call bracketed by events
+        events, originals = [], {}
+
+        def wrap(fname, fn):
+            def inner(*args, **kw):
+                fam = FAMILIES[fname]
+                if fname == "conv2d_nhwc" and args[0].shape[3] == 4 and args[1].shape[2] == 7:
+                    fam = "stem fwd"
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                out = fn(*args, **kw)
+                e1.record()
+                events.append((fam, e0, e1))
+                return out
+            return inner
+
+        for fname in FAMILIES:
+            originals[fname] = getattr(hip, fname)
+            setattr(hip, fname, wrap(fname, originals[fname]))
+        try:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            step()
+            e1.record()
+            torch.cuda.synchronize()
+        finally:
+            for fname, fn in originals.items():
+                setattr(hip, fname, fn)
+        split, calls = OrderedDict(), OrderedDict()
+        for fam, s0, s1 in events:
+            split[fam] = split.get(fam, 0.0) + s0.elapsed_time(s1)
+            calls[fam] = calls.get(fam, 0) + 1
+        traced = e0.elapsed_time(e1)
+        split["torch glue and launch gaps"] = traced - sum(split.values())
+        emit({"what": "step", "arch": "dla_34", "B": B, "HxW": S, "head_conv": a.head_conv, "step_ms": round(statistics.median(total), 2),
+              "step_ms_rounds": [round(v, 2) for v in total], "images_per_s": round(B / statistics.median(total) * 1e3, 1),
+              "traced_step_ms": round(traced, 2), "family_ms": {k: round(v, 2) for k, v in split.items()}, "family_calls": calls,
+              "peak_memory_gib": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)})
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
