@@ -554,6 +554,11 @@ int cp_pose_loss_backward(cp_stream_t stream, const cp_pose_loss_desc* d, const 
 int cp_linear_assignment(const double* cost, int n_rows, int n_cols, int solver, int* match_out) {
     if (n_rows < 0 || n_cols < 0 || (n_rows > 0 && !match_out) || (n_rows > 0 && n_cols > 0 && !cost) || (solver != 1 && solver != 2))
         return fail(CP_ERR_INVALID, "cp_linear_assignment: bad argument (solver: 1 Munkres, 2 scipy LSAP)");
+    for (int i = 0; i < n_rows; ++i)
+        for (int j = 0; j < n_cols; ++j)
+            if (!std::isfinite(cost[(size_t)i * n_cols + j]))
+                return fail(CP_ERR_INVALID, "cp_linear_assignment: non-finite cost at row " + std::to_string(i) + ", column " +
+                                                std::to_string(j) + " (forbidden pairs are 1e18, not inf)");
     const size_t ls = (size_t)(n_rows > n_cols ? n_rows : n_cols) + 1;
     auto c = [&](int i, int j) -> double { return cost[(size_t)i * n_cols + j]; };
     try {
@@ -562,13 +567,16 @@ int cp_linear_assignment(const double* cost, int n_rows, int n_cols, int solver,
             std::vector<int> path(ls), c4r(ls), r4c(ls), rem(ls);
             std::vector<unsigned char> sr(ls), sc(ls);
             const TrkLsapWork W = {u.data(), v.data(), spc.data(), path.data(), c4r.data(), r4c.data(), rem.data(), sr.data(), sc.data()};
-            trk_lsap(c, n_rows, n_cols, match_out, W);
+            if (!trk_lsap(c, n_rows, n_cols, match_out, W))
+                return fail(CP_ERR_INVALID, "cp_linear_assignment: cost matrix is infeasible (costs whose sums overflow float64?)");
         } else {
             std::vector<double> C((size_t)n_rows * n_cols + 1);
             std::vector<unsigned char> marked((size_t)n_rows * n_cols + 1), ru(ls), cu(ls);
             std::vector<int> path(2 * ((size_t)n_rows + n_cols) + 2);
             const TrkMunkresWork W = {C.data(), marked.data(), ru.data(), cu.data(), path.data()};
-            trk_munkres(c, n_rows, n_cols, match_out, W);
+            if (!trk_munkres(c, n_rows, n_cols, match_out, W))
+                return fail(CP_ERR_INVALID, "cp_linear_assignment: Munkres hit its iteration bound (costs whose differences "
+                                            "overflow float64?); match_out holds a partial matching");
         }
     } catch (const std::bad_alloc&) {
         return fail(CP_ERR_ALLOC, "cp_linear_assignment: out of host memory");

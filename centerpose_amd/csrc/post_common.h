@@ -91,6 +91,11 @@ POST_HD void post_transform_record(const float* d, const double* t, float ratio,
     }
 }
 
+POST_HD bool post_box_finite(const double* b) {
+    const double inf = __builtin_huge_val();
+    return fabs(b[0]) < inf && fabs(b[1]) < inf && fabs(b[2]) < inf && fabs(b[3]) < inf;
+}
+
 // keep score > vis_thresh in decode order, then (nms) the reference's Gaussian soft-NMS walk; arrays are rewritten in
 // place, idx[r] = decode-order index of the r-th survivor; returns the number of survivors
 POST_HD int post_filter_nms(double* s_score, double (*s_box)[4], int* s_idx, int K, double vis_thresh, int nms) {
@@ -114,9 +119,14 @@ POST_HD int post_filter_nms(double* s_score, double (*s_box)[4], int* s_idx, int
             { const double v = s_score[i]; s_score[i] = s_score[maxpos]; s_score[maxpos] = v; }
             { const int v = s_idx[i]; s_idx[i] = s_idx[maxpos]; s_idx[maxpos] = v; }
             const double tx1 = s_box[i][0], ty1 = s_box[i][1], tx2 = s_box[i][2], ty2 = s_box[i][3];
+            // A box with a NaN or infinite corner has no overlap with anything: it neither suppresses another record nor is
+            // suppressed (fmin / fmax would drop the NaN and compare the other box with itself; the decayed score would be
+            // NaN, which no threshold removes).  Finite boxes take the reference's path, bit for bit.
+            if (!post_box_finite(s_box[i])) continue;
             int pos = i + 1;
             while (pos < N) {
                 const double x1 = s_box[pos][0], y1 = s_box[pos][1], x2 = s_box[pos][2], y2 = s_box[pos][3];
+                if (!post_box_finite(s_box[pos])) { ++pos; continue; }
                 const double area = (x2 - x1 + 1) * (y2 - y1 + 1);
                 const double iw = fmin(tx2, x2) - fmax(tx1, x1) + 1;
                 if (iw > 0) {

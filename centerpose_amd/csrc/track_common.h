@@ -104,17 +104,18 @@ struct TrackParams {
 // matrix is transposed), the candidate list is filled in reverse, ties prefer a column that ends the path, the duals are
 // updated after every augmentation -- and the same float64 operations in the same order, so that even the assignments among
 // 1e18-"forbidden" pairs (whose duals swallow the low bits of the real costs) come out as scipy's do.
-// cost(i, j): det i x track j; nd x nt; match[i] = track of det i or -1.  Work space: u / spc [LS] doubles, v [LS] doubles,
-// path / col4row / row4col / remaining [LS] ints, SR / SC [LS] bytes with LS >= max(nd, nt).
+// cost(i, j): det i x track j; nd x nt; match[i] = track of det i or -1; returns false when the problem is infeasible (see
+// the exit below).  Work space: u / spc [LS] doubles, v [LS] doubles, path / col4row / row4col / remaining [LS] ints,
+// SR / SC [LS] bytes with LS >= max(nd, nt).
 struct TrkLsapWork {
     double* u; double* v; double* spc;
     int* path; int* col4row; int* row4col; int* remaining;
     unsigned char* SR; unsigned char* SC;
 };
 template <class Cost>
-CP_HD void trk_lsap(const Cost& cost, int nd, int nt, int* match, const TrkLsapWork& W) {
+CP_HD bool trk_lsap(const Cost& cost, int nd, int nt, int* match, const TrkLsapWork& W) {
     for (int i = 0; i < nd; ++i) match[i] = -1;
-    if (nd == 0 || nt == 0) return;
+    if (nd == 0 || nt == 0) return true;
     const bool tr = nt < nd;                 // tall: rows = tracks, columns = detections
     const int nr = tr ? nt : nd, nc = tr ? nd : nt;
     auto C = [&](int i, int j) -> double { return tr ? cost(j, i) : cost(i, j); };
@@ -140,7 +141,11 @@ CP_HD void trk_lsap(const Cost& cost, int nd, int nt, int* match, const TrkLsapW
                 if (W.spc[j] < lowest || (W.spc[j] == lowest && W.row4col[j] == -1)) { lowest = W.spc[j]; index = it; }
             }
             minVal = lowest;
-            if (!(minVal < INF)) return;  // infeasible (cannot happen: every cost is finite)
+            // infeasible: only a +inf / NaN cost gets here.  Unreachable from trk_associate, whose costs are sanitised into
+            // [0, 1e18] (every reduced cost is then a finite sum of at most a few finite terms); cp_linear_assignment refuses
+            // non-finite matrices before it calls, so only finite costs whose sums overflow (+-1e308) reach it there.  Kept
+            // as scipy has it (which raises here): no row has a partner, and the caller is told (false).
+            if (!(minVal < INF)) return false;
             const int j = W.remaining[index];
             if (W.row4col[j] == -1) sink = j;
             else i = W.row4col[j];
@@ -168,6 +173,7 @@ CP_HD void trk_lsap(const Cost& cost, int nd, int nt, int* match, const TrkLsapW
         if (tr) match[W.col4row[r]] = r;  // row = track, its column = the detection
         else match[r] = W.col4row[r];
     }
+    return true;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -186,13 +192,28 @@ CP_HD void trk_lsap(const Cost& cost, int nd, int nt, int* match, const TrkLsapW
 // row_unc [n] / col_unc [m] bytes, path [2 (n + m)] ints.  Cost: O(n m) per search and per adjustment, O(n^2 m) .. O(n^3 m)
 // in all on one lane -- microseconds for a frame's ten detections, long for a hundred mutually tied ones; the scipy form
 // above (hungarian = 2) is the fast one.
+// Termination does not depend on the data.  Every loop carries the bound the algorithm itself gives it:
+//   * a round (steps 3-5) ends by turning an alternating path's primes into stars, one star more than before, and n stars
+//     end the routine: at most n rounds;
+//   * inside a round a priming either ends the round (its row holds no star) or covers that row, and rows are only uncovered
+//     when a round starts: at most n + 1 primings -- the search itself only looks at uncovered rows;
+//   * an adjustment (step 6) runs when no uncovered zero is left and, on finite data, turns the smallest uncovered value
+//     into an exact zero (that entry lies in an uncovered row, so only `-= minval` touches it) which the next search primes:
+//     at most as many adjustments as primings, n + 1 per round;
+//   * the step-5 path alternates between primes and stars, visits every star at most once and starts in a row without a
+//     star: at most n - 1 stars, 2 n - 1 entries (the work space holds n + m).  A star on it without a prime in its row
+//     cannot be continued and counts as an overrun, too.
+// A matrix with NaN or +-inf entries, or finite ones whose reduction overflows (+-1e308), breaks the third argument -- the
+// "smallest uncovered value" is NaN or inf and creates no zero -- and used to spin there for ever.  On an overrun the routine
+// stops and returns false with the stars it holds: stars never share a row or a column, so `match` is a valid partial
+// matching and the other rows keep -1.  True: the complete optimal assignment.
 struct TrkMunkresWork {
     double* C; unsigned char* marked; unsigned char* row_unc; unsigned char* col_unc; int* path;
 };
 template <class Cost>
-CP_HD void trk_munkres(const Cost& cost, int nd, int nt, int* match, const TrkMunkresWork& W) {
+CP_HD bool trk_munkres(const Cost& cost, int nd, int nt, int* match, const TrkMunkresWork& W) {
     for (int i = 0; i < nd; ++i) match[i] = -1;
-    if (nd == 0 || nt == 0) return;
+    if (nd == 0 || nt == 0) return true;
     const bool tr = nt < nd;  // more rows (detections) than columns: the transpose is solved, the pairs swapped back
     const int n = tr ? nt : nd, m = tr ? nd : nt;
     double* C = W.C;
@@ -218,7 +239,8 @@ CP_HD void trk_munkres(const Cost& cost, int nd, int nt, int* match, const TrkMu
                 W.row_unc[i] = 0;
             }
         }
-    for (;;) {
+    bool overrun = false;
+    for (int round = 0; !overrun; ++round) {
         // ---- step 3: covers cleared, starred columns covered; n stars = a complete assignment ----
         for (int i = 0; i < n; ++i) W.row_unc[i] = 1;
         for (int j = 0; j < m; ++j) W.col_unc[j] = 1;
@@ -227,8 +249,9 @@ CP_HD void trk_munkres(const Cost& cost, int nd, int nt, int* match, const TrkMu
             for (int j = 0; j < m; ++j)
                 if (mk[i * m + j] == 1) { W.col_unc[j] = 0; ++stars; }
         if (stars >= n) break;
+        if (round >= n) { overrun = true; break; }
         int zr = -1, zc = -1;
-        for (;;) {
+        for (int adjustments = 0, primings = 0;;) {
             // ---- step 4: prime the first uncovered zero (row-major) until one has no star in its row ----
             for (;;) {
                 int row = -1, col = -1;
@@ -238,6 +261,7 @@ CP_HD void trk_munkres(const Cost& cost, int nd, int nt, int* match, const TrkMu
                         if (W.col_unc[j] && C[i * m + j] == 0.0) { row = i; col = j; break; }
                 }
                 if (row < 0) break;  // none left: adjust the matrix
+                if (++primings > n + 1) { overrun = true; break; }
                 mk[row * m + col] = 2;
                 int star = -1;
                 for (int j = 0; j < m; ++j)
@@ -246,7 +270,8 @@ CP_HD void trk_munkres(const Cost& cost, int nd, int nt, int* match, const TrkMu
                 W.row_unc[row] = 0;
                 W.col_unc[star] = 1;
             }
-            if (zr >= 0) break;
+            if (zr >= 0 || overrun) break;
+            if (++adjustments > n + 1) { overrun = true; break; }
             // ---- step 6: smallest uncovered value: + on covered rows, then - on uncovered columns ----
             bool any_r = false, any_c = false;
             for (int i = 0; i < n; ++i) any_r = any_r || W.row_unc[i];
@@ -267,6 +292,7 @@ CP_HD void trk_munkres(const Cost& cost, int nd, int nt, int* match, const TrkMu
                         for (int i = 0; i < n; ++i) C[i * m + j] -= minval;
             }
         }
+        if (overrun) break;
         // ---- step 5: alternating path from the primed zero; stars on it go, its primes become stars; primes erased ----
         int count = 0;
         W.path[0] = zr;
@@ -277,16 +303,19 @@ CP_HD void trk_munkres(const Cost& cost, int nd, int nt, int* match, const TrkMu
             for (int i = 0; i < n; ++i)
                 if (mk[i * m + pc] == 1) { row = i; break; }
             if (row < 0) break;
-            ++count;
-            W.path[2 * count] = row;
-            W.path[2 * count + 1] = pc;
             int pcol = -1;
             for (int j = 0; j < m; ++j)
                 if (mk[row * m + j] == 2) { pcol = j; break; }
+            // (a star on the path always has a prime in its row, and the path holds at most 2 n - 1 entries)
+            if (pcol < 0 || count + 2 > 2 * n - 2) { overrun = true; break; }
             ++count;
             W.path[2 * count] = row;
-            W.path[2 * count + 1] = pcol;  // (a star on the path always has a prime in its row)
+            W.path[2 * count + 1] = pc;
+            ++count;
+            W.path[2 * count] = row;
+            W.path[2 * count + 1] = pcol;
         }
+        if (overrun) break;  // the stars stay as they were: still a matching
         for (int k = 0; k <= count; ++k) {
             unsigned char& e = mk[W.path[2 * k] * m + W.path[2 * k + 1]];
             e = e == 1 ? 0 : 1;
@@ -300,6 +329,7 @@ CP_HD void trk_munkres(const Cost& cost, int nd, int nt, int* match, const TrkMu
                 if (tr) match[j] = i;  // row = track, column = detection
                 else match[i] = j;
             }
+    return !overrun;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -665,11 +695,15 @@ CP_HD double trk_gaussian_radius(double h, double w) {  // utils/image.py:103-12
 // The Gaussians `_get_additional_inputs` draws for one track (base_detector.py:150-388, the 'pnp' / 'kps' branches of the
 // inference configuration): rec[0] = the centre blob for pre_hm, rec[1..8] = the vertex blobs for pre_hm_hp; a record is
 // (channel, x, y, radius, k) with channel = -1 when nothing is drawn.  hm_plane / hp_plane0: planes of this video.
+// Nothing non-finite is drawn, whatever the track holds: a NaN score is not "at least pre_thresh", a NaN or infinite vertex
+// is outside the image, a spread that is no int32 is "missing", and a record whose k is not finite is withdrawn -- every
+// record that leaves here is either channel -1 or finite with 0 <= x < inp_w, 0 <= y < inp_h, 0 <= radius.  The
+// comparisons are written so that finite input gives the bits it always gave.
 CP_HD void trk_render_records(const TrackParams& P, const double* vm, const double* t, int hm_plane, int hp_plane0,
                               double* rec) {
     for (int i = 0; i < 9; ++i) rec[5 * i] = -1.0;
     const double score = t[TR_POST + PO_SCORE];
-    if (score < P.pre_thresh) return;
+    if (!(score >= P.pre_thresh)) return;
     const double* T = vm + VM_TIN;
     const double iw = vm[VM_INP_W], ih = vm[VM_INP_H], W0 = vm[VM_WIDTH], H0 = vm[VM_HEIGHT];
     // _trans_bbox: float32 box, both corners through trans_input, clipped to the input
@@ -692,8 +726,10 @@ CP_HD void trk_render_records(const TrackParams& P, const double* vm, const doub
     const int radius = (int)rr > 0 ? (int)rr : 0;
     const int ctx = (int)((bx[0] + bx[2]) / 2.f), cty = (int)((bx[1] + bx[3]) / 2.f);
     if (P.pre_hm && (P.render_hm_mode == 0 || P.render_hm_mode == 1)) {
-        rec[0] = hm_plane; rec[1] = ctx; rec[2] = cty; rec[3] = radius;
-        rec[4] = P.render_hm_mode == 1 ? score : 1.0;
+        const double k = P.render_hm_mode == 1 ? score : 1.0;
+        if (fabs(k) < __builtin_huge_val()) {  // (a score of +inf passes pre_thresh and cannot be drawn)
+            rec[0] = hm_plane; rec[1] = ctx; rec[2] = cty; rec[3] = radius; rec[4] = k;
+        }
     }
     if (!P.pre_hm_hp) return;
     const int flags = (int)t[TR_FLAGS];
@@ -727,9 +763,8 @@ CP_HD void trk_render_records(const TrackParams& P, const double* vm, const doub
         int vis = 0;
         if (j < nsrc) {
             const double qx = src[2 * j], qy = src[2 * j + 1];
-            const bool outside = qx >= W0 || qx < 0 || qy < 0 || qy >= H0;
-            px = (long long)qx;
-            py = (long long)qy;
+            const bool outside = !(qx < W0) || !(qx >= 0) || !(qy >= 0) || !(qy < H0);
+            if (!outside) { px = (long long)qx; py = (long long)qy; }  // (an outside point is never drawn: no conversion of it)
             vis = outside ? 1 : 2;
         }
         double ox, oy;
@@ -741,7 +776,9 @@ CP_HD void trk_render_records(const TrackParams& P, const double* vm, const doub
         bool draw;
         if (pnp_mode && (P.render_hmhp_mode == 0 || P.render_hmhp_mode == 2)) {
             const double* spread = P.hps_uncertainty ? t + TR_FUS_STD : t + TR_POST + PO_HM_STD;
-            draw = (int)spread[2 * j] > 0;  // astype(int32): the heat-map estimate is sometimes missing
+            // astype(int32) > 0: the heat-map estimate is sometimes missing (NaN and values beyond int32 convert to INT_MIN in
+            // numpy and on x86, so they count as missing; the conversion itself would be undefined here)
+            draw = spread[2 * j] >= 1.0 && spread[2 * j] < 2147483648.0;
             if (P.kalman && (flags & 16)) {
                 const double vx = t[TR_KF_P + 16 * j], vy = t[TR_KF_P + 16 * j + 5];
                 k = trk_conf(P, sqrt(vx + vy));
@@ -753,7 +790,7 @@ CP_HD void trk_render_records(const TrackParams& P, const double* vm, const doub
         } else {
             draw = true;
         }
-        if (!draw) continue;
+        if (!draw || !(fabs(k) < __builtin_huge_val())) continue;  // (k = NaN / inf: a poisoned filter covariance)
         double* r = rec + 5 * (1 + j);
         r[0] = hp_plane0 + j; r[1] = (double)(int)px; r[2] = (double)(int)py; r[3] = radius; r[4] = k;
     }
@@ -816,12 +853,16 @@ CP_HD int trk_associate(const TrackParams& P, const double* dets, const int* use
                                     (tr[TR_POST + PO_BBOX + 3] - tr[TR_POST + PO_BBOX + 1]));
             const bool bad = c32 > tarea || c32 > darea || (int)d[TR_POST + PO_CLS] != (int)tr[TR_POST + PO_CLS];
             const double c = (double)c32 + (bad ? 1e18 : 0.0);
-            return c > 1e18 ? 1e18 : c;  // dist[dist > 1e18] = 1e18
+            // dist[dist > 1e18] = 1e18, written so that NaN (a non-finite centre or box: every comparison of `bad` is false)
+            // is clamped as well: a cost that is not a number below 1e18 is a forbidden pair.  Same bits on finite input.
+            return !(c < 1e18) ? 1e18 : c;
         };
         // hungarian = 1: the reference's dependency (sklearn 0.22.2's Munkres); 2: scipy's rectangular LSAP -- the same optimum
         // value, possibly another optimum among tied / forbidden pairs (include/centerpose_hip.h: cp_track_params)
-        if (P.hungarian == 2 || !munkres) trk_lsap(cost, nd, np, lsap_match, *lsap);
-        else trk_munkres(cost, nd, np, lsap_match, *munkres);
+        // Neither can fail on these costs (all in [0, 1e18]): trk_lsap's infeasible exit and trk_munkres' loop bounds are out
+        // of reach, and if one were hit the partial matching it leaves is used as it stands.
+        if (P.hungarian == 2 || !munkres) (void)trk_lsap(cost, nd, np, lsap_match, *lsap);
+        else (void)trk_munkres(cost, nd, np, lsap_match, *munkres);
         for (int i = 0; i < nd; ++i) {
             const int match = lsap_match[i];
             if (match >= 0 && cost(i, match) > 1e16) {
@@ -856,6 +897,7 @@ CP_HD int trk_associate(const TrackParams& P, const double* dets, const int* use
                                     (tr[TR_POST + PO_BBOX + 3] - tr[TR_POST + PO_BBOX + 1]));
             const bool bad = c32 > tarea || c32 > darea || dcls != (int)tr[TR_POST + PO_CLS];
             double c = (double)c32 + (bad ? 1e18 : 0.0);
+            if (!(c < 1e18)) c = 1e18;  // the same rule as above: NaN and everything from 1e18 up is a forbidden pair
             if (taken[t]) c = 1e18;  // the column was overwritten by an earlier match
             if (best < 0 || c < bestc) { best = t; bestc = c; }
         }

@@ -189,7 +189,7 @@ class BaseDetector(object):
         else:
             mode = 'pnp' if o.use_pnp else 'kps'
         for det in dets:
-            if mode != 'gt' and det['score'] < o.pre_thresh:
+            if mode != 'gt' and not det['score'] >= o.pre_thresh:  # (written so that a NaN score draws nothing)
                 continue
             box = self._trans_bbox(det['bbox'], t_in, iw, ih)
             box_out = self._trans_bbox(det['bbox'], t_out, ow, oh)

@@ -33,9 +33,16 @@ def soft_nms_nvidia(src_boxes, sigma=0.5, Nt=0.3, threshold=0.001, method=0):
         src_boxes[maxpos]['score'] = ts
         swap_rest(i, maxpos)
         tx1, ty1, tx2, ty2 = src_boxes[i]['bbox'][0:4]
+        # a box with a NaN or infinite corner overlaps nothing: it neither suppresses another record nor is suppressed
+        # (post_common.h: post_filter_nms states the same rule; min / max would pick one operand by accident of order)
+        if not np.isfinite([tx1, ty1, tx2, ty2]).all():
+            continue
         pos = i + 1
         while pos < N:
             x1, y1, x2, y2 = src_boxes[pos]['bbox'][0:4]
+            if not np.isfinite([x1, y1, x2, y2]).all():
+                pos = pos + 1
+                continue
             area = (x2 - x1 + 1) * (y2 - y1 + 1)
             iw = (min(tx2, x2) - max(tx1, x1) + 1)
             if iw > 0:

@@ -148,8 +148,11 @@ class Tracker(object):
             cost = np.zeros((n, m), np.float32)
         bad = (cost > trk_area[None, :]) | (cost > det_area[:, None]) | (det_cls[:, None] != trk_cls[None, :])
         cost = cost + bad * _FORBIDDEN
+        # a cost that is not a number below 1e18 is a forbidden pair (track_common.h: trk_associate): the reference's
+        # `dist[dist > 1e18] = 1e18` widened to NaN, which a non-finite centre or box produces and which every comparison of
+        # `bad` lets through -- argmin would pick it and the assignment would never return.  Same bits on finite input.
+        cost[~(cost < _FORBIDDEN)] = _FORBIDDEN
         if self.opt.hungarian:
-            cost[cost > _FORBIDDEN] = _FORBIDDEN
             # opt.hungarian is the reference's flag (opts.py); `hungarian_solver` = 'scipy' selects the other optimum finder
             pairs = _hungarian(cost, 2 if getattr(self.opt, 'hungarian_solver', 'munkres') == 'scipy' else 1)
         else:

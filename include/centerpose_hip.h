@@ -654,7 +654,12 @@ int cp_track_status(cp_stream_t stream, const void* state, int B, int* dropped_o
  * host tracker (centerpose_amd/lib/utils/tracker.py) with the very routine the device tracker runs.
  *   cost       HOST float64 [n_rows, n_cols] row-major (detections x tracks)
  *   solver     1 = scikit-learn 0.22.2's Munkres, 2 = scipy's rectangular LSAP (cp_track_params.hungarian)
- *   match_out  HOST int32 [n_rows]: column of each row, -1 for rows left out (min(n_rows, n_cols) rows get one) */
+ *   match_out  HOST int32 [n_rows]: column of each row, -1 for rows left out (min(n_rows, n_cols) rows get one)
+ * Every entry of `cost` must be finite (a forbidden pair is 1e18, as in the tracker, never inf): a NaN or infinite entry is
+ * refused with CP_ERR_INVALID before any work, and cp_last_error names the first offending row and column.  CP_ERR_INVALID is
+ * also returned when the solver cannot finish -- Munkres met one of its iteration bounds, or the LSAP found the problem
+ * infeasible -- which only finite costs whose differences overflow float64 (entries near +-1e308) can cause; match_out then
+ * holds a valid partial matching (possibly empty).  Neither solver can loop for ever, whatever the input. */
 int cp_linear_assignment(const double* cost, int n_rows, int n_cols, int solver, int* match_out);
 
 /* Objectron box metrics, float64 (added without an ABI change: new entry points only).  Boxes are the evaluator's 9 x 3
