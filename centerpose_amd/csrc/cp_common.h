@@ -206,6 +206,21 @@ struct ConvParams {
     const float* up_t;
     const float* up_wt;
     int up_ld, up_f;
+    // The 1x1 projection of a DLA level entry (Tree.project: conv1x1 + BatchNorm, no activation) computed by the 3x3 launch that
+    // would otherwise read it back as `res` (halo16.hip, cp_halo16_project_supported): after its own K loop the workgroup runs the
+    // pj_c-deep product of its 8 x 16 pixels of pj_src into a second accumulator set -- pw16.hip's operands, K order and term
+    // order, so the value is the one the stand-alone launch stores -- and the epilogue adds acc2 * pj_scale * 2^-e + pj_shift
+    // where it adds `res`.  The projected tensor never exists.  pj_src: NHWC [B, H, W, pj_c] at output resolution, pj_c a
+    // multiple of 32; pj_amax: its |max| slot (nullptr: used as is); pj_w_*: the projection's weights in fragment order
+    // (cp_launch_frag16_repack), CoutPad rows of pj_c; pj_scale (already times 2^-e_w) / pj_shift: [CoutPad] or nullptr.
+    // pj_src == nullptr: a plain launch.  `res` must be nullptr with it.
+    const float* pj_src;
+    int pj_c;
+    const unsigned* pj_amax;
+    const void* pj_w_hi;
+    const void* pj_w_lo;
+    const float* pj_scale;
+    const float* pj_shift;
 };
 
 int cp_launch_conv(const ConvParams& p, hipStream_t stream);
@@ -227,6 +242,7 @@ const char* cp_conv_variant_name(int v);
 bool cp_conv16_supported(const ConvParams& p);
 int cp_launch_conv16(const ConvParams& p, hipStream_t stream);
 int cp_conv16_variant(const ConvParams& p);
+bool cp_conv16_project_supported(const ConvParams& p);  // ConvParams::pj_src: the launch lands on a kernel that computes it
 // halo-resident 3x3 / stride-1 convolution (halo16.hip): eligibility and launch (bn = N tile 32 / 64 / 128)
 bool cp_halo16_supported(const ConvParams& p);
 bool cp_halo16_fused_head_supported(const ConvParams& p);
@@ -234,6 +250,7 @@ int cp_launch_halo16_fused_head(const ConvParams& p, hipStream_t stream);
 bool cp_halo16_gru_supported(const ConvParams& p);
 int cp_launch_halo16_gru(const ConvParams& p, hipStream_t stream);
 int cp_launch_halo16(const ConvParams& p, int bn, hipStream_t stream);
+bool cp_halo16_project_supported(const ConvParams& p, int bn);  // ... with ConvParams::pj_src (the 64- and 128-wide N tiles)
 // strm16.hip: 64 -> <= 32 channel 3x3 / stride-1 layers (DCN offset / mask convolutions) as wave-private row streams, weights in LDS
 bool cp_strm16_supported(const ConvParams& p);
 int cp_strm16_jobs(const ConvParams& p);

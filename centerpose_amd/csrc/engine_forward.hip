@@ -382,8 +382,9 @@ struct Fwd {
     // Would the DCN `d` on a C x H x W input, asked to add the up-sampling by f of a tensor of t_c channels, run on the kernel that
     // can (dcn16t's UPADD instance)?  The answer of conv() below for the same launch, from the shapes alone: a dry run and the
     // real pass decide alike.
-    bool upadd_fusable(const DeformW& d, int C, int H, int W, int t_c, int f) {
-        if (m->precision != CP_PREC_F16X3 || m->dry_no_upadd) return false;
+    // (boundary: the site between two IDAUps, ida(): IdaNext -- the work-space query has a form that keeps only that one)
+    bool upadd_fusable(const DeformW& d, int C, int H, int W, int t_c, int f, bool boundary = false) {
+        if (m->precision != CP_PREC_F16X3 || (m->dry_no_upadd && !(boundary && m->dry_boundary_upadd))) return false;
         const float* const some = (const float*)0x1000;  // (placeholders: only null / non-null is looked at)
         ConvParams p = conv_params(B, H, W, &some, &C, 1, d.main, 1, 1, CP_ACT_RELU);
         if (p.Cin != d.main.CinP) return false;
@@ -399,9 +400,46 @@ struct Fwd {
         return p.splitk == 1 && cp_conv16_variant(p) == CP_VARIANT_DCN16T && cp_dcn16t_upadd_supported(p);
     }
 
+    // A level entry's 1x1 projection (Tree.project) computed by the block's conv2, which would otherwise read it back as its
+    // residual (halo16.hip, ConvParams::pj_src): the projected tensor and its launch do not exist
+    struct ProjFuse {
+        const Tensor* bottom;
+        const ConvW* w;  // <p>.project
+    };
+    // Would conv2 `w2` of the entry block at `p`, on a C x H x W input, run on a kernel that can take the projection `wp` of a
+    // `cb`-channel tensor as its residual -- and would that projection, launched on its own, be pw16.hip's, whose arithmetic the
+    // fused form reproduces bit for bit?  From the shapes and switches alone: a dry run and the real pass decide alike.  float32,
+    // split-K and 64 x 64-tile launches, shapes halo16 refuses, the switches that move either layer to another kernel and a tap on
+    // any entry's `.project` all keep the plain sequence (a tap unfuses every entry, not only its own: the work-space query then
+    // has two forms to run, all entries fused where they can be or none).
+    bool project_fusable(const std::string& p, const ConvW& wp, const ConvW& w2, int cb, int C, int H, int W) {
+        if (m->precision != CP_PREC_F16X3 || m->dry_no_project) return false;
+        if (m->tap_name && std::strstr(m->tap_name, ".project") != nullptr) return false;  // (every entry: two forms, as for .node_)
+        if (g_dbg & (CP_SEL_PW16_FRAG_A | CP_SEL_PW16_NEVER)) return false;  // (the projection's kernel asked for by name)
+        if (wp.CoutPad != w2.CoutPad || wp.Cout != w2.Cout || wp.Kpad16 != cb || !wp.w16f_hi || !wp.w16f_lo) return false;
+        const float* const some = (const float*)0x1000;  // (placeholders: only null / non-null is looked at)
+        const unsigned* no_amax = nullptr;
+        ConvParams q = conv_params(B, H, W, &some, &cb, 1, wp, 1, 0, CP_ACT_NONE);  // the projection on its own
+        if (q.Cin != wp.CinP || !conv_params_f16(q, wp, &no_amax, true)) return false;
+        q.store = CP_STORE_NHWC;
+        q.ldo = wp.Cout;
+        q.splitk = plan_split(q, true, wp);
+        const int qv = cp_conv16_variant(q);
+        if (q.splitk != 1 || (qv != CP_VARIANT_PW16 && qv != CP_VARIANT_PW16 + 1)) return false;
+        ConvParams c = conv_params(B, H, W, &some, &C, 1, w2, 1, 1, CP_ACT_RELU);
+        if (c.Cin != w2.CinP || !conv_params_f16(c, w2, &no_amax, true)) return false;
+        c.store = CP_STORE_NHWC;
+        c.ldo = w2.Cout;
+        c.pj_src = some;
+        c.pj_c = cb;
+        c.pj_w_hi = c.pj_w_lo = some;
+        c.splitk = plan_split(c, true, w2);
+        return c.splitk == 1 && cp_conv16_project_supported(c);
+    }
+
     Tensor conv(const ConvW& w, const std::vector<const Tensor*>& srcs, int stride, int pad, int act,
                 const Tensor* res = nullptr, const Tensor* offmask = nullptr, int act_from = 0,
-                float* out_nchw = nullptr, int out_ld = 0, const UpFuse* up = nullptr) {
+                float* out_nchw = nullptr, int out_ld = 0, const UpFuse* up = nullptr, const ProjFuse* pj = nullptr) {
         const Tensor& x0 = *srcs[0];
         const int nsrc = (int)srcs.size();
         const float* src[CP_MAX_SRC];
@@ -469,6 +507,15 @@ struct Fwd {
             p.up_f = up->f;
             // (the caller asked upadd_fusable() first; cp_launch_conv16 refuses a launch that lands on a kernel without the epilogue)
         }
+        if (pj) {  // (the caller asked project_fusable() first; as above)
+            p.pj_src = pj->bottom->ptr();
+            p.pj_c = pj->bottom->C;
+            p.pj_amax = pj->bottom->amax;
+            p.pj_w_hi = pj->w->w16f_hi;
+            p.pj_w_lo = pj->w->w16f_lo;
+            p.pj_scale = pj->w->scale16;
+            p.pj_shift = pj->w->shift;
+        }
         auto launch = [&]() -> int {
             int rc = use16 ? cp_launch_conv16(p, s) : cp_launch_conv(p, s);
             if (rc == CP_OK && p.splitk > 1) rc = cp_launch_splitk_epilogue(p, s);
@@ -481,11 +528,13 @@ struct Fwd {
                          : (w.KH == 1 && w.KW == 1) ? CP_ROLE_CONV1X1 : CP_ROLE_CONV;
                 const double M = (double)B * p.Ho * p.Wo;
                 const int cin_real = w.Cin;  // un-padded input channels
-                r.flops = 2.0 * M * w.Cout * (double)(w.KH * w.KW * cin_real);
-                // algorithmic bytes: input once + output once + weights (+ offsets/mask for DCN, + residual)
+                r.flops = 2.0 * M * w.Cout * (double)(w.KH * w.KW * cin_real + (pj ? pj->w->Cin : 0));
+                // algorithmic bytes: input once + output once + weights (+ offsets/mask for DCN, + residual, or the projection's
+                // input and weights in its place)
                 r.bytes = 4.0 * ((double)B * x0.H * x0.W * cin_real + M * w.Cout +
                                  (double)w.KH * w.KW * cin_real * w.Cout + (offmask ? M * 27 : 0.0) +
-                                 (res ? M * w.Cout : 0.0) + (up ? (double)B * up->t->H * up->t->W * w.Cout : 0.0));
+                                 (res ? M * w.Cout : 0.0) + (up ? (double)B * up->t->H * up->t->W * w.Cout : 0.0) +
+                                 (pj ? (M + w.Cout) * (double)pj->w->Cin : 0.0));
                 r.M = (int)M; r.N = w.Cout; r.K = w.KH * w.KW * cin_real; r.kh = w.KH; r.stride = stride;
             }, launch);
         gn_stats_out = nullptr;
@@ -505,9 +554,11 @@ struct Fwd {
         return o;
     }
 
-    Tensor basic_block(const std::string& p, const Tensor& x, int stride, const Tensor& residual) {
+    // residual == nullptr: pj's projection, computed by conv2 itself
+    Tensor basic_block(const std::string& p, const Tensor& x, int stride, const Tensor* residual, const ProjFuse* pj = nullptr) {
         Tensor t = conv(cw(p + ".conv1"), {&x}, stride, 1, CP_ACT_RELU);
-        Tensor o = conv(cw(p + ".conv2"), {&t}, 1, 1, CP_ACT_RELU, &residual);
+        tap(p + ".conv1", t);
+        Tensor o = conv(cw(p + ".conv2"), {&t}, 1, 1, CP_ACT_RELU, residual, nullptr, 0, nullptr, 0, nullptr, pj);
         tap(p, o);
         return o;
     }
@@ -527,14 +578,23 @@ struct Fwd {
         }
         Tensor proj;
         const Tensor* residual = bottom;
+        ProjFuse pj = {bottom, nullptr};
         if (cin != cout) {
-            proj = conv(cw(p + ".project"), {bottom}, 1, 0, CP_ACT_NONE);
-            residual = &proj;
+            const ConvW& wp = cw(p + ".project");
+            const ConvW& w2 = cw(p + ".tree1.conv2");
+            if (project_fusable(p, wp, w2, bottom->C, w2.CinP, bottom->H, bottom->W)) {
+                pj.w = &wp;  // conv2 of the first block computes the projection of its own pixels: no tensor, no launch
+                residual = nullptr;
+            } else {
+                proj = conv(wp, {bottom}, 1, 0, CP_ACT_NONE);
+                tap(p + ".project", proj);
+                residual = &proj;
+            }
         }
         if (level_root) children.insert(children.begin(), bottom);
-        Tensor x1 = basic_block(p + ".tree1", x, stride, *residual);
+        Tensor x1 = basic_block(p + ".tree1", x, stride, residual, pj.w ? &pj : nullptr);
         proj = Tensor();
-        Tensor x2 = basic_block(p + ".tree2", x1, 1, x1);
+        Tensor x2 = basic_block(p + ".tree2", x1, 1, &x1);
         std::vector<const Tensor*> srcs = {&x2, &x1};
         for (auto* c : children) srcs.push_back(c);
         Tensor o = conv(cw(p + ".root"), srcs, 1, 0, CP_ACT_RELU);
@@ -570,10 +630,21 @@ struct Fwd {
     // own output is never written and the upsample_add launch of iteration k + 1 (a read of `add`, a write of u) does not exist.
     // Where the node's launch is not dcn16t's (other shapes, small launches, float32, CP_SEL_DCN16T_NEVER) or a tap names a node,
     // the sequence is the plain one.  Both forms round identically (upadd_common.h).
-    void ida(const std::string& p, std::vector<Tensor>& layers, int startp, int endp, const std::vector<int>& up_f,
-             bool node_dead = false) {
+    // The same holds one IDAUp further out (IdaNext): where the caller reads this IDAUp's last node only as the `add` of the next
+    // IDAUp's first iteration, that IDAUp's proj_1 -- whose input is final by now -- is launched before the last node here, the node
+    // stores u_1 of the next IDAUp, and ida() returns it for the next call's `u_first`.  This site keeps the plain sequence only
+    // where the tap names that very node (or its offset / mask map): a tap on another node leaves its output unread as before, so
+    // a pass with such a tap differs from the default pass in the sites inside the IDAUps alone.
+    struct IdaNext {
+        std::string p;        // the next IDAUp
+        const Tensor* layer;  // its layers[1] (read by its proj_1)
+        int f;                // its first up-sampling factor
+    };
+    Tensor ida(const std::string& p, std::vector<Tensor>& layers, int startp, int endp, const std::vector<int>& up_f,
+               bool node_dead = false, const IdaNext* next = nullptr, Tensor u_first = Tensor()) {
         const bool tap_on_node = m->tap_name && std::strstr(m->tap_name, ".node_") != nullptr;
-        Tensor u_next;  // u of the next iteration, written by this iteration's node
+        Tensor u_next = u_first;  // u of the next iteration, written by this iteration's node (the first: by the IDAUp before)
+        u_first = Tensor();
         for (int i = startp + 1; i < endp; ++i) {
             const std::string k = std::to_string(i - startp);
             Tensor u = u_next;
@@ -592,10 +663,18 @@ struct Fwd {
                 const UpFuse up = {&t, m->ups_t.at(p + ".up_" + kn), fn};
                 u_next = deform(p + ".node_" + k, u, &up);
                 layers[i] = Tensor();  // (dead by the caller's word)
+            } else if (next && i + 1 == endp && m->ups_t.count(next->p + ".up_1") &&
+                       !(m->tap_name && std::strncmp(m->tap_name, (p + ".node_" + k).c_str(), (p + ".node_" + k).size()) == 0) &&
+                       upadd_fusable(node, u.C, u.H, u.W, m->deforms.at(next->p + ".proj_1").main.Cout, next->f, true)) {
+                Tensor t = deform(next->p + ".proj_1", *next->layer);
+                const UpFuse up = {&t, m->ups_t.at(next->p + ".up_1"), next->f};
+                u_next = deform(p + ".node_" + k, u, &up);
+                layers[i] = Tensor();  // (read by the next IDAUp's first iteration only: the caller's word)
             } else {
                 layers[i] = deform(p + ".node_" + k, u);
             }
         }
+        return u_next;  // valid only where the last node took `next`
     }
 
     // the network's first layers through lowc.hip (f16x3 mode only); returns an invalid Tensor when not applicable
@@ -872,13 +951,17 @@ struct Fwd {
         Tensor o2 = L[5];  // 256 @ 1/8... (after ida_0: 256 ch at L4 resolution)
         ida("dla_up.ida_1", L, 3, 6, {1, 2, 2});
         Tensor o1 = L[5];
-        ida("dla_up.ida_2", L, 2, 6, {1, 2, 2, 2}, true);  // (only L[5] is read below)
+        // (only L[5] is read below, and only as the `add` of ida_up's first iteration: where the last node can, it stores that
+        // iteration's u instead and o0 does not exist)
+        const IdaNext to_ida_up = {"ida_up", &o1, 2};
+        Tensor u1 = ida("dla_up.ida_2", L, 2, 6, {1, 2, 2, 2}, true, &to_ida_up);
         Tensor o0 = L[5];
         for (auto& t : L) t = Tensor();
         // DLASeg.forward (:531-536): ida_up over [o0, o1, o2]
         std::vector<Tensor> y = {o0, o1, o2};
         o0 = o1 = o2 = Tensor();
-        ida("ida_up", y, 0, 3, {1, 2, 4}, true);  // (only y[2] is read below)
+        ida("ida_up", y, 0, 3, {1, 2, 4}, true, nullptr, u1);  // (only y[2] is read below)
+        u1 = Tensor();
         Tensor feat = y[2];
         y.clear();
         tap("feat", feat);

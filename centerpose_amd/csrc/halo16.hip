@@ -44,6 +44,92 @@ constexpr int PROW = CK + 8;                                              // hal
 // combinations of a tile needed its own ~3 VALU of address arithmetic, which the compiler hoists in front of every tile's K loop:
 // 270 of the ~850 non-MFMA VALU per hidden tile of the fused heads (SQ_INSTS_VALU, profiles/r05_pmc_sq_counters.txt).
 
+// The level entry's 1x1 projection of this workgroup's 8 x 16 pixels into a second accumulator set (ConvParams::pj_src), run
+// between the K loop and the epilogue.  It is pw16.hip's product, operand for operand: K steps of 16 channels in channel order,
+// a lane's A fragment = 8 consecutive channels of its pixel straight from global memory (32 bytes, two loads: pw16_kernel's
+// form -- the tensor is the pooled one at output resolution, a sixth of the patch the main loop staged, and mostly in L2),
+// scaled by the tensor's own power-of-two pre-scale and split to hi / lo in registers; B fragments from the projection's
+// fragment-ordered weights; per accumulator lo*hi, hi*lo, hi*hi.  An MFMA output element depends on its own A row and B column
+// only, so every acc2 element is bit for bit the accumulator of the stand-alone launch, whatever tile it sat in there.
+// One K step ahead in two register sets (G is even: channels come in multiples of 32).
+template <int MT, int NT, int WN>
+__device__ __forceinline__ void halo_project(const ConvParams& p, Frag<32>::acc_t (&acc2)[MT][NT], int b, int ty0, int tx0, int tn,
+                                             int wm, int wn, int lane, float* pinv) {
+    typedef Frag<32> F;
+    float pfwd = 1.f;
+    *pinv = 1.f;
+    if (p.pj_amax) cp_amax_to_scale(cp_amax_read(p.pj_amax), &pfwd, pinv);
+    const int lcol = lane & 31, half = lane >> 5;
+    const int G = p.pj_c >> 4;
+    const __amdgpu_buffer_rsrc_t r_a = make_rsrc(p.pj_src, (unsigned)p.B * p.H * p.W * (unsigned)p.pj_c * 4u);
+    const unsigned w_bytes = (unsigned)((size_t)p.CoutPad * p.pj_c * 2);
+    const __amdgpu_buffer_rsrc_t r_wh = make_rsrc(p.pj_w_hi, w_bytes), r_wl = make_rsrc(p.pj_w_lo, w_bytes);
+    unsigned va[MT], vb[NT];
+#pragma unroll
+    for (int i = 0; i < MT; ++i) {
+        const int m = wm * (MT * 32) + i * 32 + lcol;  // tile row -> pixel (m / 16, m % 16) of the patch
+        va[i] = (unsigned)(((b * p.H + ty0 + (m >> 4)) * p.W + tx0 + (m & 15)) * p.pj_c + half * 8) * 4u;
+    }
+#pragma unroll
+    for (int j = 0; j < NT; ++j) vb[j] = (unsigned)((((tn * (NT * WN) + wn * NT + j) * G) * 64 + lane) * 16);
+    u32x4 ra[2][MT][2], wh[2][NT], wl[2][NT];
+    auto issue = [&](int set, int g) {
+        if (g >= G) return;
+#pragma unroll
+        for (int i = 0; i < MT; ++i) {
+            ra[set][i][0] = __builtin_amdgcn_raw_buffer_load_b128(r_a, (int)va[i], g * 64, 0);
+            ra[set][i][1] = __builtin_amdgcn_raw_buffer_load_b128(r_a, (int)va[i], g * 64 + 16, 0);
+        }
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+            wh[set][j] = __builtin_amdgcn_raw_buffer_load_b128(r_wh, (int)vb[j], g * 1024, 0);
+            wl[set][j] = __builtin_amdgcn_raw_buffer_load_b128(r_wl, (int)vb[j], g * 1024, 0);
+        }
+    };
+    auto step = [&](int set) {
+        h8 ah[MT], al[MT];
+#pragma unroll
+        for (int i = 0; i < MT; ++i) {
+            const u32x4 x0 = ra[set][i][0], x1 = ra[set][i][1];
+            const Split2 s0 = split2(__uint_as_float(x0.x) * pfwd, __uint_as_float(x0.y) * pfwd);
+            const Split2 s1 = split2(__uint_as_float(x0.z) * pfwd, __uint_as_float(x0.w) * pfwd);
+            const Split2 s2 = split2(__uint_as_float(x1.x) * pfwd, __uint_as_float(x1.y) * pfwd);
+            const Split2 s3 = split2(__uint_as_float(x1.z) * pfwd, __uint_as_float(x1.w) * pfwd);
+            const u32x4 hv = {s0.hi, s1.hi, s2.hi, s3.hi}, lv = {s0.lo, s1.lo, s2.lo, s3.lo};
+            ah[i] = *reinterpret_cast<const h8*>(&hv);
+            al[i] = *reinterpret_cast<const h8*>(&lv);
+        }
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int j = 0; j < NT; ++j)
+                acc2[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], *reinterpret_cast<const h8*>(&wh[set][j]), acc2[i][j], 0, 0, 0);
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int j = 0; j < NT; ++j)
+                acc2[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], *reinterpret_cast<const h8*>(&wl[set][j]), acc2[i][j], 0, 0, 0);
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int j = 0; j < NT; ++j)
+                acc2[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], *reinterpret_cast<const h8*>(&wh[set][j]), acc2[i][j], 0, 0, 0);
+    };
+    issue(0, 0);
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int j = 0; j < NT; ++j)
+#pragma unroll
+            for (int r = 0; r < F::NACC; ++r) acc2[i][j][r] = 0.f;
+    for (int g = 0; g < G; g += 2) {
+        issue(1, g + 1);
+        step(0);
+        issue(0, g + 2);
+        step(1);
+    }
+}
+
 // BDIRECT: the weight fragments of the 32-wide N tile come from global memory / L2 straight into the MFMA operand
 // registers, two K tiles ahead, out of the fragment-ordered copy of the weights (ConvParams::w16f_*, one coalesced 1 KB
 // load per fragment), so that the K loop has no barrier inside a chunk: with N = 32 a K tile is only 6 MFMAs per wave,
@@ -52,10 +138,12 @@ constexpr int PROW = CK + 8;                                              // hal
 // profiles/r02_halo_ab.txt.)
 // EPI: 0 = plain epilogue (patch16_common.h); 1 = fused prediction head (igemm16.hip: FUSE -- transposed main product,
 // bias + ReLU, second MFMA product with the 1x1 weights, slices to fuse_out); 2 = fused ConvGRU gates (igemm16.hip: GRU).
-template <int MT, int NT, int WM, int WN, bool BDIRECT = false, int EPI = 0, int FT = 0>
+// PJ: the plain epilogue with the level entry's 1x1 projection as the residual (halo_project above)
+template <int MT, int NT, int WM, int WN, bool BDIRECT = false, int EPI = 0, int FT = 0, bool PJ = false>
 __global__ __launch_bounds__(256, (BDIRECT && EPI == 0 && MT * NT <= 2) ? 3 : 2) void halo16_kernel(const ConvParams p, const int tiles_m, const int tiles_n) {
     typedef Frag<32> F;
     typedef F::acc_t acc_t;
+    static_assert(!PJ || (EPI == 0 && BDIRECT && MT == 2), "projection: the plain 64- and 128-wide tiles");
     static_assert(WM * WN == 4 && 32 * MT * WM == TH * TW, "4 waves over a 128-pixel patch");
     static_assert(FT == 0 || EPI == 1, "FT: hidden tiles a fused-head workgroup walks (ConvParams::fuse_final), 0 = one tile, slabs");
     static_assert(EPI != 1 || (MT == 2 && NT == 2 && WM == 2 && WN == 2), "fused head: 128 x 128 tiles");
@@ -639,16 +727,23 @@ __global__ __launch_bounds__(256, (BDIRECT && EPI == 0 && MT * NT <= 2) ? 3 : 2)
         if (p.out_amax) cp_amax_commit(p.out_amax, amax);
         return;
     }
-    patch_epilogue<MT, NT, WM, WN>(p, acc, b, ty0, tx0, tn, wm, wn, lane_e, ainv);
+    if constexpr (PJ) {
+        acc_t acc2[MT][NT];
+        float pinv;
+        halo_project<MT, NT, WN>(p, acc2, b, ty0, tx0, tn, wm, wn, lane_e, &pinv);
+        patch_epilogue<MT, NT, WM, WN, false, true>(p, acc, b, ty0, tx0, tn, wm, wn, lane_e, ainv, acc2, pinv);
+    } else {
+        patch_epilogue<MT, NT, WM, WN>(p, acc, b, ty0, tx0, tn, wm, wn, lane_e, ainv);
+    }
     HALO_STAMP(21);  // epilogue done (stores acknowledged)
 }
 
-template <int MT, int NT, int WM, int WN, bool BDIRECT = false, int EPI = 0, int FT = 0>
+template <int MT, int NT, int WM, int WN, bool BDIRECT = false, int EPI = 0, int FT = 0, bool PJ = false>
 int launch_halo(const ConvParams& p, hipStream_t stream) {
     constexpr int BN = 32 * NT * WN;
     // (fused heads that finish in the kernel: one workgroup per patch and head, ConvParams::fuse_final)
     const int tiles_m = p.B * (p.H / TH) * (p.W / TW), tiles_n = FT ? (p.fuse_final == 2 ? 1 : p.fuse_ngroups) : p.CoutPad / BN;
-    hipLaunchKernelGGL((halo16_kernel<MT, NT, WM, WN, BDIRECT, EPI, FT>), dim3(tiles_m * tiles_n), dim3(256), 0, stream, p,
+    hipLaunchKernelGGL((halo16_kernel<MT, NT, WM, WN, BDIRECT, EPI, FT, PJ>), dim3(tiles_m * tiles_n), dim3(256), 0, stream, p,
                        tiles_m, tiles_n);
     return hipGetLastError() == hipSuccess ? CP_OK : CP_ERR_LAUNCH;
 }
@@ -662,9 +757,22 @@ bool cp_halo16_supported(const ConvParams& p) {
            (size_t)p.B * p.H * p.W * p.Cin * 4 < (size_t)0xf0000000u && (size_t)p.B * p.H * p.W * p.ldo * 4 < (size_t)0xf0000000u;
 }
 
+// ... with the level entry's 1x1 projection as the residual (ConvParams::pj_src): the 64- and 128-wide tiles with their weight
+// fragments from L2, no other residual, no GroupNorm statistics, 32-bit byte offsets into the projection's operands
+bool cp_halo16_project_supported(const ConvParams& p, int bn) {
+    return cp_halo16_supported(p) && (bn == 64 || bn == 128) && p.CoutPad % bn == 0 && p.w16f_hi && p.w16f_lo &&
+           !(p.dbg & CP_SEL_HALO_LDS_WEIGHTS) && p.pj_src && p.pj_w_hi && p.pj_w_lo && !p.res && !p.gn_stats && p.pj_c >= 32 &&
+           p.pj_c % 32 == 0 && (size_t)p.B * p.H * p.W * p.pj_c * 4 < (size_t)0xf0000000u &&
+           (size_t)p.CoutPad * p.pj_c * 2 < (size_t)0x7fffffff;
+}
+
 // bn: N tile the weights were padded for (32 / 64 / 128)
 int cp_launch_halo16(const ConvParams& p, int bn, hipStream_t stream) {
     if (!cp_halo16_supported(p) || p.CoutPad % bn != 0) return CP_ERR_INVALID;
+    if (p.pj_src) {
+        if (!cp_halo16_project_supported(p, bn)) return CP_ERR_INVALID;
+        return bn == 128 ? launch_halo<2, 2, 2, 2, true, 0, 0, true>(p, stream) : launch_halo<2, 1, 2, 2, true, 0, 0, true>(p, stream);
+    }
     // weight fragments straight from the fragment-ordered copy when the layer has one (CP_SEL_HALO_LDS_WEIGHTS: the LDS-staged
     // weight tile instead, A/B runs)
     const bool direct = p.w16f_hi && p.w16f_lo && !(p.dbg & CP_SEL_HALO_LDS_WEIGHTS);

@@ -712,11 +712,21 @@ bool cp_conv16_supported(const ConvParams& p) {
     return true;
 }
 
+// would cp_launch_conv16 run this launch with ConvParams::pj_src set?  (the engine asks before it decides not to launch the
+// projection on its own)
+bool cp_conv16_project_supported(const ConvParams& p) {
+    if (!cp_conv16_supported(p) || p.offmask || p.gn_in_a || p.up_t) return false;
+    const int bn = conv16_tile_n(p);
+    return !(bn == 64 && p.tile_m == 64) && halo16_wanted(p, bn) && cp_halo16_project_supported(p, bn);
+}
+
 int cp_launch_conv16(const ConvParams& p, hipStream_t stream) {
     if (!cp_conv16_supported(p)) return CP_ERR_INVALID;
     // the up-sample + add epilogue (ConvParams::up_t) exists in dcn16t only: a launch that would go elsewhere is an error
     if (p.up_t && !(p.offmask && dcn16t_wanted(p) && cp_dcn16t_upadd_supported(p))) return CP_ERR_INVALID;
     const int bn = conv16_tile_n(p);
+    // ... and the 1x1 projection as the residual (ConvParams::pj_src) in halo16's 64- and 128-wide tiles only
+    if (p.pj_src) return cp_conv16_project_supported(p) ? cp_launch_halo16(p, bn, stream) : CP_ERR_INVALID;
     const bool cat = p.nsrc > 1;
     if (p.gn_in_a) {
         const int M = p.B * p.Ho * p.Wo;

@@ -15,9 +15,13 @@ constexpr int PATCH_TH = 8, PATCH_TW = 16;
 __device__ __forceinline__ int patch_perm_row(int m) { return (0x96 >> (m >> 2)) & 1; }
 __device__ __forceinline__ int patch_perm_col(int m) { return 4 * (m >> 3) + (m & 3); }
 
-template <int MT, int NT, int WM, int WN, bool PERM = false>
+// PROJ: a second accumulator set holds the level entry's 1x1 projection of the same pixels (ConvParams::pj_src, halo16.hip): its
+// value acc2 * pj_scale * 2^-e_p + pj_shift -- the expression above, as the stand-alone 1x1 launch evaluates and stores it,
+// rounded to float32 once -- is added where `res` is added.
+template <int MT, int NT, int WM, int WN, bool PERM = false, bool PROJ = false>
 __device__ __forceinline__ void patch_epilogue(const ConvParams& p, Frag<32>::acc_t (&acc)[MT][NT], int b, int ty0, int tx0,
-                                               int tn, int wm, int wn, int lane, float ainv) {
+                                               int tn, int wm, int wn, int lane, float ainv,
+                                               const Frag<32>::acc_t (*acc2)[NT] = nullptr, float pinv = 1.f) {
     typedef Frag<32> F;
     constexpr int TW = PATCH_TW;
     constexpr int BN = 32 * NT * WN;
@@ -33,6 +37,11 @@ __device__ __forceinline__ void patch_epilogue(const ConvParams& p, Frag<32>::ac
         const float sh = p.shift ? p.shift[n] : 0.f;
         const bool n_ok = n < p.Cout;
         const bool sig_lane = act == CP_ACT_SIGMOID || (act == CP_ACT_SIGMOID_FROM && n >= p.act_from);
+        float psc = 0.f, psh = 0.f;
+        if constexpr (PROJ) {
+            psc = (p.pj_scale ? p.pj_scale[n] : 1.f) * pinv;
+            psh = p.pj_shift ? p.pj_shift[n] : 0.f;
+        }
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
             // fragment = tile rows m0 .. m0 + 31 = patch rows y, y + 1 (16 pixels each)
@@ -53,6 +62,14 @@ __device__ __forceinline__ void patch_epilogue(const ConvParams& p, Frag<32>::ac
                                         : (((r >> 3) * p.W) + 8 * ((r >> 2) & 1) + (r & 3)) * p.res_ld * 4;
                     const bool flip = PERM && ((0x6 >> (r >> 2)) & 1);
                     v[r] += __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rr, (int)(flip ? vr1 : vr), so, 0));
+                }
+            }
+            if constexpr (PROJ) {
+#pragma unroll
+                for (int r = 0; r < F::NACC; ++r) {
+                    float pv = acc2[i][j][r] * psc + psh;
+                    asm volatile("" : "+v"(pv));  // (the stored tensor's value: not to be contracted with the add below)
+                    v[r] += pv;
                 }
             }
             if (act == CP_ACT_RELU) {

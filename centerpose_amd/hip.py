@@ -119,6 +119,7 @@ def lib():
     _sig(L.cp_model_finalize, c_int, c_void_p)
     _sig(L.cp_model_destroy, None, c_void_p)
     _sig(L.cp_model_workspace_bytes, c_size_t, c_void_p, c_int, c_int, c_int)
+    _sig(L.cp_model_workspace_used, c_size_t, c_void_p)
     _sig(L.cp_model_forward, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
          ctypes.POINTER(c_void_p), c_int, c_void_p, c_size_t)
     _sig(L.cp_model_forward_tap, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
@@ -223,7 +224,7 @@ def linear_assignment(cost, solver=1):
 def exported_symbols():
     """Names every declaration in include/centerpose_hip.h (+ the test hook of centerpose_hip_testing.h) must resolve to (used by CPU tests)."""
     return ["cp_version", "cp_last_error", "cp_dcnv2_workspace_bytes", "cp_dcnv2_forward", "cp_model_create",
-            "cp_model_set_param", "cp_model_finalize", "cp_model_destroy", "cp_model_workspace_bytes",
+            "cp_model_set_param", "cp_model_finalize", "cp_model_destroy", "cp_model_workspace_bytes", "cp_model_workspace_used",
             "cp_model_forward", "cp_model_forward_tap", "cp_conv2d_workspace_bytes", "cp_conv2d_nhwc",
             "cp_decode_workspace_bytes", "cp_decode", "cp_pnp_workspace_bytes", "cp_pnp_solve", "cp_model_profile", "cp_model_profile_read",
             "cp_kernel_variant_name", "cp_set_default_precision", "cp_model_set_precision", "cp_model_detect_workspace_bytes", "cp_model_detect", "cp_set_debug", "cp_preprocess", "cp_preprocess_batch", "cp_postprocess_workspace_bytes", "cp_postprocess", "cp_render_gaussians",
@@ -1461,6 +1462,10 @@ class HipModel(object):
             raise RuntimeError("cp_model_workspace_bytes failed: " + lib().cp_last_error().decode())
         return n
 
+    def workspace_used(self):
+        """Bytes of the work space the last pass reached (cp_model_workspace_used): at most workspace_bytes() of its shape."""
+        return int(lib().cp_model_workspace_used(self._h))
+
     def _workspace(self, B, H, W, device):
         key = (B, H, W, str(device))
         if self._ws_key != key:
@@ -1474,7 +1479,10 @@ class HipModel(object):
         """images [B,3,H,W] on the HIP device -> OrderedDict head -> [B,classes,H/4,W/4].
         With ``tap`` also returns the named intermediate activation as NCHW.  A tap changes the launch sequence: the fused heads
         are off, and a tap whose name contains ``.node_`` (an IDAUp node or its offset / mask map) runs every IDAUp with its
-        stand-alone up-sample + add launches, so a profile taken with such a tap is that of the unfused sequence."""
+        stand-alone up-sample + add launches, so a profile taken with such a tap is that of the unfused sequence (the one site
+        between two IDAUps, dla_up's last node storing ida_up's first sum, is unfused only by a tap on that node).  Likewise a tap on
+        any level entry's ``<entry>.project`` runs every entry's projection as a launch of its own (it is otherwise computed inside the
+        block's conv2 and never stored)."""
         L = lib()
         images = _dev(images)
         B, _, H, W = images.shape

@@ -14,7 +14,10 @@ extern "C" {
  * Every combination computes the layer correctly (to the summation-order round-off the tests state), except that
  * CP_SEL_NO_PRESCALE is correct only for inputs inside binary16's range (it exists for the range-safety tests).
  * cp_set_debug returns CP_ERR_INVALID, and keeps the current selection, when a bit outside CP_SEL_ALL is set.  Bit 11
- * (2048, once "alternative DCN wave counts") is unused and refused. */
+ * (2048, once "alternative DCN wave counts") is unused and refused.
+ * CP_SEL_PW16_FRAG_A and CP_SEL_PW16_NEVER also change the launch SEQUENCE of DLA's level entries: the entry's 1x1 projection,
+ * by default computed inside the first block's conv2 with pw16s_kernel's arithmetic and never stored, is asked for on another
+ * kernel and therefore runs as a launch of its own (same values; the parity tests' unfused reference). */
 #define CP_SEL_HEADS_SLABS 0x00000001          /* grouped fused heads write slabs + a reduction launch (no fuse_final) */
 #define CP_SEL_HEADS_WG_PER_HEAD 0x00000002    /* grouped fused heads: one workgroup per (patch, head), not per patch */
 #define CP_SEL_PW16_FRAG_A 0x00000004          /* 1x1 layers: fragment-shaped A loads (pw16_kernel), not staging rows */
