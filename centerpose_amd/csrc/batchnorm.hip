@@ -4,12 +4,8 @@
 // ReLU chains of pose_dla_dcn.py:40-62 (BasicBlock), pose_dla_dcn.py:150-168 (Root), pose_dla_dcn.py:381 (the DCN's actf) and
 // resnet_dcn.py.  Float32 arithmetic, no atomics, every sum in a fixed order that depends on the shape alone.
 //
-// All five streaming kernels share one thread map (lane_of): the tensor is P = B*H*W pixel rows of C floats; a wave reads 16
-// bytes per lane, so with L = C / 4 lanes per row, CL = min(L, 64) lanes take a row and a wave takes PW = 64 / CL rows at a
-// time (C = 16: 16 rows, one 1 KiB run of whole 128-byte lines; C = 20: 12 rows, 60 of 64 lanes busy); rows wider than a
-// wave (C > 256) are covered by ceil(L / 64) channel passes (blockIdx.y).  A workgroup is four waves on neighbouring rows and
-// owns a slab of rows (blockIdx.x); a lane keeps its four channels for the whole slab, so the per-channel coefficients sit in
-// registers and the sums need no shuffles.
+// All five streaming kernels share one thread map (lane_of, norm_common.h); groupnorm.hip uses the same map and the same
+// per-slab statistics.
 //
 // On the caller's stream:
 //   forward, training    stats_kernel     per slab and channel: mean and M2 = sum (x - mean)^2.  A lane sums d = x - pivot and d^2
@@ -22,111 +18,18 @@
 //   forward              apply_kernel     y, whole lines in and out.
 //   backward             bwd_reduce_kernel / bwd_finalize_kernel   grad_beta = sum g, grad_gamma = sum g * xhat (g gated by y > 0)
 //                        bwd_apply_kernel grad_x (and grad_residual = g when asked) in one pass.
-#include "op_common.h"
-#include "igemm_common.h"
+#include "norm_common.h"
 
 #include <algorithm>
 
 namespace {
-
-struct Lane {
-    bool active;  // this lane holds channels of this pass
-    int c;        // its first channel
-    int k, S;     // it owns the slab's rows k, k + S, ...
-    int CL;       // lanes per row
-};
-
-__device__ __forceinline__ Lane lane_of(int C) {
-    const int L = C >> 2, CL = min(L, 64), PW = 64 / CL;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int pl = lane / CL, cl = lane - pl * CL, cg = blockIdx.y * 64 + cl;
-    Lane ln;
-    ln.active = pl < PW && cg < L;
-    ln.c = 4 * cg;
-    ln.k = w * PW + pl;
-    ln.S = 4 * PW;
-    ln.CL = CL;
-    return ln;
-}
-// index into a 256-entry LDS table of the lane that owns row phase k of the same channels (k < S)
-__device__ __forceinline__ int peer(const Lane& ln, int k) {
-    const int PW = ln.S >> 2, w = k / PW, pl = k - w * PW;
-    return w * 64 + pl * ln.CL + (threadIdx.x & 63) % ln.CL;
-}
-// rows of phase k in a slab of len rows
-__device__ __forceinline__ int rows_of(int len, int k, int S) { return k < len ? (len - k + S - 1) / S : 0; }
-
-__device__ __forceinline__ void st4(float* p, const float (&v)[4]) { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
-__device__ __forceinline__ void un4(const float4 v, float (&o)[4]) { o[0] = v.x, o[1] = v.y, o[2] = v.z, o[3] = v.w; }
 
 // part[slab][0][c] = the slab's mean, part[slab][1][c] = its M2
 __global__ __launch_bounds__(256) void stats_kernel(const float* __restrict__ x, float* __restrict__ part, int P, int C, int slab_px) {
     __shared__ float4 sm[256], sq[256];
     const Lane ln = lane_of(C);
     const int q_beg = blockIdx.x * slab_px, len = min(P - q_beg, slab_px);
-    const int n = ln.active ? rows_of(len, ln.k, ln.S) : 0;
-    float piv[4] = {0.f, 0.f, 0.f, 0.f}, s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
-    if (n > 0) {
-        const float* px = x + (size_t)(q_beg + ln.k) * C + ln.c;
-        const size_t step = (size_t)ln.S * C;
-        un4(ld4(px), piv);
-        auto add = [&](const float4 v4) {
-            float v[4];
-            un4(v4, v);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float d = v[i] - piv[i];
-                s1[i] += d;
-                s2[i] = fmaf(d, d, s2[i]);
-            }
-        };
-        int j = 0;
-        for (; j + 4 <= n; j += 4) {  // four rows requested before the first is used
-            const float4 v0 = ld4(px), v1 = ld4(px + step), v2 = ld4(px + 2 * step), v3 = ld4(px + 3 * step);
-            px += 4 * step;
-            add(v0), add(v1), add(v2), add(v3);
-        }
-        for (; j < n; ++j, px += step) add(ld4(px));
-    }
-    const float rn = n > 0 ? 1.f / (float)n : 0.f;
-    float m[4], q[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        m[i] = fmaf(s1[i], rn, piv[i]);
-        q[i] = fmaxf(s2[i] - s1[i] * s1[i] * rn, 0.f);
-    }
-    sm[threadIdx.x] = make_float4(m[0], m[1], m[2], m[3]);
-    sq[threadIdx.x] = make_float4(q[0], q[1], q[2], q[3]);
-    __syncthreads();
-    if (!ln.active || ln.k != 0) return;
-    // the row phases in order; phase 0 (this lane) is never empty
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int k = 1; k < ln.S; ++k) {
-        const float nk = (float)rows_of(len, k, ln.S);
-        float t[4];
-        un4(sm[peer(ln, k)], t);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[i] = fmaf(nk, t[i] - m[i], acc[i]);
-    }
-    float mean[4], M2[4] = {0.f, 0.f, 0.f, 0.f};
-    const float rl = 1.f / (float)len;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) mean[i] = fmaf(acc[i], rl, m[i]);
-    for (int k = 0; k < ln.S; ++k) {
-        const float nk = (float)rows_of(len, k, ln.S);
-        const int p = peer(ln, k);
-        float t[4], u[4];
-        un4(sm[p], t);
-        un4(sq[p], u);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float d = t[i] - mean[i];
-            M2[i] += fmaf(nk * d, d, u[i]);
-        }
-    }
-    float* out = part + (size_t)blockIdx.x * 2 * C + ln.c;
-    st4(out, mean);
-    st4(out + C, M2);
+    slab_stats(x + (size_t)q_beg * C, len, C, ln, part + (size_t)blockIdx.x * 2 * C, sm, sq);
 }
 
 // The slabs merged per channel, 32 channels per workgroup, in two rounds of two_level_sum: the mean about slab 0's, then M2
@@ -206,10 +109,6 @@ __global__ __launch_bounds__(256) void apply_kernel(const float* __restrict__ x,
     for (; j < n; ++j, off += step) put(off, ld4(x + off), ldr(off));
 }
 
-__device__ __forceinline__ float4 gate4(const float4 g, const float4 y) {
-    return make_float4(y.x > 0.f ? g.x : 0.f, y.y > 0.f ? g.y : 0.f, y.z > 0.f ? g.z : 0.f, y.w > 0.f ? g.w : 0.f);
-}
-
 // part[slab][0][c] = sum g, part[slab][1][c] = sum g * (x - mean) over the slab's rows: rows ascending per lane, then the row
 // phases in order
 __global__ __launch_bounds__(256) void bwd_reduce_kernel(const float* __restrict__ x, const float* __restrict__ y,
@@ -247,27 +146,11 @@ __global__ __launch_bounds__(256) void bwd_reduce_kernel(const float* __restrict
         }
         for (; j < n; ++j, off += step) add(ldg(off), ld4(x + off));
     }
-    sg[threadIdx.x] = make_float4(s1[0], s1[1], s1[2], s1[3]);
-    sx[threadIdx.x] = make_float4(s2[0], s2[1], s2[2], s2[3]);
-    __syncthreads();
-    if (!ln.active || ln.k != 0) return;
-    for (int k = 1; k < ln.S; ++k) {
-        const int p = peer(ln, k);
-        float t[4], u[4];
-        un4(sg[p], t);
-        un4(sx[p], u);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) s1[i] += t[i], s2[i] += u[i];
-    }
+    if (!slab_sum2(s1, s2, ln, sg, sx)) return;
     float* out = part + (size_t)blockIdx.x * 2 * C + ln.c;
     st4(out, s1);
     st4(out + C, s2);
 }
-
-struct Sum2 {
-    float a, b;
-};
-__device__ __forceinline__ Sum2 operator+(const Sum2 x, const Sum2 y) { return {x.a + y.a, x.b + y.b}; }
 
 // sums[0][c] = grad_beta, sums[1][c] = grad_gamma = invstd * sum g (x - mean), both by one two_level_sum over the slabs; the
 // caller's grad_beta / grad_gamma get a copy when given

@@ -520,6 +520,28 @@ size_t cp_batchnorm_ws_bytes(int B, int H, int W, int C);
 int cp_launch_batchnorm_forward(hipStream_t s, const BnFwdArgs& a, void* ws);
 int cp_launch_batchnorm_backward(hipStream_t s, const BnBwdArgs& a, void* ws);
 
+// ---- GroupNorm for training, fused with the ReLU (groupnorm.hip): float32 NHWC, statistics per (image, group) ----
+struct GnFwdArgs {
+    const float *x, *gamma, *beta;  // gamma / beta nullptr: 1 / 0
+    float *y, *mean, *invstd;       // mean / invstd [B][G]
+    int B, H, W, C, G;
+    float eps;
+    int act;
+};
+struct GnBwdArgs {
+    const float *x, *y, *go, *gamma, *mean, *invstd;  // y (the activated output) or nullptr: grad_out is gated by y > 0
+    float *gx, *gg, *gb;                              // each nullptr: not computed
+    int B, H, W, C, G;
+};
+size_t cp_groupnorm_ws_bytes(int B, int H, int W, int C, int G);
+int cp_launch_groupnorm_forward(hipStream_t s, const GnFwdArgs& a, void* ws);
+int cp_launch_groupnorm_backward(hipStream_t s, const GnBwdArgs& a, void* ws);
+
+// ---- The ConvGRU's gate arithmetic for training (gru_train.hip): x3 / h3 [M][3 Ch], hprev / hout [M][Ch]; h3 nullptr: h = 0 ----
+int cp_launch_gru_gate_forward(hipStream_t s, const float* x3, const float* h3, const float* hprev, float* hout, long long M, int Ch);
+int cp_launch_gru_gate_backward(hipStream_t s, const float* x3, const float* h3, const float* hprev, const float* go, float* gx3,
+                                float* gh3, float* ghp, long long M, int Ch);
+
 // ---- MaxPool2d for training (pool.hip): (kernel, stride, pad) = (2, 2, 0), flooring, or (3, 2, 1), padding as -inf; float32
 // NHWC, C % 4 == 0, a non-empty output.  The winner of a window is torch's (first maximum in row-major order) in both calls ----
 bool cp_maxpool_geometry(int kernel, int stride, int pad);

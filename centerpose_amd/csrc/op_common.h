@@ -1,5 +1,5 @@
 // What the stand-alone operators share (ops.hip and the training operators dcn_bwd.hip, heads_bwd.hip, conv_bwd.hip,
-// deconv_bwd.hip, batchnorm.hip): the workspace carver, the launch check, the two fixed-order slab sums and the ConvParams of a
+// deconv_bwd.hip, batchnorm.hip, groupnorm.hip, gru_train.hip): the workspace carver, the launch check, the two fixed-order slab sums and the ConvParams of a
 // convolution that runs as part of a gradient.  The summation orders are contract (the tests compare bitwise), so they are
 // written here once.
 #pragma once

@@ -1,7 +1,8 @@
 // The stand-alone operators of the C ABI (include/centerpose_hip.h): single layers on caller tensors, outside any cp_model
 // -- cp_conv2d_nhwc / cp_conv2d_backward_nhwc, cp_batchnorm_forward_nhwc / _backward_nhwc, cp_conv_transpose2d_nhwc,
 // cp_conv_transpose2d_dw_nhwc / cp_conv_transpose2d_backward_nhwc, cp_dcnv2_forward / cp_dcnv2_backward, cp_pose_heads_forward / _backward,
-// cp_maxpool2d_forward_nhwc / _backward_nhwc, cp_conv2d_stem_backward.
+// cp_maxpool2d_forward_nhwc / _backward_nhwc, cp_conv2d_stem_backward, cp_groupnorm_forward_nhwc / _backward_nhwc,
+// cp_gru_gate_forward / _backward.
 // Each packs its PyTorch-layout weights into a caller-provided workspace on every call and then launches the same kernels as
 // the engine.
 #include "op_common.h"
@@ -233,6 +234,24 @@ bool bn_aligned(std::initializer_list<const void*> ptrs) {
     for (const void* p : ptrs)
         if ((uintptr_t)p & 15) return false;
     return true;
+}
+
+// GroupNorm: shape checks shared by the two calls and their workspace query, kernels in groupnorm.hip
+const char* gn_shape_error(int B, int H, int W, int C, int G) {
+    if (B < 1 || H < 1 || W < 1) return "groupnorm: B, H and W must be at least 1";
+    if (C < 4 || C > 4096 || C % 4) return "groupnorm: C must be a multiple of 4 in 4..4096";
+    if (G < 1 || C % G) return "groupnorm: G must be at least 1 and divide C";
+    if (C / G != 1 && C / G != 2 && (C / G) % 4)
+        return "groupnorm: C / G must be 1, 2 or a multiple of 4 (a lane's four channels must not straddle a group unevenly)";
+    if ((long long)B * H * W * C >= 0x7fffffffLL) return "groupnorm: a tensor has 2^31 elements or more";
+    return nullptr;
+}
+// the GRU gate: x3 [M][3 Ch] is the largest tensor
+const char* gru_shape_error(int M, int Ch) {
+    if (M < 1) return "gru_gate: M must be at least 1";
+    if (Ch < 4 || Ch > 1024 || Ch % 4) return "gru_gate: Ch must be a multiple of 4 in 4..1024";
+    if ((long long)M * 3 * Ch >= 0x7fffffffLL) return "gru_gate: a tensor has 2^31 elements or more";
+    return nullptr;
 }
 
 // cp_pose_heads_forward: per head the 3x3 layer's float32 and f16x3 operands + bias, the 1x1 layer's, one hidden chunk
@@ -534,6 +553,73 @@ int cp_batchnorm_backward_nhwc(cp_stream_t stream, const float* x, const float* 
                       grad_gamma_or_null, grad_beta_or_null, B, H, W, C, training != 0};
     const int rc = cp_launch_batchnorm_backward((hipStream_t)stream, a, workspace);
     return rc == CP_OK ? CP_OK : fail(rc, "batchnorm_backward: kernel launch failed");
+}
+
+size_t cp_groupnorm_workspace_bytes(int B, int H, int W, int C, int G) {
+    if (const char* e = gn_shape_error(B, H, W, C, G)) {
+        fail(CP_ERR_INVALID, e);
+        return 0;
+    }
+    return cp_groupnorm_ws_bytes(B, H, W, C, G);
+}
+
+int cp_groupnorm_forward_nhwc(cp_stream_t stream, const float* x, const float* gamma_or_null, const float* beta_or_null, float* y,
+                              float* save_mean, float* save_invstd, int B, int H, int W, int C, int G, float eps, int act,
+                              void* workspace, size_t workspace_bytes) {
+    if (const char* e = gn_shape_error(B, H, W, C, G)) return fail(CP_ERR_INVALID, e);
+    if (!x || !y || !save_mean || !save_invstd || !workspace) return fail(CP_ERR_INVALID, "groupnorm_forward: null argument");
+    if (act != 0 && act != 1) return fail(CP_ERR_INVALID, "groupnorm_forward: act must be 0 (none) or 1 (relu)");
+    if (!(eps >= 0.f)) return fail(CP_ERR_INVALID, "groupnorm_forward: eps must not be negative");
+    if (y == x) return fail(CP_ERR_INVALID, "groupnorm_forward: y must not alias x");
+    if (!bn_aligned({x, gamma_or_null, beta_or_null, y, save_mean, save_invstd, workspace}))
+        return fail(CP_ERR_INVALID, "groupnorm_forward: tensors must be 16-byte aligned");
+    if (workspace_bytes < cp_groupnorm_ws_bytes(B, H, W, C, G)) return fail(CP_ERR_INVALID, "groupnorm_forward: workspace too small");
+    const GnFwdArgs a{x, gamma_or_null, beta_or_null, y, save_mean, save_invstd, B, H, W, C, G, eps, act};
+    const int rc = cp_launch_groupnorm_forward((hipStream_t)stream, a, workspace);
+    return rc == CP_OK ? CP_OK : fail(rc, "groupnorm_forward: kernel launch failed");
+}
+
+int cp_groupnorm_backward_nhwc(cp_stream_t stream, const float* x, const float* y_or_null, const float* grad_out,
+                               const float* gamma_or_null, const float* save_mean, const float* save_invstd, float* grad_x_or_null,
+                               float* grad_gamma_or_null, float* grad_beta_or_null, int B, int H, int W, int C, int G,
+                               void* workspace, size_t workspace_bytes) {
+    if (const char* e = gn_shape_error(B, H, W, C, G)) return fail(CP_ERR_INVALID, e);
+    if (!x || !grad_out || !save_mean || !save_invstd || !workspace) return fail(CP_ERR_INVALID, "groupnorm_backward: null argument");
+    if (!bn_aligned({x, y_or_null, grad_out, gamma_or_null, save_mean, save_invstd, grad_x_or_null, grad_gamma_or_null,
+                     grad_beta_or_null, workspace}))
+        return fail(CP_ERR_INVALID, "groupnorm_backward: tensors must be 16-byte aligned");
+    if (workspace_bytes < cp_groupnorm_ws_bytes(B, H, W, C, G)) return fail(CP_ERR_INVALID, "groupnorm_backward: workspace too small");
+    const GnBwdArgs a{x, y_or_null, grad_out, gamma_or_null, save_mean, save_invstd, grad_x_or_null, grad_gamma_or_null,
+                      grad_beta_or_null, B, H, W, C, G};
+    const int rc = cp_launch_groupnorm_backward((hipStream_t)stream, a, workspace);
+    return rc == CP_OK ? CP_OK : fail(rc, "groupnorm_backward: kernel launch failed");
+}
+
+// The ConvGRU's gate arithmetic (gru_train.hip)
+int cp_gru_gate_forward(cp_stream_t stream, const float* x3, const float* h3_or_null, const float* hprev_or_null, float* hout, int M,
+                        int Ch) {
+    if (const char* e = gru_shape_error(M, Ch)) return fail(CP_ERR_INVALID, e);
+    if (!x3 || !hout) return fail(CP_ERR_INVALID, "gru_gate_forward: null argument");
+    if (!h3_or_null != !hprev_or_null)
+        return fail(CP_ERR_INVALID, "gru_gate_forward: h3 and hprev are given together, or neither (step 0: h = 0)");
+    if (!bn_aligned({x3, h3_or_null, hprev_or_null, hout})) return fail(CP_ERR_INVALID, "gru_gate_forward: tensors must be 16-byte aligned");
+    const int rc = cp_launch_gru_gate_forward((hipStream_t)stream, x3, h3_or_null, hprev_or_null, hout, M, Ch);
+    return rc == CP_OK ? CP_OK : fail(rc, "gru_gate_forward: kernel launch failed");
+}
+
+int cp_gru_gate_backward(cp_stream_t stream, const float* x3, const float* h3_or_null, const float* hprev_or_null,
+                         const float* grad_hout, float* grad_x3, float* grad_h3_or_null, float* grad_hprev_or_null, int M, int Ch) {
+    if (const char* e = gru_shape_error(M, Ch)) return fail(CP_ERR_INVALID, e);
+    if (!x3 || !grad_hout || !grad_x3) return fail(CP_ERR_INVALID, "gru_gate_backward: null argument");
+    if (!h3_or_null != !hprev_or_null)
+        return fail(CP_ERR_INVALID, "gru_gate_backward: h3 and hprev are given together, or neither (step 0: h = 0)");
+    if (!h3_or_null && (grad_h3_or_null || grad_hprev_or_null))
+        return fail(CP_ERR_INVALID, "gru_gate_backward: step 0 (h3 == NULL) has no hidden-side gradients");
+    if (!bn_aligned({x3, h3_or_null, hprev_or_null, grad_hout, grad_x3, grad_h3_or_null, grad_hprev_or_null}))
+        return fail(CP_ERR_INVALID, "gru_gate_backward: tensors must be 16-byte aligned");
+    const int rc = cp_launch_gru_gate_backward((hipStream_t)stream, x3, h3_or_null, hprev_or_null, grad_hout, grad_x3, grad_h3_or_null,
+                                               grad_hprev_or_null, M, Ch);
+    return rc == CP_OK ? CP_OK : fail(rc, "gru_gate_backward: kernel launch failed");
 }
 
 // MaxPool2d, forward and backward (pool.hip)

@@ -139,6 +139,11 @@ def lib():
     _sig(L.cp_batchnorm_forward_nhwc, c_int, *([c_void_p] * 10), *([c_int] * 5), ctypes.c_float, ctypes.c_float, c_int, c_void_p,
          c_size_t)
     _sig(L.cp_batchnorm_backward_nhwc, c_int, *([c_void_p] * 11), *([c_int] * 5), c_void_p, c_size_t)
+    _sig(L.cp_groupnorm_workspace_bytes, c_size_t, *([c_int] * 5))
+    _sig(L.cp_groupnorm_forward_nhwc, c_int, *([c_void_p] * 7), *([c_int] * 5), ctypes.c_float, c_int, c_void_p, c_size_t)
+    _sig(L.cp_groupnorm_backward_nhwc, c_int, *([c_void_p] * 10), *([c_int] * 5), c_void_p, c_size_t)
+    _sig(L.cp_gru_gate_forward, c_int, *([c_void_p] * 5), c_int, c_int)
+    _sig(L.cp_gru_gate_backward, c_int, *([c_void_p] * 8), c_int, c_int)
     _sig(L.cp_maxpool2d_forward_nhwc, c_int, c_void_p, c_void_p, c_void_p, *([c_int] * 7))
     _sig(L.cp_maxpool2d_backward_nhwc, c_int, c_void_p, c_void_p, c_void_p, c_void_p, *([c_int] * 7))
     _sig(L.cp_conv2d_stem_backward_workspace_bytes, c_size_t, *([c_int] * 6))
@@ -243,7 +248,8 @@ def exported_symbols():
             "cp_batchnorm_workspace_bytes", "cp_batchnorm_forward_nhwc", "cp_batchnorm_backward_nhwc",
             "cp_conv_transpose2d_dw_nhwc", "cp_conv_transpose2d_backward_workspace_bytes",
             "cp_conv_transpose2d_backward_nhwc", "cp_maxpool2d_forward_nhwc", "cp_maxpool2d_backward_nhwc",
-            "cp_conv2d_stem_backward_workspace_bytes", "cp_conv2d_stem_backward"]
+            "cp_conv2d_stem_backward_workspace_bytes", "cp_conv2d_stem_backward", "cp_groupnorm_workspace_bytes",
+            "cp_groupnorm_forward_nhwc", "cp_groupnorm_backward_nhwc", "cp_gru_gate_forward", "cp_gru_gate_backward"]
 
 
 def _check(rc, what):
@@ -584,6 +590,104 @@ def batch_norm_backward(x, grad_out, save_mean, save_invstd, gamma=None, y=None,
     if need_residual_grad and y is None:
         grad_res = grad_out
     return grad_x, grad_res, grad_g, grad_b
+
+
+def _gn_ws(L, x, G):
+    if not x.is_cuda:
+        raise RuntimeError("centerpose_hip: tensors must live on the HIP device (no CPU path)")
+    if x.dim() != 4:
+        raise RuntimeError("group_norm: x must be [B,H,W,C], got %s" % (tuple(x.shape),))
+    B, H, W, C = x.shape
+    nbytes = L.cp_groupnorm_workspace_bytes(B, H, W, C, int(G))
+    if nbytes == 0:
+        raise RuntimeError("group_norm: shape refused by the library (%s)" % L.cp_last_error().decode())
+    return (B, H, W, C, int(G)), nbytes, torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+
+
+def group_norm_forward(x, num_groups, gamma=None, beta=None, eps=1e-5, act=0):
+    """``act(group_norm(x))`` (cp_groupnorm_forward_nhwc): x [B,H,W,C] NHWC, gamma / beta [C] or None (1 / 0) -> (y [B,H,W,C],
+    save_mean [B,G], save_invstd [B,G]).  act 0 none, 1 relu.  ``C % 4 == 0`` and ``C / G`` 1, 2 or a multiple of 4.  Float32
+    and bitwise reproducible."""
+    L = lib()
+    geo, nbytes, ws = _gn_ws(L, x, num_groups)
+    x = _dev(x)
+    B, C, G = geo[0], geo[3], geo[4]
+    gamma, beta = _bn_vec(gamma, C, "gamma"), _bn_vec(beta, C, "beta")
+    y = torch.empty_like(x)
+    mean = torch.empty(B, G, device=x.device, dtype=torch.float32)
+    invstd = torch.empty_like(mean)
+    rc = L.cp_groupnorm_forward_nhwc(_stream(), _ptr(x), _ptr(gamma), _ptr(beta), _ptr(y), _ptr(mean), _ptr(invstd), *geo,
+                                     float(eps), int(act), _ptr(ws), nbytes)
+    _check(rc, "cp_groupnorm_forward_nhwc")
+    return y, mean, invstd
+
+
+def group_norm_backward(x, grad_out, num_groups, save_mean, save_invstd, gamma=None, y=None, need_x_grad=True,
+                        need_gamma_grad=True, need_beta_grad=True):
+    """Gradients of group_norm_forward (cp_groupnorm_backward_nhwc) -> (grad_x, grad_gamma, grad_beta), None where not asked
+    for.  ``y``: the activated forward output when act was 1 (grad_out is gated by y > 0).  Float32 and bitwise reproducible."""
+    L = lib()
+    geo, nbytes, ws = _gn_ws(L, x, num_groups)
+    x, grad_out = _dev(x), _dev(grad_out)
+    y = _dev(y) if y is not None else None
+    B, C, G = geo[0], geo[3], geo[4]
+    for name, t in (("grad_out", grad_out), ("y", y)):
+        if t is not None and t.shape != x.shape:
+            raise RuntimeError("group_norm_backward: %s has shape %s, expected %s" % (name, tuple(t.shape), tuple(x.shape)))
+    gamma = _bn_vec(gamma, C, "gamma")
+    save_mean, save_invstd = _dev(save_mean), _dev(save_invstd)
+    for name, t in (("save_mean", save_mean), ("save_invstd", save_invstd)):
+        if tuple(t.shape) != (B, G):
+            raise RuntimeError("group_norm_backward: %s has shape %s, expected %s" % (name, tuple(t.shape), (B, G)))
+    grad_x = torch.empty_like(x) if need_x_grad else None
+    grad_g = torch.empty(C, device=x.device, dtype=torch.float32) if need_gamma_grad else None
+    grad_b = torch.empty(C, device=x.device, dtype=torch.float32) if need_beta_grad else None
+    if need_x_grad or need_gamma_grad or need_beta_grad:
+        rc = L.cp_groupnorm_backward_nhwc(_stream(), _ptr(x), _ptr(y), _ptr(grad_out), _ptr(gamma), _ptr(save_mean),
+                                          _ptr(save_invstd), _ptr(grad_x), _ptr(grad_g), _ptr(grad_b), *geo, _ptr(ws), nbytes)
+        _check(rc, "cp_groupnorm_backward_nhwc")
+    return grad_x, grad_g, grad_b
+
+
+def _gru_args(x3, h3, hprev):
+    if not x3.is_cuda:
+        raise RuntimeError("centerpose_hip: tensors must live on the HIP device (no CPU path)")
+    if x3.dim() < 2 or x3.shape[-1] % 3:
+        raise RuntimeError("gru_gate: x3 must be [..., 3 * Ch], got %s" % (tuple(x3.shape),))
+    if (h3 is None) != (hprev is None):
+        raise RuntimeError("gru_gate: h3 and hprev are given together, or neither (step 0)")
+    x3 = _dev(x3)
+    Ch = x3.shape[-1] // 3
+    lead = tuple(x3.shape[:-1])
+    if h3 is not None:
+        h3, hprev = _dev(h3), _dev(hprev)
+        if h3.shape != x3.shape or tuple(hprev.shape) != lead + (Ch,):
+            raise RuntimeError("gru_gate: h3 %s / hprev %s do not match x3 %s" % (tuple(h3.shape), tuple(hprev.shape), tuple(x3.shape)))
+    return x3, h3, hprev, lead, x3.numel() // (3 * Ch), Ch
+
+
+def gru_gate_forward(x3, h3=None, hprev=None):
+    """The ConvGRU cell's gate arithmetic (cp_gru_gate_forward): x3 = [Wir x | Wiz x | Win x] (+ biases) and h3 = [Whr h | Whz h |
+    Whn h] as [..., 3 Ch], hprev [..., Ch] -> hout [..., Ch] = (1 - z) n + z hprev.  ``h3 = hprev = None``: step 0, h = 0."""
+    x3, h3, hprev, lead, M, Ch = _gru_args(x3, h3, hprev)
+    hout = torch.empty(lead + (Ch,), device=x3.device, dtype=torch.float32)
+    _check(lib().cp_gru_gate_forward(_stream(), _ptr(x3), _ptr(h3), _ptr(hprev), _ptr(hout), M, Ch), "cp_gru_gate_forward")
+    return hout
+
+
+def gru_gate_backward(x3, h3, hprev, grad_hout, need_h3_grad=True, need_hprev_grad=True):
+    """Gradients of gru_gate_forward (cp_gru_gate_backward) -> (grad_x3, grad_h3, grad_hprev); the gates are recomputed from
+    the inputs.  At step 0 (``h3 = hprev = None``) the two hidden-side gradients are None."""
+    x3, h3, hprev, lead, M, Ch = _gru_args(x3, h3, hprev)
+    grad_hout = _dev(grad_hout)
+    if tuple(grad_hout.shape) != lead + (Ch,):
+        raise RuntimeError("gru_gate_backward: grad_hout has shape %s, expected %s" % (tuple(grad_hout.shape), lead + (Ch,)))
+    grad_x3 = torch.empty_like(x3)
+    grad_h3 = torch.empty_like(x3) if h3 is not None and need_h3_grad else None
+    grad_hp = torch.empty_like(grad_hout) if h3 is not None and need_hprev_grad else None
+    _check(lib().cp_gru_gate_backward(_stream(), _ptr(x3), _ptr(h3), _ptr(hprev), _ptr(grad_hout), _ptr(grad_x3), _ptr(grad_h3),
+                                      _ptr(grad_hp), M, Ch), "cp_gru_gate_backward")
+    return grad_x3, grad_h3, grad_hp
 
 
 def conv_transpose2d(x, w, scale=None, shift=None, act=0):

@@ -218,12 +218,34 @@ class DLAUp(nn.Module):
 
 
 _MISSING = {
-    "dlav1": "the ConvGRU between the backbone and the heads and the heads' GroupNorm have no training kernels",
+    "dlav1": "its ConvGRU and GroupNorm heads are composed by centerpose_amd.pose_net_gru.PoseNetGRU (build one with "
+             "PoseNetGRU.from_model(model) and hand it back with model.load_module(net))",
     "hourglass": "the two-stack hourglass is not composed (its convolutions, BatchNorms and max-pools train through "
                  "use_hip_convs / use_hip_norms / use_hip_pools on the reference's own tree)",
     "resdcn": "the ResNet-DCN family is not composed (its layers train through use_hip_stems / use_hip_convs / use_hip_norms / "
               "use_hip_pools / use_hip_deconvs on the reference's own tree)",
 }
+
+
+def compose_backbone(net, opt):
+    """Registers DLASeg's ``base``, ``dla_up`` and ``ida_up`` (pose_dla_dcn.py:473-489, down_ratio 4) on ``net``, in the reference's
+    order; ``opt`` says which previous-frame stems exist.  Shared by ``PoseNet`` and ``pose_net_gru.PoseNetGRU``."""
+    net.pre_stems = tuple(bool(opt is not None and getattr(opt, f, False)) for f in ("pre_img", "pre_hm", "pre_hm_hp"))
+    net.first_level, net.last_level = 2, 5  # down_ratio 4
+    net.base = DLA(net.pre_stems)
+    ch = _CHANNELS
+    scales = [2 ** i for i in range(len(ch[net.first_level:]))]
+    net.dla_up = DLAUp(net.first_level, ch[net.first_level:], scales)
+    net.ida_up = IDAUp(ch[net.first_level], ch[net.first_level:net.last_level],
+                       [2 ** i for i in range(net.last_level - net.first_level)])
+
+
+def run_backbone(net, x, pre_img=None, pre_hm=None, pre_hm_hp=None):
+    """DLASeg.forward up to the feature map the heads (or the ConvGRU) read: [B,64,H/4,W/4]"""
+    y = net.dla_up(net.base(x, pre_img, pre_hm, pre_hm_hp))
+    y = y[:net.last_level - net.first_level]
+    net.ida_up(y, 0, len(y))
+    return y[-1]
 
 
 class PoseNet(nn.Module):
@@ -242,14 +264,8 @@ class PoseNet(nn.Module):
         self.arch = arch
         self.heads = OrderedDict(heads)
         self.head_conv = int(head_conv)
-        self.pre_stems = tuple(bool(opt is not None and getattr(opt, f, False)) for f in ("pre_img", "pre_hm", "pre_hm_hp"))
-        self.first_level, self.last_level = 2, 5  # down_ratio 4
-        self.base = DLA(self.pre_stems)
+        compose_backbone(self, opt)
         ch = _CHANNELS
-        scales = [2 ** i for i in range(len(ch[self.first_level:]))]
-        self.dla_up = DLAUp(self.first_level, ch[self.first_level:], scales)
-        self.ida_up = IDAUp(ch[self.first_level], ch[self.first_level:self.last_level],
-                            [2 ** i for i in range(self.last_level - self.first_level)])
         # the heads: one PoseHeads (one autograd function over all of them), its per-head modules registered under this
         # module so that the state-dict keys are the reference's `hm.0.weight`, ... without a prefix
         block = PoseHeads(self.heads, ch[self.first_level], self.head_conv)
@@ -260,7 +276,4 @@ class PoseNet(nn.Module):
         self.__dict__["_head_block"] = block  # (not a sub-module: its parameters are registered above)
 
     def forward(self, x, pre_img=None, pre_hm=None, pre_hm_hp=None):
-        y = self.dla_up(self.base(x, pre_img, pre_hm, pre_hm_hp))
-        y = y[:self.last_level - self.first_level]
-        self.ida_up(y, 0, len(y))
-        return [self._head_block(y[-1])]
+        return [self._head_block(run_backbone(self, x, pre_img, pre_hm, pre_hm_hp))]

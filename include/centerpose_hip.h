@@ -45,7 +45,8 @@ typedef struct cp_model cp_model;
  *     cp_pose_loss_forward, cp_pose_loss_backward, cp_pose_targets_workspace_bytes, cp_pose_targets,
  *     cp_model_lean_supported, cp_model_detect_lean(_workspace_bytes), cp_model_dense_heads, cp_model_heads_at(_workspace_bytes),
  *     cp_decode_peaks(_workspace_bytes), cp_decode_gathered; CP_NUM_KERNEL_VARIANTS 46;
- *     cp_pose_heads_forward / _backward (+ _workspace_bytes, cp_pose_heads_chunk_images), cp_model_features. */
+ *     cp_pose_heads_forward / _backward (+ _workspace_bytes, cp_pose_heads_chunk_images), cp_model_features;
+ *     cp_groupnorm_workspace_bytes, cp_groupnorm_forward_nhwc / _backward_nhwc, cp_gru_gate_forward / _backward. */
 #define CP_ABI_VERSION 7
 const char* cp_version(void);
 int cp_abi_version(void);
@@ -354,6 +355,54 @@ int cp_batchnorm_backward_nhwc(cp_stream_t stream, const float* x, const float* 
                                float* grad_x_or_null, float* grad_residual_or_null, float* grad_gamma_or_null,
                                float* grad_beta_or_null, int B, int H, int W, int C, int training, void* workspace,
                                size_t workspace_bytes);
+
+/* ------------------------------------------------------------------------------------------
+ * GroupNorm for training, fused with the ReLU — nn.GroupNorm(G, C) and the ReLU behind it in the dlav1_34 heads of
+ *   models/networks/pose_dla_dcn.py:491-521 (groups by models/networks/GN.py), forward and backward:
+ *     y = act(xhat * gamma + beta),  xhat = (x - mean) * invstd,  act: 0 none, 1 relu.
+ * All tensors float32; x, y, grad_out, grad_x [B,H,W,C] NHWC; gamma, beta and their gradients [C]; save_mean, save_invstd
+ * [B][G].  NULL gamma / beta mean 1 / 0 (affine=False).  The statistics are per (image, group) over n = (C / G) H W values,
+ * the variance biased, never formed as E[x^2] - mean^2 (pivoted sums merged by Chan's rule).  y must not alias x.
+ * Backward: g = grad_out, gated by y > 0 when y (the forward's ACTIVATED output) is given; grad_beta[c] = sum g and
+ * grad_gamma[c] = sum g * xhat over images and pixels; grad_x = invstd * (g * gamma - s1 / n - xhat * s2 / n) with s1 = sum g *
+ * gamma and s2 = sum g * gamma * xhat over the (image, group).  Outputs are written, not accumulated; a NULL output is not
+ * computed and not touched.
+ * No atomics; every sum has a fixed order that depends on the shape alone: all outputs are bitwise reproducible call to call.
+ * Refused with CP_ERR_INVALID and a cp_last_error() text before any launch (the query returns 0 for the shape ones): a NULL
+ * pointer other than those named *_or_null, a workspace below the query, B / H / W < 1, C % 4 != 0 or outside 4..4096, G < 1
+ * or C % G != 0, C / G neither 1, 2 nor a multiple of 4 (a 16-byte lane must not straddle a group boundary unevenly: 48
+ * channels in 16 groups), act outside {0, 1}, eps < 0, a tensor of 2^31 elements or more, a pointer that is not 16-byte
+ * aligned.  The query is host arithmetic, serves both calls and is monotone in B.  Launches on `stream`, never synchronises.
+ * ------------------------------------------------------------------------------------------ */
+size_t cp_groupnorm_workspace_bytes(int B, int H, int W, int C, int G);
+int cp_groupnorm_forward_nhwc(cp_stream_t stream, const float* x, const float* gamma_or_null, const float* beta_or_null,
+                              float* y, float* save_mean, float* save_invstd, int B, int H, int W, int C, int G, float eps,
+                              int act, void* workspace, size_t workspace_bytes);
+int cp_groupnorm_backward_nhwc(cp_stream_t stream, const float* x, const float* y_or_null, const float* grad_out,
+                               const float* gamma_or_null, const float* save_mean, const float* save_invstd,
+                               float* grad_x_or_null, float* grad_gamma_or_null, float* grad_beta_or_null, int B, int H, int W,
+                               int C, int G, void* workspace, size_t workspace_bytes);
+
+/* ------------------------------------------------------------------------------------------
+ * The ConvGRU's gate arithmetic for training — ConvGRUCell.forward of models/networks/convGRU.py:32-39 behind its six
+ *   convolutions, forward and backward, float32, one pass each, no workspace:
+ *     x3 = [Wir x + b | Wiz x + b | Win x + b] and h3 = [Whr h | Whz h | Whn h] as [M][3 Ch] (M = B H W pixel rows of NHWC
+ *     tensors); hprev, hout, grad_hout, grad_hprev [M][Ch]; grad_x3, grad_h3 [M][3 Ch].
+ *     r = sigmoid(x3r + h3r), z = sigmoid(x3z + h3z), n = tanh(x3n + r * h3n), hout = (1 - z) * n + z * hprev.
+ * h3 == NULL is step 0 of every forward: h = 0 and h3 = 0 (the hidden-side convolutions have no bias and are not run);
+ * hprev and the two hidden-side gradients must then be NULL too.
+ * Backward: r, z and n are recomputed from the inputs (no gate tensor is kept).  With g = grad_hout: da_n = g (1 - z) (1 - n^2),
+ * grad_x3n = da_n, grad_h3n = da_n r, grad_x3r = grad_h3r = da_n h3n r (1 - r), grad_x3z = grad_h3z = g (hprev - n) z (1 - z),
+ * grad_hprev = g z.  grad_x3 is always written; a NULL grad_h3 / grad_hprev is not computed.  Bitwise reproducible.
+ * Refused with CP_ERR_INVALID and a cp_last_error() text before any launch: a NULL pointer other than those named *_or_null,
+ * h3 without hprev or the reverse, a hidden-side gradient at step 0, M < 1, Ch % 4 != 0 or outside 4..1024, a tensor of 2^31
+ * elements or more, a pointer that is not 16-byte aligned.  Launches on `stream`, never synchronises.
+ * ------------------------------------------------------------------------------------------ */
+int cp_gru_gate_forward(cp_stream_t stream, const float* x3, const float* h3_or_null, const float* hprev_or_null, float* hout,
+                        int M, int Ch);
+int cp_gru_gate_backward(cp_stream_t stream, const float* x3, const float* h3_or_null, const float* hprev_or_null,
+                         const float* grad_hout, float* grad_x3, float* grad_h3_or_null, float* grad_hprev_or_null, int M,
+                         int Ch);
 
 /* Dense ConvTranspose2d(Cin, Cout, kernel 4, stride 2, padding 1, bias=False) followed by an optional per-channel affine
  * and ReLU (resnet_dcn.py's deconv `up` layers with their BatchNorm): x [B,H,W,Cin] NHWC, w [Cin,Cout,4,4] (PyTorch
