@@ -574,6 +574,13 @@ struct cp_pose_targets_desc;
 const char* cp_pose_targets_check(const cp_pose_targets_desc* d);  // nullptr: accepted (reads the host records)
 size_t cp_pose_targets_ws_bytes(const cp_pose_targets_desc* d);    // 0: refused
 int cp_launch_pose_targets(hipStream_t s, const cp_pose_targets_desc* d, void* ws);
+// ---- the tracking task's targets (pose_targets_track.hip; per-object logic in pose_targets_track_common.h) ----
+namespace pose_targets { struct PtTrackCur; }
+int cp_launch_pose_targets_cur(hipStream_t s, const cp_pose_targets_desc* d, void* ws, const pose_targets::PtTrackCur* tk);
+struct cp_pose_targets_track_desc;
+const char* cp_pose_targets_track_check(const cp_pose_targets_track_desc* d);  // nullptr: accepted
+size_t cp_pose_targets_track_ws_bytes(const cp_pose_targets_track_desc* d);    // 0: refused
+int cp_launch_pose_targets_track(hipStream_t s, const cp_pose_targets_track_desc* d, void* ws);
 
 // ---- Objectron box metrics (box3d.hip; numerics in box3d_common.h) ----
 int cp_launch_box_iou(hipStream_t s, const double* a, const double* b, int n, double* iou);

@@ -684,4 +684,15 @@ int cp_pose_targets(cp_stream_t stream, const cp_pose_targets_desc* d, void* wor
     return rc == CP_OK ? CP_OK : fail(rc, "pose_targets: copy or kernel launch failed");
 }
 
+size_t cp_pose_targets_track_workspace_bytes(const cp_pose_targets_track_desc* d) { return cp_pose_targets_track_ws_bytes(d); }
+
+int cp_pose_targets_track(cp_stream_t stream, const cp_pose_targets_track_desc* d, void* workspace, size_t workspace_bytes) {
+    if (const char* e = cp_pose_targets_track_check(d)) return fail(CP_ERR_INVALID, e);
+    if (!workspace) return fail(CP_ERR_INVALID, "pose_targets_track: null workspace");
+    if (workspace_bytes < cp_pose_targets_track_ws_bytes(d))
+        return fail(CP_ERR_INVALID, "pose_targets_track: workspace too small");
+    const int rc = cp_launch_pose_targets_track((hipStream_t)stream, d, workspace);
+    return rc == CP_OK ? CP_OK : fail(rc, "pose_targets_track: copy or kernel launch failed");
+}
+
 }  // extern "C"

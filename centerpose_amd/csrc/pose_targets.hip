@@ -6,6 +6,8 @@
 //                      centre and joints of pose_targets_common.h; writes every sparse slot of (b, s, k), zeros included,
 //                      and compacts, per (b, s, channel), the Gaussians to draw (channel 0 = hm, 1 + j = hm_hp joint j)
 //                      with a ballot in object order: no atomics.
+//                      For cp_pose_targets_track (pose_targets_track.hip) a PtTrackCur argument adds the tracking task's
+//                      skip and variant filter and the tracking / tracking_hp targets; all zero, it changes nothing.
 //   2. maps_kernel     one workgroup per (map plane, band of BAND elements): the plane's draw list, culled to the band's
 //                      rows, sits in LDS; every element of hm / hm_hp is written exactly once (no clear pass) as the max
 //                      over the draws that cover it of float32(exp(-(dx^2+dy^2) / (2 sigma^2))), sigma = (2r+1)/6 in
@@ -16,6 +18,7 @@
 #include "../../include/centerpose_hip.h"
 #include "cp_common.h"
 #include "pose_targets_common.h"
+#include "pose_targets_track_common.h"
 
 #include <cstdio>
 
@@ -58,17 +61,51 @@ Ws carve(const cp_pose_targets_desc* d, void* ws) {
 
 __global__ void __launch_bounds__(64) objects_kernel(cp_pose_targets_desc d, const double* __restrict__ img,
                                                      const double* __restrict__ obj, int* __restrict__ counts,
-                                                     int4* __restrict__ draws) {
+                                                     int4* __restrict__ draws, const PtTrackCur tk) {
     const int bs = blockIdx.x, b = bs / d.S, s = bs - b * d.S, k = threadIdx.x, K = d.max_objs;
     const double* im = img + (size_t)b * CP_PT_IMG_STRIDE;
     const double* ob = obj + ((size_t)b * K + (k < K ? k : 0)) * CP_PT_OBJ_STRIDE;
     const int flags = (d.center_3D ? PT_CENTER_3D : 0) | (d.use_absolute_scale ? PT_ABS_SCALE : 0);
     PtResult r;
     r.kept = 0;
-    if (k < K && k < (int)im[CP_PT_IMG_NUM_OBJS] && s < (int)ob[CP_PT_OBJ_NSYM]) pt_object(im, ob, s, d.S, d.R, flags, &r);
+    bool run = k < K && k < (int)im[CP_PT_IMG_NUM_OBJS] && s < (int)ob[CP_PT_OBJ_NSYM];
+    // the tracking task (cp_pose_targets_track): the cup / mug skip (:968-972) and the variant filter (:983-987), which
+    // reads the previous list at the CURRENT index k, as the reference does
+    const double* cu = tk.on ? tk.cur + ((size_t)b * K + (k < K ? k : 0)) * CP_PTK_CUR_STRIDE : nullptr;
+    const int npre = tk.on ? (int)tk.timg[(size_t)b * CP_PTK_IMG_STRIDE + CP_PTK_IMG_NUM_PRE] : 0;
+    const PtkPreOut* pre = tk.on ? tk.pre + (size_t)b * tk.Kp : nullptr;
+    if (tk.on && run) {
+        if (cu[CP_PTK_CUR_SKIP] != 0.0) run = false;
+        if (run && tk.pre_hm_hp && (int)ob[CP_PT_OBJ_NSYM] != 1 && k < npre && pre[k].chosen >= 0 && pre[k].chosen != s)
+            run = false;
+    }
+    if (run) pt_object(im, ob, s, d.S, d.R, flags, &r);
     if (k < K) {
         const bool kept = r.kept != 0;
         const size_t o = (size_t)bs * K + k;
+        if (tk.on) {  // the first kept previous object with this object's id (track_ids.index, :1110, :1133)
+            int m = -1;
+            if (kept) {
+                const int id = (int)cu[CP_PTK_CUR_ID];
+                for (int q = 0; q < npre && m < 0; ++q)
+                    if (pre[q].kept && pre[q].id == id) m = q;
+            }
+            if (tk.tracking) {  // previous - current, float64, into the float32 array (:1135-1137)
+                const bool has = m >= 0 && !pre[m].cts_none;
+                for (int i = 0; i < 2; ++i) tk.out_tracking[2 * o + i] = has ? (float)(pre[m].cts[i] - (double)r.ct[i]) : 0.f;
+                tk.out_tracking_mask[o] = has ? 1 : 0;
+            }
+            if (tk.tracking_hp)  // inside the joint's own block; a NaN label writes nothing (:1106-1117)
+                for (int j = 0; j < CP_PT_JOINTS; ++j) {
+                    bool wr = kept && r.joint_ok[j] && m >= 0;
+                    if (wr) wr = !(pre[m].pts[2 * j] != pre[m].pts[2 * j]) && !(pre[m].pts[2 * j + 1] != pre[m].pts[2 * j + 1]);
+                    for (int c = 0; c < 2; ++c) {
+                        const size_t e = o * 2 * CP_PT_JOINTS + 2 * j + c;
+                        tk.out_tracking_hp[e] = wr ? (float)((double)pre[m].pts[2 * j + c] - (double)r.pt[j][c]) : 0.f;
+                        tk.out_tracking_hp_mask[e] = wr ? (unsigned char)((pre[m].pmask >> j) & 1u) : 0;
+                    }
+                }
+        }
         d.out_reg_mask[o] = kept ? 1 : 0;
         d.out_ind[o] = kept ? r.ind : 0;
         for (int i = 0; i < 2; ++i) {
@@ -234,14 +271,21 @@ size_t cp_pose_targets_ws_bytes(const cp_pose_targets_desc* d) {
 }
 
 int cp_launch_pose_targets(hipStream_t s, const cp_pose_targets_desc* d, void* ws) {
+    return cp_launch_pose_targets_cur(s, d, ws, nullptr);
+}
+
+// `tk` (device pointers, or nullptr): the tracking additions of cp_pose_targets_track (pose_targets_track.hip)
+int cp_launch_pose_targets_cur(hipStream_t s, const cp_pose_targets_desc* d, void* ws, const pose_targets::PtTrackCur* tk) {
     const Ws w = carve(d, ws);
+    PtTrackCur t = {};
+    if (tk) t = *tk;
     if (hipMemcpyAsync(w.img, d->images, (size_t)d->B * CP_PT_IMG_STRIDE * sizeof(double), hipMemcpyHostToDevice, s) !=
             hipSuccess ||
         hipMemcpyAsync(w.obj, d->objects, (size_t)d->B * d->max_objs * CP_PT_OBJ_STRIDE * sizeof(double),
                        hipMemcpyHostToDevice, s) != hipSuccess)
         return CP_ERR_LAUNCH;
     hipLaunchKernelGGL(objects_kernel, dim3(d->B * d->S), dim3(64), 0, s, *d, (const double*)w.img,
-                       (const double*)w.obj, w.counts, w.draws);
+                       (const double*)w.obj, w.counts, w.draws, t);
     const int nch = d->hm_hp ? NCH : 1;
     const size_t P = (size_t)d->R * d->R;
     const int nband = (int)((P + BAND - 1) / BAND);

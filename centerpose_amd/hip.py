@@ -72,6 +72,28 @@ class PoseTargetsDesc(ctypes.Structure):
                [("images", c_void_p), ("objects", c_void_p)] + [("out_" + n, c_void_p) for n in PT_OUTPUTS]
 
 
+# ---- the tracking task's targets (cp_pose_targets_track*): record layouts of include/centerpose_hip.h ----
+PTK_IMG_STRIDE, PTK_PRE_STRIDE, PTK_CUR_STRIDE = 32, 128, 2
+PTK_IMG = dict(trans=0, num_pre=6, proj=7)
+PTK_PRE = dict(skip=56, idsym=57, id=58, draws=64)  # 0..52: PT_OBJ's nsym, cuboid, quat, loc, kps3d
+PTK_DRAW = dict(ct_noise=0, ct_lost=2, ct_heat=3, ct_fp=4, ct_fp_noise=5, ct_fp_peak=7, joints=8, joint_stride=7,
+                j_noise=0, j_lost=2, j_fp=3, j_fp_noise=4, j_fp_peak=6)
+PTK_NUM_DRAWS = 64
+PTK_CUR = dict(id=0, skip=1)
+PTK_GEOMETRY = ("input_w", "input_h", "down_ratio", "max_pre_objs")
+PTK_FLAGS = ("hm_heat_random", "hm_hp_heat_random", "tracking_label_mode", "pre_hm", "pre_hm_hp", "tracking", "tracking_hp")
+PTK_DISTURB = ("hm_disturb", "lost_disturb", "fp_disturb", "hm_hp_disturb", "hp_lost_disturb", "hp_fp_disturb")
+PTK_OUTPUTS = ("pre_hm", "pre_hm_hp", "tracking", "tracking_mask", "tracking_hp", "tracking_hp_mask")
+
+
+class PoseTargetsTrackDesc(ctypes.Structure):
+    """cp_pose_targets_track_desc of include/centerpose_hip.h (field for field)."""
+    _fields_ = [("cur", PoseTargetsDesc)] + [(n, c_int) for n in PTK_GEOMETRY + PTK_FLAGS + ("reserved",)] + \
+               [(n, ctypes.c_double) for n in PTK_DISTURB] + \
+               [(n, c_void_p) for n in ("track_images", "pre_objects", "cur_objects")] + \
+               [("out_" + n, c_void_p) for n in PTK_OUTPUTS]
+
+
 def _sig(fn, restype, *argtypes):
     fn.restype = restype
     fn.argtypes = list(argtypes)
@@ -207,6 +229,8 @@ def lib():
          ctypes.POINTER(c_void_p), c_void_p, c_size_t)
     _sig(L.cp_pose_targets_workspace_bytes, c_size_t, ctypes.POINTER(PoseTargetsDesc))
     _sig(L.cp_pose_targets, c_int, c_void_p, ctypes.POINTER(PoseTargetsDesc), c_void_p, c_size_t)
+    _sig(L.cp_pose_targets_track_workspace_bytes, c_size_t, ctypes.POINTER(PoseTargetsTrackDesc))
+    _sig(L.cp_pose_targets_track, c_int, c_void_p, ctypes.POINTER(PoseTargetsTrackDesc), c_void_p, c_size_t)
     _lib = L
     return L
 
@@ -249,7 +273,8 @@ def exported_symbols():
             "cp_conv_transpose2d_dw_nhwc", "cp_conv_transpose2d_backward_workspace_bytes",
             "cp_conv_transpose2d_backward_nhwc", "cp_maxpool2d_forward_nhwc", "cp_maxpool2d_backward_nhwc",
             "cp_conv2d_stem_backward_workspace_bytes", "cp_conv2d_stem_backward", "cp_groupnorm_workspace_bytes",
-            "cp_groupnorm_forward_nhwc", "cp_groupnorm_backward_nhwc", "cp_gru_gate_forward", "cp_gru_gate_backward"]
+            "cp_groupnorm_forward_nhwc", "cp_groupnorm_backward_nhwc", "cp_gru_gate_forward", "cp_gru_gate_backward",
+            "cp_pose_targets_track_workspace_bytes", "cp_pose_targets_track"]
 
 
 def _check(rc, what):
@@ -1936,3 +1961,51 @@ def pose_targets(images, objects, S, R, flags, out):
     if rc == CP_ERR_INVALID:
         raise ValueError("centerpose_hip: cp_pose_targets: %s" % L.cp_last_error().decode())
     _check(rc, "cp_pose_targets")
+
+
+def pose_targets_track_desc(records, S, R, flags, track, out):
+    """cp_pose_targets_track_desc.  ``records``: the five host float64 arrays {'pt_image', 'pt_objects', 'ptk_image',
+    'ptk_pre_objects', 'ptk_cur_objects'} (kept alive by the caller); ``flags`` as pose_targets_desc's; ``track``
+    {PTK_GEOMETRY / PTK_FLAGS / PTK_DISTURB name: value} (max_pre_objs comes from the records); ``out`` {PT_OUTPUTS or
+    PTK_OUTPUTS name: tensor or None}."""
+    d = PoseTargetsTrackDesc()
+    d.cur = pose_targets_desc(records["pt_image"], records["pt_objects"], S, R, flags, out)
+    for n in PTK_GEOMETRY + PTK_FLAGS:
+        setattr(d, n, int(track.get(n, 0)))
+    d.max_pre_objs = records["ptk_pre_objects"].shape[1]
+    for n in PTK_DISTURB:
+        setattr(d, n, float(track.get(n, 0.0)))
+    d.track_images = records["ptk_image"].ctypes.data
+    d.pre_objects = records["ptk_pre_objects"].ctypes.data
+    d.cur_objects = records["ptk_cur_objects"].ctypes.data
+    for n in PTK_OUTPUTS:
+        t = out.get(n)
+        setattr(d, "out_" + n, t.data_ptr() if t is not None else None)
+    return d
+
+
+def pose_targets_track(records, S, R, flags, track, out):
+    """cp_pose_targets_track: the tracking task's training targets of a batch, written into the device tensors of ``out``
+    on the current stream (arguments as pose_targets_track_desc's; the records are converted to pageable float64 copies
+    here, which the call stages before it returns).  Refused arguments raise ValueError before any launch."""
+    import numpy as np
+
+    recs = {k: np.array(records[k], dtype=np.float64, order="C", copy=True)
+            for k in ("pt_image", "pt_objects", "ptk_image", "ptk_pre_objects", "ptk_cur_objects")}
+    B = recs["pt_image"].shape[0]
+    want = {"pt_image": (PT_IMG_STRIDE,), "pt_objects": (None, PT_OBJ_STRIDE), "ptk_image": (PTK_IMG_STRIDE,),
+            "ptk_pre_objects": (None, PTK_PRE_STRIDE), "ptk_cur_objects": (None, PTK_CUR_STRIDE)}
+    for k, tail in want.items():
+        a = recs[k]
+        if a.ndim != 1 + len(tail) or a.shape[0] != B or a.shape[-1] != tail[-1]:
+            raise ValueError("pose_targets_track: %s must be [B, %s]" % (k, ", ".join("K" if t is None else str(t) for t in tail)))
+    if recs["ptk_cur_objects"].shape[1] != recs["pt_objects"].shape[1]:
+        raise ValueError("pose_targets_track: ptk_cur_objects and pt_objects must have the same max_objs")
+    L = lib()
+    d = pose_targets_track_desc(recs, S, R, flags, track, out)
+    nbytes = L.cp_pose_targets_track_workspace_bytes(ctypes.byref(d))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=out["hm"].device) if nbytes else None
+    rc = L.cp_pose_targets_track(_stream(), ctypes.byref(d), _ptr(ws), nbytes)
+    if rc == CP_ERR_INVALID:
+        raise ValueError("centerpose_hip: cp_pose_targets_track: %s" % L.cp_last_error().decode())
+    _check(rc, "cp_pose_targets_track")

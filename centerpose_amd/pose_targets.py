@@ -20,8 +20,8 @@ from . import hip
 NUM_JOINTS = 8
 MAX_OBJS = 10  # ObjectPoseDataset.max_objs (dataset_combined.py:128)
 
-_REFUSED = (("tracking_task", "opt.tracking_task: the previous-frame targets depend on frame sampling, detector "
-                              "matching and random draws on the host"),
+_REFUSED = (("tracking_task", "opt.tracking_task: the previous-frame targets depend on frame sampling and random draws on "
+                              "the host; pose_targets_track.TrackPoseTargets builds them from packed draws"),
             ("pre_hm", "opt.pre_hm: a previous-frame render"),
             ("pre_hm_hp", "opt.pre_hm_hp: a previous-frame render"),
             ("tracking", "opt.tracking: needs the previous frame's matched centres"),
@@ -39,7 +39,7 @@ def num_symmetry(opt):
     return 1
 
 
-def pack_annotations(anns, trans_output_rot, width, height, flipped, rot, opt, max_objs=MAX_OBJS):
+def pack_annotations(anns, trans_output_rot, width, height, flipped, rot, opt, max_objs=MAX_OBJS, _nsym0=None):
     """The per-image records of cp_pose_targets (layouts in include/centerpose_hip.h), on the host in numpy:
     {'pt_image': float64 [32], 'pt_objects': float64 [max_objs, 64]}.  ``anns`` is the image's annotation JSON,
     ``trans_output_rot`` the 2x3 output affine, ``width`` / ``height`` the decoded image's size, ``flipped`` / ``rot`` the
@@ -56,7 +56,7 @@ def pack_annotations(anns, trans_output_rot, width, height, flipped, rot, opt, m
     img[I["flipped"]], img[I["rot"]], img[I["num_objs"]] = float(bool(flipped)), float(rot), n
     img[I["proj"]:I["proj"] + 16] = np.asarray(anns["camera_data"]["camera_projection_matrix"], np.float64).reshape(16)
     obj = np.zeros((max_objs, hip.PT_OBJ_STRIDE), np.float64)
-    nsym = S
+    nsym = S if _nsym0 is None else _nsym0  # pack_track_annotations: the count the previous frame's loop left
     for k in range(n):
         ann = objs[k]
         if "symmetric" in ann:
