@@ -221,6 +221,11 @@ struct ConvParams {
     const void* pj_w_lo;
     const float* pj_scale;
     const float* pj_shift;
+    // A second, 2x2 max-pooled copy of the output written by the launch that produces it (pw16.hip: pw16s_kernel's POOL
+    // instances, cp_pw16_pool_supported): NHWC [B, Ho / 2, Wo / 2, ldo], each value the maximum of the four activated outputs of
+    // its window -- what cp_launch_maxpool2 makes of `out`, without reading `out` back.  Its |max| is bounded by out_amax's.
+    // pool_out == nullptr: a plain launch.
+    float* pool_out;
 };
 
 int cp_launch_conv(const ConvParams& p, hipStream_t stream);
@@ -260,6 +265,7 @@ int cp_launch_dcn16(const ConvParams& p, int bn, hipStream_t stream);
 // dcn16p.hip: patch-resident DCNv2 (gather from an LDS-staged halo); N tile 64, or 128 where cp_dcn16p_wide says so
 // pw16.hip: 1x1 / stride-1 layers (incl. virtual concats) as a register-only stream, weight fragments from w16f_*
 bool cp_pw16_supported(const ConvParams& p);
+bool cp_pw16_pool_supported(const ConvParams& p);  // ... and can write ConvParams::pool_out (whole-line loads, Ho even, Wo % 16 == 0)
 int cp_launch_pw16(const ConvParams& p, hipStream_t stream);
 bool cp_dcn16p_supported(const ConvParams& p);
 int cp_dcn16p_blocks(const ConvParams& p);
@@ -323,7 +329,10 @@ size_t cp_lowc_weight_halfs(int kind);
 int cp_launch_pack_lowc(int kind, const float* w, void* hi, void* lo, const float* fwd, int cin, hipStream_t s);
 int cp_launch_lowc(int kind, const float* in, float* out, const void* w_hi, const void* w_lo, const float* scale,
                    const float* shift, const unsigned* in_amax, unsigned* out_amax, int B, int H, int W, int planes,
-                   hipStream_t s);
+                   hipStream_t s, float* pool_out = nullptr);
+// pool_out (kind 5 only, cp_lowc_pool_supported): NHWC [B][Ho / 2][Wo / 2][32] receives the 2x2 max-pooled copy of `out`, written
+// by the same launch (what cp_launch_maxpool2 makes of `out`); its |max| is bounded by out_amax's
+bool cp_lowc_pool_supported(int kind, int H, int W);
 #define CP_VARIANT_LOWC0 23
 // stem + level0 in one launch (lowc.hip: lowc2_kernel): the 16-channel full-resolution tensor between them is never stored
 #define CP_VARIANT_LOWC01 40

@@ -145,6 +145,7 @@ int cp_model_profile_roles(cp_model* m, double* out, int num_roles) {
 }
 
 size_t cp_model_workspace_used(const cp_model* m) { return m ? m->arena.peak : 0; }
+int cp_model_maxpool_launches(const cp_model* m) { return m ? m->maxpool2_launches : 0; }
 
 size_t cp_model_workspace_bytes(cp_model* m, int B, int H, int W) {
     if (!m) {
@@ -158,24 +159,28 @@ size_t cp_model_workspace_bytes(cp_model* m, int B, int H, int W) {
     // its own): every sequence a real pass can take is one of these, so its peak is at most the one returned here
     // (cp_model_workspace_used reads a real pass's back).
     if (m->ws_cached && m->ws_key[0] == B && m->ws_key[1] == H && m->ws_key[2] == W && m->ws_key[3] == g_dbg && m->finalized)
-        return m->ws_cached;   // (cp_model_detect asks on every call: up to 24 dry passes per frame would show in the batch-1 latency)
+        return m->ws_cached;   // (cp_model_detect asks on every call: up to 48 dry passes per frame would show in the batch-1 latency)
     size_t peak = 0;
     const char* const tap_before = m->tap_name;
     const int nu = m->ups_t.empty() ? 1 : 3;  // IDAUp forms (models without an IDAUp have one)
     const int np = m->convs.count("base.level2.project") ? 2 : 1;  // level-entry forms (models without DLA's entries have one)
-    for (int v = 0; v < 4 * nu * np; ++v) {
+    // ... and the stride-2 entries' pooled input (written by its producer, or by a maxpool2 launch: switches choose, and the caller
+    // may keep one buffer per shape across them)
+    for (int v = 0; v < 4 * nu * np * np; ++v) {
         const int up = (v >> 2) % nu;
         m->dry_variant = v & 1;
         m->tap_name = (v & 2) ? "" : nullptr;   // "" matches no tensor name: only the routing changes
         m->dry_no_upadd = up != 0;              // (a tap on an IDAUp node: its output has to exist)
         m->dry_boundary_upadd = up == 2;        // (... on a node other than dla_up's last: that one still stores ida_up's first u)
-        m->dry_no_project = v >= 4 * nu;        // (a tap on a level entry's projection: likewise)
+        m->dry_no_project = (v / (4 * nu)) % np == 1;  // (a tap on a level entry's projection: likewise)
+        m->dry_no_pool = v >= 4 * nu * np;
         const int rc = forward_impl(m, nullptr, B, H, W, nullptr, (const float*)1, (const float*)1, (const float*)1, nullptr, 0,
                                     nullptr, 0, true);
         m->dry_variant = 0;
         m->dry_no_upadd = false;
         m->dry_boundary_upadd = false;
         m->dry_no_project = false;
+        m->dry_no_pool = false;
         m->tap_name = tap_before;
         if (rc != CP_OK) return 0;
         if (m->arena.peak > peak) peak = m->arena.peak;

@@ -437,9 +437,14 @@ struct Fwd {
         return c.splitk == 1 && cp_conv16_project_supported(c);
     }
 
+    // pooled: the output feeds a stride-2 level entry.  Where the launch is a whole (not split-K) one on pw16s_kernel over a picture
+    // of even height and a width of whole 16-pixel blocks (cp_pw16_pool_supported: f16x3, not CP_SEL_PW16_FRAG_A / _NEVER, 32-bit
+    // offsets), it writes maxpool2(output) as well and *pooled receives that tensor; otherwise *pooled stays invalid and the entry
+    // launches maxpool2 as before.  Shapes and switches only: a dry run and the real pass decide alike.
     Tensor conv(const ConvW& w, const std::vector<const Tensor*>& srcs, int stride, int pad, int act,
                 const Tensor* res = nullptr, const Tensor* offmask = nullptr, int act_from = 0,
-                float* out_nchw = nullptr, int out_ld = 0, const UpFuse* up = nullptr, const ProjFuse* pj = nullptr) {
+                float* out_nchw = nullptr, int out_ld = 0, const UpFuse* up = nullptr, const ProjFuse* pj = nullptr,
+                Tensor* pooled = nullptr) {
         const Tensor& x0 = *srcs[0];
         const int nsrc = (int)srcs.size();
         const float* src[CP_MAX_SRC];
@@ -500,6 +505,14 @@ struct Fwd {
             partial = make(p.splitk * p.CoutPad, p.Ho, p.Wo);
             p.partial = partial.ptr();
         }
+        if (pooled && use16 && !out_nchw && p.splitk == 1 && !up && !pj && !m->dry_no_pool) {
+            const int v = cp_conv16_variant(p);
+            if ((v == CP_VARIANT_PW16 || v == CP_VARIANT_PW16 + 1) && cp_pw16_pool_supported(p)) {
+                *pooled = make(p.ldo, p.Ho / 2, p.Wo / 2);
+                pooled->amax = out.amax;  // max|maxpool(x)| <= max|x|: the output's slot is a valid bound (maxpool())
+                p.pool_out = m->dry ? (float*)0x1000 : pooled->ptr();
+            }
+        }
         if (up) {
             p.up_t = up->t->ptr();
             p.up_wt = up->wt;
@@ -534,7 +547,7 @@ struct Fwd {
                 r.bytes = 4.0 * ((double)B * x0.H * x0.W * cin_real + M * w.Cout +
                                  (double)w.KH * w.KW * cin_real * w.Cout + (offmask ? M * 27 : 0.0) +
                                  (res ? M * w.Cout : 0.0) + (up ? (double)B * up->t->H * up->t->W * w.Cout : 0.0) +
-                                 (pj ? (M + w.Cout) * (double)pj->w->Cin : 0.0));
+                                 (pj ? (M + w.Cout) * (double)pj->w->Cin : 0.0) + (p.pool_out ? M / 4 * w.Cout : 0.0));
                 r.M = (int)M; r.N = w.Cout; r.K = w.KH * w.KW * cin_real; r.kh = w.KH; r.stride = stride;
             }, launch);
         gn_stats_out = nullptr;
@@ -550,6 +563,7 @@ struct Fwd {
     Tensor maxpool(const Tensor& x) {
         Tensor o = make(x.C, x.H / 2, x.W / 2);
         o.amax = x.amax;  // max|maxpool(x)| <= max|x|: the input's slot is a valid bound
+        ++m->maxpool2_launches;
         if (!m->dry) chk(cp_launch_maxpool2(x.ptr(), o.ptr(), B, x.H, x.W, x.C, s));
         return o;
     }
@@ -564,9 +578,10 @@ struct Fwd {
     }
 
     // one-level Tree (Tree.forward with levels == 1); `bottom` may be supplied by the caller when it
-    // already computed maxpool(x) (the outer two-level tree needs the same tensor as a root child)
+    // already has maxpool(x) (the outer two-level tree needs the same tensor as a root child; x's producer wrote it: conv(), lowc())
+    // pool_next: the root's output feeds a stride-2 entry (conv(): pooled)
     Tensor tree1(const std::string& p, const Tensor& x, int cin, int cout, int stride, bool level_root,
-                 std::vector<const Tensor*> children, const Tensor* bottom_in = nullptr) {
+                 std::vector<const Tensor*> children, const Tensor* bottom_in = nullptr, Tensor* pool_next = nullptr) {
         Tensor bottom_own;
         const Tensor* bottom = &x;
         if (stride > 1) {
@@ -575,6 +590,7 @@ struct Fwd {
                 bottom_own = maxpool(x);
                 bottom = &bottom_own;
             }
+            tap(p + ".bottom", *bottom);
         }
         Tensor proj;
         const Tensor* residual = bottom;
@@ -597,15 +613,16 @@ struct Fwd {
         Tensor x2 = basic_block(p + ".tree2", x1, 1, &x1);
         std::vector<const Tensor*> srcs = {&x2, &x1};
         for (auto* c : children) srcs.push_back(c);
-        Tensor o = conv(cw(p + ".root"), srcs, 1, 0, CP_ACT_RELU);
+        Tensor o = conv(cw(p + ".root"), srcs, 1, 0, CP_ACT_RELU, nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr, pool_next);
         tap(p + ".root", o);
         return o;
     }
-    // two-level Tree with level_root = true (base.level3 / base.level4)
-    Tensor tree2(const std::string& p, const Tensor& x, int cin, int cout) {
-        Tensor bottom = maxpool(x);
+    // two-level Tree with level_root = true (base.level3 / base.level4); bottom_in: maxpool(x) where x's producer wrote it
+    Tensor tree2(const std::string& p, const Tensor& x, int cin, int cout, const Tensor& bottom_in, Tensor* pool_next) {
+        Tensor bottom = bottom_in.valid() ? bottom_in : maxpool(x);
+        tap(p + ".bottom", bottom);
         Tensor x1 = tree1(p + ".tree1", x, cin, cout, 2, false, {}, &bottom);
-        return tree1(p + ".tree2", x1, cout, cout, 1, false, {&bottom, &x1});
+        return tree1(p + ".tree2", x1, cout, cout, 1, false, {&bottom, &x1}, nullptr, pool_next);
     }
 
     // up: the node's epilogue adds IDAUp's next up-sampled tensor; what comes back is that sum (conv(): UpFuse)
@@ -678,7 +695,10 @@ struct Fwd {
     }
 
     // the network's first layers through lowc.hip (f16x3 mode only); returns an invalid Tensor when not applicable
-    Tensor lowc(const std::string& name, int kind, const float* in, int H, int W, int planes, const unsigned* in_amax) {
+    // pooled (level1): the output feeds level2's stride-2 entry; where the row-streaming kernel runs over an output of even height
+    // and width it writes maxpool2(output) as well and *pooled receives it (conv(): pooled -- the same contract)
+    Tensor lowc(const std::string& name, int kind, const float* in, int H, int W, int planes, const unsigned* in_amax,
+                Tensor* pooled = nullptr) {
         if (m->precision != CP_PREC_F16X3 || (g_dbg & CP_SEL_NO_LOWC)) return Tensor();
         const int Ho = kind == 2 ? (H - 1) / 2 + 1 : H, Wo = kind == 2 ? (W - 1) / 2 + 1 : W;
         // level1: the row-streaming kernel (lowc1s_kernel, kind 5) from the batch at which bands of >= 8 output rows give every wave
@@ -693,17 +713,22 @@ struct Fwd {
         const bool l1 = kind == 2 || kind == 5;
         const int cout = l1 ? 32 : 16, cin = stem ? planes : 16, k = stem ? 7 : 3;
         Tensor out = make(cout, Ho, Wo);
+        const bool pool = pooled && !m->dry_no_pool && cp_lowc_pool_supported(kind, H, W);
+        if (pool) {
+            *pooled = make(cout, Ho / 2, Wo / 2);
+            pooled->amax = out.amax;  // (maxpool(): the output's slot is a valid bound)
+        }
         if (m->dry) return out;
         auto launch = [&]() {
             return cp_launch_lowc(kind, in, out.ptr(), it->second.hi, it->second.lo, it->second.scale16, w.shift, in_amax,
-                                  out.amax, B, H, W, planes, s);
+                                  out.amax, B, H, W, planes, s, pool ? pooled->ptr() : nullptr);
         };
         timed([&](cp_model::ProfRec& r) {
             r.variant = kind == 5 ? CP_VARIANT_LOWC1S : CP_VARIANT_LOWC0 + (kind == 3 ? 0 : kind);
             r.role = CP_ROLE_LOWC;
             const double M = (double)B * Ho * Wo;
             r.flops = 2.0 * M * cout * (double)(k * k * cin);
-            r.bytes = 4.0 * ((double)B * H * W * cin + M * cout + (double)k * k * cin * cout);
+            r.bytes = 4.0 * ((double)B * H * W * cin + M * cout + (double)k * k * cin * cout + (pool ? M / 4 * cout : 0.0));
             r.M = (int)M; r.N = cout; r.K = k * k * cin; r.kh = k; r.stride = l1 ? 2 : 1;
         }, launch);
         return out;
@@ -931,16 +956,22 @@ struct Fwd {
         if (!l0.valid()) l0 = conv(cw("base.level0"), {&x0}, 1, 1, CP_ACT_RELU);
         tap("base.level0", l0);
         x0 = Tensor();
-        Tensor l1 = lowc("base.level1", 2, l0.ptr(), H, W, 16, l0.amax);
+        // the 2x2 max-pooled copy each stride-2 entry reads (Tree.downsample), written by the launch that produces the entry's
+        // input where it can (lowc(), conv(): pooled); an invalid one makes the entry launch maxpool2
+        Tensor pl[4];
+        Tensor l1 = lowc("base.level1", 2, l0.ptr(), H, W, 16, l0.amax, &pl[0]);
         if (!l1.valid()) l1 = conv(cw("base.level1"), {&l0}, 2, 1, CP_ACT_RELU);
         tap("base.level1", l1);
         l0 = Tensor();
         std::vector<Tensor> L(6);
-        L[2] = tree1("base.level2", l1, 32, 64, 2, false, {});
-        l1 = Tensor();
-        L[3] = tree2("base.level3", L[2], 64, 128);
-        L[4] = tree2("base.level4", L[3], 128, 256);
-        L[5] = tree1("base.level5", L[4], 256, 512, 2, true, {});
+        L[2] = tree1("base.level2", l1, 32, 64, 2, false, {}, pl[0].valid() ? &pl[0] : nullptr, &pl[1]);
+        l1 = pl[0] = Tensor();
+        L[3] = tree2("base.level3", L[2], 64, 128, pl[1], &pl[2]);
+        pl[1] = Tensor();
+        L[4] = tree2("base.level4", L[3], 128, 256, pl[2], &pl[3]);
+        pl[2] = Tensor();
+        L[5] = tree1("base.level5", L[4], 256, 512, 2, true, {}, pl[3].valid() ? &pl[3] : nullptr);
+        pl[3] = Tensor();
         tap("base.level2", L[2]);
         tap("base.level3", L[3]);
         tap("base.level4", L[4]);
@@ -1133,6 +1164,7 @@ int cp_engine::forward_impl(cp_model* m, hipStream_t stream, int B, int H, int W
     m->arena.reset(dry ? nullptr : ws, ws_bytes);
     m->dry = dry;
     m->status = CP_OK;
+    m->maxpool2_launches = 0;
     Fwd f{m, B, stream};
     if (m->hourglass) f.run_hourglass(H, W, images, head_out, sigmoid_hm);
     else if (m->resnet) f.run_resnet(H, W, images, head_out, sigmoid_hm);

@@ -232,6 +232,7 @@ struct cp_model {
     bool dry_no_upadd = false;  // work-space query: the IDAUp sequence without the up-sample + add epilogues (a tap on a node selects it)
     bool dry_boundary_upadd = false;  // ... with dry_no_upadd: all but the site between dla_up and ida_up (a tap on another node than its own)
     bool dry_no_project = false;  // work-space query: the level entries with their projection as a launch of its own (a tap on it selects that)
+    bool dry_no_pool = false;  // work-space query: every stride-2 entry with its maxpool2 launch (no producer writes the pooled copy)
     int dry_variant = 0;  // work-space query: 1 = the dry run takes the fused stem + level0 path where the model allows it (the query
                           // runs both forms and returns the larger peak: switches and taps may select either form later)
     float stem_bound_l = 0.f, stem_bound_s = 0.f;  // |base_layer out| <= stem_bound_l * max|image| + stem_bound_s (fused stem + level0)
@@ -249,6 +250,7 @@ struct cp_model {
     int B = 0;
     bool dry = false;
     int status = CP_OK;
+    int maxpool2_launches = 0;  // stand-alone 2x2 max-pool launches of the last pass, dry or real (cp_model_maxpool_launches)
     const char* tap_name = nullptr;
     float* tap_out = nullptr;
     int* tap_dims = nullptr;

@@ -725,6 +725,9 @@ int cp_launch_conv16(const ConvParams& p, hipStream_t stream) {
     // the up-sample + add epilogue (ConvParams::up_t) exists in dcn16t only: a launch that would go elsewhere is an error
     if (p.up_t && !(p.offmask && dcn16t_wanted(p) && cp_dcn16t_upadd_supported(p))) return CP_ERR_INVALID;
     const int bn = conv16_tile_n(p);
+    // ... the 2x2 max-pooled second output (ConvParams::pool_out) in pw16s_kernel only
+    if (p.pool_out && !(pw16_wanted(p) && cp_conv16_variant(p) == CP_VARIANT_PW16 + (p.CoutPad % 128 == 0 ? 1 : 0) && cp_pw16_pool_supported(p)))
+        return CP_ERR_INVALID;
     // ... and the 1x1 projection as the residual (ConvParams::pj_src) in halo16's 64- and 128-wide tiles only
     if (p.pj_src) return cp_conv16_project_supported(p) ? cp_launch_halo16(p, bn, stream) : CP_ERR_INVALID;
     const bool cat = p.nsrc > 1;

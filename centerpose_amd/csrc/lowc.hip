@@ -555,8 +555,16 @@ struct Lowc1Params {
     const unsigned* in_amax;
     unsigned* out_amax;
     int B, H, W, Ho, Wo, rows, strips, bands, njobs;
+    float* pool;       // POOL: NHWC [B][Ho / 2][Wo / 2][32], the 2x2 max-pooled copy of `out`
 };
 
+// POOL (the output feeds level2, a stride-2 entry whose Tree.downsample is MaxPool2d(2, 2)): a wave finishes its output rows in
+// order, and with even band heights the row pairs of the pooling never straddle two jobs.  The activated even row stays in
+// registers (16 floats), the next odd row is folded into it, the maxima pass through the same transposition rows after the odd
+// row's own store has read them, and lane l takes quad l % 8 of pixels 2 q and 2 q + 1, q = l / 8 + 8 i: eight lanes store one
+// pooled pixel's 128-byte line.  No new LDS, no workgroup barrier, no branch in the row loop (which of a turn's two odd rows keeps
+// and which folds and stores is fixed: a band starts on an even output row); Ho and Wo must be even.
+template <bool POOL>
 __global__ __launch_bounds__(64 * L1_WAVES, 1) void lowc1s_kernel(const Lowc1Params p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char l1_smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -610,6 +618,11 @@ __global__ __launch_bounds__(64 * L1_WAVES, 1) void lowc1s_kernel(const Lowc1Par
                                                                             (int)((unsigned)p.H * (unsigned)p.W * 64u), 0x00020000);
         const __amdgpu_buffer_rsrc_t r_out = __builtin_amdgcn_make_buffer_rsrc(p.out + (size_t)b * p.Ho * p.Wo * 32, 0,
                                                                              (int)((unsigned)p.Ho * (unsigned)p.Wo * 128u), 0x00020000);
+        const __amdgpu_buffer_rsrc_t r_pool = __builtin_amdgcn_make_buffer_rsrc(
+            POOL ? p.pool + (size_t)b * (p.Ho >> 1) * (p.Wo >> 1) * 32 : p.out, 0, POOL ? (int)((unsigned)(p.Ho >> 1) * (unsigned)(p.Wo >> 1) * 128u) : 0, 0x00020000);
+        float4 keep[4];   // POOL: the activated even output row of this lane's pixel, then the maximum with the odd row below it
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4) keep[g4] = make_float4(0.f, 0.f, 0.f, 0.f);
         unsigned cvo[L1_NLD];
 #pragma unroll
         for (int k = 0; k < L1_NLD; ++k) {
@@ -664,7 +677,8 @@ __global__ __launch_bounds__(64 * L1_WAVES, 1) void lowc1s_kernel(const Lowc1Par
             }
         };
         // odd input row j = 2 y + 1: closes output row y (kernel row 2), stores it, and opens row y + 1 (kernel row 0)
-        auto odd_row = [&](const int j, float4 (&buf)[L1_NLD]) {
+        // (fold: POOL only -- false, the row is an even output row and is kept; true, an odd one: folded into the kept row and stored)
+        auto odd_row = [&](const int j, float4 (&buf)[L1_NLD], const bool fold) {
             stage(j, buf);
             mac(2, acc);
             f32x16 nxt;
@@ -687,6 +701,14 @@ __global__ __launch_bounds__(64 * L1_WAVES, 1) void lowc1s_kernel(const Lowc1Par
                 y.w = fmaxf(acc[4 * g4 + 3] * sc[g4].w + sh[g4].w, 0.f);
                 amax = fmaxf(amax, fmaxf(fmaxf(y.x, y.y), fmaxf(y.z, y.w)) * okf);
                 *reinterpret_cast<float4*>(tr_b + px * L1_TPITCH + (2 * g4 + kg) * 16) = y;
+                if (POOL) {
+                    if (fold) {
+                        keep[g4].x = fmaxf(keep[g4].x, y.x); keep[g4].y = fmaxf(keep[g4].y, y.y);
+                        keep[g4].z = fmaxf(keep[g4].z, y.z); keep[g4].w = fmaxf(keep[g4].w, y.w);
+                    } else {
+                        keep[g4] = y;
+                    }
+                }
             }
             __builtin_amdgcn_wave_barrier();
             // (the two "no store" marks are OR-ed in AFTER the sum: added, a masked row and a masked column would wrap into range)
@@ -699,6 +721,24 @@ __global__ __launch_bounds__(64 * L1_WAVES, 1) void lowc1s_kernel(const Lowc1Par
                 __builtin_amdgcn_raw_buffer_store_b128(pk, r_out, (int)((row_out + (unsigned)((x0 + pxo) * 128 + (lane & 7) * 16)) | row_no | col_no), 0, 0);
             }
             __builtin_amdgcn_wave_barrier();
+            if (POOL && fold) {
+                // the column maxima of rows o - 1 and o through the same rows (their full-resolution values have been read above)
+#pragma unroll
+                for (int g4 = 0; g4 < 4; ++g4) *reinterpret_cast<float4*>(tr_b + px * L1_TPITCH + (2 * g4 + kg) * 16) = keep[g4];
+                __builtin_amdgcn_wave_barrier();
+                const unsigned prow_out = (unsigned)((o >> 1) * (p.Wo >> 1)) * 128u;
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    const int q = (lane >> 3) + 8 * i;
+                    const float4 a = *reinterpret_cast<const float4*>(tr_b + (2 * q) * L1_TPITCH + (lane & 7) * 16);
+                    const float4 c = *reinterpret_cast<const float4*>(tr_b + (2 * q + 1) * L1_TPITCH + (lane & 7) * 16);
+                    const u32x4 pk = {__float_as_uint(fmaxf(a.x, c.x)), __float_as_uint(fmaxf(a.y, c.y)), __float_as_uint(fmaxf(a.z, c.z)),
+                                      __float_as_uint(fmaxf(a.w, c.w))};
+                    const unsigned col_no = (x0 >> 1) + q < (p.Wo >> 1) ? 0u : 0x80000000u;
+                    __builtin_amdgcn_raw_buffer_store_b128(pk, r_pool, (int)((prow_out + (unsigned)(((x0 >> 1) + q) * 128 + (lane & 7) * 16)) | row_no | col_no), 0, 0);
+                }
+                __builtin_amdgcn_wave_barrier();
+            }
             acc = nxt;
         };
         auto even_row = [&](const int j, float4 (&buf)[L1_NLD]) {
@@ -708,9 +748,9 @@ __global__ __launch_bounds__(64 * L1_WAVES, 1) void lowc1s_kernel(const Lowc1Par
         };
         // rows 2 y0 - 1 .. 2 y1 - 1, four per turn; what a turn runs past the band is neither fetched nor stored
         for (int j = 2 * y0 - 1; j <= jlast; j += 4) {
-            odd_row(j, pf[0]);
+            odd_row(j, pf[0], true);    // closes output row y0 - 1 + 2 t: odd (the first turn's: before the band, masked)
             even_row(j + 1, pf[1]);
-            odd_row(j + 2, pf[2]);
+            odd_row(j + 2, pf[2], false);
             even_row(j + 3, pf[3]);
         }
     }
@@ -792,9 +832,16 @@ int cp_launch_lowc_fused(const float* in, float* out, const void* w0_hi, const v
     return hipGetLastError() == hipSuccess ? CP_OK : CP_ERR_LAUNCH;
 }
 
+// the row-streaming level1 kernel (kind 5) can write the 2x2 max-pooled copy of its output: even output height and width (its band
+// heights are even: 8 .. 64 rows)
+bool cp_lowc_pool_supported(int kind, int H, int W) {
+    return kind == 5 && ((H + 2 - 3) / 2 + 1) % 2 == 0 && ((W + 2 - 3) / 2 + 1) % 2 == 0;
+}
+
 int cp_launch_lowc(int kind, const float* in, float* out, const void* w_hi, const void* w_lo, const float* scale,
                    const float* shift, const unsigned* in_amax, unsigned* out_amax, int B, int H, int W, int planes,
-                   hipStream_t s) {
+                   hipStream_t s, float* pool_out) {
+    if (pool_out && !cp_lowc_pool_supported(kind, H, W)) return CP_ERR_INVALID;
     LowcParams p;
     p.in_amax = in_amax;
     p.out_amax = out_amax;
@@ -838,7 +885,8 @@ int cp_launch_lowc(int kind, const float* in, float* out, const void* w_hi, cons
         if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return CP_ERR_LAUNCH;
         if (!cus_of[dev]) {
             hipDeviceProp_t prop;
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&lowc1s_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, L1_LDS) != hipSuccess)
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&lowc1s_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, L1_LDS) != hipSuccess ||
+                hipFuncSetAttribute(reinterpret_cast<const void*>(&lowc1s_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, L1_LDS) != hipSuccess)
                 return CP_ERR_LAUNCH;
             cus_of[dev] = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
         }
@@ -860,7 +908,9 @@ int cp_launch_lowc(int kind, const float* in, float* out, const void* w_hi, cons
         q.bands = (q.Ho + rows - 1) / rows;
         q.njobs = B * q.strips * q.bands;
         const int blocks = (q.njobs + L1_WAVES - 1) / L1_WAVES < use_cus ? (q.njobs + L1_WAVES - 1) / L1_WAVES : use_cus;
-        hipLaunchKernelGGL(lowc1s_kernel, dim3(blocks), dim3(64 * L1_WAVES), L1_LDS, s, q);
+        q.pool = pool_out;
+        if (pool_out) hipLaunchKernelGGL(lowc1s_kernel<true>, dim3(blocks), dim3(64 * L1_WAVES), L1_LDS, s, q);
+        else hipLaunchKernelGGL(lowc1s_kernel<false>, dim3(blocks), dim3(64 * L1_WAVES), L1_LDS, s, q);
         return hipGetLastError() == hipSuccess ? CP_OK : CP_ERR_LAUNCH;
     }
     return CP_ERR_INVALID;

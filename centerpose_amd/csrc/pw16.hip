@@ -152,7 +152,61 @@ constexpr int PA = 3;              // A chunk register sets = 32-channel chunks 
 constexpr int PW_PITCH = 80;       // bytes per pixel and plane of the staging rows (32 halfs + 16 B)
 constexpr int PW_PLANE = 32 * PW_PITCH;
 
+//
+// POOL (ConvParams::pool_out: the launch's output feeds a stride-2 level entry, whose Tree.downsample is MaxPool2d(2, 2)).  A 1x1
+// convolution does not care which 32 pixels a wave owns, so a POOL wave takes a 2 x 16 block of the picture instead of 32
+// consecutive pixels: 32-row group g = 4 tm + wid is pair-row g / (W / 16) (counted over B H / 2; H is even, so a pair never
+// spans two images) and column block g % (W / 16), fragment row r pixel (2 pair_row + (r >> 4)) W + 16 block + (r & 15).  The four
+// loads of a chunk keep wave-uniform scalar offsets (0, 8, W and W + 8 pixels).  Every output element depends on its own A row and
+// B column only, so the full-resolution values are the plain launch's bit for bit; in the 32 x 32 accumulator layout fragment rows
+// m, m + 1, m + 16 and m + 17 are registers r, r + 1, r + 8 and r + 9 (r = 0, 2, 4, 6) of one lane -- a whole 2x2 window -- so
+// after the usual epilogue a lane takes four maxima per N fragment and stores them where 32 lanes write one pooled pixel's 128-byte
+// line.  The stand-alone max-pool launch (a read of the whole tensor, a write of a quarter) does not exist.
 template <int NT>
+__device__ __forceinline__ void pw16s_pool_epilogue(const ConvParams& p, f32x16 (&acc)[1][NT], const int tn, const int lane, const float ainv,
+                                                    const bool live, const int pair_row, const int blk) {
+    const int lcol = lane & 31, h = lane >> 5, W = p.Wo;
+    const bool relu = p.act == CP_ACT_RELU;
+    float amax = 0.f;
+    if (live) {  // wave-uniform
+        // full resolution: the block's first pixel in the descriptor; a register's pixel rides in the scalar offset, the lane's
+        // column (4 h) and channel in the lane offset.  Pooled: pixel pair_row (W / 2) + 8 block + {2 h, 2 h + 1, 2 h + 4, 2 h + 5}
+        const size_t base = (size_t)(2 * pair_row) * W + 16 * blk;
+        const __amdgpu_buffer_rsrc_t ro = make_rsrc(p.out + base * p.ldo, (unsigned)((W + 16) * p.ldo) * 4u);
+        const __amdgpu_buffer_rsrc_t rp = make_rsrc(p.pool_out + ((size_t)pair_row * (W >> 1) + 8 * blk) * p.ldo, (unsigned)(8 * p.ldo) * 4u);
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+            const int n = tn * (32 * NT) + j * 32 + lcol;
+            const float sc = (p.scale ? p.scale[n] : 1.f) * ainv;
+            const float sh = p.shift ? p.shift[n] : 0.f;
+            const bool n_ok = n < p.Cout;
+            float v[16];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) v[r] = acc[0][j][r] * sc + sh;
+            if (relu) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) v[r] = fmaxf(v[r], 0.f);
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) amax = fmaxf(amax, fabsf(v[r]));
+            // a masked lane stays out of range with or without the scalar offset added
+            const unsigned vo = n_ok ? (unsigned)(4 * h * p.ldo + n) * 4u : 0x80000000u;
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[r]), ro, (int)vo, ((r >> 3) * W + (r & 3) + 8 * ((r >> 2) & 1)) * p.ldo * 4, 0);
+            const unsigned vp = n_ok ? (unsigned)(2 * h * p.ldo + n) * 4u : 0x80000000u;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int r = 2 * q;  // (row 0, column c), (0, c + 1), (1, c), (1, c + 1): maxpool2_kernel's order
+                const float mx = fmaxf(fmaxf(v[r], v[r + 1]), fmaxf(v[r + 8], v[r + 9]));
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(mx), rp, (int)vp, ((q & 1) + 4 * (q >> 1)) * p.ldo * 4, 0);
+            }
+        }
+    }
+    if (p.out_amax) cp_amax_commit(p.out_amax, amax);
+}
+
+template <int NT, bool POOL>
 __global__ __launch_bounds__(256, NT == 2 ? 3 : 2) void pw16s_kernel(const ConvParams p, const int tiles_m, const int tiles_n) {
     typedef Frag<32> F;
     typedef F::acc_t acc_t;
@@ -168,13 +222,18 @@ __global__ __launch_bounds__(256, NT == 2 ? 3 : 2) void pw16s_kernel(const ConvP
     unsigned char* st_lo = st_hi + PW_PLANE;
 
     // ---- A: piece c4 = lane % 8 (16 bytes = 4 channels) of pixels lane / 8 + 8 i, i = 0 .. 3 ----
-    const int c4 = lane & 7, row0 = tm * 128 + wid * 32 + (lane >> 3);
+    // (POOL: the wave's 2 x 16 block -- pixels lane / 8 and lane / 8 + 8 of its two picture rows; a group behind the last one of
+    // a ragged last tile loads and stores nothing)
+    const int grp = 4 * tm + wid, wblk = POOL ? p.Wo >> 4 : 1;
+    const int pair_row = POOL ? grp / wblk : 0, blk = POOL ? grp - pair_row * wblk : 0;
+    const bool live = !POOL || pair_row < p.B * (p.Ho >> 1);
+    const int c4 = lane & 7, row0 = POOL ? 2 * pair_row * p.Wo + 16 * blk + (lane >> 3) : tm * 128 + wid * 32 + (lane >> 3);
     const int n0 = p.src_c[0] >> 5, n1 = p.nsrc > 1 ? p.src_c[1] >> 5 : 0, n2 = p.nsrc > 2 ? p.src_c[2] >> 5 : 0;  // chunks per source
     const __amdgpu_buffer_rsrc_t r0 = make_rsrc(p.src[0], (unsigned)M * (unsigned)p.src_c[0] * 4u);
     const __amdgpu_buffer_rsrc_t r1 = make_rsrc(p.nsrc > 1 ? p.src[1] : p.src[0], p.nsrc > 1 ? (unsigned)M * (unsigned)p.src_c[1] * 4u : 0u);
     const __amdgpu_buffer_rsrc_t r2 = make_rsrc(p.nsrc > 2 ? p.src[2] : p.src[0], p.nsrc > 2 ? (unsigned)M * (unsigned)p.src_c[2] * 4u : 0u);
     const __amdgpu_buffer_rsrc_t r3 = make_rsrc(p.nsrc > 3 ? p.src[3] : p.src[0], p.nsrc > 3 ? (unsigned)M * (unsigned)p.src_c[3] * 4u : 0u);
-    const int GC = p.Kpad16 >> 5;  // 32-channel chunks
+    const int GC = live ? p.Kpad16 >> 5 : 0;  // 32-channel chunks
 
     const unsigned w_bytes = (unsigned)((size_t)p.CoutPad * p.Kpad16 * 2);
     const __amdgpu_buffer_rsrc_t r_wh = make_rsrc(p.w16f_hi, w_bytes), r_wl = make_rsrc(p.w16f_lo, w_bytes);
@@ -190,7 +249,8 @@ __global__ __launch_bounds__(256, NT == 2 ? 3 : 2) void pw16s_kernel(const ConvP
         // are beyond the descriptor (the range check counts the scalar offset in: cp_common.h's architecture guard) -> zeros
         const unsigned v = (unsigned)row0 * (unsigned)(cs * 4) + (unsigned)(c4 * 16);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) dst[i] = __builtin_amdgcn_raw_buffer_load_b128(r, (int)v, kk * 128 + i * 8 * cs * 4, 0);
+        for (int i = 0; i < 4; ++i)
+            dst[i] = __builtin_amdgcn_raw_buffer_load_b128(r, (int)v, kk * 128 + (POOL ? (i >> 1) * p.Wo + (i & 1) * 8 : i * 8) * cs * 4, 0);
     };
     auto issue_a = [&](int set, int c) {  // chunk c -> (source, chunk inside it): wave-uniform scalar work
         if (c >= GC) return;
@@ -269,14 +329,16 @@ __global__ __launch_bounds__(256, NT == 2 ? 3 : 2) void pw16s_kernel(const ConvP
             }
         }
     }
-    igemm_epilogue<32, 1, NT, 4, 1>(p, acc, tm, tn, wid, 0, lane, ainv);
+    if (POOL) pw16s_pool_epilogue<NT>(p, acc, tn, lane, ainv, live, pair_row, blk);
+    else igemm_epilogue<32, 1, NT, 4, 1>(p, acc, tm, tn, wid, 0, lane, ainv);
 }
 
 template <int NT>
 int launch_pw16s(const ConvParams& p, hipStream_t stream) {
     const int M = p.B * p.Ho * p.Wo;
     const int tiles_m = (M + 127) / 128, tiles_n = p.CoutPad / (32 * NT);
-    hipLaunchKernelGGL((pw16s_kernel<NT>), dim3(tiles_m * tiles_n), dim3(256), 0, stream, p, tiles_m, tiles_n);
+    if (p.pool_out) hipLaunchKernelGGL((pw16s_kernel<NT, true>), dim3(tiles_m * tiles_n), dim3(256), 0, stream, p, tiles_m, tiles_n);
+    else hipLaunchKernelGGL((pw16s_kernel<NT, false>), dim3(tiles_m * tiles_n), dim3(256), 0, stream, p, tiles_m, tiles_n);
     return hipGetLastError() == hipSuccess ? CP_OK : CP_ERR_LAUNCH;
 }
 
@@ -309,8 +371,16 @@ bool cp_pw16_supported(const ConvParams& p) {
     return c == p.Cin && (size_t)p.CoutPad * p.Kpad16 * 2 < (size_t)0x7fffffff && M * p.ldo * 4 < (size_t)0xf0000000u;
 }
 
+// ... and ConvParams::pool_out: pw16s_kernel (not its A/B partner) with the plain epilogue's NHWC store (scale, shift, ReLU; no
+// residual, no statistics), whole 2 x 16 blocks of the picture
+bool cp_pw16_pool_supported(const ConvParams& p) {
+    if (!cp_pw16_supported(p) || (p.dbg & CP_SEL_PW16_FRAG_A)) return false;
+    if (p.res || p.gn_stats || p.store != CP_STORE_NHWC || p.coff != 0 || (p.act != CP_ACT_NONE && p.act != CP_ACT_RELU)) return false;
+    return p.Ho % 2 == 0 && p.Wo % 16 == 0;
+}
+
 int cp_launch_pw16(const ConvParams& p, hipStream_t stream) {
-    if (!cp_pw16_supported(p)) return CP_ERR_INVALID;
+    if (!cp_pw16_supported(p) || (p.pool_out && !cp_pw16_pool_supported(p))) return CP_ERR_INVALID;
     // whole-line A loads through wave-private staging rows (CP_SEL_PW16_FRAG_A: the fragment-shaped loads of pw16_kernel, A/B runs)
     if (!(p.dbg & CP_SEL_PW16_FRAG_A)) return p.CoutPad % 128 == 0 ? launch_pw16s<4>(p, stream) : launch_pw16s<2>(p, stream);
     return p.CoutPad % 128 == 0 ? launch_pw16<4>(p, stream) : launch_pw16<2>(p, stream);

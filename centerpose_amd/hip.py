@@ -142,6 +142,7 @@ def lib():
     _sig(L.cp_model_destroy, None, c_void_p)
     _sig(L.cp_model_workspace_bytes, c_size_t, c_void_p, c_int, c_int, c_int)
     _sig(L.cp_model_workspace_used, c_size_t, c_void_p)
+    _sig(L.cp_model_maxpool_launches, c_int, c_void_p)
     _sig(L.cp_model_forward, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
          ctypes.POINTER(c_void_p), c_int, c_void_p, c_size_t)
     _sig(L.cp_model_forward_tap, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
@@ -254,6 +255,7 @@ def exported_symbols():
     """Names every declaration in include/centerpose_hip.h (+ the test hook of centerpose_hip_testing.h) must resolve to (used by CPU tests)."""
     return ["cp_version", "cp_last_error", "cp_dcnv2_workspace_bytes", "cp_dcnv2_forward", "cp_model_create",
             "cp_model_set_param", "cp_model_finalize", "cp_model_destroy", "cp_model_workspace_bytes", "cp_model_workspace_used",
+            "cp_model_maxpool_launches",
             "cp_model_forward", "cp_model_forward_tap", "cp_conv2d_workspace_bytes", "cp_conv2d_nhwc",
             "cp_decode_workspace_bytes", "cp_decode", "cp_pnp_workspace_bytes", "cp_pnp_solve", "cp_model_profile", "cp_model_profile_read",
             "cp_kernel_variant_name", "cp_set_default_precision", "cp_model_set_precision", "cp_model_detect_workspace_bytes", "cp_model_detect", "cp_set_debug", "cp_preprocess", "cp_preprocess_batch", "cp_postprocess_workspace_bytes", "cp_postprocess", "cp_render_gaussians",
@@ -1594,6 +1596,11 @@ class HipModel(object):
     def workspace_used(self):
         """Bytes of the work space the last pass reached (cp_model_workspace_used): at most workspace_bytes() of its shape."""
         return int(lib().cp_model_workspace_used(self._h))
+
+    def maxpool_launches(self):
+        """Stand-alone 2x2 max-pool launches of the last pass (cp_model_maxpool_launches): the stride-2 level entries whose pooled
+        input was not written by its producer."""
+        return int(lib().cp_model_maxpool_launches(self._h))
 
     def _workspace(self, B, H, W, device):
         key = (B, H, W, str(device))

@@ -170,6 +170,9 @@ size_t cp_model_workspace_bytes(cp_model* m, int B, int H, int W);
 /* Bytes of that scratch the last pass over m reached (a forward / detect call, or the last dry pass of the query above); 0 before
  * the first.  The launch sequence depends on taps and switches; whatever it was, this is at most what the query returned. */
 size_t cp_model_workspace_used(const cp_model* m);
+/* Stand-alone 2x2 max-pool launches (DLA's Tree.downsample) of that same last pass.  An entry whose input's producer wrote the
+ * pooled copy itself launches none: the count says which form the pass took at each of the four stride-2 entries. */
+int cp_model_maxpool_launches(const cp_model* m);
 
 /* images [B,3,H,W] NCHW (H, W multiples of 32).  pre_img [B,3,H,W], pre_hm [B,1,H,W],
  * pre_hm_hp [B,8,H,W] may each be NULL (pose_dla_dcn.py:312-318).  head_out[i] receives head i

@@ -17,7 +17,10 @@ extern "C" {
  * (2048, once "alternative DCN wave counts") is unused and refused.
  * CP_SEL_PW16_FRAG_A and CP_SEL_PW16_NEVER also change the launch SEQUENCE of DLA's level entries: the entry's 1x1 projection,
  * by default computed inside the first block's conv2 with pw16s_kernel's arithmetic and never stored, is asked for on another
- * kernel and therefore runs as a launch of its own (same values; the parity tests' unfused reference). */
+ * kernel and therefore runs as a launch of its own (same values; the parity tests' unfused reference).  Likewise the entries'
+ * 2x2 max-pooled input, by default stored by the launch that produces the entry's input (pw16s_kernel for a Root, the
+ * row-streaming level1 kernel): under these two switches, and under CP_SEL_LEVEL1_ROWS_NEVER for level 2's, it is made by a
+ * maxpool2 launch (same values; cp_model_maxpool_launches counts them). */
 #define CP_SEL_HEADS_SLABS 0x00000001          /* grouped fused heads write slabs + a reduction launch (no fuse_final) */
 #define CP_SEL_HEADS_WG_PER_HEAD 0x00000002    /* grouped fused heads: one workgroup per (patch, head), not per patch */
 #define CP_SEL_PW16_FRAG_A 0x00000004          /* 1x1 layers: fragment-shaped A loads (pw16_kernel), not staging rows */
