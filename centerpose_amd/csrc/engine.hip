@@ -152,39 +152,35 @@ size_t cp_model_workspace_bytes(cp_model* m, int B, int H, int W) {
         fail(CP_ERR_STATE, "cp_model_workspace_bytes: null model");
         return 0;
     }
-    // The launch sequence -- and with it the arena's allocation order -- has variants the caller may select later: the first
-    // layers fused or not (engine: fuse01), and a tap request, which turns the fused heads off.  The query runs the dry pass for
-    // every combination and returns the largest peak.  So does the IDAUp sequence (up-sample + add inside the preceding node at every
-    // site, at none, or at the one between dla_up and ida_up only) and the level entries' projection (inside conv2 or a launch of
-    // its own): every sequence a real pass can take is one of these, so its peak is at most the one returned here
-    // (cp_model_workspace_used reads a real pass's back).
+    // The launch sequence -- and with it the arena's allocation order -- has forms the caller may select later (cp_model::DryForm).
+    // The query runs the dry pass for every combination of them and returns the largest peak: every sequence a real pass can take
+    // is one of these, so its peak is at most the one returned here (cp_model_workspace_used reads a real pass's back).
     if (m->ws_cached && m->ws_key[0] == B && m->ws_key[1] == H && m->ws_key[2] == W && m->ws_key[3] == g_dbg && m->finalized)
         return m->ws_cached;   // (cp_model_detect asks on every call: up to 48 dry passes per frame would show in the batch-1 latency)
+    using Form = cp_model::DryForm;
     size_t peak = 0;
     const char* const tap_before = m->tap_name;
-    const int nu = m->ups_t.empty() ? 1 : 3;  // IDAUp forms (models without an IDAUp have one)
-    const int np = m->convs.count("base.level2.project") ? 2 : 1;  // level-entry forms (models without DLA's entries have one)
-    // ... and the stride-2 entries' pooled input (written by its producer, or by a maxpool2 launch: switches choose, and the caller
-    // may keep one buffer per shape across them)
-    for (int v = 0; v < 4 * nu * np * np; ++v) {
-        const int up = (v >> 2) % nu;
-        m->dry_variant = v & 1;
-        m->tap_name = (v & 2) ? "" : nullptr;   // "" matches no tensor name: only the routing changes
-        m->dry_no_upadd = up != 0;              // (a tap on an IDAUp node: its output has to exist)
-        m->dry_boundary_upadd = up == 2;        // (... on a node other than dla_up's last: that one still stores ida_up's first u)
-        m->dry_no_project = (v / (4 * nu)) % np == 1;  // (a tap on a level entry's projection: likewise)
-        m->dry_no_pool = v >= 4 * nu * np;
-        const int rc = forward_impl(m, nullptr, B, H, W, nullptr, (const float*)1, (const float*)1, (const float*)1, nullptr, 0,
-                                    nullptr, 0, true);
-        m->dry_variant = 0;
-        m->dry_no_upadd = false;
-        m->dry_boundary_upadd = false;
-        m->dry_no_project = false;
-        m->dry_no_pool = false;
-        m->tap_name = tap_before;
-        if (rc != CP_OK) return 0;
-        if (m->arena.peak > peak) peak = m->arena.peak;
-    }
+    m->tap_name = nullptr;
+    const int n_ida = m->ups_t.empty() ? 1 : 3;  // models without an IDAUp have one form of it
+    const int n_entry = m->convs.count("base.level2.project") ? 2 : 1;  // ... without DLA's level entries one of those (projection, pooled input)
+    int rc = CP_OK;
+    for (int pool = 0; pool < n_entry; ++pool)
+        for (int proj = 0; proj < n_entry; ++proj)
+            for (int ida = 0; ida < n_ida; ++ida)
+                for (int tap = 0; tap < 2; ++tap)
+                    for (int stem = 0; stem < 2 && rc == CP_OK; ++stem) {
+                        m->form.stem_level0_fused = stem == 1;
+                        m->form.tap_routing = tap == 1;
+                        m->form.idaup = ida == 0 ? Form::IDA_ALL : ida == 1 ? Form::IDA_NONE : Form::IDA_BOUNDARY;
+                        m->form.project_unfused = proj == 1;
+                        m->form.no_pooled_producer = pool == 1;
+                        rc = forward_impl(m, nullptr, B, H, W, nullptr, (const float*)1, (const float*)1, (const float*)1, nullptr, 0,
+                                          nullptr, 0, true);
+                        if (m->arena.peak > peak) peak = m->arena.peak;
+                    }
+    m->form = Form();
+    m->tap_name = tap_before;
+    if (rc != CP_OK) return 0;
     m->ws_key[0] = B; m->ws_key[1] = H; m->ws_key[2] = W; m->ws_key[3] = g_dbg;
     m->ws_cached = peak;
     return peak;

@@ -1,6 +1,7 @@
 // The forward pass: a fixed sequence of HIP kernel launches on the caller's stream out of a caller-provided workspace
 // (deterministic arena, no allocation, no sync).  Fwd decides per layer which kernel runs; a dry run of the same code is the
-// work-space query.
+// work-space query.  A generic conv is asked for with a ConvCall; plan() alone turns one into ConvParams + kernel + accepted
+// fusions, for conv() and for the predicates that ask about a launch ahead of time (upadd_fusable, project_fusable) alike.
 //
 // Topology follows the reference modules (paths relative to the reference's src/lib/models/networks):
 //   DLA.forward pose_dla_dcn.py:310-322, Tree.forward :211-224, Root :160-168, BasicBlock :48-62,
@@ -20,21 +21,14 @@ constexpr int kSplitTiles = 128, kSplitTarget = 384;  // (384 / 512 measured: B=
 // 512 x 512 (graph replay, p50, lean - dense): B = 1 (16384 pixels) +0.011 ms, B = 2 -0.049, B = 4 -0.146, B = 8 -0.333, B = 16 -0.716
 // (profiles/lean_detect_ab.txt).
 constexpr long kLeanMinPixels = 32768;
+// stands for the address of a tensor that is not there (yet): planning and eligibility checks look at null / non-null only
+float* const kDryPtr = (float*)0x1000;
 
 // ------------------------------------ forward -------------------------------------------------
 struct Fwd {
     cp_model* m;
     int B;
     hipStream_t s;
-    // GroupNorm fusion hooks for the next conv() call (reset after use)
-    double* gn_stats_out = nullptr;
-    const float* gn_in_mr = nullptr;
-    const float* gn_in_a = nullptr;  // f16x3 form of the same fusion: per (image, channel) a, d planes
-    const float* gn_in_d = nullptr;
-    const float* gn_in_gamma = nullptr;
-    const float* gn_in_beta = nullptr;
-    int role = -1;  // CP_ROLE_* of the next conv() call when the shape does not say it (heads, GRU); reset after use
-    const unsigned* gn_in_amax = nullptr;  // bound on max|relu(a*x + d)| for the GNIN loader's pre-scale
     // |max| slots of this forward's tensors (f16x3 range-safe scaling, ConvParams::in_amax): one zeroed block at the
     // start of the arena, a slot per Tensor in creation order
     static constexpr int kMaxSlots = CP_AMAX_STRIDE;
@@ -91,6 +85,7 @@ struct Fwd {
         }
     }
     void tap(const std::string& name, const Tensor& t, int c_valid = 0) { tap(name.c_str(), t, c_valid); }
+    bool tapped() const { return m->tap_name || m->form.tap_routing; }  // any tap (or the query's form of one): the fused heads are off
     // cp_model_features: hands the heads' input to the caller; true = the pass ends here, no head is launched
     bool features_only(const Tensor& t) {
         if (!m->feat_out || m->dry) return false;
@@ -148,6 +143,26 @@ struct Fwd {
         return grouped_launch(m->head_group, x.ptr(), x.amax, x.C, x.H, x.W, head_out, sigmoid_hm, nullptr);
     }
 
+    // Per-head tables of a launch over the heads g.idx[first, first + n), side by side along N: each head's final width and first slab
+    // plane for the kernel (fuse_gc2 / fuse_gbase) and the slice reduction (rg, with the bias), and what the launch is charged for over
+    // M rows, added head by head to flops / bytes.  Returns the slab planes.
+    int head_tables(const cp_model::HeadGroup& g, int first, int n, double M, ConvParams& p, HeadReduceGroup& rg, double& flops, double& bytes) {
+        std::memset(&rg, 0, sizeof(rg));
+        rg.n = n;
+        rg.slices = p.fuse_gtiles;
+        int planes = 0;
+        for (int i = 0; i < n; ++i) {
+            const HeadW& hw = m->headw[g.idx[first + i]];
+            p.fuse_gc2[i] = rg.c2[i] = hw.classes;
+            p.fuse_gbase[i] = rg.base[i] = planes;
+            planes += p.fuse_gtiles * hw.classes;
+            rg.bias[i] = hw.c1.shift;
+            flops += 2.0 * M * g.hid * (9.0 * g.Cin) + 2.0 * M * hw.classes * (double)g.hid;
+            bytes += 4.0 * (M * hw.classes + 9.0 * g.Cin * g.hid + (double)g.hid * hw.classes);
+        }
+        return planes;
+    }
+
     // the heads of group g (a subset of the model's heads, cp_model::HeadGroup::idx) on the feature map `src` in one halo16
     // launch; head_out is indexed like the model's heads.  The choice of the kernel form looks at the model's whole head set, not
     // at g: a head's map must not depend on which other heads share its launch.  slab_mem: where the slabs + reduction form keeps
@@ -155,7 +170,7 @@ struct Fwd {
     bool grouped_launch(const cp_model::HeadGroup& g, const float* src, unsigned* src_amax, int C, int H, int W,
                         float* const* head_out, int sigmoid_hm, float* slab_mem) {
         const int n = (int)g.idx.size(), n_all = (int)m->headw.size();
-        if (!g.ok || m->precision != CP_PREC_F16X3 || m->tap_name || (g_dbg & (CP_SEL_NO_HEAD_FUSION | CP_SEL_HEADS_PER_HEAD_LAUNCH)) || C != g.Cin)
+        if (!g.ok || m->precision != CP_PREC_F16X3 || tapped() || (g_dbg & (CP_SEL_NO_HEAD_FUSION | CP_SEL_HEADS_PER_HEAD_LAUNCH)) || C != g.Cin)
             return false;
         ConvW w;  // the heads' 3x3 layers side by side along N: fragment-ordered f16x3 operands only
         w.KH = w.KW = 3;
@@ -174,7 +189,7 @@ struct Fwd {
         p.fuse_w2_inv = g.w2_inv;
         p.fuse_ngroups = n;
         p.fuse_gtiles = g.hid / 128;
-        p.fuse_out = (float*)0x1000;  // placeholder for the eligibility check
+        p.fuse_out = kDryPtr;  // (for the eligibility check)
         // the kernel walks a head's hidden tiles and writes the finished maps itself (CP_SEL_HEADS_SLABS: slabs + reduction
         // launch); 2: every head of a patch in one workgroup (one staging for all of them) -- when the patches alone fill the
         // device several times over; below that (small batches, CP_SEL_HEADS_WG_PER_HEAD) one workgroup per patch and head
@@ -183,27 +198,16 @@ struct Fwd {
         if (!cp_halo16_fused_head_supported(p)) return false;
         if (B * (H / 8) * (W / 16) * (n_all * g.hid / 128) < kSplitTiles) return false;  // small maps: per-head split-K path
         HeadReduceGroup rg;
-        std::memset(&rg, 0, sizeof(rg));
-        rg.n = n;
-        rg.slices = p.fuse_gtiles;
-        int planes = 0;
         double flops = 0.0, bytes = 0.0;
         const double M = (double)B * H * W;
+        const int planes = head_tables(g, 0, n, M, p, rg, flops, bytes);
+        bytes += 4.0 * M * g.Cin;  // the shared input is read once
         for (int i = 0; i < n; ++i) {
             const HeadW& hw = m->headw[g.idx[i]];
-            p.fuse_gc2[i] = rg.c2[i] = hw.classes;
-            p.fuse_gbase[i] = rg.base[i] = planes;
-            planes += p.fuse_gtiles * hw.classes;
-            rg.sigmoid[i] = sigmoid_hm && (hw.name == "hm" || hw.name == "hm_hp");
-            rg.bias[i] = hw.c1.shift;
-            rg.out[i] = m->dry ? nullptr : head_out[g.idx[i]];
-            p.fuse_gsig[i] = rg.sigmoid[i];
+            p.fuse_gsig[i] = rg.sigmoid[i] = sigmoid_hm && (hw.name == "hm" || hw.name == "hm_hp");
             p.fuse_gbias[i] = rg.bias[i];
-            p.fuse_gout[i] = rg.out[i];
-            flops += 2.0 * M * g.hid * (9.0 * g.Cin) + 2.0 * M * hw.classes * (double)g.hid;
-            bytes += 4.0 * (M * hw.classes + 9.0 * g.Cin * g.hid + (double)g.hid * hw.classes);
+            p.fuse_gout[i] = rg.out[i] = m->dry ? nullptr : head_out[g.idx[i]];
         }
-        bytes += 4.0 * M * g.Cin;  // the shared input is read once
         Tensor slabs;
         if (!p.fuse_final && !slab_mem) slabs = make(planes, H, W);
         if (m->dry) return true;
@@ -253,25 +257,15 @@ struct Fwd {
         p.rows_per_image = rpi;
         p.row_index_stride = stride;
         HeadReduceGroup rg;
-        std::memset(&rg, 0, sizeof(rg));
-        rg.n = count;
-        rg.slices = p.fuse_gtiles;
-        int planes = 0;
         const double M = (double)B * rpi;
         double flops = 0.0, bytes = 4.0 * M * 9.0 * g.Cin;
+        head_tables(g, first, count, M, p, rg, flops, bytes);
         for (int i = 0; i < count; ++i) {
-            const HeadW& hw = m->headw[g.idx[first + i]];
-            p.fuse_gc2[i] = rg.c2[i] = hw.classes;
-            p.fuse_gbase[i] = rg.base[i] = planes;
-            planes += p.fuse_gtiles * hw.classes;
-            rg.bias[i] = hw.c1.shift;
             rg.out[i] = table_out[g.idx[first + i]];
             if (!rg.out[i]) {
-                chk(fail(CP_ERR_INVALID, "heads at pixels: no table for head " + hw.name));
+                chk(fail(CP_ERR_INVALID, "heads at pixels: no table for head " + m->headw[g.idx[first + i]].name));
                 return;
             }
-            flops += 2.0 * M * g.hid * (9.0 * g.Cin) + 2.0 * M * hw.classes * (double)g.hid;
-            bytes += 4.0 * (M * hw.classes + 9.0 * g.Cin * g.hid + (double)g.hid * hw.classes);
         }
         timed([&](cp_model::ProfRec& r) {
             r.variant = CP_VARIANT_HEAD_ROWS;
@@ -341,14 +335,48 @@ struct Fwd {
         return true;
     }
 
-    // generic conv into a fresh NHWC tensor (or into user NCHW memory when out_nchw != nullptr)
     // IDAUp's next up-sample + add, done by the epilogue of the node that produces `add` (ida()): the conv's output tensor is
     // u = act(conv) + up(t), the node's own output does not exist
-    struct UpFuse {
-        const Tensor* t;
-        const float* wt;  // cp_model::ups_t
-        int f;
+    struct UpFuse { const Tensor* t; const float* wt; int f; };  // (wt: cp_model::ups_t, f: the factor)
+    // A level entry's 1x1 projection (Tree.project) computed by the block's conv2, which would otherwise read it back as its
+    // residual (halo16.hip, ConvParams::pj_src): the projected tensor and its launch do not exist
+    struct ProjFuse { const Tensor* bottom; const ConvW* w; };  // (w: <p>.project)
+    // GroupNorm of a dlav1 head around its two convs, at most one form per call
+    struct GroupNormPart {
+        double* stats_out = nullptr;                                    // the 3x3's epilogue accumulates the statistics
+        const float *mr = nullptr, *gamma = nullptr, *beta = nullptr;   // the 1x1's loader normalises from mean / rstd per group (float32)
+        const float *a = nullptr, *d = nullptr;                         // ... or pre-folded to relu(a x + d) per (image, channel) (f16x3),
+        const unsigned* bound = nullptr;                                // with a bound on its |max| for the loader's pre-scale
     };
+    // One request to conv(): everything it is told arrives here, nothing is kept from one call to the next.  Past `act` every
+    // field defaults to "none" and a call site names the ones it uses.
+    struct ConvCall {
+        const ConvW& w;
+        std::vector<const Tensor*> srcs;  // a virtual concat along C
+        int stride, pad, act;
+        const Tensor* res = nullptr;      // added before the activation
+        const Tensor* offmask = nullptr;  // DCNv2: the offset / mask map of the same pixels
+        int act_from = 0;                 // CP_ACT_SIGMOID_FROM: first channel of the sigmoid
+        float* out_nchw = nullptr;        // the output goes to the caller's NCHW memory of out_ld planes (no tensor comes back)
+        int out_ld = 0;
+        const UpFuse* up = nullptr;       // the caller asked upadd_fusable() first
+        const ProjFuse* pj = nullptr;     // ... project_fusable()
+        Tensor* pooled = nullptr;         // the output feeds a stride-2 entry: receives maxpool2(output) where the launch can write it
+        GroupNormPart gn;
+        int role = -1;                    // CP_ROLE_* where the shape does not say it (heads, GRU)
+    };
+    // What plan() makes of a ConvCall.  p is final but for the activations' addresses: every tensor the launch reads holds
+    // kDryPtr (the kernel choice looks at null / non-null only), what it writes is null until conv() has allocated it.
+    struct ConvPlan {
+        ConvParams p;               // (with plan_split's answer: splitk, tile_m / tile_n)
+        const char* err = nullptr;  // the call cannot be launched at all
+        bool use16 = false;         // the f16x3 kernels take it (cp_launch_conv16), else the float32 ones
+        int variant = -1;           // CP_VARIANT_* of the launch
+        bool pooled = false, up = false, pj = false;  // the requested fusion is accepted: the launch lands on a kernel that has it
+    };
+    // a Tensor of that shape and no memory: what a predicate hands plan() for a tensor that does not exist yet
+    static Tensor shape_of(int C, int H, int W) { Tensor t; t.C = C; t.H = H; t.W = W; return t; }
+
     // deterministic split-K for launches with too few output tiles to fill 256 CUs (low-resolution layers at
     // small batch): slices write slabs, a small epilogue kernel sums them in order.  Returns the slices (1: no split) and sets
     // the launch's tile.
@@ -379,186 +407,180 @@ struct Fwd {
         }
         return 1;
     }
-    // Would the DCN `d` on a C x H x W input, asked to add the up-sampling by f of a tensor of t_c channels, run on the kernel that
-    // can (dcn16t's UPADD instance)?  The answer of conv() below for the same launch, from the shapes alone: a dry run and the
-    // real pass decide alike.
-    // (boundary: the site between two IDAUps, ida(): IdaNext -- the work-space query has a form that keeps only that one)
-    bool upadd_fusable(const DeformW& d, int C, int H, int W, int t_c, int f, bool boundary = false) {
-        if (m->precision != CP_PREC_F16X3 || (m->dry_no_upadd && !(boundary && m->dry_boundary_upadd))) return false;
-        const float* const some = (const float*)0x1000;  // (placeholders: only null / non-null is looked at)
-        ConvParams p = conv_params(B, H, W, &some, &C, 1, d.main, 1, 1, CP_ACT_RELU);
-        if (p.Cin != d.main.CinP) return false;
-        p.offmask = some;
-        const unsigned* no_amax = nullptr;
-        if (!conv_params_f16(p, d.main, &no_amax, true)) return false;
-        p.store = CP_STORE_NHWC;
-        p.ldo = d.main.Cout;
-        p.up_t = p.up_wt = some;
-        p.up_ld = t_c;
-        p.up_f = f;
-        p.splitk = plan_split(p, true, d.main);
-        return p.splitk == 1 && cp_conv16_variant(p) == CP_VARIANT_DCN16T && cp_dcn16t_upadd_supported(p);
-    }
 
-    // A level entry's 1x1 projection (Tree.project) computed by the block's conv2, which would otherwise read it back as its
-    // residual (halo16.hip, ConvParams::pj_src): the projected tensor and its launch do not exist
-    struct ProjFuse {
-        const Tensor* bottom;
-        const ConvW* w;  // <p>.project
-    };
-    // Would conv2 `w2` of the entry block at `p`, on a C x H x W input, run on a kernel that can take the projection `wp` of a
-    // `cb`-channel tensor as its residual -- and would that projection, launched on its own, be pw16.hip's, whose arithmetic the
-    // fused form reproduces bit for bit?  From the shapes and switches alone: a dry run and the real pass decide alike.  float32,
-    // split-K and 64 x 64-tile launches, shapes halo16 refuses, the switches that move either layer to another kernel and a tap on
-    // any entry's `.project` all keep the plain sequence (a tap unfuses every entry, not only its own: the work-space query then
-    // has two forms to run, all entries fused where they can be or none).
-    bool project_fusable(const std::string& p, const ConvW& wp, const ConvW& w2, int cb, int C, int H, int W) {
-        if (m->precision != CP_PREC_F16X3 || m->dry_no_project) return false;
-        if (m->tap_name && std::strstr(m->tap_name, ".project") != nullptr) return false;  // (every entry: two forms, as for .node_)
-        if (g_dbg & (CP_SEL_PW16_FRAG_A | CP_SEL_PW16_NEVER)) return false;  // (the projection's kernel asked for by name)
-        if (wp.CoutPad != w2.CoutPad || wp.Cout != w2.Cout || wp.Kpad16 != cb || !wp.w16f_hi || !wp.w16f_lo) return false;
-        const float* const some = (const float*)0x1000;  // (placeholders: only null / non-null is looked at)
-        const unsigned* no_amax = nullptr;
-        ConvParams q = conv_params(B, H, W, &some, &cb, 1, wp, 1, 0, CP_ACT_NONE);  // the projection on its own
-        if (q.Cin != wp.CinP || !conv_params_f16(q, wp, &no_amax, true)) return false;
-        q.store = CP_STORE_NHWC;
-        q.ldo = wp.Cout;
-        q.splitk = plan_split(q, true, wp);
-        const int qv = cp_conv16_variant(q);
-        if (q.splitk != 1 || (qv != CP_VARIANT_PW16 && qv != CP_VARIANT_PW16 + 1)) return false;
-        ConvParams c = conv_params(B, H, W, &some, &C, 1, w2, 1, 1, CP_ACT_RELU);
-        if (c.Cin != w2.CinP || !conv_params_f16(c, w2, &no_amax, true)) return false;
-        c.store = CP_STORE_NHWC;
-        c.ldo = w2.Cout;
-        c.pj_src = some;
-        c.pj_c = cb;
-        c.pj_w_hi = c.pj_w_lo = some;
-        c.splitk = plan_split(c, true, w2);
-        return c.splitk == 1 && cp_conv16_project_supported(c);
-    }
-
-    // pooled: the output feeds a stride-2 level entry.  Where the launch is a whole (not split-K) one on pw16s_kernel over a picture
-    // of even height and a width of whole 16-pixel blocks (cp_pw16_pool_supported: f16x3, not CP_SEL_PW16_FRAG_A / _NEVER, 32-bit
-    // offsets), it writes maxpool2(output) as well and *pooled receives that tensor; otherwise *pooled stays invalid and the entry
-    // launches maxpool2 as before.  Shapes and switches only: a dry run and the real pass decide alike.
-    Tensor conv(const ConvW& w, const std::vector<const Tensor*>& srcs, int stride, int pad, int act,
-                const Tensor* res = nullptr, const Tensor* offmask = nullptr, int act_from = 0,
-                float* out_nchw = nullptr, int out_ld = 0, const UpFuse* up = nullptr, const ProjFuse* pj = nullptr,
-                Tensor* pooled = nullptr) {
-        const Tensor& x0 = *srcs[0];
-        const int nsrc = (int)srcs.size();
+    // The one place a generic conv's ConvParams is assembled and its kernel chosen: a function of the call's shapes and weights, the
+    // model's precision, the switches and the dry form.  It allocates nothing and reads no activation, so conv() and the
+    // predicates below -- which ask about a launch before its tensors exist -- get the same answer from the same code.
+    ConvPlan plan(const ConvCall& c) {
+        const ConvW& w = c.w;
+        const Tensor& x0 = *c.srcs[0];
+        const int nsrc = (int)c.srcs.size();
         const float* src[CP_MAX_SRC];
         int src_c[CP_MAX_SRC];
         const unsigned* src_amax[CP_MAX_SRC];
         for (int i = 0; i < nsrc; ++i) {
-            src[i] = srcs[i]->ptr();
-            src_c[i] = srcs[i]->C;
-            src_amax[i] = srcs[i]->amax;
+            src[i] = kDryPtr;
+            src_c[i] = c.srcs[i]->C;
+            src_amax[i] = c.srcs[i]->amax;
         }
-        ConvParams p = conv_params(B, x0.H, x0.W, src, src_c, nsrc, w, stride, pad, act);
+        ConvPlan pl{conv_params(B, x0.H, x0.W, src, src_c, nsrc, w, c.stride, c.pad, c.act)};
+        ConvParams& p = pl.p;
         if (p.Cin != w.CinP) {
-            chk(fail(CP_ERR_INVALID, "conv: channel mismatch"));
-            return Tensor();
+            pl.err = "conv: channel mismatch";
+            return pl;
         }
-        p.res = res ? res->ptr() : nullptr;
-        p.res_ld = res ? res->C : 0;
-        p.act_from = act_from;
-        p.offmask = offmask ? offmask->ptr() : nullptr;
-        p.gn_stats = gn_stats_out;
+        p.res = c.res ? kDryPtr : nullptr;
+        p.res_ld = c.res ? c.res->C : 0;
+        p.act_from = c.act_from;
+        p.offmask = c.offmask ? kDryPtr : nullptr;
+        p.gn_stats = c.gn.stats_out;
         p.gn_groups = 32;
         p.gn_cpg = w.Cout / 32 > 0 ? w.Cout / 32 : 1;
-        if (gn_in_a) {
-            p.gn_in_a = gn_in_a;
-            p.gn_in_d = gn_in_d;
-        }
-        if (gn_in_mr) {
-            p.gn_in_mr = gn_in_mr;
-            p.gn_in_gamma = gn_in_gamma;
-            p.gn_in_beta = gn_in_beta;
+        p.gn_in_a = c.gn.a;
+        p.gn_in_d = c.gn.a ? c.gn.d : nullptr;
+        if (c.gn.mr) {
+            p.gn_in_mr = c.gn.mr; p.gn_in_gamma = c.gn.gamma; p.gn_in_beta = c.gn.beta;
             p.gn_cpg = w.Cin / 32;
         }
-        const bool use16 = conv_params_f16(p, w, src_amax, m->precision == CP_PREC_F16X3);
-        if (use16 && p.gn_in_a) p.in_amax[0] = gn_in_amax;
-        if (p.gn_in_a && !use16) {  // the per-channel affine form only exists in the f16x3 1x1 kernel
-            chk(fail(CP_ERR_INVALID, "conv: GroupNorm affine input without an f16x3 kernel"));
+        pl.use16 = conv_params_f16(p, w, src_amax, m->precision == CP_PREC_F16X3);
+        if (pl.use16 && p.gn_in_a) p.in_amax[0] = c.gn.bound;
+        if (p.gn_in_a && !pl.use16) {  // the per-channel affine form only exists in the f16x3 1x1 kernel
+            pl.err = "conv: GroupNorm affine input without an f16x3 kernel";
+            return pl;
+        }
+        // offset/mask maps keep their padded width so the DCN loader can index [pixel*32 + c]
+        p.store = c.out_nchw ? CP_STORE_NCHW : CP_STORE_NHWC;
+        p.ldo = c.out_nchw ? c.out_ld : c.act == CP_ACT_SIGMOID_FROM ? w.CoutPad : w.Cout;
+        p.splitk = plan_split(p, pl.use16, w);
+        const bool whole16 = pl.use16 && p.splitk == 1;
+        if (c.up) {
+            p.up_t = kDryPtr; p.up_wt = c.up->wt; p.up_ld = c.up->t->C; p.up_f = c.up->f;
+        }
+        if (c.pj) {
+            p.pj_src = kDryPtr; p.pj_c = c.pj->bottom->C; p.pj_amax = c.pj->bottom->amax;
+            p.pj_w_hi = c.pj->w->w16f_hi; p.pj_w_lo = c.pj->w->w16f_lo; p.pj_scale = c.pj->w->scale16; p.pj_shift = c.pj->w->shift;
+        }
+        pl.variant = pl.use16 ? cp_conv16_variant(p) : cp_conv_variant(p);
+        const bool pw16 = pl.variant == CP_VARIANT_PW16 || pl.variant == CP_VARIANT_PW16 + 1;
+        // dcn16t's UPADD instance; halo16's PJ on the 64- / 128-wide tile with <p>.project's fragment-ordered operands; pw16s_kernel
+        // over a picture of even height and a width of whole 16-pixel blocks (a whole launch each: no split-K)
+        pl.up = c.up && whole16 && pl.variant == CP_VARIANT_DCN16T && cp_dcn16t_upadd_supported(p);
+        pl.pj = c.pj && whole16 && c.pj->w->CoutPad == w.CoutPad && c.pj->w->Cout == w.Cout && c.pj->w->Kpad16 == p.pj_c &&
+                p.pj_w_hi && p.pj_w_lo && cp_conv16_project_supported(p);
+        pl.pooled = c.pooled && whole16 && !c.out_nchw && !c.up && !c.pj && !m->form.no_pooled_producer && pw16 && cp_pw16_pool_supported(p);
+        return pl;
+    }
+    // Would the DCN `d` on the tensor u, asked to add the up-sampling by f of a tensor of t_c channels, run on the kernel that can?
+    // (boundary: the site between two IDAUps, ida(): IdaNext -- the work-space query has a form that keeps only that one)
+    bool upadd_fusable(const DeformW& d, const Tensor& u, int t_c, int f, bool boundary = false) {
+        using Form = cp_model::DryForm;
+        if (m->form.idaup == Form::IDA_NONE || (m->form.idaup == Form::IDA_BOUNDARY && !boundary)) return false;
+        const Tensor om = shape_of(32, u.H, u.W), t = shape_of(t_c, u.H / f, u.W / f);
+        const UpFuse up = {&t, kDryPtr, f};
+        ConvCall c{d.main, {&u}, 1, 1, CP_ACT_RELU};  // deform()'s second call
+        c.offmask = &om;
+        c.up = &up;
+        return plan(c).up;
+    }
+    // Would conv2 `w2` of a level entry's first block take the projection `wp` of `bottom` as its residual -- and would that projection,
+    // launched on its own, be pw16.hip's, whose arithmetic the fused form reproduces bit for bit?  float32, split-K and 64 x 64-tile
+    // launches, shapes halo16 refuses, the switches that move either layer to another kernel and a tap on any entry's `.project` all
+    // keep the plain sequence (a tap unfuses every entry, not only its own: the work-space query then has two forms to run, all
+    // entries fused where they can be or none).
+    bool project_fusable(const ConvW& wp, const ConvW& w2, const Tensor& bottom) {
+        if (m->form.project_unfused || (m->tap_name && std::strstr(m->tap_name, ".project") != nullptr)) return false;  // (every entry)
+        if (g_dbg & (CP_SEL_PW16_FRAG_A | CP_SEL_PW16_NEVER)) return false;  // (the projection's kernel asked for by name)
+        const ConvPlan alone = plan({wp, {&bottom}, 1, 0, CP_ACT_NONE});  // tree1()'s stand-alone call
+        if (alone.err || !alone.use16 || alone.p.splitk != 1 || (alone.variant != CP_VARIANT_PW16 && alone.variant != CP_VARIANT_PW16 + 1))
+            return false;
+        const Tensor t = shape_of(w2.CinP, bottom.H, bottom.W);  // conv1's output
+        const ProjFuse pj = {&bottom, &wp};
+        ConvCall c{w2, {&t}, 1, 1, CP_ACT_RELU};  // basic_block()'s second call
+        c.pj = &pj;
+        return plan(c).pj;
+    }
+
+    // generic conv into a fresh NHWC tensor (or into user NCHW memory: ConvCall::out_nchw): plan, allocate (output, split-K slabs,
+    // pooled copy -- in this order, the dry pass stops here), patch the tensors' addresses in, launch and charge
+    Tensor conv(const ConvCall& c) {
+        ConvPlan pl = plan(c);
+        if (!pl.err && ((c.up && !pl.up) || (c.pj && !pl.pj))) pl.err = "conv: the launch has no kernel with the epilogue asked for";
+        if (pl.err) {
+            chk(fail(CP_ERR_INVALID, pl.err));
             return Tensor();
         }
-        Tensor out;
-        if (out_nchw) {
-            p.out = out_nchw;
-            p.store = CP_STORE_NCHW;
-            p.ldo = out_ld;
-            p.coff = 0;
-        } else {
-            // offset/mask maps keep their padded width so the DCN loader can index [pixel*32 + c]
-            const int cstore = (act == CP_ACT_SIGMOID_FROM) ? w.CoutPad : w.Cout;
-            out = make(cstore, p.Ho, p.Wo);
-            p.out = out.ptr();
-            p.out_amax = act == CP_ACT_SIGMOID_FROM ? nullptr : out.amax;  // offset/mask maps are never a GEMM operand
-            p.store = CP_STORE_NHWC;
-            p.ldo = cstore;
-            p.coff = 0;
+        ConvParams& p = pl.p;
+        const ConvW& w = c.w;
+        Tensor out, partial;
+        if (!c.out_nchw) out = make(p.ldo, p.Ho, p.Wo);
+        if (p.splitk > 1) partial = make(p.splitk * p.CoutPad, p.Ho, p.Wo);
+        if (pl.pooled) {
+            *c.pooled = make(p.ldo, p.Ho / 2, p.Wo / 2);
+            c.pooled->amax = out.amax;  // max|maxpool(x)| <= max|x|: the output's slot is a valid bound (maxpool())
         }
-        Tensor partial;
-        p.splitk = plan_split(p, use16, w);
-        if (p.splitk > 1) {
-            partial = make(p.splitk * p.CoutPad, p.Ho, p.Wo);
-            p.partial = partial.ptr();
-        }
-        if (pooled && use16 && !out_nchw && p.splitk == 1 && !up && !pj && !m->dry_no_pool) {
-            const int v = cp_conv16_variant(p);
-            if ((v == CP_VARIANT_PW16 || v == CP_VARIANT_PW16 + 1) && cp_pw16_pool_supported(p)) {
-                *pooled = make(p.ldo, p.Ho / 2, p.Wo / 2);
-                pooled->amax = out.amax;  // max|maxpool(x)| <= max|x|: the output's slot is a valid bound (maxpool())
-                p.pool_out = m->dry ? (float*)0x1000 : pooled->ptr();
-            }
-        }
-        if (up) {
-            p.up_t = up->t->ptr();
-            p.up_wt = up->wt;
-            p.up_ld = up->t->C;
-            p.up_f = up->f;
-            // (the caller asked upadd_fusable() first; cp_launch_conv16 refuses a launch that lands on a kernel without the epilogue)
-        }
-        if (pj) {  // (the caller asked project_fusable() first; as above)
-            p.pj_src = pj->bottom->ptr();
-            p.pj_c = pj->bottom->C;
-            p.pj_amax = pj->bottom->amax;
-            p.pj_w_hi = pj->w->w16f_hi;
-            p.pj_w_lo = pj->w->w16f_lo;
-            p.pj_scale = pj->w->scale16;
-            p.pj_shift = pj->w->shift;
-        }
+        if (m->dry) return out;
+        for (int i = 0; i < p.nsrc; ++i) p.src[i] = c.srcs[i]->ptr();
+        p.res = c.res ? c.res->ptr() : nullptr;
+        p.offmask = c.offmask ? c.offmask->ptr() : nullptr;
+        p.up_t = c.up ? c.up->t->ptr() : nullptr;
+        p.pj_src = c.pj ? c.pj->bottom->ptr() : nullptr;
+        p.out = c.out_nchw ? c.out_nchw : out.ptr();
+        p.out_amax = c.out_nchw || c.act == CP_ACT_SIGMOID_FROM ? nullptr : out.amax;  // offset/mask maps are never a GEMM operand
+        p.partial = p.splitk > 1 ? partial.ptr() : nullptr;
+        p.pool_out = pl.pooled ? c.pooled->ptr() : nullptr;
         auto launch = [&]() -> int {
-            int rc = use16 ? cp_launch_conv16(p, s) : cp_launch_conv(p, s);
+            int rc = pl.use16 ? cp_launch_conv16(p, s) : cp_launch_conv(p, s);
             if (rc == CP_OK && p.splitk > 1) rc = cp_launch_splitk_epilogue(p, s);
             return rc;
         };
-        if (!m->dry)
-            timed([&](cp_model::ProfRec& r) {
-                r.variant = use16 ? cp_conv16_variant(p) : cp_conv_variant(p);
-                r.role = role >= 0 ? role : offmask ? CP_ROLE_DCN : act == CP_ACT_SIGMOID_FROM ? CP_ROLE_DCN_OFFSET
-                         : (w.KH == 1 && w.KW == 1) ? CP_ROLE_CONV1X1 : CP_ROLE_CONV;
-                const double M = (double)B * p.Ho * p.Wo;
-                const int cin_real = w.Cin;  // un-padded input channels
-                r.flops = 2.0 * M * w.Cout * (double)(w.KH * w.KW * cin_real + (pj ? pj->w->Cin : 0));
-                // algorithmic bytes: input once + output once + weights (+ offsets/mask for DCN, + residual, or the projection's
-                // input and weights in its place)
-                r.bytes = 4.0 * ((double)B * x0.H * x0.W * cin_real + M * w.Cout +
-                                 (double)w.KH * w.KW * cin_real * w.Cout + (offmask ? M * 27 : 0.0) +
-                                 (res ? M * w.Cout : 0.0) + (up ? (double)B * up->t->H * up->t->W * w.Cout : 0.0) +
-                                 (pj ? (M + w.Cout) * (double)pj->w->Cin : 0.0) + (p.pool_out ? M / 4 * w.Cout : 0.0));
-                r.M = (int)M; r.N = w.Cout; r.K = w.KH * w.KW * cin_real; r.kh = w.KH; r.stride = stride;
-            }, launch);
-        gn_stats_out = nullptr;
-        gn_in_mr = nullptr;
-        gn_in_a = nullptr;
-        gn_in_d = nullptr;
-        gn_in_amax = nullptr;
-        role = -1;
+        timed([&](cp_model::ProfRec& r) {
+            const Tensor& x0 = *c.srcs[0];
+            r.variant = pl.variant;
+            r.role = c.role >= 0 ? c.role : c.offmask ? CP_ROLE_DCN : c.act == CP_ACT_SIGMOID_FROM ? CP_ROLE_DCN_OFFSET
+                     : (w.KH == 1 && w.KW == 1) ? CP_ROLE_CONV1X1 : CP_ROLE_CONV;
+            const double M = (double)B * p.Ho * p.Wo;
+            const int cin_real = w.Cin;  // un-padded input channels
+            r.flops = 2.0 * M * w.Cout * (double)(w.KH * w.KW * cin_real + (c.pj ? c.pj->w->Cin : 0));
+            // algorithmic bytes: input once + output once + weights (+ offsets/mask for DCN, + residual, or the projection's
+            // input and weights in its place)
+            r.bytes = 4.0 * ((double)B * x0.H * x0.W * cin_real + M * w.Cout +
+                             (double)w.KH * w.KW * cin_real * w.Cout + (c.offmask ? M * 27 : 0.0) +
+                             (c.res ? M * w.Cout : 0.0) + (c.up ? (double)B * c.up->t->H * c.up->t->W * w.Cout : 0.0) +
+                             (c.pj ? (M + w.Cout) * (double)c.pj->w->Cin : 0.0) + (pl.pooled ? M / 4 * w.Cout : 0.0));
+            r.M = (int)M; r.N = w.Cout; r.K = w.KH * w.KW * cin_real; r.kh = w.KH; r.stride = c.stride;
+        }, launch);
         return out;
     }
     const ConvW& cw(const std::string& k) { return m->convs.at(k); }
+
+    // the two convs of a prediction head as launches of their own (dlav1: GroupNorm between them, gn_stats / gn)
+    Tensor head_hidden(const HeadW& hw, const Tensor& x, int act, double* gn_stats) {
+        ConvCall c{hw.c0, {&x}, 1, 1, act};
+        c.gn.stats_out = gn_stats;
+        c.role = CP_ROLE_HEAD;
+        return conv(c);
+    }
+    // the heads of a model without GroupNorm one by one: the fused pair where it applies (try_fused), else the two convs
+    void plain_heads(const Tensor& x, float* const* head_out, int sigmoid_hm, bool try_fused) {
+        for (size_t i = 0; i < m->headw.size(); ++i) {
+            const HeadW& hw = m->headw[i];
+            const bool sg = sigmoid_hm && (hw.name == "hm" || hw.name == "hm_hp");
+            float* const out = m->dry ? kDryPtr : head_out[i];
+            if (try_fused && hw.w2_hi && m->precision == CP_PREC_F16X3 && !tapped() && !(g_dbg & CP_SEL_NO_HEAD_FUSION) &&
+                fused_head(hw, x, sg, out))
+                continue;
+            Tensor hid = head_hidden(hw, x, CP_ACT_RELU, nullptr);
+            head_final(hw, hid, sg, out, GroupNormPart());
+        }
+    }
+    void head_final(const HeadW& hw, const Tensor& hid, bool sigmoid, float* out, const GroupNormPart& gn) {
+        ConvCall c{hw.c1, {&hid}, 1, 0, sigmoid ? CP_ACT_SIGMOID : CP_ACT_NONE};
+        c.out_nchw = out;
+        c.out_ld = hw.classes;
+        c.gn = gn;
+        c.role = CP_ROLE_HEAD_FINAL;
+        conv(c);
+    }
 
     Tensor maxpool(const Tensor& x) {
         Tensor o = make(x.C, x.H / 2, x.W / 2);
@@ -570,9 +592,12 @@ struct Fwd {
 
     // residual == nullptr: pj's projection, computed by conv2 itself
     Tensor basic_block(const std::string& p, const Tensor& x, int stride, const Tensor* residual, const ProjFuse* pj = nullptr) {
-        Tensor t = conv(cw(p + ".conv1"), {&x}, stride, 1, CP_ACT_RELU);
+        Tensor t = conv({cw(p + ".conv1"), {&x}, stride, 1, CP_ACT_RELU});
         tap(p + ".conv1", t);
-        Tensor o = conv(cw(p + ".conv2"), {&t}, 1, 1, CP_ACT_RELU, residual, nullptr, 0, nullptr, 0, nullptr, pj);
+        ConvCall c2{cw(p + ".conv2"), {&t}, 1, 1, CP_ACT_RELU};
+        c2.res = residual;
+        c2.pj = pj;
+        Tensor o = conv(c2);
         tap(p, o);
         return o;
     }
@@ -598,11 +623,11 @@ struct Fwd {
         if (cin != cout) {
             const ConvW& wp = cw(p + ".project");
             const ConvW& w2 = cw(p + ".tree1.conv2");
-            if (project_fusable(p, wp, w2, bottom->C, w2.CinP, bottom->H, bottom->W)) {
+            if (project_fusable(wp, w2, *bottom)) {
                 pj.w = &wp;  // conv2 of the first block computes the projection of its own pixels: no tensor, no launch
                 residual = nullptr;
             } else {
-                proj = conv(wp, {bottom}, 1, 0, CP_ACT_NONE);
+                proj = conv({wp, {bottom}, 1, 0, CP_ACT_NONE});
                 tap(p + ".project", proj);
                 residual = &proj;
             }
@@ -613,7 +638,9 @@ struct Fwd {
         Tensor x2 = basic_block(p + ".tree2", x1, 1, &x1);
         std::vector<const Tensor*> srcs = {&x2, &x1};
         for (auto* c : children) srcs.push_back(c);
-        Tensor o = conv(cw(p + ".root"), srcs, 1, 0, CP_ACT_RELU, nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr, pool_next);
+        ConvCall root{cw(p + ".root"), srcs, 1, 0, CP_ACT_RELU};
+        root.pooled = pool_next;
+        Tensor o = conv(root);
         tap(p + ".root", o);
         return o;
     }
@@ -628,9 +655,14 @@ struct Fwd {
     // up: the node's epilogue adds IDAUp's next up-sampled tensor; what comes back is that sum (conv(): UpFuse)
     Tensor deform(const std::string& p, const Tensor& x, const UpFuse* up = nullptr) {
         const DeformW& d = m->deforms.at(p);
-        Tensor om = conv(d.offset, {&x}, 1, 1, CP_ACT_SIGMOID_FROM, nullptr, nullptr, 18);
+        ConvCall off{d.offset, {&x}, 1, 1, CP_ACT_SIGMOID_FROM};
+        off.act_from = 18;
+        Tensor om = conv(off);
         tap(p + ".offmask", om, 27);
-        Tensor o = conv(d.main, {&x}, 1, 1, CP_ACT_RELU, nullptr, &om, 0, nullptr, 0, up);
+        ConvCall main{d.main, {&x}, 1, 1, CP_ACT_RELU};
+        main.offmask = &om;
+        main.up = up;
+        Tensor o = conv(main);
         if (!up) tap(p, o);
         return o;
     }
@@ -675,14 +707,14 @@ struct Fwd {
             const int fn = i + 1 < endp ? up_f[i + 1 - startp] : 0;
             const DeformW& node = m->deforms.at(p + ".node_" + k);
             if (node_dead && !tap_on_node && i + 1 < endp && m->ups_t.count(p + ".up_" + kn) &&
-                upadd_fusable(node, u.C, u.H, u.W, m->deforms.at(p + ".proj_" + kn).main.Cout, fn)) {
+                upadd_fusable(node, u, m->deforms.at(p + ".proj_" + kn).main.Cout, fn)) {
                 Tensor t = deform(p + ".proj_" + kn, layers[i + 1]);
                 const UpFuse up = {&t, m->ups_t.at(p + ".up_" + kn), fn};
                 u_next = deform(p + ".node_" + k, u, &up);
                 layers[i] = Tensor();  // (dead by the caller's word)
             } else if (next && i + 1 == endp && m->ups_t.count(next->p + ".up_1") &&
                        !(m->tap_name && std::strncmp(m->tap_name, (p + ".node_" + k).c_str(), (p + ".node_" + k).size()) == 0) &&
-                       upadd_fusable(node, u.C, u.H, u.W, m->deforms.at(next->p + ".proj_1").main.Cout, next->f, true)) {
+                       upadd_fusable(node, u, m->deforms.at(next->p + ".proj_1").main.Cout, next->f, true)) {
                 Tensor t = deform(next->p + ".proj_1", *next->layer);
                 const UpFuse up = {&t, m->ups_t.at(next->p + ".up_1"), next->f};
                 u_next = deform(p + ".node_" + k, u, &up);
@@ -713,7 +745,7 @@ struct Fwd {
         const bool l1 = kind == 2 || kind == 5;
         const int cout = l1 ? 32 : 16, cin = stem ? planes : 16, k = stem ? 7 : 3;
         Tensor out = make(cout, Ho, Wo);
-        const bool pool = pooled && !m->dry_no_pool && cp_lowc_pool_supported(kind, H, W);
+        const bool pool = pooled && !m->form.no_pooled_producer && cp_lowc_pool_supported(kind, H, W);
         if (pool) {
             *pooled = make(cout, Ho / 2, Wo / 2);
             pooled->amax = out.amax;  // (maxpool(): the output's slot is a valid bound)
@@ -746,19 +778,19 @@ struct Fwd {
         Tensor t = lowc(name, kind, nchw, H, W, C, use_lowc && !m->dry ? input_slot(nchw, (size_t)B * C * H * W) : nullptr);
         if (!t.valid()) {
             Tensor in = to_nhwc(nchw, C, Cpad, H, W);
-            t = conv(cw(name), {&in}, 1, 3, CP_ACT_RELU);
+            t = conv({cw(name), {&in}, 1, 3, CP_ACT_RELU});
         }
         return t;
     }
 
     // ---- stacked hourglass forward (large_hourglass.py:50-78, 129-189, 266-286) ----
     Tensor hg_residual(const std::string& p, const Tensor& x, int stride) {
-        Tensor t = conv(cw(p + ".conv1"), {&x}, stride, 1, CP_ACT_RELU);
-        if (m->convs.count(p + ".skip")) {
-            Tensor sk = conv(cw(p + ".skip"), {&x}, stride, 0, CP_ACT_NONE);
-            return conv(cw(p + ".conv2"), {&t}, 1, 1, CP_ACT_RELU, &sk);  // relu(bn2(conv2) + skip)
-        }
-        return conv(cw(p + ".conv2"), {&t}, 1, 1, CP_ACT_RELU, &x);
+        Tensor t = conv({cw(p + ".conv1"), {&x}, stride, 1, CP_ACT_RELU});
+        Tensor sk;
+        if (m->convs.count(p + ".skip")) sk = conv({cw(p + ".skip"), {&x}, stride, 0, CP_ACT_NONE});
+        ConvCall c2{cw(p + ".conv2"), {&t}, 1, 1, CP_ACT_RELU};
+        c2.res = sk.valid() ? &sk : &x;  // relu(bn2(conv2) + skip)
+        return conv(c2);
     }
     Tensor hg_seq(const std::string& p, Tensor x, int n, int first_stride) {
         for (int i = 0; i < n; ++i) x = hg_residual(p + "." + std::to_string(i), x, i == 0 ? first_stride : 1);
@@ -782,7 +814,7 @@ struct Fwd {
         Tensor inter;
         {
             Tensor in = to_nhwc(images, 3, 4, H, W);
-            Tensor p0 = conv(cw("pre.0"), {&in}, 2, 3, CP_ACT_RELU);
+            Tensor p0 = conv({cw("pre.0"), {&in}, 2, 3, CP_ACT_RELU});
             inter = hg_residual("pre.1", p0, 2);
         }
         tap("pre", inter);
@@ -790,27 +822,18 @@ struct Fwd {
         for (int k = 0; k < 2; ++k) {
             const std::string ks = std::to_string(k);
             Tensor kp = hg_kp("kps." + ks, inter, 5, mods);
-            cnv = conv(cw("cnvs." + ks), {&kp}, 1, 1, CP_ACT_RELU);
+            cnv = conv({cw("cnvs." + ks), {&kp}, 1, 1, CP_ACT_RELU});
             tap("cnvs." + ks, cnv);
             if (k == 0) {
-                Tensor a = conv(cw("inters_.0"), {&inter}, 1, 0, CP_ACT_NONE);
-                Tensor b = conv(cw("cnvs_.0"), {&cnv}, 1, 0, CP_ACT_RELU, &a);  // relu(inters_(inter) + cnvs_(cnv))
+                Tensor a = conv({cw("inters_.0"), {&inter}, 1, 0, CP_ACT_NONE});
+                ConvCall cb{cw("cnvs_.0"), {&cnv}, 1, 0, CP_ACT_RELU};
+                cb.res = &a;  // relu(inters_(inter) + cnvs_(cnv))
+                Tensor b = conv(cb);
                 inter = hg_residual("inters.0", b, 1);
             }
         }
         if (fused_heads_grouped(cnv, head_out, sigmoid_hm)) return;
-        for (size_t i = 0; i < m->headw.size(); ++i) {
-            const HeadW& hw = m->headw[i];
-            const bool sg = sigmoid_hm && (hw.name == "hm" || hw.name == "hm_hp");
-            if (hw.w2_hi && m->precision == CP_PREC_F16X3 && !m->tap_name && !(g_dbg & CP_SEL_NO_HEAD_FUSION) &&
-                fused_head(hw, cnv, sg, m->dry ? (float*)0x1000 : head_out[i]))
-                continue;
-            role = CP_ROLE_HEAD;
-            Tensor hid = conv(hw.c0, {&cnv}, 1, 1, CP_ACT_RELU);
-            role = CP_ROLE_HEAD_FINAL;
-            conv(hw.c1, {&hid}, 1, 0, sg ? CP_ACT_SIGMOID : CP_ACT_NONE, nullptr, nullptr, 0,
-                 m->dry ? (float*)0x1000 : head_out[i], hw.classes);
-        }
+        plain_heads(cnv, head_out, sigmoid_hm, true);
     }
 
     // ---- PoseResNet forward (resnet_dcn.py: PoseResNet.forward, BasicBlock / Bottleneck.forward) ----
@@ -842,17 +865,20 @@ struct Fwd {
         Tensor sk;
         const Tensor* res = &x;
         if (m->convs.count(p + ".downsample")) {
-            sk = conv(cw(p + ".downsample"), {&x}, stride, 0, CP_ACT_NONE);
+            sk = conv({cw(p + ".downsample"), {&x}, stride, 0, CP_ACT_NONE});
             res = &sk;
         }
+        Tensor a, b;
         if (bott) {
-            Tensor a = conv(cw(p + ".conv1"), {&x}, 1, 0, CP_ACT_RELU);
-            Tensor b = conv(cw(p + ".conv2"), {&a}, stride, 1, CP_ACT_RELU);
+            a = conv({cw(p + ".conv1"), {&x}, 1, 0, CP_ACT_RELU});
+            b = conv({cw(p + ".conv2"), {&a}, stride, 1, CP_ACT_RELU});
             a = Tensor();
-            return conv(cw(p + ".conv3"), {&b}, 1, 0, CP_ACT_RELU, res);  // relu(bn3(conv3) + residual)
+        } else {
+            b = conv({cw(p + ".conv1"), {&x}, stride, 1, CP_ACT_RELU});
         }
-        Tensor a = conv(cw(p + ".conv1"), {&x}, stride, 1, CP_ACT_RELU);
-        return conv(cw(p + ".conv2"), {&a}, 1, 1, CP_ACT_RELU, res);  // relu(bn2(conv2) + residual)
+        ConvCall last{cw(p + (bott ? ".conv3" : ".conv2")), {&b}, 1, bott ? 0 : 1, CP_ACT_RELU};
+        last.res = res;  // relu(bn(conv) + residual)
+        return conv(last);
     }
     void run_resnet(int H, int W, const float* images, float* const* head_out, int sigmoid_hm) {
         bool bott = false;
@@ -862,7 +888,7 @@ struct Fwd {
         Tensor x;
         {
             Tensor in = to_nhwc(images, 3, 4, H, W);
-            Tensor c1 = conv(cw("conv1"), {&in}, 2, 3, CP_ACT_RELU);
+            Tensor c1 = conv({cw("conv1"), {&in}, 2, 3, CP_ACT_RELU});
             in = Tensor();
             x = maxpool3(c1);
         }
@@ -880,15 +906,7 @@ struct Fwd {
             tap("deconv_layers." + std::to_string(6 * i + 5), x);
         }
         if (features_only(x)) return;
-        for (size_t i = 0; i < m->headw.size(); ++i) {
-            const HeadW& hw = m->headw[i];
-            const bool sg = sigmoid_hm && (hw.name == "hm" || hw.name == "hm_hp");
-            role = CP_ROLE_HEAD;
-            Tensor hid = conv(hw.c0, {&x}, 1, 1, CP_ACT_RELU);
-            role = CP_ROLE_HEAD_FINAL;
-            conv(hw.c1, {&hid}, 1, 0, sg ? CP_ACT_SIGMOID : CP_ACT_NONE, nullptr, nullptr, 0,
-                 m->dry ? (float*)0x1000 : head_out[i], hw.classes);
-        }
+        plain_heads(x, head_out, sigmoid_hm, false);
     }
 
     void run(int H, int W, const float* images, const float* pre_img, const float* pre_hm, const float* pre_hm_hp,
@@ -897,7 +915,7 @@ struct Fwd {
         const bool use_lowc = m->precision == CP_PREC_F16X3 && !(g_dbg & CP_SEL_NO_LOWC) && m->lowc.count("base.base_layer");
         // stem + level0 in one launch when nothing is added to the stem's output (no previous-frame stems) and nobody asks for it
         // (CP_SEL_STEM_LEVEL0_UNFUSED: the two kernels, A/B runs and tests)
-        const bool no_pre = m->dry ? m->dry_variant == 1 : (!pre_img && !pre_hm && !pre_hm_hp);
+        const bool no_pre = m->dry ? m->form.stem_level0_fused : (!pre_img && !pre_hm && !pre_hm_hp);
         const bool fuse01 = use_lowc && no_pre && m->lowc.count("base.level0.rows") && m->stem_bound_l > 0.f &&
                             !(g_dbg & CP_SEL_STEM_LEVEL0_UNFUSED) && !(m->tap_name && std::strcmp(m->tap_name, "base.base_layer") == 0) &&
                             !m->convs.count("base.pre_img_layer") && !m->convs.count("base.pre_hm_layer") && !m->convs.count("base.pre_hm_hp_layer");
@@ -953,14 +971,14 @@ struct Fwd {
         if (!fuse01) tap("base.base_layer", x0);
         Tensor l0 = fuse01 ? l0f : lowc("base.level0", 1, x0.ptr(), H, W, 16, x0.amax);
         l0f = Tensor();  // (one owner: the block returns to the arena when l0 is dropped below)
-        if (!l0.valid()) l0 = conv(cw("base.level0"), {&x0}, 1, 1, CP_ACT_RELU);
+        if (!l0.valid()) l0 = conv({cw("base.level0"), {&x0}, 1, 1, CP_ACT_RELU});
         tap("base.level0", l0);
         x0 = Tensor();
         // the 2x2 max-pooled copy each stride-2 entry reads (Tree.downsample), written by the launch that produces the entry's
         // input where it can (lowc(), conv(): pooled); an invalid one makes the entry launch maxpool2
         Tensor pl[4];
         Tensor l1 = lowc("base.level1", 2, l0.ptr(), H, W, 16, l0.amax, &pl[0]);
-        if (!l1.valid()) l1 = conv(cw("base.level1"), {&l0}, 2, 1, CP_ACT_RELU);
+        if (!l1.valid()) l1 = conv({cw("base.level1"), {&l0}, 2, 1, CP_ACT_RELU});
         tap("base.level1", l1);
         l0 = Tensor();
         std::vector<Tensor> L(6);
@@ -1001,8 +1019,9 @@ struct Fwd {
         std::vector<Tensor> gru_out;
         if (m->gru) {
             const int steps = m->tracking ? 4 : 3;
-            role = CP_ROLE_GRU;
-            Tensor x3 = conv(m->gru_x, {&feat}, 1, 1, CP_ACT_NONE);
+            ConvCall cx{m->gru_x, {&feat}, 1, 1, CP_ACT_NONE};
+            cx.role = CP_ROLE_GRU;
+            Tensor x3 = conv(cx);
             Tensor h;
             for (int st = 0; st < steps; ++st) {
                 Tensor hn = make(64, feat.H, feat.W);
@@ -1040,8 +1059,9 @@ struct Fwd {
                         }, [&]() { return cp_launch_conv16_gru(p, s); });
                     }
                 } else {
-                    role = CP_ROLE_GRU;
-                    Tensor h3 = conv(m->gru_h, {&h}, 1, 1, CP_ACT_NONE);
+                    ConvCall ch{m->gru_h, {&h}, 1, 1, CP_ACT_NONE};
+                    ch.role = CP_ROLE_GRU;
+                    Tensor h3 = conv(ch);
                     if (!m->dry) chk(cp_launch_gru_gate(x3.ptr(), h3.ptr(), h.ptr(), hn.ptr(), M, hn.amax, s));
                 }
                 h = hn;
@@ -1050,87 +1070,71 @@ struct Fwd {
             }
         }
 
-        // GroupNorm statistics of every head (32 groups x (sum, sumsq) doubles per image = 128 floats per image and head):
-        // one block, zeroed by one memset per forward pass instead of one per head
-        if (!m->gru && fused_heads_grouped(feat, head_out, sigmoid_hm)) return;
-        Tensor stats_all;
-        if (m->gru) {
-            stats_all = make(128 * (int)m->headw.size(), 1, 1);
-            if (!m->dry && hipMemsetAsync(stats_all.ptr(), 0, sizeof(double) * 64 * B * m->headw.size(), s) != hipSuccess)
-                chk(CP_ERR_LAUNCH);
+        if (!m->gru) {
+            if (!fused_heads_grouped(feat, head_out, sigmoid_hm)) plain_heads(feat, head_out, sigmoid_hm, true);
+            return;
         }
+        // dlav1: conv3x3 -> GroupNorm -> ReLU -> conv1x1 on the head's ConvGRU step.  GroupNorm statistics of every head (32 groups x
+        // (sum, sumsq) doubles per image = 128 floats per image and head): one block, zeroed by one memset per forward pass
+        Tensor stats_all = make(128 * (int)m->headw.size(), 1, 1);
+        if (!m->dry && hipMemsetAsync(stats_all.ptr(), 0, sizeof(double) * 64 * B * m->headw.size(), s) != hipSuccess) chk(CP_ERR_LAUNCH);
         for (size_t i = 0; i < m->headw.size(); ++i) {
             const HeadW& hw = m->headw[i];
-            const Tensor* src = &feat;
-            if (m->gru) {
-                int r = -1;
-                const std::string& n = hw.name;
-                if (m->tracking) {
-                    if (n == "tracking" || n == "tracking_hp") r = 0;
-                    else if (n == "hm" || n == "wh" || n == "reg") r = 1;
-                    else if (n == "hm_hp" || n == "hp_offset" || n == "hps" || n == "hps_uncertainty") r = 2;
-                    else if (n == "scale" || n == "scale_uncertainty") r = 3;
-                } else {
-                    if (n == "hm" || n == "wh" || n == "reg") r = 0;
-                    else if (n == "hm_hp" || n == "hp_offset" || n == "hps") r = 1;
-                    else if (n == "scale") r = 2;
-                }
-                if (r < 0) {  // unreachable: cp_model_create refuses heads outside the routing table
-                    chk(fail(CP_ERR_STATE, "head without a ConvGRU step"));
-                    continue;
-                }
-                src = &gru_out[r];
+            int r = -1;
+            const std::string& n = hw.name;
+            if (m->tracking) {
+                if (n == "tracking" || n == "tracking_hp") r = 0;
+                else if (n == "hm" || n == "wh" || n == "reg") r = 1;
+                else if (n == "hm_hp" || n == "hp_offset" || n == "hps" || n == "hps_uncertainty") r = 2;
+                else if (n == "scale" || n == "scale_uncertainty") r = 3;
+            } else {
+                if (n == "hm" || n == "wh" || n == "reg") r = 0;
+                else if (n == "hm_hp" || n == "hp_offset" || n == "hps") r = 1;
+                else if (n == "scale") r = 2;
             }
-            Tensor mr, ad;
-            double* stats = m->gru && !m->dry ? (double*)stats_all.ptr() + (size_t)i * 64 * B : nullptr;
-            const bool fuse_gn = m->gru && ((src->H * src->W) % 32 == 0) && hw.c0.Cout % 32 == 0 && (hw.c0.Cout / 32) % 4 == 0;
-            if (m->gru) {
-                mr = make(64, 1, 1);
-                if (fuse_gn && !m->dry) gn_stats_out = stats;
-            }
-            const bool sg = sigmoid_hm && (hw.name == "hm" || hw.name == "hm_hp");
-            if (!m->gru && hw.w2_hi && m->precision == CP_PREC_F16X3 && !m->tap_name && !(g_dbg & CP_SEL_NO_HEAD_FUSION) &&
-                fused_head(hw, *src, sg, m->dry ? (float*)0x1000 : head_out[i]))
+            if (r < 0) {  // unreachable: cp_model_create refuses heads outside the routing table
+                chk(fail(CP_ERR_STATE, "head without a ConvGRU step"));
                 continue;
-            role = CP_ROLE_HEAD;
-            Tensor hid = conv(hw.c0, {src}, 1, 1, m->gru ? CP_ACT_NONE : CP_ACT_RELU);
-            if (m->gru) {
-                if (fuse_gn) {
-                    // statistics came out of the conv epilogue; normalise + affine + ReLU happens in the 1x1 loader
-                    const bool affine16 = m->precision == CP_PREC_F16X3 && hw.c1.w16_hi && (hid.H * hid.W) % 128 == 0 &&
-                                          !(g_dbg & CP_SEL_GN_HEAD_F32);
-                    if (affine16) {
-                        // f16x3 1x1 kernel: the normalisation pre-folded to y = relu(a*x + d) per (image, channel)
-                        ad = make(2 * hid.C, 1, 1);
-                        if (!m->dry) {
-                            float* ap = ad.ptr();
-                            float* dp = ap + (size_t)B * hid.C;
-                            unsigned* bound = new_slot();
-                            chk(cp_launch_gn_affine((const double*)stats, hw.gn_gamma, hw.gn_beta, ap, dp, B, hid.C, 32,
-                                                    (double)hid.H * hid.W * (hid.C / 32), 1e-5f, hid.amax, bound, s));
-                            gn_in_a = ap;
-                            gn_in_d = dp;
-                            gn_in_amax = bound;
-                        }
-                    } else if (!m->dry) {
-                        chk(cp_launch_gn_finalize((const double*)stats, mr.ptr(), B * 32,
-                                                  (double)hid.H * hid.W * (hid.C / 32), 1e-5f, s));
-                        gn_in_mr = mr.ptr();
-                        gn_in_gamma = hw.gn_gamma;
-                        gn_in_beta = hw.gn_beta;
+            }
+            const Tensor* src = &gru_out[r];
+            Tensor mr = make(64, 1, 1), ad;
+            double* stats = !m->dry ? (double*)stats_all.ptr() + (size_t)i * 64 * B : nullptr;
+            const bool fuse_gn = ((src->H * src->W) % 32 == 0) && hw.c0.Cout % 32 == 0 && (hw.c0.Cout / 32) % 4 == 0;
+            const bool sg = sigmoid_hm && (hw.name == "hm" || hw.name == "hm_hp");
+            // KEPT DIVERGENCE: the GroupNorm parts (`stats` here, gn below) only exist in a real pass, so the dry pass plans both
+            // convs without them: it may plan split-K slabs the real pass does not have, and it sends the final 1x1 through conv()
+            // where the real pass runs gn_final.  It over-estimates, which is safe.  (Handing the dry pass kDryPtr in their place
+            // makes the two agree, and changes what cp_model_workspace_bytes returns for dlav1.)
+            Tensor hid = head_hidden(hw, *src, CP_ACT_NONE, fuse_gn && !m->dry ? stats : nullptr);
+            GroupNormPart gn;
+            if (fuse_gn) {
+                // statistics came out of the conv epilogue; normalise + affine + ReLU happens in the 1x1 loader
+                const bool affine16 = m->precision == CP_PREC_F16X3 && hw.c1.w16_hi && (hid.H * hid.W) % 128 == 0 &&
+                                      !(g_dbg & CP_SEL_GN_HEAD_F32);
+                if (affine16) {
+                    // f16x3 1x1 kernel: the normalisation pre-folded to y = relu(a*x + d) per (image, channel)
+                    ad = make(2 * hid.C, 1, 1);
+                    if (!m->dry) {
+                        float* ap = ad.ptr();
+                        float* dp = ap + (size_t)B * hid.C;
+                        unsigned* bound = new_slot();
+                        chk(cp_launch_gn_affine((const double*)stats, hw.gn_gamma, hw.gn_beta, ap, dp, B, hid.C, 32,
+                                                (double)hid.H * hid.W * (hid.C / 32), 1e-5f, hid.amax, bound, s));
+                        gn.a = ap; gn.d = dp; gn.bound = bound;
                     }
                 } else if (!m->dry) {
-                    // in place: the slot keeps the larger of the raw and the normalised |max| -- a valid bound
-                    chk(cp_launch_groupnorm_relu(hid.ptr(), hw.gn_gamma, hw.gn_beta, stats, B,
-                                                 hid.H * hid.W, hid.C, 32, 1e-5f, hid.amax, s));
+                    chk(cp_launch_gn_finalize((const double*)stats, mr.ptr(), B * 32, (double)hid.H * hid.W * (hid.C / 32), 1e-5f, s));
+                    gn.mr = mr.ptr(); gn.gamma = hw.gn_gamma; gn.beta = hw.gn_beta;
                 }
+            } else if (!m->dry) {
+                // in place: the slot keeps the larger of the raw and the normalised |max| -- a valid bound
+                chk(cp_launch_groupnorm_relu(hid.ptr(), hw.gn_gamma, hw.gn_beta, stats, B, hid.H * hid.W, hid.C, 32, 1e-5f, hid.amax, s));
             }
-            role = CP_ROLE_HEAD_FINAL;
-            if (gn_in_a && !(g_dbg & CP_SEL_GN_HEAD_MFMA) && hid.C % 64 == 0 && hid.C <= 256 && (hid.H * hid.W) % 64 == 0 &&
-                ((size_t)B * hid.H * hid.W) % 256 == 0 && hw.classes <= 16 && !m->tap_name) {
+            if (gn.a && !(g_dbg & CP_SEL_GN_HEAD_MFMA) && hid.C % 64 == 0 && hid.C <= 256 && (hid.H * hid.W) % 64 == 0 &&
+                ((size_t)B * hid.H * hid.W) % 256 == 0 && hw.classes <= 16 && !tapped()) {
                 // float32 vector-ALU kernel (ewise.hip: gn_final_kernel): the layer is an HBM stream of the hidden tensor
                 auto launch = [&]() -> int {
-                    return cp_launch_gn_final(hid.ptr(), gn_in_a, gn_in_d, hw.c1.wp, hw.c1.shift, head_out[i], B, hid.H * hid.W,
+                    return cp_launch_gn_final(hid.ptr(), gn.a, gn.d, hw.c1.wp, hw.c1.shift, head_out[i], B, hid.H * hid.W,
                                               hid.C, hw.classes, hw.c1.CoutPad, sg ? 1 : 0, s);
                 };
                 timed([&](cp_model::ProfRec& r) {
@@ -1141,13 +1145,9 @@ struct Fwd {
                     r.bytes = 4.0 * (M * hid.C + M * hw.classes + (double)hid.C * hw.classes);
                     r.M = (int)M; r.N = hw.classes; r.K = hid.C; r.kh = 1; r.stride = 1;
                 }, launch);
-                gn_in_a = gn_in_d = nullptr;
-                gn_in_amax = nullptr;
-                role = -1;
                 continue;
             }
-            conv(hw.c1, {&hid}, 1, 0, sg ? CP_ACT_SIGMOID : CP_ACT_NONE, nullptr, nullptr, 0,
-                 m->dry ? (float*)0x1000 : head_out[i], hw.classes);
+            head_final(hw, hid, sg, m->dry ? kDryPtr : head_out[i], gn);
         }
     }
 };

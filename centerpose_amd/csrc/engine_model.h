@@ -229,12 +229,16 @@ struct cp_model {
     std::map<std::string, cp_engine::LowcW> lowc;  // hi / lo weight fragments of the lowc.hip layers
     int ws_key[4] = {0, 0, 0, -1};  // (B, H, W, g_dbg) of the cached work-space query below
     size_t ws_cached = 0;
-    bool dry_no_upadd = false;  // work-space query: the IDAUp sequence without the up-sample + add epilogues (a tap on a node selects it)
-    bool dry_boundary_upadd = false;  // ... with dry_no_upadd: all but the site between dla_up and ida_up (a tap on another node than its own)
-    bool dry_no_project = false;  // work-space query: the level entries with their projection as a launch of its own (a tap on it selects that)
-    bool dry_no_pool = false;  // work-space query: every stride-2 entry with its maxpool2 launch (no producer writes the pooled copy)
-    int dry_variant = 0;  // work-space query: 1 = the dry run takes the fused stem + level0 path where the model allows it (the query
-                          // runs both forms and returns the larger peak: switches and taps may select either form later)
+    // One form of the launch sequence for the work-space query (switches, previous-frame inputs and taps may select any of them
+    // later: cp_model_workspace_bytes).  A real pass, and cp_model_lean_supported's dry one, leaves every field at its default.
+    struct DryForm {
+        bool stem_level0_fused = false;  // the fused stem + level0 launch where the model allows it (a real pass: no previous-frame input)
+        bool tap_routing = false;        // what any tap causes whatever it names: the fused heads are off
+        enum { IDA_ALL, IDA_NONE, IDA_BOUNDARY } idaup = IDA_ALL;  // IDAUp's up-sample + add inside the preceding node at every site that
+                                         // can / at none (a tap on a node) / only between dla_up and ida_up (a tap on another node than that one)
+        bool project_unfused = false;    // the level entries' projection as a launch of its own (a tap on one selects that)
+        bool no_pooled_producer = false; // every stride-2 entry with its maxpool2 launch (no producer writes the pooled copy)
+    } form;
     float stem_bound_l = 0.f, stem_bound_s = 0.f;  // |base_layer out| <= stem_bound_l * max|image| + stem_bound_s (fused stem + level0)
     cp_engine::ConvW gru_x, gru_h;
     void* gru_h16_hi = nullptr;  // hidden-side GRU weights re-ordered [tile][r|z|n][32] for the fused-gate kernel
