@@ -1,7 +1,7 @@
 """ORACLE (test infrastructure): functional CPU restatement of the reference DLA-34 graph.
 
 Operates directly on a reference-format ``state_dict`` (same key names as the reference
-modules register), float32, NCHW, eval-mode BatchNorm.  Each function cites the reference
+modules register), float32 (``dlaseg_forward(dtype=torch.float64)``: the same graph in float64), NCHW, eval-mode BatchNorm.  Each function cites the reference
 lines it follows (paths relative to /root/reference/src/lib/models/networks/).
 
 Pinned against the reference's own modules by ``oracle/tools/make_goldens.py`` (run in the
@@ -21,8 +21,9 @@ class Ctx:
     calibration tool (hook(name, kind, tensor) may rescale weights in ``sd`` and return a
     replacement tensor)."""
 
-    def __init__(self, sd, hook=None, dcn_kind="port", taps=None):
+    def __init__(self, sd, hook=None, dcn_kind="port", taps=None, dtype=torch.float32):
         self.sd = sd
+        self.dtype = dtype  # torch.float64: every operator in float64 (sd and inputs arrive cast, the DCN dispatches in oracle/dcn.py)
         self.hook = hook
         self.dcn_kind = dcn_kind
         self.taps = taps  # optional dict: name -> tensor, filled when not None
@@ -67,7 +68,7 @@ def basic_block(ctx, x, p, stride, residual=None):
     """pose_dla_dcn.py:48-62"""
     if residual is None:
         residual = x
-    out = _conv_bn(ctx, x, p + ".conv1", p + ".bn1", stride, 1, relu=True)
+    out = ctx.tap(p + ".conv1", _conv_bn(ctx, x, p + ".conv1", p + ".bn1", stride, 1, relu=True))
     out = _conv_bn(ctx, out, p + ".conv2", p + ".bn2", 1, 1, relu=False)
     out = out + residual
     return ctx.tap(p, F.relu(out))
@@ -83,12 +84,12 @@ def tree(ctx, x, p, levels, cin, cout, stride, level_root, children=None):
     """pose_dla_dcn.py:211-224.  The ``residual`` argument of the reference is always
     recomputed inside (:214) so it is not a parameter here (SURVEY App. B #17)."""
     children = [] if children is None else children
-    bottom = F.max_pool2d(x, stride, stride) if stride > 1 else x
+    bottom = ctx.tap(p + ".bottom", F.max_pool2d(x, stride, stride)) if stride > 1 else x
     has_project = cin != cout
     if level_root:
         children.append(bottom)
     if levels == 1:
-        residual = _conv_bn(ctx, bottom, p + ".project.0", p + ".project.1", 1, 0, relu=False) \
+        residual = ctx.tap(p + ".project", _conv_bn(ctx, bottom, p + ".project.0", p + ".project.1", 1, 0, relu=False)) \
             if has_project else bottom
         x1 = basic_block(ctx, x, p + ".tree1", stride, residual)
         x2 = basic_block(ctx, x1, p + ".tree2", 1)
@@ -127,6 +128,8 @@ def deform_conv(ctx, x, p):
     # chunk(3)+cat(o1,o2) is the identity on the first 18 channels (dcn_v2.py:120-121)
     offset = out[:, :18].contiguous()
     mask = torch.sigmoid(out[:, 18:27]).contiguous()
+    if ctx.taps is not None:  # the 27 channels as the engine presents them: raw offsets, then the sigmoid of the mask
+        ctx.tap(p + ".offmask", torch.cat((offset, mask), 1))
     w = ctx.sd[p + ".conv.weight"]
     b = ctx.sd[p + ".conv.bias"]
     if ctx.hook is None:
@@ -151,8 +154,10 @@ def ida_up(ctx, layers, p, startp, endp, up_f):
     for i in range(startp + 1, endp):
         k = i - startp
         t = deform_conv(ctx, layers[i], "%s.proj_%d" % (p, k))
-        t = ctx.tap("%s.up_%d" % (p, k), _up(ctx, t, "%s.up_%d" % (p, k), up_f[k]))
-        layers[i] = deform_conv(ctx, t + layers[i - 1], "%s.node_%d" % (p, k))
+        t = _up(ctx, t, "%s.up_%d" % (p, k), up_f[k])
+        # (the tap is the node's input, up-sampled projection + skip: what the engine's up-sample + add launch writes under this name)
+        u = ctx.tap("%s.up_%d" % (p, k), t + layers[i - 1])
+        layers[i] = deform_conv(ctx, u, "%s.node_%d" % (p, k))
 
 
 def dla_up(ctx, layers):
@@ -222,11 +227,23 @@ def head_routing(heads, use_gru, tracking_task):
 @torch.no_grad()
 def dlaseg_forward(sd, x, heads, arch="dla", tracking_task=False,
                    pre_img=None, pre_hm=None, pre_hm_hp=None,
-                   hook=None, dcn_kind="port", taps=None):
-    """DLASeg.forward pose_dla_dcn.py:523-570.  Returns the head dict ``z`` (raw logits)."""
-    ctx = Ctx(sd, hook, dcn_kind, taps)
+                   hook=None, dcn_kind="port", taps=None, dtype=torch.float32):
+    """DLASeg.forward pose_dla_dcn.py:523-570.  Returns the head dict ``z`` (raw logits).
+
+    ``dtype=torch.float64`` runs every operator in float64 (state dict and inputs cast here, the deformable layers through
+    ``oracle.dcn``'s float64 gather): the reference the float32 pass's own rounding is measured against.  ``taps`` (a dict)
+    receives the intermediate tensors under the names the engine's ``forward(tap=...)`` knows."""
+    if dtype == torch.float64:
+        sd = {k: (v.double() if v.is_floating_point() else v) for k, v in sd.items()}
+        x = x.double()
+        pre_img, pre_hm, pre_hm_hp = (None if t is None else t.double() for t in (pre_img, pre_hm, pre_hm_hp))
+    elif dtype == torch.float32:
+        x = x.float()
+    else:
+        raise ValueError("dlaseg_forward: dtype must be torch.float32 or torch.float64")
+    ctx = Ctx(sd, hook, dcn_kind, taps, dtype)
     use_gru = arch == "dlav1"
-    ys = dla34_base(ctx, x.float(), pre_img, pre_hm, pre_hm_hp)
+    ys = dla34_base(ctx, x, pre_img, pre_hm, pre_hm_hp)
     ups = dla_up(ctx, ys)
     y = [ups[0], ups[1], ups[2]]  # last_level - first_level = 3 (clone not needed: functional)
     ida_up(ctx, y, "ida_up", 0, 3, [1, 2, 4])

@@ -77,7 +77,14 @@ def im2col(x, offset, mask, kh, kw, ph, pw, sh, sw, dh, dw, dg, kind="port"):
 
 def dcn_v2_forward(x, weight, bias, offset, mask, kh, kw, sh, sw, ph, pw, dh, dw, dg,
                    kind="port"):
-    """Same 14-argument signature as the reference's ``_ext.dcn_v2_forward`` (vision.cpp:5)."""
+    """Same 14-argument signature as the reference's ``_ext.dcn_v2_forward`` (vision.cpp:5).
+
+    A float64 ``x`` takes the float64 restatement below (3x3, stride 1, dilation 1, one deformable group: every DCN of the
+    networks here) and returns float64; everything else is the float32 path."""
+    if x.dtype == torch.float64:
+        if (kh, kw, sh, sw, dh, dw, dg) != (3, 3, 1, 1, 1, 1, 1) or ph != pw:
+            raise ValueError("dcn_v2_forward: the float64 path is 3x3 / stride 1 / dilation 1 / one deformable group")
+        return dcn_v2_forward_f64(x, weight, bias, offset, mask, pad=ph)
     B = x.shape[0]
     Co = weight.shape[0]
     assert weight.shape[2] == kh and weight.shape[3] == kw
