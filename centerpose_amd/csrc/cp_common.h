@@ -591,6 +591,14 @@ const char* cp_pose_targets_track_check(const cp_pose_targets_track_desc* d);  /
 size_t cp_pose_targets_track_ws_bytes(const cp_pose_targets_track_desc* d);    // 0: refused
 int cp_launch_pose_targets_track(hipStream_t s, const cp_pose_targets_track_desc* d, void* ws);
 
+// ---- training input images (train_inputs.hip; per-pixel arithmetic in train_inputs_common.h) ----
+const char* cp_train_inputs_check(const unsigned char* frames, size_t frames_bytes, const double* records, int N,
+                                  const float* mean3, const float* std3, const float* out, int out_h,
+                                  int out_w);                    // nullptr: accepted (reads the host records)
+size_t cp_train_inputs_ws_bytes(int N, int out_h, int out_w);  // 0: refused
+int cp_launch_train_inputs(hipStream_t s, const unsigned char* frames, const double* records, int N, const float* mean3,
+                           const float* std3, float* out, int out_h, int out_w, void* ws);
+
 // ---- Objectron box metrics (box3d.hip; numerics in box3d_common.h) ----
 int cp_launch_box_iou(hipStream_t s, const double* a, const double* b, int n, double* iou);
 int cp_launch_box_eval(hipStream_t s, const double* pred3d, const double* gt3d, const double* pred2d, const double* mo2c,

@@ -696,4 +696,18 @@ int cp_pose_targets_track(cp_stream_t stream, const cp_pose_targets_track_desc* 
     return rc == CP_OK ? CP_OK : fail(rc, "pose_targets_track: copy or kernel launch failed");
 }
 
+size_t cp_train_inputs_workspace_bytes(int N, int out_h, int out_w) { return cp_train_inputs_ws_bytes(N, out_h, out_w); }
+
+int cp_train_inputs(cp_stream_t stream, const unsigned char* frames, size_t frames_bytes, const double* records, int N,
+                    const float* mean3, const float* std3, float* out, int out_h, int out_w, void* workspace,
+                    size_t workspace_bytes) {
+    if (const char* e = cp_train_inputs_check(frames, frames_bytes, records, N, mean3, std3, out, out_h, out_w))
+        return fail(CP_ERR_INVALID, e);
+    if (!workspace) return fail(CP_ERR_INVALID, "train_inputs: null workspace");
+    if (workspace_bytes < cp_train_inputs_ws_bytes(N, out_h, out_w))
+        return fail(CP_ERR_INVALID, "train_inputs: workspace too small");
+    const int rc = cp_launch_train_inputs((hipStream_t)stream, frames, records, N, mean3, std3, out, out_h, out_w, workspace);
+    return rc == CP_OK ? CP_OK : fail(rc, "train_inputs: copy or kernel launch failed");
+}
+
 }  // extern "C"

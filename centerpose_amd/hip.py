@@ -94,6 +94,12 @@ class PoseTargetsTrackDesc(ctypes.Structure):
                [("out_" + n, c_void_p) for n in PTK_OUTPUTS]
 
 
+# ---- training input images (cp_train_inputs): record layout of include/centerpose_hip.h ----
+TI_STRIDE = 24
+TI_IMG = dict(offset=0, height=1, width=2, trans=3, flipped=9, color=10, order=11, alpha=12, shift=15)
+TI_ORDERS = ("bcs", "bsc", "cbs", "csb", "sbc", "scb")  # order code -> brightness / contrast / saturation as run
+
+
 def _sig(fn, restype, *argtypes):
     fn.restype = restype
     fn.argtypes = list(argtypes)
@@ -232,6 +238,9 @@ def lib():
     _sig(L.cp_pose_targets, c_int, c_void_p, ctypes.POINTER(PoseTargetsDesc), c_void_p, c_size_t)
     _sig(L.cp_pose_targets_track_workspace_bytes, c_size_t, ctypes.POINTER(PoseTargetsTrackDesc))
     _sig(L.cp_pose_targets_track, c_int, c_void_p, ctypes.POINTER(PoseTargetsTrackDesc), c_void_p, c_size_t)
+    _sig(L.cp_train_inputs_workspace_bytes, c_size_t, c_int, c_int, c_int)
+    _sig(L.cp_train_inputs, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_int, ctypes.POINTER(ctypes.c_float),
+         ctypes.POINTER(ctypes.c_float), c_void_p, c_int, c_int, c_void_p, c_size_t)
     _lib = L
     return L
 
@@ -276,7 +285,8 @@ def exported_symbols():
             "cp_conv_transpose2d_backward_nhwc", "cp_maxpool2d_forward_nhwc", "cp_maxpool2d_backward_nhwc",
             "cp_conv2d_stem_backward_workspace_bytes", "cp_conv2d_stem_backward", "cp_groupnorm_workspace_bytes",
             "cp_groupnorm_forward_nhwc", "cp_groupnorm_backward_nhwc", "cp_gru_gate_forward", "cp_gru_gate_backward",
-            "cp_pose_targets_track_workspace_bytes", "cp_pose_targets_track"]
+            "cp_pose_targets_track_workspace_bytes", "cp_pose_targets_track", "cp_train_inputs_workspace_bytes",
+            "cp_train_inputs"]
 
 
 def _check(rc, what):
@@ -2016,3 +2026,41 @@ def pose_targets_track(records, S, R, flags, track, out):
     if rc == CP_ERR_INVALID:
         raise ValueError("centerpose_hip: cp_pose_targets_track: %s" % L.cp_last_error().decode())
     _check(rc, "cp_pose_targets_track")
+
+
+def train_inputs_means_offset(N):
+    """CP_TI_WS_MEANS(N): where cp_train_inputs leaves the float32 gs_mean of every image in its workspace."""
+    return (int(N) * TI_STRIDE * 8 + 255) // 256 * 256
+
+
+def train_inputs(frames, records, mean, std, out, return_means=False):
+    """cp_train_inputs: the training input images of N frames, written into the device tensor ``out`` [N,3,out_h,out_w]
+    float32 on the current stream.  ``frames`` is one contiguous uint8 device tensor of any shape that holds every frame
+    at its record's byte offset; ``records`` the host records [N, TI_STRIDE] (converted to a pageable float64 copy
+    here, which the call stages before it returns).  Refused arguments raise ValueError before any launch.
+    ``return_means``: also return the float32 [N] grey means the call used (a view of its workspace)."""
+    import numpy as np
+
+    records = np.array(records, dtype=np.float64, order="C", copy=True)
+    if records.ndim != 2 or records.shape[1] != TI_STRIDE:
+        raise ValueError("train_inputs: records must be [N, %d]" % TI_STRIDE)
+    if not (frames.is_cuda and frames.dtype == torch.uint8 and frames.is_contiguous()):
+        raise ValueError("train_inputs: frames must be a contiguous uint8 device tensor")
+    if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 4 and
+            out.shape[0] == records.shape[0] and out.shape[1] == 3):
+        raise ValueError("train_inputs: out must be a contiguous float32 device tensor [N, 3, out_h, out_w]")
+    L = lib()
+    N, out_h, out_w = records.shape[0], int(out.shape[2]), int(out.shape[3])
+    f3 = ctypes.c_float * 3
+    nbytes = L.cp_train_inputs_workspace_bytes(N, out_h, out_w)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=out.device) if nbytes else None
+    rc = L.cp_train_inputs(_stream(), _ptr(frames), frames.numel(), records.ctypes.data, N,
+                           f3(*[float(v) for v in np.asarray(mean).reshape(-1)]),
+                           f3(*[float(v) for v in np.asarray(std).reshape(-1)]), _ptr(out), out_h, out_w, _ptr(ws), nbytes)
+    if rc == CP_ERR_INVALID:
+        raise ValueError("centerpose_hip: cp_train_inputs: %s" % L.cp_last_error().decode())
+    _check(rc, "cp_train_inputs")
+    if return_means:
+        o = train_inputs_means_offset(N)
+        return out, ws[o:o + 4 * N].view(torch.float32)
+    return out

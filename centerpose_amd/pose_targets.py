@@ -1,9 +1,10 @@
 """ObjectPose training targets on the device: the ground truth that ObjectPoseDataset.__getitem__ builds for the current
 frame (datasets/dataset_combined.py:957-1130), for a whole batch and every symmetry variant, computed by cp_pose_targets.
 
-The host keeps image decoding, the augmentation draws and the output affine.  A dataset returns, per image, the input
-plus the small fixed-size records of ``pack_annotations`` (the default collate stacks them); the training step expands
-them on the device:
+The host keeps image decoding, the augmentation draws and the output affine (the input image itself, warp and colour
+augmentation included, can be built on the device too: train_inputs.py).  A dataset returns, per image, the input or
+the decoded frame plus the small fixed-size records of ``pack_annotations`` (the default collate stacks them); the
+training step expands them on the device:
 
     records = pack_annotations(anns, trans_output_rot, width, height, flipped, rot, opt)   # per image, in the dataset
     batch.update(PoseTargets(opt)(collated_records))                                       # per batch, on the device

@@ -47,7 +47,8 @@ typedef struct cp_model cp_model;
  *     cp_model_lean_supported, cp_model_detect_lean(_workspace_bytes), cp_model_dense_heads, cp_model_heads_at(_workspace_bytes),
  *     cp_decode_peaks(_workspace_bytes), cp_decode_gathered; CP_NUM_KERNEL_VARIANTS 46;
  *     cp_pose_heads_forward / _backward (+ _workspace_bytes, cp_pose_heads_chunk_images), cp_model_features;
- *     cp_groupnorm_workspace_bytes, cp_groupnorm_forward_nhwc / _backward_nhwc, cp_gru_gate_forward / _backward. */
+ *     cp_groupnorm_workspace_bytes, cp_groupnorm_forward_nhwc / _backward_nhwc, cp_gru_gate_forward / _backward;
+ *     cp_train_inputs_workspace_bytes, cp_train_inputs. */
 #define CP_ABI_VERSION 7
 const char* cp_version(void);
 int cp_abi_version(void);
@@ -1002,6 +1003,66 @@ typedef struct cp_pose_targets_track_desc {
 } cp_pose_targets_track_desc;
 size_t cp_pose_targets_track_workspace_bytes(const cp_pose_targets_track_desc* d); /* 0: shape refused */
 int cp_pose_targets_track(cp_stream_t stream, const cp_pose_targets_track_desc* d, void* workspace, size_t workspace_bytes);
+
+/* ------------------------------------------------------------------------------------------
+ * Training input images — replaces ObjectPoseDataset._get_input (datasets/dataset_combined.py:278-288, called at :348 for
+ *   the current frame and at :456 for the tracking task's previous frame) together with the horizontal flip of the
+ *   decoded frame (:335-339, :433-435) and color_aug (utils/image.py:239-277), for N images in one call.
+ * The host keeps image decoding and every random draw; a record per image carries the draws (centerpose_amd/
+ * train_inputs.py pack_input / draw_color_aug write it).
+ * frames   DEVICE pointer: the decoded 8-bit HWC BGR frames in one buffer of `frames_bytes` bytes; record n names its
+ *          frame by byte offset, height and width, so the frames of one call may differ in size.
+ * records  HOST pointer, float64 [N][CP_TI_STRIDE]; staged into the workspace with hipMemcpyAsync on `stream`, so
+ *          pageable memory may be reused when the call returns:
+ *     0      byte offset of the frame in `frames`
+ *     1, 2   height, width of the frame (img.shape[0], img.shape[1], :322)
+ *     3..8   trans_input, the FORWARD 2x3 input affine, row-major (:344); inverted on the device exactly as
+ *            cv::invertAffineTransform / cp_preprocess do, a singular matrix giving the zero matrix (every output pixel
+ *            is then what source pixel (0, 0) gives)
+ *     9      flipped, 0 or 1: source column x is read at W - 1 - x, i.e. the warp of img[:, ::-1, :] (:337); c[0] is
+ *            mirrored in trans_input by the caller (:339)
+ *     10     colour flag, 0 or 1: split == 'train' and not opt.no_color_aug (:284)
+ *     11     order of brightness (b), contrast (c), saturation (s) after random.shuffle (utils/image.py:270-271):
+ *            0 = bcs, 1 = bsc, 2 = cbs, 3 = csb, 4 = sbc, 5 = scb
+ *     12..14 alpha = 1 + uniform(-0.4, 0.4) of the first, second and third operation RUN (:255, :260, :265)
+ *     15..17 the lighting shift per B, G, R channel, np.dot(eigvec, eigval * alpha) of lighting_ (:243-245)
+ * out      DEVICE float32 [N, 3, out_h, out_w] (opt.input_res twice), every element written.
+ * Per image, in the reference's order and precision:
+ *   1. cv2.warpAffine(INTER_LINEAR, constant 0 border) in OpenCV's fixed-point arithmetic, as cp_preprocess: the same
+ *      8-bit levels;
+ *   2. float32(v8) / 255 in float32 (:283);
+ *   3. with the colour flag: gs = 0.114 B + 0.587 G + 0.299 R in float32 (BGR2GRAY on a float image), gs_mean its mean
+ *      over the whole warped image, both taken before any operation; the three operations in the record's order in
+ *      float32, a = float32(alpha), 1 - a = float32(1.0 - alpha): brightness v *= a, contrast v = v a + gs_mean (1 - a),
+ *      saturation v = v a + gs (1 - a), every product and sum rounded on its own; then the lighting shift
+ *      v = float32(double(v) + shift[c]) (a float64 array added into the float32 image);
+ *   4. (v - mean3[c]) / std3[c] in float32 (:286; NOT cp_preprocess's float64 form), written NCHW (:287).
+ *   gs_mean is float32(sum / (out_h out_w)) of a float64 sum reduced in a fixed order without atomics: results are
+ *   bitwise reproducible, and an image's result does not depend on the other images of the call.  It differs from
+ *   numpy's pairwise float32 mean in the last bits.
+ * Images whose colour flag is clear take no grey pass; a call without a colour image is one kernel launch.
+ * Workspace: cp_train_inputs_workspace_bytes(N, out_h, out_w) bytes (0: refused).  After the call the float32 gs_mean
+ *   of every image (0 where the colour flag is clear) is at byte offset CP_TI_WS_MEANS(N) of the workspace.
+ * Refused with CP_ERR_INVALID before any device work: NULL pointers, N < 1, out_h / out_w < 1 (or a grid beyond 2^31 - 1
+ *   workgroups), a non-finite record value, a frame whose height or width is no integer >= 1, an order code outside
+ *   0..5, a frame extent [offset, offset + 3 H W) beyond frames_bytes, `out` not 16-byte aligned, a workspace below the
+ *   query.  A singular trans_input is not refused.  Launches on `stream`, never allocates, never synchronises.
+ * ------------------------------------------------------------------------------------------ */
+#define CP_TI_STRIDE 24
+#define CP_TI_OFFSET 0
+#define CP_TI_HEIGHT 1
+#define CP_TI_WIDTH 2
+#define CP_TI_TRANS 3
+#define CP_TI_FLIPPED 9
+#define CP_TI_COLOR 10
+#define CP_TI_ORDER 11
+#define CP_TI_ALPHA 12
+#define CP_TI_SHIFT 15
+#define CP_TI_WS_MEANS(N) ((((size_t)(N) * CP_TI_STRIDE * sizeof(double) + 255) / 256) * 256)
+size_t cp_train_inputs_workspace_bytes(int N, int out_h, int out_w); /* 0: shape refused */
+int cp_train_inputs(cp_stream_t stream, const unsigned char* frames, size_t frames_bytes, const double* records, int N,
+                    const float* mean3, const float* std3, float* out, int out_h, int out_w, void* workspace,
+                    size_t workspace_bytes);
 
 #ifdef __cplusplus
 }
