@@ -276,26 +276,51 @@ __global__ __launch_bounds__(256, 3) void dcn16t_kernel(const ConvParams p, cons
         const bool relu = p.act == CP_ACT_RELU;
         float amax = 0.f;
         // UPADD: u = act(...) + up(t) per 16-byte piece (upadd_common.h).  A lane's pixel, and with it its 2 x 2 taps of t and of the
-        // kernel, is the same for its eight channel quads: four byte offsets into t (a tap outside t: beyond the descriptor, zeros)
-        // and four into the weight table, + the quad's channel offset (scalar).  The table ([tap][64 channels], 4 KB for f = 2, 16 KB
-        // for f = 4) goes into the patch's LDS, which is dead once every wave has left the K loop; a tap's row is U_WSTR bytes so
-        // that the (tap, lane half) pairs of one ds_read_b128 spread over the banks.
-        constexpr int U_WSTR = 64 * 4 + 32;
-        __amdgpu_buffer_rsrc_t r_t = r_sc;
-        unsigned u_toff[2][2];
-        int u_woff[2][2];
+        // kernel, is the same for its eight channel quads: four byte offsets to the taps of t and four into the weight table, + the
+        // quad's channel offset (scalar).  Both are read from the patch's LDS, which is dead once every wave has left the K loop:
+        //   * the rectangle of t the patch can touch: rows iy0(ty0) - 1 .. iy0(ty0 + 7) = ty0 / f - 1 .. (ty0 + 8) / f (cp_upadd_axis:
+        //     ty0 % f == 0 and p < f), columns likewise: 6 x 10 pixels for f = 2, 4 x 6 for f = 4, all 64 channels, copied once per
+        //     workgroup with coalesced 16-byte loads (a pixel of t that does not exist: beyond the descriptor, zeros -- the padding
+        //     rule of cp_upadd_piece).  The 128 pixels x 4 taps that the lanes read are these 60 (24) pixels ~9 (~21) times over;
+        //     fetched per lane they went through the texture path, which also carries every wave's copy of the weights.  A pixel
+        //     is U_TSTR bytes = 17 bank groups: the 16 lanes of a ds_read_b128 group are 16 consecutive pixels of one patch row,
+        //     i.e. 9 (5) consecutive staged pixels -- as many different groups;
+        //   * behind it the table ([tap][64 channels], 4.5 KB for f = 2, 18 KB for f = 4); a tap's row is U_WSTR bytes so that the
+        //     (tap, lane half) pairs of one ds_read_b128 spread over the banks.
+        // Both copies are four pieces per thread with no branch around any of them (a branch makes every load wait for the one
+        // before it): a piece past the end of the region (table) loads zeros (piece 0 again) and lands in the slack behind it.
+        constexpr int U_WSTR = 64 * 4 + 32, U_TSTR = 64 * 4 + 16, U_NP = 4 * 256 / 16;  // U_NP: pixels (taps) four pieces per thread cover
+        constexpr int U_TBL = U_NP * U_TSTR;                                            // the table's place in the patch
+        int u_toff[2][2], u_woff[2][2];
         if constexpr (UPADD) {
             const int f = p.up_f, k = 2 * f, Ht = p.H / f, Wt = p.W / f, ntap = k * k;
-            static_assert(T_NPIX_ALL * T_PSTR >= 64 * U_WSTR, "the f = 4 table fits the patch");
+            static_assert(U_TBL + U_NP * U_WSTR <= T_NPIX_ALL * T_PSTR, "the staged region of t and the table, with their slack, fit the patch");
+            static_assert((T_TH / 2 + 2) * (T_TW / 2 + 2) <= U_NP && (T_TH / 4 + 2) * (T_TW / 4 + 2) <= U_NP && 4 * 4 * 4 <= U_NP,
+                          "four pieces per thread cover the region and the table");
+            static_assert((U_TSTR / 16) % 2 == 1, "odd region pixel pitch in bank groups");
             const int t = wid * 64 + ln;  // (the thread id, rebuilt like the lane id: not held across the K loops)
+            const int rw = T_TW / f + 2, npix = (T_TH / f + 2) * rw;  // the region: width, pixels
+            const int rinv = f == 2 ? 65536 / (T_TW / 2 + 2) + 1 : 65536 / (T_TW / 4 + 2) + 1;  // q / rw = q * rinv >> 16 for q < U_NP
+            const int ry0 = ty0 / f - 1, rx0 = tx0 / f - 1;           // the region's origin in t
+            const __amdgpu_buffer_rsrc_t r_t = make_rsrc(p.up_t, (unsigned)p.B * Ht * Wt * (unsigned)p.up_ld * 4u);
             __syncthreads();  // every wave is done with the patch
+            float4 tv[4], wv[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {  // piece i of the region = (pixel q = i / 16 = (row, column) row-major, channel quad i % 16)
+                const int q = (t >> 4) + 16 * r, row = (q * rinv) >> 16;
+                const int iy = ry0 + row, ix = rx0 + q - row * rw;
+                const bool ok = q < npix && (unsigned)iy < (unsigned)Ht && (unsigned)ix < (unsigned)Wt;
+                tv[r] = buf_ld4s(r_t, ok ? (unsigned)(((b * Ht + iy) * Wt + ix) * p.up_ld) * 4u + 16u * (t & 15) : OOB_BASE, 0);
+            }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {  // piece i of the table = (tap i / 16, channel quad i % 16)
                 const int i = t + 256 * r;
-                if (i < ntap * 16)
-                    *reinterpret_cast<float4*>(patch + (i >> 4) * U_WSTR + (i & 15) * 16) = reinterpret_cast<const float4*>(p.up_wt)[i];
+                wv[r] = reinterpret_cast<const float4*>(p.up_wt)[i < ntap * 16 ? i : 0];
             }
-            r_t = make_rsrc(p.up_t, (unsigned)p.B * Ht * Wt * (unsigned)p.up_ld * 4u);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) *reinterpret_cast<float4*>(patch + ((t >> 4) + 16 * r) * U_TSTR + (t & 15) * 16) = tv[r];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) *reinterpret_cast<float4*>(patch + U_TBL + ((t >> 4) + 16 * r) * U_WSTR + (t & 15) * 16) = wv[r];
             int ky0, kx0, iy0, ix0;
             cp_upadd_axis(ty0 + 2 * wid + patch_perm_row(lc), f, &ky0, &iy0);
             cp_upadd_axis(tx0 + patch_perm_col(lc), f, &kx0, &ix0);
@@ -303,12 +328,10 @@ __global__ __launch_bounds__(256, 3) void dcn16t_kernel(const ConvParams p, cons
             for (int a = 0; a < 2; ++a)
 #pragma unroll
                 for (int bb = 0; bb < 2; ++bb) {
-                    const int iy = iy0 - a, ix = ix0 - bb;
-                    const bool ok = (unsigned)iy < (unsigned)Ht && (unsigned)ix < (unsigned)Wt;
-                    u_toff[a][bb] = ok ? (unsigned)(((b * Ht + iy) * Wt + ix) * p.up_ld) * 4u + 16u * h4 : OOB_BASE;
-                    u_woff[a][bb] = ((ky0 + a * f) * k + kx0 + bb * f) * U_WSTR + 16 * h4;
+                    u_toff[a][bb] = ((iy0 - a - ry0) * rw + ix0 - bb - rx0) * U_TSTR + 16 * h4;
+                    u_woff[a][bb] = U_TBL + ((ky0 + a * f) * k + kx0 + bb * f) * U_WSTR + 16 * h4;
                 }
-            __syncthreads();  // the table is in LDS
+            __syncthreads();  // the table and the region are in LDS
         }
 #pragma unroll
         for (int j = 0; j < NT; ++j)
@@ -329,7 +352,7 @@ __global__ __launch_bounds__(256, 3) void dcn16t_kernel(const ConvParams p, cons
                     for (int a = 0; a < 2; ++a)
 #pragma unroll
                         for (int bb = 0; bb < 2; ++bb) {
-                            tv[a][bb] = buf_ld4s(r_t, u_toff[a][bb], nsc);
+                            tv[a][bb] = *reinterpret_cast<const float4*>(patch + u_toff[a][bb] + (32 * j + 8 * g4) * 4);
                             wv[a][bb] = *reinterpret_cast<const float4*>(patch + u_woff[a][bb] + (32 * j + 8 * g4) * 4);
                         }
                     const float4 u = cp_upadd_piece(tv, wv, make_float4(v[0], v[1], v[2], v[3]));
