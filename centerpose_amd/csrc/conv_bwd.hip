@@ -15,6 +15,9 @@
 //               roles swapped (pack_dgrad_kernel).  Stride 2, MFMA path: dgrad_s2_kernel, one dense contraction per input
 //               pixel parity class (deconv16.hip's sub-pixel form), written straight into the interleaved grad_x.  Generic
 //               path: a gather per grad_x element (dgrad_generic_kernel).  Not launched when the caller passes no grad_x.
+// A third path takes the 16-channel 3x3s of DLA's levels 0-1 (cp_conv_backward_lowc: 3x3 / pad 1, stride 1 | 2, 16 -> 16 | 32,
+// at least 4096 output pixels): steps 1 and 2 are conv_bwd_lowc.hip's kernels, step 0 and the slab reduction are the ones
+// here.  cp_conv_backward_path names the path of a geometry, for the launch and for cp_conv2d_backward_path alike.
 // The MFMA weight gradient and the stride-1 data gradient are also the library's only ones: cp_launch_conv_wgrad and
 // cp_launch_conv_dgrad_pack / _s1 (cp_common.h) are what step 1 and 2 call, and what heads_bwd.hip calls for its 3x3 layer.
 // cp_launch_rowsum_nchw, the NCHW bias gradient of dcn_bwd.hip and heads_bwd.hip, is here for the same reason.
@@ -399,15 +402,18 @@ ConvWgradPlan slab_plan(size_t rows, size_t ns, size_t wbytes, int jobs) {
 }
 
 struct Plan {
+    int path;  // CP_CONV_BWD_*
     bool mfma;
     int Ho, Wo, CoP, taps;
     int st_ct, st_px, st_slabs, st_bound;  // stage_kernel: channel lanes, pixels per slab, slabs and their upper bound
-    ConvWgradPlan wg;                      // weight gradient, either path
+    ConvWgradPlan wg;                      // weight gradient, MFMA and generic path
+    ConvLowcPlan lw;                       // weight gradient, low-channel path
 };
 
 Plan plan(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
     Plan P;
-    P.mfma = cp_conv_backward_mfma(Cin, KH, KW, stride, pad);
+    P.path = cp_conv_backward_path(B, H, W, Cin, Cout, KH, KW, stride, pad);
+    P.mfma = P.path == CP_CONV_BWD_MFMA;
     P.Ho = (H + 2 * pad - KH) / stride + 1;
     P.Wo = (W + 2 * pad - KW) / stride + 1;
     P.taps = KH * KW;
@@ -420,6 +426,12 @@ Plan plan(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, in
     P.st_px = (int)((Q + P.st_bound - 1) / P.st_bound);
     P.st_slabs = (int)((Q + P.st_px - 1) / P.st_px);
     P.wg = P.mfma ? cp_conv_wgrad_plan(rows, Cin, P.CoP, P.taps) : slab_plan(rows, 64, (size_t)P.CoP * P.taps * Cin * 4, 0);
+    P.lw = ConvLowcPlan{};
+    if (P.path == CP_CONV_BWD_LOWC) {
+        // the larger of the two plans' slab buffers: the query stays monotone in B across the path's pixel floor
+        P.lw = cp_conv_lowc_wgrad_plan(B, P.Ho, P.Wo, stride);
+        P.wg.slab_bytes = std::max(P.wg.slab_bytes, cp_conv_lowc_slab_bytes(B, P.Ho, P.Wo, Cout, stride));
+    }
     return P;
 }
 
@@ -441,6 +453,18 @@ Ws conv_bwd_carve(Carve& c, const Plan& P, int B, int Cin, int stride, bool need
 
 bool cp_conv_backward_mfma(int Cin, int KH, int KW, int stride, int pad) {
     return KH == KW && (KH == 1 || KH == 3) && (stride == 1 || stride == 2) && pad == KH / 2 && Cin % 32 == 0;
+}
+
+// The pixel floor: below it a plan of hundreds of slabs is waste, and the generic kernels cost microseconds
+bool cp_conv_backward_lowc(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
+    if (KH != 3 || KW != 3 || pad != 1 || (stride != 1 && stride != 2) || Cin != 16 || (Cout != 16 && Cout != 32)) return false;
+    const long long Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+    return B * Ho * Wo >= 4096;
+}
+
+int cp_conv_backward_path(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
+    if (cp_conv_backward_mfma(Cin, KH, KW, stride, pad)) return CP_CONV_BWD_MFMA;
+    return cp_conv_backward_lowc(B, H, W, Cin, Cout, KH, KW, stride, pad) ? CP_CONV_BWD_LOWC : CP_CONV_BWD_GENERIC;
 }
 
 // about two waves per SIMD, at most 512 slabs
@@ -524,6 +548,12 @@ int cp_launch_conv_backward(hipStream_t s, const ConvBwdArgs& a, void* ws) {
     if (P.mfma) {
         const int rc = cp_launch_conv_wgrad(s, a, gs, CoP, P.wg, slab, 0);
         if (rc != CP_OK) return rc;
+    } else if (P.path == CP_CONV_BWD_LOWC) {
+        const int rc = cp_launch_conv_lowc_wgrad(s, a, gs, P.lw, slab);
+        if (rc != CP_OK) return rc;
+        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((Cout * taps * Cin + 31) / 32), dim3(256), 0, s, (const float*)slab, a.gw,
+                           P.lw.wgs, Cout, CoP, Cin, taps, 0);
+        if (!launch_ok()) return CP_ERR_LAUNCH;
     } else {
         const int n = Cout * Cin * taps;
         hipLaunchKernelGGL(wgrad_generic_kernel, dim3((n + 255) / 256, P.wg.slabs), dim3(256), 0, s, gs, a.x, slab, rows, Ho, Wo, H,
@@ -534,6 +564,7 @@ int cp_launch_conv_backward(hipStream_t s, const ConvBwdArgs& a, void* ws) {
     }
     // 2. grad_x
     if (!a.gx) return CP_OK;
+    if (P.path == CP_CONV_BWD_LOWC) return cp_launch_conv_lowc_dgrad(s, a, gs);
     if (!P.mfma) {
         const size_t n = (size_t)B * H * W * Cin;
         hipLaunchKernelGGL(dgrad_generic_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 65536)), dim3(256), 0, s, gs, a.w,

@@ -476,6 +476,10 @@ struct ConvBwdArgs {
     int B, H, W, Cin, Cout, KH, KW, stride, pad;
 };
 bool cp_conv_backward_mfma(int Cin, int KH, int KW, int stride, int pad);  // the geometry takes the MFMA kernels
+// the geometry takes conv_bwd_lowc.hip's kernels: 3x3 / pad 1, stride 1 or 2, 16 -> 16 or 32, at least 4096 output pixels
+bool cp_conv_backward_lowc(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad);
+// CP_CONV_BWD_*: the path cp_launch_conv_backward takes (what cp_conv2d_backward_path reports); a valid geometry is assumed
+int cp_conv_backward_path(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad);
 size_t cp_conv_backward_ws_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int need_grad_x);
 int cp_launch_conv_backward(hipStream_t s, const ConvBwdArgs& a, void* ws);
 // Its two MFMA contractions (cp_conv_backward_mfma geometries) as building blocks: cp_launch_conv_backward is made of them, and
@@ -494,6 +498,17 @@ int cp_launch_conv_wgrad(hipStream_t s, const ConvBwdArgs& a, const float* gs, i
 size_t cp_conv_dgrad_pack_bytes(int Cin, int CoP, int taps);
 int cp_launch_conv_dgrad_pack(hipStream_t s, const float* w, float* wB, int Cin, int Cout, int CoP, int taps);
 int cp_launch_conv_dgrad_s1(hipStream_t s, const ConvBwdArgs& a, const float* gs, int CoP, const float* wB, const float* res);
+// The low-channel 3x3 path (conv_bwd_lowc.hip; cp_conv_backward_lowc geometries, CoP == Cout).  A workgroup walks a contiguous
+// run of `tiles_per_wg` tiles; the weight gradient's workgroups are its slabs [Cout][9 x 16], which the caller sums
+// (wgrad_reduce_kernel's layout and order).
+struct ConvLowcPlan {
+    int tiles_y, tiles_x, tiles, tiles_per_wg, wgs;
+};
+ConvLowcPlan cp_conv_lowc_wgrad_plan(int B, int Ho, int Wo, int stride);
+ConvLowcPlan cp_conv_lowc_dgrad_plan(int B, int H, int W, int stride);
+size_t cp_conv_lowc_slab_bytes(int B, int Ho, int Wo, int Cout, int stride);  // an upper bound of wgs slabs, monotone in B
+int cp_launch_conv_lowc_wgrad(hipStream_t s, const ConvBwdArgs& a, const float* gs, const ConvLowcPlan& P, float* slab);
+int cp_launch_conv_lowc_dgrad(hipStream_t s, const ConvBwdArgs& a, const float* gs);
 // out[c] = sum over images and pixels of g [B,C,HW] (NCHW): a bias gradient, in a fixed order (dcn_bwd.hip, heads_bwd.hip)
 int cp_launch_rowsum_nchw(const float* g, float* out, int B, int C, int HW, hipStream_t s);
 

@@ -455,6 +455,11 @@ int cp_conv2d_nhwc(cp_stream_t stream, const float* x, const float* w, const flo
     return cp_launch_conv(p, s);
 }
 
+int cp_conv2d_backward_path(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
+    if (const char* e = conv_bwd_shape_error(B, H, W, Cin, Cout, KH, KW, stride, pad)) return fail(CP_ERR_INVALID, e);
+    return cp_conv_backward_path(B, H, W, Cin, Cout, KH, KW, stride, pad);
+}
+
 size_t cp_conv2d_backward_workspace_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
                                           int need_grad_x) {
     if (const char* e = conv_bwd_shape_error(B, H, W, Cin, Cout, KH, KW, stride, pad)) {

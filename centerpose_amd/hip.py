@@ -161,6 +161,7 @@ def lib():
          *([c_int] * 10), c_void_p, c_size_t)
     _sig(L.cp_conv2d_backward_workspace_bytes, c_size_t, *([c_int] * 10))
     _sig(L.cp_conv2d_backward_nhwc, c_int, *([c_void_p] * 8), *([c_int] * 9), c_void_p, c_size_t)
+    _sig(L.cp_conv2d_backward_path, c_int, *([c_int] * 9))
     _sig(L.cp_conv_transpose2d_dw_nhwc, c_int, *([c_void_p] * 5), *([c_int] * 5))
     _sig(L.cp_conv_transpose2d_backward_workspace_bytes, c_size_t, *([c_int] * 10))
     _sig(L.cp_conv_transpose2d_backward_nhwc, c_int, *([c_void_p] * 6), *([c_int] * 9), c_void_p, c_size_t)
@@ -279,7 +280,7 @@ def exported_symbols():
             "cp_model_heads_at_workspace_bytes", "cp_model_heads_at", "cp_decode_peaks_workspace_bytes", "cp_decode_peaks",
             "cp_decode_gathered", "cp_pose_heads_chunk_images", "cp_pose_heads_forward_workspace_bytes",
             "cp_pose_heads_forward", "cp_pose_heads_backward_workspace_bytes", "cp_pose_heads_backward",
-            "cp_model_features", "cp_conv2d_backward_workspace_bytes", "cp_conv2d_backward_nhwc",
+            "cp_model_features", "cp_conv2d_backward_workspace_bytes", "cp_conv2d_backward_nhwc", "cp_conv2d_backward_path",
             "cp_batchnorm_workspace_bytes", "cp_batchnorm_forward_nhwc", "cp_batchnorm_backward_nhwc",
             "cp_conv_transpose2d_dw_nhwc", "cp_conv_transpose2d_backward_workspace_bytes",
             "cp_conv_transpose2d_backward_nhwc", "cp_maxpool2d_forward_nhwc", "cp_maxpool2d_backward_nhwc",
@@ -550,6 +551,21 @@ def conv2d_backward(x, w, grad_out, stride=1, pad=0, y=None, need_x_grad=True, n
                                    _ptr(grad_b), B, H, W, Cin, Cout, KH, KW, stride, pad, _ptr(ws), nbytes)
     _check(rc, "cp_conv2d_backward_nhwc")
     return grad_x, grad_w, grad_b
+
+
+CONV_BWD_GENERIC, CONV_BWD_MFMA, CONV_BWD_LOWC = 0, 1, 2   # include/centerpose_hip.h: CP_CONV_BWD_*
+
+
+def conv2d_backward_path(B, H, W, Cin, Cout, KH, KW, stride=1, pad=0):
+    """The kernels ``conv2d_backward`` takes for a geometry (cp_conv2d_backward_path; host arithmetic, no device involved):
+    CONV_BWD_MFMA (KH == KW in {1, 3}, stride 1 | 2, pad == KH // 2, Cin % 32 == 0), CONV_BWD_LOWC (3x3, pad 1, stride 1 | 2,
+    16 -> 16 | 32 channels and at least 4096 output pixels: dla_34's level0 / level1) or CONV_BWD_GENERIC (everything else the
+    operator accepts: correct, not fast).  Raises RuntimeError for a geometry the operator refuses."""
+    L = lib()
+    rc = L.cp_conv2d_backward_path(int(B), int(H), int(W), int(Cin), int(Cout), int(KH), int(KW), int(stride), int(pad))
+    if rc < 0:
+        raise RuntimeError("conv2d_backward_path: shape refused by the library (%s)" % L.cp_last_error().decode())
+    return rc
 
 
 def _bn_vec(t, C, name):

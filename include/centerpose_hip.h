@@ -314,13 +314,20 @@ int cp_conv2d_nhwc(cp_stream_t stream, const float* x, const float* w, const flo
  * all outputs are bitwise reproducible call to call.
  * MFMA path (v_mfma_f32_32x32x2_f32): KH == KW in {1, 3}, stride in {1, 2}, pad == KH / 2, Cin % 32 == 0, any H, W >= 1 and
  * any Cout (grad_out is staged once into the workspace, zero-padded to a multiple of 32 channels: 27 is the case that
- * matters).  Everything else with KH, KW in 1..7, stride in 1..4, 0 <= pad < min(KH, KW), Cin % 4 == 0 takes plain
- * deterministic kernels that are correct, not fast.
+ * matters).  Low-channel path (v_mfma_f32_16x16x4_f32): KH == KW == 3, pad == 1, stride in {1, 2}, Cin == 16, Cout in
+ * {16, 32} and B * Ho * Wo >= 4096 output pixels, any H, W (dla_34's level0 / level1 layers).  Everything else with KH, KW in
+ * 1..7, stride in 1..4, 0 <= pad < min(KH, KW), Cin % 4 == 0 takes plain deterministic kernels that are correct, not fast.
+ * cp_conv2d_backward_path reports which of the three (CP_CONV_BWD_*) cp_conv2d_backward_nhwc takes for a geometry, or
+ * CP_ERR_INVALID (with a cp_last_error() text) for one the operator refuses; host arithmetic.
  * Refused with CP_ERR_INVALID and a cp_last_error() text before any launch (the query returns 0): a NULL pointer other
  * than those named above, a workspace below the query, B / H / W / Cout < 1, Cin % 4 != 0, another geometry, an empty output
  * grid, a tensor of 2^31 elements or more.  The query is host arithmetic; need_grad_x == 0 leaves out the data gradient's
  * operands.  Launches on `stream`, never synchronises.
  * ------------------------------------------------------------------------------------------ */
+#define CP_CONV_BWD_GENERIC 0
+#define CP_CONV_BWD_MFMA 1
+#define CP_CONV_BWD_LOWC 2
+int cp_conv2d_backward_path(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad);
 size_t cp_conv2d_backward_workspace_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
                                           int need_grad_x);
 int cp_conv2d_backward_nhwc(cp_stream_t stream, const float* x, const float* w, const float* y_or_null,

@@ -1,12 +1,13 @@
 """The backbones' ordinary convolutions under training: conv.conv2d (cp_conv2d_nhwc + cp_conv2d_backward_nhwc) next to
 torch.nn.functional.conv2d under torch autograd, channels_last float32 tensors on the same device, in one process (GPU).
 
-    python tools/conv_backward_bench.py [--batch 16] [--iters 5] [--rounds 3] [--nets dla_34 resdcn_18] [--layers level2.] [--out profiles/conv_backward_bench.txt]
+    python tools/conv_backward_bench.py [--batch 16] [--iters 5] [--rounds 3] [--nets dla_34 resdcn_18 dla_34_lowc] [--layers level2.] [--out profiles/conv_backward_bench.txt]
 
 Shapes: every distinct convolution geometry of dla_34 at a 512 x 512 input (levels 2-5: the BasicBlock 3x3 pairs, the 1x1
 projects and Roots; the 3x3 C -> 27 conv_offset_mask of the DLAUp / IDAUp deformable layers) and of resdcn_18 (the residual
-3x3s, the 1x1 stride-2 down-samples, the offset convolutions of the three up-sampling stages).  The 3-channel stems and the
-16-channel levels 0-1 of dla_34 are left out (the stem is outside the operator; levels 0-1 take its generic path).
+3x3s, the 1x1 stride-2 down-samples, the offset convolutions of the three up-sampling stages).  The 3-channel stems are left
+out (the stem is outside the operator).  dla_34's 16-channel levels 0-1 (16 -> 16 at 512 x 512 and 16 -> 32, stride 2, from 512 x
+512: the operator's low-channel path) are a list of their own, `--nets dla_34_lowc`, which a run without --nets leaves out.
 Per shape one JSON line: forward + backward milliseconds of both sides (HIP events around `iters` steps, `rounds` rounds
 alternating library / torch after a warm-up of both; the median round and all rounds), their ratio, and the library's achieved
 fraction of the 157.3 TFLOP/s float32 matrix peak.  FLOP model: 2 * B*Ho*Wo * K*K*Cin * Cout per contraction, one in the
@@ -46,7 +47,10 @@ RESDCN18_512 = [
     ("deconv.dcn_offset.c512", 512, 27, 16, 3, 1), ("deconv.dcn_offset.c256", 256, 27, 32, 3, 1),
     ("deconv.dcn_offset.c128", 128, 27, 64, 3, 1),
 ]
-NETS = {"dla_34": DLA34_512, "resdcn_18": RESDCN18_512}
+# dla_34's 16-channel levels 0-1: the operator's low-channel path (conv_bwd_lowc.hip); --nets dla_34_lowc
+DLA34_LOWC_512 = [("level0.conv3x3", 16, 16, 512, 3, 1), ("level1.conv3x3", 16, 32, 512, 3, 2)]
+NETS = {"dla_34": DLA34_512, "resdcn_18": RESDCN18_512, "dla_34_lowc": DLA34_LOWC_512}
+PATHS = {0: "generic", 1: "mfma", 2: "lowc"}   # include/centerpose_hip.h: CP_CONV_BWD_*
 
 
 def contraction_flops(B, Cin, Cout, R, k, stride):
@@ -64,7 +68,7 @@ def main():
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--nets", nargs="+", default=list(NETS), choices=sorted(NETS))
+    ap.add_argument("--nets", nargs="+", default=["dla_34", "resdcn_18"], choices=sorted(NETS))
     ap.add_argument("--layers", nargs="+", default=None, help="only the layers whose name contains one of these (for kernel traces)")
     ap.add_argument("--precision", default="f32", choices=sorted(hip.PRECISIONS), help="of the forward (the backward is float32)")
     ap.add_argument("--out", default=None)
@@ -95,6 +99,7 @@ def main():
                 continue
             seen[geo] = name
             pad = k // 2
+            path = PATHS[hip.conv2d_backward_path(B, R, R, Cin, Cout, k, k, stride, pad)]
             g = torch.Generator(device=dev).manual_seed(1)
             x = torch.randn(B, Cin, R, R, device=dev, generator=g).contiguous(memory_format=torch.channels_last).requires_grad_(True)
             w = (torch.randn(Cout, Cin, k, k, device=dev, generator=g) / (Cin * k * k) ** 0.5).requires_grad_(True)
@@ -121,7 +126,7 @@ def main():
             med = {s: statistics.median(v) for s, v in res.items()}
             fl = 3 * contraction_flops(B, Cin, Cout, R, k, stride)
             line = {"net": net, "layer": name, "B": B, "Cin": Cin, "Cout": Cout, "HxW": R, "k": k, "stride": stride,
-                    "path": "mfma" if Cin % 32 == 0 and k in (1, 3) and stride in (1, 2) else "generic",
+                    "path": path,
                     "library_ms": round(med["library"], 3), "torch_ms": round(med["torch"], 3),
                     "library_over_torch": round(med["library"] / med["torch"], 2),
                     "library_ms_rounds": [round(v, 3) for v in res["library"]], "torch_ms_rounds": [round(v, 3) for v in res["torch"]],
