@@ -605,6 +605,24 @@ struct cp_pose_targets_track_desc;
 const char* cp_pose_targets_track_check(const cp_pose_targets_track_desc* d);  // nullptr: accepted
 size_t cp_pose_targets_track_ws_bytes(const cp_pose_targets_track_desc* d);    // 0: refused
 int cp_launch_pose_targets_track(hipStream_t s, const cp_pose_targets_track_desc* d, void* ws);
+// its pieces, for the detector-fed variant (pose_targets_track_det.hip): the staged records and the draw lists inside the
+// workspace, the record copies, and everything after the previous-objects kernel
+namespace pose_targets { struct PtkOpts; }
+struct cp_ptk_ws_view {
+    const double *img, *timg, *pre;  // [B][CP_PT_IMG_STRIDE], [B][CP_PTK_IMG_STRIDE], [B][Kp][CP_PTK_PRE_STRIDE]
+    void* res;                        // PtkPreOut [B][Kp]
+    int* counts;                      // [B * 9]
+    void* draws;                      // int4 [B * 9][2 * Kp]
+    double* peaks;                    // [B * 9][2 * Kp]
+};
+pose_targets::PtkOpts cp_ptk_opts(const cp_pose_targets_track_desc* d);
+int cp_ptk_stage(hipStream_t s, const cp_pose_targets_track_desc* d, void* ws, cp_ptk_ws_view* v);
+int cp_ptk_finish(hipStream_t s, const cp_pose_targets_track_desc* d, void* ws);
+// ---- the same with a detector's boxes for some images (pose_targets_track_det.hip; pose_targets_track_det_common.h) ----
+struct cp_pose_targets_track_det_desc;
+const char* cp_pose_targets_track_det_check(const cp_pose_targets_track_det_desc* d);  // nullptr: accepted
+size_t cp_pose_targets_track_det_ws_bytes(const cp_pose_targets_track_det_desc* d);    // 0: refused
+int cp_launch_pose_targets_track_det(hipStream_t s, const cp_pose_targets_track_det_desc* d, void* ws);
 
 // ---- training input images (train_inputs.hip; per-pixel arithmetic in train_inputs_common.h) ----
 const char* cp_train_inputs_check(const unsigned char* frames, size_t frames_bytes, const double* records, int N,

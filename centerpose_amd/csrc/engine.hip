@@ -696,6 +696,20 @@ int cp_pose_targets_track(cp_stream_t stream, const cp_pose_targets_track_desc* 
     return rc == CP_OK ? CP_OK : fail(rc, "pose_targets_track: copy or kernel launch failed");
 }
 
+size_t cp_pose_targets_track_det_workspace_bytes(const cp_pose_targets_track_det_desc* d) {
+    return cp_pose_targets_track_det_ws_bytes(d);
+}
+
+int cp_pose_targets_track_det(cp_stream_t stream, const cp_pose_targets_track_det_desc* d, void* workspace,
+                              size_t workspace_bytes) {
+    if (const char* e = cp_pose_targets_track_det_check(d)) return fail(CP_ERR_INVALID, e);
+    if (!workspace) return fail(CP_ERR_INVALID, "pose_targets_track_det: null workspace");
+    if (workspace_bytes < cp_pose_targets_track_det_ws_bytes(d))
+        return fail(CP_ERR_INVALID, "pose_targets_track_det: workspace too small");
+    const int rc = cp_launch_pose_targets_track_det((hipStream_t)stream, d, workspace);
+    return rc == CP_OK ? CP_OK : fail(rc, "pose_targets_track_det: copy or kernel launch failed");
+}
+
 size_t cp_train_inputs_workspace_bytes(int N, int out_h, int out_w) { return cp_train_inputs_ws_bytes(N, out_h, out_w); }
 
 int cp_train_inputs(cp_stream_t stream, const unsigned char* frames, size_t frames_bytes, const double* records, int N,

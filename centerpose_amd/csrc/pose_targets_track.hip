@@ -76,7 +76,9 @@ Ws carve(const cp_pose_targets_track_desc* d, void* ws) {
     return w;
 }
 
-PtkOpts opts_of(const cp_pose_targets_track_desc* d) {
+}  // namespace
+
+pose_targets::PtkOpts cp_ptk_opts(const cp_pose_targets_track_desc* d) {
     PtkOpts o;
     o.input_w = d->input_w, o.input_h = d->input_h, o.down_ratio = d->down_ratio;
     o.center_3D = d->cur.center_3D, o.pre_hm = d->pre_hm, o.pre_hm_hp = d->pre_hm_hp;
@@ -86,6 +88,8 @@ PtkOpts opts_of(const cp_pose_targets_track_desc* d) {
     o.hm_hp_disturb = d->hm_hp_disturb, o.hp_lost_disturb = d->hp_lost_disturb, o.hp_fp_disturb = d->hp_fp_disturb;
     return o;
 }
+
+namespace {
 
 __global__ void __launch_bounds__(64) pre_objects_kernel(const PtkOpts op, int S, int Kp, const double* __restrict__ img,
                                                          const double* __restrict__ timg, const double* __restrict__ pre,
@@ -105,21 +109,7 @@ __global__ void __launch_bounds__(64) pre_objects_kernel(const PtkOpts op, int S
         ptk_pre_object(im, pre + ((size_t)b * Kp + k) * CP_PTK_PRE_STRIDE, S, op, &r);
         res[(size_t)b * Kp + k] = r.o;
     }
-    const unsigned long long below = (1ull << k) - 1;
-    for (int c = 0; c < NCH; ++c) {
-        int base = 0;
-        for (int f = 0; f < 2; ++f) {
-            const bool v = r.draw_on[c][f] && r.draw_k[c][f] != 0.0;
-            const unsigned long long m = __ballot(v);
-            if (v) {
-                const size_t at = ((size_t)b * NCH + c) * 2 * Kp + base + __popcll(m & below);
-                draws[at] = make_int4(r.draw_xy[c][f][0], r.draw_xy[c][f][1], r.radius, 0);
-                peaks[at] = r.draw_k[c][f];
-            }
-            base += __popcll(m);
-        }
-        if (k == 0) counts[b * NCH + c] = base;
-    }
+    ptk_emit_draws(r, b, k, Kp, counts, draws, peaks);
 }
 
 __global__ void __launch_bounds__(MT) pre_maps_kernel(float* __restrict__ pre_hm, float* __restrict__ pre_hm_hp, int W, int H,
@@ -251,7 +241,8 @@ size_t cp_pose_targets_track_ws_bytes(const cp_pose_targets_track_desc* d) {
     return carve(d, nullptr).bytes;
 }
 
-int cp_launch_pose_targets_track(hipStream_t s, const cp_pose_targets_track_desc* d, void* ws) {
+// the record copies, shared with pose_targets_track_det.hip; `v` receives where the staged records and the lists are
+int cp_ptk_stage(hipStream_t s, const cp_pose_targets_track_desc* d, void* ws, cp_ptk_ws_view* v) {
     const Ws w = carve(d, ws);
     const size_t B = d->cur.B, Kp = d->max_pre_objs, K = d->cur.max_objs;
     if (hipMemcpyAsync(w.timg, d->track_images, B * CP_PTK_IMG_STRIDE * sizeof(double), hipMemcpyHostToDevice, s) != hipSuccess ||
@@ -263,8 +254,15 @@ int cp_launch_pose_targets_track(hipStream_t s, const cp_pose_targets_track_desc
         // its workspace; its launcher stages them again, with the objects)
         hipMemcpyAsync(w.cur, d->cur.images, B * CP_PT_IMG_STRIDE * sizeof(double), hipMemcpyHostToDevice, s) != hipSuccess)
         return CP_ERR_LAUNCH;
-    hipLaunchKernelGGL(pre_objects_kernel, dim3((unsigned)B), dim3(64), 0, s, opts_of(d), d->cur.S, (int)Kp,
-                       (const double*)w.cur, (const double*)w.timg, (const double*)w.pre, w.res, w.counts, w.draws, w.peaks);
+    v->img = (const double*)w.cur, v->timg = w.timg, v->pre = w.pre;
+    v->res = w.res, v->counts = w.counts, v->draws = w.draws, v->peaks = w.peaks;
+    return CP_OK;
+}
+
+// the current frame's kernels and the previous frame's maps, after a previous-objects kernel has left `res` and the lists
+int cp_ptk_finish(hipStream_t s, const cp_pose_targets_track_desc* d, void* ws) {
+    const Ws w = carve(d, ws);
+    const size_t B = d->cur.B, Kp = d->max_pre_objs;
     PtTrackCur tk = {};
     tk.on = 1, tk.Kp = (int)Kp, tk.pre_hm_hp = d->pre_hm_hp, tk.tracking = d->tracking, tk.tracking_hp = d->tracking_hp;
     tk.timg = w.timg, tk.cur = w.curo, tk.pre = w.res;
@@ -280,4 +278,12 @@ int cp_launch_pose_targets_track(hipStream_t s, const cp_pose_targets_track_desc
                            (const int4*)w.draws, (const double*)w.peaks);
     }
     return hipGetLastError() == hipSuccess ? CP_OK : CP_ERR_LAUNCH;
+}
+
+int cp_launch_pose_targets_track(hipStream_t s, const cp_pose_targets_track_desc* d, void* ws) {
+    cp_ptk_ws_view v;
+    if (cp_ptk_stage(s, d, ws, &v) != CP_OK) return CP_ERR_LAUNCH;
+    hipLaunchKernelGGL(pre_objects_kernel, dim3((unsigned)d->cur.B), dim3(64), 0, s, cp_ptk_opts(d), d->cur.S, d->max_pre_objs,
+                       v.img, v.timg, v.pre, (PtkPreOut*)v.res, v.counts, (int4*)v.draws, v.peaks);
+    return cp_ptk_finish(s, d, ws);
 }

@@ -102,23 +102,40 @@ PT_HD double ptk_heat(double nx, double ny) {
     return v > 0 ? v : 0.0;  // np.maximum propagates a NaN; the truncated normals are finite
 }
 
-// `img` has pose_targets_common.h's image layout with the PREVIOUS frame's affine (trans_input_pre) and projection
-// matrix in it; `pre` is one previous-object record; S the category's variant count (theta = 2 pi / S).
-PT_HD void ptk_pre_object(const double* img, const double* pre, int S, const PtkOpts& op, PtkPre* res) {
+// what ptk_pre_object and ptk_pre_object_det (pose_targets_track_det_common.h) share of one previous object: the points,
+// the box and the noisy centre (:575-720)
+struct PtkGeo {
+    long long pi[8][2];  // pts_pre[:, :2] before the joints' affine
+    int vis[8];
+    int idsym, radius;
+    double w, h;
+    double nx, ny;         // the centre's noise (:715)
+    double ct0[2], ct[2];  // the centre and the noisy centre: float32 values by box, float64 under center_3D
+};
+
+PT_HD void ptk_pre_clear(const double* pre, PtkPre* res) {
     PtkPreOut& o = res->o;
     o.kept = 0, o.id = (int)pre[CP_PTK_PRE_ID], o.chosen = -1, o.cts_none = 1, o.cts[0] = o.cts[1] = 0.0, o.pmask = 0, o.pad = 0;
     for (int i = 0; i < 2 * CP_PT_JOINTS; ++i) o.pts[i] = 0.f;
     res->radius = 0;
     for (int c = 0; c < 1 + CP_PT_JOINTS; ++c) res->draw_on[c][0] = res->draw_on[c][1] = 0;
-    if (pre[CP_PTK_PRE_SKIP] != 0.0) return;  // the cup / mug filter (:567-571)
+}
+
+// `img` has pose_targets_common.h's image layout with the PREVIOUS frame's affine (trans_input_pre) and projection
+// matrix in it; `pre` is one previous-object record; S the category's variant count (theta = 2 pi / S).  Returns false
+// for an object that the cup / mug filter or the box and visibility tests of :641 drop.
+PT_HD bool ptk_pre_geometry(const double* img, const double* pre, int S, const PtkOpts& op, PtkGeo* g) {
+    if (pre[CP_PTK_PRE_SKIP] != 0.0) return false;  // the cup / mug filter (:567-571)
     const double* tr = img + CP_PT_IMG_TRANS;
     const double* dw = pre + CP_PTK_PRE_DRAWS;
     const double width = img[CP_PT_IMG_WIDTH], height = img[CP_PT_IMG_HEIGHT];
     const bool flipped = img[CP_PT_IMG_FLIPPED] != 0.0;
     const int idsym = (int)pre[CP_PTK_PRE_IDSYM];
+    g->idsym = idsym;
+    long long (*pi)[2] = g->pi;
+    int* vis = g->vis;
     // the 9 points, visibility, flip: as the current frame's (:575-626)
     double p[9][2];
-    long long pi[8][2];
     if ((int)pre[CP_PT_OBJ_NSYM] != 1) {
         long long q[9][2];
         pt_project(img, pre, idsym, S, q);
@@ -126,7 +143,7 @@ PT_HD void ptk_pre_object(const double* img, const double* pre, int S, const Ptk
     } else {
         for (int i = 0; i < 9; ++i) p[i][0] = pre[CP_PT_OBJ_CUBOID + 2 * i], p[i][1] = pre[CP_PT_OBJ_CUBOID + 2 * i + 1];
     }
-    int vis[8], vsum = 0;
+    int vsum = 0;
     for (int i = 0; i < 8; ++i) {
         const double x = p[i + 1][0], y = p[i + 1][1];
         vis[i] = (x >= width || x < 0 || y < 0 || y >= height) ? 1 : 2;
@@ -168,13 +185,15 @@ PT_HD void ptk_pre_object(const double* img, const double* pre, int S, const Ptk
     const double h = bb[3] - bb[1], w = bb[2] - bb[0];
     const double cx0 = p[0][0], cy0 = p[0][1];
     const bool visible = !((cx0 >= width || cx0 < 0 || cy0 < 0 || cy0 >= height) && vsum <= 12);  // :636-639
-    if (!(((h > 0 && w > 0) || img[CP_PT_IMG_ROT] != 0.0) && visible)) return;
+    if (!(((h > 0 && w > 0) || img[CP_PT_IMG_ROT] != 0.0) && visible)) return false;
     const double rr = pt_gaussian_radius(ceil(h), ceil(w));
     const int radius = rr > 0 ? (int)rr : 0;
-    res->radius = radius;
+    g->radius = radius, g->w = w, g->h = h;
     // the centre, its noise and its truncation (:698-720): a float32 array by box, float64 under center_3D
     const double nx = dw[CP_PTK_DRAW_CT_NOISE], ny = dw[CP_PTK_DRAW_CT_NOISE + 1];
-    double ct0[2], ct[2];
+    double* ct0 = g->ct0;
+    double* ct = g->ct;
+    g->nx = nx, g->ny = ny;
     if (!op.center_3D) {
         ct0[0] = (double)(float)((bb[0] + bb[2]) / 2), ct0[1] = (double)(float)((bb[1] + bb[3]) / 2);
         ct[0] = (double)(float)(ct0[0] + nx * op.hm_disturb * w);
@@ -184,6 +203,23 @@ PT_HD void ptk_pre_object(const double* img, const double* pre, int S, const Ptk
         ct[0] = ct0[0] + nx * op.hm_disturb * w;
         ct[1] = ct0[1] + ny * op.hm_disturb * h;
     }
+    return true;
+}
+
+PT_HD void ptk_pre_object(const double* img, const double* pre, int S, const PtkOpts& op, PtkPre* res) {
+    PtkPreOut& o = res->o;
+    ptk_pre_clear(pre, res);
+    PtkGeo g;
+    if (!ptk_pre_geometry(img, pre, S, op, &g)) return;
+    const double* tr = img + CP_PT_IMG_TRANS;
+    const double* dw = pre + CP_PTK_PRE_DRAWS;
+    const long long (*pi)[2] = g.pi;
+    const int* vis = g.vis;
+    const int idsym = g.idsym, radius = g.radius;
+    const double w = g.w, h = g.h, nx = g.nx, ny = g.ny;
+    const double* ct0 = g.ct0;
+    const double* ct = g.ct;
+    res->radius = radius;
     const long long cix = pt_trunc(ct[0]), ciy = pt_trunc(ct[1]);
     // the noisy centre left the input: the object is in none of the lists (:725-727)
     if (cix >= op.input_w || ciy >= op.input_h || cix < 0 || ciy < 0) return;
@@ -247,6 +283,31 @@ PT_HD void ptk_pre_object(const double* img, const double* pre, int S, const Ptk
         }
     }
 }
+
+#ifdef __HIPCC__
+// One wavefront, lane k = previous object k of image b: compacts the Gaussians to draw, per channel, into the image's
+// lists as (x, y, r, 0) and a peak, with ballots in object order, an object's own draws before the false positives; a
+// draw with k == 0 adds nothing to a map of non-negative values and is dropped.  Every lane of the wavefront calls it.
+__device__ __forceinline__ void ptk_emit_draws(const PtkPre& r, int b, int k, int Kp, int* __restrict__ counts,
+                                               int4* __restrict__ draws, double* __restrict__ peaks) {
+    constexpr int nch = 1 + CP_PT_JOINTS;
+    const unsigned long long below = (1ull << k) - 1;
+    for (int c = 0; c < nch; ++c) {
+        int base = 0;
+        for (int f = 0; f < 2; ++f) {
+            const bool v = r.draw_on[c][f] && r.draw_k[c][f] != 0.0;
+            const unsigned long long m = __ballot(v);
+            if (v) {
+                const size_t at = ((size_t)b * nch + c) * 2 * Kp + base + __popcll(m & below);
+                draws[at] = make_int4(r.draw_xy[c][f][0], r.draw_xy[c][f][1], r.radius, 0);
+                peaks[at] = r.draw_k[c][f];
+            }
+            base += __popcll(m);
+        }
+        if (k == 0) counts[b * nch + c] = base;
+    }
+}
+#endif
 
 }  // namespace pose_targets
 

@@ -371,6 +371,42 @@ CP_HD void trk_quat_to_matrix(const double* q, double* R) {  // scipy Rotation.f
     R[6] = 2 * (x * z - y * w);     R[7] = 2 * (y * z + x * w);     R[8] = 1 - 2 * (x * x + y * y);
 }
 
+// pnp_shell's normalised points and rejects (cuboid_pnp_shell.py:46-88), shared by trk_finish and the training targets'
+// detector matching (pose_targets_track_det_common.h).  trk_shell_pnp: `pnp` [18] = the centroid of the 8 projected
+// vertices of `row`, then the vertices, divided by the image size; returns 1 when the detection survives the category rule
+// and the visible-centroid test.  trk_shell_ori: the same packaging of the detection's `kps` into `ori` [18].
+CP_HD int trk_shell_pnp(int cat_rule, double W0, double H0, const double* row, double* pnp) {
+    double mx = 0, my = 0;
+    for (int v = 0; v < 8; ++v) { mx += row[8 + 2 * v]; my += row[9 + 2 * v]; }
+    pnp[0] = (mx / 8) / W0;
+    pnp[1] = (my / 8) / H0;
+    for (int v = 0; v < 8; ++v) {
+        pnp[2 * (v + 1)] = row[8 + 2 * v] / W0;
+        pnp[2 * (v + 1) + 1] = row[9 + 2 * v] / H0;
+    }
+    if (cat_rule != 2) {
+        const int thr = cat_rule == 1 ? 6 : 3;
+        int n_out = 0;
+        for (int v = 0; v < 9; ++v) {
+            const double px = pnp[2 * v], py = pnp[2 * v + 1];
+            if (px < 0 || px > 1 || py < 0 || py > 1) ++n_out;
+        }
+        if (n_out >= thr) return 0;
+    }
+    const double px = pnp[0], py = pnp[1];
+    return (px > 0 && px < 1 && py > 0 && py < 1) ? 1 : 0;
+}
+CP_HD void trk_shell_ori(double W0, double H0, const double* kps16, double* ori) {
+    double mx = 0, my = 0;
+    for (int v = 0; v < 8; ++v) { mx += kps16[2 * v]; my += kps16[2 * v + 1]; }
+    ori[0] = (mx / 8) / W0;
+    ori[1] = (my / 8) / H0;
+    for (int v = 0; v < 8; ++v) {
+        ori[2 * (v + 1)] = kps16[2 * v] / W0;
+        ori[2 * (v + 1) + 1] = kps16[2 * v + 1] / H0;
+    }
+}
+
 // Everything pnp_shell does after a successful solve (cuboid_pnp_shell.py:26-91).  `row`: the 40 doubles of
 // cp_pnp_solve; `scale3`: the (un-normalised) relative size handed to pnp_shell; `kps16`: the detection's `kps`.
 // Writes location / quaternion / projected_cuboid / kps_3d_cam / kps_pnp into `t` (the reference sets them before its
@@ -399,35 +435,8 @@ CP_HD int trk_finish(const TrackParams& P, const double* vm, const double* row, 
     for (int r = 0; r < 3; ++r) t[TR_KPS_3D + r] = cm[r] / 8;
     // projected points, centroid first, normalised by the image size
     const double W0 = vm[VM_WIDTH], H0 = vm[VM_HEIGHT];
-    double mx = 0, my = 0;
-    for (int v = 0; v < 8; ++v) { mx += row[8 + 2 * v]; my += row[9 + 2 * v]; }
-    t[TR_KPS_PNP] = (mx / 8) / W0;
-    t[TR_KPS_PNP + 1] = (my / 8) / H0;
-    for (int v = 0; v < 8; ++v) {
-        t[TR_KPS_PNP + 2 * (v + 1)] = row[8 + 2 * v] / W0;
-        t[TR_KPS_PNP + 2 * (v + 1) + 1] = row[9 + 2 * v] / H0;
-    }
-    if (P.cat_rule != 2) {
-        const int thr = P.cat_rule == 1 ? 6 : 3;
-        int n_out = 0;
-        for (int v = 0; v < 9; ++v) {
-            const double px = t[TR_KPS_PNP + 2 * v], py = t[TR_KPS_PNP + 2 * v + 1];
-            if (px < 0 || px > 1 || py < 0 || py > 1) ++n_out;
-        }
-        if (n_out >= thr) return 0;
-    }
-    {
-        const double px = t[TR_KPS_PNP], py = t[TR_KPS_PNP + 1];
-        if (!(px > 0 && px < 1 && py > 0 && py < 1)) return 0;
-    }
-    mx = my = 0;
-    for (int v = 0; v < 8; ++v) { mx += kps16[2 * v]; my += kps16[2 * v + 1]; }
-    ori[0] = (mx / 8) / W0;
-    ori[1] = (my / 8) / H0;
-    for (int v = 0; v < 8; ++v) {
-        ori[2 * (v + 1)] = kps16[2 * v] / W0;
-        ori[2 * (v + 1) + 1] = kps16[2 * v + 1] / H0;
-    }
+    if (!trk_shell_pnp(P.cat_rule, W0, H0, row, t + TR_KPS_PNP)) return 0;
+    trk_shell_ori(W0, H0, kps16, ori);
     return 1;
 }
 

@@ -94,6 +94,20 @@ class PoseTargetsTrackDesc(ctypes.Structure):
                [("out_" + n, c_void_p) for n in PTK_OUTPUTS]
 
 
+# ---- the same with a detector's boxes (cp_pose_targets_track_det): the host record per image, the render options ----
+PTK_GEN_STRIDE = 4
+PTK_GEN = dict(mode=0, radius_scale=1)
+PTK_DET_MAX_K = 128
+PTK_DET_OPTS = ("K_det", "render_hm_mode", "render_hmhp_mode", "cat_rule")
+PTK_CAT_RULE = {"camera": 0, "bottle": 0, "cup": 0, "book": 1, "chair": 1, "cereal_box": 1, "bike": 2, "laptop": 2, "shoe": 2}
+
+
+class PoseTargetsTrackDetDesc(ctypes.Structure):
+    """cp_pose_targets_track_det_desc of include/centerpose_hip.h (field for field)."""
+    _fields_ = [("track", PoseTargetsTrackDesc)] + [(n, c_void_p) for n in ("det_post", "det_count", "det_pnp")] + \
+               [(n, c_int) for n in PTK_DET_OPTS] + [("gen", c_void_p)]
+
+
 # ---- training input images (cp_train_inputs): record layout of include/centerpose_hip.h ----
 TI_STRIDE = 24
 TI_IMG = dict(offset=0, height=1, width=2, trans=3, flipped=9, color=10, order=11, alpha=12, shift=15)
@@ -239,6 +253,8 @@ def lib():
     _sig(L.cp_pose_targets, c_int, c_void_p, ctypes.POINTER(PoseTargetsDesc), c_void_p, c_size_t)
     _sig(L.cp_pose_targets_track_workspace_bytes, c_size_t, ctypes.POINTER(PoseTargetsTrackDesc))
     _sig(L.cp_pose_targets_track, c_int, c_void_p, ctypes.POINTER(PoseTargetsTrackDesc), c_void_p, c_size_t)
+    _sig(L.cp_pose_targets_track_det_workspace_bytes, c_size_t, ctypes.POINTER(PoseTargetsTrackDetDesc))
+    _sig(L.cp_pose_targets_track_det, c_int, c_void_p, ctypes.POINTER(PoseTargetsTrackDetDesc), c_void_p, c_size_t)
     _sig(L.cp_train_inputs_workspace_bytes, c_size_t, c_int, c_int, c_int)
     _sig(L.cp_train_inputs, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_int, ctypes.POINTER(ctypes.c_float),
          ctypes.POINTER(ctypes.c_float), c_void_p, c_int, c_int, c_void_p, c_size_t)
@@ -287,7 +303,7 @@ def exported_symbols():
             "cp_conv2d_stem_backward_workspace_bytes", "cp_conv2d_stem_backward", "cp_groupnorm_workspace_bytes",
             "cp_groupnorm_forward_nhwc", "cp_groupnorm_backward_nhwc", "cp_gru_gate_forward", "cp_gru_gate_backward",
             "cp_pose_targets_track_workspace_bytes", "cp_pose_targets_track", "cp_train_inputs_workspace_bytes",
-            "cp_train_inputs"]
+            "cp_train_inputs", "cp_pose_targets_track_det_workspace_bytes", "cp_pose_targets_track_det"]
 
 
 def _check(rc, what):
@@ -2042,6 +2058,53 @@ def pose_targets_track(records, S, R, flags, track, out):
     if rc == CP_ERR_INVALID:
         raise ValueError("centerpose_hip: cp_pose_targets_track: %s" % L.cp_last_error().decode())
     _check(rc, "cp_pose_targets_track")
+
+
+def pose_targets_track_det(records, S, R, flags, track, det, out):
+    """cp_pose_targets_track_det: cp_pose_targets_track with a detector's boxes for the images whose ``records['ptk_gen']``
+    row asks for data generation mode 1.  ``det``: {'post': [B, K_det, 120] float64, 'count': [B] int32, 'pnp':
+    [B, K_det, 40] float64 device tensors of ``postprocess`` / ``pnp_from_post`` on the previous frames' input images,
+    'render_hm_mode', 'render_hmhp_mode', 'cat_rule'}.  Everything else as pose_targets_track; refused arguments raise
+    ValueError before any launch.  No host synchronisation."""
+    import numpy as np
+
+    names = ("pt_image", "pt_objects", "ptk_image", "ptk_pre_objects", "ptk_cur_objects", "ptk_gen")
+    recs = {k: np.array(records[k], dtype=np.float64, order="C", copy=True) for k in names}
+    B = recs["pt_image"].shape[0]
+    want = {"pt_image": (PT_IMG_STRIDE,), "pt_objects": (None, PT_OBJ_STRIDE), "ptk_image": (PTK_IMG_STRIDE,),
+            "ptk_pre_objects": (None, PTK_PRE_STRIDE), "ptk_cur_objects": (None, PTK_CUR_STRIDE), "ptk_gen": (PTK_GEN_STRIDE,)}
+    for k, tail in want.items():
+        a = recs[k]
+        if a.ndim != 1 + len(tail) or a.shape[0] != B or a.shape[-1] != tail[-1]:
+            raise ValueError("pose_targets_track_det: %s must be [B, %s]" %
+                             (k, ", ".join("K" if t is None else str(t) for t in tail)))
+    if recs["ptk_cur_objects"].shape[1] != recs["pt_objects"].shape[1]:
+        raise ValueError("pose_targets_track_det: ptk_cur_objects and pt_objects must have the same max_objs")
+    post, count, pnp = det["post"], det["count"], det["pnp"]
+    if not (post.is_cuda and post.dtype == torch.float64 and post.is_contiguous() and post.dim() == 3 and
+            post.shape[0] == B and post.shape[2] == POST_STRIDE):
+        raise ValueError("pose_targets_track_det: det['post'] must be a contiguous float64 device tensor [B, K_det, %d]"
+                         % POST_STRIDE)
+    K_det = int(post.shape[1])
+    if not (pnp.is_cuda and pnp.dtype == torch.float64 and pnp.is_contiguous() and tuple(pnp.shape) == (B, K_det, PNP_STRIDE)):
+        raise ValueError("pose_targets_track_det: det['pnp'] must be a contiguous float64 device tensor [B, K_det, %d]"
+                         % PNP_STRIDE)
+    if not (count.is_cuda and count.dtype == torch.int32 and count.is_contiguous() and count.numel() == B):
+        raise ValueError("pose_targets_track_det: det['count'] must be a contiguous int32 device tensor [B]")
+    L = lib()
+    d = PoseTargetsTrackDetDesc()
+    d.track = pose_targets_track_desc(recs, S, R, flags, track, out)
+    d.det_post, d.det_count, d.det_pnp = post.data_ptr(), count.data_ptr(), pnp.data_ptr()
+    d.K_det = K_det
+    for n in PTK_DET_OPTS[1:]:
+        setattr(d, n, int(det[n]))
+    d.gen = recs["ptk_gen"].ctypes.data
+    nbytes = L.cp_pose_targets_track_det_workspace_bytes(ctypes.byref(d))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=out["hm"].device) if nbytes else None
+    rc = L.cp_pose_targets_track_det(_stream(), ctypes.byref(d), _ptr(ws), nbytes)
+    if rc == CP_ERR_INVALID:
+        raise ValueError("centerpose_hip: cp_pose_targets_track_det: %s" % L.cp_last_error().decode())
+    _check(rc, "cp_pose_targets_track_det")
 
 
 def train_inputs_means_offset(N):

@@ -48,7 +48,8 @@ typedef struct cp_model cp_model;
  *     cp_decode_peaks(_workspace_bytes), cp_decode_gathered; CP_NUM_KERNEL_VARIANTS 46;
  *     cp_pose_heads_forward / _backward (+ _workspace_bytes, cp_pose_heads_chunk_images), cp_model_features;
  *     cp_groupnorm_workspace_bytes, cp_groupnorm_forward_nhwc / _backward_nhwc, cp_gru_gate_forward / _backward;
- *     cp_train_inputs_workspace_bytes, cp_train_inputs. */
+ *     cp_train_inputs_workspace_bytes, cp_train_inputs;
+ *     cp_pose_targets_track_det_workspace_bytes, cp_pose_targets_track_det. */
 #define CP_ABI_VERSION 7
 const char* cp_version(void);
 int cp_abi_version(void);
@@ -929,9 +930,9 @@ int cp_pose_targets(cp_stream_t stream, const cp_pose_targets_desc* d, void* wor
 /* ------------------------------------------------------------------------------------------
  * ObjectPose training targets of the tracking task (CenterPoseTrack) — replaces Step 1 of ObjectPoseDataset.__getitem__
  *   in its noise-simulation mode, datasets/dataset_combined.py:555-937 with data_generation_mode == 0 (the detector-in-
- *   the-loop lines 468-550, 644-693, 752-763, 890-911, 939-952 are not built), and the three places where Step 2 reads
- *   its results: the cup / mug skip (:968-972), the variant filter (:983-987), tracking / tracking_hp (:1106-1117,
- *   :1129-1137).  `cur` is cp_pose_targets' descriptor for the current frame, unchanged in meaning; every output of
+ *   the-loop lines 468-550, 644-693, 752-763, 890-911, 939-952 are cp_pose_targets_track_det's, below), and the three
+ *   places where Step 2 reads its results: the cup / mug skip (:968-972), the variant filter (:983-987), tracking /
+ *   tracking_hp (:1106-1117, :1129-1137).  `cur` is cp_pose_targets' descriptor for the current frame, unchanged in meaning; every output of
  *   cp_pose_targets is written too.  The host keeps the choice of the previous frame (:415-425), both frames' images and
  *   JSON, the augmentation draws, the affines trans_input_pre (:438-449) and trans_output_rot, and ALL random draws: a
  *   fixed set per previous object, filled whether or not the object ends up using them
@@ -1010,6 +1011,63 @@ typedef struct cp_pose_targets_track_desc {
 } cp_pose_targets_track_desc;
 size_t cp_pose_targets_track_workspace_bytes(const cp_pose_targets_track_desc* d); /* 0: shape refused */
 int cp_pose_targets_track(cp_stream_t stream, const cp_pose_targets_track_desc* d, void* workspace, size_t workspace_bytes);
+
+/* ------------------------------------------------------------------------------------------
+ * The same targets with the detector in the loop — adds data_generation_mode == 1 of ObjectPoseDataset.__getitem__
+ *   (datasets/dataset_combined.py:464-550 the matching, :644-693, :752-763, :792-794, :851-867, :890-911, :939-952 the
+ *   per-object branches) for the images whose record asks for it; the other images of the batch are computed exactly as
+ *   cp_pose_targets_track computes them (bit for bit).  The detector's answer arrives as the DEVICE records of
+ *   cp_postprocess and cp_pnp_from_post on the previous frame's input image; what BaseDetector.run and pnp_shell do
+ *   between them and `boxes` (base_detector.py:547-654, cuboid_pnp_shell.py:24-91) happens here.
+ * `track` is cp_pose_targets_track's descriptor, unchanged in meaning.  Added:
+ *   det_post  DEVICE float64 [B, K_det, CP_POST_STRIDE], det_count DEVICE int32 [B] (cp_postprocess with the meta of
+ *             get_affine_transform(c, s, 0, (output_res, output_res), inv=1), :479-489), det_pnp DEVICE float64
+ *             [B, K_det, CP_PNP_STRIDE] (cp_pnp_from_post with the camera of :469-473); K_det in [1, 128]
+ *   render_hm_mode 0 / 1, render_hmhp_mode 0..3 (opt.render_hm_mode, opt.render_hmhp_mode)
+ *   cat_rule  pnp_shell's reject by category: 0 camera / bottle / cup (3 points), 1 book / chair / cereal_box (6 points),
+ *             2 bike / laptop / shoe (none)
+ *   gen       HOST float64 [B][CP_PTKD_GEN_STRIDE]: 0 data_generation_mode of the image (0 / 1, the draw of :465, made by
+ *             the host), 1 the radius scale: aug_s when same_aug_pre and frame_dist != 0, else aug_s_pre (:681-690)
+ * Per image in mode 1 (one wavefront per image, two launches for the batch):
+ *   1. slot k < det_count[b] is a box when its PnP status is 1 and pnp_shell's rejects pass on the 9 normalised points
+ *      (the centroid of the 8 reprojected vertices, then the vertices, / width, / height in float64).
+ *   2. instances_2d of every previous object (:506-532): the projected_cuboid in float32; when flipped, x = width - x - 1
+ *      in float32 and the row swaps (0,4), (2,6), (1,5), (3,7) of the NINE-row array (the reference applies flip_idx - 1
+ *      to it, so the centre row trades places with row 4); / width, / height in float32; nine points of -10000 when row 0
+ *      is not strictly inside (0, 1).
+ *   3. per box the Frobenius norms of rows 1..8 against every object, summed in float64 in row order, and the first
+ *      minimum (:542-543); per object the only box whose minimum it is, whatever its distance, or among several the
+ *      nearest (lowest slot on exact ties), dropped when its norm exceeds 1000 (:646-661).
+ *   4. the matched object reads of its box: ct (:665), kps_ori rows 1..8 (render_hmhp_mode 0 / 1) or the reprojected
+ *      rows 1..8 (2 / 3), kps_heatmap_std and kps_heatmap_height rounded to float32 (the detector returns float32 arrays),
+ *      and a score.  The score is the one of the image's LAST box, not of the matched one: :949-951 read the loop variable
+ *      `result_ori` that the matching loop of :539-540 leaves behind.
+ *   Rounding points: ct_detector and pts_detector go through float32 into affine_transform, its products in float64;
+ *   pts_detector * (width, height) in float64; the tracking label of a matched object under tracking_label_mode 1 is
+ *   ct_detector / down_ratio in float64 and float32(pts_detector) / down_ratio in float32; the in-bounds test of :893-896
+ *   is on the float64 point and the draw at its truncation; radius_detector[j, 0] = int32(float64(float32 std[2 j]) *
+ *   scale); the peaks are float64(float32 height[j]), 1, or the score.  The noise draws of :715, :808, :814 are read as in
+ *   mode 0; the test of :725-727 does not apply, so an object whose noisy centre left the input stays in the lists.
+ * Refused with CP_ERR_INVALID before any device work: whatever cp_pose_targets_track refuses in `track`, NULL det_post /
+ *   det_count / det_pnp / gen, det_post / det_pnp not 8-byte or det_count not 4-byte aligned, K_det outside [1, 128], a
+ *   mode other than 0 / 1, a radius scale that is not finite, render_hm_mode outside 0..1, render_hmhp_mode outside 0..3,
+ *   cat_rule outside 0..2, a workspace below the query.  Launches on `stream`, never allocates, never synchronises.
+ * ------------------------------------------------------------------------------------------ */
+#define CP_PTKD_GEN_STRIDE 4
+#define CP_PTKD_GEN_MODE 0
+#define CP_PTKD_GEN_RADIUS_SCALE 1
+#define CP_PTKD_MAX_K 128
+typedef struct cp_pose_targets_track_det_desc {
+    cp_pose_targets_track_desc track;
+    const double* det_post; /* device */
+    const int* det_count;   /* device */
+    const double* det_pnp;  /* device */
+    int K_det, render_hm_mode, render_hmhp_mode, cat_rule;
+    const double* gen; /* host */
+} cp_pose_targets_track_det_desc;
+size_t cp_pose_targets_track_det_workspace_bytes(const cp_pose_targets_track_det_desc* d); /* 0: shape refused */
+int cp_pose_targets_track_det(cp_stream_t stream, const cp_pose_targets_track_det_desc* d, void* workspace,
+                              size_t workspace_bytes);
 
 /* ------------------------------------------------------------------------------------------
  * Training input images — replaces ObjectPoseDataset._get_input (datasets/dataset_combined.py:278-288, called at :348 for
