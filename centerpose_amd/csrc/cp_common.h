@@ -450,6 +450,9 @@ bool cp_dcn_backward_fast(int C, int kh, int kw, int sh, int sw, int ph, int pw,
 size_t cp_dcn_backward_ws_bytes(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw, int dh,
                                 int dw, int dg);
 int cp_launch_dcn_backward(hipStream_t s, const DcnBwdArgs& a, void* ws);
+// the deterministic form (fast geometry only: the callers check cp_dcn_backward_fast first)
+size_t cp_dcn_backward_det_ws_bytes(int B, int C, int H, int W, int Co);
+int cp_launch_dcn_backward_det(hipStream_t s, const DcnBwdArgs& a, void* ws);
 
 // ---- prediction-head block backward (heads_bwd.hip): n heads conv3x3 -> ReLU -> conv1x1 on one NHWC feature map ----
 struct PoseHeadsArgs {

@@ -22,8 +22,14 @@
 //   4. fast path: the NHWC input gradient back to NCHW.
 // grad_offset, grad_mask, grad_weight and grad_bias are bitwise reproducible (every sum has a fixed order); grad_input
 // is summed with float atomics, so its last bits depend on arrival order.
+//
+// cp_dcnv2_backward_det (fast geometry only) replaces step 2's data kernel by an inverted index: grad_col is stored
+// pixel-major, every (pixel, tap, corner) is sorted by its destination cell, and each cell sums its own list in a fixed
+// order with plain stores -- grad_input is then bitwise reproducible as well (see "the deterministic input gradient" below
+// and the contract in include/centerpose_hip.h).
 #include "op_common.h"
 #include "igemm_common.h"
+#include "dcn_bwd_det_common.h"
 
 #include <algorithm>
 
@@ -62,7 +68,9 @@ __global__ void wt_kernel(const float* __restrict__ w, float* __restrict__ wt, i
 }
 
 // grad_col of images b0 .. b0+nb-1: D[k][pix] over K = Co.  A[k][co] = wt[co][k], B[co][pix] = go[b][co][pix].
-// A workgroup of 4 waves owns 128 k x 128 pixels; each wave 64 x 64 (2 x 2 accumulators).
+// A workgroup of 4 waves owns 128 k x 128 pixels; each wave 64 x 64 (2 x 2 accumulators).  PM: the deterministic path's
+// pixel-major store grad_col[b][pix][k] (a lane's accumulator holds four consecutive k: one 16-byte store; T*C % 4 == 0 there).
+template <bool PM>
 __global__ __launch_bounds__(256) void gcol_kernel(const BwdP p) {
     const int TC = p.C * p.kh * p.kw, HWo = p.Ho * p.Wo;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -100,6 +108,16 @@ __global__ __launch_bounds__(256) void gcol_kernel(const BwdP p) {
         for (int n = 0; n < 2; ++n) {
             const int px = px0 + 32 * n + r;
             if (px >= HWo) continue;
+            if (PM) {
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const int k = k0 + 32 * m + 8 * g + 4 * h;
+                    if (k < TC)
+                        *reinterpret_cast<float4*>(out + (size_t)px * TC + k) =
+                            make_float4(acc[m][n][4 * g], acc[m][n][4 * g + 1], acc[m][n][4 * g + 2], acc[m][n][4 * g + 3]);
+                }
+                continue;
+            }
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 const int k = k0 + 32 * m + (e & 3) + 8 * (e >> 2) + 4 * h;
@@ -356,6 +374,320 @@ __global__ void wgrad_reduce_kernel(const float* __restrict__ slab, float* __res
     }
 }
 
+// ---- the deterministic input gradient (cp_dcnv2_backward_det; fast geometry only) ----
+// Per chunk of nb images, n = nb * H * W * 36 entries (pixel, tap, corner), the entry id = its position at the start:
+//   dcn_det_coord_kernel   grad_offset / grad_mask as the halo kernel sums them, from the pixel-major grad_col;
+//   dcn_det_index_kernel   keys[id] = destination cell of the corner within the chunk, or `cells` where it adds nothing;
+//   rs_* kernels           stable LSD radix sort of (key, id) in 8-bit digits: ids of one cell come out ascending;
+//   dcn_det_rows_kernel    [begin, end) of each cell's list, by key change (cells without a list keep the memset's 0, 0);
+//   dcn_det_gather_kernel  a group of lanes per cell walks the first DCN_DET_CHUNK entries of its list in order and stores
+//                          the NHWC grad_input line with plain stores (zeros for an empty list);
+//   dcn_det_long_kernel    further chunks of a longer list, one wave each, into partial rows;
+//   dcn_det_long_add_kernel  adds a long list's partial rows to its line in chunk order.
+// No float atomic anywhere: the only atomics are the radix histogram's integer counters in LDS.
+
+struct DetP {
+    uint32_t *keys, *ids;  // sorted
+    uint32_t* rows;        // [cells][2]
+    float* partial;        // [ceil(n / DCN_DET_CHUNK)][C]
+    uint32_t n, cells;
+};
+
+// (image of the chunk, pixel, tap) of lane e = pp * 9 + tap, and its sample
+struct DetTap {
+    uint32_t pp;
+    int tap, b, pix;
+    float m;
+    DcnDetSample s;
+};
+__device__ __forceinline__ DetTap det_tap(const BwdP& p, uint32_t e) {
+    const int HW = p.H * p.W;
+    DetTap t;
+    t.pp = e / 9u;
+    t.tap = (int)(e - t.pp * 9u);
+    const int bi = (int)(t.pp / (uint32_t)HW);
+    t.pix = (int)(t.pp - (uint32_t)bi * HW);
+    t.b = p.b0 + bi;
+    const int ho = t.pix / p.W, wo = t.pix - ho * p.W;
+    const float oh = p.off[((size_t)t.b * 18 + 2 * t.tap) * HW + t.pix];
+    const float ow = p.off[((size_t)t.b * 18 + 2 * t.tap + 1) * HW + t.pix];
+    t.m = p.mask[((size_t)t.b * 9 + t.tap) * HW + t.pix];
+    t.s = dcn_det_sample_at(ho, wo, t.tap, oh, ow, p.H, p.W);
+    return t;
+}
+
+__global__ __launch_bounds__(256) void dcn_det_coord_kernel(const BwdP p) {
+    const int C = p.C, HW = p.H * p.W;
+    const uint32_t e = blockIdx.x * 256u + threadIdx.x;
+    if (e >= (uint32_t)p.nb * HW * 9u) return;
+    const DetTap t = det_tap(p, e);
+    const DcnDetSample& s = t.s;
+    const float w1 = s.hh * s.hw, w2 = s.hh * s.lw, w3 = s.lh * s.hw, w4 = s.lh * s.lw;
+    float vh = 0.f, vw = 0.f, mv = 0.f;
+    if (s.in) {
+        const float* xb = p.xh + (size_t)t.b * HW * C;
+        const float* gc = p.gcol + (size_t)e * C;
+        const float* xq[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) xq[q] = xb + (s.c[q] ? ((size_t)(s.y0 + (q >> 1)) * p.W + (s.x0 + (q & 1))) * C : 0);
+        for (int c = 0; c < C; c += 4) {
+            const float4 v1 = s.c[0] ? ld4(xq[0] + c) : zero4();
+            const float4 v2 = s.c[1] ? ld4(xq[1] + c) : zero4();
+            const float4 v3 = s.c[2] ? ld4(xq[2] + c) : zero4();
+            const float4 v4 = s.c[3] ? ld4(xq[3] + c) : zero4();
+            const float4 g4 = ld4(gc + c);
+            const float a1[4] = {v1.x, v1.y, v1.z, v1.w}, a2[4] = {v2.x, v2.y, v2.z, v2.w};
+            const float a3[4] = {v3.x, v3.y, v3.z, v3.w}, a4[4] = {v4.x, v4.y, v4.z, v4.w};
+            const float ga[4] = {g4.x, g4.y, g4.z, g4.w};
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const float g = ga[u];
+                const float cwh = -s.hw * a1[u] - s.lw * a2[u] + s.hw * a3[u] + s.lw * a4[u];
+                const float cww = -s.hh * a1[u] + s.hh * a2[u] - s.lh * a3[u] + s.lh * a4[u];
+                vh += cwh * g * t.m;
+                vw += cww * g * t.m;
+                mv += g * (w1 * a1[u] + w2 * a2[u] + w3 * a3[u] + w4 * a4[u]);
+            }
+        }
+    }
+    p.goff[((size_t)t.b * 18 + 2 * t.tap) * HW + t.pix] = vh;
+    p.goff[((size_t)t.b * 18 + 2 * t.tap + 1) * HW + t.pix] = vw;
+    p.gmask[((size_t)t.b * 9 + t.tap) * HW + t.pix] = mv;
+}
+
+__global__ __launch_bounds__(256) void dcn_det_index_kernel(const BwdP p, uint32_t* __restrict__ keys, uint32_t* __restrict__ ids,
+                                                            uint32_t cells) {
+    const int HW = p.H * p.W;
+    const uint32_t e = blockIdx.x * 256u + threadIdx.x;
+    if (e >= (uint32_t)p.nb * HW * 9u) return;
+    const DetTap t = det_tap(p, e);
+    const int bi = t.b - p.b0;
+    uint4 k, i;
+    k.x = dcn_det_key(t.s, 0, bi, p.H, p.W, cells), i.x = dcn_det_id(t.pp, t.tap, 0);
+    k.y = dcn_det_key(t.s, 1, bi, p.H, p.W, cells), i.y = dcn_det_id(t.pp, t.tap, 1);
+    k.z = dcn_det_key(t.s, 2, bi, p.H, p.W, cells), i.z = dcn_det_id(t.pp, t.tap, 2);
+    k.w = dcn_det_key(t.s, 3, bi, p.H, p.W, cells), i.w = dcn_det_id(t.pp, t.tap, 3);
+    reinterpret_cast<uint4*>(keys)[e] = k;
+    reinterpret_cast<uint4*>(ids)[e] = i;
+}
+
+// Radix pass over the digit (key >> shift) & 255.  A tile is RS_TILE consecutive entries; hist[digit][tile] counts them,
+// the rs_scan_* kernels turn the table (digit-major) into start positions, rs_scatter_kernel moves each entry to its digit's
+// start + its rank among the tile's earlier entries of that digit: stable.
+constexpr int RS_TILE = 4096;
+
+__global__ __launch_bounds__(256) void rs_hist_kernel(const uint32_t* __restrict__ keys, uint32_t* __restrict__ hist, uint32_t n,
+                                                      int shift, uint32_t ntiles) {
+    __shared__ uint32_t cnt[256];
+    cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const uint32_t base = blockIdx.x * (uint32_t)RS_TILE;
+    for (uint32_t i = threadIdx.x; i < (uint32_t)RS_TILE; i += 256) {
+        const uint32_t e = base + i;
+        if (e < n) atomicAdd(&cnt[(keys[e] >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    hist[threadIdx.x * ntiles + blockIdx.x] = cnt[threadIdx.x];
+}
+
+// Exclusive scan of h[0 .. m) in place, m a multiple of 256, in two launches over segments of SCAN_SEG elements (16 per
+// thread, contiguous): rs_scan_sums_kernel leaves each segment's sum, rs_scan_apply_kernel starts a segment at the sum of the
+// segments before it (each workgroup adds those up itself) and scans its own.
+constexpr int SCAN_SEG = 4096;
+
+__device__ __forceinline__ uint32_t block_sum_256(uint32_t (&red)[256], uint32_t v) {
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (uint32_t d = 128; d > 0; d >>= 1) {
+        if (threadIdx.x < d) red[threadIdx.x] += red[threadIdx.x + d];
+        __syncthreads();
+    }
+    const uint32_t r = red[0];
+    __syncthreads();
+    return r;
+}
+
+__global__ __launch_bounds__(256) void rs_scan_sums_kernel(const uint32_t* __restrict__ h, uint32_t* __restrict__ sums, uint32_t m) {
+    __shared__ uint32_t red[256];
+    const uint32_t base = blockIdx.x * (uint32_t)SCAN_SEG + threadIdx.x * 16u;
+    uint32_t s = 0;
+    if (base < m)
+        for (int i = 0; i < 4; ++i) {
+            const uint4 v = reinterpret_cast<const uint4*>(h + base)[i];
+            s += v.x + v.y + v.z + v.w;
+        }
+    const uint32_t total = block_sum_256(red, s);
+    if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(256) void rs_scan_apply_kernel(uint32_t* __restrict__ h, const uint32_t* __restrict__ sums, uint32_t m) {
+    __shared__ uint32_t red[256];
+    const uint32_t t = threadIdx.x, base = blockIdx.x * (uint32_t)SCAN_SEG + t * 16u;
+    uint32_t before = 0;
+    for (uint32_t g = t; g < blockIdx.x; g += 256u) before += sums[g];
+    before = block_sum_256(red, before);
+    uint32_t v[16], s = 0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) v[i] = 0;
+    if (base < m)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const uint4 q = reinterpret_cast<const uint4*>(h + base)[i];
+            v[4 * i] = q.x, v[4 * i + 1] = q.y, v[4 * i + 2] = q.z, v[4 * i + 3] = q.w;
+        }
+#pragma unroll
+    for (int i = 0; i < 16; ++i) s += v[i];
+    red[t] = s;
+    __syncthreads();
+    for (uint32_t d = 1; d < 256u; d <<= 1) {  // inclusive scan of the threads' sums
+        const uint32_t u = t >= d ? red[t - d] : 0u;
+        __syncthreads();
+        red[t] += u;
+        __syncthreads();
+    }
+    uint32_t run = before + red[t] - s;
+    if (base < m)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            uint4 q;
+            q.x = run, run += v[4 * i];
+            q.y = run, run += v[4 * i + 1];
+            q.z = run, run += v[4 * i + 2];
+            q.w = run, run += v[4 * i + 3];
+            reinterpret_cast<uint4*>(h + base)[i] = q;
+        }
+}
+
+// one wave per tile, 64 entries a round in entry order: the rank of an entry among the round's equal digits comes from
+// ballots, the count of earlier rounds from pos[]
+__global__ __launch_bounds__(64) void rs_scatter_kernel(const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__ ids_in,
+                                                        uint32_t* __restrict__ keys_out, uint32_t* __restrict__ ids_out,
+                                                        const uint32_t* __restrict__ hist, uint32_t n, int shift,
+                                                        uint32_t ntiles) {
+    __shared__ uint32_t pos[256];
+    const uint32_t lane = threadIdx.x;
+    for (uint32_t d = lane; d < 256u; d += 64u) pos[d] = hist[d * ntiles + blockIdx.x];
+    __syncthreads();
+    const uint32_t base = blockIdx.x * (uint32_t)RS_TILE;
+    for (uint32_t r = 0; r < (uint32_t)RS_TILE; r += 64u) {
+        const uint32_t e = base + r + lane;
+        const bool valid = e < n;
+        const uint32_t key = valid ? keys_in[e] : 0u, id = valid ? ids_in[e] : 0u;
+        const uint32_t d = (key >> shift) & 255u;
+        unsigned long long same = __ballot(valid);  // the valid lanes with this lane's digit
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            const bool bit = (d >> b) & 1u;
+            const unsigned long long bal = __ballot(bit);
+            same &= bit ? bal : ~bal;
+        }
+        if (valid) {
+            const uint32_t q = pos[d] + (uint32_t)__popcll(same & ((1ull << lane) - 1ull));
+            if (q < n) {  // holds whenever hist is the histogram of keys_in
+                keys_out[q] = key;
+                ids_out[q] = id;
+            }
+        }
+        __syncthreads();
+        if (valid && lane == 63u - (uint32_t)__clzll(same)) pos[d] += (uint32_t)__popcll(same);
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(256) void dcn_det_rows_kernel(const uint32_t* __restrict__ keys, uint32_t* __restrict__ rows,
+                                                           uint32_t n, uint32_t cells) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t k = keys[i];
+    if (k >= cells) return;
+    if (i == 0 || keys[i - 1] != k) rows[2 * (size_t)k] = i;
+    if (i == n - 1 || keys[i + 1] != k) rows[2 * (size_t)k + 1] = i + 1;
+}
+
+// The serial sum, from zero, of the entries ids[beg .. end) for channels c0 .. c0 + 3: w_q * (grad_col * mask), each product
+// rounded (no contraction with the add), the corner weight and the mask recomputed from offset / mask.  `n`: the number of
+// entries; the sorted ids are a permutation of 0 .. n-1, and the test keeps every read in bounds whatever the index holds.
+__device__ __forceinline__ float4 det_sum(const BwdP& p, const uint32_t* __restrict__ ids, uint32_t n, uint32_t beg,
+                                          uint32_t end, int c0) {
+    const int C = p.C, HW = p.H * p.W;
+    float4 acc = zero4();
+    for (uint32_t i = beg; i < end; ++i) {
+        const uint32_t id = ids[i];
+        if (id >= n) continue;
+        uint32_t pp;
+        int tap, q;
+        dcn_det_decode(id, &pp, &tap, &q);
+        const int bi = (int)(pp / (uint32_t)HW), pix = (int)(pp - (uint32_t)bi * HW), b = p.b0 + bi;
+        const int ho = pix / p.W, wo = pix - ho * p.W;
+        const float oh = p.off[((size_t)b * 18 + 2 * tap) * HW + pix], ow = p.off[((size_t)b * 18 + 2 * tap + 1) * HW + pix];
+        const float m = p.mask[((size_t)b * 9 + tap) * HW + pix];
+        const float w = dcn_det_weight(dcn_det_sample_at(ho, wo, tap, oh, ow, p.H, p.W), q);
+        const float4 g = ld4(p.gcol + (size_t)(id >> 2) * C + c0);
+        acc.x += __fmul_rn(w, __fmul_rn(g.x, m));
+        acc.y += __fmul_rn(w, __fmul_rn(g.y, m));
+        acc.z += __fmul_rn(w, __fmul_rn(g.z, m));
+        acc.w += __fmul_rn(w, __fmul_rn(g.w, m));
+    }
+    return acc;
+}
+
+// L lanes per cell (a power of two, 4 .. 64); lane l of the group owns channels 4l .. 4l + 3 of every block of 4L channels
+__global__ __launch_bounds__(256) void dcn_det_gather_kernel(const BwdP p, const DetP d, int L) {
+    const uint32_t gid = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t cell = gid / (uint32_t)L;
+    const int l = (int)(gid - cell * (uint32_t)L);
+    if (cell >= d.cells) return;
+    const uint32_t beg = d.rows[2 * (size_t)cell], end = d.rows[2 * (size_t)cell + 1];
+    const uint32_t stop = min(end, beg + (uint32_t)DCN_DET_CHUNK);
+    float* out = p.gin + ((size_t)p.b0 * p.H * p.W + cell) * p.C;
+    for (int c0 = 4 * l; c0 < p.C; c0 += 4 * L) *reinterpret_cast<float4*>(out + c0) = det_sum(p, d.ids, d.n, beg, stop, c0);
+}
+
+// Wave j looks at the sorted positions [j * CHUNK, (j + 1) * CHUNK).  Chunks of one list start CHUNK apart and a list's
+// chunk t >= 1 starts at least CHUNK behind the list's begin, so at most one chunk t >= 1 starts in that range, and it
+// belongs to the list that covers the range's first position.  Returns false where there is none.
+__device__ __forceinline__ bool det_long_chunk(const DetP& d, uint32_t j, uint32_t* cell, uint32_t* beg, uint32_t* end,
+                                               uint32_t* t) {
+    const uint32_t pos = j * (uint32_t)DCN_DET_CHUNK;
+    if (pos >= d.n) return false;
+    const uint32_t k = d.keys[pos];
+    if (k >= d.cells) return false;
+    const uint32_t s0 = d.rows[2 * (size_t)k], e0 = d.rows[2 * (size_t)k + 1];
+    if (s0 >= pos) return false;  // the list begins here: chunk 0 is the gather kernel's
+    *t = (pos - s0 + (uint32_t)DCN_DET_CHUNK - 1u) / (uint32_t)DCN_DET_CHUNK;
+    *beg = s0 + *t * (uint32_t)DCN_DET_CHUNK;
+    *end = e0;
+    *cell = k;
+    return *beg < e0;
+}
+
+__global__ __launch_bounds__(256) void dcn_det_long_kernel(const BwdP p, const DetP d) {
+    const uint32_t j = blockIdx.x * 4u + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    uint32_t cell, beg, end, t;
+    if (!det_long_chunk(d, j, &cell, &beg, &end, &t)) return;
+    const uint32_t stop = min(end, beg + (uint32_t)DCN_DET_CHUNK);
+    for (int c0 = 4 * lane; c0 < p.C; c0 += 256)
+        *reinterpret_cast<float4*>(d.partial + (size_t)j * p.C + c0) = det_sum(p, d.ids, d.n, beg, stop, c0);
+}
+
+// the wave of a list's chunk 1 adds the list's partial rows to its line, chunks ascending
+__global__ __launch_bounds__(256) void dcn_det_long_add_kernel(const BwdP p, const DetP d) {
+    const uint32_t j = blockIdx.x * 4u + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    uint32_t cell, beg, end, t;
+    if (!det_long_chunk(d, j, &cell, &beg, &end, &t) || t != 1u) return;
+    float* out = p.gin + ((size_t)p.b0 * p.H * p.W + cell) * p.C;
+    for (int c0 = 4 * lane; c0 < p.C; c0 += 256) {
+        float4 acc = ld4(out + c0);
+        for (uint32_t q = beg; q < end; q += (uint32_t)DCN_DET_CHUNK) {
+            const float4 v = ld4(d.partial + (size_t)(q / (uint32_t)DCN_DET_CHUNK) * p.C + c0);
+            acc.x += v.x, acc.y += v.y, acc.z += v.z, acc.w += v.w;
+        }
+        *reinterpret_cast<float4*>(out + c0) = acc;
+    }
+}
+
 struct Plan {
     bool fast;
     int nb, nslab, slab_px;
@@ -393,6 +725,25 @@ Ws dcn_bwd_carve(Carve& c, const Plan& P, int B, int C, int H, int W, int Co, in
     r.gin = P.fast ? c.take<float>((size_t)B * H * W * C * 4) : nullptr;
     r.gcol = c.take<float>((size_t)P.nb * TC * HWo * 4);
     r.slab = c.take<float>((size_t)P.nslab * Co * TC * 4);
+    return r;
+}
+
+// the deterministic path's index of one chunk: keys and ids double-buffered for the radix passes (16 bytes an entry), the
+// digit table, the lists' bounds and the long lists' partial rows
+struct DetWs {
+    uint32_t *keys[2], *ids[2], *hist, *sums, *rows;
+    float* partial;
+};
+DetWs dcn_det_carve(Carve& c, const Plan& P, int C, int H, int W) {
+    const size_t cells = (size_t)P.nb * H * W, n = cells * 36;
+    DetWs r;
+    for (int i = 0; i < 2; ++i) r.keys[i] = c.take<uint32_t>(n * 4);
+    for (int i = 0; i < 2; ++i) r.ids[i] = c.take<uint32_t>(n * 4);
+    const size_t m = 256 * ((n + RS_TILE - 1) / RS_TILE);
+    r.hist = c.take<uint32_t>(m * 4);
+    r.sums = c.take<uint32_t>((m + SCAN_SEG - 1) / SCAN_SEG * 4);
+    r.rows = c.take<uint32_t>(cells * 2 * 4);
+    r.partial = c.take<float>(((n + DCN_DET_CHUNK - 1) / DCN_DET_CHUNK) * C * 4);
     return r;
 }
 
@@ -447,7 +798,7 @@ int cp_launch_dcn_backward(hipStream_t s, const DcnBwdArgs& a, void* ws) {
     for (int b0 = 0; b0 < a.B; b0 += P.nb) {
         p.b0 = b0;
         p.nb = std::min(P.nb, a.B - b0);
-        hipLaunchKernelGGL(gcol_kernel, dim3((HWo + 127) / 128, (TC + 127) / 128, p.nb), dim3(256), 0, s, p);
+        hipLaunchKernelGGL(gcol_kernel<false>, dim3((HWo + 127) / 128, (TC + 127) / 128, p.nb), dim3(256), 0, s, p);
         if (!launch_ok()) return CP_ERR_LAUNCH;
         if (P.fast) {
             const dim3 grid((a.Wo + PT_X - 1) / PT_X, (a.Ho + PT_Y - 1) / PT_Y, p.nb);
@@ -480,4 +831,101 @@ int cp_launch_dcn_backward(hipStream_t s, const DcnBwdArgs& a, void* ws) {
     if (rc != CP_OK) return rc;
     if (P.fast) return cp_launch_nhwc_to_nchw(p.gin, a.grad_input, a.B, a.C, a.H, a.W, a.C, s);
     return CP_OK;
+}
+
+size_t cp_dcn_backward_det_ws_bytes(int B, int C, int H, int W, int Co) {
+    Carve c{nullptr};
+    const Plan P = plan(B, C, H, W, Co, 3, 3, 1, 1, 1, 1, 1, 1, 1);
+    dcn_bwd_carve(c, P, B, C, H, W, Co, H, W, 9);
+    dcn_det_carve(c, P, C, H, W);
+    return c.off;
+}
+
+// The launch sequence of cp_launch_dcn_backward on the fast geometry with the data kernel replaced: pixel-major grad_col,
+// the coord kernel, the index, its sort and the gather; no memset of the input gradient (the gather stores every line).
+int cp_launch_dcn_backward_det(hipStream_t s, const DcnBwdArgs& a, void* ws) {
+    const Plan P = plan(a.B, a.C, a.H, a.W, a.Co, 3, 3, 1, 1, 1, 1, 1, 1, 1);
+    const int T = 9, TC = a.C * T, HW = a.H * a.W;
+    Carve cv{(char*)ws};
+    const Ws r = dcn_bwd_carve(cv, P, a.B, a.C, a.H, a.W, a.Co, a.Ho, a.Wo, T);
+    const DetWs dw = dcn_det_carve(cv, P, a.C, a.H, a.W);
+    BwdP p;
+    p.x = a.input;
+    p.xh = r.xh;
+    p.wt = r.wt;
+    p.off = a.offset;
+    p.mask = a.mask;
+    p.go = a.grad_output;
+    p.go_t = r.go_t;
+    p.gcol = r.gcol;
+    p.gin = r.gin;
+    p.goff = a.grad_offset;
+    p.gmask = a.grad_mask;
+    p.slab = r.slab;
+    p.B = a.B, p.C = a.C, p.H = a.H, p.W = a.W, p.Co = a.Co, p.Ho = a.Ho, p.Wo = a.Wo;
+    p.kh = a.kh, p.kw = a.kw, p.sh = a.sh, p.sw = a.sw, p.ph = a.ph, p.pw = a.pw, p.dh = a.dh, p.dw = a.dw, p.dg = a.dg;
+    p.nb = P.nb, p.slab_px = P.slab_px, p.nslab = P.nslab;
+
+    hipLaunchKernelGGL(wt_kernel, dim3(256), dim3(256), 0, s, a.weight, (float*)p.wt, a.Co, a.C, T);
+    if (!launch_ok()) return CP_ERR_LAUNCH;
+    int rc = cp_launch_nchw_to_nhwc(a.grad_output, (float*)p.go_t, a.B, a.Co, a.Ho, a.Wo, a.Co, s);
+    if (rc != CP_OK) return rc;
+    rc = cp_launch_nchw_to_nhwc(a.input, (float*)p.xh, a.B, a.C, a.H, a.W, a.C, s);
+    if (rc != CP_OK) return rc;
+
+    int L = 4;  // lanes per destination cell: the power of two that covers C / 4 float4 pieces, 64 at most
+    while (L < 64 && 4 * L < a.C) L *= 2;
+    for (int b0 = 0; b0 < a.B; b0 += P.nb) {
+        p.b0 = b0;
+        p.nb = std::min(P.nb, a.B - b0);
+        const uint32_t cells = (uint32_t)p.nb * HW, n = cells * 36u, ntiles = (n + RS_TILE - 1) / RS_TILE;
+        const unsigned tap_blocks = (cells * 9u + 255u) / 256u;
+        hipLaunchKernelGGL(gcol_kernel<true>, dim3((HW + 127) / 128, (TC + 127) / 128, p.nb), dim3(256), 0, s, p);
+        if (!launch_ok()) return CP_ERR_LAUNCH;
+        hipLaunchKernelGGL(dcn_det_coord_kernel, dim3(tap_blocks), dim3(256), 0, s, p);
+        if (!launch_ok()) return CP_ERR_LAUNCH;
+        hipLaunchKernelGGL(dcn_det_index_kernel, dim3(tap_blocks), dim3(256), 0, s, p, dw.keys[0], dw.ids[0], cells);
+        if (!launch_ok()) return CP_ERR_LAUNCH;
+        int src = 0;
+        for (int pass = 0; pass < dcn_det_passes(cells); ++pass, src ^= 1) {
+            hipLaunchKernelGGL(rs_hist_kernel, dim3(ntiles), dim3(256), 0, s, dw.keys[src], dw.hist, n, 8 * pass, ntiles);
+            if (!launch_ok()) return CP_ERR_LAUNCH;
+            const uint32_t m = 256u * ntiles, segs = (m + SCAN_SEG - 1) / SCAN_SEG;
+            hipLaunchKernelGGL(rs_scan_sums_kernel, dim3(segs), dim3(256), 0, s, dw.hist, dw.sums, m);
+            if (!launch_ok()) return CP_ERR_LAUNCH;
+            hipLaunchKernelGGL(rs_scan_apply_kernel, dim3(segs), dim3(256), 0, s, dw.hist, dw.sums, m);
+            if (!launch_ok()) return CP_ERR_LAUNCH;
+            hipLaunchKernelGGL(rs_scatter_kernel, dim3(ntiles), dim3(64), 0, s, dw.keys[src], dw.ids[src], dw.keys[src ^ 1],
+                               dw.ids[src ^ 1], dw.hist, n, 8 * pass, ntiles);
+            if (!launch_ok()) return CP_ERR_LAUNCH;
+        }
+        const DetP d{dw.keys[src], dw.ids[src], dw.rows, dw.partial, n, cells};
+        if (hipMemsetAsync(dw.rows, 0, (size_t)cells * 8, s) != hipSuccess) return CP_ERR_LAUNCH;
+        hipLaunchKernelGGL(dcn_det_rows_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, d.keys, d.rows, n, cells);
+        if (!launch_ok()) return CP_ERR_LAUNCH;
+        hipLaunchKernelGGL(dcn_det_gather_kernel, dim3((cells * (uint32_t)L + 255u) / 256u), dim3(256), 0, s, p, d, L);
+        if (!launch_ok()) return CP_ERR_LAUNCH;
+        const unsigned long_blocks = ((n + DCN_DET_CHUNK - 1) / DCN_DET_CHUNK + 3u) / 4u;
+        hipLaunchKernelGGL(dcn_det_long_kernel, dim3(long_blocks), dim3(256), 0, s, p, d);
+        if (!launch_ok()) return CP_ERR_LAUNCH;
+        hipLaunchKernelGGL(dcn_det_long_add_kernel, dim3(long_blocks), dim3(256), 0, s, p, d);
+        if (!launch_ok()) return CP_ERR_LAUNCH;
+    }
+    p.b0 = 0;
+    p.nb = P.nb;
+    const dim3 wg_grid((TC + 127) / 128, 1, P.nslab);
+    if (a.Co <= 32)
+        hipLaunchKernelGGL(wgrad_kernel<1>, wg_grid, dim3(256), 0, s, p);
+    else if (a.Co <= 64)
+        hipLaunchKernelGGL(wgrad_kernel<2>, wg_grid, dim3(256), 0, s, p);
+    else
+        hipLaunchKernelGGL(wgrad_kernel<WG_COUT>, dim3(wg_grid.x, (a.Co + 32 * WG_COUT - 1) / (32 * WG_COUT), P.nslab),
+                           dim3(256), 0, s, p);
+    if (!launch_ok()) return CP_ERR_LAUNCH;
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(1024), dim3(256), 0, s, (const float*)p.slab, a.grad_weight, P.nslab, a.Co,
+                       a.C, T);
+    if (!launch_ok()) return CP_ERR_LAUNCH;
+    rc = cp_launch_rowsum_nchw(a.grad_output, a.grad_bias, a.B, a.Co, HW, s);
+    if (rc != CP_OK) return rc;
+    return cp_launch_nhwc_to_nchw(p.gin, a.grad_input, a.B, a.C, a.H, a.W, a.C, s);
 }

@@ -1,6 +1,6 @@
 // The stand-alone operators of the C ABI (include/centerpose_hip.h): single layers on caller tensors, outside any cp_model
 // -- cp_conv2d_nhwc / cp_conv2d_backward_nhwc, cp_batchnorm_forward_nhwc / _backward_nhwc, cp_conv_transpose2d_nhwc,
-// cp_conv_transpose2d_dw_nhwc / cp_conv_transpose2d_backward_nhwc, cp_dcnv2_forward / cp_dcnv2_backward, cp_pose_heads_forward / _backward,
+// cp_conv_transpose2d_dw_nhwc / cp_conv_transpose2d_backward_nhwc, cp_dcnv2_forward / cp_dcnv2_backward / cp_dcnv2_backward_det, cp_pose_heads_forward / _backward,
 // cp_maxpool2d_forward_nhwc / _backward_nhwc, cp_conv2d_stem_backward, cp_groupnorm_forward_nhwc / _backward_nhwc,
 // cp_gru_gate_forward / _backward.
 // Each packs its PyTorch-layout weights into a caller-provided workspace on every call and then launches the same kernels as
@@ -700,6 +700,45 @@ int cp_dcnv2_backward(cp_stream_t stream, const float* input, const float* weigh
                  B, C, H, W, Co, Ho, Wo, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group};
     const int rc = cp_launch_dcn_backward((hipStream_t)stream, a, workspace);
     return rc == CP_OK ? CP_OK : fail(rc, "dcn_v2_backward: kernel launch failed");
+}
+
+// The deterministic form: cp_dcnv2_backward's refusals, and any geometry outside the fast path
+static std::string dcn_bwd_det_geometry_error(int C, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int dg) {
+    if (cp_dcn_backward_fast(C, kh, kw, sh, sw, ph, pw, dh, dw, dg)) return std::string();
+    char msg[320];
+    snprintf(msg, sizeof msg,
+             "dcn_v2_backward_det: geometry %dx%d / stride %d,%d / pad %d,%d / dilation %d,%d / deformable_group %d / C = %d is "
+             "outside the deterministic path, which covers 3x3 / stride 1 / pad 1 / dilation 1 / one group / C %% 16 == 0",
+             kh, kw, sh, sw, ph, pw, dh, dw, dg, C);
+    return msg;
+}
+
+size_t cp_dcnv2_backward_det_workspace_bytes(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw,
+                                             int dh, int dw, int deformable_group) {
+    int Ho = 0, Wo = 0;
+    if (dcn_bwd_shape_error(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group, &Ho, &Wo)) return 0;
+    if (!cp_dcn_backward_fast(C, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group)) return 0;
+    return cp_dcn_backward_det_ws_bytes(B, C, H, W, Co);
+}
+
+int cp_dcnv2_backward_det(cp_stream_t stream, const float* input, const float* weight, const float* offset, const float* mask,
+                          const float* grad_output, float* grad_input, float* grad_offset, float* grad_mask, float* grad_weight,
+                          float* grad_bias, int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw,
+                          int dh, int dw, int deformable_group, void* workspace, size_t workspace_bytes) {
+    int Ho = 0, Wo = 0;
+    if (const char* e = dcn_bwd_shape_error(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group, &Ho, &Wo))
+        return fail(CP_ERR_INVALID, e);
+    const std::string ge = dcn_bwd_det_geometry_error(C, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group);
+    if (!ge.empty()) return fail(CP_ERR_INVALID, ge);
+    if (!input || !weight || !offset || !mask || !grad_output || !grad_input || !grad_offset || !grad_mask || !grad_weight ||
+        !grad_bias || !workspace)
+        return fail(CP_ERR_INVALID, "dcn_v2_backward_det: null argument");
+    if (workspace_bytes < cp_dcn_backward_det_ws_bytes(B, C, H, W, Co))
+        return fail(CP_ERR_INVALID, "dcn_v2_backward_det: workspace too small");
+    DcnBwdArgs a{input, weight, offset, mask, grad_output, grad_input, grad_offset, grad_mask, grad_weight, grad_bias,
+                 B, C, H, W, Co, Ho, Wo, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group};
+    const int rc = cp_launch_dcn_backward_det((hipStream_t)stream, a, workspace);
+    return rc == CP_OK ? CP_OK : fail(rc, "dcn_v2_backward_det: kernel launch failed");
 }
 
 // DCNv2 forward with the reference's NCHW layouts (see header)

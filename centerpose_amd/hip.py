@@ -146,6 +146,8 @@ def lib():
          *([c_int] * 14), c_void_p, c_size_t)
     _sig(L.cp_dcnv2_backward_workspace_bytes, c_size_t, *([c_int] * 14))
     _sig(L.cp_dcnv2_backward, c_int, *([c_void_p] * 11), *([c_int] * 14), c_void_p, c_size_t)
+    _sig(L.cp_dcnv2_backward_det_workspace_bytes, c_size_t, *([c_int] * 14))
+    _sig(L.cp_dcnv2_backward_det, c_int, *([c_void_p] * 11), *([c_int] * 14), c_void_p, c_size_t)
     _sig(L.cp_pose_heads_chunk_images, c_int, c_int, c_int, c_int, c_int)
     _sig(L.cp_pose_heads_forward_workspace_bytes, c_size_t, *([c_int] * 6), ctypes.POINTER(c_int))
     _sig(L.cp_pose_heads_backward_workspace_bytes, c_size_t, *([c_int] * 6), ctypes.POINTER(c_int))
@@ -303,7 +305,8 @@ def exported_symbols():
             "cp_conv2d_stem_backward_workspace_bytes", "cp_conv2d_stem_backward", "cp_groupnorm_workspace_bytes",
             "cp_groupnorm_forward_nhwc", "cp_groupnorm_backward_nhwc", "cp_gru_gate_forward", "cp_gru_gate_backward",
             "cp_pose_targets_track_workspace_bytes", "cp_pose_targets_track", "cp_train_inputs_workspace_bytes",
-            "cp_train_inputs", "cp_pose_targets_track_det_workspace_bytes", "cp_pose_targets_track_det"]
+            "cp_train_inputs", "cp_pose_targets_track_det_workspace_bytes", "cp_pose_targets_track_det",
+            "cp_dcnv2_backward_det_workspace_bytes", "cp_dcnv2_backward_det"]
 
 
 def _check(rc, what):
@@ -395,11 +398,54 @@ def dcn_v2_forward(input, weight, bias, offset, mask, kh, kw, sh, sw, ph, pw, dh
     return out
 
 
+_deterministic = False
+_warned_nondeterministic = False
+
+
+def set_deterministic(flag):
+    """Process-wide default of ``dcn_v2_backward``'s ``deterministic`` argument (False at import): with it every gradient
+    of a training step is bitwise reproducible from run to run.  Returns the previous value."""
+    global _deterministic
+    prev, _deterministic = _deterministic, bool(flag)
+    return prev
+
+
+def deterministic():
+    return _deterministic
+
+
+def dcn_backward_is_fast(C, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group):
+    """The geometry cp_dcnv2_backward_det covers (dcn_bwd.hip: cp_dcn_backward_fast)."""
+    return (kh, kw, sh, sw, ph, pw, dh, dw, deformable_group) == (3, 3, 1, 1, 1, 1, 1, 1, 1) and C % 16 == 0
+
+
+def resolve_deterministic(requested, fast, own_flag, torch_flag, torch_warn_only, what=""):
+    """Which DCNv2 backward runs (pure: no device, no globals).  ``requested``: the call's ``deterministic`` argument (None:
+    ``own_flag or torch_flag``); ``fast``: the geometry is one the deterministic kernels cover.  Returns (use the
+    deterministic path, warn that the atomic path runs instead).  A deterministic request for any other geometry raises
+    RuntimeError, as torch does for an operator without a deterministic implementation -- unless it came from torch's flag
+    alone and torch's warn_only is set."""
+    want = (own_flag or torch_flag) if requested is None else bool(requested)
+    if not want:
+        return False, False
+    if fast:
+        return True, False
+    if requested is None and not own_flag and torch_warn_only:
+        return False, True
+    raise RuntimeError("dcn_v2_backward does not have a deterministic implementation for %s: the deterministic path covers "
+                       "3x3 / stride 1 / pad 1 / dilation 1 / deformable_group 1 / C %% 16 == 0.  Pass deterministic=False, or "
+                       "turn off hip.set_deterministic / torch.use_deterministic_algorithms." % (what or "this geometry"))
+
+
 def dcn_v2_backward(input, weight, bias, offset, mask, grad_output, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group,
-                    workspace=None):
+                    workspace=None, deterministic=None):
     """Same 15-argument signature as the reference's ``_ext.dcn_v2_backward`` (DCNv2/src/vision.cpp:6, dcn_v2.h:48-80):
     returns [grad_input, grad_offset, grad_mask, grad_weight, grad_bias], float32 on the input's device.  ``workspace`` (a
-    uint8 device tensor of at least the queried size) may be passed to skip the allocation; a smaller one is an error."""
+    uint8 device tensor of at least the queried size) may be passed to skip the allocation; a smaller one is an error.
+    ``deterministic``: True runs cp_dcnv2_backward_det (grad_input summed in a fixed order, no float atomics: all five
+    gradients bitwise reproducible; a larger workspace), False cp_dcnv2_backward, None (default) resolves at call time to
+    ``hip.deterministic() or torch.are_deterministic_algorithms_enabled()`` -- see resolve_deterministic."""
+    global _warned_nondeterministic
     L = lib()
     input, weight, bias, offset, mask, grad_output = map(_dev, (input, weight, bias, offset, mask, grad_output))
     B, C, H, W = input.shape
@@ -414,16 +460,28 @@ def dcn_v2_backward(input, weight, bias, offset, mask, grad_output, kh, kw, sh, 
                            ("grad_output", grad_output, (B, Co, Ho, Wo))):
         if tuple(t.shape) != shape:
             raise RuntimeError("dcn_v2_backward: %s has shape %s, expected %s" % (name, tuple(t.shape), shape))
+    geo = (kh, kw, sh, sw, ph, pw, dh, dw, deformable_group)
+    det, warn = resolve_deterministic(
+        deterministic, dcn_backward_is_fast(C, *geo), _deterministic, torch.are_deterministic_algorithms_enabled(),
+        torch.is_deterministic_algorithms_warn_only_enabled(),
+        "kernel %dx%d, stride (%d, %d), padding (%d, %d), dilation (%d, %d), deformable_group %d, C = %d" % (*geo, C))
+    if warn and not _warned_nondeterministic:
+        import warnings
+
+        _warned_nondeterministic = True
+        warnings.warn("dcn_v2_backward has no deterministic implementation for this geometry; running the float-atomic path "
+                      "(torch.use_deterministic_algorithms(True, warn_only=True))")
+    query, call = ((L.cp_dcnv2_backward_det_workspace_bytes, L.cp_dcnv2_backward_det) if det else
+                   (L.cp_dcnv2_backward_workspace_bytes, L.cp_dcnv2_backward))
     grads = [torch.empty_like(t) for t in (input, offset, mask, weight, bias)]
-    nbytes = L.cp_dcnv2_backward_workspace_bytes(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group)
+    nbytes = query(B, C, H, W, Co, *geo)
     if nbytes == 0:
         raise RuntimeError("dcn_v2_backward: shape refused by the library")
     if workspace is None:
         workspace = torch.empty(nbytes, dtype=torch.uint8, device=input.device)
-    rc = L.cp_dcnv2_backward(_stream(), _ptr(input), _ptr(weight), _ptr(offset), _ptr(mask), _ptr(grad_output),
-                             *[_ptr(g) for g in grads], B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group,
-                             _ptr(workspace), workspace.numel() * workspace.element_size())
-    _check(rc, "cp_dcnv2_backward")
+    rc = call(_stream(), _ptr(input), _ptr(weight), _ptr(offset), _ptr(mask), _ptr(grad_output),
+              *[_ptr(g) for g in grads], B, C, H, W, Co, *geo, _ptr(workspace), workspace.numel() * workspace.element_size())
+    _check(rc, "cp_dcnv2_backward_det" if det else "cp_dcnv2_backward")
     return grads
 
 

@@ -110,6 +110,33 @@ int cp_dcnv2_backward(cp_stream_t stream, const float* input, const float* weigh
                       void* workspace, size_t workspace_bytes);
 
 /* ------------------------------------------------------------------------------------------
+ * DCNv2 backward, deterministic — the same five gradients as cp_dcnv2_backward with the same arguments and
+ * semantics, every one of them bitwise reproducible run to run: grad_input is summed without any float atomic.
+ * Covers the fast geometry only: 3x3 / stride 1 / pad 1 / dilation 1 / deformable_group 1 / C % 16 == 0.  Any other
+ * geometry is refused before any launch (the query returns 0, the call CP_ERR_INVALID with the geometry in
+ * cp_last_error), as are the shapes, NULL pointers and short workspaces cp_dcnv2_backward refuses.
+ * The summation order of grad_input is contract:
+ *   - for destination cell (b, y, x) and channel c the contributions  w_q * (grad_col * mask)  are added in ascending
+ *     order of the entry id ((pix * 9 + tap) * 4 + q), pix = ho * Wo + wo the output pixel, q the bilinear corner
+ *     (0: (y0, x0), 1: (y0, x0 + 1), 2: (y0 + 1, x0), 3: (y0 + 1, x0 + 1));
+ *   - corners outside the image and samples outside (-1, H) x (-1, W) contribute nothing;
+ *   - a list of more than 512 entries is cut, in list order, into consecutive chunks of 512; each chunk is summed
+ *     serially from zero and the partial sums are added in chunk order.  A list of at most 512 entries is one serial sum.
+ * The result for one image is therefore a function of that image's tensors alone: not of its position in the batch, of
+ * the batch size, of how the call chunks the batch, or of the grid.  grad_offset / grad_mask sum the channels in
+ * ascending order in one lane, grad_weight / grad_bias as in cp_dcnv2_backward.
+ * The workspace is larger than cp_dcnv2_backward's (a sorted index of 16 bytes per (pixel, tap, corner) of a chunk of
+ * images); nothing is read back to the host, the call is stream-ordered and can be captured in a graph.
+ * ------------------------------------------------------------------------------------------ */
+size_t cp_dcnv2_backward_det_workspace_bytes(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph,
+                                             int pw, int dh, int dw, int deformable_group);
+int cp_dcnv2_backward_det(cp_stream_t stream, const float* input, const float* weight, const float* offset,
+                          const float* mask, const float* grad_output, float* grad_input, float* grad_offset,
+                          float* grad_mask, float* grad_weight, float* grad_bias, int B, int C, int H, int W, int Co,
+                          int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int deformable_group,
+                          void* workspace, size_t workspace_bytes);
+
+/* ------------------------------------------------------------------------------------------
  * Prediction-head block, forward and backward — replaces the per-head loop
  *   `for head in self.heads: z[head] = self.__getattr__(head)(y[-1])` and its autograd graph
  *   (models/networks/pose_dla_dcn.py:491-521 builds the Sequentials, :537-539 runs them; resnet_dcn.py likewise):

@@ -1,6 +1,6 @@
 """DCNv2 backward (cp_dcnv2_backward) per fast-path layer shape, next to the forward of the same shape (GPU).
 
-    python tools/dcn_backward_bench.py [--batches 16 64] [--iters 10] [--std 1.0]
+    python tools/dcn_backward_bench.py [--batches 16 64] [--iters 10] [--std 1.0] [--layers TEXT] [--deterministic]
 
 One JSON line per (shape, batch): ms per call of cp_dcnv2_backward and of cp_dcnv2_forward (HIP events around `iters`
 back-to-back calls with pre-allocated outputs and workspace), the backward's TFLOP/s against the f32 matrix peak
@@ -9,6 +9,9 @@ global float-atomic bytes against the chip-wide atomic rate (1.3 TB/s).  The ato
 actual offsets: the halo kernel's flush (at most one add per in-image halo cell and channel per 16 x 4 patch) plus every
 corner add that falls outside its patch's halo.  Per-kernel times: run it under
 `rocprofv3 --kernel-trace --stats -- python tools/dcn_backward_bench.py --batches 16 --iters 3`.
+--deterministic also times cp_dcnv2_backward_det on the same tensors: the two calls alternate in three rounds of `iters`
+calls each and the median round is reported for both (bwd_ms, bwd_det_ms), with the deterministic call's workspace and the
+bytes of its sorted index (16 per (pixel, tap, corner) of a grad_col chunk).
 """
 import argparse
 import ctypes
@@ -66,6 +69,8 @@ def main():
     ap.add_argument("--batches", type=int, nargs="+", default=[16, 64])
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--std", type=float, default=1.0)
+    ap.add_argument("--layers", default="", help="only the layer shapes whose name contains this text")
+    ap.add_argument("--deterministic", action="store_true", help="also time cp_dcnv2_backward_det, alternating with the default")
     a = ap.parse_args()
     L = hip.lib()
     dev = torch.device("cuda:0")
@@ -73,6 +78,8 @@ def main():
     P = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
     for B in a.batches:
         for name, C, Co, H in SHAPES:
+            if a.layers not in name:
+                continue
             W = H
             g = torch.Generator(device=dev).manual_seed(0)
             x = torch.randn(B, C, H, W, device=dev, generator=g)
@@ -95,8 +102,18 @@ def main():
             def bwd():
                 return L.cp_dcnv2_backward(s, P(x), P(w), P(off), P(mask), P(go), *[P(t) for t in grads], *geo, P(wsb), nb)
 
-            res = {}
-            for key, fn in (("fwd", fwd), ("bwd", bwd)):
+            order = [("fwd", fwd), ("bwd", bwd)]
+            if a.deterministic:
+                nd = L.cp_dcnv2_backward_det_workspace_bytes(*geo)
+                wsd = torch.empty(nd, dtype=torch.uint8, device=dev)
+
+                def det():
+                    return L.cp_dcnv2_backward_det(s, P(x), P(w), P(off), P(mask), P(go), *[P(t) for t in grads], *geo, P(wsd),
+                                                   nd)
+
+                order = [("fwd", fwd)] + [("bwd", bwd), ("bwd_det", det)] * 3
+            rounds = {}
+            for key, fn in order:
                 assert fn() == 0, L.cp_last_error()
                 torch.cuda.synchronize()
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -105,7 +122,8 @@ def main():
                     fn()
                 e1.record()
                 torch.cuda.synchronize()
-                res[key] = e0.elapsed_time(e1) / a.iters
+                rounds.setdefault(key, []).append(e0.elapsed_time(e1) / a.iters)
+            res = {k: sorted(v)[len(v) // 2] for k, v in rounds.items()}
             px = B * H * W
             flops = 4.0 * px * 9 * C * Co
             # HBM model: inputs and outputs once; NHWC input stage written + read, grad_output transposed written + read,
@@ -114,13 +132,20 @@ def main():
                 2 * px * C + 2 * px * Co + 2 * px * 9 * C + 2 * px * C)
             atom = atomic_bytes(off, B, C, H, W)
             ms = res["bwd"]
+            extra = {}
+            if a.deterministic:
+                chunk = min(B, max(1, (256 << 20) // (9 * C * H * W * 4)))  # dcn_bwd.hip: plan
+                extra = {"bwd_det_ms": round(res["bwd_det"], 4), "det_over_default": round(res["bwd_det"] / ms, 2),
+                         "det_workspace_mb": round(nd / 2 ** 20, 1), "index_entries_m": round(chunk * H * W * 36 / 1e6, 2),
+                         "index_mb": round(16 * chunk * H * W * 36 / 2 ** 20, 1), "chunks": -(-B // chunk)}
+                del wsd
             print(json.dumps({
                 "layer": name, "B": B, "offset_std": a.std, "bwd_ms": round(ms, 4), "fwd_ms": round(res["fwd"], 4),
                 "bwd_over_fwd": round(ms / res["fwd"], 2), "tflops": round(flops / ms / 1e9, 2),
                 "frac_f32_peak": round(flops / ms / 1e9 / PEAK_TF, 3), "hbm_model_gb": round(hbm / 1e9, 3),
                 "frac_hbm_peak": round(hbm / ms / 1e6 / HBM_GBPS, 3), "atomic_gb": round(atom / 1e9, 3),
                 "atomic_floor_ms": round(atom / ATOMIC_GBPS / 1e6, 4),
-                "naive_atomic_gb": round(4.0 * px * 9 * 4 * C / 1e9, 3), "workspace_mb": round(nb / 2 ** 20, 1)}),
+                "naive_atomic_gb": round(4.0 * px * 9 * 4 * C / 1e9, 3), "workspace_mb": round(nb / 2 ** 20, 1), **extra}),
                 flush=True)
             del x, w, b, off, mask, go, y, grads, wsf, wsb
             torch.cuda.empty_cache()

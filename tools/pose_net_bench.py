@@ -1,12 +1,15 @@
 """Training the whole dla_34 network on the library: one step of centerpose_amd.pose_net.PoseNet, and the two layer families it
 added (the image stems, the max-pools) next to their baselines, in one process (GPU).
 
-    python tools/pose_net_bench.py [--batch 16] [--size 512] [--iters 3] [--rounds 3] [--skip-step] [--out profiles/pose_net_bench.txt]
+    python tools/pose_net_bench.py [--batch 16] [--size 512] [--iters 3] [--rounds 3] [--skip-step] [--only-step] [--deterministic]
+                                   [--out profiles/pose_net_bench.txt]
 
 1. ``step``: forward + backward of PoseNet (random linear loss on the head maps) at ``size`` x ``size``, with the time split per
    layer family: every ``centerpose_amd.hip`` operator call of the step is bracketed by HIP events (stem / conv / bn / pool /
    dcn / up / heads, forward and backward apart); what is left of the step's wall time is torch glue (cat, sigmoid, the offset
-   split, layout copies, the loss).
+   split, layout copies, the loss).  ``--deterministic`` times the step under ``hip.set_deterministic(True)`` as well (the
+   DCNv2 input gradient summed in a fixed order: every gradient of the step bitwise reproducible), the two modes alternating
+   round by round; the family split is then the deterministic step's.
 2. ``stem``: forward + backward of the 3 -> 16 (base_layer, pre_img_layer) and 1 -> 16 (pre_hm_layer) stems, three routes:
    ``library`` (stem.stem_conv2d: 4-channel forward + cp_conv2d_stem_backward), ``torch`` (F.conv2d on the planes, weight gradient
    through torch autograd) and ``padded`` (the only route before this operator: conv.conv2d on the image padded to 4 planes,
@@ -50,6 +53,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--head-conv", type=int, default=256)
     ap.add_argument("--skip-step", action="store_true", help="only the stem and pool measurements")
+    ap.add_argument("--only-step", action="store_true", help="only the whole step")
+    ap.add_argument("--deterministic", action="store_true", help="time the step under hip.set_deterministic(True) as well")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -85,7 +90,7 @@ def main():
         return {s: (statistics.median(v), v) for s, v in res.items()}
 
     # ---- 2. the stems ----
-    for name, cin in (("base_layer / pre_img_layer", 3), ("pre_hm_layer", 1)):
+    for name, cin in () if a.only_step else (("base_layer / pre_img_layer", 3), ("pre_hm_layer", 1)):
         g = torch.Generator(device=dev).manual_seed(1)
         x = torch.randn(B, cin, S, S, device=dev, generator=g)
         w = (torch.randn(16, cin, 7, 7, device=dev, generator=g) / (49 * cin) ** 0.5).requires_grad_(True)
@@ -120,7 +125,8 @@ def main():
         torch.cuda.empty_cache()
 
     # ---- 3. the max-pools ----
-    for name, C, R in (("level2", 32, S // 2), ("level3", 64, S // 4), ("level4", 128, S // 8), ("level5", 256, S // 16)):
+    for name, C, R in () if a.only_step else (("level2", 32, S // 2), ("level3", 64, S // 4), ("level4", 128, S // 8),
+                                              ("level5", 256, S // 16)):
         g = torch.Generator(device=dev).manual_seed(2)
         x = torch.relu(torch.randn(B, C, R, R, device=dev, generator=g)).contiguous(memory_format=torch.channels_last).requires_grad_(True)
         go = torch.randn(B, C, R // 2, R // 2, device=dev, generator=g).contiguous(memory_format=torch.channels_last)
@@ -157,9 +163,23 @@ def main():
             z = net(x)[0]
             sum((z[h] * lin[h]).sum() for h in z).backward()
 
-        step()
-        step()
-        total = [timed(step) for _ in range(a.rounds)]
+        modes = [False, True] if a.deterministic else [False]
+        for m in modes:
+            hip.set_deterministic(m)
+            step()
+            step()
+        rounds = {m: [] for m in modes}
+        for _ in range(a.rounds):
+            for m in modes:
+                hip.set_deterministic(m)
+                rounds[m].append(timed(step))
+        total = rounds[False]
+        det = {}
+        if a.deterministic:  # the traced step below stays in the deterministic mode
+            det = {"deterministic_step_ms": round(statistics.median(rounds[True]), 2),
+                   "deterministic_step_ms_rounds": [round(v, 2) for v in rounds[True]],
+                   "deterministic_over_default": round(statistics.median(rounds[True]) / statistics.median(total), 3),
+                   "family_split_of": "deterministic step"}
         # one more step with every operator call bracketed by events
         events, originals = [], {}
 
@@ -198,7 +218,8 @@ def main():
         emit({"what": "step", "arch": "dla_34", "B": B, "HxW": S, "head_conv": a.head_conv, "step_ms": round(statistics.median(total), 2),
               "step_ms_rounds": [round(v, 2) for v in total], "images_per_s": round(B / statistics.median(total) * 1e3, 1),
               "traced_step_ms": round(traced, 2), "family_ms": {k: round(v, 2) for k, v in split.items()}, "family_calls": calls,
-              "peak_memory_gib": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)})
+              "peak_memory_gib": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2), **det})
+        hip.set_deterministic(False)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
