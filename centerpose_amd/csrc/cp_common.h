@@ -663,3 +663,5 @@ size_t cp_track_state_bytes_impl(int B, int cap);
 size_t cp_track_ws_bytes_impl(int B, int K, int cap);
 int cp_launch_track_step(hipStream_t s, const TrackParams& P, const double* vmeta, const double* post, const int* count,
                          const double* det_pnp, int B, int K, void* state, double* recs, void* ws);
+int cp_launch_track_seed(hipStream_t s, const TrackParams& P, const double* vmeta, const double* seeds, const int* seed_count,
+                         const int* gt_render, int B, int S, void* state, double* recs);

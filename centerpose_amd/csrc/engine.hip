@@ -526,6 +526,23 @@ int cp_track_step(cp_stream_t stream, const cp_track_params* params, const doubl
     return rc == CP_OK ? CP_OK : fail(rc, "cp_track_step: launch failed");
 }
 
+static_assert(CP_SEED_STRIDE == SD_PRESENT + 1 && SD_POST + (TR_LOC - TR_POST) == SD_PNP &&
+                  SD_PNP + (TR_KF_X - TR_KPS_PNP) == SD_KPS_GT && SD_KPS_GT + 18 == SD_PRESENT,
+              "the seed record of include/centerpose_hip.h is the one track_common.h reads");
+
+int cp_track_seed(cp_stream_t stream, const cp_track_params* params, const double* vmeta, const double* seeds,
+                  const int* seed_count, const int* gt_render, int B, int S, void* state, double* render_recs) {
+    if (!params || !vmeta || !seeds || !seed_count || !state || !render_recs)
+        return fail(CP_ERR_INVALID, "cp_track_seed: null argument");
+    if (B < 1) return fail(CP_ERR_INVALID, "cp_track_seed: B must be >= 1");
+    if (S < 1 || S > CP_TRACK_CAP) return fail(CP_ERR_INVALID, "cp_track_seed: S must be in [1, CP_TRACK_CAP]");
+    TrackParams P;
+    std::memcpy(&P, params, sizeof(P));
+    if (P.cap < 1 || P.cap > CP_TRACK_CAP) return fail(CP_ERR_INVALID, "cp_track_seed: cap must be in [1, CP_TRACK_CAP]");
+    const int rc = cp_launch_track_seed((hipStream_t)stream, P, vmeta, seeds, seed_count, gt_render, B, S, state, render_recs);
+    return rc == CP_OK ? CP_OK : fail(rc, "cp_track_seed: launch failed");
+}
+
 int cp_box_iou(cp_stream_t stream, const double* a, const double* b, int n, double* iou) {
     if (n < 1) return fail(CP_ERR_INVALID, "cp_box_iou: n must be >= 1");
     if (!a || !b || !iou) return fail(CP_ERR_INVALID, "cp_box_iou: null argument");

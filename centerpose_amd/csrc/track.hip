@@ -3,7 +3,9 @@
 // (/root/reference/src/lib/detectors/base_detector.py:501-544 Gaussian fusion, :547-654 boxes, :660-665 `tracker.step`,
 // :150-388 which Gaussians are drawn; utils/tracker.py:112-302 `Tracker.step`; utils/pnp/cuboid_pnp_shell.py:26-91).
 // The arithmetic lives in track_common.h (scalar functions, also compiled for the host by the logic tests); this file
-// is the data movement: five launches per frame, no host synchronisation.
+// is the data movement: five launches per frame, no host synchronisation.  Between two frames, track_seed_kernel (one
+// launch) replaces the lists of chosen videos by tracks made from annotations (`Tracker.init_track` with meta['pre_dets'])
+// and writes their ground-truth Gaussian records.
 //
 //   1  track_prepare_kernel    one lane per (video, detection slot): candidate record = post-processed fields, fusion,
 //                              packaged detection PnP answer, "has a box" flag
@@ -149,9 +151,57 @@ __global__ __launch_bounds__(64) void track_flip_kernel(int B, void* state) {
     if (b == 0) hdr[0] ^= 1;
 }
 
+// Seeding between two frames (Tracker.init_track with meta['pre_dets']): one wavefront per video.  A video whose seed_count is
+// negative is left alone -- nothing of its list, header or records is read or written.  Otherwise lane 0 walks the
+// acceptance rule, then the lanes build the tracks of the new list (one lane per entry, into the CURRENT half of the state:
+// no frame is in flight) and all `cap` rows of the video's Gaussian records.
+__global__ __launch_bounds__(64) void track_seed_kernel(const TrackParams P, const double* __restrict__ vmeta,
+                                                        const double* __restrict__ seeds,
+                                                        const int* __restrict__ seed_count,
+                                                        const int* __restrict__ gt_render, int B, int S, void* state,
+                                                        double* __restrict__ recs) {
+    __shared__ int accepted[128];  // cap <= CP_TRACK_CAP = 128
+    __shared__ int s_n;
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (b >= B) return;
+    const int ns_raw = seed_count[b];
+    if (ns_raw < 0) return;  // (uniform over the block: nobody waits at the barrier below)
+    const int ns = ns_raw < S ? ns_raw : S;
+    StateView V = view(state, B);
+    int* h = V.hdr + 4 + 4 * b;
+    const double* sd = seeds + (size_t)b * S * CP_SEED_STRIDE;
+    if (lane == 0) {
+        int idc = 0, dropped = 0;
+        const int n = trk_seed_walk(P, sd, ns, accepted, &idc, &dropped);
+        h[0] = n;
+        h[1] = idc;
+        h[2] += dropped;
+        s_n = n;
+    }
+    __syncthreads();
+    const int n = s_n;
+    const int gt = gt_render ? gt_render[b] != 0 : 0;
+    double* list = V.tracks + ((size_t)V.hdr[0] * B + b) * P.cap * CP_TRACK_STRIDE;
+    const double* vm = vmeta + (size_t)b * CP_VMETA_STRIDE;
+    for (int e = lane; e < P.cap; e += 64) {
+        double* rec = recs + ((size_t)b * P.cap + e) * 45;
+        if (e < n)
+            trk_seed_stage(P, vm, sd + (size_t)accepted[e] * CP_SEED_STRIDE, e + 1, gt, b, B + 8 * b,
+                           list + (size_t)e * CP_TRACK_STRIDE, rec);
+        else
+            for (int i = 0; i < 9; ++i) rec[5 * i] = -1.0;
+    }
+}
+
 inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
 
 }  // namespace
+
+int cp_launch_track_seed(hipStream_t s, const TrackParams& P, const double* vmeta, const double* seeds, const int* seed_count,
+                         const int* gt_render, int B, int S, void* state, double* recs) {
+    hipLaunchKernelGGL(track_seed_kernel, dim3(B), dim3(64), 0, s, P, vmeta, seeds, seed_count, gt_render, B, S, state, recs);
+    return hipGetLastError() == hipSuccess ? CP_OK : CP_ERR_LAUNCH;
+}
 
 size_t cp_track_state_bytes_impl(int B, int cap) {
     return state_hdr_bytes(B) + (size_t)2 * B * cap * CP_TRACK_STRIDE * sizeof(double);

@@ -708,20 +708,18 @@ CP_HD double trk_gaussian_radius(double h, double w) {  // utils/image.py:103-12
 // is outside the image, a spread that is no int32 is "missing", and a record whose k is not finite is withdrawn -- every
 // record that leaves here is either channel -1 or finite with 0 <= x < inp_w, 0 <= y < inp_h, 0 <= radius.  The
 // comparisons are written so that finite input gives the bits it always gave.
-CP_HD void trk_render_records(const TrackParams& P, const double* vm, const double* t, int hm_plane, int hp_plane0,
-                              double* rec) {
-    for (int i = 0; i < 9; ++i) rec[5 * i] = -1.0;
-    const double score = t[TR_POST + PO_SCORE];
-    if (!(score >= P.pre_thresh)) return;
+// What both branches of `_get_additional_inputs` do with a track's box (:170-179, :216-226): _trans_bbox (float32 box, both
+// corners through trans_input, clipped to the input), the Gaussian radius of the clipped box and its integer centre.
+// Returns 0 when the clipped box is degenerate (`h > 0 and w > 0` fails; a NaN corner fails it as well): nothing is drawn.
+CP_HD int trk_render_box(const double* vm, const double* bbox, int* radius, int* ctx, int* cty) {
     const double* T = vm + VM_TIN;
-    const double iw = vm[VM_INP_W], ih = vm[VM_INP_H], W0 = vm[VM_WIDTH], H0 = vm[VM_HEIGHT];
-    // _trans_bbox: float32 box, both corners through trans_input, clipped to the input
+    const double iw = vm[VM_INP_W], ih = vm[VM_INP_H];
     float bx[4];
     {
         double ox, oy;
-        trk_affine(T, (double)f32(t[TR_POST + PO_BBOX]), (double)f32(t[TR_POST + PO_BBOX + 1]), &ox, &oy);
+        trk_affine(T, (double)f32(bbox[0]), (double)f32(bbox[1]), &ox, &oy);
         bx[0] = f32(ox); bx[1] = f32(oy);
-        trk_affine(T, (double)f32(t[TR_POST + PO_BBOX + 2]), (double)f32(t[TR_POST + PO_BBOX + 3]), &ox, &oy);
+        trk_affine(T, (double)f32(bbox[2]), (double)f32(bbox[3]), &ox, &oy);
         bx[2] = f32(ox); bx[3] = f32(oy);
         const float xm = (float)(iw - 1), ym = (float)(ih - 1);
         bx[0] = bx[0] < 0.f ? 0.f : (bx[0] > xm ? xm : bx[0]);
@@ -730,10 +728,23 @@ CP_HD void trk_render_records(const TrackParams& P, const double* vm, const doub
         bx[3] = bx[3] < 0.f ? 0.f : (bx[3] > ym ? ym : bx[3]);
     }
     const float h = bx[3] - bx[1], w = bx[2] - bx[0];
-    if (!(h > 0.f && w > 0.f)) return;
+    if (!(h > 0.f && w > 0.f)) return 0;
     const double rr = trk_gaussian_radius(ceil((double)h), ceil((double)w));
-    const int radius = (int)rr > 0 ? (int)rr : 0;
-    const int ctx = (int)((bx[0] + bx[2]) / 2.f), cty = (int)((bx[1] + bx[3]) / 2.f);
+    *radius = (int)rr > 0 ? (int)rr : 0;
+    *ctx = (int)((bx[0] + bx[2]) / 2.f);
+    *cty = (int)((bx[1] + bx[3]) / 2.f);
+    return 1;
+}
+
+CP_HD void trk_render_records(const TrackParams& P, const double* vm, const double* t, int hm_plane, int hp_plane0,
+                              double* rec) {
+    for (int i = 0; i < 9; ++i) rec[5 * i] = -1.0;
+    const double score = t[TR_POST + PO_SCORE];
+    if (!(score >= P.pre_thresh)) return;
+    const double* T = vm + VM_TIN;
+    const double iw = vm[VM_INP_W], ih = vm[VM_INP_H], W0 = vm[VM_WIDTH], H0 = vm[VM_HEIGHT];
+    int radius, ctx, cty;
+    if (!trk_render_box(vm, t + TR_POST + PO_BBOX, &radius, &ctx, &cty)) return;
     if (P.pre_hm && (P.render_hm_mode == 0 || P.render_hm_mode == 1)) {
         const double k = P.render_hm_mode == 1 ? score : 1.0;
         if (fabs(k) < __builtin_huge_val()) {  // (a score of +inf passes pre_thresh and cannot be drawn)
@@ -1062,6 +1073,103 @@ CP_HD void trk_finish_stage(const TrackParams& P, const double* vm, double* t, c
     }
     t[TR_FLAGS] = flags;
     if (rec) trk_render_records(P, vm, t, hm_plane, hp_plane0, rec);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Seeding from annotations: `Tracker.init_track(meta)` with meta['pre_dets'] (utils/tracker.py:21-49,
+// tracker_baseline.py:21-49) and the ground-truth branch of `_get_additional_inputs` (base_detector.py:167-209).
+//
+// ---- one seed (the dict of tools/objectron_eval/eval_video_official.py:430-449): CP_SEED_STRIDE doubles ----
+#define SD_POST 0        // [152] the track record's [TR_POST, TR_LOC): post-processed fields, kps_fusion_mean, kps_fusion_std
+#define SD_PNP 152       // [63]  the track record's [TR_KPS_PNP, TR_KF_X): kps_pnp [18], kps_3d_cam [27], kps_ori [18]
+#define SD_KPS_GT 215    // [18]  kps_gt (centre first, normalised)
+#define SD_PRESENT 233   // bit 0: ct given (else the bbox centre); 1: kps_gt given; 2: kps_pnp / kps_3d_cam given; 3: kps_ori given
+#define CP_SEED_STRIDE 234
+
+// One accepted seed becomes track `t` with tracking id `id` (init_track :32-49): the fields a seed carries, age 1, active 1,
+// and what trk_advance does for a new track -- init_kf of the configured tracker class, a scale pool of one sample.  No
+// read-out: kps_mean_kf and the other *_kf fields stay zero until the track's first frame.
+CP_HD void trk_seed_track(const TrackParams& P, const double* seed, int id, double* t) {
+    for (int e = 0; e < CP_TRACK_STRIDE; ++e) t[e] = 0.0;
+    for (int e = 0; e < TR_LOC - TR_POST; ++e) t[TR_POST + e] = seed[SD_POST + e];
+    const int present = (int)seed[SD_PRESENT];
+    if (present & 4)
+        for (int e = 0; e < 18 + 27; ++e) t[TR_KPS_PNP + e] = seed[SD_PNP + e];
+    if (present & 8)
+        for (int e = 0; e < 18; ++e) t[TR_KPS_ORI + e] = seed[SD_PNP + 18 + 27 + e];
+    if (!(present & 1)) {
+        const double* b = t + TR_POST + PO_BBOX;
+        t[TR_POST + PO_CT] = (b[0] + b[2]) / 2;
+        t[TR_POST + PO_CT + 1] = (b[1] + b[3]) / 2;
+    }
+    t[TR_ID] = id;
+    t[TR_AGE] = 1;
+    t[TR_ACTIVE] = 1;
+    t[TR_SRC] = -1;
+    if (P.kalman) trk_kf_init(P, t);
+    if (P.scale_pool) trk_pool_add(P, t);  // (the pool was zeroed with the record)
+    t[TR_FLAGS] = ((present & 4) ? 1 : 0) | ((present & 8) ? 8 : 0) | 16;
+}
+
+// The acceptance walk of one video (init_track :31-49): seeds in order, one becomes a track iff score > new_thresh (so a
+// NaN score does not); the id counter restarts at 0 (`reset()`).  accepted [cap]: seed index of list entry e, whose id is
+// e + 1.  Returns the length of the list.  Beyond P.cap the first P.cap accepted seeds are kept, the others are counted into
+// *dropped and no id is spent on them (trk_associate's rule).
+CP_HD int trk_seed_walk(const TrackParams& P, const double* seeds, int ns, int* accepted, int* id_count, int* dropped) {
+    *dropped = 0;
+    *id_count = 0;
+    int n = 0;
+    for (int i = 0; i < ns; ++i) {
+        if (!(seeds[(long long)i * CP_SEED_STRIDE + SD_POST + PO_SCORE] > P.new_thresh)) continue;
+        if (n >= P.cap) { *dropped += 1; continue; }
+        accepted[n++] = i;
+        *id_count += 1;
+    }
+    return n;
+}
+
+// The ground-truth counterpart of trk_render_records (base_detector.py:167-209): the Gaussians drawn for one seeded track
+// from its `bbox` and `kps_gt`.  No pre_thresh test; centre and vertices with k = 1 and the centre's radius; the vertices are
+// kps_gt[1:] scaled by the frame size, truncated into the int64 visibility table, moved by trans_input, truncated again and
+// cast to int32 -- WITHOUT a visibility or bounds test, so a blob may be centred outside the input (the renderer clips).
+// The non-finite contract of trk_render_records, extended: a coordinate that is not finite or does not fit the integer it
+// is converted to (int64 for the table, int32 for the record) withdraws that record; finite input gives the reference's bits.
+CP_HD void trk_render_records_gt(const TrackParams& P, const double* vm, const double* seed, int hm_plane, int hp_plane0,
+                                 double* rec) {
+    for (int i = 0; i < 9; ++i) rec[5 * i] = -1.0;
+    int radius, ctx, cty;
+    if (!trk_render_box(vm, seed + SD_POST + PO_BBOX, &radius, &ctx, &cty)) return;
+    if (P.pre_hm) { rec[0] = hm_plane; rec[1] = ctx; rec[2] = cty; rec[3] = radius; rec[4] = 1.0; }
+    if (!P.pre_hm_hp || !((int)seed[SD_PRESENT] & 2)) return;
+    const double* T = vm + VM_TIN;
+    const double W0 = vm[VM_WIDTH], H0 = vm[VM_HEIGHT];
+    const double I64 = 9223372036854775808.0;  // 2^63
+    for (int j = 0; j < 8; ++j) {
+        const double qx = seed[SD_KPS_GT + 2 * (j + 1)] * W0, qy = seed[SD_KPS_GT + 2 * (j + 1) + 1] * H0;
+        if (!(fabs(qx) < I64) || !(fabs(qy) < I64)) continue;
+        long long px = (long long)qx, py = (long long)qy;
+        double ox, oy;
+        trk_affine(T, (double)px, (double)py, &ox, &oy);
+        if (!(fabs(ox) < I64) || !(fabs(oy) < I64)) continue;
+        px = (long long)ox;
+        py = (long long)oy;
+        if (px < -2147483648LL || px > 2147483647LL || py < -2147483648LL || py > 2147483647LL) continue;
+        double* r = rec + 5 * (1 + j);
+        r[0] = hp_plane0 + j; r[1] = (double)px; r[2] = (double)py; r[3] = radius; r[4] = 1.0;
+    }
+}
+
+// Track e of a freshly seeded list and its row of next frame's Gaussian records: the ground-truth ones where `gt`, else
+// what the tracks themselves give (trk_render_records).  A seeded track has no filter read-out yet, so where that branch
+// would re-draw kps_pnp_kf / kps_mean_kf (the reference raises a KeyError there) the vertex records are withdrawn.
+CP_HD void trk_seed_stage(const TrackParams& P, const double* vm, const double* seed, int id, int gt, int hm_plane,
+                          int hp_plane0, double* t, double* rec) {
+    trk_seed_track(P, seed, id, t);
+    if (!rec) return;
+    if (gt) { trk_render_records_gt(P, vm, seed, hm_plane, hp_plane0, rec); return; }
+    trk_render_records(P, vm, t, hm_plane, hp_plane0, rec);
+    if (P.use_pnp && (P.render_hmhp_mode == 2 || P.render_hmhp_mode == 3) && (P.kalman || P.scale_pool))
+        for (int j = 1; j < 9; ++j) rec[5 * j] = -1.0;
 }
 
 #if defined(__clang__) && defined(__HIPCC__)

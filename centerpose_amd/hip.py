@@ -243,6 +243,8 @@ def lib():
     _sig(L.cp_track_status, c_int, c_void_p, c_void_p, c_int, ctypes.POINTER(c_int))
     _sig(L.cp_track_step, c_int, c_void_p, ctypes.POINTER(TrackParams), c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
          c_void_p, c_void_p, c_size_t)
+    _sig(L.cp_track_seed, c_int, c_void_p, ctypes.POINTER(TrackParams), c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+         c_void_p, c_void_p)
     _sig(L.cp_linear_assignment, c_int, c_void_p, c_int, c_int, c_int, ctypes.POINTER(c_int))
     _sig(L.cp_box_iou, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p)
     _sig(L.cp_box_eval, c_int, c_void_p, *([c_void_p] * 6), c_int, c_int, c_void_p)
@@ -289,7 +291,7 @@ def exported_symbols():
             "cp_kernel_variant_name", "cp_set_default_precision", "cp_model_set_precision", "cp_model_detect_workspace_bytes", "cp_model_detect", "cp_set_debug", "cp_preprocess", "cp_preprocess_batch", "cp_postprocess_workspace_bytes", "cp_postprocess", "cp_render_gaussians",
             "cp_model_profile_roles", "cp_role_name", "cp_pnp_from_post_workspace_bytes", "cp_pnp_from_post", "cp_resize_u8",
             "cp_abi_version", "cp_num_kernel_variants", "cp_num_roles", "cp_track_state_bytes", "cp_track_workspace_bytes",
-            "cp_track_reset", "cp_track_step", "cp_track_status", "cp_linear_assignment", "cp_decode_tiled_workspace_bytes",
+            "cp_track_reset", "cp_track_step", "cp_track_status", "cp_track_seed", "cp_linear_assignment", "cp_decode_tiled_workspace_bytes",
             "cp_decode_tiled", "cp_box_iou", "cp_box_eval", "cp_conv_transpose2d_workspace_bytes",
             "cp_conv_transpose2d_nhwc", "cp_dcnv2_backward_workspace_bytes", "cp_dcnv2_backward",
             "cp_pose_loss_workspace_bytes", "cp_pose_loss_forward", "cp_pose_loss_backward",
@@ -1375,13 +1377,82 @@ TRACK_FIELDS = OrderedDict([  # field -> (offset, width) inside a device track r
     ("kps_3d_cam_kf", (473, 27)), ("kps_ori_kf", (500, 18))])
 
 
+SEED_STRIDE = 234
+SEED_PRESENT = 233  # presence bits of a seed record: 1 ct, 2 kps_gt, 4 kps_pnp / kps_3d_cam, 8 kps_ori
+SEED_FIELDS = OrderedDict(  # field -> (offset, width) inside a seed record (include/centerpose_hip.h: cp_track_seed)
+    list(POST_FIELDS.items()) + [("kps_fusion_mean", (120, 16)), ("kps_fusion_std", (136, 16)), ("kps_pnp", (152, 18)),
+                                 ("kps_3d_cam", (170, 27)), ("kps_ori", (197, 18)), ("kps_gt", (215, 18))])
+
+
+def seed_required_keys(params, gt=False):
+    """The keys of a seed dict that the configured mode reads: the host tracker would raise a KeyError on a seed without one
+    (`init_track` / `init_kf`, the association and read-out of its first frame, the branch of `_get_additional_inputs`
+    that draws it)."""
+    keys = ["score", "bbox", "cls", "kps"]
+    if params.kalman:
+        keys += ["kps_fusion_mean", "kps_fusion_std", "tracking_hp"]
+    if params.scale_pool:
+        keys += ["obj_scale", "obj_scale_uncertainty"]
+    if params.pre_hm_hp:
+        if gt:
+            keys.append("kps_gt")
+        elif params.use_pnp and params.render_hmhp_mode in (0, 1):
+            keys.append("kps_ori")
+    return keys
+
+
+def pack_seeds(pre_dets_per_video, params, gt_render=None, S=None):
+    """The reference's seed dicts (``meta['pre_dets']``, tools/objectron_eval/eval_video_official.py:430-449; 'ct' optional)
+    -> (seeds float64 [B, S, SEED_STRIDE], counts int32 [B]) for ``DeviceTracker.seed``, one numpy conversion per field.
+    ``pre_dets_per_video[b]`` is the list of video b, or None for a video that is not seeded now (count -1: left untouched);
+    an empty list resets the video.
+    ``gt_render[b]`` says whether video b's previous-frame maps are the ground-truth ones (it decides which keys are needed).
+    The dicts are only read -- the host tracker's ``init_track`` writes into them, and the evaluator hands the same dicts
+    to the next frame.  A seed that lacks a key the configured mode needs raises KeyError naming it, before anything is
+    copied."""
+    import numpy as np
+
+    B = len(pre_dets_per_video)
+    gt = [False] * B if gt_render is None else [bool(g) for g in gt_render]
+    for b, dets in enumerate(pre_dets_per_video):
+        for i, d in enumerate(dets or ()):
+            for k in seed_required_keys(params, gt[b]):
+                if k not in d:
+                    raise KeyError("pack_seeds: seed %d of video %d has no '%s'" % (i, b, k))
+    n_max = max([len(d) for d in pre_dets_per_video if d is not None] + [1])
+    S = n_max if S is None else int(S)
+    if not 1 <= S <= TRACK_CAP or n_max > S:
+        raise ValueError("pack_seeds: %d seeds in one video, S = %d (at most %d)" % (n_max, S, TRACK_CAP))
+    seeds = np.zeros((B, S, SEED_STRIDE))
+    counts = np.array([-1 if d is None else len(d) for d in pre_dets_per_video], np.int32)
+    flat = [d for dets in pre_dets_per_video for d in (dets or ())]
+    if flat:
+        vb = np.repeat(np.arange(B), np.maximum(counts, 0))
+        vi = np.concatenate([np.arange(max(n, 0)) for n in counts])
+        for k, (off, w) in SEED_FIELDS.items():   # one stacked conversion per field
+            have = [k in d for d in flat]
+            if all(have):
+                try:
+                    seeds[vb, vi, off:off + w] = np.asarray([d[k] for d in flat], np.float64).reshape(len(flat), w)
+                    continue
+                except ValueError:   # the seeds give this field in different shapes: one by one
+                    pass
+            if any(have):
+                for j, d in enumerate(flat):
+                    if have[j]:
+                        seeds[vb[j], vi[j], off:off + w] = np.asarray(d[k], np.float64).reshape(-1)
+        seeds[vb, vi, SEED_PRESENT] = [1 * ("ct" in d) + 2 * ("kps_gt" in d) + 4 * ("kps_pnp" in d and "kps_3d_cam" in d)
+                                       + 8 * ("kps_ori" in d) for d in flat]
+    return seeds, counts
+
+
 def track_params_from_opt(opt, K=100, cap=TRACK_CAP):
-    """cp_track_params for a reference ``opt`` (opts.py:242-300); raises for what only the host tracker does."""
+    """cp_track_params for a reference ``opt`` (opts.py:242-300); raises for what only the host tracker does.  The ground-truth /
+    empty previous-frame maps (--gt_pre_hm_hmhp, --gt_pre_hm_hmhp_first, --empty_pre_hm) are no fields of the struct: they
+    decide per frame and video what ``BatchedTracking`` seeds and renders (``DeviceTracker.seed``)."""
     baseline = bool(getattr(opt, "refined_Kalman", False))  # Tracker_baseline wins when both flags are set (base_detector.py:53-57)
     if not (getattr(opt, "tracking_task", False) or baseline) or not (opt.kalman or opt.scale_pool):
         raise RuntimeError("device tracker: tracking_task or refined_Kalman, with kalman and / or scale_pool (demo.py:117-129)")
-    if getattr(opt, "gt_pre_hm_hmhp", False) or getattr(opt, "gt_pre_hm_hmhp_first", False) or getattr(opt, "empty_pre_hm", False):
-        raise RuntimeError("device tracker: ground-truth / empty previous heat-maps are host-only modes")
     cat = {"camera": 0, "bottle": 0, "cup": 0, "book": 1, "chair": 1, "cereal_box": 1, "bike": 2, "laptop": 2, "shoe": 2}
     lo, hi = opt.conf_border[opt.c][0], opt.conf_border[opt.c][1]
     return TrackParams(new_thresh=opt.new_thresh, pre_thresh=opt.pre_thresh, R=opt.R, conf_lo=lo, conf_hi=hi,
@@ -1411,7 +1482,8 @@ def track_vmeta(metas):
 class DeviceTracker(object):
     """CenterPoseTrack's per-video track tables on the device (cp_track_*): ``step`` consumes the outputs of
     ``postprocess`` / ``pnp_from_post`` of a frame of B videos, ``render`` draws the next frame's pre_hm / pre_hm_hp from
-    the tracks, ``read`` copies the current lists to the host.  ``read`` synchronises; so does ``step`` once every
+    the tracks, ``read`` copies the current lists to the host, ``seed`` replaces the lists of chosen videos by tracks made from
+    annotations (and can leave their ground-truth Gaussians for the next ``render``).  ``read`` synchronises; so does ``step`` once every
     ``STATUS_EVERY`` frames, when it looks at the overflow counters (``check``) and raises if a frame needed more than ``cap``
     tracks -- AFTER the device state has advanced by that frame.  Set ``STATUS_EVERY = 0`` (class or instance attribute) for a
     loop that must never synchronise or that is being captured into a hipGraph, and poll ``dropped()`` / ``check()`` yourself."""
@@ -1433,6 +1505,7 @@ class DeviceTracker(object):
         self.recs = torch.empty(self.B, self.cap, 9, 5, dtype=torch.float64, device=device)
         self.planes = torch.empty(9 * self.B, self.inp_h, self.inp_w, dtype=torch.float32, device=device)
         self.hdr_bytes = ((4 + 4 * self.B) * 4 + 255) // 256 * 256
+        self._seed_ring, self._seed_calls, self._seed_dev = [], 0, None   # staging of seed()
         self.reset()
 
     def reset(self):
@@ -1455,6 +1528,53 @@ class DeviceTracker(object):
         self.frames += 1
         if check:
             self.check_due()
+
+    SEED_RING = 2  # pinned staging buffers of seed(): the host may run this many seed() calls ahead of the device
+
+    def seed(self, seeds, counts, gt_render=None):
+        """``Tracker.init_track`` with ``meta['pre_dets']`` for chosen videos, between two frames (cp_track_seed): ``seeds``
+        float64 [B, S, SEED_STRIDE] and ``counts`` int32 [B] as ``pack_seeds`` builds them (count < 0: that video is left
+        untouched; 0: reset to an empty list), ``gt_render`` [B] true where ``recs`` must hold the video's ground-truth
+        Gaussians (--gt_pre_hm_hmhp / --gt_pre_hm_hmhp_first) instead of the ones drawn from the tracks.  One pinned
+        host-to-device copy for all videos and one launch; no synchronisation (a staging buffer is re-used only once the
+        copy made from it ``SEED_RING`` calls ago has left the host).  Raises BEFORE the device state has moved."""
+        import numpy as np
+
+        seeds = np.ascontiguousarray(seeds, np.float64)
+        counts = np.ascontiguousarray(counts, np.int32)
+        if seeds.ndim != 3 or seeds.shape[0] != self.B or seeds.shape[2] != SEED_STRIDE or not 1 <= seeds.shape[1] <= TRACK_CAP:
+            raise RuntimeError("DeviceTracker.seed: seeds must be [B, S, %d] float64 with 1 <= S <= %d" % (SEED_STRIDE, TRACK_CAP))
+        if counts.shape != (self.B,) or int(counts.max()) > seeds.shape[1]:
+            raise RuntimeError("DeviceTracker.seed: counts must be [B] int32, none above S")
+        gt = np.zeros(self.B, np.int32) if gt_render is None else np.ascontiguousarray(np.asarray(gt_render) != 0, np.int32)
+        if gt.shape != (self.B,):
+            raise RuntimeError("DeviceTracker.seed: gt_render must hold one flag per video")
+        S = int(seeds.shape[1])
+        n_seed = seeds.size * 8
+        n_bytes = n_seed + 8 * self.B                     # seeds | counts int32 [B] | gt_render int32 [B]
+        ring = self._seed_ring
+        slot = self._seed_calls % self.SEED_RING
+        if len(ring) <= slot:
+            ring.append([None, None])
+        if ring[slot][0] is None or ring[slot][0].numel() < n_bytes:
+            ring[slot] = [torch.empty(max(n_bytes, 1 << 16), dtype=torch.uint8).pin_memory(), None]
+        host, ev = ring[slot]
+        if ev is not None:
+            ev.synchronize()   # the copy out of this buffer, SEED_RING calls ago
+        hv = host.numpy()
+        hv[:n_seed].view(np.float64)[:] = seeds.reshape(-1)
+        hv[n_seed:n_seed + 4 * self.B].view(np.int32)[:] = counts
+        hv[n_seed + 4 * self.B:n_bytes].view(np.int32)[:] = gt
+        dev = self._seed_dev
+        if dev is None or dev.numel() < n_bytes:
+            dev = self._seed_dev = torch.empty(max(n_bytes, 1 << 16), dtype=torch.uint8, device=self.device)
+        dev[:n_bytes].copy_(host[:n_bytes], non_blocking=True)
+        ring[slot][1] = torch.cuda.Event()
+        ring[slot][1].record()
+        self._seed_calls += 1
+        p = dev.data_ptr()
+        _check(lib().cp_track_seed(_stream(), ctypes.byref(self.P), _ptr(self.vmeta), p, p + n_seed, p + n_seed + 4 * self.B,
+                                   self.B, S, _ptr(self.state), _ptr(self.recs)), "cp_track_seed")
 
     def check_due(self):
         """The periodic overflow check of ``step`` (every STATUS_EVERY frames; synchronises when it runs)."""

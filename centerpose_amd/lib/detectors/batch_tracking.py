@@ -13,7 +13,10 @@ reports the host fraction of a step: SURVEY 8(f) N2's open question).
 ``device_tracker=True`` moves the host stages to the device as well (cp_track_step, centerpose_amd/csrc/track.hip):
 the track tables of all videos live in HBM, a frame is a fixed launch sequence render -> network -> decode ->
 post-process -> PnP -> track update -> filtered PnP -> records of the next render, and the host only reads the tracks
-when asked to (``step(..., read=True)``).
+when asked to (``step(..., read=True)``).  Seeds (``meta['pre_dets']``: the annotations the reference's evaluator hands to
+``Tracker.init_track``) and the ground-truth / empty previous-frame maps (--gt_pre_hm_hmhp, --gt_pre_hm_hmhp_first,
+--empty_pre_hm) are followed per video and frame on both paths; on the device by one cp_track_seed launch in front of
+the render (``_seed_plan``).
 """
 import time
 
@@ -38,6 +41,7 @@ class BatchedTracking(object):
         # the same choice as run() makes (base_detector.py:53-57: refined_Kalman wins when both flags are set)
         self.trackers = [_build_tracker(opt) for _ in range(self.n)]
         self._vmeta = None
+        self._zero_planes = None
         self.pre_images = None
         self.frames = 0
         self.times = {'host_records': 0.0, 'device': 0.0, 'host_tracks': 0.0, 'steps': 0}
@@ -56,6 +60,42 @@ class BatchedTracking(object):
 
         return _hip.render_gaussians(np.array(recs, np.float64).reshape(-1, 5), C, ih, iw, self.det.opt.device)
 
+    def _seed_plan(self, metas, params):
+        """What ``Tracker.init_track`` and the ground-truth branch of ``_get_additional_inputs`` would do with this frame's
+        metas, per video (base_detector.py:441-456, :166-167): -> None when no video is seeded, else the arguments of
+        ``DeviceTracker.seed``.  A video is seeded iff its meta carries 'pre_dets' and the reference calls ``init_track`` for it
+        now; its previous-frame maps are the ground-truth ones iff the tracking task renders maps, they are not the empty ones
+        and --gt_pre_hm_hmhp is set (or --gt_pre_hm_hmhp_first at ``meta['id'] == 0``).  Where the host tracker would raise a
+        KeyError this raises RuntimeError -- before anything is launched and before the loop's view of the frame moves."""
+        from centerpose_amd import hip as _hip
+
+        opt, first = self.det.opt, self.pre_images is None
+        maps = bool(opt.pre_hm or opt.pre_hm_hp)
+        lists, gt = [], []
+        for b, m in enumerate(metas):
+            gt_now = bool(opt.tracking_task and (opt.gt_pre_hm_hmhp or (opt.gt_pre_hm_hmhp_first and m.get('id') == 0)))
+            init = first or bool(opt.refined_Kalman) or gt_now
+            seeds = m['pre_dets'] if ('pre_dets' in m and init) else None
+            gt_b = gt_now and maps and not opt.empty_pre_hm
+            if gt_b and seeds is None:
+                raise RuntimeError("device tracker: ground-truth previous-frame maps are due for video %d but its meta has no "
+                                   "'pre_dets' (the tracks of a frame carry no 'kps_gt'; the host tracker raises here too)" % b)
+            if (seeds and not gt_b and maps and not opt.empty_pre_hm and opt.pre_hm_hp and opt.use_pnp
+                    and opt.render_hmhp_mode in (2, 3) and (opt.kalman or opt.scale_pool)):
+                for d in seeds:   # drawn by the branch that re-draws the filter read-out, which a seeded track does not have
+                    if d['score'] > opt.new_thresh and d['score'] >= opt.pre_thresh:
+                        box = self.det._trans_bbox(d['bbox'], m['trans_input'], m['inp_width'], m['inp_height'])
+                        if box[3] - box[1] > 0 and box[2] - box[0] > 0:
+                            raise RuntimeError("device tracker: video %d is seeded on a frame whose previous-frame maps are drawn "
+                                               "from the tracks, and render_hmhp_mode %d reads 'kps_mean_kf' / 'kps_pnp_kf', which "
+                                               "a seed does not carry (the host tracker raises KeyError here)" % (b, opt.render_hmhp_mode))
+            lists.append(seeds)
+            gt.append(gt_b)
+        if all(s is None for s in lists):
+            return None
+        seeds, counts = _hip.pack_seeds(lists, params, gt)
+        return seeds, counts, gt
+
     def _step_device(self, images, metas, read):
         """The whole frame on the device (cp_track_step); the host builds nothing unless ``read``."""
         from centerpose_amd import hip as _hip
@@ -63,12 +103,11 @@ class BatchedTracking(object):
         det, opt, B = self.det, self.det.opt, self.n
         t0 = time.time()
         images = images.to(opt.device)
+        params = self.dev.P if self.dev is not None else _hip.track_params_from_opt(opt, K=opt.K)
+        plan = self._seed_plan(metas, params)   # raises before anything is launched or remembered
         if self.dev is None:
-            if any('pre_dets' in m for m in metas):
-                raise RuntimeError("device tracker: seeding from meta['pre_dets'] is a host-tracker feature")
             self._vmeta = np.asarray(_hip.track_vmeta(metas), np.float64)
-            self.dev = _hip.DeviceTracker(B, _hip.track_params_from_opt(opt, K=opt.K), self._vmeta, opt.device,
-                                          metas[0]['inp_height'], metas[0]['inp_width'])
+            self.dev = _hip.DeviceTracker(B, params, self._vmeta, opt.device, metas[0]['inp_height'], metas[0]['inp_width'])
         elif self._vmeta is None:  # first frame after reset()
             self._vmeta = np.asarray(_hip.track_vmeta(metas), np.float64)
             self.dev.vmeta.copy_(torch.from_numpy(self._vmeta).reshape(B, 16))
@@ -80,11 +119,19 @@ class BatchedTracking(object):
             if not np.array_equal(vm, self._vmeta):
                 self._vmeta = vm
                 self.dev.vmeta.copy_(torch.from_numpy(vm).reshape(B, 16))
+        if plan is not None:
+            self.dev.seed(*plan)
         if self.pre_images is None:
             self.pre_images = images
         pre_hm = pre_hm_hp = None
         if opt.pre_hm or opt.pre_hm_hp:
-            hm, hp = self.dev.render()
+            if opt.empty_pre_hm:   # base_detector.py:166: the maps stay zero, whatever the tracks hold -- nothing to render
+                if self._zero_planes is None:
+                    ih, iw = metas[0]['inp_height'], metas[0]['inp_width']
+                    self._zero_planes = torch.zeros(9 * B, ih, iw, dtype=torch.float32, device=opt.device)
+                hm, hp = self._zero_planes[:B].unsqueeze(1), self._zero_planes[B:].view(B, 8, *self._zero_planes.shape[1:])
+            else:
+                hm, hp = self.dev.render()
             pre_hm = hm if opt.pre_hm else None
             pre_hm_hp = hp if opt.pre_hm_hp else None
         det._skip_host_dets = True

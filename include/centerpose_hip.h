@@ -688,8 +688,9 @@ int cp_pnp_from_post(cp_stream_t stream, const double* post, const int* count, i
  *   PnP; utils/pnp/cuboid_pnp_shell.py:26-91 packaging and visibility rejects).
  * Supported configuration = the demo's (src/demo.py:117-129): `tracking_task` with `kalman` and / or `scale_pool`,
  * greedy or Hungarian association (`hungarian`), `Tracker` or -- `baseline`, the reference's `--refined_Kalman` --
- * `Tracker_baseline` (utils/tracker_baseline.py:14-310), no ground-truth seeding; anything else stays on the host mirror
- * (centerpose_amd/lib/utils/tracker.py).  Per video the state holds at most `cap` (<= CP_TRACK_CAP) tracks.
+ * `Tracker_baseline` (utils/tracker_baseline.py:14-310); lists seeded from annotations and ground-truth previous-frame
+ * maps through cp_track_seed (below); anything else stays on the host mirror (centerpose_amd/lib/utils/tracker.py).  Per
+ * video the state holds at most `cap` (<= CP_TRACK_CAP) tracks.
  *
  *   params        HOST struct (opt fields; cat_rule: 0 camera / bottle / cup, 1 book / chair / cereal_box, 2 bike / laptop /
  *                 shoe -- the visibility reject of cuboid_pnp_shell.py:70-84; K = slots per image of post / det_pnp)
@@ -741,6 +742,36 @@ int cp_track_step(cp_stream_t stream, const cp_track_params* params, const doubl
                   const double* det_pnp, int B, void* state, double* render_recs, void* workspace, size_t workspace_bytes);
 /* dropped_out: HOST int32 [B], the sticky overflow counters above.  Copies 16 + 16 B bytes and synchronises `stream`. */
 int cp_track_status(cp_stream_t stream, const void* state, int B, int* dropped_out);
+
+/* Seeding from annotations, between two frames (added without an ABI change: a new entry point only) -- replaces
+ *   `Tracker.init_track(meta)` / `Tracker_baseline.init_track(meta)` with meta['pre_dets'] (utils/tracker.py:21-49,
+ *   utils/tracker_baseline.py:21-49: reset, then every seed with score > new_thresh becomes a track with the next id, age 1,
+ *   active 1, `init_kf` of the tracker class, a scale pool of one sample) and the ground-truth branch of
+ *   `_get_additional_inputs` (detectors/base_detector.py:167-209, --gt_pre_hm_hmhp / --gt_pre_hm_hmhp_first).
+ *   seeds         DEVICE float64 [B, S, CP_SEED_STRIDE], one record per seed (tools/objectron_eval/eval_video_official.py:
+ *                 430-449), 1 <= S <= CP_TRACK_CAP:
+ *                   0 the track record's [4, 156): the CP_POST_STRIDE detection fields (score, cls, obj_scale,
+ *                     obj_scale_uncertainty, kps_displacement_std, bbox, ct, kps, tracking, tracking_hp, kps_displacement_mean,
+ *                     kps_heatmap_mean, kps_heatmap_std, kps_heatmap_height), kps_fusion_mean[16], kps_fusion_std[16] |
+ *                   152 the track record's [179, 242): kps_pnp[18], kps_3d_cam[27], kps_ori[18] | 215 kps_gt[18] (centre
+ *                     first, normalised) | 233 presence bits: 1 ct given (else the bbox centre is taken), 2 kps_gt given,
+ *                     4 kps_pnp / kps_3d_cam given, 8 kps_ori given
+ *   seed_count    DEVICE int32 [B]: seeds of video b (values above S count as S).  NEGATIVE: video b is left bitwise
+ *                 untouched -- list, id counter, overflow counter and its rows of render_recs; 0: reset to an empty list.
+ *   gt_render     DEVICE int32 [B] or NULL: != 0 -> the rows of render_recs of video b hold the ground-truth Gaussians of
+ *                 its new tracks (centre from bbox when pre_hm, the eight vertices of kps_gt when pre_hm_hp, k = 1, no
+ *                 pre_thresh / visibility / bounds test: a blob may be centred outside the input and cp_render_gaussians
+ *                 clips it; a coordinate that is not finite or does not fit int32 withdraws its record, as does a missing
+ *                 kps_gt); else what cp_track_step would write for these tracks -- where that would re-draw kps_pnp_kf /
+ *                 kps_mean_kf, which a seeded track does not have yet (the reference raises), no vertex is drawn.
+ *   state         as cp_track_step; the CURRENT lists are replaced (call it between two frames, on the frames' stream).
+ *                 Beyond params->cap the first cap accepted seeds are kept and the rest is counted into the overflow counter.
+ *   render_recs   as cp_track_step: all cap rows of a seeded video are written (plane -1 beyond its list).
+ * Reads new_thresh, pre_thresh, R, kalman, scale_pool, baseline, use_pnp, the render modes, pre_hm, pre_hm_hp, hps_uncertainty,
+ * the confidence borders and cap of `params`.  One kernel launch, no host synchronisation. */
+#define CP_SEED_STRIDE 234
+int cp_track_seed(cp_stream_t stream, const cp_track_params* params, const double* vmeta, const double* seeds,
+                  const int* seed_count, const int* gt_render, int B, int S, void* state, double* render_recs);
 
 /* The tracker's assignment on the HOST (no device work, no stream): replaces `linear_assignment(dist)` of tracker.py:157 for the
  * host tracker (centerpose_amd/lib/utils/tracker.py) with the very routine the device tracker runs.
