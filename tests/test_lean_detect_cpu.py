@@ -91,8 +91,8 @@ def _lazy(gen_model, gen_call):
 
 def test_lazy_heads_order_materialisation_and_stale_access(monkeypatch):
     stub = _StubLib()
-    monkeypatch.setattr(hip, "lib", lambda: stub)
-    monkeypatch.setattr(hip, "_stream", lambda: None)
+    monkeypatch.setattr(hip._abi, "lib", lambda: stub)
+    monkeypatch.setattr(hip._abi, "_stream", lambda: None)
     z, heads = _lazy(3, 3)
     assert list(z) == list(heads) == list(z.keys()) and len(z) == len(heads)
     assert "hps" in z and "nope" not in z
