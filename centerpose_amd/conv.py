@@ -72,16 +72,32 @@ def _pair(v, what):
     return int(v)
 
 
+def _geometry_refusal(cin, kh, kw, stride, pad):
+    """Why the kernels cannot run a convolution of this geometry, or None: the one rule of ``conv2d``, ``Conv2d`` and
+    ``use_hip_convs``, and the library's own for the backward (``conv_bwd_shape_error``, csrc/ops.hip).  Kernel 1..7 on each axis,
+    stride 1..4, ``0 <= pad < min(kh, kw)``, ``cin`` a positive multiple of 4."""
+    if cin < 4 or cin % 4:
+        return "in_channels = %d is not a multiple of 4" % cin
+    if not (1 <= kh <= 7 and 1 <= kw <= 7 and 1 <= stride <= 4 and 0 <= pad < min(kh, kw)):
+        return "geometry outside kernel 1..7, stride 1..4, padding < kernel"
+    return None
+
+
 def conv2d(x, weight, bias=None, stride=1, padding=0, relu=False):
     """``relu?(F.conv2d(x, weight, bias, stride, padding))`` on the HIP kernels with autograd.  ``x`` is a logical [B,Cin,H,W] tensor on
     the device, NCHW-contiguous or channels_last (the kernels read NHWC; channels_last costs no copy); the result is
-    channels_last.  Dilation 1, groups 1, ``Cin % 4 == 0``."""
+    channels_last.  Dilation 1, groups 1, and the geometry of ``_geometry_refusal``: what the backward refuses raises
+    NotImplementedError here, before the forward runs."""
     if not x.is_cuda:
         raise RuntimeError("centerpose_hip: tensors must live on the HIP device (no CPU path)")
     if x.dim() != 4 or weight.dim() != 4 or weight.shape[1] != x.shape[1]:
         raise RuntimeError("conv2d: x must be [B,Cin,H,W] and weight [Cout,Cin,KH,KW], got %s and %s"
                            % (tuple(x.shape), tuple(weight.shape)))
-    return _Conv2dFn.apply(x, weight, bias, _pair(stride, "stride"), _pair(padding, "padding"), bool(relu))
+    stride, padding = _pair(stride, "stride"), _pair(padding, "padding")
+    why = _geometry_refusal(int(weight.shape[1]), int(weight.shape[2]), int(weight.shape[3]), stride, padding)
+    if why:
+        raise NotImplementedError("conv2d: " + why)
+    return _Conv2dFn.apply(x, weight, bias, stride, padding, bool(relu))
 
 
 def _refusal(m):
@@ -96,12 +112,7 @@ def _refusal(m):
         return "string padding %r" % m.padding
     if m.stride[0] != m.stride[1] or m.padding[0] != m.padding[1]:
         return "stride / padding differ between the axes"
-    if m.in_channels % 4:
-        return "in_channels = %d is not a multiple of 4" % m.in_channels
-    kh, kw = m.kernel_size
-    if not (1 <= kh <= 7 and 1 <= kw <= 7 and 1 <= m.stride[0] <= 4 and m.padding[0] < min(kh, kw)):
-        return "geometry outside kernel 1..7, stride 1..4, padding < kernel"
-    return None
+    return _geometry_refusal(m.in_channels, m.kernel_size[0], m.kernel_size[1], m.stride[0], m.padding[0])
 
 
 class Conv2d(nn.Conv2d):
