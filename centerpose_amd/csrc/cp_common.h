@@ -635,6 +635,16 @@ size_t cp_train_inputs_ws_bytes(int N, int out_h, int out_w);  // 0: refused
 int cp_launch_train_inputs(hipStream_t s, const unsigned char* frames, const double* records, int N, const float* mean3,
                            const float* std3, float* out, int out_h, int out_w, void* ws);
 
+// ---- clip + Adam over a param group (optim.hip; table and state layouts in include/centerpose_hip.h) ----
+const char* cp_adam_lengths_check(int n_tensors, const int64_t* lengths, const int* active_or_null,
+                                  long long* n_chunks);  // nullptr: accepted
+size_t cp_adam_table_size(int n_tensors, long long n_chunks);
+const char* cp_adam_table_fill(void* table, int n_tensors, const void* const* p, const void* const* g, const void* const* m,
+                               const void* const* v, const int64_t* lengths, const int* active_or_null);  // nullptr: written
+size_t cp_adam_ws_bytes(int n_chunks);
+int cp_launch_adam_step(hipStream_t s, const void* table, int n_tensors, int n_chunks, double lr, double beta1, double beta2, double eps,
+                        double weight_decay, double max_norm, int flags, void* state, void* ws);
+
 // ---- Objectron box metrics (box3d.hip; numerics in box3d_common.h) ----
 int cp_launch_box_iou(hipStream_t s, const double* a, const double* b, int n, double* iou);
 int cp_launch_box_eval(hipStream_t s, const double* pred3d, const double* gt3d, const double* pred2d, const double* mo2c,

@@ -2,7 +2,7 @@
 // -- cp_conv2d_nhwc / cp_conv2d_backward_nhwc, cp_batchnorm_forward_nhwc / _backward_nhwc, cp_conv_transpose2d_nhwc,
 // cp_conv_transpose2d_dw_nhwc / cp_conv_transpose2d_backward_nhwc, cp_dcnv2_forward / cp_dcnv2_backward / cp_dcnv2_backward_det, cp_pose_heads_forward / _backward,
 // cp_maxpool2d_forward_nhwc / _backward_nhwc, cp_conv2d_stem_backward, cp_groupnorm_forward_nhwc / _backward_nhwc,
-// cp_gru_gate_forward / _backward.
+// cp_gru_gate_forward / _backward, cp_adam_table_bytes / _table_build / _step.
 // Each packs its PyTorch-layout weights into a caller-provided workspace on every call and then launches the same kernels as
 // the engine.
 #include "op_common.h"
@@ -792,6 +792,56 @@ int cp_dcnv2_forward(cp_stream_t stream, const float* input, const float* weight
     rc = use16 ? cp_launch_conv16(p, s) : cp_launch_conv(p, s);
     if (rc != CP_OK) return rc;
     return cp_launch_nhwc_to_nchw(r.y, output, B, Co, H, W, Co, s);
+}
+
+// Clip + Adam over a param group (optim.hip)
+size_t cp_adam_table_bytes(int n_tensors, const int64_t* lengths, const int* active_or_null, int* n_chunks) {
+    long long nc = 0;
+    const char* e = cp_adam_lengths_check(n_tensors, lengths, active_or_null, &nc);
+    if (!e && !n_chunks) e = "adam: null n_chunks";
+    if (e) {
+        fail(CP_ERR_INVALID, e);
+        return 0;
+    }
+    *n_chunks = (int)nc;  // at most 2^31 / CP_ADAM_CHUNK + n_tensors
+    return cp_adam_table_size(n_tensors, nc);
+}
+
+int cp_adam_table_build(void* table, size_t table_bytes, int n_tensors, const void* const* p, const void* const* g,
+                        const void* const* m, const void* const* v, const int64_t* lengths, const int* active_or_null,
+                        int* n_chunks) {
+    if (!table || !p || !g || !m || !v || !lengths || !n_chunks) return fail(CP_ERR_INVALID, "adam_table_build: null argument");
+    long long nc = 0;
+    if (const char* e = cp_adam_lengths_check(n_tensors, lengths, active_or_null, &nc)) return fail(CP_ERR_INVALID, e);
+    if (table_bytes < cp_adam_table_size(n_tensors, nc)) return fail(CP_ERR_INVALID, "adam_table_build: table buffer too small");
+    if ((uintptr_t)table & 7) return fail(CP_ERR_INVALID, "adam_table_build: table must be 8-byte aligned");
+    if (const char* e = cp_adam_table_fill(table, n_tensors, p, g, m, v, lengths, active_or_null)) return fail(CP_ERR_INVALID, e);
+    *n_chunks = (int)nc;
+    return CP_OK;
+}
+
+size_t cp_adam_state_bytes(int n_tensors) { return n_tensors < 1 ? 0 : CP_ADAM_STATE_BC(n_tensors) + (size_t)n_tensors * 16; }
+
+size_t cp_adam_workspace_bytes(int n_chunks) { return n_chunks < 0 ? 0 : cp_adam_ws_bytes(n_chunks); }
+
+int cp_adam_step(cp_stream_t stream, const void* table, int n_tensors, int n_chunks, double lr, double beta1, double beta2, double eps,
+                 double weight_decay, double max_norm, int flags, void* state, void* workspace, size_t workspace_bytes) {
+    if (!table || !state || !workspace) return fail(CP_ERR_INVALID, "adam_step: null argument");
+    if (n_tensors < 1) return fail(CP_ERR_INVALID, "adam_step: n_tensors must be >= 1");
+    if (n_chunks < 0) return fail(CP_ERR_INVALID, "adam_step: n_chunks must be >= 0");
+    if (((uintptr_t)table | (uintptr_t)state | (uintptr_t)workspace) & 7)
+        return fail(CP_ERR_INVALID, "adam_step: table, state and workspace must be 8-byte aligned");
+    for (double h : {lr, beta1, beta2, eps, weight_decay, max_norm})
+        if (!std::isfinite(h)) return fail(CP_ERR_INVALID, "adam_step: non-finite hyper-parameter");
+    if (lr < 0) return fail(CP_ERR_INVALID, "adam_step: lr must be >= 0");
+    if (!(beta1 >= 0 && beta1 < 1) || !(beta2 >= 0 && beta2 < 1)) return fail(CP_ERR_INVALID, "adam_step: betas must lie in [0, 1)");
+    if (eps < 0) return fail(CP_ERR_INVALID, "adam_step: eps must be >= 0");
+    if (weight_decay < 0) return fail(CP_ERR_INVALID, "adam_step: weight_decay must be >= 0");
+    if (flags & ~CP_ADAM_SKIP_NONFINITE) return fail(CP_ERR_INVALID, "adam_step: unknown flag");
+    if (workspace_bytes < cp_adam_ws_bytes(n_chunks)) return fail(CP_ERR_INVALID, "adam_step: workspace too small");
+    const int rc = cp_launch_adam_step((hipStream_t)stream, table, n_tensors, n_chunks, lr, beta1, beta2, eps, weight_decay, max_norm,
+                                       flags, state, workspace);
+    return rc == CP_OK ? CP_OK : fail(rc, "adam_step: kernel launch failed");
 }
 
 }  // extern "C"

@@ -128,6 +128,11 @@ SIGNATURES = {
     "cp_pose_targets_track_det": (c_int, _vp + [POINTER(PoseTargetsTrackDetDesc)] + _ws),
     "cp_train_inputs_workspace_bytes": (c_size_t, _i * 3),
     "cp_train_inputs": (c_int, _vp * 2 + [c_size_t] + _vp + _i + _pf * 2 + _vp + _i * 2 + _ws),
+    "cp_adam_table_bytes": (c_size_t, _i + [POINTER(c_int64)] + _pi * 2),
+    "cp_adam_table_build": (c_int, [c_void_p, c_size_t] + _i + _pvp * 4 + [POINTER(c_int64)] + _pi * 2),
+    "cp_adam_state_bytes": (c_size_t, _i),
+    "cp_adam_workspace_bytes": (c_size_t, _i),
+    "cp_adam_step": (c_int, _vp * 2 + _i * 2 + [c_double] * 6 + _i + _vp + _ws),
 }
 
 

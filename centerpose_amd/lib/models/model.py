@@ -205,7 +205,8 @@ def create_model(arch, heads, head_conv, opt=None):
 
 
 def load_model(model, model_path, optimizer=None, resume=False, lr=None, lr_step=None):
-    """models/model.py:34-87 (the optimizer-resume branch is training-only and not mirrored)."""
+    """models/model.py:34-87.  With an ``optimizer`` (torch.optim.Adam or centerpose_amd.optim.Adam: their state dicts are
+    interchangeable) the return value is (model, optimizer, start_epoch), as the reference's."""
     checkpoint = torch.load(model_path, map_location=lambda storage, loc: storage, weights_only=False)
     print('loaded {}, epoch {}'.format(model_path, checkpoint['epoch']))
     state_dict_ = checkpoint['state_dict']
@@ -231,9 +232,29 @@ def load_model(model, model_path, optimizer=None, resume=False, lr=None, lr_step
             print('No param {}.'.format(k) + msg)
             state_dict[k] = model_state_dict[k]
     model.load_state_dict(state_dict, strict=False)
-    if optimizer is not None:
-        raise NotImplementedError("optimizer resume is training-only")
-    return model
+    if optimizer is None:
+        return model
+    if not resume:
+        return model, optimizer, 0
+    if 'optimizer' not in checkpoint:
+        print('No optimizer parameters in checkpoint.')
+        return model, optimizer, 0
+    # the optimizer continues from the checkpoint, at the learning rate its schedule has reached by that epoch
+    epoch = checkpoint['epoch']
+    optimizer.load_state_dict(checkpoint['optimizer'])
+    decayed = _decayed_lr(lr, sum(1 for milestone in lr_step if milestone <= epoch))
+    for group in optimizer.param_groups:
+        group['lr'] = decayed
+    print('Resumed optimizer with start lr', decayed)
+    return model, optimizer, epoch
+
+
+def _decayed_lr(lr, drops):
+    """``lr`` after ``drops`` decays by 0.1, one product per decay: the value a run that lived through the milestones holds
+    (``lr * 0.1 ** drops`` can differ from it in the last bit)."""
+    for _ in range(drops):
+        lr = lr * 0.1
+    return lr
 
 
 def save_model(path, epoch, model, optimizer=None):

@@ -49,7 +49,8 @@ typedef struct cp_model cp_model;
  *     cp_pose_heads_forward / _backward (+ _workspace_bytes, cp_pose_heads_chunk_images), cp_model_features;
  *     cp_groupnorm_workspace_bytes, cp_groupnorm_forward_nhwc / _backward_nhwc, cp_gru_gate_forward / _backward;
  *     cp_train_inputs_workspace_bytes, cp_train_inputs;
- *     cp_pose_targets_track_det_workspace_bytes, cp_pose_targets_track_det. */
+ *     cp_pose_targets_track_det_workspace_bytes, cp_pose_targets_track_det;
+ *     cp_adam_table_bytes, cp_adam_table_build, cp_adam_state_bytes, cp_adam_workspace_bytes, cp_adam_step. */
 #define CP_ABI_VERSION 7
 const char* cp_version(void);
 int cp_abi_version(void);
@@ -1186,6 +1187,74 @@ size_t cp_train_inputs_workspace_bytes(int N, int out_h, int out_w); /* 0: shape
 int cp_train_inputs(cp_stream_t stream, const unsigned char* frames, size_t frames_bytes, const double* records, int N,
                     const float* mean3, const float* std3, float* out, int out_h, int out_w, void* workspace,
                     size_t workspace_bytes);
+
+/* ------------------------------------------------------------------------------------------
+ * cp_adam_*: gradient-norm clipping and the Adam update of all tensors of a param group -- the update of the reference's
+ *   training step, trains/base_trainer.py:91-99 (`clip_grad_norm_(model.parameters(), 100.)`, `optimizer.step()`) with
+ *   the optimizer of test.py:41 (`torch.optim.Adam(model.parameters(), opt.lr)`; amsgrad=False, maximize=False).
+ * At most three launches per call whatever n_tensors is, no float atomics, no host synchronisation, bitwise reproducible.
+ * All tensors are float32 and dense: tensor i is `lengths[i]` consecutive floats at p[i] (parameter), g[i] (gradient),
+ * m[i] (exp_avg) and v[i] (exp_avg_sq), each 4-byte aligned; a tensor whose four pointers are all 16-byte aligned moves
+ * 16 bytes per lane, any other goes element by element.
+ *
+ * The table (one definition of the layout; cp_adam_table_build writes it into HOST memory, the caller copies it to the
+ * device as it is): n_tensors tensor records of CP_ADAM_TENSOR_BYTES, then n_chunks chunk records of
+ * CP_ADAM_CHUNK_BYTES.
+ *   tensor record  bytes 0/8/16/24: p, g, m, v (device addresses); 32: int64 length; 40: int32 active (0 or 1); 44: 0
+ *   chunk record   bytes 0: int32 tensor index; 4: uint32 first element within the tensor; 8: int32 element count
+ *                  (1..CP_ADAM_CHUNK); 12: int32 flags (CP_ADAM_VEC: all four pointers of the tensor are 16-byte aligned)
+ * Chunks are in tensor order and, within a tensor, ascending; a tensor of n elements takes ceil(n / CP_ADAM_CHUNK) chunks
+ * that start at multiples of CP_ADAM_CHUNK, so a chunk never straddles two tensors, a tensor of length 0 takes none, and
+ * a tensor that takes no part in the step (active_or_null[i] == 0: a parameter without a gradient) takes none either:
+ * its pointers are not read, its step counter and its memory do not move.
+ *
+ * The state block, DEVICE memory of cp_adam_state_bytes(n_tensors) bytes that the caller zeroes once and keeps between
+ * steps (8-byte aligned):
+ *   CP_ADAM_STATE_NORM     float32 total_norm of the last call: sqrt(sum g^2) over the active tensors, the chunk sums and
+ *                          their sum in float64 in table order; NaN when the call did not measure it (no clipping and no
+ *                          CP_ADAM_SKIP_NONFINITE)
+ *   CP_ADAM_STATE_COEF     float32 clip coefficient, torch's: min(1, max_norm / (total_norm + 1e-6)) in float32 (NaN for
+ *                          a NaN norm); 1 without clipping
+ *   CP_ADAM_STATE_SKIPPED  int32 1: the call changed nothing (see flags), else 0
+ *   CP_ADAM_STATE_STEPS    float32 [n_tensors] step counters (torch's `step`), advanced by 1 for every active tensor
+ *   CP_ADAM_STATE_BC(n)    float64 [2][n_tensors] bias corrections 1 - beta1^step and 1 - beta2^step, computed in float64
+ *                          from the double betas (in float32 1 - 0.999f alone is off by 6e-5 relative)
+ * cp_adam_step, per element of every chunk, torch's Adam as its float32 kernels round it:
+ *   g' = coef g + weight_decay p;  m += (1 - beta1)(g' - m);  v = beta2 v + (1 - beta2) g'^2;
+ *   p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps)
+ * p, m and v are written; g is NOT (clip_grad_norm_ scales .grad in place, this call leaves it as it was).
+ *   max_norm <= 0: no clipping (coef = 1; the sum-of-squares launch is dropped unless the flag below needs the norm).
+ *   flags & CP_ADAM_SKIP_NONFINITE: when total_norm is inf or NaN the call raises CP_ADAM_STATE_SKIPPED and changes
+ *   neither p, m, v nor any step counter.  Without the flag a non-finite norm goes through the arithmetic as in torch
+ *   (coef 0 or NaN).
+ * Refused with CP_ERR_INVALID and a cp_last_error text before any launch (cp_adam_table_bytes: returns 0): NULL pointers,
+ *   n_tensors < 1, a length < 0, more than 2^31 elements in the active tensors together, an active non-empty tensor with
+ *   a NULL or not 4-byte aligned address, a table buffer below cp_adam_table_bytes, n_chunks < 0, a table or state block
+ *   not 8-byte aligned, lr < 0, a beta outside [0, 1), eps < 0, weight_decay < 0, any non-finite hyper-parameter, a
+ *   workspace below cp_adam_workspace_bytes(n_chunks).  cp_adam_step cannot see the table's content (device memory): it
+ *   trusts n_tensors / n_chunks to be those of the cp_adam_table_build call that made it.
+ * ------------------------------------------------------------------------------------------ */
+#define CP_ADAM_CHUNK 4096
+#define CP_ADAM_TENSOR_BYTES 48
+#define CP_ADAM_CHUNK_BYTES 16
+#define CP_ADAM_VEC 1
+#define CP_ADAM_SKIP_NONFINITE 1
+#define CP_ADAM_STATE_NORM 0
+#define CP_ADAM_STATE_COEF 4
+#define CP_ADAM_STATE_SKIPPED 8
+#define CP_ADAM_STATE_STEPS 16
+#define CP_ADAM_STATE_BC(n) (16 + (((size_t)(n) * 4 + 7) / 8) * 8)
+/* HOST: bytes of the table of these lengths (0: refused) and, through n_chunks, its number of chunks */
+size_t cp_adam_table_bytes(int n_tensors, const int64_t* lengths, const int* active_or_null, int* n_chunks);
+/* HOST: writes the table into `table` (host memory of table_bytes) from host arrays of device addresses */
+int cp_adam_table_build(void* table, size_t table_bytes, int n_tensors, const void* const* p, const void* const* g,
+                        const void* const* m, const void* const* v, const int64_t* lengths, const int* active_or_null,
+                        int* n_chunks);
+size_t cp_adam_state_bytes(int n_tensors);  /* 0: n_tensors < 1 */
+size_t cp_adam_workspace_bytes(int n_chunks); /* 0: n_chunks < 0 */
+int cp_adam_step(cp_stream_t stream, const void* table, int n_tensors, int n_chunks, double lr, double beta1, double beta2,
+                 double eps, double weight_decay, double max_norm, int flags, void* state, void* workspace,
+                 size_t workspace_bytes);
 
 #ifdef __cplusplus
 }
