@@ -42,6 +42,22 @@ enum CpStore : int {
 #define CP_MAX_SRC 4
 #define CP_MAX_HEAD_GROUP 12
 
+// Bump carver over an operator's workspace.  Each operator describes its regions once, in a *_carve function: run on the
+// caller's pointer it hands out the regions, run on nullptr it only counts, and *_workspace_bytes is `off` of that run -- the
+// size and the carve-up cannot drift apart.  `end` is the unrounded end of the last region taken: the size of a workspace
+// whose ABI does not round its last region.
+struct Carve {
+    char* base;
+    size_t off = 0, end = 0;
+    template <class T>
+    T* take(size_t bytes) {
+        T* p = base ? (T*)(base + off) : nullptr;
+        end = off + bytes;
+        off += (bytes + 255) / 256 * 256;
+        return p;
+    }
+};
+
 #ifdef __HIPCC__
 // ---- |max| tracking and power-of-two operand scaling for the split-f16 kernels (see ConvParams::in_amax) ----
 // amax bits -> (2^e, 2^-e) with amax * 2^e in [2^14, 2^15): e = 14 - floor(log2(amax)).  Exponents are clamped so that
@@ -604,6 +620,20 @@ int cp_launch_pose_targets(hipStream_t s, const cp_pose_targets_desc* d, void* w
 // ---- the tracking task's targets (pose_targets_track.hip; per-object logic in pose_targets_track_common.h) ----
 namespace pose_targets { struct PtTrackCur; }
 int cp_launch_pose_targets_cur(hipStream_t s, const cp_pose_targets_desc* d, void* ws, const pose_targets::PtTrackCur* tk);
+double* cp_pose_targets_ws_images(const cp_pose_targets_desc* d, void* ws);  // where its launcher stages d->images in `ws`
+// the Gaussian map writer of every target builder (pose_targets.hip): each element of each plane written once, as the max
+// over the plane's draws that cover it.  A list belongs to (image, channel c): channel 0 draws on out0, 1 + j on outj's joint j.
+struct cp_gauss_maps_args {
+    float *out0, *outj;   // [images][H][W] and [images][8][H][W], 16-byte aligned; only channels ch0 .. ch0 + nch - 1 are read
+    int W, H;             // W * H < 2^31
+    int images, nch, ch0;
+    int stride;           // list entries per (image, channel): at most 64 without peaks, 128 with
+    const int* counts;    // [images * 9]
+    const int4* draws;    // [images * 9][stride] (x, y, r, 0)
+    const double* peaks;  // [images * 9][stride], or nullptr: every peak is 1
+};
+size_t cp_gauss_maps_workgroups(size_t planes, size_t plane_elems);  // the grid (the *_check functions hold it below 2^31)
+void cp_launch_gauss_maps(hipStream_t s, const cp_gauss_maps_args& a);
 struct cp_pose_targets_track_desc;
 const char* cp_pose_targets_track_check(const cp_pose_targets_track_desc* d);  // nullptr: accepted
 size_t cp_pose_targets_track_ws_bytes(const cp_pose_targets_track_desc* d);    // 0: refused

@@ -1,23 +1,10 @@
 // What the stand-alone operators share (ops.hip and the training operators dcn_bwd.hip, heads_bwd.hip, conv_bwd.hip,
-// deconv_bwd.hip, batchnorm.hip, groupnorm.hip, gru_train.hip): the workspace carver, the launch check, the two fixed-order slab sums and the ConvParams of a
-// convolution that runs as part of a gradient.  The summation orders are contract (the tests compare bitwise), so they are
-// written here once.
+// conv_bwd_lowc.hip, deconv_bwd.hip, batchnorm.hip, groupnorm.hip, gru_train.hip, pool.hip, stem_bwd.hip, optim.hip): the launch check, the two
+// fixed-order slab sums and the ConvParams of a convolution that runs as part of a gradient.  The summation orders are contract
+// (the tests compare bitwise), so they are written here once.  The workspace carver, Carve, is in cp_common.h, where the target
+// builders (pose_targets*.hip, train_inputs.hip) reach it without the engine's model header.
 #pragma once
 #include "engine_model.h"
-
-// Bump carver over an operator's workspace.  Each operator describes its regions once, in a *_carve function: run on the
-// caller's pointer it hands out the regions, run on nullptr it only counts, and *_workspace_bytes is `off` of that run -- the
-// size and the carve-up cannot drift apart.
-struct Carve {
-    char* base;
-    size_t off = 0;
-    template <class T>
-    T* take(size_t bytes) {
-        T* p = base ? (T*)(base + off) : nullptr;
-        off += cp_engine::align_up(bytes, 256);
-        return p;
-    }
-};
 
 inline bool launch_ok() { return hipGetLastError() == hipSuccess; }
 

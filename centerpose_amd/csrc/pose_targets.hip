@@ -8,27 +8,37 @@
 //                      with a ballot in object order: no atomics.
 //                      For cp_pose_targets_track (pose_targets_track.hip) a PtTrackCur argument adds the tracking task's
 //                      skip and variant filter and the tracking / tracking_hp targets; all zero, it changes nothing.
-//   2. maps_kernel     one workgroup per (map plane, band of BAND elements): the plane's draw list, culled to the band's
-//                      rows, sits in LDS; every element of hm / hm_hp is written exactly once (no clear pass) as the max
-//                      over the draws that cover it of float32(exp(-(dx^2+dy^2) / (2 sigma^2))), sigma = (2r+1)/6 in
-//                      float64 -- draw_umich_gaussian's values (utils/image.py:126-150) and render_gaussians_kernel's
-//                      arithmetic (post.hip).  A max does not depend on the order of the draws: bitwise deterministic.
-//                      Stores are float4 per lane (nontemporal), whole 128-byte lines wherever the plane is
-//                      line-aligned; a band without a draw stores zero lines only.
+//   2. maps_kernel     the one Gaussian map writer of the target builders (cp_launch_gauss_maps; the previous frame's
+//                      pre_hm / pre_hm_hp of pose_targets_track.hip go through it too).  One workgroup per (map plane,
+//                      band of BAND elements): the plane's draw list, culled to the band's rows by one wavefront, sits in
+//                      LDS; every element is written exactly once (no clear pass) as the max over the draws that cover
+//                      it of float32(exp(-(dx^2+dy^2) / (2 sigma^2))), sigma = (2r+1)/6 in float64 --
+//                      draw_umich_gaussian's values (utils/image.py:126-150) and render_gaussians_kernel's arithmetic
+//                      (post.hip).  A max does not depend on the order of the draws: bitwise deterministic.  Stores are
+//                      float4 per lane (nontemporal), whole 128-byte lines wherever the plane is line-aligned, scalar
+//                      for a plane's misaligned head and tail; a band without a draw stores zero lines only.
+//                      Two instantiations.  <false, 64>: hm / hm_hp, R x R planes, lists of up to max_objs <= 64 draws.
+//                      <true, 128>: W x H planes, lists of up to 2 * Kp <= 128 draws read in two passes of 64, each
+//                      draw with a float64 peak k, the value float32(k * exp(...)) with the product in float64, and
+//                      64-bit window tests, because a false positive's centre may lie anywhere.  A draw whose centre
+//                      lies outside the map covers what draw_umich_gaussian's clipped window covers: the pixels of the
+//                      map within r of it, none if there are none (utils/image.py:143-149).
+// The workspace is described once, in pose_targets_carve (Carve, cp_common.h): the size is that function run on nullptr.
 #include "../../include/centerpose_hip.h"
 #include "cp_common.h"
 #include "pose_targets_common.h"
 #include "pose_targets_track_common.h"
 
 #include <cstdio>
+#include <type_traits>
 
 using namespace pose_targets;
 
 namespace {
 
-constexpr int NCH = 1 + CP_PT_JOINTS;  // draw-list channels per (b, s): hm, then the 8 hm_hp joints
-constexpr int MT = 256;                // maps kernel: threads per workgroup
-constexpr int BAND = MT * 4 * 2;       // maps kernel: elements per workgroup (2 float4 per thread)
+constexpr int NCH = 1 + CP_PT_JOINTS;  // draw-list channels per image: channel 0, then the 8 joints
+constexpr int MT = 256;                // map writer: threads per workgroup
+constexpr int BAND = MT * 4 * 2;       // map writer: elements per workgroup (2 float4 per thread)
 
 // The maps are written once and read by a later kernel (the loss): nontemporal stores, 47.6 us against 71.0 us for
 // default-policy stores at B = 32, S = 12, 128 x 128 (profiles/pose_targets_bench.txt).
@@ -38,24 +48,19 @@ __device__ __forceinline__ void store_nt(float* p, float a, float b, float c, fl
     __builtin_nontemporal_store(v, reinterpret_cast<pt_f4*>(p));
 }
 
-inline size_t up256(size_t x) { return (x + 255) / 256 * 256; }
-
 struct Ws {
     double *img, *obj;
     int* counts;  // [B*S*NCH]
     int4* draws;  // [B*S*NCH][max_objs] (x, y, r, 0)
 };
 
-Ws carve(const cp_pose_targets_desc* d, void* ws) {
-    char* p = (char*)ws;
+Ws pose_targets_carve(Carve& c, const cp_pose_targets_desc* d) {
+    const size_t B = d->B, K = d->max_objs, lists = B * d->S * NCH;
     Ws w;
-    w.img = (double*)p;
-    p += up256((size_t)d->B * CP_PT_IMG_STRIDE * sizeof(double));
-    w.obj = (double*)p;
-    p += up256((size_t)d->B * d->max_objs * CP_PT_OBJ_STRIDE * sizeof(double));
-    w.counts = (int*)p;
-    p += up256((size_t)d->B * d->S * NCH * sizeof(int));
-    w.draws = (int4*)p;
+    w.img = c.take<double>(B * CP_PT_IMG_STRIDE * sizeof(double));
+    w.obj = c.take<double>(B * K * CP_PT_OBJ_STRIDE * sizeof(double));
+    w.counts = c.take<int>(lists * sizeof(int));
+    w.draws = c.take<int4>(lists * K * sizeof(int4));
     return w;
 }
 
@@ -148,32 +153,43 @@ __global__ void __launch_bounds__(64) objects_kernel(cp_pose_targets_desc d, con
     }
 }
 
-__global__ void __launch_bounds__(MT) maps_kernel(float* __restrict__ hm, float* __restrict__ hm_hp, int R, int K,
-                                                  int nch, int nband, const int* __restrict__ counts,
-                                                  const int4* __restrict__ draws) {
-    __shared__ int4 sd[64];
-    __shared__ double sden[64];
+// PEAKS: a draw has a float64 peak k and its centre may lie anywhere (a false positive's), so the window tests are 64-bit;
+// CAP: the most draws a list holds, 64 per culling pass.  The plain form <false, 64> pays for neither: 64-bit tests there
+// cost 5 us of 47 at S = 12 (profiles/targets_refactor_ab.txt).
+template <bool PEAKS, int CAP>
+__global__ void __launch_bounds__(MT) maps_kernel(const cp_gauss_maps_args a, int nband) {
+    typedef typename std::conditional<PEAKS, long long, int>::type win_t;
+    __shared__ int4 sd[CAP];
+    __shared__ double sden[CAP], sk[PEAKS ? CAP : 1];
     __shared__ int sn;
-    const int plane = blockIdx.x / nband, band = blockIdx.x - plane * nband;  // plane = (b*S + s) * nch + c
-    const int bs = plane / nch, c = plane - bs * nch;
-    const unsigned P = (unsigned)R * R;  // < 2^31 (R <= 46340): element indices within a plane stay 32-bit
+    const int W = a.W, nch = a.nch;
+    const int plane = blockIdx.x / nband, band = blockIdx.x - plane * nband;  // plane = image * nch + (c - ch0)
+    const int im = plane / nch, c = plane - im * nch + a.ch0;
+    const unsigned P = (unsigned)W * a.H;  // < 2^31 (checked): element indices within a plane stay 32-bit
     const unsigned e0 = (unsigned)band * BAND, e1 = e0 + BAND < P ? e0 + BAND : P;
-    const size_t g0 = c == 0 ? (size_t)bs * P : ((size_t)bs * CP_PT_JOINTS + (c - 1)) * P;  // plane offset in its tensor
-    float* out = (c == 0 ? hm : hm_hp) + g0;
-    if (threadIdx.x < 64) {  // the plane's draws whose rows meet the band's, compacted by one wavefront
-        const int n = counts[bs * NCH + c];
-        const int ylo = (int)(e0 / R), yhi = (int)((e1 - 1) / R);
-        int4 dr = make_int4(0, 0, -1, 0);
-        if ((int)threadIdx.x < n) dr = draws[((size_t)bs * NCH + c) * K + threadIdx.x];
-        const bool v = (int)threadIdx.x < n && dr.y - dr.z <= yhi && dr.y + dr.z >= ylo;
-        const unsigned long long m = __ballot(v);
-        if (v) {
-            const int pos = __popcll(m & ((1ull << threadIdx.x) - 1));
-            const double sigma = (double)(2 * dr.z + 1) / 6.0;
-            sd[pos] = dr;
-            sden[pos] = 2 * sigma * sigma;
+    const size_t g0 = c == 0 ? (size_t)im * P : ((size_t)im * CP_PT_JOINTS + (c - 1)) * P;  // plane offset in its tensor
+    float* out = (c == 0 ? a.out0 : a.outj) + g0;
+    if (threadIdx.x < 64) {  // the plane's draws whose rows meet the band's: one wavefront, 64 entries per pass
+        const int n = a.counts[im * NCH + c];
+        const size_t list = ((size_t)im * NCH + c) * a.stride;
+        const int ylo = (int)(e0 / W), yhi = (int)((e1 - 1) / W);
+        int base = 0;
+        for (int p0 = 0; p0 < CAP && p0 < n; p0 += 64) {
+            const int i = p0 + threadIdx.x;
+            int4 dr = make_int4(0, 0, -1, 0);
+            if (i < n) dr = a.draws[list + i];
+            const bool v = i < n && (win_t)dr.y - dr.z <= yhi && (win_t)dr.y + dr.z >= ylo;
+            const unsigned long long m = __ballot(v);
+            if (v) {
+                const int pos = base + __popcll(m & ((1ull << threadIdx.x) - 1));
+                const double sigma = (double)(2 * dr.z + 1) / 6.0;
+                sd[pos] = dr;
+                sden[pos] = 2 * sigma * sigma;
+                if constexpr (PEAKS) sk[pos] = a.peaks[list + i];
+            }
+            base += __popcll(m);
         }
-        if (threadIdx.x == 0) sn = __popcll(m);
+        if (threadIdx.x == 0) sn = base;
     }
     __syncthreads();
     const int nd = sn;
@@ -181,25 +197,28 @@ __global__ void __launch_bounds__(MT) maps_kernel(float* __restrict__ hm, float*
         float m = 0.f;
         for (int i = 0; i < nd; ++i) {
             const int4 dr = sd[i];
-            const int dx = x - dr.x, dy = y - dr.y;
+            const win_t dx = (win_t)x - dr.x, dy = (win_t)y - dr.y;
             if (dx < -dr.z || dx > dr.z || dy < -dr.z || dy > dr.z) continue;
             // inside the window (dx^2+dy^2) / (2 sigma^2) < 9, so gaussian2D's eps cut never applies
-            const float g = (float)exp(-((double)dx * dx + (double)dy * dy) / sden[i]);
+            const double e = exp(-((double)dx * dx + (double)dy * dy) / sden[i]);
+            float g;
+            if constexpr (PEAKS) g = (float)(sk[i] * e);
+            else g = (float)e;
             m = g > m ? g : m;
         }
         return m;
     };
-    // float4 body on 16-byte aligned global addresses; the plane's misaligned head and tail (R*R % 4 != 0) go scalar
+    // float4 body on 16-byte aligned global addresses; the plane's misaligned head and tail (W*H % 4 != 0) go scalar
     const unsigned head = (unsigned)((4 - (g0 + e0) % 4) % 4);
     const unsigned a0 = e0 + head < e1 ? e0 + head : e1;
     const unsigned n4 = (e1 - a0) / 4, a1 = a0 + 4 * n4;
     if (threadIdx.x < a0 - e0) {
         const unsigned e = e0 + threadIdx.x;
-        out[e] = value((int)(e % R), (int)(e / R));
+        out[e] = value((int)(e % W), (int)(e / W));
     }
     if (threadIdx.x < e1 - a1) {
         const unsigned e = a1 + threadIdx.x;
-        out[e] = value((int)(e % R), (int)(e / R));
+        out[e] = value((int)(e % W), (int)(e / W));
     }
     if (nd == 0) {  // nothing drawn in this band (most of it at any S): zero lines only
         for (unsigned i = threadIdx.x; i < n4; i += MT)
@@ -208,11 +227,11 @@ __global__ void __launch_bounds__(MT) maps_kernel(float* __restrict__ hm, float*
     }
     for (unsigned i = threadIdx.x; i < n4; i += MT) {
         const unsigned e = a0 + 4 * i;
-        int y = (int)(e / R), x = (int)(e - (unsigned)y * R);
+        int y = (int)(e / W), x = (int)(e - (unsigned)y * W);
         float v[4];
         for (int j = 0; j < 4; ++j) {
             v[j] = value(x, y);
-            if (++x == R) x = 0, ++y;
+            if (++x == W) x = 0, ++y;
         }
         store_nt(out + e, v[0], v[1], v[2], v[3]);
     }
@@ -237,7 +256,7 @@ const char* cp_pose_targets_check(const cp_pose_targets_desc* d) {
         return "pose_targets: null pointer for an output the options turn on";
     if ((uintptr_t)d->out_hm % 16 || (d->hm_hp && (uintptr_t)d->out_hm_hp % 16))
         return "pose_targets: hm / hm_hp must be 16-byte aligned";
-    const size_t nwg = (size_t)d->B * d->S * (d->hm_hp ? NCH : 1) * (((size_t)d->R * d->R + BAND - 1) / BAND);
+    const size_t nwg = cp_gauss_maps_workgroups((size_t)d->B * d->S * (d->hm_hp ? NCH : 1), (size_t)d->R * d->R);
     if (nwg > 0x7fffffff) return "pose_targets: B * S * planes * bands exceeds the grid";
     for (int b = 0; b < d->B; ++b) {
         const double* im = d->images + (size_t)b * CP_PT_IMG_STRIDE;
@@ -265,9 +284,27 @@ const char* cp_pose_targets_check(const cp_pose_targets_desc* d) {
 
 size_t cp_pose_targets_ws_bytes(const cp_pose_targets_desc* d) {
     if (!d || d->B < 1 || d->S < 1 || d->max_objs < 1 || d->max_objs > CP_PT_MAX_OBJS) return 0;
-    return up256((size_t)d->B * CP_PT_IMG_STRIDE * sizeof(double)) +
-           up256((size_t)d->B * d->max_objs * CP_PT_OBJ_STRIDE * sizeof(double)) +
-           up256((size_t)d->B * d->S * NCH * sizeof(int)) + (size_t)d->B * d->S * NCH * d->max_objs * sizeof(int4);
+    Carve c{nullptr};
+    pose_targets_carve(c, d);
+    return c.end;  // the draw lists' own end: the ABI never rounded the last region
+}
+
+double* cp_pose_targets_ws_images(const cp_pose_targets_desc* d, void* ws) {
+    Carve c{(char*)ws};
+    return pose_targets_carve(c, d).img;
+}
+
+size_t cp_gauss_maps_workgroups(size_t planes, size_t plane_elems) { return planes * ((plane_elems + BAND - 1) / BAND); }
+
+// One workgroup per (map plane, band of BAND elements).  With peaks the lists hold up to 128 draws, without up to 64.
+void cp_launch_gauss_maps(hipStream_t s, const cp_gauss_maps_args& a) {
+    const size_t P = (size_t)a.W * a.H;
+    const int nband = (int)((P + BAND - 1) / BAND);
+    const dim3 grid((unsigned)cp_gauss_maps_workgroups((size_t)a.images * a.nch, P));
+    if (a.peaks)
+        hipLaunchKernelGGL((maps_kernel<true, 2 * CP_PT_MAX_OBJS>), grid, dim3(MT), 0, s, a, nband);
+    else
+        hipLaunchKernelGGL((maps_kernel<false, CP_PT_MAX_OBJS>), grid, dim3(MT), 0, s, a, nband);
 }
 
 int cp_launch_pose_targets(hipStream_t s, const cp_pose_targets_desc* d, void* ws) {
@@ -276,7 +313,8 @@ int cp_launch_pose_targets(hipStream_t s, const cp_pose_targets_desc* d, void* w
 
 // `tk` (device pointers, or nullptr): the tracking additions of cp_pose_targets_track (pose_targets_track.hip)
 int cp_launch_pose_targets_cur(hipStream_t s, const cp_pose_targets_desc* d, void* ws, const pose_targets::PtTrackCur* tk) {
-    const Ws w = carve(d, ws);
+    Carve c{(char*)ws};
+    const Ws w = pose_targets_carve(c, d);
     PtTrackCur t = {};
     if (tk) t = *tk;
     if (hipMemcpyAsync(w.img, d->images, (size_t)d->B * CP_PT_IMG_STRIDE * sizeof(double), hipMemcpyHostToDevice, s) !=
@@ -286,11 +324,10 @@ int cp_launch_pose_targets_cur(hipStream_t s, const cp_pose_targets_desc* d, voi
         return CP_ERR_LAUNCH;
     hipLaunchKernelGGL(objects_kernel, dim3(d->B * d->S), dim3(64), 0, s, *d, (const double*)w.img,
                        (const double*)w.obj, w.counts, w.draws, t);
-    const int nch = d->hm_hp ? NCH : 1;
-    const size_t P = (size_t)d->R * d->R;
-    const int nband = (int)((P + BAND - 1) / BAND);
-    const size_t nwg = (size_t)d->B * d->S * nch * nband;
-    hipLaunchKernelGGL(maps_kernel, dim3((unsigned)nwg), dim3(MT), 0, s, d->out_hm, d->hm_hp ? d->out_hm_hp : nullptr, d->R,
-                       d->max_objs, nch, nband, (const int*)w.counts, (const int4*)w.draws);
+    cp_gauss_maps_args a = {};
+    a.out0 = d->out_hm, a.outj = d->hm_hp ? d->out_hm_hp : nullptr;
+    a.W = a.H = d->R, a.images = d->B * d->S, a.nch = d->hm_hp ? NCH : 1, a.ch0 = 0, a.stride = d->max_objs;
+    a.counts = w.counts, a.draws = w.draws, a.peaks = nullptr;
+    cp_launch_gauss_maps(s, a);
     return hipGetLastError() == hipSuccess ? CP_OK : CP_ERR_LAUNCH;
 }

@@ -285,6 +285,16 @@ PT_HD void ptk_pre_object(const double* img, const double* pre, int S, const Ptk
 }
 
 #ifdef __HIPCC__
+// What the previous-objects kernels pass to ptk_pre_object as `img`: image b's current record with the previous frame's
+// affine and projection matrix in it, into im[CP_PT_IMG_STRIDE].  Returns the image's count of previous objects.
+__device__ __forceinline__ int ptk_pre_image(const double* __restrict__ img, const double* __restrict__ timg, int b, double* im) {
+    const double* ti = timg + (size_t)b * CP_PTK_IMG_STRIDE;
+    for (int i = 0; i < CP_PT_IMG_STRIDE; ++i) im[i] = img[(size_t)b * CP_PT_IMG_STRIDE + i];
+    for (int i = 0; i < 6; ++i) im[CP_PT_IMG_TRANS + i] = ti[CP_PTK_IMG_TRANS + i];
+    for (int i = 0; i < 16; ++i) im[CP_PT_IMG_PROJ + i] = ti[CP_PTK_IMG_PROJ + i];
+    return (int)ti[CP_PTK_IMG_NUM_PRE];
+}
+
 // One wavefront, lane k = previous object k of image b: compacts the Gaussians to draw, per channel, into the image's
 // lists as (x, y, r, 0) and a peak, with ballots in object order, an object's own draws before the false positives; a
 // draw with k == 0 adds nothing to a map of non-negative values and is dropped.  Every lane of the wavefront calls it.

@@ -11,7 +11,8 @@
 //                               the match record.  No atomics; the order of every choice is the reference's.
 //   2. pre_objects_det_kernel   pose_targets_track.hip's pre_objects_kernel with ptk_pre_object_det for the mode-1 images;
 //                               a mode-0 image runs ptk_pre_object, the same code as there.
-//   3. cp_ptk_finish            the current frame's kernels and pre_maps_kernel, unchanged.
+//   3. cp_ptk_finish            the current frame's kernels and the map writer (pose_targets.hip's maps_kernel), unchanged.
+// The workspace is described once, in ptkd_carve (Carve, cp_common.h); it begins with cp_pose_targets_track's own.
 #include "../../include/centerpose_hip.h"
 #include "cp_common.h"
 #include "pose_targets_track_det_common.h"
@@ -23,26 +24,18 @@ using namespace pose_targets;
 
 namespace {
 
-inline size_t up256(size_t x) { return (x + 255) / 256 * 256; }
-
 struct DetWs {
     void* track;    // cp_pose_targets_track's own workspace
     double* gen;    // [B][CP_PTKD_GEN_STRIDE]
     double* match;  // [B][Kp][PTKD_STRIDE]
-    size_t bytes;
 };
 
-DetWs carve(const cp_pose_targets_track_det_desc* d, void* ws) {
-    char* p = (char*)ws;
+DetWs ptkd_carve(Carve& c, const cp_pose_targets_track_det_desc* d) {
     const size_t B = d->track.cur.B, Kp = d->track.max_pre_objs;
     DetWs w;
-    w.track = p;
-    p += up256(cp_pose_targets_track_ws_bytes(&d->track));
-    w.gen = (double*)p;
-    p += up256(B * CP_PTKD_GEN_STRIDE * sizeof(double));
-    w.match = (double*)p;
-    p += up256(B * Kp * PTKD_STRIDE * sizeof(double));
-    w.bytes = (size_t)(p - (char*)ws);
+    w.track = c.take<char>(cp_pose_targets_track_ws_bytes(&d->track));
+    w.gen = c.take<double>(B * CP_PTKD_GEN_STRIDE * sizeof(double));
+    w.match = c.take<double>(B * Kp * PTKD_STRIDE * sizeof(double));
     return w;
 }
 
@@ -99,13 +92,8 @@ __global__ void __launch_bounds__(64) pre_objects_det_kernel(const PtkOpts op, c
                                                              int* __restrict__ counts, int4* __restrict__ draws,
                                                              double* __restrict__ peaks) {
     const int b = blockIdx.x, k = threadIdx.x;
-    const double* ti = timg + (size_t)b * CP_PTK_IMG_STRIDE;
-    // the current image's record with the previous frame's affine and projection matrix in it
     double im[CP_PT_IMG_STRIDE];
-    for (int i = 0; i < CP_PT_IMG_STRIDE; ++i) im[i] = img[(size_t)b * CP_PT_IMG_STRIDE + i];
-    for (int i = 0; i < 6; ++i) im[CP_PT_IMG_TRANS + i] = ti[CP_PTK_IMG_TRANS + i];
-    for (int i = 0; i < 16; ++i) im[CP_PT_IMG_PROJ + i] = ti[CP_PTK_IMG_PROJ + i];
-    const int npre = (int)ti[CP_PTK_IMG_NUM_PRE];
+    const int npre = ptk_pre_image(img, timg, b, im);
     const double* gb = gen + (size_t)b * CP_PTKD_GEN_STRIDE;
     PtkPre r;
     for (int c = 0; c < 1 + CP_PT_JOINTS; ++c) r.draw_on[c][0] = r.draw_on[c][1] = 0;
@@ -150,11 +138,14 @@ const char* cp_pose_targets_track_det_check(const cp_pose_targets_track_det_desc
 
 size_t cp_pose_targets_track_det_ws_bytes(const cp_pose_targets_track_det_desc* d) {
     if (!d || !cp_pose_targets_track_ws_bytes(&d->track)) return 0;
-    return carve(d, nullptr).bytes;
+    Carve c{nullptr};
+    ptkd_carve(c, d);
+    return c.off;
 }
 
 int cp_launch_pose_targets_track_det(hipStream_t s, const cp_pose_targets_track_det_desc* d, void* ws) {
-    const DetWs w = carve(d, ws);
+    Carve c{(char*)ws};
+    const DetWs w = ptkd_carve(c, d);
     const cp_pose_targets_track_desc* t = &d->track;
     const size_t B = t->cur.B;
     cp_ptk_ws_view v;

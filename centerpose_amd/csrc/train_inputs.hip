@@ -33,24 +33,22 @@ constexpr int SLAB = TT * PPT;  // pixels per workgroup
 
 typedef float ti_f4 __attribute__((ext_vector_type(4)));
 
-inline size_t up256(size_t x) { return (x + 255) / 256 * 256; }
-
 struct Ws {
     double* rec;      // [N][CP_TI_STRIDE], the caller's records
     float* means;     // [N] gs_mean (0: no colour), at CP_TI_WS_MEANS(N)
     double* partial;  // [N][nslab] grey sums per slab
 };
 
-Ws carve(int N, void* ws) {
-    char* p = (char*)ws;
+// the public header's CP_TI_WS_MEANS(N) restates where `means` lands: right after the records, rounded up to 256 bytes
+Ws train_inputs_carve(Carve& c, size_t N, size_t nslab) {
     Ws w;
-    w.rec = (double*)p;
-    p += CP_TI_WS_MEANS(N);
-    w.means = (float*)p;
-    p += up256((size_t)N * sizeof(float));
-    w.partial = (double*)p;
+    w.rec = c.take<double>(N * CP_TI_STRIDE * sizeof(double));
+    w.means = c.take<float>(N * sizeof(float));
+    w.partial = c.take<double>(N * nslab * sizeof(double));
     return w;
 }
+
+inline size_t slabs(int out_h, int out_w) { return ((size_t)out_h * out_w + SLAB - 1) / SLAB; }
 
 struct TiArgs {
     const unsigned char* frames;
@@ -184,20 +182,23 @@ size_t cp_train_inputs_ws_bytes(int N, int out_h, int out_w) {
     if (N < 1 || out_h < 1 || out_w < 1) return 0;
     const size_t P = (size_t)out_h * out_w;
     if (P > 0x7fffffffull - SLAB) return 0;
-    const size_t nslab = (P + SLAB - 1) / SLAB;
+    const size_t nslab = slabs(out_h, out_w);
     if ((size_t)N * nslab > 0x7fffffffull) return 0;
-    return CP_TI_WS_MEANS(N) + up256((size_t)N * sizeof(float)) + (size_t)N * nslab * sizeof(double);
+    Carve c{nullptr};
+    train_inputs_carve(c, N, nslab);
+    return c.end;  // the slab sums' own end: the ABI never rounded the last region
 }
 
 int cp_launch_train_inputs(hipStream_t s, const unsigned char* frames, const double* records, int N, const float* mean3,
                            const float* std3, float* out, int out_h, int out_w, void* ws) {
-    const Ws w = carve(N, ws);
+    Carve c{(char*)ws};
+    const Ws w = train_inputs_carve(c, N, slabs(out_h, out_w));
     if (hipMemcpyAsync(w.rec, records, (size_t)N * CP_TI_STRIDE * sizeof(double), hipMemcpyHostToDevice, s) != hipSuccess)
         return CP_ERR_LAUNCH;
     TiArgs a;
     a.frames = frames, a.rec = w.rec, a.out = out, a.OW = out_w;
     a.P = (unsigned)((size_t)out_h * out_w);
-    a.nslab = (int)((a.P + SLAB - 1) / SLAB);
+    a.nslab = (int)slabs(out_h, out_w);
     for (int c = 0; c < 3; ++c) a.mean[c] = mean3[c], a.std[c] = std3[c];
     a.means = w.means, a.partial = w.partial;
     // the grey pass, once per run of consecutive colour images (a training batch is one run, or none)

@@ -7,7 +7,7 @@ import pytest
 import torch
 
 from centerpose_amd.pose_loss import ObjectPoseLoss
-from centerpose_amd.pose_targets import PoseTargets, num_symmetry, target_keys
+from centerpose_amd.pose_targets import PoseTargets, num_symmetry, pack_annotations, target_keys
 from tests import pose_loss_cases as PLC
 from tests import pose_target_cases as PC
 from tests import pose_targets_ref as R
@@ -68,6 +68,33 @@ def test_device_equals_restatement(device, S, Rr):
               % (S, Rr, center_3D, differ, int(ref["reg_mask"].sum())))
         assert differ == 0
         assert ref["reg_mask"].sum() > B  # the batch is not empty
+
+
+def test_full_draw_list(device):
+    """max_objs = 64 and an image that keeps all 64 objects: its hm plane's draw list holds 64 entries, the capacity of
+    the map writer's plain form.  R = 75: odd planes, every plane after the first off a 16-byte boundary."""
+    S, Rr, K, cat = 4, 75, 64, "chair"
+    opt = PC.make_opt(dict(c=cat, num_symmetry=S, output_res=Rr, hps_uncertainty=True))
+    rng = np.random.default_rng(64)
+    imgs, objs = [], []
+    for b, (w, h) in enumerate(((640, 480), (480, 640))):
+        syms = ["True", "False"] if b else ["True"]  # image 0: every object in every variant
+        anns = PC.synth_annotations(rng, [(syms[k % len(syms)], "pose") for k in range(K)], w, h)
+        s = Rr / max(w, h)  # the whole image lands inside the map: no object leaves it
+        t = np.array([[s, 0, (Rr - s * w) / 2], [0, s, (Rr - s * h) / 2]])
+        rec = pack_annotations(anns, t, w, h, bool(b), 0.0, opt, max_objs=K)
+        imgs.append(rec["pt_image"])
+        objs.append(rec["pt_objects"])
+    imgs, objs = np.stack(imgs), np.stack(objs)
+    ref = R.batch_targets(imgs, objs, S, Rr)
+    kept = ref["reg_mask"].sum(axis=2)  # [B, S]
+    print("objects kept per (image, variant):", kept.tolist())
+    assert kept.max() == K and (kept[0] == K).all()
+    out = PoseTargets(opt, max_objs=K)({"pt_image": torch.from_numpy(imgs), "pt_objects": torch.from_numpy(objs)})
+    torch.cuda.synchronize()
+    differ = _compare(out, ref, target_keys(opt), "64 draws")
+    print("64 draws: %d map elements not bit-identical" % differ)
+    assert differ == 0
 
 
 def test_two_streams_bitwise(device):
