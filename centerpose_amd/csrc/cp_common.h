@@ -391,6 +391,8 @@ int cp_launch_add_relu_sum(const float* a, const float* b, const float* c, const
 // hourglass merge: out[B,2H,2W,C] = up1 + nearest-x2(low[B,H,W,C])  (large_hourglass.py:186-188)
 int cp_launch_upsample2_nearest_add(const float* up1, const float* low, float* out, int B, int H, int W, int C,
                                     unsigned* out_amax, hipStream_t s);
+// its gradient with respect to low: grad_low[B,H,W,C] = the four grad_out[B,2H,2W,C] elements of each 2x2 cell, in a fixed order
+int cp_launch_upsample2_nearest_add_backward(const float* grad_out, float* grad_low, int B, int H, int W, int C, hipStream_t s);
 // ConvGRU gates (convGRU.py:32-39).  x3/h3: [M,192] = (r,z,n) pre-activations, h: [M,64]
 int cp_launch_gru_gate(const float* x3, const float* h3, const float* hprev, float* hout, size_t M, unsigned* out_amax,
                        hipStream_t s);
@@ -597,7 +599,8 @@ struct StemBwdArgs {
     float *gw, *gb;           // gb nullptr: not stored
     int B, H, W, Cin, Cout, stride;
 };
-const char* cp_stem_backward_shape_error(int B, int H, int W, int Cin, int Cout, int stride);  // nullptr: accepted
+// wide: Cout up to 128 (cp_conv2d_stem_wide_backward); otherwise up to 64 (cp_conv2d_stem_backward)
+const char* cp_stem_backward_shape_error(int B, int H, int W, int Cin, int Cout, int stride, bool wide = false);  // nullptr: accepted
 size_t cp_stem_backward_ws_bytes(int B, int H, int W, int Cin, int Cout, int stride);
 int cp_launch_stem_backward(hipStream_t s, const StemBwdArgs& a, void* ws);
 

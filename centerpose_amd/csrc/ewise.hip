@@ -556,6 +556,28 @@ __global__ void upsample2_nearest_add_kernel(const float* __restrict__ up1, cons
     if (out_amax) cp_amax_commit(out_amax, amax);
 }
 
+// Gradient of the merge with respect to low: grad_low[b,y,x] = (g[2y,2x] + g[2y,2x+1]) + (g[2y+1,2x] + g[2y+1,2x+1]), in that
+// order (bitwise reproducible; exact on dyadic data).  The forward's thread map on grad_low: one float4 per lane, channels
+// fastest, then x, so a lane's two reads of a row and its neighbours' cover whole 128-byte lines of g from C >= 32 on; every row
+// of g is read once.  g: [B, 2H, 2W, C], grad_low: [B, H, W, C].  (The gradient with respect to up1 is g itself.)
+__global__ void upsample2_nearest_add_bwd_kernel(const float* __restrict__ g, float* __restrict__ grad_low, int B, int H, int W,
+                                                 int C4) {
+    const size_t total = (size_t)B * H * W * C4;
+    const float4* g4 = reinterpret_cast<const float4*>(g);
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int c = (int)(i % C4);
+        size_t r = i / C4;
+        const int x = (int)(r % W);
+        r /= W;
+        const int y = (int)(r % H);
+        const size_t b = r / H;
+        const size_t top = ((b * 2 * H + 2 * y) * 2 * W + 2 * x) * C4 + c, bot = top + (size_t)2 * W * C4;
+        const float4 p = g4[top], q = g4[top + C4], u = g4[bot], v = g4[bot + C4];
+        reinterpret_cast<float4*>(grad_low)[i] = make_float4((p.x + q.x) + (u.x + v.x), (p.y + q.y) + (u.y + v.y),
+                                                             (p.z + q.z) + (u.z + v.z), (p.w + q.w) + (u.w + v.w));
+    }
+}
+
 inline int check() { return hipGetLastError() == hipSuccess ? CP_OK : CP_ERR_LAUNCH; }
 
 }  // namespace
@@ -615,6 +637,13 @@ int cp_launch_upsample2_nearest_add(const float* up1, const float* low, float* o
     if (C % 4) return CP_ERR_INVALID;
     hipLaunchKernelGGL(upsample2_nearest_add_kernel, dim3(grid_for((size_t)B * 4 * H * W * (C / 4))), dim3(TPB), 0, s, up1,
                        low, out, B, H, W, C / 4, out_amax);
+    return check();
+}
+
+int cp_launch_upsample2_nearest_add_backward(const float* grad_out, float* grad_low, int B, int H, int W, int C, hipStream_t s) {
+    if (C % 4) return CP_ERR_INVALID;
+    hipLaunchKernelGGL(upsample2_nearest_add_bwd_kernel, dim3(grid_for((size_t)B * H * W * (C / 4))), dim3(TPB), 0, s, grad_out,
+                       grad_low, B, H, W, C / 4);
     return check();
 }
 

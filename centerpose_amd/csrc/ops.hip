@@ -1,7 +1,8 @@
 // The stand-alone operators of the C ABI (include/centerpose_hip.h): single layers on caller tensors, outside any cp_model
 // -- cp_conv2d_nhwc / cp_conv2d_backward_nhwc, cp_batchnorm_forward_nhwc / _backward_nhwc, cp_conv_transpose2d_nhwc,
 // cp_conv_transpose2d_dw_nhwc / cp_conv_transpose2d_backward_nhwc, cp_dcnv2_forward / cp_dcnv2_backward / cp_dcnv2_backward_det, cp_pose_heads_forward / _backward,
-// cp_maxpool2d_forward_nhwc / _backward_nhwc, cp_conv2d_stem_backward, cp_groupnorm_forward_nhwc / _backward_nhwc,
+// cp_maxpool2d_forward_nhwc / _backward_nhwc, cp_upsample2_add_nhwc / cp_upsample2_add_backward_nhwc (large_hourglass.py:95-112),
+// cp_conv2d_stem_backward / cp_conv2d_stem_wide_backward, cp_groupnorm_forward_nhwc / _backward_nhwc,
 // cp_gru_gate_forward / _backward, cp_adam_table_bytes / _table_build / _step.
 // Each packs its PyTorch-layout weights into a caller-provided workspace on every call and then launches the same kernels as
 // the engine.
@@ -656,25 +657,75 @@ int cp_maxpool2d_backward_nhwc(cp_stream_t stream, const float* x, const float* 
     return rc == CP_OK ? CP_OK : fail(rc, "maxpool2d_backward: kernel launch failed");
 }
 
+// The hourglass merge up1 + nearest2x(low), forward and backward (ewise.hip)
+static const char* upsample2_shape_error(int B, int H, int W, int C) {
+    if (B < 1 || H < 1 || W < 1) return "upsample2_add: B, H and W must be at least 1";
+    if (C < 4 || C % 4) return "upsample2_add: C must be a positive multiple of 4";
+    const long long lim = 0x7fffffffLL;  // of the [B,2H,2W,C] tensors; every partial product below stays under 2^62
+    long long n = 4LL * B;
+    if (n >= lim || (n *= H) >= lim || (n *= W) >= lim || (n *= C) >= lim) return "upsample2_add: a tensor has 2^31 elements or more";
+    return nullptr;
+}
+
+int cp_upsample2_add_nhwc(cp_stream_t stream, const float* up1, const float* low, float* out, int B, int H, int W, int C) {
+    if (const char* e = upsample2_shape_error(B, H, W, C)) return fail(CP_ERR_INVALID, e);
+    if (!up1 || !low || !out) return fail(CP_ERR_INVALID, "upsample2_add: null argument");
+    if (!bn_aligned({up1, low, out})) return fail(CP_ERR_INVALID, "upsample2_add: tensors must be 16-byte aligned");
+    const int rc = cp_launch_upsample2_nearest_add(up1, low, out, B, H, W, C, nullptr, (hipStream_t)stream);
+    return rc == CP_OK ? CP_OK : fail(rc, "upsample2_add: kernel launch failed");
+}
+
+int cp_upsample2_add_backward_nhwc(cp_stream_t stream, const float* grad_out, float* grad_low, int B, int H, int W, int C) {
+    if (const char* e = upsample2_shape_error(B, H, W, C)) return fail(CP_ERR_INVALID, e);
+    if (!grad_out || !grad_low) return fail(CP_ERR_INVALID, "upsample2_add_backward: null argument");
+    if (!bn_aligned({grad_out, grad_low})) return fail(CP_ERR_INVALID, "upsample2_add_backward: tensors must be 16-byte aligned");
+    const int rc = cp_launch_upsample2_nearest_add_backward(grad_out, grad_low, B, H, W, C, (hipStream_t)stream);
+    return rc == CP_OK ? CP_OK : fail(rc, "upsample2_add_backward: kernel launch failed");
+}
+
 // The image stems' weight / bias gradient (stem_bwd.hip)
-size_t cp_conv2d_stem_backward_workspace_bytes(int B, int H, int W, int Cin, int Cout, int stride) {
-    if (const char* e = cp_stem_backward_shape_error(B, H, W, Cin, Cout, stride)) {
+// Two pairs of entry points over one launcher: the narrow pair keeps its range (Cout up to 64), the wide pair takes Cout up
+// to 128, the hourglass's stem, which the launcher splits into channel blocks
+static size_t stem_backward_query(bool wide, int B, int H, int W, int Cin, int Cout, int stride) {
+    if (const char* e = cp_stem_backward_shape_error(B, H, W, Cin, Cout, stride, wide)) {
         fail(CP_ERR_INVALID, e);
         return 0;
     }
     return cp_stem_backward_ws_bytes(B, H, W, Cin, Cout, stride);
 }
 
-int cp_conv2d_stem_backward(cp_stream_t stream, const float* x_nchw, const float* grad_out_nhwc, const float* y_or_null,
-                            float* grad_w, float* grad_bias_or_null, void* workspace, size_t workspace_bytes, int B, int H, int W,
-                            int Cin, int Cout, int stride) {
-    if (const char* e = cp_stem_backward_shape_error(B, H, W, Cin, Cout, stride)) return fail(CP_ERR_INVALID, e);
+static int stem_backward_run(bool wide, cp_stream_t stream, const float* x_nchw, const float* grad_out_nhwc, const float* y_or_null,
+                             float* grad_w, float* grad_bias_or_null, void* workspace, size_t workspace_bytes, int B, int H, int W,
+                             int Cin, int Cout, int stride) {
+    if (const char* e = cp_stem_backward_shape_error(B, H, W, Cin, Cout, stride, wide)) return fail(CP_ERR_INVALID, e);
     if (!x_nchw || !grad_out_nhwc || !grad_w || !workspace) return fail(CP_ERR_INVALID, "conv2d_stem_backward: null argument");
     if (workspace_bytes < cp_stem_backward_ws_bytes(B, H, W, Cin, Cout, stride))
         return fail(CP_ERR_INVALID, "conv2d_stem_backward: workspace too small");
     const StemBwdArgs a{x_nchw, grad_out_nhwc, y_or_null, grad_w, grad_bias_or_null, B, H, W, Cin, Cout, stride};
     const int rc = cp_launch_stem_backward((hipStream_t)stream, a, workspace);
     return rc == CP_OK ? CP_OK : fail(rc, "conv2d_stem_backward: kernel launch failed");
+}
+
+size_t cp_conv2d_stem_backward_workspace_bytes(int B, int H, int W, int Cin, int Cout, int stride) {
+    return stem_backward_query(false, B, H, W, Cin, Cout, stride);
+}
+
+int cp_conv2d_stem_backward(cp_stream_t stream, const float* x_nchw, const float* grad_out_nhwc, const float* y_or_null,
+                            float* grad_w, float* grad_bias_or_null, void* workspace, size_t workspace_bytes, int B, int H, int W,
+                            int Cin, int Cout, int stride) {
+    return stem_backward_run(false, stream, x_nchw, grad_out_nhwc, y_or_null, grad_w, grad_bias_or_null, workspace, workspace_bytes,
+                             B, H, W, Cin, Cout, stride);
+}
+
+size_t cp_conv2d_stem_wide_backward_workspace_bytes(int B, int H, int W, int Cin, int Cout, int stride) {
+    return stem_backward_query(true, B, H, W, Cin, Cout, stride);
+}
+
+int cp_conv2d_stem_wide_backward(cp_stream_t stream, const float* x_nchw, const float* grad_out_nhwc, const float* y_or_null,
+                                 float* grad_w, float* grad_bias_or_null, void* workspace, size_t workspace_bytes, int B, int H,
+                                 int W, int Cin, int Cout, int stride) {
+    return stem_backward_run(true, stream, x_nchw, grad_out_nhwc, y_or_null, grad_w, grad_bias_or_null, workspace, workspace_bytes,
+                             B, H, W, Cin, Cout, stride);
 }
 
 size_t cp_dcnv2_backward_workspace_bytes(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw,

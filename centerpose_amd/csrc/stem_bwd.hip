@@ -15,6 +15,10 @@
 //     before the first MFMA of the chunk; pixels past the image's edge are clamped addresses and zeros.
 //   * Tap column 49 Cin reads a constant 1 instead of the patch, so D[co][49 Cin] is the bias gradient's partial sum.
 //   * The four waves' accumulators are added in LDS in wave order and stored as the workgroup's slab [Cout][49 Cin + 1].
+//   * Cout above 64 (the hourglass's 3 -> 128 stem, large_hourglass.py:210) is split into channel blocks of at most 64, the
+//     grid's second dimension: a block reads grad_out and y with the layer's Cout as the pixel stride, stages the same patch
+//     once more (cheap next to the reads of grad_out) and writes its own rows of the slab.  One 128-wide instantiation would
+//     hold 320 accumulator registers.  Up to 64 channels there is one block, and the arithmetic is what it was.
 // stem_reduce_kernel sums the slabs with op_common.h's two_level_sum into grad_w (PyTorch layout) and grad_bias.  No atomics:
 // every sum has an order fixed by the shape, so the results are bitwise reproducible.
 #include "op_common.h"
@@ -48,8 +52,11 @@ StemPlan stem_plan(int B, int H, int W, int stride) {
 template <int CIN, int NCO>
 __global__ __launch_bounds__(256) void stem_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ go,
                                                          const float* __restrict__ y, float* __restrict__ slab, int H, int W, int Ho,
-                                                         int Wo, int stride, int tiles_y, int tiles_x, int tiles, int tiles_per_wg) {
+                                                         int Wo, int stride, int tiles_y, int tiles_x, int tiles, int tiles_per_wg,
+                                                         int CT, int co_base) {
+    // Cout: this workgroup's block of output channels, co0 .. co0 + Cout of the layer's CT (the pixel stride of go and y)
     constexpr int NT = CIN * 49, NS = NT + 1, NTT = (NS + 15) / 16, Cout = NCO * 16, U = 4;
+    const int co0 = co_base + blockIdx.y * Cout;
     __shared__ float lds[LDS_FLOATS];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, kq = lane >> 4;
     const int IR = (TR - 1) * stride + 7, IC = (TCW - 1) * stride + 7, LW = IC | 1, ONE = CIN * IR * LW;
@@ -93,7 +100,7 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const float* __restrict
                 const int q = wave + 4 * (j0 + u), ry = q >> 4, cx = ((q & 15) << 2) + kq;
                 const int oy = oy0 + ry, ox = ox0 + cx;
                 const bool ok = oy < Ho && ox < Wo;
-                const size_t p = (((size_t)b * Ho + (ok ? oy : 0)) * Wo + (ok ? ox : 0)) * Cout + r;
+                const size_t p = (((size_t)b * Ho + (ok ? oy : 0)) * Wo + (ok ? ox : 0)) * CT + co0 + r;
                 poff[u] = ry * stride * LW + cx * stride;
 #pragma unroll
                 for (int ct = 0; ct < NCO; ++ct) {
@@ -130,7 +137,7 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const float* __restrict
         }
     }
     __syncthreads();
-    float* out = slab + (size_t)blockIdx.x * Cout * NS;
+    float* out = slab + ((size_t)blockIdx.x * CT + co0) * NS;
     for (int i = threadIdx.x; i < Cout * NS; i += 256) out[i] = lds[i];
 }
 
@@ -152,23 +159,27 @@ __global__ __launch_bounds__(256) void stem_reduce_kernel(const float* __restric
 }
 
 template <int CIN>
-void launch_wgrad(hipStream_t s, int nco, const StemBwdArgs& a, const StemPlan& P, float* slab) {
-#define CP_STEM_LAUNCH(NCO)                                                                                                         \
-    hipLaunchKernelGGL((stem_wgrad_kernel<CIN, NCO>), dim3(P.slabs), dim3(256), 0, s, a.x, a.go, a.y, slab, a.H, a.W, P.Ho, P.Wo, \
-                       a.stride, P.tiles_y, P.tiles_x, P.tiles, P.tiles_per_wg)
-    if (nco == 1) CP_STEM_LAUNCH(1);
-    else if (nco == 2) CP_STEM_LAUNCH(2);
-    else if (nco == 3) CP_STEM_LAUNCH(3);
-    else CP_STEM_LAUNCH(4);
+void launch_wgrad(hipStream_t s, const StemBwdArgs& a, const StemPlan& P, float* slab) {
+    // channel blocks of at most 64 (NCO <= 4: the accumulators' register budget): the full blocks as the grid's second dimension,
+    // then the ragged one.  Every block writes its own rows of the slabs, so the order of the launches does not matter.
+    const int full = a.Cout / 64, rest = a.Cout % 64 / 16;
+#define CP_STEM_LAUNCH(NCO, BLOCKS, BASE)                                                                                     \
+    hipLaunchKernelGGL((stem_wgrad_kernel<CIN, NCO>), dim3(P.slabs, BLOCKS), dim3(256), 0, s, a.x, a.go, a.y, slab, a.H, a.W, \
+                       P.Ho, P.Wo, a.stride, P.tiles_y, P.tiles_x, P.tiles, P.tiles_per_wg, a.Cout, BASE)
+    if (full) CP_STEM_LAUNCH(4, full, 0);
+    if (rest == 1) CP_STEM_LAUNCH(1, 1, full * 64);
+    else if (rest == 2) CP_STEM_LAUNCH(2, 1, full * 64);
+    else if (rest == 3) CP_STEM_LAUNCH(3, 1, full * 64);
 #undef CP_STEM_LAUNCH
 }
 
 }  // namespace
 
-const char* cp_stem_backward_shape_error(int B, int H, int W, int Cin, int Cout, int stride) {
+const char* cp_stem_backward_shape_error(int B, int H, int W, int Cin, int Cout, int stride, bool wide) {
     if (B < 1 || H < 1 || W < 1) return "conv2d_stem_backward: B, H and W must be at least 1";
     if (Cin < 1 || Cin > 3) return "conv2d_stem_backward: Cin must be 1, 2 or 3 (wider inputs take cp_conv2d_backward_nhwc)";
-    if (Cout < 16 || Cout > 64 || Cout % 16) return "conv2d_stem_backward: Cout must be 16, 32, 48 or 64";
+    if (wide && (Cout < 16 || Cout > 128 || Cout % 16)) return "conv2d_stem_backward: Cout must be a multiple of 16 from 16 to 128";
+    if (!wide && (Cout < 16 || Cout > 64 || Cout % 16)) return "conv2d_stem_backward: Cout must be 16, 32, 48 or 64";
     if (stride != 1 && stride != 2) return "conv2d_stem_backward: stride must be 1 or 2";
     const long long ho = (H - 1) / stride + 1, wo = (W - 1) / stride + 1, lim = 0x7fffffffLL;
     if ((long long)B * Cin * H * W >= lim || (long long)B * ho * wo * Cout >= lim)
@@ -186,9 +197,9 @@ int cp_launch_stem_backward(hipStream_t s, const StemBwdArgs& a, void* ws) {
     const StemPlan P = stem_plan(a.B, a.H, a.W, a.stride);
     Carve c{(char*)ws};
     float* slab = c.take<float>((size_t)P.slabs * a.Cout * (49 * a.Cin + 1) * sizeof(float));
-    if (a.Cin == 1) launch_wgrad<1>(s, a.Cout / 16, a, P, slab);
-    else if (a.Cin == 2) launch_wgrad<2>(s, a.Cout / 16, a, P, slab);
-    else launch_wgrad<3>(s, a.Cout / 16, a, P, slab);
+    if (a.Cin == 1) launch_wgrad<1>(s, a, P, slab);
+    else if (a.Cin == 2) launch_wgrad<2>(s, a, P, slab);
+    else launch_wgrad<3>(s, a, P, slab);
     if (!launch_ok()) return CP_ERR_LAUNCH;
     const int n = a.Cout * (49 * a.Cin + 1);
     hipLaunchKernelGGL(stem_reduce_kernel, dim3((n + 31) / 32), dim3(256), 0, s, slab, a.gw, a.gb, P.slabs, a.Cout, 49 * a.Cin);

@@ -75,6 +75,10 @@ SIGNATURES = {
     "cp_maxpool2d_backward_nhwc": (c_int, _vp * 4 + _i * 7),
     "cp_conv2d_stem_backward_workspace_bytes": (c_size_t, _i * 6),
     "cp_conv2d_stem_backward": (c_int, _vp * 7 + [c_size_t] + _i * 6),
+    "cp_conv2d_stem_wide_backward_workspace_bytes": (c_size_t, _i * 6),
+    "cp_conv2d_stem_wide_backward": (c_int, _vp * 7 + [c_size_t] + _i * 6),
+    "cp_upsample2_add_nhwc": (c_int, _vp * 4 + _i * 4),
+    "cp_upsample2_add_backward_nhwc": (c_int, _vp * 3 + _i * 4),
     "cp_decode_workspace_bytes": (c_size_t, _i * 2),
     "cp_decode": (c_int, _vp + _i * 3 + _vp * 11 + _i * 3 + [c_float] + _i * 2 + _vp + _ws),
     "cp_decode_tiled_workspace_bytes": (c_size_t, _i * 4),

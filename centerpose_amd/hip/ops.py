@@ -490,12 +490,44 @@ def conv2d_stem_backward(x, grad_out, stride=1, y=None, need_bias_grad=True):
                            % (tuple(x.shape), tuple(grad_out.shape)))
     B, Cin, H, W = x.shape
     Cout, stride = grad_out.shape[3], int(stride)
-    ws = _abi._workspace(L.cp_conv2d_stem_backward_workspace_bytes(B, H, W, Cin, Cout, stride), x.device, "conv2d_stem_backward")
+    # above 64 channels the pair that runs the same kernels over channel blocks (the hourglass's 3 -> 128 stem)
+    query, launch = ((L.cp_conv2d_stem_backward_workspace_bytes, L.cp_conv2d_stem_backward) if Cout <= 64 else
+                     (L.cp_conv2d_stem_wide_backward_workspace_bytes, L.cp_conv2d_stem_wide_backward))
+    ws = _abi._workspace(query(B, H, W, Cin, Cout, stride), x.device, "conv2d_stem_backward")
     want = (B, (H - 1) // stride + 1, (W - 1) // stride + 1, Cout)
     _abi._check_shapes("conv2d_stem_backward", (("grad_out", grad_out, want), ("y", y, want)))
     grad_w = torch.empty(Cout, Cin, 7, 7, device=x.device, dtype=torch.float32)
     grad_b = torch.empty(Cout, device=x.device, dtype=torch.float32) if need_bias_grad else None
-    rc = L.cp_conv2d_stem_backward(_abi._stream(), *_abi._ptrs(x, grad_out, y, grad_w, grad_b, ws), ws.numel(),
-                                   B, H, W, Cin, Cout, stride)
+    rc = launch(_abi._stream(), *_abi._ptrs(x, grad_out, y, grad_w, grad_b, ws), ws.numel(), B, H, W, Cin, Cout, stride)
     _abi._check(rc, "cp_conv2d_stem_backward")
     return grad_w, grad_b
+
+
+def _upsample2_args(what, low, big, big_name):
+    if low.dim() != 4 or big.dim() != 4:
+        raise RuntimeError("%s: low must be [B,H,W,C] and %s [B,2H,2W,C], got %s and %s"
+                           % (what, big_name, tuple(low.shape), tuple(big.shape)))
+    B, H, W, C = low.shape
+    _abi._check_shapes(what, [(big_name, big, (B, 2 * H, 2 * W, C))])
+    return B, H, W, C
+
+
+def upsample2_add_forward(up1, low):
+    """The hourglass merge on NHWC tensors (cp_upsample2_add_nhwc): up1 [B,2H,2W,C] + nearest2x(low [B,H,W,C]) -> [B,2H,2W,C];
+    C % 4 == 0."""
+    up1, low = _abi._dev(up1), _abi._dev(low)
+    geo = _upsample2_args("upsample2_add", low, up1, "up1")
+    out = torch.empty_like(up1)
+    _abi._check_args(_abi.lib().cp_upsample2_add_nhwc(_abi._stream(), *_abi._ptrs(up1, low, out), *geo), "cp_upsample2_add_nhwc")
+    return out
+
+
+def upsample2_add_backward(grad_out, low_shape):
+    """Gradient of upsample2_add_forward with respect to ``low`` (cp_upsample2_add_backward_nhwc): grad_out [B,2H,2W,C] ->
+    grad_low [B,H,W,C], each 2x2 cell added in a fixed order (bitwise reproducible).  The gradient of ``up1`` is grad_out."""
+    grad_out = _abi._dev(grad_out)
+    grad_low = torch.empty(tuple(low_shape), device=grad_out.device, dtype=torch.float32)
+    geo = _upsample2_args("upsample2_add_backward", grad_low, grad_out, "grad_out")
+    _abi._check_args(_abi.lib().cp_upsample2_add_backward_nhwc(_abi._stream(), *_abi._ptrs(grad_out, grad_low), *geo),
+                     "cp_upsample2_add_backward_nhwc")
+    return grad_low

@@ -220,8 +220,9 @@ class DLAUp(nn.Module):
 _MISSING = {
     "dlav1": "its ConvGRU and GroupNorm heads are composed by centerpose_amd.pose_net_gru.PoseNetGRU (build one with "
              "PoseNetGRU.from_model(model) and hand it back with model.load_module(net))",
-    "hourglass": "the two-stack hourglass is not composed (its convolutions, BatchNorms and max-pools train through "
-                 "use_hip_convs / use_hip_norms / use_hip_pools on the reference's own tree)",
+    "hourglass": "the two-stack hourglass is composed by centerpose_amd.pose_net_hourglass.PoseNetHourglass, which returns one "
+                 "head dict per stack (build one with PoseNetHourglass.from_model(model) and hand it back with "
+                 "model.load_module(net))",
     "resdcn": "the ResNet-DCN family is not composed (its layers train through use_hip_stems / use_hip_convs / use_hip_norms / "
               "use_hip_pools / use_hip_deconvs on the reference's own tree)",
 }

@@ -61,21 +61,26 @@ class _StemConv2dFn(Function):
         return None, gw if need_w else None, gb if need_b else None, None, None
 
 
-def _geometry_refusal(cin, cout, kernel, stride, pad):
-    """Why (Cin, Cout, kernel, stride, padding) is not a stem the library runs, or None."""
+_RECLASS_MAX_COUT = 64  # use_hip_stems: what it has always re-classed
+_MAX_COUT = 128         # stem_conv2d and a directly constructed StemConv2d (the hourglass's 3 -> 128 stem)
+
+
+def _geometry_refusal(cin, cout, kernel, stride, pad, max_cout=_MAX_COUT):
+    """Why (Cin, Cout, kernel, stride, padding) is not a stem the library runs, or None.  ``max_cout``: 128 for ``stem_conv2d``
+    and ``StemConv2d``, 64 for what ``use_hip_stems`` re-classes."""
     if not 1 <= cin <= 3:
         return "in_channels = %d is outside 1..3" % cin
     if (kernel, pad) != (7, 3) or stride not in (1, 2):
         return "geometry outside kernel 7, padding 3, stride 1 or 2 (got %d, %d, %d)" % (kernel, pad, stride)
-    if cout % 16 or not 16 <= cout <= 64:
-        return "out_channels = %d is not 16, 32, 48 or 64" % cout
+    if cout % 16 or not 16 <= cout <= max_cout:
+        return "out_channels = %d is not a multiple of 16 from 16 to %d" % (cout, max_cout)
     return None
 
 
 def stem_conv2d(x, weight, bias=None, stride=1, relu=False):
     """``relu?(F.conv2d(x, weight, bias, stride, padding=3))`` for a 7x7 stem on the HIP kernels with autograd.  ``x`` is a
-    [B,Cin,H,W] float32 image on the device with Cin in 1..3 (NCHW planes); ``weight`` [Cout,Cin,7,7] with Cout in {16, 32, 48,
-    64}; stride 1 or 2.  The result is channels_last.  ``x`` must not require a gradient."""
+    [B,Cin,H,W] float32 image on the device with Cin in 1..3 (NCHW planes); ``weight`` [Cout,Cin,7,7] with Cout a multiple of 16
+    from 16 to 128; stride 1 or 2.  The result is channels_last.  ``x`` must not require a gradient."""
     if not x.is_cuda:
         raise RuntimeError("centerpose_hip: tensors must live on the HIP device (no CPU path)")
     if x.dim() != 4 or weight.dim() != 4 or weight.shape[1] != x.shape[1]:
@@ -92,22 +97,23 @@ def stem_conv2d(x, weight, bias=None, stride=1, relu=False):
     return _StemConv2dFn.apply(x, weight, bias, stride, bool(relu))
 
 
-def _eligible(m):
+def _eligible(m, max_cout=_MAX_COUT):
     return (tuple(m.dilation) == (1, 1) and m.groups == 1 and m.padding_mode == 'zeros' and not isinstance(m.padding, str)
             and m.kernel_size[0] == m.kernel_size[1] and m.stride[0] == m.stride[1] and m.padding[0] == m.padding[1]
             and m.weight.dtype == torch.float32
-            and _geometry_refusal(m.in_channels, m.out_channels, m.kernel_size[0], m.stride[0], m.padding[0]) is None)
+            and _geometry_refusal(m.in_channels, m.out_channels, m.kernel_size[0], m.stride[0], m.padding[0], max_cout) is None)
 
 
 class StemConv2d(nn.Conv2d):
     """``nn.Conv2d`` for a 7x7 image stem whose forward and backward run on the library (``stem_conv2d``).  Constructor,
-    parameters, initial values, ``state_dict`` and ``repr`` are ``nn.Conv2d``'s; ``relu = True`` fuses a following ReLU."""
+    parameters, initial values, ``state_dict`` and ``repr`` are ``nn.Conv2d``'s; ``relu = True`` fuses a following ReLU.
+    Constructed directly it takes ``out_channels`` in multiples of 16 up to 128 (``use_hip_stems`` re-classes up to 64 only)."""
     relu = False
 
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
         if not _eligible(self):
-            raise NotImplementedError("centerpose_amd.stem.StemConv2d: only Conv2d(1..3, 16 | 32 | 48 | 64, 7, stride 1 | 2, "
+            raise NotImplementedError("centerpose_amd.stem.StemConv2d: only Conv2d(1..3, 16 | 32 | ... | 128, 7, stride 1 | 2, "
                                       "padding 3) without dilation or groups is built")
 
     def _get_name(self):
@@ -122,10 +128,11 @@ def use_hip_stems(module):
     kernel 7, padding 3, stride 1 or 2, ``out_channels`` in {16, 32, 48, 64}, no dilation or groups -- to ``StemConv2d`` in
     place: the Parameter objects, the module names and the state-dict keys stay as they are.  Returns ``(converted, skipped)``;
     ``skipped`` is always empty, because every other module (``conv.use_hip_convs`` reports the convolutions) is left
-    unmentioned and untouched.  A second call converts nothing."""
+    unmentioned and untouched.  A second call converts nothing.  The wider stems ``StemConv2d`` itself accepts (80 .. 128 output
+    channels) are left alone here, as they always were: a caller's tree changes only where it did before."""
     converted = []
     for name, m in module.named_modules():
-        if type(m) is nn.Conv2d and _eligible(m):
+        if type(m) is nn.Conv2d and _eligible(m, _RECLASS_MAX_COUT):
             m.__class__ = StemConv2d
             converted.append(name)
     return converted, {}

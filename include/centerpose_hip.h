@@ -522,6 +522,27 @@ size_t cp_conv2d_stem_backward_workspace_bytes(int B, int H, int W, int Cin, int
 int cp_conv2d_stem_backward(cp_stream_t stream, const float* x_nchw, const float* grad_out_nhwc, const float* y_or_null,
                             float* grad_w, float* grad_bias_or_null, void* workspace, size_t workspace_bytes, int B, int H,
                             int W, int Cin, int Cout, int stride);
+/* The same operator for Cout in multiples of 16 from 16 to 128 — convolution(7, 3, 128, stride=2), the first layer of
+ * models/networks/large_hourglass.py:209-212.  The kernels are the ones above, run over channel blocks of at most 64, so up to
+ * 64 channels the two pairs give the same bits; same arguments, same workspace rule, same refusals but for the range of Cout.
+ * (A pair of its own: cp_conv2d_stem_backward keeps refusing what it has always refused.) */
+size_t cp_conv2d_stem_wide_backward_workspace_bytes(int B, int H, int W, int Cin, int Cout, int stride);
+int cp_conv2d_stem_wide_backward(cp_stream_t stream, const float* x_nchw, const float* grad_out_nhwc, const float* y_or_null,
+                                 float* grad_w, float* grad_bias_or_null, void* workspace, size_t workspace_bytes, int B, int H,
+                                 int W, int Cin, int Cout, int stride);
+
+/* ------------------------------------------------------------------------------------------
+ * The kp_module merge of the stacked hourglass for training — models/networks/large_hourglass.py:95-112 (MergeUp,
+ *   make_unpool_layer) as kp_module.forward uses them (:176-187): out = up1 + Upsample(scale_factor=2)(low), nearest neighbour,
+ *   forward and backward, float32 NHWC: low, grad_low [B,H,W,C]; up1, out, grad_out [B,2H,2W,C].
+ * Backward: grad_low[b,y,x,c] = (g[2y,2x] + g[2y,2x+1]) + (g[2y+1,2x] + g[2y+1,2x+1]), g = grad_out, in exactly that order:
+ * bitwise reproducible, and exact on dyadic data.  grad_low is written, not accumulated.  The gradient with respect to up1 is
+ * grad_out itself: there is no kernel and no copy for it.  No atomics, no workspace.
+ * Refused with CP_ERR_INVALID and a cp_last_error() text before any launch: a NULL pointer, B / H / W < 1, C < 4 or C % 4 != 0,
+ * a pointer that is not 16-byte aligned, a tensor of 2^31 elements or more.  Launches on `stream`, never synchronises.
+ * ------------------------------------------------------------------------------------------ */
+int cp_upsample2_add_nhwc(cp_stream_t stream, const float* up1, const float* low, float* out, int B, int H, int W, int C);
+int cp_upsample2_add_backward_nhwc(cp_stream_t stream, const float* grad_out, float* grad_low, int B, int H, int W, int C);
 
 /* ------------------------------------------------------------------------------------------
  * Heat-map decode — replaces `object_pose_decode(..., Inference=True)` (models/decode.py:72-375,
