@@ -12,7 +12,9 @@ extern "C" {
 /* Kernel SELECTION switches (process-global; 0 = the engine's own choice).  Every bit picks another implementation of the
  * same layer among the ones the library ships, so that the parity tests can compare two implementations on one input.
  * Every combination computes the layer correctly (to the summation-order round-off the tests state), except that
- * CP_SEL_NO_PRESCALE is correct only for inputs inside binary16's range (it exists for the range-safety tests).
+ * CP_SEL_NO_PRESCALE is correct only for inputs inside binary16's range (it exists for the range-safety tests:
+ * tests/test_scale_equivariance_gpu.py, test_without_the_prescale_the_scaled_case_leaves_binary16, runs a model whose activations
+ * sit 2^14 above synth's under it and requires the per-layer gate to fail).
  * cp_set_debug returns CP_ERR_INVALID, and keeps the current selection, when a bit outside CP_SEL_ALL is set.  Bit 11
  * (2048, once "alternative DCN wave counts") is unused and refused.
  * CP_SEL_PW16_FRAG_A and CP_SEL_PW16_NEVER also change the launch SEQUENCE of DLA's level entries: the entry's 1x1 projection,

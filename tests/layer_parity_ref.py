@@ -112,15 +112,18 @@ def inputs(key):
     return x, kw
 
 
-def oracle(key, dtype, hook=None):
-    """One oracle pass of a case in `dtype` -> (taps in the order recorded, heads)"""
+def oracle(key, dtype, hook=None, sd=None, x=None, kw=None):
+    """One oracle pass of a case in `dtype` -> (taps in the order recorded, heads).  `sd`, `x`, `kw`: another state dict and
+    other inputs of the case's graph and shape (tests/scale_gauge_ref.py's transformed models); the case's own by default."""
     from oracle import backbone as ob
     from oracle import hourglass as oh
     from tests.resdcn_ref import torch_resdcn_forward
 
     c = CASES[key]
-    sd = state_dict(key)
-    x, kw = inputs(key)
+    if sd is None:
+        sd = state_dict(key)
+    if x is None:
+        x, kw = inputs(key)
     taps = OrderedDict()
     nthreads = torch.get_num_threads()
     torch.set_num_threads(min(16, nthreads))
