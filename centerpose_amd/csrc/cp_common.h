@@ -678,6 +678,15 @@ size_t cp_adam_ws_bytes(int n_chunks);
 int cp_launch_adam_step(hipStream_t s, const void* table, int n_tensors, int n_chunks, double lr, double beta1, double beta2, double eps,
                         double weight_decay, double max_norm, int flags, void* state, void* ws);
 
+// ---- the gradient pack of data-parallel training (grad_pack.hip; layouts in include/centerpose_hip.h) ----
+const char* cp_grad_layout(int n_tensors, const int64_t* lengths, int64_t* offsets_or_null, long long* flat_elems,
+                           long long* n_chunks);  // nullptr: accepted; offsets: n_tensors + 1 values
+size_t cp_grad_pack_table_size(int n_tensors, long long n_chunks);
+const char* cp_grad_pack_table_fill(void* table, int n_tensors, const void* const* src, const int64_t* lengths,
+                                    const int64_t* offsets);  // nullptr: written
+long long cp_grad_min_flat_elems(int n_tensors, int n_chunks);
+int cp_launch_grad_pack(hipStream_t s, const void* table, int n_tensors, int n_chunks, float* flat, long long flat_elems, float scale);
+
 // ---- Objectron box metrics (box3d.hip; numerics in box3d_common.h) ----
 int cp_launch_box_iou(hipStream_t s, const double* a, const double* b, int n, double* iou);
 int cp_launch_box_eval(hipStream_t s, const double* pred3d, const double* gt3d, const double* pred2d, const double* mo2c,

@@ -1,5 +1,5 @@
 // What the stand-alone operators share (ops.hip and the training operators dcn_bwd.hip, heads_bwd.hip, conv_bwd.hip,
-// conv_bwd_lowc.hip, deconv_bwd.hip, batchnorm.hip, groupnorm.hip, gru_train.hip, pool.hip, stem_bwd.hip, optim.hip): the launch check, the two
+// conv_bwd_lowc.hip, deconv_bwd.hip, batchnorm.hip, groupnorm.hip, gru_train.hip, pool.hip, stem_bwd.hip, optim.hip, grad_pack.hip): the launch check, the two
 // fixed-order slab sums and the ConvParams of a convolution that runs as part of a gradient.  The summation orders are contract
 // (the tests compare bitwise), so they are written here once.  The workspace carver, Carve, is in cp_common.h, where the target
 // builders (pose_targets*.hip, train_inputs.hip) reach it without the engine's model header.

@@ -3,7 +3,7 @@
 // cp_conv_transpose2d_dw_nhwc / cp_conv_transpose2d_backward_nhwc, cp_dcnv2_forward / cp_dcnv2_backward / cp_dcnv2_backward_det, cp_pose_heads_forward / _backward,
 // cp_maxpool2d_forward_nhwc / _backward_nhwc, cp_upsample2_add_nhwc / cp_upsample2_add_backward_nhwc (large_hourglass.py:95-112),
 // cp_conv2d_stem_backward / cp_conv2d_stem_wide_backward, cp_groupnorm_forward_nhwc / _backward_nhwc,
-// cp_gru_gate_forward / _backward, cp_adam_table_bytes / _table_build / _step.
+// cp_gru_gate_forward / _backward, cp_adam_table_bytes / _table_build / _step, cp_grad_flat_elems / _flat_offsets / _pack_table_bytes / _pack_table_build / _pack.
 // Each packs its PyTorch-layout weights into a caller-provided workspace on every call and then launches the same kernels as
 // the engine.
 #include "op_common.h"
@@ -893,6 +893,59 @@ int cp_adam_step(cp_stream_t stream, const void* table, int n_tensors, int n_chu
     const int rc = cp_launch_adam_step((hipStream_t)stream, table, n_tensors, n_chunks, lr, beta1, beta2, eps, weight_decay, max_norm,
                                        flags, state, workspace);
     return rc == CP_OK ? CP_OK : fail(rc, "adam_step: kernel launch failed");
+}
+
+// The gradient pack of data-parallel training (grad_pack.hip)
+size_t cp_grad_flat_elems(int n_tensors, const int64_t* lengths) {
+    long long total = 0;
+    if (const char* e = cp_grad_layout(n_tensors, lengths, nullptr, &total, nullptr)) {
+        fail(CP_ERR_INVALID, e);
+        return 0;
+    }
+    return (size_t)total;
+}
+
+int cp_grad_flat_offsets(int n_tensors, const int64_t* lengths, int64_t* offsets) {
+    if (!offsets) return fail(CP_ERR_INVALID, "grad_pack: null offsets");
+    if (const char* e = cp_grad_layout(n_tensors, lengths, offsets, nullptr, nullptr)) return fail(CP_ERR_INVALID, e);
+    return CP_OK;
+}
+
+size_t cp_grad_pack_table_bytes(int n_tensors, const int64_t* lengths, int* n_chunks) {
+    long long nc = 0;
+    const char* e = cp_grad_layout(n_tensors, lengths, nullptr, nullptr, &nc);
+    if (!e && !n_chunks) e = "grad_pack: null n_chunks";
+    if (e) {
+        fail(CP_ERR_INVALID, e);
+        return 0;
+    }
+    *n_chunks = (int)nc;  // at most 2^31 / CP_ADAM_CHUNK + n_tensors
+    return cp_grad_pack_table_size(n_tensors, nc);
+}
+
+int cp_grad_pack_table_build(void* table, size_t table_bytes, int n_tensors, const void* const* src, const int64_t* lengths,
+                             const int64_t* offsets, int* n_chunks) {
+    if (!table || !src || !lengths || !offsets || !n_chunks) return fail(CP_ERR_INVALID, "grad_pack_table_build: null argument");
+    long long nc = 0;
+    if (const char* e = cp_grad_layout(n_tensors, lengths, nullptr, nullptr, &nc)) return fail(CP_ERR_INVALID, e);
+    if (table_bytes < cp_grad_pack_table_size(n_tensors, nc)) return fail(CP_ERR_INVALID, "grad_pack_table_build: table buffer too small");
+    if ((uintptr_t)table & 7) return fail(CP_ERR_INVALID, "grad_pack_table_build: table must be 8-byte aligned");
+    if (const char* e = cp_grad_pack_table_fill(table, n_tensors, src, lengths, offsets)) return fail(CP_ERR_INVALID, e);
+    *n_chunks = (int)nc;
+    return CP_OK;
+}
+
+int cp_grad_pack(cp_stream_t stream, const void* table, int n_tensors, int n_chunks, float* flat, int64_t flat_elems, float scale) {
+    if (!table || !flat) return fail(CP_ERR_INVALID, "grad_pack: null argument");
+    if (n_tensors < 1) return fail(CP_ERR_INVALID, "grad_pack: n_tensors must be >= 1");
+    if (n_chunks < 0) return fail(CP_ERR_INVALID, "grad_pack: n_chunks must be >= 0");
+    if ((uintptr_t)table & 7) return fail(CP_ERR_INVALID, "grad_pack: table must be 8-byte aligned");
+    if ((uintptr_t)flat & 15) return fail(CP_ERR_INVALID, "grad_pack: flat must be 16-byte aligned");
+    if (!std::isfinite(scale)) return fail(CP_ERR_INVALID, "grad_pack: non-finite scale");
+    if (flat_elems < cp_grad_min_flat_elems(n_tensors, n_chunks))
+        return fail(CP_ERR_INVALID, "grad_pack: flat_elems is below every layout of n_tensors tensors and n_chunks chunks");
+    const int rc = cp_launch_grad_pack((hipStream_t)stream, table, n_tensors, n_chunks, flat, (long long)flat_elems, scale);
+    return rc == CP_OK ? CP_OK : fail(rc, "grad_pack: kernel launch failed");
 }
 
 }  // extern "C"

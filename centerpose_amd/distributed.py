@@ -12,6 +12,9 @@ every frame: ``allgather_detections`` gathers the fixed-size detection records (
 with a single ``all_gather`` (RCCL over xGMI when the backend is "nccl").  Records are ~47 KB per image, so the
 exchange is latency-bound; one un-bucketed all-gather of the whole shard is the right shape for point-to-point
 xGMI links (no ring pipeline to fill).
+
+Training across GPUs (``data_parallel.DataParallel``) uses three more helpers from here: ``shard_batch``, and the coalesced
+``broadcast_coalesced`` / ``all_reduce_sum``.
 """
 import os
 
@@ -93,3 +96,52 @@ def allgather_detections_compact(det, thresh, score_index=4, group=None):
     packed = torch.cat([rec, idx.to(rec.dtype).unsqueeze(1)], 1)
     out = allgather_detections_ragged(packed, group=group)
     return out[:, :-1].contiguous(), out[:, -1].to(torch.int64)
+
+
+def shard_batch(batch, rank, world):
+    """This rank's part of a batch dict: every tensor sliced on dimension 0 by ``shard_range`` of its own length (a batch
+    of 5 over 2 ranks: 3 + 2), everything else passed through.  What the reference's DataParallel scatter does with
+    ``chunk_sizes`` (opts.py:358-367), for one process per GPU."""
+    out = {}
+    for k, v in batch.items():
+        if isinstance(v, torch.Tensor) and v.dim() > 0:
+            s, e = shard_range(v.shape[0], rank, world)
+            v = v[s:e]
+        out[k] = v
+    return out
+
+
+def _on_host_if_refused(collective, t):
+    """``collective(t)``; a backend that refuses ``t``'s device gets a host copy instead, copied back afterwards."""
+    try:
+        collective(t)
+    except RuntimeError:
+        if not t.is_cuda:
+            raise
+        host = t.cpu()
+        collective(host)
+        t.copy_(host)
+
+
+def all_reduce_sum(t, group=None):
+    """In-place SUM over the ranks of one contiguous tensor."""
+    _on_host_if_refused(lambda x: dist.all_reduce(x, dist.ReduceOp.SUM, group=group), t)
+
+
+@torch.no_grad()
+def broadcast_coalesced(tensors, src=0, group=None):
+    """Every rank's ``tensors`` (the same shapes and dtypes everywhere; any memory layout) become rank ``src``'s (a rank of
+    ``group``), with one broadcast per dtype: the tensors of a dtype travel as one flat buffer -- for a network, one for
+    the float tensors and one for the int64 ``num_batches_tracked``."""
+    if not dist.is_initialized() or dist.get_world_size(group) == 1:
+        return
+    root = dist.get_global_rank(group, src) if group is not None else src
+    by_dtype = {}
+    for t in tensors:
+        by_dtype.setdefault(t.dtype, []).append(t)
+    for ts in by_dtype.values():
+        flat = torch.cat([t.detach().reshape(-1) for t in ts])
+        _on_host_if_refused(lambda x: dist.broadcast(x, root, group=group), flat)
+        if dist.get_rank(group) != src:
+            for t, part in zip(ts, flat.split([t.numel() for t in ts])):
+                t.copy_(part.view(t.shape))

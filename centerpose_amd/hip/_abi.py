@@ -137,6 +137,11 @@ SIGNATURES = {
     "cp_adam_state_bytes": (c_size_t, _i),
     "cp_adam_workspace_bytes": (c_size_t, _i),
     "cp_adam_step": (c_int, _vp * 2 + _i * 2 + [c_double] * 6 + _i + _vp + _ws),
+    "cp_grad_flat_elems": (c_size_t, _i + [POINTER(c_int64)]),
+    "cp_grad_flat_offsets": (c_int, _i + [POINTER(c_int64)] * 2),
+    "cp_grad_pack_table_bytes": (c_size_t, _i + [POINTER(c_int64)] + _pi),
+    "cp_grad_pack_table_build": (c_int, [c_void_p, c_size_t] + _i + _pvp + [POINTER(c_int64)] * 2 + _pi),
+    "cp_grad_pack": (c_int, _vp * 2 + _i * 2 + _vp + [c_int64, c_float]),
 }
 
 

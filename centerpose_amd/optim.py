@@ -32,12 +32,23 @@ def _same_layout(g, p):
     return all(a == b for a, b, size in zip(g.stride(), p.stride(), p.shape) if size > 1)
 
 
+def _check_params(params):
+    """Adam's rule for what it updates (data_parallel.DataParallel packs the same tensors): float32, strided, dense."""
+    for p in params:
+        if p.dtype != torch.float32 or p.layout != torch.strided:
+            raise NotImplementedError("centerpose_amd.optim.Adam: float32 strided parameters only (got %s, %s)" % (p.dtype, p.layout))
+        if not _dense(p):
+            raise NotImplementedError("centerpose_amd.optim.Adam: a parameter that is a non-dense view (shape %s, strides %s) "
+                                      "is not implemented" % (tuple(p.shape), p.stride()))
+
+
 class _Group(object):
     """What one param group keeps between steps, none of it part of ``state_dict``: the host arrays the table is built from,
     the device table, state block and workspace, and the pinned buffers the table is uploaded from."""
 
-    def __init__(self, params):
+    def __init__(self, params, owner):
         n = len(params)
+        self.owner = owner   # the optimizer, whose table_uploads counts the uploads of all its groups
         dev = params[0].device
         if any(p.device != dev for p in params):   # one table, one state block, one launch set: one device
             raise NotImplementedError("centerpose_amd.optim.Adam: the parameters of a param group must live on one device "
@@ -74,6 +85,7 @@ class _Group(object):
         self.table.copy_(slot[0], non_blocking=True)
         slot[1].record()
         self.dirty = False
+        self.owner._table_uploads += 1
 
 
 class Adam(torch.optim.Optimizer):
@@ -88,7 +100,7 @@ class Adam(torch.optim.Optimizer):
     the step writes: reading them on the host is the caller's synchronisation, ``step()`` itself never waits for the device.
     ``last_grad_norm`` is NaN after a step that did not measure it (no clipping and no ``skip_nonfinite``).  With more than
     one group they hold one value per group.  ``layout_copies`` counts the gradients that had to be copied into their
-    parameter's memory layout before a step.
+    parameter's memory layout before a step, ``table_uploads`` (read-only) the uploads of a group's device table.
 
     Streams and devices.  ``step()`` queues everything on the stream that is current when it is called, in order: the upload
     of the group's one device table, then the launches that read it.  Call every ``step()`` of an optimizer on the same
@@ -120,6 +132,7 @@ class Adam(torch.optim.Optimizer):
         defaults.update(max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
         self._groups = None
         self.layout_copies = 0
+        self._table_uploads = 0
         super().__init__(params, defaults)
         for group in self.param_groups:
             self._check_group(group)
@@ -135,12 +148,7 @@ class Adam(torch.optim.Optimizer):
     @classmethod
     def _check_group(cls, group):
         cls._check_options(group)
-        for p in group["params"]:
-            if p.dtype != torch.float32 or p.layout != torch.strided:
-                raise NotImplementedError("centerpose_amd.optim.Adam: float32 strided parameters only (got %s, %s)" % (p.dtype, p.layout))
-            if not _dense(p):
-                raise NotImplementedError("centerpose_amd.optim.Adam: a parameter that is a non-dense view (shape %s, strides %s) "
-                                          "is not implemented" % (tuple(p.shape), p.stride()))
+        _check_params(group["params"])
 
     def __setstate__(self, state):
         super().__setstate__(state)
@@ -150,6 +158,7 @@ class Adam(torch.optim.Optimizer):
             self._check_group(group)
         self._groups = None   # the step counters go back into state blocks at the next step
         self.__dict__.setdefault("layout_copies", 0)   # (unpickling restores defaults, state and param_groups alone)
+        self.__dict__.setdefault("_table_uploads", 0)
 
     def add_param_group(self, param_group):
         super().add_param_group(param_group)
@@ -178,7 +187,7 @@ class Adam(torch.optim.Optimizer):
             for p in params:
                 if not p.is_cuda:
                     raise RuntimeError("centerpose_amd.optim.Adam: parameters must live on the HIP device (no CPU path)")
-            rt = _Group(params)
+            rt = _Group(params, self)
             host = torch.zeros(rt.n, dtype=torch.float32)
             on_host = False
             for i, p in enumerate(params):
@@ -204,6 +213,13 @@ class Adam(torch.optim.Optimizer):
             groups.append(rt)
         self._groups = groups
         return groups
+
+    @property
+    def table_uploads(self):
+        """How many times a group's device table was laid out and uploaded since construction: once per step while the
+        gradients are fresh allocations, once in all while their addresses stay put (``data_parallel.DataParallel``'s views
+        of its flat buffer)."""
+        return self._table_uploads
 
     @property
     def last_grad_norm(self):

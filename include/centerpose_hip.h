@@ -50,7 +50,8 @@ typedef struct cp_model cp_model;
  *     cp_groupnorm_workspace_bytes, cp_groupnorm_forward_nhwc / _backward_nhwc, cp_gru_gate_forward / _backward;
  *     cp_train_inputs_workspace_bytes, cp_train_inputs;
  *     cp_pose_targets_track_det_workspace_bytes, cp_pose_targets_track_det;
- *     cp_adam_table_bytes, cp_adam_table_build, cp_adam_state_bytes, cp_adam_workspace_bytes, cp_adam_step. */
+ *     cp_adam_table_bytes, cp_adam_table_build, cp_adam_state_bytes, cp_adam_workspace_bytes, cp_adam_step;
+ *     cp_grad_flat_elems, cp_grad_flat_offsets, cp_grad_pack_table_bytes, cp_grad_pack_table_build, cp_grad_pack. */
 #define CP_ABI_VERSION 7
 const char* cp_version(void);
 int cp_abi_version(void);
@@ -1276,6 +1277,57 @@ size_t cp_adam_workspace_bytes(int n_chunks); /* 0: n_chunks < 0 */
 int cp_adam_step(cp_stream_t stream, const void* table, int n_tensors, int n_chunks, double lr, double beta1, double beta2,
                  double eps, double weight_decay, double max_norm, int flags, void* state, void* workspace,
                  size_t workspace_bytes);
+
+/* ------------------------------------------------------------------------------------------
+ * cp_grad_*: the gradient pack of data-parallel training -- every gradient of a model into one flat float32 buffer,
+ *   scaled, in one launch whatever n_tensors is; one all-reduce then runs over the buffer and cp_adam_step reads its
+ *   gradients from it (the reference: torch's DataParallel, trains/base_trainer.py:42-48, and loss.mean() over the
+ *   replicas, base_trainer.py:89).  No atomics, no host synchronisation, never allocates.
+ *
+ * The flat layout is decided by the lengths alone, so it is the same on every rank: tensor i takes lengths[i] floats at
+ *   offsets[i], a multiple of 4 floats (16 bytes), offsets ascending in tensor order (a tensor of length 0 takes no
+ *   space); behind the last tensor, at offsets[n_tensors] (a multiple of 4 as well), come n_tensors float flags, padded to
+ *   a multiple of 4.  cp_grad_flat_elems is the length of all of it, cp_grad_flat_offsets writes the n_tensors + 1 offsets.
+ *   Refused (cp_grad_flat_elems and cp_grad_pack_table_bytes: return 0; the others: CP_ERR_INVALID) with a cp_last_error
+ *   text: n_tensors < 1, a length < 0, more than 2^31 - 1 elements in all.
+ *
+ * The table (cp_grad_pack_table_build writes it into HOST memory, the caller copies it to the device as it is):
+ *   n_tensors + 1 tensor records of CP_GRAD_TENSOR_BYTES, then n_chunks chunk records of CP_GRAD_CHUNK_BYTES.
+ *   tensor record  bytes 0: source (device address; NULL: the tensor has no gradient); 8: int64 offset in the flat buffer.
+ *                  Record n_tensors has a NULL source and the offset of the flags.
+ *   chunk record   bytes 0: int32 tensor index; 4: uint32 first element within the tensor; 8: int32 element count
+ *                  (1..CP_ADAM_CHUNK); 12: int32 flags (CP_GRAD_VEC: the source is 16-byte aligned; CP_GRAD_ZERO: no source)
+ *   Chunks are in tensor order and, within a tensor, ascending; a tensor of n elements takes ceil(n / CP_ADAM_CHUNK) chunks
+ *   that start at multiples of CP_ADAM_CHUNK, whether it has a source or not: a chunk never straddles two tensors, and
+ *   n_chunks depends on the lengths alone.  `offsets` must be the n_tensors + 1 values of cp_grad_flat_offsets.
+ *
+ * cp_grad_pack, one launch: for a tensor with a source flat[offsets[i] + k] = scale * src_i[k] (one float32 multiply;
+ *   scale == 1 is a plain copy); for a tensor without, the region is set to 0; flat[offsets[n_tensors] + i] = 1.0 where
+ *   tensor i has a source, else 0.0.  The padding floats between the tensors and behind the flags are never written (the
+ *   caller zeroes the buffer once), nor is anything at or past flat_elems.  A source that IS its destination
+ *   (src_i == flat + offsets[i]) is allowed and scales in place; any other overlap of a source with the flat buffer is NOT
+ *   checked and gives undefined values.  A source that is 16-byte aligned moves 16 bytes per lane, any other goes element by
+ *   element (the destination is always 16-byte aligned).
+ *   Refused with CP_ERR_INVALID before any launch: a NULL table or flat, n_tensors < 1, n_chunks < 0, a table not 8-byte or a
+ *   flat not 16-byte aligned, a source not 4-byte aligned (at cp_grad_pack_table_build), a non-finite scale, a flat_elems
+ *   below what a table of n_tensors tensors and n_chunks chunks can describe.  cp_grad_pack cannot see the table's content
+ *   (device memory): it trusts n_tensors / n_chunks to be those of the cp_grad_pack_table_build call that made it.
+ * ------------------------------------------------------------------------------------------ */
+#define CP_GRAD_TENSOR_BYTES 16
+#define CP_GRAD_CHUNK_BYTES 16
+#define CP_GRAD_VEC 1
+#define CP_GRAD_ZERO 2
+/* HOST: floats of the flat buffer of these lengths (0: refused) */
+size_t cp_grad_flat_elems(int n_tensors, const int64_t* lengths);
+/* HOST: writes offsets[0 .. n_tensors] */
+int cp_grad_flat_offsets(int n_tensors, const int64_t* lengths, int64_t* offsets);
+/* HOST: bytes of the table of these lengths (0: refused) and, through n_chunks, its number of chunks */
+size_t cp_grad_pack_table_bytes(int n_tensors, const int64_t* lengths, int* n_chunks);
+/* HOST: writes the table into `table` (host memory of table_bytes) from a host array of device addresses */
+int cp_grad_pack_table_build(void* table, size_t table_bytes, int n_tensors, const void* const* src, const int64_t* lengths,
+                             const int64_t* offsets, int* n_chunks);
+int cp_grad_pack(cp_stream_t stream, const void* table, int n_tensors, int n_chunks, float* flat, int64_t flat_elems,
+                 float scale);
 
 #ifdef __cplusplus
 }
