@@ -18,6 +18,13 @@
 //   forward              apply_kernel     y, whole lines in and out.
 //   backward             bwd_reduce_kernel / bwd_finalize_kernel   grad_beta = sum g, grad_gamma = sum g * xhat (g gated by y > 0)
 //                        bwd_apply_kernel grad_x (and grad_residual = g when asked) in one pass.
+//
+// SyncBatchNorm (cp_batchnorm_sync_*): the same kernels in phases around the caller's two all-gathers.  A rank is one more
+// level of the Chan merge (chan_merge, shared by all three merging kernels):
+//   forward A   stats_kernel, sync_record_kernel    this rank's record mean[C] | M2[C] | count
+//   forward B   sync_merge_kernel, apply_kernel     the ranks' records merged in rank order; the global count stays on the device
+//   backward A  bwd_reduce_kernel, bwd_finalize_kernel   this rank's two sums against the global mean
+//   backward B  sync_sum_kernel, bwd_apply_kernel   the ranks' sums added in rank order; n read from the device
 #include "norm_common.h"
 
 #include <algorithm>
@@ -32,8 +39,41 @@ __global__ __launch_bounds__(256) void stats_kernel(const float* __restrict__ x,
     slab_stats(x + (size_t)q_beg * C, len, C, ln, part + (size_t)blockIdx.x * 2 * C, sm, sq);
 }
 
-// The slabs merged per channel, 32 channels per workgroup, in two rounds of two_level_sum: the mean about slab 0's, then M2
-// about that mean.
+// Chan's many-way merge of `nparts` partial statistics of one channel, in two rounds of two_level_sum: the mean about part 0's,
+// then M2 about that mean.  rows(s), mean_of(s), m2_of(s): part s's count (as a float), mean and M2; n: the total count.  The
+// slabs of a tensor (finalize_kernel, sync_record_kernel) and the ranks of a process group (sync_merge_kernel) are merged by
+// these expressions and no others, so a merge of one part about its own mean adds exact zeros.  Every thread of the workgroup
+// must call it (two barriers).
+template <class N, class M, class Q>
+__device__ __forceinline__ void chan_merge(float (&red)[256], bool cv, int nparts, float n, N rows, M mean_of, Q m2_of, float& mean,
+                                           float& M2) {
+    const float ref = cv ? mean_of(0) : 0.f;
+    const float t = two_level_sum(red, cv, nparts, 0.f, [&](float a, int s) { return fmaf(rows(s), mean_of(s) - ref, a); });
+    mean = ref + t / n;
+    __syncthreads();
+    M2 = two_level_sum(red, cv, nparts, 0.f, [&](float b, int s) {
+        const float d = mean_of(s) - mean;
+        return b + fmaf(rows(s) * d, d, m2_of(s));
+    });
+}
+// the slabs of stats_kernel's part[slab][2][C], channel c
+__device__ __forceinline__ void slab_merge(float (&red)[256], bool cv, const float* __restrict__ part, int c, int P, int C, int slab_px,
+                                           int nslab, float& mean, float& M2) {
+    chan_merge(
+        red, cv, nslab, (float)P, [&](int s) { return (float)min(slab_px, P - s * slab_px); },
+        [&](int s) { return part[(size_t)s * 2 * C + c]; }, [&](int s) { return part[(size_t)s * 2 * C + C + c]; }, mean, M2);
+}
+// what the forward keeps of a channel's merged statistics over n values
+__device__ __forceinline__ void store_stats(int c, float mean, float M2, float n, float* __restrict__ save_mean,
+                                            float* __restrict__ save_invstd, float* __restrict__ rmean, float* __restrict__ rvar,
+                                            float momentum, float eps) {
+    save_mean[c] = mean;
+    save_invstd[c] = 1.f / sqrtf(M2 / n + eps);
+    if (rmean) rmean[c] = (1.f - momentum) * rmean[c] + momentum * mean;
+    if (rvar) rvar[c] = (1.f - momentum) * rvar[c] + momentum * (M2 / (n - 1.f));
+}
+
+// The slabs merged per channel, 32 channels per workgroup.
 __global__ __launch_bounds__(256) void finalize_kernel(const float* __restrict__ part, float* __restrict__ save_mean,
                                                        float* __restrict__ save_invstd, float* __restrict__ rmean,
                                                        float* __restrict__ rvar, int P, int C, int slab_px, int nslab, float momentum,
@@ -41,22 +81,60 @@ __global__ __launch_bounds__(256) void finalize_kernel(const float* __restrict__
     __shared__ float red[256];
     const int c = blockIdx.x * 32 + (threadIdx.x & 31);
     const bool cv = c < C;
-    const float ref = cv ? part[c] : 0.f, n = (float)P;
-    auto rows = [&](int s) { return (float)min(slab_px, P - s * slab_px); };
-    const float t = two_level_sum(red, cv, nslab, 0.f,
-                                  [&](float a, int s) { return fmaf(rows(s), part[(size_t)s * 2 * C + c] - ref, a); });
-    const float mean = ref + t / n;
-    __syncthreads();
-    const float M2 = two_level_sum(red, cv, nslab, 0.f, [&](float b, int s) {
-        const float* ps = part + (size_t)s * 2 * C + c;
-        const float d = ps[0] - mean;
-        return b + fmaf(rows(s) * d, d, ps[C]);
-    });
+    float mean, M2;
+    slab_merge(red, cv, part, c, P, C, slab_px, nslab, mean, M2);
     if (threadIdx.x >= 32 || !cv) return;
-    save_mean[c] = mean;
-    save_invstd[c] = 1.f / sqrtf(M2 / n + eps);
-    if (rmean) rmean[c] = (1.f - momentum) * rmean[c] + momentum * mean;
-    if (rvar) rvar[c] = (1.f - momentum) * rvar[c] + momentum * (M2 / (n - 1.f));
+    store_stats(c, mean, M2, (float)P, save_mean, save_invstd, rmean, rvar, momentum, eps);
+}
+
+// ---- SyncBatchNorm: the same statistics with one more level of the merge, the ranks of a process group ----
+// A rank's record is mean[C] | M2[C] | count: the count of values per channel as a 32-bit integer's bit pattern in the first
+// word of the last 16-byte slot (a float would round it above 2^24; an all-gather moves bits unchanged), the slot's other
+// three words zero.
+constexpr int kCountSlot = 4;
+
+// forward, phase A: this rank's slabs merged exactly as finalize_kernel merges them -> its record
+__global__ __launch_bounds__(256) void sync_record_kernel(const float* __restrict__ part, float* __restrict__ record, int P, int C,
+                                                          int slab_px, int nslab) {
+    __shared__ float red[256];
+    const int c = blockIdx.x * 32 + (threadIdx.x & 31);
+    const bool cv = c < C;
+    float mean, M2;
+    slab_merge(red, cv, part, c, P, C, slab_px, nslab, mean, M2);
+    if (blockIdx.x == 0 && threadIdx.x == 0) *reinterpret_cast<int4*>(record + 2 * C) = make_int4(P, 0, 0, 0);
+    if (threadIdx.x >= 32 || !cv) return;
+    record[c] = mean;
+    record[C + c] = M2;
+}
+
+// forward, phase B: records[world][2C + 4] merged in rank order about rank 0's mean; every rank computes the same bits.  The
+// global count goes to *save_count as a float, (float)P's rounding of it: what the backward divides by.
+__global__ __launch_bounds__(256) void sync_merge_kernel(const float* __restrict__ records, int world, float* __restrict__ save_mean,
+                                                         float* __restrict__ save_invstd, float* __restrict__ rmean,
+                                                         float* __restrict__ rvar, float* __restrict__ save_count, int C,
+                                                         float momentum, float eps) {
+    __shared__ float red[256];
+    const int c = blockIdx.x * 32 + (threadIdx.x & 31);
+    const bool cv = c < C;
+    const size_t rec = (size_t)2 * C + kCountSlot;
+    auto count = [&](int r) { return *reinterpret_cast<const int*>(records + r * rec + 2 * C); };
+    unsigned long long total = 0;
+    for (int r = 0; r < world; ++r) total += (unsigned)count(r);
+    const float n = (float)total;
+    float mean, M2;
+    chan_merge(
+        red, cv, world, n, [&](int r) { return (float)count(r); }, [&](int r) { return records[r * rec + c]; },
+        [&](int r) { return records[r * rec + C + c]; }, mean, M2);
+    if (blockIdx.x == 0 && threadIdx.x == 0) *save_count = n;
+    if (threadIdx.x >= 32 || !cv) return;
+    store_stats(c, mean, M2, n, save_mean, save_invstd, rmean, rvar, momentum, eps);
+}
+
+// backward, phase B: sums[i] = sums_all[0][i] + sums_all[1][i] + ..., ranks ascending (a backend's SUM has an order of its own)
+__global__ __launch_bounds__(256) void sync_sum_kernel(const float* __restrict__ sums_all, float* __restrict__ sums, int world,
+                                                       int C2) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < C2) sums[i] = serial_sum(sums_all + C2, world - 1, (size_t)C2, (size_t)i, sums_all[i]);
 }
 
 __global__ void eval_stats_kernel(const float* __restrict__ rmean, const float* __restrict__ rvar, float* __restrict__ save_mean,
@@ -173,12 +251,14 @@ __global__ __launch_bounds__(256) void bwd_finalize_kernel(const float* __restri
 }
 
 // training: grad_x = gamma * invstd * (g - grad_beta / n - xhat * grad_gamma / n); evaluation: gamma * invstd * g;
-// grad_residual = g.  gx or gres may be null (not both).
+// grad_residual = g.  gx or gres may be null (not both).  n is P, or *count where given (the sync backward: the global count
+// the forward left on the device, with `sums` the global sums).
 __global__ __launch_bounds__(256) void bwd_apply_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                         const float* __restrict__ go, const float* __restrict__ gamma,
                                                         const float* __restrict__ mean, const float* __restrict__ invstd,
                                                         const float* __restrict__ sums, float* __restrict__ gx,
-                                                        float* __restrict__ gres, int P, int C, int slab_px, int training) {
+                                                        float* __restrict__ gres, int P, int C, int slab_px, int training,
+                                                        const float* __restrict__ count) {
     const Lane ln = lane_of(C);
     const int q_beg = blockIdx.x * slab_px, len = min(P - q_beg, slab_px);
     const int n = ln.active ? rows_of(len, ln.k, ln.S) : 0;
@@ -188,7 +268,7 @@ __global__ __launch_bounds__(256) void bwd_apply_kernel(const float* __restrict_
     un4(ld4(invstd + ln.c), a);
     if (need_x) {
         float s1[4], s2[4];
-        const float rn = 1.f / (float)P;
+        const float rn = 1.f / (count ? *count : (float)P);
         un4(ld4(mean + ln.c), mu);
         un4(ld4(sums + ln.c), s1);
         un4(ld4(sums + C + ln.c), s2);
@@ -302,6 +382,56 @@ int cp_launch_batchnorm_backward(hipStream_t s, const BnBwdArgs& a, void* ws) {
     }
     if (!a.gx && !a.gres) return CP_OK;
     hipLaunchKernelGGL(bwd_apply_kernel, dim3(p.app_slabs, p.npass), dim3(256), 0, s, a.x, a.y, a.go, a.gamma, a.mean, a.invstd,
-                       (const float*)sums, a.gx, a.gres, p.P, a.C, p.app_px, a.training);
+                       (const float*)sums, a.gx, a.gres, p.P, a.C, p.app_px, a.training, (const float*)nullptr);
+    return launch_ok() ? CP_OK : CP_ERR_LAUNCH;
+}
+
+int cp_batchnorm_sync_rec_floats(int C) { return 2 * C + kCountSlot; }
+
+int cp_launch_batchnorm_sync_stats(hipStream_t s, const float* x, float* record, int B, int H, int W, int C, void* ws) {
+    const Plan p = plan(B, H, W, C);
+    Carve cv{(char*)ws};
+    float* part = bn_carve(cv, p, C).part;
+    hipLaunchKernelGGL(stats_kernel, dim3(p.red_slabs, p.npass), dim3(256), 0, s, x, part, p.P, C, p.red_px);
+    if (!launch_ok()) return CP_ERR_LAUNCH;
+    hipLaunchKernelGGL(sync_record_kernel, dim3((C + 31) / 32), dim3(256), 0, s, (const float*)part, record, p.P, C, p.red_px,
+                       p.red_slabs);
+    return launch_ok() ? CP_OK : CP_ERR_LAUNCH;
+}
+
+int cp_launch_batchnorm_sync_forward(hipStream_t s, const BnFwdArgs& a, const float* records, int world, float* save_count) {
+    const Plan p = plan(a.B, a.H, a.W, a.C);
+    hipLaunchKernelGGL(sync_merge_kernel, dim3((a.C + 31) / 32), dim3(256), 0, s, records, world, a.mean, a.invstd, a.rmean, a.rvar,
+                       save_count, a.C, a.momentum, a.eps);
+    if (!launch_ok()) return CP_ERR_LAUNCH;
+    hipLaunchKernelGGL(apply_kernel, dim3(p.app_slabs, p.npass), dim3(256), 0, s, a.x, a.res, a.y, (const float*)a.mean,
+                       (const float*)a.invstd, a.gamma, a.beta, p.P, a.C, p.app_px, a.act);
+    return launch_ok() ? CP_OK : CP_ERR_LAUNCH;
+}
+
+// a.mean / a.invstd: the global pair; sums [2][C], a.gg, a.gb: this rank's own sums
+int cp_launch_batchnorm_sync_backward_reduce(hipStream_t s, const BnBwdArgs& a, float* sums, void* ws) {
+    const Plan p = plan(a.B, a.H, a.W, a.C);
+    Carve cv{(char*)ws};
+    float* part = bn_carve(cv, p, a.C).part;
+    hipLaunchKernelGGL(bwd_reduce_kernel, dim3(p.red_slabs, p.npass), dim3(256), 0, s, a.x, a.y, a.go, a.mean, part, p.P, a.C,
+                       p.red_px);
+    if (!launch_ok()) return CP_ERR_LAUNCH;
+    hipLaunchKernelGGL(bwd_finalize_kernel, dim3((a.C + 31) / 32), dim3(256), 0, s, (const float*)part, a.invstd, sums, a.gg, a.gb,
+                       a.C, p.red_slabs);
+    return launch_ok() ? CP_OK : CP_ERR_LAUNCH;
+}
+
+int cp_launch_batchnorm_sync_backward_apply(hipStream_t s, const BnBwdArgs& a, const float* sums_all, int world,
+                                            const float* save_count, void* ws) {
+    const Plan p = plan(a.B, a.H, a.W, a.C);
+    Carve cv{(char*)ws};
+    float* sums = bn_carve(cv, p, a.C).sums;
+    if (a.gx) {
+        hipLaunchKernelGGL(sync_sum_kernel, dim3((2 * a.C + 255) / 256), dim3(256), 0, s, sums_all, sums, world, 2 * a.C);
+        if (!launch_ok()) return CP_ERR_LAUNCH;
+    }
+    hipLaunchKernelGGL(bwd_apply_kernel, dim3(p.app_slabs, p.npass), dim3(256), 0, s, a.x, a.y, a.go, a.gamma, a.mean, a.invstd,
+                       (const float*)sums, a.gx, a.gres, p.P, a.C, p.app_px, 1, save_count);
     return launch_ok() ? CP_OK : CP_ERR_LAUNCH;
 }

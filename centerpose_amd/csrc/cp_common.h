@@ -564,6 +564,14 @@ struct BnBwdArgs {
 size_t cp_batchnorm_ws_bytes(int B, int H, int W, int C);
 int cp_launch_batchnorm_forward(hipStream_t s, const BnFwdArgs& a, void* ws);
 int cp_launch_batchnorm_backward(hipStream_t s, const BnBwdArgs& a, void* ws);
+// SyncBatchNorm's four phases (batchnorm.hip); the workspace is cp_batchnorm_ws_bytes'.  BnFwdArgs / BnBwdArgs: `training` is
+// not read (always training); mean / invstd are the global pair; gg / gb of the reduce are this rank's own sums.
+int cp_batchnorm_sync_rec_floats(int C);
+int cp_launch_batchnorm_sync_stats(hipStream_t s, const float* x, float* record, int B, int H, int W, int C, void* ws);
+int cp_launch_batchnorm_sync_forward(hipStream_t s, const BnFwdArgs& a, const float* records, int world, float* save_count);
+int cp_launch_batchnorm_sync_backward_reduce(hipStream_t s, const BnBwdArgs& a, float* sums, void* ws);
+int cp_launch_batchnorm_sync_backward_apply(hipStream_t s, const BnBwdArgs& a, const float* sums_all, int world,
+                                            const float* save_count, void* ws);
 
 // ---- GroupNorm for training, fused with the ReLU (groupnorm.hip): float32 NHWC, statistics per (image, group) ----
 struct GnFwdArgs {

@@ -561,6 +561,86 @@ int cp_batchnorm_backward_nhwc(cp_stream_t stream, const float* x, const float* 
     return rc == CP_OK ? CP_OK : fail(rc, "batchnorm_backward: kernel launch failed");
 }
 
+int cp_batchnorm_sync_record_floats(int C) {
+    if (C < 4 || C > 4096 || C % 4) {
+        fail(CP_ERR_INVALID, "batchnorm: C must be a multiple of 4 in 4..4096");
+        return 0;
+    }
+    return cp_batchnorm_sync_rec_floats(C);
+}
+
+int cp_batchnorm_sync_stats_nhwc(cp_stream_t stream, const float* x, float* record, int B, int H, int W, int C, void* workspace,
+                                 size_t workspace_bytes) {
+    if (const char* e = bn_shape_error(B, H, W, C)) return fail(CP_ERR_INVALID, e);
+    if (!x || !record || !workspace) return fail(CP_ERR_INVALID, "batchnorm_sync_stats: null argument");
+    if (!bn_aligned({x, record, workspace})) return fail(CP_ERR_INVALID, "batchnorm_sync_stats: tensors must be 16-byte aligned");
+    if (workspace_bytes < cp_batchnorm_ws_bytes(B, H, W, C)) return fail(CP_ERR_INVALID, "batchnorm_sync_stats: workspace too small");
+    const int rc = cp_launch_batchnorm_sync_stats((hipStream_t)stream, x, record, B, H, W, C, workspace);
+    return rc == CP_OK ? CP_OK : fail(rc, "batchnorm_sync_stats: kernel launch failed");
+}
+
+int cp_batchnorm_sync_forward_nhwc(cp_stream_t stream, const float* x, const float* gamma_or_null, const float* beta_or_null,
+                                   const float* residual_or_null, float* running_mean_or_null, float* running_var_or_null, float* y,
+                                   float* save_mean, float* save_invstd, float* save_count, const float* records, int world, int B,
+                                   int H, int W, int C, float momentum, float eps, int act, void* workspace,
+                                   size_t workspace_bytes) {
+    if (const char* e = bn_shape_error(B, H, W, C)) return fail(CP_ERR_INVALID, e);
+    if (!x || !y || !save_mean || !save_invstd || !save_count || !records || !workspace)
+        return fail(CP_ERR_INVALID, "batchnorm_sync_forward: null argument");
+    if (world < 1 || world > 1024) return fail(CP_ERR_INVALID, "batchnorm_sync_forward: world must be in 1..1024");
+    // (every rank holds at least one value per channel, so only a single rank can fall short of two)
+    if (world == 1 && (long long)B * H * W < 2)
+        return fail(CP_ERR_INVALID, "batchnorm_sync_forward: needs more than one value per channel over the ranks (global count >= 2)");
+    if (act != 0 && act != 1) return fail(CP_ERR_INVALID, "batchnorm_sync_forward: act must be 0 (none) or 1 (relu)");
+    if (!(eps >= 0.f)) return fail(CP_ERR_INVALID, "batchnorm_sync_forward: eps must not be negative");
+    if (y == x) return fail(CP_ERR_INVALID, "batchnorm_sync_forward: y must not alias x");
+    if (!bn_aligned({x, gamma_or_null, beta_or_null, residual_or_null, y, save_mean, save_invstd, records, workspace}))
+        return fail(CP_ERR_INVALID, "batchnorm_sync_forward: tensors must be 16-byte aligned");
+    if (workspace_bytes < cp_batchnorm_ws_bytes(B, H, W, C)) return fail(CP_ERR_INVALID, "batchnorm_sync_forward: workspace too small");
+    const BnFwdArgs a{x, gamma_or_null, beta_or_null, residual_or_null, running_mean_or_null, running_var_or_null, y, save_mean,
+                      save_invstd, B, H, W, C, 1, momentum, eps, act};
+    const int rc = cp_launch_batchnorm_sync_forward((hipStream_t)stream, a, records, world, save_count);
+    return rc == CP_OK ? CP_OK : fail(rc, "batchnorm_sync_forward: kernel launch failed");
+}
+
+int cp_batchnorm_sync_backward_reduce_nhwc(cp_stream_t stream, const float* x, const float* y_or_null, const float* grad_out,
+                                           const float* save_mean, const float* save_invstd, float* sums, float* grad_gamma_or_null,
+                                           float* grad_beta_or_null, int B, int H, int W, int C, void* workspace,
+                                           size_t workspace_bytes) {
+    if (const char* e = bn_shape_error(B, H, W, C)) return fail(CP_ERR_INVALID, e);
+    if (!x || !grad_out || !save_mean || !save_invstd || !sums || !workspace)
+        return fail(CP_ERR_INVALID, "batchnorm_sync_backward_reduce: null argument");
+    if (!bn_aligned({x, y_or_null, grad_out, save_mean, save_invstd, sums, workspace}))
+        return fail(CP_ERR_INVALID, "batchnorm_sync_backward_reduce: tensors must be 16-byte aligned");
+    if (workspace_bytes < cp_batchnorm_ws_bytes(B, H, W, C))
+        return fail(CP_ERR_INVALID, "batchnorm_sync_backward_reduce: workspace too small");
+    const BnBwdArgs a{x, y_or_null, grad_out, nullptr, save_mean, save_invstd, nullptr, nullptr, grad_gamma_or_null,
+                      grad_beta_or_null, B, H, W, C, 1};
+    const int rc = cp_launch_batchnorm_sync_backward_reduce((hipStream_t)stream, a, sums, workspace);
+    return rc == CP_OK ? CP_OK : fail(rc, "batchnorm_sync_backward_reduce: kernel launch failed");
+}
+
+int cp_batchnorm_sync_backward_apply_nhwc(cp_stream_t stream, const float* x, const float* y_or_null, const float* grad_out,
+                                          const float* gamma_or_null, const float* save_mean, const float* save_invstd,
+                                          const float* sums_all, int world, const float* save_count, float* grad_x_or_null,
+                                          float* grad_residual_or_null, int B, int H, int W, int C, void* workspace,
+                                          size_t workspace_bytes) {
+    if (const char* e = bn_shape_error(B, H, W, C)) return fail(CP_ERR_INVALID, e);
+    if (!x || !grad_out || !save_mean || !save_invstd || !sums_all || !save_count || !workspace)
+        return fail(CP_ERR_INVALID, "batchnorm_sync_backward_apply: null argument");
+    if (world < 1 || world > 1024) return fail(CP_ERR_INVALID, "batchnorm_sync_backward_apply: world must be in 1..1024");
+    if (!bn_aligned({x, y_or_null, grad_out, gamma_or_null, save_mean, save_invstd, sums_all, grad_x_or_null, grad_residual_or_null,
+                     workspace}))
+        return fail(CP_ERR_INVALID, "batchnorm_sync_backward_apply: tensors must be 16-byte aligned");
+    if (workspace_bytes < cp_batchnorm_ws_bytes(B, H, W, C))
+        return fail(CP_ERR_INVALID, "batchnorm_sync_backward_apply: workspace too small");
+    if (!grad_x_or_null && !grad_residual_or_null) return CP_OK;
+    const BnBwdArgs a{x, y_or_null, grad_out, gamma_or_null, save_mean, save_invstd, grad_x_or_null, grad_residual_or_null,
+                      nullptr, nullptr, B, H, W, C, 1};
+    const int rc = cp_launch_batchnorm_sync_backward_apply((hipStream_t)stream, a, sums_all, world, save_count, workspace);
+    return rc == CP_OK ? CP_OK : fail(rc, "batchnorm_sync_backward_apply: kernel launch failed");
+}
+
 size_t cp_groupnorm_workspace_bytes(int B, int H, int W, int C, int G) {
     if (const char* e = gn_shape_error(B, H, W, C, G)) {
         fail(CP_ERR_INVALID, e);

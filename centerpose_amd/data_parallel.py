@@ -30,9 +30,13 @@ Which parameters have a gradient must be the same on every rank.  It is a proper
 ``project`` parameters have none anywhere); ``active_sets_differ`` says whether the last call saw it broken, and the first call
 checks it on the host and raises.
 
-BatchNorm: every rank normalises with the statistics of its own shard (no SyncBatchNorm), and between two ``sync_buffers()``
-calls each rank's running statistics are its own; ``sync_buffers()`` gives everyone rank 0's, which is what survives in the
-reference, where only replica 0's buffers are kept.
+BatchNorm: by default every rank normalises with the statistics of its own shard, and between two ``sync_buffers()`` calls
+each rank's running statistics are its own; ``sync_buffers()`` gives everyone rank 0's, which is what survives in the
+reference, where only replica 0's buffers are kept.  ``DataParallel(net, sync_batchnorm=True)`` re-classes the network's
+BatchNorm layers to ``sync_norm.SyncBatchNorm`` (``use_hip_sync_norms``): the statistics are the global batch's, the reduced
+gradient is that of the mean of the rank losses on the concatenated batch whatever the number of ranks, and the running
+statistics are identical on every rank with no ``sync_buffers()``.  The price is two small all-gathers per BatchNorm layer
+and step; every rank's shard must then hold at least one image.
 """
 import torch
 import torch.distributed as dist
@@ -41,6 +45,7 @@ from torch import nn
 from . import distributed as cpd
 from . import hip
 from .optim import _check_params, _same_layout
+from .sync_norm import use_hip_sync_norms
 
 
 class _Runtime(object):
@@ -69,8 +74,8 @@ class _Runtime(object):
 
 
 class DataParallel(nn.Module):
-    """``DataParallel(module, group=None)``: ``module`` on this process's GPU, one process per GPU (see the module text; this
-    is NOT torch's single-process ``nn.DataParallel``).  ``.module`` is the network (what ``state_dict`` consumers such as
+    """``DataParallel(module, group=None, stage_on_host=None, sync_batchnorm=False)``: ``module`` on this process's GPU, one
+    process per GPU (see the module text; this is NOT torch's single-process ``nn.DataParallel``).  ``.module`` is the network (what ``state_dict`` consumers such as
     the reference's ``save_model`` look for), ``forward`` delegates to it.  Construction broadcasts rank 0's parameters and
     buffers (two coalesced broadcasts: the float tensors, the integer ones) and allocates the zeroed flat gradient buffer on
     the module's device.  Every parameter must be float32, strided and dense, by ``optim.Adam``'s rule.
@@ -80,13 +85,18 @@ class DataParallel(nn.Module):
     "device", "pinned host" or "none" (world size 1 or no process group: no collective).  Staging is the one path that
     waits for the device.
 
+    ``sync_batchnorm=True`` first re-classes the module's BatchNorm layers to ``sync_norm.SyncBatchNorm`` over ``group``
+    (``sync_norm.use_hip_sync_norms``; what it returned is kept as ``sync_batchnorm_converted`` / ``sync_batchnorm_skipped``).
+    The default leaves the module as it is.
+
     ``layout_copies`` counts the gradients that had to be copied into their parameter's memory layout; ``pack_table_uploads``
     the uploads of the pack table (one per call whose gradient addresses changed: a few KB)."""
 
-    def __init__(self, module, group=None, stage_on_host=None):
+    def __init__(self, module, group=None, stage_on_host=None, sync_batchnorm=False):
         super().__init__()
         self.module = module
         self.group = group
+        self.sync_batchnorm_converted, self.sync_batchnorm_skipped = use_hip_sync_norms(module, group) if sync_batchnorm else ([], {})
         named = list(module.named_parameters())
         if not named:
             raise ValueError("DataParallel: the module has no parameters")

@@ -14,7 +14,7 @@ exchange is latency-bound; one un-bucketed all-gather of the whole shard is the 
 xGMI links (no ring pipeline to fill).
 
 Training across GPUs (``data_parallel.DataParallel``) uses three more helpers from here: ``shard_batch``, and the coalesced
-``broadcast_coalesced`` / ``all_reduce_sum``.
+``broadcast_coalesced`` / ``all_reduce_sum``; ``sync_norm.SyncBatchNorm`` gathers its per-rank statistics with ``all_gather_flat``.
 """
 import os
 
@@ -126,6 +126,23 @@ def _on_host_if_refused(collective, t):
 def all_reduce_sum(t, group=None):
     """In-place SUM over the ranks of one contiguous tensor."""
     _on_host_if_refused(lambda x: dist.all_reduce(x, dist.ReduceOp.SUM, group=group), t)
+
+
+def all_gather_flat(t, group=None):
+    """One contiguous 1-D tensor of the same length on every rank -> [world, len] in rank order, the bits unchanged
+    (``all_gather_into_tensor``); without a process group, [1, len].  A backend that refuses device tensors gets a host copy
+    instead (``_on_host_if_refused``); that path waits for the device."""
+    if t.dim() != 1 or not t.is_contiguous():
+        raise ValueError("all_gather_flat: one contiguous 1-D tensor, got shape %s" % (tuple(t.shape),))
+    t = t.detach()
+    if not dist.is_initialized():
+        return t.clone().unsqueeze(0)
+    rank = dist.get_rank(group)
+    n = t.numel()
+    out = torch.empty(dist.get_world_size(group) * n, dtype=t.dtype, device=t.device)   # (flat: the concatenation form)
+    out[rank * n:(rank + 1) * n].copy_(t)   # this rank's part travels with the buffer, so the host path needs no second copy
+    _on_host_if_refused(lambda o: dist.all_gather_into_tensor(o, o[rank * n:(rank + 1) * n].clone(), group=group), out)
+    return out.view(-1, n)
 
 
 @torch.no_grad()

@@ -66,6 +66,11 @@ SIGNATURES = {
     "cp_batchnorm_workspace_bytes": (c_size_t, _i * 4),
     "cp_batchnorm_forward_nhwc": (c_int, _vp * 10 + _i * 5 + [c_float, c_float, c_int] + _ws),
     "cp_batchnorm_backward_nhwc": (c_int, _vp * 11 + _i * 5 + _ws),
+    "cp_batchnorm_sync_record_floats": (c_int, _i),
+    "cp_batchnorm_sync_stats_nhwc": (c_int, _vp * 3 + _i * 4 + _ws),
+    "cp_batchnorm_sync_forward_nhwc": (c_int, _vp * 12 + _i * 5 + [c_float, c_float, c_int] + _ws),
+    "cp_batchnorm_sync_backward_reduce_nhwc": (c_int, _vp * 9 + _i * 4 + _ws),
+    "cp_batchnorm_sync_backward_apply_nhwc": (c_int, _vp * 8 + _i + _vp * 3 + _i * 4 + _ws),
     "cp_groupnorm_workspace_bytes": (c_size_t, _i * 5),
     "cp_groupnorm_forward_nhwc": (c_int, _vp * 7 + _i * 5 + [c_float, c_int] + _ws),
     "cp_groupnorm_backward_nhwc": (c_int, _vp * 10 + _i * 5 + _ws),

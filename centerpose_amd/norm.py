@@ -9,8 +9,9 @@ apply pass) and ``cp_batchnorm_backward_nhwc`` (one reduction and one apply pass
 ``BatchNorm2d`` is ``nn.BatchNorm2d`` with that forward and nothing else changed, and ``use_hip_norms(model)`` re-classes a
 tree's eligible layers in place, the contract of ``conv.use_hip_convs``.
 
-GroupNorm is ``group_norm.py``'s (``use_hip_group_norms``); ``SyncBatchNorm``, ``BatchNorm1d/3d``, bf16 and
-``num_features % 4 != 0`` are not built.
+GroupNorm is ``group_norm.py``'s (``use_hip_group_norms``); ``SyncBatchNorm``, the same layer with the statistics of a process
+group's global batch, is ``sync_norm.py``'s (``use_hip_sync_norms``, ``DataParallel(sync_batchnorm=True)``).  ``BatchNorm1d/3d``,
+bf16 and ``num_features % 4 != 0`` are not built.
 """
 import torch
 from torch import nn

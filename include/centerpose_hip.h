@@ -399,6 +399,51 @@ int cp_batchnorm_backward_nhwc(cp_stream_t stream, const float* x, const float* 
                                size_t workspace_bytes);
 
 /* ------------------------------------------------------------------------------------------
+ * SyncBatchNorm — the training BatchNorm above with the statistics of the GLOBAL batch of a process group (one process per
+ *   GPU, the batch sharded by images), and the gradients that go with them.  The library holds no communicator: each pass is
+ *   two calls with one all-gather of the caller's between them, and every rank calls them with the same `world` and C.
+ * Tensors, layouts, NULL conventions and constraints are cp_batchnorm_*'s; the workspace is cp_batchnorm_workspace_bytes'.
+ * Forward, phase A, cp_batchnorm_sync_stats_nhwc: this rank's record = mean[C] | M2[C] | count, M2 = sum (x - mean)^2 over
+ *   the rank's B*H*W values per channel (one value is allowed: M2 = 0).  A record is cp_batchnorm_sync_record_floats(C) =
+ *   2 C + 4 floats (0 for a refused C); the count is carried exactly, as a 32-bit integer's bit pattern in the first word of
+ *   the last 16-byte slot (the other three words zero), so the records must be moved as bits (an all-gather), never summed.
+ * Forward, phase B, cp_batchnorm_sync_forward_nhwc: records = [world][record_floats] in rank order.  The ranks are merged by
+ *   Chan's many-way rule in rank order about rank 0's mean, with the expressions that merge a tensor's slabs in
+ *   cp_batchnorm_forward_nhwc: n = sum n_r, mean = m_0 + sum n_r (m_r - m_0) / n, M2 = sum M2_r + n_r (m_r - mean)^2,
+ *   save_invstd = 1 / sqrt(M2 / n + eps); running_mean / running_var are updated as above, the variance unbiased by the
+ *   global n / (n - 1).  Every rank therefore computes bit-identical save_mean, save_invstd and running statistics.
+ *   *save_count (one float on the device) = n; the backward reads it there.  Then y as above.  Every record's count must be
+ *   at least 1 (not checked: the records are on the device).
+ * Backward, phase A, cp_batchnorm_sync_backward_reduce_nhwc: with the global save_mean / save_invstd, sums = [2][C]: sum g
+ *   and invstd * sum g (x - mean) over this rank's values (g gated by y > 0 as above); grad_beta / grad_gamma, when given, are
+ *   copies: the LOCAL sums, which a data-parallel gradient reduction averages like every other parameter gradient.
+ * Backward, phase B, cp_batchnorm_sync_backward_apply_nhwc: sums_all = [world][2][C] in rank order is added in rank order
+ *   (S1, S2), then grad_x = gamma * invstd * (g - S1 / n - xhat * S2 / n) with n = *save_count; grad_residual = g.
+ * With world == 1 every output is bitwise that of cp_batchnorm_forward_nhwc / _backward_nhwc (training).  No atomics; all
+ * outputs are bitwise reproducible call to call.
+ * Refused with CP_ERR_INVALID and a cp_last_error() text before any launch: what cp_batchnorm_* refuses for the shape, NULL
+ * pointers, alignment and the workspace; world outside 1..1024; a global count below 2 (world == 1 with B*H*W < 2).  Launch
+ * on `stream`, never synchronise.
+ * ------------------------------------------------------------------------------------------ */
+int cp_batchnorm_sync_record_floats(int C);
+int cp_batchnorm_sync_stats_nhwc(cp_stream_t stream, const float* x, float* record, int B, int H, int W, int C, void* workspace,
+                                 size_t workspace_bytes);
+int cp_batchnorm_sync_forward_nhwc(cp_stream_t stream, const float* x, const float* gamma_or_null, const float* beta_or_null,
+                                   const float* residual_or_null, float* running_mean_or_null, float* running_var_or_null,
+                                   float* y, float* save_mean, float* save_invstd, float* save_count, const float* records,
+                                   int world, int B, int H, int W, int C, float momentum, float eps, int act, void* workspace,
+                                   size_t workspace_bytes);
+int cp_batchnorm_sync_backward_reduce_nhwc(cp_stream_t stream, const float* x, const float* y_or_null, const float* grad_out,
+                                           const float* save_mean, const float* save_invstd, float* sums,
+                                           float* grad_gamma_or_null, float* grad_beta_or_null, int B, int H, int W, int C,
+                                           void* workspace, size_t workspace_bytes);
+int cp_batchnorm_sync_backward_apply_nhwc(cp_stream_t stream, const float* x, const float* y_or_null, const float* grad_out,
+                                          const float* gamma_or_null, const float* save_mean, const float* save_invstd,
+                                          const float* sums_all, int world, const float* save_count, float* grad_x_or_null,
+                                          float* grad_residual_or_null, int B, int H, int W, int C, void* workspace,
+                                          size_t workspace_bytes);
+
+/* ------------------------------------------------------------------------------------------
  * GroupNorm for training, fused with the ReLU — nn.GroupNorm(G, C) and the ReLU behind it in the dlav1_34 heads of
  *   models/networks/pose_dla_dcn.py:491-521 (groups by models/networks/GN.py), forward and backward:
  *     y = act(xhat * gamma + beta),  xhat = (x - mean) * invstd,  act: 0 none, 1 relu.

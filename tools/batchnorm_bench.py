@@ -13,6 +13,13 @@ ceiling.  Byte model, in units of the activation's bytes T = B*C*H*W*4 -- a mode
     backward   library 8 T (reduce: x, grad_out, y; apply: the same  torch 8 T (ReLU 3 T, BN backward 5 T; the add's backward
                three in, grad_x and grad_residual out)                      moves nothing)
 There is no speed gate: the reference time is torch's on the same device in the same run.
+
+    python tools/batchnorm_bench.py --sync [--out profiles/sync_batchnorm_bench.txt]
+
+SyncBatchNorm's four device phases (hip.sync_norm: stats, forward, backward_reduce, backward_apply) next to the plain operator
+(hip.batch_norm_forward + hip.batch_norm_backward) on the same shapes, one GPU, NO collective: the records and sums of 1 and
+of 8 ranks are built by hand, this rank's own repeated.  Same timing scheme, the three sides alternating.  What it shows is
+the device cost the phases add to a step (the merge launches); what the two all-gathers per layer cost is not in it.
 """
 import argparse
 import json
@@ -33,6 +40,72 @@ DLA34_512 = [("base / level0", 16, 512), ("level1", 32, 256), ("level2, ida node
              ("dla_up / ida proj", 64, 64), ("ida proj", 64, 32)]
 
 
+def _timed(fn, iters):
+    import torch
+
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters
+
+
+def _write(out, lines):
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+def sync_main(a, dev):
+    """--sync: one training step of the layer (forward + backward, residual and ReLU) at the binding's level, NHWC."""
+    import torch
+
+    from centerpose_amd import hip
+
+    S, B, lines = hip.sync_norm, a.batch, []
+    for where, C, R in DLA34_512:
+        g = torch.Generator(device=dev).manual_seed(1)
+        x, res, go = (torch.randn(B, R, R, C, device=dev, generator=g) for _ in range(3))
+        w, b = 1 + 0.5 * torch.randn(C, device=dev, generator=g), torch.randn(C, device=dev, generator=g)
+        rm, rv = torch.zeros(C, device=dev), torch.ones(C, device=dev)
+
+        def plain():
+            y, mean, invstd = hip.batch_norm_forward(x, w, b, res, rm, rv, True, 0.1, 1e-5, 1)
+            return hip.batch_norm_backward(x, go, mean, invstd, gamma=w, y=y, need_residual_grad=True)
+
+        def sync(world):
+            records = S.stats(x).repeat(world, 1)   # the all-gather's output, by hand
+            y, mean, invstd, count = S.forward(x, records, w, b, res, rm, rv, 0.1, 1e-5, 1)
+            sums, gg, gb = S.backward_reduce(x, go, mean, invstd, y=y)
+            return S.backward_apply(x, go, mean, invstd, count, sums.repeat(world, 1), gamma=w, y=y, need_residual_grad=True) + (gg, gb)
+
+        sides = {"plain": plain, "sync_world1": lambda: sync(1), "sync_world8": lambda: sync(8)}
+        for fn in sides.values():   # warm-up of all before anything is timed
+            for _ in range(2):
+                fn()
+        ms = {s: [] for s in sides}
+        for _ in range(a.rounds):
+            for s, fn in sides.items():   # alternating
+                ms[s].append(_timed(fn, a.iters))
+        same = all(torch.equal(p, q) for p, q in zip(plain(), sync(1)))
+        med = {s: statistics.median(v) for s, v in ms.items()}
+        line = {"where": where, "B": B, "C": C, "HxW": R, "step_ms": {s: round(med[s], 4) for s in sides},
+                "sync_world1_over_plain": round(med["sync_world1"] / med["plain"], 2),
+                "sync_world8_over_plain": round(med["sync_world8"] / med["plain"], 2),
+                "extra_us_world1": round(1e3 * (med["sync_world1"] - med["plain"]), 1),
+                "extra_us_world8": round(1e3 * (med["sync_world8"] - med["plain"]), 1),
+                "step_ms_rounds": {s: [round(v, 4) for v in ms[s]] for s in sides}, "world1_bitwise_plain": same}
+        print(json.dumps(line), flush=True)
+        lines.append(json.dumps(line))
+        del x, res, go
+        torch.cuda.empty_cache()
+    _write(a.out, lines)
+
+
 def main():
     import torch
     import torch.nn.functional as F
@@ -44,22 +117,15 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--sync", action="store_true", help="time SyncBatchNorm's four phases against the plain operator")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("batchnorm_bench: no HIP device (there is nothing to measure on the CPU)")
     dev = torch.device("cuda:0")
+    if a.sync:
+        return sync_main(a, dev)
     B = a.batch
-
-    def timed(fn):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record()
-        for _ in range(a.iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / a.iters
-
+    timed = lambda fn: _timed(fn, a.iters)
     lines = []
     for where, C, R in DLA34_512:
         g = torch.Generator(device=dev).manual_seed(1)
@@ -117,10 +183,7 @@ def main():
         lines.append(json.dumps(line))
         del x, res, go, w, b, sides
         torch.cuda.empty_cache()
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    _write(a.out, lines)
 
 
 if __name__ == "__main__":
