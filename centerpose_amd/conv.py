@@ -10,37 +10,18 @@ torch moves its convolutions onto the library in one line and keeps its paramete
 BatchNorm and the residual adds are ``norm.py``'s (``use_hip_norms``); pooling and everything else stay torch's; dilation, groups
 and ``in_channels % 4 != 0`` are not built.
 """
-import torch
 from torch import nn
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import hip as _hip
-
-
-def _nhwc(t):
-    """Logical [B,C,H,W] tensor -> its values as a contiguous [B,H,W,C] tensor (no copy when it is channels_last already)."""
-    return _hip._nhwc_view(t).permute(0, 2, 3, 1)
+from ._layers import _nhwc, _on_device, _one, _reclass, _same
 
 
 class _Conv2dFn(Function):
     @staticmethod
     def forward(ctx, x, weight, bias, stride, pad, relu):
-        xh = _nhwc(x)
-        w = _hip._dev(weight)
-        cout = w.shape[0]
-        wf, shift = w, None
-        if bias is not None:
-            # the forward operator reads `shift` up to its N tile: pad the weight and the bias with zero channels, slice the output
-            tile = 16 if cout <= 16 else 32 if cout <= 32 else 128 if cout % 128 == 0 else 64
-            cpad = (cout + tile - 1) // tile * tile
-            shift = _hip._dev(bias)
-            if cpad != cout:
-                wf = torch.cat([w, w.new_zeros((cpad - cout,) + tuple(w.shape[1:]))])
-                shift = torch.cat([shift, shift.new_zeros(cpad - cout)])
-        y = _hip.conv2d_nhwc(xh, wf, shift=shift, stride=stride, pad=pad, act=1 if relu else 0)
-        if y.shape[3] != cout:
-            y = y[..., :cout].contiguous()
+        y = _hip.conv2d_nhwc(_nhwc(x), weight, shift=bias, stride=stride, pad=pad, act=1 if relu else 0)
         ctx.stride, ctx.pad, ctx.relu, ctx.has_bias = stride, pad, relu, bias is not None
         if relu:
             ctx.save_for_backward(x, weight, y)
@@ -62,16 +43,6 @@ class _Conv2dFn(Function):
         return (gx.permute(0, 3, 1, 2) if need_x else None, gw if need_w else None, gb if need_b else None, None, None, None)
 
 
-def _pair(v, what):
-    if isinstance(v, str):
-        raise NotImplementedError("conv2d: string %s is not built" % what)
-    if isinstance(v, (tuple, list)):
-        if len(v) != 2 or v[0] != v[1]:
-            raise NotImplementedError("conv2d: %s must be the same on both axes, got %r" % (what, tuple(v)))
-        v = v[0]
-    return int(v)
-
-
 def _geometry_refusal(cin, kh, kw, stride, pad):
     """Why the kernels cannot run a convolution of this geometry, or None: the one rule of ``conv2d``, ``Conv2d`` and
     ``use_hip_convs``, and the library's own for the backward (``conv_bwd_shape_error``, csrc/ops.hip).  Kernel 1..7 on each axis,
@@ -88,12 +59,11 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, relu=False):
     the device, NCHW-contiguous or channels_last (the kernels read NHWC; channels_last costs no copy); the result is
     channels_last.  Dilation 1, groups 1, and the geometry of ``_geometry_refusal``: what the backward refuses raises
     NotImplementedError here, before the forward runs."""
-    if not x.is_cuda:
-        raise RuntimeError("centerpose_hip: tensors must live on the HIP device (no CPU path)")
+    _on_device(x)
     if x.dim() != 4 or weight.dim() != 4 or weight.shape[1] != x.shape[1]:
         raise RuntimeError("conv2d: x must be [B,Cin,H,W] and weight [Cout,Cin,KH,KW], got %s and %s"
                            % (tuple(x.shape), tuple(weight.shape)))
-    stride, padding = _pair(stride, "stride"), _pair(padding, "padding")
+    stride, padding = _one(stride, "conv2d", "stride"), _one(padding, "conv2d", "padding")
     why = _geometry_refusal(int(weight.shape[1]), int(weight.shape[2]), int(weight.shape[3]), stride, padding)
     if why:
         raise NotImplementedError("conv2d: " + why)
@@ -110,7 +80,7 @@ def _refusal(m):
         return "padding_mode %r (only 'zeros' is built)" % m.padding_mode
     if isinstance(m.padding, str):
         return "string padding %r" % m.padding
-    if m.stride[0] != m.stride[1] or m.padding[0] != m.padding[1]:
+    if not (_same(m.stride) and _same(m.padding)):
         return "stride / padding differ between the axes"
     return _geometry_refusal(m.in_channels, m.kernel_size[0], m.kernel_size[1], m.stride[0], m.padding[0])
 
@@ -135,19 +105,5 @@ def use_hip_convs(module):
     module names and the state-dict keys stay as they are.  Returns ``(converted, skipped)``: the converted modules' names and
     ``{name: reason}`` for the convolutions left alone (groups, dilation, ``in_channels % 4``, transposed or subclassed
     convolutions).  Modules that already are ``Conv2d`` appear in neither."""
-    converted, skipped = [], {}
-    for name, m in module.named_modules():
-        if isinstance(m, Conv2d):
-            continue
-        if isinstance(m, nn.ConvTranspose2d):
-            skipped[name] = "ConvTranspose2d is not built"
-        elif type(m) is nn.Conv2d:
-            why = _refusal(m)
-            if why:
-                skipped[name] = why
-            else:
-                m.__class__ = Conv2d
-                converted.append(name)
-        elif isinstance(m, nn.Conv2d):
-            skipped[name] = "subclass %s of nn.Conv2d keeps its own forward" % type(m).__name__
-    return converted, skipped
+    return _reclass(module, (nn.Conv2d,), Conv2d, _refusal, of=" of nn.Conv2d",
+                    unbuilt=((nn.ConvTranspose2d, "ConvTranspose2d is not built"),))

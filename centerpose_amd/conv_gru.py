@@ -17,7 +17,8 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import hip as _hip
-from .conv import Conv2d, _nhwc, conv2d
+from ._layers import _nhwc, _on_device
+from .conv import Conv2d, conv2d
 
 
 class _GruGateFn(Function):
@@ -51,8 +52,7 @@ def gru_gate(x3, h3=None, hprev=None):
     and ``h3`` = [Whr h | Whz h | Whn h] as logical [B,3 Ch,H,W] tensors, ``hprev`` [B,Ch,H,W] -> the new state [B,Ch,H,W]
     (channels_last), ``(1 - z) n + z hprev`` with ``r = sigmoid(x3r + h3r)``, ``z = sigmoid(x3z + h3z)``, ``n = tanh(x3n + r h3n)``.
     ``h3 = hprev = None`` is step 0: the state is zero.  ``Ch % 4 == 0``, float32."""
-    if not x3.is_cuda:
-        raise RuntimeError("centerpose_hip: tensors must live on the HIP device (no CPU path)")
+    _on_device(x3)
     if (h3 is None) != (hprev is None):
         raise RuntimeError("gru_gate: h3 and hprev are given together, or neither (step 0)")
     if x3.dim() != 4 or x3.shape[1] % 12:

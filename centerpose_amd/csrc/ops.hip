@@ -103,18 +103,50 @@ int pack_f16x3(const Pack16& r, const float* wt, const float* scale, int taps, C
     return rc;
 }
 
-// cp_conv2d_nhwc: f32 packed weights [kpad][cpad] + the f16x3 regions
-struct Conv2dWs {
-    float* wp;
+// One convolution's operands in an operator's workspace.  The float32 ones back to back, so that one memset zeroes all `bytes`
+// of them: the packed weight [kpad][cpad] and the epilogue vectors, cpad floats each because the kernels read them up to the
+// N tile (scale: only where the operator takes one).  Then the f16x3 regions, where the operator has that form.
+struct ConvOps {
+    float *wp, *scale, *shift;
+    size_t bytes;
     Pack16 f16;
 };
-Conv2dWs conv2d_carve(Carve& c, int Cin, int Cout, int KH, int KW) {
-    const size_t kpad = align_up((size_t)KH * KW * Cin, 16);
-    const size_t cpad = align_up((size_t)Cout, cp_conv_tile_n(Cout));
-    Conv2dWs r;
+ConvOps carve_conv_ops(Carve& c, size_t kpad, size_t cpad, bool with_scale, bool with_f16) {
+    const size_t start = c.off;
+    ConvOps r{};
     r.wp = c.take<float>(kpad * cpad * sizeof(float));
-    r.f16 = carve_pack16(c, kpad, cpad);
+    r.scale = with_scale ? c.take<float>(cpad * sizeof(float)) : nullptr;
+    r.shift = c.take<float>(cpad * sizeof(float));
+    r.bytes = c.off - start;
+    if (with_f16) r.f16 = carve_pack16(c, kpad, cpad);
     return r;
+}
+
+// What cp_conv2d_nhwc, cp_dcnv2_forward and each layer of cp_pose_heads_forward do with a PyTorch-layout weight `w`
+// ([Cout][Cin][KH][KW]) before they launch: zero the regions `r`, pack the weight, copy the Cout floats of each given
+// epilogue vector into its zero-padded region and, with `f16x3` (the caller chose those kernels), pack their operands from
+// the same weight and measure the input (pack_f16x3: x, nx, om, px).  `cw` describes the staged operands.
+int stage_conv(ConvW& cw, const ConvOps& r, bool f16x3, const float* w, const float* scale, const float* shift, int Cin,
+               int Cout, int KH, int KW, const float* x, size_t nx, const float* om, size_t px, hipStream_t s) {
+    cw = conv_w_f32(r.wp, scale ? r.scale : nullptr, shift ? r.shift : nullptr, Cin, Cout, KH, KW);
+    if (hipMemsetAsync(r.wp, 0, r.bytes, s) != hipSuccess) return CP_ERR_LAUNCH;
+    const int rc = cp_launch_pack_weight(w, r.wp, Cout, Cin, KH * KW, Cin, cw.CoutPad, 0, s);
+    if (rc != CP_OK) return rc;
+    if ((scale && hipMemcpyAsync(r.scale, scale, (size_t)Cout * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) ||
+        (shift && hipMemcpyAsync(r.shift, shift, (size_t)Cout * 4, hipMemcpyDeviceToDevice, s) != hipSuccess))
+        return CP_ERR_LAUNCH;
+    return f16x3 ? pack_f16x3(r.f16, w, scale, KH * KW, cw, x, nx, om, px, s) : CP_OK;
+}
+
+// Launches `p`, built from stage_conv's `cw`: on the f16x3 kernels with `f16x3` where they take the launch, else in float32
+int launch_conv(ConvParams& p, const ConvW& cw, const ConvOps& r, bool f16x3, hipStream_t s) {
+    const unsigned* slot = r.f16.slot;
+    return f16x3 && conv_params_f16(p, cw, &slot, true) ? cp_launch_conv16(p, s) : cp_launch_conv(p, s);
+}
+
+// cp_conv2d_nhwc: the float32 operands (scale and shift included) + the f16x3 regions
+ConvOps conv2d_carve(Carve& c, int Cin, int Cout, int KH, int KW) {
+    return carve_conv_ops(c, align_up((size_t)KH * KW * Cin, 16), align_up((size_t)Cout, cp_conv_tile_n(Cout)), true, true);
 }
 
 // cp_conv_transpose2d_nhwc: float32 sub-kernels + two binary16 copies + 2^-e per row + scale * 2^-e + the input's |max| slot
@@ -139,8 +171,8 @@ DeconvWs deconv_carve(Carve& c, int Cin, int Cout) {
 // cp_dcnv2_forward (fast path): [x NHWC B*H*W*C][offmask NHWC B*H*W*32][y NHWC B*H*W*Co][packed weights][shift cpad] + the
 // f16x3 regions
 struct DcnWs {
-    float *x, *om, *y, *wp, *shift;
-    Pack16 f16;
+    float *x, *om, *y;
+    ConvOps ops;
 };
 DcnWs dcn_carve(Carve& c, int B, int C, int H, int W, int Co) {
     const size_t px = (size_t)B * H * W;
@@ -149,9 +181,7 @@ DcnWs dcn_carve(Carve& c, int B, int C, int H, int W, int Co) {
     r.x = c.take<float>(px * C * 4);
     r.om = c.take<float>(px * 32 * 4);
     r.y = c.take<float>(px * Co * 4);
-    r.wp = c.take<float>((size_t)9 * C * cpad * 4);
-    r.shift = c.take<float>(cpad * 4);
-    r.f16 = carve_pack16(c, (size_t)9 * C, cpad);
+    r.ops = carve_conv_ops(c, (size_t)9 * C, cpad, false, true);
     return r;
 }
 
@@ -257,17 +287,14 @@ const char* gru_shape_error(int M, int Ch) {
 
 // cp_pose_heads_forward: per head the 3x3 layer's float32 and f16x3 operands + bias, the 1x1 layer's, one hidden chunk
 struct HeadsFwdWs {
-    float *wp0, *shift0, *wp1, *shift1, *hid;
-    Pack16 f16;
+    ConvOps ops0, ops1;
+    float* hid;
 };
 HeadsFwdWs heads_fwd_carve(Carve& c, int B, int H, int W, int Cin, int hid) {
     const size_t k0 = (size_t)9 * Cin, hpad = align_up((size_t)hid, cp_conv_tile_n(hid));
     HeadsFwdWs r;
-    r.wp0 = c.take<float>(k0 * hpad * 4);
-    r.shift0 = c.take<float>(hpad * 4);
-    r.wp1 = c.take<float>((size_t)hid * 64 * 4);
-    r.shift1 = c.take<float>(64 * 4);
-    r.f16 = carve_pack16(c, k0, hpad);
+    r.ops0 = carve_conv_ops(c, k0, hpad, false, true);
+    r.ops1 = carve_conv_ops(c, (size_t)hid, 64, false, false);
     r.hid = c.take<float>((size_t)cp_pose_heads_chunk(B, H, W, hid) * H * W * hid * 4);
     return r;
 }
@@ -314,22 +341,14 @@ int cp_pose_heads_forward(cp_stream_t stream, const float* feat, int n, const fl
     if (workspace_bytes < c.off) return fail(CP_ERR_INVALID, "pose_heads_forward: workspace too small");
     hipStream_t s = (hipStream_t)stream;
     const int HW = H * W, chunk = cp_pose_heads_chunk(B, H, W, hid);
+    // range-safe f16x3 operands of the 3x3 layer, as cp_conv2d_nhwc builds them; the 1x1 layer stays exact
     const bool f16x3 = g_default_precision == CP_PREC_F16X3;
     for (int i = 0; i < n; ++i) {
         const int cls = classes[i];
-        ConvW c0 = conv_w_f32(r.wp0, nullptr, r.shift0, Cin, hid, 3, 3);
-        const ConvW c1 = conv_w_f32(r.wp1, nullptr, r.shift1, hid, cls, 1, 1);
-        if (hipMemsetAsync(r.wp0, 0, (char*)r.f16.hi - (char*)r.wp0, s) != hipSuccess) return CP_ERR_LAUNCH;
-        int rc = cp_launch_pack_weight(w0[i], r.wp0, hid, Cin, 9, Cin, c0.CoutPad, 0, s);
-        if (rc == CP_OK) rc = cp_launch_pack_weight(w1[i], r.wp1, cls, hid, 1, hid, c1.CoutPad, 0, s);
+        ConvW c0, c1;
+        int rc = stage_conv(c0, r.ops0, f16x3, w0[i], nullptr, b0[i], Cin, hid, 3, 3, feat, (size_t)B * HW * Cin, nullptr, 0, s);
+        if (rc == CP_OK) rc = stage_conv(c1, r.ops1, false, w1[i], nullptr, b1[i], hid, cls, 1, 1, nullptr, 0, nullptr, 0, s);
         if (rc != CP_OK) return fail(rc, "pose_heads_forward: weight packing failed");
-        if (hipMemcpyAsync(r.shift0, b0[i], (size_t)hid * 4, hipMemcpyDeviceToDevice, s) != hipSuccess ||
-            hipMemcpyAsync(r.shift1, b1[i], (size_t)cls * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)
-            return CP_ERR_LAUNCH;
-        if (f16x3) {  // range-safe f16x3 operands of the 3x3 layer, as cp_conv2d_nhwc builds them; the 1x1 layer stays exact
-            rc = pack_f16x3(r.f16, w0[i], nullptr, 9, c0, feat, (size_t)B * HW * Cin, nullptr, 0, s);
-            if (rc != CP_OK) return fail(rc, "pose_heads_forward: f16x3 packing failed");
-        }
         for (int b = 0; b < B; b += chunk) {
             const int nb = std::min(chunk, B - b);
             const float* src = feat + (size_t)b * HW * Cin;
@@ -337,12 +356,7 @@ int cp_pose_heads_forward(cp_stream_t stream, const float* feat, int n, const fl
             p.out = r.hid;
             p.store = CP_STORE_NHWC;
             p.ldo = hid;
-            const unsigned* slot = r.f16.slot;
-            if (f16x3 && conv_params_f16(p, c0, &slot, true)) rc = cp_launch_conv16(p, s);
-            else {
-                p.w16_hi = p.w16_lo = p.w16f_hi = p.w16f_lo = nullptr;
-                rc = cp_launch_conv(p, s);
-            }
+            rc = launch_conv(p, c0, r.ops0, f16x3, s);
             if (rc != CP_OK) return fail(rc, "pose_heads_forward: 3x3 launch failed");
             const float* hsrc = r.hid;
             ConvParams q = conv_params(nb, H, W, &hsrc, &hid, 1, c1, 1, 0, CP_ACT_NONE);
@@ -395,23 +409,24 @@ size_t cp_dcnv2_workspace_bytes(int B, int C, int H, int W, int Co) {
 
 int cp_conv_transpose2d_nhwc(cp_stream_t stream, const float* x, const float* w, const float* scale, const float* shift, float* out,
                              int B, int H, int W, int Cin, int Cout, int act, void* workspace, size_t workspace_bytes) {
-    if (!x || !w || !out || !workspace) return fail(CP_ERR_INVALID, "null argument");
-    if (B < 1 || H < 1 || W < 1 || Cout < 1) return fail(CP_ERR_INVALID, "empty shape");
-    if (Cin % 32) return fail(CP_ERR_INVALID, "Cin must be a multiple of 32");
-    if (act != CP_ACT_NONE && act != CP_ACT_RELU) return fail(CP_ERR_INVALID, "act must be 0 (none) or 1 (relu)");
+    if (!x || !w || !out || !workspace) return fail(CP_ERR_INVALID, "conv_transpose2d_forward: null argument");
+    if (B < 1 || H < 1 || W < 1 || Cout < 1) return fail(CP_ERR_INVALID, "conv_transpose2d_forward: empty shape");
+    if (Cin % 32) return fail(CP_ERR_INVALID, "conv_transpose2d_forward: Cin must be a multiple of 32");
+    if (act != CP_ACT_NONE && act != CP_ACT_RELU)
+        return fail(CP_ERR_INVALID, "conv_transpose2d_forward: act must be 0 (none) or 1 (relu)");
     Carve c{(char*)workspace};
     const DeconvWs r = deconv_carve(c, Cin, Cout);
-    if (workspace_bytes < c.off) return fail(CP_ERR_INVALID, "workspace too small");
+    if (workspace_bytes < c.off) return fail(CP_ERR_INVALID, "conv_transpose2d_forward: workspace too small");
     hipStream_t s = (hipStream_t)stream;
     const bool f16x3 = g_default_precision == CP_PREC_F16X3;
     int rc = cp_launch_pack_deconv(w, f16x3 ? nullptr : r.wf, f16x3 ? r.hi : nullptr, f16x3 ? r.lo : nullptr, r.inv, Cin, Cout, s);
     if (rc == CP_OK && f16x3) {
         // range-safe operands as in cp_conv2d_nhwc: per-channel weight scale (folded into scale16), per-tensor activation scale
-        if (hipMemsetAsync(r.slot, 0, kSlotBytes, s) != hipSuccess) return CP_ERR_LAUNCH;
-        rc = cp_launch_scale16(scale, r.inv, r.sc16, Cout, s);
+        if (hipMemsetAsync(r.slot, 0, kSlotBytes, s) != hipSuccess) rc = CP_ERR_LAUNCH;
+        if (rc == CP_OK) rc = cp_launch_scale16(scale, r.inv, r.sc16, Cout, s);
         if (rc == CP_OK) rc = cp_launch_absmax(x, (size_t)B * H * W * Cin, r.slot, s);
     }
-    if (rc != CP_OK) return fail(rc, "deconv weight packing failed");
+    if (rc != CP_OK) return fail(rc, "conv_transpose2d_forward: deconv weight packing failed");
     DeconvW d;
     d.wf = r.wf;
     d.hi = r.hi;
@@ -422,38 +437,30 @@ int cp_conv_transpose2d_nhwc(cp_stream_t stream, const float* x, const float* w,
     d.Cin = Cin;
     d.Cout = Cout;
     rc = cp_launch_deconv(deconv_launch(d, f16x3, x, f16x3 ? r.slot : nullptr, B, H, W, out, nullptr, act == CP_ACT_RELU), s);
-    return rc == CP_OK ? CP_OK : fail(rc, "deconv launch failed (shape too large for 32-bit offsets?)");
+    return rc == CP_OK ? CP_OK : fail(rc, "conv_transpose2d_forward: deconv launch failed (shape too large for 32-bit offsets?)");
 }
 
 int cp_conv2d_nhwc(cp_stream_t stream, const float* x, const float* w, const float* scale, const float* shift,
                    const float* residual, float* out, int B, int H, int W, int Cin, int Cout, int KH, int KW,
                    int stride, int pad, int act, void* workspace, size_t workspace_bytes) {
-    if (!x || !w || !out || !workspace) return fail(CP_ERR_INVALID, "null argument");
-    if (Cin % 4) return fail(CP_ERR_INVALID, "Cin must be a multiple of 4");
+    if (!x || !w || !out || !workspace) return fail(CP_ERR_INVALID, "conv2d_forward: null argument");
+    if (Cin % 4) return fail(CP_ERR_INVALID, "conv2d_forward: Cin must be a multiple of 4");
     Carve c{(char*)workspace};
-    const Conv2dWs r = conv2d_carve(c, Cin, Cout, KH, KW);
-    if (workspace_bytes < c.off) return fail(CP_ERR_INVALID, "workspace too small");
+    const ConvOps r = conv2d_carve(c, Cin, Cout, KH, KW);
+    if (workspace_bytes < c.off) return fail(CP_ERR_INVALID, "conv2d_forward: workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    const int bn = cp_conv_tile_n(Cout);
-    ConvW cw = conv_w_f32(r.wp, scale, shift, Cin, Cout, KH, KW);
-    // scale/shift are read up to CoutPad: only allow un-padded Cout when they are given
-    if ((scale || shift) && cw.CoutPad != Cout) return fail(CP_ERR_INVALID, "scale/shift need Cout % tile_n == 0");
-    if (hipMemsetAsync(r.wp, 0, (size_t)cw.Kpad * cw.CoutPad * sizeof(float), s) != hipSuccess) return CP_ERR_LAUNCH;
-    int rc = cp_launch_pack_weight(w, r.wp, Cout, Cin, KH * KW, Cin, cw.CoutPad, 0, s);
-    if (rc != CP_OK) return rc;
+    const bool f16x3 = g_default_precision == CP_PREC_F16X3 && Cin % 32 == 0 && KH * KW <= 32 && cp_conv_tile_n(Cout) >= 32;
+    ConvW cw;
+    int rc = stage_conv(cw, r, f16x3, w, scale, shift, Cin, Cout, KH, KW, x, (size_t)B * H * W * Cin, nullptr, 0, s);
+    if (rc != CP_OK) return fail(rc, "conv2d_forward: weight packing failed");
     ConvParams p = conv_params(B, H, W, &x, &Cin, 1, cw, stride, pad, act);
     p.res = residual;
     p.res_ld = Cout;
     p.out = out;
     p.store = CP_STORE_NHWC;
     p.ldo = Cout;
-    if (g_default_precision == CP_PREC_F16X3 && Cin % 32 == 0 && KH * KW <= 32 && bn >= 32) {
-        rc = pack_f16x3(r.f16, w, scale, KH * KW, cw, x, (size_t)B * H * W * Cin, nullptr, 0, s);
-        if (rc != CP_OK) return rc;
-        const unsigned* slot = r.f16.slot;
-        if (conv_params_f16(p, cw, &slot, true)) return cp_launch_conv16(p, s);
-    }
-    return cp_launch_conv(p, s);
+    rc = launch_conv(p, cw, r, f16x3, s);
+    return rc == CP_OK ? CP_OK : fail(rc, "conv2d_forward: kernel launch failed");
 }
 
 int cp_conv2d_backward_path(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
@@ -877,7 +884,7 @@ int cp_dcnv2_forward(cp_stream_t stream, const float* input, const float* weight
                      const float* mask, float* output, int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw,
                      int ph, int pw, int dh, int dw, int deformable_group, void* workspace, size_t workspace_bytes) {
     if (!input || !weight || !bias || !offset || !mask || !output || !workspace)
-        return fail(CP_ERR_INVALID, "null argument");
+        return fail(CP_ERR_INVALID, "dcn_v2_forward: null argument");
     if (B < 1 || C < 1 || H < 1 || W < 1 || Co < 1 || kh < 1 || kw < 1 || sh < 1 || sw < 1 || ph < 0 || pw < 0 || dh < 1 ||
         dw < 1 || deformable_group < 1 || C % deformable_group != 0)
         return fail(CP_ERR_INVALID, "dcn_v2_forward: bad shape argument (C must be divisible by deformable_group)");
@@ -895,34 +902,24 @@ int cp_dcnv2_forward(cp_stream_t stream, const float* input, const float* weight
     }
     Carve c{(char*)workspace};
     const DcnWs r = dcn_carve(c, B, C, H, W, Co);
-    if (workspace_bytes < c.off) return fail(CP_ERR_INVALID, "workspace too small");
+    if (workspace_bytes < c.off) return fail(CP_ERR_INVALID, "dcn_v2_forward: workspace too small");
     const size_t px = (size_t)B * H * W;
-    ConvW cw = conv_w_f32(r.wp, nullptr, r.shift, C, Co, 3, 3);
     int rc = cp_launch_nchw_to_nhwc(input, r.x, B, C, H, W, C, s);
-    if (rc != CP_OK) return rc;
+    if (rc != CP_OK) return fail(rc, "dcn_v2_forward: input re-layout failed");
     hipLaunchKernelGGL(dcn_offmask_pack_kernel, dim3(2048), dim3(256), 0, s, offset, mask, r.om, B, H * W);
-    if (hipMemsetAsync(r.wp, 0, (size_t)9 * C * cw.CoutPad * 4, s) != hipSuccess) return CP_ERR_LAUNCH;
-    if (hipMemsetAsync(r.shift, 0, (size_t)cw.CoutPad * 4, s) != hipSuccess) return CP_ERR_LAUNCH;
-    if (hipMemcpyAsync(r.shift, bias, (size_t)Co * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return CP_ERR_LAUNCH;
-    rc = cp_launch_pack_weight(weight, r.wp, Co, C, 9, C, cw.CoutPad, 0, s);
-    if (rc != CP_OK) return rc;
+    const bool f16x3 = g_default_precision == CP_PREC_F16X3 && C % 32 == 0;
+    ConvW cw;
+    rc = stage_conv(cw, r.ops, f16x3, weight, nullptr, bias, C, Co, 3, 3, r.x, px * C, r.om, px, s);
+    if (rc != CP_OK) return fail(rc, "dcn_v2_forward: weight packing failed");
     const float* src = r.x;
     ConvParams p = conv_params(B, H, W, &src, &C, 1, cw, 1, 1, CP_ACT_NONE);
     p.out = r.y;
     p.store = CP_STORE_NHWC;
     p.ldo = Co;
     p.offmask = r.om;
-    bool use16 = false;
-    if (g_default_precision == CP_PREC_F16X3 && C % 32 == 0) {
-        rc = pack_f16x3(r.f16, weight, nullptr, 9, cw, r.x, px * C, r.om, px, s);
-        if (rc != CP_OK) return rc;
-        const unsigned* slot = r.f16.slot;
-        use16 = conv_params_f16(p, cw, &slot, true);
-        if (!use16) p.w16_hi = p.w16_lo = nullptr;
-    }
-    rc = use16 ? cp_launch_conv16(p, s) : cp_launch_conv(p, s);
-    if (rc != CP_OK) return rc;
-    return cp_launch_nhwc_to_nchw(r.y, output, B, Co, H, W, Co, s);
+    rc = launch_conv(p, cw, r.ops, f16x3, s);
+    if (rc == CP_OK) rc = cp_launch_nhwc_to_nchw(r.y, output, B, Co, H, W, Co, s);
+    return rc == CP_OK ? CP_OK : fail(rc, "dcn_v2_forward: kernel launch failed");
 }
 
 // Clip + Adam over a param group (optim.hip)

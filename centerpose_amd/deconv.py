@@ -18,7 +18,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import hip as _hip
-from .conv import _nhwc
+from ._layers import _nhwc, _on_device, _one, _reclass, _same
 
 _DW_TABLE_BYTES = 61440  # the depth-wise kernels' LDS weight table (include/centerpose_hip.h)
 
@@ -68,18 +68,6 @@ def _geometry_refusal(cin, cout, k, stride, pad, groups):
     return None
 
 
-def _same(v):
-    return len(v) == 2 and v[0] == v[1]
-
-
-def _one(v, what):
-    if isinstance(v, (tuple, list)):
-        if not _same(v):
-            raise NotImplementedError("conv_transpose2d: %s must be the same on both axes, got %r" % (what, tuple(v)))
-        v = v[0]
-    return int(v)
-
-
 def _refusal(m):
     """Why the library cannot run this nn.ConvTranspose2d's configuration, or None."""
     if m.bias is not None:
@@ -103,13 +91,12 @@ def conv_transpose2d(x, weight, stride, padding, groups=1, add=None):
     copy); the result and the gradients are channels_last.  Depth-wise (groups == Cin == Cout, stride f in {2, 4}, kernel 2f,
     padding f // 2; ``add`` [B,C,fH,fW] is IDAUp's ``+ layers[i - 1]``, fused, and its gradient is grad_out itself) or dense
     (groups 1, kernel 4, stride 2, padding 1, channels % 32 == 0; precision: ``hip.set_default_precision``)."""
-    if not x.is_cuda:
-        raise RuntimeError("centerpose_hip: tensors must live on the HIP device (no CPU path)")
+    _on_device(x)
     groups = int(groups)
     if x.dim() != 4 or weight.dim() != 4 or weight.shape[0] != x.shape[1] or weight.shape[2] != weight.shape[3] or groups < 1:
         raise RuntimeError("conv_transpose2d: x must be [B,Cin,H,W] and weight [Cin,Cout/groups,K,K], got %s and %s"
                            % (tuple(x.shape), tuple(weight.shape)))
-    stride, padding = _one(stride, "stride"), _one(padding, "padding")
+    stride, padding = _one(stride, "conv_transpose2d", "stride"), _one(padding, "conv_transpose2d", "padding")
     why = _geometry_refusal(x.shape[1], weight.shape[1] * groups, weight.shape[2], stride, padding, groups)
     if why:
         raise NotImplementedError("conv_transpose2d: " + why)
@@ -143,17 +130,4 @@ def use_hip_deconvs(module):
     converted modules' names and ``{name: reason}`` for the transposed convolutions left alone (a bias, ``output_padding``,
     dilation, a dtype other than float32, a geometry outside the two the library runs, subclasses).  Modules that already are
     ``ConvTranspose2d`` appear in neither, and no other kind of module is mentioned or touched."""
-    converted, skipped = [], {}
-    for name, m in module.named_modules():
-        if isinstance(m, ConvTranspose2d):
-            continue
-        if type(m) is nn.ConvTranspose2d:
-            why = _refusal(m)
-            if why:
-                skipped[name] = why
-            else:
-                m.__class__ = ConvTranspose2d
-                converted.append(name)
-        elif isinstance(m, nn.ConvTranspose2d):
-            skipped[name] = "subclass %s of nn.ConvTranspose2d keeps its own forward" % type(m).__name__
-    return converted, skipped
+    return _reclass(module, (nn.ConvTranspose2d,), ConvTranspose2d, _refusal, of=" of nn.ConvTranspose2d")

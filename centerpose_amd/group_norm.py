@@ -16,7 +16,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import hip as _hip
-from .conv import _nhwc
+from ._layers import _nhwc, _on_device, _reclass
 
 
 class _GroupNormFn(Function):
@@ -57,8 +57,7 @@ def group_norm(x, num_groups, weight, bias, eps=1e-5, relu=False):
     float32 tensor on the device, NCHW-contiguous or channels_last (the kernels read NHWC; channels_last costs no copy); the
     result and the gradients are channels_last.  ``weight`` / ``bias`` None: 1 / 0.  ``C % 4 == 0`` and ``C / num_groups`` 1, 2
     or a multiple of 4."""
-    if not x.is_cuda:
-        raise RuntimeError("centerpose_hip: tensors must live on the HIP device (no CPU path)")
+    _on_device(x)
     if x.dim() != 4:
         raise RuntimeError("group_norm: x must be [B,C,H,W], got %s" % (tuple(x.shape),))
     for name, t in (("x", x), ("weight", weight), ("bias", bias)):
@@ -96,17 +95,4 @@ def use_hip_group_norms(module):
     modules' names and ``{name: reason}`` for the GroupNorm layers left alone (``num_channels % 4``, a group width the kernels
     refuse, a dtype other than float32, user-derived subclasses).  Modules that already are ``GroupNorm`` appear in neither, and
     no other kind of module is mentioned or touched."""
-    converted, skipped = [], {}
-    for name, m in module.named_modules():
-        if isinstance(m, GroupNorm):
-            continue
-        if type(m) is nn.GroupNorm:
-            why = _refusal(m)
-            if why:
-                skipped[name] = why
-            else:
-                m.__class__ = GroupNorm
-                converted.append(name)
-        elif isinstance(m, nn.GroupNorm):
-            skipped[name] = "subclass %s keeps its own forward" % type(m).__name__
-    return converted, skipped
+    return _reclass(module, (nn.GroupNorm,), GroupNorm, _refusal)

@@ -19,7 +19,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import hip as _hip
-from .conv import _nhwc
+from ._layers import _nhwc, _on_device, _reclass
 
 
 class _BatchNormFn(Function):
@@ -47,26 +47,44 @@ class _BatchNormFn(Function):
         return (gx.permute(0, 3, 1, 2) if need_x else None, gw, gb, gr.permute(0, 3, 1, 2) if need_r else None) + (None,) * 6
 
 
+def _check_args(op, x, weight, bias, running_mean, running_var, residual):
+    """The argument checks of ``batch_norm`` and ``sync_norm.sync_batch_norm``, under the operator's own name."""
+    _on_device(x)
+    if x.dim() != 4:
+        raise RuntimeError("%s: x must be [B,C,H,W], got %s" % (op, tuple(x.shape)))
+    for name, t in (("x", x), ("residual", residual), ("weight", weight), ("bias", bias), ("running_mean", running_mean),
+                    ("running_var", running_var)):
+        if t is not None and t.dtype != torch.float32:
+            raise RuntimeError("%s: %s is %s (only float32 is built)" % (op, name, t.dtype))
+    if residual is not None and residual.shape != x.shape:
+        raise RuntimeError("%s: residual has shape %s, expected %s" % (op, tuple(residual.shape), tuple(x.shape)))
+
+
 def batch_norm(x, weight, bias, running_mean, running_var, training, momentum, eps, residual=None, relu=False):
     """``relu?(F.batch_norm(x, running_mean, running_var, weight, bias, training, momentum, eps) [+ residual])`` on the HIP kernels
     with autograd.  ``x`` and ``residual`` are logical [B,C,H,W] float32 tensors on the device, NCHW-contiguous or channels_last
     (the kernels read NHWC; channels_last costs no copy); the result and the gradients are channels_last.  ``weight`` / ``bias``
     None: 1 / 0.  ``training``: running_mean / running_var (None, or float32 device tensors) are updated in place; otherwise
     they are the statistics and must be given.  ``C % 4 == 0``."""
-    if not x.is_cuda:
-        raise RuntimeError("centerpose_hip: tensors must live on the HIP device (no CPU path)")
-    if x.dim() != 4:
-        raise RuntimeError("batch_norm: x must be [B,C,H,W], got %s" % (tuple(x.shape),))
-    for name, t in (("x", x), ("residual", residual), ("weight", weight), ("bias", bias), ("running_mean", running_mean),
-                    ("running_var", running_var)):
-        if t is not None and t.dtype != torch.float32:
-            raise RuntimeError("batch_norm: %s is %s (only float32 is built)" % (name, t.dtype))
-    if residual is not None and residual.shape != x.shape:
-        raise RuntimeError("batch_norm: residual has shape %s, expected %s" % (tuple(residual.shape), tuple(x.shape)))
+    _check_args("batch_norm", x, weight, bias, running_mean, running_var, residual)
     if not training and (running_mean is None or running_var is None):
         raise RuntimeError("batch_norm: evaluation needs running_mean and running_var")
     return _BatchNormFn.apply(x, weight, bias, residual, running_mean, running_var, bool(training), float(momentum), float(eps),
                               bool(relu))
+
+
+def _bookkeeping(m):
+    """nn.BatchNorm2d's bookkeeping for one forward of ``m`` (torch/nn/modules/batchnorm.py, _BatchNorm.forward): counts the
+    batch and returns this call's ``(running_mean, running_var, training, momentum)``.  A function, not a method: the layer
+    classes add nothing to ``nn.BatchNorm2d`` but ``forward`` and ``relu``."""
+    factor = 0.0 if m.momentum is None else m.momentum
+    if m.training and m.track_running_stats and m.num_batches_tracked is not None:
+        m.num_batches_tracked.add_(1)
+        if m.momentum is None:  # cumulative moving average
+            factor = 1.0 / float(m.num_batches_tracked)
+    training = m.training or (m.running_mean is None and m.running_var is None)
+    track = not m.training or m.track_running_stats
+    return m.running_mean if track else None, m.running_var if track else None, training, factor
 
 
 class BatchNorm2d(nn.BatchNorm2d):
@@ -77,16 +95,7 @@ class BatchNorm2d(nn.BatchNorm2d):
 
     def forward(self, input, residual=None):
         self._check_input_dim(input)
-        # nn.BatchNorm2d's bookkeeping (torch/nn/modules/batchnorm.py, _BatchNorm.forward)
-        factor = 0.0 if self.momentum is None else self.momentum
-        if self.training and self.track_running_stats and self.num_batches_tracked is not None:
-            self.num_batches_tracked.add_(1)
-            if self.momentum is None:  # cumulative moving average
-                factor = 1.0 / float(self.num_batches_tracked)
-        training = self.training or (self.running_mean is None and self.running_var is None)
-        track = not self.training or self.track_running_stats
-        return batch_norm(input, self.weight, self.bias, self.running_mean if track else None, self.running_var if track else None,
-                          training, factor, self.eps, residual, self.relu)
+        return batch_norm(input, self.weight, self.bias, *_bookkeeping(self), self.eps, residual, self.relu)
 
 
 def _refusal(m):
@@ -105,17 +114,4 @@ def use_hip_norms(module):
     converted modules' names and ``{name: reason}`` for the BatchNorm2d layers left alone (``num_features % 4``, a dtype other
     than float32, subclasses such as ``SyncBatchNorm``-converted or user-derived ones).  Modules that already are
     ``BatchNorm2d`` appear in neither, and no other kind of module is mentioned or touched."""
-    converted, skipped = [], {}
-    for name, m in module.named_modules():
-        if isinstance(m, BatchNorm2d):
-            continue
-        if type(m) is nn.BatchNorm2d:
-            why = _refusal(m)
-            if why:
-                skipped[name] = why
-            else:
-                m.__class__ = BatchNorm2d
-                converted.append(name)
-        elif isinstance(m, (nn.BatchNorm2d, nn.SyncBatchNorm)):
-            skipped[name] = "subclass %s keeps its own forward" % type(m).__name__
-    return converted, skipped
+    return _reclass(module, (nn.BatchNorm2d,), BatchNorm2d, _refusal, also=(nn.SyncBatchNorm,))

@@ -17,7 +17,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import hip as _hip
-from .conv import _nhwc
+from ._layers import _nhwc, _on_device, _one, _reclass, _same
 
 _GEOMETRIES = ((2, 2, 0), (3, 2, 1))
 
@@ -39,14 +39,6 @@ class _MaxPool2dFn(Function):
         return _hip.max_pool2d_backward(_nhwc(x), _nhwc(grad_out), *ctx.geo).permute(0, 3, 1, 2), None, None, None
 
 
-def _one(v, what):
-    if isinstance(v, (tuple, list)):
-        if len(v) != 2 or v[0] != v[1]:
-            raise NotImplementedError("max_pool2d: %s must be the same on both axes, got %r" % (what, tuple(v)))
-        v = v[0]
-    return int(v)
-
-
 def _geometry_refusal(kernel, stride, pad):
     if (kernel, stride, pad) not in _GEOMETRIES:
         return ("geometry outside the table: (kernel, stride, padding) must be (2, 2, 0) or (3, 2, 1), got (%d, %d, %d)"
@@ -58,23 +50,18 @@ def max_pool2d(x, kernel_size, stride=None, padding=0):
     """``F.max_pool2d(x, kernel_size, stride, padding)`` on the HIP kernels with autograd.  ``x`` is a logical [B,C,H,W] float32
     tensor on the device, NCHW-contiguous or channels_last (the kernels read NHWC; channels_last costs no copy); the result and
     the gradient are channels_last.  (kernel, stride, padding) is (2, 2, 0), which floors, or (3, 2, 1); ``C % 4 == 0``."""
-    if not x.is_cuda:
-        raise RuntimeError("centerpose_hip: tensors must live on the HIP device (no CPU path)")
+    _on_device(x)
     if x.dim() != 4:
         raise RuntimeError("max_pool2d: x must be [B,C,H,W], got %s" % (tuple(x.shape),))
     if x.dtype != torch.float32:
         raise RuntimeError("max_pool2d: x is %s (only float32 is built)" % x.dtype)
-    kernel = _one(kernel_size, "kernel_size")
-    stride = kernel if stride is None or stride == [] or stride == () else _one(stride, "stride")
-    pad = _one(padding, "padding")
+    kernel = _one(kernel_size, "max_pool2d", "kernel_size")
+    stride = kernel if stride is None or stride == [] or stride == () else _one(stride, "max_pool2d", "stride")
+    pad = _one(padding, "max_pool2d", "padding")
     why = _geometry_refusal(kernel, stride, pad)
     if why:
         raise NotImplementedError("max_pool2d: " + why)
     return _MaxPool2dFn.apply(x, kernel, stride, pad)
-
-
-def _same(v):
-    return not isinstance(v, (tuple, list)) or (len(v) == 2 and v[0] == v[1])
 
 
 def _refusal(m):
@@ -88,7 +75,7 @@ def _refusal(m):
     stride = m.kernel_size if m.stride is None else m.stride
     if not (_same(m.kernel_size) and _same(stride) and _same(m.padding)):
         return "geometry outside the table: kernel / stride / padding differ between the axes"
-    return _geometry_refusal(_one(m.kernel_size, "kernel_size"), _one(stride, "stride"), _one(m.padding, "padding"))
+    return _geometry_refusal(*(_one(v, "max_pool2d", "geometry") for v in (m.kernel_size, stride, m.padding)))
 
 
 class MaxPool2d(nn.MaxPool2d):
@@ -111,17 +98,4 @@ def use_hip_pools(module):
     max-pool layers left alone (``dilation != 1``, ``ceil_mode``, ``return_indices``, a geometry other than (2, 2, 0) and
     (3, 2, 1), subclasses).  Modules that already are ``MaxPool2d`` appear in neither, and no other kind of module is mentioned
     or touched."""
-    converted, skipped = [], {}
-    for name, m in module.named_modules():
-        if isinstance(m, MaxPool2d):
-            continue
-        if type(m) is nn.MaxPool2d:
-            why = _refusal(m)
-            if why:
-                skipped[name] = why
-            else:
-                m.__class__ = MaxPool2d
-                converted.append(name)
-        elif isinstance(m, nn.MaxPool2d):
-            skipped[name] = "subclass %s keeps its own forward" % type(m).__name__
-    return converted, skipped
+    return _reclass(module, (nn.MaxPool2d,), MaxPool2d, _refusal)

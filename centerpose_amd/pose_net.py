@@ -27,7 +27,7 @@ import torch
 from torch import nn
 
 from . import synth as _synth
-from .conv import Conv2d
+from .conv import Conv2d, use_hip_convs
 from .deconv import ConvTranspose2d
 from .lib.models.networks.DCNv2.dcn_v2 import DCN
 from .norm import BatchNorm2d
@@ -163,7 +163,7 @@ class DeformConv(nn.Module):
         super().__init__()
         self.actf = nn.Sequential(_bn(cho, True))
         self.conv = DCN(chi, cho, kernel_size=(3, 3), stride=1, padding=1, dilation=1, deformable_groups=1)
-        self.conv.conv_offset_mask.__class__ = Conv2d  # what conv.use_hip_convs does
+        use_hip_convs(self.conv.conv_offset_mask)
 
     def forward(self, x):
         return self.actf[0](self.conv(x))

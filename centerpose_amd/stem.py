@@ -17,7 +17,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import hip as _hip
-from .conv import _pair
+from ._layers import _nhwc, _on_device, _one, _reclass, _same
 
 
 class _StemConv2dFn(Function):
@@ -31,18 +31,7 @@ class _StemConv2dFn(Function):
         x4[..., :cin] = x.permute(0, 2, 3, 1)
         w4 = w.new_zeros((cout, 4, 7, 7))
         w4[:, :cin] = w
-        shift = None
-        if bias is not None:
-            # the forward operator reads `shift` up to its N tile (conv.py): pad with zero channels, slice the output
-            tile = 16 if cout <= 16 else 32 if cout <= 32 else 64
-            cpad = (cout + tile - 1) // tile * tile
-            shift = _hip._dev(bias)
-            if cpad != cout:
-                w4 = torch.cat([w4, w4.new_zeros((cpad - cout, 4, 7, 7))])
-                shift = torch.cat([shift, shift.new_zeros(cpad - cout)])
-        y = _hip.conv2d_nhwc(x4, w4, shift=shift, stride=stride, pad=3, act=1 if relu else 0)
-        if y.shape[3] != cout:
-            y = y[..., :cout].contiguous()
+        y = _hip.conv2d_nhwc(x4, w4, shift=bias, stride=stride, pad=3, act=1 if relu else 0)
         ctx.stride, ctx.relu, ctx.has_bias = stride, relu, bias is not None
         ctx.save_for_backward(*((x, y) if relu else (x,)))
         return y.permute(0, 3, 1, 2)
@@ -56,8 +45,7 @@ class _StemConv2dFn(Function):
         need_b = ctx.has_bias and ctx.needs_input_grad[2]
         if not (need_w or need_b):
             return None, None, None, None, None
-        go = _hip._nhwc_view(grad_out).permute(0, 2, 3, 1)
-        gw, gb = _hip.conv2d_stem_backward(x, go, stride=ctx.stride, y=y, need_bias_grad=need_b)
+        gw, gb = _hip.conv2d_stem_backward(x, _nhwc(grad_out), stride=ctx.stride, y=y, need_bias_grad=need_b)
         return None, gw if need_w else None, gb if need_b else None, None, None
 
 
@@ -81,14 +69,13 @@ def stem_conv2d(x, weight, bias=None, stride=1, relu=False):
     """``relu?(F.conv2d(x, weight, bias, stride, padding=3))`` for a 7x7 stem on the HIP kernels with autograd.  ``x`` is a
     [B,Cin,H,W] float32 image on the device with Cin in 1..3 (NCHW planes); ``weight`` [Cout,Cin,7,7] with Cout a multiple of 16
     from 16 to 128; stride 1 or 2.  The result is channels_last.  ``x`` must not require a gradient."""
-    if not x.is_cuda:
-        raise RuntimeError("centerpose_hip: tensors must live on the HIP device (no CPU path)")
+    _on_device(x)
     if x.dim() != 4 or weight.dim() != 4 or weight.shape[1] != x.shape[1]:
         raise RuntimeError("stem_conv2d: x must be [B,Cin,H,W] and weight [Cout,Cin,7,7], got %s and %s"
                            % (tuple(x.shape), tuple(weight.shape)))
     if weight.shape[2] != weight.shape[3]:
         raise NotImplementedError("stem_conv2d: the kernel must be square, got %s" % (tuple(weight.shape[2:]),))
-    stride = _pair(stride, "stride")
+    stride = _one(stride, "stem_conv2d", "stride")
     why = _geometry_refusal(weight.shape[1], weight.shape[0], weight.shape[2], stride, 3)
     if why:
         raise NotImplementedError("stem_conv2d: " + why)
@@ -99,8 +86,7 @@ def stem_conv2d(x, weight, bias=None, stride=1, relu=False):
 
 def _eligible(m, max_cout=_MAX_COUT):
     return (tuple(m.dilation) == (1, 1) and m.groups == 1 and m.padding_mode == 'zeros' and not isinstance(m.padding, str)
-            and m.kernel_size[0] == m.kernel_size[1] and m.stride[0] == m.stride[1] and m.padding[0] == m.padding[1]
-            and m.weight.dtype == torch.float32
+            and _same(m.kernel_size) and _same(m.stride) and _same(m.padding) and m.weight.dtype == torch.float32
             and _geometry_refusal(m.in_channels, m.out_channels, m.kernel_size[0], m.stride[0], m.padding[0], max_cout) is None)
 
 
@@ -130,9 +116,4 @@ def use_hip_stems(module):
     ``skipped`` is always empty, because every other module (``conv.use_hip_convs`` reports the convolutions) is left
     unmentioned and untouched.  A second call converts nothing.  The wider stems ``StemConv2d`` itself accepts (80 .. 128 output
     channels) are left alone here, as they always were: a caller's tree changes only where it did before."""
-    converted = []
-    for name, m in module.named_modules():
-        if type(m) is nn.Conv2d and _eligible(m, _RECLASS_MAX_COUT):
-            m.__class__ = StemConv2d
-            converted.append(name)
-    return converted, {}
+    return _reclass(module, (nn.Conv2d,), StemConv2d, lambda m: not _eligible(m, _RECLASS_MAX_COUT))[0], {}

@@ -18,7 +18,6 @@ What it guarantees:
 Every rank must hold at least one image (``input.shape[0] >= 1``): a global batch must give every rank a shard.  Nothing
 here reads a device value on the host; the global count stays on the device between the forward and the backward.
 """
-import torch
 import torch.distributed as dist
 from torch import nn
 from torch.autograd import Function
@@ -26,8 +25,8 @@ from torch.autograd.function import once_differentiable
 
 from . import distributed as cpd
 from . import hip as _hip
-from .conv import _nhwc
-from .norm import BatchNorm2d, _refusal, batch_norm
+from ._layers import _nhwc, _reclass
+from .norm import BatchNorm2d, _bookkeeping, _check_args, _refusal, batch_norm
 
 
 class _SyncBatchNormFn(Function):
@@ -71,18 +70,9 @@ def sync_batch_norm(x, weight, bias, running_mean, running_var, training, moment
     the group must call it, in the same order, each with at least one image."""
     if not training or not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
         return batch_norm(x, weight, bias, running_mean, running_var, training, momentum, eps, residual, relu)
-    if not x.is_cuda:
-        raise RuntimeError("centerpose_hip: tensors must live on the HIP device (no CPU path)")
-    if x.dim() != 4:
-        raise RuntimeError("sync_batch_norm: x must be [B,C,H,W], got %s" % (tuple(x.shape),))
+    _check_args("sync_batch_norm", x, weight, bias, running_mean, running_var, residual)
     if x.shape[0] == 0:
         raise RuntimeError("sync_batch_norm: this rank has no image (a global batch must give every rank at least one)")
-    for name, t in (("x", x), ("residual", residual), ("weight", weight), ("bias", bias), ("running_mean", running_mean),
-                    ("running_var", running_var)):
-        if t is not None and t.dtype != torch.float32:
-            raise RuntimeError("sync_batch_norm: %s is %s (only float32 is built)" % (name, t.dtype))
-    if residual is not None and residual.shape != x.shape:
-        raise RuntimeError("sync_batch_norm: residual has shape %s, expected %s" % (tuple(residual.shape), tuple(x.shape)))
     return _SyncBatchNormFn.apply(x, weight, bias, residual, running_mean, running_var, float(momentum), float(eps), bool(relu), group)
 
 
@@ -97,16 +87,7 @@ class SyncBatchNorm(BatchNorm2d):
         self._check_input_dim(input)
         if input.shape[0] == 0:
             raise RuntimeError("SyncBatchNorm: this rank has no image (a global batch must give every rank at least one)")
-        # nn.BatchNorm2d's bookkeeping, as in norm.BatchNorm2d.forward
-        factor = 0.0 if self.momentum is None else self.momentum
-        if self.training and self.track_running_stats and self.num_batches_tracked is not None:
-            self.num_batches_tracked.add_(1)
-            if self.momentum is None:  # cumulative moving average
-                factor = 1.0 / float(self.num_batches_tracked)
-        training = self.training or (self.running_mean is None and self.running_var is None)
-        track = not self.training or self.track_running_stats
-        return sync_batch_norm(input, self.weight, self.bias, self.running_mean if track else None, self.running_var if track else None,
-                               training, factor, self.eps, residual, self.relu, self.process_group)
+        return sync_batch_norm(input, self.weight, self.bias, *_bookkeeping(self), self.eps, residual, self.relu, self.process_group)
 
 
 def use_hip_sync_norms(module, group=None):
@@ -117,19 +98,8 @@ def use_hip_sync_norms(module, group=None):
     modules' names and ``{name: reason}`` for the layers left alone (``num_features % 4``, a dtype other than float32,
     user-derived subclasses).  Modules that already are ``SyncBatchNorm`` appear in neither (their group is left alone), and
     no other kind of module is mentioned or touched."""
-    converted, skipped = [], {}
-    for name, m in module.named_modules():
-        if isinstance(m, SyncBatchNorm):
-            continue
-        if type(m) in (BatchNorm2d, nn.BatchNorm2d, nn.SyncBatchNorm):
-            why = _refusal(m)
-            if why:
-                skipped[name] = why
-                continue
-            own = m.__dict__.pop("process_group", None)   # (nn.SyncBatchNorm's instance attribute)
-            m.__class__ = SyncBatchNorm   # (a layer's own ``relu = True`` is an instance attribute and stays)
-            m.process_group = group if group is not None else own
-            converted.append(name)
-        elif isinstance(m, (nn.BatchNorm2d, nn.SyncBatchNorm)):
-            skipped[name] = "subclass %s keeps its own forward" % type(m).__name__
-    return converted, skipped
+    def regroup(m):   # (a layer's own ``relu = True`` is an instance attribute and stays)
+        own = m.__dict__.pop("process_group", None)   # (nn.SyncBatchNorm's instance attribute)
+        m.process_group = group if group is not None else own
+
+    return _reclass(module, (BatchNorm2d, nn.BatchNorm2d, nn.SyncBatchNorm), SyncBatchNorm, _refusal, converted_hook=regroup)

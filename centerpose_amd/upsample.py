@@ -15,7 +15,7 @@ from torch import nn
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from .conv import _nhwc
+from ._layers import _nhwc, _on_device
 from .hip import ops as _ops
 
 
@@ -41,8 +41,7 @@ def upsample2_add(up1, low):
     channels_last costs no copy); ``C % 4 == 0``.  The result and the gradient of ``low`` are channels_last; the gradient of
     ``up1`` is the incoming gradient itself."""
     for name, t in (("up1", up1), ("low", low)):
-        if not t.is_cuda:
-            raise RuntimeError("centerpose_hip: tensors must live on the HIP device (no CPU path)")
+        _on_device(t)
         if t.dim() != 4:
             raise RuntimeError("upsample2_add: %s must be [B,C,H,W], got %s" % (name, tuple(t.shape)))
         if t.dtype != torch.float32:

@@ -324,6 +324,13 @@ const char* cp_role_name(int role);
  * Generic NHWC convolution (exposed for unit tests of the implicit-GEMM kernel).
  *   x [B,H,W,Cin] NHWC, w [Cout,Cin,KH,KW] (reference/PyTorch layout, DEVICE), scale/shift/
  *   residual may be NULL.  out [B,Ho,Wo,Cout] NHWC.  act: 0 none, 1 relu, 2 sigmoid.
+ *   Any Cout is accepted with scale / shift ([Cout] each): the call copies them into zero-padded regions of the
+ *   workspace, which the kernels read up to their N tile.  The N tile follows the Cout passed in (16 up to 16, 32 up to
+ *   32, 128 for multiples of 128, else 64), so a caller that used to pad the weight, scale and shift by hand to the tile
+ *   gets the same kernel for every width but 65..127: those, padded to 128 before, now run on the 64-wide tile.
+ *   One more case under the f16x3 precision: the row-streaming kernel of 64 -> (<= 32) channel 3x3 layers stores 16
+ *   bytes at a time and needs an output row of Cout % 4 == 0 floats, so such a layer with 27 true channels, padded to 32
+ *   by hand before, now runs on the halo kernel of the same 32-wide tile.
  * ------------------------------------------------------------------------------------------ */
 size_t cp_conv2d_workspace_bytes(int Cin, int Cout, int KH, int KW);
 int cp_conv2d_nhwc(cp_stream_t stream, const float* x, const float* w, const float* scale, const float* shift,

@@ -163,6 +163,19 @@ def test_use_hip_convs_reclasses_in_place():
     # a lone convolution is converted too (the root module itself)
     lone = nn.Conv2d(4, 4, 1)
     assert conv.use_hip_convs(lone) == ([""], {}) and type(lone) is conv.Conv2d
+    # a subclass keeps its own forward, with this reason; a subclassed transposed convolution is a transposed convolution
+    derived, derived_up = _DerivedConv(4, 4, 1), _DerivedUp(4, 4, 2)
+    assert conv.use_hip_convs(derived) == ([], {"": "subclass _DerivedConv of nn.Conv2d keeps its own forward"})
+    assert conv.use_hip_convs(derived_up) == ([], {"": "ConvTranspose2d is not built"})
+    assert type(derived) is _DerivedConv and type(derived_up) is _DerivedUp
+
+
+class _DerivedConv(nn.Conv2d):
+    pass
+
+
+class _DerivedUp(nn.ConvTranspose2d):
+    pass
 
 
 @pytest.mark.parametrize("c", R.CASES, ids=R.case_id)

@@ -139,6 +139,70 @@ def test_gaussian_inputs(device, c):
         assert not torch.equal(out16, got[0]), "the split-f16 kernel did not run: its output is bit-equal to the float32 one"
 
 
+def _hand_padded(xh, w, bias, stride, pad, relu):
+    """``hip.conv2d_nhwc`` the way the layers called it while the library refused a ``shift`` shorter than its N tile: weight and
+    bias padded with zero channels to the tile of the width, the output sliced.  xh NHWC -> NHWC."""
+    cout = w.shape[0]
+    tile = 16 if cout <= 16 else 32 if cout <= 32 else 128 if cout % 128 == 0 else 64
+    cpad = (cout + tile - 1) // tile * tile
+    wp = torch.cat([w, w.new_zeros((cpad - cout,) + tuple(w.shape[1:]))])
+    bp = torch.cat([bias, bias.new_zeros(cpad - cout)])
+    return hip.conv2d_nhwc(xh, wp, shift=bp, stride=stride, pad=pad, act=1 if relu else 0)[..., :cout]
+
+
+def _biased_inputs(device, seed, B, Cin, Cout, H, W, K):
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(B, Cin, H, W, generator=g)
+    w = torch.randn(Cout, Cin, K, K, generator=g) / (Cin * K * K) ** 0.5
+    return x.to(device), w.to(device), torch.randn(Cout, generator=g).to(device)
+
+
+BIASED_GEOMETRIES = [((2, 16, 32), 3, 1, 1),    # whole 8 x 16 patches
+                     ((1, 9, 13), 3, 1, 1),     # ragged
+                     ((2, 16, 32), 1, 2, 0)]
+
+
+def test_bias_of_any_width_equals_the_hand_padded_call(device):
+    """cp_conv2d_nhwc stages ``shift`` into its workspace itself: conv.conv2d and stem.stem_conv2d with a bias of a width that is
+    no multiple of the N tile are bit-equal to the call on hand-padded weight and bias, whose N tile is the same."""
+    from centerpose_amd import stem
+
+    for precision in ("f32", "f16x3"):
+        hip.set_default_precision(precision)
+        for (B, H, W), K, stride, pad in BIASED_GEOMETRIES:
+            for Cin in (4, 32):
+                for Cout in (1, 8, 27, 48, 160):
+                    x, w, bias = _biased_inputs(device, Cout + Cin + K, B, Cin, Cout, H, W, K)
+                    xh = x.permute(0, 2, 3, 1).contiguous()
+                    for relu in (False, True):
+                        got = conv.conv2d(x, w, bias, stride, pad, relu=relu)
+                        old = _hand_padded(xh, w, bias, stride, pad, relu).permute(0, 3, 1, 2)
+                        assert got.shape == old.shape and got.shape[1] == Cout
+                        assert torch.equal(got, old), (precision, (B, H, W), K, stride, Cin, Cout, relu)
+        for Cout in (16, 48):
+            x, w, bias = _biased_inputs(device, Cout, 2, 3, Cout, 32, 48, 7)
+            x4 = torch.cat([x, x.new_zeros(2, 1, 32, 48)], 1).permute(0, 2, 3, 1).contiguous()
+            w4 = torch.cat([w, w.new_zeros(Cout, 1, 7, 7)], 1)
+            for stride in (1, 2):
+                for relu in (False, True):
+                    got = stem.stem_conv2d(x, w, bias, stride, relu=relu)
+                    old = _hand_padded(x4, w4, bias, stride, 3, relu).permute(0, 3, 1, 2)
+                    assert got.shape == old.shape and torch.equal(got, old), (precision, "stem", Cout, stride, relu)
+
+
+@pytest.mark.parametrize("precision", ["f32", "f16x3"])
+def test_bias_of_width_100_runs_on_the_64_wide_tile(device, precision):
+    """The one family of widths whose N tile differs between the routes: 65 .. 127 that are no multiple of 64 ran on the 128-wide
+    tile when padded by hand and run on the 64-wide tile now.  Both are within the forward bound of the float64 reference."""
+    x, w, bias = _biased_inputs(device, 100, 2, 32, 100, 16, 32, 3)
+    exp = torch.nn.functional.conv2d(x.cpu().double(), w.cpu().double(), bias.cpu().double(), 1, 1)
+    hip.set_default_precision(precision)
+    new = conv.conv2d(x, w, bias, 1, 1).cpu()
+    old = _hand_padded(x.permute(0, 2, 3, 1).contiguous(), w, bias, 1, 1, False).permute(0, 3, 1, 2).cpu()
+    _close((new,), (exp,), "%s Cout=100, true width (64-wide tile)" % precision)
+    _close((old,), (exp,), "%s Cout=100, hand-padded to 128" % precision)
+
+
 def _swapped(c, inp):
     """The case and its inputs with the spatial axes exchanged (KH <-> KW, H <-> W)."""
     t = lambda a: a.transpose(2, 3).contiguous()

@@ -142,6 +142,8 @@ def test_argument_validation_without_gpu(built):
     assert built.cp_decode_workspace_bytes(32, 100) >= 32 * 9 * 100 * 8
     assert built.cp_pnp_workspace_bytes(10) >= 10 * 288 * 8
     assert built.cp_conv2d_workspace_bytes(64, 64, 3, 3) >= 576 * 64 * 4
+    # ... plus the zero-padded scale and shift the call stages itself (27 channels: the 32-wide N tile)
+    assert built.cp_conv2d_workspace_bytes(64, 27, 3, 3) >= 576 * 32 * 4 + 2 * 32 * 4
     assert built.cp_model_workspace_bytes(None, 1, 512, 512) == 0 and b"null model" in built.cp_last_error()
 
 

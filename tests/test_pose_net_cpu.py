@@ -141,6 +141,7 @@ def test_use_hip_pools_contract():
     assert set(skipped) == {"4", "5", "6", "7", "8", "9"}
     for k, word in (("4", "dilation"), ("5", "ceil_mode"), ("6", "return_indices"), ("7", "geometry"), ("8", "geometry"), ("9", "subclass")):
         assert word in skipped[k], (k, skipped[k])
+    assert skipped["9"] == "subclass Mine keeps its own forward"
     assert all(type(net[i]) is pool.MaxPool2d for i in range(4)) and type(net[4]) is nn.MaxPool2d and type(net[9]) is Mine
     assert repr(net) == before
     assert pool.use_hip_pools(net) == ([], skipped)   # idempotent: converted layers appear in neither
