@@ -26,6 +26,21 @@ static void drop_kept_in(cp_model* m, const void* ws, size_t bytes) {
     if (k && k >= (const char*)ws && k < (const char*)ws + bytes) m->kept = cp_model::KeptFeat();
 }
 
+// The gate in front of a pass that allocates from the caller's workspace: nothing is launched on a workspace smaller than the query's
+// answer for this (shape, switches, precision).  Arena::alloc hands out offsets beyond its cap and only notes the overflow, which
+// forward_impl reports once every launch is enqueued: without this gate a buffer sized for another arithmetic mode or switch setting
+// is written past its end.  (The query is cached per shape and switches and dropped by cp_model_set_precision: a compare.)
+static int workspace_refused(cp_model* m, const char* what, int B, int H, int W, size_t workspace_bytes) {
+    if (!m) return fail(CP_ERR_INVALID, std::string(what) + ": null model");
+    if (!m->finalized) return fail(CP_ERR_STATE, "model not finalized");
+    const size_t need = cp_model_workspace_bytes(m, B, H, W);
+    if (need == 0) return CP_ERR_INVALID;  // (the shape was refused: the dry pass left the reason in cp_last_error)
+    if (workspace_bytes < need)
+        return fail(CP_ERR_INVALID, std::string(what) + ": workspace too small: " + std::to_string(workspace_bytes) +
+                                        " bytes given, cp_model_workspace_bytes asks for " + std::to_string(need));
+    return CP_OK;
+}
+
 // captured launch sequences of a model, keyed by every argument: replay the graph of `key`, capturing `enqueue` on first use
 template <class F>
 static int replay_or_capture(cp_model* m, hipStream_t s, const std::vector<uint64_t>& key, F&& enqueue) {
@@ -189,7 +204,8 @@ size_t cp_model_workspace_bytes(cp_model* m, int B, int H, int W) {
 int cp_model_forward(cp_model* m, cp_stream_t stream, int B, int H, int W, const float* images, const float* pre_img,
                      const float* pre_hm, const float* pre_hm_hp, float* const* head_out, int sigmoid_hm,
                      void* workspace, size_t workspace_bytes) {
-    if (!images || !head_out || !workspace) return fail(CP_ERR_INVALID, "null argument");
+    if (!m || !images || !head_out || !workspace) return fail(CP_ERR_INVALID, "null argument");
+    if (const int rc = workspace_refused(m, "cp_model_forward", B, H, W, workspace_bytes)) return rc;
     m->tap_name = nullptr;
     drop_kept_in(m, workspace, workspace_bytes);
     return forward_impl(m, (hipStream_t)stream, B, H, W, images, pre_img, pre_hm, pre_hm_hp, head_out, sigmoid_hm,
@@ -201,6 +217,7 @@ int cp_model_features(cp_model* m, cp_stream_t stream, int B, int H, int W, cons
     if (!m || !images || !feat_out || !workspace) return fail(CP_ERR_INVALID, "null argument");
     if (m->gru) return fail(CP_ERR_STATE, "cp_model_features: dlav1 heads read the ConvGRU steps through GroupNorm, not one feature map");
     if (m->hourglass) return fail(CP_ERR_STATE, "cp_model_features: hourglass has two stacks of heads, not one feature map");
+    if (const int rc = workspace_refused(m, "cp_model_features", B, H, W, workspace_bytes)) return rc;
     m->tap_name = nullptr;
     drop_kept_in(m, workspace, workspace_bytes);
     m->feat_out = feat_out;
@@ -237,7 +254,9 @@ int cp_model_detect(cp_model* m, cp_stream_t stream, int B, int H, int W, const 
     const bool tiled = (H / 4) * (W / 4) > 32768;
     const size_t dec_ws = detect_decode_ws_bytes(B, H, W, K);
     if (dec_ws == 0) return fail(CP_ERR_INVALID, "detect: unsupported decode shape (need K <= 128, K <= H*W/16 <= 2^20, W/4 <= 4096)");
-    if (workspace_bytes < model_ws + dec_ws) return fail(CP_ERR_INVALID, "workspace too small");
+    if (workspace_bytes < model_ws + dec_ws)
+        return fail(CP_ERR_INVALID, "cp_model_detect: workspace too small: " + std::to_string(workspace_bytes) +
+                                        " bytes given, cp_model_detect_workspace_bytes asks for " + std::to_string(model_ws + dec_ws));
     // decode inputs by head name (opts.py:394-426)
     float* hp[11] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     const char* names[11] = {"hm", "hps", "wh", "hps_uncertainty", "scale", "scale_uncertainty", "reg", "hm_hp",
@@ -328,7 +347,9 @@ int cp_model_detect_lean(cp_model* m, cp_stream_t stream, int B, int H, int W, c
     const size_t scratch = lean_scratch_bytes(m, B, H, W, K);
     if (model_ws == 0) return CP_ERR_INVALID;
     if (scratch == 0) return fail(CP_ERR_INVALID, "detect: unsupported decode shape (need K <= 128, K <= H*W/16 <= 2^20, W/4 <= 4096)");
-    if (workspace_bytes < model_ws + scratch) return fail(CP_ERR_INVALID, "workspace too small");
+    if (workspace_bytes < model_ws + scratch)
+        return fail(CP_ERR_INVALID, "cp_model_detect_lean: workspace too small: " + std::to_string(workspace_bytes) +
+                                        " bytes given, cp_model_detect_lean_workspace_bytes asks for " + std::to_string(model_ws + scratch));
     for (size_t i = 0; i < m->headw.size(); ++i) {
         const bool map = m->headw[i].name == "hm" || m->headw[i].name == "hm_hp";
         if (map ? !head_out[i] : !table_out[i]) return fail(CP_ERR_INVALID, "lean detect: hm / hm_hp need a map, every other head a table");
@@ -400,7 +421,8 @@ int cp_model_forward_tap(cp_model* m, cp_stream_t stream, int B, int H, int W, c
                          const float* pre_img, const float* pre_hm, const float* pre_hm_hp, float* const* head_out,
                          int sigmoid_hm, void* workspace, size_t workspace_bytes, const char* tap_name, float* tap_out,
                          int* tap_dims) {
-    if (!images || !head_out || !workspace) return fail(CP_ERR_INVALID, "null argument");
+    if (!m || !images || !head_out || !workspace) return fail(CP_ERR_INVALID, "null argument");
+    if (const int rc = workspace_refused(m, "cp_model_forward_tap", B, H, W, workspace_bytes)) return rc;
     drop_kept_in(m, workspace, workspace_bytes);
     m->tap_name = tap_name;
     m->tap_out = tap_out;

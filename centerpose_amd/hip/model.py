@@ -82,7 +82,6 @@ class HipModel(object):
         if precision is not None:
             self.set_precision(precision)
         self._ws = None
-        self._ws_key = None
 
     def __del__(self):
         try:
@@ -135,12 +134,19 @@ class HipModel(object):
         input was not written by its producer."""
         return int(_abi.lib().cp_model_maxpool_launches(self._h))
 
+    @staticmethod
+    def _fits(buf, nbytes, device):
+        """The one rule for every work-space buffer the model keeps between calls: ``buf`` serves again only while it has exactly
+        the size the library asks for now, on the same device.  What a shape needs also depends on the precision and on the
+        kernel-selection switches, so every call asks (the library caches its answer) and no buffer outlives the size it was
+        allocated for."""
+        return buf is not None and buf.numel() == nbytes and buf.device == torch.device(device)
+
     def _workspace(self, B, H, W, device):
-        key = (B, H, W, str(device))
-        if self._ws_key != key:
-            self._ws = None
-            self._ws = _abi._workspace(self.workspace_bytes(B, H, W), device)
-            self._ws_key = key
+        need = self.workspace_bytes(B, H, W)
+        if not self._fits(self._ws, need, device):
+            self._ws = None   # (freed before its successor is allocated)
+            self._ws = _abi._workspace(need, device)
         return self._ws
 
     def forward(self, images, pre_img=None, pre_hm=None, pre_hm_hp=None, sigmoid_hm=False, tap=None):
@@ -214,8 +220,11 @@ class HipModel(object):
         B, _, H, W = images.shape
         dev = images.device
         key = ("lean", B, H, W, str(dev), K)
+        need = self._sized("cp_model_detect_lean_workspace_bytes", B, H, W, K)
         st = getattr(self, "_lean_state", None)
-        if st is None or st[0] != key:
+        if st is not None and (st[0] != key or not self._fits(st[6], need, dev)):
+            st = self._lean_state = None   # (another shape, or the same one under another precision / switch setting)
+        if st is None:
             f32 = dict(device=dev, dtype=torch.float32)
             maps = OrderedDict((k, torch.empty(B, self.heads[k], H // 4, W // 4, **f32)) for k in _MAP_HEADS)
             tables = OrderedDict((k, torch.empty(*((B, 8, 2, K) if k == "hp_offset" else (B, c, K)), **f32))
@@ -223,7 +232,7 @@ class HipModel(object):
             pk_score = torch.empty(B, 9, K, **f32)
             pk_ind = torch.empty(B, 9, K, device=dev, dtype=torch.int32)
             det = torch.empty(B, K, DET_STRIDE, **f32)
-            ws = _abi._workspace(self._sized("cp_model_detect_lean_workspace_bytes", B, H, W, K), dev)
+            ws = _abi._workspace(need, dev)
             hp = (c_void_p * len(self.heads))(*[maps[k].data_ptr() if k in maps else 0 for k in self.heads])
             tp = (c_void_p * len(self.heads))(*[tables[k].data_ptr() if k in tables else 0 for k in self.heads])
             shapes = OrderedDict((k, (B, c, H // 4, W // 4)) for k, c in self.heads.items())
@@ -263,12 +272,15 @@ class HipModel(object):
             return self._detect_lean(images, pre_img, pre_hm, pre_hm_hp, K, rep_mode, fit_gaussian, balance, legacy_bool_mask,
                                      graph)
         key = ("det", B, H, W, str(images.device), K)
+        need = self._sized("cp_model_detect_workspace_bytes", B, H, W, K)
         st = getattr(self, "_det_state", None)
-        if st is None or st[0] != key:
+        if st is not None and (st[0] != key or not self._fits(st[3], need, images.device)):
+            st = self._det_state = None   # (another shape, or the same one under another precision / switch setting)
+        if st is None:
             outs = OrderedDict((k, torch.empty(B, c, H // 4, W // 4, device=images.device, dtype=torch.float32))
                                for k, c in self.heads.items())
             det = torch.empty(B, K, DET_STRIDE, device=images.device, dtype=torch.float32)
-            ws = _abi._workspace(self._sized("cp_model_detect_workspace_bytes", B, H, W, K), images.device)
+            ws = _abi._workspace(need, images.device)
             ptrs = (c_void_p * len(outs))(*[t.data_ptr() for t in outs.values()])
             st = (key, outs, det, ws, ptrs)
             self._det_state = st

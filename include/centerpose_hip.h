@@ -196,7 +196,9 @@ int cp_model_set_param(cp_model* m, const char* name, const float* host_data, in
 int cp_model_finalize(cp_model* m);
 void cp_model_destroy(cp_model* m);
 
-/* Bytes of device scratch needed by cp_model_forward for a batch of B images of H x W. */
+/* Bytes of device scratch needed by cp_model_forward for a batch of B images of H x W -- under the model's precision and the
+ * kernel-selection switches as they stand now: ask again after changing either.  cp_model_forward, cp_model_forward_tap and
+ * cp_model_features refuse a smaller workspace_bytes with CP_ERR_INVALID before their first launch. */
 size_t cp_model_workspace_bytes(cp_model* m, int B, int H, int W);
 /* Bytes of that scratch the last pass over m reached (a forward / detect call, or the last dry pass of the query above); 0 before
  * the first.  The launch sequence depends on taps and switches; whatever it was, this is at most what the query returned. */

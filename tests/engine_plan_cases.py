@@ -111,7 +111,6 @@ def record(case, device, passes=1):
     x, kw = _inputs(key, B, H, W, device)
     pin = OrderedDict(id=case_id(case))
     with hip.select_kernels(sel):
-        m._ws_key = None  # (the binding keeps one buffer per shape: size it under this case's switches)
         pin["workspace_bytes"] = m.workspace_bytes(B, H, W)
         digests = []
         for _ in range(passes):

@@ -118,7 +118,6 @@ def test_layers_vs_float64_oracle(device, key, prec, sel):
     got, form = {}, {}
     problems = []
     with hip.select_kernels(switches):
-        m._ws_key = None  # (the binding keeps one buffer per shape: size it under this selection)
         heads = m.forward(x, **kw)  # untapped: the production head kernels
         for h in c["heads"]:
             got["head:" + h], form["head:" + h] = heads[h], "untapped"

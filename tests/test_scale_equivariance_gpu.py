@@ -82,7 +82,6 @@ def _engine(key, prec, switches, variant, device, profile_all=False):
             _, got[tap] = m.forward(x, tap=tap, **kw)
 
     with hip.select_kernels(switches):
-        m._ws_key = None  # (the binding keeps one buffer per shape: size it under this selection)
         heads, rows0 = L._launch_rows(m, lambda: m.forward(x, **kw))  # untapped: the production head kernels
         for h in c["heads"]:
             got["head:" + h] = heads[h]
@@ -91,7 +90,6 @@ def _engine(key, prec, switches, variant, device, profile_all=False):
         else:
             taps()
         torch.cuda.synchronize()
-    m._ws_key = None
     _passes[ck] = (got, sorted({r[0] for r in rows0}), sorted({r[0] for r in rows} | {r[0] for r in rows0}) if profile_all else None)
     return _passes[ck]
 
@@ -223,7 +221,6 @@ def test_production_kernels_at_the_detect_shape(device, dla, sel):  # noqa: F811
     x = synth.frames(8, seed=59, h=256, w=256).to(device)
     problems, ran = [], set()
     with hip.select_kernels(DETECT_SHAPE_SELECTIONS[sel]):
-        model._ws_key = None
         base, rows = L._launch_rows(model, lambda: model.forward(x))
         ran |= {r[0] for r in rows}
         variants = [("gauge t=%d" % T, G.gauge(sd, T)[0], 1.0)] + [("a=%s" % an, G.homogeneous(sd, a), a) for an, a in ALPHAS.items()]
@@ -236,7 +233,6 @@ def test_production_kernels_at_the_detect_shape(device, dla, sel):  # noqa: F811
                 if not torch.equal(got[h], base[h] * a):
                     problems.append("%s: head %s is not %g x the base model's (%d of %d elements differ)"
                                     % (label, h, a, int((got[h] != base[h] * a).sum()), base[h].numel()))
-    model._ws_key = None
     print("scale-equivariance 8x256x256 %s: kernels: %s" % (sel, " ".join(sorted(ran))))
     _reached.update(ran)
     assert not problems, "\n".join(problems + ["kernels: " + " ".join(sorted(ran))])
