@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "../../include/centerpose_hip_testing.h"  // CP_SEL_* (ConvParams::dbg)
+#include "conv_variants.h"  // CP_VARIANT_*: the kernel variants the launchers below choose from
 
 // The kernels of this library rely on the raw-buffer range check of the gfx9 / CDNA family as gfx950 implements it: a lane whose
 // (voffset + soffset [+ immediate]) lies beyond the descriptor's num_records reads 0 -- per dword for a 16-byte access that
@@ -245,20 +246,15 @@ struct ConvParams {
 };
 
 int cp_launch_conv(const ConvParams& p, hipStream_t stream);
-// Tile N-width the launcher will pick for `cout` (weights must be padded to a multiple of it).
+// Tile N-width the launcher will pick for `cout` (weights must be padded to a multiple of it); cp_conv16_tile_n: of the f16x3 launch
 int cp_conv_tile_n(int cout);
+int cp_conv16_tile_n(const ConvParams& p);
+// The selectors: the CP_VARIANT_* (conv_variants.h) that cp_launch_conv / cp_launch_conv16 run p on -- the launchers dispatch on this answer
 int cp_conv_variant(const ConvParams& p);
 int cp_launch_splitk_epilogue(const ConvParams& p, hipStream_t stream);
 // K steps (of 16 for the f32 kernels, 32 for f16x3) and output tiles of the launch cp_launch_conv[16] would make
 void cp_conv_geometry(const ConvParams& p, bool f16x3, int* tiles, int* nk);
 const char* cp_conv_variant_name(int v);
-#define CP_NUM_CONV_VARIANTS 46
-#define CP_VARIANT_HEAD_ROWS 45  // igemm16p fused head over a pixel list (regression heads at the decoded peaks)
-#define CP_VARIANT_DECONV_F32 43  // deconv16.hip, exact f32
-#define CP_VARIANT_DECONV16 44    // deconv16.hip, f16x3
-#define CP_VARIANT_STRM16 41
-#define CP_VARIANT_LOWC1S 42
-#define CP_VARIANT_GRU 26
 // split-f16 ("f16x3") implicit GEMM (igemm16.hip)
 bool cp_conv16_supported(const ConvParams& p);
 int cp_launch_conv16(const ConvParams& p, hipStream_t stream);
@@ -278,34 +274,26 @@ int cp_strm16_jobs(const ConvParams& p);
 int cp_launch_strm16(const ConvParams& p, hipStream_t stream);
 // fused DCNv2 gather + contraction (dcn16.hip); bn = N tile (64 / 128)
 int cp_launch_dcn16(const ConvParams& p, int bn, hipStream_t stream);
-// dcn16p.hip: patch-resident DCNv2 (gather from an LDS-staged halo); N tile 64, or 128 where cp_dcn16p_wide says so
 // pw16.hip: 1x1 / stride-1 layers (incl. virtual concats) as a register-only stream, weight fragments from w16f_*
 bool cp_pw16_supported(const ConvParams& p);
 bool cp_pw16_pool_supported(const ConvParams& p);  // ... and can write ConvParams::pool_out (whole-line loads, Ho even, Wo % 16 == 0)
 int cp_launch_pw16(const ConvParams& p, hipStream_t stream);
+// dcn16p.hip: patch-resident DCNv2 (gather from an LDS-staged halo); N tile 64, or 128 (`wide`, NT = 4) where the selector, asking
+// cp_dcn16p_wide, chose CP_VARIANT_DCN16PW
 bool cp_dcn16p_supported(const ConvParams& p);
 int cp_dcn16p_blocks(const ConvParams& p);
-int cp_launch_dcn16p(const ConvParams& p, hipStream_t stream);
-bool cp_dcn16p_wide(const ConvParams& p);  // the launch takes the 128-wide N tile (NT = 4)
+bool cp_dcn16p_wide(const ConvParams& p);
+int cp_launch_dcn16p(const ConvParams& p, bool wide, hipStream_t stream);
 // dcn16s.hip: the same gather as a persistent kernel with the halo streamed by LDS-DMA into two 16-channel buffers
 // (launches with several (patch, N tile) items per resident workgroup)
-#define CP_VARIANT_DCN16S 36
-#define CP_VARIANT_M64N64 37  // igemm16p on 64 x 64 tiles (small launches)
-#define CP_VARIANT_DCN16PW 38  // dcn16p on the 128-wide N tile
 bool cp_dcn16s_supported(const ConvParams& p);
 int cp_dcn16s_items(const ConvParams& p);
 int cp_launch_dcn16s(const ConvParams& p, hipStream_t stream);
 int cp_launch_frag16_repack(const void* w16, void* w16f, int CoutPad, int Kpad16, hipStream_t s);
 // dcn16t.hip: dcn16p's gather written for three workgroups per CU (16-channel chunks, one gather set, two weight sets)
-#define CP_VARIANT_DCN16T 39
 bool cp_dcn16t_supported(const ConvParams& p);
 bool cp_dcn16t_upadd_supported(const ConvParams& p);  // ... with ConvParams::up_t (one 64-channel N tile, up_f 2 or 4)
 int cp_launch_dcn16t(const ConvParams& p, hipStream_t stream);
-#define CP_VARIANT_DCN16P 30
-#define CP_VARIANT_GN_FINAL 31
-#define CP_VARIANT_HALO_HEAD 32
-#define CP_VARIANT_HALO_GRU 33
-#define CP_VARIANT_PW16 34  // + 1 for the 128-wide N tile
 // `fwd` (may be nullptr = 1): per-output-channel power-of-two factor applied before the split, indexed [coff + co]
 int cp_launch_pack_weight16(const float* w, void* hi, void* lo, int Cout, int Cin, int taps, int Kpad16, int coff,
                             const float* fwd, hipStream_t s);
@@ -336,7 +324,8 @@ struct HeadReduceGroup {
 };
 int cp_launch_head_reduce_grouped(const float* slabs, const HeadReduceGroup& g, int B, int HW, hipStream_t s);
 int cp_launch_conv16_gru(const ConvParams& p, hipStream_t stream);
-#define CP_VARIANT_FUSED_HEAD 22
+int cp_conv16_fused_head_variant(const ConvParams& p);  // what cp_launch_conv16_fused_head / _gru run p on
+int cp_conv16_gru_variant(const ConvParams& p);
 // direct low-channel convolutions of the network's first three layers in f16x3 mode (lowc.hip).
 // kind: 0 stem 7x7 (NCHW input, `planes` <= 4) -> 16; 1 level0 3x3 16->16; 2 level1 3x3 stride 2 16->32
 size_t cp_lowc_weight_halfs(int kind);
@@ -349,9 +338,7 @@ int cp_launch_lowc(int kind, const float* in, float* out, const void* w_hi, cons
 // pool_out (kind 5 only, cp_lowc_pool_supported): NHWC [B][Ho / 2][Wo / 2][32] receives the 2x2 max-pooled copy of `out`, written
 // by the same launch (what cp_launch_maxpool2 makes of `out`); its |max| is bounded by out_amax's
 bool cp_lowc_pool_supported(int kind, int H, int W);
-#define CP_VARIANT_LOWC0 23
 // stem + level0 in one launch (lowc.hip: lowc2_kernel): the 16-channel full-resolution tensor between them is never stored
-#define CP_VARIANT_LOWC01 40
 int cp_launch_lowc_fused(const float* in, float* out, const void* w0_hi, const void* w0_lo, const float* scale0, const float* shift0,
                          const void* w1_hi, const void* w1_lo, const float* scale1, const float* shift1, float bound_l, float bound_s,
                          const unsigned* in_amax, unsigned* out_amax, int B, int H, int W, int planes, hipStream_t s);

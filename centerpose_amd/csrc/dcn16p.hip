@@ -307,10 +307,10 @@ bool cp_dcn16p_wide(const ConvParams& p) {
            ((p.dbg & CP_SEL_DCN16P_ALWAYS) || p.B * (p.H / TH) * (p.W / TW) * (p.CoutPad / 128) >= 256);  // (ALWAYS: any size, tests)
 }
 
-int cp_launch_dcn16p(const ConvParams& p, hipStream_t stream) {
-    if (!cp_dcn16p_supported(p)) return CP_ERR_INVALID;
-    if (cp_dcn16p_wide(p)) return launch_dcn16p<4>(p, stream);
-    return launch_dcn16p<2>(p, stream);
+// wide: the selector's answer (cp_conv16_variant: CP_VARIANT_DCN16PW, where cp_dcn16p_wide says so)
+int cp_launch_dcn16p(const ConvParams& p, bool wide, hipStream_t stream) {
+    if (!cp_dcn16p_supported(p) || (wide && p.CoutPad % 128 != 0)) return CP_ERR_INVALID;
+    return wide ? launch_dcn16p<4>(p, stream) : launch_dcn16p<2>(p, stream);
 }
 
 int cp_launch_frag16_repack(const void* w16, void* w16f, int CoutPad, int Kpad16, hipStream_t s) {

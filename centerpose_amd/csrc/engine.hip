@@ -274,7 +274,7 @@ int cp_model_detect(cp_model* m, cp_stream_t stream, int B, int H, int W, const 
             // algorithmic bytes of the decode: one read of hm + hm_hp, the gathers at the K centres
             // (<= 60 channels) and at the 8K joint peaks (2 channels), the records written
             const double hw = (double)(H / 4) * (W / 4);
-            r.variant = -1;
+            r.variant = CP_VARIANT_NONE;
             r.role = CP_ROLE_DECODE;
             r.flops = 0.0;
             r.bytes = (double)B * (9.0 * hw * 4 + K * 60.0 * 4 + 8.0 * K * 2 * 4 + (double)K * CP_DET_STRIDE * 4);

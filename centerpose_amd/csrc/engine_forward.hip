@@ -123,7 +123,7 @@ struct Fwd {
         };
         if (m->dry) return true;
         timed([&](cp_model::ProfRec& r) {
-            r.variant = cp_halo16_fused_head_supported(p) ? CP_VARIANT_HALO_HEAD : CP_VARIANT_FUSED_HEAD;
+            r.variant = cp_conv16_fused_head_variant(p);
             r.role = CP_ROLE_HEAD;
             const double M = (double)B * p.Ho * p.Wo;
             r.flops = 2.0 * M * w.Cout * (double)(w.KH * w.KW * w.Cin) + 2.0 * M * hw.classes * (double)w.Cout;
@@ -314,7 +314,7 @@ struct Fwd {
         float* slabs = (float*)((char*)lc.scratch + align_up(cand, 256));
         const double hw = (double)x.H * x.W;
         auto decode_rec = [&](cp_model::ProfRec& r, double bytes) {
-            r.variant = -1;
+            r.variant = CP_VARIANT_NONE;
             r.role = CP_ROLE_DECODE;
             r.flops = 0.0;
             r.bytes = bytes;
@@ -371,7 +371,7 @@ struct Fwd {
         ConvParams p;               // (with plan_split's answer: splitk, tile_m / tile_n)
         const char* err = nullptr;  // the call cannot be launched at all
         bool use16 = false;         // the f16x3 kernels take it (cp_launch_conv16), else the float32 ones
-        int variant = -1;           // CP_VARIANT_* of the launch
+        int variant = CP_VARIANT_NONE;  // of the launch (conv_variants.h)
         bool pooled = false, up = false, pj = false;  // the requested fusion is accepted: the launch lands on a kernel that has it
     };
     // a Tensor of that shape and no memory: what a predicate hands plan() for a tensor that does not exist yet
@@ -461,7 +461,7 @@ struct Fwd {
             p.pj_w_hi = c.pj->w->w16f_hi; p.pj_w_lo = c.pj->w->w16f_lo; p.pj_scale = c.pj->w->scale16; p.pj_shift = c.pj->w->shift;
         }
         pl.variant = pl.use16 ? cp_conv16_variant(p) : cp_conv_variant(p);
-        const bool pw16 = pl.variant == CP_VARIANT_PW16 || pl.variant == CP_VARIANT_PW16 + 1;
+        const bool pw16 = cp_variant_is_pw16(pl.variant);
         // dcn16t's UPADD instance; halo16's PJ on the 64- / 128-wide tile with <p>.project's fragment-ordered operands; pw16s_kernel
         // over a picture of even height and a width of whole 16-pixel blocks (a whole launch each: no split-K)
         pl.up = c.up && whole16 && pl.variant == CP_VARIANT_DCN16T && cp_dcn16t_upadd_supported(p);
@@ -491,7 +491,7 @@ struct Fwd {
         if (m->form.project_unfused || (m->tap_name && std::strstr(m->tap_name, ".project") != nullptr)) return false;  // (every entry)
         if (g_dbg & (CP_SEL_PW16_FRAG_A | CP_SEL_PW16_NEVER)) return false;  // (the projection's kernel asked for by name)
         const ConvPlan alone = plan({wp, {&bottom}, 1, 0, CP_ACT_NONE});  // tree1()'s stand-alone call
-        if (alone.err || !alone.use16 || alone.p.splitk != 1 || (alone.variant != CP_VARIANT_PW16 && alone.variant != CP_VARIANT_PW16 + 1))
+        if (alone.err || !alone.use16 || alone.p.splitk != 1 || !cp_variant_is_pw16(alone.variant))
             return false;
         const Tensor t = shape_of(w2.CinP, bottom.H, bottom.W);  // conv1's output
         const ProjFuse pj = {&bottom, &wp};
@@ -756,7 +756,7 @@ struct Fwd {
                                   out.amax, B, H, W, planes, s, pool ? pooled->ptr() : nullptr);
         };
         timed([&](cp_model::ProfRec& r) {
-            r.variant = kind == 5 ? CP_VARIANT_LOWC1S : CP_VARIANT_LOWC0 + (kind == 3 ? 0 : kind);
+            r.variant = kind == 5 ? CP_VARIANT_LOWC1S : kind == 1 ? CP_VARIANT_LOWC1 : kind == 2 ? CP_VARIANT_LOWC2 : CP_VARIANT_LOWC0;  // (3: the 8-plane stem)
             r.role = CP_ROLE_LOWC;
             const double M = (double)B * Ho * Wo;
             r.flops = 2.0 * M * cout * (double)(k * k * cin);
@@ -1051,7 +1051,7 @@ struct Fwd {
                         p.gru_hprev = h.ptr();
                         p.splitk = 1;
                         timed([&](cp_model::ProfRec& r) {
-                            r.variant = cp_halo16_gru_supported(p) ? CP_VARIANT_HALO_GRU : CP_VARIANT_GRU;
+                            r.variant = cp_conv16_gru_variant(p);
                             r.role = CP_ROLE_GRU;
                             r.flops = 2.0 * (double)M * 192 * 576;
                             r.bytes = 4.0 * ((double)M * (64 + 192 + 64 + 64) + 576.0 * 192);

@@ -341,16 +341,6 @@ static bool conv_aligned(const ConvParams& p) {
     return aligned;
 }
 
-template <int FRAG, int MT, int NT, int WM, int WN, bool DCN>
-int launch(const ConvParams& p, hipStream_t stream) {
-    const bool aligned = conv_aligned(p);
-    if (DCN) return aligned ? launch_a<FRAG, MT, NT, WM, WN, DCN, true, false>(p, stream) : CP_ERR_INVALID;
-    if (aligned && p.nsrc > 1) return launch_a<FRAG, MT, NT, WM, WN, false, true, true>(p, stream);
-    if (aligned) return launch_a<FRAG, MT, NT, WM, WN, false, true, false>(p, stream);
-    if (p.nsrc != 1) return CP_ERR_INVALID;
-    return launch_a<FRAG, MT, NT, WM, WN, false, false, false>(p, stream);
-}
-
 }  // namespace
 
 int cp_conv_tile_n(int cout) {
@@ -360,40 +350,30 @@ int cp_conv_tile_n(int cout) {
     return 64;
 }
 
-// Kernel variant id = one template instantiation family (what rocprofv3 lists as one kernel name):
-//   0..3  plain conv, N tile 16/32/64/128      4..5  fused DCNv2, N tile 64/128
-//   6..9  plain conv over a virtual channel concat (Root), N tile 16/32/64/128
-//   10..13 unaligned-channel plain conv (7x7 stems), N tile 16/32/64/128
+// N tile of the f16x3 launch: cp_conv_tile_n, except that a split-K plan's smaller tile (ConvParams::tile_n) is taken where it divides
+// the padded width, and <= 16-wide outputs whose weights were packed to 32 columns (the GroupNorm'd final 1x1 heads) take the 32-wide tile
+int cp_conv16_tile_n(const ConvParams& p) {
+    const int bn = cp_conv_tile_n(p.Cout);
+    if (p.tile_n && p.tile_n < bn && p.CoutPad % p.tile_n == 0 && (!p.offmask || p.tile_n == 64)) return p.tile_n;
+    return (bn < 32 && p.CoutPad >= 32 && p.CoutPad % 32 == 0) ? 32 : bn;
+}
+
+// The exact-f32 selector (ids and families: conv_variants.h); cp_launch_conv dispatches on its answer.
 int cp_conv_variant(const ConvParams& p) {
     const int bn = cp_conv_tile_n(p.Cout);
-    if (p.offmask) return bn == 128 ? 5 : 4;
-    const int t = bn == 16 ? 0 : bn == 32 ? 1 : bn == 64 ? 2 : 3;
-    if (!conv_aligned(p)) return 10 + t;
-    return (p.nsrc > 1 ? 6 : 0) + t;
+    if (p.offmask) return cp_variant_for_tile(CP_FAMILY_DCN_IGEMM, bn);
+    return cp_variant_for_tile(!conv_aligned(p) ? CP_FAMILY_IGEMM_UNALIGNED : p.nsrc > 1 ? CP_FAMILY_IGEMM_CAT : CP_FAMILY_IGEMM, bn);
 }
 
 const char* cp_conv_variant_name(int v) {
-    static const char* names[CP_NUM_CONV_VARIANTS] = {
-        "igemm_f32_16x16x4_m256n16", "igemm_f32_32x32x2_m256n32", "igemm_f32_32x32x2_m128n64",
-        "igemm_f32_32x32x2_m128n128", "dcn_igemm_f32_32x32x2_m128n64", "dcn_igemm_f32_32x32x2_m128n128",
-        "igemm_cat_f32_16x16x4_m256n16", "igemm_cat_f32_32x32x2_m256n32", "igemm_cat_f32_32x32x2_m128n64",
-        "igemm_cat_f32_32x32x2_m128n128", "igemm_unaligned_f32_16x16x4_m256n16", "igemm_unaligned_f32_32x32x2_m256n32",
-        "igemm_unaligned_f32_32x32x2_m128n64", "igemm_unaligned_f32_32x32x2_m128n128",
-        "igemm16_f16x3_m128n32", "igemm16_f16x3_m128n64", "igemm16_f16x3_m128n128", "dcn_igemm16_f16x3_m128n64",
-        "dcn_igemm16_f16x3_m128n128", "igemm16_cat_f16x3_m128n32", "igemm16_cat_f16x3_m128n64",
-        "igemm16_cat_f16x3_m128n128", "igemm16_head_f16x3_m128n128",
-        "lowc_stem7x7_f16x3", "lowc_3x3_c16_f16x3", "lowc_3x3s2_c16_f16x3", "igemm16_gru_f16x3_m128n96",
-        "halo16_f16x3_m128n32", "halo16_f16x3_m128n64", "halo16_f16x3_m128n128", "dcn16p_f16x3_p128n64", "gn_final_f32_valu", "halo16_head_f16x3_m128n128",
-        "halo16_gru_f16x3_m128n96", "pw16_f16x3_m128n64", "pw16_f16x3_m128n128", "dcn16s_f16x3_p128n64", "igemm16_f16x3_m64n64", "dcn16p_f16x3_p128n128",
-        "dcn16t_f16x3_p128n64", "lowc_stem_level0_f16x3", "strm16_f16x3_w32n32", "lowc_3x3s2_c16_rows_f16x3",
-        "deconv16_f32_32x32x2_m256n64", "deconv16_f16x3_m256n64", "igemm16_head_rows_f16x3_m128n128"};
+#define CP_X(name, id, str) str,
+    static const char* const names[CP_NUM_CONV_VARIANTS] = {CP_CONV_VARIANT_TABLE(CP_X)};
+#undef CP_X
     return (v >= 0 && v < CP_NUM_CONV_VARIANTS) ? names[v] : "?";
 }
 
 void cp_conv_geometry(const ConvParams& p, bool f16x3, int* tiles, int* nk) {
-    int bn = cp_conv_tile_n(p.Cout);
-    if (f16x3 && bn < 32) bn = 32;
-    if (f16x3 && p.tile_n && p.tile_n < bn && p.CoutPad % p.tile_n == 0 && (!p.offmask || p.tile_n == 64)) bn = p.tile_n;
+    const int bn = f16x3 ? cp_conv16_tile_n(p) : cp_conv_tile_n(p.Cout);
     const int bm = f16x3 ? ((bn == 64 && p.tile_m == 64) ? 64 : 128) : (bn <= 32 ? 256 : 128);
     const int M = p.B * p.Ho * p.Wo;
     *tiles = ((M + bm - 1) / bm) * ((p.Cout + bn - 1) / bn);
@@ -516,20 +496,27 @@ int cp_launch_conv(const ConvParams& p, hipStream_t stream) {
     if (p.nsrc < 1 || p.nsrc > CP_MAX_SRC || p.Cin % 4 != 0 || p.up_t) return CP_ERR_INVALID;  // (up_t: an f16x3 epilogue, dcn16t.hip)
     for (int s = 0; s < p.nsrc; ++s)
         if (p.src_c[s] % 4 != 0 || (p.nsrc > 1 && p.src_c[s] % BK != 0)) return CP_ERR_INVALID;
-    const int bn = cp_conv_tile_n(p.Cout);
-    if (p.offmask) {
-        // DCN: 3x3, stride 1, pad 1, one source, Cin % 16 == 0 (a K-step never straddles a tap)
-        if (p.KH != 3 || p.KW != 3 || p.stride != 1 || p.pad != 1 || p.nsrc != 1 || p.Cin % BK != 0 ||
-            p.H != p.Ho || p.W != p.Wo)
-            return CP_ERR_INVALID;
-        if (bn == 128) return launch<32, 2, 2, 2, 2, true>(p, stream);
-        if (bn == 64) return launch<32, 2, 1, 2, 2, true>(p, stream);
+    // DCN: 3x3, stride 1, pad 1, one source, Cin % 16 == 0 (a K-step never straddles a tap), Cout > 32
+    if (p.offmask && (p.KH != 3 || p.KW != 3 || p.stride != 1 || p.pad != 1 || p.nsrc != 1 || p.Cin % BK != 0 || p.H != p.Ho ||
+                      p.W != p.Wo || cp_conv_tile_n(p.Cout) < 64 || !conv_aligned(p)))
         return CP_ERR_INVALID;
-    }
-    switch (bn) {
-        case 16: return launch<16, 4, 1, 4, 1, false>(p, stream);
-        case 32: return launch<32, 2, 1, 4, 1, false>(p, stream);
-        case 64: return launch<32, 2, 1, 2, 2, false>(p, stream);
-        default: return launch<32, 2, 2, 2, 2, false>(p, stream);
+    if (!conv_aligned(p) && p.nsrc != 1) return CP_ERR_INVALID;
+    //                                                        FRAG MT NT WM WN  DCN   ALIGNED MULTISRC
+    switch (cp_conv_variant(p)) {
+        case CP_VARIANT_IGEMM_N16: return launch_a<16, 4, 1, 4, 1, false, true, false>(p, stream);
+        case CP_VARIANT_IGEMM_N32: return launch_a<32, 2, 1, 4, 1, false, true, false>(p, stream);
+        case CP_VARIANT_IGEMM_N64: return launch_a<32, 2, 1, 2, 2, false, true, false>(p, stream);
+        case CP_VARIANT_IGEMM_N128: return launch_a<32, 2, 2, 2, 2, false, true, false>(p, stream);
+        case CP_VARIANT_DCN_IGEMM_N64: return launch_a<32, 2, 1, 2, 2, true, true, false>(p, stream);
+        case CP_VARIANT_DCN_IGEMM_N128: return launch_a<32, 2, 2, 2, 2, true, true, false>(p, stream);
+        case CP_VARIANT_IGEMM_CAT_N16: return launch_a<16, 4, 1, 4, 1, false, true, true>(p, stream);
+        case CP_VARIANT_IGEMM_CAT_N32: return launch_a<32, 2, 1, 4, 1, false, true, true>(p, stream);
+        case CP_VARIANT_IGEMM_CAT_N64: return launch_a<32, 2, 1, 2, 2, false, true, true>(p, stream);
+        case CP_VARIANT_IGEMM_CAT_N128: return launch_a<32, 2, 2, 2, 2, false, true, true>(p, stream);
+        case CP_VARIANT_IGEMM_UNALIGNED_N16: return launch_a<16, 4, 1, 4, 1, false, false, false>(p, stream);
+        case CP_VARIANT_IGEMM_UNALIGNED_N32: return launch_a<32, 2, 1, 4, 1, false, false, false>(p, stream);
+        case CP_VARIANT_IGEMM_UNALIGNED_N64: return launch_a<32, 2, 1, 2, 2, false, false, false>(p, stream);
+        case CP_VARIANT_IGEMM_UNALIGNED_N128: return launch_a<32, 2, 2, 2, 2, false, false, false>(p, stream);
+        default: return CP_ERR_INVALID;
     }
 }

@@ -635,14 +635,6 @@ int cp_launch_absmax(const float* x, size_t n, unsigned* slot, hipStream_t s) {
     return hipGetLastError() == hipSuccess ? CP_OK : CP_ERR_LAUNCH;
 }
 
-// N tile of the f16x3 launch: cp_conv_tile_n, except that <= 16-wide outputs whose weights were packed to 32 columns
-// (the GroupNorm'd final 1x1 heads) take the 32-wide tile
-static int conv16_tile_n(const ConvParams& p) {
-    const int bn = cp_conv_tile_n(p.Cout);
-    if (p.tile_n && p.tile_n < bn && p.CoutPad % p.tile_n == 0 && (!p.offmask || p.tile_n == 64)) return p.tile_n;
-    return (bn < 32 && p.CoutPad >= 32 && p.CoutPad % 32 == 0) ? 32 : bn;
-}
-
 // DCNv2 layers whose launch fills the chip gather from an LDS-staged halo (dcn16p.hip); small launches keep dcn16.hip
 // (split-K).  CP_SEL_DCN16P_NEVER / _ALWAYS: never / every eligible layer (tests, A/B runs).
 static bool dcn16p_wanted(const ConvParams& p) {
@@ -696,7 +688,7 @@ bool cp_conv16_supported(const ConvParams& p) {
     if (!p.w16_hi || !p.w16_lo || p.Cin % BK16 != 0 || p.KH * p.KW > 32) return false;
     for (int s = 0; s < p.nsrc; ++s)
         if (p.src_c[s] % BK16 != 0) return false;
-    const int bn = conv16_tile_n(p);
+    const int bn = cp_conv16_tile_n(p);
     if (bn < 32) return false;
     if (p.gn_in_mr) return false;  // the per-group form belongs to the exact-f32 loader
     if (p.gn_in_a || p.gn_in_d) {
@@ -712,40 +704,16 @@ bool cp_conv16_supported(const ConvParams& p) {
     return true;
 }
 
-// would cp_launch_conv16 run this launch with ConvParams::pj_src set?  (the engine asks before it decides not to launch the
-// projection on its own)
-bool cp_conv16_project_supported(const ConvParams& p) {
-    if (!cp_conv16_supported(p) || p.offmask || p.gn_in_a || p.up_t) return false;
-    const int bn = conv16_tile_n(p);
-    return !(bn == 64 && p.tile_m == 64) && halo16_wanted(p, bn) && cp_halo16_project_supported(p, bn);
-}
-
-int cp_launch_conv16(const ConvParams& p, hipStream_t stream) {
-    if (!cp_conv16_supported(p)) return CP_ERR_INVALID;
-    // the up-sample + add epilogue (ConvParams::up_t) exists in dcn16t only: a launch that would go elsewhere is an error
-    if (p.up_t && !(p.offmask && dcn16t_wanted(p) && cp_dcn16t_upadd_supported(p))) return CP_ERR_INVALID;
-    const int bn = conv16_tile_n(p);
-    // ... the 2x2 max-pooled second output (ConvParams::pool_out) in pw16s_kernel only
-    if (p.pool_out && !(pw16_wanted(p) && cp_conv16_variant(p) == CP_VARIANT_PW16 + (p.CoutPad % 128 == 0 ? 1 : 0) && cp_pw16_pool_supported(p)))
-        return CP_ERR_INVALID;
-    // ... and the 1x1 projection as the residual (ConvParams::pj_src) in halo16's 64- and 128-wide tiles only
-    if (p.pj_src) return cp_conv16_project_supported(p) ? cp_launch_halo16(p, bn, stream) : CP_ERR_INVALID;
-    const bool cat = p.nsrc > 1;
-    if (p.gn_in_a) {
-        const int M = p.B * p.Ho * p.Wo;
-        const int tiles_m = (M + 127) / 128, tiles_n = p.CoutPad / 32;
-        hipLaunchKernelGGL((igemm16p_kernel<1, 1, 4, 1, false, false, true>),
-                           dim3(tiles_m * tiles_n, p.splitk > 1 ? p.splitk : 1), dim3(NT16), 0, stream, p, tiles_m, tiles_n);
-        return hipGetLastError() == hipSuccess ? CP_OK : CP_ERR_LAUNCH;
-    }
+// The f16x3 selector, the one place the cascade is written (ids: conv_variants.h): cp_launch_conv16 dispatches on its answer, and
+// the engine records it and decides its fusions by it.  For a launch cp_conv16_supported accepts.
+int cp_conv16_variant(const ConvParams& p) {
+    const int bn = cp_conv16_tile_n(p);
     if (p.offmask) {
-        if (p.KH != 3 || p.KW != 3 || p.stride != 1 || p.pad != 1 || p.nsrc != 1 || p.H != p.Ho || p.W != p.Wo)
-            return CP_ERR_INVALID;
         // the patch-resident gathers where the launch fills the chip, dcn16.hip's software-pipelined gather otherwise
-        if (dcn16t_wanted(p)) return cp_launch_dcn16t(p, stream);
-        if (dcn16s_wanted(p)) return cp_launch_dcn16s(p, stream);
-        if (dcn16p_wanted(p)) return cp_launch_dcn16p(p, stream);
-        return cp_launch_dcn16(p, bn, stream);
+        if (dcn16t_wanted(p)) return CP_VARIANT_DCN16T;
+        if (dcn16s_wanted(p)) return CP_VARIANT_DCN16S;
+        if (dcn16p_wanted(p)) return cp_dcn16p_wide(p) ? CP_VARIANT_DCN16PW : CP_VARIANT_DCN16P;
+        return cp_variant_for_tile(CP_FAMILY_DCN16, bn);
     }
     // 3x3 / stride 1 layers with full 8x16 patches can run on the halo-resident kernel (halo16.hip).  Measured on the
     // dlav1_34 B=32 step (profiles/r02_halo_ab.txt): N tile 32 (conv_offset_mask) 62 -> 103 TFLOP/s, N 64 223 -> 212,
@@ -753,25 +721,57 @@ int cp_launch_conv16(const ConvParams& p, hipStream_t stream) {
     // clock, not by the A-side loads / conversion the halo removes, so only the 32-wide tile uses it by default.
     // CP_SEL_HALO_NEVER / _ALWAYS: never / every eligible layer (A/B runs).
     // small launches on 64 x 64 tiles (ConvParams::tile_m): the LDS-staged loop, whatever the layer shape
-    if (bn == 64 && p.tile_m == 64) return cat ? launch16<1, 1, 2, 2, true>(p, stream) : launch16<1, 1, 2, 2, false>(p, stream);
-    if (bn == 32 && strm16_wanted(p)) return cp_launch_strm16(p, stream);
-    if (halo16_wanted(p, bn)) return cp_launch_halo16(p, bn, stream);
-    if (pw16_wanted(p)) return cp_launch_pw16(p, stream);
-    if (bn == 128) return cat ? launch16<2, 2, 2, 2, true>(p, stream) : launch16<2, 2, 2, 2, false>(p, stream);
-    if (bn == 64) return cat ? launch16<2, 1, 2, 2, true>(p, stream) : launch16<2, 1, 2, 2, false>(p, stream);
-    return cat ? launch16<1, 1, 4, 1, true>(p, stream) : launch16<1, 1, 4, 1, false>(p, stream);
-}
-
-// kernel-variant ids continue after the exact-f32 ones (cp_conv_variant): 14.. = split-f16 instantiations
-int cp_conv16_variant(const ConvParams& p) {
-    const int bn = conv16_tile_n(p);
-    if (p.offmask) return dcn16t_wanted(p) ? CP_VARIANT_DCN16T : dcn16s_wanted(p) ? CP_VARIANT_DCN16S : dcn16p_wanted(p) ? (cp_dcn16p_wide(p) ? CP_VARIANT_DCN16PW : CP_VARIANT_DCN16P) : bn == 128 ? 18 : 17;
-    const int t = bn == 32 ? 0 : bn == 64 ? 1 : 2;
     if (bn == 64 && p.tile_m == 64) return CP_VARIANT_M64N64;
     if (bn == 32 && strm16_wanted(p)) return CP_VARIANT_STRM16;
-    if (halo16_wanted(p, bn)) return 27 + t;
-    if (pw16_wanted(p)) return CP_VARIANT_PW16 + (p.CoutPad % 128 == 0 ? 1 : 0);
-    return (p.nsrc > 1 ? 19 : 14) + t;
+    if (halo16_wanted(p, bn)) return cp_variant_for_tile(CP_FAMILY_HALO16, bn);
+    if (pw16_wanted(p)) return cp_variant_for_tile(CP_FAMILY_PW16, p.CoutPad % 128 == 0 ? 128 : 64);
+    return cp_variant_for_tile(p.nsrc > 1 ? CP_FAMILY_IGEMM16_CAT : CP_FAMILY_IGEMM16, bn);
+}
+
+// ConvParams::pj_src (the 1x1 projection as the residual) exists in halo16's 64- and 128-wide tiles only: does the launch, on
+// variant v, land there?
+static bool conv16_project_on(const ConvParams& p, int v) {
+    return !p.up_t && cp_variant_is_halo16(v) && cp_halo16_project_supported(p, cp_conv16_tile_n(p));
+}
+// would cp_launch_conv16 run this launch with ConvParams::pj_src set?  (the engine asks before it decides not to launch the
+// projection on its own)
+bool cp_conv16_project_supported(const ConvParams& p) { return cp_conv16_supported(p) && conv16_project_on(p, cp_conv16_variant(p)); }
+
+int cp_launch_conv16(const ConvParams& p, hipStream_t stream) {
+    if (!cp_conv16_supported(p)) return CP_ERR_INVALID;
+    const int v = cp_conv16_variant(p), bn = cp_conv16_tile_n(p);
+    // the up-sample + add epilogue (ConvParams::up_t) exists in dcn16t only: a launch that would go elsewhere is an error
+    if (p.up_t && !(v == CP_VARIANT_DCN16T && cp_dcn16t_upadd_supported(p))) return CP_ERR_INVALID;
+    // ... the 2x2 max-pooled second output (ConvParams::pool_out) in pw16s_kernel only, and the projection (above)
+    if (p.pool_out && !(cp_variant_is_pw16(v) && cp_pw16_pool_supported(p))) return CP_ERR_INVALID;
+    if (p.pj_src && !conv16_project_on(p, v)) return CP_ERR_INVALID;
+    if (p.offmask && (p.KH != 3 || p.KW != 3 || p.stride != 1 || p.pad != 1 || p.nsrc != 1 || p.H != p.Ho || p.W != p.Wo))
+        return CP_ERR_INVALID;
+    switch (v) {
+        case CP_VARIANT_DCN16T: return cp_launch_dcn16t(p, stream);
+        case CP_VARIANT_DCN16S: return cp_launch_dcn16s(p, stream);
+        case CP_VARIANT_DCN16P: return cp_launch_dcn16p(p, false, stream);
+        case CP_VARIANT_DCN16PW: return cp_launch_dcn16p(p, true, stream);
+        case CP_VARIANT_DCN16_N64: case CP_VARIANT_DCN16_N128: return cp_launch_dcn16(p, bn, stream);
+        case CP_VARIANT_M64N64: return p.nsrc > 1 ? launch16<1, 1, 2, 2, true>(p, stream) : launch16<1, 1, 2, 2, false>(p, stream);
+        case CP_VARIANT_STRM16: return cp_launch_strm16(p, stream);
+        case CP_VARIANT_HALO16_N32: case CP_VARIANT_HALO16_N64: case CP_VARIANT_HALO16_N128: return cp_launch_halo16(p, bn, stream);
+        case CP_VARIANT_PW16_N64: case CP_VARIANT_PW16_N128: return cp_launch_pw16(p, stream);
+        case CP_VARIANT_IGEMM16_N128: return launch16<2, 2, 2, 2, false>(p, stream);
+        case CP_VARIANT_IGEMM16_CAT_N128: return launch16<2, 2, 2, 2, true>(p, stream);
+        case CP_VARIANT_IGEMM16_N64: return launch16<2, 1, 2, 2, false>(p, stream);
+        case CP_VARIANT_IGEMM16_CAT_N64: return launch16<2, 1, 2, 2, true>(p, stream);
+        case CP_VARIANT_IGEMM16_CAT_N32: return launch16<1, 1, 4, 1, true>(p, stream);
+        case CP_VARIANT_IGEMM16_N32: {
+            if (!p.gn_in_a) return launch16<1, 1, 4, 1, false>(p, stream);
+            const int M = p.B * p.Ho * p.Wo;  // the GroupNorm'd 1x1: normalise + affine + ReLU on load
+            const int tiles_m = (M + 127) / 128, tiles_n = p.CoutPad / 32;
+            hipLaunchKernelGGL((igemm16p_kernel<1, 1, 4, 1, false, false, true>),
+                               dim3(tiles_m * tiles_n, p.splitk > 1 ? p.splitk : 1), dim3(NT16), 0, stream, p, tiles_m, tiles_n);
+            return hipGetLastError() == hipSuccess ? CP_OK : CP_ERR_LAUNCH;
+        }
+        default: return CP_ERR_INVALID;
+    }
 }
 
 int cp_launch_pack_weight16(const float* w, void* hi, void* lo, int Cout, int Cin, int taps, int Kpad16, int coff,
@@ -790,10 +790,14 @@ bool cp_head_fuse_supported(const ConvParams& p, int c2) {
            (p.act == CP_ACT_RELU || p.act == CP_ACT_NONE);
 }
 
+// the fused head's and the fused GRU step's kernel: halo16.hip's where it takes the launch, igemm16p's otherwise
+int cp_conv16_fused_head_variant(const ConvParams& p) { return cp_halo16_fused_head_supported(p) ? CP_VARIANT_HALO_HEAD : CP_VARIANT_FUSED_HEAD; }
+int cp_conv16_gru_variant(const ConvParams& p) { return cp_halo16_gru_supported(p) ? CP_VARIANT_HALO_GRU : CP_VARIANT_GRU; }
+
 int cp_launch_conv16_fused_head(const ConvParams& p, hipStream_t stream) {
     if (!cp_head_fuse_supported(p, p.fuse_c2) || !p.fuse_w2_hi || !p.fuse_w2_lo || !p.fuse_out || p.splitk > 1)
         return CP_ERR_INVALID;
-    if (cp_halo16_fused_head_supported(p)) return cp_launch_halo16_fused_head(p, stream);  // halo16.hip
+    if (cp_conv16_fused_head_variant(p) == CP_VARIANT_HALO_HEAD) return cp_launch_halo16_fused_head(p, stream);
     const int M = p.B * p.Ho * p.Wo;
     const int tiles_m = (M + 127) / 128, tiles_n = p.CoutPad / 128;
     hipLaunchKernelGGL((igemm16p_kernel<2, 2, 2, 2, false, true>), dim3(tiles_m * tiles_n), dim3(NT16), 0, stream, p,
@@ -858,7 +862,7 @@ int cp_launch_conv16_gru(const ConvParams& p, hipStream_t stream) {
         p.CoutPad != 192 || p.KH != 3 || p.KW != 3 || p.stride != 1 || p.pad != 1 || p.Kpad16 != 576 || p.splitk > 1 ||
         (size_t)p.B * p.H * p.W * 192 * 4 >= (size_t)0xf0000000u)
         return CP_ERR_INVALID;
-    if (cp_halo16_gru_supported(p)) return cp_launch_halo16_gru(p, stream);  // halo16.hip
+    if (cp_conv16_gru_variant(p) == CP_VARIANT_HALO_GRU) return cp_launch_halo16_gru(p, stream);
     const int M = p.B * p.Ho * p.Wo;
     const int tiles_m = (M + 127) / 128, tiles_n = 2;
     hipLaunchKernelGGL((igemm16p_kernel<1, 3, 4, 1, false, false, false, true>), dim3(tiles_m * tiles_n), dim3(NT16), 0,

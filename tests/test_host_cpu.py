@@ -111,6 +111,10 @@ def test_kernel_variant_and_role_tables_match_the_header(built):
     names = [built.cp_kernel_variant_name(v).decode() for v in range(nv)]
     assert all(n and n != "?" for n in names) and len(set(names)) == nv, names
     assert built.cp_kernel_variant_name(nv).decode() == "?"
+    # ids are contract (profiles/, tests/golden/engine_plan_pins.json): a name belongs to its id, not only to the table
+    pinned = {22: "igemm16_head_f16x3_m128n128", 30: "dcn16p_f16x3_p128n64", 36: "dcn16s_f16x3_p128n64", 39: "dcn16t_f16x3_p128n64",
+              41: "strm16_f16x3_w32n32", 45: "igemm16_head_rows_f16x3_m128n128"}
+    assert {v: names[v] for v in pinned} == pinned
     roles = [built.cp_role_name(r).decode() for r in range(nr)]
     assert all(n and n != "?" for n in roles) and len(set(roles)) == nr, roles
     # the binding sizes its buffers from the library's own counts (no copies of the #defines in hip.py)
