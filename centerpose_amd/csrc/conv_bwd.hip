@@ -1,7 +1,9 @@
 // Backward of the ordinary convolution (cp_conv2d_backward_nhwc): autograd's gradients of out = conv2d(x, w) + bias, dilation 1,
 // groups 1, on the forward's layouts (x [B,H,W,Cin] NHWC, w [Cout,Cin,KH,KW], grad_out [B,Ho,Wo,Cout] NHWC).  It replaces
 // torch.nn.Conv2d's backward in pose_dla_dcn.py:48-62 (BasicBlock), the Root / project 1x1s and DCNv2/dcn_v2.py:118-128
-// (conv_offset_mask).  Float32 arithmetic only; every sum has a fixed order; no atomics.
+// (conv_offset_mask).  Float32 arithmetic by default; every sum has a fixed order; no atomics.  With CP_PREC_F16X3
+// (cp_conv2d_backward_prec_nhwc) the two contractions of the MFMA path, steps 1 and 2, run on the split-binary16 kernels of
+// conv_bwd16.hip; step 0, the slab reduction's order and the other two paths are the same in either mode.
 //
 // On the caller's stream:
 //   0. stage    (stage_kernel) gs[q][CoP] = grad_out[q][co] * (y[q][co] > 0), zero in the pad lanes co >= Cout, CoP = Cout
@@ -165,14 +167,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void w
 // grad_w[co][c][tap] = the slabs [co][tap * Cin + c] (co < Cout of CoP rows), summed by two_level_sum; threads walk the slabs'
 // own element order (whole 128-byte lines per slab) and scatter the one write.  `accum`: the value already in grad_w is added
 // LAST, to the finished sum of the slabs (a caller that works through its batch in chunks: chunks in chunk order); without it
-// the slabs' sum is stored as it is.
+// the slabs' sum is stored as it is.  `ga`, `xa` (f16x3 slabs, conv_bwd16.hip): the |max| slots of the two operands; the finished
+// sum of the slabs is multiplied by 2^-e_g, then 2^-e_x (exact), before it is stored or accumulated.
 __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ slab, float* __restrict__ gw, int nslab, int Cout,
-                                                           int CoP, int Cin, int taps, int accum) {
+                                                           int CoP, int Cin, int taps, int accum, const unsigned* __restrict__ ga,
+                                                           const unsigned* __restrict__ xa) {
     __shared__ float red[256];
+    float gi = 1.f, xi = 1.f, fw;
+    if (ga) {
+        cp_amax_to_scale(cp_amax_read(ga), &fw, &gi);
+        cp_amax_to_scale(cp_amax_read(xa), &fw, &xi);
+    }
     const size_t TC = (size_t)taps * Cin, n = (size_t)Cout * TC, ss = (size_t)CoP * TC;
     for (size_t base = (size_t)blockIdx.x * 32; base < n; base += (size_t)gridDim.x * 32) {  // (uniform per workgroup)
         const size_t i = base + (threadIdx.x & 31);
-        const float t = two_level_sum(red, i < n, nslab, 0.f, [&](float v, int s) { return v + slab[(size_t)s * ss + i]; });
+        float t = two_level_sum(red, i < n, nslab, 0.f, [&](float v, int s) { return v + slab[(size_t)s * ss + i]; });
+        if (ga) t = t * gi * xi;
         if (threadIdx.x < 32 && i < n) {
             const size_t h = i / TC;
             const int k = (int)(i - h * TC), tap = k / Cin, c = k - tap * Cin;
@@ -408,9 +418,10 @@ struct Plan {
     int st_ct, st_px, st_slabs, st_bound;  // stage_kernel: channel lanes, pixels per slab, slabs and their upper bound
     ConvWgradPlan wg;                      // weight gradient, MFMA and generic path
     ConvLowcPlan lw;                       // weight gradient, low-channel path
+    bool wg16, dg16;                       // f16x3 (conv_bwd16.hip): the weight gradient, the data gradient
 };
 
-Plan plan(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
+Plan plan(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int precision) {
     Plan P;
     P.path = cp_conv_backward_path(B, H, W, Cin, Cout, KH, KW, stride, pad);
     P.mfma = P.path == CP_CONV_BWD_MFMA;
@@ -432,20 +443,36 @@ Plan plan(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, in
         P.lw = cp_conv_lowc_wgrad_plan(B, P.Ho, P.Wo, stride);
         P.wg.slab_bytes = std::max(P.wg.slab_bytes, cp_conv_lowc_slab_bytes(B, P.Ho, P.Wo, Cout, stride));
     }
+    // f16x3: the MFMA path only; a stride-1 data gradient igemm16.hip cannot take (byte offsets past 32 bits) stays float32
+    P.wg16 = P.mfma && precision == CP_PREC_F16X3;
+    P.dg16 = P.wg16 && (stride == 2 || cp_conv_dgrad16_s1_supported(B, H, W, Cin, P.CoP, KH));
     return P;
 }
 
 struct Ws {
     float *gs, *part, *slab, *wB;
+    // f16x3: the |max| slot block (slot 0: gs, slot 1: x) and the split copies of gs and x
+    unsigned* slot;
+    uint32_t *gs16, *x16;
 };
-Ws conv_bwd_carve(Carve& c, const Plan& P, int B, int Cin, int stride, bool need_gx) {
+Ws conv_bwd_carve(Carve& c, const Plan& P, int B, int H, int W, int Cin, int stride, bool need_gx) {
     Ws r;
-    r.gs = c.take<float>((size_t)B * P.Ho * P.Wo * P.CoP * 4);
+    const size_t gsb = (size_t)B * P.Ho * P.Wo * P.CoP * 4;
+    r.gs = c.take<float>(gsb);
     r.part = c.take<float>((size_t)P.st_bound * P.CoP * 4);  // (the slab count's upper bound: monotone in B)
     r.slab = c.take<float>(P.wg.slab_bytes);
     r.wB = c.take<float>(!need_gx || !P.mfma ? 0
+                         : P.dg16            ? cp_conv_dgrad16_pack_bytes(Cin, P.CoP, P.taps, stride)
                          : stride == 1       ? cp_conv_dgrad_pack_bytes(Cin, P.CoP, P.taps)
                                              : (size_t)P.CoP * P.taps * Cin * 4);
+    r.slot = nullptr;
+    r.gs16 = r.x16 = nullptr;
+    if (P.wg16) {  // (nothing is taken in float32: that workspace is the one it always was)
+        r.slot = c.take<unsigned>((size_t)CP_AMAX_SUB * CP_AMAX_STRIDE * sizeof(unsigned));
+        r.gs16 = c.take<uint32_t>(gsb);
+        // (a 1x1 layer reads each x element once: its weight gradient splits x in registers, no copy)
+        r.x16 = c.take<uint32_t>(P.taps > 1 ? (size_t)B * H * W * Cin * 4 : 0);
+    }
     return r;
 }
 
@@ -474,38 +501,48 @@ ConvWgradPlan cp_conv_wgrad_plan(size_t rows, int Cin, int CoP, int taps) {
 }
 
 int cp_launch_conv_wgrad(hipStream_t s, const ConvBwdArgs& a, const float* gs, int CoP, const ConvWgradPlan& P, float* slab,
-                         int accum) {
+                         int accum, const ConvWgrad16* h) {
     const int Ho = (a.H + 2 * a.pad - a.KH) / a.stride + 1, Wo = (a.W + 2 * a.pad - a.KW) / a.stride + 1;
     const int taps = a.KH * a.KW, rows = a.B * Ho, slabs = (rows + P.rows_per_slab - 1) / P.rows_per_slab;
     const dim3 wg((P.jobs + 3) / 4, 1, slabs);
 #define CP_WGRAD(NH)                                                                                                            \
     hipLaunchKernelGGL(wgrad_kernel<NH>, wg, dim3(256), 0, s, gs, a.x, slab, rows, Ho, Wo, a.H, a.W, a.Cin, CoP, a.KW, taps, a.stride, \
                        a.pad, P.rows_per_slab)
-    switch (nh_of(CoP)) {
-        case 4: CP_WGRAD(4); break;
-        case 2: CP_WGRAD(2); break;
-        default: CP_WGRAD(1);
+    if (h) {
+        const int rc = cp_launch_conv_wgrad16_slabs(s, a, *h, CoP, P, slab);
+        if (rc != CP_OK) return rc;
+    } else {
+        switch (nh_of(CoP)) {
+            case 4: CP_WGRAD(4); break;
+            case 2: CP_WGRAD(2); break;
+            default: CP_WGRAD(1);
+        }
     }
 #undef CP_WGRAD
     if (!launch_ok()) return CP_ERR_LAUNCH;
     const size_t rg = std::min<size_t>(((size_t)a.Cout * taps * a.Cin + 31) / 32, 8192);
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)rg), dim3(256), 0, s, (const float*)slab, a.gw, slabs, a.Cout, CoP, a.Cin,
-                       taps, accum);
+                       taps, accum, h ? h->gs_amax : (const unsigned*)nullptr, h ? h->x_amax : (const unsigned*)nullptr);
     return launch_ok() ? CP_OK : CP_ERR_LAUNCH;
 }
 
 // wB [taps CoP][cpad], cpad = Cin rounded up to the N tile of the convolution that reads it
 static int dgrad_cpad(int Cin) { return (int)cp_engine::align_up((size_t)Cin, cp_conv_tile_n(Cin)); }
 
-size_t cp_conv_dgrad_pack_bytes(int Cin, int CoP, int taps) { return (size_t)taps * CoP * dgrad_cpad(Cin) * 4; }
+size_t cp_conv_dgrad_pack_bytes(int Cin, int CoP, int taps, int precision) {
+    return precision == CP_PREC_F16X3 ? cp_conv_dgrad16_pack_bytes(Cin, CoP, taps, 1) : (size_t)taps * CoP * dgrad_cpad(Cin) * 4;
+}
 
-int cp_launch_conv_dgrad_pack(hipStream_t s, const float* w, float* wB, int Cin, int Cout, int CoP, int taps) {
+int cp_launch_conv_dgrad_pack(hipStream_t s, const float* w, float* wB, int Cin, int Cout, int CoP, int taps, int precision) {
+    if (precision == CP_PREC_F16X3) return cp_launch_conv_dgrad16_pack(s, w, wB, Cin, Cout, CoP, taps, 1);
     if (hipMemsetAsync(wB, 0, cp_conv_dgrad_pack_bytes(Cin, CoP, taps), s) != hipSuccess) return CP_ERR_LAUNCH;
     hipLaunchKernelGGL(pack_dgrad_kernel, dim3(256), dim3(256), 0, s, w, wB, Cout, CoP, Cin, taps, dgrad_cpad(Cin));
     return launch_ok() ? CP_OK : CP_ERR_LAUNCH;
 }
 
-int cp_launch_conv_dgrad_s1(hipStream_t s, const ConvBwdArgs& a, const float* gs, int CoP, const float* wB, const float* res) {
+int cp_launch_conv_dgrad_s1(hipStream_t s, const ConvBwdArgs& a, const float* gs, int CoP, const float* wB, const float* res,
+                            const unsigned* gs_amax) {
+    if (gs_amax) return cp_launch_conv_dgrad16_s1(s, a, gs, CoP, wB, res, gs_amax);
     // (stride 1, pad K / 2: the output grid is the input grid, and the operand is a [a.Cin][CoP][KH][KW] weight)
     ConvParams d = grad_conv_params(a.B, a.H, a.W, gs, CoP, (float*)wB, nullptr, a.Cin, a.KH, a.KW, 1, a.pad, a.gx);
     d.res = res;
@@ -518,16 +555,22 @@ int cp_launch_rowsum_nchw(const float* g, float* out, int B, int C, int HW, hipS
     return launch_ok() ? CP_OK : CP_ERR_LAUNCH;
 }
 
-size_t cp_conv_backward_ws_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int need_grad_x) {
+size_t cp_conv_backward_ws_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int need_grad_x,
+                                 int precision) {
     Carve c{nullptr};
-    conv_bwd_carve(c, plan(B, H, W, Cin, Cout, KH, KW, stride, pad), B, Cin, stride, need_grad_x != 0);
+    conv_bwd_carve(c, plan(B, H, W, Cin, Cout, KH, KW, stride, pad, precision), B, H, W, Cin, stride, need_grad_x != 0);
     return c.off;
 }
 
-int cp_launch_conv_backward(hipStream_t s, const ConvBwdArgs& a, void* ws) {
-    const Plan P = plan(a.B, a.H, a.W, a.Cin, a.Cout, a.KH, a.KW, a.stride, a.pad);
+int cp_conv_backward_prec_mask(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int precision) {
+    const Plan P = plan(B, H, W, Cin, Cout, KH, KW, stride, pad, precision);
+    return (P.wg16 ? 1 : 0) | (P.dg16 ? 2 : 0);
+}
+
+int cp_launch_conv_backward(hipStream_t s, const ConvBwdArgs& a, void* ws, int precision) {
+    const Plan P = plan(a.B, a.H, a.W, a.Cin, a.Cout, a.KH, a.KW, a.stride, a.pad, precision);
     Carve cv{(char*)ws};
-    const Ws r = conv_bwd_carve(cv, P, a.B, a.Cin, a.stride, a.gx != nullptr);
+    const Ws r = conv_bwd_carve(cv, P, a.B, a.H, a.W, a.Cin, a.stride, a.gx != nullptr);
     float *gsb = r.gs, *part = r.part, *slab = r.slab, *wB = r.wB;
     const int B = a.B, H = a.H, W = a.W, Cin = a.Cin, Cout = a.Cout, Ho = P.Ho, Wo = P.Wo, CoP = P.CoP, taps = P.taps;
     const int Q = B * Ho * Wo, rows = B * Ho;
@@ -544,15 +587,27 @@ int cp_launch_conv_backward(hipStream_t s, const ConvBwdArgs& a, void* ws) {
             if (!launch_ok()) return CP_ERR_LAUNCH;
         }
     }
+    // f16x3: the |max| of gs and x, then their split copies (the gate, the pad lanes and grad_bias above stay float32)
+    const unsigned *g_amax = r.slot, *x_amax = r.slot + 1;
+    if (P.wg16) {
+        const size_t ng = (size_t)Q * CoP, nx = (size_t)B * H * W * Cin;
+        if (hipMemsetAsync(r.slot, 0, (size_t)CP_AMAX_SUB * CP_AMAX_STRIDE * sizeof(unsigned), s) != hipSuccess) return CP_ERR_LAUNCH;
+        int rc = cp_launch_absmax32(gs, ng, r.slot, s);
+        if (rc == CP_OK) rc = cp_launch_absmax32(a.x, nx, r.slot + 1, s);
+        if (rc == CP_OK) rc = cp_launch_split16(gs, r.gs16, ng, g_amax, s);
+        if (rc == CP_OK && taps > 1) rc = cp_launch_split16(a.x, r.x16, nx, x_amax, s);
+        if (rc != CP_OK) return rc;
+    }
     // 1. grad_w
     if (P.mfma) {
-        const int rc = cp_launch_conv_wgrad(s, a, gs, CoP, P.wg, slab, 0);
+        const ConvWgrad16 h{r.gs16, taps > 1 ? r.x16 : nullptr, g_amax, x_amax};
+        const int rc = cp_launch_conv_wgrad(s, a, gs, CoP, P.wg, slab, 0, P.wg16 ? &h : nullptr);
         if (rc != CP_OK) return rc;
     } else if (P.path == CP_CONV_BWD_LOWC) {
         const int rc = cp_launch_conv_lowc_wgrad(s, a, gs, P.lw, slab);
         if (rc != CP_OK) return rc;
         hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((Cout * taps * Cin + 31) / 32), dim3(256), 0, s, (const float*)slab, a.gw,
-                           P.lw.wgs, Cout, CoP, Cin, taps, 0);
+                           P.lw.wgs, Cout, CoP, Cin, taps, 0, (const unsigned*)nullptr, (const unsigned*)nullptr);
         if (!launch_ok()) return CP_ERR_LAUNCH;
     } else {
         const int n = Cout * Cin * taps;
@@ -572,8 +627,12 @@ int cp_launch_conv_backward(hipStream_t s, const ConvBwdArgs& a, void* ws) {
         return launch_ok() ? CP_OK : CP_ERR_LAUNCH;
     }
     if (a.stride == 1) {
-        const int rc = cp_launch_conv_dgrad_pack(s, a.w, wB, Cin, Cout, CoP, taps);
-        return rc != CP_OK ? rc : cp_launch_conv_dgrad_s1(s, a, gs, CoP, wB, nullptr);
+        const int rc = cp_launch_conv_dgrad_pack(s, a.w, wB, Cin, Cout, CoP, taps, P.dg16 ? CP_PREC_F16X3 : CP_PREC_F32);
+        return rc != CP_OK ? rc : cp_launch_conv_dgrad_s1(s, a, gs, CoP, wB, nullptr, P.dg16 ? g_amax : nullptr);
+    }
+    if (P.dg16) {
+        const int rc = cp_launch_conv_dgrad16_pack(s, a.w, wB, Cin, Cout, CoP, taps, 2);
+        return rc != CP_OK ? rc : cp_launch_conv_dgrad16_s2(s, a, r.gs16, CoP, wB, g_amax);
     }
     if (hipMemsetAsync(wB, 0, (size_t)CoP * taps * Cin * 4, s) != hipSuccess) return CP_ERR_LAUNCH;
     hipLaunchKernelGGL(pack_dgrad_s2_kernel, dim3(256), dim3(256), 0, s, a.w, wB, Cout, CoP, Cin, taps);

@@ -488,8 +488,13 @@ bool cp_conv_backward_mfma(int Cin, int KH, int KW, int stride, int pad);  // th
 bool cp_conv_backward_lowc(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad);
 // CP_CONV_BWD_*: the path cp_launch_conv_backward takes (what cp_conv2d_backward_path reports); a valid geometry is assumed
 int cp_conv_backward_path(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad);
-size_t cp_conv_backward_ws_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int need_grad_x);
-int cp_launch_conv_backward(hipStream_t s, const ConvBwdArgs& a, void* ws);
+// `precision` (CP_PREC_*): CP_PREC_F16X3 runs the MFMA path's two contractions on the split-binary16 kernels of conv_bwd16.hip;
+// the other paths, the gate, the pad lanes and grad_bias are float32 in either mode.  cp_conv_backward_prec_mask: bit 0 = the
+// weight gradient, bit 1 = the data gradient runs in f16x3 (0 for CP_PREC_F32 and off the MFMA path).
+size_t cp_conv_backward_ws_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int need_grad_x,
+                                 int precision = 0);
+int cp_launch_conv_backward(hipStream_t s, const ConvBwdArgs& a, void* ws, int precision = 0);
+int cp_conv_backward_prec_mask(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int precision);
 // Its two MFMA contractions (cp_conv_backward_mfma geometries) as building blocks: cp_launch_conv_backward is made of them, and
 // heads_bwd.hip runs them per head and chunk of images.  They read the geometry, x, gw and gx of `a` and, in place of a.go,
 // gs [B,Ho,Wo,CoP]: grad_out already gated, CoP = Cout rounded up to 32 with zeros in the pad lanes.
@@ -499,13 +504,35 @@ struct ConvWgradPlan {
 };
 ConvWgradPlan cp_conv_wgrad_plan(size_t rows, int Cin, int CoP, int taps);  // rows = B x Ho
 // a.gw = (accum ? a.gw : 0) + the slabs' sum.  P may have been planned for more rows than a.B x Ho (a partial last chunk).
+// `h` (f16x3): the split operands of conv_bwd16.hip in place of gs and a.x -- one dword per element, binary16 hi | lo << 16 of
+// the element times 2^e from the tensor's |max| slot (cp_launch_absmax32, then cp_launch_split16); the slabs' sum is multiplied
+// by 2^-(e_g + e_x) before it is stored or accumulated.  nullptr: float32.
+struct ConvWgrad16 {
+    const uint32_t *gs16, *x16;        // [B,Ho,Wo,CoP], [B,H,W,Cin]; x16 nullptr: a.x is scaled and split inside the kernel
+    const unsigned *gs_amax, *x_amax;  // their |max| slots (CP_AMAX_SUB sub-slots each)
+};
 int cp_launch_conv_wgrad(hipStream_t s, const ConvBwdArgs& a, const float* gs, int CoP, const ConvWgradPlan& P, float* slab,
-                         int accum);
+                         int accum, const ConvWgrad16* h = nullptr);
 // Stride 1: w in the data gradient's operand form wB (any contents before), once per weight; then a.gx = gs (*) w^T (+ res
-// [B,H,W,Cin], which may be a.gx itself) per launch
-size_t cp_conv_dgrad_pack_bytes(int Cin, int CoP, int taps);
-int cp_launch_conv_dgrad_pack(hipStream_t s, const float* w, float* wB, int Cin, int Cout, int CoP, int taps);
-int cp_launch_conv_dgrad_s1(hipStream_t s, const ConvBwdArgs& a, const float* gs, int CoP, const float* wB, const float* res);
+// [B,H,W,Cin], which may be a.gx itself) per launch.  precision CP_PREC_F16X3 packs the split-binary16 operand of igemm16.hip
+// instead (a power-of-two scale per input channel of the layer); the launch then takes gs's |max| slot, and is only valid where
+// cp_conv_dgrad16_s1_supported says so.
+size_t cp_conv_dgrad_pack_bytes(int Cin, int CoP, int taps, int precision = 0);
+int cp_launch_conv_dgrad_pack(hipStream_t s, const float* w, float* wB, int Cin, int Cout, int CoP, int taps, int precision = 0);
+int cp_launch_conv_dgrad_s1(hipStream_t s, const ConvBwdArgs& a, const float* gs, int CoP, const float* wB, const float* res,
+                            const unsigned* gs_amax = nullptr);  // gs_amax given: wB is the f16x3 pack
+// conv_bwd16.hip: the pieces of the f16x3 mode.  |max| of x[0..n) into a zeroed slot; dst[i] = split(src[i] * 2^e of the slot);
+// the slab kernel of the weight gradient; the data gradient's packed weight (stride 1 or 2), the stride-1 launch's eligibility
+// (host arithmetic: cp_conv16_supported on the launch it would make) and the two launches.
+int cp_launch_absmax32(const float* x, size_t n, unsigned* slot, hipStream_t s);
+int cp_launch_split16(const float* src, uint32_t* dst, size_t n, const unsigned* slot, hipStream_t s);
+int cp_launch_conv_wgrad16_slabs(hipStream_t s, const ConvBwdArgs& a, const ConvWgrad16& h, int CoP, const ConvWgradPlan& P, float* slab);
+size_t cp_conv_dgrad16_pack_bytes(int Cin, int CoP, int taps, int stride);
+int cp_launch_conv_dgrad16_pack(hipStream_t s, const float* w, void* wB, int Cin, int Cout, int CoP, int taps, int stride);
+bool cp_conv_dgrad16_s1_supported(int B, int H, int W, int Cin, int CoP, int K);
+int cp_launch_conv_dgrad16_s1(hipStream_t s, const ConvBwdArgs& a, const float* gs, int CoP, const void* wB, const float* res,
+                              const unsigned* gs_amax);
+int cp_launch_conv_dgrad16_s2(hipStream_t s, const ConvBwdArgs& a, const uint32_t* gs16, int CoP, const void* wB, const unsigned* gs_amax);
 // The low-channel 3x3 path (conv_bwd_lowc.hip; cp_conv_backward_lowc geometries, CoP == Cout).  A workgroup walks a contiguous
 // run of `tiles_per_wg` tiles; the weight gradient's workgroups are its slabs [Cout][9 x 16], which the caller sums
 // (wgrad_reduce_kernel's layout and order).

@@ -1,5 +1,5 @@
 // The stand-alone operators of the C ABI (include/centerpose_hip.h): single layers on caller tensors, outside any cp_model
-// -- cp_conv2d_nhwc / cp_conv2d_backward_nhwc, cp_batchnorm_forward_nhwc / _backward_nhwc, cp_conv_transpose2d_nhwc,
+// -- cp_conv2d_nhwc / cp_conv2d_backward_nhwc / cp_conv2d_backward_prec_nhwc, cp_batchnorm_forward_nhwc / _backward_nhwc, cp_conv_transpose2d_nhwc,
 // cp_conv_transpose2d_dw_nhwc / cp_conv_transpose2d_backward_nhwc, cp_dcnv2_forward / cp_dcnv2_backward / cp_dcnv2_backward_det, cp_pose_heads_forward / _backward,
 // cp_maxpool2d_forward_nhwc / _backward_nhwc, cp_upsample2_add_nhwc / cp_upsample2_add_backward_nhwc (large_hourglass.py:95-112),
 // cp_conv2d_stem_backward / cp_conv2d_stem_wide_backward, cp_groupnorm_forward_nhwc / _backward_nhwc,
@@ -486,6 +486,43 @@ int cp_conv2d_backward_nhwc(cp_stream_t stream, const float* x, const float* w, 
         return fail(CP_ERR_INVALID, "conv2d_backward: workspace too small");
     const ConvBwdArgs a{x, w, y_or_null, grad_out, grad_x_or_null, grad_w, grad_bias_or_null, B, H, W, Cin, Cout, KH, KW, stride, pad};
     const int rc = cp_launch_conv_backward((hipStream_t)stream, a, workspace);
+    return rc == CP_OK ? CP_OK : fail(rc, "conv2d_backward: kernel launch failed");
+}
+
+// The precision-aware forms: CP_PREC_F32 is the calls above; CP_PREC_F16X3 runs the MFMA path's contractions on conv_bwd16.hip
+static const char* conv_bwd_prec_error(int precision) {
+    return precision == CP_PREC_F32 || precision == CP_PREC_F16X3 ? nullptr
+                                                                  : "conv2d_backward: unknown precision (CP_PREC_F32 or CP_PREC_F16X3)";
+}
+
+int cp_conv2d_backward_prec_mask(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int precision) {
+    if (const char* e = conv_bwd_shape_error(B, H, W, Cin, Cout, KH, KW, stride, pad)) return fail(CP_ERR_INVALID, e);
+    if (const char* e = conv_bwd_prec_error(precision)) return fail(CP_ERR_INVALID, e);
+    return cp_conv_backward_prec_mask(B, H, W, Cin, Cout, KH, KW, stride, pad, precision);
+}
+
+size_t cp_conv2d_backward_prec_workspace_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
+                                               int need_grad_x, int precision) {
+    const char* e = conv_bwd_shape_error(B, H, W, Cin, Cout, KH, KW, stride, pad);
+    if (!e) e = conv_bwd_prec_error(precision);
+    if (e) {
+        fail(CP_ERR_INVALID, e);
+        return 0;
+    }
+    return cp_conv_backward_ws_bytes(B, H, W, Cin, Cout, KH, KW, stride, pad, need_grad_x, precision);
+}
+
+int cp_conv2d_backward_prec_nhwc(cp_stream_t stream, const float* x, const float* w, const float* y_or_null, const float* grad_out,
+                                 float* grad_x_or_null, float* grad_w, float* grad_bias_or_null, int B, int H, int W, int Cin,
+                                 int Cout, int KH, int KW, int stride, int pad, int precision, void* workspace,
+                                 size_t workspace_bytes) {
+    if (const char* e = conv_bwd_shape_error(B, H, W, Cin, Cout, KH, KW, stride, pad)) return fail(CP_ERR_INVALID, e);
+    if (const char* e = conv_bwd_prec_error(precision)) return fail(CP_ERR_INVALID, e);
+    if (!x || !w || !grad_out || !grad_w || !workspace) return fail(CP_ERR_INVALID, "conv2d_backward: null argument");
+    if (workspace_bytes < cp_conv_backward_ws_bytes(B, H, W, Cin, Cout, KH, KW, stride, pad, grad_x_or_null != nullptr, precision))
+        return fail(CP_ERR_INVALID, "conv2d_backward: workspace too small");
+    const ConvBwdArgs a{x, w, y_or_null, grad_out, grad_x_or_null, grad_w, grad_bias_or_null, B, H, W, Cin, Cout, KH, KW, stride, pad};
+    const int rc = cp_launch_conv_backward((hipStream_t)stream, a, workspace, precision);
     return rc == CP_OK ? CP_OK : fail(rc, "conv2d_backward: kernel launch failed");
 }
 

@@ -204,11 +204,29 @@ def conv2d_nhwc(x, w, scale=None, shift=None, residual=None, stride=1, pad=0, ac
     return out
 
 
+def _bwd_precision(name):
+    if name not in _abi.PRECISIONS:
+        raise ValueError("conv2d_backward: precision must be one of %s, got %r" % (sorted(_abi.PRECISIONS), name))
+    return _abi.PRECISIONS[name]
+
+
 def conv2d_backward(x, w, grad_out, stride=1, pad=0, y=None, need_x_grad=True, need_bias_grad=True):
     """Gradients of ``conv2d_nhwc(x, w, shift=bias)`` (cp_conv2d_backward_nhwc): x [B,H,W,Cin] NHWC, w [Cout,Cin,KH,KW],
     grad_out [B,Ho,Wo,Cout] NHWC -> (grad_x [B,H,W,Cin] | None, grad_w [Cout,Cin,KH,KW], grad_bias [Cout] | None).  ``y``: the
-    activated forward output when the layer ended in a ReLU (grad_out is gated by y > 0).  Float32 and bitwise reproducible."""
+    activated forward output when the layer ended in a ReLU (grad_out is gated by y > 0).  Float32 and bitwise reproducible.
+    ``ops.conv2d_backward_prec`` is the same operator with a ``precision`` argument."""
+    return conv2d_backward_prec(x, w, grad_out, stride=stride, pad=pad, y=y, need_x_grad=need_x_grad, need_bias_grad=need_bias_grad,
+                                precision="f32")
+
+
+def conv2d_backward_prec(x, w, grad_out, stride=1, pad=0, y=None, need_x_grad=True, need_bias_grad=True, precision="f32"):
+    """``conv2d_backward`` with the arithmetic of its matrix products as an argument.  ``precision``: "f32" (exact float32:
+    cp_conv2d_backward_nhwc, the bits of ``conv2d_backward``) or "f16x3" (cp_conv2d_backward_prec_nhwc: the MFMA path's weight
+    and data gradient on split-binary16 matrix instructions, float32-class accuracy and bitwise reproducible; the other paths
+    stay float32 -- ``conv2d_backward_precision_mask`` tells which).  Reached as ``hip.ops.conv2d_backward_prec``: the ``hip``
+    package's own list of names and the signature of ``hip.conv2d_backward`` are kept as they were."""
     L = _abi.lib()
+    prec = _bwd_precision(precision)
     x, w, grad_out, y = _abi._dev(x), _abi._dev(w), _abi._dev(grad_out), _abi._dev_opt(y)
     if x.dim() != 4 or w.dim() != 4 or w.shape[1] != x.shape[3]:
         raise RuntimeError("conv2d_backward: x must be [B,H,W,Cin] and w [Cout,Cin,KH,KW], got %s and %s"
@@ -216,17 +234,35 @@ def conv2d_backward(x, w, grad_out, stride=1, pad=0, y=None, need_x_grad=True, n
     B, H, W, Cin = x.shape
     Cout, _, KH, KW = w.shape
     stride, pad = int(stride), int(pad)
-    ws = _abi._workspace(L.cp_conv2d_backward_workspace_bytes(B, H, W, Cin, Cout, KH, KW, stride, pad, int(bool(need_x_grad))),
-                         x.device, "conv2d_backward")
+    if prec:
+        nbytes = L.cp_conv2d_backward_prec_workspace_bytes(B, H, W, Cin, Cout, KH, KW, stride, pad, int(bool(need_x_grad)), prec)
+    else:
+        nbytes = L.cp_conv2d_backward_workspace_bytes(B, H, W, Cin, Cout, KH, KW, stride, pad, int(bool(need_x_grad)))
+    ws = _abi._workspace(nbytes, x.device, "conv2d_backward")
     Ho, Wo = _conv_out(H, W, KH, KW, stride, stride, pad, pad)
     _abi._check_shapes("conv2d_backward", (("grad_out", grad_out, (B, Ho, Wo, Cout)), ("y", y, (B, Ho, Wo, Cout))))
     grad_x = torch.empty_like(x) if need_x_grad else None
     grad_w = torch.empty_like(w)
     grad_b = torch.empty(Cout, device=x.device, dtype=torch.float32) if need_bias_grad else None
-    rc = L.cp_conv2d_backward_nhwc(_abi._stream(), *_abi._ptrs(x, w, y, grad_out, grad_x, grad_w, grad_b),
-                                   B, H, W, Cin, Cout, KH, KW, stride, pad, _abi._ptr(ws), ws.numel())
-    _abi._check(rc, "cp_conv2d_backward_nhwc")
+    if prec:
+        rc = L.cp_conv2d_backward_prec_nhwc(_abi._stream(), *_abi._ptrs(x, w, y, grad_out, grad_x, grad_w, grad_b),
+                                            B, H, W, Cin, Cout, KH, KW, stride, pad, prec, _abi._ptr(ws), ws.numel())
+    else:
+        rc = L.cp_conv2d_backward_nhwc(_abi._stream(), *_abi._ptrs(x, w, y, grad_out, grad_x, grad_w, grad_b),
+                                       B, H, W, Cin, Cout, KH, KW, stride, pad, _abi._ptr(ws), ws.numel())
+    _abi._check(rc, "cp_conv2d_backward_prec_nhwc" if prec else "cp_conv2d_backward_nhwc")
     return grad_x, grad_w, grad_b
+
+
+def conv2d_backward_precision_mask(B, H, W, Cin, Cout, KH, KW, stride=1, pad=0, precision="f16x3"):
+    """What ``conv2d_backward_prec(..., precision=precision)`` runs in f16x3 for a geometry (cp_conv2d_backward_prec_mask; host
+    arithmetic): bit 0 = the weight gradient, bit 1 = the data gradient.  0 for "f32" and for the low-channel and generic paths.
+    Raises RuntimeError for a geometry the operator refuses."""
+    rc = _abi.lib().cp_conv2d_backward_prec_mask(int(B), int(H), int(W), int(Cin), int(Cout), int(KH), int(KW), int(stride), int(pad),
+                                                 _bwd_precision(precision))
+    if rc < 0:
+        _abi._refuse("conv2d_backward_precision_mask")
+    return rc
 
 
 CONV_BWD_GENERIC, CONV_BWD_MFMA, CONV_BWD_LOWC = 0, 1, 2   # include/centerpose_hip.h: CP_CONV_BWD_*

@@ -349,8 +349,20 @@ int cp_conv2d_nhwc(cp_stream_t stream, const float* x, const float* w, const flo
  * not computed and not touched.  y (the ACTIVATED forward output, [B,Ho,Wo,Cout]) or NULL: when given, the layer was
  * relu(conv + bias) and grad_out is gated by y > 0 wherever it is read.  BatchNorm scale / shift and residual inputs of the
  * forward are not part of this operator: callers compose them.
- * Arithmetic is float32 whatever cp_set_default_precision says; every sum has a fixed order and there are no atomics, so
- * all outputs are bitwise reproducible call to call.
+ * Arithmetic is float32 whatever cp_set_default_precision says (that switch governs the forward only); every sum has a
+ * fixed order and there are no atomics, so all outputs are bitwise reproducible call to call.
+ * cp_conv2d_backward_prec_* are the same three calls with a `precision` argument (CP_PREC_*).  CP_PREC_F32 IS the calls
+ * without it: same kernels, same bits, same workspace size.  CP_PREC_F16X3 runs the two contractions of the MFMA path --
+ * the weight gradient and the data gradient, both strides -- on v_mfma_f32_32x32x16_f16: grad_out (gated and padded), x
+ * and w are pre-scaled by exact powers of two (grad_out and x per tensor from one |max| pass each, w per input channel),
+ * split into two binary16 numbers hi + lo, and every product block is hi*hi + hi*lo + lo*hi with float32 accumulation;
+ * the scales are undone by exact power-of-two multiplies.  The relative error of a product is below 2^-20, so accuracy
+ * stays float32-class; the gate, the pad lanes and grad_bias are float32, every sum still has a fixed order and the
+ * gradients are bitwise reproducible call to call; results are equivariant, bit for bit, under power-of-two scalings of
+ * x, w and grad_out.  The low-channel and the generic path are float32 in either mode.  The f16x3 workspace is larger (the
+ * split copies of grad_out and x).  cp_conv2d_backward_prec_mask (host arithmetic) reports what a geometry gets: bit 0 =
+ * the weight gradient, bit 1 = the data gradient runs in f16x3; 0 for CP_PREC_F32 and off the MFMA path; CP_ERR_INVALID
+ * (with a text) for a refused geometry or an unknown precision, which the other two calls refuse likewise before any launch.
  * MFMA path (v_mfma_f32_32x32x2_f32): KH == KW in {1, 3}, stride in {1, 2}, pad == KH / 2, Cin % 32 == 0, any H, W >= 1 and
  * any Cout (grad_out is staged once into the workspace, zero-padded to a multiple of 32 channels: 27 is the case that
  * matters).  Low-channel path (v_mfma_f32_16x16x4_f32): KH == KW == 3, pad == 1, stride in {1, 2}, Cin == 16, Cout in
@@ -373,6 +385,14 @@ int cp_conv2d_backward_nhwc(cp_stream_t stream, const float* x, const float* w, 
                             const float* grad_out, float* grad_x_or_null, float* grad_w, float* grad_bias_or_null, int B,
                             int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, void* workspace,
                             size_t workspace_bytes);
+size_t cp_conv2d_backward_prec_workspace_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
+                                               int need_grad_x, int precision);
+int cp_conv2d_backward_prec_nhwc(cp_stream_t stream, const float* x, const float* w, const float* y_or_null,
+                                 const float* grad_out, float* grad_x_or_null, float* grad_w, float* grad_bias_or_null,
+                                 int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
+                                 int precision, void* workspace, size_t workspace_bytes);
+int cp_conv2d_backward_prec_mask(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
+                                 int precision);
 
 /* ------------------------------------------------------------------------------------------
  * BatchNorm2d for training, fused with the residual add and the ReLU — replaces the nn.BatchNorm2d(momentum=0.1) ->

@@ -55,6 +55,9 @@ def main():
     ap.add_argument("--skip-step", action="store_true", help="only the stem and pool measurements")
     ap.add_argument("--only-step", action="store_true", help="only the whole step")
     ap.add_argument("--deterministic", action="store_true", help="time the step under hip.set_deterministic(True) as well")
+    ap.add_argument("--backward-precision", default="f32", choices=["f32", "f16x3", "both"],
+                    help="of the step's conv.Conv2d layers (conv.set_backward_precision); both: the two modes alternating, "
+                         "the traced step in f16x3")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -163,23 +166,35 @@ def main():
             z = net(x)[0]
             sum((z[h] * lin[h]).sum() for h in z).backward()
 
+        precs = ["f32", "f16x3"] if a.backward_precision == "both" else [a.backward_precision]
         modes = [False, True] if a.deterministic else [False]
+        modes += ["f16x3"] if len(precs) == 2 else []   # (the deterministic step is timed in the first precision)
+
+        def enter(m):
+            hip.set_deterministic(m is True)
+            conv.set_backward_precision(net, "f16x3" if m == "f16x3" else precs[0])
+
         for m in modes:
-            hip.set_deterministic(m)
+            enter(m)
             step()
             step()
         rounds = {m: [] for m in modes}
         for _ in range(a.rounds):
             for m in modes:
-                hip.set_deterministic(m)
+                enter(m)
                 rounds[m].append(timed(step))
         total = rounds[False]
-        det = {}
-        if a.deterministic:  # the traced step below stays in the deterministic mode
-            det = {"deterministic_step_ms": round(statistics.median(rounds[True]), 2),
-                   "deterministic_step_ms_rounds": [round(v, 2) for v in rounds[True]],
-                   "deterministic_over_default": round(statistics.median(rounds[True]) / statistics.median(total), 3),
-                   "family_split_of": "deterministic step"}
+        det = {"backward_precision": a.backward_precision, "traced_backward_precision": precs[-1]}
+        if len(precs) == 2:
+            det.update({"f16x3_step_ms": round(statistics.median(rounds["f16x3"]), 2),
+                        "f16x3_step_ms_rounds": [round(v, 2) for v in rounds["f16x3"]],
+                        "f16x3_over_f32": round(statistics.median(rounds["f16x3"]) / statistics.median(total), 3)})
+        enter(True if a.deterministic else modes[-1])  # the traced step below: the deterministic mode if asked for, else the last precision
+        if a.deterministic:
+            det.update({"deterministic_step_ms": round(statistics.median(rounds[True]), 2),
+                        "deterministic_step_ms_rounds": [round(v, 2) for v in rounds[True]],
+                        "deterministic_over_default": round(statistics.median(rounds[True]) / statistics.median(total), 3),
+                        "family_split_of": "deterministic step", "traced_backward_precision": precs[0]})
         # one more step with every operator call bracketed by events
         events, originals = [], {}
 

@@ -54,6 +54,9 @@ def main():
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--skip-step", action="store_true", help="only the merge and stem measurements")
+    ap.add_argument("--backward-precision", default="f32", choices=["f32", "f16x3", "both"],
+                    help="of the step's conv.Conv2d layers (conv.set_backward_precision); both: the two modes alternating "
+                         "(library = f32, library_f16x3), the traced step in f16x3")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -209,9 +212,24 @@ def main():
             zs = ref.forward(tsd, xc, heads, True)
             sum((z[h] * lin[k][h]).sum() for k, z in enumerate(zs) for h in z).backward()
 
-        r = compare(OrderedDict([("library", step), ("torch", torch_step)]))
+        modes = ["f32", "f16x3"] if a.backward_precision == "both" else [a.backward_precision]
+        current = [None]
+
+        def step_in(mode):
+            def run_step():
+                if current[0] != mode:
+                    current[0] = mode
+                    conv.set_backward_precision(net, mode)
+                step()
+            return run_step
+
+        routes = OrderedDict([("library", step_in(modes[0]))])
+        if len(modes) == 2:
+            routes["library_f16x3"] = step_in(modes[1])
+        routes["torch"] = torch_step
+        r = compare(routes)
         del tsd, leaves
-        step()
+        step_in(modes[-1])()
         torch.cuda.synchronize()
         torch.cuda.reset_peak_memory_stats()
         # one more step with every operator call bracketed by events (no empty_cache() ahead of it: the allocator's blocks stay,
@@ -251,7 +269,8 @@ def main():
             calls[fam] = calls.get(fam, 0) + 1
         traced = e0.elapsed_time(e1)
         split["torch glue and launch gaps"] = traced - sum(split.values())
-        report({"what": "step", "arch": "hourglass", "B": B, "HxW": S, "images_per_s": round(B / r["library"][0] * 1e3, 1),
+        report({"what": "step", "arch": "hourglass", "backward_precision": a.backward_precision, "traced_backward_precision": modes[-1],
+                "B": B, "HxW": S, "images_per_s": round(B / r["library"][0] * 1e3, 1),
                 "traced_step_ms": round(traced, 2), "family_ms": {k: round(v, 2) for k, v in split.items()}, "family_calls": calls,
                 "peak_memory_gib": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)}, r)
     if a.out:
