@@ -471,11 +471,16 @@ struct PoseHeadsArgs {
     int B, H, W, Cin, hid;
 };
 int cp_pose_heads_chunk(int B, int H, int W, int hid);  // images whose hidden layer is materialised at a time
-size_t cp_pose_heads_backward_ws_bytes(int B, int H, int W, int Cin, int hid, int max_classes);
+// `precision` (CP_PREC_*): CP_PREC_F16X3 runs the three wide contractions of a head -- the recomputed hidden layer, the 3x3
+// weight gradient and the data gradient -- on the split-binary16 kernels (igemm16.hip's, conv_bwd16.hip's); the gate, grad_w1
+// and the bias gradients are float32 in either mode.  cp_pose_heads_backward_mask: bit 0 = the weight gradient, bit 1 = the data
+// gradient, bit 2 = the hidden layer runs in f16x3 (0 for CP_PREC_F32).
+size_t cp_pose_heads_backward_ws_bytes(int B, int H, int W, int Cin, int hid, int max_classes, int precision = 0);
+int cp_pose_heads_backward_mask(int B, int H, int W, int Cin, int hid, int precision);
 // grad_out[i] NCHW or nullptr (zero parameter gradients, no contribution); grad_feat NHWC or nullptr (not computed)
 int cp_launch_pose_heads_backward(hipStream_t s, const PoseHeadsArgs& a, const float* const* grad_out, float* const* grad_w0,
                                   float* const* grad_b0, float* const* grad_w1, float* const* grad_b1, float* grad_feat,
-                                  void* ws);
+                                  void* ws, int precision = 0);
 
 // ---- Conv2d backward (conv_bwd.hip): gradients of out = conv2d(x, w) + bias on the forward's NHWC layouts, float32 ----
 struct ConvBwdArgs {

@@ -264,7 +264,7 @@ inline int timed(cp_model* m, hipStream_t s, D&& describe, F&& launch) {
 }
 
 // ConvW of a float32 weight as cp_launch_pack_weight lays it out in a caller's buffer: wp [Kpad][CoutPad], K = KH KW Cin rounded
-// up to the kernels' K step and Cout to the launch's N tile; no f16x3 operands (pack_f16x3 of ops.hip adds them)
+// up to the kernels' K step and Cout to the launch's N tile; no f16x3 operands (cp_pack_f16x3 of ops.hip adds them)
 inline ConvW conv_w_f32(float* wp, const float* scale, const float* shift, int Cin, int Cout, int KH, int KW) {
     ConvW w;
     w.wp = wp;

@@ -49,3 +49,29 @@ inline ConvParams grad_conv_params(int B, int H, int W, const float* src, int Ci
     p.ldo = Cout;
     return p;
 }
+
+// Regions of a [Cout,Cin,kh,kw] weight packed for the f16x3 kernels: two binary16 copies [cpad][kpad], the per-channel weight
+// scales (2^e, 2^-e, scale * 2^-e), the input's |max| slot block, the fragment-ordered copies of the binary16 weights
+constexpr size_t cp_amax_slot_bytes = (size_t)CP_AMAX_SUB * CP_AMAX_STRIDE * sizeof(unsigned);  // one |max| slot block
+struct Pack16 {
+    void *hi, *lo;
+    float *wfwd, *winv, *sc16;
+    unsigned* slot;
+    void *fhi, *flo;
+};
+inline Pack16 carve_pack16(Carve& c, size_t kpad, size_t cpad) {
+    Pack16 r;
+    r.hi = c.take<void>(kpad * cpad * 2);
+    r.lo = c.take<void>(kpad * cpad * 2);
+    r.wfwd = c.take<float>(cpad * sizeof(float));
+    r.winv = c.take<float>(cpad * sizeof(float));
+    r.sc16 = c.take<float>(cpad * sizeof(float));
+    r.slot = c.take<unsigned>(cp_amax_slot_bytes);
+    r.fhi = c.take<void>(kpad * cpad * 2);
+    r.flo = c.take<void>(kpad * cpad * 2);
+    return r;
+}
+// ops.hip: the f16x3 operands of a forward convolution from its PyTorch-layout weight (what cp_conv2d_nhwc, cp_dcnv2_forward and
+// cp_pose_heads_forward launch on)
+int cp_pack_f16x3(const Pack16& r, const float* wt, const float* scale, int taps, cp_engine::ConvW& w, const float* x, size_t nx,
+                  const float* om, size_t px, hipStream_t s);

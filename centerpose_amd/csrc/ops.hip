@@ -1,6 +1,6 @@
 // The stand-alone operators of the C ABI (include/centerpose_hip.h): single layers on caller tensors, outside any cp_model
 // -- cp_conv2d_nhwc / cp_conv2d_backward_nhwc / cp_conv2d_backward_prec_nhwc, cp_batchnorm_forward_nhwc / _backward_nhwc, cp_conv_transpose2d_nhwc,
-// cp_conv_transpose2d_dw_nhwc / cp_conv_transpose2d_backward_nhwc, cp_dcnv2_forward / cp_dcnv2_backward / cp_dcnv2_backward_det, cp_pose_heads_forward / _backward,
+// cp_conv_transpose2d_dw_nhwc / cp_conv_transpose2d_backward_nhwc, cp_dcnv2_forward / cp_dcnv2_backward / cp_dcnv2_backward_det, cp_pose_heads_forward / _backward / _backward_prec,
 // cp_maxpool2d_forward_nhwc / _backward_nhwc, cp_upsample2_add_nhwc / cp_upsample2_add_backward_nhwc (large_hourglass.py:95-112),
 // cp_conv2d_stem_backward / cp_conv2d_stem_wide_backward, cp_groupnorm_forward_nhwc / _backward_nhwc,
 // cp_gru_gate_forward / _backward, cp_adam_table_bytes / _table_build / _step, cp_grad_flat_elems / _flat_offsets / _pack_table_bytes / _pack_table_build / _pack.
@@ -12,28 +12,7 @@ using namespace cp_engine;
 
 namespace {
 
-constexpr size_t kSlotBytes = (size_t)CP_AMAX_SUB * CP_AMAX_STRIDE * sizeof(unsigned);  // one |max| slot block
-
-// Regions of a [Cout,Cin,kh,kw] weight packed for the f16x3 kernels: two binary16 copies [cpad][kpad], the per-channel weight
-// scales (2^e, 2^-e, scale * 2^-e), the input's |max| slot block, the fragment-ordered copies of the binary16 weights
-struct Pack16 {
-    void *hi, *lo;
-    float *wfwd, *winv, *sc16;
-    unsigned* slot;
-    void *fhi, *flo;
-};
-Pack16 carve_pack16(Carve& c, size_t kpad, size_t cpad) {
-    Pack16 r;
-    r.hi = c.take<void>(kpad * cpad * 2);
-    r.lo = c.take<void>(kpad * cpad * 2);
-    r.wfwd = c.take<float>(cpad * sizeof(float));
-    r.winv = c.take<float>(cpad * sizeof(float));
-    r.sc16 = c.take<float>(cpad * sizeof(float));
-    r.slot = c.take<unsigned>(kSlotBytes);
-    r.fhi = c.take<void>(kpad * cpad * 2);
-    r.flo = c.take<void>(kpad * cpad * 2);
-    return r;
-}
+constexpr size_t kSlotBytes = cp_amax_slot_bytes;  // one |max| slot block
 
 __global__ void dcn_offmask_pack_kernel(const float* __restrict__ offset, const float* __restrict__ mask,
                                         float* __restrict__ om, int B, int HW) {
@@ -71,38 +50,6 @@ __global__ void dcn_act_bound_kernel(unsigned* __restrict__ x_slot, const unsign
     x_slot[0] = max(x_slot[0], __float_as_uint(bound));
 }
 
-// Packs the PyTorch-layout weight `wt` ([w.Cout][w.Cin][taps]) for the f16x3 path into the carved regions `r` and measures the
-// input: range-safe operands -- per-channel power-of-two weight scale (folded into scale16 with `scale`), per-tensor activation
-// scale from one |max| pass over x[0..nx).  `om` (DCN: the packed offset / mask records of `px` pixels): the mask's |max| goes to
-// slot 1 of the (zeroed) slot block and is folded into x's bound.  The fragment-ordered copies exist when the shape allows
-// them.  On CP_OK the f16x3 fields of `w` describe the packed operands.
-int pack_f16x3(const Pack16& r, const float* wt, const float* scale, int taps, ConvW& w, const float* x, size_t nx,
-               const float* om, size_t px, hipStream_t s) {
-    if (hipMemsetAsync(r.hi, 0, (char*)r.wfwd - (char*)r.hi, s) != hipSuccess) return CP_ERR_LAUNCH;
-    if (hipMemsetAsync(r.wfwd, 0, (char*)r.fhi - (char*)r.wfwd, s) != hipSuccess) return CP_ERR_LAUNCH;
-    w.w16_hi = r.hi;
-    w.w16_lo = r.lo;
-    w.Kpad16 = w.K;
-    w.scale16 = r.sc16;
-    int rc = cp_launch_weight_scale(wt, w.Cout, w.Cin * taps, r.wfwd, r.winv, s);
-    if (rc == CP_OK) rc = cp_launch_pack_weight16(wt, r.hi, r.lo, w.Cout, w.Cin, taps, w.Kpad16, 0, r.wfwd, s);
-    if (rc == CP_OK) rc = cp_launch_scale16(scale, r.winv, r.sc16, w.Cout, s);
-    if (rc == CP_OK) rc = cp_launch_absmax(x, nx, r.slot, s);
-    if (rc == CP_OK && om) {
-        const size_t g = std::min<size_t>((px * 9 + 255) / 256, 2048);
-        hipLaunchKernelGGL(dcn_mask_amax_kernel, dim3((unsigned)g), dim3(256), 0, s, om, px, r.slot + 1);
-        hipLaunchKernelGGL(dcn_act_bound_kernel, dim3(1), dim3(64), 0, s, r.slot, (const unsigned*)(r.slot + 1));
-        if (hipGetLastError() != hipSuccess) rc = CP_ERR_LAUNCH;
-    }
-    if (rc == CP_OK && w.CoutPad % 32 == 0 && w.Kpad16 % 16 == 0) {
-        rc = cp_launch_frag16_repack(r.hi, r.fhi, w.CoutPad, w.Kpad16, s);
-        if (rc == CP_OK) rc = cp_launch_frag16_repack(r.lo, r.flo, w.CoutPad, w.Kpad16, s);
-        w.w16f_hi = r.fhi;
-        w.w16f_lo = r.flo;
-    }
-    return rc;
-}
-
 // One convolution's operands in an operator's workspace.  The float32 ones back to back, so that one memset zeroes all `bytes`
 // of them: the packed weight [kpad][cpad] and the epilogue vectors, cpad floats each because the kernels read them up to the
 // N tile (scale: only where the operator takes one).  Then the f16x3 regions, where the operator has that form.
@@ -125,7 +72,7 @@ ConvOps carve_conv_ops(Carve& c, size_t kpad, size_t cpad, bool with_scale, bool
 // What cp_conv2d_nhwc, cp_dcnv2_forward and each layer of cp_pose_heads_forward do with a PyTorch-layout weight `w`
 // ([Cout][Cin][KH][KW]) before they launch: zero the regions `r`, pack the weight, copy the Cout floats of each given
 // epilogue vector into its zero-padded region and, with `f16x3` (the caller chose those kernels), pack their operands from
-// the same weight and measure the input (pack_f16x3: x, nx, om, px).  `cw` describes the staged operands.
+// the same weight and measure the input (cp_pack_f16x3: x, nx, om, px).  `cw` describes the staged operands.
 int stage_conv(ConvW& cw, const ConvOps& r, bool f16x3, const float* w, const float* scale, const float* shift, int Cin,
                int Cout, int KH, int KW, const float* x, size_t nx, const float* om, size_t px, hipStream_t s) {
     cw = conv_w_f32(r.wp, scale ? r.scale : nullptr, shift ? r.shift : nullptr, Cin, Cout, KH, KW);
@@ -135,7 +82,7 @@ int stage_conv(ConvW& cw, const ConvOps& r, bool f16x3, const float* w, const fl
     if ((scale && hipMemcpyAsync(r.scale, scale, (size_t)Cout * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) ||
         (shift && hipMemcpyAsync(r.shift, shift, (size_t)Cout * 4, hipMemcpyDeviceToDevice, s) != hipSuccess))
         return CP_ERR_LAUNCH;
-    return f16x3 ? pack_f16x3(r.f16, w, scale, KH * KW, cw, x, nx, om, px, s) : CP_OK;
+    return f16x3 ? cp_pack_f16x3(r.f16, w, scale, KH * KW, cw, x, nx, om, px, s) : CP_OK;
 }
 
 // Launches `p`, built from stage_conv's `cw`: on the f16x3 kernels with `f16x3` where they take the launch, else in float32
@@ -301,6 +248,39 @@ HeadsFwdWs heads_fwd_carve(Carve& c, int B, int H, int W, int Cin, int hid) {
 
 }  // namespace
 
+// Packs the PyTorch-layout weight `wt` ([w.Cout][w.Cin][taps]) for the f16x3 path into the carved regions `r` and measures the
+// input: range-safe operands -- per-channel power-of-two weight scale (folded into scale16 with `scale`), per-tensor activation
+// scale from one |max| pass over x[0..nx) (x == nullptr: the caller measures the input into a slot block of its own and r.slot
+// stays zero).  `om` (DCN: the packed offset / mask records of `px` pixels): the mask's |max| goes to slot 1 of the (zeroed) slot
+// block and is folded into x's bound.  The fragment-ordered copies exist when the shape allows them.  On CP_OK the f16x3
+// fields of `w` describe the packed operands.  Declared in op_common.h: heads_bwd.hip packs its recomputed hidden layer with it.
+int cp_pack_f16x3(const Pack16& r, const float* wt, const float* scale, int taps, ConvW& w, const float* x, size_t nx,
+                  const float* om, size_t px, hipStream_t s) {
+    if (hipMemsetAsync(r.hi, 0, (char*)r.wfwd - (char*)r.hi, s) != hipSuccess) return CP_ERR_LAUNCH;
+    if (hipMemsetAsync(r.wfwd, 0, (char*)r.fhi - (char*)r.wfwd, s) != hipSuccess) return CP_ERR_LAUNCH;
+    w.w16_hi = r.hi;
+    w.w16_lo = r.lo;
+    w.Kpad16 = w.K;
+    w.scale16 = r.sc16;
+    int rc = cp_launch_weight_scale(wt, w.Cout, w.Cin * taps, r.wfwd, r.winv, s);
+    if (rc == CP_OK) rc = cp_launch_pack_weight16(wt, r.hi, r.lo, w.Cout, w.Cin, taps, w.Kpad16, 0, r.wfwd, s);
+    if (rc == CP_OK) rc = cp_launch_scale16(scale, r.winv, r.sc16, w.Cout, s);
+    if (rc == CP_OK && x) rc = cp_launch_absmax(x, nx, r.slot, s);
+    if (rc == CP_OK && om) {
+        const size_t g = std::min<size_t>((px * 9 + 255) / 256, 2048);
+        hipLaunchKernelGGL(dcn_mask_amax_kernel, dim3((unsigned)g), dim3(256), 0, s, om, px, r.slot + 1);
+        hipLaunchKernelGGL(dcn_act_bound_kernel, dim3(1), dim3(64), 0, s, r.slot, (const unsigned*)(r.slot + 1));
+        if (hipGetLastError() != hipSuccess) rc = CP_ERR_LAUNCH;
+    }
+    if (rc == CP_OK && w.CoutPad % 32 == 0 && w.Kpad16 % 16 == 0) {
+        rc = cp_launch_frag16_repack(r.hi, r.fhi, w.CoutPad, w.Kpad16, s);
+        if (rc == CP_OK) rc = cp_launch_frag16_repack(r.lo, r.flo, w.CoutPad, w.Kpad16, s);
+        w.w16f_hi = r.fhi;
+        w.w16f_lo = r.flo;
+    }
+    return rc;
+}
+
 extern "C" {
 
 int cp_pose_heads_chunk_images(int B, int H, int W, int hid) {
@@ -386,6 +366,53 @@ int cp_pose_heads_backward(cp_stream_t stream, const float* feat, int n, const f
     const PoseHeadsArgs a{feat, n, w0, b0, w1, b1, classes, B, H, W, Cin, hid};
     const int rc = cp_launch_pose_heads_backward((hipStream_t)stream, a, grad_out, grad_w0, grad_b0, grad_w1, grad_b1, grad_feat,
                                                  workspace);
+    return rc == CP_OK ? CP_OK : fail(rc, "pose_heads_backward: kernel launch failed");
+}
+
+// The precision-aware forms: CP_PREC_F32 is the calls above; CP_PREC_F16X3 runs the three wide contractions of a head on the
+// split-binary16 kernels (heads_bwd.hip)
+static const char* heads_bwd_prec_error(int precision) {
+    return precision == CP_PREC_F32 || precision == CP_PREC_F16X3 ? nullptr
+                                                                  : "pose_heads_backward: unknown precision (CP_PREC_F32 or CP_PREC_F16X3)";
+}
+
+int cp_pose_heads_backward_prec_mask(int B, int H, int W, int Cin, int hid, int precision) {
+    const int one = 1;
+    int cmax = 0;
+    if (const char* e = heads_shape_error(B, H, W, Cin, hid, 1, &one, &cmax)) return fail(CP_ERR_INVALID, e);
+    if (const char* e = heads_bwd_prec_error(precision)) return fail(CP_ERR_INVALID, e);
+    return cp_pose_heads_backward_mask(B, H, W, Cin, hid, precision);
+}
+
+size_t cp_pose_heads_backward_prec_workspace_bytes(int B, int H, int W, int Cin, int hid, int n, const int* classes, int precision) {
+    int cmax = 0;
+    const char* e = heads_shape_error(B, H, W, Cin, hid, n, classes, &cmax);
+    if (!e) e = heads_bwd_prec_error(precision);
+    if (e) {
+        fail(CP_ERR_INVALID, e);
+        return 0;
+    }
+    return cp_pose_heads_backward_ws_bytes(B, H, W, Cin, hid, cmax, precision);
+}
+
+int cp_pose_heads_backward_prec(cp_stream_t stream, const float* feat, int n, const float* const* w0, const float* const* b0,
+                                const float* const* w1, const float* const* b1, const int* classes, const float* const* grad_out,
+                                float* const* grad_w0, float* const* grad_b0, float* const* grad_w1, float* const* grad_b1,
+                                float* grad_feat, int B, int H, int W, int Cin, int hid, int precision, void* workspace,
+                                size_t workspace_bytes) {
+    int cmax = 0;
+    if (const char* e = heads_shape_error(B, H, W, Cin, hid, n, classes, &cmax)) return fail(CP_ERR_INVALID, e);
+    if (const char* e = heads_bwd_prec_error(precision)) return fail(CP_ERR_INVALID, e);
+    if (!feat || !w0 || !b0 || !w1 || !b1 || !grad_out || !grad_w0 || !grad_b0 || !grad_w1 || !grad_b1 || !workspace)
+        return fail(CP_ERR_INVALID, "pose_heads_backward: null argument");
+    for (int i = 0; i < n; ++i)
+        if (!w0[i] || !b0[i] || !w1[i] || !b1[i] || !grad_w0[i] || !grad_b0[i] || !grad_w1[i] || !grad_b1[i])
+            return fail(CP_ERR_INVALID, "pose_heads_backward: null argument");
+    if (workspace_bytes < cp_pose_heads_backward_ws_bytes(B, H, W, Cin, hid, cmax, precision))
+        return fail(CP_ERR_INVALID, "pose_heads_backward: workspace too small");
+    const PoseHeadsArgs a{feat, n, w0, b0, w1, b1, classes, B, H, W, Cin, hid};
+    const int rc = cp_launch_pose_heads_backward((hipStream_t)stream, a, grad_out, grad_w0, grad_b0, grad_w1, grad_b1, grad_feat,
+                                                 workspace, precision);
     return rc == CP_OK ? CP_OK : fail(rc, "pose_heads_backward: kernel launch failed");
 }
 

@@ -43,6 +43,9 @@ SIGNATURES = {
     "cp_pose_heads_backward_workspace_bytes": (c_size_t, _i * 6 + _pi),
     "cp_pose_heads_forward": (c_int, _vp * 2 + _i + _pvp * 4 + _pi + _pvp + _i * 5 + _ws),
     "cp_pose_heads_backward": (c_int, _vp * 2 + _i + _pvp * 4 + _pi + _pvp * 5 + _vp + _i * 5 + _ws),
+    "cp_pose_heads_backward_prec_workspace_bytes": (c_size_t, _i * 6 + _pi + _i),
+    "cp_pose_heads_backward_prec": (c_int, _vp * 2 + _i + _pvp * 4 + _pi + _pvp * 5 + _vp + _i * 6 + _ws),
+    "cp_pose_heads_backward_prec_mask": (c_int, _i * 6),
     "cp_model_features": (c_int, _model + _vp + _ws),
     "cp_model_create": (c_int, [c_char_p, c_int, c_int, POINTER(c_char_p)] + _pi + _i + _pvp),
     "cp_model_set_param": (c_int, [c_void_p, c_char_p, c_void_p, c_int64]),

@@ -154,13 +154,31 @@ def pose_heads_forward(feat, params):
     return outs
 
 
+def _heads_bwd_precision(name):
+    if name not in _abi.PRECISIONS:
+        raise ValueError("pose_heads_backward: precision must be one of %s, got %r" % (sorted(_abi.PRECISIONS), name))
+    return _abi.PRECISIONS[name]
+
+
 def pose_heads_backward(feat, params, grad_outs, need_feat_grad=True, grad_feat=None):
     """Gradients of pose_heads_forward (cp_pose_heads_backward).  ``grad_outs``: per head a [B,classes_i,H,W] tensor or None (a
     head the loss does not use: zero parameter gradients, nothing added to grad_feat).  Returns (grad_feat, grads) with
     grads[i] = (grad_w0, grad_b0, grad_w1, grad_b1); grad_feat is a [B,Cin,H,W] channels_last tensor, or None when
     ``need_feat_grad`` is false (the data-gradient contraction is then not launched).  ``grad_feat``: an optional
-    channels_last buffer to write into."""
+    channels_last buffer to write into.  Float32 and bitwise reproducible.  ``ops.pose_heads_backward_prec`` is the same
+    operator with a ``precision`` argument."""
+    return pose_heads_backward_prec(feat, params, grad_outs, need_feat_grad=need_feat_grad, grad_feat=grad_feat, precision="f32")
+
+
+def pose_heads_backward_prec(feat, params, grad_outs, need_feat_grad=True, grad_feat=None, precision="f32"):
+    """``pose_heads_backward`` with the arithmetic of its matrix products as an argument.  ``precision``: "f32" (exact float32:
+    cp_pose_heads_backward, the bits of ``pose_heads_backward``) or "f16x3" (cp_pose_heads_backward_prec: the recomputed hidden
+    layer, the 3x3 weight gradient and the data gradient of every head on split-binary16 matrix instructions, float32-class
+    accuracy and bitwise reproducible; the gate, grad_w1 and the bias gradients stay float32 --
+    ``pose_heads_backward_precision_mask`` tells what a shape gets).  Reached as ``hip.ops.pose_heads_backward_prec``: the
+    ``hip`` package's own list of names and the signature of ``hip.pose_heads_backward`` are kept as they were."""
     L = _abi.lib()
+    prec = _heads_bwd_precision(precision)
     feat = _abi._nhwc_view(feat)
     flat, tables, cls_arr, classes, (B, H, W, Cin, hid) = _heads_args(feat, params)
     n = len(flat)
@@ -179,13 +197,29 @@ def pose_heads_backward(feat, params, grad_outs, need_feat_grad=True, grad_feat=
     if need_feat_grad and not (grad_feat.is_cuda and grad_feat.dtype == torch.float32 and grad_feat.shape == feat.shape and
                                grad_feat.is_contiguous(memory_format=torch.channels_last)):
         raise RuntimeError("pose_heads_backward: grad_feat must be a float32 channels_last tensor of feat's shape")
-    ws = _abi._workspace(L.cp_pose_heads_backward_workspace_bytes(B, H, W, Cin, hid, n, cls_arr), feat.device,
-                         "pose_heads_backward")
-    rc = L.cp_pose_heads_backward(_abi._stream(), _abi._ptr(feat), n, *tables, cls_arr, goptr, *gtab,
-                                  _abi._ptr(grad_feat) if need_feat_grad else c_void_p(0), B, H, W, Cin, hid, _abi._ptr(ws),
-                                  ws.numel())
-    _abi._check(rc, "cp_pose_heads_backward")
+    gfp = _abi._ptr(grad_feat) if need_feat_grad else c_void_p(0)
+    if prec:
+        ws = _abi._workspace(L.cp_pose_heads_backward_prec_workspace_bytes(B, H, W, Cin, hid, n, cls_arr, prec), feat.device,
+                             "pose_heads_backward")
+        rc = L.cp_pose_heads_backward_prec(_abi._stream(), _abi._ptr(feat), n, *tables, cls_arr, goptr, *gtab, gfp, B, H, W, Cin,
+                                           hid, prec, _abi._ptr(ws), ws.numel())
+    else:
+        ws = _abi._workspace(L.cp_pose_heads_backward_workspace_bytes(B, H, W, Cin, hid, n, cls_arr), feat.device,
+                             "pose_heads_backward")
+        rc = L.cp_pose_heads_backward(_abi._stream(), _abi._ptr(feat), n, *tables, cls_arr, goptr, *gtab, gfp, B, H, W, Cin, hid,
+                                      _abi._ptr(ws), ws.numel())
+    _abi._check(rc, "cp_pose_heads_backward_prec" if prec else "cp_pose_heads_backward")
     return (grad_feat if need_feat_grad else None), grads
+
+
+def pose_heads_backward_precision_mask(B, H, W, Cin, hid, precision="f16x3"):
+    """What ``pose_heads_backward_prec(..., precision=precision)`` runs in f16x3 for a shape (cp_pose_heads_backward_prec_mask;
+    host arithmetic): bit 0 = the 3x3 weight gradient, bit 1 = the data gradient, bit 2 = the recomputed hidden layer.  0 for
+    "f32".  Raises RuntimeError for a shape the operator refuses."""
+    rc = _abi.lib().cp_pose_heads_backward_prec_mask(int(B), int(H), int(W), int(Cin), int(hid), _heads_bwd_precision(precision))
+    if rc < 0:
+        _abi._refuse("pose_heads_backward_precision_mask")
+    return rc
 
 
 def conv2d_nhwc(x, w, scale=None, shift=None, residual=None, stride=1, pad=0, act=0):

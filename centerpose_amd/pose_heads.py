@@ -8,7 +8,9 @@ with the same deterministic initial values (``hm*`` final bias -2.19, other bias
 
 Forward is ``hip.pose_heads_forward`` (the same kernels, and so the same values, inside and outside grad mode); backward is one
 ``hip.pose_heads_backward`` call with every head's gradient (``None`` for a head the loss does not use).  Only the feature
-map and the parameters are saved between the two: the hidden layers are recomputed, never stored.
+map and the parameters are saved between the two: the hidden layers are recomputed, never stored.  The backward is float32
+unless the module's ``backward_precision`` is "f16x3", which moves its three wide contractions per head onto split-binary16
+matrix instructions (``hip.ops.pose_heads_backward_prec``; ``set_backward_precision`` sets it on a whole network).
 """
 from collections import OrderedDict
 
@@ -22,9 +24,10 @@ from . import hip as _hip
 
 class _PoseHeadsFn(Function):
     @staticmethod
-    def forward(ctx, feat, *flat):
+    def forward(ctx, feat, backward_precision, *flat):
         params = [tuple(flat[4 * i:4 * i + 4]) for i in range(len(flat) // 4)]
         outs = _hip.pose_heads_forward(feat, params)
+        ctx.backward_precision = backward_precision
         ctx.save_for_backward(feat, *flat)
         ctx.set_materialize_grads(False)   # a head the loss does not use arrives as None, not as a zero map
         return tuple(outs)
@@ -35,10 +38,11 @@ class _PoseHeadsFn(Function):
         feat, flat = ctx.saved_tensors[0], ctx.saved_tensors[1:]
         params = [tuple(flat[4 * i:4 * i + 4]) for i in range(len(flat) // 4)]
         need_feat = ctx.needs_input_grad[0]
-        gfeat, grads = _hip.pose_heads_backward(feat, params, list(grad_outs), need_feat_grad=need_feat)
-        out = [gfeat]
+        gfeat, grads = _hip.ops.pose_heads_backward_prec(feat, params, list(grad_outs), need_feat_grad=need_feat,
+                                                         precision=ctx.backward_precision)
+        out = [gfeat, None]
         for i, g in enumerate(grads):
-            out.extend(g[k] if ctx.needs_input_grad[1 + 4 * i + k] else None for k in range(4))
+            out.extend(g[k] if ctx.needs_input_grad[2 + 4 * i + k] else None for k in range(4))
         return tuple(out)
 
 
@@ -51,12 +55,22 @@ class _Slot(nn.Module):
         self.bias = nn.Parameter(bias)
 
 
+def _precision_name(name):
+    if name not in _hip.PRECISIONS:
+        raise ValueError("backward_precision must be one of %s, got %r" % (sorted(_hip.PRECISIONS), name))
+    return name
+
+
 class PoseHeads(nn.Module):
     """``PoseHeads(heads, in_channels, head_conv)``: ``heads`` maps head name -> classes (``opt.heads``).  ``forward(feat)``
-    takes the [B, in_channels, H, W] feature map (NCHW-contiguous or channels_last) and returns the reference's ``z`` dict."""
+    takes the [B, in_channels, H, W] feature map (NCHW-contiguous or channels_last) and returns the reference's ``z`` dict.
+    ``backward_precision``: "f32" or "f16x3", the arithmetic of the backward's matrix products; an attribute, read at every
+    forward, so a built module can be switched (``set_backward_precision``).  The forward's follows
+    ``hip.set_default_precision``."""
 
-    def __init__(self, heads, in_channels=64, head_conv=256):
+    def __init__(self, heads, in_channels=64, head_conv=256, backward_precision="f32"):
         super().__init__()
+        self.backward_precision = _precision_name(backward_precision)
         if head_conv <= 0:
             raise NotImplementedError("PoseHeads: head_conv must be positive (the single-convolution head form is not built)")
         if in_channels % 32 or head_conv % 32:
@@ -84,5 +98,25 @@ class PoseHeads(nn.Module):
 
     def forward(self, feat):
         flat = [p for name in self.heads for p in self.head_params(name)]
-        outs = _PoseHeadsFn.apply(feat, *flat)
+        outs = _PoseHeadsFn.apply(feat, _precision_name(self.backward_precision), *flat)
         return OrderedDict(zip(self.heads, outs))
+
+
+def set_backward_precision(module, name):
+    """Set ``backward_precision`` ("f32" or "f16x3") on every ``PoseHeads`` under ``module`` (itself included); returns how many
+    head blocks were set.  Besides the ``PoseHeads`` that are sub-modules it reaches the two ways a net holds its heads: a
+    ``PoseHeads`` kept outside the sub-module tree as ``_head_block`` (``PoseNet``, whose state-dict keys carry no prefix), and a
+    net that runs ``_PoseHeadsFn`` on its own parameters and carries the name as ``heads_backward_precision``
+    (``PoseNetHourglass``, one block per stack, counted once).  ``conv.set_backward_precision`` is the switch of the
+    ``Conv2d`` layers and leaves all of these alone."""
+    name = _precision_name(name)
+    n = 0
+    for m in module.modules():
+        for h in (m, m.__dict__.get("_head_block")):
+            if isinstance(h, PoseHeads):
+                h.backward_precision = name
+                n += 1
+        if hasattr(m, "heads_backward_precision"):
+            m.heads_backward_precision = name
+            n += 1
+    return n

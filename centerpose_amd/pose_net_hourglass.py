@@ -25,7 +25,7 @@ from torch import nn
 from . import synth as _synth
 from .conv import Conv2d
 from .norm import BatchNorm2d
-from .pose_heads import _PoseHeadsFn, _Slot
+from .pose_heads import _PoseHeadsFn, _precision_name, _Slot
 from .stem import StemConv2d
 from .upsample import UpsampleAdd
 
@@ -119,6 +119,7 @@ class PoseNetHourglass(nn.Module):
     reference network.  ``forward(x)`` takes an NCHW image batch on the device, H and W multiples of ``4 * 2**n``, and returns
     a list of ``num_stacks`` dicts of raw head maps.  ``eval()`` runs the same layers on the running statistics."""
     arch = "hourglass"
+    heads_backward_precision = "f32"  # the heads' backward arithmetic (pose_heads.set_backward_precision)
 
     def __init__(self, heads, opt=None, n=5, dims=_synth.HG_DIMS, modules=_synth.HG_MODULES, num_stacks=2):
         super().__init__()
@@ -169,7 +170,7 @@ class PoseNetHourglass(nn.Module):
         for k in range(self.nstack):
             cnv = self.cnvs[k](self.kps[k](inter))
             # all heads of the stack in one autograd function (pose_heads.py), on this module's own parameters
-            outs.append(OrderedDict(zip(self.heads, _PoseHeadsFn.apply(cnv, *self._head_params(k)))))
+            outs.append(OrderedDict(zip(self.heads, _PoseHeadsFn.apply(cnv, _precision_name(self.heads_backward_precision), *self._head_params(k)))))
             if k < self.nstack - 1:
                 a, b = self.inters_[k], self.cnvs_[k]
                 inter = self.inters[k](b[1](b[0](cnv), a[1](a[0](inter))))

@@ -154,7 +154,7 @@ int cp_dcnv2_backward_det(cp_stream_t stream, const float* input, const float* w
  *             = the sum over the heads, or NULL (frozen backbone): the data-gradient contraction is then not launched.
  * Semantics are autograd's for the block; the ReLU gate is `hidden > 0` on the hidden value the backward recomputes.
  * Backward arithmetic is exact float32 (v_mfma_f32_32x32x2_f32 contractions, float32 VALU elsewhere) whatever
- * cp_set_default_precision says.  Nothing is kept between forward and backward: the backward recomputes a head's hidden
+ * cp_set_default_precision says (that switch governs the forward only).  Nothing is kept between forward and backward: the backward recomputes a head's hidden
  * layer for cp_pose_heads_chunk_images(B, H, W, hid) images at a time (at most 256 MiB, or one image) inside `workspace`
  * and drops it; the hidden maps of all heads never exist together.
  * Reproducibility: every gradient, grad_feat included, is bitwise reproducible run to run (weight and bias gradients are
@@ -163,6 +163,20 @@ int cp_dcnv2_backward_det(cp_stream_t stream, const float* input, const float* w
  * elements; anything else, a NULL pointer other than those named above or a workspace below the query returns
  * CP_ERR_INVALID with a cp_last_error() text before any launch (the queries return 0).  Launches on `stream`, never
  * synchronises.
+ * cp_pose_heads_backward_prec_* are the backward's calls with a `precision` argument (CP_PREC_*), for the same block
+ * (pose_dla_dcn.py:491-521, :537-539).  CP_PREC_F32 IS the calls without it: same kernels, same bits, same workspace
+ * size.  CP_PREC_F16X3 runs the three wide contractions of a head on v_mfma_f32_32x32x16_f16 with the split-binary16
+ * arithmetic of cp_conv2d_backward_prec_nhwc (hi*hi + hi*lo + lo*hi, float32 accumulation, exact power-of-two pre-scales):
+ * the recomputed hidden layer on the kernel and operands an f16x3 cp_pose_heads_forward uses, so the gate is the one that
+ * forward's ReLU applied; the 3x3 weight gradient; the data gradient.  The gate, grad_w1, grad_b0 and grad_b1 stay float32
+ * sums in the float32 mode's orders.  The only atomics are order-free |max| commits, so every gradient stays bitwise
+ * reproducible run to run, and is equivariant, bit for bit, under power-of-two scalings of grad_out.  The f16x3 workspace
+ * is larger: a split copy of the whole feature map (made once per call, B H W Cin x 4 bytes), one of the hidden chunk, the
+ * binary16 weight packs and two |max| slot blocks.  cp_pose_heads_backward_prec_mask (host arithmetic) reports what a shape
+ * gets: bit 0 = the weight gradient, bit 1 = the data gradient, bit 2 = the recomputed hidden layer runs in f16x3 (the last
+ * two stay float32 for a chunk of 0xf0000000 bytes or more); 0 for CP_PREC_F32; CP_ERR_INVALID (with a text) for a refused
+ * shape or an unknown precision, which the other two calls refuse likewise before any launch, as they do everything
+ * cp_pose_heads_backward refuses.
  * ------------------------------------------------------------------------------------------ */
 int cp_pose_heads_chunk_images(int B, int H, int W, int hid);
 size_t cp_pose_heads_forward_workspace_bytes(int B, int H, int W, int Cin, int hid, int n, const int* classes);
@@ -175,6 +189,14 @@ int cp_pose_heads_backward(cp_stream_t stream, const float* feat, int n, const f
                            const float* const* grad_out, float* const* grad_w0, float* const* grad_b0,
                            float* const* grad_w1, float* const* grad_b1, float* grad_feat, int B, int H, int W, int Cin,
                            int hid, void* workspace, size_t workspace_bytes);
+size_t cp_pose_heads_backward_prec_workspace_bytes(int B, int H, int W, int Cin, int hid, int n, const int* classes,
+                                                   int precision);
+int cp_pose_heads_backward_prec(cp_stream_t stream, const float* feat, int n, const float* const* w0,
+                                const float* const* b0, const float* const* w1, const float* const* b1, const int* classes,
+                                const float* const* grad_out, float* const* grad_w0, float* const* grad_b0,
+                                float* const* grad_w1, float* const* grad_b1, float* grad_feat, int B, int H, int W, int Cin,
+                                int hid, int precision, void* workspace, size_t workspace_bytes);
+int cp_pose_heads_backward_prec_mask(int B, int H, int W, int Cin, int hid, int precision);
 
 /* ------------------------------------------------------------------------------------------
  * Backbone + heads — replaces `create_model` / `load_model` / `model(images, pre_images,

@@ -1,0 +1,259 @@
+"""Cases, input generators and helpers of the f16x3 PoseHeads backward tests (tests/test_pose_heads_f16x3_{cpu,gpu}.py).  No
+test lives here.
+
+The mode (cp_pose_heads_backward_prec with CP_PREC_F16X3) runs three contractions per head in split binary16 -- the recomputed
+hidden layer, the 3x3 weight gradient, the data gradient: each operand is pre-scaled by an exact power of two, split into two
+binary16 numbers hi + lo, and hi*hi + hi*lo + lo*hi is summed in float32 (tests/conv_backward_f16x3_cases.py).  The gate,
+grad_w1, grad_b0 and grad_b1 are the float32 mode's code.  Four kinds of inputs:
+
+* strict dyadic (pose_heads_ref.dyadic_case): feat and w0 are multiples of 1/4 in [-2, 2] and have no lo part, every hidden value
+  is an odd multiple of 1/32, exact in either arithmetic and never zero: the gate is the reference's by construction.
+* exact two-level, variant "go": feat, w0 and w1 in {-1, 0, 1}, b0 an odd multiple of 1/32, grad_out = a + b 2^-12 with a, b in
+  {-1, 0, 1}.  grad_hidden = gate * (grad_out x w1) is then a multiple of 2^-12 of magnitude at most classes (1 + 2^-12), which is
+  hi + lo exactly with a non-zero lo wherever both parts are there.  Variant "feat": the two-level values are in feat, and w0,
+  w1 and grad_out are in {-1, 0, 1}; b0 is an odd multiple of 2^-13, below feat's 2^-12 grid, so no hidden value can be zero.
+  With B H W classes <= 4000 and 9 hid classes <= 4000 every partial sum of grad_w0, grad_b0, grad_b1 and grad_feat, in any
+  order, is a multiple of 2^-12 below 2^12 x (1 + 2^-12), hence exact in float32: those four must EQUAL the float64 reference,
+  and a kernel that drops hi*lo ("feat": the weight gradient and the hidden layer; "go": lo*hi of the weight and the data
+  gradient) cannot.  grad_w1 sums relu(hidden) x grad_out, 14 x 13 bits per product, in a float32 FMA chain: GRAD_TOL.
+* Gaussian / power-of-two scaled: GRAD_TOL = 1e-4 x max |reference| per gradient, the project's gradient tolerance.
+* realistic: synth's head parameters of dla_34 and resdcn_18 on a non-negative feature map (the backbones end in a ReLU), with
+  the element-wise allowance for hidden units whose gate the arithmetic may decide differently -- pose_heads_ref.allowance with
+  the threshold per unit widened by the mode's error model (``f16x3_allowance``).
+"""
+import functools
+from types import SimpleNamespace
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from tests import pose_heads_ref as R
+from tests.conv_backward_f16x3_cases import TWO_LEVEL_MAX_SUM, np_scale, np_split
+
+GRAD_TOL = 1e-4
+NAMES = ("grad_w0", "grad_b0", "grad_w1", "grad_b1")
+MASK_ALL = 7   # weight gradient | data gradient | hidden layer
+
+# ---- strict dyadic shapes: name -> (seed, B, Cin, hid, H, W, classes)
+# every shape of the float32 tests but the 128 x 128 one; five widths around wgrad16_kernel's sixteen-pixel K step; the three
+# single-head shapes that reach NH = 1 / 2 / 4 in the float32 kernel (NH = 1 / 2 / 2 in wgrad16_kernel)
+KSTEP_WIDTHS = (15, 16, 17, 31, 33)
+STRICT_SHAPES = {name: (sum(map(ord, name)),) + shape for name, shape in R.DYADIC_SHAPES.items() if name != "dla_128"}
+STRICT_SHAPES.update({"kstep_w%d" % w: (200 + w, 1, 32, 64, 5, w, (2,)) for w in KSTEP_WIDTHS})
+STRICT_SHAPES.update(R.SHARED_CONV_CASES)
+
+# ---- exact two-level shapes: (B, Cin, hid, H, W, classes), one head each
+TWO_LEVEL_SHAPES = {
+    "c32_h64_9x7": (1, 32, 64, 9, 7, (1,)),
+    "c64_h256_two_images_5x3": (2, 64, 256, 5, 3, (1,)),
+    "c32_h32_16x17_four_classes": (1, 32, 32, 16, 17, (4,)),
+}
+TWO_LEVEL_KINDS = ("go", "feat")
+
+
+def two_level_ok(shape):
+    B, Cin, hid, H, W, classes = shape
+    return len(classes) == 1 and B * H * W * classes[0] <= TWO_LEVEL_MAX_SUM and 9 * hid * classes[0] <= TWO_LEVEL_MAX_SUM and Cin <= 64
+
+
+def _unit(g, *shape):
+    return torch.randint(-1, 2, shape, generator=g).float()
+
+
+def _two(g, *shape):
+    a = torch.randint(-1, 2, shape, generator=g).double()
+    b = torch.randint(-1, 2, shape, generator=g).double()
+    return (a + b * 2.0 ** -12).float()
+
+
+def two_level_case(seed, shape, kind):
+    """-> SimpleNamespace(feat, params, grad_outs) of float32 CPU tensors (module docstring); asserts its value sets."""
+    assert two_level_ok(shape) and kind in TWO_LEVEL_KINDS
+    B, Cin, hid, H, W, (c,) = shape
+    g = torch.Generator().manual_seed(seed)
+    odd = (2 * torch.randint(-16, 16, (hid,), generator=g) + 1).float()
+    if kind == "go":
+        feat, b0, go = _unit(g, B, Cin, H, W), odd / 32, _two(g, B, c, H, W)
+    else:
+        feat, b0, go = _two(g, B, Cin, H, W), odd * 2.0 ** -13, _unit(g, B, c, H, W)
+    w0, w1 = _unit(g, hid, Cin, 3, 3), _unit(g, c, hid, 1, 1)
+    b1 = torch.randn(c, generator=g)
+    for t in (w0, w1) + ((feat,) if kind == "go" else (go,)):
+        assert torch.equal(t, t.round()) and float(t.abs().max()) == 1.0
+    return SimpleNamespace(feat=feat, params=[(w0, b0, w1, b1)], grad_outs=[go])
+
+
+def grad_hidden64(case):
+    """Per head (hidden, grad_hidden = gate * (grad_out x w1)) in float64."""
+    outs = []
+    for (w0, b0, w1, _), go in zip(case.params, case.grad_outs):
+        h = F.conv2d(case.feat.double(), w0.double(), b0.double(), padding=1)
+        outs.append((h, torch.einsum("bcyx,ch->bhyx", go.double(), w1.double()[:, :, 0, 0]) * (h > 0)))
+    return outs
+
+
+def split_is_exact(t):
+    """hi + lo of the device's scale and split reproduces the float32 tensor ``t`` exactly; -> whether any lo is non-zero."""
+    v = t.float().numpy()
+    assert np.all(v.astype(np.float64) == t.double().numpy())          # a float32 tensor to begin with
+    s = np_scale(float(np.abs(v).max()))
+    hi, lo = np_split(v * np.float32(s))
+    assert np.all(hi + lo == v.astype(np.float64) * s)
+    return bool(np.any(lo != 0))
+
+
+def check_two_level(case, shape, kind):
+    """The premises of the exact cases, on the CPU: float32 == float64 hidden values, none zero, about half active; every split
+    operand is exactly hi + lo, with a non-zero lo in the operand the variant is about; the sums are bounded."""
+    B, Cin, hid, H, W, (c,) = shape
+    (w0, b0, w1, _), go = case.params[0], case.grad_outs[0]
+    h32 = F.conv2d(case.feat, w0, b0, padding=1)
+    (h64, gh), = grad_hidden64(case)
+    assert torch.equal(h32.double(), h64) and not bool((h64 == 0).any())
+    assert 0.25 <= float((h64 > 0).double().mean()) <= 0.75
+    assert torch.equal(gh.float().double(), gh)
+    lo_feat, lo_gh = split_is_exact(case.feat), split_is_exact(gh)
+    assert (lo_feat, lo_gh) == ((False, True) if kind == "go" else (True, False)), (kind, lo_feat, lo_gh)
+    # the weights: a power-of-two scale per row (hidden layer) or per input channel (data gradient) of values in {-1, 0, 1}
+    assert not split_is_exact(w0)
+    unit = 2.0 ** -12
+    k = gh / unit
+    assert torch.equal(k, k.round()) and float(gh.abs().max()) <= c * (1 + unit)
+    assert float(case.feat.abs().max()) <= 1 + unit
+    # grad_w0 / grad_b0 / grad_b1 sum B H W terms, grad_feat 9 hid terms, each a multiple of 2^-12 below c (1 + 2^-12)
+    assert max(B * H * W, 9 * hid) * c * (1 + unit) < 2 ** 12
+    # the hidden layer sums 9 Cin terms below 1 + 2^-12 on a grid of 2^-13 (b0's): 24 bits hold them
+    assert (9 * Cin * (1 + unit) + float(b0.abs().max())) * 2 ** 13 < 2 ** 24
+
+
+# ---- the realistic cases: arch -> (head_conv, seed of the feature map, B, H, W)
+REALISTIC = {"dla_34": (256, 11, 1, 64, 64), "resdcn_18": (64, 12, 2, 32, 32)}
+PRODUCT_REL = 2.0 ** -19   # the relative error of one f16x3 product is below 2^-19.4
+
+
+@functools.lru_cache(maxsize=None)
+def realistic_case(arch):
+    """synth's head parameters of ``arch`` (as tests/test_pose_heads_gpu.py's realistic test draws them) on a non-negative
+    feature map of the backbones' last layer (a ReLU output: half-normal, a third of it zero) and Gaussian grad_outs."""
+    from centerpose_amd import synth
+
+    heads = synth.HEADS_POSE
+    head_conv, seed, B, H, W = REALISTIC[arch]
+    sd = synth.make_state_dict(arch, heads, head_conv=head_conv)
+    params = R.head_params(sd, heads)
+    g = torch.Generator().manual_seed(seed)
+    feat = F.relu(torch.randn(B, 64, H, W, generator=g) - 0.4)
+    return SimpleNamespace(feat=feat, params=params, grad_outs=R.gaussian_grad_outs(seed + 1, B, list(heads.values()), H, W))
+
+
+def f16x3_allowance(feat, params, grad_outs, hidden):
+    """pose_heads_ref.allowance with the ambiguity threshold of a hidden unit widened by what the f16x3 hidden layer may be off
+    by: |h64| <= AMBIGUOUS_REL * max|h64| + 2^-19 * (|feat| (*) |w0|) of that unit, in float64.  -> the same dict."""
+    x = feat.detach().cpu().double().abs()
+    gfeat = torch.zeros_like(x)
+    grads, amb_n, n = [], 0, 0
+    for (w0, b0, w1, b1), go, h in zip(params, grad_outs, hidden):
+        w0, w1 = w0.detach().cpu().double().abs(), w1.detach().cpu().double().abs()
+        if go is None:
+            grads.append(tuple(torch.zeros(tuple(t.shape), dtype=torch.float64) for t in (w0, b0, w1, b1)))
+            continue
+        go = go.detach().cpu().double().abs()
+        thr = R.AMBIGUOUS_REL * float(h.abs().max()) + PRODUCT_REL * F.conv2d(x, w0, padding=1)
+        amb = h.abs() <= thr
+        amb_n += int(amb.sum())
+        n += amb.numel()
+        gh = torch.einsum("bcyx,ch->bhyx", go, w1[:, :, 0, 0]) * amb
+        gw1 = torch.einsum("bcyx,bhyx->ch", go, h.abs() * amb).reshape(w1.shape)
+        gfeat += F.conv_transpose2d(gh, w0, padding=1)
+        grads.append((R._wgrad3x3(x, gh), gh.sum(dim=(0, 2, 3)), gw1, torch.zeros(w1.shape[0], dtype=torch.float64)))
+    return dict(share=amb_n / max(n, 1), gfeat=gfeat, grads=grads)
+
+
+# ---- shared, never modified
+@functools.lru_cache(maxsize=None)
+def cached_case(kind, name):
+    """kind "strict" (STRICT_SHAPES), "two_go" / "two_feat" (TWO_LEVEL_SHAPES), "gauss" (STRICT_SHAPES' shape, Gaussian inputs) or
+    "realistic" (REALISTIC)."""
+    if kind == "strict":
+        seed, *shape = STRICT_SHAPES[name]
+        return R.dyadic_case(seed, *shape)
+    if kind == "gauss":
+        seed, B, Cin, hid, H, W, classes = STRICT_SHAPES[name]
+        g = torch.Generator().manual_seed(seed + 1000)
+        feat = torch.randn(B, Cin, H, W, generator=g)
+        params = [(torch.randn(hid, Cin, 3, 3, generator=g) * 0.05, torch.randn(hid, generator=g) * 0.1,
+                   torch.randn(c, hid, 1, 1, generator=g) * 0.05, torch.randn(c, generator=g)) for c in classes]
+        return SimpleNamespace(feat=feat, params=params, grad_outs=[torch.randn(B, c, H, W, generator=g) for c in classes])
+    if kind == "realistic":
+        return realistic_case(name)
+    shape = TWO_LEVEL_SHAPES[name]
+    return two_level_case(sum(map(ord, name)) + 7, shape, kind[4:])
+
+
+@functools.lru_cache(maxsize=None)
+def cached_reference(kind, name):
+    case = cached_case(kind, name)
+    return R.reference(case.feat, case.params, case.grad_outs)
+
+
+def shape_of(case):
+    B, Cin, H, W = case.feat.shape
+    return B, H, W, Cin, case.params[0][0].shape[0]
+
+
+def assert_f16x3(case, want=MASK_ALL):
+    """The three contractions of the case run in f16x3: a silent float32 fallback cannot pass a test that calls this first."""
+    from centerpose_amd import hip
+
+    assert hip.ops.pose_heads_backward_precision_mask(*shape_of(case), precision="f16x3") == want, shape_of(case)
+    assert hip.ops.pose_heads_backward_precision_mask(*shape_of(case), precision="f32") == 0
+
+
+def to_device(dev, case):
+    feat = case.feat.to(dev).contiguous(memory_format=torch.channels_last)
+    params = [tuple(t.to(dev) for t in p) for p in case.params]
+    return feat, params, [g.to(dev) if g is not None else None for g in case.grad_outs]
+
+
+def device_backward(dev, case, precision="f16x3", grad_outs=None, **kw):
+    """hip.ops.pose_heads_backward_prec on the case -> (grad_feat | None, grads) on the device."""
+    from centerpose_amd import hip
+
+    feat, params, gos = to_device(dev, case)
+    if grad_outs is not None:
+        gos = [g.to(dev) if g is not None else None for g in grad_outs]
+    return hip.ops.pose_heads_backward_prec(feat, params, gos, precision=precision, **kw)
+
+
+def flat(result):
+    """(grad_feat, grads) -> [(name, tensor)]"""
+    gfeat, grads = result
+    out = [("grad_feat", gfeat)] if gfeat is not None else []
+    return out + [("head %d %s" % (i, NAMES[k]), g[k]) for i, g in enumerate(grads) for k in range(4)]
+
+
+def flat_ref(ref, with_feat=True):
+    return flat((ref["gfeat"] if with_feat else None, ref["grads"]))
+
+
+def bit_equal(a, b):
+    return all(torch.equal(x, y) for (_, x), (_, y) in zip(flat(a), flat(b)))
+
+
+def assert_close(result, ref, what, allow=None, tol=GRAD_TOL, exact=()):
+    """Every gradient within tol x max |reference| (+ the element-wise allowance); the ones named in ``exact`` (suffixes of
+    ``flat``'s names) must EQUAL the reference.  Prints each figure before it asserts."""
+    al = dict(flat((allow["gfeat"], allow["grads"]))) if allow else {}
+    for (name, got), (_, exp) in zip(flat(result), flat_ref(ref, result[0] is not None)):
+        d = (got.detach().cpu().double() - exp).abs()
+        scale = float(exp.abs().max())
+        extra = al.get(name, torch.zeros(()))
+        bad = int((d != 0).sum())
+        print("%s %s: max err %.3g, max |ref| %.3g, allowance up to %.3g, %d of %d differ"
+              % (what, name, float(d.max()), scale, float(extra.max()), bad, d.numel()))
+        assert got.shape == exp.shape, (what, name)
+        if any(name.endswith(e) for e in exact):
+            assert bad == 0, "%s %s: %d elements differ from the float64 reference (max err %.3g)" % (what, name, bad, float(d.max()))
+        else:
+            assert bool((d <= tol * scale + extra).all()), "%s %s: max err %.3g vs max |ref| %.3g" % (what, name, float(d.max()), scale)

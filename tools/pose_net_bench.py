@@ -32,18 +32,20 @@ from collections import OrderedDict
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
-FAMILIES = {"conv2d_nhwc": "conv fwd", "conv2d_backward": "conv bwd", "conv2d_stem_backward": "stem bwd",
+FAMILIES = {"conv2d_nhwc": "conv fwd", "conv2d_stem_backward": "stem bwd",
             "batch_norm_forward": "bn fwd", "batch_norm_backward": "bn bwd", "max_pool2d_forward": "pool fwd",
             "max_pool2d_backward": "pool bwd", "conv_transpose2d_dw": "up fwd", "conv_transpose2d_backward": "up bwd",
-            "dcn_v2_forward": "dcn fwd", "dcn_v2_backward": "dcn bwd", "pose_heads_forward": "heads fwd",
-            "pose_heads_backward": "heads bwd"}
+            "dcn_v2_forward": "dcn fwd", "dcn_v2_backward": "dcn bwd", "pose_heads_forward": "heads fwd"}
+# the layers reach these two through hip.ops, with a precision argument (hip.conv2d_backward and hip.pose_heads_backward go through
+# them too, so each call is bracketed once)
+OPS_FAMILIES = {"conv2d_backward_prec": "conv bwd", "pose_heads_backward_prec": "heads bwd"}
 
 
 def main():
     import torch
     import torch.nn.functional as F
 
-    from centerpose_amd import conv, hip, pool, stem, synth
+    from centerpose_amd import conv, hip, pool, pose_heads, stem, synth
     from centerpose_amd.pose_net import PoseNet
 
     ap = argparse.ArgumentParser()
@@ -58,6 +60,9 @@ def main():
     ap.add_argument("--backward-precision", default="f32", choices=["f32", "f16x3", "both"],
                     help="of the step's conv.Conv2d layers (conv.set_backward_precision); both: the two modes alternating, "
                          "the traced step in f16x3")
+    ap.add_argument("--heads-backward-precision", default="f32", choices=["f32", "f16x3"],
+                    help="of the heads' backward (pose_heads.set_backward_precision) in every step but the f32 side of "
+                         "--backward-precision both, which stays the all-float32 step")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -173,6 +178,8 @@ def main():
         def enter(m):
             hip.set_deterministic(m is True)
             conv.set_backward_precision(net, "f16x3" if m == "f16x3" else precs[0])
+            heads_mode = "f32" if len(precs) == 2 and m != "f16x3" else a.heads_backward_precision
+            assert pose_heads.set_backward_precision(net, heads_mode) == 1
 
         for m in modes:
             enter(m)
@@ -184,7 +191,8 @@ def main():
                 enter(m)
                 rounds[m].append(timed(step))
         total = rounds[False]
-        det = {"backward_precision": a.backward_precision, "traced_backward_precision": precs[-1]}
+        det = {"backward_precision": a.backward_precision, "traced_backward_precision": precs[-1],
+               "heads_backward_precision": a.heads_backward_precision}
         if len(precs) == 2:
             det.update({"f16x3_step_ms": round(statistics.median(rounds["f16x3"]), 2),
                         "f16x3_step_ms_rounds": [round(v, 2) for v in rounds["f16x3"]],
@@ -200,7 +208,7 @@ def main():
 
         def wrap(fname, fn):
             def inner(*args, **kw):
-                fam = FAMILIES[fname]
+                fam = FAMILIES.get(fname) or OPS_FAMILIES[fname]
                 if fname == "conv2d_nhwc" and args[0].shape[3] == 4 and args[1].shape[2] == 7:
                     fam = "stem fwd"
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -211,9 +219,10 @@ def main():
                 return out
             return inner
 
-        for fname in FAMILIES:
-            originals[fname] = getattr(hip, fname)
-            setattr(hip, fname, wrap(fname, originals[fname]))
+        for module, table in ((hip, FAMILIES), (hip.ops, OPS_FAMILIES)):
+            for fname in table:
+                originals[(module, fname)] = getattr(module, fname)
+                setattr(module, fname, wrap(fname, originals[(module, fname)]))
         try:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             torch.cuda.synchronize()
@@ -222,8 +231,8 @@ def main():
             e1.record()
             torch.cuda.synchronize()
         finally:
-            for fname, fn in originals.items():
-                setattr(hip, fname, fn)
+            for (module, fname), fn in originals.items():
+                setattr(module, fname, fn)
         split, calls = OrderedDict(), OrderedDict()
         for fam, s0, s1 in events:
             split[fam] = split.get(fam, 0.0) + s0.elapsed_time(s1)

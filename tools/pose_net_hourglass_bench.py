@@ -34,17 +34,19 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
 # function -> (module attribute it is reached through, family)
-FAMILIES = {"conv2d_nhwc": "conv fwd", "conv2d_backward": "conv bwd", "conv2d_stem_backward": "stem bwd",
-            "batch_norm_forward": "bn fwd", "batch_norm_backward": "bn bwd", "pose_heads_forward": "heads fwd",
-            "pose_heads_backward": "heads bwd"}
-MERGE = {"upsample2_add_forward": "merge fwd", "upsample2_add_backward": "merge bwd"}
+FAMILIES = {"conv2d_nhwc": "conv fwd", "conv2d_stem_backward": "stem bwd",
+            "batch_norm_forward": "bn fwd", "batch_norm_backward": "bn bwd", "pose_heads_forward": "heads fwd"}
+# reached through hip.ops: the two backwards with a precision argument (the layers call these; hip.conv2d_backward and
+# hip.pose_heads_backward go through them too) and the merge
+MERGE = {"upsample2_add_forward": "merge fwd", "upsample2_add_backward": "merge bwd", "conv2d_backward_prec": "conv bwd",
+         "pose_heads_backward_prec": "heads bwd"}
 
 
 def main():
     import torch
     import torch.nn.functional as F
 
-    from centerpose_amd import conv, hip, stem, synth, upsample
+    from centerpose_amd import conv, hip, pose_heads, stem, synth, upsample
     from centerpose_amd.hip import ops
     from centerpose_amd.pose_net_hourglass import PoseNetHourglass
 
@@ -57,6 +59,9 @@ def main():
     ap.add_argument("--backward-precision", default="f32", choices=["f32", "f16x3", "both"],
                     help="of the step's conv.Conv2d layers (conv.set_backward_precision); both: the two modes alternating "
                          "(library = f32, library_f16x3), the traced step in f16x3")
+    ap.add_argument("--heads-backward-precision", default="f32", choices=["f32", "f16x3"],
+                    help="of the heads' backward (pose_heads.set_backward_precision) in every step but the f32 side of "
+                         "--backward-precision both, which stays the all-float32 step")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -220,6 +225,8 @@ def main():
                 if current[0] != mode:
                     current[0] = mode
                     conv.set_backward_precision(net, mode)
+                    heads_mode = "f32" if len(modes) == 2 and mode == "f32" else a.heads_backward_precision
+                    assert pose_heads.set_backward_precision(net, heads_mode) == 1
                 step()
             return run_step
 
@@ -270,6 +277,7 @@ def main():
         traced = e0.elapsed_time(e1)
         split["torch glue and launch gaps"] = traced - sum(split.values())
         report({"what": "step", "arch": "hourglass", "backward_precision": a.backward_precision, "traced_backward_precision": modes[-1],
+                "heads_backward_precision": a.heads_backward_precision,
                 "B": B, "HxW": S, "images_per_s": round(B / r["library"][0] * 1e3, 1),
                 "traced_step_ms": round(traced, 2), "family_ms": {k: round(v, 2) for k, v in split.items()}, "family_calls": calls,
                 "peak_memory_gib": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)}, r)
