@@ -35,36 +35,12 @@ __global__ __launch_bounds__(256) void absmax32_kernel(const float* __restrict__
     cp_amax_commit(slot, m);
 }
 
-__device__ __forceinline__ uint32_t split_dword(float v) {
-    const Split2 s = split2(v, 0.f);
-    return (s.hi & 0xffffu) | (s.lo << 16);
-}
-
 // dst[i] = split(src[i] * 2^e), e from the slot
 __global__ __launch_bounds__(256) void split_kernel(const float* __restrict__ src, uint32_t* __restrict__ dst, size_t n,
                                                     const unsigned* __restrict__ slot) {
     float fwd, inv;
     cp_amax_to_scale(cp_amax_read(slot), &fwd, &inv);
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) dst[i] = split_dword(src[i] * fwd);
-}
-
-// eight split dwords -> the hi and the lo operand of one MFMA (element j = dword j)
-__device__ __forceinline__ void unpack8(const uint32_t (&p)[8], h8& hi, h8& lo) {
-    u32x4 h, l;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        h[k] = __builtin_amdgcn_perm(p[2 * k + 1], p[2 * k], 0x05040100u);
-        l[k] = __builtin_amdgcn_perm(p[2 * k + 1], p[2 * k], 0x07060302u);
-    }
-    hi = __builtin_bit_cast(h8, h);
-    lo = __builtin_bit_cast(h8, l);
-}
-
-// the three products of a block, small terms first (deconv16.hip's order)
-__device__ __forceinline__ f32x16 mma3(const h8& ah, const h8& al, const h8& bh, const h8& bl, f32x16 acc) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc, 0, 0, 0);
 }
 
 template <int NH>

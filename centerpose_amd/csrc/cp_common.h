@@ -445,19 +445,42 @@ int cp_launch_dcn_generic(hipStream_t s, const float* x, const float* w, const f
                           const float* mask, float* out, int B, int C, int H, int W, int Co, int Ho, int Wo, int kh, int kw,
                           int sh, int sw, int ph, int pw, int dh, int dw, int dg);
 
-// ---- DCNv2 backward (dcn_bwd.hip): every shape the forward accepts; NCHW in and out, float32 ----
+// ---- DCNv2 backward (dcn_bwd.hip): every shape the forward accepts; NCHW in and out ----
 struct DcnBwdArgs {
     const float *input, *weight, *offset, *mask, *grad_output;
     float *grad_input, *grad_offset, *grad_mask, *grad_weight, *grad_bias;
     int B, C, H, W, Co, Ho, Wo, kh, kw, sh, sw, ph, pw, dh, dw, dg;
 };
 bool cp_dcn_backward_fast(int C, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int dg);
+// `precision` (CP_PREC_*): CP_PREC_F16X3 runs the two contractions of the fast geometry on the split-binary16 kernels of
+// dcn_bwd16.hip and conv_bwd16.hip; the data side, grad_bias and the generic geometry are float32 in either mode.
+// cp_dcn_backward_prec_mask: bit 0 = the weight gradient, bit 1 = grad_col runs in f16x3 (0 for CP_PREC_F32 and off the fast
+// geometry; the chunk plan is the same on both paths, so the mask does not depend on `deterministic`).
 size_t cp_dcn_backward_ws_bytes(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw, int dh,
-                                int dw, int dg);
-int cp_launch_dcn_backward(hipStream_t s, const DcnBwdArgs& a, void* ws);
+                                int dw, int dg, int precision = 0);
+int cp_launch_dcn_backward(hipStream_t s, const DcnBwdArgs& a, void* ws, int precision = 0);
 // the deterministic form (fast geometry only: the callers check cp_dcn_backward_fast first)
-size_t cp_dcn_backward_det_ws_bytes(int B, int C, int H, int W, int Co);
-int cp_launch_dcn_backward_det(hipStream_t s, const DcnBwdArgs& a, void* ws);
+size_t cp_dcn_backward_det_ws_bytes(int B, int C, int H, int W, int Co, int precision = 0);
+int cp_launch_dcn_backward_det(hipStream_t s, const DcnBwdArgs& a, void* ws, int precision = 0);
+int cp_dcn_backward_prec_mask(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
+                              int dg, int precision);
+// dcn_bwd16.hip: the pieces of the f16x3 mode on the fast geometry.  Slots are |max| slots of one zeroed block.
+//   go_pad    go_t [B HW][CoP] = grad_output [B,Co,HW] transposed, zeros in the pad lanes (CoP % 32 == 0), and its |max|
+//   col16     the modulated deformable im2col of images b0 .. b0 + nb - 1 as split dwords [image][pixel][tap][C], times 2^e of the
+//             bound |max x| * |max mask| (x_amax, m_amax)
+//   wgrad16   slab[s][co][k] (+)= sum over the pixels of slab s of go16[q][co] * col16[q][k], q < Q pixels from the pointers
+//   reduce    grad_weight[co][c][tap] = (the slabs' two-level sum) * 2^-e_g * 2^-e_col
+struct DcnWgrad16Plan {
+    int slab_px, nslab, nh, jobs;
+};
+DcnWgrad16Plan cp_dcn_wgrad16_plan(size_t Q, int C, int CoP);  // Q: the pixels of a full chunk
+int cp_launch_dcn_go_pad(hipStream_t s, const float* go, float* go_t, int B, int Co, int CoP, int HW, unsigned* slot);
+int cp_launch_dcn_col16(hipStream_t s, const float* xh, const float* off, const float* mask, uint32_t* col16, const unsigned* x_amax,
+                        const unsigned* m_amax, int b0, int nb, int C, int H, int W);
+int cp_launch_dcn_wgrad16_slabs(hipStream_t s, const uint32_t* go16, const uint32_t* col16, float* slab, int Q, int C, int CoP,
+                                const DcnWgrad16Plan& P, int accum);
+int cp_launch_dcn_wgrad16_reduce(hipStream_t s, const float* slab, float* gw, int nslab, int Co, int CoP, int C,
+                                 const unsigned* g_amax, const unsigned* x_amax, const unsigned* m_amax);
 
 // ---- prediction-head block backward (heads_bwd.hip): n heads conv3x3 -> ReLU -> conv1x1 on one NHWC feature map ----
 struct PoseHeadsArgs {

@@ -27,9 +27,19 @@
 // pixel-major, every (pixel, tap, corner) is sorted by its destination cell, and each cell sums its own list in a fixed
 // order with plain stores -- grad_input is then bitwise reproducible as well (see "the deterministic input gradient" below
 // and the contract in include/centerpose_hip.h).
+//
+// CP_PREC_F16X3 (cp_dcnv2_backward_prec; fast geometry, both forms): the two contractions run in split binary16 (dcn_bwd16.hip).
+//   1'. go_t becomes [B*Ho*Wo][CoP] with zeroed pad lanes (CoP = Co rounded up to 32), its |max|, |max x| and |max mask| go to
+//       three slots of one block, go16 = split(go_t); wt is packed as the data gradient's operand of the 1x1 convolution 9C -> Co.
+//   2'. per chunk: grad_col[b][pix][k], pixel-major on BOTH forms, = that convolution's stride-1 data gradient
+//       (cp_launch_conv_dgrad16_s1; gcol_kernel<true> where cp_conv_dgrad16_s1_supported refuses the chunk); the halo kernel reads
+//       it through its PM flag; col16 = the chunk's deformable columns as split dwords; the slab kernel adds the chunk's sums.
+//   3'. the slabs' two-level sum times the two inverse scales.  wgrad_kernel does not run.
+// grad_col and col16 of a chunk each follow the 256 MiB rule, so the chunks are the float32 mode's.
 #include "op_common.h"
 #include "igemm_common.h"
 #include "dcn_bwd_det_common.h"
+#include "dcn_bwd_sample.h"
 
 #include <algorithm>
 
@@ -126,35 +136,10 @@ __global__ __launch_bounds__(256) void gcol_kernel(const BwdP p) {
         }
 }
 
-// One sample: position, 1-D weights and corner validity (dcn_v2_im2col_cuda.cu dmcn_im2col_bilinear / the get_*_weight
-// helpers use the same floor / +1 corners and the same in-image tests).
-struct Sample {
-    bool in;          // inside (-1, H) x (-1, W): otherwise it contributes to nothing
-    int y0, x0;       // low corner
-    float lh, lw, hh, hw;
-    bool c1, c2, c3, c4;  // (y0,x0) (y0,x0+1) (y0+1,x0) (y0+1,x0+1) inside the image
-};
-
-__device__ __forceinline__ Sample make_sample(float sy, float sx, int H, int W) {
-    Sample s;
-    s.in = !(sy <= -1.f || sx <= -1.f || sy >= (float)H || sx >= (float)W);
-    const float fy = floorf(sy), fx = floorf(sx);
-    s.y0 = s.in ? (int)fy : -2;
-    s.x0 = s.in ? (int)fx : -2;
-    s.lh = sy - fy;
-    s.lw = sx - fx;
-    s.hh = 1.f - s.lh;
-    s.hw = 1.f - s.lw;
-    s.c1 = s.in && s.y0 >= 0 && s.x0 >= 0;
-    s.c2 = s.in && s.y0 >= 0 && s.x0 + 1 <= W - 1;
-    s.c3 = s.in && s.y0 + 1 <= H - 1 && s.x0 >= 0;
-    s.c4 = s.in && s.y0 + 1 <= H - 1 && s.x0 + 1 <= W - 1;
-    return s;
-}
-
 // fast path: 3x3, stride 1, pad 1, dilation 1, one deformable group, C % CH == 0; x and the input gradient NHWC.
-// 9 waves: wave = tap, lane = pixel of the 16 x 4 patch.
-template <int CH>
+// 9 waves: wave = tap, lane = pixel of the 16 x 4 patch.  PM: grad_col is pixel-major [b][pix][k] (the f16x3 mode's data gradient
+// stores it so): a lane reads its four channels as one 16-byte piece.
+template <int CH, bool PM>
 __global__ __launch_bounds__(576) void dcn_bwd_halo_kernel(const BwdP p) {
     __shared__ float halo[HY * HX * (CH + 1)];  // + 1: cells of one channel fall in different banks
     const int C = p.C, H = p.H, W = p.W, HWo = p.Ho * p.Wo, TC = 9 * C;
@@ -184,7 +169,8 @@ __global__ __launch_bounds__(576) void dcn_bwd_halo_kernel(const BwdP p) {
         gaddr[q] = cv[q] ? (((size_t)b * H + y) * W + x) * C : 0;
     }
     const float* xb = p.xh;
-    const float* gc = p.gcol + ((size_t)bi * TC + (size_t)tap * C) * HWo + pix;
+    const float* gc = PM ? p.gcol + ((size_t)bi * HWo + pix) * TC + (size_t)tap * C
+                         : p.gcol + ((size_t)bi * TC + (size_t)tap * C) * HWo + pix;
     float vh = 0.f, vw = 0.f, mv = 0.f;
     for (int c0 = 0; c0 < C; c0 += CH) {
         for (int e = threadIdx.x; e < HY * HX * (CH + 1); e += 576) halo[e] = 0.f;
@@ -198,9 +184,11 @@ __global__ __launch_bounds__(576) void dcn_bwd_halo_kernel(const BwdP p) {
                 const float4 v4 = cv[3] ? ld4(xb + gaddr[3] + c) : zero4();
                 const float a1[4] = {v1.x, v1.y, v1.z, v1.w}, a2[4] = {v2.x, v2.y, v2.z, v2.w};
                 const float a3[4] = {v3.x, v3.y, v3.z, v3.w}, a4[4] = {v4.x, v4.y, v4.z, v4.w};
+                const float4 g4 = PM ? ld4(gc + c) : zero4();
+                const float ga[4] = {g4.x, g4.y, g4.z, g4.w};
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
-                    const float g = gc[(size_t)(c + u) * HWo];
+                    const float g = PM ? ga[u] : gc[(size_t)(c + u) * HWo];
                     const float cwh = -s.hw * a1[u] - s.lw * a2[u] + s.hw * a3[u] + s.lw * a4[u];
                     const float cww = -s.hh * a1[u] + s.hh * a2[u] - s.lh * a3[u] + s.lh * a4[u];
                     vh += cwh * g * m;
@@ -691,9 +679,13 @@ __global__ __launch_bounds__(256) void dcn_det_long_add_kernel(const BwdP p, con
 struct Plan {
     bool fast;
     int nb, nslab, slab_px;
+    // f16x3 (dcn_bwd16.hip, conv_bwd16.hip): the weight gradient, grad_col; go_t's row length; the weight gradient's slabs
+    bool wg16, dg16;
+    int CoP;
+    DcnWgrad16Plan w16;
 };
 
-Plan plan(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int dg) {
+Plan plan(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int dg, int precision) {
     Plan P;
     const int Ho = (H + 2 * ph - (dh * (kh - 1) + 1)) / sh + 1, Wo = (W + 2 * pw - (dw * (kw - 1) + 1)) / sw + 1;
     const size_t HWo = (size_t)Ho * Wo, TC = (size_t)C * kh * kw, Q = (size_t)B * HWo;
@@ -709,22 +701,42 @@ Plan plan(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, in
     spx = (spx + 1) & ~(size_t)1;
     P.slab_px = (int)spx;
     P.nslab = (int)((Q + spx - 1) / spx);
+    // f16x3: the fast geometry only; a chunk igemm16.hip cannot take as a 1x1 convolution's data gradient keeps gcol_kernel
+    P.wg16 = P.fast && precision == CP_PREC_F16X3;
+    P.CoP = P.wg16 ? (Co + 31) / 32 * 32 : Co;
+    P.w16 = P.wg16 ? cp_dcn_wgrad16_plan((size_t)P.nb * HWo, C, P.CoP) : DcnWgrad16Plan{};
+    P.dg16 = P.wg16 && cp_conv_dgrad16_s1_supported(P.nb, H, W, (int)TC, P.CoP, 1);
     return P;
 }
 
 // xh / gin (the NHWC copies of input and grad_input) exist on the fast path only
 struct Ws {
     float *wt, *go_t, *xh, *gin, *gcol, *slab;
+    // f16x3: the |max| slot block (slot 0: go_t, 1: x, 2: mask), the split copy of go_t, a chunk's split columns, the packed weight
+    unsigned* slot;
+    uint32_t *go16, *col16;
+    void* wB;
 };
 Ws dcn_bwd_carve(Carve& c, const Plan& P, int B, int C, int H, int W, int Co, int Ho, int Wo, int T) {
     const size_t TC = (size_t)C * T, HWo = (size_t)Ho * Wo;
     Ws r;
     r.wt = c.take<float>((size_t)Co * TC * 4);
-    r.go_t = c.take<float>((size_t)B * HWo * Co * 4);
+    r.go_t = c.take<float>((size_t)B * HWo * P.CoP * 4);
     r.xh = P.fast ? c.take<float>((size_t)B * H * W * C * 4) : nullptr;
     r.gin = P.fast ? c.take<float>((size_t)B * H * W * C * 4) : nullptr;
     r.gcol = c.take<float>((size_t)P.nb * TC * HWo * 4);
-    r.slab = c.take<float>((size_t)P.nslab * Co * TC * 4);
+    // (f16x3: never less than the float32 plan's slabs, so that the mode's workspace is never the smaller one)
+    const size_t slab32 = (size_t)P.nslab * Co * TC * 4;
+    r.slab = c.take<float>(P.wg16 ? std::max(slab32, (size_t)P.w16.nslab * P.CoP * TC * 4) : slab32);
+    r.slot = nullptr;
+    r.go16 = r.col16 = nullptr;
+    r.wB = nullptr;
+    if (P.wg16) {  // (nothing is taken in float32: that workspace is the one it always was)
+        r.slot = c.take<unsigned>(cp_amax_slot_bytes);
+        r.go16 = c.take<uint32_t>((size_t)B * HWo * P.CoP * 4);
+        r.col16 = c.take<uint32_t>((size_t)P.nb * TC * HWo * 4);
+        r.wB = c.take<void>(P.dg16 ? cp_conv_dgrad16_pack_bytes((int)TC, P.CoP, 1, 1) : 0);
+    }
     return r;
 }
 
@@ -754,18 +766,22 @@ bool cp_dcn_backward_fast(int C, int kh, int kw, int sh, int sw, int ph, int pw,
 }
 
 size_t cp_dcn_backward_ws_bytes(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw, int dh,
-                                int dw, int dg) {
+                                int dw, int dg, int precision) {
     const int Ho = (H + 2 * ph - (dh * (kh - 1) + 1)) / sh + 1, Wo = (W + 2 * pw - (dw * (kw - 1) + 1)) / sw + 1;
     Carve c{nullptr};
-    dcn_bwd_carve(c, plan(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, dg), B, C, H, W, Co, Ho, Wo, kh * kw);
+    dcn_bwd_carve(c, plan(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, dg, precision), B, C, H, W, Co, Ho, Wo, kh * kw);
     return c.off;
 }
 
-int cp_launch_dcn_backward(hipStream_t s, const DcnBwdArgs& a, void* ws) {
-    const Plan P = plan(a.B, a.C, a.H, a.W, a.Co, a.kh, a.kw, a.sh, a.sw, a.ph, a.pw, a.dh, a.dw, a.dg);
-    const int T = a.kh * a.kw, TC = a.C * T;
-    Carve cv{(char*)ws};
-    const Ws r = dcn_bwd_carve(cv, P, a.B, a.C, a.H, a.W, a.Co, a.Ho, a.Wo, T);
+int cp_dcn_backward_prec_mask(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
+                              int dg, int precision) {
+    const Plan P = plan(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, dg, precision);
+    return (P.wg16 ? 1 : 0) | (P.dg16 ? 2 : 0);
+}
+
+namespace {
+
+BwdP bwd_params(const DcnBwdArgs& a, const Plan& P, const Ws& r) {
     BwdP p;
     p.x = a.input;
     p.xh = r.xh;
@@ -781,31 +797,112 @@ int cp_launch_dcn_backward(hipStream_t s, const DcnBwdArgs& a, void* ws) {
     p.slab = r.slab;
     p.B = a.B, p.C = a.C, p.H = a.H, p.W = a.W, p.Co = a.Co, p.Ho = a.Ho, p.Wo = a.Wo;
     p.kh = a.kh, p.kw = a.kw, p.sh = a.sh, p.sw = a.sw, p.ph = a.ph, p.pw = a.pw, p.dh = a.dh, p.dw = a.dw, p.dg = a.dg;
-    p.nb = P.nb, p.slab_px = P.slab_px, p.nslab = P.nslab;
+    p.b0 = 0, p.nb = P.nb, p.slab_px = P.slab_px, p.nslab = P.nslab;
+    return p;
+}
+
+// step 1: wt, go_t, and on the fast path x staged NHWC.  f16x3 (step 1'): go_t padded with its |max|, the |max| of x and of the
+// mask, the split copy of go_t and the packed weight.
+int stage(hipStream_t s, const DcnBwdArgs& a, const Plan& P, const Ws& r) {
+    const int T = a.kh * a.kw, HWo = a.Ho * a.Wo;
+    hipLaunchKernelGGL(wt_kernel, dim3(256), dim3(256), 0, s, a.weight, r.wt, a.Co, a.C, T);
+    if (!launch_ok()) return CP_ERR_LAUNCH;
+    int rc;
+    if (P.wg16) {
+        if (hipMemsetAsync(r.slot, 0, cp_amax_slot_bytes, s) != hipSuccess) return CP_ERR_LAUNCH;
+        rc = cp_launch_dcn_go_pad(s, a.grad_output, r.go_t, a.B, a.Co, P.CoP, HWo, r.slot);
+    } else {
+        rc = cp_launch_nchw_to_nhwc(a.grad_output, r.go_t, a.B, a.Co, a.Ho, a.Wo, a.Co, s);
+    }
+    if (rc != CP_OK) return rc;
+    if (P.fast) {
+        rc = cp_launch_nchw_to_nhwc(a.input, r.xh, a.B, a.C, a.H, a.W, a.C, s);
+        if (rc != CP_OK) return rc;
+    }
+    if (!P.wg16) return CP_OK;
+    rc = cp_launch_absmax32(a.input, (size_t)a.B * a.C * a.H * a.W, r.slot + 1, s);
+    if (rc == CP_OK) rc = cp_launch_absmax32(a.mask, (size_t)a.B * 9 * HWo, r.slot + 2, s);
+    if (rc == CP_OK) rc = cp_launch_split16(r.go_t, r.go16, (size_t)a.B * HWo * P.CoP, r.slot, s);
+    if (rc == CP_OK && P.dg16) rc = cp_launch_conv_dgrad16_pack(s, r.wt, r.wB, 9 * a.C, a.Co, P.CoP, 1, 1);
+    return rc;
+}
+
+// f16x3, per chunk (p.b0, p.nb): grad_col pixel-major, the chunk's split columns and their sums into the slabs
+int chunk16(hipStream_t s, const DcnBwdArgs& a, const Plan& P, const Ws& r, const BwdP& p) {
+    const int TC = 9 * a.C, HW = a.H * a.W;
+    const float* go_t = r.go_t + (size_t)p.b0 * HW * P.CoP;
+    if (P.dg16) {
+        // the 1x1 convolution 9C -> Co on the chunk's pixels: its data gradient from gs = go_t, w = wt [Co][9C][1]
+        const ConvBwdArgs ca{nullptr, nullptr, nullptr, nullptr, r.gcol, nullptr, nullptr, p.nb, a.H, a.W, TC, a.Co, 1, 1, 1, 0};
+        const int rc = cp_launch_conv_dgrad16_s1(s, ca, go_t, P.CoP, r.wB, nullptr, r.slot);
+        if (rc != CP_OK) return rc;
+    } else {
+        hipLaunchKernelGGL(gcol_kernel<true>, dim3((HW + 127) / 128, (TC + 127) / 128, p.nb), dim3(256), 0, s, p);
+        if (!launch_ok()) return CP_ERR_LAUNCH;
+    }
+    int rc = cp_launch_dcn_col16(s, r.xh, a.offset, a.mask, r.col16, r.slot + 1, r.slot + 2, p.b0, p.nb, a.C, a.H, a.W);
+    if (rc != CP_OK) return rc;
+    return cp_launch_dcn_wgrad16_slabs(s, r.go16 + (size_t)p.b0 * HW * P.CoP, r.col16, r.slab, p.nb * HW, a.C, P.CoP, P.w16, p.b0 > 0);
+}
+
+// step 3 (p.b0 = 0, p.nb = P.nb): grad_weight from the slabs -- f16x3: the chunks have filled them -- and grad_bias
+int weight_bias(hipStream_t s, const DcnBwdArgs& a, const Plan& P, const Ws& r, const BwdP& p) {
+    const int T = a.kh * a.kw, TC = a.C * T;
+    if (P.wg16) {
+        const int rc = cp_launch_dcn_wgrad16_reduce(s, r.slab, a.grad_weight, P.w16.nslab, a.Co, P.CoP, a.C, r.slot, r.slot + 1, r.slot + 2);
+        if (rc != CP_OK) return rc;
+    } else {
+        const dim3 wg_grid((TC + 127) / 128, 1, P.nslab);
+        if (a.Co <= 32)
+            hipLaunchKernelGGL(wgrad_kernel<1>, wg_grid, dim3(256), 0, s, p);
+        else if (a.Co <= 64)
+            hipLaunchKernelGGL(wgrad_kernel<2>, wg_grid, dim3(256), 0, s, p);
+        else
+            hipLaunchKernelGGL(wgrad_kernel<WG_COUT>, dim3(wg_grid.x, (a.Co + 32 * WG_COUT - 1) / (32 * WG_COUT), P.nslab),
+                               dim3(256), 0, s, p);
+        if (!launch_ok()) return CP_ERR_LAUNCH;
+        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(1024), dim3(256), 0, s, (const float*)p.slab, a.grad_weight, P.nslab, a.Co,
+                           a.C, T);
+        if (!launch_ok()) return CP_ERR_LAUNCH;
+    }
+    return cp_launch_rowsum_nchw(a.grad_output, a.grad_bias, a.B, a.Co, a.Ho * a.Wo, s);
+}
+
+}  // namespace
+
+int cp_launch_dcn_backward(hipStream_t s, const DcnBwdArgs& a, void* ws, int precision) {
+    const Plan P = plan(a.B, a.C, a.H, a.W, a.Co, a.kh, a.kw, a.sh, a.sw, a.ph, a.pw, a.dh, a.dw, a.dg, precision);
+    const int T = a.kh * a.kw, TC = a.C * T;
+    Carve cv{(char*)ws};
+    const Ws r = dcn_bwd_carve(cv, P, a.B, a.C, a.H, a.W, a.Co, a.Ho, a.Wo, T);
+    BwdP p = bwd_params(a, P, r);
     const int HWo = a.Ho * a.Wo;
     const size_t in_bytes = (size_t)a.B * a.C * a.H * a.W * 4;
 
-    hipLaunchKernelGGL(wt_kernel, dim3(256), dim3(256), 0, s, a.weight, (float*)p.wt, a.Co, a.C, T);
-    if (!launch_ok()) return CP_ERR_LAUNCH;
-    int rc = cp_launch_nchw_to_nhwc(a.grad_output, (float*)p.go_t, a.B, a.Co, a.Ho, a.Wo, a.Co, s);
+    int rc = stage(s, a, P, r);
     if (rc != CP_OK) return rc;
-    if (P.fast) {
-        rc = cp_launch_nchw_to_nhwc(a.input, (float*)p.xh, a.B, a.C, a.H, a.W, a.C, s);
-        if (rc != CP_OK) return rc;
-    }
     if (hipMemsetAsync(p.gin, 0, in_bytes, s) != hipSuccess) return CP_ERR_LAUNCH;
 
     for (int b0 = 0; b0 < a.B; b0 += P.nb) {
         p.b0 = b0;
         p.nb = std::min(P.nb, a.B - b0);
-        hipLaunchKernelGGL(gcol_kernel<false>, dim3((HWo + 127) / 128, (TC + 127) / 128, p.nb), dim3(256), 0, s, p);
-        if (!launch_ok()) return CP_ERR_LAUNCH;
+        if (P.wg16) {
+            rc = chunk16(s, a, P, r, p);
+            if (rc != CP_OK) return rc;
+        } else {
+            hipLaunchKernelGGL(gcol_kernel<false>, dim3((HWo + 127) / 128, (TC + 127) / 128, p.nb), dim3(256), 0, s, p);
+            if (!launch_ok()) return CP_ERR_LAUNCH;
+        }
         if (P.fast) {
             const dim3 grid((a.Wo + PT_X - 1) / PT_X, (a.Ho + PT_Y - 1) / PT_Y, p.nb);
-            if (a.C % 32 == 0)
-                hipLaunchKernelGGL(dcn_bwd_halo_kernel<32>, grid, dim3(576), 0, s, p);
+            if (a.C % 32 == 0 && P.wg16)
+                hipLaunchKernelGGL((dcn_bwd_halo_kernel<32, true>), grid, dim3(576), 0, s, p);
+            else if (P.wg16)
+                hipLaunchKernelGGL((dcn_bwd_halo_kernel<16, true>), grid, dim3(576), 0, s, p);
+            else if (a.C % 32 == 0)
+                hipLaunchKernelGGL((dcn_bwd_halo_kernel<32, false>), grid, dim3(576), 0, s, p);
             else
-                hipLaunchKernelGGL(dcn_bwd_halo_kernel<16>, grid, dim3(576), 0, s, p);
+                hipLaunchKernelGGL((dcn_bwd_halo_kernel<16, false>), grid, dim3(576), 0, s, p);
         } else {
             const size_t n = (size_t)p.nb * a.dg * T * HWo;
             const size_t blocks = std::min<size_t>((n + 255) / 256, 65536);
@@ -815,27 +912,15 @@ int cp_launch_dcn_backward(hipStream_t s, const DcnBwdArgs& a, void* ws) {
     }
     p.b0 = 0;
     p.nb = P.nb;
-    const dim3 wg_grid((TC + 127) / 128, 1, P.nslab);
-    if (a.Co <= 32)
-        hipLaunchKernelGGL(wgrad_kernel<1>, wg_grid, dim3(256), 0, s, p);
-    else if (a.Co <= 64)
-        hipLaunchKernelGGL(wgrad_kernel<2>, wg_grid, dim3(256), 0, s, p);
-    else
-        hipLaunchKernelGGL(wgrad_kernel<WG_COUT>, dim3(wg_grid.x, (a.Co + 32 * WG_COUT - 1) / (32 * WG_COUT), P.nslab),
-                           dim3(256), 0, s, p);
-    if (!launch_ok()) return CP_ERR_LAUNCH;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(1024), dim3(256), 0, s, (const float*)p.slab, a.grad_weight, P.nslab, a.Co,
-                       a.C, T);
-    if (!launch_ok()) return CP_ERR_LAUNCH;
-    rc = cp_launch_rowsum_nchw(a.grad_output, a.grad_bias, a.B, a.Co, HWo, s);
+    rc = weight_bias(s, a, P, r, p);
     if (rc != CP_OK) return rc;
     if (P.fast) return cp_launch_nhwc_to_nchw(p.gin, a.grad_input, a.B, a.C, a.H, a.W, a.C, s);
     return CP_OK;
 }
 
-size_t cp_dcn_backward_det_ws_bytes(int B, int C, int H, int W, int Co) {
+size_t cp_dcn_backward_det_ws_bytes(int B, int C, int H, int W, int Co, int precision) {
     Carve c{nullptr};
-    const Plan P = plan(B, C, H, W, Co, 3, 3, 1, 1, 1, 1, 1, 1, 1);
+    const Plan P = plan(B, C, H, W, Co, 3, 3, 1, 1, 1, 1, 1, 1, 1, precision);
     dcn_bwd_carve(c, P, B, C, H, W, Co, H, W, 9);
     dcn_det_carve(c, P, C, H, W);
     return c.off;
@@ -843,34 +928,15 @@ size_t cp_dcn_backward_det_ws_bytes(int B, int C, int H, int W, int Co) {
 
 // The launch sequence of cp_launch_dcn_backward on the fast geometry with the data kernel replaced: pixel-major grad_col,
 // the coord kernel, the index, its sort and the gather; no memset of the input gradient (the gather stores every line).
-int cp_launch_dcn_backward_det(hipStream_t s, const DcnBwdArgs& a, void* ws) {
-    const Plan P = plan(a.B, a.C, a.H, a.W, a.Co, 3, 3, 1, 1, 1, 1, 1, 1, 1);
+int cp_launch_dcn_backward_det(hipStream_t s, const DcnBwdArgs& a, void* ws, int precision) {
+    const Plan P = plan(a.B, a.C, a.H, a.W, a.Co, 3, 3, 1, 1, 1, 1, 1, 1, 1, precision);
     const int T = 9, TC = a.C * T, HW = a.H * a.W;
     Carve cv{(char*)ws};
     const Ws r = dcn_bwd_carve(cv, P, a.B, a.C, a.H, a.W, a.Co, a.Ho, a.Wo, T);
     const DetWs dw = dcn_det_carve(cv, P, a.C, a.H, a.W);
-    BwdP p;
-    p.x = a.input;
-    p.xh = r.xh;
-    p.wt = r.wt;
-    p.off = a.offset;
-    p.mask = a.mask;
-    p.go = a.grad_output;
-    p.go_t = r.go_t;
-    p.gcol = r.gcol;
-    p.gin = r.gin;
-    p.goff = a.grad_offset;
-    p.gmask = a.grad_mask;
-    p.slab = r.slab;
-    p.B = a.B, p.C = a.C, p.H = a.H, p.W = a.W, p.Co = a.Co, p.Ho = a.Ho, p.Wo = a.Wo;
-    p.kh = a.kh, p.kw = a.kw, p.sh = a.sh, p.sw = a.sw, p.ph = a.ph, p.pw = a.pw, p.dh = a.dh, p.dw = a.dw, p.dg = a.dg;
-    p.nb = P.nb, p.slab_px = P.slab_px, p.nslab = P.nslab;
+    BwdP p = bwd_params(a, P, r);
 
-    hipLaunchKernelGGL(wt_kernel, dim3(256), dim3(256), 0, s, a.weight, (float*)p.wt, a.Co, a.C, T);
-    if (!launch_ok()) return CP_ERR_LAUNCH;
-    int rc = cp_launch_nchw_to_nhwc(a.grad_output, (float*)p.go_t, a.B, a.Co, a.Ho, a.Wo, a.Co, s);
-    if (rc != CP_OK) return rc;
-    rc = cp_launch_nchw_to_nhwc(a.input, (float*)p.xh, a.B, a.C, a.H, a.W, a.C, s);
+    int rc = stage(s, a, P, r);
     if (rc != CP_OK) return rc;
 
     int L = 4;  // lanes per destination cell: the power of two that covers C / 4 float4 pieces, 64 at most
@@ -880,8 +946,13 @@ int cp_launch_dcn_backward_det(hipStream_t s, const DcnBwdArgs& a, void* ws) {
         p.nb = std::min(P.nb, a.B - b0);
         const uint32_t cells = (uint32_t)p.nb * HW, n = cells * 36u, ntiles = (n + RS_TILE - 1) / RS_TILE;
         const unsigned tap_blocks = (cells * 9u + 255u) / 256u;
-        hipLaunchKernelGGL(gcol_kernel<true>, dim3((HW + 127) / 128, (TC + 127) / 128, p.nb), dim3(256), 0, s, p);
-        if (!launch_ok()) return CP_ERR_LAUNCH;
+        if (P.wg16) {
+            rc = chunk16(s, a, P, r, p);
+            if (rc != CP_OK) return rc;
+        } else {
+            hipLaunchKernelGGL(gcol_kernel<true>, dim3((HW + 127) / 128, (TC + 127) / 128, p.nb), dim3(256), 0, s, p);
+            if (!launch_ok()) return CP_ERR_LAUNCH;
+        }
         hipLaunchKernelGGL(dcn_det_coord_kernel, dim3(tap_blocks), dim3(256), 0, s, p);
         if (!launch_ok()) return CP_ERR_LAUNCH;
         hipLaunchKernelGGL(dcn_det_index_kernel, dim3(tap_blocks), dim3(256), 0, s, p, dw.keys[0], dw.ids[0], cells);
@@ -913,19 +984,7 @@ int cp_launch_dcn_backward_det(hipStream_t s, const DcnBwdArgs& a, void* ws) {
     }
     p.b0 = 0;
     p.nb = P.nb;
-    const dim3 wg_grid((TC + 127) / 128, 1, P.nslab);
-    if (a.Co <= 32)
-        hipLaunchKernelGGL(wgrad_kernel<1>, wg_grid, dim3(256), 0, s, p);
-    else if (a.Co <= 64)
-        hipLaunchKernelGGL(wgrad_kernel<2>, wg_grid, dim3(256), 0, s, p);
-    else
-        hipLaunchKernelGGL(wgrad_kernel<WG_COUT>, dim3(wg_grid.x, (a.Co + 32 * WG_COUT - 1) / (32 * WG_COUT), P.nslab),
-                           dim3(256), 0, s, p);
-    if (!launch_ok()) return CP_ERR_LAUNCH;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(1024), dim3(256), 0, s, (const float*)p.slab, a.grad_weight, P.nslab, a.Co,
-                       a.C, T);
-    if (!launch_ok()) return CP_ERR_LAUNCH;
-    rc = cp_launch_rowsum_nchw(a.grad_output, a.grad_bias, a.B, a.Co, HW, s);
+    rc = weight_bias(s, a, P, r, p);
     if (rc != CP_OK) return rc;
     return cp_launch_nhwc_to_nchw(p.gin, a.grad_input, a.B, a.C, a.H, a.W, a.C, s);
 }

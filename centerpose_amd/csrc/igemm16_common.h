@@ -57,4 +57,30 @@ __device__ __forceinline__ Split2 split2(float a, float b) {
     return s;
 }
 
+// ---- the split-dword operand form of the training kernels (conv_bwd16.hip, dcn_bwd16.hip): one dword per element, binary16
+// hi in the low half and lo in the high half ----
+__device__ __forceinline__ uint32_t split_dword(float v) {
+    const Split2 s = split2(v, 0.f);
+    return (s.hi & 0xffffu) | (s.lo << 16);
+}
+
+// eight split dwords -> the hi and the lo operand of one MFMA (element j = dword j)
+__device__ __forceinline__ void unpack8(const uint32_t (&p)[8], h8& hi, h8& lo) {
+    u32x4 h, l;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        h[k] = __builtin_amdgcn_perm(p[2 * k + 1], p[2 * k], 0x05040100u);
+        l[k] = __builtin_amdgcn_perm(p[2 * k + 1], p[2 * k], 0x07060302u);
+    }
+    hi = __builtin_bit_cast(h8, h);
+    lo = __builtin_bit_cast(h8, l);
+}
+
+// the three products of a block, small terms first (deconv16.hip's order)
+__device__ __forceinline__ f32x16 mma3(const h8& ah, const h8& al, const h8& bh, const h8& bl, f32x16 acc) {
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc, 0, 0, 0);
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc, 0, 0, 0);
+}
+
 }  // namespace

@@ -1,6 +1,6 @@
 // The stand-alone operators of the C ABI (include/centerpose_hip.h): single layers on caller tensors, outside any cp_model
 // -- cp_conv2d_nhwc / cp_conv2d_backward_nhwc / cp_conv2d_backward_prec_nhwc, cp_batchnorm_forward_nhwc / _backward_nhwc, cp_conv_transpose2d_nhwc,
-// cp_conv_transpose2d_dw_nhwc / cp_conv_transpose2d_backward_nhwc, cp_dcnv2_forward / cp_dcnv2_backward / cp_dcnv2_backward_det, cp_pose_heads_forward / _backward / _backward_prec,
+// cp_conv_transpose2d_dw_nhwc / cp_conv_transpose2d_backward_nhwc, cp_dcnv2_forward / cp_dcnv2_backward / cp_dcnv2_backward_det / cp_dcnv2_backward_prec, cp_pose_heads_forward / _backward / _backward_prec,
 // cp_maxpool2d_forward_nhwc / _backward_nhwc, cp_upsample2_add_nhwc / cp_upsample2_add_backward_nhwc (large_hourglass.py:95-112),
 // cp_conv2d_stem_backward / cp_conv2d_stem_wide_backward, cp_groupnorm_forward_nhwc / _backward_nhwc,
 // cp_gru_gate_forward / _backward, cp_adam_table_bytes / _table_build / _step, cp_grad_flat_elems / _flat_offsets / _pack_table_bytes / _pack_table_build / _pack.
@@ -941,6 +941,65 @@ int cp_dcnv2_backward_det(cp_stream_t stream, const float* input, const float* w
                  B, C, H, W, Co, Ho, Wo, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group};
     const int rc = cp_launch_dcn_backward_det((hipStream_t)stream, a, workspace);
     return rc == CP_OK ? CP_OK : fail(rc, "dcn_v2_backward_det: kernel launch failed");
+}
+
+// The two calls above with a precision argument: CP_PREC_F32 is the call without it
+static const char* dcn_bwd_prec_error(int precision) {
+    return precision == CP_PREC_F32 || precision == CP_PREC_F16X3 ? nullptr
+                                                                  : "dcn_v2_backward: unknown precision (CP_PREC_F32 or CP_PREC_F16X3)";
+}
+
+int cp_dcnv2_backward_prec_mask(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
+                                int deformable_group, int deterministic, int precision) {
+    int Ho = 0, Wo = 0;
+    if (const char* e = dcn_bwd_shape_error(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group, &Ho, &Wo))
+        return fail(CP_ERR_INVALID, e);
+    if (const char* e = dcn_bwd_prec_error(precision)) return fail(CP_ERR_INVALID, e);
+    if (deterministic) {
+        const std::string ge = dcn_bwd_det_geometry_error(C, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group);
+        if (!ge.empty()) return fail(CP_ERR_INVALID, ge);
+    }
+    return cp_dcn_backward_prec_mask(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group, precision);
+}
+
+size_t cp_dcnv2_backward_prec_workspace_bytes(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw,
+                                              int dh, int dw, int deformable_group, int deterministic, int precision) {
+    int Ho = 0, Wo = 0;
+    if (dcn_bwd_shape_error(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group, &Ho, &Wo)) return 0;
+    if (const char* e = dcn_bwd_prec_error(precision)) {
+        fail(CP_ERR_INVALID, e);
+        return 0;
+    }
+    if (!deterministic) return cp_dcn_backward_ws_bytes(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group, precision);
+    if (!cp_dcn_backward_fast(C, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group)) return 0;
+    return cp_dcn_backward_det_ws_bytes(B, C, H, W, Co, precision);
+}
+
+int cp_dcnv2_backward_prec(cp_stream_t stream, const float* input, const float* weight, const float* offset, const float* mask,
+                           const float* grad_output, float* grad_input, float* grad_offset, float* grad_mask, float* grad_weight,
+                           float* grad_bias, int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw,
+                           int dh, int dw, int deformable_group, int deterministic, int precision, void* workspace,
+                           size_t workspace_bytes) {
+    int Ho = 0, Wo = 0;
+    if (const char* e = dcn_bwd_shape_error(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group, &Ho, &Wo))
+        return fail(CP_ERR_INVALID, e);
+    if (const char* e = dcn_bwd_prec_error(precision)) return fail(CP_ERR_INVALID, e);
+    if (deterministic) {
+        const std::string ge = dcn_bwd_det_geometry_error(C, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group);
+        if (!ge.empty()) return fail(CP_ERR_INVALID, ge);
+    }
+    const char* name = deterministic ? "dcn_v2_backward_det" : "dcn_v2_backward";
+    if (!input || !weight || !offset || !mask || !grad_output || !grad_input || !grad_offset || !grad_mask || !grad_weight ||
+        !grad_bias || !workspace)
+        return fail(CP_ERR_INVALID, std::string(name) + ": null argument");
+    const size_t need = deterministic ? cp_dcn_backward_det_ws_bytes(B, C, H, W, Co, precision)
+                                      : cp_dcn_backward_ws_bytes(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group, precision);
+    if (workspace_bytes < need) return fail(CP_ERR_INVALID, std::string(name) + ": workspace too small");
+    DcnBwdArgs a{input, weight, offset, mask, grad_output, grad_input, grad_offset, grad_mask, grad_weight, grad_bias,
+                 B, C, H, W, Co, Ho, Wo, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group};
+    const int rc = deterministic ? cp_launch_dcn_backward_det((hipStream_t)stream, a, workspace, precision)
+                                 : cp_launch_dcn_backward((hipStream_t)stream, a, workspace, precision);
+    return rc == CP_OK ? CP_OK : fail(rc, std::string(name) + ": kernel launch failed");
 }
 
 // DCNv2 forward with the reference's NCHW layouts (see header)

@@ -38,6 +38,9 @@ SIGNATURES = {
     "cp_dcnv2_backward": (c_int, _vp * 11 + _i * 14 + _ws),
     "cp_dcnv2_backward_det_workspace_bytes": (c_size_t, _i * 14),
     "cp_dcnv2_backward_det": (c_int, _vp * 11 + _i * 14 + _ws),
+    "cp_dcnv2_backward_prec_workspace_bytes": (c_size_t, _i * 16),
+    "cp_dcnv2_backward_prec": (c_int, _vp * 11 + _i * 16 + _ws),
+    "cp_dcnv2_backward_prec_mask": (c_int, _i * 16),
     "cp_pose_heads_chunk_images": (c_int, _i * 4),
     "cp_pose_heads_forward_workspace_bytes": (c_size_t, _i * 6 + _pi),
     "cp_pose_heads_backward_workspace_bytes": (c_size_t, _i * 6 + _pi),

@@ -71,15 +71,36 @@ def resolve_deterministic(requested, fast, own_flag, torch_flag, torch_warn_only
                        "turn off hip.set_deterministic / torch.use_deterministic_algorithms." % (what or "this geometry"))
 
 
+def _dcn_bwd_precision(name):
+    if name not in _abi.PRECISIONS:
+        raise ValueError("dcn_v2_backward: precision must be one of %s, got %r" % (sorted(_abi.PRECISIONS), name))
+    return _abi.PRECISIONS[name]
+
+
+def dcn_backward_precision_mask(B, C, H, W, Co, kh=3, kw=3, sh=1, sw=1, ph=1, pw=1, dh=1, dw=1, deformable_group=1,
+                                deterministic=False, precision="f16x3"):
+    """What ``dcn_v2_backward(..., precision=precision)`` runs in f16x3 for a shape (cp_dcnv2_backward_prec_mask; host
+    arithmetic, no device): bit 0 = the weight gradient, bit 1 = grad_col.  0 for "f32" and outside the fast geometry."""
+    rc = _abi.lib().cp_dcnv2_backward_prec_mask(*map(int, (B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group)),
+                                                int(bool(deterministic)), _dcn_bwd_precision(precision))
+    if rc < 0:
+        _abi._refuse("dcn_backward_precision_mask")
+    return rc
+
+
 def dcn_v2_backward(input, weight, bias, offset, mask, grad_output, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group,
-                    workspace=None, deterministic=None):
+                    workspace=None, deterministic=None, precision="f32"):
     """Same 15-argument signature as the reference's ``_ext.dcn_v2_backward`` (DCNv2/src/vision.cpp:6, dcn_v2.h:48-80):
     returns [grad_input, grad_offset, grad_mask, grad_weight, grad_bias], float32 on the input's device.  ``workspace`` (a
     uint8 device tensor of at least the queried size) may be passed to skip the allocation; a smaller one is an error.
     ``deterministic``: True runs cp_dcnv2_backward_det (grad_input summed in a fixed order, no float atomics: all five
     gradients bitwise reproducible; a larger workspace), False cp_dcnv2_backward, None (default) resolves at call time to
-    ``hip.deterministic() or torch.are_deterministic_algorithms_enabled()`` -- see resolve_deterministic."""
+    ``hip.deterministic() or torch.are_deterministic_algorithms_enabled()`` -- see resolve_deterministic.
+    ``precision``: "f32" (the two calls above, bit for bit) or "f16x3": on the fast geometry, with either ``deterministic``
+    value, the weight gradient and grad_col run in split binary16 (cp_dcnv2_backward_prec; ``dcn_backward_precision_mask``
+    tells what a shape gets); any other geometry runs float32."""
     global _warned_nondeterministic
+    prec = _dcn_bwd_precision(precision)
     L = _abi.lib()
     input, weight, bias, offset, mask, grad_output = map(_abi._dev, (input, weight, bias, offset, mask, grad_output))
     B, C, H, W = input.shape
@@ -102,14 +123,26 @@ def dcn_v2_backward(input, weight, bias, offset, mask, grad_output, kh, kw, sh, 
         _warned_nondeterministic = True
         warnings.warn("dcn_v2_backward has no deterministic implementation for this geometry; running the float-atomic path "
                       "(torch.use_deterministic_algorithms(True, warn_only=True))")
-    query, call = ((L.cp_dcnv2_backward_det_workspace_bytes, L.cp_dcnv2_backward_det) if det else
-                   (L.cp_dcnv2_backward_workspace_bytes, L.cp_dcnv2_backward))
     grads = [torch.empty_like(t) for t in (input, offset, mask, weight, bias)]
-    workspace = _abi._workspace(query(B, C, H, W, Co, *geo), input.device, "dcn_v2_backward", last_error=False, given=workspace)
-    rc = call(_abi._stream(), *_abi._ptrs(input, weight, offset, mask, grad_output, *grads), B, C, H, W, Co, *geo,
+    if prec == _abi.PRECISIONS["f32"]:
+        query, call = ((L.cp_dcnv2_backward_det_workspace_bytes, L.cp_dcnv2_backward_det) if det else
+                       (L.cp_dcnv2_backward_workspace_bytes, L.cp_dcnv2_backward))
+        tail = ()
+    else:
+        query, call, tail = L.cp_dcnv2_backward_prec_workspace_bytes, L.cp_dcnv2_backward_prec, (int(det), prec)
+    workspace = _abi._workspace(query(B, C, H, W, Co, *geo, *tail), input.device, "dcn_v2_backward", last_error=False, given=workspace)
+    rc = call(_abi._stream(), *_abi._ptrs(input, weight, offset, mask, grad_output, *grads), B, C, H, W, Co, *geo, *tail,
               _abi._ptr(workspace), workspace.numel() * workspace.element_size())
-    _abi._check(rc, "cp_dcnv2_backward_det" if det else "cp_dcnv2_backward")
+    _abi._check(rc, "cp_dcnv2_backward_prec" if tail else "cp_dcnv2_backward_det" if det else "cp_dcnv2_backward")
     return grads
+
+
+def dcn_v2_backward_f32(input, weight, bias, offset, mask, grad_output, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group,
+                        workspace=None, deterministic=None):
+    """``dcn_v2_backward`` without the ``precision`` argument: what the package exports as ``hip.dcn_v2_backward`` (its
+    recorded signature); ``hip.ops.dcn_v2_backward`` is the operator with the argument."""
+    return dcn_v2_backward(input, weight, bias, offset, mask, grad_output, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group,
+                           workspace=workspace, deterministic=deterministic, precision="f32")
 
 
 def _heads_args(feat, params):

@@ -23,6 +23,16 @@ def dcn_v2_backward(input, weight, bias, offset, mask, grad_output, kernel_h, ke
                                 pad_h, pad_w, dilation_h, dilation_w, deformable_group)
 
 
+def dcn_v2_backward_prec(input, weight, bias, offset, mask, grad_output, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w,
+                         dilation_h, dilation_w, deformable_group, *, precision="f32"):
+    """Not the reference's: ``dcn_v2_backward`` with the arithmetic of its two contractions as a keyword, "f32" or "f16x3"
+    (``hip.ops.dcn_v2_backward``).  ``dcn_v2_backward`` itself keeps the reference's 15 arguments."""
+    if not input.is_cuda:
+        raise RuntimeError("Not compiled with CPU support: centerpose_hip runs on the HIP device only")
+    return _hip.ops.dcn_v2_backward(input, weight, bias, offset, mask, grad_output, kernel_h, kernel_w, stride_h, stride_w,
+                                    pad_h, pad_w, dilation_h, dilation_w, deformable_group, precision=precision)
+
+
 def _not_built(*args, **kwargs):
     raise RuntimeError("centerpose_hip: PS-ROI pooling is not built (CenterPose does not use it)")
 

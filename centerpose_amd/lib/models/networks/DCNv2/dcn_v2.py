@@ -11,9 +11,17 @@ from torch import nn
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
+from centerpose_amd import hip as _hip
+
 from . import _ext
 
 _Geometry = collections.namedtuple("_Geometry", "kernel stride pad dilation groups")
+
+
+def _precision_name(name):
+    if name not in _hip.PRECISIONS:
+        raise ValueError("backward_precision must be one of %s, got %r" % (sorted(_hip.PRECISIONS), name))
+    return name
 
 
 def _two(v):
@@ -25,7 +33,8 @@ class _DCNv2(Function):
     the same values, as a call outside grad mode), backward through ``_ext.dcn_v2_backward``."""
 
     @staticmethod
-    def forward(ctx, input, offset, mask, weight, bias, stride, padding, dilation, deformable_groups):
+    def forward(ctx, input, offset, mask, weight, bias, stride, padding, dilation, deformable_groups, backward_precision="f32"):
+        ctx.backward_precision = _precision_name(backward_precision)
         ctx.stride, ctx.padding, ctx.dilation = _two(stride), _two(padding), _two(dilation)
         ctx.kernel_size = _two(weight.shape[2:4])
         ctx.deformable_groups = int(deformable_groups)
@@ -39,17 +48,25 @@ class _DCNv2(Function):
     @once_differentiable
     def backward(ctx, grad_output):
         input, offset, mask, weight, bias = ctx.saved_tensors
-        grad_input, grad_offset, grad_mask, grad_weight, grad_bias = _ext.dcn_v2_backward(
-            input, weight, bias, offset, mask, grad_output, ctx.kernel_size[0], ctx.kernel_size[1], ctx.stride[0],
-            ctx.stride[1], ctx.padding[0], ctx.padding[1], ctx.dilation[0], ctx.dilation[1], ctx.deformable_groups)
-        return grad_input, grad_offset, grad_mask, grad_weight, grad_bias, None, None, None, None
+        args = (input, weight, bias, offset, mask, grad_output, ctx.kernel_size[0], ctx.kernel_size[1], ctx.stride[0],
+                ctx.stride[1], ctx.padding[0], ctx.padding[1], ctx.dilation[0], ctx.dilation[1], ctx.deformable_groups)
+        if ctx.backward_precision == "f32":
+            grads = _ext.dcn_v2_backward(*args)
+        else:
+            grads = _ext.dcn_v2_backward_prec(*args, precision=ctx.backward_precision)
+        grad_input, grad_offset, grad_mask, grad_weight, grad_bias = grads
+        # (one None per non-tensor argument; autograd drops the last where backward_precision was not passed)
+        return grad_input, grad_offset, grad_mask, grad_weight, grad_bias, None, None, None, None, None
 
 
+# the reference's nine arguments (dcn_v2.py:54), and an optional tenth: backward_precision
 dcn_v2_conv = _DCNv2.apply
 
 
 class DCNv2(nn.Module):
-    """Modulated deformable convolution whose offsets and masks are inputs (dcn_v2.py:57-91)."""
+    """Modulated deformable convolution whose offsets and masks are inputs (dcn_v2.py:57-91).  ``backward_precision``: read
+    at every forward, so a built module can be switched (``set_backward_precision``)."""
+    backward_precision = "f32"
 
     def __init__(self, in_channels, out_channels, kernel_size, stride, padding, dilation=1, deformable_groups=1):
         super().__init__()
@@ -72,7 +89,7 @@ class DCNv2(nn.Module):
 
     def _apply_op(self, x, offset, mask):
         return dcn_v2_conv(x, offset, mask, self.weight, self.bias, self.stride, self.padding, self.dilation,
-                           self.deformable_groups)
+                           self.deformable_groups, self.backward_precision)
 
     def forward(self, input, offset, mask):
         n = self.taps()
@@ -96,3 +113,16 @@ class DCN(DCNv2):
         n = self.taps()
         om = self.conv_offset_mask(input)
         return self._apply_op(input, om[:, :2 * n].contiguous(), torch.sigmoid(om[:, 2 * n:]))
+
+
+def set_backward_precision(module, name):
+    """Set ``backward_precision`` ("f32" or "f16x3") on every ``DCNv2`` / ``DCN`` under ``module`` (itself included); returns how
+    many were set.  ``PoseNet``, ``PoseNetGRU`` and the resdcn trees are built on these layers.  The offset convolutions inside
+    ``DCN`` are not touched: ``centerpose_amd.conv.set_backward_precision`` is their switch."""
+    name = _precision_name(name)
+    n = 0
+    for m in module.modules():
+        if isinstance(m, DCNv2):
+            m.backward_precision = name
+            n += 1
+    return n

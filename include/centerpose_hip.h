@@ -51,7 +51,8 @@ typedef struct cp_model cp_model;
  *     cp_train_inputs_workspace_bytes, cp_train_inputs;
  *     cp_pose_targets_track_det_workspace_bytes, cp_pose_targets_track_det;
  *     cp_adam_table_bytes, cp_adam_table_build, cp_adam_state_bytes, cp_adam_workspace_bytes, cp_adam_step;
- *     cp_grad_flat_elems, cp_grad_flat_offsets, cp_grad_pack_table_bytes, cp_grad_pack_table_build, cp_grad_pack. */
+ *     cp_grad_flat_elems, cp_grad_flat_offsets, cp_grad_pack_table_bytes, cp_grad_pack_table_build, cp_grad_pack;
+ *     cp_dcnv2_backward_prec_workspace_bytes, cp_dcnv2_backward_prec, cp_dcnv2_backward_prec_mask. */
 #define CP_ABI_VERSION 7
 const char* cp_version(void);
 int cp_abi_version(void);
@@ -137,6 +138,50 @@ int cp_dcnv2_backward_det(cp_stream_t stream, const float* input, const float* w
                           float* grad_mask, float* grad_weight, float* grad_bias, int B, int C, int H, int W, int Co,
                           int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int deformable_group,
                           void* workspace, size_t workspace_bytes);
+
+/* ------------------------------------------------------------------------------------------
+ * DCNv2 backward with a precision argument — cp_dcnv2_backward (deterministic == 0) or cp_dcnv2_backward_det
+ * (deterministic != 0) with `precision` (CP_PREC_*).  CP_PREC_F32 IS the call without it, for either `deterministic`
+ * value: same kernels, same bits, same workspace size.  CP_PREC_F16X3 runs the two contractions of the fast geometry
+ * (3x3 / stride 1 / pad 1 / dilation 1 / deformable_group 1 / C % 16 == 0) on v_mfma_f32_32x32x16_f16 with the
+ * split-binary16 arithmetic of cp_conv2d_backward_prec_nhwc (hi*hi + hi*lo + lo*hi, float32 accumulation, exact
+ * power-of-two pre-scales):
+ *   - the modulated deformable columns of a chunk of images are materialised once, pixel-major, as split dwords (the
+ *     float32 value the float32 weight gradient builds, times 2^e of the bound |max input| * |max mask|: a column is a
+ *     convex combination of input values times one mask value, so the scaled column stays below 2^15 (1 + 2^-20) for any
+ *     mask, sigmoid output or not), and grad_weight is the weight gradient of the 1x1 convolution 9C -> Co over them;
+ *   - grad_col is the data gradient of that 1x1 convolution (weight scaled per column k = tap * C + c), pixel-major.
+ * Everything else is the float32 code of the two calls: staging, the scatter or the deterministic index, grad_bias, the
+ * copy-out.  grad_bias is therefore bit-identical between the modes; grad_offset, grad_mask and grad_input are computed
+ * from an f16x3 grad_col and differ from the float32 mode's in the last bits (relative error of a product below 2^-20).
+ * The generic geometry runs float32 in either mode.  cp_dcnv2_backward_prec_mask (host arithmetic) reports what a shape
+ * gets: bit 0 = the weight gradient, bit 1 = grad_col runs in f16x3 (grad_col stays float32 for a chunk the f16x3
+ * convolution kernels cannot address); 0 for CP_PREC_F32 and for the generic geometry; CP_ERR_INVALID (with a text)
+ * for a refused shape or an unknown precision ("unknown precision" in cp_last_error), which the other two calls refuse
+ * likewise before any launch.  A deterministic request outside the fast geometry is refused as cp_dcnv2_backward_det
+ * refuses it.
+ * Reproducibility in f16x3: the only new atomics are order-free |max| commits, so on the deterministic path all five
+ * gradients stay bitwise reproducible run to run, and on the default path all but grad_input do.  The |max| slots are per
+ * CALL (over the whole batch), so cp_dcnv2_backward_det's clause "the result for one image is a function of that image's
+ * tensors alone" holds in this mode to the mode's tolerance, not to the bit: a pre-scale that differs by a power of two
+ * between two batches can move the last bit of a `lo` half that falls into binary16's subnormals.  Results are
+ * equivariant, bit for bit, under power-of-two scalings of input, weight, mask and grad_output (short of overflow and
+ * underflow).  The contract of cp_dcnv2_backward_det itself is unchanged.
+ * Workspace: grad_col and the split columns of a chunk EACH follow the 256 MiB rule (at most 256 MiB, or one image), so the
+ * chunks are the float32 mode's; the mode adds that column buffer, one |max| slot block, the split copy of grad_output
+ * (padded, like the float32 copy, to a multiple of 32 channels) and the binary16 weight pack, and is never smaller than the
+ * float32 workspace; the query is exact and a shorter buffer is refused before any launch.
+ * ------------------------------------------------------------------------------------------ */
+size_t cp_dcnv2_backward_prec_workspace_bytes(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph,
+                                              int pw, int dh, int dw, int deformable_group, int deterministic,
+                                              int precision);
+int cp_dcnv2_backward_prec(cp_stream_t stream, const float* input, const float* weight, const float* offset,
+                           const float* mask, const float* grad_output, float* grad_input, float* grad_offset,
+                           float* grad_mask, float* grad_weight, float* grad_bias, int B, int C, int H, int W, int Co,
+                           int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int deformable_group,
+                           int deterministic, int precision, void* workspace, size_t workspace_bytes);
+int cp_dcnv2_backward_prec_mask(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw, int dh,
+                                int dw, int deformable_group, int deterministic, int precision);
 
 /* ------------------------------------------------------------------------------------------
  * Prediction-head block, forward and backward — replaces the per-head loop

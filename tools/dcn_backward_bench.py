@@ -1,6 +1,7 @@
 """DCNv2 backward (cp_dcnv2_backward) per fast-path layer shape, next to the forward of the same shape (GPU).
 
     python tools/dcn_backward_bench.py [--batches 16 64] [--iters 10] [--std 1.0] [--layers TEXT] [--deterministic]
+                                       [--precision f32|both]
 
 One JSON line per (shape, batch): ms per call of cp_dcnv2_backward and of cp_dcnv2_forward (HIP events around `iters`
 back-to-back calls with pre-allocated outputs and workspace), the backward's TFLOP/s against the f32 matrix peak
@@ -12,6 +13,9 @@ corner add that falls outside its patch's halo.  Per-kernel times: run it under
 --deterministic also times cp_dcnv2_backward_det on the same tensors: the two calls alternate in three rounds of `iters`
 calls each and the median round is reported for both (bwd_ms, bwd_det_ms), with the deterministic call's workspace and the
 bytes of its sorted index (16 per (pixel, tap, corner) of a grad_col chunk).
+--precision both times cp_dcnv2_backward_prec in CP_PREC_F32 (the two calls above, bit for bit) and in CP_PREC_F16X3 on both
+paths: the four calls alternate in three rounds after a warm-up of each, and the median round is reported (f32_ms, f16x3_ms,
+f32_det_ms, f16x3_det_ms and the two ratios), with the f16x3 workspaces and the mask of what ran in f16x3.
 """
 import argparse
 import ctypes
@@ -71,6 +75,8 @@ def main():
     ap.add_argument("--std", type=float, default=1.0)
     ap.add_argument("--layers", default="", help="only the layer shapes whose name contains this text")
     ap.add_argument("--deterministic", action="store_true", help="also time cp_dcnv2_backward_det, alternating with the default")
+    ap.add_argument("--precision", default="f32", choices=["f32", "both"],
+                    help="both: also time cp_dcnv2_backward_prec in f32 and f16x3 on both paths, alternating")
     a = ap.parse_args()
     L = hip.lib()
     dev = torch.device("cuda:0")
@@ -112,6 +118,19 @@ def main():
                                                    nd)
 
                 order = [("fwd", fwd)] + [("bwd", bwd), ("bwd_det", det)] * 3
+            prec_ws = {}
+            if a.precision == "both":
+                def prec_call(det, prec):
+                    n = L.cp_dcnv2_backward_prec_workspace_bytes(*geo, det, prec)
+                    buf = torch.empty(n, dtype=torch.uint8, device=dev)
+                    prec_ws[(det, prec)] = n
+                    return lambda: L.cp_dcnv2_backward_prec(s, P(x), P(w), P(off), P(mask), P(go), *[P(t) for t in grads], *geo,
+                                                            det, prec, P(buf), n)
+
+                four = [("f32", prec_call(0, 0)), ("f16x3", prec_call(0, 1)), ("f32_det", prec_call(1, 0)), ("f16x3_det", prec_call(1, 1))]
+                for _, fn in four:   # the warm-up of each, before the first timed round of any
+                    assert fn() == 0, L.cp_last_error()
+                order = order + four * 3
             rounds = {}
             for key, fn in order:
                 assert fn() == 0, L.cp_last_error()
@@ -139,6 +158,13 @@ def main():
                          "det_workspace_mb": round(nd / 2 ** 20, 1), "index_entries_m": round(chunk * H * W * 36 / 1e6, 2),
                          "index_mb": round(16 * chunk * H * W * 36 / 2 ** 20, 1), "chunks": -(-B // chunk)}
                 del wsd
+            if a.precision == "both":
+                extra.update({k + "_ms": round(res[k], 4) for k in ("f32", "f16x3", "f32_det", "f16x3_det")})
+                extra.update({"f16x3_over_f32": round(res["f16x3"] / res["f32"], 3),
+                              "f16x3_det_over_f32_det": round(res["f16x3_det"] / res["f32_det"], 3),
+                              "f16x3_mask": L.cp_dcnv2_backward_prec_mask(*geo, 0, 1),
+                              "f16x3_workspace_mb": round(prec_ws[(0, 1)] / 2 ** 20, 1),
+                              "f16x3_det_workspace_mb": round(prec_ws[(1, 1)] / 2 ** 20, 1)})
             print(json.dumps({
                 "layer": name, "B": B, "offset_std": a.std, "bwd_ms": round(ms, 4), "fwd_ms": round(res["fwd"], 4),
                 "bwd_over_fwd": round(ms / res["fwd"], 2), "tflops": round(flops / ms / 1e9, 2),

@@ -2,6 +2,7 @@
 added (the image stems, the max-pools) next to their baselines, in one process (GPU).
 
     python tools/pose_net_bench.py [--batch 16] [--size 512] [--iters 3] [--rounds 3] [--skip-step] [--only-step] [--deterministic]
+                                   [--backward-precision P] [--heads-backward-precision P] [--dcn-backward-precision P]
                                    [--out profiles/pose_net_bench.txt]
 
 1. ``step``: forward + backward of PoseNet (random linear loss on the head maps) at ``size`` x ``size``, with the time split per
@@ -35,10 +36,10 @@ sys.path.insert(0, REPO)
 FAMILIES = {"conv2d_nhwc": "conv fwd", "conv2d_stem_backward": "stem bwd",
             "batch_norm_forward": "bn fwd", "batch_norm_backward": "bn bwd", "max_pool2d_forward": "pool fwd",
             "max_pool2d_backward": "pool bwd", "conv_transpose2d_dw": "up fwd", "conv_transpose2d_backward": "up bwd",
-            "dcn_v2_forward": "dcn fwd", "dcn_v2_backward": "dcn bwd", "pose_heads_forward": "heads fwd"}
-# the layers reach these two through hip.ops, with a precision argument (hip.conv2d_backward and hip.pose_heads_backward go through
-# them too, so each call is bracketed once)
-OPS_FAMILIES = {"conv2d_backward_prec": "conv bwd", "pose_heads_backward_prec": "heads bwd"}
+            "dcn_v2_forward": "dcn fwd", "pose_heads_forward": "heads fwd"}
+# the layers reach these three through hip.ops, with a precision argument (hip.conv2d_backward, hip.pose_heads_backward and
+# hip.dcn_v2_backward go through them too, so each call is bracketed once)
+OPS_FAMILIES = {"conv2d_backward_prec": "conv bwd", "pose_heads_backward_prec": "heads bwd", "dcn_v2_backward": "dcn bwd"}
 
 
 def main():
@@ -46,6 +47,7 @@ def main():
     import torch.nn.functional as F
 
     from centerpose_amd import conv, hip, pool, pose_heads, stem, synth
+    from centerpose_amd.lib.models.networks.DCNv2 import dcn_v2
     from centerpose_amd.pose_net import PoseNet
 
     ap = argparse.ArgumentParser()
@@ -63,6 +65,9 @@ def main():
     ap.add_argument("--heads-backward-precision", default="f32", choices=["f32", "f16x3"],
                     help="of the heads' backward (pose_heads.set_backward_precision) in every step but the f32 side of "
                          "--backward-precision both, which stays the all-float32 step")
+    ap.add_argument("--dcn-backward-precision", default="f32", choices=["f32", "f16x3", "both"],
+                    help="of the DCN layers' backward (dcn_v2.set_backward_precision); both: the step with the other two switches "
+                         "as given is timed with the DCN layers in f32 and in f16x3, alternating, and traced in f16x3")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -174,12 +179,16 @@ def main():
         precs = ["f32", "f16x3"] if a.backward_precision == "both" else [a.backward_precision]
         modes = [False, True] if a.deterministic else [False]
         modes += ["f16x3"] if len(precs) == 2 else []   # (the deterministic step is timed in the first precision)
+        modes += ["dcn16"] if a.dcn_backward_precision == "both" else []
+        n_dcn = sum(isinstance(m, dcn_v2.DCNv2) for m in net.modules())
 
         def enter(m):
             hip.set_deterministic(m is True)
             conv.set_backward_precision(net, "f16x3" if m == "f16x3" else precs[0])
             heads_mode = "f32" if len(precs) == 2 and m != "f16x3" else a.heads_backward_precision
             assert pose_heads.set_backward_precision(net, heads_mode) == 1
+            dcn16 = a.dcn_backward_precision == "f16x3" or m == "dcn16"
+            assert dcn_v2.set_backward_precision(net, "f16x3" if dcn16 else "f32") == n_dcn > 0
 
         for m in modes:
             enter(m)
@@ -197,6 +206,11 @@ def main():
             det.update({"f16x3_step_ms": round(statistics.median(rounds["f16x3"]), 2),
                         "f16x3_step_ms_rounds": [round(v, 2) for v in rounds["f16x3"]],
                         "f16x3_over_f32": round(statistics.median(rounds["f16x3"]) / statistics.median(total), 3)})
+        det["dcn_backward_precision"] = a.dcn_backward_precision
+        if "dcn16" in rounds:
+            det.update({"dcn_f16x3_step_ms": round(statistics.median(rounds["dcn16"]), 2),
+                        "dcn_f16x3_step_ms_rounds": [round(v, 2) for v in rounds["dcn16"]],
+                        "dcn_f16x3_over_dcn_f32": round(statistics.median(rounds["dcn16"]) / statistics.median(total), 3)})
         enter(True if a.deterministic else modes[-1])  # the traced step below: the deterministic mode if asked for, else the last precision
         if a.deterministic:
             det.update({"deterministic_step_ms": round(statistics.median(rounds[True]), 2),
