@@ -1,6 +1,7 @@
 """What the training layers share (``conv.py``, ``stem.py``, ``deconv.py``, ``norm.py``, ``sync_norm.py``, ``group_norm.py``,
 ``pool.py``, ``upsample.py``, ``conv_gru.py``): the NHWC view of a logical NCHW tensor, the device gate, the "same on both axes"
-rule of the geometry arguments and the in-place re-class walk behind every ``use_hip_*``.
+rule of the geometry arguments, the in-place re-class walk behind every ``use_hip_*``, and the name check and the walk
+behind every ``set_backward_precision`` (``conv.py``, ``pose_heads.py``, ``DCNv2/dcn_v2.py``).
 """
 from .hip import _abi
 
@@ -24,6 +25,25 @@ def _one(v, op, what):
     if not _same(v):
         raise NotImplementedError("%s: %s must be the same on both axes, got %r" % (op, what, tuple(v)))
     return int(v[0] if isinstance(v, (tuple, list)) else v)
+
+
+def _precision_name(name):
+    """``name`` if it is a precision a backward pass can run in ("f32", "f16x3"); ValueError otherwise."""
+    if name not in _abi.PRECISIONS:
+        raise ValueError("backward_precision must be one of %s, got %r" % (sorted(_abi.PRECISIONS), name))
+    return name
+
+
+def _set_backward_precision(module, name, targets):
+    """The walk of every ``set_backward_precision``: check ``name``, then for each module ``m`` under ``module`` (itself
+    included) set ``name`` on every ``(object, attribute)`` pair that ``targets(m)`` yields.  Returns how many were set."""
+    name = _precision_name(name)
+    n = 0
+    for m in module.modules():
+        for obj, attr in targets(m):
+            setattr(obj, attr, name)
+            n += 1
+    return n
 
 
 def _reclass(module, sources, target, refusal, also=(), of="", unbuilt=(), converted_hook=None):

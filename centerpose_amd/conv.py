@@ -16,7 +16,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import hip as _hip
-from ._layers import _nhwc, _on_device, _one, _reclass, _same
+from ._layers import _nhwc, _on_device, _one, _precision_name, _reclass, _same, _set_backward_precision
 
 
 class _Conv2dFn(Function):
@@ -56,12 +56,6 @@ def _geometry_refusal(cin, kh, kw, stride, pad):
     if not (1 <= kh <= 7 and 1 <= kw <= 7 and 1 <= stride <= 4 and 0 <= pad < min(kh, kw)):
         return "geometry outside kernel 1..7, stride 1..4, padding < kernel"
     return None
-
-
-def _precision_name(name):
-    if name not in _hip.PRECISIONS:
-        raise ValueError("backward_precision must be one of %s, got %r" % (sorted(_hip.PRECISIONS), name))
-    return name
 
 
 def conv2d(x, weight, bias=None, stride=1, padding=0, relu=False, backward_precision="f32"):
@@ -117,13 +111,7 @@ class Conv2d(nn.Conv2d):
 def set_backward_precision(module, name):
     """Set ``backward_precision`` ("f32" or "f16x3") on every ``Conv2d`` under ``module`` (itself included); returns how many were
     set.  One line moves a network built on these layers -- ``PoseNet``, ``PoseNetGRU``, ``PoseNetHourglass`` -- onto the mode."""
-    name = _precision_name(name)
-    n = 0
-    for m in module.modules():
-        if isinstance(m, Conv2d):
-            m.backward_precision = name
-            n += 1
-    return n
+    return _set_backward_precision(module, name, lambda m: [(m, "backward_precision")] if isinstance(m, Conv2d) else [])
 
 
 def use_hip_convs(module, backward_precision=None):

@@ -463,7 +463,7 @@ Ws conv_bwd_carve(Carve& c, const Plan& P, int B, int H, int W, int Cin, int str
     r.slab = c.take<float>(P.wg.slab_bytes);
     r.wB = c.take<float>(!need_gx || !P.mfma ? 0
                          : P.dg16            ? cp_conv_dgrad16_pack_bytes(Cin, P.CoP, P.taps, stride)
-                         : stride == 1       ? cp_conv_dgrad_pack_bytes(Cin, P.CoP, P.taps)
+                         : stride == 1       ? cp_conv_dgrad_pack_bytes(Cin, P.CoP, P.taps, CP_PREC_F32)
                                              : (size_t)P.CoP * P.taps * Cin * 4);
     r.slot = nullptr;
     r.gs16 = r.x16 = nullptr;
@@ -535,7 +535,7 @@ size_t cp_conv_dgrad_pack_bytes(int Cin, int CoP, int taps, int precision) {
 
 int cp_launch_conv_dgrad_pack(hipStream_t s, const float* w, float* wB, int Cin, int Cout, int CoP, int taps, int precision) {
     if (precision == CP_PREC_F16X3) return cp_launch_conv_dgrad16_pack(s, w, wB, Cin, Cout, CoP, taps, 1);
-    if (hipMemsetAsync(wB, 0, cp_conv_dgrad_pack_bytes(Cin, CoP, taps), s) != hipSuccess) return CP_ERR_LAUNCH;
+    if (hipMemsetAsync(wB, 0, cp_conv_dgrad_pack_bytes(Cin, CoP, taps, CP_PREC_F32), s) != hipSuccess) return CP_ERR_LAUNCH;
     hipLaunchKernelGGL(pack_dgrad_kernel, dim3(256), dim3(256), 0, s, w, wB, Cout, CoP, Cin, taps, dgrad_cpad(Cin));
     return launch_ok() ? CP_OK : CP_ERR_LAUNCH;
 }

@@ -457,11 +457,11 @@ bool cp_dcn_backward_fast(int C, int kh, int kw, int sh, int sw, int ph, int pw,
 // cp_dcn_backward_prec_mask: bit 0 = the weight gradient, bit 1 = grad_col runs in f16x3 (0 for CP_PREC_F32 and off the fast
 // geometry; the chunk plan is the same on both paths, so the mask does not depend on `deterministic`).
 size_t cp_dcn_backward_ws_bytes(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw, int dh,
-                                int dw, int dg, int precision = 0);
-int cp_launch_dcn_backward(hipStream_t s, const DcnBwdArgs& a, void* ws, int precision = 0);
+                                int dw, int dg, int precision);
+int cp_launch_dcn_backward(hipStream_t s, const DcnBwdArgs& a, void* ws, int precision);
 // the deterministic form (fast geometry only: the callers check cp_dcn_backward_fast first)
-size_t cp_dcn_backward_det_ws_bytes(int B, int C, int H, int W, int Co, int precision = 0);
-int cp_launch_dcn_backward_det(hipStream_t s, const DcnBwdArgs& a, void* ws, int precision = 0);
+size_t cp_dcn_backward_det_ws_bytes(int B, int C, int H, int W, int Co, int precision);
+int cp_launch_dcn_backward_det(hipStream_t s, const DcnBwdArgs& a, void* ws, int precision);
 int cp_dcn_backward_prec_mask(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
                               int dg, int precision);
 // dcn_bwd16.hip: the pieces of the f16x3 mode on the fast geometry.  Slots are |max| slots of one zeroed block.
@@ -498,12 +498,12 @@ int cp_pose_heads_chunk(int B, int H, int W, int hid);  // images whose hidden l
 // weight gradient and the data gradient -- on the split-binary16 kernels (igemm16.hip's, conv_bwd16.hip's); the gate, grad_w1
 // and the bias gradients are float32 in either mode.  cp_pose_heads_backward_mask: bit 0 = the weight gradient, bit 1 = the data
 // gradient, bit 2 = the hidden layer runs in f16x3 (0 for CP_PREC_F32).
-size_t cp_pose_heads_backward_ws_bytes(int B, int H, int W, int Cin, int hid, int max_classes, int precision = 0);
+size_t cp_pose_heads_backward_ws_bytes(int B, int H, int W, int Cin, int hid, int max_classes, int precision);
 int cp_pose_heads_backward_mask(int B, int H, int W, int Cin, int hid, int precision);
 // grad_out[i] NCHW or nullptr (zero parameter gradients, no contribution); grad_feat NHWC or nullptr (not computed)
 int cp_launch_pose_heads_backward(hipStream_t s, const PoseHeadsArgs& a, const float* const* grad_out, float* const* grad_w0,
                                   float* const* grad_b0, float* const* grad_w1, float* const* grad_b1, float* grad_feat,
-                                  void* ws, int precision = 0);
+                                  void* ws, int precision);
 
 // ---- Conv2d backward (conv_bwd.hip): gradients of out = conv2d(x, w) + bias on the forward's NHWC layouts, float32 ----
 struct ConvBwdArgs {
@@ -520,8 +520,8 @@ int cp_conv_backward_path(int B, int H, int W, int Cin, int Cout, int KH, int KW
 // the other paths, the gate, the pad lanes and grad_bias are float32 in either mode.  cp_conv_backward_prec_mask: bit 0 = the
 // weight gradient, bit 1 = the data gradient runs in f16x3 (0 for CP_PREC_F32 and off the MFMA path).
 size_t cp_conv_backward_ws_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int need_grad_x,
-                                 int precision = 0);
-int cp_launch_conv_backward(hipStream_t s, const ConvBwdArgs& a, void* ws, int precision = 0);
+                                 int precision);
+int cp_launch_conv_backward(hipStream_t s, const ConvBwdArgs& a, void* ws, int precision);
 int cp_conv_backward_prec_mask(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int precision);
 // Its two MFMA contractions (cp_conv_backward_mfma geometries) as building blocks: cp_launch_conv_backward is made of them, and
 // heads_bwd.hip runs them per head and chunk of images.  They read the geometry, x, gw and gx of `a` and, in place of a.go,
@@ -545,8 +545,8 @@ int cp_launch_conv_wgrad(hipStream_t s, const ConvBwdArgs& a, const float* gs, i
 // [B,H,W,Cin], which may be a.gx itself) per launch.  precision CP_PREC_F16X3 packs the split-binary16 operand of igemm16.hip
 // instead (a power-of-two scale per input channel of the layer); the launch then takes gs's |max| slot, and is only valid where
 // cp_conv_dgrad16_s1_supported says so.
-size_t cp_conv_dgrad_pack_bytes(int Cin, int CoP, int taps, int precision = 0);
-int cp_launch_conv_dgrad_pack(hipStream_t s, const float* w, float* wB, int Cin, int Cout, int CoP, int taps, int precision = 0);
+size_t cp_conv_dgrad_pack_bytes(int Cin, int CoP, int taps, int precision);
+int cp_launch_conv_dgrad_pack(hipStream_t s, const float* w, float* wB, int Cin, int Cout, int CoP, int taps, int precision);
 int cp_launch_conv_dgrad_s1(hipStream_t s, const ConvBwdArgs& a, const float* gs, int CoP, const float* wB, const float* res,
                             const unsigned* gs_amax = nullptr);  // gs_amax given: wB is the f16x3 pack
 // conv_bwd16.hip: the pieces of the f16x3 mode.  |max| of x[0..n) into a zeroed slot; dst[i] = split(src[i] * 2^e of the slot);

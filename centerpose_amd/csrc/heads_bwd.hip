@@ -193,7 +193,7 @@ Ws heads_bwd_carve(Carve& c, const Plan& P, int B, int H, int W, int Cin, int hi
     Ws r;
     r.wA = c.take<float>((size_t)9 * Cin * P.hpad * 4);
     r.shift = c.take<float>((size_t)P.hpad * 4);
-    r.wB = c.take<float>(cp_conv_dgrad_pack_bytes(Cin, hid, 9));
+    r.wB = c.take<float>(cp_conv_dgrad_pack_bytes(Cin, hid, 9, CP_PREC_F32));
     r.hb = c.take<float>(Q * hid * 4);
     r.go_t = c.take<float>(Q * cmax * 4);
     r.part = c.take<float>((size_t)P.thin_slabs * (cmax + 1) * hid * 4);
@@ -262,7 +262,7 @@ int cp_launch_pose_heads_backward(hipStream_t s, const PoseHeadsArgs& a, const f
         if (hipMemcpyAsync(shift, a.b0[i], (size_t)hid * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return CP_ERR_LAUNCH;
         if (grad_feat) {
             rc = P.dg16 ? cp_launch_conv_dgrad_pack(s, a.w0[i], r.wB16, Cin, hid, hid, 9, CP_PREC_F16X3)
-                        : cp_launch_conv_dgrad_pack(s, a.w0[i], wB, Cin, hid, hid, 9);
+                        : cp_launch_conv_dgrad_pack(s, a.w0[i], wB, Cin, hid, hid, 9, CP_PREC_F32);
             if (rc != CP_OK) return rc;
         }
         if (P.wg16 && !feat_split) {  // f16x3 step 0, before the first head that needs it

@@ -232,6 +232,19 @@ const char* gru_shape_error(int M, int Ch) {
     return nullptr;
 }
 
+// The precision argument of the backward passes that take one (`op`: conv2d_backward, pose_heads_backward, dcn_v2_backward)
+std::string prec_error(const char* op, int precision) {
+    if (precision == CP_PREC_F32 || precision == CP_PREC_F16X3) return std::string();
+    return std::string(op) + ": unknown precision (CP_PREC_F32 or CP_PREC_F16X3)";
+}
+// What every entry of such an operator checks first, in this order: its shape (the operator's *_shape_error), then the
+// precision.  Records the first refusal in cp_last_error and returns true.
+bool refused(const char* shape_error, const char* op, int precision) {
+    const std::string e = shape_error ? std::string(shape_error) : prec_error(op, precision);
+    if (!e.empty()) fail(CP_ERR_INVALID, e);
+    return !e.empty();
+}
+
 // cp_pose_heads_forward: per head the 3x3 layer's float32 and f16x3 operands + bias, the 1x1 layer's, one hidden chunk
 struct HeadsFwdWs {
     ConvOps ops0, ops1;
@@ -299,15 +312,6 @@ size_t cp_pose_heads_forward_workspace_bytes(int B, int H, int W, int Cin, int h
     return c.off;
 }
 
-size_t cp_pose_heads_backward_workspace_bytes(int B, int H, int W, int Cin, int hid, int n, const int* classes) {
-    int cmax = 0;
-    if (const char* e = heads_shape_error(B, H, W, Cin, hid, n, classes, &cmax)) {
-        fail(CP_ERR_INVALID, e);
-        return 0;
-    }
-    return cp_pose_heads_backward_ws_bytes(B, H, W, Cin, hid, cmax);
-}
-
 int cp_pose_heads_forward(cp_stream_t stream, const float* feat, int n, const float* const* w0, const float* const* b0,
                           const float* const* w1, const float* const* b1, const int* classes, float* const* out, int B, int H,
                           int W, int Cin, int hid, void* workspace, size_t workspace_bytes) {
@@ -350,59 +354,21 @@ int cp_pose_heads_forward(cp_stream_t stream, const float* feat, int n, const fl
     return CP_OK;
 }
 
-int cp_pose_heads_backward(cp_stream_t stream, const float* feat, int n, const float* const* w0, const float* const* b0,
-                           const float* const* w1, const float* const* b1, const int* classes, const float* const* grad_out,
-                           float* const* grad_w0, float* const* grad_b0, float* const* grad_w1, float* const* grad_b1,
-                           float* grad_feat, int B, int H, int W, int Cin, int hid, void* workspace, size_t workspace_bytes) {
+// The prediction heads' backward (heads_bwd.hip).  One implementation under two pairs of entry points: the plain pair is
+// CP_PREC_F32; CP_PREC_F16X3 runs the three wide contractions of a head on the split-binary16 kernels.
+static size_t pose_heads_backward_query(int B, int H, int W, int Cin, int hid, int n, const int* classes, int precision) {
     int cmax = 0;
-    if (const char* e = heads_shape_error(B, H, W, Cin, hid, n, classes, &cmax)) return fail(CP_ERR_INVALID, e);
-    if (!feat || !w0 || !b0 || !w1 || !b1 || !grad_out || !grad_w0 || !grad_b0 || !grad_w1 || !grad_b1 || !workspace)
-        return fail(CP_ERR_INVALID, "pose_heads_backward: null argument");
-    for (int i = 0; i < n; ++i)
-        if (!w0[i] || !b0[i] || !w1[i] || !b1[i] || !grad_w0[i] || !grad_b0[i] || !grad_w1[i] || !grad_b1[i])
-            return fail(CP_ERR_INVALID, "pose_heads_backward: null argument");
-    if (workspace_bytes < cp_pose_heads_backward_ws_bytes(B, H, W, Cin, hid, cmax))
-        return fail(CP_ERR_INVALID, "pose_heads_backward: workspace too small");
-    const PoseHeadsArgs a{feat, n, w0, b0, w1, b1, classes, B, H, W, Cin, hid};
-    const int rc = cp_launch_pose_heads_backward((hipStream_t)stream, a, grad_out, grad_w0, grad_b0, grad_w1, grad_b1, grad_feat,
-                                                 workspace);
-    return rc == CP_OK ? CP_OK : fail(rc, "pose_heads_backward: kernel launch failed");
-}
-
-// The precision-aware forms: CP_PREC_F32 is the calls above; CP_PREC_F16X3 runs the three wide contractions of a head on the
-// split-binary16 kernels (heads_bwd.hip)
-static const char* heads_bwd_prec_error(int precision) {
-    return precision == CP_PREC_F32 || precision == CP_PREC_F16X3 ? nullptr
-                                                                  : "pose_heads_backward: unknown precision (CP_PREC_F32 or CP_PREC_F16X3)";
-}
-
-int cp_pose_heads_backward_prec_mask(int B, int H, int W, int Cin, int hid, int precision) {
-    const int one = 1;
-    int cmax = 0;
-    if (const char* e = heads_shape_error(B, H, W, Cin, hid, 1, &one, &cmax)) return fail(CP_ERR_INVALID, e);
-    if (const char* e = heads_bwd_prec_error(precision)) return fail(CP_ERR_INVALID, e);
-    return cp_pose_heads_backward_mask(B, H, W, Cin, hid, precision);
-}
-
-size_t cp_pose_heads_backward_prec_workspace_bytes(int B, int H, int W, int Cin, int hid, int n, const int* classes, int precision) {
-    int cmax = 0;
-    const char* e = heads_shape_error(B, H, W, Cin, hid, n, classes, &cmax);
-    if (!e) e = heads_bwd_prec_error(precision);
-    if (e) {
-        fail(CP_ERR_INVALID, e);
-        return 0;
-    }
+    if (refused(heads_shape_error(B, H, W, Cin, hid, n, classes, &cmax), "pose_heads_backward", precision)) return 0;
     return cp_pose_heads_backward_ws_bytes(B, H, W, Cin, hid, cmax, precision);
 }
 
-int cp_pose_heads_backward_prec(cp_stream_t stream, const float* feat, int n, const float* const* w0, const float* const* b0,
-                                const float* const* w1, const float* const* b1, const int* classes, const float* const* grad_out,
-                                float* const* grad_w0, float* const* grad_b0, float* const* grad_w1, float* const* grad_b1,
-                                float* grad_feat, int B, int H, int W, int Cin, int hid, int precision, void* workspace,
-                                size_t workspace_bytes) {
+static int pose_heads_backward_run(cp_stream_t stream, const float* feat, int n, const float* const* w0, const float* const* b0,
+                                   const float* const* w1, const float* const* b1, const int* classes,
+                                   const float* const* grad_out, float* const* grad_w0, float* const* grad_b0,
+                                   float* const* grad_w1, float* const* grad_b1, float* grad_feat, int B, int H, int W, int Cin,
+                                   int hid, int precision, void* workspace, size_t workspace_bytes) {
     int cmax = 0;
-    if (const char* e = heads_shape_error(B, H, W, Cin, hid, n, classes, &cmax)) return fail(CP_ERR_INVALID, e);
-    if (const char* e = heads_bwd_prec_error(precision)) return fail(CP_ERR_INVALID, e);
+    if (refused(heads_shape_error(B, H, W, Cin, hid, n, classes, &cmax), "pose_heads_backward", precision)) return CP_ERR_INVALID;
     if (!feat || !w0 || !b0 || !w1 || !b1 || !grad_out || !grad_w0 || !grad_b0 || !grad_w1 || !grad_b1 || !workspace)
         return fail(CP_ERR_INVALID, "pose_heads_backward: null argument");
     for (int i = 0; i < n; ++i)
@@ -414,6 +380,40 @@ int cp_pose_heads_backward_prec(cp_stream_t stream, const float* feat, int n, co
     const int rc = cp_launch_pose_heads_backward((hipStream_t)stream, a, grad_out, grad_w0, grad_b0, grad_w1, grad_b1, grad_feat,
                                                  workspace, precision);
     return rc == CP_OK ? CP_OK : fail(rc, "pose_heads_backward: kernel launch failed");
+}
+
+size_t cp_pose_heads_backward_workspace_bytes(int B, int H, int W, int Cin, int hid, int n, const int* classes) {
+    return pose_heads_backward_query(B, H, W, Cin, hid, n, classes, CP_PREC_F32);
+}
+
+int cp_pose_heads_backward(cp_stream_t stream, const float* feat, int n, const float* const* w0, const float* const* b0,
+                           const float* const* w1, const float* const* b1, const int* classes, const float* const* grad_out,
+                           float* const* grad_w0, float* const* grad_b0, float* const* grad_w1, float* const* grad_b1,
+                           float* grad_feat, int B, int H, int W, int Cin, int hid, void* workspace, size_t workspace_bytes) {
+    return pose_heads_backward_run(stream, feat, n, w0, b0, w1, b1, classes, grad_out, grad_w0, grad_b0, grad_w1, grad_b1, grad_feat,
+                                   B, H, W, Cin, hid, CP_PREC_F32, workspace, workspace_bytes);
+}
+
+size_t cp_pose_heads_backward_prec_workspace_bytes(int B, int H, int W, int Cin, int hid, int n, const int* classes, int precision) {
+    return pose_heads_backward_query(B, H, W, Cin, hid, n, classes, precision);
+}
+
+int cp_pose_heads_backward_prec(cp_stream_t stream, const float* feat, int n, const float* const* w0, const float* const* b0,
+                                const float* const* w1, const float* const* b1, const int* classes, const float* const* grad_out,
+                                float* const* grad_w0, float* const* grad_b0, float* const* grad_w1, float* const* grad_b1,
+                                float* grad_feat, int B, int H, int W, int Cin, int hid, int precision, void* workspace,
+                                size_t workspace_bytes) {
+    return pose_heads_backward_run(stream, feat, n, w0, b0, w1, b1, classes, grad_out, grad_w0, grad_b0, grad_w1, grad_b1, grad_feat,
+                                   B, H, W, Cin, hid, precision, workspace, workspace_bytes);
+}
+
+// (which contractions run in f16x3 does not depend on the heads: the shape is checked as that of one single-class head)
+int cp_pose_heads_backward_prec_mask(int B, int H, int W, int Cin, int hid, int precision) {
+    const int one = 1;
+    int cmax = 0;
+    return refused(heads_shape_error(B, H, W, Cin, hid, 1, &one, &cmax), "pose_heads_backward", precision)
+               ? CP_ERR_INVALID
+               : cp_pose_heads_backward_mask(B, H, W, Cin, hid, precision);
 }
 
 size_t cp_conv2d_workspace_bytes(int Cin, int Cout, int KH, int KW) {
@@ -495,62 +495,56 @@ int cp_conv2d_backward_path(int B, int H, int W, int Cin, int Cout, int KH, int 
     return cp_conv_backward_path(B, H, W, Cin, Cout, KH, KW, stride, pad);
 }
 
-size_t cp_conv2d_backward_workspace_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
-                                          int need_grad_x) {
-    if (const char* e = conv_bwd_shape_error(B, H, W, Cin, Cout, KH, KW, stride, pad)) {
-        fail(CP_ERR_INVALID, e);
-        return 0;
-    }
-    return cp_conv_backward_ws_bytes(B, H, W, Cin, Cout, KH, KW, stride, pad, need_grad_x);
-}
-
-int cp_conv2d_backward_nhwc(cp_stream_t stream, const float* x, const float* w, const float* y_or_null, const float* grad_out,
-                            float* grad_x_or_null, float* grad_w, float* grad_bias_or_null, int B, int H, int W, int Cin,
-                            int Cout, int KH, int KW, int stride, int pad, void* workspace, size_t workspace_bytes) {
-    if (const char* e = conv_bwd_shape_error(B, H, W, Cin, Cout, KH, KW, stride, pad)) return fail(CP_ERR_INVALID, e);
-    if (!x || !w || !grad_out || !grad_w || !workspace) return fail(CP_ERR_INVALID, "conv2d_backward: null argument");
-    if (workspace_bytes < cp_conv_backward_ws_bytes(B, H, W, Cin, Cout, KH, KW, stride, pad, grad_x_or_null != nullptr))
-        return fail(CP_ERR_INVALID, "conv2d_backward: workspace too small");
-    const ConvBwdArgs a{x, w, y_or_null, grad_out, grad_x_or_null, grad_w, grad_bias_or_null, B, H, W, Cin, Cout, KH, KW, stride, pad};
-    const int rc = cp_launch_conv_backward((hipStream_t)stream, a, workspace);
-    return rc == CP_OK ? CP_OK : fail(rc, "conv2d_backward: kernel launch failed");
-}
-
-// The precision-aware forms: CP_PREC_F32 is the calls above; CP_PREC_F16X3 runs the MFMA path's contractions on conv_bwd16.hip
-static const char* conv_bwd_prec_error(int precision) {
-    return precision == CP_PREC_F32 || precision == CP_PREC_F16X3 ? nullptr
-                                                                  : "conv2d_backward: unknown precision (CP_PREC_F32 or CP_PREC_F16X3)";
-}
-
-int cp_conv2d_backward_prec_mask(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int precision) {
-    if (const char* e = conv_bwd_shape_error(B, H, W, Cin, Cout, KH, KW, stride, pad)) return fail(CP_ERR_INVALID, e);
-    if (const char* e = conv_bwd_prec_error(precision)) return fail(CP_ERR_INVALID, e);
-    return cp_conv_backward_prec_mask(B, H, W, Cin, Cout, KH, KW, stride, pad, precision);
-}
-
-size_t cp_conv2d_backward_prec_workspace_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
-                                               int need_grad_x, int precision) {
-    const char* e = conv_bwd_shape_error(B, H, W, Cin, Cout, KH, KW, stride, pad);
-    if (!e) e = conv_bwd_prec_error(precision);
-    if (e) {
-        fail(CP_ERR_INVALID, e);
-        return 0;
-    }
+// The Conv2d backward (conv_bwd.hip).  One implementation under two pairs of entry points: the plain pair is CP_PREC_F32;
+// CP_PREC_F16X3 runs the MFMA path's contractions on conv_bwd16.hip.
+static size_t conv2d_backward_query(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int need_grad_x,
+                                    int precision) {
+    if (refused(conv_bwd_shape_error(B, H, W, Cin, Cout, KH, KW, stride, pad), "conv2d_backward", precision)) return 0;
     return cp_conv_backward_ws_bytes(B, H, W, Cin, Cout, KH, KW, stride, pad, need_grad_x, precision);
 }
 
-int cp_conv2d_backward_prec_nhwc(cp_stream_t stream, const float* x, const float* w, const float* y_or_null, const float* grad_out,
-                                 float* grad_x_or_null, float* grad_w, float* grad_bias_or_null, int B, int H, int W, int Cin,
-                                 int Cout, int KH, int KW, int stride, int pad, int precision, void* workspace,
-                                 size_t workspace_bytes) {
-    if (const char* e = conv_bwd_shape_error(B, H, W, Cin, Cout, KH, KW, stride, pad)) return fail(CP_ERR_INVALID, e);
-    if (const char* e = conv_bwd_prec_error(precision)) return fail(CP_ERR_INVALID, e);
+static int conv2d_backward_run(cp_stream_t stream, const float* x, const float* w, const float* y_or_null, const float* grad_out,
+                               float* grad_x_or_null, float* grad_w, float* grad_bias_or_null, int B, int H, int W, int Cin,
+                               int Cout, int KH, int KW, int stride, int pad, int precision, void* workspace,
+                               size_t workspace_bytes) {
+    if (refused(conv_bwd_shape_error(B, H, W, Cin, Cout, KH, KW, stride, pad), "conv2d_backward", precision)) return CP_ERR_INVALID;
     if (!x || !w || !grad_out || !grad_w || !workspace) return fail(CP_ERR_INVALID, "conv2d_backward: null argument");
     if (workspace_bytes < cp_conv_backward_ws_bytes(B, H, W, Cin, Cout, KH, KW, stride, pad, grad_x_or_null != nullptr, precision))
         return fail(CP_ERR_INVALID, "conv2d_backward: workspace too small");
     const ConvBwdArgs a{x, w, y_or_null, grad_out, grad_x_or_null, grad_w, grad_bias_or_null, B, H, W, Cin, Cout, KH, KW, stride, pad};
     const int rc = cp_launch_conv_backward((hipStream_t)stream, a, workspace, precision);
     return rc == CP_OK ? CP_OK : fail(rc, "conv2d_backward: kernel launch failed");
+}
+
+size_t cp_conv2d_backward_workspace_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
+                                          int need_grad_x) {
+    return conv2d_backward_query(B, H, W, Cin, Cout, KH, KW, stride, pad, need_grad_x, CP_PREC_F32);
+}
+
+int cp_conv2d_backward_nhwc(cp_stream_t stream, const float* x, const float* w, const float* y_or_null, const float* grad_out,
+                            float* grad_x_or_null, float* grad_w, float* grad_bias_or_null, int B, int H, int W, int Cin,
+                            int Cout, int KH, int KW, int stride, int pad, void* workspace, size_t workspace_bytes) {
+    return conv2d_backward_run(stream, x, w, y_or_null, grad_out, grad_x_or_null, grad_w, grad_bias_or_null, B, H, W, Cin, Cout, KH,
+                               KW, stride, pad, CP_PREC_F32, workspace, workspace_bytes);
+}
+
+size_t cp_conv2d_backward_prec_workspace_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
+                                               int need_grad_x, int precision) {
+    return conv2d_backward_query(B, H, W, Cin, Cout, KH, KW, stride, pad, need_grad_x, precision);
+}
+
+int cp_conv2d_backward_prec_nhwc(cp_stream_t stream, const float* x, const float* w, const float* y_or_null, const float* grad_out,
+                                 float* grad_x_or_null, float* grad_w, float* grad_bias_or_null, int B, int H, int W, int Cin,
+                                 int Cout, int KH, int KW, int stride, int pad, int precision, void* workspace,
+                                 size_t workspace_bytes) {
+    return conv2d_backward_run(stream, x, w, y_or_null, grad_out, grad_x_or_null, grad_w, grad_bias_or_null, B, H, W, Cin, Cout, KH,
+                               KW, stride, pad, precision, workspace, workspace_bytes);
+}
+
+int cp_conv2d_backward_prec_mask(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int precision) {
+    return refused(conv_bwd_shape_error(B, H, W, Cin, Cout, KH, KW, stride, pad), "conv2d_backward", precision)
+               ? CP_ERR_INVALID
+               : cp_conv_backward_prec_mask(B, H, W, Cin, Cout, KH, KW, stride, pad, precision);
 }
 
 int cp_conv_transpose2d_dw_nhwc(cp_stream_t stream, const float* x, const float* w, const float* add_or_null, float* out, int B,
@@ -879,32 +873,10 @@ int cp_conv2d_stem_wide_backward(cp_stream_t stream, const float* x_nchw, const 
                              B, H, W, Cin, Cout, stride);
 }
 
-size_t cp_dcnv2_backward_workspace_bytes(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw,
-                                         int dh, int dw, int deformable_group) {
-    int Ho = 0, Wo = 0;
-    if (dcn_bwd_shape_error(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group, &Ho, &Wo)) return 0;
-    return cp_dcn_backward_ws_bytes(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group);
-}
-
-int cp_dcnv2_backward(cp_stream_t stream, const float* input, const float* weight, const float* offset, const float* mask,
-                      const float* grad_output, float* grad_input, float* grad_offset, float* grad_mask, float* grad_weight,
-                      float* grad_bias, int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw,
-                      int dh, int dw, int deformable_group, void* workspace, size_t workspace_bytes) {
-    int Ho = 0, Wo = 0;
-    if (const char* e = dcn_bwd_shape_error(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group, &Ho, &Wo))
-        return fail(CP_ERR_INVALID, e);
-    if (!input || !weight || !offset || !mask || !grad_output || !grad_input || !grad_offset || !grad_mask || !grad_weight ||
-        !grad_bias || !workspace)
-        return fail(CP_ERR_INVALID, "dcn_v2_backward: null argument");
-    if (workspace_bytes < cp_dcn_backward_ws_bytes(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group))
-        return fail(CP_ERR_INVALID, "dcn_v2_backward: workspace too small");
-    DcnBwdArgs a{input, weight, offset, mask, grad_output, grad_input, grad_offset, grad_mask, grad_weight, grad_bias,
-                 B, C, H, W, Co, Ho, Wo, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group};
-    const int rc = cp_launch_dcn_backward((hipStream_t)stream, a, workspace);
-    return rc == CP_OK ? CP_OK : fail(rc, "dcn_v2_backward: kernel launch failed");
-}
-
-// The deterministic form: cp_dcnv2_backward's refusals, and any geometry outside the fast path
+// The DCNv2 backward (dcn_bwd.hip).  One implementation under three pairs of entry points: the plain pair (float atomics in
+// grad_input) and the _det pair (bit-reproducible, the fast geometry only) are CP_PREC_F32; the _prec pair takes `deterministic`
+// and the precision as arguments, CP_PREC_F16X3 running the fast geometry's contractions on dcn_bwd16.hip.
+// The deterministic form refuses what the plain form refuses, and any geometry outside the fast path:
 static std::string dcn_bwd_det_geometry_error(int C, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int dg) {
     if (cp_dcn_backward_fast(C, kh, kw, sh, sw, ph, pw, dh, dw, dg)) return std::string();
     char msg[320];
@@ -915,79 +887,36 @@ static std::string dcn_bwd_det_geometry_error(int C, int kh, int kw, int sh, int
     return msg;
 }
 
-size_t cp_dcnv2_backward_det_workspace_bytes(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw,
-                                             int dh, int dw, int deformable_group) {
-    int Ho = 0, Wo = 0;
-    if (dcn_bwd_shape_error(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group, &Ho, &Wo)) return 0;
-    if (!cp_dcn_backward_fast(C, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group)) return 0;
-    return cp_dcn_backward_det_ws_bytes(B, C, H, W, Co);
+// What the call and the mask refuse before they look at anything else, recorded in cp_last_error: the shape (on success Ho,
+// Wo are the output's), then the precision, then (deterministic only) the geometry
+static bool dcn_backward_refused(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
+                                 int dg, int deterministic, int precision, int* Ho, int* Wo) {
+    if (refused(dcn_bwd_shape_error(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, dg, Ho, Wo), "dcn_v2_backward", precision)) return true;
+    const std::string ge = deterministic ? dcn_bwd_det_geometry_error(C, kh, kw, sh, sw, ph, pw, dh, dw, dg) : std::string();
+    if (!ge.empty()) fail(CP_ERR_INVALID, ge);
+    return !ge.empty();
 }
 
-int cp_dcnv2_backward_det(cp_stream_t stream, const float* input, const float* weight, const float* offset, const float* mask,
-                          const float* grad_output, float* grad_input, float* grad_offset, float* grad_mask, float* grad_weight,
-                          float* grad_bias, int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw,
-                          int dh, int dw, int deformable_group, void* workspace, size_t workspace_bytes) {
+// The same checks in the same order, but a refused shape or geometry is 0 without a cp_last_error text, as these queries
+// have answered since before there was a precision to name: only an unknown precision records one.
+static size_t dcn_backward_query(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
+                                 int dg, int deterministic, int precision) {
     int Ho = 0, Wo = 0;
-    if (const char* e = dcn_bwd_shape_error(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group, &Ho, &Wo))
-        return fail(CP_ERR_INVALID, e);
-    const std::string ge = dcn_bwd_det_geometry_error(C, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group);
-    if (!ge.empty()) return fail(CP_ERR_INVALID, ge);
-    if (!input || !weight || !offset || !mask || !grad_output || !grad_input || !grad_offset || !grad_mask || !grad_weight ||
-        !grad_bias || !workspace)
-        return fail(CP_ERR_INVALID, "dcn_v2_backward_det: null argument");
-    if (workspace_bytes < cp_dcn_backward_det_ws_bytes(B, C, H, W, Co))
-        return fail(CP_ERR_INVALID, "dcn_v2_backward_det: workspace too small");
-    DcnBwdArgs a{input, weight, offset, mask, grad_output, grad_input, grad_offset, grad_mask, grad_weight, grad_bias,
-                 B, C, H, W, Co, Ho, Wo, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group};
-    const int rc = cp_launch_dcn_backward_det((hipStream_t)stream, a, workspace);
-    return rc == CP_OK ? CP_OK : fail(rc, "dcn_v2_backward_det: kernel launch failed");
-}
-
-// The two calls above with a precision argument: CP_PREC_F32 is the call without it
-static const char* dcn_bwd_prec_error(int precision) {
-    return precision == CP_PREC_F32 || precision == CP_PREC_F16X3 ? nullptr
-                                                                  : "dcn_v2_backward: unknown precision (CP_PREC_F32 or CP_PREC_F16X3)";
-}
-
-int cp_dcnv2_backward_prec_mask(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
-                                int deformable_group, int deterministic, int precision) {
-    int Ho = 0, Wo = 0;
-    if (const char* e = dcn_bwd_shape_error(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group, &Ho, &Wo))
-        return fail(CP_ERR_INVALID, e);
-    if (const char* e = dcn_bwd_prec_error(precision)) return fail(CP_ERR_INVALID, e);
-    if (deterministic) {
-        const std::string ge = dcn_bwd_det_geometry_error(C, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group);
-        if (!ge.empty()) return fail(CP_ERR_INVALID, ge);
-    }
-    return cp_dcn_backward_prec_mask(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group, precision);
-}
-
-size_t cp_dcnv2_backward_prec_workspace_bytes(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw,
-                                              int dh, int dw, int deformable_group, int deterministic, int precision) {
-    int Ho = 0, Wo = 0;
-    if (dcn_bwd_shape_error(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group, &Ho, &Wo)) return 0;
-    if (const char* e = dcn_bwd_prec_error(precision)) {
-        fail(CP_ERR_INVALID, e);
-        return 0;
-    }
-    if (!deterministic) return cp_dcn_backward_ws_bytes(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group, precision);
-    if (!cp_dcn_backward_fast(C, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group)) return 0;
+    if (dcn_bwd_shape_error(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, dg, &Ho, &Wo)) return 0;
+    if (refused(nullptr, "dcn_v2_backward", precision)) return 0;
+    if (!deterministic) return cp_dcn_backward_ws_bytes(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, dg, precision);
+    if (!cp_dcn_backward_fast(C, kh, kw, sh, sw, ph, pw, dh, dw, dg)) return 0;
     return cp_dcn_backward_det_ws_bytes(B, C, H, W, Co, precision);
 }
 
-int cp_dcnv2_backward_prec(cp_stream_t stream, const float* input, const float* weight, const float* offset, const float* mask,
-                           const float* grad_output, float* grad_input, float* grad_offset, float* grad_mask, float* grad_weight,
-                           float* grad_bias, int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw,
-                           int dh, int dw, int deformable_group, int deterministic, int precision, void* workspace,
-                           size_t workspace_bytes) {
+static int dcn_backward_run(cp_stream_t stream, const float* input, const float* weight, const float* offset, const float* mask,
+                            const float* grad_output, float* grad_input, float* grad_offset, float* grad_mask, float* grad_weight,
+                            float* grad_bias, int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw,
+                            int dh, int dw, int deformable_group, int deterministic, int precision, void* workspace,
+                            size_t workspace_bytes) {
     int Ho = 0, Wo = 0;
-    if (const char* e = dcn_bwd_shape_error(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group, &Ho, &Wo))
-        return fail(CP_ERR_INVALID, e);
-    if (const char* e = dcn_bwd_prec_error(precision)) return fail(CP_ERR_INVALID, e);
-    if (deterministic) {
-        const std::string ge = dcn_bwd_det_geometry_error(C, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group);
-        if (!ge.empty()) return fail(CP_ERR_INVALID, ge);
-    }
+    if (dcn_backward_refused(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group, deterministic, precision, &Ho, &Wo))
+        return CP_ERR_INVALID;
     const char* name = deterministic ? "dcn_v2_backward_det" : "dcn_v2_backward";
     if (!input || !weight || !offset || !mask || !grad_output || !grad_input || !grad_offset || !grad_mask || !grad_weight ||
         !grad_bias || !workspace)
@@ -1000,6 +929,57 @@ int cp_dcnv2_backward_prec(cp_stream_t stream, const float* input, const float* 
     const int rc = deterministic ? cp_launch_dcn_backward_det((hipStream_t)stream, a, workspace, precision)
                                  : cp_launch_dcn_backward((hipStream_t)stream, a, workspace, precision);
     return rc == CP_OK ? CP_OK : fail(rc, std::string(name) + ": kernel launch failed");
+}
+
+size_t cp_dcnv2_backward_workspace_bytes(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw,
+                                         int dh, int dw, int deformable_group) {
+    return dcn_backward_query(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group, 0, CP_PREC_F32);
+}
+
+int cp_dcnv2_backward(cp_stream_t stream, const float* input, const float* weight, const float* offset, const float* mask,
+                      const float* grad_output, float* grad_input, float* grad_offset, float* grad_mask, float* grad_weight,
+                      float* grad_bias, int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw,
+                      int dh, int dw, int deformable_group, void* workspace, size_t workspace_bytes) {
+    return dcn_backward_run(stream, input, weight, offset, mask, grad_output, grad_input, grad_offset, grad_mask, grad_weight,
+                            grad_bias, B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group, 0, CP_PREC_F32, workspace,
+                            workspace_bytes);
+}
+
+size_t cp_dcnv2_backward_det_workspace_bytes(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw,
+                                             int dh, int dw, int deformable_group) {
+    return dcn_backward_query(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group, 1, CP_PREC_F32);
+}
+
+int cp_dcnv2_backward_det(cp_stream_t stream, const float* input, const float* weight, const float* offset, const float* mask,
+                          const float* grad_output, float* grad_input, float* grad_offset, float* grad_mask, float* grad_weight,
+                          float* grad_bias, int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw,
+                          int dh, int dw, int deformable_group, void* workspace, size_t workspace_bytes) {
+    return dcn_backward_run(stream, input, weight, offset, mask, grad_output, grad_input, grad_offset, grad_mask, grad_weight,
+                            grad_bias, B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group, 1, CP_PREC_F32, workspace,
+                            workspace_bytes);
+}
+
+size_t cp_dcnv2_backward_prec_workspace_bytes(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw,
+                                              int dh, int dw, int deformable_group, int deterministic, int precision) {
+    return dcn_backward_query(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group, deterministic, precision);
+}
+
+int cp_dcnv2_backward_prec(cp_stream_t stream, const float* input, const float* weight, const float* offset, const float* mask,
+                           const float* grad_output, float* grad_input, float* grad_offset, float* grad_mask, float* grad_weight,
+                           float* grad_bias, int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw,
+                           int dh, int dw, int deformable_group, int deterministic, int precision, void* workspace,
+                           size_t workspace_bytes) {
+    return dcn_backward_run(stream, input, weight, offset, mask, grad_output, grad_input, grad_offset, grad_mask, grad_weight,
+                            grad_bias, B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group, deterministic, precision,
+                            workspace, workspace_bytes);
+}
+
+int cp_dcnv2_backward_prec_mask(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
+                                int deformable_group, int deterministic, int precision) {
+    int Ho = 0, Wo = 0;
+    return dcn_backward_refused(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group, deterministic, precision, &Ho, &Wo)
+               ? CP_ERR_INVALID
+               : cp_dcn_backward_prec_mask(B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group, precision);
 }
 
 // DCNv2 forward with the reference's NCHW layouts (see header)

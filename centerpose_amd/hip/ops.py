@@ -12,6 +12,21 @@ def _conv_out(H, W, kh, kw, sh, sw, ph, pw, dh=1, dw=1):
     return (H + 2 * ph - (dh * (kh - 1) + 1)) // sh + 1, (W + 2 * pw - (dw * (kw - 1) + 1)) // sw + 1
 
 
+def _precision(op, name):
+    """The C ABI's value of a backward pass's ``precision`` argument (``op``: the operator named in the refusal)."""
+    if name not in _abi.PRECISIONS:
+        raise ValueError("%s: precision must be one of %s, got %r" % (op, sorted(_abi.PRECISIONS), name))
+    return _abi.PRECISIONS[name]
+
+
+def _precision_mask(what, op, symbol, precision, *ints):
+    """The three ``*_precision_mask`` queries: ``symbol(*ints, precision)``, a negative answer being a refusal of ``what``."""
+    rc = getattr(_abi.lib(), symbol)(*map(int, ints), _precision(op, precision))
+    if rc < 0:
+        _abi._refuse(what)
+    return rc
+
+
 def dcn_v2_forward(input, weight, bias, offset, mask, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group):
     """Same 14-argument signature as the reference's ``_ext.dcn_v2_forward`` (DCNv2/src/vision.cpp:5)."""
     L = _abi.lib()
@@ -71,21 +86,12 @@ def resolve_deterministic(requested, fast, own_flag, torch_flag, torch_warn_only
                        "turn off hip.set_deterministic / torch.use_deterministic_algorithms." % (what or "this geometry"))
 
 
-def _dcn_bwd_precision(name):
-    if name not in _abi.PRECISIONS:
-        raise ValueError("dcn_v2_backward: precision must be one of %s, got %r" % (sorted(_abi.PRECISIONS), name))
-    return _abi.PRECISIONS[name]
-
-
 def dcn_backward_precision_mask(B, C, H, W, Co, kh=3, kw=3, sh=1, sw=1, ph=1, pw=1, dh=1, dw=1, deformable_group=1,
                                 deterministic=False, precision="f16x3"):
     """What ``dcn_v2_backward(..., precision=precision)`` runs in f16x3 for a shape (cp_dcnv2_backward_prec_mask; host
     arithmetic, no device): bit 0 = the weight gradient, bit 1 = grad_col.  0 for "f32" and outside the fast geometry."""
-    rc = _abi.lib().cp_dcnv2_backward_prec_mask(*map(int, (B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group)),
-                                                int(bool(deterministic)), _dcn_bwd_precision(precision))
-    if rc < 0:
-        _abi._refuse("dcn_backward_precision_mask")
-    return rc
+    return _precision_mask("dcn_backward_precision_mask", "dcn_v2_backward", "cp_dcnv2_backward_prec_mask", precision,
+                           B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group, bool(deterministic))
 
 
 def dcn_v2_backward(input, weight, bias, offset, mask, grad_output, kh, kw, sh, sw, ph, pw, dh, dw, deformable_group,
@@ -100,7 +106,7 @@ def dcn_v2_backward(input, weight, bias, offset, mask, grad_output, kh, kw, sh, 
     value, the weight gradient and grad_col run in split binary16 (cp_dcnv2_backward_prec; ``dcn_backward_precision_mask``
     tells what a shape gets); any other geometry runs float32."""
     global _warned_nondeterministic
-    prec = _dcn_bwd_precision(precision)
+    prec = _precision("dcn_v2_backward", precision)
     L = _abi.lib()
     input, weight, bias, offset, mask, grad_output = map(_abi._dev, (input, weight, bias, offset, mask, grad_output))
     B, C, H, W = input.shape
@@ -187,12 +193,6 @@ def pose_heads_forward(feat, params):
     return outs
 
 
-def _heads_bwd_precision(name):
-    if name not in _abi.PRECISIONS:
-        raise ValueError("pose_heads_backward: precision must be one of %s, got %r" % (sorted(_abi.PRECISIONS), name))
-    return _abi.PRECISIONS[name]
-
-
 def pose_heads_backward(feat, params, grad_outs, need_feat_grad=True, grad_feat=None):
     """Gradients of pose_heads_forward (cp_pose_heads_backward).  ``grad_outs``: per head a [B,classes_i,H,W] tensor or None (a
     head the loss does not use: zero parameter gradients, nothing added to grad_feat).  Returns (grad_feat, grads) with
@@ -211,7 +211,7 @@ def pose_heads_backward_prec(feat, params, grad_outs, need_feat_grad=True, grad_
     ``pose_heads_backward_precision_mask`` tells what a shape gets).  Reached as ``hip.ops.pose_heads_backward_prec``: the
     ``hip`` package's own list of names and the signature of ``hip.pose_heads_backward`` are kept as they were."""
     L = _abi.lib()
-    prec = _heads_bwd_precision(precision)
+    prec = _precision("pose_heads_backward", precision)
     feat = _abi._nhwc_view(feat)
     flat, tables, cls_arr, classes, (B, H, W, Cin, hid) = _heads_args(feat, params)
     n = len(flat)
@@ -231,17 +231,12 @@ def pose_heads_backward_prec(feat, params, grad_outs, need_feat_grad=True, grad_
                                grad_feat.is_contiguous(memory_format=torch.channels_last)):
         raise RuntimeError("pose_heads_backward: grad_feat must be a float32 channels_last tensor of feat's shape")
     gfp = _abi._ptr(grad_feat) if need_feat_grad else c_void_p(0)
-    if prec:
-        ws = _abi._workspace(L.cp_pose_heads_backward_prec_workspace_bytes(B, H, W, Cin, hid, n, cls_arr, prec), feat.device,
-                             "pose_heads_backward")
-        rc = L.cp_pose_heads_backward_prec(_abi._stream(), _abi._ptr(feat), n, *tables, cls_arr, goptr, *gtab, gfp, B, H, W, Cin,
-                                           hid, prec, _abi._ptr(ws), ws.numel())
-    else:
-        ws = _abi._workspace(L.cp_pose_heads_backward_workspace_bytes(B, H, W, Cin, hid, n, cls_arr), feat.device,
-                             "pose_heads_backward")
-        rc = L.cp_pose_heads_backward(_abi._stream(), _abi._ptr(feat), n, *tables, cls_arr, goptr, *gtab, gfp, B, H, W, Cin, hid,
-                                      _abi._ptr(ws), ws.numel())
-    _abi._check(rc, "cp_pose_heads_backward_prec" if prec else "cp_pose_heads_backward")
+    query, call, tail = (("cp_pose_heads_backward_prec_workspace_bytes", "cp_pose_heads_backward_prec", (prec,)) if prec else
+                         ("cp_pose_heads_backward_workspace_bytes", "cp_pose_heads_backward", ()))
+    ws = _abi._workspace(getattr(L, query)(B, H, W, Cin, hid, n, cls_arr, *tail), feat.device, "pose_heads_backward")
+    rc = getattr(L, call)(_abi._stream(), _abi._ptr(feat), n, *tables, cls_arr, goptr, *gtab, gfp, B, H, W, Cin, hid, *tail,
+                          _abi._ptr(ws), ws.numel())
+    _abi._check(rc, call)
     return (grad_feat if need_feat_grad else None), grads
 
 
@@ -249,10 +244,8 @@ def pose_heads_backward_precision_mask(B, H, W, Cin, hid, precision="f16x3"):
     """What ``pose_heads_backward_prec(..., precision=precision)`` runs in f16x3 for a shape (cp_pose_heads_backward_prec_mask;
     host arithmetic): bit 0 = the 3x3 weight gradient, bit 1 = the data gradient, bit 2 = the recomputed hidden layer.  0 for
     "f32".  Raises RuntimeError for a shape the operator refuses."""
-    rc = _abi.lib().cp_pose_heads_backward_prec_mask(int(B), int(H), int(W), int(Cin), int(hid), _heads_bwd_precision(precision))
-    if rc < 0:
-        _abi._refuse("pose_heads_backward_precision_mask")
-    return rc
+    return _precision_mask("pose_heads_backward_precision_mask", "pose_heads_backward", "cp_pose_heads_backward_prec_mask", precision,
+                           B, H, W, Cin, hid)
 
 
 def conv2d_nhwc(x, w, scale=None, shift=None, residual=None, stride=1, pad=0, act=0):
@@ -271,12 +264,6 @@ def conv2d_nhwc(x, w, scale=None, shift=None, residual=None, stride=1, pad=0, ac
     return out
 
 
-def _bwd_precision(name):
-    if name not in _abi.PRECISIONS:
-        raise ValueError("conv2d_backward: precision must be one of %s, got %r" % (sorted(_abi.PRECISIONS), name))
-    return _abi.PRECISIONS[name]
-
-
 def conv2d_backward(x, w, grad_out, stride=1, pad=0, y=None, need_x_grad=True, need_bias_grad=True):
     """Gradients of ``conv2d_nhwc(x, w, shift=bias)`` (cp_conv2d_backward_nhwc): x [B,H,W,Cin] NHWC, w [Cout,Cin,KH,KW],
     grad_out [B,Ho,Wo,Cout] NHWC -> (grad_x [B,H,W,Cin] | None, grad_w [Cout,Cin,KH,KW], grad_bias [Cout] | None).  ``y``: the
@@ -293,7 +280,7 @@ def conv2d_backward_prec(x, w, grad_out, stride=1, pad=0, y=None, need_x_grad=Tr
     stay float32 -- ``conv2d_backward_precision_mask`` tells which).  Reached as ``hip.ops.conv2d_backward_prec``: the ``hip``
     package's own list of names and the signature of ``hip.conv2d_backward`` are kept as they were."""
     L = _abi.lib()
-    prec = _bwd_precision(precision)
+    prec = _precision("conv2d_backward", precision)
     x, w, grad_out, y = _abi._dev(x), _abi._dev(w), _abi._dev(grad_out), _abi._dev_opt(y)
     if x.dim() != 4 or w.dim() != 4 or w.shape[1] != x.shape[3]:
         raise RuntimeError("conv2d_backward: x must be [B,H,W,Cin] and w [Cout,Cin,KH,KW], got %s and %s"
@@ -301,23 +288,18 @@ def conv2d_backward_prec(x, w, grad_out, stride=1, pad=0, y=None, need_x_grad=Tr
     B, H, W, Cin = x.shape
     Cout, _, KH, KW = w.shape
     stride, pad = int(stride), int(pad)
-    if prec:
-        nbytes = L.cp_conv2d_backward_prec_workspace_bytes(B, H, W, Cin, Cout, KH, KW, stride, pad, int(bool(need_x_grad)), prec)
-    else:
-        nbytes = L.cp_conv2d_backward_workspace_bytes(B, H, W, Cin, Cout, KH, KW, stride, pad, int(bool(need_x_grad)))
-    ws = _abi._workspace(nbytes, x.device, "conv2d_backward")
+    query, call, tail = (("cp_conv2d_backward_prec_workspace_bytes", "cp_conv2d_backward_prec_nhwc", (prec,)) if prec else
+                         ("cp_conv2d_backward_workspace_bytes", "cp_conv2d_backward_nhwc", ()))
+    ws = _abi._workspace(getattr(L, query)(B, H, W, Cin, Cout, KH, KW, stride, pad, int(bool(need_x_grad)), *tail), x.device,
+                         "conv2d_backward")
     Ho, Wo = _conv_out(H, W, KH, KW, stride, stride, pad, pad)
     _abi._check_shapes("conv2d_backward", (("grad_out", grad_out, (B, Ho, Wo, Cout)), ("y", y, (B, Ho, Wo, Cout))))
     grad_x = torch.empty_like(x) if need_x_grad else None
     grad_w = torch.empty_like(w)
     grad_b = torch.empty(Cout, device=x.device, dtype=torch.float32) if need_bias_grad else None
-    if prec:
-        rc = L.cp_conv2d_backward_prec_nhwc(_abi._stream(), *_abi._ptrs(x, w, y, grad_out, grad_x, grad_w, grad_b),
-                                            B, H, W, Cin, Cout, KH, KW, stride, pad, prec, _abi._ptr(ws), ws.numel())
-    else:
-        rc = L.cp_conv2d_backward_nhwc(_abi._stream(), *_abi._ptrs(x, w, y, grad_out, grad_x, grad_w, grad_b),
-                                       B, H, W, Cin, Cout, KH, KW, stride, pad, _abi._ptr(ws), ws.numel())
-    _abi._check(rc, "cp_conv2d_backward_prec_nhwc" if prec else "cp_conv2d_backward_nhwc")
+    rc = getattr(L, call)(_abi._stream(), *_abi._ptrs(x, w, y, grad_out, grad_x, grad_w, grad_b), B, H, W, Cin, Cout, KH, KW, stride,
+                          pad, *tail, _abi._ptr(ws), ws.numel())
+    _abi._check(rc, call)
     return grad_x, grad_w, grad_b
 
 
@@ -325,11 +307,8 @@ def conv2d_backward_precision_mask(B, H, W, Cin, Cout, KH, KW, stride=1, pad=0, 
     """What ``conv2d_backward_prec(..., precision=precision)`` runs in f16x3 for a geometry (cp_conv2d_backward_prec_mask; host
     arithmetic): bit 0 = the weight gradient, bit 1 = the data gradient.  0 for "f32" and for the low-channel and generic paths.
     Raises RuntimeError for a geometry the operator refuses."""
-    rc = _abi.lib().cp_conv2d_backward_prec_mask(int(B), int(H), int(W), int(Cin), int(Cout), int(KH), int(KW), int(stride), int(pad),
-                                                 _bwd_precision(precision))
-    if rc < 0:
-        _abi._refuse("conv2d_backward_precision_mask")
-    return rc
+    return _precision_mask("conv2d_backward_precision_mask", "conv2d_backward", "cp_conv2d_backward_prec_mask", precision,
+                           B, H, W, Cin, Cout, KH, KW, stride, pad)
 
 
 CONV_BWD_GENERIC, CONV_BWD_MFMA, CONV_BWD_LOWC = 0, 1, 2   # include/centerpose_hip.h: CP_CONV_BWD_*

@@ -11,17 +11,11 @@ from torch import nn
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from centerpose_amd import hip as _hip
+from centerpose_amd._layers import _precision_name, _set_backward_precision
 
 from . import _ext
 
 _Geometry = collections.namedtuple("_Geometry", "kernel stride pad dilation groups")
-
-
-def _precision_name(name):
-    if name not in _hip.PRECISIONS:
-        raise ValueError("backward_precision must be one of %s, got %r" % (sorted(_hip.PRECISIONS), name))
-    return name
 
 
 def _two(v):
@@ -119,10 +113,4 @@ def set_backward_precision(module, name):
     """Set ``backward_precision`` ("f32" or "f16x3") on every ``DCNv2`` / ``DCN`` under ``module`` (itself included); returns how
     many were set.  ``PoseNet``, ``PoseNetGRU`` and the resdcn trees are built on these layers.  The offset convolutions inside
     ``DCN`` are not touched: ``centerpose_amd.conv.set_backward_precision`` is their switch."""
-    name = _precision_name(name)
-    n = 0
-    for m in module.modules():
-        if isinstance(m, DCNv2):
-            m.backward_precision = name
-            n += 1
-    return n
+    return _set_backward_precision(module, name, lambda m: [(m, "backward_precision")] if isinstance(m, DCNv2) else [])

@@ -20,6 +20,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import hip as _hip
+from ._layers import _precision_name, _set_backward_precision
 
 
 class _PoseHeadsFn(Function):
@@ -53,12 +54,6 @@ class _Slot(nn.Module):
         super().__init__()
         self.weight = nn.Parameter(weight)
         self.bias = nn.Parameter(bias)
-
-
-def _precision_name(name):
-    if name not in _hip.PRECISIONS:
-        raise ValueError("backward_precision must be one of %s, got %r" % (sorted(_hip.PRECISIONS), name))
-    return name
 
 
 class PoseHeads(nn.Module):
@@ -109,14 +104,11 @@ def set_backward_precision(module, name):
     net that runs ``_PoseHeadsFn`` on its own parameters and carries the name as ``heads_backward_precision``
     (``PoseNetHourglass``, one block per stack, counted once).  ``conv.set_backward_precision`` is the switch of the
     ``Conv2d`` layers and leaves all of these alone."""
-    name = _precision_name(name)
-    n = 0
-    for m in module.modules():
+    def targets(m):
         for h in (m, m.__dict__.get("_head_block")):
             if isinstance(h, PoseHeads):
-                h.backward_precision = name
-                n += 1
+                yield h, "backward_precision"
         if hasattr(m, "heads_backward_precision"):
-            m.heads_backward_precision = name
-            n += 1
-    return n
+            yield m, "heads_backward_precision"
+
+    return _set_backward_precision(module, name, targets)

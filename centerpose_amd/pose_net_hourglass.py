@@ -23,9 +23,10 @@ from collections import OrderedDict
 from torch import nn
 
 from . import synth as _synth
+from ._layers import _precision_name
 from .conv import Conv2d
 from .norm import BatchNorm2d
-from .pose_heads import _PoseHeadsFn, _precision_name, _Slot
+from .pose_heads import _PoseHeadsFn, _Slot
 from .stem import StemConv2d
 from .upsample import UpsampleAdd
 

@@ -14,10 +14,10 @@ hi*hi + hi*lo + lo*hi in float32.  Three kinds of inputs:
 """
 import functools
 
-import numpy as np
 import torch
 
 from tests import conv_backward_ref as R
+from tests.f16x3_common import TWO_LEVEL_MAX_SUM, TWO_LEVEL_VALUES, _two, _unit, np_scale, np_split  # noqa: F401  (reached as C.*)
 
 NAMES = ("grad_x", "grad_w", "grad_bias")
 
@@ -44,9 +44,6 @@ MODULE_CASES = [R.Case(2, 64, 64, 16, 16, 3, 1, 1), R.Case(2, 32, 27, 9, 11, 3, 
                 R.Case(1, 32, 64, 12, 9, 3, 2, 1)]
 assert all(R.is_mfma(c) for c in MODULE_CASES)
 
-TWO_LEVEL_MAX_SUM = 4000
-
-
 def cop(c):
     return (c.Cout + 31) // 32 * 32
 
@@ -59,19 +56,6 @@ def two_level_ok(c):
 
 TWO_LEVEL_CASES = [c for c in CASES if two_level_ok(c)]
 assert len(TWO_LEVEL_CASES) >= 20 and any(c.stride == 1 and c.k == 3 for c in TWO_LEVEL_CASES)
-
-TWO_LEVEL_VALUES = sorted({a + b * 2.0 ** -12 for a in (-1, 0, 1) for b in (-1, 0, 1)})
-
-
-def _two(g, *shape):
-    a = torch.randint(-1, 2, shape, generator=g).double()
-    b = torch.randint(-1, 2, shape, generator=g).double()
-    return (a + b * 2.0 ** -12).float()
-
-
-def _unit(g, *shape):
-    return torch.randint(-1, 2, shape, generator=g).float()
-
 
 def two_level_inputs(seed, c, which):
     """``which`` == "xw": x and w two-level, grad_out integer; "go": grad_out two-level, x and w integer.  Asserts the premise."""
@@ -146,21 +130,3 @@ def assert_equal(got, exp, what):
         bad = int((a.double() != e.double()).sum())
         print("%s %s: %d of %d differ" % (what, name, bad, e.numel()))
         assert a.shape == e.shape and bad == 0, (what, name, bad)
-
-
-# ---- a numpy restatement of the device's scale and split (csrc/cp_common.h: cp_amax_to_scale; igemm16_common.h: split2) ----
-def np_scale(amax):
-    """2^e with amax * 2^e in [2^14, 2^15) (clamped as the device clamps)."""
-    bits = int(np.float32(amax).view(np.uint32))
-    e = min(max((bits >> 23) & 0xff, 16), 253)
-    return float(np.uint32((268 - e) << 23).view(np.float32))
-
-
-def np_split(v):
-    """float32 array -> (hi, lo) as float64: hi = v rounded towards zero to binary16's 11 significant bits (normal range), lo =
-    the residual rounded to binary16 (nearest even)."""
-    v = np.asarray(v, dtype=np.float32)
-    hi = (v.view(np.uint32) & np.uint32(0xffffe000)).view(np.float32)
-    assert np.all(hi.astype(np.float16).astype(np.float32) == hi)   # representable: inside binary16's normal range
-    lo = (v - hi).astype(np.float16)
-    return hi.astype(np.float64), lo.astype(np.float64)

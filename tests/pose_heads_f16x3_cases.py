@@ -3,7 +3,7 @@ test lives here.
 
 The mode (cp_pose_heads_backward_prec with CP_PREC_F16X3) runs three contractions per head in split binary16 -- the recomputed
 hidden layer, the 3x3 weight gradient, the data gradient: each operand is pre-scaled by an exact power of two, split into two
-binary16 numbers hi + lo, and hi*hi + hi*lo + lo*hi is summed in float32 (tests/conv_backward_f16x3_cases.py).  The gate,
+binary16 numbers hi + lo, and hi*hi + hi*lo + lo*hi is summed in float32 (tests/f16x3_common.py).  The gate,
 grad_w1, grad_b0 and grad_b1 are the float32 mode's code.  Four kinds of inputs:
 
 * strict dyadic (pose_heads_ref.dyadic_case): feat and w0 are multiples of 1/4 in [-2, 2] and have no lo part, every hidden value
@@ -29,7 +29,7 @@ import torch
 import torch.nn.functional as F
 
 from tests import pose_heads_ref as R
-from tests.conv_backward_f16x3_cases import TWO_LEVEL_MAX_SUM, np_scale, np_split
+from tests.f16x3_common import TWO_LEVEL_MAX_SUM, _two, _unit, np_scale, np_split
 
 GRAD_TOL = 1e-4
 NAMES = ("grad_w0", "grad_b0", "grad_w1", "grad_b1")
@@ -55,16 +55,6 @@ TWO_LEVEL_KINDS = ("go", "feat")
 def two_level_ok(shape):
     B, Cin, hid, H, W, classes = shape
     return len(classes) == 1 and B * H * W * classes[0] <= TWO_LEVEL_MAX_SUM and 9 * hid * classes[0] <= TWO_LEVEL_MAX_SUM and Cin <= 64
-
-
-def _unit(g, *shape):
-    return torch.randint(-1, 2, shape, generator=g).float()
-
-
-def _two(g, *shape):
-    a = torch.randint(-1, 2, shape, generator=g).double()
-    b = torch.randint(-1, 2, shape, generator=g).double()
-    return (a + b * 2.0 ** -12).float()
 
 
 def two_level_case(seed, shape, kind):
