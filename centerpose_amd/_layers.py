@@ -1,7 +1,7 @@
 """What the training layers share (``conv.py``, ``stem.py``, ``deconv.py``, ``norm.py``, ``sync_norm.py``, ``group_norm.py``,
 ``pool.py``, ``upsample.py``, ``conv_gru.py``): the NHWC view of a logical NCHW tensor, the device gate, the "same on both axes"
 rule of the geometry arguments, the in-place re-class walk behind every ``use_hip_*``, and the name check and the walk
-behind every ``set_backward_precision`` (``conv.py``, ``pose_heads.py``, ``DCNv2/dcn_v2.py``).
+behind every ``set_backward_precision`` (``conv.py``, ``deconv.py``, ``pose_heads.py``, ``DCNv2/dcn_v2.py``).
 """
 from .hip import _abi
 

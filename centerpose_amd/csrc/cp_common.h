@@ -576,7 +576,7 @@ int cp_launch_conv_lowc_dgrad(hipStream_t s, const ConvBwdArgs& a, const float* 
 int cp_launch_rowsum_nchw(const float* g, float* out, int B, int C, int HW, hipStream_t s);
 
 // ---- ConvTranspose2d backward (deconv_bwd.hip): IDAUp's depth-wise `up` (k = 2 stride, pad = stride / 2, groups = C) and the
-// dense k 4 / stride 2 / pad 1 layer, on the forward's NHWC layouts, float32 ----
+// dense k 4 / stride 2 / pad 1 layer, on the forward's NHWC layouts, float32 or (dense) f16x3 ----
 #define CP_DECONV_DW_TABLE_BYTES 61440  // the depth-wise kernels stage w as [k k][C] floats in LDS beside a 4 KiB exchange area
 struct DeconvBwdArgs {
     const float *x, *w, *go;  // x [B,H,W,Cin], w [Cin,Cout/groups,K,K], go [B,stride H,stride W,Cout]
@@ -585,9 +585,13 @@ struct DeconvBwdArgs {
 };
 bool cp_deconv_dw_geometry(int Cin, int Cout, int K, int stride, int pad, int groups);
 bool cp_deconv_dense_geometry(int Cin, int Cout, int K, int stride, int pad, int groups);
-// (for a geometry one of the two predicates accepts)
-size_t cp_deconv_backward_ws_bytes(int B, int H, int W, int Cin, int Cout, int stride, int groups, int need_grad_x);
-int cp_launch_deconv_backward(hipStream_t s, const DeconvBwdArgs& a, void* ws);
+// (for a geometry one of the two predicates accepts)  `precision` (CP_PREC_*): CP_PREC_F16X3 runs the dense layer's two
+// contractions in split binary16 -- the weight gradient on conv_bwd16.hip's slab kernel, the data gradient on igemm16.hip where a
+// variant takes the launch; the depth-wise layers have no matrix product and are float32 in either mode.
+// cp_deconv_backward_prec_mask: bit 0 = the weight gradient, bit 1 = the data gradient runs in f16x3.
+size_t cp_deconv_backward_ws_bytes(int B, int H, int W, int Cin, int Cout, int stride, int groups, int need_grad_x, int precision);
+int cp_deconv_backward_prec_mask(int B, int H, int W, int Cin, int Cout, int groups, int precision);
+int cp_launch_deconv_backward(hipStream_t s, const DeconvBwdArgs& a, void* ws, int precision);
 
 // ---- BatchNorm2d, training and evaluation, fused with the residual add and ReLU (batchnorm.hip): float32 NHWC ----
 struct BnFwdArgs {

@@ -1,5 +1,5 @@
-// Backward of the two transposed convolutions of the up-sampling paths (cp_conv_transpose2d_backward_nhwc), float32 NHWC, no
-// atomics, every sum in a fixed order:
+// Backward of the two transposed convolutions of the up-sampling paths (cp_conv_transpose2d_backward_nhwc / _prec_nhwc), float32
+// NHWC, no atomics (but the f16x3 mode's |max| slots'), every sum in a fixed order:
 //   depth-wise  IDAUp's `up` (pose_dla_dcn.py:402-417): ConvTranspose2d(C, C, k = 2f, stride f, padding f/2, groups C), the
 //               forward of upsample_add_kernel (ewise.hip) in upadd_common.h's notation.  New kernels, below.
 //   dense       resnet_dcn.py:232-240's deconv layers: ConvTranspose2d(Cin, Cout, 4, stride 2, padding 1).  No kernel of its own:
@@ -7,6 +7,9 @@
 //               [out,in,4,4], so its data gradient IS that convolution of grad_out (the exact-f32 implicit GEMM of igemm.hip) and
 //               its weight gradient is that convolution's weight gradient with the roles of input and output gradient swapped
 //               (cp_launch_conv_wgrad: `x` = grad_out, `gs` = x; wgrad_reduce_kernel then writes [Cin][Cout][4][4]).
+//               CP_PREC_F16X3 runs the same two contractions in split binary16 on what conv_bwd16.hip and igemm16.hip
+//               provide: wgrad16_kernel on the split copies of grad_out and x, and cp_launch_conv16 on w packed as a forward
+//               convolution's weight (cp_pack_f16x3).  The depth-wise kernels have no matrix product: float32 in either mode.
 #include "op_common.h"
 
 #include <algorithm>
@@ -172,21 +175,58 @@ float* dw_carve(Carve& c, const DwPlan& P) { return c.take<float>(P.part_bytes);
 
 struct DensePlan {
     ConvWgradPlan wg;
-    int cpad;  // the data gradient's N tile padding of Cin
+    int cpad;          // the data gradient's N tile padding of Cin
+    bool wg16, dg16;   // f16x3: the weight gradient, the data gradient
 };
-DensePlan dense_plan(int B, int H, int Cin, int Cout) {
+
+// The f16x3 data gradient's launch: grad_out [B,2H,2W,Cout] (*) w read as [out = Cin][in = Cout][4][4], stride 2, pad 1, on the
+// operands cp_pack_f16x3 made (`cw`); false where no f16x3 kernel takes it
+bool dense_dgrad16_params(ConvParams& p, const cp_engine::ConvW& cw, const DeconvBwdArgs& a, const unsigned* go_amax) {
+    p = cp_engine::conv_params(a.B, 2 * a.H, 2 * a.W, &a.go, &a.Cout, 1, cw, 2, 1, CP_ACT_NONE);
+    p.dbg = 0;
+    p.out = a.gx;
+    p.store = CP_STORE_NHWC;
+    p.ldo = a.Cin;
+    return cp_engine::conv_params_f16(p, cw, &go_amax, true);
+}
+
+DensePlan dense_plan(int B, int H, int W, int Cin, int Cout, int precision) {
     DensePlan P;
     P.wg = cp_conv_wgrad_plan((size_t)B * H, Cout, Cin, 16);
     P.cpad = (int)cp_engine::align_up((size_t)Cin, cp_conv_tile_n(Cin));
+    P.wg16 = precision == CP_PREC_F16X3;
+    P.dg16 = false;
+    if (P.wg16) {  // (host arithmetic on the launch's shape: the pointers only have to be there)
+        static const float dummy = 0.f;
+        cp_engine::ConvW cw = cp_engine::conv_w_f32(nullptr, nullptr, nullptr, Cout, Cin, 4, 4);
+        cw.w16_hi = cw.w16_lo = (void*)&dummy;
+        cw.Kpad16 = cw.K;
+        const DeconvBwdArgs a{&dummy, &dummy, &dummy, nullptr, nullptr, B, H, W, Cin, Cout, 2, 1};
+        ConvParams p;
+        P.dg16 = dense_dgrad16_params(p, cw, a, nullptr);
+    }
     return P;
 }
+// float32: [slab][wp], the workspace it always was.  f16x3: [slab][wp, or the data gradient's f16x3 pack][|max| slot block
+// (slot 0: grad_out, slot 1: x)][grad_out split][x split]
 struct DenseWs {
     float *slab, *wp;
+    Pack16 f16;
+    unsigned* slot;
+    uint32_t *go16, *x16;
 };
-DenseWs dense_carve(Carve& c, const DensePlan& P, int Cout, bool need_gx) {
-    DenseWs r;
+DenseWs dense_carve(Carve& c, const DensePlan& P, int B, int H, int W, int Cin, int Cout, bool need_gx) {
+    DenseWs r{};
     r.slab = c.take<float>(P.wg.slab_bytes);
-    r.wp = c.take<float>(need_gx ? (size_t)16 * Cout * P.cpad * 4 : 0);
+    if (need_gx && P.dg16)
+        r.f16 = carve_pack16(c, (size_t)16 * Cout, (size_t)P.cpad);
+    else
+        r.wp = c.take<float>(need_gx ? (size_t)16 * Cout * P.cpad * 4 : 0);
+    if (P.wg16) {
+        r.slot = c.take<unsigned>(cp_amax_slot_bytes);
+        r.go16 = c.take<uint32_t>((size_t)B * H * W * 4 * Cout * 4);
+        r.x16 = c.take<uint32_t>((size_t)B * H * W * Cin * 4);
+    }
     return r;
 }
 
@@ -201,16 +241,22 @@ bool cp_deconv_dense_geometry(int Cin, int Cout, int K, int stride, int pad, int
     return groups == 1 && K == 4 && stride == 2 && pad == 1 && Cin >= 32 && Cin % 32 == 0 && Cout >= 32 && Cout % 32 == 0;
 }
 
-size_t cp_deconv_backward_ws_bytes(int B, int H, int W, int Cin, int Cout, int stride, int groups, int need_grad_x) {
+size_t cp_deconv_backward_ws_bytes(int B, int H, int W, int Cin, int Cout, int stride, int groups, int need_grad_x, int precision) {
     Carve c{nullptr};
     if (groups != 1)
         dw_carve(c, dw_plan(B, H, W, Cin, stride));
     else
-        dense_carve(c, dense_plan(B, H, Cin, Cout), Cout, need_grad_x != 0);
+        dense_carve(c, dense_plan(B, H, W, Cin, Cout, precision), B, H, W, Cin, Cout, need_grad_x != 0);
     return c.off;
 }
 
-int cp_launch_deconv_backward(hipStream_t s, const DeconvBwdArgs& a, void* ws) {
+int cp_deconv_backward_prec_mask(int B, int H, int W, int Cin, int Cout, int groups, int precision) {
+    if (groups != 1) return 0;  // (no matrix product)
+    const DensePlan P = dense_plan(B, H, W, Cin, Cout, precision);
+    return (P.wg16 ? 1 : 0) | (P.dg16 ? 2 : 0);
+}
+
+int cp_launch_deconv_backward(hipStream_t s, const DeconvBwdArgs& a, void* ws, int precision) {
     Carve cv{(char*)ws};
     if (a.groups != 1) {
         const DwPlan P = dw_plan(a.B, a.H, a.W, a.Cin, a.stride);
@@ -227,12 +273,34 @@ int cp_launch_deconv_backward(hipStream_t s, const DeconvBwdArgs& a, void* ws) {
                            a.Cin, kk);
         return launch_ok() ? CP_OK : CP_ERR_LAUNCH;
     }
-    const DensePlan P = dense_plan(a.B, a.H, a.Cin, a.Cout);
-    const DenseWs r = dense_carve(cv, P, a.Cout, a.gx != nullptr);
+    const DensePlan P = dense_plan(a.B, a.H, a.W, a.Cin, a.Cout, precision);
+    const DenseWs r = dense_carve(cv, P, a.B, a.H, a.W, a.Cin, a.Cout, a.gx != nullptr);
+    // f16x3: the |max| of grad_out and x, then their split copies (conv_bwd16.hip's operand form)
+    const unsigned *go_amax = r.slot, *x_amax = r.slot + 1;
+    if (P.wg16) {
+        const size_t nx = (size_t)a.B * a.H * a.W * a.Cin, ng = (size_t)a.B * a.H * a.W * 4 * a.Cout;
+        if (hipMemsetAsync(r.slot, 0, cp_amax_slot_bytes, s) != hipSuccess) return CP_ERR_LAUNCH;
+        int rc = cp_launch_absmax32(a.go, ng, r.slot, s);
+        if (rc == CP_OK) rc = cp_launch_absmax32(a.x, nx, r.slot + 1, s);
+        if (rc == CP_OK) rc = cp_launch_split16(a.go, r.go16, ng, go_amax, s);
+        if (rc == CP_OK) rc = cp_launch_split16(a.x, r.x16, nx, x_amax, s);
+        if (rc != CP_OK) return rc;
+    }
     // grad_w: the stride-2 convolution's weight gradient with grad_out as its input and x as its output gradient
     const ConvBwdArgs c{a.go, nullptr, nullptr, nullptr, nullptr, a.gw, nullptr, a.B, 2 * a.H, 2 * a.W, a.Cout, a.Cin, 4, 4, 2, 1};
-    int rc = cp_launch_conv_wgrad(s, c, a.x, a.Cin, P.wg, r.slab, 0);
+    const ConvWgrad16 h{r.x16, r.go16, x_amax, go_amax};
+    int rc = cp_launch_conv_wgrad(s, c, a.x, a.Cin, P.wg, r.slab, 0, P.wg16 ? &h : nullptr);
     if (rc != CP_OK || !a.gx) return rc;
+    if (P.dg16) {
+        // grad_x on the f16x3 implicit GEMM: w is already a [out = Cin][in = Cout][4][4] weight, so it is packed as a forward
+        // convolution's (a power-of-two scale per row, its inverse in the epilogue); grad_out's |max| is slot 0 above
+        cp_engine::ConvW cw = cp_engine::conv_w_f32(nullptr, nullptr, nullptr, a.Cout, a.Cin, 4, 4);
+        rc = cp_pack_f16x3(r.f16, a.w, nullptr, 16, cw, nullptr, 0, nullptr, 0, s);
+        if (rc != CP_OK) return rc;
+        ConvParams d;
+        if (!dense_dgrad16_params(d, cw, a, go_amax)) return CP_ERR_LAUNCH;  // (the plan asked the same question)
+        return cp_launch_conv16(d, s);
+    }
     // grad_x = conv2d(grad_out, w as [out = Cin][in = Cout][4][4], stride 2, pad 1), exact float32
     if (hipMemsetAsync(r.wp, 0, (size_t)16 * a.Cout * P.cpad * 4, s) != hipSuccess) return CP_ERR_LAUNCH;
     rc = cp_launch_pack_weight(a.w, r.wp, a.Cin, a.Cout, 16, a.Cout, P.cpad, 0, s);

@@ -1,6 +1,6 @@
 // The stand-alone operators of the C ABI (include/centerpose_hip.h): single layers on caller tensors, outside any cp_model
 // -- cp_conv2d_nhwc / cp_conv2d_backward_nhwc / cp_conv2d_backward_prec_nhwc, cp_batchnorm_forward_nhwc / _backward_nhwc, cp_conv_transpose2d_nhwc,
-// cp_conv_transpose2d_dw_nhwc / cp_conv_transpose2d_backward_nhwc, cp_dcnv2_forward / cp_dcnv2_backward / cp_dcnv2_backward_det / cp_dcnv2_backward_prec, cp_pose_heads_forward / _backward / _backward_prec,
+// cp_conv_transpose2d_dw_nhwc / cp_conv_transpose2d_backward_nhwc / cp_conv_transpose2d_backward_prec_nhwc, cp_dcnv2_forward / cp_dcnv2_backward / cp_dcnv2_backward_det / cp_dcnv2_backward_prec, cp_pose_heads_forward / _backward / _backward_prec,
 // cp_maxpool2d_forward_nhwc / _backward_nhwc, cp_upsample2_add_nhwc / cp_upsample2_add_backward_nhwc (large_hourglass.py:95-112),
 // cp_conv2d_stem_backward / cp_conv2d_stem_wide_backward, cp_groupnorm_forward_nhwc / _backward_nhwc,
 // cp_gru_gate_forward / _backward, cp_adam_table_bytes / _table_build / _step, cp_grad_flat_elems / _flat_offsets / _pack_table_bytes / _pack_table_build / _pack.
@@ -232,7 +232,7 @@ const char* gru_shape_error(int M, int Ch) {
     return nullptr;
 }
 
-// The precision argument of the backward passes that take one (`op`: conv2d_backward, pose_heads_backward, dcn_v2_backward)
+// The precision argument of the backward passes that take one (`op`: conv2d_backward, conv_transpose2d_backward, pose_heads_backward, dcn_v2_backward)
 std::string prec_error(const char* op, int precision) {
     if (precision == CP_PREC_F32 || precision == CP_PREC_F16X3) return std::string();
     return std::string(op) + ": unknown precision (CP_PREC_F32 or CP_PREC_F16X3)";
@@ -556,27 +556,59 @@ int cp_conv_transpose2d_dw_nhwc(cp_stream_t stream, const float* x, const float*
     return rc == CP_OK ? CP_OK : fail(rc, "conv_transpose2d_dw: kernel launch failed");
 }
 
+// The ConvTranspose2d backward (deconv_bwd.hip).  One implementation under two pairs of entry points: the plain pair is
+// CP_PREC_F32; CP_PREC_F16X3 runs the dense layer's contractions on conv_bwd16.hip and igemm16.hip.
+static size_t deconv_backward_query(int B, int H, int W, int Cin, int Cout, int K, int stride, int pad, int groups, int need_grad_x,
+                                    int precision) {
+    if (refused(deconv_shape_error(B, H, W, Cin, Cout, K, stride, pad, groups), "conv_transpose2d_backward", precision)) return 0;
+    return cp_deconv_backward_ws_bytes(B, H, W, Cin, Cout, stride, groups, need_grad_x, precision);
+}
+
+static int deconv_backward_run(cp_stream_t stream, const float* x, const float* w, const float* grad_out, float* grad_x_or_null,
+                               float* grad_w, int B, int H, int W, int Cin, int Cout, int K, int stride, int pad, int groups,
+                               int precision, void* workspace, size_t workspace_bytes) {
+    if (refused(deconv_shape_error(B, H, W, Cin, Cout, K, stride, pad, groups), "conv_transpose2d_backward", precision))
+        return CP_ERR_INVALID;
+    if (!x || !w || !grad_out || !grad_w || !workspace) return fail(CP_ERR_INVALID, "conv_transpose2d_backward: null argument");
+    if (!bn_aligned({x, w, grad_out, grad_x_or_null, grad_w, workspace}))
+        return fail(CP_ERR_INVALID, "conv_transpose2d_backward: tensors must be 16-byte aligned");
+    if (workspace_bytes < cp_deconv_backward_ws_bytes(B, H, W, Cin, Cout, stride, groups, grad_x_or_null != nullptr, precision))
+        return fail(CP_ERR_INVALID, "conv_transpose2d_backward: workspace too small");
+    const DeconvBwdArgs a{x, w, grad_out, grad_x_or_null, grad_w, B, H, W, Cin, Cout, stride, groups};
+    const int rc = cp_launch_deconv_backward((hipStream_t)stream, a, workspace, precision);
+    return rc == CP_OK ? CP_OK : fail(rc, "conv_transpose2d_backward: kernel launch failed");
+}
+
 size_t cp_conv_transpose2d_backward_workspace_bytes(int B, int H, int W, int Cin, int Cout, int K, int stride, int pad, int groups,
                                                     int need_grad_x) {
-    if (const char* e = deconv_shape_error(B, H, W, Cin, Cout, K, stride, pad, groups)) {
-        fail(CP_ERR_INVALID, e);
-        return 0;
-    }
-    return cp_deconv_backward_ws_bytes(B, H, W, Cin, Cout, stride, groups, need_grad_x);
+    return deconv_backward_query(B, H, W, Cin, Cout, K, stride, pad, groups, need_grad_x, CP_PREC_F32);
 }
 
 int cp_conv_transpose2d_backward_nhwc(cp_stream_t stream, const float* x, const float* w, const float* grad_out,
                                       float* grad_x_or_null, float* grad_w, int B, int H, int W, int Cin, int Cout, int K,
                                       int stride, int pad, int groups, void* workspace, size_t workspace_bytes) {
-    if (const char* e = deconv_shape_error(B, H, W, Cin, Cout, K, stride, pad, groups)) return fail(CP_ERR_INVALID, e);
-    if (!x || !w || !grad_out || !grad_w || !workspace) return fail(CP_ERR_INVALID, "conv_transpose2d_backward: null argument");
-    if (!bn_aligned({x, w, grad_out, grad_x_or_null, grad_w, workspace}))
-        return fail(CP_ERR_INVALID, "conv_transpose2d_backward: tensors must be 16-byte aligned");
-    if (workspace_bytes < cp_deconv_backward_ws_bytes(B, H, W, Cin, Cout, stride, groups, grad_x_or_null != nullptr))
-        return fail(CP_ERR_INVALID, "conv_transpose2d_backward: workspace too small");
-    const DeconvBwdArgs a{x, w, grad_out, grad_x_or_null, grad_w, B, H, W, Cin, Cout, stride, groups};
-    const int rc = cp_launch_deconv_backward((hipStream_t)stream, a, workspace);
-    return rc == CP_OK ? CP_OK : fail(rc, "conv_transpose2d_backward: kernel launch failed");
+    return deconv_backward_run(stream, x, w, grad_out, grad_x_or_null, grad_w, B, H, W, Cin, Cout, K, stride, pad, groups, CP_PREC_F32,
+                               workspace, workspace_bytes);
+}
+
+size_t cp_conv_transpose2d_backward_prec_workspace_bytes(int B, int H, int W, int Cin, int Cout, int K, int stride, int pad,
+                                                         int groups, int need_grad_x, int precision) {
+    return deconv_backward_query(B, H, W, Cin, Cout, K, stride, pad, groups, need_grad_x, precision);
+}
+
+int cp_conv_transpose2d_backward_prec_nhwc(cp_stream_t stream, const float* x, const float* w, const float* grad_out,
+                                           float* grad_x_or_null, float* grad_w, int B, int H, int W, int Cin, int Cout, int K,
+                                           int stride, int pad, int groups, int precision, void* workspace,
+                                           size_t workspace_bytes) {
+    return deconv_backward_run(stream, x, w, grad_out, grad_x_or_null, grad_w, B, H, W, Cin, Cout, K, stride, pad, groups, precision,
+                               workspace, workspace_bytes);
+}
+
+int cp_conv_transpose2d_backward_prec_mask(int B, int H, int W, int Cin, int Cout, int K, int stride, int pad, int groups,
+                                           int precision) {
+    return refused(deconv_shape_error(B, H, W, Cin, Cout, K, stride, pad, groups), "conv_transpose2d_backward", precision)
+               ? CP_ERR_INVALID
+               : cp_deconv_backward_prec_mask(B, H, W, Cin, Cout, groups, precision);
 }
 
 size_t cp_batchnorm_workspace_bytes(int B, int H, int W, int C) {

@@ -6,7 +6,9 @@ Both backbone families up-sample with ``nn.ConvTranspose2d``.  DLA's ``IDAUp`` (
 ``up = ConvTranspose2d(o, o, 2f, stride=f, padding=f // 2, groups=o, bias=False)``; resnet_dcn.py:232-240 stacks three dense
 ``ConvTranspose2d(planes, planes, 4, stride=2, padding=1, bias=False)``.  ``conv_transpose2d`` is one autograd function over
 ``cp_conv_transpose2d_dw_nhwc`` / ``cp_conv_transpose2d_nhwc`` (forward; the dense one's precision follows
-``hip.set_default_precision``) and ``cp_conv_transpose2d_backward_nhwc`` (backward; float32, bitwise reproducible).
+``hip.set_default_precision``) and ``cp_conv_transpose2d_backward_nhwc`` (backward; bitwise reproducible; float32 unless the
+layer's ``backward_precision`` is "f16x3", which moves the dense layer's weight and data gradient onto split-binary16 matrix
+instructions: ``cp_conv_transpose2d_backward_prec_nhwc``; the depth-wise layers have no matrix product and stay float32).
 ``ConvTranspose2d`` is ``nn.ConvTranspose2d`` with that forward and nothing else changed, and ``use_hip_deconvs(model)`` re-classes
 a tree's eligible layers in place, as ``conv.use_hip_convs`` and ``norm.use_hip_norms`` do for theirs.
 
@@ -18,12 +20,14 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import hip as _hip
-from ._layers import _nhwc, _on_device, _one, _reclass, _same
+from ._layers import _nhwc, _on_device, _one, _precision_name, _reclass, _same, _set_backward_precision
 
 _DW_TABLE_BYTES = 61440  # the depth-wise kernels' LDS weight table (include/centerpose_hip.h)
 
 
 class _ConvTranspose2dFn(Function):
+    _backward_precision = "f32"  # (the backward reads it from the function class its context belongs to)
+
     @staticmethod
     def forward(ctx, x, weight, add, stride, pad, groups):
         xh = _nhwc(x)
@@ -42,10 +46,18 @@ class _ConvTranspose2dFn(Function):
         need_x, need_w, need_add = ctx.needs_input_grad[:3]
         gx = gw = None
         if need_x or need_w:
-            gx, gw = _hip.conv_transpose2d_backward(_nhwc(x), weight, _nhwc(grad_out), ctx.stride, ctx.pad, ctx.groups,
-                                                    need_x_grad=need_x)
+            gx, gw = _hip.ops.conv_transpose2d_backward(_nhwc(x), weight, _nhwc(grad_out), ctx.stride, ctx.pad, ctx.groups,
+                                                        need_x_grad=need_x, precision=ctx._forward_cls._backward_precision)
         return (gx.permute(0, 3, 1, 2) if need_x else None, gw if need_w else None, grad_out if need_add else None, None, None,
                 None)
+
+
+class _ConvTranspose2dF16x3Fn(_ConvTranspose2dFn):
+    """The same function with the backward's matrix products in split binary16 (the arguments stay the six above)."""
+    _backward_precision = "f16x3"
+
+
+_FUNCTIONS = {"f32": _ConvTranspose2dFn, "f16x3": _ConvTranspose2dF16x3Fn}
 
 
 def _geometry_refusal(cin, cout, k, stride, pad, groups):
@@ -85,12 +97,15 @@ def _refusal(m):
     return _geometry_refusal(m.in_channels, m.out_channels, m.kernel_size[0], m.stride[0], m.padding[0], m.groups)
 
 
-def conv_transpose2d(x, weight, stride, padding, groups=1, add=None):
+def conv_transpose2d(x, weight, stride, padding, groups=1, add=None, backward_precision="f32"):
     """``F.conv_transpose2d(x, weight, None, stride, padding, groups=groups) (+ add)`` on the HIP kernels with autograd.  ``x`` is a
     logical [B,Cin,H,W] tensor on the device, NCHW-contiguous or channels_last (the kernels read NHWC; channels_last costs no
     copy); the result and the gradients are channels_last.  Depth-wise (groups == Cin == Cout, stride f in {2, 4}, kernel 2f,
     padding f // 2; ``add`` [B,C,fH,fW] is IDAUp's ``+ layers[i - 1]``, fused, and its gradient is grad_out itself) or dense
-    (groups 1, kernel 4, stride 2, padding 1, channels % 32 == 0; precision: ``hip.set_default_precision``)."""
+    (groups 1, kernel 4, stride 2, padding 1, channels % 32 == 0; precision: ``hip.set_default_precision``).
+    ``backward_precision``: "f32" or "f16x3", the arithmetic of the dense backward's matrix products
+    (``hip.ops.conv_transpose2d_backward``); a depth-wise layer is float32 in either."""
+    backward_precision = _precision_name(backward_precision)
     _on_device(x)
     groups = int(groups)
     if x.dim() != 4 or weight.dim() != 4 or weight.shape[0] != x.shape[1] or weight.shape[2] != weight.shape[3] or groups < 1:
@@ -106,28 +121,45 @@ def conv_transpose2d(x, weight, stride, padding, groups=1, add=None):
         want = (x.shape[0], x.shape[1], stride * x.shape[2], stride * x.shape[3])
         if tuple(add.shape) != want:
             raise RuntimeError("conv_transpose2d: add has shape %s, expected %s" % (tuple(add.shape), want))
-    return _ConvTranspose2dFn.apply(x, weight, add, stride, padding, groups)
+    return _FUNCTIONS[backward_precision].apply(x, weight, add, stride, padding, groups)
 
 
 class ConvTranspose2d(nn.ConvTranspose2d):
     """``nn.ConvTranspose2d`` whose forward and backward run on the library (``conv_transpose2d``).  Constructor, parameters,
     initial values, ``state_dict`` and ``repr`` are ``nn.ConvTranspose2d``'s; ``forward(input, add)`` adds ``add`` to the
-    up-sampled tensor inside the kernel (depth-wise layers: IDAUp's ``layers[i] + layers[i - 1]``)."""
+    up-sampled tensor inside the kernel (depth-wise layers: IDAUp's ``layers[i] + layers[i - 1]``);
+    the instance attribute ``backward_precision`` ("f32" at construction and after a re-class; ``set_backward_precision``) set to
+    "f16x3" runs a dense layer's backward matrix products in split binary16.  The class body adds nothing but ``forward``."""
 
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
+        self.backward_precision = "f32"
         why = _refusal(self)
         if why:
             raise NotImplementedError("centerpose_amd.deconv.ConvTranspose2d: " + why)
 
     def forward(self, input, add=None):
-        return conv_transpose2d(input, self.weight, self.stride[0], self.padding[0], self.groups, add)
+        return conv_transpose2d(input, self.weight, self.stride[0], self.padding[0], self.groups, add, getattr(self, "backward_precision", "f32"))
 
 
-def use_hip_deconvs(module):
+def set_backward_precision(module, name):
+    """Set ``backward_precision`` ("f32" or "f16x3") on every ``ConvTranspose2d`` under ``module`` (itself included); returns how
+    many were set.  ``PoseNetResDCN`` has three dense ones; a depth-wise layer takes the name and stays float32."""
+    return _set_backward_precision(module, name, lambda m: [(m, "backward_precision")] if isinstance(m, ConvTranspose2d) else [])
+
+
+def use_hip_deconvs(module, backward_precision=None):
     """Re-class every eligible ``nn.ConvTranspose2d`` under ``module`` (itself included) to ``ConvTranspose2d`` in place: the
     Parameter objects, the module names and the state-dict keys stay as they are.  Returns ``(converted, skipped)``: the
     converted modules' names and ``{name: reason}`` for the transposed convolutions left alone (a bias, ``output_padding``,
     dilation, a dtype other than float32, a geometry outside the two the library runs, subclasses).  Modules that already are
-    ``ConvTranspose2d`` appear in neither, and no other kind of module is mentioned or touched."""
-    return _reclass(module, (nn.ConvTranspose2d,), ConvTranspose2d, _refusal, of=" of nn.ConvTranspose2d")
+    ``ConvTranspose2d`` appear in neither, and no other kind of module is mentioned or touched.  ``backward_precision``: None
+    leaves every layer's attribute alone; a name sets it on every ``ConvTranspose2d`` under ``module`` afterwards
+    (``set_backward_precision``)."""
+    if backward_precision is not None:
+        _precision_name(backward_precision)
+    res = _reclass(module, (nn.ConvTranspose2d,), ConvTranspose2d, _refusal, of=" of nn.ConvTranspose2d",
+                   converted_hook=lambda m: setattr(m, "backward_precision", "f32"))
+    if backward_precision is not None:
+        set_backward_precision(module, backward_precision)
+    return res

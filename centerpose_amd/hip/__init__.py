@@ -28,7 +28,7 @@ from .metrics import (BOX_EVAL_FIELDS, BOX_EVAL_STRIDE, BOX_FLAG_CLIP_OVERFLOW, 
                       box_eval, box_iou)
 from .model import HipModel, LazyHeads
 from .ops import (CONV_BWD_GENERIC, CONV_BWD_LOWC, CONV_BWD_MFMA, batch_norm_backward, batch_norm_forward, conv2d_backward,
-                  conv2d_backward_path, conv2d_nhwc, conv2d_stem_backward, conv_transpose2d, conv_transpose2d_backward,
+                  conv2d_backward_path, conv2d_nhwc, conv2d_stem_backward, conv_transpose2d, conv_transpose2d_backward_f32 as conv_transpose2d_backward,
                   conv_transpose2d_dw, dcn_backward_is_fast, dcn_v2_backward_f32 as dcn_v2_backward, dcn_v2_forward, deterministic, group_norm_backward,
                   group_norm_forward, gru_gate_backward, gru_gate_forward, max_pool2d_backward, max_pool2d_forward,
                   pose_heads_backward, pose_heads_chunk_images, pose_heads_forward, resolve_deterministic, set_deterministic)

@@ -72,6 +72,9 @@ SIGNATURES = {
     "cp_conv_transpose2d_dw_nhwc": (c_int, _vp * 5 + _i * 5),
     "cp_conv_transpose2d_backward_workspace_bytes": (c_size_t, _i * 10),
     "cp_conv_transpose2d_backward_nhwc": (c_int, _vp * 6 + _i * 9 + _ws),
+    "cp_conv_transpose2d_backward_prec_workspace_bytes": (c_size_t, _i * 11),
+    "cp_conv_transpose2d_backward_prec_nhwc": (c_int, _vp * 6 + _i * 10 + _ws),
+    "cp_conv_transpose2d_backward_prec_mask": (c_int, _i * 10),
     "cp_batchnorm_workspace_bytes": (c_size_t, _i * 4),
     "cp_batchnorm_forward_nhwc": (c_int, _vp * 10 + _i * 5 + [c_float, c_float, c_int] + _ws),
     "cp_batchnorm_backward_nhwc": (c_int, _vp * 11 + _i * 5 + _ws),

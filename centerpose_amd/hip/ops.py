@@ -506,11 +506,15 @@ def conv_transpose2d_dw(x, w, f, add=None):
     return out
 
 
-def conv_transpose2d_backward(x, w, grad_out, stride, pad, groups=1, need_x_grad=True):
+def conv_transpose2d_backward(x, w, grad_out, stride, pad, groups=1, need_x_grad=True, precision="f32"):
     """Gradients of a bias-free ``ConvTranspose2d`` (cp_conv_transpose2d_backward_nhwc): x [B,H,W,Cin] NHWC, w [Cin,Cout/groups,K,K],
     grad_out [B,stride H,stride W,Cout] NHWC -> (grad_x [B,H,W,Cin] | None, grad_w like w).  Depth-wise (groups == Cin == Cout,
-    stride 2 or 4, K = 2 stride, pad = stride / 2) or dense (groups 1, K 4, stride 2, pad 1).  Float32 and bitwise reproducible."""
+    stride 2 or 4, K = 2 stride, pad = stride / 2) or dense (groups 1, K 4, stride 2, pad 1).  Bitwise reproducible.
+    ``precision``: "f32" (exact float32, the plain call) or "f16x3" (cp_conv_transpose2d_backward_prec_nhwc: the dense layer's
+    weight and data gradient in split binary16; depth-wise layers stay float32 --
+    ``conv_transpose2d_backward_precision_mask`` tells what a geometry gets)."""
     L = _abi.lib()
+    prec = _precision("conv_transpose2d_backward", precision)
     x, w, grad_out = _abi._dev(x), _abi._dev(w), _abi._dev(grad_out)
     stride, pad, groups = int(stride), int(pad), int(groups)
     if x.dim() != 4 or w.dim() != 4 or w.shape[0] != x.shape[3] or w.shape[2] != w.shape[3] or groups < 1:
@@ -518,16 +522,31 @@ def conv_transpose2d_backward(x, w, grad_out, stride, pad, groups=1, need_x_grad
                            % (tuple(x.shape), tuple(w.shape)))
     B, H, W, Cin = x.shape
     Cout, K = w.shape[1] * groups, w.shape[2]
-    ws = _abi._workspace(L.cp_conv_transpose2d_backward_workspace_bytes(B, H, W, Cin, Cout, K, stride, pad, groups,
-                                                                        int(bool(need_x_grad))),
+    query, call, tail = (("cp_conv_transpose2d_backward_prec_workspace_bytes", "cp_conv_transpose2d_backward_prec_nhwc", (prec,))
+                         if prec else ("cp_conv_transpose2d_backward_workspace_bytes", "cp_conv_transpose2d_backward_nhwc", ()))
+    ws = _abi._workspace(getattr(L, query)(B, H, W, Cin, Cout, K, stride, pad, groups, int(bool(need_x_grad)), *tail),
                          x.device, "conv_transpose2d_backward")
     _abi._check_shapes("conv_transpose2d_backward", [("grad_out", grad_out, (B, stride * H, stride * W, Cout))])
     grad_x = torch.empty_like(x) if need_x_grad else None
     grad_w = torch.empty_like(w)
-    rc = L.cp_conv_transpose2d_backward_nhwc(_abi._stream(), *_abi._ptrs(x, w, grad_out, grad_x, grad_w), B, H, W, Cin,
-                                             Cout, K, stride, pad, groups, _abi._ptr(ws), ws.numel())
-    _abi._check(rc, "cp_conv_transpose2d_backward_nhwc")
+    rc = getattr(L, call)(_abi._stream(), *_abi._ptrs(x, w, grad_out, grad_x, grad_w), B, H, W, Cin, Cout, K, stride, pad, groups,
+                          *tail, _abi._ptr(ws), ws.numel())
+    _abi._check(rc, call)
     return grad_x, grad_w
+
+
+def conv_transpose2d_backward_f32(x, w, grad_out, stride, pad, groups=1, need_x_grad=True):
+    """``conv_transpose2d_backward`` without the ``precision`` argument: what the package exports as
+    ``hip.conv_transpose2d_backward`` (its recorded signature); ``hip.ops.conv_transpose2d_backward`` is the operator with the
+    argument."""
+    return conv_transpose2d_backward(x, w, grad_out, stride, pad, groups, need_x_grad=need_x_grad, precision="f32")
+
+
+def conv_transpose2d_backward_precision_mask(B, H, W, Cin, Cout, K=4, stride=2, pad=1, groups=1, precision="f16x3"):
+    """What ``conv_transpose2d_backward(..., precision=precision)`` runs in f16x3 for a geometry
+    (cp_conv_transpose2d_backward_prec_mask; host arithmetic): bit 0 = the weight gradient, bit 1 = the data gradient."""
+    return _precision_mask("conv_transpose2d_backward_precision_mask", "conv_transpose2d_backward",
+                           "cp_conv_transpose2d_backward_prec_mask", precision, B, H, W, Cin, Cout, K, stride, pad, groups)
 
 
 def _pool_args(what, x, kernel, stride, pad):

@@ -223,8 +223,8 @@ _MISSING = {
     "hourglass": "the two-stack hourglass is composed by centerpose_amd.pose_net_hourglass.PoseNetHourglass, which returns one "
                  "head dict per stack (build one with PoseNetHourglass.from_model(model) and hand it back with "
                  "model.load_module(net))",
-    "resdcn": "the ResNet-DCN family is not composed (its layers train through use_hip_stems / use_hip_convs / use_hip_norms / "
-              "use_hip_pools / use_hip_deconvs on the reference's own tree)",
+    "resdcn": "the ResNet-DCN family is composed by centerpose_amd.pose_net_resdcn.PoseNetResDCN (build one with "
+              "PoseNetResDCN.from_model(model) and hand it back with model.load_module(net))",
 }
 
 

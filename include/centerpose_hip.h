@@ -606,7 +606,7 @@ int cp_conv_transpose2d_nhwc(cp_stream_t stream, const float* x, const float* w,
  * the `layers[i] + layers[i - 1]` of the following node fused (add and out [B,fH,fW,C]; NULL: no addend).  No workspace.
  * cp_conv_transpose2d_backward_nhwc: autograd's gradients of either layer from grad_out [B, stride H, stride W, Cout]:
  * grad_w in w's layout and grad_x [B,H,W,Cin], written, not accumulated; a NULL grad_x is not computed and not touched.
- * Arithmetic is float32 whatever cp_set_default_precision says; every sum has a fixed order and there are no atomics, so all
+ * Arithmetic is float32 whatever cp_set_default_precision says (the _prec calls below take their own); every sum has a fixed order and there are no atomics, so all
  * outputs are bitwise reproducible call to call.
  * Accepted geometries:
  *   depth-wise  groups == Cin == Cout, stride in {2, 4}, K == 2 stride, pad == stride / 2, C % 4 == 0, and the [K K][C] float
@@ -617,6 +617,18 @@ int cp_conv_transpose2d_nhwc(cp_stream_t stream, const float* x, const float* w,
  * those named *_or_null, a workspace below the query, B / H / W < 1, another geometry, a tensor of 2^31 elements or more, a
  * pointer that is not 16-byte aligned.  The query is host arithmetic and monotone in B; need_grad_x == 0 leaves out the data
  * gradient's operands.  Launches on `stream`, never synchronises.
+ *
+ * cp_conv_transpose2d_backward_prec_* are the same calls with a `precision` argument (CP_PREC_*).  CP_PREC_F32 IS the calls
+ * above: the same kernels, bits and workspace size.  CP_PREC_F16X3 runs the dense layer's two contractions in the
+ * split-binary16 arithmetic of cp_conv2d_backward_prec_nhwc (hi*hi + hi*lo + lo*hi, float32 accumulation, exact power-of-two
+ * pre-scales from |max| slots): the weight gradient on that operator's slab kernel with grad_out as the input and x as the
+ * output gradient (16 taps, stride 2, pad 1), the data gradient as the 4x4 / stride-2 convolution of grad_out on the forward's
+ * f16x3 implicit GEMM, w packed with a power-of-two scale per row.  A data gradient no f16x3 kernel takes (a tensor of
+ * 0xf0000000 bytes or more) stays float32.  The depth-wise layers have no matrix product: they are the float32 call bit for
+ * bit.  Fixed summation order, no atomics but the |max| slots': bitwise reproducible call to call.  The workspace is larger
+ * (the |max| slots, the split copies of grad_out and x, the packed weight).  cp_conv_transpose2d_backward_prec_mask (host
+ * arithmetic) reports what a geometry gets: bit 0 = the weight gradient, bit 1 = the data gradient runs in f16x3; 0 for
+ * CP_PREC_F32 and for depth-wise layers; CP_ERR_INVALID for a refused geometry.  Any other `precision` is refused.
  * ------------------------------------------------------------------------------------------ */
 int cp_conv_transpose2d_dw_nhwc(cp_stream_t stream, const float* x, const float* w, const float* add_or_null, float* out,
                                 int B, int H, int W, int C, int f);
@@ -625,6 +637,14 @@ size_t cp_conv_transpose2d_backward_workspace_bytes(int B, int H, int W, int Cin
 int cp_conv_transpose2d_backward_nhwc(cp_stream_t stream, const float* x, const float* w, const float* grad_out,
                                       float* grad_x_or_null, float* grad_w, int B, int H, int W, int Cin, int Cout, int K,
                                       int stride, int pad, int groups, void* workspace, size_t workspace_bytes);
+size_t cp_conv_transpose2d_backward_prec_workspace_bytes(int B, int H, int W, int Cin, int Cout, int K, int stride, int pad,
+                                                         int groups, int need_grad_x, int precision);
+int cp_conv_transpose2d_backward_prec_nhwc(cp_stream_t stream, const float* x, const float* w, const float* grad_out,
+                                           float* grad_x_or_null, float* grad_w, int B, int H, int W, int Cin, int Cout, int K,
+                                           int stride, int pad, int groups, int precision, void* workspace,
+                                           size_t workspace_bytes);
+int cp_conv_transpose2d_backward_prec_mask(int B, int H, int W, int Cin, int Cout, int K, int stride, int pad, int groups,
+                                           int precision);
 
 /* ------------------------------------------------------------------------------------------
  * MaxPool2d for training — Tree.downsample of models/networks/pose_dla_dcn.py:211-224 (kernel 2, stride 2, padding 0; it floors,

@@ -2,7 +2,8 @@
 cp_conv_transpose2d_backward_nhwc) next to F.conv_transpose2d under torch autograd, channels_last float32 tensors on the same
 device, in one process (GPU).
 
-    python tools/deconv_backward_bench.py [--batch 16] [--iters 10] [--rounds 3] [--out profiles/deconv_backward_bench.txt]
+    python tools/deconv_backward_bench.py [--batch 16] [--iters 10] [--rounds 3] [--precision f32|both]
+                                          [--out profiles/deconv_backward_bench.txt]
 
 Shapes at a 512 x 512 input: the eight depth-wise IDAUp / DLAUp layers of dla_34 (pose_dla_dcn.py:402-417) and the three dense
 deconv layers of resdcn_18 (resnet_dcn.py:232-240).  Per shape one JSON line: milliseconds of the forward alone and of forward +
@@ -14,6 +15,11 @@ ceiling.  Byte model -- a model, not a measurement of traffic; the backward's ti
 The dense layers are contractions (16 taps x Cin x Cout per output pixel), so their fraction of the streaming ceiling says how
 far they are from being memory-bound, not how good they are.  There is no speed gate: the reference time is torch's on the
 same device in the same run.
+
+``--precision both``: only the three dense layers, the operator alone (hip.ops.conv_transpose2d_backward on NHWC tensors, no
+autograd, no forward) with precision "f32" and "f16x3" alternating round by round after a warm-up of both: milliseconds of each
+(median round and all rounds), their ratio, what the f16x3 mask says runs in f16x3, and both modes' error against a float64
+reference of one image on the CPU.
 """
 import argparse
 import json
@@ -45,6 +51,8 @@ def main():
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--precision", default="f32", choices=["f32", "both"],
+                    help="both: the dense layers' backward operator in f32 and f16x3, alternating (nothing else is measured)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -63,7 +71,47 @@ def main():
         return e0.elapsed_time(e1) / a.iters
 
     lines = []
-    for where, kind, C, R, f in SHAPES:
+    if a.precision == "both":
+        from centerpose_amd import hip
+
+        for where, kind, C, R, f in SHAPES:
+            if kind != "dense":
+                continue
+            g = torch.Generator(device=dev).manual_seed(1)
+            x = torch.randn(B, R, R, C, device=dev, generator=g)
+            w = torch.randn(C, C, 4, 4, device=dev, generator=g)
+            go = torch.randn(B, 2 * R, 2 * R, C, device=dev, generator=g)
+            sides = {p: (lambda p=p: hip.ops.conv_transpose2d_backward(x, w, go, 2, 1, 1, precision=p)) for p in ("f32", "f16x3")}
+            for fn in sides.values():
+                fn()
+                fn()
+            rounds = {p: [] for p in sides}
+            for _ in range(a.rounds):
+                for p, fn in sides.items():
+                    rounds[p].append(timed(fn))
+            med = {p: statistics.median(v) for p, v in rounds.items()}
+            # both modes against float64 autograd of the first image (grad_w of that image alone)
+            x1, go1 = x[:1].permute(0, 3, 1, 2).cpu().double().requires_grad_(True), go[:1].permute(0, 3, 1, 2).cpu().double()
+            w1 = w.cpu().double().requires_grad_(True)
+            ref = torch.autograd.grad(F.conv_transpose2d(x1, w1, None, 2, 1), (x1, w1), go1)
+            err = {}
+            for p in sides:
+                gx, gw = hip.ops.conv_transpose2d_backward(x[:1].contiguous(), w, go[:1].contiguous(), 2, 1, 1, precision=p)
+                err[p] = {"grad_x": float((gx.permute(0, 3, 1, 2).cpu().double() - ref[0]).abs().max() / ref[0].abs().max()),
+                          "grad_w": float((gw.cpu().double() - ref[1]).abs().max() / ref[1].abs().max())}
+            flop = 2 * 2.0 * B * R * R * 16 * C * C     # the two contractions
+            line = {"where": where, "what": "backward operator", "B": B, "C": C, "HxW_in": R,
+                    "f16x3_mask": hip.ops.conv_transpose2d_backward_precision_mask(B, R, R, C, C),
+                    "backward_ms": {p: round(v, 4) for p, v in med.items()},
+                    "backward_ms_rounds": {p: [round(v, 4) for v in r] for p, r in rounds.items()},
+                    "f16x3_over_f32": round(med["f16x3"] / med["f32"], 3),
+                    "tflops": {p: round(flop / (v * 1e-3) / 1e12, 1) for p, v in med.items()},
+                    "max_rel_err_vs_float64_one_image": err}
+            print(json.dumps(line), flush=True)
+            lines.append(json.dumps(line))
+            del x, w, go, sides
+            torch.cuda.empty_cache()
+    for where, kind, C, R, f in SHAPES if a.precision == "f32" else ():
         g = torch.Generator(device=dev).manual_seed(1)
         cl = lambda t: t.contiguous(memory_format=torch.channels_last)
         groups, k, pad = (C, 2 * f, f // 2) if kind == "dw" else (1, 4, 1)

@@ -35,11 +35,12 @@ sys.path.insert(0, REPO)
 
 FAMILIES = {"conv2d_nhwc": "conv fwd", "conv2d_stem_backward": "stem bwd",
             "batch_norm_forward": "bn fwd", "batch_norm_backward": "bn bwd", "max_pool2d_forward": "pool fwd",
-            "max_pool2d_backward": "pool bwd", "conv_transpose2d_dw": "up fwd", "conv_transpose2d_backward": "up bwd",
+            "max_pool2d_backward": "pool bwd", "conv_transpose2d_dw": "up fwd",
             "dcn_v2_forward": "dcn fwd", "pose_heads_forward": "heads fwd"}
-# the layers reach these three through hip.ops, with a precision argument (hip.conv2d_backward, hip.pose_heads_backward and
+# the layers reach these four through hip.ops, with a precision argument (hip.conv2d_backward, hip.pose_heads_backward and
 # hip.dcn_v2_backward go through them too, so each call is bracketed once)
-OPS_FAMILIES = {"conv2d_backward_prec": "conv bwd", "pose_heads_backward_prec": "heads bwd", "dcn_v2_backward": "dcn bwd"}
+OPS_FAMILIES = {"conv2d_backward_prec": "conv bwd", "pose_heads_backward_prec": "heads bwd", "dcn_v2_backward": "dcn bwd",
+                "conv_transpose2d_backward": "up bwd"}
 
 
 def main():
