@@ -173,7 +173,7 @@ __global__ __launch_bounds__(256) void apply_kernel(const float* __restrict__ x,
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const float t = fmaf(v[i] - mu[i], a[i], sh[i]) + r[i];
-            out[i] = act ? fmaxf(t, 0.f) : t;
+            out[i] = act ? cp_relu(t) : t;
         }
         st4(y + o, out);
     };

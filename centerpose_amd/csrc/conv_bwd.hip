@@ -47,7 +47,7 @@ __global__ __launch_bounds__(256) void stage_kernel(const float* __restrict__ go
     for (int q = q_beg + pl; q < q_end; q += PL) {
         const size_t src = cv ? (size_t)q * Cout + c : 0;
         float v = go[src];
-        if (y) v = y[src] > 0.f ? v : 0.f;
+        if (y) v = cp_relu_gate(v, y[src]);
         v = cv ? v : 0.f;
         if (cw) gs[(size_t)q * CoP + c] = v;
         sum += v;
@@ -168,7 +168,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void w
 // own element order (whole 128-byte lines per slab) and scatter the one write.  `accum`: the value already in grad_w is added
 // LAST, to the finished sum of the slabs (a caller that works through its batch in chunks: chunks in chunk order); without it
 // the slabs' sum is stored as it is.  `ga`, `xa` (f16x3 slabs, conv_bwd16.hip): the |max| slots of the two operands; the finished
-// sum of the slabs is multiplied by 2^-e_g, then 2^-e_x (exact), before it is stored or accumulated.
+// sum of the slabs is scaled by 2^-(e_g + e_x) in one exact step (cp_scale_pow2) before it is stored or accumulated.
 __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ slab, float* __restrict__ gw, int nslab, int Cout,
                                                            int CoP, int Cin, int taps, int accum, const unsigned* __restrict__ ga,
                                                            const unsigned* __restrict__ xa) {
@@ -182,7 +182,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
     for (size_t base = (size_t)blockIdx.x * 32; base < n; base += (size_t)gridDim.x * 32) {  // (uniform per workgroup)
         const size_t i = base + (threadIdx.x & 31);
         float t = two_level_sum(red, i < n, nslab, 0.f, [&](float v, int s) { return v + slab[(size_t)s * ss + i]; });
-        if (ga) t = t * gi * xi;
+        if (ga) t = cp_scale_pow2(t, gi, xi);
         if (threadIdx.x < 32 && i < n) {
             const size_t h = i / TC;
             const int k = (int)(i - h * TC), tap = k / Cin, c = k - tap * Cin;

@@ -316,7 +316,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void d
             if (o < 0) continue;
             float* dst = gx + (size_t)o * Cin + n0 + r;
 #pragma unroll
-            for (int t = 0; t < NT; ++t) dst[32 * t] = acc[i][t][e] * gi * wi[t];
+            for (int t = 0; t < NT; ++t) dst[32 * t] = cp_scale_pow2(acc[i][t][e], gi, wi[t]);
         }
 }
 

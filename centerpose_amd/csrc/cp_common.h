@@ -60,14 +60,32 @@ struct Carve {
 };
 
 #ifdef __HIPCC__
+// ---- ReLU and its gradient gate as the training operators compute them: torch's rules, under which a NaN stays a NaN ----
+// relu(v) = 0 where v <= 0, else v: equal to fmaxf(v, 0.f) bit for bit on every number (-0 gives +0 either way), but a NaN
+// passes -- fmaxf(NaN, 0) is 0, which would turn a poisoned activation into a healthy-looking dead one ("Non-finite
+// values").  cp_relu_gate: threshold_backward, the gradient passes unless y <= 0, so it passes where y is NaN.
+__device__ __forceinline__ float cp_relu(float v) { return v <= 0.f ? 0.f : v; }
+__device__ __forceinline__ float cp_relu_gate(float g, float y) { return y <= 0.f ? 0.f : g; }
 // ---- |max| tracking and power-of-two operand scaling for the split-f16 kernels (see ConvParams::in_amax) ----
 // amax bits -> (2^e, 2^-e) with amax * 2^e in [2^14, 2^15): e = 14 - floor(log2(amax)).  Exponents are clamped so that
-// both factors stay normal float32 numbers (amax = 0 or < 2^-111: 2^125; inf / NaN inputs stay inf / NaN).
+// both factors stay normal float32 numbers (amax = 0 or < 2^-111: 2^125; inf / NaN inputs stay inf / NaN).  The upper clamp
+// leaves the largest binade [2^127, 2^128) at [2^15, 2^16) instead of [2^14, 2^15): still finite in binary16 -- the split's hi
+// half is rounded toward zero, so it stops at 65504 and the residual (< 32) goes to the lo half.  An infinite amax gets the
+// same factor 2^-112.  A limit of the mode: the forward kernels and the stride-1 data gradient form scale * inv
+// (weight factor times this inverse) before they multiply the accumulator, which under- or overflows for operands near 2^-112
+// against weights near 2^112 although the result would be an ordinary number; cp_scale_pow2 below is the form without it.
 __device__ __forceinline__ void cp_amax_to_scale(unsigned amax_bits, float* fwd, float* inv) {
     int e = (int)((amax_bits >> 23) & 0xffu);
     e = e < 16 ? 16 : (e > 253 ? 253 : e);
     *fwd = __uint_as_float((unsigned)(268 - e) << 23);
     *inv = __uint_as_float((unsigned)(e - 14) << 23);
+}
+// v * a * b for two of the power-of-two factors above, as ONE exact scaling: the exponents are added as integers and applied by
+// ldexpf.  Written v * a * b, the first product overflows where one operand is huge and the other tiny (grad_out near 2^127 with
+// weights near 2^-100: acc * 2^112 is infinite although acc * 2^112 * 2^-115 is an ordinary number); a * b first has the mirror
+// problem.  Equal to v * a * b bit for bit wherever no intermediate leaves the normal range.
+__device__ __forceinline__ float cp_scale_pow2(float v, float a, float b) {
+    return ldexpf(v, (int)((__float_as_uint(a) >> 23) & 0xffu) + (int)((__float_as_uint(b) >> 23) & 0xffu) - 254);
 }
 // A tensor's |max| lives in CP_AMAX_SUB sub-slots CP_AMAX_STRIDE uints apart (different cache lines): all waves of a
 // small kernel finish at about the same time, all find the slot still at its old value and all issue their atomic --

@@ -207,7 +207,7 @@ __global__ __launch_bounds__(256) void dcn_wgrad16_reduce_kernel(const float* __
     for (size_t base = (size_t)blockIdx.x * 32; base < n; base += (size_t)gridDim.x * 32) {  // (uniform per workgroup)
         const size_t i = base + (threadIdx.x & 31);
         float t = two_level_sum(red, i < n, nslab, 0.f, [&](float v, int s) { return v + slab[(size_t)s * ss + i]; });
-        t = t * gi * ci;
+        t = cp_scale_pow2(t, gi, ci);
         if (threadIdx.x < 32 && i < n) {
             const size_t h = i / TC;
             const int k = (int)(i - h * TC), tap = k / C, c = k - tap * C;

@@ -16,8 +16,12 @@ __device__ __forceinline__ Sample make_sample(float sy, float sx, int H, int W) 
     Sample s;
     s.in = !(sy <= -1.f || sx <= -1.f || sy >= (float)H || sx >= (float)W);
     const float fy = floorf(sy), fx = floorf(sx);
-    s.y0 = s.in ? (int)fy : -2;
-    s.x0 = s.in ? (int)fx : -2;
+    // `in` is true for a NaN coordinate (every comparison above is false): the sample's weights are NaN and so is everything it
+    // contributes to.  Its corner is (0, 0) by statement (fy == fy), not by what a float-to-int conversion makes of a NaN: for a
+    // finite coordinate `in` bounds y0 to [-1, H - 1] and x0 to [-1, W - 1], for a NaN one they are 0, and c1 .. c4 below then
+    // keep every corner that is read or written inside the image.
+    s.y0 = s.in ? (fy == fy ? (int)fy : 0) : -2;
+    s.x0 = s.in ? (fx == fx ? (int)fx : 0) : -2;
     s.lh = sy - fy;
     s.lw = sx - fx;
     s.hh = 1.f - s.lh;

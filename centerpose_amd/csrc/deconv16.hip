@@ -202,7 +202,7 @@ __global__ void __launch_bounds__(64 * DC_WAVES) deconv_kernel(DeconvArgs a) {
             for (int r = 0; r < 16; ++r) {
                 const int m = mw + 32 * i + F::row(r, lane);
                 float v = acc[i][j][r] * sc + sh;
-                if (a.relu) v = fmaxf(v, 0.f);
+                if (a.relu) v = cp_relu(v);
                 int b, ii, jj;
                 pd.split(m < M ? m : 0, &b, &ii, &jj);
                 const bool ok = n_ok && m < M;

@@ -86,7 +86,7 @@ __global__ __launch_bounds__(256) void thin_kernel(float* __restrict__ hb, const
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 if (j0 + u >= np) break;  // wave-uniform
-                const float a = fmaxf(v[u], 0.f);
+                const float a = cp_relu(v[u]);
                 float g = 0.f;
                 const float* gr = &gs[wv][(j0 + u) * CMAX];
 #pragma unroll
@@ -95,7 +95,7 @@ __global__ __launch_bounds__(256) void thin_kernel(float* __restrict__ hb, const
                     acc[c] = fmaf(a, gc, acc[c]);
                     g = fmaf(gc, w1r[c], g);
                 }
-                g = v[u] > 0.f ? g : 0.f;
+                g = cp_relu_gate(g, v[u]);
                 if (hv) hb[(size_t)(qb + j0 + u) * hid + h] = g;
                 gb0 += g;
                 if (AMAX) gm = fmaxf(gm, fabsf(g));

@@ -199,8 +199,12 @@ __global__ __launch_bounds__(NTHREADS, 3) void igemm_kernel(const ConvParams p, 
                         const float dh = om[2 * u_tap], dw = om[2 * u_tap + 1], mk = om[18 + u_tap];
                         const float h_im = (float)(a_h0[j] + u_kh) + dh;
                         const float w_im = (float)(a_w0[j] + u_kw) + dw;
-                        if (h_im > -1.f && w_im > -1.f && h_im < (float)p.H && w_im < (float)p.W) {
-                            const int h_lo = (int)floorf(h_im), w_lo = (int)floorf(w_im);
+                        // "inside" is written so that a NaN coordinate counts as inside, as make_sample (dcn_bwd_sample.h) has it:
+                        // its weights, and with them the sample, are NaN.  Its corner is (0, 0) by statement, not by what a
+                        // float-to-int conversion makes of a NaN; the four tests below then keep every index in the image.
+                        if (!(h_im <= -1.f || w_im <= -1.f || h_im >= (float)p.H || w_im >= (float)p.W)) {
+                            const float fh = floorf(h_im), fw = floorf(w_im);
+                            const int h_lo = fh == fh ? (int)fh : 0, w_lo = fw == fw ? (int)fw : 0;
                             const int h_hi = h_lo + 1, w_hi = w_lo + 1;
                             const float lh = h_im - (float)h_lo, lw = w_im - (float)w_lo;
                             const float hh = 1.f - lh, hw = 1.f - lw;
@@ -413,7 +417,7 @@ __global__ void splitk_epilogue_kernel(const ConvParams p) {
         }
         float y = acc * (sc * ainv) + sh;
         if (p.res) y += rs;
-        if (p.act == CP_ACT_RELU) y = fmaxf(y, 0.f);
+        if (p.act == CP_ACT_RELU) y = cp_relu(y);
         else if (p.act == CP_ACT_SIGMOID || (p.act == CP_ACT_SIGMOID_FROM && n >= p.act_from)) y = 1.f / (1.f + expf(-y));
         amax = fmaxf(amax, fabsf(y));
         if (p.store == CP_STORE_NHWC) p.out[(size_t)m * p.ldo + p.coff + n] = y;
@@ -464,7 +468,7 @@ __global__ __launch_bounds__(256) void splitk_epilogue4_kernel(const ConvParams 
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             if (p.res) y[e] += re[e];
-            if (p.act == CP_ACT_RELU) y[e] = fmaxf(y[e], 0.f);
+            if (p.act == CP_ACT_RELU) y[e] = cp_relu(y[e]);
             else if (p.act == CP_ACT_SIGMOID || (p.act == CP_ACT_SIGMOID_FROM && n + e >= p.act_from)) y[e] = 1.f / (1.f + expf(-y[e]));
             amax = fmaxf(amax, fabsf(y[e]));
         }

@@ -163,7 +163,10 @@ __device__ __forceinline__ void conv_in_scale_finish(const ConvParams& p, const 
 
 // Epilogue of every implicit-GEMM tile: y = acc*scale[n] + shift[n] (+ residual) -> ReLU / sigmoid -> NHWC or NCHW
 // store (folded eval-mode BatchNorm, conv bias, BasicBlock residual: pose_dla_dcn.py:48-62, DeformConv.actf :380-389).
-template <int FRAG, int MT, int NT, int WM, int WN>
+// KEEP_NAN: the ReLU is cp_relu (a NaN stays a NaN: every launch a training entry can make); false: the inference engine's
+// fmaxf, under which a NaN becomes 0 -- pw16.hip's instances, whose instruction streams are pinned (tests/test_pooled_store_cpu.py)
+// and which hip.conv2d_nhwc does not run for a layer that ends in a ReLU (ops.hip).
+template <int FRAG, int MT, int NT, int WM, int WN, bool KEEP_NAN = true>
 __device__ __forceinline__ void igemm_epilogue(const ConvParams& p, typename Frag<FRAG>::acc_t (&acc)[MT][NT], int tm,
                                                int tn, int wm, int wn, int lane, float ainv = 1.f) {
     typedef Frag<FRAG> F;
@@ -215,7 +218,7 @@ __device__ __forceinline__ void igemm_epilogue(const ConvParams& p, typename Fra
             }
             if (act == CP_ACT_RELU) {
 #pragma unroll
-                for (int r = 0; r < F::NACC; ++r) v[r] = fmaxf(v[r], 0.f);
+                for (int r = 0; r < F::NACC; ++r) v[r] = KEEP_NAN ? cp_relu(v[r]) : fmaxf(v[r], 0.f);
             } else if (act == CP_ACT_SIGMOID || act == CP_ACT_SIGMOID_FROM) {
 #pragma unroll
                 for (int r = 0; r < F::NACC; ++r) v[r] = sig_lane ? 1.f / (1.f + expf(-v[r])) : v[r];

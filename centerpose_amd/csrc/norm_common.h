@@ -42,7 +42,7 @@ __device__ __forceinline__ void st4(float* p, const float (&v)[4]) { *reinterpre
 __device__ __forceinline__ void un4(const float4 v, float (&o)[4]) { o[0] = v.x, o[1] = v.y, o[2] = v.z, o[3] = v.w; }
 
 __device__ __forceinline__ float4 gate4(const float4 g, const float4 y) {
-    return make_float4(y.x > 0.f ? g.x : 0.f, y.y > 0.f ? g.y : 0.f, y.z > 0.f ? g.z : 0.f, y.w > 0.f ? g.w : 0.f);
+    return make_float4(cp_relu_gate(g.x, y.x), cp_relu_gate(g.y, y.y), cp_relu_gate(g.z, y.z), cp_relu_gate(g.w, y.w));
 }
 
 // One slab's statistics per channel: out[0][c] = the mean, out[1][c] = M2 = sum (x - mean)^2 over the slab's `len` rows, which

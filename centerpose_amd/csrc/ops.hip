@@ -481,6 +481,9 @@ int cp_conv2d_nhwc(cp_stream_t stream, const float* x, const float* w, const flo
     int rc = stage_conv(cw, r, f16x3, w, scale, shift, Cin, Cout, KH, KW, x, (size_t)B * H * W * Cin, nullptr, 0, s);
     if (rc != CP_OK) return fail(rc, "conv2d_forward: weight packing failed");
     ConvParams p = conv_params(B, H, W, &x, &Cin, 1, cw, stride, pad, act);
+    // A ReLU of this entry keeps a NaN (cp_relu).  pw16.hip's epilogue keeps the inference engine's fmaxf -- its instruction stream
+    // is pinned (tests/test_pooled_store_cpu.py) -- so a 1x1 layer that ends in a ReLU takes the LDS-staged loop here.
+    if (act == CP_ACT_RELU) p.dbg |= CP_SEL_PW16_NEVER;
     p.res = residual;
     p.res_ld = Cout;
     p.out = out;

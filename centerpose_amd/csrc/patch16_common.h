@@ -74,7 +74,7 @@ __device__ __forceinline__ void patch_epilogue(const ConvParams& p, Frag<32>::ac
             }
             if (act == CP_ACT_RELU) {
 #pragma unroll
-                for (int r = 0; r < F::NACC; ++r) v[r] = fmaxf(v[r], 0.f);
+                for (int r = 0; r < F::NACC; ++r) v[r] = cp_relu(v[r]);
             } else if (act == CP_ACT_SIGMOID || act == CP_ACT_SIGMOID_FROM) {
 #pragma unroll
                 for (int r = 0; r < F::NACC; ++r) v[r] = sig_lane ? 1.f / (1.f + expf(-v[r])) : v[r];

@@ -137,7 +137,7 @@ __global__ __launch_bounds__(256, 2) void pw16_kernel(const ConvParams p, const 
             }
         }
     }
-    igemm_epilogue<32, 1, NT, 4, 1>(p, acc, tm, tn, wid, 0, lane, ainv);
+    igemm_epilogue<32, 1, NT, 4, 1, false>(p, acc, tm, tn, wid, 0, lane, ainv);
 }
 
 // The same stream with the A operand loaded in WHOLE LINES and turned into fragments by a wave-private LDS round trip (round 6).
@@ -330,7 +330,7 @@ __global__ __launch_bounds__(256, NT == 2 ? 3 : 2) void pw16s_kernel(const ConvP
         }
     }
     if (POOL) pw16s_pool_epilogue<NT>(p, acc, tn, lane, ainv, live, pair_row, blk);
-    else igemm_epilogue<32, 1, NT, 4, 1>(p, acc, tm, tn, wid, 0, lane, ainv);
+    else igemm_epilogue<32, 1, NT, 4, 1, false>(p, acc, tm, tn, wid, 0, lane, ainv);
 }
 
 template <int NT>

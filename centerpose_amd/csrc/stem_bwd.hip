@@ -105,7 +105,7 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const float* __restrict
 #pragma unroll
                 for (int ct = 0; ct < NCO; ++ct) {
                     float v = go[p + 16 * ct];
-                    if (y) v = y[p + 16 * ct] > 0.f ? v : 0.f;
+                    if (y) v = cp_relu_gate(v, y[p + 16 * ct]);
                     a[u][ct] = ok ? v : 0.f;
                 }
             }

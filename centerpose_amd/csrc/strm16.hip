@@ -188,7 +188,7 @@ __global__ __launch_bounds__(64 * SM_WAVES, 1) void strm16_kernel(const ConvPara
                 }
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    v[e] = fmaxf(v[e], relu_floor);
+                    v[e] = v[e] <= relu_floor ? relu_floor : v[e];  // (cp_relu's rule: a NaN stays a NaN)
                     v[e] = n0 + e < p.Cout ? v[e] : 0.f;
                     amax = fmaxf(amax, fabsf(v[e]) * okf);
                 }

@@ -71,7 +71,7 @@ def reference_backward(inp, residual, gate_y=None, training=True, affine=True):
     out, leaves, _, _ = _pre(inp, residual, training, affine)
     g = inp.go.double()
     if gate_y is not None:
-        g = g * (gate_y > 0).double()
+        g = torch.where(gate_y <= 0, torch.zeros_like(g), g)   # torch's threshold_backward: a NaN y passes the gradient
     grads = torch.autograd.grad(out, [t for t in leaves if t is not None], g)
     it = iter(grads)
     return dict(zip(("grad_x", "grad_gamma", "grad_beta", "grad_residual"), [next(it) if t is not None else None for t in leaves]))

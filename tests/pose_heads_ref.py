@@ -67,7 +67,8 @@ def manual_backward64(feat, params, grad_outs):
         h = F.conv2d(x, w0, b0, padding=1)
         gw1 = torch.einsum("bcyx,bhyx->ch", go, F.relu(h)).reshape(w1.shape)
         gb1 = go.sum(dim=(0, 2, 3))
-        gh = torch.einsum("bcyx,ch->bhyx", go, w1[:, :, 0, 0]) * (h > 0)
+        gh = torch.einsum("bcyx,ch->bhyx", go, w1[:, :, 0, 0])
+        gh = torch.where(h <= 0, torch.zeros_like(gh), gh)   # torch's threshold_backward: a NaN h passes the gradient
         gb0 = gh.sum(dim=(0, 2, 3))
         gw0 = _wgrad3x3(x, gh)
         gfeat += F.conv_transpose2d(gh, w0, padding=1)
