@@ -428,6 +428,15 @@ __global__ __launch_bounds__(64) void pnp_kernel(const float* __restrict__ pts, 
 
     const int iters = lm_refine16(q, param, sub);
     if (sub == 0) o[35] = nv;
+    // A model that spans no volume with sc > DBL_EPS (relative size (0, 1, 0): eight points on a segment) leaves a singular
+    // 3 x 3 block, polar3 divides by its determinant, and the walk carries NaN to its iteration cap; `param[5] < 0` is false
+    // for NaN, so write_pose16 would report it as a pose.  Same test as pnp_rare_kernel's (identical on the 16 lanes).
+    bool finite = true;
+    for (int k = 0; k < 6; ++k) finite = finite && (param[k] == param[k]) && fabs(param[k]) < 1e300;
+    if (!finite) {
+        if (sub == 0) o[0] = 0;
+        return;
+    }
     write_pose16(q, param, iters, o, sub);
 }
 

@@ -323,8 +323,10 @@ def is_planar(obj):
     return w[2] / w[1] < 1e-3
 
 
-def solve_pnp_iterative(obj, img, Kmat, max_iter=20, eps=FLT_EPSILON, return_iters=False):
-    """SOLVEPNP_ITERATIVE for >= 6 non-planar points, zero distortion.  Returns (ok, rvec, tvec)."""
+def solve_pnp_iterative(obj, img, Kmat, max_iter=20, eps=FLT_EPSILON, return_iters=False, init=None):
+    """SOLVEPNP_ITERATIVE for >= 6 non-planar points, zero distortion.  Returns (ok, rvec, tvec).
+    ``init`` = (rvec, tvec) replaces the planar / DLT initialisation (tests measure how far two correct Levenberg-Marquardt
+    walks of one problem end from each other with it; OpenCV's useExtrinsicGuess)."""
     obj = np.asarray(obj, np.float64)
     img = np.asarray(img, np.float64)
     Kmat = np.asarray(Kmat, np.float64)
@@ -333,7 +335,9 @@ def solve_pnp_iterative(obj, img, Kmat, max_iter=20, eps=FLT_EPSILON, return_ite
         raise ValueError("solvePnP needs at least 4 points")
     fx, fy, cx, cy = Kmat[0, 0], Kmat[1, 1], Kmat[0, 2], Kmat[1, 2]
     mn = np.stack([(img[:, 0] - cx) / fx, (img[:, 1] - cy) / fy], axis=1)
-    if is_planar(obj):
+    if init is not None:
+        r, t = np.asarray(init[0], np.float64).reshape(3), np.asarray(init[1], np.float64).reshape(3)
+    elif is_planar(obj):
         r, t = planar_init(obj, mn)
     elif N < 6:
         raise ValueError("DLT algorithm needs at least 6 points (OpenCV asserts here; the reference switches to EPnP)")
@@ -388,12 +392,14 @@ def _lm_step(JtJ, JtErr, prev_param, lambda_lg10):
     return prev_param - delta
 
 
-def solve_pnp_any(obj, img, Kmat, epnp=False):
+def solve_pnp_any(obj, img, Kmat, epnp=False, **lm):
     """cv2.solvePnPGeneric as the reference calls it (cuboid_pnp_solver.py:162-171): SOLVEPNP_EPNP when fewer than 6
-    correspondences survive, SOLVEPNP_ITERATIVE (planar or DLT initialisation + LM) otherwise."""
+    correspondences survive, SOLVEPNP_ITERATIVE (planar or DLT initialisation + LM) otherwise.  ``lm``: max_iter / init of
+    / return_iters of solve_pnp_iterative (EPnP has no refinement to apply them to: 0 iterations)."""
     if epnp:
-        return solve_pnp_epnp(obj, img, Kmat)
-    return solve_pnp_iterative(obj, img, Kmat)
+        r = solve_pnp_epnp(obj, img, Kmat)
+        return r + (0,) if lm.get("return_iters") else r
+    return solve_pnp_iterative(obj, img, Kmat, **lm)
 
 
 def axis_angle_quat_xyzw(rvec):
@@ -414,10 +420,13 @@ def quat_xyzw_to_matrix(q):
                      [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
 
 
-def solve_cuboid_pnp(points2d, scale, Kmat, opencv_return=False):
+def solve_cuboid_pnp(points2d, scale, Kmat, opencv_return=False, reject=None, **lm):
     """CuboidPNPSolver.solve_pnp (cuboid_pnp_solver.py:91-239) for one detection.
     points2d: (8*n, 2), entries with x or y < -5000 are invalid.  scale: relative cuboid size.
-    Returns dict(location, quaternion_xyzw, projected_points (8x2), rvec, tvec, reproj_err) or None."""
+    Returns dict(location, quaternion_xyzw, projected_points (8x2), rvec, tvec, reproj_err, iters = Levenberg-Marquardt
+    iterations) or None; a list passed as
+    ``reject`` receives why it is None ("few_points", "solver_failed" or "behind_camera").  ``lm``: see solve_pnp_any."""
+    reject = [] if reject is None else reject
     pts = np.asarray(points2d, np.float64).reshape(-1, 2)
     verts = cuboid_vertices(np.asarray(scale, np.float64) / scale[1])  # cuboid_pnp_shell.py:12
     n_per = len(pts) / 8
@@ -430,9 +439,11 @@ def solve_cuboid_pnp(points2d, scale, Kmat, opencv_return=False):
     o2 = np.array(o2, dtype=float)
     o3 = np.array(o3, dtype=float)
     if len(o2) < 4:
+        reject.append("few_points")
         return None
-    ok, rvec, tvec = solve_pnp_any(o3, o2, Kmat, epnp=len(o2) < 6)
+    ok, rvec, tvec, iters = solve_pnp_any(o3, o2, Kmat, epnp=len(o2) < 6, return_iters=True, **lm)
     if not ok:
+        reject.append("solver_failed")
         return None
     proj_v = project_points(o3, rvec, tvec, Kmat)
     reproj = float(np.linalg.norm(proj_v - o2) / np.sqrt(2 * len(o2)))
@@ -443,13 +454,14 @@ def solve_cuboid_pnp(points2d, scale, Kmat, opencv_return=False):
     rvec_gl = matrix_to_rodrigues(R_gl)
     projected = project_points(verts, rvec, tvec, Kmat)
     if tvec[2] < 0:
+        reject.append("behind_camera")
         return None
     if opencv_return:
         loc, quat = tvec.copy(), axis_angle_quat_xyzw(rvec)
     else:
         loc, quat = t_gl, axis_angle_quat_xyzw(rvec_gl)
     return {"location": loc, "quaternion_xyzw": quat, "projected_points": projected, "rvec": rvec, "tvec": tvec,
-            "reproj_err": reproj}
+            "reproj_err": reproj, "iters": iters}
 
 
 def pnp_shell(points2d, scale, Kmat, width, height, category="cup", kps=None, opencv_return=False):

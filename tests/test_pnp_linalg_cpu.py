@@ -226,3 +226,62 @@ def test_jacobi_eig_floor_exit_changes_nothing_on_well_conditioned_matrices(host
         w1, V1 = run(A, 1)
         np.testing.assert_allclose(A @ V1, V1 * w1[None, :], atol=1e-9 * np.abs(w1).max())
         assert np.sum(np.abs(w1) < 1e-9 * np.abs(w1).max()) == 5
+
+
+def _singular_rotations():
+    from tests.pnp_edge_cases import AXES, M_GL, THETAS
+
+    for ax in AXES:
+        for th in THETAS:
+            Rax = opnp.rodrigues_to_matrix(np.array(ax) * th)
+            yield ax, th, "cv", Rax                # the rotation the DLT / homography start hands to rot_to_rvec
+            yield ax, th, "gl", M_GL @ (M_GL.T @ Rax)  # the OpenGL-frame product write_pose hands to it (M R with R = M^T rot)
+            yield ax, th, "gl of cv", M_GL @ Rax   # and the OpenGL-frame rotation of an OpenCV-frame singular pose
+
+
+def test_rot_to_rvec_at_singular_angles(host):
+    """theta in {0, 1e-12, 1e-8, 1e-4, pi - 1e-4, pi - 1e-8, pi - 1e-12, pi} about x, y, z and (1, 2, 3) / sqrt(14): the
+    theta -> 0 and theta -> pi branches (s < 1e-5) and their neighbours, against oracle.pnp.matrix_to_rodrigues.  Rotation
+    MATRICES rebuilt from both vectors are compared, since at pi the sign of the axis is free.  Limits: inside the singular
+    branches the angle is acos of a cosine that has rounded to +-1 and the axis comes from sqrt((R_ii + 1) / 2), so an ulp of
+    R moves the result by sqrt(DBL_EPSILON) = 1.5e-8 (the oracle re-orthogonalises R by an SVD first, the device code does
+    not): 2e-7, the limit test_polar_factor_and_rotation_vector already uses beyond 3.1 rad.  In the regular branch
+    v = theta / (2 s) with s >= 1e-5 loses at most 1e-16 / 1e-5: 1e-10."""
+    n_zero = n_pi = 0
+    for ax, th, frame, R in _singular_rotations():
+        Rc = np.ascontiguousarray(R.reshape(9))
+        r = np.zeros(3)
+        host.pnp_host_rot_to_rvec(_ptr(Rc), _ptr(r))
+        assert np.isfinite(r).all(), (ax, th, frame, r)
+        s = 0.5 * np.sqrt((R[2, 1] - R[1, 2]) ** 2 + (R[0, 2] - R[2, 0]) ** 2 + (R[1, 0] - R[0, 1]) ** 2)
+        tol = 2e-7 if s < 1e-5 else 1e-10
+        np.testing.assert_allclose(opnp.rodrigues_to_matrix(r), opnp.rodrigues_to_matrix(opnp.matrix_to_rodrigues(R)), rtol=0, atol=tol,
+                                   err_msg="%s theta=%r %s" % (ax, th, frame))
+        np.testing.assert_allclose(opnp.rodrigues_to_matrix(r), R, rtol=0, atol=tol, err_msg="%s theta=%r %s" % (ax, th, frame))
+        if s < 1e-5 and np.trace(R) > 1:
+            assert not r.any()          # cv::Rodrigues returns the zero vector there, and axis_angle_quat then divides 0 / 0
+            n_zero += 1
+        if s < 1e-5 and np.trace(R) < 1:
+            assert abs(np.linalg.norm(r) - np.pi) < 2e-7
+            n_pi += 1
+    assert n_zero >= 24 and n_pi >= 24  # both singular branches are reached, in both frames
+
+
+def test_rodrigues_jacobian_at_zero_and_next_to_it(host):
+    """theta = 0 (the identity branch: R = I, dR/dr = the three generators) and theta = 1e-12 (the first angle of the general
+    branch: 1 - cos rounds to 0, sin(theta) / theta to 1), against the oracle's rodrigues_to_matrix(jac=True)."""
+    from tests.pnp_edge_cases import AXES
+
+    for ax in AXES:
+        for th in (0.0, 1e-12):
+            r = np.ascontiguousarray(np.array(ax) * th)
+            R, J, R2 = np.zeros(9), np.zeros(27), np.zeros(9)
+            host.pnp_host_rodrigues(_ptr(r), _ptr(R), _ptr(J))
+            host.pnp_host_rodrigues_nojac(_ptr(r), _ptr(R2))
+            Ro, Jo = opnp.rodrigues_to_matrix(r, jac=True)
+            np.testing.assert_allclose(R.reshape(3, 3), Ro, rtol=0, atol=1e-15)
+            np.testing.assert_array_equal(R, R2)
+            np.testing.assert_allclose(J.reshape(3, 9), Jo, rtol=0, atol=1e-15)
+            # and against what it must be: the generators of so(3), to first order in theta
+            G = np.array([[0, 0, 0, 0, 0, -1, 0, 1, 0], [0, 0, 1, 0, 0, 0, -1, 0, 0], [0, -1, 0, 1, 0, 0, 0, 0, 0]], np.float64)
+            np.testing.assert_allclose(J.reshape(3, 9), G, rtol=0, atol=2 * th + 1e-15)
