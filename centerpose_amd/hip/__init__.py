@@ -8,9 +8,10 @@ One job per module -- ``_abi``: the library, the table of its signatures and the
 ``_structs``: the header's structs; ``ops``: the stand-alone operators; ``detect``: preprocess to poses; ``model``: the
 network; ``track``: the device tracker; ``metrics``: the box metrics; ``train``: loss, targets and input images; ``optim``: the clip + Adam
 step and the gradient pack of data-parallel training, reached as ``hip.optim.NAME``; ``sync_norm``: SyncBatchNorm's four
-phases, reached as ``hip.sync_norm.NAME`` (the names re-exported here are a recorded surface).  This file only re-exports: callers use ``hip.NAME``, and the modules that time or stub an operator replace ``hip.NAME``.
+phases, reached as ``hip.sync_norm.NAME``; ``draw``: the overlay, reached as ``hip.draw.NAME`` (the names re-exported here are a recorded surface).  This file only re-exports: callers use ``hip.NAME``, and the modules that time or stub an operator replace ``hip.NAME``.
 """
 from . import _abi
+from . import draw
 from . import optim
 from . import sync_norm
 from ._abi import (ABI_VERSION, CP_ERR_INVALID, LIB_PATH, PRECISIONS, KernelSel, _dev, _nhwc_view, exported_symbols, lib,

@@ -9,7 +9,7 @@ from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_size_
 
 import torch
 
-from ._structs import PoseLossDesc, PoseTargetsDesc, PoseTargetsTrackDesc, PoseTargetsTrackDetDesc, TrackParams
+from ._structs import DrawParams, PoseLossDesc, PoseTargetsDesc, PoseTargetsTrackDesc, PoseTargetsTrackDetDesc, TrackParams
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))  # centerpose_amd/, where csrc/Makefile leaves the library
 # $CENTERPOSE_HIP_LIB selects another build of the same ABI (tuning variants: make -C csrc EXP=n)
@@ -159,6 +159,10 @@ SIGNATURES = {
     "cp_grad_pack_table_bytes": (c_size_t, _i + [POINTER(c_int64)] + _pi),
     "cp_grad_pack_table_build": (c_int, [c_void_p, c_size_t] + _i + _pvp + [POINTER(c_int64)] * 2 + _pi),
     "cp_grad_pack": (c_int, _vp * 2 + _i * 2 + _vp + [c_int64, c_float]),
+    "cp_draw_workspace_bytes": (c_size_t, _i * 2),
+    "cp_draw_primitives": (c_int, _vp * 2 + _i * 3 + [c_size_t] + _vp + _i + _ws),
+    "cp_draw_detections": (c_int, _vp * 5 + _i * 2 + [POINTER(DrawParams)] + _vp),
+    "cp_draw_tracks": (c_int, _vp * 2 + _i * 2 + _vp + [POINTER(DrawParams)] + _vp),
 }
 
 

@@ -90,3 +90,18 @@ class PoseTargetsTrackDetDesc(ctypes.Structure):
 TI_STRIDE = 24
 TI_IMG = dict(offset=0, height=1, width=2, trans=3, flipped=9, color=10, order=11, alpha=12, shift=15)
 TI_ORDERS = ("bcs", "bsc", "cbs", "csb", "sbc", "scb")  # order code -> brightness / contrast / saturation as run
+
+
+# ---- the overlay (cp_draw_*): primitive kinds, the slots of a record and the params struct of include/centerpose_hip.h ----
+DRAW_SEGMENT, DRAW_DISC, DRAW_RECT, DRAW_FILL, DRAW_GLYPH = 1, 2, 3, 4, 5
+DRAW_COORD_MIN, DRAW_COORD_MAX, DRAW_MAX_DIM, DRAW_MAX_P = -8192, 8191, 8192, 65536
+DRAW_SLOTS = 44
+DRAW_SLOT = dict(box=0, label=1, discs=15, edges=23, cross=35, axes=41)
+DRAW_LABEL_CHARS, DRAW_LABEL_SCALE = 13, 2
+DRAW_CAT0 = {"black": 0xFFFFFF, "white": 0x8080FF}  # the reference's category-0 colour per theme, B | G << 8 | R << 16
+
+
+class DrawParams(ctypes.Structure):
+    """cp_draw_params of include/centerpose_hip.h (field for field)."""
+    _fields_ = [("vis_thresh", ctypes.c_double)] + \
+               [(n, c_int) for n in ("reg_bbox", "show_axes", "paper_display", "tracking_task", "theme", "labels", "width", "height")]

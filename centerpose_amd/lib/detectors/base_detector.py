@@ -8,8 +8,13 @@ CenterPoseTrack (``opt.tracking_task``) and the Kalman baseline (``opt.refined_K
 per-frame loop (:445-464 previous-frame inputs rendered from the tracks, :501-544 Gaussian fusion of the two keypoint
 estimates, :660-665 ``tracker.step``); the previous-frame heat-maps are drawn on the device (cp_render_gaussians).
 
-Not mirrored (out of scope for the inference hot path): the Debugger drawing
-(debug 1-3 only prints) and the GMM sampling of rep_mode 2.
+With ``opt.debug`` >= 1 ``run`` builds a ``Debugger`` (utils/debugger.py) as the reference does (:393) and hands it to
+``show_results`` / ``save_results``: ``--debug 4`` writes ``<demo_save>/<name>/<file>_out_img_pred.png`` beside the JSON,
+drawn by the library's own rasteriser (cp_draw_primitives).  ``run_batch(..., draw=frames)`` draws a batch's detections into
+device frames without a read-back (cp_draw_detections).
+
+Not mirrored: the heat-map views of ``debug()`` (debug 2 / 3: gen_colormap, add_blend_img, add_arrow),
+cv2's anti-aliasing and font, and the GMM sampling of rep_mode 2.
 """
 import copy
 import json
@@ -445,22 +450,30 @@ class BaseDetector(object):
         tot_time += end_time - start_time
 
         dict_out = self._dict_out(meta, boxes)
-        if self.opt.debug >= 1 and self.opt.debug < 4:
-            self.show_results(None, image, results)
-        elif self.opt.debug == 4:
-            self.save_results(None, image, results, image_or_path_or_tensor, dict_out)
+        if self.opt.debug >= 1:  # (nothing is constructed or drawn at debug 0: the timed path)
+            from ..utils.debugger import Debugger
+            debugger = Debugger(dataset=self.opt.dataset, ipynb=(self.opt.debug == 3), theme=self.opt.debugger_theme,
+                                device=self.opt.device)   # base_detector.py:393
+            if self.opt.debug < 4:
+                self.show_results(debugger, image, results)
+            elif self.opt.debug == 4:
+                self.save_results(debugger, image, results, image_or_path_or_tensor, dict_out)
         return {'results': results, 'boxes': boxes, 'output': output, 'tot': tot_time, 'load': load_time,
                 'pre': pre_time, 'net': net_time, 'dec': dec_time, 'post': post_time, 'merge': merge_time,
                 'pnp': pnp_time, 'track': track_time}
 
-    def run_batch(self, images, metas):
+    def run_batch(self, images, metas, draw=None):
         """Batched inference (added): ``images`` [B,3,H,W] already pre-processed (float32, on any device),
         ``metas`` a list of B meta dicts as produced by ``pre_process`` (+ 'camera_matrix').  Returns a list of
         B dicts with the keys of ``run`` ('results', 'boxes'); the network, decode and PnP each run once
-        for the whole batch."""
+        for the whole batch.  ``draw``: device uint8 frames [B,H,W,3] in the original image size; the detections are drawn
+        into them in place (cp_draw_detections + cp_draw_primitives) behind the PnP, on its stream, before anything is read
+        back.  The returned records do not depend on it."""
         t0 = time.time()
         images = images.to(self.opt.device)
         on_device = self.opt.device.type == 'cuda' and hasattr(self, 'post_process_merge_device')
+        if draw is not None and not on_device:
+            raise RuntimeError("run_batch: draw= needs the device post-process (a CUDA device)")
         self._skip_host_dets = on_device  # the packed detections stay on the device
         try:
             output, dets = self.process(images, None, None, None, None)
@@ -471,7 +484,7 @@ class BaseDetector(object):
         outs = []
         if on_device:
             # coordinate transform + threshold + soft-NMS of the whole batch in one launch (cp_postprocess)
-            all_results = self.post_process_merge_device(metas)
+            all_results = self.post_process_merge_device(metas, draw=draw)
         else:
             all_results = []
             for b, meta in enumerate(metas):
@@ -510,12 +523,15 @@ class BaseDetector(object):
                          'pnp': t3 - t2})
         return outs
 
-    def save_results(self, debugger, image, results, image_or_path_or_tensor, dict_out=None):
-        """JSON side of object_pose.py:383-414 (image drawing is out of scope)."""
+    def _demo_target(self):
+        """`<demo_save>/<folder or source name>` (object_pose.py:394-401)."""
         if os.path.isdir(self.opt.demo):
-            target = os.path.join(self.opt.demo_save, os.path.basename(self.opt.demo))
-        else:
-            target = os.path.join(self.opt.demo_save, os.path.splitext(os.path.basename(self.opt.demo))[0])
+            return os.path.join(self.opt.demo_save, os.path.basename(self.opt.demo))
+        return os.path.join(self.opt.demo_save, os.path.splitext(os.path.basename(self.opt.demo))[0])
+
+    def save_results(self, debugger, image, results, image_or_path_or_tensor, dict_out=None):
+        """JSON side of object_pose.py:383-414 (ObjectPoseDetector.save_results adds the picture)."""
+        target = self._demo_target()
         os.makedirs(target, exist_ok=True)
         if dict_out is not None and isinstance(image_or_path_or_tensor, str):
             name = os.path.splitext(os.path.basename(image_or_path_or_tensor))[0]

@@ -96,8 +96,10 @@ class BatchedTracking(object):
         seeds, counts = _hip.pack_seeds(lists, params, gt)
         return seeds, counts, gt
 
-    def _step_device(self, images, metas, read):
-        """The whole frame on the device (cp_track_step); the host builds nothing unless ``read``."""
+    def _step_device(self, images, metas, read, draw=None):
+        """The whole frame on the device (cp_track_step); the host builds nothing unless ``read``.  ``draw``: device uint8
+        frames [B,H,W,3] in the original image size, into which the tracks of this frame's boxes are drawn (cp_draw_tracks +
+        cp_draw_primitives) behind the track update, on its stream, without a synchronisation."""
         from centerpose_amd import hip as _hip
 
         det, opt, B = self.det, self.det.opt, self.n
@@ -144,6 +146,9 @@ class BatchedTracking(object):
         # must not move either.  The periodic overflow check raises AFTER the device has advanced, so it runs once the host's
         # view has followed.
         self.dev.step(rec, cnt, poses, check=False)
+        if draw is not None:
+            params = _hip.draw.draw_params(opt, width=draw.shape[2], height=draw.shape[1], labels=True)
+            _hip.draw.draw_primitives(draw, _hip.draw.draw_tracks(self.dev.state, B, self.dev.cap, self.dev.vmeta[:, 10:14], params))
         self.pre_images = images
         self.frames += 1
         self.dev.check_due()
@@ -161,16 +166,19 @@ class BatchedTracking(object):
         self.times['steps'] += 1
         return outs
 
-    def step(self, images, metas, read=True):
+    def step(self, images, metas, read=True, draw=None):
         """images [B,3,H,W] pre-processed frames (frame t of each video), metas: B meta dicts as ``pre_process`` builds
         them (+ 'camera_matrix', 'id').  Returns a list of B dicts {'results': tracks, 'boxes': boxes} (``read=False``
-        with the device tracker: None, the tracks stay in HBM)."""
+        with the device tracker: None, the tracks stay in HBM).  ``draw`` (device tracker only): device uint8 frames
+        [B,H,W,3] in the original image size that get this frame's tracks drawn in place, without leaving the device."""
         det, opt = self.det, self.det.opt
         B = self.n
         if images.shape[0] != B or len(metas) != B:
             raise ValueError("expected one frame and one meta per video")
+        if draw is not None and not self.device_tracker:
+            raise RuntimeError("BatchedTracking.step: draw= needs the device tracker (the host tracker's lists are drawn by Debugger)")
         if self.device_tracker:
-            return self._step_device(images, metas, read)
+            return self._step_device(images, metas, read, draw)
         t0 = time.time()
         images = images.to(opt.device)
         first = self.pre_images is None

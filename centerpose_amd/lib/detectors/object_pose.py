@@ -1,4 +1,6 @@
-"""``ObjectPoseDetector`` (detectors/object_pose.py:126-197) and ``soft_nms_nvidia`` (:27-124)."""
+"""``ObjectPoseDetector`` (detectors/object_pose.py:126-197, the result pictures of :281-414) and ``soft_nms_nvidia`` (:27-124)."""
+import json
+import os
 import time
 
 import numpy as np
@@ -151,13 +153,25 @@ class ObjectPoseDetector(BaseDetector):
             self.pnp_dev = _hip.pnp_from_post(rec, cnt, torch.from_numpy(cams).to(rec.device), self.opt.rep_mode)
         return rec, cnt, self.pnp_dev
 
-    def post_process_merge_device(self, metas):
+    def draw_device(self, frames, metas, rec, cnt, pnp):
+        """The records of ``post_pnp_device`` drawn into the device uint8 ``frames`` [B,H,W,3] (original image size): two
+        launches for the list, two for the pixels, on the current stream, nothing read back."""
+        from centerpose_amd import hip as _hip
+
+        params = _hip.draw.draw_params(self.opt, width=frames.shape[2], height=frames.shape[1])
+        prims = _hip.draw.draw_detections(rec, cnt, pnp, _hip.draw.cam_rows(metas), params)
+        return _hip.draw.draw_primitives(frames, prims)
+
+    def post_process_merge_device(self, metas, draw=None):
         """post_process + merge_outputs of every image of the last ``process`` call in one device launch
-        (cp_postprocess); returns a list of per-image numpy arrays of detection dicts like ``merge_outputs``."""
+        (cp_postprocess); returns a list of per-image numpy arrays of detection dicts like ``merge_outputs``.  ``draw``:
+        device frames the records are drawn into (``draw_device``) before the copy to the host."""
         from centerpose_amd import hip as _hip
 
         B = len(metas)
-        rec, cnt, _ = self.post_pnp_device(metas)
+        rec, cnt, pnp = self.post_pnp_device(metas)
+        if draw is not None:
+            self.draw_device(draw, metas, rec, cnt, pnp)
         rec = rec.cpu().numpy()
         cnt = cnt.cpu().numpy()
         f32_fields = ('obj_scale', 'obj_scale_uncertainty', 'kps_displacement_std', 'tracking', 'tracking_hp',
@@ -183,5 +197,86 @@ class ObjectPoseDetector(BaseDetector):
             out.append(np.array(items))
         return out
 
+    def _draw_box_and_cuboid(self, debugger, bbox, paper=False):
+        """What save_results draws per record inside `if opt.reg_bbox` (object_pose.py:361-379)."""
+        o = self.opt
+        if not paper:
+            if o.tracking_task == True:  # noqa: E712
+                debugger.add_coco_bbox(bbox['bbox'], 0, bbox['score'], id=bbox['tracking_id'], img_id='out_img_pred')
+            else:
+                debugger.add_coco_bbox(bbox['bbox'], 0, bbox['score'], img_id='out_img_pred')
+        if 'projected_cuboid' in bbox:
+            debugger.add_coco_hp(bbox['projected_cuboid'], img_id='out_img_pred', pred_flag='pnp', PAPER_DISPLAY=bool(paper))
+            if o.show_axes == True or o.paper_display == True:  # noqa: E712
+                key = 'kps_3d_cam_kf' if o.tracking_task == True else 'kps_3d_cam'  # noqa: E712
+                debugger.add_axes(bbox[key], o.cam_intrinsic, img_id='out_img_pred')
+
     def show_results(self, debugger, image, results):
-        print('[centerpose_hip] %d detection(s) (drawing is not part of this library)' % len(results))
+        """object_pose.py:281-317.  There is no window to show: the picture stays in ``debugger`` (``render``)."""
+        o = self.opt
+        debugger.add_img(image, img_id='out_img_pred')
+        for bbox in results:
+            if bbox['score'] > o.vis_thresh:
+                if o.tracking_task == True:  # noqa: E712
+                    if 'kps_pnp_kf' in bbox:
+                        kps_disp = np.array(bbox['kps_pnp_kf'], np.float64).copy()
+                        kps_disp[:, 0] = kps_disp[:, 0] * image.shape[1]
+                        kps_disp[:, 1] = kps_disp[:, 1] * image.shape[0]
+                        debugger.add_coco_hp(kps_disp[1:].reshape(-1), img_id='out_img_pred')
+                        debugger.add_coco_bbox(bbox['bbox'], 0, bbox['score'], id=bbox['tracking_id'], img_id='out_img_pred')
+                else:
+                    if o.reg_bbox:
+                        debugger.add_coco_bbox(bbox['bbox'], 0, bbox['score'], img_id='out_img_pred')
+                    if 'projected_cuboid' in bbox:
+                        debugger.add_coco_hp(bbox['projected_cuboid'], img_id='out_img_pred', pred_flag='pnp')
+                    else:
+                        debugger.add_coco_hp(bbox['kps'], img_id='out_img_pred')
+                if o.obj_scale == True:  # noqa: E712
+                    if o.reg_bbox:
+                        debugger.add_obj_scale(bbox['bbox'], bbox['obj_scale'], img_id='out_img_pred')
+                        if o.show_axes == True:  # noqa: E712
+                            key = 'kps_3d_cam_kf' if o.tracking_task == True else 'kps_3d_cam'  # noqa: E712
+                            if key in bbox:
+                                debugger.add_axes(bbox[key], o.cam_intrinsic, img_id='out_img_pred')
+                    else:
+                        debugger.add_obj_scale([20, 20, 0, 0], bbox['obj_scale'], img_id='out_img_pred')
+        print('[centerpose_hip] %d detection(s)' % len(results))
+        debugger.show_all_imgs(pause=getattr(self, 'pause', False))
+
+    def save_results(self, debugger, image, results, image_or_path_or_tensor, dict_out=None):
+        """object_pose.py:357-414: `<demo_save>/<name>/<file>_out_img_pred.png` beside the JSON."""
+        o = self.opt
+        debugger.add_img(image, img_id='out_img_pred')
+        for bbox in results:
+            if bbox['score'] > o.vis_thresh:
+                if o.reg_bbox:
+                    self._draw_box_and_cuboid(debugger, bbox, paper=o.paper_display)
+                if not o.paper_display:
+                    if o.obj_scale == True:  # noqa: E712
+                        obj_scale = bbox['obj_scale_kf'] if o.scale_pool == True else bbox['obj_scale']  # noqa: E712
+                        debugger.add_obj_scale(bbox['bbox'] if o.reg_bbox else [20, 20, 0, 0], obj_scale, img_id='out_img_pred')
+        BaseDetector.save_results(self, debugger, image, results, image_or_path_or_tensor, dict_out)  # the folder, the JSON
+        if isinstance(image_or_path_or_tensor, str):
+            debugger.save_all_imgs_demo(image_or_path_or_tensor, path=self._demo_target())
+
+    def save_results_eval(self, debugger, image, results, image_or_path_or_tensor, dict_out=None, video_layout=False):
+        """object_pose.py:319-355 (the hard-coded `demo/<model name>/` layout of the evaluation scripts)."""
+        o = self.opt
+        debugger.add_img(image, img_id='out_img_pred')
+        for bbox in results:
+            if bbox['score'] > o.vis_thresh and o.reg_bbox:
+                debugger.add_coco_bbox(bbox['bbox'], 0, bbox['score'], img_id='out_img_pred')
+                if 'projected_cuboid' in bbox:
+                    debugger.add_coco_hp(bbox['projected_cuboid'], img_id='out_img_pred', pred_flag='pnp')
+        if o.tracking_task or getattr(o, 'eval_max_num', None) == 100:
+            video_layout = True
+        root = os.path.join('demo/', os.path.splitext(os.path.basename(o.load_model))[0])
+        file_id_name = image_or_path_or_tensor[image_or_path_or_tensor.rfind('_') + 1:]
+        folder_name = image_or_path_or_tensor[:image_or_path_or_tensor.rfind('_')]
+        target = os.path.join(root, folder_name) if video_layout else root
+        os.makedirs(target, exist_ok=True)
+        debugger.save_all_imgs_eval(image_or_path_or_tensor, path=target, video_layout=video_layout)
+        if dict_out is not None:
+            name = file_id_name if video_layout else '%s_%s' % (folder_name, file_id_name)
+            with open(os.path.join(target, name + '.json'), 'w') as fp:
+                json.dump(dict_out, fp)

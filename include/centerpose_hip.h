@@ -52,7 +52,8 @@ typedef struct cp_model cp_model;
  *     cp_pose_targets_track_det_workspace_bytes, cp_pose_targets_track_det;
  *     cp_adam_table_bytes, cp_adam_table_build, cp_adam_state_bytes, cp_adam_workspace_bytes, cp_adam_step;
  *     cp_grad_flat_elems, cp_grad_flat_offsets, cp_grad_pack_table_bytes, cp_grad_pack_table_build, cp_grad_pack;
- *     cp_dcnv2_backward_prec_workspace_bytes, cp_dcnv2_backward_prec, cp_dcnv2_backward_prec_mask. */
+ *     cp_dcnv2_backward_prec_workspace_bytes, cp_dcnv2_backward_prec, cp_dcnv2_backward_prec_mask;
+ *     cp_draw_workspace_bytes, cp_draw_primitives, cp_draw_detections, cp_draw_tracks. */
 #define CP_ABI_VERSION 7
 const char* cp_version(void);
 int cp_abi_version(void);
@@ -1489,6 +1490,79 @@ int cp_grad_pack_table_build(void* table, size_t table_bytes, int n_tensors, con
                              const int64_t* offsets, int* n_chunks);
 int cp_grad_pack(cp_stream_t stream, const void* table, int n_tensors, int n_chunks, float* flat, int64_t flat_elems,
                  float scale);
+
+/* ------------------------------------------------------------------------------------------
+ * Overlay: the detections drawn into the 8-bit frames on the device -- what the reference's `out_img_pred` shows
+ *   (detectors/object_pose.py:357-392 `save_results` through utils/debugger.py:131-162 `add_coco_bbox`, :214-296
+ *   `add_coco_hp`, :299-320 `add_axes`), without a read-back of the records.  Added without an ABI change (new entry points).
+ *
+ * A primitive is 8 x int32: kind, x0, y0, x1, y1, size, colour (B | G << 8 | R << 16), aux.  Pixel Q is covered by
+ *   CP_DRAW_SEGMENT  size = thickness t in 1..16: 4 dist^2(Q, segment P0P1) <= t^2, in exact integers (a capsule)
+ *   CP_DRAW_DISC     size = radius r in 0..64: |Q - P0|^2 <= r^2
+ *   CP_DRAW_RECT     size = thickness t: the union of the four segments between (x0,y0) (x1,y0) (x1,y1) (x0,y1)
+ *   CP_DRAW_FILL     the rectangle with both corners inclusive, corners in any order
+ *   CP_DRAW_GLYPH    aux = ASCII code, (x0, y0) = top-left of the cell, size = integer scale s in 1..8: each set bit of the
+ *                    library's own 5 x 7 font is an s x s block (cell pitch 6 s); the digits, ' ', '.', ':', '/', '-' and the
+ *                    letters of "op", "ID:", "Pred:", "Frame", "GT", "PnP" exist, any other code draws nothing
+ *   kind 0 or unknown: nothing.
+ * Coordinates lie in [CP_DRAW_COORD_MIN, CP_DRAW_COORD_MAX]; a primitive with a coordinate or a size outside its range is
+ * skipped whole, never clamped (csrc/draw_common.h states the rule and its int64 bounds; cv2's rasteriser is not reproduced:
+ * no anti-aliasing, not its thick-line polygons, not its Hershey font).
+ * Painter's order: a pixel takes the colour of the highest-indexed primitive of its image that covers it.  Pixels no
+ * primitive covers, and the pad bytes of a pitched row, are not written.
+ *
+ * cp_draw_primitives: frames DEVICE uint8 [B, H, pitch_bytes] (rows of W BGR pixels), drawn in place; prims DEVICE int32
+ *   [B, P, 8], P slots per image, unused slots kind 0 (the capacity is known to the host, the occupancy is not: device-built
+ *   lists need no read-back).  Two launches on `stream` (per-image compaction of the slots that draw, then one workgroup per
+ *   64 x 16 pixel tile), no allocation, no synchronisation, no atomics: deterministic and capturable.
+ *   workspace: cp_draw_workspace_bytes(B, P) bytes (0: B or P refused), 16-byte aligned.
+ *   Refused with CP_ERR_INVALID before any device work: NULL pointers, B < 1, P outside 1..CP_DRAW_MAX_P, H or W outside
+ *   1..CP_DRAW_MAX_DIM, pitch_bytes < 3 W, a workspace below the query or not 16-byte aligned.
+ *
+ * cp_draw_detections / cp_draw_tracks: the list builders, one thread per record.  Record (b, k) owns the CP_DRAW_SLOTS
+ *   slots [k CP_DRAW_SLOTS, (k + 1) CP_DRAW_SLOTS) of image b in prims [B, K CP_DRAW_SLOTS, 8] (K = cap for the tracks) and
+ *   leaves all-zero slots where it draws nothing: slot CP_DRAW_SLOT_BOX the box, CP_DRAW_SLOT_LABEL the label's rectangle and
+ *   its CP_DRAW_LABEL_CHARS glyphs ("ID:<n>"; the score and `Pred:` lines need Python's decimal formatting and are drawn by
+ *   the host path only), CP_DRAW_SLOT_DISCS the 8 vertices, CP_DRAW_SLOT_EDGES the 12 edges, CP_DRAW_SLOT_CROSS the crosses
+ *   (front, top, top, front, top, top: the reference's nested loop as it runs), CP_DRAW_SLOT_AXES the 3 axes.
+ *   Only records with score > vis_thresh; float64 coordinates are truncated towards zero as np.int32 / int() do, and one that
+ *   is not finite or leaves the coordinate range withdraws its primitive; the box is clipped to [0, width] x [0, height].
+ *   cp_draw_detections: post / count from cp_postprocess, det_pnp from cp_pnp_from_post or NULL (no cuboids), cam DEVICE
+ *   float64 [B,4] (fx, fy, cx, cy) or NULL (no axes); the axes' camera-frame box is rebuilt from the solve as
+ *   `finish_detection` does (OpenCV frame with show_axes, the evaluation's otherwise).
+ *   cp_draw_tracks: `state` of cp_track_step; draws the tracks in this frame's `boxes` (flags bit 2) with projected_cuboid
+ *   (bit 0) and the axes of kps_3d_cam_kf (bit 1).
+ * cp_draw_params: HOST struct.  theme: 0 'black', 1 'white' (opt.debugger_theme); labels: draw "ID:<n>" (with tracking_task);
+ *   width, height: the frame size the boxes are clipped to.
+ * ------------------------------------------------------------------------------------------ */
+#define CP_DRAW_SEGMENT 1
+#define CP_DRAW_DISC 2
+#define CP_DRAW_RECT 3
+#define CP_DRAW_FILL 4
+#define CP_DRAW_GLYPH 5
+#define CP_DRAW_COORD_MIN (-8192)
+#define CP_DRAW_COORD_MAX 8191
+#define CP_DRAW_MAX_DIM 8192
+#define CP_DRAW_MAX_P 65536
+#define CP_DRAW_SLOTS 44
+#define CP_DRAW_SLOT_BOX 0
+#define CP_DRAW_SLOT_LABEL 1   /* the label's filled rectangle, then CP_DRAW_LABEL_CHARS glyphs */
+#define CP_DRAW_LABEL_CHARS 13 /* "ID:" + at most 10 digits */
+#define CP_DRAW_SLOT_DISCS 15  /* 8 vertices */
+#define CP_DRAW_SLOT_EDGES 23  /* 12 edges */
+#define CP_DRAW_SLOT_CROSS 35  /* front, top, top, front, top, top: the reference's nested loop as it runs */
+#define CP_DRAW_SLOT_AXES 41   /* y, z, x */
+typedef struct cp_draw_params {
+    double vis_thresh;
+    int reg_bbox, show_axes, paper_display, tracking_task, theme, labels, width, height;
+} cp_draw_params;
+size_t cp_draw_workspace_bytes(int B, int P);
+int cp_draw_primitives(cp_stream_t stream, unsigned char* frames_bhwc_bgr, int B, int H, int W, size_t pitch_bytes,
+                       const int* prims, int P, void* workspace, size_t workspace_bytes);
+int cp_draw_detections(cp_stream_t stream, const double* post, const int* count, const double* det_pnp, const double* cam, int B,
+                       int K, const cp_draw_params* params, int* prims);
+int cp_draw_tracks(cp_stream_t stream, const void* state, int B, int cap, const double* cam, const cp_draw_params* params,
+                   int* prims);
 
 #ifdef __cplusplus
 }
