@@ -436,3 +436,104 @@ def rendered_heads(batch, seed=DEFAULT_SEED, n_obj=(1, 10), img=512, hw=128, sig
     h["hm"] = np.maximum(h["hm"], np.abs(rng.randn(batch, 1, hw, hw) * noise).astype(f32).clip(0, 0.2))
     h["hm_hp"] = np.maximum(h["hm_hp"], np.abs(rng.randn(batch, 8, hw, hw) * noise).astype(f32).clip(0, 0.2))
     return {k: torch.from_numpy(v) for k, v in h.items()}, counts
+
+
+# ---- a training set in the reference's on-disk layout (lib.datasets.dataset_combined reads it) ----
+
+def _quat_matrix(q):
+    x, y, z, w = q
+    return [[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+            [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+            [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]]
+
+
+def dataset_annotations(rng, width, height, n_obj=2, category="chair", drift=None):
+    """One frame's annotation JSON as a dict, in the Objectron pre-processing's format: ``n_obj`` posed boxes and the
+    keys the packers read (projected_cuboid as 9 (x, y) pixel pairs, centre first; quaternion_xyzw, location,
+    keypoints_3d, scale relative to the height; 'symmetric' for the chair; 'name' and 'mug' for the tracking task) and
+    the camera (a 4x4 projection in the reference's viewport convention, x from the second row, and its intrinsics).
+    ``drift``: a list the poses are kept in between the frames of one video, so that the objects move a little from
+    frame to frame; None draws fresh poses."""
+    import numpy as np
+
+    f = 1.5
+    P = np.array([[f * 480 / height, 0, 0, 0], [0, f * 480 / width, 0, 0], [0, 0, -1.002, -0.2002], [0, 0, -1, 0]])
+    if drift is None:
+        drift = []
+    if not drift:
+        for k in range(n_obj):
+            q = rng.normal(size=4)
+            drift.append({"Z": -rng.uniform(2.0, 3.5), "px": (k + 0.5 + rng.uniform(-0.2, 0.2)) / n_obj * width,
+                          "py": rng.uniform(0.35, 0.65) * height, "q": q / np.linalg.norm(q), "dims": rng.uniform(0.15, 0.35, 3)})
+    objects = []
+    for k, o in enumerate(drift):
+        o["px"] += rng.uniform(-3, 3)
+        o["py"] += rng.uniform(-3, 3)
+        Z, dims, q = o["Z"], o["dims"], o["q"]
+        X = np.array([(2 * o["py"] / height - 1) * -Z / P[0, 0], (2 * o["px"] / width - 1) * -Z / P[1, 1], Z])
+        Rm = np.array(_quat_matrix(q))
+        corners = [X] + [X + Rm @ (np.array([sx, sy, sz]) * dims / 2) for sx in (-1, 1) for sy in (-1, 1) for sz in (-1, 1)]
+        cub = []
+        for c in corners:
+            p = P @ np.append(c, 1.0)
+            p = p[:3] / p[3]
+            cub.append([float((p[1] + 1) / 2 * width), float((p[0] + 1) / 2 * height)])
+        obj = {"projected_cuboid": cub, "quaternion_xyzw": [float(v) for v in q], "location": [float(v) for v in X],
+               "keypoints_3d": [[float(v) for v in c] for c in corners], "scale": [float(v) for v in dims / dims[1]],
+               "name": "obj_%d" % k, "mug": False}
+        if category == "chair":
+            obj["symmetric"] = "False"
+        objects.append(obj)
+    camera = {"camera_projection_matrix": P.tolist(), "width": width, "height": height,
+              "intrinsics": {"fx": float(P[1, 1] * width / 2), "fy": float(P[0, 0] * height / 2), "cx": width / 2.0,
+                             "cy": height / 2.0}}
+    return {"camera_data": camera, "objects": objects}
+
+
+def dataset_frame(rng, anns, width, height):
+    """A uint8 HWC RGB picture of one frame's annotations: faint noise, each box's projected outline filled with its own
+    colour and its eight corners marked, so that a network has something to learn from."""
+    import numpy as np
+    from PIL import Image, ImageDraw
+
+    img = Image.fromarray(rng.randint(96, 160, (height, width, 3)).astype(np.uint8), "RGB")
+    draw = ImageDraw.Draw(img)
+    for k, o in enumerate(anns["objects"]):
+        pts = np.asarray(o["projected_cuboid"])[1:]
+        x0, y0, x1, y1 = pts[:, 0].min(), pts[:, 1].min(), pts[:, 0].max(), pts[:, 1].max()
+        draw.rectangle([x0, y0, x1, y1], fill=(40 + 90 * (k % 3), 220 - 70 * (k % 3), 30 + 50 * k % 256))
+        for j, (x, y) in enumerate(pts):
+            draw.ellipse([x - 3, y - 3, x + 3, y + 3], fill=(255 - 30 * j, 30 * j, 255))
+    return np.asarray(img)
+
+
+def write_dataset(data_dir, n_frames, category="chair", splits=("train", "val"), tracking=False, size=(160, 120), n_videos=2,
+                  n_obj=2, seed=DEFAULT_SEED):
+    """Writes an ``n_frames``-frame training set under ``data_dir`` the way the Objectron pre-processing lays it out:
+    ``<data_dir>/outf/<category>_<split>/<video>/<frame>.png`` with ``<frame>.json`` beside it (``outf_all`` for the
+    tracking task), the frames spread over ``n_videos`` videos with consecutive five-digit frame ids.  PNG is lossless,
+    so every decoder returns the same bytes.  Every split gets the same number of frames from its own seed.  Returns the
+    directory of the first split."""
+    import numpy as np
+    from PIL import Image
+
+    width, height = size
+    root = os.path.join(data_dir, "outf_all" if tracking else "outf")
+    first = None
+    for s, split in enumerate(splits):
+        rng = np.random.RandomState((int(seed) + 7919 * s) % (2 ** 31))
+        split_dir = os.path.join(root, "%s_%s" % (category, split))
+        first = first or split_dir
+        per = [(n_frames + n_videos - 1 - v) // n_videos for v in range(n_videos)]
+        for v, count in enumerate(per):
+            if not count:
+                continue
+            video = os.path.join(split_dir, "video_%02d" % v)
+            os.makedirs(video, exist_ok=True)
+            drift = []
+            for i in range(count):
+                anns = dataset_annotations(rng, width, height, n_obj, category, drift)
+                Image.fromarray(dataset_frame(rng, anns, width, height), "RGB").save(os.path.join(video, "%05d.png" % i))
+                with open(os.path.join(video, "%05d.json" % i), "w") as fh:
+                    json.dump(anns, fh)
+    return first
